@@ -8,7 +8,12 @@ rank holds all 200 poses and its own 50k-point / 400k-measurement shard (weak sc
 reduced pose system is summed with RCCL once per trial.  value = N * K / time.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full --dump-outputs DIR
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run prints the headline alone; --full adds what takes runs of its own (set-up medians, the call after outlier
+removal, the per-stage roofline pass, the CPU baselines and parity, the recent window, the secondary configurations and
+the tracker lines).  --dump-outputs DIR writes what the timed run's caller receives after its last step as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -186,9 +191,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="metric")
-    ap.add_argument("--cpu-iters", type=int, default=8, help="LM iterations of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-tracker", action="store_true", help="skip the secondary Tracker line (BASELINE config c3) that is appended under `tracker_c3`")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: set-up medians, the call after outlier removal, the per-stage roofline pass, CPU baselines + parity, "
+                         "the recent window, the secondary configurations and the tracker lines (a plain run sets up, warms up, times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed run computed (rank 0: poses, points, outlier measurements, iteration log) "
+                         "as DIR/<name>.npy in float64")
+    ap.add_argument("--cpu-iters", type=int, default=8, help="with --full: LM iterations of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-stage timing pass")
+    ap.add_argument("--no-tracker", action="store_true", help="with --full: skip the secondary Tracker line (BASELINE config c3) that is appended under `tracker_c3`")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: every rank brings its own shard of the configuration's size (the headline); strong: ONE map of the configuration's "
                          "size is partitioned over the ranks (synth.partition: points by source MKF, measurement counts balanced) -- BASELINE c4 as stated")
@@ -260,7 +271,7 @@ def main():
     def fresh(profile=False):
         b = chain_bundle.ChainBundle(problem.cams, True, True, False, disable_convergence=True, device=local_rank, profile=profile)
         t0 = time.perf_counter()
-        problem.populate(b)
+        b.ids = problem.populate(b)
         t1 = time.perf_counter()
         if comm is not None:
             b.SetComm(comm)
@@ -291,7 +302,7 @@ def main():
     # (the first adjustment after a keyframe or points were added) -- and CACHED: the topology of the call before, which is what
     # MCPTAM's repeated adjustments of an unconverged map bring (src/MapMaker.cc run loop; include/mcp_ba.h structure cache).
     samples, cold = [], []
-    if world == 1 and args.warmup > 0:
+    if args.full and world == 1 and args.warmup > 0:
         for _ in range(4):
             chain_bundle.struct_cache_clear()
             fresh().close()
@@ -323,6 +334,16 @@ def main():
     tm_run = b.Timing()
     trials = sum(l["trials"] for l in logs)
     chi_first, chi_last = logs[0]["chi2_start"], logs[-1]["chi2_end"]
+    if args.dump_outputs and rank == 0:
+        # what the caller of Compute() reads back after the last timed step; the outlier set sorted, so that two builds compare row by row
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        R_out, t_out = b.GetPoses(b.ids["mkf"])
+        outliers = np.array(sorted(b.GetOutlierMeasurements()), dtype=np.float64).reshape(-1, 3)
+        log_keys = ("chi2_start", "chi2_end", "lambda_end", "sigma_sq", "rms_update", "trials", "accepted")
+        for name, arr in (("poses_R", R_out), ("poses_t", t_out), ("points", b.GetPoints(b.ids["point"])), ("outlier_measurements", outliers),
+                          ("iteration_log", [[l[k] for k in log_keys] for l in logs])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
     b.close()
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.debug_single_device else dev)
@@ -333,7 +354,7 @@ def main():
     # (MapMakerServerBase::HandleOutliers, src/MapMakerServerBase.cc:1198-1238), poses and points stay where it left them, and a fresh
     # ChainBundle adjusts again -- a topology the structure cache has NOT seen, but a subset of one it has (include/mcp_ba.h, near miss)
     after_removal = None
-    if world == 1 and args.warmup > 0:
+    if args.full and world == 1 and args.warmup > 0:
         try:
             import copy
             import numpy as _np
@@ -400,7 +421,7 @@ def main():
         if args.debug_single_device:
             result["config"]["debug"] = "all ranks share GPU 0, gloo transport: code-path check only, not a measurement"
     # per-stage HIP-event timing of the same run shape (separate pass so the events do not perturb `value`)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         bp = fresh(profile=True)
         bp.Compute(args.steps)
         tm = bp.Timing()
@@ -422,7 +443,7 @@ def main():
             result["stages"] = {"ms_total": stage_ms, "per_stage": {k: {kk: v[kk] for kk in ("bound", "achieved", "unit", "frac", "avg_ms", "launches", "traffic", "limited_by", "mfma_executed", "plan_basis") if kk in v} for k, v in roofs.items()}}
     # CPU baselines on this box's host cores, same map, same run; the oracle's iteration log doubles as the
     # parity check of the GPU run that was just timed
-    if rank == 0 and world == 1 and args.cpu_iters > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_iters > 0:
         build_note = native_oracle()
         from oracle import OracleBundle
 
@@ -493,7 +514,7 @@ def main():
     # secondary line: the call MCPTAM makes most -- BundleAdjustRecent (src/BundleAdjusterBase.cc:188-265): the newest MKF + its 3
     # neighbours free, every other MKF that sees their points fixed, 10 iterations; timed as WHOLE calls (fresh handle, bulk replay,
     # Prepare, Compute(10), read-back of poses and points), the way BundleAdjusterMulti::BundleAdjust runs it
-    if rank == 0 and world == 1 and args.config == "metric" and args.cpu_iters > 0:      # (--cpu-iters 0 = the profiling passes: headline workload only)
+    if args.full and rank == 0 and world == 1 and args.config == "metric" and args.cpu_iters > 0:      # (--cpu-iters 0 = the profiling passes: headline workload only)
         try:
             import numpy as np
             w = synth.recent_window(problem)
@@ -527,7 +548,7 @@ def main():
             result["recent_window"] = {"error": repr(exc)}
     # secondary lines: the other ChainBundle configurations of BASELINE.json on this one device -- c2, c4 as a whole map, and one rank's
     # eighth of c4 through the multi-rank machine (scripts/bench_secondary.py); the inputs of DESIGN.md 6's scaling model
-    if rank == 0 and world == 1 and args.config == "metric" and args.cpu_iters > 0:
+    if args.full and rank == 0 and world == 1 and args.config == "metric" and args.cpu_iters > 0:
         try:
             sys.path.insert(0, os.path.join(ROOT, "scripts"))
             import bench_secondary
@@ -540,7 +561,7 @@ def main():
         except Exception as exc:
             result["secondary"] = {"error": repr(exc)}
     # secondary line: the per-frame Tracker path (BASELINE config c3), GPU through the C ABI next to the scalar CPU port
-    if rank == 0 and world == 1 and not args.no_tracker and args.cpu_iters > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_tracker and args.cpu_iters > 0:
         try:
             sys.path.insert(0, os.path.join(ROOT, "scripts"))
             import bench_tracker

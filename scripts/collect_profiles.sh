@@ -5,7 +5,6 @@ ROUND=${ROUND:-r06}
 cd "$(dirname "$0")/.."
 mkdir -p profiles/$ROUND
 cp gpurun_out/traffic.json profiles/$ROUND/pmc_traffic_per_launch.json
-cp gpurun_out/final_bench.json profiles/$ROUND/final_bench.json
 f=$(ls -t gpurun_out/prof_final/*/*kernel_stats.csv | head -1); cp "$f" profiles/$ROUND/final_bench_kernel_stats.csv
 cp gpurun_out/final_tests.log profiles/$ROUND/final_gpu_tests.log
 ls -la profiles/$ROUND

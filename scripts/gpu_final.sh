@@ -19,7 +19,9 @@ rm -rf $R/gpurun_out/prof_final
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_final -- python $R/bench.py --steps 20 --warmup 3 --cpu-iters 0 --no-roofline > $R/gpurun_out/prof_final.log 2>&1
 echo "stats rc=$?"; tail -1 $R/gpurun_out/prof_final.log | cut -c1-300
 cd $R
-timeout -k 10 500 python bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err; echo "bench rc=$?"; cut -c1-900 gpurun_out/final_bench.json; tail -2 gpurun_out/final_bench.err
+# the whole bench line (--full: set-up medians, roofline, CPU baselines, secondary and tracker lines) goes straight to profiles/$ROUND/
+mkdir -p profiles/$ROUND
+timeout -k 10 500 python bench.py --full 2>&1 > profiles/$ROUND/final_bench.json | tail -2; echo "bench rc=${PIPESTATUS[0]}"; cut -c1-900 profiles/$ROUND/final_bench.json
 bash $R/scripts/gpu_trk_prof.sh > gpurun_out/trk_prof_stdout.log 2>&1; tail -3 gpurun_out/trk_prof_stdout.log
 # kernel stats of the c5 tracker frame (eight 1280x960 cameras, 8000 points, one device)
 cd /tmp; rm -rf $R/gpurun_out/trk5_prof

@@ -10,8 +10,8 @@ for v in "$@"; do
   cp variants/lib_$v.so mcptam_amd/libmcptam_hip.so
   case $v in
     prof*) echo "== $v"; MCP_BA_SPECULATE=0 timeout 100 python scripts/gpu_quick.py metric 2>&1 | grep "prof\]" | sed -n 2,3p ;;
-    *) timeout 100 python bench.py --cpu-iters 0 2>/dev/null | show $v ;;
+    *) timeout 100 python bench.py --full --cpu-iters 0 2>/dev/null | show $v ;;
   esac
 done
 cp /tmp/lib_base.so mcptam_amd/libmcptam_hip.so
-timeout 100 python bench.py --cpu-iters 0 2>/dev/null | show base
+timeout 100 python bench.py --full --cpu-iters 0 2>/dev/null | show base

@@ -1320,6 +1320,33 @@ def test_bench_spawns_its_own_ranks(gpu_required):
     assert "5000 points, 40000 measurements per rank" in d["config"]["workload"]
 
 
+@pytest.mark.timeout(600)
+def test_bench_dumps_what_the_timed_run_computed(gpu_required, tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run, no --full): the result line carries the step count and the time of one step, and
+    DIR holds what a caller of the timed run reads back -- the same poses, points, outliers and iteration log as a ChainBundle that
+    runs the same seeded map for the same number of iterations here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from mcptam_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--config", "c2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=500, cwd=root)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-9 * d["value"]
+    assert "cpu_baseline" not in d and "roofline" not in d          # what takes runs of its own waits for --full
+    p = synth.make_config("c2")
+    ref = run_bundle(_gpu(p.cams, disable_convergence=True), p, 4)
+    got = {n: np.load(str(tmp_path / (n + ".npy"))) for n in ("poses_R", "poses_t", "points", "outlier_measurements", "iteration_log")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert rel_err(got["poses_R"], ref["R"]) < 1e-12 and rel_err(got["poses_t"], ref["t"]) < 1e-12 and rel_err(got["points"], ref["X"]) < 1e-12
+    assert np.array_equal(got["outlier_measurements"], np.array(sorted(ref["outliers"]), dtype=np.float64).reshape(-1, 3))
+    assert got["iteration_log"].shape == (4, 7)
+    assert np.array_equal(got["iteration_log"][:, 5:], [[l["trials"], l["accepted"]] for l in ref["logs"]])
+
+
 @pytest.mark.parametrize("shape", ["arc", "ring", "chains_that_couple", "ring_in_another_add_order"])
 def test_a_trajectory_band_is_factorised_as_two_chains(gpu_required, shape, monkeypatch):
     """A trajectory whose poses see only points of their neighbours -- an open arc, or a loop walked once -- has a banded (cyclic-banded)
