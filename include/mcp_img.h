@@ -284,6 +284,53 @@ int mcp_track_frame(int ncam, mcp_kf* const* targets, const uint8_t* const* imgs
  * without points, NULL + mcp_last_error() for a camera index the last frame did not have. */
 const mcp_td_out* mcp_track_frame_view(const mcp_kf* first_target, int cam, int* count);
 
+/* ---- Tracker::FindPVS over a device-resident map --------------------------------------- src/Tracker.cc:662-723, 950-961
+ * A map-point table lives on one device: per row (= point index, in the caller's order) the MapPoint fields FindPVS reads --
+ * mv3WorldPos, mv3PixelRight_W, mv3PixelDown_W -- and `usable` (0 = mbBad || !mbOptimized, Tracker.cc:680).  Rows that were never
+ * written (a gap left by an upload past the end) are unusable.  Uploads are enqueued on the table's stream: a PVS call that follows
+ * sees them, whole; the caller's arrays may be reused as soon as an upload returns. */
+typedef struct mcp_map_points mcp_map_points;
+mcp_map_points* mcp_map_points_create(int device /* HIP device ordinal, -1 = current */);
+void mcp_map_points_destroy(mcp_map_points*);
+int  mcp_map_points_rows(const mcp_map_points*);
+/* rows first .. first+count-1 from SoA arrays (world_pos / pixel_right_w / pixel_down_w: count x 3, usable: count); the table grows
+ * when first + count passes its size */
+int  mcp_map_points_set(mcp_map_points*, int first, int count, const double* world_pos, const double* pixel_right_w,
+                        const double* pixel_down_w, const uint8_t* usable);
+/* the table's size becomes `rows`: rows past it are dropped (they reach no later PVS; should the table grow again they come back
+ * unusable, as zero rows); a larger size appends unusable rows.  A caller that re-uploads the whole map every frame calls this with the
+ * map's current size first, so that points the map has since dropped leave the table. */
+int  mcp_map_points_resize(mcp_map_points*, int rows);
+/* rows ids[0..count-1] (distinct; an id past the size grows the table) -- the points the map maker moved, flagged or added */
+int  mcp_map_points_update(mcp_map_points*, int count, const int* ids, const double* world_pos, const double* pixel_right_w,
+                           const double* pixel_down_w, const uint8_t* usable);
+
+/* One PVS entry: what FindPVS leaves in the TrackerData and its PatchFinder (TrackerData::mv2Image, mm2CamDerivs, PatchFinder::
+ * mnSearchLevel, mm2WarpInverse) -- bit-identical to mcp_track_search's image / cam_derivs / search_level / warp_inverse. */
+typedef struct mcp_pvs_entry {
+  int    point;                 /* table row                                 */
+  int    level;                 /* search level 0..MCP_LEVELS-1              */
+  double image[2];
+  double cam_derivs[4];         /* row-major                                 */
+  double warp_inverse[4];       /* row-major                                 */
+} mcp_pvs_entry;
+
+/* FindPVS of every camera of a frame in one call (two launches on the table's stream, one wait).  CamFromWorld = cam_from_base[c] *
+ * base_from_world, (R row-major 9, t 3).  A row enters camera c's PVS when it is usable, its projection is valid and inside
+ * [0, image_size] (inclusive), the level-0 mask of targets[c] -- if it has one -- is not 0 at ((int)u, (int)v), and the search level is
+ * not -1.  One deviation: with a mask, a projection on u == w or v == h is dropped (the reference reads past the mask there).
+ * Order: ascending row within each (camera, level) -- the reference random_shuffles every level next (Tracker.cc:983), so a fixed
+ * order is as good and makes the result reproducible; the caller shuffles with its own RNG.
+ * out[c] (caps[c] entries) receives camera c's list level by level (level 0 first); counts[c*MCP_LEVELS + l] = entries of
+ * (c, l), always.  A camera whose PVS exceeds caps[c] gets nothing written; the call returns -1 and mcp_last_error() names it.
+ * out == NULL: nothing is copied, the lists stay in the library's pinned block -- mcp_track_find_pvs_view.  Every target must be on the
+ * table's device; their pyramids / masks are those of the last mcp_kf_* call. */
+int mcp_track_find_pvs(mcp_map_points*, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double base_from_world[12],
+                       const double* cam_from_base /* ncam x 12 */, const int* caps, mcp_pvs_entry* const* out, int* counts /* ncam x MCP_LEVELS */);
+/* zero-copy: the (cam, level) list of the last mcp_track_find_pvs on this table, valid until the next one; NULL + count 0 for an empty
+ * list, NULL + mcp_last_error() for a (cam, level) the last call did not produce */
+const mcp_pvs_entry* mcp_track_find_pvs_view(const mcp_map_points*, int cam, int level, int* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,67 @@ class KeyFrame {
   mcp_kf* mpDev = nullptr;
 };
 
+/// The map points Tracker::FindPVS reads (src/Tracker.cc:662-723), resident on one device: row = the caller's point index.
+class MapPointTable {
+ public:
+  explicit MapPointTable(int device = -1) {
+    mpDev = mcp_map_points_create(device);
+    if (!mpDev) throw std::runtime_error(std::string("MapPointTable: ") + mcp_last_error());
+  }
+  ~MapPointTable() { mcp_map_points_destroy(mpDev); }
+  MapPointTable(const MapPointTable&) = delete;
+  MapPointTable& operator=(const MapPointTable&) = delete;
+
+  int Rows() const { return mcp_map_points_rows(mpDev); }
+  /// rows first .. first+n-1 (SoA: 3 doubles per point in each vector; usable = !mbBad && mbOptimized)
+  void Set(int first, const std::vector<double>& vWorldPos, const std::vector<double>& vPixelRight, const std::vector<double>& vPixelDown,
+           const std::vector<uint8_t>& vUsable) {
+    const int n = (int)vUsable.size();
+    sizes(n, vWorldPos, vPixelRight, vPixelDown);
+    check(mcp_map_points_set(mpDev, first, n, vWorldPos.data(), vPixelRight.data(), vPixelDown.data(), vUsable.data()));
+  }
+  /// the size becomes nRows: rows past it are dropped (they come back unusable if the table grows again)
+  void Resize(int nRows) { check(mcp_map_points_resize(mpDev, nRows)); }
+  /// rows vIds (distinct) -- the points the map maker moved, flagged or added
+  void Update(const std::vector<int>& vIds, const std::vector<double>& vWorldPos, const std::vector<double>& vPixelRight,
+              const std::vector<double>& vPixelDown, const std::vector<uint8_t>& vUsable) {
+    const int n = (int)vIds.size();
+    if ((int)vUsable.size() != n) throw std::invalid_argument("MapPointTable::Update: array sizes");
+    sizes(n, vWorldPos, vPixelRight, vPixelDown);
+    check(mcp_map_points_update(mpDev, n, vIds.data(), vWorldPos.data(), vPixelRight.data(), vPixelDown.data(), vUsable.data()));
+  }
+  /// Tracker::FindPVS for every camera of a frame in one call: result[c][level] = that camera's entries of that level, rows ascending
+  /// (copied out of the library's block).  vCaps empty = the table's rows per camera.
+  std::vector<std::array<std::vector<mcp_pvs_entry>, MCP_LEVELS>> FindPVS(const std::vector<KeyFrame*>& vTargets, const std::vector<mcp_camera>& vCams,
+                                                                         const double base_from_world[12], const std::vector<double>& vCamFromBase,
+                                                                         std::vector<int> vCaps = {}) {
+    const int nc = (int)vTargets.size();
+    if ((int)vCams.size() != nc || (int)vCamFromBase.size() != 12*nc) throw std::invalid_argument("MapPointTable::FindPVS: array sizes");
+    if (vCaps.empty()) vCaps.assign(nc, Rows());
+    std::vector<mcp_kf*> h(nc);
+    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    std::vector<int> counts(nc*MCP_LEVELS);
+    check(mcp_track_find_pvs(mpDev, nc, h.data(), vCams.data(), base_from_world, vCamFromBase.data(), vCaps.data(), nullptr, counts.data()));
+    std::vector<std::array<std::vector<mcp_pvs_entry>, MCP_LEVELS>> out(nc);
+    for (int c = 0; c < nc; ++c)
+      for (int l = 0; l < MCP_LEVELS; ++l) {
+        int n = 0;
+        const mcp_pvs_entry* e = mcp_track_find_pvs_view(mpDev, c, l, &n);
+        if (n != counts[c*MCP_LEVELS + l]) throw std::runtime_error(mcp_last_error());
+        out[c][l].assign(e, e + n);
+      }
+    return out;
+  }
+  mcp_map_points* Handle() const { return mpDev; }
+
+ private:
+  static void check(int rc) { if (rc < 0) throw std::runtime_error(mcp_last_error()); }
+  static void sizes(int n, const std::vector<double>& a, const std::vector<double>& b, const std::vector<double>& c) {
+    if ((int)a.size() != 3*n || (int)b.size() != 3*n || (int)c.size() != 3*n) throw std::invalid_argument("MapPointTable: array sizes");
+  }
+  mcp_map_points* mpDev = nullptr;
+};
+
 /// Tracker::CalcPoseUpdate (src/Tracker.cc:1386-1512): mu, Tukey sigma^2; weights (0 = outlier) if asked for
 inline std::pair<std::array<double, 6>, double> CalcPoseUpdate(const std::vector<uint8_t>& vFound, const std::vector<double>& vFoundPos /*2n*/,
                                                                const std::vector<double>& vImagePos /*2n*/, const std::vector<double>& vSqrtInvNoise /*n*/,

@@ -1,5 +1,5 @@
 // img_api.hip -- C ABI of the KeyFrame / Tracker image path (include/mcp_img.h); host side only
-// marshals buffers and launches the kernels of img_kernels.h.  No CPU fallback.
+// marshals buffers and launches the kernels of img_kernels.h and pvs_kernels.h.  No CPU fallback.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -14,6 +14,7 @@
 
 #include "../../include/mcp_img.h"
 #include "img_kernels.h"
+#include "pvs_kernels.h"
 #include "ba_select.h"
 
 using namespace mcp;
@@ -1077,6 +1078,183 @@ int mcp_track_pose_update_m(int n, const uint8_t* found, const double* fpos, con
   if (wout) ICK(hipMemcpy(wout, dw.p, 8*(size_t)n, hipMemcpyDeviceToHost));
   if (sigma_out) ICK(hipMemcpy(sigma_out, dsig.p, 8, hipMemcpyDeviceToHost));
   return 0;
+}
+
+}  // extern "C"
+
+// ---- Tracker::FindPVS over a device-resident map-point table (include/mcp_img.h, pvs_kernels.h) ------------------------------------
+struct mcp_map_points {
+  int device = 0; hipStream_t st = nullptr;
+  int rows = 0;
+  Buf<PvsPoint> pts;                                 // capacity = pts.n
+  // uploads: staged in pinned memory, copied (and scattered) on st; `staged` marks when the staging may be refilled
+  PinBuf<PvsPoint> h_recs; PinBuf<int> h_ids; Buf<PvsPoint> d_recs; Buf<int> d_ids;
+  hipEvent_t staged = nullptr; bool stage_busy = false;
+  std::vector<int> sorted_ids;                       // duplicate check of mcp_map_points_update
+  // FindPVS: the camera table (uploaded when it changes), the passes' scratch, the pinned result block
+  PinBuf<PvsCam> h_tab; Buf<PvsCam> d_tab; std::vector<PvsCam> tab_last;
+  Buf<signed char> lvl; Buf<mcp_pvs_entry> ent; Buf<int> blk_cnt;
+  PinBuf<mcp_pvs_entry> h_out; PinBuf<int> h_counts;
+  int view_ncam = 0; int view_first[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; int view_count[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; bool view_ok[MCP_MAX_FRAME_CAMS] = {};
+  ~mcp_map_points() { if (st) (void)hipStreamSynchronize(st); if (st) (void)hipStreamDestroy(st); if (staged) (void)hipEventDestroy(staged); }
+  int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
+  // rows [rows, new_rows) become unusable zero rows; the contents so far move to a larger block when the capacity is passed
+  int grow(int new_rows) {
+    if (new_rows <= rows) return 0;
+    if ((size_t)new_rows > pts.n || !pts.p) {
+      Buf<PvsPoint> bigger;
+      if (bigger.alloc(std::max<size_t>({(size_t)new_rows, 2*pts.n, (size_t)1024}))) return -1;
+      if (rows) ICK(hipMemcpyAsync(bigger.p, pts.p, sizeof(PvsPoint)*(size_t)rows, hipMemcpyDeviceToDevice, st));
+      ICK(hipStreamSynchronize(st));                 // the old block is freed below, with nothing in flight on it
+      stage_busy = false;
+      pts.swap(bigger);
+    }
+    ICK(hipMemsetAsync(pts.p + rows, 0, sizeof(PvsPoint)*(size_t)(new_rows - rows), st));
+    rows = new_rows;
+    return 0;
+  }
+};
+
+static void pvs_pack(PvsPoint& r, int k, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
+  std::memcpy(r.world_pos, wp + 3*(size_t)k, 24); std::memcpy(r.pixel_right_w, pr + 3*(size_t)k, 24); std::memcpy(r.pixel_down_w, pd + 3*(size_t)k, 24);
+  r.usable = us[k] ? 1 : 0; r.pad_ = 0;
+}
+
+extern "C" {
+
+mcp_map_points* mcp_map_points_create(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { mcp_set_error("mcp_map_points_create: no HIP device available (the HIP path has no CPU fallback)"); return nullptr; }
+  int dev = device; if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+  if (dev >= ndev || !gfx950(dev)) { mcp_set_error("mcp_map_points_create: device is not a gfx950 (MI355X)"); return nullptr; }
+  if (hipSetDevice(dev) != hipSuccess) { mcp_set_error("hipSetDevice failed"); return nullptr; }
+  mcp_map_points* m = new mcp_map_points(); m->device = dev;
+  if (hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->staged, hipEventDisableTiming) != hipSuccess) {
+    mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr;
+  }
+  return m;
+}
+void mcp_map_points_destroy(mcp_map_points* m) { if (m) { (void)hipSetDevice(m->device); delete m; } }
+int mcp_map_points_rows(const mcp_map_points* m) { if (!m) return img_fail("mcp_map_points_rows: NULL table"); return m->rows; }
+
+int mcp_map_points_resize(mcp_map_points* m, int rows) {
+  if (!m) return img_fail("mcp_map_points_resize: NULL table");
+  if (rows < 0) return img_fail("mcp_map_points_resize: bad arguments");
+  if (rows <= m->rows) { m->rows = rows; return 0; }       // the rows past the end are gone; growing again zeroes them (grow)
+  ICK(hipSetDevice(m->device));
+  return m->grow(rows);
+}
+
+int mcp_map_points_set(mcp_map_points* m, int first, int count, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
+  if (!m) return img_fail("mcp_map_points_set: NULL table");
+  if (first < 0 || count < 0 || (long long)first + count > 0x7fffffffLL || (count > 0 && (!wp || !pr || !pd || !us))) return img_fail("mcp_map_points_set: bad arguments");
+  if (count == 0) return 0;
+  ICK(hipSetDevice(m->device));
+  if (m->wait_staging()) return -1;
+  if (m->h_recs.alloc(count)) return -1;
+  for (int k = 0; k < count; ++k) pvs_pack(m->h_recs.p[k], k, wp, pr, pd, us);
+  if (m->grow(first + count)) return -1;
+  ICK(hipMemcpyAsync(m->pts.p + first, m->h_recs.p, sizeof(PvsPoint)*(size_t)count, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  return 0;
+}
+
+int mcp_map_points_update(mcp_map_points* m, int count, const int* ids, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
+  if (!m) return img_fail("mcp_map_points_update: NULL table");
+  if (count < 0 || (count > 0 && (!ids || !wp || !pr || !pd || !us))) return img_fail("mcp_map_points_update: bad arguments");
+  if (count == 0) return 0;
+  int top = m->rows;
+  for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail("mcp_map_points_update: bad row id"); top = std::max(top, ids[k] + 1); }
+  // distinct ids: checked on a sorted copy (host memory ~ count, whatever the ids' values)
+  m->sorted_ids.assign(ids, ids + count);
+  std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
+  for (int k = 1; k < count; ++k)
+    if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail("mcp_map_points_update: row " + std::to_string(m->sorted_ids[k]) + " appears twice");
+  ICK(hipSetDevice(m->device));
+  if (m->wait_staging()) return -1;
+  if (m->h_recs.alloc(count) || m->h_ids.alloc(count)) return -1;
+  if ((size_t)count > m->d_recs.n || (size_t)count > m->d_ids.n) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
+  if (m->d_recs.alloc(count) || m->d_ids.alloc(count)) return -1;
+  for (int k = 0; k < count; ++k) { pvs_pack(m->h_recs.p[k], k, wp, pr, pd, us); m->h_ids.p[k] = ids[k]; }
+  if (m->grow(top)) return -1;
+  ICK(hipMemcpyAsync(m->d_recs.p, m->h_recs.p, sizeof(PvsPoint)*(size_t)count, hipMemcpyHostToDevice, m->st));
+  ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+  hipLaunchKernelGGL(k_map_points_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->pts.p, count, (const int*)m->d_ids.p, (const PvsPoint*)m->d_recs.p);
+  ICK(hipGetLastError());
+  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  return 0;
+}
+
+int mcp_track_find_pvs(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb,
+                       const int* caps, mcp_pvs_entry* const* out, int* counts) {
+  if (!m) return img_fail("mcp_track_find_pvs: NULL table");
+  m->view_ncam = 0;
+  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !caps || !counts) return img_fail("mcp_track_find_pvs: bad arguments");
+  for (int c = 0; c < ncam; ++c) {
+    if (!targets[c] || !cam_ok(&cams[c]) || caps[c] < 0 || (out && !out[c])) return img_fail("mcp_track_find_pvs: bad arguments for camera " + std::to_string(c));
+    if (targets[c]->device != m->device)
+      return img_fail("mcp_track_find_pvs: camera " + std::to_string(c) + "'s target is on device " + std::to_string(targets[c]->device) + ", the table on device " + std::to_string(m->device));
+  }
+  for (int k = 0; k < ncam*MCP_LEVELS; ++k) counts[k] = 0;
+  ICK(hipSetDevice(m->device));
+  const int n = m->rows;
+  if (n == 0) {
+    for (int c = 0; c < ncam; ++c) { m->view_ok[c] = true; for (int l = 0; l < MCP_LEVELS; ++l) { m->view_first[c][l] = 0; m->view_count[c][l] = 0; } }
+    m->view_ncam = ncam;
+    return 0;
+  }
+  const int nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
+  std::vector<PvsCam> tab(ncam);
+  size_t room = 0;
+  for (int c = 0; c < ncam; ++c) {
+    PvsCam& C = tab[c];
+    std::memset(&C, 0, sizeof(PvsCam));              // (the table is compared byte-wise with the last one uploaded)
+    C.cam = cams[c]; std::memcpy(C.cfb.R, cfb + 12*c, 72); std::memcpy(C.cfb.t, cfb + 12*c + 9, 24);
+    const Level& L0 = targets[c]->lev[0];
+    C.mask0 = L0.has_mask ? L0.mask.p : nullptr; C.mask_w = L0.w; C.mask_h = L0.h;
+    C.cap = std::min(caps[c], n); C.out_first = (int)room;
+    room += (size_t)C.cap;
+  }
+  if (m->h_out.alloc(room) || m->h_counts.alloc((size_t)ncam*MCP_LEVELS) || m->lvl.alloc((size_t)ncam*n) || m->ent.alloc((size_t)ncam*n) ||
+      m->blk_cnt.alloc((size_t)ncam*nblk*MCP_LEVELS) || m->d_tab.alloc(MCP_MAX_FRAME_CAMS) || m->h_tab.alloc(MCP_MAX_FRAME_CAMS)) return -1;
+  // the cameras, their CamFromBase, masks and caps rarely change from frame to frame: their table is uploaded only when they do
+  if (m->tab_last.size() != tab.size() || std::memcmp(m->tab_last.data(), tab.data(), sizeof(PvsCam)*tab.size()) != 0) {
+    std::memcpy(m->h_tab.p, tab.data(), sizeof(PvsCam)*tab.size());
+    ICK(hipMemcpyAsync(m->d_tab.p, m->h_tab.p, sizeof(PvsCam)*tab.size(), hipMemcpyHostToDevice, m->st));
+    m->tab_last = tab;
+  }
+  Se3 B; std::memcpy(B.R, bfw, 72); std::memcpy(B.t, bfw + 9, 24);
+  hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)m->d_tab.p, B, (const PvsPoint*)m->pts.p, n, nblk, m->lvl.p, m->ent.p, m->blk_cnt.p);
+  hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)m->d_tab.p, n, nblk, (const signed char*)m->lvl.p,
+                     (const mcp_pvs_entry*)m->ent.p, (const int*)m->blk_cnt.p, m->h_out.p, m->h_counts.p);
+  const hipError_t le = hipGetLastError();
+  const hipError_t se = hipStreamSynchronize(m->st);
+  if (le != hipSuccess) { m->tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: launch: ") + hipGetErrorString(le)); }
+  if (se != hipSuccess) { m->tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: ") + hipGetErrorString(se)); }
+  m->stage_busy = false;
+  std::memcpy(counts, m->h_counts.p, sizeof(int)*(size_t)ncam*MCP_LEVELS);
+  std::string over;
+  for (int c = 0; c < ncam; ++c) {
+    int first = tab[c].out_first, all = 0;
+    for (int l = 0; l < MCP_LEVELS; ++l) { m->view_first[c][l] = first; m->view_count[c][l] = counts[c*MCP_LEVELS + l]; first += counts[c*MCP_LEVELS + l]; all += counts[c*MCP_LEVELS + l]; }
+    m->view_ok[c] = all <= caps[c];
+    if (!m->view_ok[c]) { if (over.empty()) over = "mcp_track_find_pvs: camera " + std::to_string(c) + "'s PVS has " + std::to_string(all) + " entries, its cap is " + std::to_string(caps[c]); continue; }
+    if (out && all) std::memcpy(out[c], m->h_out.p + tab[c].out_first, sizeof(mcp_pvs_entry)*(size_t)all);
+  }
+  m->view_ncam = ncam;
+  if (!over.empty()) return img_fail(over);
+  return 0;
+}
+
+const mcp_pvs_entry* mcp_track_find_pvs_view(const mcp_map_points* m, int cam, int level, int* count) {
+  if (count) *count = 0;
+  if (!m || cam < 0 || cam >= m->view_ncam || level < 0 || level >= MCP_LEVELS || !m->view_ok[cam]) {
+    img_fail("mcp_track_find_pvs_view: the last mcp_track_find_pvs on this table produced no list for that camera / level");
+    return nullptr;
+  }
+  const int k = m->view_count[cam][level];
+  if (count) *count = k;
+  return k > 0 ? m->h_out.p + m->view_first[cam][level] : nullptr;
 }
 
 }  // extern "C"

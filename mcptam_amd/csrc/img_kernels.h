@@ -619,6 +619,33 @@ __device__ __forceinline__ int pf_iterate(const uint8_t* __restrict__ limg, int 
   return conv;
 }
 
+// TrackerData::Project (include/mcptam/TrackerData.h:102-119) at CamFromWorld = CamFromBase * BaseFromWorld (Tracker::UpdateCamsFromWorld,
+// src/Tracker.cc:654-659): cfw, camera-frame point, projection with derivatives; returns mbInImage (inclusive bounds, `>` as there).
+// Shared by the per-point search (patch_item) and FindPVS (pvs_kernels.h): both see the same bits.
+__device__ __forceinline__ bool track_project(const mcp_camera& cam, const Se3& bfw, const Se3& cfb, const double* world_pos, Se3& cfw, double xc[3], Projection& pr) {
+  se3_compose(cfb, bfw, cfw);
+  se3_apply(cfw, world_pos, xc);
+  cam_project<true>(cam, xc, pr);
+  return !pr.invalid && !(pr.u < 0 || pr.v < 0 || pr.u > cam.image_size[0] || pr.v > cam.image_size[1]);
+}
+// GetDerivsUnsafe's sphere derivatives + PatchFinder::CalcSearchLevelAndWarpMatrix (src/PatchFinder.cc:69-122): the warp (WI = the
+// inverse warp's matrix, row-major) and the search level; *rejected = the reference returns -1 (determinant quartered while > 3 and
+// level < 3, then > 3, < 0.5 or not finite).  The returned level is the loop's even when rejected (the map maker's finders use it).
+__device__ __forceinline__ int track_warp_level(const Se3& cfw, const double xc[3], const Projection& pr, const double* pixel_right_w, const double* pixel_down_w,
+                                                double dT[3], double dP[3], double WI[4], bool* rejected) {
+  cam_sphere_deriv(xc, dT, dP);
+  double mr[3], md[3]; mat3_vec(cfw.R, pixel_right_w, mr); mat3_vec(cfw.R, pixel_down_w, md);
+  const double sr0 = dT[0]*mr[0] + dT[1]*mr[1] + dT[2]*mr[2], sr1 = dP[0]*mr[0] + dP[1]*mr[1] + dP[2]*mr[2];
+  const double sd0 = dT[0]*md[0] + dT[1]*md[1] + dT[2]*md[2], sd1 = dP[0]*md[0] + dP[1]*md[1] + dP[2]*md[2];
+  WI[0] = pr.D[0]*sr0 + pr.D[1]*sr1; WI[2] = pr.D[2]*sr0 + pr.D[3]*sr1;
+  WI[1] = pr.D[0]*sd0 + pr.D[1]*sd1; WI[3] = pr.D[2]*sd0 + pr.D[3]*sd1;
+  double dDet = WI[0]*WI[3] - WI[1]*WI[2];
+  int lv = 0;
+  while (dDet > 3 && lv < MCP_LEVELS - 1) { lv++; dDet *= 0.25; }
+  *rejected = (dDet > 3 || dDet < 0.5 || !isfinite(dDet));
+  return lv;
+}
+
 // one item of one finder, one wavefront (control flow is wave-uniform: every lane computes the geometry redundantly)
 __device__ __forceinline__ void patch_item(int mode, const DevKfView& T, const uint8_t* __restrict__ mask0, const mcp_camera& cam, const Se3& bfw, const Se3& cfb,
                                            const DevTdIn& P, int point_key, double start_x, double start_y, PfRegs& S, uint8_t* tmpl, uint8_t* jtmpl,
@@ -626,12 +653,11 @@ __device__ __forceinline__ void patch_item(int mode, const DevKfView& T, const u
                                            mcp_td_out* O2 = nullptr /* a second copy of the record (pinned host memory), or null */,
                                            mcp_pose_point* PP = nullptr /* the record the pose iterations read (what the loops of Tracker::TrackMap take from vTD after SearchForPoints, src/Tracker.cc:1040-1075: world position, found position, noise, projection + camera derivatives at the search pose, camera, found flag), or null */, int cam_index = 0) {
   const int MAXSSD = 8*8*250;
-  Se3 cfw; se3_compose(cfb, bfw, cfw);
-  double xc[3]; se3_apply(cfw, P.world_pos, xc);
-  Projection pr; cam_project<true>(cam, xc, pr);
+  Se3 cfw; double xc[3]; Projection pr;
+  const bool projected_in = track_project(cam, bfw, cfb, P.world_pos, cfw, xc, pr);
   bool go = true;
   if (mode == PF_TRACK || mode == PF_REFIND) {          // TrackerData.h:102-119; MapMakerServerBase.cc:941-953
-    go = !pr.invalid && !(pr.u < 0 || pr.v < 0 || pr.u > cam.image_size[0] || pr.v > cam.image_size[1]);
+    go = projected_in;
   } else if (mode == PF_EPI_COARSE) {                   // :757-765: Invalid(), in_image(CVD::ir(v2Image)), mask == 0
     go = !pr.invalid;
     if (go) { const int ix = (int)pr.u, iy = (int)pr.v; go = ix >= 0 && iy >= 0 && ix < T.w[0] && iy < T.h[0] && !(mask0 && mask0[(size_t)iy*T.w[0] + ix] == 0); }
@@ -643,7 +669,8 @@ __device__ __forceinline__ void patch_item(int mode, const DevKfView& T, const u
   for (int k = 0; k < 12; ++k) J[k] = 0;
   bool have_templ = false;
   if (go) {
-    double dT[3], dP[3]; cam_sphere_deriv(xc, dT, dP);
+    double dT[3], dP[3]; bool rejected;
+    const int lv = track_warp_level(cfw, xc, pr, P.pixel_right_w, P.pixel_down_w, dT, dP, WI, &rejected);
     double xb[3]; se3_apply(bfw, P.world_pos, xb);
 #pragma unroll
     for (int m = 0; m < 6; ++m) {
@@ -651,15 +678,6 @@ __device__ __forceinline__ void patch_item(int mode, const DevKfView& T, const u
       const double s0 = dT[0]*mc[0] + dT[1]*mc[1] + dT[2]*mc[2], s1 = dP[0]*mc[0] + dP[1]*mc[1] + dP[2]*mc[2];
       J[m] = pr.D[0]*s0 + pr.D[1]*s1; J[6 + m] = pr.D[2]*s0 + pr.D[3]*s1;
     }
-    double mr[3], md[3]; mat3_vec(cfw.R, P.pixel_right_w, mr); mat3_vec(cfw.R, P.pixel_down_w, md);
-    const double sr0 = dT[0]*mr[0] + dT[1]*mr[1] + dT[2]*mr[2], sr1 = dP[0]*mr[0] + dP[1]*mr[1] + dP[2]*mr[2];
-    const double sd0 = dT[0]*md[0] + dT[1]*md[1] + dT[2]*md[2], sd1 = dP[0]*md[0] + dP[1]*md[1] + dP[2]*md[2];
-    WI[0] = pr.D[0]*sr0 + pr.D[1]*sr1; WI[2] = pr.D[2]*sr0 + pr.D[3]*sr1;
-    WI[1] = pr.D[0]*sd0 + pr.D[1]*sd1; WI[3] = pr.D[2]*sd0 + pr.D[3]*sd1;
-    double dDet = WI[0]*WI[3] - WI[1]*WI[2];
-    int lv = 0;
-    while (dDet > 3 && lv < MCP_LEVELS - 1) { lv++; dDet *= 0.25; }
-    const bool rejected = (dDet > 3 || dDet < 0.5 || !isfinite(dDet));
     if (rejected) {
       S.bad = 1;                                        // PatchFinder.cc:116-117: the member is set before -1 is returned
       if (mode == PF_TRACK || mode == PF_EPI_COARSE) { template_bad = 1; go = false; }     // FindPVS drops the point; MapMakerServerBase.cc:769-770

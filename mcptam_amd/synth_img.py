@@ -117,3 +117,24 @@ def make_smooth_scene(seed=5, size=(640, 480)):
     rot = ndimage.rotate(out[0].astype(float), 3.0, reshape=False, order=1, mode="nearest")
     rot = ndimage.shift(rot, (6, -9), order=1, mode="nearest").astype(np.uint8)
     return out[0], rot, out[1]
+
+
+def points_soa(pts):
+    """The FindPVS fields of a list of map-point dicts as SoA arrays: world_pos, pixel_right_w, pixel_down_w (n x 3 each)."""
+    return (np.array([p["world_pos"] for p in pts], dtype=np.float64).reshape(-1, 3),
+            np.array([p["pixel_right_w"] for p in pts], dtype=np.float64).reshape(-1, 3),
+            np.array([p["pixel_down_w"] for p in pts], dtype=np.float64).reshape(-1, 3))
+
+
+def make_map_cloud(pts, n, seed=DEFAULT_SEED, spread=4.0):
+    """A whole map of n points grown from the scene's map points (FindPVS sees every point of the map): copies
+    moved sideways by up to +-spread metres (many leave a camera's view) with patch vectors scaled by 1/2 .. 8 (every search level,
+    some rejected warps).  Returns world_pos, pixel_right_w, pixel_down_w (n x 3) and usable (n, about 3 % unusable)."""
+    rng = np.random.default_rng([seed, 31])
+    wp, pr, pd = points_soa(pts)
+    src = rng.integers(0, len(wp), n)
+    shift = np.zeros((n, 3))
+    shift[:, :2] = rng.uniform(-spread, spread, (n, 2))
+    scale = 2.0 ** rng.uniform(-1.0, 3.0, n)
+    usable = (rng.random(n) >= 0.03).astype(np.uint8)
+    return wp[src] + shift, pr[src] * scale[:, None], pd[src] * scale[:, None], usable

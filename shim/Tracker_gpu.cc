@@ -1,8 +1,8 @@
-// Tracker_gpu.cc -- MI355X bodies of Tracker::SearchForPoints and Tracker::CalcPoseUpdate.
+// Tracker_gpu.cc -- MI355X bodies of Tracker::FindPVS, Tracker::SearchForPoints and Tracker::CalcPoseUpdate.
 //
-// Replace /root/reference/src/Tracker.cc:1297-1377 (SearchForPoints) and :1379-1512 (CalcPoseUpdate): delete those two member
-// functions there (or fence them with #ifndef MCPTAM_HIP) and add this file to the library's sources.  The tracker keeps all of its
-// control flow -- FindPVS, the level buckets, the 1000-patch budget, the shuffles, the coarse / fine stages, the motion model -- and
+// Replace /root/reference/src/Tracker.cc:662-723 (FindPVS), :1297-1377 (SearchForPoints) and :1379-1512 (CalcPoseUpdate): delete those
+// member functions there (or fence them with #ifndef MCPTAM_HIP) and add this file to the library's sources.  The tracker keeps all of its
+// control flow -- the level buckets, the 1000-patch budget, the shuffles, the coarse / fine stages, the motion model -- and
 // calls these two members exactly where it did (src/Tracker.cc:841-906, 1027-1075).  The per-point inner loops (TrackerData::Project /
 // CalcJacobian, PatchFinder::MakeTemplateCoarseCont / FindPatchCoarse / IterateSubPixToConvergence, the WLS accumulation) run as one
 // batched device call each.  Needs KeyFrame::mpDev (shim/KeyFrame_gpu.cc) and shim/CameraExport.h.
@@ -339,4 +339,121 @@ Vector<6> Tracker::TrackStageOnDevice(std::vector<TrackerDataPtrVector>& vIterat
     }
   }
   return makeVector(adMu[0], adMu[1], adMu[2], adMu[3], adMu[4], adMu[5]);
+}
+
+// ---- FindPVS over a device-resident map-point table (include/mcp_img.h, mcp_track_find_pvs) ------------------------------------------
+// Members this needs in class Tracker (include/mcptam/Tracker.h):
+//     mcp_map_points* mpMapTable;              // mcp_map_points_create(-1) in the constructor (the keyframes' device), destroyed in ~Tracker
+//     std::vector<MapPoint*> mvMapTableRows;   // table row -> MapPoint
+//     std::vector<mcp_pvs_entry> mvPvsOut;     // scratch of the call
+//     void UploadMapTable();                   // option (a) below
+// and in class PatchFinder (include/mcptam/PatchFinder.h) a setter for the two members CalcSearchLevelAndWarpMatrix leaves behind:
+//     void SetSearchLevelAndWarp(int nLevel, const TooN::Matrix<2>& m2WarpInverse) { mnSearchLevel = nLevel; mm2WarpInverse = m2WarpInverse; }
+//
+// Keeping the table current.  Two ways, both under mMap.mMutex (the lock FindPVS already takes, src/Tracker.cc:668):
+//  (a) UploadMapTable() below: every frame, before the first FindPVS, the table is cut to the map's current size (mcp_map_points_resize:
+//      the map shrinks whenever Map::MoveBadPointsToTrash erases points from mlpPoints, src/Map.cc:106-107, 158-159, and rows past the
+//      new size must not reach the PVS) and all points of the map go up again (mcp_map_points_set of one range, usable = !mbBad &&
+//      mbOptimized); mvMapTableRows is rebuilt.  Nothing else in the system changes; the cost is one pass over the map on the host plus
+//      80 B per point over PCIe (scripts/bench_pvs.py: table_full_upload_ms).
+//  (b) A slot per MapPoint (an int mnTableRow in class MapPoint, assigned when the point enters the map, never reused while it lives):
+//      BundleAdjusterMulti writes the new positions back (src/BundleAdjusterMulti.cc, where it copies the adjusted points into the map)
+//      -> mcp_map_points_update of those rows; MapMakerBase adds a point / refreshes its pixel vectors -> update of that row; a point
+//      marked mbBad or moved to the trash -> update with usable = 0 (its slot is recycled only after the trash is emptied).  Per frame
+//      nothing goes up that did not change (table_update_5pct_ms).  The updates are enqueued on the table's stream, so the FindPVS that
+//      follows sees them whole, whichever thread made them.
+// (a) is what is written out here; (b) replaces UploadMapTable() by those calls.
+void Tracker::UploadMapTable()
+{
+  // caller holds mMap.mMutex
+  mvMapTableRows.clear();
+  std::vector<double> vPos, vRight, vDown;
+  std::vector<uint8_t> vUsable;
+  for(MapPointPtrList::iterator point_it = mMap.mlpPoints.begin(); point_it != mMap.mlpPoints.end(); ++point_it)
+  {
+    MapPoint& point = *(*point_it);
+    mvMapTableRows.push_back(&point);
+    for(int k = 0; k < 3; ++k)
+    {
+      vPos.push_back(point.mv3WorldPos[k]);
+      vRight.push_back(point.mv3PixelRight_W[k]);
+      vDown.push_back(point.mv3PixelDown_W[k]);
+    }
+    vUsable.push_back((point.mbBad || !point.mbOptimized) ? 0 : 1);      // src/Tracker.cc:680
+  }
+  // rows = the map's size, also when the map has shrunk or is empty: every row of the table is then a row of mvMapTableRows
+  if(mcp_map_points_resize(mpMapTable, (int)vUsable.size()) != 0 ||
+     (!vUsable.empty() && mcp_map_points_set(mpMapTable, 0, (int)vUsable.size(), &vPos[0], &vRight[0], &vDown[0], &vUsable[0]) != 0))
+  {
+    ROS_FATAL_STREAM("Tracker::UploadMapTable: "<<mcp_last_error());
+    ros::shutdown();
+  }
+}
+
+// The reference body collects the nearest points (sbCollectAllPoints = true: all of them, :1785-1795), projects each, tests the mask,
+// takes the derivatives and asks the PatchFinder for the search level.  Here one device call does that for every row of the table; the
+// host only walks the PVS.  A TrackerData is created for PVS points only: one the reference would create for a point outside the PVS holds
+// a PatchFinder that has seen nothing and is only ever touched again by the next FindPVS, so creating it then changes nothing.
+// Drop-in: one camera per call, as TrackMap calls it (:950-961); INTEGRATION.md shows the one-call form for all cameras of the frame.
+void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
+{
+  TaylorCamera& camera = mmCameraModels[cameraName];
+  KeyFrame& kf = *(mpCurrentMKF->mmpKeyFrames[cameraName]);
+  ROS_ASSERT(kf.mpDev);
+
+  boost::mutex::scoped_lock lock(mMap.mMutex);
+  if(cameraName == mvCurrCamNames[0])
+    UploadMapTable();                 // option (a): once per frame, before the first camera
+
+  mcp_camera cam = mcptam_hip::CameraExport::Make(camera);
+  double adBaseFromWorld[12], adCamFromBase[12];
+  ToArray12(mpCurrentMKF->mse3BaseFromWorld, adBaseFromWorld);
+  ToArray12(kf.mse3CamFromBase, adCamFromBase);
+  int nCap = (int)mvMapTableRows.size();
+  mvPvsOut.resize(std::max(nCap, 1));
+  mcp_pvs_entry* pOut = &mvPvsOut[0];
+  int anCounts[MCP_LEVELS];
+  mcp_kf* pTarget = kf.mpDev;
+  if(mcp_track_find_pvs(mpMapTable, 1, &pTarget, &cam, adBaseFromWorld, adCamFromBase, &nCap, &pOut, anCounts) != 0)
+  {
+    ROS_FATAL_STREAM("Tracker::FindPVS: "<<mcp_last_error());
+    ros::shutdown();
+    return;
+  }
+
+  const SE3<>& se3CamFromWorld = kf.mse3CamFromWorld;      // = CamFromBase * BaseFromWorld (UpdateCamsFromWorld, :654-659)
+  int k = 0;
+  for(int l = 0; l < MCP_LEVELS; ++l)
+  {
+    for(int i = 0; i < anCounts[l]; ++i, ++k)
+    {
+      const mcp_pvs_entry& e = mvPvsOut[k];
+      ROS_ASSERT(e.point >= 0 && e.point < (int)mvMapTableRows.size());     // the table has exactly the rows UploadMapTable wrote
+      MapPoint& point = *mvMapTableRows[e.point];
+      if(!point.mmpTData.count(cameraName))
+        point.mmpTData[cameraName] = new TrackerData(&point, mmSizes[cameraName]);
+      boost::intrusive_ptr<TrackerData> pTData(point.mmpTData[cameraName]);
+
+      // what Project, GetDerivsUnsafe and CalcSearchLevelAndWarpMatrix leave behind (TrackerData.h:102-130, PatchFinder.cc:69-122)
+      pTData->mv3Cam = se3CamFromWorld * point.mv3WorldPos;
+      pTData->mbInImage = true;
+      pTData->mv2Image = makeVector(e.image[0], e.image[1]);
+      pTData->mm2CamDerivs(0, 0) = e.cam_derivs[0]; pTData->mm2CamDerivs(0, 1) = e.cam_derivs[1];
+      pTData->mm2CamDerivs(1, 0) = e.cam_derivs[2]; pTData->mm2CamDerivs(1, 1) = e.cam_derivs[3];
+      Matrix<2> m2WarpInverse;
+      m2WarpInverse(0, 0) = e.warp_inverse[0]; m2WarpInverse(0, 1) = e.warp_inverse[1];
+      m2WarpInverse(1, 0) = e.warp_inverse[2]; m2WarpInverse(1, 1) = e.warp_inverse[3];
+      pTData->mFinder.SetSearchLevelAndWarp(e.level, m2WarpInverse);
+      pTData->mnSearchLevel = e.level;
+
+      if(point.mnUsing > mmCameraModels.size())
+      {
+        ROS_FATAL_STREAM("Tracker: mnUsing greater than number of cameras, counting leak!: "<<point.mnUsing);
+        ROS_BREAK();
+      }
+      pTData->mbSearched = false;
+      pTData->mbFound = false;
+      vPVSLevels[l].push_back(pTData);      // rows ascending; TrackMap random_shuffles every level next (:983)
+    }
+  }
 }
