@@ -331,6 +331,73 @@ int mcp_track_find_pvs(mcp_map_points*, int ncam, mcp_kf* const* targets, const 
  * list, NULL + mcp_last_error() for a (cam, level) the last call did not produce */
 const mcp_pvs_entry* mcp_track_find_pvs_view(const mcp_map_points*, int cam, int level, int* count);
 
+/* ---- Tracker::TrackMap of a frame from the resident table ------------------------------------------ src/Tracker.cc:938-1075
+ * The shuffle of the reference (random_shuffle, :983 and :876-883) cannot be reproduced bit for bit; every layer uses this keyed one
+ * instead.  "Shuffled" means ascending (key, row); for a given (seed, stage, cam) the keys of distinct rows are distinct (mcp_mix64 is a
+ * bijection).  Stage 0 orders each PVS level, stage 1 the chop of the fine stage's budget. */
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MCP_HOST_DEVICE __host__ __device__      /* the library's kernels use these very definitions */
+#else
+#define MCP_HOST_DEVICE
+#endif
+static inline MCP_HOST_DEVICE uint64_t mcp_mix64(uint64_t z) { z += 0x9E3779B97F4A7C15ull; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                                               z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); }
+static inline MCP_HOST_DEVICE uint64_t mcp_track_shuffle_key(uint64_t seed, int stage, int cam, int row) {
+  return mcp_mix64(mcp_mix64(seed ^ ((uint64_t)stage << 40) ^ ((uint64_t)cam << 32)) ^ (uint32_t)row); }
+
+/* The patch source of each row (MapPoint::mpPatchSourceKF, mnSourceLevel, mirCenter (center_xy: count x 2), mbFixed) and its identity
+ * keys[k] (the point_key of that row's finders).  source_kf[k] == NULL: the row has no source.  The table keeps (handle, creation serial)
+ * and resolves it at every mcp_track_map through the library's registry of live keyframes: a row whose source has been destroyed is dropped
+ * from the selection (counted in mcp_track_map_result::stale), never dereferenced.  Sources must live on the table's device.  A row whose
+ * key changes gets finders that have seen nothing for every camera.  Enqueued on the table's stream like mcp_map_points_set. */
+int mcp_map_points_set_source(mcp_map_points*, int first, int count, const int* keys, mcp_kf* const* source_kf, const int* source_level,
+                              const int* center_xy, const uint8_t* fixed);
+int mcp_map_points_update_source(mcp_map_points*, int count, const int* ids, const int* keys, mcp_kf* const* source_kf, const int* source_level,
+                                 const int* center_xy, const uint8_t* fixed);
+/* The persistent finders (TrackerData::mFinder, one per (row, camera index of mcp_track_map)) of rows first .. first+count-1 for camera
+ * `cam`; a camera no call has used yet reads as zeroed states.  Waits for the table's stream. */
+int mcp_map_points_get_states(const mcp_map_points*, int cam, int first, int count, mcp_pf_state* out);
+
+typedef struct mcp_track_map_params {
+  int try_coarse, coarse_max, coarse_range, coarse_min, coarse_subpix_its;  /* after TrackMap's heuristics, doubling on recovery included (:990-1008) */
+  int max_patches;                                                        /* snMaxPatchesPerFrame                                          */
+  int estimator;                                                          /* MCP_MEST_*                                                    */
+  unsigned long long seed;                                                /* of mcp_track_shuffle_key                                      */
+} mcp_track_map_params;
+typedef struct mcp_track_map_result {
+  int did_coarse, coarse_found;                   /* coarse_found = sum of found && !template_bad over the coarse set; did_coarse = > coarse_min */
+  int pvs_counts[MCP_MAX_FRAME_CAMS][MCP_LEVELS]; /* this frame's PVS per (camera, level), stale-source rows included                  */
+  int set_sizes[MCP_MAX_FRAME_CAMS][3];           /* |C|, |T|, |R| per camera                                                          */
+  int stale[MCP_MAX_FRAME_CAMS];                  /* PVS entries dropped because the row's source keyframe is missing or destroyed      */
+  double mu_last[6];                              /* last update of the fine iterations                                                */
+} mcp_track_map_result;
+typedef struct mcp_track_map_item {
+  int point;                                      /* table row                                                                          */
+  int stage;                                      /* 0 = coarse set C, 1 = remaining top level T, 2 = budgeted rest R                    */
+  double weight_last;                             /* M-estimator weight of the last fine iteration (0 = outlier or not found)            */
+  mcp_td_out out;                                 /* the search's record (C: the coarse search's)                                       */
+} mcp_track_map_item;
+/* The whole TrackMap of a frame in one submission with one wait, from the table to the refined pose (base_from_world in / out):
+ *   imgs != NULL: mcp_kf_make_lite_batch(ncam, targets, imgs, strides, imgs_on_device, masks) first;
+ *   FindPVS (as mcp_track_find_pvs with caps = rows; mcp_track_find_pvs_view then returns this frame's lists);
+ *   per camera c, with P[l] = its PVS level l without stale-source rows, S_l = P[l] in stage-0 key order:
+ *     C = (try_coarse) the first min(|S_3|, coarse_max) of S_3, then the first min(|S_2|, coarse_max - |C|) of S_2, removed from them;
+ *     T = the rest of S_3; R0 = the rest of S_2, then S_1, then S_0; K = max(0, max_patches - |C| - |T|);
+ *     R = R0 if |R0| <= K, else the K entries of R0 with the smallest stage-1 keys, in that order;
+ *   coarse search of every C (MCP_PF_TRACK finders from the table, coarse_range, coarse_subpix_its, the prior pose);
+ *   did_coarse = coarse_found > coarse_min: then 10 iterations over the C records, all re-projecting, override {0 x 6, 1.0 x 4};
+ *   fine search of T (range did_coarse ? 5 : 10, 8 sub-pixel iterations) and R (same range, 0) at the current pose;
+ *   10 iterations over the camera-major records [C_c, T_c, R_c], re-projecting at 0, 4, 9, override {0 x 6, 16.0 x 4};
+ *   the searched finders' states back into the table.
+ * Results equal mcp_track_find_pvs + the selection above + mcp_patch_sequences + mcp_track_pose_refine_m composed on the host, bit for bit,
+ * with one deviation: more than 1024 records in one iteration stage run in the single-workgroup kernel (mcp_track_pose_refine_m's path with
+ * MCP_TRACK_REFINE_MULTI=0), since the record count is only known on the device.  Refusals (-1) happen before anything is enqueued. */
+int mcp_track_map(mcp_map_points*, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                  const uint8_t* const* const* masks, const mcp_camera* cams, double base_from_world[12], const double* cam_from_base /* ncam x 12 */,
+                  const mcp_track_map_params*, mcp_track_map_result* res);
+/* zero-copy: camera cam's items [C, T, R] of the last mcp_track_map on this table, in the library's pinned block; valid until the next call */
+const mcp_track_map_item* mcp_track_map_view(const mcp_map_points*, int cam, int* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,10 +213,60 @@ class MapPointTable {
       }
     return out;
   }
+  /// rows first .. first+n-1: the patch source of each MapPoint (mpPatchSourceKF, nullptr = none; mnSourceLevel; mirCenter as x, y pairs;
+  /// mbFixed) and its identity key (a changed key gives the row finders that have seen nothing)
+  void SetSource(int first, const std::vector<int>& vKeys, const std::vector<KeyFrame*>& vSources, const std::vector<int>& vLevels,
+                 const std::vector<int>& vCenters, const std::vector<uint8_t>& vFixed) {
+    std::vector<mcp_kf*> h = sources((int)vKeys.size(), vSources, vLevels, vCenters, vFixed);
+    check(mcp_map_points_set_source(mpDev, first, (int)vKeys.size(), vKeys.data(), h.data(), vLevels.data(), vCenters.data(), vFixed.data()));
+  }
+  void UpdateSource(const std::vector<int>& vIds, const std::vector<int>& vKeys, const std::vector<KeyFrame*>& vSources, const std::vector<int>& vLevels,
+                    const std::vector<int>& vCenters, const std::vector<uint8_t>& vFixed) {
+    if (vIds.size() != vKeys.size()) throw std::invalid_argument("MapPointTable::UpdateSource: array sizes");
+    std::vector<mcp_kf*> h = sources((int)vKeys.size(), vSources, vLevels, vCenters, vFixed);
+    check(mcp_map_points_update_source(mpDev, (int)vIds.size(), vIds.data(), vKeys.data(), h.data(), vLevels.data(), vCenters.data(), vFixed.data()));
+  }
+  /// the persistent finders of camera nCam for rows first .. first+n-1
+  std::vector<mcp_pf_state> States(int nCam, int first, int n) const {
+    std::vector<mcp_pf_state> out(n);
+    check(mcp_map_points_get_states(mpDev, nCam, first, n, out.data()));
+    return out;
+  }
+  /// Tracker::TrackMap of a frame in one call (mcp_track_map): vImages empty = the pyramids are current; base_from_world in / out.
+  /// Returns the items of every camera ([C, T, R], copied out of the library's block) and fills *pResult.
+  std::vector<std::vector<mcp_track_map_item>> TrackMap(const std::vector<KeyFrame*>& vTargets, const std::vector<const uint8_t*>& vImages,
+                                                        const std::vector<int>& vStrides, bool bImagesOnDevice, const std::vector<mcp_camera>& vCams,
+                                                        double base_from_world[12], const std::vector<double>& vCamFromBase,
+                                                        const mcp_track_map_params& params, mcp_track_map_result* pResult) {
+    const int nc = (int)vTargets.size();
+    if ((int)vCams.size() != nc || (int)vCamFromBase.size() != 12*nc || (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)))
+      throw std::invalid_argument("MapPointTable::TrackMap: array sizes");
+    std::vector<mcp_kf*> h(nc);
+    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    mcp_track_map_result r;
+    check(mcp_track_map(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
+                        nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r));
+    if (pResult) *pResult = r;
+    std::vector<std::vector<mcp_track_map_item>> out(nc);
+    for (int c = 0; c < nc; ++c) {
+      int n = 0;
+      const mcp_track_map_item* it = mcp_track_map_view(mpDev, c, &n);
+      out[c].assign(it, it + n);
+    }
+    return out;
+  }
   mcp_map_points* Handle() const { return mpDev; }
 
  private:
   static void check(int rc) { if (rc < 0) throw std::runtime_error(mcp_last_error()); }
+  static std::vector<mcp_kf*> sources(int n, const std::vector<KeyFrame*>& vSources, const std::vector<int>& vLevels, const std::vector<int>& vCenters,
+                                      const std::vector<uint8_t>& vFixed) {
+    if ((int)vSources.size() != n || (int)vLevels.size() != n || (int)vCenters.size() != 2*n || (int)vFixed.size() != n)
+      throw std::invalid_argument("MapPointTable: source array sizes");
+    std::vector<mcp_kf*> h(n);
+    for (int k = 0; k < n; ++k) h[k] = vSources[k] ? vSources[k]->handle() : nullptr;
+    return h;
+  }
   static void sizes(int n, const std::vector<double>& a, const std::vector<double>& b, const std::vector<double>& c) {
     if ((int)a.size() != 3*n || (int)b.size() != 3*n || (int)c.size() != 3*n) throw std::invalid_argument("MapPointTable: array sizes");
   }

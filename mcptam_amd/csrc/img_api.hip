@@ -11,10 +11,13 @@
 #include <map>
 #include <memory>
 #include <cmath>
+#include <mutex>
+#include <unordered_map>
 
 #include "../../include/mcp_img.h"
 #include "img_kernels.h"
 #include "pvs_kernels.h"
+#include "track_map_kernels.h"
 #include "ba_select.h"
 
 using namespace mcp;
@@ -70,6 +73,7 @@ struct Level {
 
 struct mcp_kf {
   int device = 0; hipStream_t st = nullptr;
+  unsigned long long serial = 0;    // creation serial: the map-point table keeps (handle, serial) of patch sources, never a device pointer
   mcp_kf_params prm;
   Level lev[MCP_LEVELS];
   // scratch reused across calls (no hipMalloc on the per-frame path)
@@ -99,6 +103,12 @@ struct mcp_kf {
   }
 };
 
+// the live keyframes and their creation serials (mcp_map_points_set_source / mcp_track_map resolve a source handle here)
+static std::mutex g_kf_mu;
+static std::unordered_map<const mcp_kf*, unsigned long long> g_kf_live;
+static unsigned long long g_kf_serial = 0;
+static unsigned long long kf_live_serial(const mcp_kf* k) { std::lock_guard<std::mutex> g(g_kf_mu); auto it = g_kf_live.find(k); return it == g_kf_live.end() ? 0ull : it->second; }
+
 static bool gfx950(int dev) { hipDeviceProp_t p; return hipGetDeviceProperties(&p, dev) == hipSuccess && std::strncmp(p.gcnArchName, "gfx950", 6) == 0; }
 
 extern "C" {
@@ -125,9 +135,14 @@ mcp_kf* mcp_kf_create(int w, int h, const mcp_kf_params* params) {
     (void)hipMemset(L.info.p, 0, sizeof(LevelInfo));
     (void)hipMemset(L.scan.p, 0, ((size_t)(L.h + 3)/4 + 1)*sizeof(unsigned long long));      // (epoch 0 = never written; frames count from 1)
   }
+  { std::lock_guard<std::mutex> g(g_kf_mu); k->serial = ++g_kf_serial; g_kf_live[k] = k->serial; }
   return k;
 }
-void mcp_kf_destroy(mcp_kf* k) { if (k) { (void)hipSetDevice(k->device); delete k; } }
+void mcp_kf_destroy(mcp_kf* k) {
+  if (!k) return;
+  { std::lock_guard<std::mutex> g(g_kf_mu); g_kf_live.erase(k); }
+  (void)hipSetDevice(k->device); delete k;
+}
 
 // MakeKeyFrame_Lite of every camera of a frame in one submission (the loop of Tracker::TrackFrame, src/Tracker.cc:303-318): the
 // uploads, three launches for all levels of all cameras (k_pyr_fast, k_row_count, k_row_compact) and one wait.
@@ -1096,6 +1111,38 @@ struct mcp_map_points {
   Buf<signed char> lvl; Buf<mcp_pvs_entry> ent; Buf<int> blk_cnt;
   PinBuf<mcp_pvs_entry> h_out; PinBuf<int> h_counts;
   int view_ncam = 0; int view_first[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; int view_count[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; bool view_ok[MCP_MAX_FRAME_CAMS] = {};
+  // mcp_track_map: the lists of its PVS stay in device memory (tm_pvs) until mcp_track_find_pvs_view asks for them
+  bool pvs_on_device = false; int pvs_rows = 0;      // (... laid out camera by camera at c * pvs_rows: the table's size at that call)
+  // TrackMap: patch sources per row (capacity = pts.n), the persistent finders per (camera, row), the source keyframes as (handle, serial)
+  Buf<TmSrc> src; Buf<mcp_pf_state> states[MCP_MAX_FRAME_CAMS]; int st_ncam = 0;
+  // slots are reference-counted by the rows that name them (row_slot: the host's copy of each row's slot1); a slot no row names is
+  // released and its index reused, so the table walked per call stays as long as the keyframes the map currently uses as sources
+  std::vector<std::pair<const mcp_kf*, unsigned long long>> slots; std::map<std::pair<const mcp_kf*, unsigned long long>, int> slot_of;
+  std::vector<int> slot_refs, free_slots, row_slot;
+  int slot_acquire(const std::pair<const mcp_kf*, unsigned long long>& id) {      // 1 + index, one more reference
+    auto it = slot_of.find(id);
+    int q;
+    if (it != slot_of.end()) q = it->second;
+    else {
+      if (free_slots.empty()) { q = (int)slots.size(); slots.push_back(id); slot_refs.push_back(0); }
+      else { q = free_slots.back(); free_slots.pop_back(); slots[q] = id; }
+      slot_of.emplace(id, q);
+    }
+    ++slot_refs[q];
+    return q + 1;
+  }
+  void slot_release(int slot1) {
+    if (slot1 <= 0) return;
+    const int q = slot1 - 1;
+    if (--slot_refs[q] == 0) { slot_of.erase(slots[q]); slots[q] = std::make_pair((const mcp_kf*)nullptr, 0ull); free_slots.push_back(q); }
+  }
+  PinBuf<TmSrc> h_src; Buf<TmSrc> d_src;
+  // mcp_track_map's scratch and its pinned results
+  Buf<mcp_pvs_entry> tm_pvs; Buf<int> tm_counts, tm_sel; Buf<unsigned long long> tm_k0, tm_k1; Buf<uint8_t> tm_live, tm_blk; Buf<TmCtl> tm_ctl; Buf<TmSlot> tm_slots;
+  Buf<mcp_pose_point> tm_crec, tm_frec; Buf<double> tm_w, tm_J, tm_ex, tm_e2; Buf<mcp_track_map_item> tm_items;
+  PinBuf<uint8_t> h_blk; PinBuf<TmSlot> h_slots; PinBuf<mcp_track_map_item> h_items; PinBuf<TmOut> h_res;
+  int tm_ncam = 0; int tm_first[MCP_MAX_FRAME_CAMS + 1] = {};
+  TmStates state_ptrs() const { TmStates S; for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c) S.s[c] = states[c].p; return S; }
   ~mcp_map_points() { if (st) (void)hipStreamSynchronize(st); if (st) (void)hipStreamDestroy(st); if (staged) (void)hipEventDestroy(staged); }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
   // rows [rows, new_rows) become unusable zero rows; the contents so far move to a larger block when the capacity is passed
@@ -1105,12 +1152,34 @@ struct mcp_map_points {
       Buf<PvsPoint> bigger;
       if (bigger.alloc(std::max<size_t>({(size_t)new_rows, 2*pts.n, (size_t)1024}))) return -1;
       if (rows) ICK(hipMemcpyAsync(bigger.p, pts.p, sizeof(PvsPoint)*(size_t)rows, hipMemcpyDeviceToDevice, st));
+      // the columns of TrackMap follow the table's capacity
+      Buf<TmSrc> src2; if (src2.alloc(bigger.n)) return -1;
+      if (rows && src.p) ICK(hipMemcpyAsync(src2.p, src.p, sizeof(TmSrc)*(size_t)rows, hipMemcpyDeviceToDevice, st));
+      Buf<mcp_pf_state> st2[MCP_MAX_FRAME_CAMS];
+      for (int c = 0; c < st_ncam; ++c) {
+        if (st2[c].alloc(bigger.n)) return -1;
+        if (rows) ICK(hipMemcpyAsync(st2[c].p, states[c].p, sizeof(mcp_pf_state)*(size_t)rows, hipMemcpyDeviceToDevice, st));
+      }
       ICK(hipStreamSynchronize(st));                 // the old block is freed below, with nothing in flight on it
       stage_busy = false;
-      pts.swap(bigger);
+      pts.swap(bigger); src.swap(src2);
+      for (int c = 0; c < st_ncam; ++c) states[c].swap(st2[c]);
     }
     ICK(hipMemsetAsync(pts.p + rows, 0, sizeof(PvsPoint)*(size_t)(new_rows - rows), st));
+    // (rows dropped by a resize come back without a source, and with finders that have seen nothing)
+    ICK(hipMemsetAsync(src.p + rows, 0, sizeof(TmSrc)*(size_t)(new_rows - rows), st));
+    for (int c = 0; c < st_ncam; ++c) ICK(hipMemsetAsync(states[c].p + rows, 0, sizeof(mcp_pf_state)*(size_t)(new_rows - rows), st));
+    row_slot.resize(new_rows, 0);
     rows = new_rows;
+    return 0;
+  }
+  // finders for cameras 0 .. ncam-1 (zeroed when new)
+  int ensure_states(int ncam) {
+    for (int c = st_ncam; c < ncam; ++c) {
+      if (states[c].alloc(std::max<size_t>(pts.n, 1))) return -1;
+      ICK(hipMemsetAsync(states[c].p, 0, sizeof(mcp_pf_state)*states[c].n, st));
+    }
+    st_ncam = std::max(st_ncam, ncam);
     return 0;
   }
 };
@@ -1140,7 +1209,12 @@ int mcp_map_points_rows(const mcp_map_points* m) { if (!m) return img_fail("mcp_
 int mcp_map_points_resize(mcp_map_points* m, int rows) {
   if (!m) return img_fail("mcp_map_points_resize: NULL table");
   if (rows < 0) return img_fail("mcp_map_points_resize: bad arguments");
-  if (rows <= m->rows) { m->rows = rows; return 0; }       // the rows past the end are gone; growing again zeroes them (grow)
+  if (rows <= m->rows) {                                    // the rows past the end are gone; growing again zeroes them (grow)
+    for (int r = rows; r < m->rows && r < (int)m->row_slot.size(); ++r) m->slot_release(m->row_slot[r]);
+    if ((int)m->row_slot.size() > rows) m->row_slot.resize(rows);
+    m->rows = rows;
+    return 0;
+  }
   ICK(hipSetDevice(m->device));
   return m->grow(rows);
 }
@@ -1188,7 +1262,7 @@ int mcp_map_points_update(mcp_map_points* m, int count, const int* ids, const do
 int mcp_track_find_pvs(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb,
                        const int* caps, mcp_pvs_entry* const* out, int* counts) {
   if (!m) return img_fail("mcp_track_find_pvs: NULL table");
-  m->view_ncam = 0;
+  m->view_ncam = 0; m->pvs_on_device = false;
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !caps || !counts) return img_fail("mcp_track_find_pvs: bad arguments");
   for (int c = 0; c < ncam; ++c) {
     if (!targets[c] || !cam_ok(&cams[c]) || caps[c] < 0 || (out && !out[c])) return img_fail("mcp_track_find_pvs: bad arguments for camera " + std::to_string(c));
@@ -1252,9 +1326,269 @@ const mcp_pvs_entry* mcp_track_find_pvs_view(const mcp_map_points* m, int cam, i
     img_fail("mcp_track_find_pvs_view: the last mcp_track_find_pvs on this table produced no list for that camera / level");
     return nullptr;
   }
+  if (m->pvs_on_device) {
+    // the lists of the last mcp_track_map: copied to the pinned block on first demand
+    mcp_map_points* w = const_cast<mcp_map_points*>(m);
+    w->pvs_on_device = false;
+    bool ok = hipSetDevice(w->device) == hipSuccess && w->h_out.alloc((size_t)w->view_ncam*std::max(w->pvs_rows, 1)) == 0;      // (the call's layout, whatever the table's size now)
+    for (int c = 0; ok && c < w->view_ncam; ++c) {
+      int all = 0; for (int l = 0; l < MCP_LEVELS; ++l) all += w->view_count[c][l];
+      if (all) ok = hipMemcpy(w->h_out.p + w->view_first[c][0], w->tm_pvs.p + w->view_first[c][0], sizeof(mcp_pvs_entry)*(size_t)all, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (!ok) { w->view_ncam = 0; img_fail("mcp_track_find_pvs_view: copy of the PVS lists failed"); return nullptr; }
+  }
   const int k = m->view_count[cam][level];
   if (count) *count = k;
   return k > 0 ? m->h_out.p + m->view_first[cam][level] : nullptr;
+}
+
+// ---- TrackMap from the table (include/mcp_img.h mcp_track_map, track_map_kernels.h) -------------------------------------------------
+static int source_upload(mcp_map_points* m, const char* what, int first, int count, const int* ids, const int* keys, mcp_kf* const* kfs,
+                         const int* levels, const int* cxy, const uint8_t* fixed) {
+  if (!m) return img_fail(std::string(what) + ": NULL table");
+  if (count < 0 || (!ids && (first < 0 || (long long)first + count > 0x7fffffffLL)) || (count > 0 && (!keys || !kfs || !levels || !cxy || !fixed)))
+    return img_fail(std::string(what) + ": bad arguments");
+  if (count == 0) return 0;
+  int top = ids ? m->rows : first + count;
+  if (ids) {
+    for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(std::string(what) + ": bad row id"); top = std::max(top, ids[k] + 1); }
+    m->sorted_ids.assign(ids, ids + count);
+    std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
+    for (int k = 1; k < count; ++k) if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail(std::string(what) + ": row " + std::to_string(m->sorted_ids[k]) + " appears twice");
+  }
+  std::vector<unsigned long long> ser(count, 0ull);
+  for (int k = 0; k < count; ++k) {
+    if (!kfs[k]) continue;
+    ser[k] = kf_live_serial(kfs[k]);
+    if (!ser[k]) return img_fail(std::string(what) + ": entry " + std::to_string(k) + "'s source keyframe is not a live handle");
+    if (kfs[k]->device != m->device) return img_fail(std::string(what) + ": entry " + std::to_string(k) + "'s source keyframe is on another device than the table");
+    if (levels[k] < 0 || levels[k] >= MCP_LEVELS) return img_fail(std::string(what) + ": bad source level");
+  }
+  ICK(hipSetDevice(m->device));
+  if (m->wait_staging()) return -1;
+  if (m->h_src.alloc(count) || (ids && m->h_ids.alloc(count))) return -1;
+  if ((size_t)count > m->d_src.n || (ids && (size_t)count > m->d_ids.n)) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
+  if (m->d_src.alloc(count) || (ids && m->d_ids.alloc(count))) return -1;
+  if (m->grow(top)) return -1;
+  for (int k = 0; k < count; ++k) {
+    TmSrc& r = m->h_src.p[k];
+    r.key = keys[k]; r.slot1 = 0; r.level = 0; r.cx = cxy[2*(size_t)k]; r.cy = cxy[2*(size_t)k + 1]; r.fixed = fixed[k] ? 1 : 0;
+    if (kfs[k]) { r.slot1 = m->slot_acquire(std::make_pair((const mcp_kf*)kfs[k], ser[k])); r.level = levels[k]; }
+    const int row = ids ? ids[k] : first + k;
+    m->slot_release(m->row_slot[row]);                   // (after the acquire: a row that keeps its source keeps the slot)
+    m->row_slot[row] = r.slot1;
+    if (ids) m->h_ids.p[k] = ids[k];
+  }
+  ICK(hipMemcpyAsync(m->d_src.p, m->h_src.p, sizeof(TmSrc)*(size_t)count, hipMemcpyHostToDevice, m->st));
+  if (ids) ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+  hipLaunchKernelGGL(k_tm_source_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->src.p, count, ids ? 0 : first, ids ? (const int*)m->d_ids.p : (const int*)nullptr,
+                     (const TmSrc*)m->d_src.p, m->state_ptrs(), m->st_ncam);
+  ICK(hipGetLastError());
+  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  return 0;
+}
+int mcp_map_points_set_source(mcp_map_points* m, int first, int count, const int* keys, mcp_kf* const* kfs, const int* levels, const int* cxy, const uint8_t* fixed) {
+  return source_upload(m, "mcp_map_points_set_source", first, count, nullptr, keys, kfs, levels, cxy, fixed);
+}
+int mcp_map_points_update_source(mcp_map_points* m, int count, const int* ids, const int* keys, mcp_kf* const* kfs, const int* levels, const int* cxy, const uint8_t* fixed) {
+  if (count > 0 && !ids) return img_fail("mcp_map_points_update_source: bad arguments");
+  return source_upload(m, "mcp_map_points_update_source", 0, count, ids, keys, kfs, levels, cxy, fixed);
+}
+int mcp_map_points_get_states(const mcp_map_points* mc, int cam, int first, int count, mcp_pf_state* out) {
+  if (!mc) return img_fail("mcp_map_points_get_states: NULL table");
+  if (cam < 0 || cam >= MCP_MAX_FRAME_CAMS || first < 0 || count < 0 || (long long)first + count > mc->rows || (count > 0 && !out))
+    return img_fail("mcp_map_points_get_states: bad arguments");
+  if (count == 0) return 0;
+  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
+  if (cam >= m->st_ncam) { std::memset(out, 0, sizeof(mcp_pf_state)*(size_t)count); return 0; }
+  ICK(hipSetDevice(m->device));
+  ICK(hipMemcpyAsync(out, m->states[cam].p + first, sizeof(mcp_pf_state)*(size_t)count, hipMemcpyDeviceToHost, m->st));
+  ICK(hipStreamSynchronize(m->st));
+  m->stage_busy = false;
+  return 0;
+}
+
+// the register-resident pose kernel's dynamic LDS, once per device and thread (as refine_enqueue)
+static bool tm_regs_ok() {
+  static thread_local unsigned long long set_mask = 0, ok_mask = 0;
+  int dev = 0; (void)hipGetDevice(&dev);
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(set_mask & bit)) {
+    set_mask |= bit;
+    if (hipFuncSetAttribute((const void*)k_pose_refine_regs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRR_DYN_LDS) == hipSuccess) ok_mask |= bit;
+    else (void)hipGetLastError();
+  }
+  const char* e = getenv("MCP_TRACK_REFINE_REGS");
+  return (ok_mask & bit) && (e ? atoi(e) != 0 : true);
+}
+
+static size_t tm_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                  const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
+                  mcp_track_map_result* res) {
+  if (!m) return img_fail("mcp_track_map: NULL table");
+  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail("mcp_track_map: bad arguments");
+  if (prm->coarse_max < 0 || prm->coarse_range < 0 || prm->coarse_min < 0 || prm->coarse_subpix_its < 0 || prm->max_patches < 0)
+    return img_fail("mcp_track_map: negative cap, range or iteration count");
+  if (!est_ok(prm->estimator)) return img_fail("mcp_track_map: unknown M-estimator");
+  for (int c = 0; c < ncam; ++c) {
+    if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail("mcp_track_map: bad arguments for camera " + std::to_string(c));
+    if (targets[c]->device != m->device)
+      return img_fail("mcp_track_map: camera " + std::to_string(c) + "'s target is on device " + std::to_string(targets[c]->device) + ", the table on device " + std::to_string(m->device));
+    for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail("mcp_track_map: a keyframe appears twice in a frame with images");
+  }
+  ICK(hipSetDevice(m->device));
+  // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
+  m->view_ncam = 0; m->pvs_on_device = false; m->tm_ncam = 0;
+  const int n = m->rows;
+  const size_t NB = (size_t)ncam*std::max(n, 1);                   // bound of every per-item array: a camera's sets are distinct rows
+  const bool coarse = prm->try_coarse && prm->coarse_max > 0;
+  const size_t n_coarse_max = coarse ? std::min(NB, (size_t)ncam*prm->coarse_max) : 0;
+  const bool regs = tm_regs_ok();
+  // everything is allocated before the first enqueue
+  if (m->ensure_states(ncam)) return -1;
+  if (m->tm_pvs.alloc(NB) || m->tm_counts.alloc((size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS) || m->tm_sel.alloc(NB) || m->tm_k0.alloc(NB) || m->tm_k1.alloc(NB) || m->tm_live.alloc(NB) ||
+      m->tm_ctl.alloc(1) || m->tm_slots.alloc(std::max<size_t>(m->slots.size(), 1)) || m->h_slots.alloc(std::max<size_t>(m->slots.size(), 1)) ||
+      m->tm_crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm_frec.alloc(NB) || m->tm_w.alloc(NB) || m->tm_items.alloc(NB) || m->h_items.alloc(NB) || m->h_res.alloc(1) ||
+      m->lvl.alloc(NB) || m->ent.alloc(NB) || m->blk_cnt.alloc((size_t)ncam*((std::max(n, 1) + PVS_BLOCK - 1)/PVS_BLOCK)*MCP_LEVELS) ||
+      m->d_tab.alloc(MCP_MAX_FRAME_CAMS) || m->h_tab.alloc(MCP_MAX_FRAME_CAMS)) return -1;
+  if (NB > (size_t)PRR_THREADS*PRR_PPT || !regs) {
+    if (m->tm_J.alloc(12*NB) || m->tm_ex.alloc(2*NB) || m->tm_e2.alloc(NB)) return -1;
+  }
+  // (param block: cameras' search table | camera models | CamFromBase | BaseFromWorld + mu | override sigma x 2 | nonlinear flags x 2)
+  const size_t o_tab = 0, o_cam = tm_align(sizeof(TmCam)*(size_t)ncam), o_cfb = o_cam + tm_align(sizeof(mcp_camera)*(size_t)ncam), o_pm = o_cfb + tm_align(96*(size_t)ncam);
+  const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), blk = o_nl + tm_align(20);
+  if (m->tm_blk.alloc(blk) || m->h_blk.alloc(blk)) return -1;
+  mcp_kf* k0 = targets[0];
+  struct Drain { mcp_map_points* m; bool armed; int ncam; mcp_kf* const* targets; bool lite;
+                 ~Drain() { if (armed) { (void)hipStreamSynchronize(m->st); if (lite) { (void)hipStreamSynchronize(targets[0]->st); (void)lite_batch_finish(ncam, targets); } m->tab_last.clear(); m->tm_ncam = 0; (void)hipGetLastError(); } } };
+  Drain drain{m, true, ncam, targets, imgs != nullptr};
+  if (imgs) {
+    if (lite_batch_enqueue(ncam, targets, imgs, strides, imgs_on_device, masks)) return -1;
+    ICK(hipEventRecord(k0->ev, k0->st));
+    ICK(hipStreamWaitEvent(m->st, k0->ev, 0));
+  }
+  // the tables are built after the pyramids' launch: it rotates the level images of the targets
+  uint8_t* hb = m->h_blk.p;
+  std::memset(hb, 0, blk);
+  TmCam* tab = reinterpret_cast<TmCam*>(hb + o_tab);
+  for (int c = 0; c < ncam; ++c) {
+    tab[c].T = targets[c]->view(); tab[c].mask0 = targets[c]->lev[0].has_mask ? targets[c]->lev[0].mask.p : nullptr; tab[c].cam = cams[c];
+    std::memcpy(tab[c].cfb.R, cfb + 12*c, 72); std::memcpy(tab[c].cfb.t, cfb + 12*c + 9, 24);
+  }
+  std::memcpy(hb + o_cam, cams, sizeof(mcp_camera)*(size_t)ncam);
+  std::memcpy(hb + o_cfb, cfb, 96*(size_t)ncam);
+  std::memcpy(hb + o_pm, bfw, 96);
+  double* ov = reinterpret_cast<double*>(hb + o_ov); uint8_t* nl = hb + o_nl;
+  for (int i = 0; i < 10; ++i) {
+    ov[i] = i < 6 ? 0.0 : 1.0; nl[i] = 1;                                                 // coarse, Tracker.cc:1012-1020
+    ov[10 + i] = i < 6 ? 0.0 : 16.0; nl[10 + i] = (i == 0 || i == 4 || i == 9) ? 1 : 0;   // fine, :1063-1075
+  }
+  const size_t nslot = std::max<size_t>(m->slots.size(), 1);
+  std::memset(m->h_slots.p, 0, sizeof(TmSlot)*nslot);
+  std::unique_lock<std::mutex> reg(g_kf_mu);
+  for (size_t q = 0; q < m->slots.size(); ++q) {
+    const mcp_kf* s = m->slots[q].first;
+    auto live = s ? g_kf_live.find(s) : g_kf_live.end();
+    if (live == g_kf_live.end() || live->second != m->slots[q].second) continue;     // released, destroyed, or its address reused: dead
+    TmSlot& S = m->h_slots.p[q];
+    for (int l = 0; l < MCP_LEVELS; ++l) { S.img[l] = s->lev[l].img.p; S.w[l] = s->lev[l].w; S.h[l] = s->lev[l].h; }
+    S.live = 1;
+  }
+  reg.unlock();
+  hipStream_t st = m->st;
+  ICK(hipMemcpyAsync(m->tm_blk.p, hb, blk, hipMemcpyHostToDevice, st));
+  ICK(hipMemcpyAsync(m->tm_slots.p, m->h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
+  // 1. FindPVS, lists and counts in device memory (caps = rows; camera c's list at c * rows)
+  if (n > 0) {
+    const int nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
+    std::vector<PvsCam> ptab(ncam);
+    for (int c = 0; c < ncam; ++c) {
+      PvsCam& C = ptab[c];
+      std::memset(&C, 0, sizeof(PvsCam));
+      C.cam = cams[c]; std::memcpy(C.cfb.R, cfb + 12*c, 72); std::memcpy(C.cfb.t, cfb + 12*c + 9, 24);
+      const Level& L0 = targets[c]->lev[0];
+      C.mask0 = L0.has_mask ? L0.mask.p : nullptr; C.mask_w = L0.w; C.mask_h = L0.h;
+      C.cap = n; C.out_first = c*n;
+    }
+    if (m->tab_last.size() != ptab.size() || std::memcmp(m->tab_last.data(), ptab.data(), sizeof(PvsCam)*ptab.size()) != 0) {
+      std::memcpy(m->h_tab.p, ptab.data(), sizeof(PvsCam)*ptab.size());
+      ICK(hipMemcpyAsync(m->d_tab.p, m->h_tab.p, sizeof(PvsCam)*ptab.size(), hipMemcpyHostToDevice, st));
+      m->tab_last = ptab;
+    }
+    Se3 B; std::memcpy(B.R, bfw, 72); std::memcpy(B.t, bfw + 9, 24);
+    hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, st, (const PvsCam*)m->d_tab.p, B, (const PvsPoint*)m->pts.p, n, nblk, m->lvl.p, m->ent.p, m->blk_cnt.p);
+    hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, st, (const PvsCam*)m->d_tab.p, n, nblk, (const signed char*)m->lvl.p,
+                       (const mcp_pvs_entry*)m->ent.p, (const int*)m->blk_cnt.p, m->tm_pvs.p, m->tm_counts.p);
+  } else ICK(hipMemsetAsync(m->tm_counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
+  // 2. the sets
+  TmParams P; P.ncam = ncam; P.rows = n; P.try_coarse = prm->try_coarse ? 1 : 0; P.coarse_max = prm->coarse_max; P.coarse_range = prm->coarse_range;
+  P.coarse_subpix_its = prm->coarse_subpix_its; P.coarse_min = prm->coarse_min; P.max_patches = prm->max_patches; P.seed = prm->seed;
+  hipLaunchKernelGGL(k_tm_select, dim3(ncam), dim3(TM_SEL_NT), 0, st, P, (const mcp_pvs_entry*)m->tm_pvs.p, (const int*)m->tm_counts.p, (const TmSrc*)m->src.p,
+                     (const TmSlot*)m->tm_slots.p, m->tm_k0.p, m->tm_k1.p, m->tm_live.p, m->tm_sel.p, m->tm_ctl.p);
+  const TmCam* d_tab = reinterpret_cast<const TmCam*>(m->tm_blk.p + o_tab);
+  const mcp_camera* d_cams = reinterpret_cast<const mcp_camera*>(m->tm_blk.p + o_cam);
+  const double* d_cfb = reinterpret_cast<const double*>(m->tm_blk.p + o_cfb);
+  double* d_pm = reinterpret_cast<double*>(m->tm_blk.p + o_pm);
+  const double* d_ov = reinterpret_cast<const double*>(m->tm_blk.p + o_ov);
+  const uint8_t* d_nl = m->tm_blk.p + o_nl;
+  TmCtl* ctl = m->tm_ctl.p;
+  auto iterate = [&](size_t bound, const int* n_dev, const int* gate, mcp_pose_point* recs, int stage) -> int {
+    const double* o = d_ov + 10*stage; const uint8_t* f = d_nl + 10*stage;
+    if (regs) hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, d_pm + 12, m->tm_w.p, prm->estimator, ncam, n_dev, gate);
+    if (!regs || bound > (size_t)PRR_THREADS*PRR_PPT)      // (more records than the register-resident kernel holds, or no such kernel)
+      hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, m->tm_J.p, m->tm_ex.p, m->tm_e2.p, d_pm + 12, m->tm_w.p,
+                         prm->estimator, n_dev, gate, regs ? PRR_THREADS*PRR_PPT : -1);
+    ICK(hipGetLastError());
+    return 0;
+  };
+  // 3-5. coarse search, the gate, the coarse iterations
+  if (coarse)
+    hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(n_coarse_max, 8192)), dim3(64), 0, st, P, 0, d_tab, (const double*)d_pm, (const PvsPoint*)m->pts.p,
+                       (const TmSrc*)m->src.p, (const TmSlot*)m->tm_slots.p, (const int*)m->tm_sel.p, m->state_ptrs(), ctl, m->tm_items.p, m->tm_crec.p, m->tm_frec.p, m->tm_w.p);
+  hipLaunchKernelGGL(k_tm_gate, dim3(1), dim3(1), 0, st, P, ctl);
+  if (coarse && iterate(n_coarse_max, &ctl->n_coarse, &ctl->did_coarse, m->tm_crec.p, 0)) return -1;
+  // 6-7. fine searches at the current pose, the fine iterations over [C_c, T_c, R_c]
+  hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, (const PvsPoint*)m->pts.p,
+                     (const TmSrc*)m->src.p, (const TmSlot*)m->tm_slots.p, (const int*)m->tm_sel.p, m->state_ptrs(), ctl, m->tm_items.p, m->tm_crec.p, m->tm_frec.p, m->tm_w.p);
+  if (iterate(NB, &ctl->n_fine, nullptr, m->tm_frec.p, 1)) return -1;
+  hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm_w.p,
+                     (const mcp_track_map_item*)m->tm_items.p, m->h_items.p,
+                     (const double*)d_pm, (const int*)m->tm_counts.p, m->h_res.p);
+  ICK(hipGetLastError());
+  ICK(hipStreamSynchronize(st));
+  drain.armed = false;
+  m->stage_busy = false;
+  if (imgs && lite_batch_finish(ncam, targets)) return -1;
+  const TmOut& R = *m->h_res.p;
+  std::memset(res, 0, sizeof *res);
+  res->did_coarse = R.ctl.did_coarse; res->coarse_found = R.ctl.coarse_found;
+  int first = 0;
+  for (int c = 0; c < ncam; ++c) {
+    int off = c*n;
+    for (int l = 0; l < MCP_LEVELS; ++l) {
+      res->pvs_counts[c][l] = R.counts[c][l];
+      m->view_first[c][l] = off; m->view_count[c][l] = R.counts[c][l]; off += R.counts[c][l];
+    }
+    m->view_ok[c] = true;
+    for (int q = 0; q < 3; ++q) res->set_sizes[c][q] = R.ctl.sizes[c][q];
+    res->stale[c] = R.ctl.stale[c];
+    m->tm_first[c] = first; first += R.ctl.sizes[c][0] + R.ctl.sizes[c][1] + R.ctl.sizes[c][2];
+  }
+  m->tm_first[ncam] = first; m->tm_ncam = ncam;
+  m->view_ncam = ncam; m->pvs_on_device = true; m->pvs_rows = n;
+  std::memcpy(res->mu_last, R.mu, 48);
+  std::memcpy(bfw, R.pose, 96);
+  return 0;
+}
+
+const mcp_track_map_item* mcp_track_map_view(const mcp_map_points* m, int cam, int* count) {
+  if (count) *count = 0;
+  if (!m || cam < 0 || cam >= m->tm_ncam) { img_fail("mcp_track_map_view: the last mcp_track_map on this table produced no items for that camera"); return nullptr; }
+  const int k = m->tm_first[cam + 1] - m->tm_first[cam];
+  if (count) *count = k;
+  return k > 0 ? m->h_items.p + m->tm_first[cam] : nullptr;
 }
 
 }  // extern "C"

@@ -1233,12 +1233,17 @@ constexpr int PR_THREADS = 1024;
 __global__ void __launch_bounds__(PR_THREADS)
 k_pose_refine(int n, mcp_pose_point* __restrict__ pts, const mcp_camera* __restrict__ cams, const double* __restrict__ cfb_all,
               double* __restrict__ bfw_io, int n_iter, const uint8_t* __restrict__ nonlinear, const double* __restrict__ override_sigma,
-              double* __restrict__ J, double* __restrict__ ex /* 2n */, double* __restrict__ e2s, double* __restrict__ mu_out, double* __restrict__ w_out, int est) {
+              double* __restrict__ J, double* __restrict__ ex /* 2n */, double* __restrict__ e2s, double* __restrict__ mu_out, double* __restrict__ w_out, int est,
+              const int* __restrict__ n_dev = nullptr /* mcp_track_map: the record count, from device memory */,
+              const int* __restrict__ gate = nullptr /* ... and the stage's gate: 0 = nothing runs, the pose stays */, int run_above = -1 /* run only for n > run_above */) {
   __shared__ unsigned int hist[2048];
   __shared__ unsigned long long sel_sc[1024/64 + 3], sel_st[2];
   __shared__ double red[PR_THREADS/64][28];
   __shared__ double pose[12], v6[6], tot[27];
   __shared__ int nf_s;
+  if (gate && *gate == 0) return;
+  if (n_dev) n = *n_dev;
+  if (n <= run_above) return;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   if (t < 12) pose[t] = bfw_io[t];
   if (t < 6) v6[t] = 0.0;
@@ -1601,8 +1606,12 @@ constexpr size_t PRR_DYN_LDS = sizeof(double)*((12 + 3)*(size_t)PRR_THREADS*PRR_
 __global__ void __launch_bounds__(PRR_THREADS)
 k_pose_refine_regs(int n, mcp_pose_point* __restrict__ pts, const mcp_camera* __restrict__ cams, const double* __restrict__ cfb_all,
                    double* __restrict__ bfw_io, int n_iter, const uint8_t* __restrict__ nonlinear, const double* __restrict__ override_sigma,
-                   double* __restrict__ mu_out, double* __restrict__ w_out, int est, int ncam) {
+                   double* __restrict__ mu_out, double* __restrict__ w_out, int est, int ncam,
+                   const int* __restrict__ n_dev = nullptr /* mcp_track_map: the record count, from device memory (more than fit: k_pose_refine runs them) */,
+                   const int* __restrict__ gate = nullptr /* ... and the stage's gate: 0 = nothing runs, the pose stays */) {
 #pragma clang fp contract(fast)                   // (the sums and the linear updates; the camera model keeps its own uncontracted arithmetic)
+  if (gate && *gate == 0) return;
+  if (n_dev) { n = *n_dev; if (n > PRR_THREADS*PRR_PPT) return; }
   constexpr int NT = PRR_THREADS, NW = NT/64, BPT = SEL_BINS/NT;
   PRR_STAMP_K(0);
   __shared__ unsigned int hist[SEL_BINS];

@@ -1,4 +1,5 @@
-// Tracker_gpu.cc -- MI355X bodies of Tracker::FindPVS, Tracker::SearchForPoints and Tracker::CalcPoseUpdate.
+// Tracker_gpu.cc -- MI355X bodies of Tracker::FindPVS, Tracker::SearchForPoints and Tracker::CalcPoseUpdate, and the optional one-call
+// forms of a TrackMap stage (TrackStageOnDevice) and of the whole TrackMap from the map table (TrackMapOnDevice).
 //
 // Replace /root/reference/src/Tracker.cc:662-723 (FindPVS), :1297-1377 (SearchForPoints) and :1379-1512 (CalcPoseUpdate): delete those
 // member functions there (or fence them with #ifndef MCPTAM_HIP) and add this file to the library's sources.  The tracker keeps all of its
@@ -454,6 +455,157 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
       pTData->mbSearched = false;
       pTData->mbFound = false;
       vPVSLevels[l].push_back(pTData);      // rows ascending; TrackMap random_shuffles every level next (:983)
+    }
+  }
+}
+
+// ---- the whole TrackMap from the table in one submission (include/mcp_img.h, mcp_track_map) --------------------------------------------
+// Replaces src/Tracker.cc:938-1075 (FindPVS of every camera, the shuffles, TestForCoarse, the coarse gate and iterations,
+// SetupFineTracking, the fine iterations).  Needs, in addition to the FindPVS members above, in class Tracker:
+//     void TrackMapOnDevice();
+//     void UploadMapSources();
+// and the patch sources of the rows: UploadMapSources() below, after UploadMapTable() (option (a); with option (b) the same call goes
+// with each row update, as mcp_map_points_update_source).  Keys: the point's address >> 4, as TrackStageOnDevice uses.  Truncated to an
+// int two live points can share a key, and with option (a) a row changes points whenever the map drops one; either only costs a finder
+// that has seen nothing (a new key) or a template cache tested against another point's warp (a shared key).  A unique id per MapPoint
+// (a counter assigned when the point enters the map) avoids the second.  The cameras go in mvCurrCamNames order every frame (the
+// table keeps a finder per (row, camera index)).
+// What the host still does afterwards: the counters, mvIterationSets and the outlier marks are rebuilt from the items below; then
+// RefreshSceneDepth (:1085) as before.  Deviation: mv3Cam of the tracked points is the final pose's (the reference leaves the value of the
+// last ProjectAndDerivs).
+void Tracker::UploadMapSources()
+{
+  // caller holds mMap.mMutex; rows as UploadMapTable() wrote them
+  const int n = (int)mvMapTableRows.size();
+  if(n == 0)
+    return;
+  std::vector<int> vKeys(n), vLevels(n), vCenters(2*n);
+  std::vector<mcp_kf*> vSources(n);
+  std::vector<uint8_t> vFixed(n);
+  for(int k = 0; k < n; ++k)
+  {
+    MapPoint& point = *mvMapTableRows[k];
+    vKeys[k] = (int)(reinterpret_cast<uintptr_t>(&point) >> 4);
+    vSources[k] = point.mpPatchSourceKF ? point.mpPatchSourceKF->mpDev : NULL;
+    vLevels[k] = point.mnSourceLevel;
+    vCenters[2*k] = point.mirCenter.x;
+    vCenters[2*k + 1] = point.mirCenter.y;
+    vFixed[k] = point.mbFixed ? 1 : 0;
+  }
+  if(mcp_map_points_set_source(mpMapTable, 0, n, &vKeys[0], &vSources[0], &vLevels[0], &vCenters[0], &vFixed[0]) != 0)
+  {
+    ROS_FATAL_STREAM("Tracker::UploadMapSources: "<<mcp_last_error());
+    ros::shutdown();
+  }
+}
+
+void Tracker::TrackMapOnDevice()
+{
+  const int nCams = (int)mvCurrCamNames.size();
+  std::vector<mcp_kf*> vKF(nCams);
+  std::vector<mcp_camera> vCams(nCams);
+  std::vector<double> vCfB(12 * nCams);
+  for(int c = 0; c < nCams; ++c)
+  {
+    KeyFrame& kf = *mpCurrentMKF->mmpKeyFrames[mvCurrCamNames[c]];
+    ROS_ASSERT(kf.mpDev);
+    vKF[c] = kf.mpDev;
+    vCams[c] = mcptam_hip::CameraExport::Make(mmCameraModels[mvCurrCamNames[c]]);
+    ToArray12(kf.mse3CamFromBase, &vCfB[12*c]);
+    for(int l = 0; l < LEVELS; ++l)
+      mmMeasAttemptedLevels[mvCurrCamNames[c]][l] = mmMeasFoundLevels[mvCurrCamNames[c]][l] = 0;
+  }
+
+  // the heuristics of :988-1008 stay here
+  mcp_track_map_params prm;
+  prm.try_coarse = !(Tracker::sbDisableCoarse || mdMSDScaledVelocityMagnitude < Tracker::sdCoarseMinVelocity || Tracker::snCoarseMax == 0);
+  prm.coarse_max = Tracker::snCoarseMax;
+  prm.coarse_range = Tracker::snCoarseRange;
+  if(mbJustRecoveredSoUseCoarse)
+  {
+    prm.try_coarse = 1;
+    prm.coarse_max *= 2;
+    prm.coarse_range *= 2;
+    mbJustRecoveredSoUseCoarse = false;
+  }
+  prm.coarse_min = Tracker::snCoarseMin;
+  prm.coarse_subpix_its = Tracker::snCoarseSubPixIts;
+  prm.max_patches = Tracker::snMaxPatchesPerFrame;
+  prm.estimator = MCP_MEST_TUKEY;
+  if(Tracker::sMEstimatorName == "Cauchy") prm.estimator = MCP_MEST_CAUCHY;
+  else if(Tracker::sMEstimatorName == "Huber") prm.estimator = MCP_MEST_HUBER;
+  prm.seed = mnFrame;                                   // a different shuffle every frame, reproducible per frame
+
+  double adBfW[12];
+  ToArray12(mpCurrentMKF->mse3BaseFromWorld, adBfW);
+  mcp_track_map_result res;
+  {
+    boost::mutex::scoped_lock lock(mMap.mMutex);
+    UploadMapTable();
+    UploadMapSources();
+    if(mcp_track_map(mpMapTable, nCams, &vKF[0], NULL, NULL, 0, NULL, &vCams[0], adBfW, &vCfB[0], &prm, &res) != 0)
+    {
+      ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: "<<mcp_last_error());
+      ros::shutdown();
+      return;
+    }
+  }
+  mbDidCoarse = res.did_coarse != 0;
+  Matrix<3> m3R;
+  Vector<3> v3T;
+  for(int i = 0; i < 3; ++i)
+  {
+    for(int j = 0; j < 3; ++j)
+      m3R(i, j) = adBfW[3*i + j];
+    v3T[i] = adBfW[9 + i];
+  }
+  mpCurrentMKF->mse3BaseFromWorld = SE3<>(SO3<>(m3R), v3T);
+  UpdateCamsFromWorld();
+
+  // mvIterationSets, the level counters (SearchForPoints :1322, 1347, 1361) and the outlier marks of the last iteration (:1454-1488)
+  mvIterationSets.assign(nCams, TrackerDataPtrVector());
+  mnNumInliers = 0;
+  for(int c = 0; c < nCams; ++c)
+  {
+    const std::string& camName = mvCurrCamNames[c];
+    const SE3<>& se3CamFromWorld = mpCurrentMKF->mmpKeyFrames[camName]->mse3CamFromWorld;
+    int n = 0;
+    const mcp_track_map_item* it = mcp_track_map_view(mpMapTable, c, &n);
+    for(int i = 0; i < n; ++i)
+    {
+      const mcp_td_out& o = it[i].out;
+      MapPoint& point = *mvMapTableRows[it[i].point];
+      if(!point.mmpTData.count(camName))
+        point.mmpTData[camName] = new TrackerData(&point, mmSizes[camName]);
+      boost::intrusive_ptr<TrackerData> pTData(point.mmpTData[camName]);
+      TrackerData& td = *pTData;
+      td.mv3Cam = se3CamFromWorld * point.mv3WorldPos;
+      td.mbInImage = o.in_image != 0;
+      td.mv2Image = makeVector(o.image[0], o.image[1]);
+      td.mm2CamDerivs(0, 0) = o.cam_derivs[0]; td.mm2CamDerivs(0, 1) = o.cam_derivs[1];
+      td.mm2CamDerivs(1, 0) = o.cam_derivs[2]; td.mm2CamDerivs(1, 1) = o.cam_derivs[3];
+      td.mnSearchLevel = o.search_level;
+      td.mbSearched = o.searched != 0;
+      td.mbFound = o.found != 0;
+      td.mv2Found = makeVector(o.found_pos[0], o.found_pos[1]);
+      td.mdSqrtInvNoise = o.sqrt_inv_noise;
+      if(!o.template_bad && o.search_level >= 0)
+      {
+        mmMeasAttemptedLevels[camName][o.search_level]++;
+        if(o.found) mmMeasFoundLevels[camName][o.search_level]++;
+      }
+      if(!td.mbFound)
+      {
+        if(td.mbSearched && !IsLost()) point.mnMEstimatorOutlierCount++;
+      }
+      else if(it[i].weight_last == 0.0)
+        point.mnMEstimatorOutlierCount++;
+      else
+      {
+        point.mnMEstimatorInlierCount++;
+        mnNumInliers++;
+      }
+      mvIterationSets[c].push_back(pTData);
     }
   }
 }
