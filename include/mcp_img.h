@@ -398,6 +398,66 @@ int mcp_track_map(mcp_map_points*, int ncam, mcp_kf* const* targets, const uint8
 /* zero-copy: camera cam's items [C, T, R] of the last mcp_track_map on this table, in the library's pinned block; valid until the next call */
 const mcp_track_map_item* mcp_track_map_view(const mcp_map_points*, int cam, int* count);
 
+/* ---- MapMakerServerBase::AddStereoMapPoints of one source keyframe and level in ONE submission ---- src/MapMakerServerBase.cc:411-496, 604-918
+ * The reference loops over the targets j = 0, 1, ... (ClosestKeyFramesWithinDist, after the caller has dropped the targets it skips: mbBad parents,
+ * CrossCamera, sbOnlyFirstCameraGeneratesPoints) and per target over the candidates left by ThinCandidates, calling AddPointEpipolar.  Here, per
+ * target and on the device:
+ *   ThinCandidates: a candidate (level position) survives when (busy - pos).mag_squared() >= 100 for every busy position -- ir_rounded(root_pos /
+ *     LevelScale(level)) of every source measurement at `level` or `level + 1`, and the root positions of the points this call created so far;
+ *   per surviving candidate (one wavefront each): the epipolar arc of :611-723, the probe MapPoint of :726-738, its hypotheses walked through ONE fresh
+ *     finder in MCP_PF_EPI_COARSE semantics (range 3), the ambiguity rules of :798-825 as the code has them (matches in (score, hypothesis) order;
+ *     nResizeTo = 1 + #{later matches with score > 0.9 best}; reject above 3 or when a kept index is more than 1 from the best), the kept matches in
+ *     MCP_PF_EPI_REFINE semantics on the same finder (first to converge wins), ReprojectPoint (:123-143, one-sided Jacobi SVD) and the new point;
+ *   nLimit as the reference counts it: numSuccess runs over all targets and the break only leaves the candidate loop, so once the limit is reached every
+ *     later target still tries its first surviving candidate.
+ * Results equal mcp_stereo_hypotheses + mcp_patch_sequences(EPI_COARSE) with fresh states + that selection + mcp_patch_sequences(EPI_REFINE) on the
+ * returned states, composed on the host.  Runs on the source's stream with scratch owned by the source; targets are only read. */
+typedef struct mcp_stereo_target {
+  mcp_kf* kf;                   /* keyframe searched in (its level-0 mask, if any, gates hypotheses as in MCP_PF_EPI_COARSE) */
+  const mcp_camera* cam;
+  double cam_from_world[12];    /* KeyFrame::mse3CamFromWorld (R row-major 9, t 3)                                          */
+  double one_pixel_angle;       /* TaylorCamera::OnePixelAngle() of the target camera (src/TaylorCamera.cc:194-196), > 0       */
+} mcp_stereo_target;
+typedef struct mcp_stereo_meas {       /* one entry of the source's mmpMeasurements                                         */
+  double root_pos[2];           /* Measurement::v2RootPos                                                                 */
+  int level;                    /* Measurement::nLevel                                                                    */
+  int pad_;
+} mcp_stereo_meas;
+typedef struct mcp_stereo_point {      /* one created MapPoint with its two measurements (:855-914)                       */
+  int candidate;                /* index into the caller's candidate list                                                 */
+  int target;                   /* index into targets[]                                                                   */
+  int hypothesis;               /* winning hypothesis (step along the arc)                                                */
+  int score;                    /* its coarse ZMSSD                                                                       */
+  double world_pos[3];          /* mv3WorldPos                                                                            */
+  double root_pos[2];           /* SRC_ROOT measurement: LevelZeroPos of the candidate                                    */
+  double target_pos[2];         /* SRC_EPIPOLAR measurement: the sub-pixel position in the target, level 0                */
+  double center_nc[3], one_right_nc[3], one_down_nc[3];   /* mv3Center_NC, mv3OneRightFromCenter_NC, mv3OneDownFromCenter_NC */
+  double pixel_right_w[3], pixel_down_w[3];               /* RefreshPixelVectors at world_pos                              */
+} mcp_stereo_point;
+/* outcome per (target, candidate) */
+#define MCP_STEREO_THINNED 1      /* not in the candidate list when the target's turn came                               */
+#define MCP_STEREO_NO_ARC 2       /* v3BetweenEndpoints too small, or a non-finite arc / step count                      */
+#define MCP_STEREO_NO_MATCH 3     /* no hypothesis found a match                                                         */
+#define MCP_STEREO_TOO_MANY 4     /* nResizeTo > 3                                                                       */
+#define MCP_STEREO_INDEX_FAR 5    /* a kept match more than one hypothesis from the best                                 */
+#define MCP_STEREO_NO_SUBPIX 6    /* no kept match converged                                                             */
+#define MCP_STEREO_CREATED 7
+#define MCP_STEREO_PAST_LIMIT 8   /* a surviving candidate the reference never tries because numSuccess reached nLimit    */
+/* src / src_cam / src_cam_from_world: the source keyframe; cand: its level-`level` candidate positions (Level::vCandidates, in order); meas: its
+ * measurements.  Returns the number of created points (<= n_cand <= cap), written to out in the reference's creation order (target-major, candidate
+ * ascending).  keep[n_cand]: vCandidates as the reference leaves it (thinned before the last target).  outcome: NULL or n_targets x n_cand codes.
+ * Refusals (-1, mcp_last_error()) happen before anything is enqueued: NULL or destroyed keyframes, keyframes without a frame, a target on another
+ * device, a level outside 0..3, negative counts, a bad camera, cap < n_cand, a candidate outside the level image, a non-finite measurement, a
+ * one_pixel_angle that is not positive and finite. */
+int mcp_stereo_points(mcp_kf* src, const mcp_camera* src_cam, const double src_cam_from_world[12], int level, int n_cand, const mcp_int2* cand,
+                      int n_meas, const mcp_stereo_meas* meas, int n_targets, const mcp_stereo_target* targets, int limit,
+                      int cap, mcp_stereo_point* out, uint8_t* keep, uint8_t* outcome);
+/* The hypotheses of mcp_stereo_points for candidates cand[0..n_cand) against one target, computed by the same device code: hypothesis h of candidate
+ * i is out[offsets[i] + h] (offsets: n_cand + 1), as the mcp_td_in the finder sees (world position, pixel vectors of the probe MapPoint, source =
+ * src at `level`, center = the candidate).  Returns the total; out == NULL counts only, otherwise total > cap is refused. */
+int mcp_stereo_hypotheses(mcp_kf* src, const mcp_camera* src_cam, const double src_cam_from_world[12], int level, int n_cand, const mcp_int2* cand,
+                          const mcp_stereo_target* target, int cap, mcp_td_in* out, int* offsets);
+
 #ifdef __cplusplus
 }
 #endif

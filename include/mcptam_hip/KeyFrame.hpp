@@ -135,6 +135,31 @@ class KeyFrame {
 
   mcp_kf* handle() { return mpDev; }
 
+  // ---- MapMakerServerBase::AddStereoMapPoints of this (source) KeyFrame at one level in one submission (mcp_stereo_points,
+  // src/MapMakerServerBase.cc:452-496): the candidates vCandidates of the level against the ordered targets
+  struct StereoTarget { KeyFrame* pKF; mcp_camera cam; std::array<double, 12> cam_from_world; double one_pixel_angle; };
+  struct StereoResult {
+    std::vector<mcp_stereo_point> vPoints;   // creation order (target-major, candidate ascending)
+    std::vector<uint8_t> vKeep;              // vCandidates as the reference leaves it (thinned before the last target)
+    std::vector<uint8_t> vOutcome;           // targets x candidates, MCP_STEREO_*
+  };
+  StereoResult AddStereoPoints(const mcp_camera& cam, const double cam_from_world[12], int nLevel, const std::vector<mcp_int2>& vCandidates,
+                               const std::vector<mcp_stereo_meas>& vMeasurements, const std::vector<StereoTarget>& vTargets, int nLimit) {
+    std::vector<mcp_stereo_target> t(vTargets.size() + 1);
+    for (size_t j = 0; j < vTargets.size(); ++j) {
+      t[j].kf = vTargets[j].pKF->mpDev; t[j].cam = &vTargets[j].cam; t[j].one_pixel_angle = vTargets[j].one_pixel_angle;
+      for (int k = 0; k < 12; ++k) t[j].cam_from_world[k] = vTargets[j].cam_from_world[k];
+    }
+    const int n = (int)vCandidates.size();
+    StereoResult r;
+    r.vPoints.resize(n + 1); r.vKeep.resize(n + 1); r.vOutcome.resize(vTargets.size()*n + 1);
+    const int made = mcp_stereo_points(mpDev, &cam, cam_from_world, nLevel, n, vCandidates.data(), (int)vMeasurements.size(), vMeasurements.data(),
+                                       (int)vTargets.size(), t.data(), nLimit, n, r.vPoints.data(), r.vKeep.data(), r.vOutcome.data());
+    check(made);
+    r.vPoints.resize(made); r.vKeep.resize(n); r.vOutcome.resize(vTargets.size()*n);
+    return r;
+  }
+
   // ---- the cameras of a frame in one submission (the per-camera loops of Tracker::TrackFrame, src/Tracker.cc:303-318, and of
   // Tracker::TrackMap, :985-1030): results equal the per-camera calls bit for bit
   /// MakeKeyFrame_Lite on every KeyFrame of `kfs` (<= MCP_MAX_FRAME_CAMS, one device); on_device: `ims` are device pointers

@@ -18,6 +18,7 @@
 #include "img_kernels.h"
 #include "pvs_kernels.h"
 #include "track_map_kernels.h"
+#include "stereo_kernels.h"
 #include "ba_select.h"
 
 using namespace mcp;
@@ -95,6 +96,9 @@ struct mcp_kf {
   Buf<uint8_t> sbi_small; Buf<float> sbi_templ, sbi_jacs; bool has_sbi = false;
   Buf<uint8_t> sbi_last_small; Buf<float> sbi_last_templ, sbi_last_jacs; bool has_last_sbi = false;   // the SBI made before the current one (Tracker::mmpSBILastFrame)
   Buf<const float*> sbi_ptrs; Buf<double> sbi_out;
+  // mcp_stereo_points / mcp_stereo_hypotheses with this handle as the source: their scratch
+  Buf<StereoTargetDev> st_tab; Buf<mcp_int2> st_cand; Buf<mcp_stereo_meas> st_meas; Buf<uint8_t> st_alive, st_outcome; Buf<mcp_stereo_point> st_res;
+  Buf<int> st_counts; Buf<mcp_td_in> st_hyp; PinBuf<mcp_stereo_point> h_st_out; PinBuf<int> h_st_counts; PinBuf<uint8_t> h_st_keep, h_st_outcome;
   ~mcp_kf() { if (st) (void)hipStreamDestroy(st); if (h_info) (void)hipHostFree(h_info); if (ev) (void)hipEventDestroy(ev); }
   DevKfView view() const {
     DevKfView v;
@@ -1591,4 +1595,121 @@ const mcp_track_map_item* mcp_track_map_view(const mcp_map_points* m, int cam, i
   return k > 0 ? m->h_items.p + m->tm_first[cam] : nullptr;
 }
 
+// ---- MapMakerServerBase::AddStereoMapPoints of one source keyframe and level (stereo_kernels.h) ----------------------------------------------------
+static Se3 se3_of12(const double* a) { Se3 T; std::memcpy(T.R, a, 72); std::memcpy(T.t, a + 9, 24); return T; }
+static bool finite12(const double* a) { for (int k = 0; k < 12; ++k) if (!std::isfinite(a[k])) return false; return true; }
+static bool kf_live(const mcp_kf* k) { return k && kf_live_serial(k) != 0ull; }
+// the checks both entries share: source, level, candidates
+static int stereo_check_source(const char* what, mcp_kf* src, const mcp_camera* src_cam, const double* src_cfw, int level, int n_cand, const mcp_int2* cand) {
+  if (!kf_live(src)) return img_fail(std::string(what) + ": the source is not a live keyframe handle");
+  if (!src->has_image) return img_fail(std::string(what) + ": the source holds no frame");
+  if (!cam_ok(src_cam) || !src_cfw || !finite12(src_cfw)) return img_fail(std::string(what) + ": bad source camera or pose");
+  if (level < 0 || level >= MCP_LEVELS) return img_fail(std::string(what) + ": level outside 0..3");
+  if (n_cand < 0 || (n_cand > 0 && !cand)) return img_fail(std::string(what) + ": bad candidate list");
+  const Level& L = src->lev[level];
+  for (int i = 0; i < n_cand; ++i)
+    if (cand[i].x < 0 || cand[i].y < 0 || cand[i].x >= L.w || cand[i].y >= L.h) return img_fail(std::string(what) + ": a candidate outside the level image");
+  return 0;
+}
+static int stereo_target_dev(const char* what, const mcp_kf* src, const mcp_stereo_target& G, StereoTargetDev& D) {
+  if (!kf_live(G.kf)) return img_fail(std::string(what) + ": a target is not a live keyframe handle");
+  if (!G.kf->has_image) return img_fail(std::string(what) + ": a target holds no frame");
+  if (G.kf->device != src->device) return img_fail(std::string(what) + ": a target lives on another device than the source");
+  if (!cam_ok(G.cam) || !finite12(G.cam_from_world)) return img_fail(std::string(what) + ": bad target camera or pose");
+  if (!(G.one_pixel_angle > 0) || !std::isfinite(G.one_pixel_angle)) return img_fail(std::string(what) + ": one_pixel_angle must be positive and finite");
+  D.T = G.kf->view(); D.mask0 = G.kf->lev[0].has_mask ? G.kf->lev[0].mask.p : nullptr; D.cam = *G.cam;
+  D.cfw = se3_of12(G.cam_from_world); D.opa = G.one_pixel_angle;
+  return 0;
+}
+
+int mcp_stereo_points(mcp_kf* src, const mcp_camera* src_cam, const double src_cfw[12], int level, int n_cand, const mcp_int2* cand,
+                      int n_meas, const mcp_stereo_meas* meas, int n_targets, const mcp_stereo_target* targets, int limit,
+                      int cap, mcp_stereo_point* out, uint8_t* keep, uint8_t* outcome) {
+  static const char* W = "mcp_stereo_points";
+  if (stereo_check_source(W, src, src_cam, src_cfw, level, n_cand, cand)) return -1;
+  if (n_meas < 0 || (n_meas > 0 && !meas) || n_targets < 0 || (n_targets > 0 && !targets)) return img_fail("mcp_stereo_points: negative count or missing array");
+  if (cap < n_cand) return img_fail("mcp_stereo_points: cap < n_cand");
+  if (n_cand > 0 && (!out || !keep)) return img_fail("mcp_stereo_points: out and keep are needed");
+  for (int m = 0; m < n_meas; ++m)
+    if (!std::isfinite(meas[m].root_pos[0]) || !std::isfinite(meas[m].root_pos[1]) || std::fabs(meas[m].root_pos[0]) > 1e9 || std::fabs(meas[m].root_pos[1]) > 1e9)
+      return img_fail("mcp_stereo_points: a measurement with a non-finite or huge root position");
+  std::vector<StereoTargetDev> tab(std::max(n_targets, 1));
+  for (int t = 0; t < n_targets; ++t) if (stereo_target_dev(W, src, targets[t], tab[t])) return -1;
+  if (n_cand == 0) return 0;
+  ICK(hipSetDevice(src->device));
+  hipStream_t st = src->st;
+  const size_t nto = (size_t)std::max(n_targets, 1)*n_cand;
+  if (src->st_tab.alloc(std::max(n_targets, 1)) || src->st_cand.alloc(n_cand) || src->st_meas.alloc(std::max(n_meas, 1)) || src->st_alive.alloc(n_cand) ||
+      src->st_outcome.alloc(nto) || src->st_res.alloc(n_cand) || src->st_counts.alloc(n_targets + 1) || src->h_st_out.alloc(n_cand) ||
+      src->h_st_counts.alloc(n_targets + 1) || src->h_st_keep.alloc(n_cand) || src->h_st_outcome.alloc(nto)) return -1;
+  StereoSrcDev S; S.cam = *src_cam; S.cfw = se3_of12(src_cfw);
+  S.img = src->lev[level].img.p; S.w = src->lev[level].w; S.h = src->lev[level].h; S.level = level;
+  if (n_targets) ICK(hipMemcpyAsync(src->st_tab.p, tab.data(), sizeof(StereoTargetDev)*(size_t)n_targets, hipMemcpyHostToDevice, st));
+  ICK(hipMemcpyAsync(src->st_cand.p, cand, sizeof(mcp_int2)*(size_t)n_cand, hipMemcpyHostToDevice, st));
+  if (n_meas) ICK(hipMemcpyAsync(src->st_meas.p, meas, sizeof(mcp_stereo_meas)*(size_t)n_meas, hipMemcpyHostToDevice, st));
+  ICK(hipMemsetAsync(src->st_counts.p, 0, sizeof(int)*(size_t)(n_targets + 1), st));
+  const int nb = (n_cand + 255)/256;
+  hipLaunchKernelGGL(k_stereo_thin_meas, dim3(nb), dim3(256), 0, st, n_cand, (const mcp_int2*)src->st_cand.p, n_meas, (const mcp_stereo_meas*)src->st_meas.p,
+                     level, src->st_alive.p);
+  for (int j = 0; j < n_targets; ++j) {
+    if (j > 0)
+      hipLaunchKernelGGL(k_stereo_thin_new, dim3(nb), dim3(256), 0, st, j, n_cand, (const mcp_int2*)src->st_cand.p, level, (const int*)src->st_counts.p,
+                         (const mcp_stereo_point*)src->h_st_out.p, src->st_alive.p);
+    hipLaunchKernelGGL(k_stereo_walk, dim3(n_cand), dim3(64), 0, st, S, (const StereoTargetDev*)src->st_tab.p, j, n_cand, (const mcp_int2*)src->st_cand.p,
+                       (const uint8_t*)src->st_alive.p, src->st_res.p, src->st_outcome.p);
+    hipLaunchKernelGGL(k_stereo_commit, dim3(1), dim3(STEREO_COMMIT_NT), 0, st, j, n_cand, limit, (const uint8_t*)src->st_alive.p, src->st_outcome.p,
+                       (const mcp_stereo_point*)src->st_res.p, src->st_counts.p, src->h_st_out.p);
+  }
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(src->h_st_counts.p, src->st_counts.p, sizeof(int)*(size_t)(n_targets + 1), hipMemcpyDeviceToHost, st));
+  ICK(hipMemcpyAsync(src->h_st_keep.p, src->st_alive.p, (size_t)n_cand, hipMemcpyDeviceToHost, st));
+  if (outcome && n_targets) ICK(hipMemcpyAsync(src->h_st_outcome.p, src->st_outcome.p, (size_t)n_targets*n_cand, hipMemcpyDeviceToHost, st));
+  ICK(hipStreamSynchronize(st));
+  const int made = src->h_st_counts.p[n_targets];
+  if (made < 0 || made > n_cand) return img_fail("mcp_stereo_points: inconsistent device count");
+  std::memcpy(out, src->h_st_out.p, sizeof(mcp_stereo_point)*(size_t)made);
+  std::memcpy(keep, src->h_st_keep.p, (size_t)n_cand);
+  if (outcome && n_targets) std::memcpy(outcome, src->h_st_outcome.p, (size_t)n_targets*n_cand);
+  return made;
+}
+
+int mcp_stereo_hypotheses(mcp_kf* src, const mcp_camera* src_cam, const double src_cfw[12], int level, int n_cand, const mcp_int2* cand,
+                          const mcp_stereo_target* target, int cap, mcp_td_in* out, int* offsets) {
+  static const char* W = "mcp_stereo_hypotheses";
+  if (stereo_check_source(W, src, src_cam, src_cfw, level, n_cand, cand)) return -1;
+  if (!target || !offsets || cap < 0) return img_fail("mcp_stereo_hypotheses: bad arguments");
+  StereoTargetDev D;
+  if (stereo_target_dev(W, src, *target, D)) return -1;
+  offsets[0] = 0;
+  if (n_cand == 0) return 0;
+  ICK(hipSetDevice(src->device));
+  hipStream_t st = src->st;
+  if (src->st_cand.alloc(n_cand) || src->st_counts.alloc(n_cand + 1) || src->h_st_counts.alloc(n_cand + 1)) return -1;
+  const Se3 Ts = se3_of12(src_cfw);
+  const int nb = (n_cand + 255)/256;
+  ICK(hipMemcpyAsync(src->st_cand.p, cand, sizeof(mcp_int2)*(size_t)n_cand, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_stereo_hyp_count, dim3(nb), dim3(256), 0, st, *src_cam, Ts, D.cfw, D.opa, level, n_cand, (const mcp_int2*)src->st_cand.p, src->st_counts.p);
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(src->h_st_counts.p, src->st_counts.p, sizeof(int)*(size_t)n_cand, hipMemcpyDeviceToHost, st));
+  ICK(hipStreamSynchronize(st));
+  long long total = 0;
+  for (int i = 0; i < n_cand; ++i) {
+    total += src->h_st_counts.p[i];
+    if (total > 0x7fffffff) return img_fail("mcp_stereo_hypotheses: more than INT_MAX hypotheses");
+    offsets[i + 1] = (int)total;
+  }
+  if (!out) return (int)total;
+  if (total > cap) return img_fail("mcp_stereo_hypotheses: cap is smaller than the number of hypotheses");
+  if (total == 0) return 0;
+  if (src->st_hyp.alloc((size_t)total)) return -1;
+  ICK(hipMemcpyAsync(src->st_counts.p, offsets, sizeof(int)*(size_t)(n_cand + 1), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_stereo_hyp_fill, dim3(nb), dim3(256), 0, st, *src_cam, Ts, D.cfw, D.opa, level, n_cand, (const mcp_int2*)src->st_cand.p,
+                     (const int*)src->st_counts.p, (const mcp_kf*)src, src->st_hyp.p);
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(out, src->st_hyp.p, sizeof(mcp_td_in)*(size_t)total, hipMemcpyDeviceToHost, st));
+  ICK(hipStreamSynchronize(st));
+  return (int)total;
+}
+
 }  // extern "C"
+

@@ -46,7 +46,7 @@ IMG_SYMBOLS = [
     "mcp_patch_sequences", "mcp_track_frame", "mcp_track_frame_view", "mcp_track_pose_update_m", "mcp_track_pose_refine_m", "mcp_track_pose_refine_sharded_m", "mcp_track_pose_refine", "mcp_track_pose_refine_sharded", "mcp_kf_make_sbi", "mcp_kf_get_sbi", "mcp_sbi_score", "mcp_sbi_iterate", "mcp_sbi_iterate_last", "mcp_sbi_se3_from_se2",
     "mcp_map_points_create", "mcp_map_points_destroy", "mcp_map_points_rows", "mcp_map_points_resize", "mcp_map_points_set", "mcp_map_points_update", "mcp_track_find_pvs",
     "mcp_track_find_pvs_view", "mcp_map_points_set_source", "mcp_map_points_update_source", "mcp_map_points_get_states", "mcp_track_map",
-    "mcp_track_map_view", "mcp_mix64", "mcp_track_shuffle_key",
+    "mcp_track_map_view", "mcp_mix64", "mcp_track_shuffle_key", "mcp_stereo_points", "mcp_stereo_hypotheses",
 ]
 _BOUND = False
 

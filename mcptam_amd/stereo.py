@@ -1,0 +1,359 @@
+"""MapMakerServerBase::AddStereoMapPoints of one source keyframe and level on the GPU (include/mcp_img.h mcp_stereo_points), its hypothesis
+export (mcp_stereo_hypotheses), and numpy restatements of the pieces the device runs -- ThinCandidates, the epipolar arc, the ambiguity rules,
+ReprojectPoint -- with which the tests compose the same result from existing calls.  src/MapMakerServerBase.cc:123-143, 411-496, 604-918."""
+import ctypes
+import math
+
+import numpy as np
+
+from . import chain_bundle as _cb
+from . import keyframe as K
+
+THINNED, NO_ARC, NO_MATCH, TOO_MANY, INDEX_FAR, NO_SUBPIX, CREATED, PAST_LIMIT = range(1, 9)
+OUTCOME_NAMES = {THINNED: "THINNED", NO_ARC: "NO_ARC", NO_MATCH: "NO_MATCH", TOO_MANY: "TOO_MANY", INDEX_FAR: "INDEX_FAR", NO_SUBPIX: "NO_SUBPIX",
+                 CREATED: "CREATED", PAST_LIMIT: "PAST_LIMIT"}
+STEREO_SYMBOLS = ["mcp_stereo_points", "mcp_stereo_hypotheses"]
+
+
+class StereoTarget(ctypes.Structure):
+    _fields_ = [("kf", ctypes.c_void_p), ("cam", ctypes.c_void_p), ("cam_from_world", ctypes.c_double * 12), ("one_pixel_angle", ctypes.c_double)]
+
+
+class StereoMeas(ctypes.Structure):
+    _fields_ = [("root_pos", ctypes.c_double * 2), ("level", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
+class StereoPoint(ctypes.Structure):
+    _fields_ = [("candidate", ctypes.c_int), ("target", ctypes.c_int), ("hypothesis", ctypes.c_int), ("score", ctypes.c_int),
+                ("world_pos", ctypes.c_double * 3), ("root_pos", ctypes.c_double * 2), ("target_pos", ctypes.c_double * 2),
+                ("center_nc", ctypes.c_double * 3), ("one_right_nc", ctypes.c_double * 3), ("one_down_nc", ctypes.c_double * 3),
+                ("pixel_right_w", ctypes.c_double * 3), ("pixel_down_w", ctypes.c_double * 3)]
+
+
+STEREO_POINT_DTYPE = np.dtype([("candidate", "i4"), ("target", "i4"), ("hypothesis", "i4"), ("score", "i4"), ("world_pos", "f8", 3),
+                               ("root_pos", "f8", 2), ("target_pos", "f8", 2), ("center_nc", "f8", 3), ("one_right_nc", "f8", 3),
+                               ("one_down_nc", "f8", 3), ("pixel_right_w", "f8", 3), ("pixel_down_w", "f8", 3)], align=True)
+STEREO_MEAS_DTYPE = np.dtype([("root_pos", "f8", 2), ("level", "i4"), ("pad_", "i4")], align=True)
+TD_IN_DTYPE = np.dtype([("world_pos", "f8", 3), ("pixel_right_w", "f8", 3), ("pixel_down_w", "f8", 3), ("source_kf", "u8"), ("source_level", "i4"),
+                        ("center_x", "i4"), ("center_y", "i4"), ("fixed", "i4")], align=True)
+assert STEREO_POINT_DTYPE.itemsize == ctypes.sizeof(StereoPoint)
+assert STEREO_MEAS_DTYPE.itemsize == ctypes.sizeof(StereoMeas)
+assert TD_IN_DTYPE.itemsize == ctypes.sizeof(K.TdIn)
+_BOUND = False
+
+
+def lib():
+    global _BOUND
+    L = K.lib()
+    if not _BOUND:
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        L.mcp_stereo_points.argtypes = [vp, vp, vp, ip, ip, vp, ip, vp, ip, vp, ip, ip, vp, vp, vp]
+        L.mcp_stereo_points.restype = ip
+        L.mcp_stereo_hypotheses.argtypes = [vp, vp, vp, ip, ip, vp, vp, ip, vp, vp]
+        L.mcp_stereo_hypotheses.restype = ip
+        _BOUND = True
+    return L
+
+
+def _pose12(pose):
+    R, t = pose
+    return np.ascontiguousarray(np.concatenate([np.asarray(R, dtype=np.float64).reshape(9), np.asarray(t, dtype=np.float64).reshape(3)]))
+
+
+def _targets(targets):
+    """targets: list of (keyframe, camera, CamFromWorld (R, t)[, one_pixel_angle]) -> ctypes table + keep-alive"""
+    cams = [t[1].to_struct() for t in targets]
+    tab = (StereoTarget * max(len(targets), 1))()
+    for i, t in enumerate(targets):
+        tab[i].kf = t[0]._h if t[0] is not None else None
+        tab[i].cam = ctypes.addressof(cams[i])
+        p = _pose12(t[2])
+        for k in range(12):
+            tab[i].cam_from_world[k] = p[k]
+        tab[i].one_pixel_angle = float(t[3]) if len(t) > 3 else t[1].one_pixel_angle()
+    return tab, cams
+
+
+def _cand(cand):
+    return np.ascontiguousarray(np.asarray(cand, dtype=np.int32).reshape(-1, 2))
+
+
+def make_meas(root_pos, levels):
+    m = np.zeros(len(levels), dtype=STEREO_MEAS_DTYPE)
+    m["root_pos"] = np.asarray(root_pos, dtype=np.float64).reshape(-1, 2)
+    m["level"] = levels
+    return m
+
+
+def stereo_points(src, src_cam, src_pose, level, cand, targets, limit=1 << 30, meas=None, outcomes=True, cap=None):
+    """mcp_stereo_points.  Returns (points: STEREO_POINT_DTYPE array in creation order, keep mask (bool, n_cand), outcome (n_targets x n_cand uint8 or
+    None))."""
+    L = lib()
+    c = _cand(cand)
+    n = len(c)
+    meas = make_meas(np.zeros((0, 2)), []) if meas is None else meas
+    tab, keep_cams = _targets(targets)
+    cs = src_cam.to_struct()
+    sp = _pose12(src_pose)
+    out = np.zeros(max(n, 1), dtype=STEREO_POINT_DTYPE)
+    keep = np.zeros(max(n, 1), dtype=np.uint8)
+    oc = np.zeros((max(len(targets), 1), max(n, 1)), dtype=np.uint8) if outcomes else None
+    rc = L.mcp_stereo_points(src._h, ctypes.addressof(cs), sp.ctypes.data, int(level), n, c.ctypes.data, len(meas), meas.ctypes.data, len(targets),
+                             ctypes.addressof(tab), int(limit), n if cap is None else int(cap), out.ctypes.data, keep.ctypes.data,
+                             oc.ctypes.data if oc is not None else None)
+    if rc < 0:
+        raise RuntimeError("mcp_stereo_points failed: " + _cb.last_error())
+    del keep_cams
+    if oc is not None:
+        oc = oc[:len(targets), :n]
+    return out[:rc].copy(), keep[:n].astype(bool), oc
+
+
+def stereo_hypotheses(src, src_cam, src_pose, level, cand, target):
+    """mcp_stereo_hypotheses: (TD_IN_DTYPE array of every hypothesis, offsets (n_cand + 1))."""
+    L = lib()
+    c = _cand(cand)
+    n = len(c)
+    tab, keep_cams = _targets([target])
+    cs = src_cam.to_struct()
+    sp = _pose12(src_pose)
+    off = np.zeros(n + 1, dtype=np.int32)
+    tot = L.mcp_stereo_hypotheses(src._h, ctypes.addressof(cs), sp.ctypes.data, int(level), n, c.ctypes.data, ctypes.addressof(tab), 0, None, off.ctypes.data)
+    if tot < 0:
+        raise RuntimeError("mcp_stereo_hypotheses failed: " + _cb.last_error())
+    out = np.zeros(max(tot, 1), dtype=TD_IN_DTYPE)
+    if tot > 0:
+        rc = L.mcp_stereo_hypotheses(src._h, ctypes.addressof(cs), sp.ctypes.data, int(level), n, c.ctypes.data, ctypes.addressof(tab), tot,
+                                     out.ctypes.data, off.ctypes.data)
+        if rc != tot:
+            raise RuntimeError("mcp_stereo_hypotheses failed: " + _cb.last_error())
+    del keep_cams
+    return out[:tot], off
+
+
+# ---- numpy restatements (test infrastructure) ------------------------------------------------------------------------------------------------
+def level_zero_pos(c, level):
+    """LevelZeroPos (include/mcptam/LevelHelpers.h:61-82)"""
+    return (np.asarray(c, dtype=np.float64) + 0.5) * (1 << level) - 0.5
+
+
+def ir_rounded(v):
+    """CVD::ir_rounded: half away from zero.  [3P-memory] restated from memory of libCVD (v > 0 ? v + 0.5 : v - 0.5, then truncated), not checked
+    against its source here."""
+    v = np.asarray(v, dtype=np.float64)
+    return np.trunc(np.where(v > 0.0, v + 0.5, v - 0.5)).astype(np.int64)
+
+
+def thin_candidates(cand, level, meas_root=(), meas_level=(), created_root=()):
+    """ThinCandidates (:411-446): keep mask of the candidates (level positions) further than 10 px from every busy position -- measurements at
+    level or level + 1 (v2RootPos / LevelScale, ir_rounded) and the SRC_ROOT positions of points created since (level `level`)."""
+    c = np.asarray(cand, dtype=np.int64).reshape(-1, 2)
+    sc = float(1 << level)
+    busy = [ir_rounded(np.asarray(r, dtype=np.float64) / sc) for r, l in zip(meas_root, meas_level) if l == level or l == level + 1]
+    busy += [ir_rounded(np.asarray(r, dtype=np.float64) / sc) for r in created_root]
+    keep = np.ones(len(c), dtype=bool)
+    for b in busy:
+        d = c - b
+        keep &= (d * d).sum(axis=1) >= 100
+    return keep
+
+
+def _unit(v):
+    return v / math.sqrt(float(v @ v))
+
+
+def pixel_vectors(pose_src, center, right, down, world):
+    """MapPoint::RefreshPixelVectors (src/MapPoint.cc:62-87), normal (0, 0, -1); world: (n, 3) -> (pixel_right_w, pixel_down_w), (n, 3) each"""
+    Rs, ts = pose_src
+    w = np.atleast_2d(world)
+    h = np.abs(-(w @ Rs.T + ts)[:, 2])
+    c = center[None, :] * h[:, None] / abs(center[2])
+    r = right[None, :] * h[:, None] / abs(right[2]) - c
+    d = down[None, :] * h[:, None] / abs(down[2]) - c
+    return r @ Rs, d @ Rs
+
+
+def probe(cam_src, level, c):
+    """the probe MapPoint's root position and NC vectors (:726-738)"""
+    s = 1 << level
+    root = level_zero_pos(c, level)
+    vs = cam_src.unproject(np.stack([root, root + [s, 0.0], root + [0.0, s]]))
+    return root, _unit(vs[0]), _unit(vs[1]), _unit(vs[2])
+
+
+def arc(cam_src, pose_src, pose_tgt, one_pixel_angle, level, c):
+    """The hypotheses of AddPointEpipolar (:611-723) for candidate c: dict(n, world (n x 3), tc (n x 3), pixel_right_w, pixel_down_w, root,
+    center, right, down); n = 0 when the v3BetweenEndpoints guard or a non-finite step count stops it."""
+    Rs, ts = pose_src
+    Rt, tt = pose_tgt
+    s = 1 << level
+    root, cen, rig, dow = probe(cam_src, level, c)
+    ray = cam_src.unproject(root)[0]
+    dirn = Rt @ (Rs.T @ ray)
+    cc_tc = Rt @ (-(Rs.T @ ts)) + tt
+    cc_sc = Rs @ (-(Rt.T @ tt)) + ts
+    sep = math.sqrt(float(cc_sc @ cc_sc))
+    res = dict(n=0, world=np.zeros((0, 3)), tc=np.zeros((0, 3)), pixel_right_w=np.zeros((0, 3)), pixel_down_w=np.zeros((0, 3)), root=root,
+               center=cen, right=rig, down=dow, step=0.0)
+    if sep == 0.0:                    # the device divides by zero here and gets NaN all the way to the step count: no hypotheses
+        return res
+    src_angle = math.acos(float(cc_sc @ ray) / sep)
+    start = sep * math.sin(math.pi - src_angle - math.pi / 3) / math.sin(math.pi / 3)
+    end = sep * math.sin(math.pi - src_angle - 0.05) / math.sin(0.05)
+    start = max(start, 0.2)
+    RS, RE = cc_tc + start * dirn, cc_tc + end * dirn
+    a, b = _unit(RS), _unit(RE)
+    res.update(start=start, end=end)
+    if (a - b) @ (a - b) < 1e-8:
+        return res
+    nrm = _unit(np.cross(a, b))
+    J = np.cross(nrm, a)
+    max_angle = math.acos(float(a @ b))
+    q = math.ceil(max_angle / (one_pixel_angle * s * 3)) if math.isfinite(max_angle) else float("nan")
+    if not (-2147483648.0 <= q <= 2147483646.0):
+        return res
+    n_steps = int(q)
+    step = max_angle / n_steps
+    rs = np.array([a @ RS, J @ RS])
+    rd = np.array([a @ RE, J @ RE]) - rs
+    rd = rd / math.sqrt(float(rd @ rd))
+    ang = np.arange(n_steps + 1) * step
+    cs, sn = np.cos(ang), np.sin(ang)
+    alpha = (rs[0] * sn - rs[1] * cs) / (rd[1] * cs - rd[0] * sn)
+    tc = RS[None, :] + alpha[:, None] * dirn[None, :]
+    world = (tc - tt) @ Rt
+    pr, pd = pixel_vectors(pose_src, cen, rig, dow, world)
+    res.update(n=n_steps + 1, world=world, tc=tc, pixel_right_w=pr, pixel_down_w=pd, step=step)
+    return res
+
+
+def select_matches(matches):
+    """The ambiguity rules of :798-825 as the code has them.  matches: [(score, hypothesis, coarse_pos)] in hypothesis order.  Returns
+    (outcome code or 0, kept matches in sorted order).  Python's sort is stable (libstdc++'s std::sort is a stable insertion sort up to 16 entries)."""
+    if not matches:
+        return NO_MATCH, []
+    best = min(m[0] for m in matches)
+    n_best = next(m[1] for m in matches if m[0] == best)
+    srt = sorted(matches, key=lambda m: m[0])
+    n_resize = 1 + sum(1 for m in srt[1:] if m[0] > best * 0.9)
+    if n_resize > 3:
+        return TOO_MANY, []
+    kept = srt[:n_resize]
+    if any(abs(m[1] - n_best) > 1 for m in kept[1:]):
+        return INDEX_FAR, []
+    return 0, kept
+
+
+def reproject_point(pose_ab, vA, vB):
+    """ReprojectPoint (:123-143): point in frame B from the rays vA (frame A) and vB (frame B), se3AfromB = pose_ab"""
+    R, t = pose_ab
+    P = np.hstack([R, np.asarray(t).reshape(3, 1)])
+    A = np.zeros((4, 4))
+    A[0] = [-vB[2], 0.0, vB[0], 0.0]
+    A[1] = [0.0, -vB[2], vB[1], 0.0]
+    A[2] = vA[0] * P[2] - vA[2] * P[0]
+    A[3] = vA[1] * P[2] - vA[2] * P[1]
+    v = np.linalg.svd(A)[2][3].copy()
+    if v[3] == 0.0:
+        v[3] = 0.00001
+    return v[:3] / v[3]
+
+
+def triangulate(cam_src, cam_tgt, pose_src, pose_tgt, root, sub):
+    """:857-860: world position of the new point"""
+    Rs, ts = pose_src
+    Rt, tt = pose_tgt
+    Rab = Rs @ Rt.T
+    tab = ts - Rab @ tt
+    xb = reproject_point((Rab, tab), cam_src.unproject(root)[0], cam_tgt.unproject(sub)[0])
+    return Rt.T @ (xb - tt)
+
+
+def hypothesis_points(hyp, off, i, src, src_oracle=None):
+    """point dicts (keyframe.patch_sequences / oracle_patch_sequences) of candidate i's hypotheses from a stereo_hypotheses export"""
+    pts = []
+    for h in hyp[off[i]:off[i + 1]]:
+        pts.append(dict(world_pos=h["world_pos"], pixel_right_w=h["pixel_right_w"], pixel_down_w=h["pixel_down_w"], source_kf=src,
+                        source_kf_oracle=src_oracle, source_level=int(h["source_level"]), center=(int(h["center_x"]), int(h["center_y"])), fixed=0))
+    return pts
+
+
+def compose_target(patch_sequences, tgt, cam_tgt, pose_tgt, hyp, off, idx, src, src_oracle=None):
+    """One target of AddStereoMapPoints as the composition of existing calls for the candidates idx: their hypotheses (a stereo_hypotheses export
+    hyp / off) as one MCP_PF_EPI_COARSE sequence each with fresh finders, select_matches, the kept matches as MCP_PF_EPI_REFINE sequences on the
+    returned states.  patch_sequences: keyframe.patch_sequences, or the oracle's with tgt = its keyframe.  Returns {candidate: (code, hypothesis,
+    score, sub-pixel position or None)}."""
+    I = (np.eye(3), np.zeros(3))
+    targets = [(tgt, cam_tgt, pose_tgt, I)]
+    seqs, pts = [], {}
+    for i in idx:
+        pts[i] = hypothesis_points(hyp, off, i, src, src_oracle)
+        seqs.append([dict(point=p, point_key=1, target=0) for p in pts[i]])
+    res = {}
+    if not seqs:
+        return res
+    states = K.new_pf_states(len(seqs))
+    co = patch_sequences(K.PF_EPI_COARSE, targets, seqs, states, 3)
+    pos, kept = 0, {}
+    for q, i in enumerate(idx):
+        n = len(seqs[q])
+        o = co[pos:pos + n]
+        pos += n
+        if off[i + 1] == off[i]:
+            res[i] = (NO_ARC, -1, 0, None)
+            continue
+        m = [(int(o[h]["score"]), h, o[h]["found_pos"].copy()) for h in range(n) if o[h]["found"]]
+        code, k = select_matches(m)
+        if code:
+            res[i] = (code, -1, 0, None)
+        else:
+            kept[q] = k
+    ref_seqs = [[dict(point=pts[idx[q]][m[1]], point_key=1, target=0, start_pos=m[2]) for m in kept.get(q, [])] for q in range(len(idx))]
+    ro = patch_sequences(K.PF_EPI_REFINE, targets, ref_seqs, states, 3, 10)
+    pos = 0
+    for q, i in enumerate(idx):
+        n = len(ref_seqs[q])
+        o = ro[pos:pos + n]
+        pos += n
+        if q not in kept:
+            continue
+        win = next((k for k in range(n) if o[k]["found"]), None)
+        if win is None:
+            res[i] = (NO_SUBPIX, -1, 0, None)
+        else:
+            m = kept[q][win]
+            res[i] = (CREATED, m[1], m[0], o[win]["found_pos"].copy())
+    return res
+
+
+def compose(patch_sequences, src, src_cam, src_pose, level, cand, targets, limit=1 << 30, meas_root=(), meas_level=(), src_oracle=None,
+            search_kfs=None):
+    """AddStereoMapPoints of one source and level composed from existing calls: numpy ThinCandidates before every target, stereo_hypotheses of the
+    survivors, compose_target, the reference's nLimit loop (:486-493) and triangulate.  targets: (keyframe, camera, CamFromWorld[, one_pixel_angle])
+    as for stereo_points; search_kfs: the keyframes patch_sequences searches in (default: the targets' own).  Returns (list of created point dicts in
+    creation order, keep mask)."""
+    cand = np.asarray(cand, dtype=np.int64).reshape(-1, 2)
+    alive = thin_candidates(cand, level, meas_root, meas_level)
+    keep = alive.copy()
+    made, num = [], 0
+    for j, t in enumerate(targets):
+        new = [p["root_pos"] for p in made if p["target"] == j - 1]
+        if new:
+            alive &= thin_candidates(cand, level, created_root=new)
+        keep = alive.copy()
+        idx = np.nonzero(alive)[0]
+        if len(idx) == 0:
+            continue
+        hyp, off = stereo_hypotheses(src, src_cam, src_pose, level, cand[idx], t)
+        sk = t[0] if search_kfs is None else search_kfs[j]
+        res = compose_target(patch_sequences, sk, t[1], t[2], hyp, off, list(range(len(idx))), src, src_oracle)
+        for q, i in enumerate(idx):
+            code, h, score, sub = res[q]
+            if code == CREATED:
+                root = level_zero_pos(cand[i], level)
+                made.append(dict(candidate=int(i), target=j, hypothesis=h, score=score, root_pos=root, target_pos=sub,
+                                 world_pos=triangulate(src_cam, t[1], src_pose, t[2], root, sub)))
+                num += 1
+            if num >= limit:
+                break
+    return made, keep

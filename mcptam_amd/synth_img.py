@@ -50,6 +50,24 @@ def make_tracking_scene(seed=DEFAULT_SEED, size=(640, 480), depth=6.0):
     return dict(cam=cam, imgA=imgA, imgB=imgB, poseA=(RA, tA), poseB=(RB, tB), depth=depth, tex=tex)
 
 
+def make_stereo_scene(seed=DEFAULT_SEED, size=(640, 480), depth=6.0):
+    """One source view and four target views of the textured plane for MapMakerServerBase::AddStereoMapPoints, with baselines of 0.45 - 0.7 m:
+    at 6 m the true depth then lies inside the epipolar arc's [start, end] (end ~ baseline * sin(angle + 0.05) / sin 0.05), which the 0.15 m
+    pair of make_tracking_scene does not reach.  Poses are CamFromWorld (R, t); the source is the world frame."""
+    cam = TaylorCamera(DEFAULT_CAM_PARAMS[:4] + (size[0] / 2.0, size[1] / 2.0) + DEFAULT_CAM_PARAMS[6:], size, size, size)
+    tex = make_texture(seed)
+    src = (np.eye(3), np.zeros(3))
+    centres = [(0.6, 0.02, 0.0), (-0.5, 0.25, 0.05), (0.3, -0.55, -0.1), (-0.45, -0.3, 0.1)]
+    turns = [(0.004, 0.05, 0.01), (-0.02, -0.04, -0.008), (0.05, 0.02, 0.005), (0.03, -0.04, 0.0)]
+    targets = []
+    for c, w in zip(centres, turns):
+        R = so3_exp(np.array(w))
+        targets.append((R, -R @ np.array(c)))
+    img_src = render_plane(cam, src[0], src[1], tex, depth)
+    imgs = [render_plane(cam, R, t, tex, depth) for R, t in targets]
+    return dict(cam=cam, img_src=img_src, imgs=imgs, pose_src=src, poses=targets, depth=depth, tex=tex)
+
+
 def make_map_points(cam, kf, kf_oracle, pose, depth, per_level=(400, 300, 200, 100), normal_c=(0.0, 0.0, -1.0)):
     """Map points at the FAST candidates of keyframe `kf` (pose = CamFromWorld of that keyframe),
     with the patch vectors of MapPoint::RefreshPixelVectors (/root/reference/src/MapPoint.cc:62-87)."""

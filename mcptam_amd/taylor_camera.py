@@ -166,6 +166,13 @@ class TaylorCamera:
         v = np.stack([d[:, 0], d[:, 1], polyval_low_first(self.poly, rho)], axis=1)
         return v / np.linalg.norm(v, axis=1, keepdims=True)
 
+    # TaylorCamera::OnePixelAngle (mdOnePixelAngle, TaylorCamera.cc:194-196): the angle between the rays through the image centre and one pixel
+    # diagonally from it, over sqrt(2)
+    def one_pixel_angle(self):
+        c = self.image_size / 2
+        a, b = self.unproject(np.stack([c, c + 1.0]))
+        return math.acos(float(a @ b)) / math.sqrt(2.0)
+
     def to_struct(self):
         s = McpCamera()
         for i in range(9):

@@ -319,3 +319,108 @@ void MapMakerServerBase::ReFindFromFailureQueue()
     ReFindBatch(vPairs, false);
   }
 }
+
+// ---- AddStereoMapPoints (:452-496) with one mcp_stereo_points call per source keyframe and level: ThinCandidates before every target, the arc,
+// both PatchFinder loops, the selection, ReprojectPoint and the nLimit counter run on the device in one submission (include/mcp_img.h).  The
+// host keeps what needs the map: ClosestKeyFramesWithinDist, the mbBad / CrossCamera / sbOnlyFirstCameraGeneratesPoints skips (a skipped target
+// neither thins nor creates), and building the MapPoints and Measurements from the records, in the reference's creation order.
+void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, int nLimit, double dDistThresh, KeyFrameRegion region)
+{
+  static gvar3<int> gvnCrossCamera("CrossCamera", 1, HIDDEN|SILENT);
+  for(KeyFramePtrMap::iterator it = mkfSrc.mmpKeyFrames.begin(); it != mkfSrc.mmpKeyFrames.end(); it++)
+  {
+    if(MapMakerServerBase::sbOnlyFirstCameraGeneratesPoints && it != mkfSrc.mmpKeyFrames.begin())
+      break;
+    KeyFrame& kfSrc = *(it->second);
+    Level& level = kfSrc.maLevels[nLevel];
+    const double dDistThreshUsed = dDistThresh < 0 ? 1000 : dDistThresh;
+    std::vector<KeyFrame*> vpAll = ClosestKeyFramesWithinDist(kfSrc, dDistThreshUsed, MapMakerServerBase::snMaxTriangulationKFs, region);
+    std::vector<KeyFrame*> vpTargets;
+    for(unsigned j = 0; j < vpAll.size(); ++j)
+    {
+      if(vpAll[j]->mpParent->mbBad)
+        continue;
+      if(!*gvnCrossCamera && kfSrc.mCamName != vpAll[j]->mCamName)     // AddPointEpipolar's first check: the target creates nothing
+        continue;
+      vpTargets.push_back(vpAll[j]);
+    }
+    TaylorCamera& cameraSrc = mmCameraModels[kfSrc.mCamName];
+    const mcp_camera camSrc = mcptam_hip::CameraExport::Make(cameraSrc);
+    std::vector<mcp_camera> vCams(vpTargets.size());
+    std::vector<mcp_stereo_target> vTargets(vpTargets.size());
+    for(unsigned j = 0; j < vpTargets.size(); ++j)
+    {
+      TaylorCamera& cameraTarget = mmCameraModels[vpTargets[j]->mCamName];
+      vCams[j] = mcptam_hip::CameraExport::Make(cameraTarget);
+      ROS_ASSERT(vpTargets[j]->mpDev);
+      vTargets[j].kf = vpTargets[j]->mpDev;
+      vTargets[j].cam = &vCams[j];
+      ToArray12(vpTargets[j]->mse3CamFromWorld, vTargets[j].cam_from_world);
+      vTargets[j].one_pixel_angle = cameraTarget.OnePixelAngle();
+    }
+    std::vector<mcp_int2> vCand(level.vCandidates.size());
+    for(unsigned i = 0; i < vCand.size(); ++i)
+    {
+      vCand[i].x = level.vCandidates[i].irLevelPos.x;
+      vCand[i].y = level.vCandidates[i].irLevelPos.y;
+    }
+    std::vector<mcp_stereo_meas> vMeas;
+    for(MeasPtrMap::iterator itm = kfSrc.mmpMeasurements.begin(); itm != kfSrc.mmpMeasurements.end(); ++itm)
+    {
+      mcp_stereo_meas m;
+      m.root_pos[0] = itm->second->v2RootPos[0];
+      m.root_pos[1] = itm->second->v2RootPos[1];
+      m.level = itm->second->nLevel;
+      m.pad_ = 0;
+      vMeas.push_back(m);
+    }
+    double adSrc[12];
+    ToArray12(kfSrc.mse3CamFromWorld, adSrc);
+    const int n = (int)vCand.size();
+    std::vector<mcp_stereo_point> vOut(n + 1);
+    std::vector<uint8_t> vKeep(n + 1);
+    ROS_ASSERT(kfSrc.mpDev);
+    const int nMade = mcp_stereo_points(kfSrc.mpDev, &camSrc, adSrc, nLevel, n, n ? &vCand[0] : NULL, (int)vMeas.size(), vMeas.empty() ? NULL : &vMeas[0],
+                                        (int)vTargets.size(), vTargets.empty() ? NULL : &vTargets[0], nLimit, n, &vOut[0], &vKeep[0], NULL);
+    if(nMade < 0)
+    {
+      ROS_FATAL_STREAM("MapMakerServerBase::AddStereoMapPoints: "<<mcp_last_error());
+      ros::shutdown();
+      return;
+    }
+    for(int k = 0; k < nMade; ++k)       // :862-914, in creation order
+    {
+      const mcp_stereo_point& r = vOut[k];
+      KeyFrame& kfTarget = *vpTargets[r.target];
+      MapPoint* pPointNew = new MapPoint;
+      pPointNew->mv3WorldPos = makeVector(r.world_pos[0], r.world_pos[1], r.world_pos[2]);
+      pPointNew->mpPatchSourceKF = &kfSrc;
+      pPointNew->mnSourceLevel = nLevel;
+      pPointNew->mv3Normal_NC = makeVector(0, 0, -1);
+      pPointNew->mirCenter = level.vCandidates[r.candidate].irLevelPos;
+      pPointNew->mv3Center_NC = makeVector(r.center_nc[0], r.center_nc[1], r.center_nc[2]);
+      pPointNew->mv3OneRightFromCenter_NC = makeVector(r.one_right_nc[0], r.one_right_nc[1], r.one_right_nc[2]);
+      pPointNew->mv3OneDownFromCenter_NC = makeVector(r.one_down_nc[0], r.one_down_nc[1], r.one_down_nc[2]);
+      pPointNew->mv3PixelRight_W = makeVector(r.pixel_right_w[0], r.pixel_right_w[1], r.pixel_right_w[2]);     // RefreshPixelVectors, on the device
+      pPointNew->mv3PixelDown_W = makeVector(r.pixel_down_w[0], r.pixel_down_w[1], r.pixel_down_w[2]);
+      Measurement* pMeasSrc = new Measurement;
+      pMeasSrc->eSource = Measurement::SRC_ROOT;
+      pMeasSrc->v2RootPos = makeVector(r.root_pos[0], r.root_pos[1]);
+      pMeasSrc->nLevel = nLevel;
+      pMeasSrc->bSubPix = true;
+      Measurement* pMeasTarget = new Measurement;
+      *pMeasTarget = *pMeasSrc;
+      pMeasTarget->eSource = Measurement::SRC_EPIPOLAR;
+      pMeasTarget->v2RootPos = makeVector(r.target_pos[0], r.target_pos[1]);
+      kfSrc.AddMeasurement(pPointNew, pMeasSrc);
+      kfTarget.AddMeasurement(pPointNew, pMeasTarget);
+      mMap.mlpPoints.push_back(pPointNew);
+      mlpNewQueue.push_back(pPointNew);
+    }
+    std::vector<Candidate> vKept;                // ThinCandidates as the reference leaves it: before the last target
+    for(int i = 0; i < n; ++i)
+      if(vKeep[i])
+        vKept.push_back(level.vCandidates[i]);
+    level.vCandidates = vKept;
+  }
+}
