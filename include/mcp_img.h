@@ -458,6 +458,74 @@ int mcp_stereo_points(mcp_kf* src, const mcp_camera* src_cam, const double src_c
 int mcp_stereo_hypotheses(mcp_kf* src, const mcp_camera* src_cam, const double src_cam_from_world[12], int level, int n_cand, const mcp_int2* cand,
                           const mcp_stereo_target* target, int cap, mcp_td_in* out, int* offsets);
 
+/* ---- BundleAdjusterMulti::AdjustAndUpdate: the write-back of an adjustment into the table ---------- src/BundleAdjusterMulti.cc:286-334
+ * (the same in BundleAdjusterSingle.cc:175-215 and BundleAdjusterCalib.cc).  After a successful adjustment the reference (1) refreshes every
+ * keyframe's mse3CamFromWorld, (2) sets every point's mv3WorldPos from the bundle and calls MapPoint::RefreshPixelVectors (src/MapPoint.cc:62-87),
+ * (3) calls RefreshSceneDepthRobust of every keyframe (src/KeyFrame.cc:547-645).  mcp_ba_write_back does the three steps on the device, from the
+ * solver's state to the table's rows, in one submission with one wait.
+ *
+ * RefreshPixelVectors needs the patch rays of a point -- mv3Center_NC, mv3OneRightFromCenter_NC, mv3OneDownFromCenter_NC, set once when the
+ * point is created (mcp_stereo_point returns them); mv3Normal_NC is (0, 0, -1) everywhere.  They are a column of the table: */
+/* rays of rows first .. first+count-1 / of rows ids[0..count-1] (count x 3 each).  Shapes, growth, the duplicate check and the stream
+ * ordering are those of mcp_map_points_set / mcp_map_points_update; the other columns of the rows keep their contents.  The table remembers on
+ * the host which rows have rays: a row dropped by mcp_map_points_resize, or one that came into being as a gap, has none until they are set again. */
+int mcp_map_points_set_rays(mcp_map_points*, int first, int count, const double* center_nc, const double* one_right_nc, const double* one_down_nc);
+int mcp_map_points_update_rays(mcp_map_points*, int count, const int* ids, const double* center_nc, const double* one_right_nc, const double* one_down_nc);
+/* rows first .. first+count-1 read back (every pointer may be NULL: that column is skipped); waits for the table's stream */
+int mcp_map_points_get(const mcp_map_points*, int first, int count, double* world_pos, double* pixel_right_w, double* pixel_down_w, uint8_t* usable);
+
+typedef struct mcp_scene_depth {
+  double mean, sigma;           /* mdSceneDepthMean, mdSceneDepthSigma; written only when refreshed != 0                                     */
+  double median, sigma_sq;      /* dMedianDepth and the Huber sigma^2 after the clamp at 0.4; written only when refreshed != 0                */
+  int n;                        /* entries of the keyframe's list                                                                            */
+  int refreshed;                /* 1: refreshed;  0: n <= 3, the keyframe is left alone (:587-591);  -1: the mean is not finite (all weights
+                                   0) -- the reference stops the process there (:635-644), here the caller decides                           */
+} mcp_scene_depth;
+
+/* RefreshSceneDepthRobust(vector&) of n_kf keyframes over the table, one workgroup per keyframe, one wait.  cam_from_world: n_kf x 12 (R row-major
+ * 9, t 3).  seg_rows[seg_start[j] .. seg_start[j+1]) are the table rows of keyframe j's measured points that are not bad (the caller filters
+ * mbBad, :558; a row may appear more than once), seg_weights their inlier ratios (:566).  Depth = norm(CamFromWorld_j * world_pos[row]) from the
+ * table as it stands on its stream.  Then, exactly: n <= 3 leaves the keyframe alone; median = element [n/2] of the sorted depths; squared distances
+ * from it; Huber::FindSigmaSquared (MEstimator.h:194-204, its [n/2] element and small-sample factor) clamped below at 0.4;
+ * Huber::SquareRootWeight times the given weight; mean = S(w d) / S(w), sigma = sqrt(S(w d d) / S(w) - mean^2).
+ * SUMMATION ORDER (fixed, part of the contract): with the list in the caller's order, thread t of 256 adds entries t, t + 256, ... in ascending
+ * position; each wavefront folds its 64 partial sums by halving (lane l += lane l + 32, then 16, 8, 4, 2, 1); the four wavefront totals are added
+ * 0, 1, 2, 3.  The reference adds in sorted order, so mean and sigma differ from it by rounding (<= n 2^-52 relative per sum); median and
+ * sigma_sq are exact, and two calls on the same table give the same bits.
+ * depth_out: NULL or n_kf entries;  seg_depths_out: NULL or seg_start[n_kf] depths in the caller's order.  A segment may be empty; n_kf == 0 is
+ * allowed.  Refusals as mcp_ba_write_back's.  Threading: as mcp_map_points_update. */
+int mcp_scene_depth_robust(mcp_map_points*, int n_kf, const double* cam_from_world, const int* seg_start /* n_kf + 1 */, const int* seg_rows,
+                           const double* seg_weights, mcp_scene_depth* depth_out, double* seg_depths_out);
+
+/* The write-back.  STATE READ: the solver's current device state -- after mcp_ba_compute, or after mcp_ba_prepare alone (then: the state as added).
+ * No host copy of it is used.
+ * POINTS: point_ids[k] is a bundle point id, rows[k] the table row it belongs to (rows distinct, every one with rays).  With Ts = the product of
+ * the current poses along the point's own chain (what the solver's residual uses), world = Ts^-1 * x; for a fixed point world = x.
+ * RefreshPixelVectors runs at the pose of src_chains[k * chain_stride .. + src_chain_len[k]) (pose ids as in mcp_ba_add_meas); length 0, or
+ * src_chains == NULL: the point's own chain -- a fixed point lives on the world pose's chain and names its patch source's chain here.  The row
+ * becomes (world, pixel_right_w, pixel_down_w, usable = 1); rows not named keep every byte.  world_pos_out / pixel_right_out / pixel_down_out
+ * (all three NULL, or n_points x 3 each) receive the same bits.
+ * KEYFRAMES: kf_chains[j * chain_stride .. + kf_chain_len[j]) names keyframe j's CamFromWorld as a chain of the bundle ({MKF id, camera id} for
+ * BundleAdjusterMulti, {KF id} for Single); its product at the current state goes to kf_cam_from_world_out (NULL or n_kf x 12) and is the pose of
+ * the scene-depth step, which is mcp_scene_depth_robust's (same kernel) and reads the table AFTER the point step of this call: points that were
+ * not in the bundle contribute their current position, as in the reference.
+ * ORDER AND WAITS: one event makes the table's stream wait for the solver's stream; the kernels run on the table's stream, so a mcp_track_map /
+ * mcp_track_find_pvs that follows sees whole rows.  The call returns after its one wait: nothing reads the solver's device memory once it has
+ * returned, the handle may be destroyed at once.  Threading: as mcp_map_points_update -- the caller serialises calls on one table, and drives the
+ * solver handle from the same thread or otherwise keeps it idle during the call.
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, table unchanged): NULL handles; table and solver on different devices; a handle that was
+ * never prepared (or changed since); a handle with an all-reduce hook or a communicator installed (its points are sharded over ranks: out of
+ * scope); an id that is not a point; a chain entry that is not a pose, or a chain longer than MCP_MAX_CHAIN (or chain_stride); a negative or
+ * repeated row; a row without rays; seg_start not non-decreasing from 0; a seg_rows entry outside the table; a non-finite or negative weight; a
+ * required pointer NULL with a positive count.  n_points == 0 or n_kf == 0 is allowed. */
+int mcp_ba_write_back(mcp_ba*, mcp_map_points*, int n_points, const int* point_ids, const int* rows, const int* src_chains, int chain_stride,
+                      const int* src_chain_len, double* world_pos_out, double* pixel_right_out, double* pixel_down_out,
+                      int n_kf, const int* kf_chains, const int* kf_chain_len, const int* seg_start, const int* seg_rows, const double* seg_weights,
+                      double* kf_cam_from_world_out, mcp_scene_depth* depth_out, double* seg_depths_out);
+/* device time of the last completed mcp_ba_write_back / mcp_scene_depth_robust on this table, milliseconds between HIP events on the table's
+ * stream: the copy of the packed inputs, the chain table + point kernel (0 for mcp_scene_depth_robust), the scene-depth kernel.  Each may be NULL. */
+int mcp_map_points_last_timing(const mcp_map_points*, double* copy_ms, double* points_ms, double* depth_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../mcp_img.h"
+#include "ChainBundle.hpp"
 
 namespace mcptam_hip {
 
@@ -187,6 +188,24 @@ class KeyFrame {
   mcp_kf* mpDev = nullptr;
 };
 
+/// The keyframes' lists of BundleAdjusterMulti::AdjustAndUpdate's last step (RefreshSceneDepthRobust, src/KeyFrame.cc:547-645) and the chains of
+/// the write-back: keyframe j's CamFromWorld is the chain kf_chains[j*chain_stride .. + kf_chain_len[j]) of the bundle ({MKF id, camera id} /
+/// {KF id}); its measured, non-bad points are the table rows seg_rows[seg_start[j] .. seg_start[j+1]) with their inlier ratios seg_weights.
+/// src_chains (empty, or chain_stride ints per point) / src_chain_len: the chain RefreshPixelVectors uses, length 0 = the point's own chain.
+struct WriteBackLists {
+  int chain_stride = 2;
+  std::vector<int> src_chains, src_chain_len;
+  std::vector<int> kf_chains, kf_chain_len;
+  std::vector<int> seg_start, seg_rows;             // seg_start: keyframes + 1 entries (or a single 0 / empty: no keyframes)
+  std::vector<double> seg_weights;
+};
+struct WriteBackResult {
+  std::vector<double> world_pos, pixel_right_w, pixel_down_w;      // 3 per point: MapPoint::mv3WorldPos, mv3PixelRight_W, mv3PixelDown_W
+  std::vector<double> kf_cam_from_world;                           // 12 per keyframe: KeyFrame::mse3CamFromWorld
+  std::vector<mcp_scene_depth> depth;                              // per keyframe: mdSceneDepthMean / mdSceneDepthSigma where refreshed == 1
+  std::vector<double> seg_depths;
+};
+
 /// The map points Tracker::FindPVS reads (src/Tracker.cc:662-723), resident on one device: row = the caller's point index.
 class MapPointTable {
  public:
@@ -279,6 +298,52 @@ class MapPointTable {
       out[c].assign(it, it + n);
     }
     return out;
+  }
+  // ---- BundleAdjusterMulti::AdjustAndUpdate (src/BundleAdjusterMulti.cc:286-334) over the table: mcp_ba_write_back
+  /// patch rays (mv3Center_NC, mv3OneRightFromCenter_NC, mv3OneDownFromCenter_NC; 3 doubles per point) of rows first .. / of rows vIds
+  void SetRays(int first, const std::vector<double>& vCenter, const std::vector<double>& vOneRight, const std::vector<double>& vOneDown) {
+    const int n = (int)vCenter.size()/3;
+    sizes(n, vCenter, vOneRight, vOneDown);
+    check(mcp_map_points_set_rays(mpDev, first, n, vCenter.data(), vOneRight.data(), vOneDown.data()));
+  }
+  void UpdateRays(const std::vector<int>& vIds, const std::vector<double>& vCenter, const std::vector<double>& vOneRight, const std::vector<double>& vOneDown) {
+    sizes((int)vIds.size(), vCenter, vOneRight, vOneDown);
+    check(mcp_map_points_update_rays(mpDev, (int)vIds.size(), vIds.data(), vCenter.data(), vOneRight.data(), vOneDown.data()));
+  }
+  /// rows first .. first+n-1 read back
+  void Get(int first, int n, std::vector<double>& vWorldPos, std::vector<double>& vPixelRight, std::vector<double>& vPixelDown, std::vector<uint8_t>& vUsable) const {
+    vWorldPos.assign(3*(size_t)n, 0.0); vPixelRight.assign(3*(size_t)n, 0.0); vPixelDown.assign(3*(size_t)n, 0.0); vUsable.assign((size_t)n, 0);
+    check(mcp_map_points_get(mpDev, first, n, vWorldPos.data(), vPixelRight.data(), vPixelDown.data(), vUsable.data()));
+  }
+  /// KeyFrame::RefreshSceneDepthRobust of keyframes with explicit poses (12 doubles each) over the table (mcp_scene_depth_robust)
+  std::vector<mcp_scene_depth> SceneDepthRobust(const std::vector<double>& vCamFromWorld, const std::vector<int>& vSegStart, const std::vector<int>& vSegRows,
+                                                const std::vector<double>& vSegWeights, std::vector<double>* pvDepths = nullptr) {
+    const int nkf = vSegStart.empty() ? 0 : (int)vSegStart.size() - 1;
+    if ((int)vCamFromWorld.size() != 12*nkf || vSegRows.size() != vSegWeights.size() || (nkf && vSegStart.back() != (int)vSegRows.size()))
+      throw std::invalid_argument("MapPointTable::SceneDepthRobust: array sizes");
+    std::vector<mcp_scene_depth> out((size_t)nkf);
+    if (pvDepths) pvDepths->assign(vSegRows.size(), 0.0);
+    check(mcp_scene_depth_robust(mpDev, nkf, vCamFromWorld.data(), vSegStart.data(), vSegRows.data(), vSegWeights.data(), out.data(),
+                                 pvDepths ? pvDepths->data() : nullptr));
+    return out;
+  }
+  /// the whole write-back of an adjustment: vPointIds[k] (bundle point id) belongs to row vRows[k]
+  WriteBackResult WriteBack(ChainBundle& bundle, const std::vector<int>& vPointIds, const std::vector<int>& vRows, const WriteBackLists& lists) {
+    const int n = (int)vPointIds.size(), nkf = (int)lists.kf_chain_len.size();
+    if ((int)vRows.size() != n || (!lists.src_chains.empty() && ((int)lists.src_chains.size() != n*lists.chain_stride || (int)lists.src_chain_len.size() != n)) ||
+        (int)lists.kf_chains.size() != nkf*lists.chain_stride || lists.seg_rows.size() != lists.seg_weights.size() ||
+        (nkf && ((int)lists.seg_start.size() != nkf + 1 || lists.seg_start.back() != (int)lists.seg_rows.size())))
+      throw std::invalid_argument("MapPointTable::WriteBack: array sizes");
+    WriteBackResult r;
+    r.world_pos.resize(3*(size_t)n + 1); r.pixel_right_w.resize(3*(size_t)n + 1); r.pixel_down_w.resize(3*(size_t)n + 1);
+    r.kf_cam_from_world.resize(12*(size_t)nkf + 1); r.depth.resize((size_t)nkf + 1); r.seg_depths.resize(lists.seg_rows.size() + 1);
+    check(mcp_ba_write_back(bundle.handle(), mpDev, n, vPointIds.data(), vRows.data(), lists.src_chains.empty() ? nullptr : lists.src_chains.data(),
+                            lists.chain_stride, lists.src_chains.empty() ? nullptr : lists.src_chain_len.data(), r.world_pos.data(), r.pixel_right_w.data(),
+                            r.pixel_down_w.data(), nkf, lists.kf_chains.data(), lists.kf_chain_len.data(), lists.seg_start.data(), lists.seg_rows.data(),
+                            lists.seg_weights.data(), r.kf_cam_from_world.data(), r.depth.data(), r.seg_depths.data()));
+    r.world_pos.resize(3*(size_t)n); r.pixel_right_w.resize(3*(size_t)n); r.pixel_down_w.resize(3*(size_t)n);
+    r.kf_cam_from_world.resize(12*(size_t)nkf); r.depth.resize((size_t)nkf); r.seg_depths.resize(lists.seg_rows.size());
+    return r;
   }
   mcp_map_points* Handle() const { return mpDev; }
 

@@ -38,6 +38,7 @@
 #include "ba_head.h"
 #include "ba_small.h"
 #include "ba_headl.h"
+#include "ba_bridge.h"
 
 using namespace mcp;
 
@@ -4001,3 +4002,32 @@ int mcp_dense_spd_solve(const double* A, int n, const double* b, double* x) {
 }
 
 }  // extern "C"
+
+// ---- ba_bridge.h: the solver's current device state for mcp_ba_write_back (img_api.hip) ------------------------------------------
+namespace mcp {
+int ba_bridge_state(mcp_ba* h, const char* who, BaDeviceState* out) {
+  if (h->hook || h->comm) { set_err(std::string(who) + ": the handle has an all-reduce hook or a communicator installed (its points are sharded over ranks)"); return -1; }
+  if (h->dirty) { set_err(std::string(who) + ": the handle was never prepared (or was changed since): call mcp_ba_prepare or mcp_ba_compute first"); return -1; }
+  out->device = h->device; out->stream = h->st;
+  out->pose = h->d_pose[h->cur].p; out->point = h->d_pt[h->cur].p;
+  out->npose = (int)h->poses.size(); out->npoint = (int)h->points.size();
+  return 0;
+}
+int ba_bridge_point(const mcp_ba* h, int id, int* index, int* fixed, int* chain) {
+  if (id <= 0 || id >= h->next_id || h->id_kind[id] != 2) return -1;
+  const HPoint& p = h->points[h->id_index[id]];
+  *index = h->id_index[id]; *fixed = p.fixed; *chain = p.chain;
+  return 0;
+}
+int ba_bridge_num_chains(const mcp_ba* h) { return (int)h->chains.size(); }
+void ba_bridge_chain(const mcp_ba* h, int c, int* len, int v[MCP_MAX_CHAIN]) {
+  const HChain& C = h->chains[c];
+  *len = C.len;
+  for (int k = 0; k < MCP_MAX_CHAIN; ++k) v[k] = k < C.len ? C.v[k] : 0;
+}
+int ba_bridge_lookup_chain(const mcp_ba* h, const int* ids, int n, int v[MCP_MAX_CHAIN]) {
+  const int c = h->lookup_chain(ids, n);
+  if (c == -1) for (int k = 0; k < MCP_MAX_CHAIN; ++k) v[k] = k < n ? h->id_index[ids[k]] : 0;
+  return c;
+}
+}  // namespace mcp

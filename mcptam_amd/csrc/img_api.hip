@@ -19,6 +19,8 @@
 #include "pvs_kernels.h"
 #include "track_map_kernels.h"
 #include "stereo_kernels.h"
+#include "write_back_kernels.h"
+#include "ba_bridge.h"
 #include "ba_select.h"
 
 using namespace mcp;
@@ -1146,8 +1148,23 @@ struct mcp_map_points {
   Buf<mcp_pose_point> tm_crec, tm_frec; Buf<double> tm_w, tm_J, tm_ex, tm_e2; Buf<mcp_track_map_item> tm_items;
   PinBuf<uint8_t> h_blk; PinBuf<TmSlot> h_slots; PinBuf<mcp_track_map_item> h_items; PinBuf<TmOut> h_res;
   int tm_ncam = 0; int tm_first[MCP_MAX_FRAME_CAMS + 1] = {};
+  // AdjustAndUpdate write-back: the patch rays per row (9 doubles; capacity follows pts.n once the first rays arrive), which rows have them
+  // (host), the staging of the ray uploads, and the packed inputs / pinned outputs of mcp_ba_write_back and mcp_scene_depth_robust
+  Buf<double> rays; std::vector<uint8_t> has_rays; PinBuf<double> h_rays; Buf<double> d_rays;
+  PinBuf<char> wb_in; Buf<char> wb_dev; PinBuf<char> wb_out; Buf<double> wb_T, wb_depth; hipEvent_t wb_ev = nullptr;
+  std::vector<int> wb_slot, wb_mark; int wb_stamp = 0;      // (wb_mark[row] == wb_stamp: the row was named earlier in this call)
+  hipEvent_t wb_t[4] = {nullptr, nullptr, nullptr, nullptr}; bool wb_timed = false;      // mcp_map_points_last_timing: input copy | points | scene depth
+  int ensure_rays() {
+    if (rays.p && rays.n >= 9*pts.n) return 0;
+    Buf<double> r2; if (r2.alloc(9*std::max<size_t>(pts.n, 1))) return -1;
+    if (rays.p && rows) ICK(hipMemcpyAsync(r2.p, rays.p, 72*(size_t)rows, hipMemcpyDeviceToDevice, st));
+    ICK(hipStreamSynchronize(st)); stage_busy = false;
+    rays.swap(r2);
+    return 0;
+  }
   TmStates state_ptrs() const { TmStates S; for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c) S.s[c] = states[c].p; return S; }
-  ~mcp_map_points() { if (st) (void)hipStreamSynchronize(st); if (st) (void)hipStreamDestroy(st); if (staged) (void)hipEventDestroy(staged); }
+  ~mcp_map_points() { if (st) (void)hipStreamSynchronize(st); if (st) (void)hipStreamDestroy(st); if (staged) (void)hipEventDestroy(staged); if (wb_ev) (void)hipEventDestroy(wb_ev);
+    for (hipEvent_t e : wb_t) if (e) (void)hipEventDestroy(e); }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
   // rows [rows, new_rows) become unusable zero rows; the contents so far move to a larger block when the capacity is passed
   int grow(int new_rows) {
@@ -1164,9 +1181,15 @@ struct mcp_map_points {
         if (st2[c].alloc(bigger.n)) return -1;
         if (rows) ICK(hipMemcpyAsync(st2[c].p, states[c].p, sizeof(mcp_pf_state)*(size_t)rows, hipMemcpyDeviceToDevice, st));
       }
+      Buf<double> rays2;
+      if (rays.p) {
+        if (rays2.alloc(9*bigger.n)) return -1;
+        if (rows) ICK(hipMemcpyAsync(rays2.p, rays.p, 72*(size_t)rows, hipMemcpyDeviceToDevice, st));
+      }
       ICK(hipStreamSynchronize(st));                 // the old block is freed below, with nothing in flight on it
       stage_busy = false;
       pts.swap(bigger); src.swap(src2);
+      if (rays2.p) rays.swap(rays2);
       for (int c = 0; c < st_ncam; ++c) states[c].swap(st2[c]);
     }
     ICK(hipMemsetAsync(pts.p + rows, 0, sizeof(PvsPoint)*(size_t)(new_rows - rows), st));
@@ -1174,6 +1197,7 @@ struct mcp_map_points {
     ICK(hipMemsetAsync(src.p + rows, 0, sizeof(TmSrc)*(size_t)(new_rows - rows), st));
     for (int c = 0; c < st_ncam; ++c) ICK(hipMemsetAsync(states[c].p + rows, 0, sizeof(mcp_pf_state)*(size_t)(new_rows - rows), st));
     row_slot.resize(new_rows, 0);
+    has_rays.resize(new_rows, 0);                    // (a new row has no patch rays until mcp_map_points_set_rays / _update_rays names it)
     rows = new_rows;
     return 0;
   }
@@ -1205,6 +1229,8 @@ mcp_map_points* mcp_map_points_create(int device) {
   if (hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->staged, hipEventDisableTiming) != hipSuccess) {
     mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr;
   }
+  for (hipEvent_t& e : m->wb_t) if (hipEventCreate(&e) != hipSuccess) { mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr; }
+  if (hipEventCreateWithFlags(&m->wb_ev, hipEventDisableTiming) != hipSuccess) { mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr; }
   return m;
 }
 void mcp_map_points_destroy(mcp_map_points* m) { if (m) { (void)hipSetDevice(m->device); delete m; } }
@@ -1216,6 +1242,7 @@ int mcp_map_points_resize(mcp_map_points* m, int rows) {
   if (rows <= m->rows) {                                    // the rows past the end are gone; growing again zeroes them (grow)
     for (int r = rows; r < m->rows && r < (int)m->row_slot.size(); ++r) m->slot_release(m->row_slot[r]);
     if ((int)m->row_slot.size() > rows) m->row_slot.resize(rows);
+    if ((int)m->has_rays.size() > rows) m->has_rays.resize(rows);
     m->rows = rows;
     return 0;
   }
@@ -1713,3 +1740,297 @@ int mcp_stereo_hypotheses(mcp_kf* src, const mcp_camera* src_cam, const double s
 
 }  // extern "C"
 
+
+// ---- AdjustAndUpdate: the write-back of an adjustment into the table (include/mcp_img.h, write_back_kernels.h) -----------------------
+namespace {
+size_t wb_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// the argument checks of the scene-depth lists (nothing is enqueued before they pass); *total = seg_start[n_kf]
+int sd_check(const std::string& who, const mcp_map_points* m, int n_kf, const int* seg_start, const int* seg_rows, const double* seg_w, int* total) {
+  *total = 0;
+  if (n_kf < 0) return img_fail(who + ": negative keyframe count");
+  if (n_kf == 0) return 0;
+  if (!seg_start) return img_fail(who + ": seg_start is NULL");
+  if (seg_start[0] != 0) return img_fail(who + ": seg_start does not begin at 0");
+  for (int j = 0; j < n_kf; ++j) if (seg_start[j + 1] < seg_start[j]) return img_fail(who + ": seg_start decreases at keyframe " + std::to_string(j));
+  const int tot = seg_start[n_kf];
+  if (tot > 0 && (!seg_rows || !seg_w)) return img_fail(who + ": seg_rows / seg_weights is NULL");
+  for (int i = 0; i < tot; ++i) {
+    if (seg_rows[i] < 0 || seg_rows[i] >= m->rows) return img_fail(who + ": seg_rows[" + std::to_string(i) + "] = " + std::to_string(seg_rows[i]) + " is outside the table");
+    if (!(seg_w[i] >= 0.0) || !std::isfinite(seg_w[i])) return img_fail(who + ": seg_weights[" + std::to_string(i) + "] is negative or not finite");
+  }
+  *total = tot;
+  return 0;
+}
+
+// packed inputs of one call (pinned -> device in one copy) and its pinned outputs
+struct WbLayout {
+  size_t chains = 0, items = 0, kf_slot = 0, seg_start = 0, seg_rows = 0, seg_w = 0, poses = 0, in_bytes = 0;
+  size_t T = 0, vec = 0, sd = 0, depths = 0, out_bytes = 0;
+  WbLayout(int nslot, int n_points, int n_kf, int total, bool want_vec, bool want_depths, int n_pose = 0 /* explicit poses (mcp_scene_depth_robust) */) {
+    size_t o = 0;
+    chains = o; o = wb_align(o + sizeof(WbChain)*(size_t)nslot);
+    items = o; o = wb_align(o + sizeof(WbItem)*(size_t)n_points);
+    kf_slot = o; o = wb_align(o + sizeof(int)*(size_t)n_kf);
+    seg_start = o; o = wb_align(o + sizeof(int)*((size_t)n_kf + 1));
+    seg_rows = o; o = wb_align(o + sizeof(int)*(size_t)total);
+    seg_w = o; o = wb_align(o + sizeof(double)*(size_t)total);
+    poses = o; o = wb_align(o + 96*(size_t)n_pose);
+    in_bytes = o;
+    o = 0;
+    T = o; o = wb_align(o + 96*(size_t)nslot);
+    vec = o; o = wb_align(o + (want_vec ? 72*(size_t)n_points : 0));
+    sd = o; o = wb_align(o + sizeof(mcp_scene_depth)*(size_t)n_kf);
+    depths = o; o = wb_align(o + (want_depths ? 8*(size_t)total : 0));
+    out_bytes = o;
+  }
+};
+
+void sd_copy_out(int n_kf, const mcp_scene_depth* got, mcp_scene_depth* depth_out) {
+  if (!depth_out) return;
+  for (int j = 0; j < n_kf; ++j) {
+    if (got[j].refreshed == 0) { depth_out[j].n = got[j].n; depth_out[j].refreshed = 0; }      // left alone: mean / sigma keep the caller's values
+    else depth_out[j] = got[j];
+  }
+}
+
+int rays_upload(mcp_map_points* m, const char* who, int first, int count, const int* ids, const double* ce, const double* ri, const double* dn) {
+  if (!m) return img_fail(std::string(who) + ": NULL table");
+  if (first < 0 || count < 0 || (long long)first + count > 0x7fffffffLL || (count > 0 && (!ce || !ri || !dn))) return img_fail(std::string(who) + ": bad arguments");
+  if (count == 0) return 0;
+  int top = first + count;
+  if (ids) {
+    top = m->rows;
+    for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(std::string(who) + ": bad row id"); top = std::max(top, ids[k] + 1); }
+    m->sorted_ids.assign(ids, ids + count);
+    std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
+    for (int k = 1; k < count; ++k)
+      if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail(std::string(who) + ": row " + std::to_string(m->sorted_ids[k]) + " appears twice");
+  }
+  ICK(hipSetDevice(m->device));
+  if (m->wait_staging()) return -1;
+  if (m->h_rays.alloc(9*(size_t)count)) return -1;
+  if (ids) {
+    if (m->h_ids.alloc(count)) return -1;
+    if (9*(size_t)count > m->d_rays.n || (size_t)count > m->d_ids.n) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
+    if (m->d_rays.alloc(9*(size_t)count) || m->d_ids.alloc(count)) return -1;
+  }
+  for (int k = 0; k < count; ++k) {
+    double* r = m->h_rays.p + 9*(size_t)k;
+    std::memcpy(r, ce + 3*(size_t)k, 24); std::memcpy(r + 3, ri + 3*(size_t)k, 24); std::memcpy(r + 6, dn + 3*(size_t)k, 24);
+    if (ids) m->h_ids.p[k] = ids[k];
+  }
+  if (m->grow(top)) return -1;
+  if (m->ensure_rays()) return -1;
+  if (!ids) ICK(hipMemcpyAsync(m->rays.p + 9*(size_t)first, m->h_rays.p, 72*(size_t)count, hipMemcpyHostToDevice, m->st));
+  else {
+    ICK(hipMemcpyAsync(m->d_rays.p, m->h_rays.p, 72*(size_t)count, hipMemcpyHostToDevice, m->st));
+    ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+    hipLaunchKernelGGL(k_map_rays_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->rays.p, count, (const int*)m->d_ids.p, (const double*)m->d_rays.p);
+    ICK(hipGetLastError());
+  }
+  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  for (int k = 0; k < count; ++k) m->has_rays[ids ? ids[k] : first + k] = 1;
+  return 0;
+}
+
+// the scene-depth launch on the table's stream, inputs already on the device
+void sd_launch(mcp_map_points* m, int n_kf, const double* T, const int* slot, const char* dev_in, const WbLayout& L, char* out_pinned, bool want_depths) {
+  hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)n_kf), dim3(SD_BLOCK), 0, m->st, T, slot, (const int*)(dev_in + L.seg_start), (const int*)(dev_in + L.seg_rows),
+                     (const double*)(dev_in + L.seg_w), (const PvsPoint*)m->pts.p, m->wb_depth.p, (mcp_scene_depth*)(out_pinned + L.sd),
+                     want_depths ? (double*)(out_pinned + L.depths) : (double*)nullptr);
+}
+}  // namespace
+
+extern "C" {
+
+int mcp_map_points_set_rays(mcp_map_points* m, int first, int count, const double* ce, const double* ri, const double* dn) {
+  return rays_upload(m, "mcp_map_points_set_rays", first, count, nullptr, ce, ri, dn);
+}
+int mcp_map_points_update_rays(mcp_map_points* m, int count, const int* ids, const double* ce, const double* ri, const double* dn) {
+  if (m && count > 0 && !ids) return img_fail("mcp_map_points_update_rays: bad arguments");
+  return rays_upload(m, "mcp_map_points_update_rays", 0, count, ids, ce, ri, dn);
+}
+
+int mcp_map_points_get(const mcp_map_points* mc, int first, int count, double* wp, double* pr, double* pd, uint8_t* us) {
+  if (!mc) return img_fail("mcp_map_points_get: NULL table");
+  if (first < 0 || count < 0 || (long long)first + count > mc->rows) return img_fail("mcp_map_points_get: bad arguments");
+  if (count == 0) return 0;
+  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
+  ICK(hipSetDevice(m->device));
+  std::vector<PvsPoint> h((size_t)count);
+  ICK(hipMemcpyAsync(h.data(), m->pts.p + first, sizeof(PvsPoint)*(size_t)count, hipMemcpyDeviceToHost, m->st));
+  ICK(hipStreamSynchronize(m->st));
+  m->stage_busy = false;
+  for (int k = 0; k < count; ++k) {
+    if (wp) std::memcpy(wp + 3*(size_t)k, h[k].world_pos, 24);
+    if (pr) std::memcpy(pr + 3*(size_t)k, h[k].pixel_right_w, 24);
+    if (pd) std::memcpy(pd + 3*(size_t)k, h[k].pixel_down_w, 24);
+    if (us) us[k] = h[k].usable ? 1 : 0;
+  }
+  return 0;
+}
+
+int mcp_map_points_last_timing(const mcp_map_points* m, double* copy_ms, double* points_ms, double* depth_ms) {
+  if (!m) return img_fail("mcp_map_points_last_timing: NULL table");
+  if (!m->wb_timed) return img_fail("mcp_map_points_last_timing: no completed mcp_ba_write_back / mcp_scene_depth_robust on this table");
+  float a = 0, b = 0, c = 0;
+  ICK(hipEventElapsedTime(&a, m->wb_t[0], m->wb_t[1])); ICK(hipEventElapsedTime(&b, m->wb_t[1], m->wb_t[2])); ICK(hipEventElapsedTime(&c, m->wb_t[2], m->wb_t[3]));
+  if (copy_ms) *copy_ms = a;
+  if (points_ms) *points_ms = b;
+  if (depth_ms) *depth_ms = c;
+  return 0;
+}
+
+int mcp_scene_depth_robust(mcp_map_points* m, int n_kf, const double* cfw, const int* seg_start, const int* seg_rows, const double* seg_w,
+                           mcp_scene_depth* depth_out, double* seg_depths_out) {
+  const std::string who = "mcp_scene_depth_robust";
+  if (!m) return img_fail(who + ": NULL table");
+  int total = 0;
+  if (sd_check(who, m, n_kf, seg_start, seg_rows, seg_w, &total)) return -1;
+  if (n_kf == 0) return 0;
+  if (!cfw) return img_fail(who + ": cam_from_world is NULL");
+  ICK(hipSetDevice(m->device));
+  const bool want_depths = seg_depths_out != nullptr;
+  const WbLayout L(0, 0, n_kf, total, false, want_depths, n_kf);
+  if (m->wb_in.alloc(L.in_bytes) || m->wb_dev.alloc(L.in_bytes) || m->wb_out.alloc(L.out_bytes) || m->wb_depth.alloc((size_t)total)) return -1;
+  char* hin = m->wb_in.p;
+  std::memcpy(hin + L.poses, cfw, 96*(size_t)n_kf);
+  std::memcpy(hin + L.seg_start, seg_start, sizeof(int)*((size_t)n_kf + 1));
+  if (total) { std::memcpy(hin + L.seg_rows, seg_rows, sizeof(int)*(size_t)total); std::memcpy(hin + L.seg_w, seg_w, 8*(size_t)total); }
+  m->wb_timed = false;
+  ICK(hipEventRecord(m->wb_t[0], m->st));
+  ICK(hipMemcpyAsync(m->wb_dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->wb_t[1], m->st)); ICK(hipEventRecord(m->wb_t[2], m->st));
+  sd_launch(m, n_kf, (const double*)(m->wb_dev.p + L.poses), nullptr, m->wb_dev.p, L, m->wb_out.p, want_depths);
+  const hipError_t le = hipGetLastError();
+  (void)hipEventRecord(m->wb_t[3], m->st);
+  ICK(hipStreamSynchronize(m->st));
+  m->stage_busy = false;
+  if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
+  m->wb_timed = true;
+  sd_copy_out(n_kf, (const mcp_scene_depth*)(m->wb_out.p + L.sd), depth_out);
+  if (seg_depths_out && total) std::memcpy(seg_depths_out, m->wb_out.p + L.depths, 8*(size_t)total);
+  return 0;
+}
+
+int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* point_ids, const int* rows, const int* src_chains, int chain_stride,
+                      const int* src_chain_len, double* world_out, double* right_out, double* down_out,
+                      int n_kf, const int* kf_chains, const int* kf_chain_len, const int* seg_start, const int* seg_rows, const double* seg_w,
+                      double* kf_cfw_out, mcp_scene_depth* depth_out, double* seg_depths_out) {
+  const std::string who = "mcp_ba_write_back";
+  if (!h) return img_fail(who + ": NULL solver handle");
+  if (!m) return img_fail(who + ": NULL table");
+  BaDeviceState S;
+  if (ba_bridge_state(h, who.c_str(), &S)) return -1;
+  if (S.device != m->device) return img_fail(who + ": the table lives on device " + std::to_string(m->device) + ", the solver on device " + std::to_string(S.device));
+  if (n_points < 0) return img_fail(who + ": negative point count");
+  if (n_points > 0 && (!point_ids || !rows)) return img_fail(who + ": point_ids / rows is NULL");
+  if (n_points > 0 && src_chains && !src_chain_len) return img_fail(who + ": src_chain_len is NULL");
+  int total = 0;
+  if (sd_check(who, m, n_kf, seg_start, seg_rows, seg_w, &total)) return -1;
+  if (n_kf > 0 && (!kf_chains || !kf_chain_len)) return img_fail(who + ": kf_chains / kf_chain_len is NULL");
+  if (((n_points > 0 && src_chains) || n_kf > 0) && chain_stride < 1) return img_fail(who + ": chain_stride must be positive");
+  // distinct chains of the call -> slots of the product table (the solver's own chains by number, a chain it does not know by its pose indices)
+  const int nsolver = ba_bridge_num_chains(h);
+  m->wb_slot.assign((size_t)nsolver, -1);
+  std::vector<WbChain> chains;
+  std::map<std::vector<int>, int> extra;
+  auto slot_of_solver = [&](int c) -> int {
+    int& s = m->wb_slot[c];
+    if (s < 0) { WbChain C; ba_bridge_chain(h, c, &C.len, C.v); s = (int)chains.size(); chains.push_back(C); }
+    return s;
+  };
+  auto slot_of_ids = [&](const int* ids, int len, const char* what, int k) -> int {      // -1: refused
+    if (len > chain_stride) { img_fail(who + ": " + what + " " + std::to_string(k) + " is longer than chain_stride"); return -1; }
+    int v[MCP_MAX_CHAIN];
+    const int c = ba_bridge_lookup_chain(h, ids, len, v);
+    if (c == -2) { img_fail(who + ": " + what + " " + std::to_string(k) + " is not a chain of poses of this bundle (1.." + std::to_string(MCP_MAX_CHAIN) + " pose ids)"); return -1; }
+    if (c >= 0) return slot_of_solver(c);
+    std::vector<int> key(v, v + len);
+    auto it = extra.find(key);
+    if (it != extra.end()) return it->second;
+    WbChain C; C.len = len; for (int i = 0; i < MCP_MAX_CHAIN; ++i) C.v[i] = i < len ? v[i] : 0;
+    const int s = (int)chains.size(); chains.push_back(C); extra.emplace(key, s);
+    return s;
+  };
+  std::vector<WbItem> items((size_t)n_points);
+  if (m->wb_stamp == 0x7fffffff) { m->wb_stamp = 0; std::fill(m->wb_mark.begin(), m->wb_mark.end(), 0); }
+  const int stamp = ++m->wb_stamp;
+  if ((int)m->wb_mark.size() < m->rows) m->wb_mark.resize((size_t)m->rows, 0);
+  for (int k = 0; k < n_points; ++k) {
+    int idx, fixed, c;
+    if (ba_bridge_point(h, point_ids[k], &idx, &fixed, &c)) return img_fail(who + ": point_ids[" + std::to_string(k) + "] = " + std::to_string(point_ids[k]) + " is not a point of this bundle");
+    const int r = rows[k];
+    if (r < 0) return img_fail(who + ": rows[" + std::to_string(k) + "] is negative");
+    if (r >= m->rows || !m->has_rays[r]) return img_fail(who + ": row " + std::to_string(r) + " has no patch rays (mcp_map_points_set_rays)");
+    if (m->wb_mark[r] == stamp) return img_fail(who + ": row " + std::to_string(r) + " appears twice");
+    m->wb_mark[r] = stamp;
+    const int own = slot_of_solver(c);
+    int src = own;
+    if (src_chains && src_chain_len[k] != 0) {
+      src = slot_of_ids(src_chains + (size_t)chain_stride*k, src_chain_len[k], "src_chains of point", k);
+      if (src < 0) return -1;
+    }
+    items[k].pt = idx; items[k].row = r; items[k].own = own; items[k].src2_fixed = 2*src + (fixed ? 1 : 0);
+  }
+  std::vector<int> kf_slot((size_t)n_kf);
+  for (int j = 0; j < n_kf; ++j) {
+    kf_slot[j] = slot_of_ids(kf_chains + (size_t)chain_stride*j, kf_chain_len[j], "kf_chains of keyframe", j);
+    if (kf_slot[j] < 0) return -1;
+  }
+  if (n_points == 0 && n_kf == 0) return 0;
+  // ---- every check has passed: from here on things are enqueued ----
+  ICK(hipSetDevice(m->device));
+  const int nslot = (int)chains.size();
+  const bool want_vec = n_points > 0 && (world_out || right_out || down_out), want_depths = seg_depths_out != nullptr;
+  const WbLayout L(nslot, n_points, n_kf, total, want_vec, want_depths);
+  if (m->wb_in.alloc(L.in_bytes) || m->wb_dev.alloc(L.in_bytes) || m->wb_out.alloc(L.out_bytes) || m->wb_T.alloc(12*(size_t)nslot) || m->wb_depth.alloc((size_t)total)) return -1;
+  char* hin = m->wb_in.p;
+  std::memcpy(hin + L.chains, chains.data(), sizeof(WbChain)*(size_t)nslot);
+  if (n_points) std::memcpy(hin + L.items, items.data(), sizeof(WbItem)*(size_t)n_points);
+  if (n_kf) {
+    std::memcpy(hin + L.kf_slot, kf_slot.data(), sizeof(int)*(size_t)n_kf);
+    std::memcpy(hin + L.seg_start, seg_start, sizeof(int)*((size_t)n_kf + 1));
+    if (total) { std::memcpy(hin + L.seg_rows, seg_rows, sizeof(int)*(size_t)total); std::memcpy(hin + L.seg_w, seg_w, 8*(size_t)total); }
+  }
+  // the table's stream waits for whatever the solver's stream still has to write of the state
+  ICK(hipEventRecord(m->wb_ev, S.stream));
+  ICK(hipStreamWaitEvent(m->st, m->wb_ev, 0));
+  m->wb_timed = false;
+  ICK(hipEventRecord(m->wb_t[0], m->st));
+  ICK(hipMemcpyAsync(m->wb_dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->wb_t[1], m->st));
+  const char* din = m->wb_dev.p; char* hout = m->wb_out.p;
+  hipLaunchKernelGGL(k_wb_chains, dim3((unsigned)((nslot + 63)/64)), dim3(64), 0, m->st, nslot, (const WbChain*)(din + L.chains), S.pose, m->wb_T.p,
+                     kf_cfw_out ? (double*)(hout + L.T) : (double*)nullptr);
+  if (n_points) {
+    double* vo = want_vec ? (double*)(hout + L.vec) : nullptr;
+    hipLaunchKernelGGL(k_wb_points, dim3((unsigned)((n_points + WB_BLOCK - 1)/WB_BLOCK)), dim3(WB_BLOCK), 0, m->st, n_points, (const WbItem*)(din + L.items), S.point,
+                       (const double*)m->wb_T.p, (const double*)m->rays.p, m->pts.p, vo, vo ? vo + 3*(size_t)n_points : nullptr, vo ? vo + 6*(size_t)n_points : nullptr);
+  }
+  hipError_t le = hipGetLastError();
+  (void)hipEventRecord(m->wb_t[2], m->st);
+  if (n_kf) sd_launch(m, n_kf, (const double*)m->wb_T.p, (const int*)(din + L.kf_slot), din, L, hout, want_depths);
+  if (le == hipSuccess) le = hipGetLastError();
+  (void)hipEventRecord(m->wb_t[3], m->st);
+  const hipError_t se = hipStreamSynchronize(m->st);                 // the one wait: the solver's memory is not read after this
+  m->stage_busy = false;
+  if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
+  if (se != hipSuccess) return img_fail(who + ": " + hipGetErrorString(se));
+  m->wb_timed = true;
+  if (want_vec) {
+    const double* vo = (const double*)(hout + L.vec);
+    if (world_out) std::memcpy(world_out, vo, 24*(size_t)n_points);
+    if (right_out) std::memcpy(right_out, vo + 3*(size_t)n_points, 24*(size_t)n_points);
+    if (down_out) std::memcpy(down_out, vo + 6*(size_t)n_points, 24*(size_t)n_points);
+  }
+  if (n_kf) {
+    if (kf_cfw_out) for (int j = 0; j < n_kf; ++j) std::memcpy(kf_cfw_out + 12*(size_t)j, hout + L.T + 96*(size_t)kf_slot[j], 96);
+    sd_copy_out(n_kf, (const mcp_scene_depth*)(hout + L.sd), depth_out);
+    if (seg_depths_out && total) std::memcpy(seg_depths_out, hout + L.depths, 8*(size_t)total);
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -104,4 +104,14 @@ k_map_points_scatter(PvsPoint* __restrict__ rows, int count, const int* __restri
   if (k < count) rows[ids[k]] = recs[k];
 }
 
+// mcp_map_points_update_rays: the patch rays (9 doubles) of rows ids[k] <- recs[k] (ids distinct, checked on the host)
+__global__ void __launch_bounds__(256)
+k_map_rays_scatter(double* __restrict__ rays, int count, const int* __restrict__ ids, const double* __restrict__ recs) {
+  const int k = blockIdx.x*256 + threadIdx.x;
+  if (k >= count) return;
+  double* o = rays + 9*(size_t)ids[k];
+#pragma unroll
+  for (int a = 0; a < 9; ++a) o[a] = recs[9*(size_t)k + a];
+}
+
 }  // namespace mcp

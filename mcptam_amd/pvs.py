@@ -2,6 +2,7 @@
 mcp_track_find_pvs, mcp_track_map).  The table holds, per row, what FindPVS reads of a MapPoint (world position, the two pixel vectors, usable =
 !mbBad && mbOptimized); one find_pvs call gives the potentially visible set of every camera of a frame, level by level."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -142,6 +143,92 @@ class MapPointTable:
             else:
                 offs = np.concatenate([[0], np.cumsum(counts[c])]).astype(int)
                 res.append([out[c][offs[l]:offs[l + 1]] for l in range(LEVELS)])
+        return res
+
+    # ---- AdjustAndUpdate: patch rays, read-back, the write-back of an adjustment (include/mcp_img.h mcp_ba_write_back) ----
+    def set_rays(self, center_nc, one_right_nc, one_down_nc, first=0):
+        """Patch rays (mv3Center_NC, mv3OneRightFromCenter_NC, mv3OneDownFromCenter_NC) of rows first .. first+n-1."""
+        L = _bind_write_back(self._L)
+        n = len(center_nc)
+        ce, ri, dn = _soa(center_nc, n, "center_nc"), _soa(one_right_nc, n, "one_right_nc"), _soa(one_down_nc, n, "one_down_nc")
+        _chk(L.mcp_map_points_set_rays(self._h, int(first), n, ce.ctypes.data, ri.ctypes.data, dn.ctypes.data), "map_points_set_rays")
+
+    def update_rays(self, ids, center_nc, one_right_nc, one_down_nc):
+        L = _bind_write_back(self._L)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        n = len(ids)
+        ce, ri, dn = _soa(center_nc, n, "center_nc"), _soa(one_right_nc, n, "one_right_nc"), _soa(one_down_nc, n, "one_down_nc")
+        _chk(L.mcp_map_points_update_rays(self._h, n, ids.ctypes.data, ce.ctypes.data, ri.ctypes.data, dn.ctypes.data), "map_points_update_rays")
+
+    def get(self, first=0, count=None):
+        """Rows first .. first+count-1 read back: (world_pos, pixel_right_w, pixel_down_w, usable)."""
+        L = _bind_write_back(self._L)
+        count = self.rows - first if count is None else int(count)
+        wp, pr, pd = (np.zeros((count, 3)) for _ in range(3))
+        us = np.zeros(count, dtype=np.uint8)
+        _chk(L.mcp_map_points_get(self._h, int(first), count, wp.ctypes.data, pr.ctypes.data, pd.ctypes.data, us.ctypes.data), "map_points_get")
+        return wp, pr, pd, us
+
+    def last_timing(self):
+        """Device milliseconds of the last write_back / scene_depth on this table: dict(copy, points, depth)."""
+        L = _bind_write_back(self._L)
+        v = (ctypes.c_double * 3)()
+        _chk(L.mcp_map_points_last_timing(self._h, ctypes.byref(v, 0), ctypes.byref(v, 8), ctypes.byref(v, 16)), "map_points_last_timing")
+        return dict(copy=v[0], points=v[1], depth=v[2])
+
+    def scene_depth(self, cam_from_world, seg_start, seg_rows, seg_weights, depths=True):
+        """mcp_scene_depth_robust: KeyFrame::RefreshSceneDepthRobust of every keyframe j with pose cam_from_world[j] (12 doubles) over the rows
+        seg_rows[seg_start[j]:seg_start[j+1]].  Returns (SCENE_DEPTH_DTYPE array, depths in list order or None)."""
+        L = _bind_write_back(self._L)
+        ss, sr, sw = _csr(seg_start, seg_rows, seg_weights)
+        n_kf = len(ss) - 1
+        cfw = np.ascontiguousarray(cam_from_world, dtype=np.float64).reshape(n_kf, 12)
+        out = np.zeros(n_kf, dtype=SCENE_DEPTH_DTYPE)
+        dep = np.zeros(len(sr)) if depths else None
+        _chk(L.mcp_scene_depth_robust(self._h, n_kf, cfw.ctypes.data, ss.ctypes.data, sr.ctypes.data, sw.ctypes.data, out.ctypes.data,
+                                      dep.ctypes.data if depths else None), "scene_depth_robust")
+        return out, dep
+
+    def write_back(self, bundle, point_ids, rows, src_chains=None, src_chain_len=None, kf_chains=None, kf_chain_len=None, seg_start=None,
+                   seg_rows=None, seg_weights=None, outputs=True):
+        """mcp_ba_write_back: AdjustAndUpdate from `bundle` (a ChainBundle that was prepared or solved) into this table.  point_ids: bundle point
+        ids, rows: their table rows; src_chains (n, stride) / src_chain_len: the chain RefreshPixelVectors uses (length 0: the point's own);
+        kf_chains (n_kf, stride) / kf_chain_len: every keyframe's CamFromWorld as a chain; seg_*: the keyframes' lists (CSR) of rows and weights.
+        Returns a dict: world_pos, pixel_right_w, pixel_down_w (n, 3), kf_cam_from_world (n_kf, 12), depth (SCENE_DEPTH_DTYPE), seg_depths --
+        or None with outputs=False."""
+        L = _bind_write_back(self._L)
+        pid = np.ascontiguousarray(point_ids, dtype=np.int32)
+        rw = np.ascontiguousarray(rows, dtype=np.int32)
+        n = len(pid)
+        if len(rw) != n:
+            raise ValueError("write_back: point_ids and rows differ in length")
+        stride = 1
+        sc = sl = None
+        if src_chains is not None:
+            sc = np.ascontiguousarray(src_chains, dtype=np.int32).reshape(n, -1)
+            sl = np.ascontiguousarray(src_chain_len, dtype=np.int32)
+            stride = sc.shape[1]
+        n_kf = 0 if kf_chains is None else len(kf_chains)
+        kc = kl = ss = sr = sw = None
+        if n_kf:
+            kc = np.ascontiguousarray(kf_chains, dtype=np.int32).reshape(n_kf, -1)
+            kl = np.ascontiguousarray(kf_chain_len, dtype=np.int32)
+            if sc is not None and kc.shape[1] != stride:      # one stride for both chain arrays
+                w = max(stride, kc.shape[1])
+                sc = np.ascontiguousarray(np.pad(sc, ((0, 0), (0, w - stride))))
+                kc = np.ascontiguousarray(np.pad(kc, ((0, 0), (0, w - kc.shape[1]))))
+            stride = kc.shape[1]
+            ss, sr, sw = _csr(seg_start, seg_rows, seg_weights)
+            if len(ss) != n_kf + 1:
+                raise ValueError("write_back: seg_start must have n_kf + 1 entries")
+        res = None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        if outputs:
+            res = dict(world_pos=np.zeros((n, 3)), pixel_right_w=np.zeros((n, 3)), pixel_down_w=np.zeros((n, 3)), kf_cam_from_world=np.zeros((n_kf, 12)),
+                       depth=np.zeros(n_kf, dtype=SCENE_DEPTH_DTYPE), seg_depths=np.zeros(0 if sr is None else len(sr)))
+        o = (lambda k: res[k].ctypes.data) if outputs else (lambda k: None)
+        _chk(L.mcp_ba_write_back(bundle._h, self._h, n, ptr(pid), ptr(rw), ptr(sc), stride, ptr(sl), o("world_pos"), o("pixel_right_w"), o("pixel_down_w"),
+                                 n_kf, ptr(kc), ptr(kl), ptr(ss), ptr(sr), ptr(sw), o("kf_cam_from_world"), o("depth"), o("seg_depths")), "ba_write_back")
         return res
 
     def set_source(self, keys, sources, levels, centers, fixed=None, first=0):
@@ -293,3 +380,128 @@ def _source_arrays(n, keys, sources, levels, centers, fixed):
     return keys, hs, lv, cx, fx
 
 
+# ---- AdjustAndUpdate write-back (include/mcp_img.h mcp_ba_write_back) and its numpy restatement ----------------------------------------
+WRITE_BACK_SYMBOLS = ["mcp_map_points_set_rays", "mcp_map_points_update_rays", "mcp_map_points_get", "mcp_scene_depth_robust", "mcp_ba_write_back", "mcp_map_points_last_timing"]
+
+
+class SceneDepth(ctypes.Structure):
+    _fields_ = [("mean", ctypes.c_double), ("sigma", ctypes.c_double), ("median", ctypes.c_double), ("sigma_sq", ctypes.c_double),
+                ("n", ctypes.c_int), ("refreshed", ctypes.c_int)]
+
+
+SCENE_DEPTH_DTYPE = np.dtype([("mean", "f8"), ("sigma", "f8"), ("median", "f8"), ("sigma_sq", "f8"), ("n", "i4"), ("refreshed", "i4")], align=True)
+assert SCENE_DEPTH_DTYPE.itemsize == ctypes.sizeof(SceneDepth)
+
+
+def _bind_write_back(L):
+    if getattr(L, "_write_back_bound", False):
+        return L
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.mcp_map_points_set_rays.argtypes = [vp, ip, ip, vp, vp, vp]
+    L.mcp_map_points_update_rays.argtypes = [vp, ip, vp, vp, vp, vp]
+    L.mcp_map_points_get.argtypes = [vp, ip, ip, vp, vp, vp, vp]
+    L.mcp_scene_depth_robust.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp]
+    L.mcp_ba_write_back.argtypes = [vp, vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mcp_map_points_last_timing.argtypes = [vp, vp, vp, vp]
+    L._write_back_bound = True
+    return L
+
+
+def _csr(seg_start, seg_rows, seg_weights):
+    ss = np.ascontiguousarray(seg_start, dtype=np.int32)
+    sr = np.ascontiguousarray(seg_rows, dtype=np.int32)
+    sw = np.ascontiguousarray(seg_weights, dtype=np.float64)
+    if len(sr) != len(sw):
+        raise ValueError("seg_rows and seg_weights differ in length")
+    return ss, sr, sw
+
+
+def huber_sigma_squared(err_sq):
+    """Huber::FindSigmaSquared (include/mcptam/MEstimator.h:194-204)."""
+    e = np.sort(np.asarray(err_sq, dtype=np.float64))
+    n = len(e)
+    sigma = 1.4826 * (1 + 5.0 / (n * 2 - 6)) * math.sqrt(e[n // 2])
+    sigma = 1.345 * sigma
+    return sigma * sigma
+
+
+def scene_depth_robust(depths, weights):
+    """KeyFrame::RefreshSceneDepthRobust(vector&) (src/KeyFrame.cc:585-645) on one list, summing in the reference's order (the list sorted as
+    std::pair<double, double> sorts).  Returns a dict with the fields of mcp_scene_depth; n <= 3: refreshed = 0 and nothing else."""
+    d = np.asarray(depths, dtype=np.float64)
+    w = np.asarray(weights, dtype=np.float64)
+    n = len(d)
+    if n <= 3:
+        return dict(n=n, refreshed=0)
+    order = np.lexsort((w, d))
+    d, w = d[order], w[order]
+    median = float(d[n // 2])
+    e2 = (d - median) * (d - median)
+    sigma_sq = max(huber_sigma_squared(e2), 0.4)
+    s_d = s_dd = s_w = 0.0
+    for i in range(n):
+        hw = math.sqrt(1.0 if e2[i] < sigma_sq else math.sqrt(sigma_sq / e2[i]))
+        cw = float(w[i]) * hw
+        s_d += cw * float(d[i])
+        s_dd += cw * float(d[i]) * float(d[i])
+        s_w += cw
+    with np.errstate(all="ignore"):
+        mean = float(np.float64(s_d) / np.float64(s_w))
+        sigma = float(np.sqrt(np.float64(s_dd) / np.float64(s_w) - np.float64(mean) * np.float64(mean)))
+    return dict(n=n, refreshed=1 if math.isfinite(mean) else -1, mean=mean, sigma=sigma, median=median, sigma_sq=sigma_sq)
+
+
+def _mat3_vec(R, v):
+    """R v for batches R (n, 3, 3), v (n, 3), every row summed left to right (no fused multiply-add, no BLAS): the device's order."""
+    return np.stack([R[:, i, 0] * v[:, 0] + R[:, i, 1] * v[:, 1] + R[:, i, 2] * v[:, 2] for i in range(3)], axis=1)
+
+
+def _mat3t_vec(R, v):
+    return np.stack([R[:, 0, i] * v[:, 0] + R[:, 1, i] * v[:, 1] + R[:, 2, i] * v[:, 2] for i in range(3)], axis=1)
+
+
+def chain_pose(poses):
+    """Product of a chain of (R, t) poses as the solver composes it: starting from the identity, every link multiplied on from the left
+    (CamFromBase * BaseFromWorld for {MKF, camera}), sums left to right -- the bits of the device's chain table."""
+    R, t = np.eye(3), np.zeros(3)
+    for Rk, tk in poses:
+        Rk, tk = np.asarray(Rk, dtype=np.float64), np.asarray(tk, dtype=np.float64)
+        Rn = np.array([[Rk[i, 0] * R[0, j] + Rk[i, 1] * R[1, j] + Rk[i, 2] * R[2, j] for j in range(3)] for i in range(3)])
+        tn = np.array([(Rk[i, 0] * t[0] + Rk[i, 1] * t[1] + Rk[i, 2] * t[2]) + tk[i] for i in range(3)])
+        R, t = Rn, tn
+    return R, t
+
+
+def write_back_point(x, own_pose, fixed, center_nc, one_right_nc, one_down_nc, src_pose=None):
+    """The point step of AdjustAndUpdate (src/BundleAdjusterMulti.cc:307-319) for one point: world = own_pose^-1 * x (a fixed point: x), then
+    MapPoint::RefreshPixelVectors at src_pose (default: own_pose) -- stereo.pixel_vectors.  Returns (world, pixel_right_w, pixel_down_w)."""
+    from .stereo import pixel_vectors
+    x = np.asarray(x, dtype=np.float64)
+    Ro, to = own_pose
+    world = x.copy() if fixed else Ro.T @ (x - to)
+    pr, pd = pixel_vectors(own_pose if src_pose is None else src_pose, np.asarray(center_nc, dtype=np.float64), np.asarray(one_right_nc, dtype=np.float64),
+                           np.asarray(one_down_nc, dtype=np.float64), world)
+    return world, pr[0], pd[0]
+
+
+def write_back_points(x, own_R, own_t, fixed, center_nc, one_right_nc, one_down_nc, src_R=None, src_t=None):
+    """write_back_point for n points at once, in the device's order of operations (IEEE double, no contraction: the same bits): x (n, 3),
+    own_R (n, 3, 3) / own_t (n, 3) the product of each point's own chain, fixed (n,), the rays (n, 3) each, src_R / src_t the pose
+    RefreshPixelVectors uses (default: own).  Returns (world, pixel_right_w, pixel_down_w), (n, 3) each."""
+    x = np.asarray(x, dtype=np.float64)
+    fixed = np.asarray(fixed, dtype=bool)
+    world = np.where(fixed[:, None], x, _mat3t_vec(own_R, x - own_t))
+    Rs, ts = (own_R, own_t) if src_R is None else (src_R, src_t)
+    h = np.abs((_mat3_vec(Rs, world) + ts)[:, 2])
+    c = center_nc * h[:, None] / np.abs(center_nc[:, 2])[:, None]
+    r = one_right_nc * h[:, None] / np.abs(one_right_nc[:, 2])[:, None] - c
+    d = one_down_nc * h[:, None] / np.abs(one_down_nc[:, 2])[:, None] - c
+    return world, _mat3t_vec(Rs, r), _mat3t_vec(Rs, d)
+
+
+def scene_depths(cam_from_world, world_pos):
+    """norm(CamFromWorld * mv3WorldPos) (src/KeyFrame.cc:561-567) for an (n, 3) array of positions."""
+    R, t = cam_from_world
+    w = np.asarray(world_pos, dtype=np.float64)
+    xc = _mat3_vec(np.broadcast_to(R, (len(w), 3, 3)), w) + t
+    return np.sqrt(xc[:, 0] * xc[:, 0] + xc[:, 1] * xc[:, 1] + xc[:, 2] * xc[:, 2])
