@@ -526,6 +526,52 @@ int mcp_ba_write_back(mcp_ba*, mcp_map_points*, int n_points, const int* point_i
  * stream: the copy of the packed inputs, the chain table + point kernel (0 for mcp_scene_depth_robust), the scene-depth kernel.  Each may be NULL. */
 int mcp_map_points_last_timing(const mcp_map_points*, double* copy_ms, double* points_ms, double* depth_ms);
 
+/* ---- MapMakerServerBase::ReFind_Common over the table in ONE submission ---------------------------- src/MapMakerServerBase.cc:921-1080
+ * ReFindInSingleKeyFrame (every point of the map against a new keyframe), ReFindNewlyMade (every new point against every keyframe) and
+ * ReFindFromFailureQueue all run ReFind_Common per (keyframe, point) pair.  The caller keeps the early-outs that read its own sets (:925-937:
+ * measurement and never-retry sets, mbBad, CrossCamera) and passes the pairs that survive them as (table row, target index).  Per pair and on
+ * the device, from the row's columns (world position, pixel vectors, patch source, level, centre, key): the projection and the inclusive
+ * in-image test (:941-956), MakeTemplateCoarse with the warp's verdict ignored, FindPatchCoarse with range 4, and above level 0
+ * MakeSubPixTemplate + eight sub-pixel iterations whose position is kept converged or not (:958-987) -- MCP_PF_REFIND of mcp_patch_sequences,
+ * the same device code.  The row's patch source is resolved per call through the registry of live keyframes; a stale source is never
+ * dereferenced.  `usable` is NOT consulted (new points are not optimised yet when ReFindNewlyMade runs); the table's per-(row, camera)
+ * tracker finders are neither read nor written.  Pairs are processed as given: duplicates are not detected.
+ * FINDERS, exactly mcp_patch_sequences' sequences: per_row_finders = 0: every pair is its own sequence (ReFindInSingleKeyFrame, the failure
+ * queue); per_row_finders = 1: each maximal run of consecutive pairs with the same row is one sequence that one finder walks in order
+ * (ReFindNewlyMade: keyframes with similar warps share the point's template).  *finder enters the first sequence, every other sequence starts
+ * from a zeroed state; on return *finder is the state of the last sequence after its last pair.  finder == NULL: a fresh one, nothing
+ * returned.  A pair that fails the projection test (or has no source) does not touch a finder.  The point key is the row's key.
+ * OUTPUTS: verdict[i] for every pair; meas (cap_meas entries) receives the FOUND pairs in ascending pair index, or -- meas == NULL -- they
+ * stay in the library's pinned block (mcp_map_refind_view, valid until the next call on this table); res is always filled.  More than cap_meas
+ * FOUND pairs: -1, verdicts and counts filled, meas untouched (mcp_track_find_pvs's rule).
+ * ORDER: enqueued on the table's stream -- uploads and a write-back issued before it are seen whole -- one copy of the packed inputs, four
+ * launches, one wait.  Targets must be on the table's device; their pyramids are those of the last mcp_kf_* call.  Any number of targets.
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, outputs untouched): NULL table; negative counts; a NULL pointer with a positive count; a
+ * NULL or destroyed target keyframe; a bad camera; a target on another device; a row or target index out of range. */
+#define MCP_REFIND_FOUND        1   /* a Measurement was produced                                   */
+#define MCP_REFIND_OUTSIDE      2   /* camera.Invalid() or outside [0,size] (:945-956)              */
+#define MCP_REFIND_TEMPLATE_BAD 3   /* finder.TemplateBad() (:961-965)                              */
+#define MCP_REFIND_NOT_FOUND    4   /* FindPatchCoarse failed (:968-973)                            */
+#define MCP_REFIND_NO_SOURCE    5   /* row without a source, or its source keyframe was destroyed   */
+/* 2..4 are what the reference puts into spNeverRetryKFs; 5 cannot occur there, is not a never-retry, and is counted */
+
+typedef struct mcp_refind_target { mcp_kf* kf; const mcp_camera* cam; double cam_from_world[12]; } mcp_refind_target;
+typedef struct mcp_refind_meas {
+  int pair, row, target;      /* index into pairs[], and that pair                                 */
+  int level, subpix, score;   /* Measurement::nLevel, bSubPix; nBestSSD                            */
+  double root_pos[2];         /* v2RootPos, level-0 coordinates                                    */
+} mcp_refind_meas;
+typedef struct mcp_refind_result { int counts[6]; /* per verdict, [0] unused */ int n_meas; } mcp_refind_result;
+
+int mcp_map_refind(mcp_map_points*, int n_targets, const mcp_refind_target* targets,
+                   int n_pairs, const int* pairs /* n_pairs x (row, target) */, int per_row_finders,
+                   mcp_pf_state* finder /* in/out, NULL = a fresh one and nothing returned */,
+                   uint8_t* verdict /* n_pairs */, int cap_meas, mcp_refind_meas* meas /* NULL: stay in the pinned block */,
+                   mcp_refind_result* res);
+/* zero-copy: the measurements of the last mcp_map_refind on this table (also when it copied them out); NULL + count 0 when there are none,
+ * NULL + mcp_last_error() when the last call was refused or ran over its cap */
+const mcp_refind_meas* mcp_map_refind_view(const mcp_map_points*, int* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,17 @@ struct WriteBackResult {
   std::vector<double> seg_depths;
 };
 
+/// What MapMakerServerBase::ReFind_Common decided for a list of (row, target) pairs (mcp_map_refind): a verdict per pair (MCP_REFIND_*), the
+/// Measurements of the FOUND pairs in ascending pair index, the counts per verdict.  bKeepInPlace: vMeas stays empty and `view` points at the
+/// n_meas records in the library's pinned block, valid until the next ReFindPairs on the table.
+struct ReFindResult {
+  std::vector<uint8_t> verdict;
+  std::vector<mcp_refind_meas> vMeas;
+  const mcp_refind_meas* view = nullptr;
+  int n_meas = 0;
+  int counts[6] = {0, 0, 0, 0, 0, 0};
+};
+
 /// The map points Tracker::FindPVS reads (src/Tracker.cc:662-723), resident on one device: row = the caller's point index.
 class MapPointTable {
  public:
@@ -343,6 +354,26 @@ class MapPointTable {
                             lists.seg_weights.data(), r.kf_cam_from_world.data(), r.depth.data(), r.seg_depths.data()));
     r.world_pos.resize(3*(size_t)n); r.pixel_right_w.resize(3*(size_t)n); r.pixel_down_w.resize(3*(size_t)n);
     r.kf_cam_from_world.resize(12*(size_t)nkf); r.depth.resize((size_t)nkf); r.seg_depths.resize(lists.seg_rows.size());
+    return r;
+  }
+  // ---- MapMakerServerBase::ReFind_Common (src/MapMakerServerBase.cc:921-1002) over the table: mcp_map_refind
+  /// vPairs: (row, target index) per pair, the pairs that survive the caller's early-outs (:925-937), processed as given.  bOneFinderPerRow:
+  /// runs of one row share a finder (ReFindNewlyMade); pFinder: the map maker's static finder, in / out (nullptr: a fresh one).
+  ReFindResult ReFindPairs(const std::vector<mcp_refind_target>& vTargets, const std::vector<int>& vPairs, bool bOneFinderPerRow,
+                           mcp_pf_state* pFinder = nullptr, bool bKeepInPlace = false) {
+    if (vPairs.size() % 2) throw std::invalid_argument("MapPointTable::ReFindPairs: array sizes");
+    const int n = (int)(vPairs.size()/2);
+    ReFindResult r;
+    r.verdict.resize((size_t)n + 1);
+    if (!bKeepInPlace) r.vMeas.resize((size_t)n + 1);
+    mcp_refind_result res;
+    check(mcp_map_refind(mpDev, (int)vTargets.size(), vTargets.data(), n, vPairs.data(), bOneFinderPerRow ? 1 : 0, pFinder, r.verdict.data(), n,
+                         bKeepInPlace ? nullptr : r.vMeas.data(), &res));
+    r.verdict.resize((size_t)n);
+    r.n_meas = res.n_meas;
+    for (int k = 0; k < 6; ++k) r.counts[k] = res.counts[k];
+    if (bKeepInPlace) { int m = 0; r.view = mcp_map_refind_view(mpDev, &m); if (m != res.n_meas) throw std::runtime_error(mcp_last_error()); }
+    else r.vMeas.resize((size_t)res.n_meas);
     return r;
   }
   mcp_map_points* Handle() const { return mpDev; }

@@ -1,5 +1,6 @@
 // img_api.hip -- C ABI of the KeyFrame / Tracker image path (include/mcp_img.h); host side only
-// marshals buffers and launches the kernels of img_kernels.h and pvs_kernels.h.  No CPU fallback.
+// marshals buffers and launches the kernels of img_kernels.h, pvs_kernels.h, track_map_kernels.h, stereo_kernels.h, write_back_kernels.h
+// and refind_kernels.h.  No CPU fallback.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -20,6 +21,7 @@
 #include "track_map_kernels.h"
 #include "stereo_kernels.h"
 #include "write_back_kernels.h"
+#include "refind_kernels.h"
 #include "ba_bridge.h"
 #include "ba_select.h"
 
@@ -1154,6 +1156,9 @@ struct mcp_map_points {
   PinBuf<char> wb_in; Buf<char> wb_dev; PinBuf<char> wb_out; Buf<double> wb_T, wb_depth; hipEvent_t wb_ev = nullptr;
   std::vector<int> wb_slot, wb_mark; int wb_stamp = 0;      // (wb_mark[row] == wb_stamp: the row was named earlier in this call)
   hipEvent_t wb_t[4] = {nullptr, nullptr, nullptr, nullptr}; bool wb_timed = false;      // mcp_map_points_last_timing: input copy | points | scene depth
+  // mcp_map_refind: the packed inputs (pinned | device), the passes' scratch, the pinned results (RfOut | verdict bytes | measurements)
+  PinBuf<char> rf_in; Buf<char> rf_dev; Buf<uint8_t> rf_flags, rf_vd; Buf<int> rf_blk, rf_first; Buf<RfItem> rf_items; Buf<mcp_refind_meas> rf_cand; PinBuf<char> rf_out;
+  size_t rf_meas_off = 0; int rf_view = -1;            // mcp_map_refind_view: where the measurements start in rf_out, how many (-1: none to show)
   int ensure_rays() {
     if (rays.p && rays.n >= 9*pts.n) return 0;
     Buf<double> r2; if (r2.alloc(9*std::max<size_t>(pts.n, 1))) return -1;
@@ -2031,6 +2036,107 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
     if (seg_depths_out && total) std::memcpy(seg_depths_out, hout + L.depths, 8*(size_t)total);
   }
   return 0;
+}
+
+}  // extern "C"
+
+// ---- ReFind_Common over the table (include/mcp_img.h mcp_map_refind, refind_kernels.h) ----------------------------------------------
+extern "C" {
+
+int mcp_map_refind(mcp_map_points* m, int n_targets, const mcp_refind_target* targets, int n_pairs, const int* pairs, int per_row_finders,
+                   mcp_pf_state* finder, uint8_t* verdict, int cap_meas, mcp_refind_meas* meas, mcp_refind_result* res) {
+  static_assert(sizeof(mcp_pf_state) % 8 == 0 && sizeof(RfTarget) % 8 == 0 && sizeof(TmSlot) % 8 == 0, "the packed inputs keep 8-byte alignment");
+  if (!m) return img_fail("mcp_map_refind: NULL table");
+  m->rf_view = -1;
+  if (n_targets < 0 || n_pairs < 0 || cap_meas < 0 || !res || (n_pairs > 0 && (!pairs || !verdict || !targets || n_targets == 0)) || (n_targets > 0 && !targets))
+    return img_fail("mcp_map_refind: bad arguments");
+  for (int t = 0; t < n_targets; ++t) {
+    const mcp_refind_target& G = targets[t];
+    if (!G.kf || !kf_live(G.kf)) return img_fail("mcp_map_refind: target " + std::to_string(t) + " has no live keyframe");
+    if (!cam_ok(G.cam)) return img_fail("mcp_map_refind: target " + std::to_string(t) + " has a bad camera");
+    if (G.kf->device != m->device)
+      return img_fail("mcp_map_refind: target " + std::to_string(t) + " is on device " + std::to_string(G.kf->device) + ", the table on device " + std::to_string(m->device));
+  }
+  const int rows = m->rows;
+  for (int i = 0; i < n_pairs; ++i) {
+    if (pairs[2*(size_t)i] < 0 || pairs[2*(size_t)i] >= rows) return img_fail("mcp_map_refind: pair " + std::to_string(i) + " names row " + std::to_string(pairs[2*(size_t)i]) + ", the table has " + std::to_string(rows));
+    if (pairs[2*(size_t)i + 1] < 0 || pairs[2*(size_t)i + 1] >= n_targets) return img_fail("mcp_map_refind: pair " + std::to_string(i) + " names target " + std::to_string(pairs[2*(size_t)i + 1]) + " of " + std::to_string(n_targets));
+  }
+  std::memset(res, 0, sizeof *res);
+  if (n_pairs == 0) { m->rf_view = 0; return 0; }
+  ICK(hipSetDevice(m->device));
+  const int n = n_pairs, nblk = (n + RF_BLOCK - 1)/RF_BLOCK;
+  const size_t nslot = std::max<size_t>(m->slots.size(), 1);
+  const int room = std::min(cap_meas, n);
+  // packed inputs: control block | FOUND and TEMPLATE_BAD counts per RF_BLOCK pairs (all zero) | targets | source slots | pairs | the finder
+  const size_t o_ctl = 0, o_fb = tm_align(sizeof(RfCtl)), o_tg = o_fb + tm_align(sizeof(int)*2*(size_t)nblk), o_sl = o_tg + tm_align(sizeof(RfTarget)*(size_t)n_targets);
+  const size_t o_pr = o_sl + tm_align(sizeof(TmSlot)*nslot), o_st = o_pr + tm_align(8*(size_t)n), blk = o_st + tm_align(sizeof(mcp_pf_state));
+  // pinned results: RfOut | verdict bytes | measurements
+  const size_t r_vd = tm_align(sizeof(RfOut)), r_ms = r_vd + tm_align((size_t)n), rblk = r_ms + sizeof(mcp_refind_meas)*(size_t)std::max(room, 1);
+  // everything is allocated before the first enqueue
+  if (m->rf_in.alloc(blk) || m->rf_dev.alloc(blk) || m->rf_out.alloc(rblk) || m->rf_flags.alloc(n) || m->rf_vd.alloc(n) || m->rf_blk.alloc(2*(size_t)nblk) ||
+      m->rf_items.alloc(n) || m->rf_first.alloc(n) || m->rf_cand.alloc(n)) return -1;
+  char* hb = m->rf_in.p;
+  std::memset(hb, 0, o_pr);
+  RfTarget* tab = reinterpret_cast<RfTarget*>(hb + o_tg);
+  for (int t = 0; t < n_targets; ++t) {
+    const mcp_refind_target& G = targets[t];
+    tab[t].T = G.kf->view(); tab[t].cam = *G.cam;
+    std::memcpy(tab[t].cfw.R, G.cam_from_world, 72); std::memcpy(tab[t].cfw.t, G.cam_from_world + 9, 24);
+  }
+  TmSlot* hs = reinterpret_cast<TmSlot*>(hb + o_sl);
+  {
+    std::lock_guard<std::mutex> reg(g_kf_mu);
+    for (size_t q = 0; q < m->slots.size(); ++q) {
+      const mcp_kf* s = m->slots[q].first;
+      auto live = s ? g_kf_live.find(s) : g_kf_live.end();
+      if (live == g_kf_live.end() || live->second != m->slots[q].second) continue;     // released, destroyed, or its address reused: dead
+      for (int l = 0; l < MCP_LEVELS; ++l) { hs[q].img[l] = s->lev[l].img.p; hs[q].w[l] = s->lev[l].w; hs[q].h[l] = s->lev[l].h; }
+      hs[q].live = 1;
+    }
+  }
+  std::memcpy(hb + o_pr, pairs, 8*(size_t)n);
+  if (finder) std::memcpy(hb + o_st, finder, sizeof(mcp_pf_state)); else std::memset(hb + o_st, 0, sizeof(mcp_pf_state));
+  hipStream_t st = m->st;
+  char* db = m->rf_dev.p;
+  RfCtl* ctl = reinterpret_cast<RfCtl*>(db + o_ctl);
+  int* found_blk = reinterpret_cast<int*>(db + o_fb); int* bad_blk = found_blk + nblk;
+  const RfTarget* d_tg = reinterpret_cast<const RfTarget*>(db + o_tg);
+  const TmSlot* d_sl = reinterpret_cast<const TmSlot*>(db + o_sl);
+  const int* d_pr = reinterpret_cast<const int*>(db + o_pr);
+  const mcp_pf_state* d_st = finder ? reinterpret_cast<const mcp_pf_state*>(db + o_st) : nullptr;
+  RfOut* h_out = reinterpret_cast<RfOut*>(m->rf_out.p);
+  uint8_t* h_vd = reinterpret_cast<uint8_t*>(m->rf_out.p + r_vd);
+  mcp_refind_meas* h_ms = reinterpret_cast<mcp_refind_meas*>(m->rf_out.p + r_ms);
+  struct Drain { mcp_map_points* m; bool armed; ~Drain() { if (armed) { (void)hipStreamSynchronize(m->st); (void)hipGetLastError(); } } } drain{m, true};
+  ICK(hipMemcpyAsync(db, hb, blk, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_rf_mark, dim3(nblk), dim3(RF_BLOCK), 0, st, n, per_row_finders ? 1 : 0, d_pr, d_tg, (const PvsPoint*)m->pts.p, (const TmSrc*)m->src.p, d_sl,
+                     m->rf_flags.p, m->rf_vd.p, m->rf_blk.p, m->rf_first.p, ctl);
+  hipLaunchKernelGGL(k_rf_scatter, dim3(nblk), dim3(RF_BLOCK), 0, st, n, nblk, (const uint8_t*)m->rf_flags.p, (const int*)m->rf_blk.p, d_pr, (const TmSrc*)m->src.p, m->rf_items.p, m->rf_first.p, ctl);
+  hipLaunchKernelGGL(k_rf_walk, dim3((unsigned)std::min(n, 65536)), dim3(64), 0, st, d_tg, (const PvsPoint*)m->pts.p, d_sl, (const RfItem*)m->rf_items.p, (const int*)m->rf_first.p, d_st,
+                     m->rf_vd.p, m->rf_cand.p, found_blk, bad_blk, ctl, &h_out->state);
+  hipLaunchKernelGGL(k_rf_commit, dim3(nblk), dim3(RF_BLOCK), 0, st, n, nblk, room, (const uint8_t*)m->rf_vd.p, (const mcp_refind_meas*)m->rf_cand.p, (const int*)found_blk,
+                     (const int*)bad_blk, (const RfItem*)m->rf_items.p, (const RfCtl*)ctl, d_st, h_vd, h_ms, h_out);
+  ICK(hipGetLastError());
+  ICK(hipStreamSynchronize(st));
+  drain.armed = false;
+  m->stage_busy = false;
+  for (int q = 0; q < 6; ++q) res->counts[q] = h_out->counts[q];
+  res->n_meas = h_out->n_meas;
+  std::memcpy(verdict, h_vd, (size_t)n);
+  if (finder) *finder = h_out->state;
+  if (res->n_meas > cap_meas)
+    return img_fail("mcp_map_refind: " + std::to_string(res->n_meas) + " pairs were found, cap_meas is " + std::to_string(cap_meas));
+  m->rf_meas_off = r_ms; m->rf_view = res->n_meas;
+  if (meas && res->n_meas) std::memcpy(meas, h_ms, sizeof(mcp_refind_meas)*(size_t)res->n_meas);
+  return 0;
+}
+
+const mcp_refind_meas* mcp_map_refind_view(const mcp_map_points* m, int* count) {
+  if (count) *count = 0;
+  if (!m || m->rf_view < 0) { img_fail("mcp_map_refind_view: the last mcp_map_refind on this table left no measurements to show"); return nullptr; }
+  if (count) *count = m->rf_view;
+  return m->rf_view > 0 ? reinterpret_cast<const mcp_refind_meas*>(m->rf_out.p + m->rf_meas_off) : nullptr;
 }
 
 }  // extern "C"

@@ -231,6 +231,12 @@ class MapPointTable:
                                  n_kf, ptr(kc), ptr(kl), ptr(ss), ptr(sr), ptr(sw), o("kf_cam_from_world"), o("depth"), o("seg_depths")), "ba_write_back")
         return res
 
+    def refind(self, targets, pairs, per_row_finders=False, finder=None, view=False, cap_meas=None):
+        """mcp_map_refind: MapMakerServerBase::ReFind_Common of (row, target) pairs in one call -- see mcptam_amd.refind.refind.  Returns
+        (verdicts, measurements, counts, finder)."""
+        from .refind import refind
+        return refind(self, targets, pairs, per_row_finders, finder, view, cap_meas)
+
     def set_source(self, keys, sources, levels, centers, fixed=None, first=0):
         """Rows first .. first+n-1: patch source keyframe (None = no source), level, centre (n x 2), fixed flag, and the row's identity key."""
         L = _bind_track_map(self._L)

@@ -7,9 +7,11 @@
 //     by the bodies below.
 // The reference runs ONE PatchFinder through each of these loops and PatchFinder is stateful (template cache of
 // MakeTemplateCoarseCont, src/PatchFinder.cc:144-181; Jacobians / mean difference of the sub-pixel iteration), so the loops become
-// SEQUENCES handed to mcp_patch_sequences (include/mcp_img.h): one wavefront walks one finder's items in order, its members live in
-// an mcp_pf_state.  The map-side bookkeeping (measurement maps, never-retry sets, failure queue) is the reference's, unchanged.
-// Needs KeyFrame::mpDev (shim/KeyFrame_gpu.cc) and shim/CameraExport.h.
+// SEQUENCES: one wavefront walks one finder's items in order, its members live in an mcp_pf_state.  The epipolar loops hand them to
+// mcp_patch_sequences, the re-find loops to mcp_map_refind, which reads the points from the resident map-point table (include/mcp_img.h).
+// The map-side bookkeeping (measurement maps, never-retry sets, failure queue) is the reference's, unchanged.
+// Needs KeyFrame::mpDev (shim/KeyFrame_gpu.cc), shim/CameraExport.h, and the table with MapPoint::mnTableRow (shim/Tracker_gpu.cc: the map
+// maker holds the same mcp_map_points* as mpMapTable).
 #include <mcptam/MapMakerServerBase.h>
 #include <mcptam/MapPoint.h>
 #include <mcptam/KeyFrame.h>
@@ -155,11 +157,16 @@ bool MapMakerServerBase::EpipolarRefine(KeyFrame& kfTarget, TaylorCamera& camera
   return false;
 }
 
-// ---- ReFind_Common (:921-1002) for one keyframe and MANY points, or one point and MANY keyframes: the checks that need no image
-// (:925-937) first, then one sequence per finder.  The reference's finder is `static` (:939): its cache can only hit when consecutive
-// calls carry the same MapPoint, which is what ReFindNewlyMade does (a new point walked over all keyframes), so there every point is
-// one sequence over its keyframes; ReFindInSingleKeyFrame and ReFindFromFailureQueue change the point from call to call, i.e. every
-// pair is a sequence of one.  mFinderStateReFind (a new member, zero-initialised) carries the static finder across calls.
+// ---- ReFind_Common (:921-1002) for one keyframe and MANY points, or one point and MANY keyframes: the checks that need the map's own
+// sets (:925-937) stay here; everything after them is ONE mcp_map_refind over the resident map-point table (shim/Tracker_gpu.cc keeps the
+// table and gives every MapPoint its row, MapPoint::mnTableRow): per pair the device projects, makes the template from the row's patch
+// source, searches and refines, and returns one verdict byte per pair and a Measurement record per found pair -- no mcp_pf_item goes up, no
+// mcp_td_out comes down.  The reference's finder is `static` (:939): its cache can only hit when consecutive calls carry the same MapPoint,
+// which is what ReFindNewlyMade does (a new point walked over all keyframes), so there every run of one point is one finder
+// (per_row_finders = 1); ReFindInSingleKeyFrame and ReFindFromFailureQueue change the point from call to call, i.e. every pair has its own.
+// mFinderStateReFind (a member, zero-initialised) carries the static finder across calls.  The table must hold the points' current
+// positions and sources: the map maker updates the rows it moves (mcp_ba_write_back does it for an adjustment) and uploads the rows of
+// new points (mcp_map_points_update / _update_source / _update_rays) before it re-finds them.
 int MapMakerServerBase::ReFindBatch(std::vector<std::pair<KeyFrame*, MapPoint*> >& vPairs, bool bOneFinderPerPoint)
 {
   // the early-outs of :925-937
@@ -182,8 +189,6 @@ int MapMakerServerBase::ReFindBatch(std::vector<std::pair<KeyFrame*, MapPoint*> 
 
   // targets: the distinct keyframes
   std::vector<KeyFrame*> vKFs;
-  std::vector<mcp_camera> vCams;
-  std::vector<mcp_pf_target> vTargets;
   std::map<KeyFrame*, int> mTargetIdx;
   for(unsigned i = 0; i < vWork.size(); ++i)
   {
@@ -193,71 +198,59 @@ int MapMakerServerBase::ReFindBatch(std::vector<std::pair<KeyFrame*, MapPoint*> 
     mTargetIdx[pKF] = (int)vKFs.size();
     vKFs.push_back(pKF);
   }
-  vCams.resize(vKFs.size());
-  vTargets.resize(vKFs.size());
+  std::vector<mcp_camera> vCams(vKFs.size());
+  std::vector<mcp_refind_target> vTargets(vKFs.size());
   for(unsigned t = 0; t < vKFs.size(); ++t)
   {
     ROS_ASSERT(vKFs[t]->mpDev);
     vCams[t] = mcptam_hip::CameraExport::Make(mmCameraModels[vKFs[t]->mCamName]);
     vTargets[t].kf = vKFs[t]->mpDev;
     vTargets[t].cam = &vCams[t];
-    ToArray12(vKFs[t]->mse3CamFromWorld, vTargets[t].base_from_world);
-    Identity12(vTargets[t].cam_from_base);
+    ToArray12(vKFs[t]->mse3CamFromWorld, vTargets[t].cam_from_world);
   }
 
-  // sequences
-  std::vector<mcp_pf_item> vItems(vWork.size());
-  std::vector<int> vSeqStart;
-  std::vector<mcp_pf_state> vStates;
+  // the pair list: (table row, target)
+  std::vector<int> vRowTarget(2*vWork.size());
   for(unsigned i = 0; i < vWork.size(); ++i)
   {
-    const bool bNewSeq = (i == 0) || !bOneFinderPerPoint || vWork[i].second != vWork[i - 1].second;
-    if(bNewSeq)
-    {
-      vSeqStart.push_back((int)i);
-      mcp_pf_state fresh;
-      std::memset(&fresh, 0, sizeof fresh);
-      vStates.push_back(i == 0 ? mFinderStateReFind : fresh);       // the static finder enters the first sequence ...
-    }
-    FillPoint(*vWork[i].second, vItems[i].point);
-    vItems[i].point_key = KeyOf(vWork[i].second);
-    vItems[i].target = mTargetIdx[vWork[i].first];
-    vItems[i].start_pos[0] = vItems[i].start_pos[1] = 0.0;
+    ROS_ASSERT(vWork[i].second->mnTableRow >= 0);
+    vRowTarget[2*i] = vWork[i].second->mnTableRow;
+    vRowTarget[2*i + 1] = mTargetIdx[vWork[i].first];
   }
-  vSeqStart.push_back((int)vWork.size());
-  std::vector<mcp_td_out> vOut(vWork.size());
-  if(mcp_patch_sequences(MCP_PF_REFIND, (int)vTargets.size(), &vTargets[0], (int)vStates.size(), &vSeqStart[0], &vItems[0], &vStates[0], 4, 8, 0, &vOut[0]) != 0)
+  std::vector<uint8_t> vVerdict(vWork.size());
+  mcp_refind_result res;
+  if(mcp_map_refind(mpMapTable, (int)vTargets.size(), &vTargets[0], (int)vWork.size(), &vRowTarget[0], bOneFinderPerPoint ? 1 : 0, &mFinderStateReFind,
+                    &vVerdict[0], (int)vWork.size(), NULL, &res) != 0)
   {
     ROS_FATAL_STREAM("MapMakerServerBase::ReFind: "<<mcp_last_error());
     ros::shutdown();
     return 0;
   }
-  mFinderStateReFind = vStates.back();                                  // ... and leaves with the last one
 
-  // the rest of ReFind_Common per pair (:941-1001)
-  int nFound = 0;
+  // the rest of ReFind_Common per pair (:941-1001): camera.Invalid() / outside the image (:945-955), TemplateBad (:960-964) and not found
+  // (:967-971) are never retried; a row whose patch source is gone (it cannot happen in the reference, which keeps the image) is left alone
   for(unsigned i = 0; i < vWork.size(); ++i)
   {
-    KeyFrame& kf = *vWork[i].first;
-    MapPoint& point = *vWork[i].second;
-    const mcp_td_out& out = vOut[i];
-    // camera.Invalid() / outside the image (:945-955), TemplateBad (:960-964), not found (:967-971)
-    if(!out.in_image || out.template_bad || !out.found)
-    {
-      point.mMMData.spNeverRetryKFs.insert(&kf);
-      continue;
-    }
+    if(vVerdict[i] == MCP_REFIND_OUTSIDE || vVerdict[i] == MCP_REFIND_TEMPLATE_BAD || vVerdict[i] == MCP_REFIND_NOT_FOUND)
+      vWork[i].second->mMMData.spNeverRetryKFs.insert(vWork[i].first);
+  }
+  int nMeas = 0;
+  const mcp_refind_meas* pMeasDev = mcp_map_refind_view(mpMapTable, &nMeas);     // read in place, in ascending pair index
+  for(int k = 0; k < nMeas; ++k)
+  {
+    const mcp_refind_meas& r = pMeasDev[k];
+    KeyFrame& kf = *vWork[r.pair].first;
+    MapPoint& point = *vWork[r.pair].second;
     Measurement* pMeas = new Measurement;
-    pMeas->nLevel = out.search_level;
+    pMeas->nLevel = r.level;
     pMeas->eSource = Measurement::SRC_REFIND;
-    pMeas->v2RootPos = makeVector(out.found_pos[0], out.found_pos[1]);    // sub-pixel position above level 0 (kept converged or not), coarse at level 0
-    pMeas->bSubPix = out.did_subpix != 0;
+    pMeas->v2RootPos = makeVector(r.root_pos[0], r.root_pos[1]);    // sub-pixel position above level 0 (kept converged or not), coarse at level 0
+    pMeas->bSubPix = r.subpix != 0;
     if(kf.mmpMeasurements.count(&point))
       ROS_BREAK();
     kf.AddMeasurement(&point, pMeas);
-    nFound++;
   }
-  return nFound;
+  return nMeas;
 }
 
 bool MapMakerServerBase::ReFind_Common(KeyFrame& kf, MapPoint& point)
