@@ -526,6 +526,89 @@ int mcp_ba_write_back(mcp_ba*, mcp_map_points*, int n_points, const int* point_i
  * stream: the copy of the packed inputs, the chain table + point kernel (0 for mcp_scene_depth_robust), the scene-depth kernel.  Each may be NULL. */
 int mcp_map_points_last_timing(const mcp_map_points*, double* copy_ms, double* points_ms, double* depth_ms);
 
+/* ---- TrackMap with its bookkeeping on the device ------------------------------- src/Tracker.cc:1157-1274, 1322-1361, 1452-1489, 1618-1658
+ * The counts column: MapPoint::mnMEstimatorInlierCount / mnMEstimatorOutlierCount of every row, two ints.  A row whose counts were never set
+ * reads (1, 0) -- the MapPoint constructor's values (include/mcptam/MapPoint.h:103-104) -- and so does a row that came into being as a gap, or
+ * one that mcp_map_points_resize dropped and a later growth brought back.  Growth, the duplicate-id check and the stream ordering are those of
+ * mcp_map_points_set / mcp_map_points_update; the other columns keep their contents.  inlier < 1 or outlier < 0 is refused with the column
+ * untouched (the reference asserts inlier > 0; every weight inlier / (inlier + outlier) stays finite).  Only these calls and
+ * mcp_track_map_record change counts: a key change in mcp_map_points_set_source does NOT reset them -- the owner of the table sets the counts
+ * when it puts a new point into a row.  mcp_map_points_get_counts waits for the table's stream. */
+int mcp_map_points_set_counts(mcp_map_points*, int first, int count, const int* inlier, const int* outlier);
+int mcp_map_points_update_counts(mcp_map_points*, int count, const int* ids, const int* inlier, const int* outlier);
+int mcp_map_points_get_counts(const mcp_map_points*, int first, int count, int* inlier, int* outlier);
+
+typedef struct mcp_track_record_params {
+  int lost;                     /* Tracker::IsLost() before this frame: != 0 -> searched-but-not-found items get no outlier mark (:1454)     */
+  int want_items;               /* != 0: the items as mcp_track_map leaves them (mcp_track_map_view); 0: no 320-byte item leaves the device */
+  int min_patches;              /* snMinPatchesPerFrame  } AssessTrackingQuality                                                            */
+  int coarse_min;               /* snCoarseMin           }                                                                                  */
+  double quality_good, quality_bad;   /* sdTrackingQualityGood / sdTrackingQualityBad                                                     */
+} mcp_track_record_params;
+
+/* 8 bytes per item, camera-major [C_c, T_c, R_c]: the order of mcp_track_map's items */
+typedef struct mcp_track_note {
+  int row;                      /* table row                                                                                                */
+  uint8_t cam, stage;           /* camera index; 0 = C, 1 = T, 2 = R                                                                         */
+  uint8_t level;                /* search_level, 255 = -1                                                                                   */
+  uint8_t flags;                /* MCP_TN_*                                                                                                 */
+} mcp_track_note;
+#define MCP_TN_SEARCHED     0x01
+#define MCP_TN_FOUND        0x02
+#define MCP_TN_DID_SUBPIX   0x04
+#define MCP_TN_TEMPLATE_BAD 0x08
+#define MCP_TN_IN_IMAGE     0x10
+#define MCP_TN_ATTEMPTED    0x20   /* !template_bad && level >= 0: the item counts in attempted[cam][level]                                */
+#define MCP_TN_MARK_SHIFT   6      /* bits 6-7, the mark of this frame: 0 none, 1 inlier, 2 outlier                                         */
+#define MCP_TN_MARK(flags)  (((flags) >> MCP_TN_MARK_SHIFT) & 3)
+
+/* 32 bytes per FOUND item, in item order: what SaveSimpleMeasurements / RecordMeasurements walk (:1157-1177, 1237-1274).  Every item's row was
+ * usable (!mbBad && mbOptimized) when the call started -- FindPVS admits no other -- so the list needs no mbBad filter. */
+typedef struct mcp_track_meas {
+  int item;                     /* index into the camera's items / notes                                                                    */
+  int row, level, subpix;       /* table row, search level, did_subpix                                                                      */
+  double found_pos[2];          /* TrackerData::mv2Found, level-0 coordinates                                                               */
+} mcp_track_meas;
+
+typedef struct mcp_track_record {
+  int attempted[MCP_MAX_FRAME_CAMS][MCP_LEVELS], found[MCP_MAX_FRAME_CAMS][MCP_LEVELS];   /* mmMeasAttemptedLevels / mmMeasFoundLevels       */
+  int quality[MCP_MAX_FRAME_CAMS];   /* 0 BAD, 1 DODGY, 2 GOOD: the arithmetic of AssessTrackingQuality (:1618-1658), in double             */
+  int quality_max;                   /* the maximum over the cameras: AssessOverallTrackingQuality before its host-only heuristics           */
+  int n_items[MCP_MAX_FRAME_CAMS], n_meas[MCP_MAX_FRAME_CAMS];
+  int n_inliers, n_outlier_marks;    /* mnNumInliers; all outlier marks of the frame                                                        */
+  double cam_from_world[MCP_MAX_FRAME_CAMS][12];   /* cam_from_base[c] * refined base_from_world: the bits the depth step used               */
+  mcp_scene_depth depth[MCP_MAX_FRAME_CAMS];       /* RefreshSceneDepth (:1180-1228); refreshed == 0: all other fields 0 but n               */
+} mcp_track_record;
+
+/* mcp_track_map plus the bookkeeping Tracker::TrackMap leaves behind, in one submission with one wait.
+ * POSE AND RESULT: base_from_world, res, the finders' states and the PVS views are mcp_track_map's, bit for bit; with want_items != 0 so are the
+ * items.  With want_items == 0 mcp_track_map_view returns NULL and mcp_last_error() says why.
+ * MARKS follow the weights of the last fine iteration (items of the coarse set keep the coarse search's record, as in mcp_track_map).  Per item:
+ *   !found: an outlier mark iff searched && !lost;   found && weight_last == 0.0: an outlier mark;   found && weight_last != 0.0: an inlier mark,
+ *   counted in n_inliers.
+ * Every mark adds 1 to the row's count column; a row tracked by several cameras is marked once per camera (integer atomic adds: the sums do not
+ * depend on the order).
+ * COUNTERS: attempted[c][l] counts the items of camera c with !template_bad && search_level == l >= 0, found[c][l] those that are found as well.
+ * quality[c]: with F / A the sums over the levels and LF / LA those over levels 2 and 3 -- F < min_patches: BAD; else t = (double)F / A,
+ * g = LA > coarse_min ? (double)LF / LA : t;  t > quality_good: GOOD;  else g < quality_bad: BAD;  else DODGY.
+ * MEASUREMENTS: camera c's found items in item order (mcp_track_map_meas_view).
+ * SCENE DEPTH runs after all marks of all cameras (a kernel boundary).  Camera c's list is its found items in item order, the weights
+ * (double)inlier / (double)(inlier + outlier) from the column as it then stands, the depth norm(cam_from_world[c] * world_pos[row]) with
+ * cam_from_world[c] = cam_from_base[c] * base_from_world AFTER the iterations (FindPVS's product).  One deviation: the reference reads td.mv3Cam, the value of the
+ * last re-projecting iteration (:1204); here every depth is taken at the final pose.  The
+ * kernel is mcp_scene_depth_robust's, the lists are built on the device: its summation-order contract holds word for word; n <= 3 gives
+ * refreshed = 0, a non-finite mean refreshed = -1.
+ * REFUSALS: mcp_track_map's, a NULL mcp_track_record_params / mcp_track_record, a non-finite quality threshold -- before anything is enqueued,
+ * with the counts column untouched. */
+int mcp_track_map_record(mcp_map_points*, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                         const uint8_t* const* const* masks, const mcp_camera* cams, double base_from_world[12], const double* cam_from_base /* ncam x 12 */,
+                         const mcp_track_map_params*, mcp_track_map_result* res, const mcp_track_record_params*, mcp_track_record* rec);
+/* zero-copy, in the library's pinned blocks, valid until the next track / PVS call on this table: camera cam's notes (one per item) and
+ * measurements (one per found item).  NULL + count 0 for an empty list; NULL + mcp_last_error() unless the last such call on the table was a
+ * successful mcp_track_map_record with that camera. */
+const mcp_track_note* mcp_track_map_notes_view(const mcp_map_points*, int cam, int* count);
+const mcp_track_meas* mcp_track_map_meas_view(const mcp_map_points*, int cam, int* count);
+
 /* ---- MapMakerServerBase::ReFind_Common over the table in ONE submission ---------------------------- src/MapMakerServerBase.cc:921-1080
  * ReFindInSingleKeyFrame (every point of the map against a new keyframe), ReFindNewlyMade (every new point against every keyframe) and
  * ReFindFromFailureQueue all run ReFind_Common per (keyframe, point) pair.  The caller keeps the early-outs that read its own sets (:925-937:

@@ -310,6 +310,39 @@ class MapPointTable {
     }
     return out;
   }
+  /// mnMEstimatorInlierCount / mnMEstimatorOutlierCount of rows first .. first+n-1 / of rows vIds (inlier >= 1, outlier >= 0).  A row never
+  /// named reads (1, 0).  A key change in SetSource leaves the counts alone: whoever puts a new point into a row sets them.
+  void SetCounts(int first, const std::vector<int>& vInlier, const std::vector<int>& vOutlier) {
+    if (vInlier.size() != vOutlier.size()) throw std::invalid_argument("MapPointTable::SetCounts: array sizes");
+    check(mcp_map_points_set_counts(mpDev, first, (int)vInlier.size(), vInlier.data(), vOutlier.data()));
+  }
+  void UpdateCounts(const std::vector<int>& vIds, const std::vector<int>& vInlier, const std::vector<int>& vOutlier) {
+    if (vInlier.size() != vIds.size() || vOutlier.size() != vIds.size()) throw std::invalid_argument("MapPointTable::UpdateCounts: array sizes");
+    check(mcp_map_points_update_counts(mpDev, (int)vIds.size(), vIds.data(), vInlier.data(), vOutlier.data()));
+  }
+  void GetCounts(int first, int n, std::vector<int>& vInlier, std::vector<int>& vOutlier) const {
+    vInlier.assign((size_t)n, 0); vOutlier.assign((size_t)n, 0);
+    check(mcp_map_points_get_counts(mpDev, first, n, vInlier.data(), vOutlier.data()));
+  }
+  /// TrackMap with its bookkeeping (mcp_track_map_record): the marks go into the count column, the level counters, quality, scene depth and
+  /// cam_from_world of every camera into *pRecord.  Notes (one per item) and measurements (one per found item) are read in place through
+  /// Notes() / Measurements() until the next track / PVS call; with recParams.want_items the items through mcp_track_map_view as well.
+  void TrackMapRecord(const std::vector<KeyFrame*>& vTargets, const std::vector<const uint8_t*>& vImages, const std::vector<int>& vStrides, bool bImagesOnDevice,
+                      const std::vector<mcp_camera>& vCams, double base_from_world[12], const std::vector<double>& vCamFromBase, const mcp_track_map_params& params,
+                      const mcp_track_record_params& recParams, mcp_track_map_result* pResult, mcp_track_record* pRecord) {
+    const int nc = (int)vTargets.size();
+    if ((int)vCams.size() != nc || (int)vCamFromBase.size() != 12*nc || (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !pRecord)
+      throw std::invalid_argument("MapPointTable::TrackMapRecord: array sizes");
+    std::vector<mcp_kf*> h(nc);
+    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    mcp_track_map_result r;
+    check(mcp_track_map_record(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
+                               nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord));
+    if (pResult) *pResult = r;
+  }
+  /// nullptr with *pnCount == 0: the camera's list is empty -- or the last track / PVS call was no TrackMapRecord with that camera (mcp_last_error())
+  const mcp_track_note* Notes(int nCam, int* pnCount) const { return mcp_track_map_notes_view(mpDev, nCam, pnCount); }
+  const mcp_track_meas* Measurements(int nCam, int* pnCount) const { return mcp_track_map_meas_view(mpDev, nCam, pnCount); }
   // ---- BundleAdjusterMulti::AdjustAndUpdate (src/BundleAdjusterMulti.cc:286-334) over the table: mcp_ba_write_back
   /// patch rays (mv3Center_NC, mv3OneRightFromCenter_NC, mv3OneDownFromCenter_NC; 3 doubles per point) of rows first .. / of rows vIds
   void SetRays(int first, const std::vector<double>& vCenter, const std::vector<double>& vOneRight, const std::vector<double>& vOneDown) {

@@ -22,6 +22,7 @@
 #include "stereo_kernels.h"
 #include "write_back_kernels.h"
 #include "refind_kernels.h"
+#include "track_record_kernels.h"
 #include "ba_bridge.h"
 #include "ba_select.h"
 
@@ -1149,7 +1150,13 @@ struct mcp_map_points {
   Buf<mcp_pvs_entry> tm_pvs; Buf<int> tm_counts, tm_sel; Buf<unsigned long long> tm_k0, tm_k1; Buf<uint8_t> tm_live, tm_blk; Buf<TmCtl> tm_ctl; Buf<TmSlot> tm_slots;
   Buf<mcp_pose_point> tm_crec, tm_frec; Buf<double> tm_w, tm_J, tm_ex, tm_e2; Buf<mcp_track_map_item> tm_items;
   PinBuf<uint8_t> h_blk; PinBuf<TmSlot> h_slots; PinBuf<mcp_track_map_item> h_items; PinBuf<TmOut> h_res;
-  int tm_ncam = 0; int tm_first[MCP_MAX_FRAME_CAMS + 1] = {};
+  int tm_ncam = 0; int tm_first[MCP_MAX_FRAME_CAMS + 1] = {}; bool tm_items_ok = false;      // (false: the last call kept its items on the device)
+  // the count column (inlier, outlier per row; capacity follows pts.n, new rows read (1, 0)), the staging of its uploads, and what
+  // mcp_track_map_record adds: its scratch and the pinned notes / measurements / record
+  Buf<int> cnt; PinBuf<int> h_cnt; Buf<int> d_cnt;
+  Buf<uint8_t> tr_flags; Buf<int> tr_tile, tr_seg_start, tr_seg_rows; Buf<TrAcc> tr_acc; Buf<double> tr_seg_w, tr_cfw;
+  PinBuf<mcp_track_note> h_notes; PinBuf<mcp_track_meas> h_meas; PinBuf<mcp_track_record> h_rec;
+  bool tr_ok = false; int tr_ncam = 0; int tr_meas_first[MCP_MAX_FRAME_CAMS + 1] = {};
   // AdjustAndUpdate write-back: the patch rays per row (9 doubles; capacity follows pts.n once the first rays arrive), which rows have them
   // (host), the staging of the ray uploads, and the packed inputs / pinned outputs of mcp_ba_write_back and mcp_scene_depth_robust
   Buf<double> rays; std::vector<uint8_t> has_rays; PinBuf<double> h_rays; Buf<double> d_rays;
@@ -1186,6 +1193,8 @@ struct mcp_map_points {
         if (st2[c].alloc(bigger.n)) return -1;
         if (rows) ICK(hipMemcpyAsync(st2[c].p, states[c].p, sizeof(mcp_pf_state)*(size_t)rows, hipMemcpyDeviceToDevice, st));
       }
+      Buf<int> cnt2; if (cnt2.alloc(2*bigger.n)) return -1;
+      if (rows && cnt.p) ICK(hipMemcpyAsync(cnt2.p, cnt.p, 2*sizeof(int)*(size_t)rows, hipMemcpyDeviceToDevice, st));
       Buf<double> rays2;
       if (rays.p) {
         if (rays2.alloc(9*bigger.n)) return -1;
@@ -1193,7 +1202,7 @@ struct mcp_map_points {
       }
       ICK(hipStreamSynchronize(st));                 // the old block is freed below, with nothing in flight on it
       stage_busy = false;
-      pts.swap(bigger); src.swap(src2);
+      pts.swap(bigger); src.swap(src2); cnt.swap(cnt2);
       if (rays2.p) rays.swap(rays2);
       for (int c = 0; c < st_ncam; ++c) states[c].swap(st2[c]);
     }
@@ -1201,6 +1210,9 @@ struct mcp_map_points {
     // (rows dropped by a resize come back without a source, and with finders that have seen nothing)
     ICK(hipMemsetAsync(src.p + rows, 0, sizeof(TmSrc)*(size_t)(new_rows - rows), st));
     for (int c = 0; c < st_ncam; ++c) ICK(hipMemsetAsync(states[c].p + rows, 0, sizeof(mcp_pf_state)*(size_t)(new_rows - rows), st));
+    // (... and with the counts of a point that has just been made: 1 inlier, 0 outliers)
+    hipLaunchKernelGGL(k_tr_counts_fill, dim3((unsigned)((new_rows - rows + 255)/256)), dim3(256), 0, st, cnt.p, rows, new_rows - rows);
+    ICK(hipGetLastError());
     row_slot.resize(new_rows, 0);
     has_rays.resize(new_rows, 0);                    // (a new row has no patch rays until mcp_map_points_set_rays / _update_rays names it)
     rows = new_rows;
@@ -1298,7 +1310,7 @@ int mcp_map_points_update(mcp_map_points* m, int count, const int* ids, const do
 int mcp_track_find_pvs(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb,
                        const int* caps, mcp_pvs_entry* const* out, int* counts) {
   if (!m) return img_fail("mcp_track_find_pvs: NULL table");
-  m->view_ncam = 0; m->pvs_on_device = false;
+  m->view_ncam = 0; m->pvs_on_device = false; m->tr_ok = false;
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !caps || !counts) return img_fail("mcp_track_find_pvs: bad arguments");
   for (int c = 0; c < ncam; ++c) {
     if (!targets[c] || !cam_ok(&cams[c]) || caps[c] < 0 || (out && !out[c])) return img_fail("mcp_track_find_pvs: bad arguments for camera " + std::to_string(c));
@@ -1460,23 +1472,25 @@ static bool tm_regs_ok() {
 
 static size_t tm_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
-int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
-                  const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
-                  mcp_track_map_result* res) {
-  if (!m) return img_fail("mcp_track_map: NULL table");
-  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail("mcp_track_map: bad arguments");
+// the body of mcp_track_map (rp == NULL: exactly its launches) and of mcp_track_map_record (rp, rec checked by the caller)
+static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                         const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
+                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec) {
+  if (!m) return img_fail(who + ": NULL table");
+  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail(who + ": bad arguments");
   if (prm->coarse_max < 0 || prm->coarse_range < 0 || prm->coarse_min < 0 || prm->coarse_subpix_its < 0 || prm->max_patches < 0)
-    return img_fail("mcp_track_map: negative cap, range or iteration count");
-  if (!est_ok(prm->estimator)) return img_fail("mcp_track_map: unknown M-estimator");
+    return img_fail(who + ": negative cap, range or iteration count");
+  if (!est_ok(prm->estimator)) return img_fail(who + ": unknown M-estimator");
   for (int c = 0; c < ncam; ++c) {
-    if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail("mcp_track_map: bad arguments for camera " + std::to_string(c));
+    if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail(who + ": bad arguments for camera " + std::to_string(c));
     if (targets[c]->device != m->device)
-      return img_fail("mcp_track_map: camera " + std::to_string(c) + "'s target is on device " + std::to_string(targets[c]->device) + ", the table on device " + std::to_string(m->device));
-    for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail("mcp_track_map: a keyframe appears twice in a frame with images");
+      return img_fail(who + ": camera " + std::to_string(c) + "'s target is on device " + std::to_string(targets[c]->device) + ", the table on device " + std::to_string(m->device));
+    for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail(who + ": a keyframe appears twice in a frame with images");
   }
   ICK(hipSetDevice(m->device));
   // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
-  m->view_ncam = 0; m->pvs_on_device = false; m->tm_ncam = 0;
+  m->view_ncam = 0; m->pvs_on_device = false; m->tm_ncam = 0; m->tr_ok = false;
+  const bool want_items = !rp || rp->want_items != 0;
   const int n = m->rows;
   const size_t NB = (size_t)ncam*std::max(n, 1);                   // bound of every per-item array: a camera's sets are distinct rows
   const bool coarse = prm->try_coarse && prm->coarse_max > 0;
@@ -1486,7 +1500,7 @@ int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uin
   if (m->ensure_states(ncam)) return -1;
   if (m->tm_pvs.alloc(NB) || m->tm_counts.alloc((size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS) || m->tm_sel.alloc(NB) || m->tm_k0.alloc(NB) || m->tm_k1.alloc(NB) || m->tm_live.alloc(NB) ||
       m->tm_ctl.alloc(1) || m->tm_slots.alloc(std::max<size_t>(m->slots.size(), 1)) || m->h_slots.alloc(std::max<size_t>(m->slots.size(), 1)) ||
-      m->tm_crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm_frec.alloc(NB) || m->tm_w.alloc(NB) || m->tm_items.alloc(NB) || m->h_items.alloc(NB) || m->h_res.alloc(1) ||
+      m->tm_crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm_frec.alloc(NB) || m->tm_w.alloc(NB) || m->tm_items.alloc(NB) || (want_items && m->h_items.alloc(NB)) || m->h_res.alloc(1) ||
       m->lvl.alloc(NB) || m->ent.alloc(NB) || m->blk_cnt.alloc((size_t)ncam*((std::max(n, 1) + PVS_BLOCK - 1)/PVS_BLOCK)*MCP_LEVELS) ||
       m->d_tab.alloc(MCP_MAX_FRAME_CAMS) || m->h_tab.alloc(MCP_MAX_FRAME_CAMS)) return -1;
   if (NB > (size_t)PRR_THREADS*PRR_PPT || !regs) {
@@ -1496,6 +1510,12 @@ int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uin
   const size_t o_tab = 0, o_cam = tm_align(sizeof(TmCam)*(size_t)ncam), o_cfb = o_cam + tm_align(sizeof(mcp_camera)*(size_t)ncam), o_pm = o_cfb + tm_align(96*(size_t)ncam);
   const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), blk = o_nl + tm_align(20);
   if (m->tm_blk.alloc(blk) || m->h_blk.alloc(blk)) return -1;
+  const size_t n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK;
+  if (rp) {
+    if (m->h_notes.alloc(NB) || m->h_meas.alloc(NB) || m->h_rec.alloc(1) || m->tr_flags.alloc(NB) || m->tr_tile.alloc(n_tile) || m->tr_acc.alloc(1) ||
+        m->tr_seg_start.alloc(MCP_MAX_FRAME_CAMS + 1) || m->tr_seg_rows.alloc(NB) || m->tr_seg_w.alloc(NB) || m->tr_cfw.alloc(12*MCP_MAX_FRAME_CAMS) || m->wb_depth.alloc(NB)) return -1;
+    std::memset(m->h_rec.p, 0, sizeof(mcp_track_record));          // (the cameras past ncam read as zeros)
+  }
   mcp_kf* k0 = targets[0];
   struct Drain { mcp_map_points* m; bool armed; int ncam; mcp_kf* const* targets; bool lite;
                  ~Drain() { if (armed) { (void)hipStreamSynchronize(m->st); if (lite) { (void)hipStreamSynchronize(targets[0]->st); (void)lite_batch_finish(ncam, targets); } m->tab_last.clear(); m->tm_ncam = 0; (void)hipGetLastError(); } } };
@@ -1589,7 +1609,21 @@ int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uin
   hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, (const PvsPoint*)m->pts.p,
                      (const TmSrc*)m->src.p, (const TmSlot*)m->tm_slots.p, (const int*)m->tm_sel.p, m->state_ptrs(), ctl, m->tm_items.p, m->tm_crec.p, m->tm_frec.p, m->tm_w.p);
   if (iterate(NB, &ctl->n_fine, nullptr, m->tm_frec.p, 1)) return -1;
-  hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm_w.p,
+  if (rp) {
+    // the bookkeeping, from the items, the last weights and the refined pose where the iterations left them
+    TrParams Q; Q.ncam = ncam; Q.lost = rp->lost ? 1 : 0; Q.min_patches = rp->min_patches; Q.coarse_min = rp->coarse_min; Q.good = rp->quality_good; Q.bad = rp->quality_bad;
+    const unsigned grid = (unsigned)std::min<size_t>(n_tile, 2048);
+    ICK(hipMemsetAsync(m->tr_acc.p, 0, sizeof(TrAcc), st));
+    hipLaunchKernelGGL(k_tr_mark, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, d_tab, (const double*)d_pm, (const mcp_track_map_item*)m->tm_items.p, (const double*)m->tm_w.p,
+                       m->cnt.p, m->h_notes.p, m->tr_flags.p, m->tr_tile.p, m->tr_acc.p, m->tr_cfw.p, &m->h_rec.p->cam_from_world[0][0]);
+    hipLaunchKernelGGL(k_tr_scatter, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, (const mcp_track_map_item*)m->tm_items.p, (const uint8_t*)m->tr_flags.p,
+                       (const int*)m->tr_tile.p, (const TrAcc*)m->tr_acc.p, (const int*)m->cnt.p, m->h_meas.p, m->tr_seg_start.p, m->tr_seg_rows.p, m->tr_seg_w.p, m->h_rec.p);
+    hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)ncam), dim3(SD_BLOCK), 0, st, (const double*)m->tr_cfw.p, (const int*)nullptr, (const int*)m->tr_seg_start.p,
+                       (const int*)m->tr_seg_rows.p, (const double*)m->tr_seg_w.p, (const PvsPoint*)m->pts.p, m->wb_depth.p, &m->h_rec.p->depth[0], (double*)nullptr);
+    ICK(hipGetLastError());
+  }
+  if (!want_items) hipLaunchKernelGGL(k_tr_finish, dim3(1), dim3(64), 0, st, P, (const TmCtl*)ctl, (const double*)d_pm, (const int*)m->tm_counts.p, m->h_res.p);
+  else hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm_w.p,
                      (const mcp_track_map_item*)m->tm_items.p, m->h_items.p,
                      (const double*)d_pm, (const int*)m->tm_counts.p, m->h_res.p);
   ICK(hipGetLastError());
@@ -1612,16 +1646,107 @@ int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uin
     res->stale[c] = R.ctl.stale[c];
     m->tm_first[c] = first; first += R.ctl.sizes[c][0] + R.ctl.sizes[c][1] + R.ctl.sizes[c][2];
   }
-  m->tm_first[ncam] = first; m->tm_ncam = ncam;
+  m->tm_first[ncam] = first; m->tm_ncam = ncam; m->tm_items_ok = want_items;
+  if (rp) {
+    *rec = *m->h_rec.p;
+    m->tr_meas_first[0] = 0;
+    for (int c = 0; c < ncam; ++c) m->tr_meas_first[c + 1] = m->tr_meas_first[c] + rec->n_meas[c];
+    m->tr_ncam = ncam; m->tr_ok = true;
+  }
   m->view_ncam = ncam; m->pvs_on_device = true; m->pvs_rows = n;
   std::memcpy(res->mu_last, R.mu, 48);
   std::memcpy(bfw, R.pose, 96);
   return 0;
 }
 
+int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                  const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
+                  mcp_track_map_result* res) {
+  return track_map_run("mcp_track_map", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, nullptr, nullptr);
+}
+
+int mcp_track_map_record(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                         const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
+                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec) {
+  if (!m) return img_fail("mcp_track_map_record: NULL table");
+  if (!rp || !rec) return img_fail("mcp_track_map_record: NULL record parameters or record");
+  if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_map_record: a quality threshold is not finite");
+  return track_map_run("mcp_track_map_record", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec);
+}
+
+const mcp_track_note* mcp_track_map_notes_view(const mcp_map_points* m, int cam, int* count) {
+  if (count) *count = 0;
+  if (!m || !m->tr_ok || cam < 0 || cam >= m->tr_ncam) { img_fail("mcp_track_map_notes_view: the last track / PVS call on this table was no mcp_track_map_record with that camera"); return nullptr; }
+  const int k = m->tm_first[cam + 1] - m->tm_first[cam];
+  if (count) *count = k;
+  return k > 0 ? m->h_notes.p + m->tm_first[cam] : nullptr;
+}
+const mcp_track_meas* mcp_track_map_meas_view(const mcp_map_points* m, int cam, int* count) {
+  if (count) *count = 0;
+  if (!m || !m->tr_ok || cam < 0 || cam >= m->tr_ncam) { img_fail("mcp_track_map_meas_view: the last track / PVS call on this table was no mcp_track_map_record with that camera"); return nullptr; }
+  const int k = m->tr_meas_first[cam + 1] - m->tr_meas_first[cam];
+  if (count) *count = k;
+  return k > 0 ? m->h_meas.p + m->tr_meas_first[cam] : nullptr;
+}
+
+// ---- the count column (include/mcp_img.h mcp_map_points_set_counts) --------------------------------------------------------------------
+static int counts_upload(mcp_map_points* m, const std::string& who, int first, int count, const int* ids, const int* inl, const int* outl) {
+  if (!m) return img_fail(who + ": NULL table");
+  if (count < 0 || (!ids && (first < 0 || (long long)first + count > 0x7fffffffLL)) || (count > 0 && (!inl || !outl))) return img_fail(who + ": bad arguments");
+  if (count == 0) return 0;
+  for (int k = 0; k < count; ++k)
+    if (inl[k] < 1 || outl[k] < 0) return img_fail(who + ": entry " + std::to_string(k) + " has inlier < 1 or outlier < 0");
+  int top = ids ? m->rows : first + count;
+  if (ids) {
+    for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(who + ": bad row id"); top = std::max(top, ids[k] + 1); }
+    m->sorted_ids.assign(ids, ids + count);
+    std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
+    for (int k = 1; k < count; ++k) if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail(who + ": row " + std::to_string(m->sorted_ids[k]) + " appears twice");
+  }
+  ICK(hipSetDevice(m->device));
+  if (m->wait_staging()) return -1;
+  if (m->h_cnt.alloc(2*(size_t)count) || (ids && m->h_ids.alloc(count))) return -1;
+  if (ids) {
+    if (2*(size_t)count > m->d_cnt.n || (size_t)count > m->d_ids.n) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
+    if (m->d_cnt.alloc(2*(size_t)count) || m->d_ids.alloc(count)) return -1;
+  }
+  for (int k = 0; k < count; ++k) { m->h_cnt.p[2*(size_t)k] = inl[k]; m->h_cnt.p[2*(size_t)k + 1] = outl[k]; if (ids) m->h_ids.p[k] = ids[k]; }
+  if (m->grow(top)) return -1;
+  if (!ids) ICK(hipMemcpyAsync(m->cnt.p + 2*(size_t)first, m->h_cnt.p, 2*sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+  else {
+    ICK(hipMemcpyAsync(m->d_cnt.p, m->h_cnt.p, 2*sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+    ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+    hipLaunchKernelGGL(k_tr_counts_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->cnt.p, count, (const int*)m->d_ids.p, (const int*)m->d_cnt.p);
+    ICK(hipGetLastError());
+  }
+  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  return 0;
+}
+int mcp_map_points_set_counts(mcp_map_points* m, int first, int count, const int* inl, const int* outl) {
+  return counts_upload(m, "mcp_map_points_set_counts", first, count, nullptr, inl, outl);
+}
+int mcp_map_points_update_counts(mcp_map_points* m, int count, const int* ids, const int* inl, const int* outl) {
+  if (m && count > 0 && !ids) return img_fail("mcp_map_points_update_counts: bad arguments");
+  return counts_upload(m, "mcp_map_points_update_counts", 0, count, ids, inl, outl);
+}
+int mcp_map_points_get_counts(const mcp_map_points* mc, int first, int count, int* inl, int* outl) {
+  if (!mc) return img_fail("mcp_map_points_get_counts: NULL table");
+  if (first < 0 || count < 0 || (long long)first + count > mc->rows) return img_fail("mcp_map_points_get_counts: bad arguments");
+  if (count == 0) return 0;
+  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
+  ICK(hipSetDevice(m->device));
+  std::vector<int> h(2*(size_t)count);
+  ICK(hipMemcpyAsync(h.data(), m->cnt.p + 2*(size_t)first, 2*sizeof(int)*(size_t)count, hipMemcpyDeviceToHost, m->st));
+  ICK(hipStreamSynchronize(m->st));
+  m->stage_busy = false;
+  for (int k = 0; k < count; ++k) { if (inl) inl[k] = h[2*(size_t)k]; if (outl) outl[k] = h[2*(size_t)k + 1]; }
+  return 0;
+}
+
 const mcp_track_map_item* mcp_track_map_view(const mcp_map_points* m, int cam, int* count) {
   if (count) *count = 0;
   if (!m || cam < 0 || cam >= m->tm_ncam) { img_fail("mcp_track_map_view: the last mcp_track_map on this table produced no items for that camera"); return nullptr; }
+  if (!m->tm_items_ok) { img_fail("mcp_track_map_view: the last call on this table was mcp_track_map_record with want_items = 0: no item left the device"); return nullptr; }
   const int k = m->tm_first[cam + 1] - m->tm_first[cam];
   if (count) *count = k;
   return k > 0 ? m->h_items.p + m->tm_first[cam] : nullptr;

@@ -270,6 +270,14 @@ __global__ void k_tm_gate(TmParams P, TmCtl* __restrict__ ctl) {
   C.fine_range = C.did_coarse ? 5 : 10;                            // SetupFineTracking :851-853
 }
 
+// the result block (pinned), by threads 0 .. 63 of one workgroup
+__device__ __forceinline__ void tm_write_out(const TmParams& P, const TmCtl* __restrict__ ctl, const double* __restrict__ pose_mu, const int* __restrict__ counts,
+                                             TmOut* __restrict__ res, int t) {
+  if (t < 18) { if (t < 12) res->pose[t] = pose_mu[t]; else res->mu[t - 12] = pose_mu[t]; }
+  if (t < P.ncam*MCP_LEVELS) (&res->counts[0][0])[t] = counts[t];
+  if (t == 0) res->ctl = *ctl;
+}
+
 // the items, with the weights of the last fine iteration, and the result block to pinned host memory.  The search kernels write the items
 // to device memory; they cross as 8-byte words, a wavefront's 64 consecutive words at a time.
 __global__ void __launch_bounds__(256)
@@ -288,12 +296,7 @@ k_tm_finish(TmParams P, const TmCtl* __restrict__ ctl, const double* __restrict_
     const long long i = g/W; const int q = (int)(g - i*W);
     dst[g] = q == 1 ? (unsigned long long)__double_as_longlong(weights[i]) : (q == W - 1 ? src[g] & last_mask : src[g]);
   }
-  if (blockIdx.x == 0) {
-    const int t = threadIdx.x;
-    if (t < 18) { if (t < 12) res->pose[t] = pose_mu[t]; else res->mu[t - 12] = pose_mu[t]; }
-    if (t < P.ncam*MCP_LEVELS) (&res->counts[0][0])[t] = counts[t];
-    if (t == 0) res->ctl = *ctl;
-  }
+  if (blockIdx.x == 0) tm_write_out(P, ctl, pose_mu, counts, res, threadIdx.x);
 }
 
 // mcp_map_points_set_source / _update_source: rows (ids[k], or first + k) <- recs[k]; a row whose key changes gets zeroed finders

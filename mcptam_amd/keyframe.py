@@ -49,6 +49,8 @@ IMG_SYMBOLS = [
     "mcp_track_map_view", "mcp_mix64", "mcp_track_shuffle_key", "mcp_stereo_points", "mcp_stereo_hypotheses",
     "mcp_map_points_set_rays", "mcp_map_points_update_rays", "mcp_map_points_get", "mcp_scene_depth_robust", "mcp_ba_write_back", "mcp_map_points_last_timing",
     "mcp_map_refind", "mcp_map_refind_view",
+    "mcp_map_points_set_counts", "mcp_map_points_update_counts", "mcp_map_points_get_counts", "mcp_track_map_record", "mcp_track_map_notes_view",
+    "mcp_track_map_meas_view",
 ]
 _BOUND = False
 

@@ -1,6 +1,8 @@
 """ctypes binding of Tracker::FindPVS and TrackMap over a device-resident map-point table (include/mcp_img.h: mcp_map_points_*,
 mcp_track_find_pvs, mcp_track_map).  The table holds, per row, what FindPVS reads of a MapPoint (world position, the two pixel vectors, usable =
-!mbBad && mbOptimized); one find_pvs call gives the potentially visible set of every camera of a frame, level by level."""
+!mbBad && mbOptimized); one find_pvs call gives the potentially visible set of every camera of a frame, level by level.  track_map runs the
+whole TrackMap of a frame from the table; track_map_record also leaves its bookkeeping (marks into the table's count column, level counters,
+quality, found measurements, scene depth), with track_record_restate / tracking_quality as the numpy restatements."""
 import ctypes
 import math
 
@@ -293,6 +295,75 @@ class MapPointTable:
             items.append(a.copy() if copy else a)
         return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res
 
+    # ---- TrackMap with its bookkeeping (include/mcp_img.h mcp_track_map_record) ----
+    def set_counts(self, inlier, outlier, first=0):
+        """mnMEstimatorInlierCount / mnMEstimatorOutlierCount of rows first .. first+n-1 (inlier >= 1, outlier >= 0)."""
+        L = _bind_track_record(self._L)
+        i, o = _counts_arrays(inlier, outlier)
+        _chk(L.mcp_map_points_set_counts(self._h, int(first), len(i), i.ctypes.data, o.ctypes.data), "map_points_set_counts")
+
+    def update_counts(self, ids, inlier, outlier):
+        L = _bind_track_record(self._L)
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        i, o = _counts_arrays(inlier, outlier)
+        if len(i) != len(ids):
+            raise ValueError("update_counts: ids and counts differ in length")
+        _chk(L.mcp_map_points_update_counts(self._h, len(ids), ids.ctypes.data, i.ctypes.data, o.ctypes.data), "map_points_update_counts")
+
+    def get_counts(self, first=0, count=None):
+        """(inlier, outlier) of rows first .. first+count-1; a row whose counts were never set reads (1, 0)."""
+        L = _bind_track_record(self._L)
+        count = self.rows - first if count is None else int(count)
+        i, o = np.zeros(max(count, 1), dtype=np.int32), np.zeros(max(count, 1), dtype=np.int32)
+        _chk(L.mcp_map_points_get_counts(self._h, int(first), count, i.ctypes.data, o.ctypes.data), "map_points_get_counts")
+        return i[:count], o[:count]
+
+    def track_map_record(self, targets, cams, base_from_world, cams_from_base, lost=False, want_items=True, min_patches=10, quality_coarse_min=20,
+                         quality_good=0.3, quality_bad=0.13, try_coarse=True, coarse_max=60, coarse_range=30, coarse_min=20, coarse_subpix_its=8,
+                         max_patches=1000, estimator="Tukey", seed=0, imgs=None, on_device=False, strides=None, copy=True):
+        """mcp_track_map_record: track_map plus what TrackMap leaves behind -- marks into the count column, level counters and quality, the
+        found measurements, the scene depth per camera.  quality_coarse_min is AssessTrackingQuality's snCoarseMin (coarse_min: the coarse
+        gate's).  Returns (items per camera, or None with want_items=False; (R, t); TrackMapResult; notes per camera (TRACK_NOTE_DTYPE);
+        measurements per camera (TRACK_MEAS_DTYPE); TrackRecord) -- copies unless copy=False."""
+        L = _bind_track_record(_bind_track_map(self._L))
+        ncam = len(targets)
+        hs = (ctypes.c_void_p * ncam)(*[t._h for t in targets])
+        cs = cams if isinstance(cams, ctypes.Array) else camera_array(cams)
+        b = _pose12(*base_from_world).copy()
+        cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1) if isinstance(cams_from_base, np.ndarray) else \
+            np.ascontiguousarray(np.concatenate([_pose12(*c) for c in cams_from_base]))
+        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
+                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
+        rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
+        res, rec = TrackMapResult(), TrackRecord()
+        ip = st = keep = None
+        if imgs is not None:
+            if on_device:
+                ip = (ctypes.c_void_p * ncam)(*[int(a) for a in imgs])
+                st = (ctypes.c_int * ncam)(*[int(s_) for s_ in (strides or [k.w for k in targets])])
+            else:
+                keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in imgs]
+                ip = (ctypes.c_void_p * ncam)(*[a.ctypes.data for a in keep])
+                st = (ctypes.c_int * ncam)(*[a.strides[0] for a in keep])
+        _chk(L.mcp_track_map_record(self._h, ncam, hs, ip, st, int(on_device), None, ctypes.cast(cs, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
+                                    ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec)), "track_map_record")
+        del keep
+
+        def views(fn, dtype, expect):
+            out = []
+            for c in range(ncam):
+                cnt = ctypes.c_int(0)
+                ptr = fn(self._h, c, ctypes.byref(cnt))
+                if cnt.value != expect[c]:
+                    raise RuntimeError("track_map_record: view of camera %d has %d entries, the record says %d: %s" % (c, cnt.value, expect[c], _cb.last_error()))
+                a = np.frombuffer((ctypes.c_char * (cnt.value * dtype.itemsize)).from_address(ptr), dtype=dtype) if cnt.value else np.zeros(0, dtype=dtype)
+                out.append(a.copy() if copy else a)
+            return out
+        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
+        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
+        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
+        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec
+
 
 # ---- Tracker::TrackMap of a frame from the table (include/mcp_img.h mcp_track_map) ---------------------------------------------------
 TRACK_MAP_SYMBOLS = ["mcp_map_points_set_source", "mcp_map_points_update_source", "mcp_map_points_get_states", "mcp_track_map", "mcp_track_map_view",
@@ -511,3 +582,111 @@ def scene_depths(cam_from_world, world_pos):
     w = np.asarray(world_pos, dtype=np.float64)
     xc = _mat3_vec(np.broadcast_to(R, (len(w), 3, 3)), w) + t
     return np.sqrt(xc[:, 0] * xc[:, 0] + xc[:, 1] * xc[:, 1] + xc[:, 2] * xc[:, 2])
+
+
+# ---- TrackMap's bookkeeping (include/mcp_img.h mcp_track_map_record) and its numpy restatement -------------------------------------------
+TRACK_RECORD_SYMBOLS = ["mcp_map_points_set_counts", "mcp_map_points_update_counts", "mcp_map_points_get_counts", "mcp_track_map_record",
+                        "mcp_track_map_notes_view", "mcp_track_map_meas_view"]
+TN_SEARCHED, TN_FOUND, TN_DID_SUBPIX, TN_TEMPLATE_BAD, TN_IN_IMAGE, TN_ATTEMPTED, TN_MARK_SHIFT = 1, 2, 4, 8, 16, 32, 6
+MARK_NONE, MARK_INLIER, MARK_OUTLIER = 0, 1, 2
+QUALITY_BAD, QUALITY_DODGY, QUALITY_GOOD = 0, 1, 2
+
+
+class TrackRecordParams(ctypes.Structure):
+    _fields_ = [("lost", ctypes.c_int), ("want_items", ctypes.c_int), ("min_patches", ctypes.c_int), ("coarse_min", ctypes.c_int),
+                ("quality_good", ctypes.c_double), ("quality_bad", ctypes.c_double)]
+
+
+class TrackNote(ctypes.Structure):
+    _fields_ = [("row", ctypes.c_int), ("cam", ctypes.c_uint8), ("stage", ctypes.c_uint8), ("level", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+class TrackMeas(ctypes.Structure):
+    _fields_ = [("item", ctypes.c_int), ("row", ctypes.c_int), ("level", ctypes.c_int), ("subpix", ctypes.c_int), ("found_pos", ctypes.c_double * 2)]
+
+
+class TrackRecord(ctypes.Structure):
+    _fields_ = [("attempted", (ctypes.c_int * LEVELS) * MAX_FRAME_CAMS), ("found", (ctypes.c_int * LEVELS) * MAX_FRAME_CAMS),
+                ("quality", ctypes.c_int * MAX_FRAME_CAMS), ("quality_max", ctypes.c_int), ("n_items", ctypes.c_int * MAX_FRAME_CAMS),
+                ("n_meas", ctypes.c_int * MAX_FRAME_CAMS), ("n_inliers", ctypes.c_int), ("n_outlier_marks", ctypes.c_int),
+                ("cam_from_world", (ctypes.c_double * 12) * MAX_FRAME_CAMS), ("depth", SceneDepth * MAX_FRAME_CAMS)]
+
+
+TRACK_NOTE_DTYPE = np.dtype([("row", "i4"), ("cam", "u1"), ("stage", "u1"), ("level", "u1"), ("flags", "u1")], align=True)
+TRACK_MEAS_DTYPE = np.dtype([("item", "i4"), ("row", "i4"), ("level", "i4"), ("subpix", "i4"), ("found_pos", "f8", 2)], align=True)
+assert TRACK_NOTE_DTYPE.itemsize == ctypes.sizeof(TrackNote) == 8 and TRACK_MEAS_DTYPE.itemsize == ctypes.sizeof(TrackMeas) == 32
+
+
+def _bind_track_record(L):
+    if getattr(L, "_track_record_bound", False):
+        return L
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.mcp_map_points_set_counts.argtypes = [vp, ip, ip, vp, vp]
+    L.mcp_map_points_update_counts.argtypes = [vp, ip, vp, vp, vp]
+    L.mcp_map_points_get_counts.argtypes = [vp, ip, ip, vp, vp]
+    L.mcp_track_map_record.argtypes = [vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp]
+    for f in (L.mcp_track_map_notes_view, L.mcp_track_map_meas_view):
+        f.restype = vp
+        f.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_int)]
+    L._track_record_bound = True
+    return L
+
+
+def _counts_arrays(inlier, outlier):
+    i, o = np.ascontiguousarray(inlier, dtype=np.int32), np.ascontiguousarray(outlier, dtype=np.int32)
+    if i.ndim != 1 or i.shape != o.shape:
+        raise ValueError("counts: inlier and outlier must be 1-d arrays of one length")
+    return i, o
+
+
+def tracking_quality(attempted, found, min_patches, coarse_min, good, bad):
+    """Tracker::AssessTrackingQuality (src/Tracker.cc:1618-1658) of one camera from its per-level counters: 0 BAD, 1 DODGY, 2 GOOD."""
+    a, f = [int(v) for v in attempted], [int(v) for v in found]
+    ta, tf, la, lf = sum(a), sum(f), sum(a[2:]), sum(f[2:])
+    if tf < min_patches:
+        return QUALITY_BAD
+    with np.errstate(all="ignore"):                          # (0 / 0 is a NaN that passes neither test: DODGY, as in C++)
+        total = np.float64(tf) / np.float64(ta)
+        large = np.float64(lf) / np.float64(la) if la > coarse_min else total
+    if total > good:
+        return QUALITY_GOOD
+    return QUALITY_BAD if large < bad else QUALITY_DODGY
+
+
+def track_record_restate(items, counts_before, lost, ncam):
+    """What mcp_track_map_record leaves behind, restated from the items of mcp_track_map (one TRACK_MAP_ITEM_DTYPE array per camera) and the
+    count column before the call, counts_before = (inlier, outlier).  Returns a dict: notes, meas (per camera), attempted, found
+    (MAX_FRAME_CAMS x LEVELS), n_items, n_meas, n_inliers, n_outlier_marks, counts = (inlier, outlier) after the marks, and the scene-depth
+    lists seg_start (ncam + 1), seg_rows, seg_w -- camera c's found items in item order, weighted inlier / (inlier + outlier) after ALL
+    marks of all cameras."""
+    inl, outl = np.array(counts_before[0], dtype=np.int64), np.array(counts_before[1], dtype=np.int64)
+    attempted, found = np.zeros((MAX_FRAME_CAMS, LEVELS), dtype=np.int32), np.zeros((MAX_FRAME_CAMS, LEVELS), dtype=np.int32)
+    notes, meas, n_inliers, n_out = [], [], 0, 0
+    for c in range(ncam):
+        it = items[c]
+        o = it["out"]
+        level = o["search_level"].astype(np.int64)
+        fnd, srch, bad = o["found"] != 0, o["searched"] != 0, o["template_bad"] != 0
+        att = ~bad & (level >= 0)
+        mark = np.where(fnd, np.where(it["weight_last"] == 0.0, MARK_OUTLIER, MARK_INLIER), np.where(srch & (not lost), MARK_OUTLIER, MARK_NONE))
+        nt = np.zeros(len(it), dtype=TRACK_NOTE_DTYPE)
+        nt["row"], nt["cam"], nt["stage"], nt["level"] = it["point"], c, it["stage"], level & 255
+        nt["flags"] = (srch * TN_SEARCHED + fnd * TN_FOUND + (o["did_subpix"] != 0) * TN_DID_SUBPIX + bad * TN_TEMPLATE_BAD + (o["in_image"] != 0) * TN_IN_IMAGE +
+                       att * TN_ATTEMPTED + (mark << TN_MARK_SHIFT)).astype(np.uint8)
+        notes.append(nt)
+        for l in range(LEVELS):
+            attempted[c, l] = int((att & (level == l)).sum())
+            found[c, l] = int((att & fnd & (level == l)).sum())
+        np.add.at(inl, it["point"][mark == MARK_INLIER], 1)
+        np.add.at(outl, it["point"][mark == MARK_OUTLIER], 1)
+        n_inliers += int((mark == MARK_INLIER).sum())
+        n_out += int((mark == MARK_OUTLIER).sum())
+        k = np.nonzero(fnd)[0]
+        ms = np.zeros(len(k), dtype=TRACK_MEAS_DTYPE)
+        ms["item"], ms["row"], ms["level"], ms["subpix"], ms["found_pos"] = k, it["point"][k], level[k], o["did_subpix"][k] != 0, o["found_pos"][k]
+        meas.append(ms)
+    seg_start = np.concatenate([[0], np.cumsum([len(m_) for m_ in meas])]).astype(np.int32)
+    seg_rows = np.concatenate([m_["row"] for m_ in meas] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
+    seg_w = inl[seg_rows].astype(np.float64) / (inl[seg_rows] + outl[seg_rows]).astype(np.float64)
+    return dict(notes=notes, meas=meas, attempted=attempted, found=found, n_items=[len(items[c]) for c in range(ncam)], n_meas=[len(m_) for m_ in meas],
+                n_inliers=n_inliers, n_outlier_marks=n_out, counts=(inl.astype(np.int32), outl.astype(np.int32)), seg_start=seg_start, seg_rows=seg_rows, seg_w=seg_w)

@@ -370,6 +370,7 @@ void Tracker::UploadMapTable()
   mvMapTableRows.clear();
   std::vector<double> vPos, vRight, vDown;
   std::vector<uint8_t> vUsable;
+  std::vector<int> vInlier, vOutlier;
   for(MapPointPtrList::iterator point_it = mMap.mlpPoints.begin(); point_it != mMap.mlpPoints.end(); ++point_it)
   {
     MapPoint& point = *(*point_it);
@@ -381,10 +382,13 @@ void Tracker::UploadMapTable()
       vDown.push_back(point.mv3PixelDown_W[k]);
     }
     vUsable.push_back((point.mbBad || !point.mbOptimized) ? 0 : 1);      // src/Tracker.cc:680
+    vInlier.push_back(point.mnMEstimatorInlierCount);                    // the count column mcp_track_map_record marks and weighs with
+    vOutlier.push_back(point.mnMEstimatorOutlierCount);
   }
   // rows = the map's size, also when the map has shrunk or is empty: every row of the table is then a row of mvMapTableRows
   if(mcp_map_points_resize(mpMapTable, (int)vUsable.size()) != 0 ||
-     (!vUsable.empty() && mcp_map_points_set(mpMapTable, 0, (int)vUsable.size(), &vPos[0], &vRight[0], &vDown[0], &vUsable[0]) != 0))
+     (!vUsable.empty() && (mcp_map_points_set(mpMapTable, 0, (int)vUsable.size(), &vPos[0], &vRight[0], &vDown[0], &vUsable[0]) != 0 ||
+                           mcp_map_points_set_counts(mpMapTable, 0, (int)vUsable.size(), &vInlier[0], &vOutlier[0]) != 0)))
   {
     ROS_FATAL_STREAM("Tracker::UploadMapTable: "<<mcp_last_error());
     ros::shutdown();
@@ -470,9 +474,16 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
 // that has seen nothing (a new key) or a template cache tested against another point's warp (a shared key).  A unique id per MapPoint
 // (a counter assigned when the point enters the map) avoids the second.  The cameras go in mvCurrCamNames order every frame (the
 // table keeps a finder per (row, camera index)).
-// What the host still does afterwards: the counters, mvIterationSets and the outlier marks are rebuilt from the items below; then
-// RefreshSceneDepth (:1085) as before.  Deviation: mv3Cam of the tracked points is the final pose's (the reference leaves the value of the
-// last ProjectAndDerivs).
+// The bookkeeping TrackMap leaves behind comes from the same submission (mcp_track_map_record with want_items = 0): the level counters and
+// the per-camera quality arithmetic, the inlier / outlier marks (applied to the table's count column on the device; the host repeats them
+// on the MapPoints from the 8-byte notes, so that the next UploadMapTable sends the same numbers up again), the found measurements (32
+// bytes each) and RefreshSceneDepth (:1085, :1180-1228) of every camera.  No 320-byte item crosses.  The host keeps mdTotalDepthMean,
+// IsDistanceToNearestMultiKeyFrameExcessive and mnLostFrames, and AssessOverallTrackingQuality's heuristics on top of rec.quality[].
+// Needs in class Tracker:   mcp_track_record mTrackRecord;   (the last frame's record, read by AssessTrackingQuality below)
+// Deviations: mv3Cam of the tracked points, and with it the depths of RefreshSceneDepth, are the final pose's (the reference leaves the
+// value of the last ProjectAndDerivs).  mv2Image / mm2CamDerivs of the TrackerData keep FindPVS's values of the prior pose: nothing after
+// TrackMap reads them before the next frame's FindPVS overwrites them (a caller that draws the re-projections asks for want_items = 1 and
+// reads mcp_track_map_view as before).
 void Tracker::UploadMapSources()
 {
   // caller holds mMap.mMutex; rows as UploadMapTable() wrote them
@@ -538,18 +549,26 @@ void Tracker::TrackMapOnDevice()
 
   double adBfW[12];
   ToArray12(mpCurrentMKF->mse3BaseFromWorld, adBfW);
+  mcp_track_record_params rprm;
+  rprm.lost = IsLost() ? 1 : 0;
+  rprm.want_items = 0;
+  rprm.min_patches = Tracker::snMinPatchesPerFrame;
+  rprm.coarse_min = Tracker::snCoarseMin;
+  rprm.quality_good = Tracker::sdTrackingQualityGood;
+  rprm.quality_bad = Tracker::sdTrackingQualityBad;
   mcp_track_map_result res;
   {
     boost::mutex::scoped_lock lock(mMap.mMutex);
-    UploadMapTable();
+    UploadMapTable();                                   // rows and their counts
     UploadMapSources();
-    if(mcp_track_map(mpMapTable, nCams, &vKF[0], NULL, NULL, 0, NULL, &vCams[0], adBfW, &vCfB[0], &prm, &res) != 0)
+    if(mcp_track_map_record(mpMapTable, nCams, &vKF[0], NULL, NULL, 0, NULL, &vCams[0], adBfW, &vCfB[0], &prm, &res, &rprm, &mTrackRecord) != 0)
     {
       ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: "<<mcp_last_error());
       ros::shutdown();
       return;
     }
   }
+  const mcp_track_record& rec = mTrackRecord;
   mbDidCoarse = res.did_coarse != 0;
   Matrix<3> m3R;
   Vector<3> v3T;
@@ -562,50 +581,89 @@ void Tracker::TrackMapOnDevice()
   mpCurrentMKF->mse3BaseFromWorld = SE3<>(SO3<>(m3R), v3T);
   UpdateCamsFromWorld();
 
-  // mvIterationSets, the level counters (SearchForPoints :1322, 1347, 1361) and the outlier marks of the last iteration (:1454-1488)
+  // mvIterationSets and the MapPoint counters from the notes, mv2Found from the measurements, the level maps and the scene depth from the record
   mvIterationSets.assign(nCams, TrackerDataPtrVector());
-  mnNumInliers = 0;
+  mnNumInliers = rec.n_inliers;
   for(int c = 0; c < nCams; ++c)
   {
     const std::string& camName = mvCurrCamNames[c];
-    const SE3<>& se3CamFromWorld = mpCurrentMKF->mmpKeyFrames[camName]->mse3CamFromWorld;
-    int n = 0;
-    const mcp_track_map_item* it = mcp_track_map_view(mpMapTable, c, &n);
+    KeyFrame& kf = *mpCurrentMKF->mmpKeyFrames[camName];
+    const SE3<>& se3CamFromWorld = kf.mse3CamFromWorld;
+    for(int l = 0; l < LEVELS; ++l)
+    {
+      mmMeasAttemptedLevels[camName][l] = rec.attempted[c][l];      // SearchForPoints :1322, 1347, 1361
+      mmMeasFoundLevels[camName][l] = rec.found[c][l];
+    }
+    int n = 0, nMeas = 0;
+    const mcp_track_note* pNotes = mcp_track_map_notes_view(mpMapTable, c, &n);
+    const mcp_track_meas* pMeas = mcp_track_map_meas_view(mpMapTable, c, &nMeas);
+    mvIterationSets[c].reserve(n);
     for(int i = 0; i < n; ++i)
     {
-      const mcp_td_out& o = it[i].out;
-      MapPoint& point = *mvMapTableRows[it[i].point];
+      const mcp_track_note& note = pNotes[i];
+      MapPoint& point = *mvMapTableRows[note.row];
       if(!point.mmpTData.count(camName))
         point.mmpTData[camName] = new TrackerData(&point, mmSizes[camName]);
       boost::intrusive_ptr<TrackerData> pTData(point.mmpTData[camName]);
       TrackerData& td = *pTData;
       td.mv3Cam = se3CamFromWorld * point.mv3WorldPos;
-      td.mbInImage = o.in_image != 0;
-      td.mv2Image = makeVector(o.image[0], o.image[1]);
-      td.mm2CamDerivs(0, 0) = o.cam_derivs[0]; td.mm2CamDerivs(0, 1) = o.cam_derivs[1];
-      td.mm2CamDerivs(1, 0) = o.cam_derivs[2]; td.mm2CamDerivs(1, 1) = o.cam_derivs[3];
-      td.mnSearchLevel = o.search_level;
-      td.mbSearched = o.searched != 0;
-      td.mbFound = o.found != 0;
-      td.mv2Found = makeVector(o.found_pos[0], o.found_pos[1]);
-      td.mdSqrtInvNoise = o.sqrt_inv_noise;
-      if(!o.template_bad && o.search_level >= 0)
-      {
-        mmMeasAttemptedLevels[camName][o.search_level]++;
-        if(o.found) mmMeasFoundLevels[camName][o.search_level]++;
-      }
-      if(!td.mbFound)
-      {
-        if(td.mbSearched && !IsLost()) point.mnMEstimatorOutlierCount++;
-      }
-      else if(it[i].weight_last == 0.0)
-        point.mnMEstimatorOutlierCount++;
-      else
-      {
-        point.mnMEstimatorInlierCount++;
-        mnNumInliers++;
-      }
+      td.mbInImage = (note.flags & MCP_TN_IN_IMAGE) != 0;
+      td.mnSearchLevel = note.level == 255 ? -1 : (int)note.level;
+      td.mbSearched = (note.flags & MCP_TN_SEARCHED) != 0;
+      td.mbFound = (note.flags & MCP_TN_FOUND) != 0;
+      td.mbDidSubPix = (note.flags & MCP_TN_DID_SUBPIX) != 0;
+      if(td.mnSearchLevel >= 0)
+        td.mdSqrtInvNoise = 1.0 / LevelScale(td.mnSearchLevel);
+      // the marks of the last iteration (:1452-1489), as the device applied them to the table's count column
+      if(MCP_TN_MARK(note.flags) == 1) point.mnMEstimatorInlierCount++;
+      else if(MCP_TN_MARK(note.flags) == 2) point.mnMEstimatorOutlierCount++;
       mvIterationSets[c].push_back(pTData);
     }
+    // the found items in item order: what SaveSimpleMeasurements / RecordMeasurements walk (:1157-1177, 1237-1274).  Every row was usable
+    // when the call started, so there is no mbBad to filter here
+    for(int k = 0; k < nMeas; ++k)
+      mvIterationSets[c][pMeas[k].item]->mv2Found = makeVector(pMeas[k].found_pos[0], pMeas[k].found_pos[1]);
+    // RefreshSceneDepth (:1180-1209): KeyFrame::RefreshSceneDepthRobust(vector&) of this camera ran on the device
+    if(rec.depth[c].refreshed == 1)
+    {
+      kf.mdSceneDepthMean = rec.depth[c].mean;
+      kf.mdSceneDepthSigma = rec.depth[c].sigma;
+    }
+    else if(rec.depth[c].refreshed < 0)                  // :635-644: the reference stops the process on a non-finite mean
+    {
+      ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: scene depth of "<<camName<<" is not finite");
+      ros::shutdown();
+      return;
+    }
   }
+  // the rest of RefreshSceneDepth (:1212-1226) stays on the host
+  double dSumDepth = 0.0;
+  int nNum = 0;
+  for(KeyFramePtrMap::iterator kf_it = mpCurrentMKF->mmpKeyFrames.begin(); kf_it != mpCurrentMKF->mmpKeyFrames.end(); ++kf_it)
+  {
+    KeyFrame& kf = *(kf_it->second);
+    if(!kf.mbActive)
+      continue;
+    dSumDepth += kf.mdSceneDepthMean;
+    ++nNum;
+  }
+  ROS_ASSERT(nNum > 0);
+  mpCurrentMKF->mdTotalDepthMean = dSumDepth/nNum;
+}
+
+// AssessTrackingQuality (:1618-1658) from the record of TrackMapOnDevice: the same arithmetic ran on the device from the same counters
+// (mnTotalAttempted / mnTotalFound are kept for the caller's messages)
+Tracker::TrackingQuality Tracker::AssessTrackingQuality(std::string cameraName)
+{
+  int c = 0;
+  while(c < (int)mvCurrCamNames.size() && mvCurrCamNames[c] != cameraName)
+    ++c;
+  ROS_ASSERT(c < (int)mvCurrCamNames.size());
+  mnTotalAttempted = mnTotalFound = 0;
+  for(int l = 0; l < LEVELS; ++l)
+  {
+    mnTotalAttempted += mTrackRecord.attempted[c][l];
+    mnTotalFound += mTrackRecord.found[c][l];
+  }
+  return mTrackRecord.quality[c] == 2 ? GOOD : (mTrackRecord.quality[c] == 1 ? DODGY : BAD);
 }
