@@ -1107,25 +1107,44 @@ int mcp_track_pose_update_m(int n, const uint8_t* found, const double* fpos, con
 }  // extern "C"
 
 // ---- Tracker::FindPVS over a device-resident map-point table (include/mcp_img.h, pvs_kernels.h) ------------------------------------
+static Se3 se3_of12(const double* a) { Se3 T; std::memcpy(T.R, a, 72); std::memcpy(T.t, a + 9, 24); return T; }
+static size_t tm_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// one column of the table: bytes per row, how a row that appears is filled, whether the column exists yet (the rays and the finders are
+// created on demand); its block holds the table's capacity in rows.  The table's own code moves blocks; everything else reads row().
+enum { FILL_ZERO, FILL_COUNTS /* (1, 0): 1 inlier, 0 outliers */, FILL_NONE };
+struct Column {
+  size_t bytes; int fill; bool on; Buf<char> block;
+  Column(size_t b, int f, bool o) : bytes(b), fill(f), on(o) {}
+  char* at(size_t r) const { return block.p + bytes*r; }
+};
+template <class T, int PER_ROW = 1> struct ColumnOf : Column {       // a row is PER_ROW elements of T
+  ColumnOf(int f, bool o) : Column(sizeof(T)*PER_ROW, f, o) {}
+  T* row(size_t r = 0) const { return reinterpret_cast<T*>(at(r)); }
+};
+struct FinderColumn : ColumnOf<mcp_pf_state> { FinderColumn() : ColumnOf(FILL_ZERO, false) {} };
+
 struct mcp_map_points {
   int device = 0; hipStream_t st = nullptr;
-  int rows = 0;
-  Buf<PvsPoint> pts;                                 // capacity = pts.n
-  // uploads: staged in pinned memory, copied (and scattered) on st; `staged` marks when the staging may be refilled
-  PinBuf<PvsPoint> h_recs; PinBuf<int> h_ids; Buf<PvsPoint> d_recs; Buf<int> d_ids;
+  int rows = 0; size_t cap = 0;                      // cap: the rows every live column has room for
+  // the columns: points | patch sources (TrackMap) | the persistent finders per (camera, row) | (inlier, outlier) counts | patch rays (9 doubles:
+  // AdjustAndUpdate).  A further column is its declaration here and its name in cols (the order grow copies and fills them in): the capacity,
+  // the fills and the uploads follow from that.
+  ColumnOf<PvsPoint> pts{FILL_ZERO, true}; ColumnOf<TmSrc> src{FILL_ZERO, true};
+  FinderColumn states[MCP_MAX_FRAME_CAMS]; int st_ncam = 0;
+  ColumnOf<int, 2> cnt{FILL_COUNTS, true}; ColumnOf<double, 9> rays{FILL_NONE, false};
+  std::vector<Column*> cols;                         // (pointers into this object: it is never copied)
+  mcp_map_points() { cols = {&pts, &src}; for (Column& s : states) cols.push_back(&s); cols.push_back(&cnt); cols.push_back(&rays); }
+  mcp_map_points(const mcp_map_points&) = delete;
+  std::vector<uint8_t> has_rays;                     // (host: which rows have patch rays)
+  // uploads: packed into pinned memory (records | ids), copied (and scattered from the device staging) on st; `staged` marks when the
+  // staging may be refilled.  One event serialises every upload, so one pair of blocks serves all columns.
+  PinBuf<char> up_in; Buf<char> up_dev;
   hipEvent_t staged = nullptr; bool stage_busy = false;
-  std::vector<int> sorted_ids;                       // duplicate check of mcp_map_points_update
-  // FindPVS: the camera table (uploaded when it changes), the passes' scratch, the pinned result block
-  PinBuf<PvsCam> h_tab; Buf<PvsCam> d_tab; std::vector<PvsCam> tab_last;
-  Buf<signed char> lvl; Buf<mcp_pvs_entry> ent; Buf<int> blk_cnt;
-  PinBuf<mcp_pvs_entry> h_out; PinBuf<int> h_counts;
-  int view_ncam = 0; int view_first[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; int view_count[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; bool view_ok[MCP_MAX_FRAME_CAMS] = {};
-  // mcp_track_map: the lists of its PVS stay in device memory (tm_pvs) until mcp_track_find_pvs_view asks for them
-  bool pvs_on_device = false; int pvs_rows = 0;      // (... laid out camera by camera at c * pvs_rows: the table's size at that call)
-  // TrackMap: patch sources per row (capacity = pts.n), the persistent finders per (camera, row), the source keyframes as (handle, serial)
-  Buf<TmSrc> src; Buf<mcp_pf_state> states[MCP_MAX_FRAME_CAMS]; int st_ncam = 0;
-  // slots are reference-counted by the rows that name them (row_slot: the host's copy of each row's slot1); a slot no row names is
-  // released and its index reused, so the table walked per call stays as long as the keyframes the map currently uses as sources
+  std::vector<int> sorted_ids;                       // duplicate check of the uploads by id
+  // the source keyframes as (handle, serial).  Slots are reference-counted by the rows that name them (row_slot: the host's copy of each
+  // row's slot1); a slot no row names is released and its index reused, so the table walked per call stays as long as the keyframes the
+  // map currently uses as sources
   std::vector<std::pair<const mcp_kf*, unsigned long long>> slots; std::map<std::pair<const mcp_kf*, unsigned long long>, int> slot_of;
   std::vector<int> slot_refs, free_slots, row_slot;
   int slot_acquire(const std::pair<const mcp_kf*, unsigned long long>& id) {      // 1 + index, one more reference
@@ -1145,93 +1164,194 @@ struct mcp_map_points {
     const int q = slot1 - 1;
     if (--slot_refs[q] == 0) { slot_of.erase(slots[q]); slots[q] = std::make_pair((const mcp_kf*)nullptr, 0ull); free_slots.push_back(q); }
   }
-  PinBuf<TmSrc> h_src; Buf<TmSrc> d_src;
+  // ---- what each call owns: its scratch, its pinned results, and what its views need; invalidate(): the last call's results are gone ----
+  // FindPVS: the camera table (uploaded when it changes), the passes' scratch, the pinned result block
+  struct Pvs {
+    PinBuf<PvsCam> h_tab; Buf<PvsCam> d_tab; std::vector<PvsCam> tab_last;
+    Buf<signed char> lvl; Buf<mcp_pvs_entry> ent; Buf<int> blk_cnt;
+    PinBuf<mcp_pvs_entry> h_out; PinBuf<int> h_counts;
+    int ncam = 0; int first[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; int count[MCP_MAX_FRAME_CAMS][MCP_LEVELS] = {}; bool ok[MCP_MAX_FRAME_CAMS] = {};
+    // mcp_track_map: the lists of its PVS stay in device memory (tm.pvs) until mcp_track_find_pvs_view asks for them
+    bool on_device = false; int rows = 0;            // (... laid out camera by camera at c * rows: the table's size at that call)
+    int reserve(int nc, int n) {                     // the scratch of the passes over n rows for nc cameras
+      const size_t nb = (size_t)nc*std::max(n, 1);
+      return (lvl.alloc(nb) || ent.alloc(nb) || blk_cnt.alloc((size_t)nc*((std::max(n, 1) + PVS_BLOCK - 1)/PVS_BLOCK)*MCP_LEVELS) ||
+              d_tab.alloc(MCP_MAX_FRAME_CAMS) || h_tab.alloc(MCP_MAX_FRAME_CAMS)) ? -1 : 0;
+    }
+    void invalidate() { ncam = 0; on_device = false; }
+  } pvs;
   // mcp_track_map's scratch and its pinned results
-  Buf<mcp_pvs_entry> tm_pvs; Buf<int> tm_counts, tm_sel; Buf<unsigned long long> tm_k0, tm_k1; Buf<uint8_t> tm_live, tm_blk; Buf<TmCtl> tm_ctl; Buf<TmSlot> tm_slots;
-  Buf<mcp_pose_point> tm_crec, tm_frec; Buf<double> tm_w, tm_J, tm_ex, tm_e2; Buf<mcp_track_map_item> tm_items;
-  PinBuf<uint8_t> h_blk; PinBuf<TmSlot> h_slots; PinBuf<mcp_track_map_item> h_items; PinBuf<TmOut> h_res;
-  int tm_ncam = 0; int tm_first[MCP_MAX_FRAME_CAMS + 1] = {}; bool tm_items_ok = false;      // (false: the last call kept its items on the device)
-  // the count column (inlier, outlier per row; capacity follows pts.n, new rows read (1, 0)), the staging of its uploads, and what
-  // mcp_track_map_record adds: its scratch and the pinned notes / measurements / record
-  Buf<int> cnt; PinBuf<int> h_cnt; Buf<int> d_cnt;
-  Buf<uint8_t> tr_flags; Buf<int> tr_tile, tr_seg_start, tr_seg_rows; Buf<TrAcc> tr_acc; Buf<double> tr_seg_w, tr_cfw;
-  PinBuf<mcp_track_note> h_notes; PinBuf<mcp_track_meas> h_meas; PinBuf<mcp_track_record> h_rec;
-  bool tr_ok = false; int tr_ncam = 0; int tr_meas_first[MCP_MAX_FRAME_CAMS + 1] = {};
-  // AdjustAndUpdate write-back: the patch rays per row (9 doubles; capacity follows pts.n once the first rays arrive), which rows have them
-  // (host), the staging of the ray uploads, and the packed inputs / pinned outputs of mcp_ba_write_back and mcp_scene_depth_robust
-  Buf<double> rays; std::vector<uint8_t> has_rays; PinBuf<double> h_rays; Buf<double> d_rays;
-  PinBuf<char> wb_in; Buf<char> wb_dev; PinBuf<char> wb_out; Buf<double> wb_T, wb_depth; hipEvent_t wb_ev = nullptr;
-  std::vector<int> wb_slot, wb_mark; int wb_stamp = 0;      // (wb_mark[row] == wb_stamp: the row was named earlier in this call)
-  hipEvent_t wb_t[4] = {nullptr, nullptr, nullptr, nullptr}; bool wb_timed = false;      // mcp_map_points_last_timing: input copy | points | scene depth
+  struct Tm {
+    Buf<mcp_pvs_entry> pvs; Buf<int> counts, sel; Buf<unsigned long long> k0, k1; Buf<uint8_t> live, blk; Buf<TmCtl> ctl; Buf<TmSlot> slots;
+    Buf<mcp_pose_point> crec, frec; Buf<double> w, J, ex, e2; Buf<mcp_track_map_item> items;
+    PinBuf<uint8_t> h_blk; PinBuf<TmSlot> h_slots; PinBuf<mcp_track_map_item> h_items; PinBuf<TmOut> h_res;
+    int ncam = 0; int first[MCP_MAX_FRAME_CAMS + 1] = {}; bool items_ok = false;      // (false: the last call kept its items on the device)
+    void invalidate() { ncam = 0; }
+  } tm;
+  // what mcp_track_map_record adds: its scratch and the pinned notes / measurements / record
+  struct Tr {
+    Buf<uint8_t> flags; Buf<int> tile, seg_start, seg_rows; Buf<TrAcc> acc; Buf<double> seg_w, cfw;
+    PinBuf<mcp_track_note> h_notes; PinBuf<mcp_track_meas> h_meas; PinBuf<mcp_track_record> h_rec;
+    bool ok = false; int ncam = 0; int meas_first[MCP_MAX_FRAME_CAMS + 1] = {};
+    void invalidate() { ok = false; }
+  } tr;
+  // AdjustAndUpdate write-back and scene depth: the packed inputs (pinned | device) / pinned outputs of mcp_ba_write_back and mcp_scene_depth_robust
+  struct Wb {
+    PinBuf<char> in; Buf<char> dev; PinBuf<char> out; Buf<double> T, depth; hipEvent_t ev = nullptr;
+    std::vector<int> slot, mark; int stamp = 0;      // (mark[row] == stamp: the row was named earlier in this call)
+    hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr}; bool timed = false;      // mcp_map_points_last_timing: input copy | points | scene depth
+    void invalidate() { timed = false; }
+  } wb;
   // mcp_map_refind: the packed inputs (pinned | device), the passes' scratch, the pinned results (RfOut | verdict bytes | measurements)
-  PinBuf<char> rf_in; Buf<char> rf_dev; Buf<uint8_t> rf_flags, rf_vd; Buf<int> rf_blk, rf_first; Buf<RfItem> rf_items; Buf<mcp_refind_meas> rf_cand; PinBuf<char> rf_out;
-  size_t rf_meas_off = 0; int rf_view = -1;            // mcp_map_refind_view: where the measurements start in rf_out, how many (-1: none to show)
-  int ensure_rays() {
-    if (rays.p && rays.n >= 9*pts.n) return 0;
-    Buf<double> r2; if (r2.alloc(9*std::max<size_t>(pts.n, 1))) return -1;
-    if (rays.p && rows) ICK(hipMemcpyAsync(r2.p, rays.p, 72*(size_t)rows, hipMemcpyDeviceToDevice, st));
-    ICK(hipStreamSynchronize(st)); stage_busy = false;
-    rays.swap(r2);
+  struct Rf {
+    PinBuf<char> in; Buf<char> dev; Buf<uint8_t> flags, vd; Buf<int> blk, first; Buf<RfItem> items; Buf<mcp_refind_meas> cand; PinBuf<char> out;
+    size_t meas_off = 0; int view = -1;              // mcp_map_refind_view: where the measurements start in out, how many (-1: none to show)
+    void invalidate() { view = -1; }
+  } rf;
+
+  ~mcp_map_points() { if (st) (void)hipStreamSynchronize(st); if (st) (void)hipStreamDestroy(st); if (staged) (void)hipEventDestroy(staged); if (wb.ev) (void)hipEventDestroy(wb.ev);
+    for (hipEvent_t e : wb.t) if (e) (void)hipEventDestroy(e); }
+  TmStates state_ptrs() const { TmStates S; for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c) S.s[c] = states[c].row(); return S; }
+  int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
+  hipError_t sync() { const hipError_t e = hipStreamSynchronize(st); if (e == hipSuccess) stage_busy = false; return e; }      // (nothing staged is in flight after it)
+  // every live column (or `only` this one, about to come to life) gets a block of new_cap rows where it has less, the rows so far copied over
+  int reserve(size_t new_cap, Column* only = nullptr) {
+    std::vector<Buf<char>> fresh(cols.size());
+    bool any = false, stale = false;
+    for (size_t i = 0; i < cols.size(); ++i) {
+      Column& c = *cols[i];
+      if ((only ? &c != only : !c.on) || (c.block.p && c.block.n >= c.bytes*new_cap)) continue;
+      if (fresh[i].alloc(c.bytes*new_cap)) return -1;
+      if (c.block.p && rows) ICK(hipMemcpyAsync(fresh[i].p, c.block.p, c.bytes*(size_t)rows, hipMemcpyDeviceToDevice, st));
+      any = true; stale = stale || c.block.p;
+    }
+    if (!any) return 0;
+    if (stale) ICK(sync());                          // the old blocks are freed below, with nothing in flight on them
+    for (size_t i = 0; i < cols.size(); ++i) if (fresh[i].p) cols[i]->block.swap(fresh[i]);
     return 0;
   }
-  TmStates state_ptrs() const { TmStates S; for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c) S.s[c] = states[c].p; return S; }
-  ~mcp_map_points() { if (st) (void)hipStreamSynchronize(st); if (st) (void)hipStreamDestroy(st); if (staged) (void)hipEventDestroy(staged); if (wb_ev) (void)hipEventDestroy(wb_ev);
-    for (hipEvent_t e : wb_t) if (e) (void)hipEventDestroy(e); }
-  int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
-  // rows [rows, new_rows) become unusable zero rows; the contents so far move to a larger block when the capacity is passed
+  // rows [first, first + count) of a column read as a row that has just appeared does
+  int fill(Column& c, size_t first, size_t count) {
+    if (c.fill == FILL_ZERO) ICK(hipMemsetAsync(c.at(first), 0, c.bytes*count, st));
+    if (c.fill == FILL_COUNTS) {
+      hipLaunchKernelGGL(k_tr_counts_fill, dim3((unsigned)((count + 255)/256)), dim3(256), 0, st, reinterpret_cast<int*>(c.at(0)), (int)first, (int)count);
+      ICK(hipGetLastError());
+    }
+    return 0;
+  }
+  // rows [rows, new_rows) appear: unusable zero rows without a source, with finders that have seen nothing, the counts of a point that has
+  // just been made and no patch rays; the contents so far move to larger blocks when the capacity is passed
   int grow(int new_rows) {
     if (new_rows <= rows) return 0;
-    if ((size_t)new_rows > pts.n || !pts.p) {
-      Buf<PvsPoint> bigger;
-      if (bigger.alloc(std::max<size_t>({(size_t)new_rows, 2*pts.n, (size_t)1024}))) return -1;
-      if (rows) ICK(hipMemcpyAsync(bigger.p, pts.p, sizeof(PvsPoint)*(size_t)rows, hipMemcpyDeviceToDevice, st));
-      // the columns of TrackMap follow the table's capacity
-      Buf<TmSrc> src2; if (src2.alloc(bigger.n)) return -1;
-      if (rows && src.p) ICK(hipMemcpyAsync(src2.p, src.p, sizeof(TmSrc)*(size_t)rows, hipMemcpyDeviceToDevice, st));
-      Buf<mcp_pf_state> st2[MCP_MAX_FRAME_CAMS];
-      for (int c = 0; c < st_ncam; ++c) {
-        if (st2[c].alloc(bigger.n)) return -1;
-        if (rows) ICK(hipMemcpyAsync(st2[c].p, states[c].p, sizeof(mcp_pf_state)*(size_t)rows, hipMemcpyDeviceToDevice, st));
-      }
-      Buf<int> cnt2; if (cnt2.alloc(2*bigger.n)) return -1;
-      if (rows && cnt.p) ICK(hipMemcpyAsync(cnt2.p, cnt.p, 2*sizeof(int)*(size_t)rows, hipMemcpyDeviceToDevice, st));
-      Buf<double> rays2;
-      if (rays.p) {
-        if (rays2.alloc(9*bigger.n)) return -1;
-        if (rows) ICK(hipMemcpyAsync(rays2.p, rays.p, 72*(size_t)rows, hipMemcpyDeviceToDevice, st));
-      }
-      ICK(hipStreamSynchronize(st));                 // the old block is freed below, with nothing in flight on it
-      stage_busy = false;
-      pts.swap(bigger); src.swap(src2); cnt.swap(cnt2);
-      if (rays2.p) rays.swap(rays2);
-      for (int c = 0; c < st_ncam; ++c) states[c].swap(st2[c]);
+    if ((size_t)new_rows > cap) {
+      const size_t bigger = std::max<size_t>({(size_t)new_rows, 2*cap, (size_t)1024});
+      if (reserve(bigger)) return -1;
+      cap = bigger;
     }
-    ICK(hipMemsetAsync(pts.p + rows, 0, sizeof(PvsPoint)*(size_t)(new_rows - rows), st));
-    // (rows dropped by a resize come back without a source, and with finders that have seen nothing)
-    ICK(hipMemsetAsync(src.p + rows, 0, sizeof(TmSrc)*(size_t)(new_rows - rows), st));
-    for (int c = 0; c < st_ncam; ++c) ICK(hipMemsetAsync(states[c].p + rows, 0, sizeof(mcp_pf_state)*(size_t)(new_rows - rows), st));
-    // (... and with the counts of a point that has just been made: 1 inlier, 0 outliers)
-    hipLaunchKernelGGL(k_tr_counts_fill, dim3((unsigned)((new_rows - rows + 255)/256)), dim3(256), 0, st, cnt.p, rows, new_rows - rows);
-    ICK(hipGetLastError());
+    for (Column* c : cols) if (c->on && fill(*c, rows, new_rows - rows)) return -1;
     row_slot.resize(new_rows, 0);
     has_rays.resize(new_rows, 0);                    // (a new row has no patch rays until mcp_map_points_set_rays / _update_rays names it)
     rows = new_rows;
     return 0;
   }
+  // a column created on demand comes to life: its block, every row of it filled as a new one; it is live only once both are done
+  int ensure(Column& c) {
+    if (c.on) return 0;
+    if (reserve(std::max<size_t>(cap, 1), &c) || fill(c, 0, c.block.n/c.bytes)) return -1;
+    c.on = true;
+    return 0;
+  }
   // finders for cameras 0 .. ncam-1 (zeroed when new)
   int ensure_states(int ncam) {
-    for (int c = st_ncam; c < ncam; ++c) {
-      if (states[c].alloc(std::max<size_t>(pts.n, 1))) return -1;
-      ICK(hipMemsetAsync(states[c].p, 0, sizeof(mcp_pf_state)*states[c].n, st));
-    }
+    for (int c = st_ncam; c < ncam; ++c) if (ensure(states[c])) return -1;
     st_ncam = std::max(st_ncam, ncam);
     return 0;
   }
 };
 
-static void pvs_pack(PvsPoint& r, int k, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
-  std::memcpy(r.world_pos, wp + 3*(size_t)k, 24); std::memcpy(r.pixel_right_w, pr + 3*(size_t)k, 24); std::memcpy(r.pixel_down_w, pd + 3*(size_t)k, 24);
-  r.usable = us[k] ? 1 : 0; r.pad_ = 0;
+// ---- the uploads and read-backs of the columns -----------------------------------------------------------------------------------------
+// The rows an upload names: first .. first+count-1, or (by_ids) ids[0 .. count): distinct, none negative, none without a successor.  *top is
+// the table's size once they exist.  Every upload refuses in this order: its arguments (have_arrays: the caller's own pointers), the row ids,
+// then the values it carries.
+static int rows_check(mcp_map_points* m, const std::string& who, bool by_ids, int first, int count, const int* ids, bool have_arrays, int* top) {
+  if (!m) return img_fail(who + ": NULL table");
+  if (count < 0 || (by_ids ? (count > 0 && !ids) : (first < 0 || (long long)first + count > 0x7fffffffLL)) || (count > 0 && !have_arrays))
+    return img_fail(who + ": bad arguments");
+  *top = by_ids ? m->rows : first + count;
+  if (!by_ids || count == 0) return 0;
+  for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(who + ": bad row id"); *top = std::max(*top, ids[k] + 1); }
+  // distinct ids: checked on a sorted copy (host memory ~ count, whatever the ids' values)
+  std::vector<int>& sorted = m->sorted_ids;
+  sorted.assign(ids, ids + count);
+  std::sort(sorted.begin(), sorted.end());
+  for (int k = 1; k < count; ++k) if (sorted[k] == sorted[k - 1]) return img_fail(who + ": row " + std::to_string(sorted[k]) + " appears twice");
+  return 0;
+}
+
+// One upload into a column (count > 0, the rows checked): the table grows to `top`, pack(k, record) fills record k of col.bytes in the pinned
+// staging, and the packed block is copied straight to rows first .. (ids == NULL) -- or, with ids, records and ids go to the device staging
+// and scatter(records, ids) launches the column's kernel.  always_scatter: the kernel takes the ranged form too (ids == NULL there).
+template <class Pack, class Scatter>
+static int column_upload(mcp_map_points* m, Column& col, int first, int count, const int* ids, int top, bool always_scatter, Pack pack, Scatter scatter) {
+  ICK(hipSetDevice(m->device));
+  if (m->wait_staging()) return -1;
+  const bool via_dev = ids || always_scatter;
+  const size_t rec_bytes = col.bytes*(size_t)count, o_ids = tm_align(rec_bytes), need = o_ids + (ids ? sizeof(int)*(size_t)count : 0);
+  if (m->up_in.alloc(need)) return -1;
+  if (via_dev) {
+    if (need > m->up_dev.n) ICK(m->sync());           // the device staging is reallocated below
+    if (m->up_dev.alloc(need)) return -1;
+  }
+  if (m->grow(top) || m->ensure(col)) return -1;
+  for (int k = 0; k < count; ++k) pack(k, m->up_in.p + col.bytes*(size_t)k);
+  if (ids) std::memcpy(m->up_in.p + o_ids, ids, sizeof(int)*(size_t)count);
+  if (!via_dev) ICK(hipMemcpyAsync(col.at(first), m->up_in.p, rec_bytes, hipMemcpyHostToDevice, m->st));
+  else {
+    ICK(hipMemcpyAsync(m->up_dev.p, m->up_in.p, rec_bytes, hipMemcpyHostToDevice, m->st));
+    if (ids) ICK(hipMemcpyAsync(m->up_dev.p + o_ids, m->up_in.p + o_ids, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
+    scatter((const void*)m->up_dev.p, ids ? (const int*)(m->up_dev.p + o_ids) : (const int*)nullptr, dim3((unsigned)((count + 255)/256)));
+    ICK(hipGetLastError());
+  }
+  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  return 0;
+}
+
+// rows first .. first+count-1 of a column read back (col == NULL: the caller's own arguments were bad) into `out` -- or, out == NULL, into
+// `bounce`, sized only once the range has passed; a column not created yet reads as zeros
+static int column_get(const mcp_map_points* mc, const std::string& who, const Column* col, int first, int count, void* out, std::vector<char>* bounce = nullptr) {
+  if (!mc) return img_fail(who + ": NULL table");
+  if (!col || first < 0 || count < 0 || (long long)first + count > mc->rows) return img_fail(who + ": bad arguments");
+  if (count == 0) return 0;
+  if (!out) { bounce->resize(col->bytes*(size_t)count); out = bounce->data(); }
+  if (!col->on) { std::memset(out, 0, col->bytes*(size_t)count); return 0; }
+  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
+  ICK(hipSetDevice(m->device));
+  ICK(hipMemcpyAsync(out, col->at(first), col->bytes*(size_t)count, hipMemcpyDeviceToHost, m->st));
+  ICK(m->sync());
+  return 0;
+}
+
+// camera cam's stretch first[cam] .. first[cam + 1] of a pinned list that holds the cameras one after the other
+template <class T> static const T* cam_view(const T* list, const int* first, int cam, int* count) {
+  const int k = first[cam + 1] - first[cam];
+  if (count) *count = k;
+  return k > 0 ? list + first[cam] : nullptr;
+}
+
+static int points_upload(mcp_map_points* m, const char* who, bool by_ids, int first, int count, const int* ids, const double* wp, const double* pr, const double* pd,
+                         const uint8_t* us) {
+  int top = 0;
+  if (rows_check(m, who, by_ids, first, count, ids, wp && pr && pd && us, &top)) return -1;
+  if (count == 0) return 0;
+  return column_upload(m, m->pts, first, count, ids, top, false,
+    [&](int k, char* rec) {
+      PvsPoint& r = *reinterpret_cast<PvsPoint*>(rec);
+      std::memcpy(r.world_pos, wp + 3*(size_t)k, 24); std::memcpy(r.pixel_right_w, pr + 3*(size_t)k, 24); std::memcpy(r.pixel_down_w, pd + 3*(size_t)k, 24);
+      r.usable = us[k] ? 1 : 0; r.pad_ = 0;
+    },
+    [&](const void* recs, const int* d_ids, dim3 grid) {
+      hipLaunchKernelGGL(k_map_points_scatter, grid, dim3(256), 0, m->st, m->pts.row(), count, d_ids, (const PvsPoint*)recs);
+    });
 }
 
 extern "C" {
@@ -1243,11 +1363,9 @@ mcp_map_points* mcp_map_points_create(int device) {
   if (dev >= ndev || !gfx950(dev)) { mcp_set_error("mcp_map_points_create: device is not a gfx950 (MI355X)"); return nullptr; }
   if (hipSetDevice(dev) != hipSuccess) { mcp_set_error("hipSetDevice failed"); return nullptr; }
   mcp_map_points* m = new mcp_map_points(); m->device = dev;
-  if (hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m->staged, hipEventDisableTiming) != hipSuccess) {
-    mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr;
-  }
-  for (hipEvent_t& e : m->wb_t) if (hipEventCreate(&e) != hipSuccess) { mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr; }
-  if (hipEventCreateWithFlags(&m->wb_ev, hipEventDisableTiming) != hipSuccess) { mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr; }
+  bool ok = hipStreamCreateWithFlags(&m->st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&m->staged, hipEventDisableTiming) == hipSuccess;
+  for (hipEvent_t& e : m->wb.t) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (!ok || hipEventCreateWithFlags(&m->wb.ev, hipEventDisableTiming) != hipSuccess) { mcp_set_error("mcp_map_points_create: stream / event creation failed"); delete m; return nullptr; }
   return m;
 }
 void mcp_map_points_destroy(mcp_map_points* m) { if (m) { (void)hipSetDevice(m->device); delete m; } }
@@ -1256,7 +1374,7 @@ int mcp_map_points_rows(const mcp_map_points* m) { if (!m) return img_fail("mcp_
 int mcp_map_points_resize(mcp_map_points* m, int rows) {
   if (!m) return img_fail("mcp_map_points_resize: NULL table");
   if (rows < 0) return img_fail("mcp_map_points_resize: bad arguments");
-  if (rows <= m->rows) {                                    // the rows past the end are gone; growing again zeroes them (grow)
+  if (rows <= m->rows) {                                    // the rows past the end are gone; growing again fills them afresh (grow)
     for (int r = rows; r < m->rows && r < (int)m->row_slot.size(); ++r) m->slot_release(m->row_slot[r]);
     if ((int)m->row_slot.size() > rows) m->row_slot.resize(rows);
     if ((int)m->has_rays.size() > rows) m->has_rays.resize(rows);
@@ -1268,142 +1386,147 @@ int mcp_map_points_resize(mcp_map_points* m, int rows) {
 }
 
 int mcp_map_points_set(mcp_map_points* m, int first, int count, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
-  if (!m) return img_fail("mcp_map_points_set: NULL table");
-  if (first < 0 || count < 0 || (long long)first + count > 0x7fffffffLL || (count > 0 && (!wp || !pr || !pd || !us))) return img_fail("mcp_map_points_set: bad arguments");
-  if (count == 0) return 0;
-  ICK(hipSetDevice(m->device));
-  if (m->wait_staging()) return -1;
-  if (m->h_recs.alloc(count)) return -1;
-  for (int k = 0; k < count; ++k) pvs_pack(m->h_recs.p[k], k, wp, pr, pd, us);
-  if (m->grow(first + count)) return -1;
-  ICK(hipMemcpyAsync(m->pts.p + first, m->h_recs.p, sizeof(PvsPoint)*(size_t)count, hipMemcpyHostToDevice, m->st));
-  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
-  return 0;
+  return points_upload(m, "mcp_map_points_set", false, first, count, nullptr, wp, pr, pd, us);
+}
+int mcp_map_points_update(mcp_map_points* m, int count, const int* ids, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
+  return points_upload(m, "mcp_map_points_update", true, 0, count, ids, wp, pr, pd, us);
 }
 
-int mcp_map_points_update(mcp_map_points* m, int count, const int* ids, const double* wp, const double* pr, const double* pd, const uint8_t* us) {
-  if (!m) return img_fail("mcp_map_points_update: NULL table");
-  if (count < 0 || (count > 0 && (!ids || !wp || !pr || !pd || !us))) return img_fail("mcp_map_points_update: bad arguments");
-  if (count == 0) return 0;
-  int top = m->rows;
-  for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail("mcp_map_points_update: bad row id"); top = std::max(top, ids[k] + 1); }
-  // distinct ids: checked on a sorted copy (host memory ~ count, whatever the ids' values)
-  m->sorted_ids.assign(ids, ids + count);
-  std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
-  for (int k = 1; k < count; ++k)
-    if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail("mcp_map_points_update: row " + std::to_string(m->sorted_ids[k]) + " appears twice");
-  ICK(hipSetDevice(m->device));
-  if (m->wait_staging()) return -1;
-  if (m->h_recs.alloc(count) || m->h_ids.alloc(count)) return -1;
-  if ((size_t)count > m->d_recs.n || (size_t)count > m->d_ids.n) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
-  if (m->d_recs.alloc(count) || m->d_ids.alloc(count)) return -1;
-  for (int k = 0; k < count; ++k) { pvs_pack(m->h_recs.p[k], k, wp, pr, pd, us); m->h_ids.p[k] = ids[k]; }
-  if (m->grow(top)) return -1;
-  ICK(hipMemcpyAsync(m->d_recs.p, m->h_recs.p, sizeof(PvsPoint)*(size_t)count, hipMemcpyHostToDevice, m->st));
-  ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
-  hipLaunchKernelGGL(k_map_points_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->pts.p, count, (const int*)m->d_ids.p, (const PvsPoint*)m->d_recs.p);
-  ICK(hipGetLastError());
-  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+// ---- what the frame calls share (mcp_track_find_pvs, mcp_track_map, mcp_track_map_record, mcp_map_refind) -----------------------------------
+static int target_on_table_device(const std::string& who, const mcp_map_points* m, int c, const mcp_kf* k) {
+  if (k->device == m->device) return 0;
+  return img_fail(who + ": camera " + std::to_string(c) + "'s target is on device " + std::to_string(k->device) + ", the table on device " + std::to_string(m->device));
+}
+
+// what an early return after the first enqueue leaves behind: nothing in flight on the table's stream and no error waiting in the runtime;
+// (track) no camera table taken for uploaded and no items to view; (lite) the frame's pyramids finished
+struct Drain {
+  mcp_map_points* m; bool armed; bool track = false; int ncam = 0; mcp_kf* const* lite = nullptr;
+  ~Drain() {
+    if (!armed) return;
+    (void)hipStreamSynchronize(m->st);
+    if (lite) { (void)hipStreamSynchronize(lite[0]->st); (void)lite_batch_finish(ncam, lite); }
+    if (track) { m->pvs.tab_last.clear(); m->tm.invalidate(); }
+    (void)hipGetLastError();
+  }
+};
+
+// the source keyframes of the table as the kernels walk them: `out` (zeroed by the caller) gets the level images of every slot still alive
+static void fill_slots(const mcp_map_points* m, TmSlot* out) {
+  std::lock_guard<std::mutex> reg(g_kf_mu);
+  for (size_t q = 0; q < m->slots.size(); ++q) {
+    const mcp_kf* s = m->slots[q].first;
+    auto live = s ? g_kf_live.find(s) : g_kf_live.end();
+    if (live == g_kf_live.end() || live->second != m->slots[q].second) continue;     // released, destroyed, or its address reused: dead
+    for (int l = 0; l < MCP_LEVELS; ++l) { out[q].img[l] = s->lev[l].img.p; out[q].w[l] = s->lev[l].w; out[q].h[l] = s->lev[l].h; }
+    out[q].live = 1;
+  }
+}
+
+// where the cameras' PVS lists go: camera c lists at most cap[c] = min(caps[c], n) rows (caps == NULL: n) from first[c], behind the cameras
+// before it; returns the entries all lists take together
+struct PvsLayout { int cap[MCP_MAX_FRAME_CAMS], first[MCP_MAX_FRAME_CAMS]; };
+static size_t pvs_layout(int ncam, const int* caps, int n, PvsLayout* Y) {
+  size_t room = 0;
+  for (int c = 0; c < ncam; ++c) { Y->cap[c] = caps ? std::min(caps[c], n) : n; Y->first[c] = (int)room; room += (size_t)Y->cap[c]; }
+  return room;
+}
+
+// FindPVS of the table's n > 0 rows, enqueued on its stream (m->pvs.reserve has been called): the lists, laid out as Y says, and the counts
+// per (camera, level) go to `lists` and `counts`, pinned or device memory.  The launches' errors are the caller's to collect (and to answer
+// with tab_last.clear()).
+static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double* cfb, const double* bfw, const PvsLayout& Y,
+                       mcp_pvs_entry* lists, int* counts) {
+  const int n = m->rows, nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
+  std::vector<PvsCam> tab(ncam);
+  for (int c = 0; c < ncam; ++c) {
+    PvsCam& C = tab[c];
+    std::memset(&C, 0, sizeof(PvsCam));              // (the table is compared byte-wise with the last one uploaded)
+    C.cam = cams[c]; C.cfb = se3_of12(cfb + 12*c);
+    const Level& L0 = targets[c]->lev[0];
+    C.mask0 = L0.has_mask ? L0.mask.p : nullptr; C.mask_w = L0.w; C.mask_h = L0.h;
+    C.cap = Y.cap[c]; C.out_first = Y.first[c];
+  }
+  // the cameras, their CamFromBase, masks and caps rarely change from frame to frame: their table is uploaded only when they do
+  mcp_map_points::Pvs& V = m->pvs;
+  if (V.tab_last.size() != tab.size() || std::memcmp(V.tab_last.data(), tab.data(), sizeof(PvsCam)*tab.size()) != 0) {
+    std::memcpy(V.h_tab.p, tab.data(), sizeof(PvsCam)*tab.size());
+    ICK(hipMemcpyAsync(V.d_tab.p, V.h_tab.p, sizeof(PvsCam)*tab.size(), hipMemcpyHostToDevice, m->st));
+    V.tab_last = tab;
+  }
+  hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
+  hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, n, nblk, (const signed char*)V.lvl.p,
+                     (const mcp_pvs_entry*)V.ent.p, (const int*)V.blk_cnt.p, lists, counts);
   return 0;
 }
 
 int mcp_track_find_pvs(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb,
                        const int* caps, mcp_pvs_entry* const* out, int* counts) {
   if (!m) return img_fail("mcp_track_find_pvs: NULL table");
-  m->view_ncam = 0; m->pvs_on_device = false; m->tr_ok = false;
+  m->pvs.invalidate(); m->tr.invalidate();
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !caps || !counts) return img_fail("mcp_track_find_pvs: bad arguments");
   for (int c = 0; c < ncam; ++c) {
     if (!targets[c] || !cam_ok(&cams[c]) || caps[c] < 0 || (out && !out[c])) return img_fail("mcp_track_find_pvs: bad arguments for camera " + std::to_string(c));
-    if (targets[c]->device != m->device)
-      return img_fail("mcp_track_find_pvs: camera " + std::to_string(c) + "'s target is on device " + std::to_string(targets[c]->device) + ", the table on device " + std::to_string(m->device));
+    if (target_on_table_device("mcp_track_find_pvs", m, c, targets[c])) return -1;
   }
   for (int k = 0; k < ncam*MCP_LEVELS; ++k) counts[k] = 0;
   ICK(hipSetDevice(m->device));
+  mcp_map_points::Pvs& V = m->pvs;
   const int n = m->rows;
   if (n == 0) {
-    for (int c = 0; c < ncam; ++c) { m->view_ok[c] = true; for (int l = 0; l < MCP_LEVELS; ++l) { m->view_first[c][l] = 0; m->view_count[c][l] = 0; } }
-    m->view_ncam = ncam;
+    for (int c = 0; c < ncam; ++c) { V.ok[c] = true; for (int l = 0; l < MCP_LEVELS; ++l) { V.first[c][l] = 0; V.count[c][l] = 0; } }
+    V.ncam = ncam;
     return 0;
   }
-  const int nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
-  std::vector<PvsCam> tab(ncam);
-  size_t room = 0;
-  for (int c = 0; c < ncam; ++c) {
-    PvsCam& C = tab[c];
-    std::memset(&C, 0, sizeof(PvsCam));              // (the table is compared byte-wise with the last one uploaded)
-    C.cam = cams[c]; std::memcpy(C.cfb.R, cfb + 12*c, 72); std::memcpy(C.cfb.t, cfb + 12*c + 9, 24);
-    const Level& L0 = targets[c]->lev[0];
-    C.mask0 = L0.has_mask ? L0.mask.p : nullptr; C.mask_w = L0.w; C.mask_h = L0.h;
-    C.cap = std::min(caps[c], n); C.out_first = (int)room;
-    room += (size_t)C.cap;
-  }
-  if (m->h_out.alloc(room) || m->h_counts.alloc((size_t)ncam*MCP_LEVELS) || m->lvl.alloc((size_t)ncam*n) || m->ent.alloc((size_t)ncam*n) ||
-      m->blk_cnt.alloc((size_t)ncam*nblk*MCP_LEVELS) || m->d_tab.alloc(MCP_MAX_FRAME_CAMS) || m->h_tab.alloc(MCP_MAX_FRAME_CAMS)) return -1;
-  // the cameras, their CamFromBase, masks and caps rarely change from frame to frame: their table is uploaded only when they do
-  if (m->tab_last.size() != tab.size() || std::memcmp(m->tab_last.data(), tab.data(), sizeof(PvsCam)*tab.size()) != 0) {
-    std::memcpy(m->h_tab.p, tab.data(), sizeof(PvsCam)*tab.size());
-    ICK(hipMemcpyAsync(m->d_tab.p, m->h_tab.p, sizeof(PvsCam)*tab.size(), hipMemcpyHostToDevice, m->st));
-    m->tab_last = tab;
-  }
-  Se3 B; std::memcpy(B.R, bfw, 72); std::memcpy(B.t, bfw + 9, 24);
-  hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)m->d_tab.p, B, (const PvsPoint*)m->pts.p, n, nblk, m->lvl.p, m->ent.p, m->blk_cnt.p);
-  hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)m->d_tab.p, n, nblk, (const signed char*)m->lvl.p,
-                     (const mcp_pvs_entry*)m->ent.p, (const int*)m->blk_cnt.p, m->h_out.p, m->h_counts.p);
+  PvsLayout Y;
+  if (V.h_out.alloc(pvs_layout(ncam, caps, n, &Y)) || V.h_counts.alloc((size_t)ncam*MCP_LEVELS) || V.reserve(ncam, n)) return -1;
+  if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, V.h_out.p, V.h_counts.p)) return -1;
   const hipError_t le = hipGetLastError();
-  const hipError_t se = hipStreamSynchronize(m->st);
-  if (le != hipSuccess) { m->tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: launch: ") + hipGetErrorString(le)); }
-  if (se != hipSuccess) { m->tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: ") + hipGetErrorString(se)); }
-  m->stage_busy = false;
-  std::memcpy(counts, m->h_counts.p, sizeof(int)*(size_t)ncam*MCP_LEVELS);
+  const hipError_t se = m->sync();
+  if (le != hipSuccess) { V.tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: launch: ") + hipGetErrorString(le)); }
+  if (se != hipSuccess) { V.tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: ") + hipGetErrorString(se)); }
+  std::memcpy(counts, V.h_counts.p, sizeof(int)*(size_t)ncam*MCP_LEVELS);
   std::string over;
   for (int c = 0; c < ncam; ++c) {
-    int first = tab[c].out_first, all = 0;
-    for (int l = 0; l < MCP_LEVELS; ++l) { m->view_first[c][l] = first; m->view_count[c][l] = counts[c*MCP_LEVELS + l]; first += counts[c*MCP_LEVELS + l]; all += counts[c*MCP_LEVELS + l]; }
-    m->view_ok[c] = all <= caps[c];
-    if (!m->view_ok[c]) { if (over.empty()) over = "mcp_track_find_pvs: camera " + std::to_string(c) + "'s PVS has " + std::to_string(all) + " entries, its cap is " + std::to_string(caps[c]); continue; }
-    if (out && all) std::memcpy(out[c], m->h_out.p + tab[c].out_first, sizeof(mcp_pvs_entry)*(size_t)all);
+    int first = Y.first[c], all = 0;
+    for (int l = 0; l < MCP_LEVELS; ++l) { V.first[c][l] = first; V.count[c][l] = counts[c*MCP_LEVELS + l]; first += counts[c*MCP_LEVELS + l]; all += counts[c*MCP_LEVELS + l]; }
+    V.ok[c] = all <= caps[c];
+    if (!V.ok[c]) { if (over.empty()) over = "mcp_track_find_pvs: camera " + std::to_string(c) + "'s PVS has " + std::to_string(all) + " entries, its cap is " + std::to_string(caps[c]); continue; }
+    if (out && all) std::memcpy(out[c], V.h_out.p + Y.first[c], sizeof(mcp_pvs_entry)*(size_t)all);
   }
-  m->view_ncam = ncam;
+  V.ncam = ncam;
   if (!over.empty()) return img_fail(over);
   return 0;
 }
 
 const mcp_pvs_entry* mcp_track_find_pvs_view(const mcp_map_points* m, int cam, int level, int* count) {
   if (count) *count = 0;
-  if (!m || cam < 0 || cam >= m->view_ncam || level < 0 || level >= MCP_LEVELS || !m->view_ok[cam]) {
+  if (!m || cam < 0 || cam >= m->pvs.ncam || level < 0 || level >= MCP_LEVELS || !m->pvs.ok[cam]) {
     img_fail("mcp_track_find_pvs_view: the last mcp_track_find_pvs on this table produced no list for that camera / level");
     return nullptr;
   }
-  if (m->pvs_on_device) {
+  if (m->pvs.on_device) {
     // the lists of the last mcp_track_map: copied to the pinned block on first demand
     mcp_map_points* w = const_cast<mcp_map_points*>(m);
-    w->pvs_on_device = false;
-    bool ok = hipSetDevice(w->device) == hipSuccess && w->h_out.alloc((size_t)w->view_ncam*std::max(w->pvs_rows, 1)) == 0;      // (the call's layout, whatever the table's size now)
-    for (int c = 0; ok && c < w->view_ncam; ++c) {
-      int all = 0; for (int l = 0; l < MCP_LEVELS; ++l) all += w->view_count[c][l];
-      if (all) ok = hipMemcpy(w->h_out.p + w->view_first[c][0], w->tm_pvs.p + w->view_first[c][0], sizeof(mcp_pvs_entry)*(size_t)all, hipMemcpyDeviceToHost) == hipSuccess;
+    w->pvs.on_device = false;
+    bool ok = hipSetDevice(w->device) == hipSuccess && w->pvs.h_out.alloc((size_t)w->pvs.ncam*std::max(w->pvs.rows, 1)) == 0;      // (the call's layout, whatever the table's size now)
+    for (int c = 0; ok && c < w->pvs.ncam; ++c) {
+      int all = 0; for (int l = 0; l < MCP_LEVELS; ++l) all += w->pvs.count[c][l];
+      if (all) ok = hipMemcpy(w->pvs.h_out.p + w->pvs.first[c][0], w->tm.pvs.p + w->pvs.first[c][0], sizeof(mcp_pvs_entry)*(size_t)all, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    if (!ok) { w->view_ncam = 0; img_fail("mcp_track_find_pvs_view: copy of the PVS lists failed"); return nullptr; }
+    if (!ok) { w->pvs.ncam = 0; img_fail("mcp_track_find_pvs_view: copy of the PVS lists failed"); return nullptr; }
   }
-  const int k = m->view_count[cam][level];
+  const int k = m->pvs.count[cam][level];
   if (count) *count = k;
-  return k > 0 ? m->h_out.p + m->view_first[cam][level] : nullptr;
+  return k > 0 ? m->pvs.h_out.p + m->pvs.first[cam][level] : nullptr;
 }
 
 // ---- TrackMap from the table (include/mcp_img.h mcp_track_map, track_map_kernels.h) -------------------------------------------------
-static int source_upload(mcp_map_points* m, const char* what, int first, int count, const int* ids, const int* keys, mcp_kf* const* kfs,
+static int source_upload(mcp_map_points* m, const char* what, bool by_ids, int first, int count, const int* ids, const int* keys, mcp_kf* const* kfs,
                          const int* levels, const int* cxy, const uint8_t* fixed) {
-  if (!m) return img_fail(std::string(what) + ": NULL table");
-  if (count < 0 || (!ids && (first < 0 || (long long)first + count > 0x7fffffffLL)) || (count > 0 && (!keys || !kfs || !levels || !cxy || !fixed)))
-    return img_fail(std::string(what) + ": bad arguments");
+  int top = 0;
+  if (rows_check(m, what, by_ids, first, count, ids, keys && kfs && levels && cxy && fixed, &top)) return -1;
   if (count == 0) return 0;
-  int top = ids ? m->rows : first + count;
-  if (ids) {
-    for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(std::string(what) + ": bad row id"); top = std::max(top, ids[k] + 1); }
-    m->sorted_ids.assign(ids, ids + count);
-    std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
-    for (int k = 1; k < count; ++k) if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail(std::string(what) + ": row " + std::to_string(m->sorted_ids[k]) + " appears twice");
-  }
   std::vector<unsigned long long> ser(count, 0ull);
   for (int k = 0; k < count; ++k) {
     if (!kfs[k]) continue;
@@ -1412,48 +1535,29 @@ static int source_upload(mcp_map_points* m, const char* what, int first, int cou
     if (kfs[k]->device != m->device) return img_fail(std::string(what) + ": entry " + std::to_string(k) + "'s source keyframe is on another device than the table");
     if (levels[k] < 0 || levels[k] >= MCP_LEVELS) return img_fail(std::string(what) + ": bad source level");
   }
-  ICK(hipSetDevice(m->device));
-  if (m->wait_staging()) return -1;
-  if (m->h_src.alloc(count) || (ids && m->h_ids.alloc(count))) return -1;
-  if ((size_t)count > m->d_src.n || (ids && (size_t)count > m->d_ids.n)) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
-  if (m->d_src.alloc(count) || (ids && m->d_ids.alloc(count))) return -1;
-  if (m->grow(top)) return -1;
-  for (int k = 0; k < count; ++k) {
-    TmSrc& r = m->h_src.p[k];
-    r.key = keys[k]; r.slot1 = 0; r.level = 0; r.cx = cxy[2*(size_t)k]; r.cy = cxy[2*(size_t)k + 1]; r.fixed = fixed[k] ? 1 : 0;
-    if (kfs[k]) { r.slot1 = m->slot_acquire(std::make_pair((const mcp_kf*)kfs[k], ser[k])); r.level = levels[k]; }
-    const int row = ids ? ids[k] : first + k;
-    m->slot_release(m->row_slot[row]);                   // (after the acquire: a row that keeps its source keeps the slot)
-    m->row_slot[row] = r.slot1;
-    if (ids) m->h_ids.p[k] = ids[k];
-  }
-  ICK(hipMemcpyAsync(m->d_src.p, m->h_src.p, sizeof(TmSrc)*(size_t)count, hipMemcpyHostToDevice, m->st));
-  if (ids) ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
-  hipLaunchKernelGGL(k_tm_source_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->src.p, count, ids ? 0 : first, ids ? (const int*)m->d_ids.p : (const int*)nullptr,
-                     (const TmSrc*)m->d_src.p, m->state_ptrs(), m->st_ncam);
-  ICK(hipGetLastError());
-  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
-  return 0;
+  // (the kernel takes both forms: it also resets the finders of a row whose key changed)
+  return column_upload(m, m->src, first, count, ids, top, true,
+    [&](int k, char* rec) {
+      TmSrc& r = *reinterpret_cast<TmSrc*>(rec);
+      r.key = keys[k]; r.slot1 = 0; r.level = 0; r.cx = cxy[2*(size_t)k]; r.cy = cxy[2*(size_t)k + 1]; r.fixed = fixed[k] ? 1 : 0;
+      if (kfs[k]) { r.slot1 = m->slot_acquire(std::make_pair((const mcp_kf*)kfs[k], ser[k])); r.level = levels[k]; }
+      const int row = ids ? ids[k] : first + k;
+      m->slot_release(m->row_slot[row]);                   // (after the acquire: a row that keeps its source keeps the slot)
+      m->row_slot[row] = r.slot1;
+    },
+    [&](const void* recs, const int* d_ids, dim3 grid) {
+      hipLaunchKernelGGL(k_tm_source_scatter, grid, dim3(256), 0, m->st, m->src.row(), count, ids ? 0 : first, d_ids, (const TmSrc*)recs, m->state_ptrs(), m->st_ncam);
+    });
 }
 int mcp_map_points_set_source(mcp_map_points* m, int first, int count, const int* keys, mcp_kf* const* kfs, const int* levels, const int* cxy, const uint8_t* fixed) {
-  return source_upload(m, "mcp_map_points_set_source", first, count, nullptr, keys, kfs, levels, cxy, fixed);
+  return source_upload(m, "mcp_map_points_set_source", false, first, count, nullptr, keys, kfs, levels, cxy, fixed);
 }
 int mcp_map_points_update_source(mcp_map_points* m, int count, const int* ids, const int* keys, mcp_kf* const* kfs, const int* levels, const int* cxy, const uint8_t* fixed) {
-  if (count > 0 && !ids) return img_fail("mcp_map_points_update_source: bad arguments");
-  return source_upload(m, "mcp_map_points_update_source", 0, count, ids, keys, kfs, levels, cxy, fixed);
+  return source_upload(m, "mcp_map_points_update_source", true, 0, count, ids, keys, kfs, levels, cxy, fixed);
 }
-int mcp_map_points_get_states(const mcp_map_points* mc, int cam, int first, int count, mcp_pf_state* out) {
-  if (!mc) return img_fail("mcp_map_points_get_states: NULL table");
-  if (cam < 0 || cam >= MCP_MAX_FRAME_CAMS || first < 0 || count < 0 || (long long)first + count > mc->rows || (count > 0 && !out))
-    return img_fail("mcp_map_points_get_states: bad arguments");
-  if (count == 0) return 0;
-  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
-  if (cam >= m->st_ncam) { std::memset(out, 0, sizeof(mcp_pf_state)*(size_t)count); return 0; }
-  ICK(hipSetDevice(m->device));
-  ICK(hipMemcpyAsync(out, m->states[cam].p + first, sizeof(mcp_pf_state)*(size_t)count, hipMemcpyDeviceToHost, m->st));
-  ICK(hipStreamSynchronize(m->st));
-  m->stage_busy = false;
-  return 0;
+int mcp_map_points_get_states(const mcp_map_points* m, int cam, int first, int count, mcp_pf_state* out) {
+  const bool ok = cam >= 0 && cam < MCP_MAX_FRAME_CAMS && (count <= 0 || out);
+  return column_get(m, "mcp_map_points_get_states", m && ok ? &m->states[cam] : nullptr, first, count, out);
 }
 
 // the register-resident pose kernel's dynamic LDS, once per device and thread (as refine_enqueue)
@@ -1470,8 +1574,6 @@ static bool tm_regs_ok() {
   return (ok_mask & bit) && (e ? atoi(e) != 0 : true);
 }
 
-static size_t tm_align(size_t x) { return (x + 15) & ~(size_t)15; }
-
 // the body of mcp_track_map (rp == NULL: exactly its launches) and of mcp_track_map_record (rp, rec checked by the caller)
 static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                          const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
@@ -1483,13 +1585,12 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   if (!est_ok(prm->estimator)) return img_fail(who + ": unknown M-estimator");
   for (int c = 0; c < ncam; ++c) {
     if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail(who + ": bad arguments for camera " + std::to_string(c));
-    if (targets[c]->device != m->device)
-      return img_fail(who + ": camera " + std::to_string(c) + "'s target is on device " + std::to_string(targets[c]->device) + ", the table on device " + std::to_string(m->device));
+    if (target_on_table_device(who, m, c, targets[c])) return -1;
     for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail(who + ": a keyframe appears twice in a frame with images");
   }
   ICK(hipSetDevice(m->device));
   // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
-  m->view_ncam = 0; m->pvs_on_device = false; m->tm_ncam = 0; m->tr_ok = false;
+  m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate();
   const bool want_items = !rp || rp->want_items != 0;
   const int n = m->rows;
   const size_t NB = (size_t)ncam*std::max(n, 1);                   // bound of every per-item array: a camera's sets are distinct rows
@@ -1498,40 +1599,37 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   const bool regs = tm_regs_ok();
   // everything is allocated before the first enqueue
   if (m->ensure_states(ncam)) return -1;
-  if (m->tm_pvs.alloc(NB) || m->tm_counts.alloc((size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS) || m->tm_sel.alloc(NB) || m->tm_k0.alloc(NB) || m->tm_k1.alloc(NB) || m->tm_live.alloc(NB) ||
-      m->tm_ctl.alloc(1) || m->tm_slots.alloc(std::max<size_t>(m->slots.size(), 1)) || m->h_slots.alloc(std::max<size_t>(m->slots.size(), 1)) ||
-      m->tm_crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm_frec.alloc(NB) || m->tm_w.alloc(NB) || m->tm_items.alloc(NB) || (want_items && m->h_items.alloc(NB)) || m->h_res.alloc(1) ||
-      m->lvl.alloc(NB) || m->ent.alloc(NB) || m->blk_cnt.alloc((size_t)ncam*((std::max(n, 1) + PVS_BLOCK - 1)/PVS_BLOCK)*MCP_LEVELS) ||
-      m->d_tab.alloc(MCP_MAX_FRAME_CAMS) || m->h_tab.alloc(MCP_MAX_FRAME_CAMS)) return -1;
+  if (m->tm.pvs.alloc(NB) || m->tm.counts.alloc((size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS) || m->tm.sel.alloc(NB) || m->tm.k0.alloc(NB) || m->tm.k1.alloc(NB) || m->tm.live.alloc(NB) ||
+      m->tm.ctl.alloc(1) || m->tm.slots.alloc(std::max<size_t>(m->slots.size(), 1)) || m->tm.h_slots.alloc(std::max<size_t>(m->slots.size(), 1)) ||
+      m->tm.crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm.frec.alloc(NB) || m->tm.w.alloc(NB) || m->tm.items.alloc(NB) || (want_items && m->tm.h_items.alloc(NB)) || m->tm.h_res.alloc(1) ||
+      m->pvs.reserve(ncam, n)) return -1;
   if (NB > (size_t)PRR_THREADS*PRR_PPT || !regs) {
-    if (m->tm_J.alloc(12*NB) || m->tm_ex.alloc(2*NB) || m->tm_e2.alloc(NB)) return -1;
+    if (m->tm.J.alloc(12*NB) || m->tm.ex.alloc(2*NB) || m->tm.e2.alloc(NB)) return -1;
   }
   // (param block: cameras' search table | camera models | CamFromBase | BaseFromWorld + mu | override sigma x 2 | nonlinear flags x 2)
   const size_t o_tab = 0, o_cam = tm_align(sizeof(TmCam)*(size_t)ncam), o_cfb = o_cam + tm_align(sizeof(mcp_camera)*(size_t)ncam), o_pm = o_cfb + tm_align(96*(size_t)ncam);
   const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), blk = o_nl + tm_align(20);
-  if (m->tm_blk.alloc(blk) || m->h_blk.alloc(blk)) return -1;
+  if (m->tm.blk.alloc(blk) || m->tm.h_blk.alloc(blk)) return -1;
   const size_t n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK;
   if (rp) {
-    if (m->h_notes.alloc(NB) || m->h_meas.alloc(NB) || m->h_rec.alloc(1) || m->tr_flags.alloc(NB) || m->tr_tile.alloc(n_tile) || m->tr_acc.alloc(1) ||
-        m->tr_seg_start.alloc(MCP_MAX_FRAME_CAMS + 1) || m->tr_seg_rows.alloc(NB) || m->tr_seg_w.alloc(NB) || m->tr_cfw.alloc(12*MCP_MAX_FRAME_CAMS) || m->wb_depth.alloc(NB)) return -1;
-    std::memset(m->h_rec.p, 0, sizeof(mcp_track_record));          // (the cameras past ncam read as zeros)
+    if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
+        m->tr.seg_start.alloc(MCP_MAX_FRAME_CAMS + 1) || m->tr.seg_rows.alloc(NB) || m->tr.seg_w.alloc(NB) || m->tr.cfw.alloc(12*MCP_MAX_FRAME_CAMS) || m->wb.depth.alloc(NB)) return -1;
+    std::memset(m->tr.h_rec.p, 0, sizeof(mcp_track_record));          // (the cameras past ncam read as zeros)
   }
   mcp_kf* k0 = targets[0];
-  struct Drain { mcp_map_points* m; bool armed; int ncam; mcp_kf* const* targets; bool lite;
-                 ~Drain() { if (armed) { (void)hipStreamSynchronize(m->st); if (lite) { (void)hipStreamSynchronize(targets[0]->st); (void)lite_batch_finish(ncam, targets); } m->tab_last.clear(); m->tm_ncam = 0; (void)hipGetLastError(); } } };
-  Drain drain{m, true, ncam, targets, imgs != nullptr};
+  Drain drain{m, true, true, ncam, imgs ? targets : nullptr};
   if (imgs) {
     if (lite_batch_enqueue(ncam, targets, imgs, strides, imgs_on_device, masks)) return -1;
     ICK(hipEventRecord(k0->ev, k0->st));
     ICK(hipStreamWaitEvent(m->st, k0->ev, 0));
   }
   // the tables are built after the pyramids' launch: it rotates the level images of the targets
-  uint8_t* hb = m->h_blk.p;
+  uint8_t* hb = m->tm.h_blk.p;
   std::memset(hb, 0, blk);
   TmCam* tab = reinterpret_cast<TmCam*>(hb + o_tab);
   for (int c = 0; c < ncam; ++c) {
     tab[c].T = targets[c]->view(); tab[c].mask0 = targets[c]->lev[0].has_mask ? targets[c]->lev[0].mask.p : nullptr; tab[c].cam = cams[c];
-    std::memcpy(tab[c].cfb.R, cfb + 12*c, 72); std::memcpy(tab[c].cfb.t, cfb + 12*c + 9, 24);
+    tab[c].cfb = se3_of12(cfb + 12*c);
   }
   std::memcpy(hb + o_cam, cams, sizeof(mcp_camera)*(size_t)ncam);
   std::memcpy(hb + o_cfb, cfb, 96*(size_t)ncam);
@@ -1542,118 +1640,92 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
     ov[10 + i] = i < 6 ? 0.0 : 16.0; nl[10 + i] = (i == 0 || i == 4 || i == 9) ? 1 : 0;   // fine, :1063-1075
   }
   const size_t nslot = std::max<size_t>(m->slots.size(), 1);
-  std::memset(m->h_slots.p, 0, sizeof(TmSlot)*nslot);
-  std::unique_lock<std::mutex> reg(g_kf_mu);
-  for (size_t q = 0; q < m->slots.size(); ++q) {
-    const mcp_kf* s = m->slots[q].first;
-    auto live = s ? g_kf_live.find(s) : g_kf_live.end();
-    if (live == g_kf_live.end() || live->second != m->slots[q].second) continue;     // released, destroyed, or its address reused: dead
-    TmSlot& S = m->h_slots.p[q];
-    for (int l = 0; l < MCP_LEVELS; ++l) { S.img[l] = s->lev[l].img.p; S.w[l] = s->lev[l].w; S.h[l] = s->lev[l].h; }
-    S.live = 1;
-  }
-  reg.unlock();
+  std::memset(m->tm.h_slots.p, 0, sizeof(TmSlot)*nslot);
+  fill_slots(m, m->tm.h_slots.p);
   hipStream_t st = m->st;
-  ICK(hipMemcpyAsync(m->tm_blk.p, hb, blk, hipMemcpyHostToDevice, st));
-  ICK(hipMemcpyAsync(m->tm_slots.p, m->h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
+  ICK(hipMemcpyAsync(m->tm.blk.p, hb, blk, hipMemcpyHostToDevice, st));
+  ICK(hipMemcpyAsync(m->tm.slots.p, m->tm.h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
   // 1. FindPVS, lists and counts in device memory (caps = rows; camera c's list at c * rows)
+  PvsLayout Y;
+  pvs_layout(ncam, nullptr, n, &Y);
   if (n > 0) {
-    const int nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
-    std::vector<PvsCam> ptab(ncam);
-    for (int c = 0; c < ncam; ++c) {
-      PvsCam& C = ptab[c];
-      std::memset(&C, 0, sizeof(PvsCam));
-      C.cam = cams[c]; std::memcpy(C.cfb.R, cfb + 12*c, 72); std::memcpy(C.cfb.t, cfb + 12*c + 9, 24);
-      const Level& L0 = targets[c]->lev[0];
-      C.mask0 = L0.has_mask ? L0.mask.p : nullptr; C.mask_w = L0.w; C.mask_h = L0.h;
-      C.cap = n; C.out_first = c*n;
-    }
-    if (m->tab_last.size() != ptab.size() || std::memcmp(m->tab_last.data(), ptab.data(), sizeof(PvsCam)*ptab.size()) != 0) {
-      std::memcpy(m->h_tab.p, ptab.data(), sizeof(PvsCam)*ptab.size());
-      ICK(hipMemcpyAsync(m->d_tab.p, m->h_tab.p, sizeof(PvsCam)*ptab.size(), hipMemcpyHostToDevice, st));
-      m->tab_last = ptab;
-    }
-    Se3 B; std::memcpy(B.R, bfw, 72); std::memcpy(B.t, bfw + 9, 24);
-    hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, st, (const PvsCam*)m->d_tab.p, B, (const PvsPoint*)m->pts.p, n, nblk, m->lvl.p, m->ent.p, m->blk_cnt.p);
-    hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, st, (const PvsCam*)m->d_tab.p, n, nblk, (const signed char*)m->lvl.p,
-                       (const mcp_pvs_entry*)m->ent.p, (const int*)m->blk_cnt.p, m->tm_pvs.p, m->tm_counts.p);
-  } else ICK(hipMemsetAsync(m->tm_counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
+    if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p)) return -1;
+  } else ICK(hipMemsetAsync(m->tm.counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
   // 2. the sets
   TmParams P; P.ncam = ncam; P.rows = n; P.try_coarse = prm->try_coarse ? 1 : 0; P.coarse_max = prm->coarse_max; P.coarse_range = prm->coarse_range;
   P.coarse_subpix_its = prm->coarse_subpix_its; P.coarse_min = prm->coarse_min; P.max_patches = prm->max_patches; P.seed = prm->seed;
-  hipLaunchKernelGGL(k_tm_select, dim3(ncam), dim3(TM_SEL_NT), 0, st, P, (const mcp_pvs_entry*)m->tm_pvs.p, (const int*)m->tm_counts.p, (const TmSrc*)m->src.p,
-                     (const TmSlot*)m->tm_slots.p, m->tm_k0.p, m->tm_k1.p, m->tm_live.p, m->tm_sel.p, m->tm_ctl.p);
-  const TmCam* d_tab = reinterpret_cast<const TmCam*>(m->tm_blk.p + o_tab);
-  const mcp_camera* d_cams = reinterpret_cast<const mcp_camera*>(m->tm_blk.p + o_cam);
-  const double* d_cfb = reinterpret_cast<const double*>(m->tm_blk.p + o_cfb);
-  double* d_pm = reinterpret_cast<double*>(m->tm_blk.p + o_pm);
-  const double* d_ov = reinterpret_cast<const double*>(m->tm_blk.p + o_ov);
-  const uint8_t* d_nl = m->tm_blk.p + o_nl;
-  TmCtl* ctl = m->tm_ctl.p;
+  hipLaunchKernelGGL(k_tm_select, dim3(ncam), dim3(TM_SEL_NT), 0, st, P, (const mcp_pvs_entry*)m->tm.pvs.p, (const int*)m->tm.counts.p, m->src.row(),
+                     (const TmSlot*)m->tm.slots.p, m->tm.k0.p, m->tm.k1.p, m->tm.live.p, m->tm.sel.p, m->tm.ctl.p);
+  const TmCam* d_tab = reinterpret_cast<const TmCam*>(m->tm.blk.p + o_tab);
+  const mcp_camera* d_cams = reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cam);
+  const double* d_cfb = reinterpret_cast<const double*>(m->tm.blk.p + o_cfb);
+  double* d_pm = reinterpret_cast<double*>(m->tm.blk.p + o_pm);
+  const double* d_ov = reinterpret_cast<const double*>(m->tm.blk.p + o_ov);
+  const uint8_t* d_nl = m->tm.blk.p + o_nl;
+  TmCtl* ctl = m->tm.ctl.p;
   auto iterate = [&](size_t bound, const int* n_dev, const int* gate, mcp_pose_point* recs, int stage) -> int {
     const double* o = d_ov + 10*stage; const uint8_t* f = d_nl + 10*stage;
-    if (regs) hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, d_pm + 12, m->tm_w.p, prm->estimator, ncam, n_dev, gate);
+    if (regs) hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, d_pm + 12, m->tm.w.p, prm->estimator, ncam, n_dev, gate);
     if (!regs || bound > (size_t)PRR_THREADS*PRR_PPT)      // (more records than the register-resident kernel holds, or no such kernel)
-      hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, m->tm_J.p, m->tm_ex.p, m->tm_e2.p, d_pm + 12, m->tm_w.p,
+      hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, m->tm.J.p, m->tm.ex.p, m->tm.e2.p, d_pm + 12, m->tm.w.p,
                          prm->estimator, n_dev, gate, regs ? PRR_THREADS*PRR_PPT : -1);
     ICK(hipGetLastError());
     return 0;
   };
   // 3-5. coarse search, the gate, the coarse iterations
   if (coarse)
-    hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(n_coarse_max, 8192)), dim3(64), 0, st, P, 0, d_tab, (const double*)d_pm, (const PvsPoint*)m->pts.p,
-                       (const TmSrc*)m->src.p, (const TmSlot*)m->tm_slots.p, (const int*)m->tm_sel.p, m->state_ptrs(), ctl, m->tm_items.p, m->tm_crec.p, m->tm_frec.p, m->tm_w.p);
+    hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(n_coarse_max, 8192)), dim3(64), 0, st, P, 0, d_tab, (const double*)d_pm, m->pts.row(),
+                       m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
   hipLaunchKernelGGL(k_tm_gate, dim3(1), dim3(1), 0, st, P, ctl);
-  if (coarse && iterate(n_coarse_max, &ctl->n_coarse, &ctl->did_coarse, m->tm_crec.p, 0)) return -1;
+  if (coarse && iterate(n_coarse_max, &ctl->n_coarse, &ctl->did_coarse, m->tm.crec.p, 0)) return -1;
   // 6-7. fine searches at the current pose, the fine iterations over [C_c, T_c, R_c]
-  hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, (const PvsPoint*)m->pts.p,
-                     (const TmSrc*)m->src.p, (const TmSlot*)m->tm_slots.p, (const int*)m->tm_sel.p, m->state_ptrs(), ctl, m->tm_items.p, m->tm_crec.p, m->tm_frec.p, m->tm_w.p);
-  if (iterate(NB, &ctl->n_fine, nullptr, m->tm_frec.p, 1)) return -1;
+  hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, m->pts.row(),
+                     m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
+  if (iterate(NB, &ctl->n_fine, nullptr, m->tm.frec.p, 1)) return -1;
   if (rp) {
     // the bookkeeping, from the items, the last weights and the refined pose where the iterations left them
     TrParams Q; Q.ncam = ncam; Q.lost = rp->lost ? 1 : 0; Q.min_patches = rp->min_patches; Q.coarse_min = rp->coarse_min; Q.good = rp->quality_good; Q.bad = rp->quality_bad;
     const unsigned grid = (unsigned)std::min<size_t>(n_tile, 2048);
-    ICK(hipMemsetAsync(m->tr_acc.p, 0, sizeof(TrAcc), st));
-    hipLaunchKernelGGL(k_tr_mark, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, d_tab, (const double*)d_pm, (const mcp_track_map_item*)m->tm_items.p, (const double*)m->tm_w.p,
-                       m->cnt.p, m->h_notes.p, m->tr_flags.p, m->tr_tile.p, m->tr_acc.p, m->tr_cfw.p, &m->h_rec.p->cam_from_world[0][0]);
-    hipLaunchKernelGGL(k_tr_scatter, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, (const mcp_track_map_item*)m->tm_items.p, (const uint8_t*)m->tr_flags.p,
-                       (const int*)m->tr_tile.p, (const TrAcc*)m->tr_acc.p, (const int*)m->cnt.p, m->h_meas.p, m->tr_seg_start.p, m->tr_seg_rows.p, m->tr_seg_w.p, m->h_rec.p);
-    hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)ncam), dim3(SD_BLOCK), 0, st, (const double*)m->tr_cfw.p, (const int*)nullptr, (const int*)m->tr_seg_start.p,
-                       (const int*)m->tr_seg_rows.p, (const double*)m->tr_seg_w.p, (const PvsPoint*)m->pts.p, m->wb_depth.p, &m->h_rec.p->depth[0], (double*)nullptr);
+    ICK(hipMemsetAsync(m->tr.acc.p, 0, sizeof(TrAcc), st));
+    hipLaunchKernelGGL(k_tr_mark, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, d_tab, (const double*)d_pm, (const mcp_track_map_item*)m->tm.items.p, (const double*)m->tm.w.p,
+                       m->cnt.row(), m->tr.h_notes.p, m->tr.flags.p, m->tr.tile.p, m->tr.acc.p, m->tr.cfw.p, &m->tr.h_rec.p->cam_from_world[0][0]);
+    hipLaunchKernelGGL(k_tr_scatter, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, (const mcp_track_map_item*)m->tm.items.p, (const uint8_t*)m->tr.flags.p,
+                       (const int*)m->tr.tile.p, (const TrAcc*)m->tr.acc.p, m->cnt.row(), m->tr.h_meas.p, m->tr.seg_start.p, m->tr.seg_rows.p, m->tr.seg_w.p, m->tr.h_rec.p);
+    hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)ncam), dim3(SD_BLOCK), 0, st, (const double*)m->tr.cfw.p, (const int*)nullptr, (const int*)m->tr.seg_start.p,
+                       (const int*)m->tr.seg_rows.p, (const double*)m->tr.seg_w.p, m->pts.row(), m->wb.depth.p, &m->tr.h_rec.p->depth[0], (double*)nullptr);
     ICK(hipGetLastError());
   }
-  if (!want_items) hipLaunchKernelGGL(k_tr_finish, dim3(1), dim3(64), 0, st, P, (const TmCtl*)ctl, (const double*)d_pm, (const int*)m->tm_counts.p, m->h_res.p);
-  else hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm_w.p,
-                     (const mcp_track_map_item*)m->tm_items.p, m->h_items.p,
-                     (const double*)d_pm, (const int*)m->tm_counts.p, m->h_res.p);
+  if (!want_items) hipLaunchKernelGGL(k_tr_finish, dim3(1), dim3(64), 0, st, P, (const TmCtl*)ctl, (const double*)d_pm, (const int*)m->tm.counts.p, m->tm.h_res.p);
+  else hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm.w.p,
+                     (const mcp_track_map_item*)m->tm.items.p, m->tm.h_items.p,
+                     (const double*)d_pm, (const int*)m->tm.counts.p, m->tm.h_res.p);
   ICK(hipGetLastError());
-  ICK(hipStreamSynchronize(st));
+  ICK(m->sync());
   drain.armed = false;
-  m->stage_busy = false;
   if (imgs && lite_batch_finish(ncam, targets)) return -1;
-  const TmOut& R = *m->h_res.p;
+  const TmOut& R = *m->tm.h_res.p;
   std::memset(res, 0, sizeof *res);
   res->did_coarse = R.ctl.did_coarse; res->coarse_found = R.ctl.coarse_found;
   int first = 0;
   for (int c = 0; c < ncam; ++c) {
-    int off = c*n;
+    int off = Y.first[c];
     for (int l = 0; l < MCP_LEVELS; ++l) {
       res->pvs_counts[c][l] = R.counts[c][l];
-      m->view_first[c][l] = off; m->view_count[c][l] = R.counts[c][l]; off += R.counts[c][l];
+      m->pvs.first[c][l] = off; m->pvs.count[c][l] = R.counts[c][l]; off += R.counts[c][l];
     }
-    m->view_ok[c] = true;
+    m->pvs.ok[c] = true;
     for (int q = 0; q < 3; ++q) res->set_sizes[c][q] = R.ctl.sizes[c][q];
     res->stale[c] = R.ctl.stale[c];
-    m->tm_first[c] = first; first += R.ctl.sizes[c][0] + R.ctl.sizes[c][1] + R.ctl.sizes[c][2];
+    m->tm.first[c] = first; first += R.ctl.sizes[c][0] + R.ctl.sizes[c][1] + R.ctl.sizes[c][2];
   }
-  m->tm_first[ncam] = first; m->tm_ncam = ncam; m->tm_items_ok = want_items;
+  m->tm.first[ncam] = first; m->tm.ncam = ncam; m->tm.items_ok = want_items;
   if (rp) {
-    *rec = *m->h_rec.p;
-    m->tr_meas_first[0] = 0;
-    for (int c = 0; c < ncam; ++c) m->tr_meas_first[c + 1] = m->tr_meas_first[c] + rec->n_meas[c];
-    m->tr_ncam = ncam; m->tr_ok = true;
+    *rec = *m->tr.h_rec.p;
+    m->tr.meas_first[0] = 0;
+    for (int c = 0; c < ncam; ++c) m->tr.meas_first[c + 1] = m->tr.meas_first[c] + rec->n_meas[c];
+    m->tr.ncam = ncam; m->tr.ok = true;
   }
-  m->view_ncam = ncam; m->pvs_on_device = true; m->pvs_rows = n;
+  m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
   std::memcpy(res->mu_last, R.mu, 48);
   std::memcpy(bfw, R.pose, 96);
   return 0;
@@ -1676,84 +1748,50 @@ int mcp_track_map_record(mcp_map_points* m, int ncam, mcp_kf* const* targets, co
 
 const mcp_track_note* mcp_track_map_notes_view(const mcp_map_points* m, int cam, int* count) {
   if (count) *count = 0;
-  if (!m || !m->tr_ok || cam < 0 || cam >= m->tr_ncam) { img_fail("mcp_track_map_notes_view: the last track / PVS call on this table was no mcp_track_map_record with that camera"); return nullptr; }
-  const int k = m->tm_first[cam + 1] - m->tm_first[cam];
-  if (count) *count = k;
-  return k > 0 ? m->h_notes.p + m->tm_first[cam] : nullptr;
+  if (!m || !m->tr.ok || cam < 0 || cam >= m->tr.ncam) { img_fail("mcp_track_map_notes_view: the last track / PVS call on this table was no mcp_track_map_record with that camera"); return nullptr; }
+  return cam_view(m->tr.h_notes.p, m->tm.first, cam, count);
 }
 const mcp_track_meas* mcp_track_map_meas_view(const mcp_map_points* m, int cam, int* count) {
   if (count) *count = 0;
-  if (!m || !m->tr_ok || cam < 0 || cam >= m->tr_ncam) { img_fail("mcp_track_map_meas_view: the last track / PVS call on this table was no mcp_track_map_record with that camera"); return nullptr; }
-  const int k = m->tr_meas_first[cam + 1] - m->tr_meas_first[cam];
-  if (count) *count = k;
-  return k > 0 ? m->h_meas.p + m->tr_meas_first[cam] : nullptr;
+  if (!m || !m->tr.ok || cam < 0 || cam >= m->tr.ncam) { img_fail("mcp_track_map_meas_view: the last track / PVS call on this table was no mcp_track_map_record with that camera"); return nullptr; }
+  return cam_view(m->tr.h_meas.p, m->tr.meas_first, cam, count);
 }
 
 // ---- the count column (include/mcp_img.h mcp_map_points_set_counts) --------------------------------------------------------------------
-static int counts_upload(mcp_map_points* m, const std::string& who, int first, int count, const int* ids, const int* inl, const int* outl) {
-  if (!m) return img_fail(who + ": NULL table");
-  if (count < 0 || (!ids && (first < 0 || (long long)first + count > 0x7fffffffLL)) || (count > 0 && (!inl || !outl))) return img_fail(who + ": bad arguments");
-  if (count == 0) return 0;
+static int counts_upload(mcp_map_points* m, const std::string& who, bool by_ids, int first, int count, const int* ids, const int* inl, const int* outl) {
+  int top = 0;
+  if (rows_check(m, who, by_ids, first, count, ids, inl && outl, &top)) return -1;
   for (int k = 0; k < count; ++k)
     if (inl[k] < 1 || outl[k] < 0) return img_fail(who + ": entry " + std::to_string(k) + " has inlier < 1 or outlier < 0");
-  int top = ids ? m->rows : first + count;
-  if (ids) {
-    for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(who + ": bad row id"); top = std::max(top, ids[k] + 1); }
-    m->sorted_ids.assign(ids, ids + count);
-    std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
-    for (int k = 1; k < count; ++k) if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail(who + ": row " + std::to_string(m->sorted_ids[k]) + " appears twice");
-  }
-  ICK(hipSetDevice(m->device));
-  if (m->wait_staging()) return -1;
-  if (m->h_cnt.alloc(2*(size_t)count) || (ids && m->h_ids.alloc(count))) return -1;
-  if (ids) {
-    if (2*(size_t)count > m->d_cnt.n || (size_t)count > m->d_ids.n) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
-    if (m->d_cnt.alloc(2*(size_t)count) || m->d_ids.alloc(count)) return -1;
-  }
-  for (int k = 0; k < count; ++k) { m->h_cnt.p[2*(size_t)k] = inl[k]; m->h_cnt.p[2*(size_t)k + 1] = outl[k]; if (ids) m->h_ids.p[k] = ids[k]; }
-  if (m->grow(top)) return -1;
-  if (!ids) ICK(hipMemcpyAsync(m->cnt.p + 2*(size_t)first, m->h_cnt.p, 2*sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
-  else {
-    ICK(hipMemcpyAsync(m->d_cnt.p, m->h_cnt.p, 2*sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
-    ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
-    hipLaunchKernelGGL(k_tr_counts_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->cnt.p, count, (const int*)m->d_ids.p, (const int*)m->d_cnt.p);
-    ICK(hipGetLastError());
-  }
-  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
-  return 0;
+  if (count == 0) return 0;
+  return column_upload(m, m->cnt, first, count, ids, top, false,
+    [&](int k, char* rec) { int* r = reinterpret_cast<int*>(rec); r[0] = inl[k]; r[1] = outl[k]; },
+    [&](const void* recs, const int* d_ids, dim3 grid) {
+      hipLaunchKernelGGL(k_tr_counts_scatter, grid, dim3(256), 0, m->st, m->cnt.row(), count, d_ids, (const int*)recs);
+    });
 }
 int mcp_map_points_set_counts(mcp_map_points* m, int first, int count, const int* inl, const int* outl) {
-  return counts_upload(m, "mcp_map_points_set_counts", first, count, nullptr, inl, outl);
+  return counts_upload(m, "mcp_map_points_set_counts", false, first, count, nullptr, inl, outl);
 }
 int mcp_map_points_update_counts(mcp_map_points* m, int count, const int* ids, const int* inl, const int* outl) {
-  if (m && count > 0 && !ids) return img_fail("mcp_map_points_update_counts: bad arguments");
-  return counts_upload(m, "mcp_map_points_update_counts", 0, count, ids, inl, outl);
+  return counts_upload(m, "mcp_map_points_update_counts", true, 0, count, ids, inl, outl);
 }
-int mcp_map_points_get_counts(const mcp_map_points* mc, int first, int count, int* inl, int* outl) {
-  if (!mc) return img_fail("mcp_map_points_get_counts: NULL table");
-  if (first < 0 || count < 0 || (long long)first + count > mc->rows) return img_fail("mcp_map_points_get_counts: bad arguments");
-  if (count == 0) return 0;
-  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
-  ICK(hipSetDevice(m->device));
-  std::vector<int> h(2*(size_t)count);
-  ICK(hipMemcpyAsync(h.data(), m->cnt.p + 2*(size_t)first, 2*sizeof(int)*(size_t)count, hipMemcpyDeviceToHost, m->st));
-  ICK(hipStreamSynchronize(m->st));
-  m->stage_busy = false;
+int mcp_map_points_get_counts(const mcp_map_points* m, int first, int count, int* inl, int* outl) {
+  std::vector<char> bounce;
+  if (column_get(m, "mcp_map_points_get_counts", m ? &m->cnt : nullptr, first, count, nullptr, &bounce)) return -1;
+  const int* h = reinterpret_cast<const int*>(bounce.data());
   for (int k = 0; k < count; ++k) { if (inl) inl[k] = h[2*(size_t)k]; if (outl) outl[k] = h[2*(size_t)k + 1]; }
   return 0;
 }
 
 const mcp_track_map_item* mcp_track_map_view(const mcp_map_points* m, int cam, int* count) {
   if (count) *count = 0;
-  if (!m || cam < 0 || cam >= m->tm_ncam) { img_fail("mcp_track_map_view: the last mcp_track_map on this table produced no items for that camera"); return nullptr; }
-  if (!m->tm_items_ok) { img_fail("mcp_track_map_view: the last call on this table was mcp_track_map_record with want_items = 0: no item left the device"); return nullptr; }
-  const int k = m->tm_first[cam + 1] - m->tm_first[cam];
-  if (count) *count = k;
-  return k > 0 ? m->h_items.p + m->tm_first[cam] : nullptr;
+  if (!m || cam < 0 || cam >= m->tm.ncam) { img_fail("mcp_track_map_view: the last mcp_track_map on this table produced no items for that camera"); return nullptr; }
+  if (!m->tm.items_ok) { img_fail("mcp_track_map_view: the last call on this table was mcp_track_map_record with want_items = 0: no item left the device"); return nullptr; }
+  return cam_view(m->tm.h_items.p, m->tm.first, cam, count);
 }
 
 // ---- MapMakerServerBase::AddStereoMapPoints of one source keyframe and level (stereo_kernels.h) ----------------------------------------------------
-static Se3 se3_of12(const double* a) { Se3 T; std::memcpy(T.R, a, 72); std::memcpy(T.t, a + 9, 24); return T; }
 static bool finite12(const double* a) { for (int k = 0; k < 12; ++k) if (!std::isfinite(a[k])) return false; return true; }
 static bool kf_live(const mcp_kf* k) { return k && kf_live_serial(k) != 0ull; }
 // the checks both entries share: source, level, candidates
@@ -1924,42 +1962,18 @@ void sd_copy_out(int n_kf, const mcp_scene_depth* got, mcp_scene_depth* depth_ou
   }
 }
 
-int rays_upload(mcp_map_points* m, const char* who, int first, int count, const int* ids, const double* ce, const double* ri, const double* dn) {
-  if (!m) return img_fail(std::string(who) + ": NULL table");
-  if (first < 0 || count < 0 || (long long)first + count > 0x7fffffffLL || (count > 0 && (!ce || !ri || !dn))) return img_fail(std::string(who) + ": bad arguments");
+int rays_upload(mcp_map_points* m, const char* who, bool by_ids, int first, int count, const int* ids, const double* ce, const double* ri, const double* dn) {
+  int top = 0;
+  if (rows_check(m, who, by_ids, first, count, ids, ce && ri && dn, &top)) return -1;
   if (count == 0) return 0;
-  int top = first + count;
-  if (ids) {
-    top = m->rows;
-    for (int k = 0; k < count; ++k) { if (ids[k] < 0 || ids[k] == 0x7fffffff) return img_fail(std::string(who) + ": bad row id"); top = std::max(top, ids[k] + 1); }
-    m->sorted_ids.assign(ids, ids + count);
-    std::sort(m->sorted_ids.begin(), m->sorted_ids.end());
-    for (int k = 1; k < count; ++k)
-      if (m->sorted_ids[k] == m->sorted_ids[k - 1]) return img_fail(std::string(who) + ": row " + std::to_string(m->sorted_ids[k]) + " appears twice");
-  }
-  ICK(hipSetDevice(m->device));
-  if (m->wait_staging()) return -1;
-  if (m->h_rays.alloc(9*(size_t)count)) return -1;
-  if (ids) {
-    if (m->h_ids.alloc(count)) return -1;
-    if (9*(size_t)count > m->d_rays.n || (size_t)count > m->d_ids.n) ICK(hipStreamSynchronize(m->st));     // the device staging is reallocated below
-    if (m->d_rays.alloc(9*(size_t)count) || m->d_ids.alloc(count)) return -1;
-  }
-  for (int k = 0; k < count; ++k) {
-    double* r = m->h_rays.p + 9*(size_t)k;
-    std::memcpy(r, ce + 3*(size_t)k, 24); std::memcpy(r + 3, ri + 3*(size_t)k, 24); std::memcpy(r + 6, dn + 3*(size_t)k, 24);
-    if (ids) m->h_ids.p[k] = ids[k];
-  }
-  if (m->grow(top)) return -1;
-  if (m->ensure_rays()) return -1;
-  if (!ids) ICK(hipMemcpyAsync(m->rays.p + 9*(size_t)first, m->h_rays.p, 72*(size_t)count, hipMemcpyHostToDevice, m->st));
-  else {
-    ICK(hipMemcpyAsync(m->d_rays.p, m->h_rays.p, 72*(size_t)count, hipMemcpyHostToDevice, m->st));
-    ICK(hipMemcpyAsync(m->d_ids.p, m->h_ids.p, sizeof(int)*(size_t)count, hipMemcpyHostToDevice, m->st));
-    hipLaunchKernelGGL(k_map_rays_scatter, dim3((unsigned)((count + 255)/256)), dim3(256), 0, m->st, m->rays.p, count, (const int*)m->d_ids.p, (const double*)m->d_rays.p);
-    ICK(hipGetLastError());
-  }
-  ICK(hipEventRecord(m->staged, m->st)); m->stage_busy = true;
+  if (column_upload(m, m->rays, first, count, ids, top, false,
+    [&](int k, char* rec) {
+      double* r = reinterpret_cast<double*>(rec);
+      std::memcpy(r, ce + 3*(size_t)k, 24); std::memcpy(r + 3, ri + 3*(size_t)k, 24); std::memcpy(r + 6, dn + 3*(size_t)k, 24);
+    },
+    [&](const void* recs, const int* d_ids, dim3 grid) {
+      hipLaunchKernelGGL(k_map_rays_scatter, grid, dim3(256), 0, m->st, m->rays.row(), count, d_ids, (const double*)recs);
+    })) return -1;
   for (int k = 0; k < count; ++k) m->has_rays[ids ? ids[k] : first + k] = 1;
   return 0;
 }
@@ -1967,7 +1981,7 @@ int rays_upload(mcp_map_points* m, const char* who, int first, int count, const 
 // the scene-depth launch on the table's stream, inputs already on the device
 void sd_launch(mcp_map_points* m, int n_kf, const double* T, const int* slot, const char* dev_in, const WbLayout& L, char* out_pinned, bool want_depths) {
   hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)n_kf), dim3(SD_BLOCK), 0, m->st, T, slot, (const int*)(dev_in + L.seg_start), (const int*)(dev_in + L.seg_rows),
-                     (const double*)(dev_in + L.seg_w), (const PvsPoint*)m->pts.p, m->wb_depth.p, (mcp_scene_depth*)(out_pinned + L.sd),
+                     (const double*)(dev_in + L.seg_w), m->pts.row(), m->wb.depth.p, (mcp_scene_depth*)(out_pinned + L.sd),
                      want_depths ? (double*)(out_pinned + L.depths) : (double*)nullptr);
 }
 }  // namespace
@@ -1975,23 +1989,16 @@ void sd_launch(mcp_map_points* m, int n_kf, const double* T, const int* slot, co
 extern "C" {
 
 int mcp_map_points_set_rays(mcp_map_points* m, int first, int count, const double* ce, const double* ri, const double* dn) {
-  return rays_upload(m, "mcp_map_points_set_rays", first, count, nullptr, ce, ri, dn);
+  return rays_upload(m, "mcp_map_points_set_rays", false, first, count, nullptr, ce, ri, dn);
 }
 int mcp_map_points_update_rays(mcp_map_points* m, int count, const int* ids, const double* ce, const double* ri, const double* dn) {
-  if (m && count > 0 && !ids) return img_fail("mcp_map_points_update_rays: bad arguments");
-  return rays_upload(m, "mcp_map_points_update_rays", 0, count, ids, ce, ri, dn);
+  return rays_upload(m, "mcp_map_points_update_rays", true, 0, count, ids, ce, ri, dn);
 }
 
-int mcp_map_points_get(const mcp_map_points* mc, int first, int count, double* wp, double* pr, double* pd, uint8_t* us) {
-  if (!mc) return img_fail("mcp_map_points_get: NULL table");
-  if (first < 0 || count < 0 || (long long)first + count > mc->rows) return img_fail("mcp_map_points_get: bad arguments");
-  if (count == 0) return 0;
-  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
-  ICK(hipSetDevice(m->device));
-  std::vector<PvsPoint> h((size_t)count);
-  ICK(hipMemcpyAsync(h.data(), m->pts.p + first, sizeof(PvsPoint)*(size_t)count, hipMemcpyDeviceToHost, m->st));
-  ICK(hipStreamSynchronize(m->st));
-  m->stage_busy = false;
+int mcp_map_points_get(const mcp_map_points* m, int first, int count, double* wp, double* pr, double* pd, uint8_t* us) {
+  std::vector<char> bounce;
+  if (column_get(m, "mcp_map_points_get", m ? &m->pts : nullptr, first, count, nullptr, &bounce)) return -1;
+  const PvsPoint* h = reinterpret_cast<const PvsPoint*>(bounce.data());
   for (int k = 0; k < count; ++k) {
     if (wp) std::memcpy(wp + 3*(size_t)k, h[k].world_pos, 24);
     if (pr) std::memcpy(pr + 3*(size_t)k, h[k].pixel_right_w, 24);
@@ -2003,9 +2010,9 @@ int mcp_map_points_get(const mcp_map_points* mc, int first, int count, double* w
 
 int mcp_map_points_last_timing(const mcp_map_points* m, double* copy_ms, double* points_ms, double* depth_ms) {
   if (!m) return img_fail("mcp_map_points_last_timing: NULL table");
-  if (!m->wb_timed) return img_fail("mcp_map_points_last_timing: no completed mcp_ba_write_back / mcp_scene_depth_robust on this table");
+  if (!m->wb.timed) return img_fail("mcp_map_points_last_timing: no completed mcp_ba_write_back / mcp_scene_depth_robust on this table");
   float a = 0, b = 0, c = 0;
-  ICK(hipEventElapsedTime(&a, m->wb_t[0], m->wb_t[1])); ICK(hipEventElapsedTime(&b, m->wb_t[1], m->wb_t[2])); ICK(hipEventElapsedTime(&c, m->wb_t[2], m->wb_t[3]));
+  ICK(hipEventElapsedTime(&a, m->wb.t[0], m->wb.t[1])); ICK(hipEventElapsedTime(&b, m->wb.t[1], m->wb.t[2])); ICK(hipEventElapsedTime(&c, m->wb.t[2], m->wb.t[3]));
   if (copy_ms) *copy_ms = a;
   if (points_ms) *points_ms = b;
   if (depth_ms) *depth_ms = c;
@@ -2023,24 +2030,23 @@ int mcp_scene_depth_robust(mcp_map_points* m, int n_kf, const double* cfw, const
   ICK(hipSetDevice(m->device));
   const bool want_depths = seg_depths_out != nullptr;
   const WbLayout L(0, 0, n_kf, total, false, want_depths, n_kf);
-  if (m->wb_in.alloc(L.in_bytes) || m->wb_dev.alloc(L.in_bytes) || m->wb_out.alloc(L.out_bytes) || m->wb_depth.alloc((size_t)total)) return -1;
-  char* hin = m->wb_in.p;
+  if (m->wb.in.alloc(L.in_bytes) || m->wb.dev.alloc(L.in_bytes) || m->wb.out.alloc(L.out_bytes) || m->wb.depth.alloc((size_t)total)) return -1;
+  char* hin = m->wb.in.p;
   std::memcpy(hin + L.poses, cfw, 96*(size_t)n_kf);
   std::memcpy(hin + L.seg_start, seg_start, sizeof(int)*((size_t)n_kf + 1));
   if (total) { std::memcpy(hin + L.seg_rows, seg_rows, sizeof(int)*(size_t)total); std::memcpy(hin + L.seg_w, seg_w, 8*(size_t)total); }
-  m->wb_timed = false;
-  ICK(hipEventRecord(m->wb_t[0], m->st));
-  ICK(hipMemcpyAsync(m->wb_dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
-  ICK(hipEventRecord(m->wb_t[1], m->st)); ICK(hipEventRecord(m->wb_t[2], m->st));
-  sd_launch(m, n_kf, (const double*)(m->wb_dev.p + L.poses), nullptr, m->wb_dev.p, L, m->wb_out.p, want_depths);
+  m->wb.invalidate();
+  ICK(hipEventRecord(m->wb.t[0], m->st));
+  ICK(hipMemcpyAsync(m->wb.dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->wb.t[1], m->st)); ICK(hipEventRecord(m->wb.t[2], m->st));
+  sd_launch(m, n_kf, (const double*)(m->wb.dev.p + L.poses), nullptr, m->wb.dev.p, L, m->wb.out.p, want_depths);
   const hipError_t le = hipGetLastError();
-  (void)hipEventRecord(m->wb_t[3], m->st);
-  ICK(hipStreamSynchronize(m->st));
-  m->stage_busy = false;
+  (void)hipEventRecord(m->wb.t[3], m->st);
+  ICK(m->sync());
   if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
-  m->wb_timed = true;
-  sd_copy_out(n_kf, (const mcp_scene_depth*)(m->wb_out.p + L.sd), depth_out);
-  if (seg_depths_out && total) std::memcpy(seg_depths_out, m->wb_out.p + L.depths, 8*(size_t)total);
+  m->wb.timed = true;
+  sd_copy_out(n_kf, (const mcp_scene_depth*)(m->wb.out.p + L.sd), depth_out);
+  if (seg_depths_out && total) std::memcpy(seg_depths_out, m->wb.out.p + L.depths, 8*(size_t)total);
   return 0;
 }
 
@@ -2063,11 +2069,11 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
   if (((n_points > 0 && src_chains) || n_kf > 0) && chain_stride < 1) return img_fail(who + ": chain_stride must be positive");
   // distinct chains of the call -> slots of the product table (the solver's own chains by number, a chain it does not know by its pose indices)
   const int nsolver = ba_bridge_num_chains(h);
-  m->wb_slot.assign((size_t)nsolver, -1);
+  m->wb.slot.assign((size_t)nsolver, -1);
   std::vector<WbChain> chains;
   std::map<std::vector<int>, int> extra;
   auto slot_of_solver = [&](int c) -> int {
-    int& s = m->wb_slot[c];
+    int& s = m->wb.slot[c];
     if (s < 0) { WbChain C; ba_bridge_chain(h, c, &C.len, C.v); s = (int)chains.size(); chains.push_back(C); }
     return s;
   };
@@ -2085,17 +2091,17 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
     return s;
   };
   std::vector<WbItem> items((size_t)n_points);
-  if (m->wb_stamp == 0x7fffffff) { m->wb_stamp = 0; std::fill(m->wb_mark.begin(), m->wb_mark.end(), 0); }
-  const int stamp = ++m->wb_stamp;
-  if ((int)m->wb_mark.size() < m->rows) m->wb_mark.resize((size_t)m->rows, 0);
+  if (m->wb.stamp == 0x7fffffff) { m->wb.stamp = 0; std::fill(m->wb.mark.begin(), m->wb.mark.end(), 0); }
+  const int stamp = ++m->wb.stamp;
+  if ((int)m->wb.mark.size() < m->rows) m->wb.mark.resize((size_t)m->rows, 0);
   for (int k = 0; k < n_points; ++k) {
     int idx, fixed, c;
     if (ba_bridge_point(h, point_ids[k], &idx, &fixed, &c)) return img_fail(who + ": point_ids[" + std::to_string(k) + "] = " + std::to_string(point_ids[k]) + " is not a point of this bundle");
     const int r = rows[k];
     if (r < 0) return img_fail(who + ": rows[" + std::to_string(k) + "] is negative");
     if (r >= m->rows || !m->has_rays[r]) return img_fail(who + ": row " + std::to_string(r) + " has no patch rays (mcp_map_points_set_rays)");
-    if (m->wb_mark[r] == stamp) return img_fail(who + ": row " + std::to_string(r) + " appears twice");
-    m->wb_mark[r] = stamp;
+    if (m->wb.mark[r] == stamp) return img_fail(who + ": row " + std::to_string(r) + " appears twice");
+    m->wb.mark[r] = stamp;
     const int own = slot_of_solver(c);
     int src = own;
     if (src_chains && src_chain_len[k] != 0) {
@@ -2115,8 +2121,8 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
   const int nslot = (int)chains.size();
   const bool want_vec = n_points > 0 && (world_out || right_out || down_out), want_depths = seg_depths_out != nullptr;
   const WbLayout L(nslot, n_points, n_kf, total, want_vec, want_depths);
-  if (m->wb_in.alloc(L.in_bytes) || m->wb_dev.alloc(L.in_bytes) || m->wb_out.alloc(L.out_bytes) || m->wb_T.alloc(12*(size_t)nslot) || m->wb_depth.alloc((size_t)total)) return -1;
-  char* hin = m->wb_in.p;
+  if (m->wb.in.alloc(L.in_bytes) || m->wb.dev.alloc(L.in_bytes) || m->wb.out.alloc(L.out_bytes) || m->wb.T.alloc(12*(size_t)nslot) || m->wb.depth.alloc((size_t)total)) return -1;
+  char* hin = m->wb.in.p;
   std::memcpy(hin + L.chains, chains.data(), sizeof(WbChain)*(size_t)nslot);
   if (n_points) std::memcpy(hin + L.items, items.data(), sizeof(WbItem)*(size_t)n_points);
   if (n_kf) {
@@ -2125,30 +2131,29 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
     if (total) { std::memcpy(hin + L.seg_rows, seg_rows, sizeof(int)*(size_t)total); std::memcpy(hin + L.seg_w, seg_w, 8*(size_t)total); }
   }
   // the table's stream waits for whatever the solver's stream still has to write of the state
-  ICK(hipEventRecord(m->wb_ev, S.stream));
-  ICK(hipStreamWaitEvent(m->st, m->wb_ev, 0));
-  m->wb_timed = false;
-  ICK(hipEventRecord(m->wb_t[0], m->st));
-  ICK(hipMemcpyAsync(m->wb_dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
-  ICK(hipEventRecord(m->wb_t[1], m->st));
-  const char* din = m->wb_dev.p; char* hout = m->wb_out.p;
-  hipLaunchKernelGGL(k_wb_chains, dim3((unsigned)((nslot + 63)/64)), dim3(64), 0, m->st, nslot, (const WbChain*)(din + L.chains), S.pose, m->wb_T.p,
+  ICK(hipEventRecord(m->wb.ev, S.stream));
+  ICK(hipStreamWaitEvent(m->st, m->wb.ev, 0));
+  m->wb.invalidate();
+  ICK(hipEventRecord(m->wb.t[0], m->st));
+  ICK(hipMemcpyAsync(m->wb.dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->wb.t[1], m->st));
+  const char* din = m->wb.dev.p; char* hout = m->wb.out.p;
+  hipLaunchKernelGGL(k_wb_chains, dim3((unsigned)((nslot + 63)/64)), dim3(64), 0, m->st, nslot, (const WbChain*)(din + L.chains), S.pose, m->wb.T.p,
                      kf_cfw_out ? (double*)(hout + L.T) : (double*)nullptr);
   if (n_points) {
     double* vo = want_vec ? (double*)(hout + L.vec) : nullptr;
     hipLaunchKernelGGL(k_wb_points, dim3((unsigned)((n_points + WB_BLOCK - 1)/WB_BLOCK)), dim3(WB_BLOCK), 0, m->st, n_points, (const WbItem*)(din + L.items), S.point,
-                       (const double*)m->wb_T.p, (const double*)m->rays.p, m->pts.p, vo, vo ? vo + 3*(size_t)n_points : nullptr, vo ? vo + 6*(size_t)n_points : nullptr);
+                       (const double*)m->wb.T.p, m->rays.row(), m->pts.row(), vo, vo ? vo + 3*(size_t)n_points : nullptr, vo ? vo + 6*(size_t)n_points : nullptr);
   }
   hipError_t le = hipGetLastError();
-  (void)hipEventRecord(m->wb_t[2], m->st);
-  if (n_kf) sd_launch(m, n_kf, (const double*)m->wb_T.p, (const int*)(din + L.kf_slot), din, L, hout, want_depths);
+  (void)hipEventRecord(m->wb.t[2], m->st);
+  if (n_kf) sd_launch(m, n_kf, (const double*)m->wb.T.p, (const int*)(din + L.kf_slot), din, L, hout, want_depths);
   if (le == hipSuccess) le = hipGetLastError();
-  (void)hipEventRecord(m->wb_t[3], m->st);
-  const hipError_t se = hipStreamSynchronize(m->st);                 // the one wait: the solver's memory is not read after this
-  m->stage_busy = false;
+  (void)hipEventRecord(m->wb.t[3], m->st);
+  const hipError_t se = m->sync();                                   // the one wait: the solver's memory is not read after this
   if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
   if (se != hipSuccess) return img_fail(who + ": " + hipGetErrorString(se));
-  m->wb_timed = true;
+  m->wb.timed = true;
   if (want_vec) {
     const double* vo = (const double*)(hout + L.vec);
     if (world_out) std::memcpy(world_out, vo, 24*(size_t)n_points);
@@ -2172,7 +2177,7 @@ int mcp_map_refind(mcp_map_points* m, int n_targets, const mcp_refind_target* ta
                    mcp_pf_state* finder, uint8_t* verdict, int cap_meas, mcp_refind_meas* meas, mcp_refind_result* res) {
   static_assert(sizeof(mcp_pf_state) % 8 == 0 && sizeof(RfTarget) % 8 == 0 && sizeof(TmSlot) % 8 == 0, "the packed inputs keep 8-byte alignment");
   if (!m) return img_fail("mcp_map_refind: NULL table");
-  m->rf_view = -1;
+  m->rf.invalidate();
   if (n_targets < 0 || n_pairs < 0 || cap_meas < 0 || !res || (n_pairs > 0 && (!pairs || !verdict || !targets || n_targets == 0)) || (n_targets > 0 && !targets))
     return img_fail("mcp_map_refind: bad arguments");
   for (int t = 0; t < n_targets; ++t) {
@@ -2188,7 +2193,7 @@ int mcp_map_refind(mcp_map_points* m, int n_targets, const mcp_refind_target* ta
     if (pairs[2*(size_t)i + 1] < 0 || pairs[2*(size_t)i + 1] >= n_targets) return img_fail("mcp_map_refind: pair " + std::to_string(i) + " names target " + std::to_string(pairs[2*(size_t)i + 1]) + " of " + std::to_string(n_targets));
   }
   std::memset(res, 0, sizeof *res);
-  if (n_pairs == 0) { m->rf_view = 0; return 0; }
+  if (n_pairs == 0) { m->rf.view = 0; return 0; }
   ICK(hipSetDevice(m->device));
   const int n = n_pairs, nblk = (n + RF_BLOCK - 1)/RF_BLOCK;
   const size_t nslot = std::max<size_t>(m->slots.size(), 1);
@@ -2199,69 +2204,58 @@ int mcp_map_refind(mcp_map_points* m, int n_targets, const mcp_refind_target* ta
   // pinned results: RfOut | verdict bytes | measurements
   const size_t r_vd = tm_align(sizeof(RfOut)), r_ms = r_vd + tm_align((size_t)n), rblk = r_ms + sizeof(mcp_refind_meas)*(size_t)std::max(room, 1);
   // everything is allocated before the first enqueue
-  if (m->rf_in.alloc(blk) || m->rf_dev.alloc(blk) || m->rf_out.alloc(rblk) || m->rf_flags.alloc(n) || m->rf_vd.alloc(n) || m->rf_blk.alloc(2*(size_t)nblk) ||
-      m->rf_items.alloc(n) || m->rf_first.alloc(n) || m->rf_cand.alloc(n)) return -1;
-  char* hb = m->rf_in.p;
+  if (m->rf.in.alloc(blk) || m->rf.dev.alloc(blk) || m->rf.out.alloc(rblk) || m->rf.flags.alloc(n) || m->rf.vd.alloc(n) || m->rf.blk.alloc(2*(size_t)nblk) ||
+      m->rf.items.alloc(n) || m->rf.first.alloc(n) || m->rf.cand.alloc(n)) return -1;
+  char* hb = m->rf.in.p;
   std::memset(hb, 0, o_pr);
   RfTarget* tab = reinterpret_cast<RfTarget*>(hb + o_tg);
   for (int t = 0; t < n_targets; ++t) {
     const mcp_refind_target& G = targets[t];
     tab[t].T = G.kf->view(); tab[t].cam = *G.cam;
-    std::memcpy(tab[t].cfw.R, G.cam_from_world, 72); std::memcpy(tab[t].cfw.t, G.cam_from_world + 9, 24);
+    tab[t].cfw = se3_of12(G.cam_from_world);
   }
-  TmSlot* hs = reinterpret_cast<TmSlot*>(hb + o_sl);
-  {
-    std::lock_guard<std::mutex> reg(g_kf_mu);
-    for (size_t q = 0; q < m->slots.size(); ++q) {
-      const mcp_kf* s = m->slots[q].first;
-      auto live = s ? g_kf_live.find(s) : g_kf_live.end();
-      if (live == g_kf_live.end() || live->second != m->slots[q].second) continue;     // released, destroyed, or its address reused: dead
-      for (int l = 0; l < MCP_LEVELS; ++l) { hs[q].img[l] = s->lev[l].img.p; hs[q].w[l] = s->lev[l].w; hs[q].h[l] = s->lev[l].h; }
-      hs[q].live = 1;
-    }
-  }
+  fill_slots(m, reinterpret_cast<TmSlot*>(hb + o_sl));
   std::memcpy(hb + o_pr, pairs, 8*(size_t)n);
   if (finder) std::memcpy(hb + o_st, finder, sizeof(mcp_pf_state)); else std::memset(hb + o_st, 0, sizeof(mcp_pf_state));
   hipStream_t st = m->st;
-  char* db = m->rf_dev.p;
+  char* db = m->rf.dev.p;
   RfCtl* ctl = reinterpret_cast<RfCtl*>(db + o_ctl);
   int* found_blk = reinterpret_cast<int*>(db + o_fb); int* bad_blk = found_blk + nblk;
   const RfTarget* d_tg = reinterpret_cast<const RfTarget*>(db + o_tg);
   const TmSlot* d_sl = reinterpret_cast<const TmSlot*>(db + o_sl);
   const int* d_pr = reinterpret_cast<const int*>(db + o_pr);
   const mcp_pf_state* d_st = finder ? reinterpret_cast<const mcp_pf_state*>(db + o_st) : nullptr;
-  RfOut* h_out = reinterpret_cast<RfOut*>(m->rf_out.p);
-  uint8_t* h_vd = reinterpret_cast<uint8_t*>(m->rf_out.p + r_vd);
-  mcp_refind_meas* h_ms = reinterpret_cast<mcp_refind_meas*>(m->rf_out.p + r_ms);
-  struct Drain { mcp_map_points* m; bool armed; ~Drain() { if (armed) { (void)hipStreamSynchronize(m->st); (void)hipGetLastError(); } } } drain{m, true};
+  RfOut* h_out = reinterpret_cast<RfOut*>(m->rf.out.p);
+  uint8_t* h_vd = reinterpret_cast<uint8_t*>(m->rf.out.p + r_vd);
+  mcp_refind_meas* h_ms = reinterpret_cast<mcp_refind_meas*>(m->rf.out.p + r_ms);
+  Drain drain{m, true};
   ICK(hipMemcpyAsync(db, hb, blk, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_rf_mark, dim3(nblk), dim3(RF_BLOCK), 0, st, n, per_row_finders ? 1 : 0, d_pr, d_tg, (const PvsPoint*)m->pts.p, (const TmSrc*)m->src.p, d_sl,
-                     m->rf_flags.p, m->rf_vd.p, m->rf_blk.p, m->rf_first.p, ctl);
-  hipLaunchKernelGGL(k_rf_scatter, dim3(nblk), dim3(RF_BLOCK), 0, st, n, nblk, (const uint8_t*)m->rf_flags.p, (const int*)m->rf_blk.p, d_pr, (const TmSrc*)m->src.p, m->rf_items.p, m->rf_first.p, ctl);
-  hipLaunchKernelGGL(k_rf_walk, dim3((unsigned)std::min(n, 65536)), dim3(64), 0, st, d_tg, (const PvsPoint*)m->pts.p, d_sl, (const RfItem*)m->rf_items.p, (const int*)m->rf_first.p, d_st,
-                     m->rf_vd.p, m->rf_cand.p, found_blk, bad_blk, ctl, &h_out->state);
-  hipLaunchKernelGGL(k_rf_commit, dim3(nblk), dim3(RF_BLOCK), 0, st, n, nblk, room, (const uint8_t*)m->rf_vd.p, (const mcp_refind_meas*)m->rf_cand.p, (const int*)found_blk,
-                     (const int*)bad_blk, (const RfItem*)m->rf_items.p, (const RfCtl*)ctl, d_st, h_vd, h_ms, h_out);
+  hipLaunchKernelGGL(k_rf_mark, dim3(nblk), dim3(RF_BLOCK), 0, st, n, per_row_finders ? 1 : 0, d_pr, d_tg, m->pts.row(), m->src.row(), d_sl,
+                     m->rf.flags.p, m->rf.vd.p, m->rf.blk.p, m->rf.first.p, ctl);
+  hipLaunchKernelGGL(k_rf_scatter, dim3(nblk), dim3(RF_BLOCK), 0, st, n, nblk, (const uint8_t*)m->rf.flags.p, (const int*)m->rf.blk.p, d_pr, m->src.row(), m->rf.items.p, m->rf.first.p, ctl);
+  hipLaunchKernelGGL(k_rf_walk, dim3((unsigned)std::min(n, 65536)), dim3(64), 0, st, d_tg, m->pts.row(), d_sl, (const RfItem*)m->rf.items.p, (const int*)m->rf.first.p, d_st,
+                     m->rf.vd.p, m->rf.cand.p, found_blk, bad_blk, ctl, &h_out->state);
+  hipLaunchKernelGGL(k_rf_commit, dim3(nblk), dim3(RF_BLOCK), 0, st, n, nblk, room, (const uint8_t*)m->rf.vd.p, (const mcp_refind_meas*)m->rf.cand.p, (const int*)found_blk,
+                     (const int*)bad_blk, (const RfItem*)m->rf.items.p, (const RfCtl*)ctl, d_st, h_vd, h_ms, h_out);
   ICK(hipGetLastError());
-  ICK(hipStreamSynchronize(st));
+  ICK(m->sync());
   drain.armed = false;
-  m->stage_busy = false;
   for (int q = 0; q < 6; ++q) res->counts[q] = h_out->counts[q];
   res->n_meas = h_out->n_meas;
   std::memcpy(verdict, h_vd, (size_t)n);
   if (finder) *finder = h_out->state;
   if (res->n_meas > cap_meas)
     return img_fail("mcp_map_refind: " + std::to_string(res->n_meas) + " pairs were found, cap_meas is " + std::to_string(cap_meas));
-  m->rf_meas_off = r_ms; m->rf_view = res->n_meas;
+  m->rf.meas_off = r_ms; m->rf.view = res->n_meas;
   if (meas && res->n_meas) std::memcpy(meas, h_ms, sizeof(mcp_refind_meas)*(size_t)res->n_meas);
   return 0;
 }
 
 const mcp_refind_meas* mcp_map_refind_view(const mcp_map_points* m, int* count) {
   if (count) *count = 0;
-  if (!m || m->rf_view < 0) { img_fail("mcp_map_refind_view: the last mcp_map_refind on this table left no measurements to show"); return nullptr; }
-  if (count) *count = m->rf_view;
-  return m->rf_view > 0 ? reinterpret_cast<const mcp_refind_meas*>(m->rf_out.p + m->rf_meas_off) : nullptr;
+  if (!m || m->rf.view < 0) { img_fail("mcp_map_refind_view: the last mcp_map_refind on this table left no measurements to show"); return nullptr; }
+  if (count) *count = m->rf.view;
+  return m->rf.view > 0 ? reinterpret_cast<const mcp_refind_meas*>(m->rf.out.p + m->rf.meas_off) : nullptr;
 }
 
 }  // extern "C"

@@ -60,6 +60,39 @@ def _usable(u, n):
     return u
 
 
+def _frame_args(targets, cams, base_from_world, cams_from_base, imgs=None, on_device=False, strides=None):
+    """What every frame call passes: (ncam, target handles, camera array as void*, BaseFromWorld as 12 doubles (a copy: track_map refines it),
+    CamFromBase (ncam x 12), image pointers or None, strides or None, and whatever must stay alive until the call returns)."""
+    ncam = len(targets)
+    hs = (ctypes.c_void_p * ncam)(*[t._h for t in targets])
+    cs = cams if isinstance(cams, ctypes.Array) else camera_array(cams)
+    b = _pose12(*base_from_world).copy()
+    cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1) if isinstance(cams_from_base, np.ndarray) else \
+        np.ascontiguousarray(np.concatenate([_pose12(*c) for c in cams_from_base]))
+    ip = st = keep = None
+    if imgs is not None:
+        if on_device:
+            ip = (ctypes.c_void_p * ncam)(*[int(a) for a in imgs])
+            st = (ctypes.c_int * ncam)(*[int(s_) for s_ in (strides or [k.w for k in targets])])
+        else:
+            keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in imgs]
+            ip = (ctypes.c_void_p * ncam)(*[a.ctypes.data for a in keep])
+            st = (ctypes.c_int * ncam)(*[a.strides[0] for a in keep])
+    return ncam, hs, ctypes.cast(cs, ctypes.c_void_p), b, cfb, ip, st, (cs, keep)
+
+
+def _view(fn, args, dtype, expect=None, copy=False, mismatch=""):
+    """The array behind one of the library's *_view calls: fn(*args, &count) -> pointer into a pinned block that stays valid until the next
+    call on the table.  expect: the count the call's own results announce; mismatch: the error's text when the view disagrees, a format
+    of (got, expect), followed by the library's last error."""
+    cnt = ctypes.c_int(0)
+    ptr = fn(*args, ctypes.byref(cnt))
+    if expect is not None and cnt.value != expect:
+        raise RuntimeError(mismatch % dict(got=cnt.value, expect=expect) + _cb.last_error())
+    a = np.frombuffer((ctypes.c_char * (cnt.value * dtype.itemsize)).from_address(ptr), dtype=dtype) if cnt.value else np.zeros(0, dtype=dtype)
+    return a.copy() if copy else a
+
+
 class MapPointTable:
     """Device-resident map-point table (one device).  Row = point index in the caller's order.  Inputs are numpy SoA arrays."""
 
@@ -109,12 +142,7 @@ class MapPointTable:
         camera (default: the table's rows); out: per-camera PVS_ENTRY_DTYPE arrays of at least caps[c] entries, or None.
         view=True: the lists are views of the library's pinned block, valid until the next call on this table.
         Returns, per camera, the four per-level arrays (rows ascending).  self.counts = (ncam, LEVELS) counts, set even when the call fails."""
-        ncam = len(targets)
-        hs = (ctypes.c_void_p * ncam)(*[t._h for t in targets])
-        cs = cams if isinstance(cams, ctypes.Array) else camera_array(cams)
-        b = _pose12(*base_from_world)
-        cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1) if isinstance(cams_from_base, np.ndarray) else \
-            np.ascontiguousarray(np.concatenate([_pose12(*c) for c in cams_from_base]))
+        ncam, hs, cs, b, cfb, _, _, keep = _frame_args(targets, cams, base_from_world, cams_from_base)
         rows = self.rows
         caps = np.ascontiguousarray([rows] * ncam if caps is None else caps, dtype=np.int32)
         counts = np.zeros((ncam, LEVELS), dtype=np.int32)
@@ -128,20 +156,13 @@ class MapPointTable:
             for c in range(ncam):
                 assert out[c].dtype == PVS_ENTRY_DTYPE and len(out[c]) >= caps[c] and out[c].flags.c_contiguous
             ops = (ctypes.c_void_p * ncam)(*[o.ctypes.data for o in out])
-        _chk(self._L.mcp_track_find_pvs(self._h, ncam, hs, ctypes.cast(cs, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data, caps.ctypes.data,
-                                        ops, counts.ctypes.data), "track_find_pvs")
+        _chk(self._L.mcp_track_find_pvs(self._h, ncam, hs, cs, b.ctypes.data, cfb.ctypes.data, caps.ctypes.data, ops, counts.ctypes.data), "track_find_pvs")
+        del keep
         res = []
         for c in range(ncam):
             if view:
-                lv = []
-                for l in range(LEVELS):
-                    cnt = ctypes.c_int(0)
-                    ptr = self._L.mcp_track_find_pvs_view(self._h, c, l, ctypes.byref(cnt))
-                    if cnt.value != counts[c, l]:
-                        raise RuntimeError("mcp_track_find_pvs_view: " + _cb.last_error())
-                    lv.append(np.frombuffer((ctypes.c_char * (cnt.value * PVS_ENTRY_DTYPE.itemsize)).from_address(ptr), dtype=PVS_ENTRY_DTYPE)
-                              if cnt.value else np.zeros(0, dtype=PVS_ENTRY_DTYPE))
-                res.append(lv)
+                res.append([_view(self._L.mcp_track_find_pvs_view, (self._h, c, l), PVS_ENTRY_DTYPE, counts[c, l], mismatch="mcp_track_find_pvs_view: ")
+                            for l in range(LEVELS)])
             else:
                 offs = np.concatenate([[0], np.cumsum(counts[c])]).astype(int)
                 res.append([out[c][offs[l]:offs[l + 1]] for l in range(LEVELS)])
@@ -265,34 +286,13 @@ class MapPointTable:
         """mcp_track_map: the whole TrackMap of a frame.  Returns (items per camera (TRACK_MAP_ITEM_DTYPE; copies unless copy=False: views of
         the library's pinned block), (R, t), TrackMapResult)."""
         L = _bind_track_map(self._L)
-        ncam = len(targets)
-        hs = (ctypes.c_void_p * ncam)(*[t._h for t in targets])
-        cs = cams if isinstance(cams, ctypes.Array) else camera_array(cams)
-        b = _pose12(*base_from_world).copy()
-        cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1) if isinstance(cams_from_base, np.ndarray) else \
-            np.ascontiguousarray(np.concatenate([_pose12(*c) for c in cams_from_base]))
+        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
         prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
                              MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
         res = TrackMapResult()
-        ip = st = keep = None
-        if imgs is not None:
-            if on_device:
-                ip = (ctypes.c_void_p * ncam)(*[int(a) for a in imgs])
-                st = (ctypes.c_int * ncam)(*[int(s_) for s_ in (strides or [k.w for k in targets])])
-            else:
-                keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in imgs]
-                ip = (ctypes.c_void_p * ncam)(*[a.ctypes.data for a in keep])
-                st = (ctypes.c_int * ncam)(*[a.strides[0] for a in keep])
-        _chk(L.mcp_track_map(self._h, ncam, hs, ip, st, int(on_device), None, ctypes.cast(cs, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
-                             ctypes.byref(prm), ctypes.byref(res)), "track_map")
+        _chk(L.mcp_track_map(self._h, ncam, hs, ip, st, int(on_device), None, cs, b.ctypes.data, cfb.ctypes.data, ctypes.byref(prm), ctypes.byref(res)), "track_map")
         del keep
-        items = []
-        for c in range(ncam):
-            cnt = ctypes.c_int(0)
-            ptr = L.mcp_track_map_view(self._h, c, ctypes.byref(cnt))
-            a = np.frombuffer((ctypes.c_char * (cnt.value * TRACK_MAP_ITEM_DTYPE.itemsize)).from_address(ptr), dtype=TRACK_MAP_ITEM_DTYPE) \
-                if cnt.value else np.zeros(0, dtype=TRACK_MAP_ITEM_DTYPE)
-            items.append(a.copy() if copy else a)
+        items = [_view(L.mcp_track_map_view, (self._h, c), TRACK_MAP_ITEM_DTYPE, copy=copy) for c in range(ncam)]
         return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res
 
     # ---- TrackMap with its bookkeeping (include/mcp_img.h mcp_track_map_record) ----
@@ -326,39 +326,18 @@ class MapPointTable:
         gate's).  Returns (items per camera, or None with want_items=False; (R, t); TrackMapResult; notes per camera (TRACK_NOTE_DTYPE);
         measurements per camera (TRACK_MEAS_DTYPE); TrackRecord) -- copies unless copy=False."""
         L = _bind_track_record(_bind_track_map(self._L))
-        ncam = len(targets)
-        hs = (ctypes.c_void_p * ncam)(*[t._h for t in targets])
-        cs = cams if isinstance(cams, ctypes.Array) else camera_array(cams)
-        b = _pose12(*base_from_world).copy()
-        cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1) if isinstance(cams_from_base, np.ndarray) else \
-            np.ascontiguousarray(np.concatenate([_pose12(*c) for c in cams_from_base]))
+        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
         prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
                              MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
         rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
         res, rec = TrackMapResult(), TrackRecord()
-        ip = st = keep = None
-        if imgs is not None:
-            if on_device:
-                ip = (ctypes.c_void_p * ncam)(*[int(a) for a in imgs])
-                st = (ctypes.c_int * ncam)(*[int(s_) for s_ in (strides or [k.w for k in targets])])
-            else:
-                keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in imgs]
-                ip = (ctypes.c_void_p * ncam)(*[a.ctypes.data for a in keep])
-                st = (ctypes.c_int * ncam)(*[a.strides[0] for a in keep])
-        _chk(L.mcp_track_map_record(self._h, ncam, hs, ip, st, int(on_device), None, ctypes.cast(cs, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
+        _chk(L.mcp_track_map_record(self._h, ncam, hs, ip, st, int(on_device), None, cs, b.ctypes.data, cfb.ctypes.data,
                                     ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec)), "track_map_record")
         del keep
 
         def views(fn, dtype, expect):
-            out = []
-            for c in range(ncam):
-                cnt = ctypes.c_int(0)
-                ptr = fn(self._h, c, ctypes.byref(cnt))
-                if cnt.value != expect[c]:
-                    raise RuntimeError("track_map_record: view of camera %d has %d entries, the record says %d: %s" % (c, cnt.value, expect[c], _cb.last_error()))
-                a = np.frombuffer((ctypes.c_char * (cnt.value * dtype.itemsize)).from_address(ptr), dtype=dtype) if cnt.value else np.zeros(0, dtype=dtype)
-                out.append(a.copy() if copy else a)
-            return out
+            text = "track_map_record: view of camera %d has %%(got)d entries, the record says %%(expect)d: "
+            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
         items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
         notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
         meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)

@@ -60,6 +60,12 @@ def test_pvs_refuses_without_a_table():
     assert L.mcp_map_points_resize(None, 0) == -1
     n = ctypes.c_int(5)
     assert L.mcp_track_find_pvs_view(None, 0, 0, ctypes.byref(n)) is None and n.value == 0
+    # the read-backs refuse before they size anything from `count`
+    from mcptam_amd.pvs import _bind_track_map, _bind_track_record, _bind_write_back
+    L = _bind_track_record(_bind_track_map(_bind_write_back(L)))
+    for call in (lambda: L.mcp_map_points_get(None, 0, 0x7fffffff, None, None, None, None), lambda: L.mcp_map_points_get_counts(None, 0, 0x7fffffff, None, None),
+                 lambda: L.mcp_map_points_get_states(None, 0, 0, 0x7fffffff, None)):
+        assert call() == -1 and "NULL table" in chain_bundle.last_error()
 
 
 def test_cpp_map_point_table_compiles_and_links(tmp_path):

@@ -219,6 +219,39 @@ def test_pvs_table_life(gpu_required, world):
     assert all((lv["point"] % 2 == 1).all() for cam in got for lv in cam)
 
 
+@pytest.mark.parametrize("column", ["update", "update_source", "update_rays", "update_counts"])
+def test_update_refuses_bad_row_ids(gpu_required, column):
+    """Every upload by id refuses a row named twice, a negative row and row 0x7fffffff (it has no successor) with the matching message,
+    and leaves the table's size and its columns as they were."""
+    from mcptam_amd.pvs import MapPointTable
+    rng = np.random.default_rng(21)
+    t = MapPointTable()
+    t.set(rng.normal(size=(8, 3)), rng.normal(size=(8, 3)), rng.normal(size=(8, 3)), np.arange(8) % 2)
+    t.set_counts(np.arange(2, 10), np.arange(8))
+    t.set_rays(rng.normal(size=(8, 3)), rng.normal(size=(8, 3)), rng.normal(size=(8, 3)))
+    t.set_source(np.arange(8), [None] * 8, [0] * 8, np.zeros((8, 2), dtype=np.int32))
+    snapshot = lambda: (t.rows, [a.tobytes() for a in t.get()], [a.tobytes() for a in t.get_counts()], t.get_states(0).tobytes())
+    before = snapshot()
+    for ids, err in (([1, 5, 1], "row 1 appears twice"), ([3, -1, 4], "bad row id"), ([2, 0x7fffffff, 6], "bad row id")):
+        z = np.ones((3, 3))
+        call = {"update": lambda: t.update(ids, z, z, z), "update_source": lambda: t.update_source(ids, [7, 8, 9], [None] * 3, [0] * 3, np.zeros((3, 2))),
+                "update_rays": lambda: t.update_rays(ids, z, z, z), "update_counts": lambda: t.update_counts(ids, [5, 5, 5], [1, 1, 1])}[column]
+        with pytest.raises(RuntimeError) as e:
+            call()
+        assert "mcp_map_points_" + column in str(e.value) and err in str(e.value), (ids, str(e.value))
+        assert snapshot() == before
+    # a read-back past the table's rows is refused before anything is sized from the count
+    from mcptam_amd import chain_bundle
+    from mcptam_amd.pvs import _bind_track_map, _bind_track_record, _bind_write_back
+    L = _bind_track_record(_bind_track_map(_bind_write_back(t._L)))
+    for name, call in (("get", lambda: L.mcp_map_points_get(t._h, 0, 0x7fffffff, None, None, None, None)),
+                       ("get", lambda: L.mcp_map_points_get(t._h, 7, 2, None, None, None, None)),
+                       ("get_counts", lambda: L.mcp_map_points_get_counts(t._h, 0, 0x7fffffff, None, None)),
+                       ("get_states", lambda: L.mcp_map_points_get_states(t._h, 0, 1, 8, None))):
+        assert call() == -1 and chain_bundle.last_error() == "mcp_map_points_%s: bad arguments" % name
+    assert snapshot() == before
+
+
 def test_pvs_batch_equals_single_cameras_and_is_deterministic(gpu_required, world):
     w = world
     t = _table(w["wp"], w["pr"], w["pd"], w["usable"])
