@@ -10,8 +10,8 @@
 #include <vector>
 #include <limits>
 #include <map>
+#include <functional>
 #include <memory>
-#include <cmath>
 #include <mutex>
 #include <unordered_map>
 
@@ -118,6 +118,36 @@ static std::unordered_map<const mcp_kf*, unsigned long long> g_kf_live;
 static unsigned long long g_kf_serial = 0;
 static unsigned long long kf_live_serial(const mcp_kf* k) { std::lock_guard<std::mutex> g(g_kf_mu); auto it = g_kf_live.find(k); return it == g_kf_live.end() ? 0ull : it->second; }
 
+// ---- what the entries below pack for the kernels, each said once ---------------------------------------------------------------------
+static Se3 se3_of12(const double* a) { Se3 T; std::memcpy(T.R, a, 72); std::memcpy(T.t, a + 9, 24); return T; }
+// the level-0 mask of the frame a keyframe holds, or null
+static const uint8_t* mask0_of(const mcp_kf* k) { return k->lev[0].has_mask ? k->lev[0].mask.p : nullptr; }
+// a target record's view, mask and camera (PfTargetDev, TmCam, StereoTargetDev: the poses that follow differ) ...
+template <class Target> static void target_of(Target& D, const mcp_kf* k, const mcp_camera& cam) { D.T = k->view(); D.mask0 = mask0_of(k); D.cam = cam; }
+// ... and a finder target whole
+static void target_of(PfTargetDev& D, const mcp_kf* k, const mcp_camera& cam, const double* bfw, const double* cfb) {
+  target_of(D, k, cam); D.bfw = se3_of12(bfw); D.cfb = se3_of12(cfb);
+}
+// a caller's point as the kernels read it; false, and nothing written, for a point without a resident source keyframe and level
+static bool td_in_resident(const mcp_td_in& p) { return p.source_kf && p.source_level >= 0 && p.source_level < MCP_LEVELS; }
+static bool td_in_dev(const mcp_td_in& p, DevTdIn& d) {
+  if (!td_in_resident(p)) return false;
+  std::memcpy(d.world_pos, p.world_pos, 24); std::memcpy(d.pixel_right_w, p.pixel_right_w, 24); std::memcpy(d.pixel_down_w, p.pixel_down_w, 24);
+  const Level& S = p.source_kf->lev[p.source_level];
+  d.src_img = S.img.p; d.src_w = S.w; d.src_h = S.h; d.center_x = p.center_x; d.center_y = p.center_y; d.fixed = p.fixed;
+  return true;
+}
+// the inputs of a frame's search as its pack step leaves them: at most four (pinned source, device destination, bytes).  They reach the
+// device as copies on the stream, or inside the pyramids' second launch (FrameBatch::up_*, 8-byte words: a source is padded to a whole word)
+struct Uploads {
+  const void* src[4]; void* dst[4]; size_t bytes[4]; int n = 0;
+  void add(const void* s, void* d, size_t b) { src[n] = s; dst[n] = d; bytes[n] = b; ++n; }
+  int copy(hipStream_t st) const { for (int r = 0; r < n; ++r) ICK(hipMemcpyAsync(dst[r], src[r], bytes[r], hipMemcpyHostToDevice, st)); return 0; }
+  void ride(FrameBatch& B) const {
+    for (int r = 0; r < n; ++r) { B.up_src[r] = static_cast<const unsigned long long*>(src[r]); B.up_dst[r] = static_cast<unsigned long long*>(dst[r]); B.up_n8[r] = (int)((bytes[r] + 7)/8); }
+  }
+};
+
 static bool gfx950(int dev) { hipDeviceProp_t p; return hipGetDeviceProperties(&p, dev) == hipSuccess && std::strncmp(p.gcnArchName, "gfx950", 6) == 0; }
 
 extern "C" {
@@ -156,9 +186,9 @@ void mcp_kf_destroy(mcp_kf* k) {
 // MakeKeyFrame_Lite of every camera of a frame in one submission (the loop of Tracker::TrackFrame, src/Tracker.cc:303-318): the
 // uploads, three launches for all levels of all cameras (k_pyr_fast, k_row_count, k_row_compact) and one wait.
 // (enqueue on kfs[0]->st without waiting; lite_batch_finish after the stream has been waited for)
-// (ride: called after k_pyr_fast has been launched -- host work done here overlaps it -- to name up to two pinned-host -> device copies that
+// (ride: called after k_pyr_fast has been launched -- host work done here overlaps it -- to name up to four pinned-host -> device copies that
 //  k_row_count's grid then carries in one more z-slice, FrameBatch::up_*)
-struct FrameRide { int (*fn)(void* ctx, FrameBatch& B); void* ctx; };
+using FrameRide = std::function<int(FrameBatch&)>;
 static int lite_batch_enqueue(int ncam, mcp_kf* const* kfs, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                               const uint8_t* const* const* masks, const FrameRide* ride = nullptr) {
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !kfs || !imgs || !strides) return img_fail("mcp_kf_make_lite_batch: bad arguments");
@@ -214,7 +244,7 @@ static int lite_batch_enqueue(int ncam, mcp_kf* const* kfs, const uint8_t* const
       hipLaunchKernelGGL(k_glare_mask, dim3((unsigned)((npx + 255)/256)), dim3(256), 0, st, src, internal, L.mask.p, (int)npx);
     }
   }
-  if (ride && ride->fn(ride->ctx, B)) return -1;
+  if (ride && (*ride)(B)) return -1;
   const int up = (B.up_n8[0] > 0 || B.up_n8[1] > 0 || B.up_n8[2] > 0 || B.up_n8[3] > 0) ? 1 : 0;
   static const bool one_launch = [] { const char* e = getenv("MCP_IMG_ROW_TABLES"); return e ? atoi(e) != 0 : true; }();      // (0: k_row_count + k_row_compact, the round-5 pair)
   if (one_launch) hipLaunchKernelGGL(k_row_tables, dim3((maxh + 3)/4, MCP_LEVELS, ncam + up), dim3(256), 0, st, B);
@@ -392,25 +422,38 @@ static RefineScratch& refine_scratch() {
   if (!p) p.reset(new RefineScratch());
   return *p;
 }
+// where the parts behind the block's 24-double head start, and its size
+struct RefineBlock {
+  size_t ov, cfb, cam, nl, bytes;
+  RefineBlock(int n_iter, int ncam) : ov(24*sizeof(double)), cfb(ov + 8*(size_t)n_iter), cam(cfb + 96*(size_t)ncam), nl(cam + sizeof(mcp_camera)*(size_t)ncam),
+                                      bytes(((nl + (size_t)n_iter + 15)/16)*16) {}
+};
+// k_pose_refine_regs' dynamic LDS is a function attribute, and those are per device: set on first use by this thread on `dev`; whether the
+// device took it
+static bool pose_regs_attr(int dev) {
+  static thread_local unsigned long long set_mask = 0, ok_mask = 0;
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(set_mask & bit)) {
+    set_mask |= bit;
+    if (hipFuncSetAttribute((const void*)k_pose_refine_regs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRR_DYN_LDS) == hipSuccess) ok_mask |= bit;
+    else (void)hipGetLastError();
+  }
+  return (ok_mask & bit) != 0;
+}
 // The iterations enqueued on `st`: the points come from host_pts (uploaded first) or are in the scratch's dp already (host_pts == nullptr:
 // mcp_track_frame packs them on the device).  BaseFromWorld | mu are left at the head of the scratch's dblk, the weights in dw; *prm_err
 // receives the multi-workgroup kernel's give-up flag once the stream has been waited for.
 static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const mcp_camera* cams, const double* cfb, const double bfw[12], int n_iter,
                           const uint8_t* nonlinear, const double* override_sigma, int est, hipStream_t st, unsigned int* prm_err) {
   RefineScratch& rs = refine_scratch();
-  const size_t o_ov = 24*sizeof(double), o_cfb = o_ov + 8*(size_t)n_iter, o_cam = o_cfb + 96*(size_t)ncam;
-  const size_t o_nl = o_cam + sizeof(mcp_camera)*(size_t)ncam, blk = ((o_nl + (size_t)n_iter + 15)/16)*16;
+  const RefineBlock O(n_iter, ncam);
+  const size_t blk = O.bytes;
   static const int use_regs = [] { const char* e = getenv("MCP_TRACK_REFINE_REGS"); return e ? atoi(e) : 1; }();
-  // (function attributes are per device: set on the device this call runs on, once per device and thread)
-  static thread_local unsigned long long regs_set_mask = 0, regs_ok_mask = 0;
+  static thread_local unsigned long long regs_refused_mask = 0;      // devices that took the attribute and then refused the launch
   int cur_dev = 0; (void)hipGetDevice(&cur_dev);
   const unsigned long long dbit = 1ull << (cur_dev & 63);
-  if (!(regs_set_mask & dbit)) {
-    regs_set_mask |= dbit;
-    if (hipFuncSetAttribute((const void*)k_pose_refine_regs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRR_DYN_LDS) == hipSuccess) regs_ok_mask |= dbit;
-    else (void)hipGetLastError();
-  }
-  bool regs = use_regs && (regs_ok_mask & dbit) && n <= PRR_THREADS*PRR_PPT && ncam <= PRR_CAMS;          // the points fit the register-resident kernel, the rig its LDS
+  const bool regs_ok = pose_regs_attr(cur_dev) && !(regs_refused_mask & dbit);
+  bool regs = use_regs && regs_ok && n <= PRR_THREADS*PRR_PPT && ncam <= PRR_CAMS;          // the points fit the register-resident kernel, the rig its LDS
   // many points: the iterations over several workgroups (k_pose_refine_multi); MCP_TRACK_REFINE_MULTI = 0 never, 1 whenever the
   // points do not fit the register-resident kernel (default), 2 always
   const int use_multi = [] { const char* e = getenv("MCP_TRACK_REFINE_MULTI"); return e ? atoi(e) : 1; }();
@@ -422,10 +465,10 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
   if (!regs && alloc_plain()) return -1;
   rs.hblk.assign(blk, 0);
   std::memcpy(rs.hblk.data(), bfw, 96);
-  std::memcpy(rs.hblk.data() + o_ov, override_sigma, 8*(size_t)n_iter);
-  std::memcpy(rs.hblk.data() + o_cfb, cfb, 96*(size_t)ncam);
-  std::memcpy(rs.hblk.data() + o_cam, cams, sizeof(mcp_camera)*(size_t)ncam);
-  std::memcpy(rs.hblk.data() + o_nl, nonlinear, (size_t)n_iter);
+  std::memcpy(rs.hblk.data() + O.ov, override_sigma, 8*(size_t)n_iter);
+  std::memcpy(rs.hblk.data() + O.cfb, cfb, 96*(size_t)ncam);
+  std::memcpy(rs.hblk.data() + O.cam, cams, sizeof(mcp_camera)*(size_t)ncam);
+  std::memcpy(rs.hblk.data() + O.nl, nonlinear, (size_t)n_iter);
   if (host_pts) ICK(hipMemcpyAsync(rs.dp.p, host_pts, sizeof(mcp_pose_point)*(size_t)n, hipMemcpyHostToDevice, st));
   rs.res_pinned = false;
   if (regs) {
@@ -434,16 +477,16 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
     std::memset(rs.pw.p, 0, 8*(size_t)n);                       // weights stay zero when a point was not found
     uint8_t* b = rs.pblk.p;
     double* p_bfw = reinterpret_cast<double*>(b);
-    hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, n, rs.dp.p, reinterpret_cast<const mcp_camera*>(b + o_cam), reinterpret_cast<const double*>(b + o_cfb),
-                       p_bfw, n_iter, (const uint8_t*)(b + o_nl), reinterpret_cast<const double*>(b + o_ov), p_bfw + 12, rs.pw.p, est, ncam);
+    hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, n, rs.dp.p, reinterpret_cast<const mcp_camera*>(b + O.cam), reinterpret_cast<const double*>(b + O.cfb),
+                       p_bfw, n_iter, (const uint8_t*)(b + O.nl), reinterpret_cast<const double*>(b + O.ov), p_bfw + 12, rs.pw.p, est, ncam);
     if (hipGetLastError() != hipSuccess) {       // the launch was refused (123 KB of dynamic LDS): the plain kernel does the same work from global memory
-      regs = false; regs_ok_mask &= ~dbit;
+      regs = false; regs_refused_mask |= dbit;
       if (alloc_plain()) return -1;
     } else rs.res_pinned = true;
   }
   double* d_bfw = reinterpret_cast<double*>(rs.dblk.p); double* d_mu = d_bfw + 12;
-  const double* d_ov = reinterpret_cast<const double*>(rs.dblk.p + o_ov); const double* d_cfb = reinterpret_cast<const double*>(rs.dblk.p + o_cfb);
-  const mcp_camera* d_cam = reinterpret_cast<const mcp_camera*>(rs.dblk.p + o_cam); const uint8_t* d_nl = rs.dblk.p + o_nl;
+  const double* d_ov = reinterpret_cast<const double*>(rs.dblk.p + O.ov); const double* d_cfb = reinterpret_cast<const double*>(rs.dblk.p + O.cfb);
+  const mcp_camera* d_cam = reinterpret_cast<const mcp_camera*>(rs.dblk.p + O.cam); const uint8_t* d_nl = rs.dblk.p + O.nl;
   if (!regs) {
     ICK(hipMemcpyAsync(rs.dblk.p, rs.hblk.data(), blk, hipMemcpyHostToDevice, st));
     if (!multi) ICK(hipMemsetAsync(rs.dw.p, 0, 8*(size_t)n, st));             // weights stay zero when no point was found
@@ -514,14 +557,33 @@ static int refine_redo_single(int n, int n_iter, int ncam, int est, hipStream_t 
   RefineScratch& rs = refine_scratch();
   if (!rs.dp_keep.p || rs.hblk.empty()) return img_fail("pose iterations: nothing kept to redo them from");
   rs.res_pinned = false;
-  const size_t o_ov = 24*sizeof(double), o_cfb = o_ov + 8*(size_t)n_iter, o_cam = o_cfb + 96*(size_t)ncam, o_nl = o_cam + sizeof(mcp_camera)*(size_t)ncam;
+  const RefineBlock O(n_iter, ncam);
   ICK(hipMemcpyAsync(rs.dp.p, rs.dp_keep.p, sizeof(mcp_pose_point)*(size_t)n, hipMemcpyDeviceToDevice, st));
   ICK(hipMemcpyAsync(rs.dblk.p, rs.hblk.data(), rs.hblk.size(), hipMemcpyHostToDevice, st));
   ICK(hipMemsetAsync(rs.dw.p, 0, 8*(size_t)n, st));
   double* d_bfw = reinterpret_cast<double*>(rs.dblk.p); double* d_mu = d_bfw + 12;
-  hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, n, rs.dp.p, reinterpret_cast<const mcp_camera*>(rs.dblk.p + o_cam), reinterpret_cast<const double*>(rs.dblk.p + o_cfb),
-                     d_bfw, n_iter, (const uint8_t*)(rs.dblk.p + o_nl), reinterpret_cast<const double*>(rs.dblk.p + o_ov), rs.dJ.p, rs.dex.p, rs.de2.p, d_mu, rs.dw.p, est);
+  hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, n, rs.dp.p, reinterpret_cast<const mcp_camera*>(rs.dblk.p + O.cam), reinterpret_cast<const double*>(rs.dblk.p + O.cfb),
+                     d_bfw, n_iter, (const uint8_t*)(rs.dblk.p + O.nl), reinterpret_cast<const double*>(rs.dblk.p + O.ov), rs.dJ.p, rs.dex.p, rs.de2.p, d_mu, rs.dw.p, est);
   ICK(hipGetLastError());
+  return 0;
+}
+// the tail of the iterations refine_enqueue put on `st`: the results' copies, the wait, the results taken from pinned memory; should a
+// workgroup of the multi-workgroup kernel have given up (*prm_err; MCP_TRACK_TEST_PRM_GIVEUP forces it), the same once more after
+// refine_redo_single.  `back` gets BaseFromWorld | mu; pts_back, where not null, the pose records each time.
+static int refine_collect(int n, int n_iter, int ncam, int est, hipStream_t st, const unsigned int* prm_err, mcp_pose_point* pts_back, double back[18], double* weights_last) {
+  RefineScratch& rs = refine_scratch();
+  auto fetch = [&]() -> int {
+    if (pts_back) ICK(hipMemcpyAsync(pts_back, rs.dp.p, sizeof(mcp_pose_point)*(size_t)n, hipMemcpyDeviceToHost, st));
+    if (refine_results_enqueue(rs, n, back, weights_last, st)) return -1;
+    ICK(hipStreamSynchronize(st));
+    refine_results_finish(rs, n, back, weights_last);
+    return 0;
+  };
+  if (fetch()) return -1;
+  if (*prm_err || (rs.last_multi && getenv("MCP_TRACK_TEST_PRM_GIVEUP"))) {
+    // a workgroup gave up waiting for the others: the frame is not lost, one workgroup redoes the iterations
+    if (refine_redo_single(n, n_iter, ncam, est, st) || fetch()) return -1;
+  }
   return 0;
 }
 int mcp_track_pose_refine_m(int n, mcp_pose_point* pts, int ncam, const mcp_camera* cams, const double* cfb, double bfw[12], int n_iter,
@@ -536,19 +598,9 @@ int mcp_track_pose_refine_m(int n, mcp_pose_point* pts, int ncam, const mcp_came
   int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return img_fail("mcp_track_pose_refine: no HIP device");
   hipStream_t st = nullptr;
   unsigned int prm_err = 0;
-  if (refine_enqueue(n, pts, ncam, cams, cfb, bfw, n_iter, nonlinear, override_sigma, est, st, &prm_err)) return -1;
-  RefineScratch& rs = refine_scratch();
   double back[18];
-  ICK(hipMemcpyAsync(pts, rs.dp.p, sizeof(mcp_pose_point)*(size_t)n, hipMemcpyDeviceToHost, st));
-  if (refine_results_enqueue(rs, n, back, weights_last, st)) return -1;
-  ICK(hipStreamSynchronize(st));
-  refine_results_finish(rs, n, back, weights_last);
-  if (prm_err || (rs.last_multi && getenv("MCP_TRACK_TEST_PRM_GIVEUP"))) {
-    if (refine_redo_single(n, n_iter, ncam, est, st)) return -1;
-    ICK(hipMemcpyAsync(pts, rs.dp.p, sizeof(mcp_pose_point)*(size_t)n, hipMemcpyDeviceToHost, st));
-    if (refine_results_enqueue(rs, n, back, weights_last, st)) return -1;
-    ICK(hipStreamSynchronize(st));
-  }
+  if (refine_enqueue(n, pts, ncam, cams, cfb, bfw, n_iter, nonlinear, override_sigma, est, st, &prm_err) ||
+      refine_collect(n, n_iter, ncam, est, st, &prm_err, pts, back, weights_last)) return -1;
   std::memcpy(bfw, back, 96); std::memcpy(mu_last, back + 12, 48);
   return 0;
 }
@@ -744,27 +796,21 @@ int mcp_track_search(mcp_kf* target, const mcp_camera* cam, const double bfw[12]
   if (n == 0) return 0;
   ICK(hipSetDevice(target->device));
   std::vector<DevTdIn> h(n);
-  for (int i = 0; i < n; ++i) {
-    const mcp_td_in& p = in[i];
-    if (!p.source_kf || p.source_level < 0 || p.source_level >= MCP_LEVELS) return img_fail("mcp_track_search: point without a resident source keyframe");
-    std::memcpy(h[i].world_pos, p.world_pos, 24); std::memcpy(h[i].pixel_right_w, p.pixel_right_w, 24); std::memcpy(h[i].pixel_down_w, p.pixel_down_w, 24);
-    const Level& S = p.source_kf->lev[p.source_level];
-    h[i].src_img = S.img.p; h[i].src_w = S.w; h[i].src_h = S.h; h[i].center_x = p.center_x; h[i].center_y = p.center_y; h[i].fixed = p.fixed;
-  }
+  for (int i = 0; i < n; ++i) if (!td_in_dev(in[i], h[i])) return img_fail("mcp_track_search: point without a resident source keyframe");
   Buf<DevTdIn>& din = target->td_in; Buf<mcp_td_out>& dout = target->td_out;
   if (din.alloc(n) || dout.alloc(n)) return -1;
   ICK(hipMemcpyAsync(din.p, h.data(), sizeof(DevTdIn)*(size_t)n, hipMemcpyHostToDevice, target->st));
-  Se3 B, C; std::memcpy(B.R, bfw, 72); std::memcpy(B.t, bfw + 9, 24); std::memcpy(C.R, cfb, 72); std::memcpy(C.t, cfb + 9, 24);
-  hipLaunchKernelGGL(k_track_search, dim3(n), dim3(64), 0, target->st, target->view(), *cam, B, C, n, (const DevTdIn*)din.p, range, subpix_its, exhaustive, dout.p);
+  hipLaunchKernelGGL(k_track_search, dim3(n), dim3(64), 0, target->st, target->view(), *cam, se3_of12(bfw), se3_of12(cfb), n, (const DevTdIn*)din.p, range, subpix_its, exhaustive, dout.p);
   ICK(hipMemcpyAsync(out, dout.p, sizeof(mcp_td_out)*(size_t)n, hipMemcpyDeviceToHost, target->st));
   ICK(hipStreamSynchronize(target->st));
   return 0;
 }
 
 // pack: arguments checked, the camera table and the points of all cameras written to the pinned staging (targets[0]->h_stab / h_bt_in), device
-// buffers sized.  launch: the two uploads (unless something else has carried them: `uploaded`) and the kernel.
+// buffers sized, the staging's way to them listed in `up`.  launch: the kernel, once something has carried the uploads.
 static int search_batch_pack(int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double* cfb, const int* n, const mcp_td_in* const* in,
-                             mcp_td_out* const* out, int* total_out, int* maxn_out, bool view = false /* mcp_track_frame's view mode: no caller arrays */) {
+                             mcp_td_out* const* out, int* total_out, int* maxn_out, Uploads* up, bool view = false /* mcp_track_frame's view mode: no caller arrays */) {
+  static_assert(sizeof(SearchCam) % 8 == 0 && sizeof(DevTdIn) % 8 == 0, "the frame's upload slice copies 8-byte words");
   *total_out = 0; *maxn_out = 0;
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !cfb || !n || !in || (!out && !view)) return img_fail("mcp_track_search_batch: bad arguments");
   int total = 0, maxn = 0;
@@ -780,30 +826,18 @@ static int search_batch_pack(int ncam, mcp_kf* const* targets, const mcp_camera*
   int first = 0;
   for (int c = 0; c < ncam; ++c) {
     SearchCam& S = tab[c];
-    S.T = targets[c]->view(); S.cam = cams[c]; std::memcpy(S.cfb.R, cfb + 12*c, 72); std::memcpy(S.cfb.t, cfb + 12*c + 9, 24); S.n = n[c]; S.first = first;
-    for (int i = 0; i < n[c]; ++i) {
-      const mcp_td_in& p = in[c][i]; DevTdIn& d = h[first + i];
-      if (!p.source_kf || p.source_level < 0 || p.source_level >= MCP_LEVELS) return img_fail("mcp_track_search_batch: point without a resident source keyframe");
-      std::memcpy(d.world_pos, p.world_pos, 24); std::memcpy(d.pixel_right_w, p.pixel_right_w, 24); std::memcpy(d.pixel_down_w, p.pixel_down_w, 24);
-      const Level& Sl = p.source_kf->lev[p.source_level];
-      d.src_img = Sl.img.p; d.src_w = Sl.w; d.src_h = Sl.h; d.center_x = p.center_x; d.center_y = p.center_y; d.fixed = p.fixed;
-    }
+    S.T = targets[c]->view(); S.cam = cams[c]; S.cfb = se3_of12(cfb + 12*c); S.n = n[c]; S.first = first;      // (no mask: this search does not read one)
+    for (int i = 0; i < n[c]; ++i) if (!td_in_dev(in[c][i], h[first + i])) return img_fail("mcp_track_search_batch: point without a resident source keyframe");
     first += n[c];
   }
   if (k0->stab.alloc(MCP_MAX_FRAME_CAMS) || k0->bt_in.alloc(total) || k0->bt_out.alloc(total)) return -1;
+  up->add(tab, k0->stab.p, sizeof(SearchCam)*(size_t)ncam);
+  up->add(h, k0->bt_in.p, sizeof(DevTdIn)*(size_t)total);
   *total_out = total; *maxn_out = maxn;
   return 0;
 }
-static int search_batch_launch(int ncam, mcp_kf* k0, int total, int maxn, const double bfw[12], int range, int subpix_its, int exhaustive, bool uploaded,
-                               mcp_td_out* host_out, mcp_pose_point* pose_pts) {
-  static_assert(sizeof(SearchCam) % 8 == 0 && sizeof(DevTdIn) % 8 == 0, "the frame's upload slice copies 8-byte words");
-  hipStream_t st = k0->st;
-  if (!uploaded) {
-    ICK(hipMemcpyAsync(k0->stab.p, k0->h_stab.p, sizeof(SearchCam)*(size_t)ncam, hipMemcpyHostToDevice, st));
-    ICK(hipMemcpyAsync(k0->bt_in.p, k0->h_bt_in.p, sizeof(DevTdIn)*(size_t)total, hipMemcpyHostToDevice, st));
-  }
-  Se3 Bw; std::memcpy(Bw.R, bfw, 72); std::memcpy(Bw.t, bfw + 9, 24);
-  hipLaunchKernelGGL(k_track_search_batch, dim3(maxn, ncam), dim3(64), 0, st, (const SearchCam*)k0->stab.p, Bw, (const DevTdIn*)k0->bt_in.p, range, subpix_its, exhaustive, k0->bt_out.p,
+static int search_batch_launch(int ncam, mcp_kf* k0, int maxn, const double bfw[12], int range, int subpix_its, int exhaustive, mcp_td_out* host_out, mcp_pose_point* pose_pts) {
+  hipLaunchKernelGGL(k_track_search_batch, dim3(maxn, ncam), dim3(64), 0, k0->st, (const SearchCam*)k0->stab.p, se3_of12(bfw), (const DevTdIn*)k0->bt_in.p, range, subpix_its, exhaustive, k0->bt_out.p,
                      host_out, pose_pts);
   ICK(hipGetLastError());
   return 0;
@@ -815,9 +849,10 @@ static int search_batch_enqueue(int ncam, mcp_kf* const* targets, const mcp_came
   int total = 0, maxn = 0;
   *total_out = 0;
   if (!bfw) return img_fail("mcp_track_search_batch: bad arguments");
-  if (search_batch_pack(ncam, targets, cams, cfb, n, in, out, &total, &maxn)) return -1;
+  Uploads up;
+  if (search_batch_pack(ncam, targets, cams, cfb, n, in, out, &total, &maxn, &up)) return -1;
   if (total == 0) return 0;
-  if (search_batch_launch(ncam, targets[0], total, maxn, bfw, range, subpix_its, exhaustive, false, nullptr, nullptr)) return -1;
+  if (up.copy(targets[0]->st) || search_batch_launch(ncam, targets[0], maxn, bfw, range, subpix_its, exhaustive, nullptr, nullptr)) return -1;
   *total_out = total;
   return 0;
 }
@@ -854,7 +889,8 @@ int mcp_track_search_batch(int ncam, mcp_kf* const* targets, const mcp_camera* c
 // mcp_track_pose_refine_m back to back on the frame's stream, the TrackerData -> pose-point packing in between done on the device, one wait at
 // the end.  Same kernels on the same data as the three calls: identical results.
 static int track_sequences_pack(int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb, const int* n,
-                                const mcp_td_in* const* in, const int* const* point_key, mcp_pf_state* const* state, int* total_out) {
+                                const mcp_td_in* const* in, const int* const* point_key, mcp_pf_state* const* state, int* total_out, Uploads* up) {
+  static_assert(sizeof(PfTargetDev) % 8 == 0 && sizeof(PfItemDev) % 8 == 0 && sizeof(mcp_pf_state) % 8 == 0, "the frame's upload slice copies 8-byte words");
   *total_out = 0;
   int total = 0;
   for (int c = 0; c < ncam; ++c) {
@@ -865,20 +901,12 @@ static int track_sequences_pack(int ncam, mcp_kf* const* targets, const mcp_came
   mcp_kf* k0 = targets[0];
   if (k0->h_pf_tab.alloc(MCP_MAX_FRAME_CAMS) || k0->h_pf_items.alloc(total) || k0->h_pf_seq.alloc(total + 2) || k0->h_pf_state.alloc(total) || k0->h_pf_state_out.alloc(total)) return -1;
   PfTargetDev* tab = k0->h_pf_tab.p; PfItemDev* h = k0->h_pf_items.p; int* seq = k0->h_pf_seq.p; mcp_pf_state* hs = k0->h_pf_state.p;
-  for (int c = 0; c < ncam; ++c) {
-    PfTargetDev& D = tab[c];
-    D.T = targets[c]->view(); D.mask0 = targets[c]->lev[0].has_mask ? targets[c]->lev[0].mask.p : nullptr; D.cam = cams[c];
-    std::memcpy(D.bfw.R, bfw, 72); std::memcpy(D.bfw.t, bfw + 9, 24);
-    std::memcpy(D.cfb.R, cfb + 12*c, 72); std::memcpy(D.cfb.t, cfb + 12*c + 9, 24);
-  }
+  for (int c = 0; c < ncam; ++c) target_of(tab[c], targets[c], cams[c], bfw, cfb + 12*c);
   int first = 0;
   for (int c = 0; c < ncam; ++c) {
     for (int i = 0; i < n[c]; ++i) {
-      const mcp_td_in& p = in[c][i]; PfItemDev& d = h[first + i];
-      if (!p.source_kf || p.source_level < 0 || p.source_level >= MCP_LEVELS) return img_fail("mcp_track_frame: point without a resident source keyframe");
-      std::memcpy(d.p.world_pos, p.world_pos, 24); std::memcpy(d.p.pixel_right_w, p.pixel_right_w, 24); std::memcpy(d.p.pixel_down_w, p.pixel_down_w, 24);
-      const Level& Sl = p.source_kf->lev[p.source_level];
-      d.p.src_img = Sl.img.p; d.p.src_w = Sl.w; d.p.src_h = Sl.h; d.p.center_x = p.center_x; d.p.center_y = p.center_y; d.p.fixed = p.fixed;
+      PfItemDev& d = h[first + i];
+      if (!td_in_dev(in[c][i], d.p)) return img_fail("mcp_track_frame: point without a resident source keyframe");
       d.point_key = point_key[c][i]; d.target = c; d.start_x = 0.0; d.start_y = 0.0;
     }
     if (n[c]) std::memcpy(&hs[first], state[c], sizeof(mcp_pf_state)*(size_t)n[c]);
@@ -888,20 +916,15 @@ static int track_sequences_pack(int ncam, mcp_kf* const* targets, const mcp_came
   seq[total + 1] = 0;                              // (padding: the ride copies 8-byte words)
   ICK(hipSetDevice(k0->device));
   if (k0->pf_tab.alloc(MCP_MAX_FRAME_CAMS) || k0->pf_items.alloc(total) || k0->pf_seq.alloc(total + 2) || k0->pf_state.alloc(total) || k0->bt_out.alloc(total)) return -1;
+  up->add(tab, k0->pf_tab.p, sizeof(PfTargetDev)*(size_t)ncam);
+  up->add(h, k0->pf_items.p, sizeof(PfItemDev)*(size_t)total);
+  up->add(seq, k0->pf_seq.p, sizeof(int)*(size_t)(total + 1));
+  up->add(hs, k0->pf_state.p, sizeof(mcp_pf_state)*(size_t)total);
   *total_out = total;
   return 0;
 }
-static int track_sequences_launch(int ncam, mcp_kf* k0, int total, int range, int subpix_its, int exhaustive, bool uploaded, mcp_td_out* host_out, mcp_pf_state* host_state,
-                                  mcp_pose_point* pose_pts) {
-  static_assert(sizeof(PfTargetDev) % 8 == 0 && sizeof(PfItemDev) % 8 == 0 && sizeof(mcp_pf_state) % 8 == 0, "the frame's upload slice copies 8-byte words");
-  hipStream_t st = k0->st;
-  if (!uploaded) {
-    ICK(hipMemcpyAsync(k0->pf_tab.p, k0->h_pf_tab.p, sizeof(PfTargetDev)*(size_t)ncam, hipMemcpyHostToDevice, st));
-    ICK(hipMemcpyAsync(k0->pf_items.p, k0->h_pf_items.p, sizeof(PfItemDev)*(size_t)total, hipMemcpyHostToDevice, st));
-    ICK(hipMemcpyAsync(k0->pf_seq.p, k0->h_pf_seq.p, sizeof(int)*(size_t)(total + 1), hipMemcpyHostToDevice, st));
-    ICK(hipMemcpyAsync(k0->pf_state.p, k0->h_pf_state.p, sizeof(mcp_pf_state)*(size_t)total, hipMemcpyHostToDevice, st));
-  }
-  hipLaunchKernelGGL(k_patch_sequences, dim3(total), dim3(64), 0, st, (int)MCP_PF_TRACK, (const PfTargetDev*)k0->pf_tab.p, total, (const int*)k0->pf_seq.p,
+static int track_sequences_launch(mcp_kf* k0, int total, int range, int subpix_its, int exhaustive, mcp_td_out* host_out, mcp_pf_state* host_state, mcp_pose_point* pose_pts) {
+  hipLaunchKernelGGL(k_patch_sequences, dim3(total), dim3(64), 0, k0->st, (int)MCP_PF_TRACK, (const PfTargetDev*)k0->pf_tab.p, total, (const int*)k0->pf_seq.p,
                      (const PfItemDev*)k0->pf_items.p, k0->pf_state.p, range, subpix_its, exhaustive, k0->bt_out.p, host_out, host_state, pose_pts);
   ICK(hipGetLastError());
   return 0;
@@ -920,88 +943,58 @@ int mcp_track_frame(int ncam, mcp_kf* const* targets, const uint8_t* const* imgs
   // every per-point argument is checked BEFORE the first enqueue: an input rejected later would leave launches and copies in flight
   for (int c = 0; c < ncam; ++c) {
     if (targets[c]->device != targets[0]->device || (n[c] > 0 && (!in[c] || (state && (!state[c] || !point_key[c]))))) return img_fail("mcp_track_frame: bad arguments");
-    for (int i = 0; i < n[c]; ++i) if (!in[c][i].source_kf || in[c][i].source_level < 0 || in[c][i].source_level >= MCP_LEVELS) return img_fail("mcp_track_frame: point without a resident source keyframe");
+    for (int i = 0; i < n[c]; ++i) if (!td_in_resident(in[c][i])) return img_fail("mcp_track_frame: point without a resident source keyframe");
   }
   mcp_kf* k0 = targets[0];
   hipStream_t st = k0->st;
   // ... and whatever fails after it waits for the stream before the stack variables the copies write to (back, prm_err) go away
+  // (the map table's Drain does the same for calls that own a table; this one has only the frame's stream)
   struct DrainOnError { hipStream_t st; bool armed; int ncam; mcp_kf* const* targets; bool lite; ~DrainOnError() { if (armed) { (void)hipStreamSynchronize(st); if (lite) (void)lite_batch_finish(ncam, targets); (void)hipGetLastError(); } } };
   DrainOnError drain{st, true, ncam, targets, imgs != nullptr};
+  // the search: stateless (mcp_track_search_batch's) or, with finder states, one single-item sequence per point.  Its tables and points are
+  // packed on the host while the pyramids run and ride to the device in their next launch; without images they are copied on the stream
   int total = 0, maxn = 0;
-  bool rode = false;              // the search's inputs went to the device inside k_row_count's launch
-  // the search's tables and points are packed on the host while the pyramids run, and ride to the device in the next launch
-  struct Ctx { int ncam; mcp_kf* const* targets; const mcp_camera* cams; const double* bfw; const double* cfb; const int* n; const mcp_td_in* const* in; const int* const* point_key;
-               mcp_pf_state* const* state; mcp_td_out* const* out; int* total; int* maxn; };
-  Ctx ctx{ncam, targets, cams, bfw, cfb, n, in, point_key, state, out, &total, &maxn};
-  auto words = [](size_t bytes) { return (int)((bytes + 7)/8); };
+  Uploads up;
+  auto pack = [&]() -> int {
+    return state ? track_sequences_pack(ncam, targets, cams, bfw, cfb, n, in, point_key, state, &total, &up)
+                 : search_batch_pack(ncam, targets, cams, cfb, n, in, out, &total, &maxn, &up, view);
+  };
   if (imgs) {
-    FrameRide ride{nullptr, &ctx};
-    if (!state) ride.fn = [](void* c_, FrameBatch& B) -> int {
-      Ctx& c = *static_cast<Ctx*>(c_);
-      if (search_batch_pack(c.ncam, c.targets, c.cams, c.cfb, c.n, c.in, c.out, c.total, c.maxn, c.out == nullptr)) return -1;
-      if (*c.total == 0) return 0;
-      mcp_kf* k0 = c.targets[0];
-      B.up_src[0] = reinterpret_cast<const unsigned long long*>(k0->h_stab.p); B.up_dst[0] = reinterpret_cast<unsigned long long*>(k0->stab.p); B.up_n8[0] = (int)(sizeof(SearchCam)*(size_t)c.ncam/8);
-      B.up_src[1] = reinterpret_cast<const unsigned long long*>(k0->h_bt_in.p); B.up_dst[1] = reinterpret_cast<unsigned long long*>(k0->bt_in.p); B.up_n8[1] = (int)(sizeof(DevTdIn)*(size_t)*c.total/8);
-      return 0; };
-    else ride.fn = [](void* c_, FrameBatch& B) -> int {
-      Ctx& c = *static_cast<Ctx*>(c_);
-      if (track_sequences_pack(c.ncam, c.targets, c.cams, c.bfw, c.cfb, c.n, c.in, c.point_key, c.state, c.total)) return -1;
-      if (*c.total == 0) return 0;
-      mcp_kf* k0 = c.targets[0]; const size_t t = (size_t)*c.total;
-      const void* src[4] = { k0->h_pf_tab.p, k0->h_pf_items.p, k0->h_pf_seq.p, k0->h_pf_state.p };
-      void* dst[4] = { k0->pf_tab.p, k0->pf_items.p, k0->pf_seq.p, k0->pf_state.p };
-      const size_t bytes[4] = { sizeof(PfTargetDev)*(size_t)c.ncam, sizeof(PfItemDev)*t, sizeof(int)*(t + 1), sizeof(mcp_pf_state)*t };
-      for (int r = 0; r < 4; ++r) { B.up_src[r] = static_cast<const unsigned long long*>(src[r]); B.up_dst[r] = static_cast<unsigned long long*>(dst[r]); B.up_n8[r] = (int)((bytes[r] + 7)/8); }
-      return 0; };
+    const FrameRide ride = [&](FrameBatch& B) -> int { if (pack()) return -1; up.ride(B); return 0; };
     if (lite_batch_enqueue(ncam, targets, imgs, strides, imgs_on_device, masks, &ride)) return -1;
-    rode = true;
   }
-  (void)words;
   ICK(hipSetDevice(k0->device));
   RefineScratch& rs = refine_scratch();
-  bool out_pinned = false;        // the search kernel wrote the TrackerData results (and the finder states) to pinned host memory as well
-  if (state) {
-    if (!rode && track_sequences_pack(ncam, targets, cams, bfw, cfb, n, in, point_key, state, &total)) return -1;
-    if (total > 0) {
-      if (k0->h_bt_out.alloc(total) || rs.dp.alloc(total)) return -1;
-      if (track_sequences_launch(ncam, k0, total, range, subpix_its, exhaustive, rode, k0->h_bt_out.p, k0->h_pf_state_out.p, rs.dp.p)) return -1;
-      out_pinned = true;
-    }
-  } else {
-    if (!rode && search_batch_pack(ncam, targets, cams, cfb, n, in, out, &total, &maxn, view)) return -1;
-    if (total > 0) {
-      // the search leaves its results in pinned host memory too and writes the pose iterations' records itself (no packing launch)
-      if (k0->h_bt_out.alloc(total) || rs.dp.alloc(total)) return -1;
-      if (search_batch_launch(ncam, k0, total, maxn, bfw, range, subpix_its, exhaustive, rode, k0->h_bt_out.p, rs.dp.p)) return -1;
-      out_pinned = true;
-    }
+  if (!imgs && pack()) return -1;
+  if (total > 0) {
+    // the search leaves its results (and the finders' states) in pinned host memory too and writes the pose iterations' records itself
+    if (k0->h_bt_out.alloc(total) || rs.dp.alloc(total)) return -1;
+    if (!imgs && up.copy(st)) return -1;
+    if (state ? track_sequences_launch(k0, total, range, subpix_its, exhaustive, k0->h_bt_out.p, k0->h_pf_state_out.p, rs.dp.p)
+              : search_batch_launch(ncam, k0, maxn, bfw, range, subpix_its, exhaustive, k0->h_bt_out.p, rs.dp.p)) return -1;
   }
   unsigned int prm_err = 0;
   double back[18];
   const bool iterate = total > 0 && n_iter > 0;
-  if (total > 0) {
-    if (iterate && refine_enqueue(total, nullptr, ncam, cams, cfb, bfw, n_iter, nonlinear, override_sigma, est, st, &prm_err)) return -1;
-    if (!out_pinned && search_batch_copy_out(ncam, k0, n, out, total)) return -1;
-    if (pts_out) ICK(hipMemcpyAsync(pts_out, rs.dp.p, sizeof(mcp_pose_point)*(size_t)total, hipMemcpyDeviceToHost, st));
-    if (iterate) { if (refine_results_enqueue(rs, total, back, weights_last, st)) return -1; }
-    else if (weights_last) std::memset(weights_last, 0, 8*(size_t)total);
-  }
-  ICK(hipStreamSynchronize(st));
-  drain.armed = false;
-  if (imgs && lite_batch_finish(ncam, targets)) return -1;
-  { int first = 0; for (int c = 0; c < ncam; ++c) { k0->view_first[c] = first; first += n[c]; } k0->view_first[ncam] = first; k0->view_ncam = (out_pinned || total == 0) ? ncam : 0; }
-  if (out_pinned && !view) { int first = 0; for (int c = 0; c < ncam; ++c) { if (n[c]) std::memcpy(out[c], k0->h_bt_out.p + first, sizeof(mcp_td_out)*(size_t)n[c]); first += n[c]; } }
-  if (view && !out_pinned && total > 0) return img_fail("mcp_track_frame: results were not written to the pinned block (view mode needs a search of at least one point)");
-  if (iterate) refine_results_finish(rs, total, back, weights_last);
-  if (state && total > 0) { int first = 0; for (int c = 0; c < ncam; ++c) { if (n[c]) std::memcpy(state[c], k0->h_pf_state_out.p + first, sizeof(mcp_pf_state)*(size_t)n[c]); first += n[c]; } }
-  if (iterate && (prm_err || (rs.last_multi && getenv("MCP_TRACK_TEST_PRM_GIVEUP")))) {
-    // a workgroup of the multi-workgroup iterations gave up waiting for the others: the frame is not lost, one workgroup redoes them
-    if (refine_redo_single(total, n_iter, ncam, est, st)) return -1;
-    if (pts_out) ICK(hipMemcpyAsync(pts_out, rs.dp.p, sizeof(mcp_pose_point)*(size_t)total, hipMemcpyDeviceToHost, st));
-    if (refine_results_enqueue(rs, total, back, weights_last, st)) return -1;
+  if (iterate) {
+    if (refine_enqueue(total, nullptr, ncam, cams, cfb, bfw, n_iter, nonlinear, override_sigma, est, st, &prm_err) ||
+        refine_collect(total, n_iter, ncam, est, st, &prm_err, pts_out, back, weights_last)) return -1;
+  } else {
+    if (total > 0 && pts_out) ICK(hipMemcpyAsync(pts_out, rs.dp.p, sizeof(mcp_pose_point)*(size_t)total, hipMemcpyDeviceToHost, st));
+    if (total > 0 && weights_last) std::memset(weights_last, 0, 8*(size_t)total);
     ICK(hipStreamSynchronize(st));
   }
+  drain.armed = false;
+  if (imgs && lite_batch_finish(ncam, targets)) return -1;
+  // camera c's results start at view_first[c] of the pinned block (mcp_track_frame_view); copied out for a caller that brought arrays
+  int first = 0;
+  for (int c = 0; c < ncam; ++c) {
+    k0->view_first[c] = first;
+    if (n[c] && !view) std::memcpy(out[c], k0->h_bt_out.p + first, sizeof(mcp_td_out)*(size_t)n[c]);
+    if (n[c] && state) std::memcpy(state[c], k0->h_pf_state_out.p + first, sizeof(mcp_pf_state)*(size_t)n[c]);
+    first += n[c];
+  }
+  k0->view_first[ncam] = first; k0->view_ncam = ncam;
   if (iterate) { std::memcpy(bfw, back, 96); std::memcpy(mu_last, back + 12, 48); }
   return 0;
 }
@@ -1029,19 +1022,13 @@ int mcp_patch_sequences(int mode, int n_targets, const mcp_pf_target* targets, i
   for (int t = 0; t < n_targets; ++t) {
     const mcp_pf_target& G = targets[t];
     if (!G.kf || !cam_ok(G.cam) || G.kf->device != k0->device) return img_fail("mcp_patch_sequences: bad target");
-    PfTargetDev& D = tab[t];
-    D.T = G.kf->view(); D.mask0 = G.kf->lev[0].has_mask ? G.kf->lev[0].mask.p : nullptr; D.cam = *G.cam;
-    std::memcpy(D.bfw.R, G.base_from_world, 72); std::memcpy(D.bfw.t, G.base_from_world + 9, 24);
-    std::memcpy(D.cfb.R, G.cam_from_base, 72); std::memcpy(D.cfb.t, G.cam_from_base + 9, 24);
+    target_of(tab[t], G.kf, *G.cam, G.base_from_world, G.cam_from_base);
   }
   std::vector<PfItemDev> h(std::max(total, 1));
   for (int i = 0; i < total; ++i) {
-    const mcp_pf_item& I = items[i]; const mcp_td_in& p = I.point; PfItemDev& d = h[i];
+    const mcp_pf_item& I = items[i]; PfItemDev& d = h[i];
     if (I.target < 0 || I.target >= n_targets) return img_fail("mcp_patch_sequences: item with a bad target index");
-    if (!p.source_kf || p.source_level < 0 || p.source_level >= MCP_LEVELS) return img_fail("mcp_patch_sequences: point without a resident source keyframe");
-    std::memcpy(d.p.world_pos, p.world_pos, 24); std::memcpy(d.p.pixel_right_w, p.pixel_right_w, 24); std::memcpy(d.p.pixel_down_w, p.pixel_down_w, 24);
-    const Level& Sl = p.source_kf->lev[p.source_level];
-    d.p.src_img = Sl.img.p; d.p.src_w = Sl.w; d.p.src_h = Sl.h; d.p.center_x = p.center_x; d.p.center_y = p.center_y; d.p.fixed = p.fixed;
+    if (!td_in_dev(I.point, d.p)) return img_fail("mcp_patch_sequences: point without a resident source keyframe");
     d.point_key = I.point_key; d.target = I.target; d.start_x = I.start_pos[0]; d.start_y = I.start_pos[1];
   }
   ICK(hipSetDevice(k0->device));
@@ -1107,7 +1094,6 @@ int mcp_track_pose_update_m(int n, const uint8_t* found, const double* fpos, con
 }  // extern "C"
 
 // ---- Tracker::FindPVS over a device-resident map-point table (include/mcp_img.h, pvs_kernels.h) ------------------------------------
-static Se3 se3_of12(const double* a) { Se3 T; std::memcpy(T.R, a, 72); std::memcpy(T.t, a + 9, 24); return T; }
 static size_t tm_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // one column of the table: bytes per row, how a row that appears is filled, whether the column exists yet (the rays and the finders are
@@ -1443,8 +1429,7 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
     PvsCam& C = tab[c];
     std::memset(&C, 0, sizeof(PvsCam));              // (the table is compared byte-wise with the last one uploaded)
     C.cam = cams[c]; C.cfb = se3_of12(cfb + 12*c);
-    const Level& L0 = targets[c]->lev[0];
-    C.mask0 = L0.has_mask ? L0.mask.p : nullptr; C.mask_w = L0.w; C.mask_h = L0.h;
+    C.mask0 = mask0_of(targets[c]); C.mask_w = targets[c]->lev[0].w; C.mask_h = targets[c]->lev[0].h;
     C.cap = Y.cap[c]; C.out_first = Y.first[c];
   }
   // the cameras, their CamFromBase, masks and caps rarely change from frame to frame: their table is uploaded only when they do
@@ -1560,18 +1545,11 @@ int mcp_map_points_get_states(const mcp_map_points* m, int cam, int first, int c
   return column_get(m, "mcp_map_points_get_states", m && ok ? &m->states[cam] : nullptr, first, count, out);
 }
 
-// the register-resident pose kernel's dynamic LDS, once per device and thread (as refine_enqueue)
+// mcp_track_map may use the register-resident pose kernel (MCP_TRACK_REFINE_REGS is read at every call here)
 static bool tm_regs_ok() {
-  static thread_local unsigned long long set_mask = 0, ok_mask = 0;
   int dev = 0; (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(set_mask & bit)) {
-    set_mask |= bit;
-    if (hipFuncSetAttribute((const void*)k_pose_refine_regs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRR_DYN_LDS) == hipSuccess) ok_mask |= bit;
-    else (void)hipGetLastError();
-  }
   const char* e = getenv("MCP_TRACK_REFINE_REGS");
-  return (ok_mask & bit) && (e ? atoi(e) != 0 : true);
+  return pose_regs_attr(dev) && (e ? atoi(e) != 0 : true);
 }
 
 // the body of mcp_track_map (rp == NULL: exactly its launches) and of mcp_track_map_record (rp, rec checked by the caller)
@@ -1628,8 +1606,7 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   std::memset(hb, 0, blk);
   TmCam* tab = reinterpret_cast<TmCam*>(hb + o_tab);
   for (int c = 0; c < ncam; ++c) {
-    tab[c].T = targets[c]->view(); tab[c].mask0 = targets[c]->lev[0].has_mask ? targets[c]->lev[0].mask.p : nullptr; tab[c].cam = cams[c];
-    tab[c].cfb = se3_of12(cfb + 12*c);
+    target_of(tab[c], targets[c], cams[c]); tab[c].cfb = se3_of12(cfb + 12*c);
   }
   std::memcpy(hb + o_cam, cams, sizeof(mcp_camera)*(size_t)ncam);
   std::memcpy(hb + o_cfb, cfb, 96*(size_t)ncam);
@@ -1812,8 +1789,7 @@ static int stereo_target_dev(const char* what, const mcp_kf* src, const mcp_ster
   if (G.kf->device != src->device) return img_fail(std::string(what) + ": a target lives on another device than the source");
   if (!cam_ok(G.cam) || !finite12(G.cam_from_world)) return img_fail(std::string(what) + ": bad target camera or pose");
   if (!(G.one_pixel_angle > 0) || !std::isfinite(G.one_pixel_angle)) return img_fail(std::string(what) + ": one_pixel_angle must be positive and finite");
-  D.T = G.kf->view(); D.mask0 = G.kf->lev[0].has_mask ? G.kf->lev[0].mask.p : nullptr; D.cam = *G.cam;
-  D.cfw = se3_of12(G.cam_from_world); D.opa = G.one_pixel_angle;
+  target_of(D, G.kf, *G.cam); D.cfw = se3_of12(G.cam_from_world); D.opa = G.one_pixel_angle;
   return 0;
 }
 

@@ -1089,3 +1089,62 @@ def test_pose_iterations_survive_a_workgroup_that_gives_up(gpu_required, monkeyp
     assert np.allclose(pr[0], pg[0], rtol=0, atol=1e-11) and np.allclose(pr[1], pg[1], rtol=0, atol=1e-11) and np.allclose(mr, mg, rtol=0, atol=1e-11)
     assert np.array_equal(wr == 0, wg == 0) and np.allclose(wr, wg, rtol=0, atol=1e-9)
     assert np.allclose(orr["image"], og["image"], rtol=0, atol=1e-9)
+
+
+def test_a_point_without_a_resident_source_is_refused_by_the_entry_s_own_name(gpu_required, scene):
+    """mcp_track_search, mcp_track_search_batch, mcp_track_frame (stateless and with finder states) and mcp_patch_sequences check every
+    point on the host before anything is enqueued: a NULL source_kf or a source_level outside the pyramid is refused with the entry's own
+    name in front of ": point without a resident source keyframe", and the same call with valid points succeeds straight afterwards
+    (nothing was left in flight; mcp_track_frame has not rotated the targets' history either)."""
+    from mcptam_amd import keyframe as kf
+    cam = scene["cam"]
+    gA, oA = _pair(640, 480)
+    gA.MakeKeyFrame_Lite(scene["imgA"]); oA.MakeKeyFrame_Lite(scene["imgA"])
+    pts = _points(scene, gA, oA)[:60]
+    handle = lambda k: None if k is None else k._h
+    good = kf.pack_points(pts, handle)
+    bad_lists = [pts[:17] + [dict(pts[17], source_kf=None)] + pts[18:],
+                 pts[:17] + [dict(pts[17], source_level=4)] + pts[18:],
+                 pts[:17] + [dict(pts[17], source_level=-1)] + pts[18:]]
+    tg = [kf.KeyFrame(640, 480) for _ in range(2)]
+    kf.make_lite_batch(tg, [scene["imgB"]]*2)
+    I = (np.eye(3), np.zeros(3))
+    cfbs = [I, (np.eye(3), np.array([0.01, 0.0, 0.0]))]
+    cfb_arr = np.ascontiguousarray(np.stack([kf._pose12(*c) for c in cfbs]))
+    pose = scene["poseB"]
+
+    def search(plist):
+        return [kf.track_search(tg[0], cam, pose, I, kf.pack_points(plist, handle), 10, 8)]
+
+    def search_batch(plist):
+        return kf.track_search_batch(tg, [cam]*2, pose, cfb_arr, [good, kf.pack_points(plist, handle)], 10, 8)
+
+    def frame(stateful):
+        def run(plist):
+            prev = tg[0].NumPrev()
+            try:
+                tf = kf.TrackFrame(tg, [cam]*2, cfb_arr, [good, kf.pack_points(plist, handle)], stateful=stateful)
+                return [o_.copy() for o_ in tf.run([scene["imgB"]]*2, pose, 10, 8)[0]]      # (the results live in tf's pinned block)
+            except RuntimeError:
+                assert tg[0].NumPrev() == prev           # refused before the pyramids' launch
+                raise
+        return run
+
+    def sequences(plist):
+        seqs = [[dict(point=p, point_key=i, target=i % 2)] for i, p in enumerate(plist)]
+        keep, ntar, tab, seq_start, items, nflat = kf.marshal_patch_sequences([(tg[0], cam, pose, cfbs[0]), (tg[1], cam, pose, cfbs[1])], seqs, handle, handle)
+        states = kf.new_pf_states(nflat)
+        out = np.zeros(nflat, dtype=kf.TD_OUT_DTYPE)
+        kf._chk(kf.lib().mcp_patch_sequences(kf.PF_TRACK, ntar, tab, nflat, seq_start.ctypes.data, items, states.ctypes.data, 10, 8, 0, out.ctypes.data), "patch_sequences")
+        del keep
+        return [out]
+
+    entries = [("mcp_track_search", search), ("mcp_track_search_batch", search_batch), ("mcp_track_frame", frame(False)), ("mcp_track_frame", frame(True)),
+               ("mcp_patch_sequences", sequences)]
+    for name, call in entries:
+        for bad in bad_lists:
+            with pytest.raises(RuntimeError):
+                call(bad)
+            assert kf._cb.last_error() == name + ": point without a resident source keyframe", (name, kf._cb.last_error())
+            outs = call(pts)
+            assert sum(int(o_["found"].sum()) for o_ in outs) > 20, name
