@@ -399,3 +399,4 @@ def test_sets_longer_than_one_sort_go_in_chunks(gpu_required, world, monkeypatch
     _assert_same(got, ref, 1)
     counts = list(got[2].pvs_counts[0])
     assert min(counts) > 2048 and got[2].set_sizes[0][1] > 2048, counts
+    assert sum(ref["sizes"][0]) > 16384, ref["sizes"]              # k_tm_search's grid of 16 384 wavefronts strides once over the items
