@@ -609,6 +609,62 @@ int mcp_track_map_record(mcp_map_points*, int ncam, mcp_kf* const* targets, cons
 const mcp_track_note* mcp_track_map_notes_view(const mcp_map_points*, int cam, int* count);
 const mcp_track_meas* mcp_track_map_meas_view(const mcp_map_points*, int cam, int* count);
 
+/* ---- Tracker::TrackFrame's tracking branch in ONE submission ------------------------------------ src/Tracker.cc:319-330, 431-434, 1516-1555, 1687-1749
+ * mcp_track_map_record with the pose it starts from made on the device: TrackFrameSetup's SmallBlurryImages (blur 0.75), CalcSBIRotation,
+ * ApplyMotionModel, then TrackMap with its bookkeeping, then UpdateMotionModel -- one submission, one wait.
+ * THE TRACKER'S SBIs live in the table, a `this` and a `last` one per camera index 0 .. MCP_MAX_FRAME_CAMS-1 (pass the cameras in the same
+ * order every frame, as for the finders).  They are not the keyframe handles' SBIs (mcp_kf_make_sbi: KeyFrame::mpSBI, the relocaliser's) and
+ * survive a change of target handles (AddNewKeyFrame).  Every call makes `this` from level 0 of the target -- after the pyramids when imgs is
+ * given, as held when imgs == NULL -- the previous `this` becoming `last`; the first frame of a camera index after creation or
+ * mcp_track_motion_reset (Tracker::Reset) makes `last` equal to `this` (:319-324) and reports first_frame[c] = 1: its alignment is the identity
+ * (se2 = identity, score 0), its rotation exactly zero, and it counts as used.
+ * USED CAMERAS: apply != 0 && use_rotation_estimator != 0 && cam_good[c] != 0.  A used camera's SBI is aligned against its `last` for
+ * sbi_iterations rounds (mcp_sbi_iterate's bits), turned into a rotation with cams_sbi[c] (SE3fromSE2; the 40x30 camera, mmCameraModelsSBI),
+ * its logarithm carried into the base frame by cam_from_base[c].R^-1.  The used cameras' rotations are averaged in camera order
+ * (FindAverageRotation, eps 1e-3).  DEVIATION: the reference's averaging loop has no bound; here it ends after 32 evaluations of the mean
+ * residual at the latest, avg_rounds reports how many ran.
+ * PRIOR: v6 = velocity * dt, its rotation part replaced by the average when n_used > 0; prior = SE3::exp(v6) * base_from_world as given
+ * (`start`).  apply == 0 (the frame after AttemptRecovery, :496-500): the SBIs are made and rolled, prior = start bit for bit, v_new zeros and
+ * velocity returned as given.
+ * EVERYTHING ELSE is mcp_track_map_record's, word for word, started from `prior`: base_from_world returns refined, res / rec / the views / the
+ * finders / the count column as there.
+ * VELOCITY: v_new = SE3::ln(refined * start^-1) / dt, velocity = 0.9 (0.5 v_new + 0.5 velocity_in) (UpdateMotionModel; TooN order [t; w]).
+ * mdMSDScaledVelocityMagnitude stays with the caller (it needs mdTotalDepthMean).
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, no SBI rolled, outputs untouched): mcp_track_map_record's; NULL motion structs; NULL
+ * cams_sbi or a bad camera in it; blur <= 0; sbi_iterations < 0; a non-finite velocity; imgs == NULL with a target that holds no frame; and
+ * -- DEVIATION, the reference would divide by it -- apply != 0 with dt not finite or <= 0. */
+typedef struct mcp_track_motion_params {
+  int apply;                    /* 0: a frame after AttemptRecovery -- SBIs made and rolled, prior = base_from_world as given, velocity returned as given */
+  int use_rotation_estimator;   /* Tracker::sbUseRotationEstimator */
+  int sbi_iterations;           /* 6 */
+  double blur;                  /* Tracker::sdRotationEstimatorBlur, 0.75 */
+  double dt;                    /* mLastProcessDur.toSec() */
+  double velocity[6];           /* mv6BaseVelocity before the frame, TooN order [t; w] */
+  uint8_t cam_good[MCP_MAX_FRAME_CAMS];   /* mmTrackingQuality[cam] == GOOD after the previous frame */
+} mcp_track_motion_params;
+typedef struct mcp_track_motion {
+  double start[12], prior[12];            /* mse3StartPose; the pose TrackMap started from: the bits the PVS kernel read */
+  double se2[MCP_MAX_FRAME_CAMS][6], sbi_score[MCP_MAX_FRAME_CAMS];   /* as mcp_sbi_iterate; zeros for a camera not aligned */
+  double cam_rot[MCP_MAX_FRAME_CAMS][3];  /* axis-angle in the base frame, per used camera */
+  double sbi_rot[3]; int n_used, avg_rounds, first_frame[MCP_MAX_FRAME_CAMS];
+  double v_new[6], velocity[6];           /* UpdateMotionModel: the new mv6BaseVelocity */
+} mcp_track_motion;
+int mcp_track_frame_motion(mcp_map_points*, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                           const uint8_t* const* const* masks, const mcp_camera* cams, const mcp_camera* cams_sbi, double base_from_world[12],
+                           const double* cam_from_base, const mcp_track_map_params*, mcp_track_map_result*, const mcp_track_record_params*,
+                           mcp_track_record*, const mcp_track_motion_params*, mcp_track_motion*);
+/* Tracker::Reset (:163-164): every camera index forgets its SBIs */
+int mcp_track_motion_reset(mcp_map_points*);
+/* camera index cam's SBI, which = 0 this, 1 last, in mcp_kf_get_sbi's layouts (NULL: not wanted); waits for the table's stream; -1 when that
+ * camera index has none */
+int mcp_track_motion_get_sbi(const mcp_map_points*, int cam, int which, uint8_t* small_img, float* templ, float* jacs);
+/* host restatements of the two motion kernels (same source, host compiler); need no device.  _prior_host takes the alignments (se2 is read
+ * for used cameras only) and fills start, prior, se2 (zeros for a camera not used), cam_rot, sbi_rot, n_used and avg_rounds of *out;
+ * _update_host fills v_new and velocity.  Refusals as above where they apply, *out untouched. */
+int mcp_track_motion_prior_host(int ncam, const double* se2 /*ncam x 6*/, const mcp_camera* cams_sbi, const double* cam_from_base, const double start[12],
+                                const mcp_track_motion_params*, mcp_track_motion* out);
+int mcp_track_motion_update_host(const double start[12], const double refined[12], const mcp_track_motion_params*, mcp_track_motion* out);
+
 /* ---- MapMakerServerBase::ReFind_Common over the table in ONE submission ---------------------------- src/MapMakerServerBase.cc:921-1080
  * ReFindInSingleKeyFrame (every point of the map against a new keyframe), ReFindNewlyMade (every new point against every keyframe) and
  * ReFindFromFailureQueue all run ReFind_Common per (keyframe, point) pair.  The caller keeps the early-outs that read its own sets (:925-937:

@@ -340,6 +340,28 @@ class MapPointTable {
                                nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord));
     if (pResult) *pResult = r;
   }
+  /// Tracker::TrackFrame's tracking branch (src/Tracker.cc:431-434) in one call: ApplyMotionModel with the SBI rotation estimate, TrackMap with
+  /// its bookkeeping, UpdateMotionModel (mcp_track_frame_motion).  base_from_world: last frame's pose in, the refined pose out; vCamsSBI: the
+  /// 40x30 cameras (mmCameraModelsSBI).  Notes(), Measurements() and the item / PVS views are TrackMapRecord's.
+  void TrackFrameMotion(const std::vector<KeyFrame*>& vTargets, const std::vector<const uint8_t*>& vImages, const std::vector<int>& vStrides, bool bImagesOnDevice,
+                        const std::vector<mcp_camera>& vCams, const std::vector<mcp_camera>& vCamsSBI, double base_from_world[12], const std::vector<double>& vCamFromBase,
+                        const mcp_track_map_params& params, const mcp_track_record_params& recParams, const mcp_track_motion_params& motionParams,
+                        mcp_track_map_result* pResult, mcp_track_record* pRecord, mcp_track_motion* pMotion) {
+    const int nc = (int)vTargets.size();
+    if ((int)vCams.size() != nc || (int)vCamsSBI.size() != nc || (int)vCamFromBase.size() != 12*nc ||
+        (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !pRecord || !pMotion)
+      throw std::invalid_argument("MapPointTable::TrackFrameMotion: array sizes");
+    std::vector<mcp_kf*> h(nc);
+    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    mcp_track_map_result r;
+    check(mcp_track_frame_motion(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
+                                 nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord, &motionParams, pMotion));
+    if (pResult) *pResult = r;
+  }
+  /// Tracker::Reset: every camera index forgets its SmallBlurryImages
+  void MotionReset() { check(mcp_track_motion_reset(mpDev)); }
+  /// the tracker's SBI of camera index nCam (nWhich 0: this frame's, 1: last frame's): 1200 bytes, 1200 floats, 2400 floats; nullptr: not wanted
+  void MotionSBI(int nCam, int nWhich, uint8_t* pSmall, float* pTemplate, float* pJacs) const { check(mcp_track_motion_get_sbi(mpDev, nCam, nWhich, pSmall, pTemplate, pJacs)); }
   /// nullptr with *pnCount == 0: the camera's list is empty -- or the last track / PVS call was no TrackMapRecord with that camera (mcp_last_error())
   const mcp_track_note* Notes(int nCam, int* pnCount) const { return mcp_track_map_notes_view(mpDev, nCam, pnCount); }
   const mcp_track_meas* Measurements(int nCam, int* pnCount) const { return mcp_track_map_meas_view(mpDev, nCam, pnCount); }

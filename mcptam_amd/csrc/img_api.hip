@@ -23,6 +23,7 @@
 #include "write_back_kernels.h"
 #include "refind_kernels.h"
 #include "track_record_kernels.h"
+#include "track_motion_kernels.h"
 #include "ba_bridge.h"
 #include "ba_select.h"
 
@@ -668,6 +669,18 @@ static void sbi_resize_coeffs(int src, int dst, int* idx, short* w0, short* w1) 
     w0[d] = (short)lrintf((1.f - f)*2048.f); w1[d] = (short)lrintf(f*2048.f);
   }
 }
+// the tables of one SmallBlurryImage: resize taps for a w x h source and
+// CVD::convolveGaussian's taps [3P-memory]: half size ceil(3 sigma), exp(-i^2/2 sigma^2), unit sum
+static void sbi_tables(int w, int h, double blur, SbiTables& tb) {
+  std::memset(&tb, 0, sizeof tb);
+  sbi_resize_coeffs(w, SBI_W, tb.xi, tb.xa, tb.xb);
+  sbi_resize_coeffs(h, SBI_H, tb.yi, tb.ya, tb.yb);
+  tb.ks = std::min(31, (int)std::ceil(3.0*blur));
+  double sum = 1.0;
+  for (int i = 1; i <= tb.ks; ++i) sum += 2.0*std::exp(-(double)i*i/(2.0*blur*blur));
+  tb.k[0] = (float)(1.0/sum);
+  for (int i = 1; i < 32; ++i) tb.k[i] = (i <= tb.ks) ? (float)(std::exp(-(double)i*i/(2.0*blur*blur))/sum) : 0.f;
+}
 int mcp_kf_make_sbi(mcp_kf* k, double blur) {
   if (!k->has_image) return img_fail("mcp_kf_make_sbi: the handle holds no frame");
   if (!(blur > 0)) return img_fail("mcp_kf_make_sbi: blur must be positive");
@@ -679,14 +692,7 @@ int mcp_kf_make_sbi(mcp_kf* k, double blur) {
   if (k->sbi_small.alloc(SBI_N) || k->sbi_templ.alloc(SBI_N) || k->sbi_jacs.alloc(2*SBI_N)) return -1;
   SbiTables tb;
   const Level& L = k->lev[0];
-  sbi_resize_coeffs(L.w, SBI_W, tb.xi, tb.xa, tb.xb);
-  sbi_resize_coeffs(L.h, SBI_H, tb.yi, tb.ya, tb.yb);
-  // CVD::convolveGaussian taps [3P-memory]: half size ceil(3 sigma), exp(-i^2/2 sigma^2), unit sum
-  tb.ks = std::min(31, (int)std::ceil(3.0*blur));
-  double sum = 1.0;
-  for (int i = 1; i <= tb.ks; ++i) sum += 2.0*std::exp(-(double)i*i/(2.0*blur*blur));
-  tb.k[0] = (float)(1.0/sum);
-  for (int i = 1; i < 32; ++i) tb.k[i] = (i <= tb.ks) ? (float)(std::exp(-(double)i*i/(2.0*blur*blur))/sum) : 0.f;
+  sbi_tables(L.w, L.h, blur, tb);
   hipLaunchKernelGGL(k_sbi_make, dim3(1), dim3(256), 0, k->st, (const uint8_t*)L.img.p, L.w, L.h, tb, k->sbi_small.p, k->sbi_templ.p, k->sbi_jacs.p);
   ICK(hipStreamSynchronize(k->st));
   k->has_sbi = true;
@@ -739,54 +745,11 @@ int mcp_sbi_iterate_last(mcp_kf* k, int iterations, double se2[6], double* score
   std::memcpy(se2, o, 6*sizeof(double)); *score = o[6];
   return 0;
 }
-// SmallBlurryImage::SE3fromSE2 (:250-310): two points, three Gauss-Newton steps on SO3 -- control-plane arithmetic, run on the
-// host with the same camera functions the kernels use (ba_device.h is __host__ __device__)
+// SmallBlurryImage::SE3fromSE2 (:250-310): two points, three Gauss-Newton steps on SO3 -- here on the host, from the source
+// k_motion_prior runs on the device (track_motion.h, __host__ __device__ like the camera functions of ba_device.h)
 int mcp_sbi_se3_from_se2(const double se2[6], const mcp_camera* cs, const mcp_camera* ct, double R[9]) {
   if (!cs || !ct || cs->n_inv < 0 || cs->n_inv > MCP_MAX_INV || ct->n_inv < 0 || ct->n_inv > MCP_MAX_INV) return img_fail("mcp_sbi_se3_from_se2: bad camera");
-  const double c[2] = { SBI_W/2, SBI_H/2 };
-  const double off[2][2] = { { 5, 0 }, { -5, 0 } };
-  double turned[2][2], orig[2][3];
-  for (int i = 0; i < 2; ++i) {
-    turned[i][0] = c[0] + se2[0]*off[i][0] + se2[1]*off[i][1] + se2[4];
-    turned[i][1] = c[1] + se2[2]*off[i][0] + se2[3]*off[i][1] + se2[5];
-    // TaylorCamera::UnProject, TaylorCamera.cc:319-347
-    const double det = ct->affine[0]*ct->affine[3] - ct->affine[1]*ct->affine[2];
-    const double ai[4] = { ct->affine[3]/det, -ct->affine[1]/det, -ct->affine[2]/det, ct->affine[0]/det };
-    const double dx = c[0] + off[i][0] - ct->center[0], dy = c[1] + off[i][1] - ct->center[1];
-    const double x = ai[0]*dx + ai[1]*dy, y = ai[2]*dx + ai[3]*dy;
-    const double rho = std::sqrt(x*x + y*y);
-    const double p[5] = { ct->params[0], 0.0, ct->params[1], ct->params[2], ct->params[3] };
-    double z = p[4]; for (int q = 3; q >= 0; --q) z = z*rho + p[q];
-    const double n = std::sqrt(x*x + y*y + z*z);
-    orig[i][0] = x/n; orig[i][1] = y/n; orig[i][2] = z/n;
-  }
-  double so3[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
-  for (int it = 0; it < 3; ++it) {
-    double C[9] = { 10, 0, 0, 0, 10, 0, 0, 0, 10 }, v[3] = { 0, 0, 0 };
-    for (int i = 0; i < 2; ++i) {
-      double cam[3]; mat3_vec(so3, orig[i], cam);
-      Projection P; cam_project<true>(*cs, cam, P);
-      const double err[2] = { turned[i][0] - P.u, turned[i][1] - P.v };
-      double dT[3], dP[3]; cam_sphere_deriv(cam, dT, dP);
-      double J[2][3];
-      for (int m = 0; m < 3; ++m) {
-        double mot[3] = { 0, 0, 0 };
-        mot[(m + 1)%3] = -cam[(m + 2)%3]; mot[(m + 2)%3] = cam[(m + 1)%3];
-        const double sm[2] = { dT[0]*mot[0] + dT[1]*mot[1] + dT[2]*mot[2], dP[0]*mot[0] + dP[1]*mot[1] + dP[2]*mot[2] };
-        J[0][m] = P.D[0]*sm[0] + P.D[1]*sm[1]; J[1][m] = P.D[2]*sm[0] + P.D[3]*sm[1];
-      }
-      for (int r = 0; r < 2; ++r) for (int a = 0; a < 3; ++a) { v[a] += J[r][a]*err[r]; for (int b = 0; b < 3; ++b) C[3*a + b] += J[r][a]*J[r][b]; }
-    }
-    const double c00 = C[4]*C[8] - C[5]*C[7], c01 = C[5]*C[6] - C[3]*C[8], c02 = C[3]*C[7] - C[4]*C[6];
-    const double id = 1.0/(C[0]*c00 + C[1]*c01 + C[2]*c02);
-    const double Ci[9] = { c00*id, (C[2]*C[7] - C[1]*C[8])*id, (C[1]*C[5] - C[2]*C[4])*id,
-                           c01*id, (C[0]*C[8] - C[2]*C[6])*id, (C[2]*C[3] - C[0]*C[5])*id,
-                           c02*id, (C[1]*C[6] - C[0]*C[7])*id, (C[0]*C[4] - C[1]*C[3])*id };
-    double mu[3]; mat3_vec(Ci, v, mu);
-    double E[9], Rn[9]; so3_exp(mu, E); mat3_mul(E, so3, Rn);
-    std::memcpy(so3, Rn, sizeof Rn);
-  }
-  std::memcpy(R, so3, 9*sizeof(double));
+  sbi_se3_from_se2(se2, cs, ct, R);
   return 0;
 }
 
@@ -1188,6 +1151,16 @@ struct mcp_map_points {
     hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr}; bool timed = false;      // mcp_map_points_last_timing: input copy | points | scene depth
     void invalidate() { timed = false; }
   } wb;
+  // mcp_track_frame_motion: the tracker's SmallBlurryImages, two sets per camera index (cur[c]: which is this frame's, the other is last
+  // frame's; have[c]: the index has made one since creation / mcp_track_motion_reset), the SBI tables (uploaded when they change), the
+  // alignments (se2[6], score per camera) and the pinned report
+  struct Mo {
+    Buf<SbiSet> sets; int cur[MCP_MAX_FRAME_CAMS] = {}; bool have[MCP_MAX_FRAME_CAMS] = {};
+    Buf<SbiTables> d_tabs; PinBuf<SbiTables> h_tabs; std::vector<SbiTables> tabs_last;
+    Buf<double> se2; PinBuf<mcp_track_motion> h_out;
+    int reserve() { return (sets.alloc(2*MCP_MAX_FRAME_CAMS) || d_tabs.alloc(MCP_MAX_FRAME_CAMS) || h_tabs.alloc(MCP_MAX_FRAME_CAMS) || se2.alloc(8*MCP_MAX_FRAME_CAMS) || h_out.alloc(1)) ? -1 : 0; }
+    void reset() { for (bool& h : have) h = false; }
+  } mo;
   // mcp_map_refind: the packed inputs (pinned | device), the passes' scratch, the pinned results (RfOut | verdict bytes | measurements)
   struct Rf {
     PinBuf<char> in; Buf<char> dev; Buf<uint8_t> flags, vd; Buf<int> blk, first; Buf<RfItem> items; Buf<mcp_refind_meas> cand; PinBuf<char> out;
@@ -1421,8 +1394,9 @@ static size_t pvs_layout(int ncam, const int* caps, int n, PvsLayout* Y) {
 // FindPVS of the table's n > 0 rows, enqueued on its stream (m->pvs.reserve has been called): the lists, laid out as Y says, and the counts
 // per (camera, level) go to `lists` and `counts`, pinned or device memory.  The launches' errors are the caller's to collect (and to answer
 // with tab_last.clear()).
+// d_bfw != NULL: the pose is read from there (12 doubles in device memory, left by an earlier kernel of the stream) instead of bfw.
 static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double* cfb, const double* bfw, const PvsLayout& Y,
-                       mcp_pvs_entry* lists, int* counts) {
+                       mcp_pvs_entry* lists, int* counts, const double* d_bfw = nullptr) {
   const int n = m->rows, nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
   std::vector<PvsCam> tab(ncam);
   for (int c = 0; c < ncam; ++c) {
@@ -1439,7 +1413,8 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
     ICK(hipMemcpyAsync(V.d_tab.p, V.h_tab.p, sizeof(PvsCam)*tab.size(), hipMemcpyHostToDevice, m->st));
     V.tab_last = tab;
   }
-  hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
+  if (d_bfw) hipLaunchKernelGGL(k_pvs_mark_at, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
+  else hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
   hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, n, nblk, (const signed char*)V.lvl.p,
                      (const mcp_pvs_entry*)V.ent.p, (const int*)V.blk_cnt.p, lists, counts);
   return 0;
@@ -1552,10 +1527,28 @@ static bool tm_regs_ok() {
   return pose_regs_attr(dev) && (e ? atoi(e) != 0 : true);
 }
 
-// the body of mcp_track_map (rp == NULL: exactly its launches) and of mcp_track_map_record (rp, rec checked by the caller)
+// what mcp_track_frame_motion adds to the frame: the 40x30 cameras, the motion model's inputs and its report
+struct MotionArg { const mcp_camera* cams_sbi; const mcp_track_motion_params* p; mcp_track_motion* out; };
+static bool finite6(const double* a) { for (int k = 0; k < 6; ++k) if (!std::isfinite(a[k])) return false; return true; }
+// the refusals the motion model's entries share
+static int motion_check(const std::string& who, int ncam, const mcp_camera* cams_sbi, const mcp_track_motion_params* p, const mcp_track_motion* out) {
+  if (!p || !out) return img_fail(who + ": NULL motion parameters or motion result");
+  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS) return img_fail(who + ": bad camera count");
+  if (!cams_sbi) return img_fail(who + ": NULL SBI cameras");
+  for (int c = 0; c < ncam; ++c) if (!cam_ok(&cams_sbi[c])) return img_fail(who + ": bad SBI camera " + std::to_string(c));
+  if (!(p->blur > 0) || !std::isfinite(p->blur)) return img_fail(who + ": blur must be positive");
+  if (p->sbi_iterations < 0) return img_fail(who + ": negative SBI iteration count");
+  if (p->apply && !(std::isfinite(p->dt) && p->dt > 0)) return img_fail(who + ": dt must be finite and positive when the motion model is applied");
+  if (!finite6(p->velocity)) return img_fail(who + ": the velocity is not finite");
+  return 0;
+}
+
+// the body of mcp_track_map (rp == NULL: exactly its launches), of mcp_track_map_record (rp, rec checked by the caller) and of
+// mcp_track_frame_motion (mo: k_frame_sbi and k_motion_prior between the pyramids' event and the PVS, which then reads the pose from the
+// parameter block, and k_motion_update behind the fine iterations; mo == NULL: no launch more or less than before)
 static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                          const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
-                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec) {
+                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec, const MotionArg* mo = nullptr) {
   if (!m) return img_fail(who + ": NULL table");
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail(who + ": bad arguments");
   if (prm->coarse_max < 0 || prm->coarse_range < 0 || prm->coarse_min < 0 || prm->coarse_subpix_its < 0 || prm->max_patches < 0)
@@ -1565,7 +1558,9 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
     if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail(who + ": bad arguments for camera " + std::to_string(c));
     if (target_on_table_device(who, m, c, targets[c])) return -1;
     for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail(who + ": a keyframe appears twice in a frame with images");
+    if (mo && !imgs && !targets[c]->has_image) return img_fail(who + ": camera " + std::to_string(c) + "'s target holds no frame and no images were given");
   }
+  if (mo && motion_check(who, ncam, mo->cams_sbi, mo->p, mo->out)) return -1;
   ICK(hipSetDevice(m->device));
   // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
   m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate();
@@ -1586,8 +1581,10 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   }
   // (param block: cameras' search table | camera models | CamFromBase | BaseFromWorld + mu | override sigma x 2 | nonlinear flags x 2)
   const size_t o_tab = 0, o_cam = tm_align(sizeof(TmCam)*(size_t)ncam), o_cfb = o_cam + tm_align(sizeof(mcp_camera)*(size_t)ncam), o_pm = o_cfb + tm_align(96*(size_t)ncam);
-  const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), blk = o_nl + tm_align(20);
+  const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), o_cs = o_nl + tm_align(20);      // (| the SBI cameras, with a motion model)
+  const size_t blk = o_cs + (mo ? tm_align(sizeof(mcp_camera)*(size_t)ncam) : 0);
   if (m->tm.blk.alloc(blk) || m->tm.h_blk.alloc(blk)) return -1;
+  if (mo && m->mo.reserve()) return -1;
   const size_t n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK;
   if (rp) {
     if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
@@ -1611,6 +1608,7 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   std::memcpy(hb + o_cam, cams, sizeof(mcp_camera)*(size_t)ncam);
   std::memcpy(hb + o_cfb, cfb, 96*(size_t)ncam);
   std::memcpy(hb + o_pm, bfw, 96);
+  if (mo) std::memcpy(hb + o_cs, mo->cams_sbi, sizeof(mcp_camera)*(size_t)ncam);
   double* ov = reinterpret_cast<double*>(hb + o_ov); uint8_t* nl = hb + o_nl;
   for (int i = 0; i < 10; ++i) {
     ov[i] = i < 6 ? 0.0 : 1.0; nl[i] = 1;                                                 // coarse, Tracker.cc:1012-1020
@@ -1622,11 +1620,40 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   hipStream_t st = m->st;
   ICK(hipMemcpyAsync(m->tm.blk.p, hb, blk, hipMemcpyHostToDevice, st));
   ICK(hipMemcpyAsync(m->tm.slots.p, m->tm.h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
+  double* d_pm = reinterpret_cast<double*>(m->tm.blk.p + o_pm);
+  const double* d_cfb = reinterpret_cast<const double*>(m->tm.blk.p + o_cfb);
+  if (mo) {
+    // 0. the motion model: this frame's SBI of every camera (the one before becomes last frame's), its alignment, the prior into the pose slot
+    mcp_map_points::Mo& M = m->mo;
+    const mcp_track_motion_params& mp = *mo->p;
+    std::vector<SbiTables> tabs(ncam);
+    FrameSbiArgs fa; std::memset(&fa, 0, sizeof fa);
+    MotionFirst first; std::memset(&first, 0, sizeof first);
+    for (int c = 0; c < ncam; ++c) {
+      const Level& L0 = targets[c]->lev[0];
+      sbi_tables(L0.w, L0.h, mp.blur, tabs[c]);
+      first.v[c] = M.have[c] ? 0 : 1;
+      if (M.have[c]) M.cur[c] ^= 1;
+      M.have[c] = true;
+      FrameSbiCam& F = fa.c[c];
+      F.img = L0.img.p; F.w = L0.w; F.h = L0.h; F.first = first.v[c]; F.align = motion_cam_used(mp, c) ? 1 : 0;
+      F.cur = M.sets.p + 2*c + M.cur[c]; F.last = M.sets.p + 2*c + (M.cur[c] ^ 1);
+    }
+    if (M.tabs_last.size() != tabs.size() || std::memcmp(M.tabs_last.data(), tabs.data(), sizeof(SbiTables)*tabs.size()) != 0) {
+      std::memcpy(M.h_tabs.p, tabs.data(), sizeof(SbiTables)*tabs.size());
+      ICK(hipMemcpyAsync(M.d_tabs.p, M.h_tabs.p, sizeof(SbiTables)*tabs.size(), hipMemcpyHostToDevice, st));
+      M.tabs_last = tabs;
+    }
+    std::memset(M.h_out.p, 0, sizeof(mcp_track_motion));
+    hipLaunchKernelGGL(k_frame_sbi, dim3(ncam), dim3(256), 0, st, fa, (const SbiTables*)M.d_tabs.p, mp.sbi_iterations, M.se2.p);
+    hipLaunchKernelGGL(k_motion_prior, dim3(1), dim3(64), 0, st, ncam, (const double*)M.se2.p, first, reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cs), d_cfb, d_pm, mp, M.h_out.p);
+    ICK(hipGetLastError());
+  }
   // 1. FindPVS, lists and counts in device memory (caps = rows; camera c's list at c * rows)
   PvsLayout Y;
   pvs_layout(ncam, nullptr, n, &Y);
   if (n > 0) {
-    if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p)) return -1;
+    if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? d_pm : nullptr)) return -1;
   } else ICK(hipMemsetAsync(m->tm.counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
   // 2. the sets
   TmParams P; P.ncam = ncam; P.rows = n; P.try_coarse = prm->try_coarse ? 1 : 0; P.coarse_max = prm->coarse_max; P.coarse_range = prm->coarse_range;
@@ -1635,8 +1662,6 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
                      (const TmSlot*)m->tm.slots.p, m->tm.k0.p, m->tm.k1.p, m->tm.live.p, m->tm.sel.p, m->tm.ctl.p);
   const TmCam* d_tab = reinterpret_cast<const TmCam*>(m->tm.blk.p + o_tab);
   const mcp_camera* d_cams = reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cam);
-  const double* d_cfb = reinterpret_cast<const double*>(m->tm.blk.p + o_cfb);
-  double* d_pm = reinterpret_cast<double*>(m->tm.blk.p + o_pm);
   const double* d_ov = reinterpret_cast<const double*>(m->tm.blk.p + o_ov);
   const uint8_t* d_nl = m->tm.blk.p + o_nl;
   TmCtl* ctl = m->tm.ctl.p;
@@ -1659,6 +1684,10 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, m->pts.row(),
                      m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
   if (iterate(NB, &ctl->n_fine, nullptr, m->tm.frec.p, 1)) return -1;
+  if (mo) {      // UpdateMotionModel, from the refined pose
+    Pose12 start; std::memcpy(start.v, bfw, 96);
+    hipLaunchKernelGGL(k_motion_update, dim3(1), dim3(64), 0, st, (const double*)d_pm, start, *mo->p, m->mo.h_out.p);
+  }
   if (rp) {
     // the bookkeeping, from the items, the last weights and the refined pose where the iterations left them
     TrParams Q; Q.ncam = ncam; Q.lost = rp->lost ? 1 : 0; Q.min_patches = rp->min_patches; Q.coarse_min = rp->coarse_min; Q.good = rp->quality_good; Q.bad = rp->quality_bad;
@@ -1705,6 +1734,7 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
   std::memcpy(res->mu_last, R.mu, 48);
   std::memcpy(bfw, R.pose, 96);
+  if (mo) *mo->out = *m->mo.h_out.p;
   return 0;
 }
 
@@ -1721,6 +1751,62 @@ int mcp_track_map_record(mcp_map_points* m, int ncam, mcp_kf* const* targets, co
   if (!rp || !rec) return img_fail("mcp_track_map_record: NULL record parameters or record");
   if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_map_record: a quality threshold is not finite");
   return track_map_run("mcp_track_map_record", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec);
+}
+
+int mcp_track_frame_motion(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                           const uint8_t* const* const* masks, const mcp_camera* cams, const mcp_camera* cams_sbi, double bfw[12], const double* cfb,
+                           const mcp_track_map_params* prm, mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec,
+                           const mcp_track_motion_params* mp, mcp_track_motion* out) {
+  if (!m) return img_fail("mcp_track_frame_motion: NULL table");
+  if (!rp || !rec) return img_fail("mcp_track_frame_motion: NULL record parameters or record");
+  if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_frame_motion: a quality threshold is not finite");
+  if (!mp || !out) return img_fail("mcp_track_frame_motion: NULL motion parameters or motion result");
+  const MotionArg mo{cams_sbi, mp, out};
+  return track_map_run("mcp_track_frame_motion", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec, &mo);
+}
+
+int mcp_track_motion_reset(mcp_map_points* m) {
+  if (!m) return img_fail("mcp_track_motion_reset: NULL table");
+  m->mo.reset();
+  return 0;
+}
+
+int mcp_track_motion_get_sbi(const mcp_map_points* mc, int cam, int which, uint8_t* small_img, float* templ, float* jacs) {
+  if (!mc) return img_fail("mcp_track_motion_get_sbi: NULL table");
+  if (cam < 0 || cam >= MCP_MAX_FRAME_CAMS || which < 0 || which > 1) return img_fail("mcp_track_motion_get_sbi: bad camera index or selector");
+  if (!mc->mo.have[cam]) return img_fail("mcp_track_motion_get_sbi: camera index " + std::to_string(cam) + " has made no SmallBlurryImage since the table was created or reset");
+  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
+  ICK(hipSetDevice(m->device));
+  ICK(m->sync());
+  const SbiSet* S = m->mo.sets.p + 2*cam + (m->mo.cur[cam] ^ which);
+  if (small_img) ICK(hipMemcpy(small_img, S->small_img, SBI_N, hipMemcpyDeviceToHost));
+  if (templ) ICK(hipMemcpy(templ, S->templ, SBI_N*sizeof(float), hipMemcpyDeviceToHost));
+  if (jacs) ICK(hipMemcpy(jacs, S->jacs, 2*SBI_N*sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mcp_track_motion_prior_host(int ncam, const double* se2, const mcp_camera* cams_sbi, const double* cfb, const double start[12],
+                                const mcp_track_motion_params* p, mcp_track_motion* out) {
+  if (motion_check("mcp_track_motion_prior_host", ncam, cams_sbi, p, out)) return -1;
+  if (!se2 || !cfb || !start) return img_fail("mcp_track_motion_prior_host: NULL alignments, CamFromBase or start pose");
+  double rot[MCP_MAX_FRAME_CAMS][3] = {};
+  for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c) {
+    const bool used = c < ncam && motion_cam_used(*p, c);
+    for (int k = 0; k < 6; ++k) out->se2[c][k] = used ? se2[6*c + k] : 0.0;
+    if (used) motion_cam_rotation(se2 + 6*c, cams_sbi + c, cfb + 12*c, rot[c]);
+  }
+  double prior[12];
+  motion_prior(ncam, rot, *p, start, out, prior);
+  return 0;
+}
+
+int mcp_track_motion_update_host(const double start[12], const double refined[12], const mcp_track_motion_params* p, mcp_track_motion* out) {
+  if (!p || !out) return img_fail("mcp_track_motion_update_host: NULL motion parameters or motion result");
+  if (!start || !refined) return img_fail("mcp_track_motion_update_host: NULL pose");
+  if (p->apply && !(std::isfinite(p->dt) && p->dt > 0)) return img_fail("mcp_track_motion_update_host: dt must be finite and positive when the motion model is applied");
+  if (!finite6(p->velocity)) return img_fail("mcp_track_motion_update_host: the velocity is not finite");
+  motion_update(start, refined, *p, out->v_new, out->velocity);
+  return 0;
 }
 
 const mcp_track_note* mcp_track_map_notes_view(const mcp_map_points* m, int cam, int* count) {

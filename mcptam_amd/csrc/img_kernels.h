@@ -998,11 +998,10 @@ struct SbiTables {               // cv::resize fixed-point taps and the Gaussian
 
 // one workgroup: resize (integer, as cv::resize 8U INTER_LINEAR), exact integer sum -> float mean, separable Gaussian in
 // float with the taps accumulated centre-first then outwards (zero outside the image), central differences
-__global__ void __launch_bounds__(256)
-k_sbi_make(const uint8_t* __restrict__ img, int iw, int ih, SbiTables tb, uint8_t* __restrict__ small_out,
-           float* __restrict__ templ_out, float* __restrict__ jacs_out) {
-  __shared__ float A[SBI_N], B[SBI_N];
-  __shared__ unsigned int red[4];
+// (the body, shared with k_frame_sbi of track_motion_kernels.h: A, B (SBI_N floats each) and red (4) are the caller's LDS; on return -- no barrier
+// after the last loop, which only reads A -- A holds the template)
+__device__ __forceinline__ void sbi_make_body(const uint8_t* __restrict__ img, int iw, int ih, const SbiTables& tb, uint8_t* __restrict__ small_out,
+                                              float* __restrict__ templ_out, float* __restrict__ jacs_out, float* A, float* B, unsigned int* red) {
   const int t = threadIdx.x;
   unsigned int loc = 0;
   for (int i = t; i < SBI_N; i += 256) {
@@ -1042,6 +1041,13 @@ k_sbi_make(const uint8_t* __restrict__ img, int iw, int ih, SbiTables tb, uint8_
     jacs_out[2*i] = gx; jacs_out[2*i + 1] = gy;
   }
 }
+__global__ void __launch_bounds__(256)
+k_sbi_make(const uint8_t* __restrict__ img, int iw, int ih, SbiTables tb, uint8_t* __restrict__ small_out,
+           float* __restrict__ templ_out, float* __restrict__ jacs_out) {
+  __shared__ float A[SBI_N], B[SBI_N];
+  __shared__ unsigned int red[4];
+  sbi_make_body(img, iw, ih, tb, small_out, templ_out, jacs_out, A, B, red);
+}
 
 // one thread per candidate keyframe, raster-order double accumulation exactly as the scalar loop (so scores, and with them
 // the "first smallest" winner, are bit-identical); the 1200-float templates are a few kB each
@@ -1058,14 +1064,14 @@ k_sbi_score(const float* __restrict__ cur, const float* const* __restrict__ cand
 
 // ESM alignment, all iterations in one launch (single workgroup): warp by closed-form source positions, 15 partial sums per
 // thread in double, fixed-order tree reduction, 4x4 LDL^T solve and SE2 update on thread 0
-__global__ void __launch_bounds__(256)
-k_sbi_iterate(const float* __restrict__ me, const float* __restrict__ ot_templ, const float* __restrict__ ot_jacs, int iterations,
-              double* __restrict__ out /* se2[6], score */) {
-  __shared__ float Tm[SBI_N], warped[SBI_N];
-  __shared__ double X[6], red[256][15 + 1], st[8];
+constexpr int SBI_RED = 15 + 1;      // the row of the reduction scratch: 15 sums and one of padding
+// (the body, shared with k_frame_sbi: Tm, warped (SBI_N floats each), X (6), red (256 rows of SBI_RED) and st (8) are the caller's LDS; me == NULL:
+// Tm already holds this frame's template and every thread has passed a barrier since it was written)
+__device__ __forceinline__ void sbi_iterate_body(const float* __restrict__ me, const float* __restrict__ ot_templ, const float* __restrict__ ot_jacs, int iterations,
+                                                 double* __restrict__ out /* se2[6], score */, float* Tm, float* warped, double* X, double (*red)[SBI_RED], double* st) {
   const int t = threadIdx.x;
   const int cx = SBI_W/2, cy = SBI_H/2;
-  for (int i = t; i < SBI_N; i += 256) Tm[i] = me[i];
+  if (me) for (int i = t; i < SBI_N; i += 256) Tm[i] = me[i];
   if (t == 0) { st[0] = 1; st[1] = 0; st[2] = 0; st[3] = 1; st[4] = 0; st[5] = 0; st[6] = 0; st[7] = 0; }   // CtoC, mean offset, score
   __syncthreads();
   for (int it = 0; it < iterations; ++it) {
@@ -1147,6 +1153,13 @@ k_sbi_iterate(const float* __restrict__ me, const float* __restrict__ ot_templ, 
   }
   if (t < 6) out[t] = st[t];
   if (t == 6) out[6] = st[7];
+}
+__global__ void __launch_bounds__(256)
+k_sbi_iterate(const float* __restrict__ me, const float* __restrict__ ot_templ, const float* __restrict__ ot_jacs, int iterations,
+              double* __restrict__ out /* se2[6], score */) {
+  __shared__ float Tm[SBI_N], warped[SBI_N];
+  __shared__ double X[6], red[256][SBI_RED], st[8];
+  sbi_iterate_body(me, ot_templ, ot_jacs, iterations, out, Tm, warped, X, red, st);
 }
 
 

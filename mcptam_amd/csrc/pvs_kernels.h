@@ -1,6 +1,6 @@
 // pvs_kernels.h -- Tracker::FindPVS over a device-resident map-point table (src/Tracker.cc:662-723), gfx950.
 //
-// One thread per (row, camera).  k_pvs_mark runs the per-point part of FindPVS -- TrackerData::Project, the level-0 mask test,
+// One thread per (row, camera).  k_pvs_mark (k_pvs_mark_at: the same body with the pose read from device memory) runs the per-point part of FindPVS -- TrackerData::Project, the level-0 mask test,
 // GetDerivsUnsafe, PatchFinder::CalcSearchLevelAndWarpMatrix -- through the same __device__ helpers the per-point search uses
 // (track_project / track_warp_level, img_kernels.h), so the results carry the search's bits; it leaves every accepted entry in a
 // (camera, row) slot and the per-workgroup counts of each level.  k_pvs_scatter (same stream, next launch) sums the counts of the
@@ -20,10 +20,9 @@ struct PvsCam {
 };
 constexpr int PVS_BLOCK = 256;
 
-__global__ void __launch_bounds__(PVS_BLOCK)
-k_pvs_mark(const PvsCam* __restrict__ tab, Se3 bfw, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl /* ncam x n */,
-           mcp_pvs_entry* __restrict__ ent /* ncam x n, written where lvl >= 0 */, int* __restrict__ blk_cnt /* ncam x nblk x MCP_LEVELS */) {
-  __shared__ int cnt[MCP_LEVELS];
+// (the body of k_pvs_mark and k_pvs_mark_at; cnt: MCP_LEVELS ints of the caller's LDS)
+__device__ __forceinline__ void pvs_mark_body(const PvsCam* __restrict__ tab, const Se3& bfw, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl,
+                                              mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt, int* cnt) {
   const int c = blockIdx.y, i = blockIdx.x*PVS_BLOCK + threadIdx.x;
   if (threadIdx.x < MCP_LEVELS) cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -54,6 +53,25 @@ k_pvs_mark(const PvsCam* __restrict__ tab, Se3 bfw, const PvsPoint* __restrict__
   }
   __syncthreads();
   if (threadIdx.x < MCP_LEVELS) blk_cnt[((size_t)c*nblk + blockIdx.x)*MCP_LEVELS + threadIdx.x] = cnt[threadIdx.x];
+}
+__global__ void __launch_bounds__(PVS_BLOCK)
+k_pvs_mark(const PvsCam* __restrict__ tab, Se3 bfw, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl /* ncam x n */,
+           mcp_pvs_entry* __restrict__ ent /* ncam x n, written where lvl >= 0 */, int* __restrict__ blk_cnt /* ncam x nblk x MCP_LEVELS */) {
+  __shared__ int cnt[MCP_LEVELS];
+  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt);
+}
+// the same pass with BaseFromWorld read from device memory (12 doubles, R row-major then t): the pose an earlier kernel of the same stream left
+// there (mcp_track_frame_motion: k_motion_prior)
+__global__ void __launch_bounds__(PVS_BLOCK)
+k_pvs_mark_at(const PvsCam* __restrict__ tab, const double* __restrict__ bfw12, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl,
+              mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt) {
+  __shared__ int cnt[MCP_LEVELS];
+  Se3 bfw;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) bfw.R[k] = bfw12[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) bfw.t[k] = bfw12[9 + k];
+  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt);
 }
 
 __global__ void __launch_bounds__(PVS_BLOCK)

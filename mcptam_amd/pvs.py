@@ -2,7 +2,9 @@
 mcp_track_find_pvs, mcp_track_map).  The table holds, per row, what FindPVS reads of a MapPoint (world position, the two pixel vectors, usable =
 !mbBad && mbOptimized); one find_pvs call gives the potentially visible set of every camera of a frame, level by level.  track_map runs the
 whole TrackMap of a frame from the table; track_map_record also leaves its bookkeeping (marks into the table's count column, level counters,
-quality, found measurements, scene depth), with track_record_restate / tracking_quality as the numpy restatements."""
+quality, found measurements, scene depth), with track_record_restate / tracking_quality as the numpy restatements.  track_frame_motion is
+track_map_record started from the pose the tracker's motion model gives on the device (SmallBlurryImage rotation estimate, velocity), with
+so3_ln / se3_ln / average_rotation / motion_prior / motion_update as the numpy restatements."""
 import ctypes
 import math
 
@@ -343,6 +345,47 @@ class MapPointTable:
         meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
         return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec
 
+    # ---- TrackFrame's tracking branch: motion model + TrackMap + its bookkeeping (include/mcp_img.h mcp_track_frame_motion) ----
+    def track_frame_motion(self, targets, cams, cams_sbi, base_from_world, cams_from_base, velocity=None, dt=1.0 / 30, cam_good=None, apply=True,
+                           use_rotation_estimator=True, sbi_iterations=6, blur=0.75, lost=False, want_items=True, min_patches=10, quality_coarse_min=20,
+                           quality_good=0.3, quality_bad=0.13, try_coarse=True, coarse_max=60, coarse_range=30, coarse_min=20, coarse_subpix_its=8,
+                           max_patches=1000, estimator="Tukey", seed=0, imgs=None, on_device=False, strides=None, copy=True):
+        """mcp_track_frame_motion: ApplyMotionModel (with the SBI rotation estimate), TrackMap with its bookkeeping and UpdateMotionModel in one
+        call.  base_from_world: last frame's pose (mse3StartPose); cams_sbi: the 40x30 camera per camera; velocity: mv6BaseVelocity [t; w];
+        cam_good: per camera, was its tracking quality GOOD after the previous frame (default: all).  Returns track_map_record's tuple plus the
+        TrackMotion report (start, prior, se2, sbi_score, cam_rot, sbi_rot, n_used, avg_rounds, first_frame, v_new, velocity)."""
+        L = _bind_track_motion(_bind_track_record(_bind_track_map(self._L)))
+        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
+        css = cams_sbi if isinstance(cams_sbi, ctypes.Array) else camera_array(cams_sbi)
+        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
+                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
+        rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
+        mp = motion_params(velocity, dt, cam_good, apply, use_rotation_estimator, sbi_iterations, blur, ncam)
+        res, rec, mo = TrackMapResult(), TrackRecord(), TrackMotion()
+        _chk(L.mcp_track_frame_motion(self._h, ncam, hs, ip, st, int(on_device), None, cs, ctypes.cast(css, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
+                                      ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec), ctypes.byref(mp), ctypes.byref(mo)), "track_frame_motion")
+        del keep
+
+        def views(fn, dtype, expect):
+            text = "track_frame_motion: view of camera %d has %%(got)d entries, the record says %%(expect)d: "
+            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
+        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
+        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
+        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
+        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec, mo
+
+    def motion_reset(self):
+        """Tracker::Reset: every camera index forgets its SmallBlurryImages."""
+        _chk(_bind_track_motion(self._L).mcp_track_motion_reset(self._h), "track_motion_reset")
+
+    def motion_sbi(self, cam, which=0):
+        """The tracker's SBI of camera index cam, which = 0 this frame's, 1 last frame's: (small u8 30x40, template f32 30x40, jacs f32 30x40x2)."""
+        small = np.zeros((30, 40), dtype=np.uint8)
+        templ = np.zeros((30, 40), dtype=np.float32)
+        jacs = np.zeros((30, 40, 2), dtype=np.float32)
+        _chk(_bind_track_motion(self._L).mcp_track_motion_get_sbi(self._h, int(cam), int(which), small.ctypes.data, templ.ctypes.data, jacs.ctypes.data), "track_motion_get_sbi")
+        return small, templ, jacs
+
 
 # ---- Tracker::TrackMap of a frame from the table (include/mcp_img.h mcp_track_map) ---------------------------------------------------
 TRACK_MAP_SYMBOLS = ["mcp_map_points_set_source", "mcp_map_points_update_source", "mcp_map_points_get_states", "mcp_track_map", "mcp_track_map_view",
@@ -669,3 +712,179 @@ def track_record_restate(items, counts_before, lost, ncam):
     seg_w = inl[seg_rows].astype(np.float64) / (inl[seg_rows] + outl[seg_rows]).astype(np.float64)
     return dict(notes=notes, meas=meas, attempted=attempted, found=found, n_items=[len(items[c]) for c in range(ncam)], n_meas=[len(m_) for m_ in meas],
                 n_inliers=n_inliers, n_outlier_marks=n_out, counts=(inl.astype(np.int32), outl.astype(np.int32)), seg_start=seg_start, seg_rows=seg_rows, seg_w=seg_w)
+
+
+# ---- the tracker's motion model (include/mcp_img.h mcp_track_frame_motion) and its numpy restatement -------------------------------------
+TRACK_MOTION_SYMBOLS = ["mcp_track_frame_motion", "mcp_track_motion_reset", "mcp_track_motion_get_sbi", "mcp_track_motion_prior_host",
+                        "mcp_track_motion_update_host"]
+MOTION_AVG_ROUNDS, MOTION_AVG_EPS = 32, 1e-3
+
+
+class TrackMotionParams(ctypes.Structure):
+    _fields_ = [("apply", ctypes.c_int), ("use_rotation_estimator", ctypes.c_int), ("sbi_iterations", ctypes.c_int), ("blur", ctypes.c_double),
+                ("dt", ctypes.c_double), ("velocity", ctypes.c_double * 6), ("cam_good", ctypes.c_uint8 * MAX_FRAME_CAMS)]
+
+
+class TrackMotion(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_double * 12), ("prior", ctypes.c_double * 12), ("se2", (ctypes.c_double * 6) * MAX_FRAME_CAMS),
+                ("sbi_score", ctypes.c_double * MAX_FRAME_CAMS), ("cam_rot", (ctypes.c_double * 3) * MAX_FRAME_CAMS), ("sbi_rot", ctypes.c_double * 3),
+                ("n_used", ctypes.c_int), ("avg_rounds", ctypes.c_int), ("first_frame", ctypes.c_int * MAX_FRAME_CAMS),
+                ("v_new", ctypes.c_double * 6), ("velocity", ctypes.c_double * 6)]
+
+
+def motion_params(velocity=None, dt=1.0 / 30, cam_good=None, apply=True, use_rotation_estimator=True, sbi_iterations=6, blur=0.75, ncam=MAX_FRAME_CAMS):
+    """A TrackMotionParams; cam_good defaults to every one of the ncam cameras."""
+    good = [1] * ncam if cam_good is None else [int(bool(g)) for g in cam_good]
+    good = (good + [0] * MAX_FRAME_CAMS)[:MAX_FRAME_CAMS]
+    v = np.zeros(6) if velocity is None else np.asarray(velocity, dtype=np.float64).reshape(6)
+    return TrackMotionParams(int(bool(apply)), int(bool(use_rotation_estimator)), int(sbi_iterations), float(blur), float(dt), (ctypes.c_double * 6)(*v),
+                             (ctypes.c_uint8 * MAX_FRAME_CAMS)(*good))
+
+
+def _bind_track_motion(L):
+    if getattr(L, "_track_motion_bound", False):
+        return L
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.mcp_track_frame_motion.argtypes = [vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mcp_track_motion_reset.argtypes = [vp]
+    L.mcp_track_motion_get_sbi.argtypes = [vp, ip, ip, vp, vp, vp]
+    L.mcp_track_motion_prior_host.argtypes = [ip, vp, vp, vp, vp, vp, vp]
+    L.mcp_track_motion_update_host.argtypes = [vp, vp, vp, vp]
+    L._track_motion_bound = True
+    return L
+
+
+def motion_prior_host(se2, cams_sbi, cams_from_base, start, mp):
+    """mcp_track_motion_prior_host: se2 (ncam, 6), cams_sbi: TaylorCameras (or a ctypes camera array), cams_from_base (ncam, 12), start: 12
+    doubles, mp: TrackMotionParams.  Returns the TrackMotion it filled."""
+    L = _bind_track_motion(lib())
+    se2 = np.ascontiguousarray(se2, dtype=np.float64).reshape(-1, 6)
+    css = cams_sbi if isinstance(cams_sbi, ctypes.Array) else camera_array(cams_sbi)
+    cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1)
+    st = np.ascontiguousarray(start, dtype=np.float64).reshape(12)
+    out = TrackMotion()
+    _chk(L.mcp_track_motion_prior_host(len(se2), se2.ctypes.data, ctypes.cast(css, ctypes.c_void_p), cfb.ctypes.data, st.ctypes.data, ctypes.byref(mp), ctypes.byref(out)),
+         "track_motion_prior_host")
+    return out
+
+
+def motion_update_host(start, refined, mp):
+    """mcp_track_motion_update_host: (v_new, velocity) from two poses of 12 doubles."""
+    L = _bind_track_motion(lib())
+    a, b = np.ascontiguousarray(start, dtype=np.float64).reshape(12), np.ascontiguousarray(refined, dtype=np.float64).reshape(12)
+    out = TrackMotion()
+    _chk(L.mcp_track_motion_update_host(a.ctypes.data, b.ctypes.data, ctypes.byref(mp), ctypes.byref(out)), "track_motion_update_host")
+    return np.array(out.v_new), np.array(out.velocity)
+
+
+def _hat(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def _abc(th):
+    """sin t / t, (1 - cos t) / t^2, (t - sin t) / t^3: series below 0.03 rad (the next term is under 1e-17), closed forms above."""
+    t2 = th * th
+    if th < 0.03:
+        return (1 - t2 / 6 * (1 - t2 / 20 * (1 - t2 / 42)), 0.5 - t2 / 24 * (1 - t2 / 30 * (1 - t2 / 56)), 1.0 / 6 - t2 / 120 * (1 - t2 / 42 * (1 - t2 / 72)))
+    A = math.sin(th) / th
+    return A, 2 * math.sin(th / 2) ** 2 / t2, (1 - A) / t2
+
+
+def so3_exp(w):
+    """Rodrigues' formula, no truncation thresholds: I + A [w]x + B [w]x^2."""
+    w = np.asarray(w, dtype=np.float64)
+    A, B, _ = _abc(float(np.linalg.norm(w)))
+    K = _hat(w)
+    return np.eye(3) + A * K + B * (K @ K)
+
+
+def se3_exp(mu):
+    """(R, t) of the twist mu = [t; w]: R = exp(w), t = (I + B [w]x + C [w]x^2) mu_t."""
+    mu = np.asarray(mu, dtype=np.float64)
+    w = mu[3:]
+    A, B, C = _abc(float(np.linalg.norm(w)))
+    K = _hat(w)
+    return np.eye(3) + A * K + B * (K @ K), (np.eye(3) + B * K + C * (K @ K)) @ mu[:3]
+
+
+def so3_ln(R):
+    """Axis-angle of a rotation matrix: the angle is atan2(|a|, (tr R - 1) / 2) with a the vector of the antisymmetric part; towards pi, where
+    a vanishes, the axis is the largest column of R + I, signed by a."""
+    R = np.asarray(R, dtype=np.float64)
+    a = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = float(np.linalg.norm(a)), 0.5 * (np.trace(R) - 1.0)
+    th = math.atan2(s, c)
+    if s < 1e-4 and c > 0:
+        return a * (1 + s * s / 6 * (1 + 9 * s * s / 20))          # asin(s) / s
+    if s < 1e-4:
+        S = 0.5 * (R + R.T) + np.eye(3)                              # (1 - cos t)(n n^T) + (1 + cos t) I, cos t ~ -1
+        k = int(np.argmax(np.diag(S)))
+        n = S[:, k] / np.linalg.norm(S[:, k])
+        return th * (-n if n @ a < 0 else n)
+    return a * (th / s)
+
+
+def se3_ln(R, t):
+    """The twist [t; w] with se3_exp = (R, t): w = so3_ln(R), mu_t = (I - [w]x / 2 + D [w]x^2) t, D = (1 - A / 2B) / |w|^2."""
+    w = so3_ln(R)
+    th = float(np.linalg.norm(w))
+    if th < 0.03:
+        D = 1.0 / 12 + th * th / 720 * (1 + th * th / 42)
+    else:
+        A, B, _ = _abc(th)
+        D = (1 - A / (2 * B)) / (th * th)
+    K = _hat(w)
+    return np.concatenate([(np.eye(3) - 0.5 * K + D * (K @ K)) @ np.asarray(t, dtype=np.float64), w])
+
+
+def average_rotation(rots, eps=MOTION_AVG_EPS, max_rounds=MOTION_AVG_ROUNDS):
+    """Tracker::FindAverageRotation (src/Tracker.cc:1723-1749), the geodesic L2 mean of axis-angle rotations, ended after max_rounds
+    evaluations of the mean residual at the latest.  Returns (mean, rounds)."""
+    rots = [np.asarray(r, dtype=np.float64) for r in rots]
+    R = so3_exp(rots[0])
+    rounds = 0
+    while rounds < max_rounds:
+        r = sum(so3_ln(R.T @ so3_exp(q)) for q in rots) / len(rots)
+        rounds += 1
+        if r @ r < eps * eps:
+            break
+        R = R @ so3_exp(r)
+    return so3_ln(R), rounds
+
+
+def motion_prior(se2, cams_sbi, cams_from_base, start, velocity, dt, cam_good, apply=True, use_rotation_estimator=True, se3_from_se2=None):
+    """Tracker::ApplyMotionModel with CalcSBIRotation (src/Tracker.cc:1516-1536, 1687-1721): se2 (ncam, 6) = the alignments [R row-major; t],
+    cams_sbi: the 40x30 TaylorCameras, cams_from_base: (R, t) per camera, start: (R, t).  se3_from_se2(R2, t2, cam, cam) -> 3x3 rotation,
+    default the library's host entry.  Returns dict(prior=(R, t), cam_rot (ncam, 3), sbi_rot, n_used, avg_rounds)."""
+    if se3_from_se2 is None:
+        from .keyframe import sbi_se3_from_se2 as se3_from_se2
+    se2 = np.asarray(se2, dtype=np.float64).reshape(-1, 6)
+    ncam = len(se2)
+    cam_rot, used = np.zeros((ncam, 3)), []
+    for c in range(ncam):
+        if not (apply and use_rotation_estimator and cam_good[c]):
+            continue
+        if not np.array_equal(se2[c], [1, 0, 0, 1, 0, 0]):              # (an SBI against itself: exactly no rotation)
+            Rc = se3_from_se2(se2[c, :4].reshape(2, 2), se2[c, 4:], cams_sbi[c], cams_sbi[c])
+            cam_rot[c] = np.asarray(cams_from_base[c][0]).T @ so3_ln(Rc)
+        used.append(cam_rot[c])
+    Rs, ts = np.asarray(start[0], dtype=np.float64), np.asarray(start[1], dtype=np.float64)
+    sbi_rot, rounds = (average_rotation(used) if used else (np.zeros(3), 0))
+    if not apply:
+        return dict(prior=(Rs.copy(), ts.copy()), cam_rot=cam_rot, sbi_rot=sbi_rot, n_used=len(used), avg_rounds=rounds)
+    v6 = np.asarray(velocity, dtype=np.float64) * dt
+    if used:
+        v6[3:] = sbi_rot
+    Re, te = se3_exp(v6)
+    return dict(prior=(Re @ Rs, Re @ ts + te), cam_rot=cam_rot, sbi_rot=sbi_rot, n_used=len(used), avg_rounds=rounds)
+
+
+def motion_update(start, refined, velocity, dt, apply=True):
+    """Tracker::UpdateMotionModel (src/Tracker.cc:1539-1547): (v_new, velocity) from mse3StartPose and the refined pose, both (R, t)."""
+    velocity = np.asarray(velocity, dtype=np.float64)
+    if not apply:
+        return np.zeros(6), velocity.copy()
+    (Rs, ts), (Rr, tr) = start, refined
+    Rd = np.asarray(Rr) @ np.asarray(Rs).T
+    v_new = se3_ln(Rd, np.asarray(tr) - Rd @ np.asarray(ts)) / dt
+    return v_new, 0.9 * (0.5 * v_new + 0.5 * velocity)

@@ -466,7 +466,7 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
 // ---- the whole TrackMap from the table in one submission (include/mcp_img.h, mcp_track_map) --------------------------------------------
 // Replaces src/Tracker.cc:938-1075 (FindPVS of every camera, the shuffles, TestForCoarse, the coarse gate and iterations,
 // SetupFineTracking, the fine iterations).  Needs, in addition to the FindPVS members above, in class Tracker:
-//     void TrackMapOnDevice();
+//     void TrackMapOnDevice(...);      (its full declaration is with TrackFrameOnDevice below)
 //     void UploadMapSources();
 // and the patch sources of the rows: UploadMapSources() below, after UploadMapTable() (option (a); with option (b) the same call goes
 // with each row update, as mcp_map_points_update_source).  Keys: the point's address >> 4, as TrackStageOnDevice uses.  Truncated to an
@@ -510,11 +510,14 @@ void Tracker::UploadMapSources()
   }
 }
 
-void Tracker::TrackMapOnDevice()
+// With pMotion the same submission also runs the frame's pyramids (apImages / anStrides: one 8-bit image per camera, mvCurrCamNames order),
+// the tracker's SmallBlurryImages, CalcSBIRotation and ApplyMotionModel before TrackMap and UpdateMotionModel's velocity behind it
+// (mcp_track_frame_motion): see TrackFrameOnDevice below.  Without it: TrackMap alone from the pose and the pyramids as they stand.
+void Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uint8_t* const* apImages, const int* anStrides, mcp_track_motion* pMotionOut)
 {
   const int nCams = (int)mvCurrCamNames.size();
   std::vector<mcp_kf*> vKF(nCams);
-  std::vector<mcp_camera> vCams(nCams);
+  std::vector<mcp_camera> vCams(nCams), vCamsSBI(pMotion ? nCams : 0);
   std::vector<double> vCfB(12 * nCams);
   for(int c = 0; c < nCams; ++c)
   {
@@ -522,6 +525,8 @@ void Tracker::TrackMapOnDevice()
     ROS_ASSERT(kf.mpDev);
     vKF[c] = kf.mpDev;
     vCams[c] = mcptam_hip::CameraExport::Make(mmCameraModels[mvCurrCamNames[c]]);
+    if(pMotion)
+      vCamsSBI[c] = mcptam_hip::CameraExport::Make(mmCameraModelsSBI[mvCurrCamNames[c]]);      // the 40x30 camera of SE3fromSE2 (:1701)
     ToArray12(kf.mse3CamFromBase, &vCfB[12*c]);
     for(int l = 0; l < LEVELS; ++l)
       mmMeasAttemptedLevels[mvCurrCamNames[c]][l] = mmMeasFoundLevels[mvCurrCamNames[c]][l] = 0;
@@ -561,7 +566,10 @@ void Tracker::TrackMapOnDevice()
     boost::mutex::scoped_lock lock(mMap.mMutex);
     UploadMapTable();                                   // rows and their counts
     UploadMapSources();
-    if(mcp_track_map_record(mpMapTable, nCams, &vKF[0], NULL, NULL, 0, NULL, &vCams[0], adBfW, &vCfB[0], &prm, &res, &rprm, &mTrackRecord) != 0)
+    const int rc = pMotion ? mcp_track_frame_motion(mpMapTable, nCams, &vKF[0], apImages, anStrides, 0, NULL, &vCams[0], &vCamsSBI[0], adBfW, &vCfB[0], &prm, &res, &rprm,
+                                                    &mTrackRecord, pMotion, pMotionOut)
+                           : mcp_track_map_record(mpMapTable, nCams, &vKF[0], NULL, NULL, 0, NULL, &vCams[0], adBfW, &vCfB[0], &prm, &res, &rprm, &mTrackRecord);
+    if(rc != 0)
     {
       ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: "<<mcp_last_error());
       ros::shutdown();
@@ -649,6 +657,50 @@ void Tracker::TrackMapOnDevice()
   }
   ROS_ASSERT(nNum > 0);
   mpCurrentMKF->mdTotalDepthMean = dSumDepth/nNum;
+}
+
+// ---- TrackFrame's tracking branch in one submission (include/mcp_img.h, mcp_track_frame_motion) ------------------------------------------
+// Replaces, for a frame with a good map, src/Tracker.cc:303-330 (MakeKeyFrame_Lite and the SmallBlurryImages of every camera), :431-434
+// (ApplyMotionModel, TrackMap, UpdateMotionModel) with :1516-1555 and :1687-1749 behind them, and -- bRecovered, after AttemptRecovery has set
+// the pose -- :498 (TrackMap alone; the SBIs are still made and rolled, as TrackFrameSetup does every frame).  The tracker's SBIs live in the
+// map table per camera index, so mmpSBIThisFrame / mmpSBILastFrame are not kept here; Tracker::Reset calls mcp_track_motion_reset(mpMapTable).
+// The caller keeps mbActive, the timing messages and everything after UpdateMotionModel (:436 on).  Needs in class Tracker:
+//     void TrackMapOnDevice(const mcp_track_motion_params* pMotion = NULL, const uint8_t* const* apImages = NULL, const int* anStrides = NULL,
+//                           mcp_track_motion* pMotionOut = NULL);
+//     void TrackFrameOnDevice(ImageBWMap& imFrames, bool bRecovered);
+// Deviation: a process duration that is not positive is an error here (the reference divides by it).
+void Tracker::TrackFrameOnDevice(ImageBWMap& imFrames, bool bRecovered)
+{
+  const int nCams = (int)mvCurrCamNames.size();
+  std::vector<const uint8_t*> vImages(nCams);
+  std::vector<int> vStrides(nCams);
+  mcp_track_motion_params mprm;
+  std::memset(&mprm, 0, sizeof mprm);
+  mprm.apply = bRecovered ? 0 : 1;
+  mprm.use_rotation_estimator = Tracker::sbUseRotationEstimator ? 1 : 0;
+  mprm.sbi_iterations = 6;                                     // :1700
+  mprm.blur = Tracker::sdRotationEstimatorBlur;
+  mprm.dt = mLastProcessDur.toSec();
+  for(int k = 0; k < 6; ++k)
+    mprm.velocity[k] = mv6BaseVelocity[k];
+  for(int c = 0; c < nCams; ++c)
+  {
+    CVD::Image<CVD::byte>& im = imFrames[mvCurrCamNames[c]];
+    vImages[c] = im.data();
+    vStrides[c] = im.row_stride();
+    mprm.cam_good[c] = mmTrackingQuality[mvCurrCamNames[c]] == GOOD ? 1 : 0;      // :1695
+  }
+  mse3StartPose = mpCurrentMKF->mse3BaseFromWorld;              // :1518
+  mcp_track_motion motion;
+  TrackMapOnDevice(&mprm, &vImages[0], &vStrides[0], &motion);  // pose, cameras' poses, the record's bookkeeping, mdTotalDepthMean
+  if(bRecovered)
+    return;
+  for(int k = 0; k < 6; ++k)
+    mv6BaseVelocity[k] = motion.velocity[k];                    // :1547
+  // :1552-1554: the velocity scaled by the mean scene depth, which mixes in the depths of cameras that were not refreshed: host
+  Vector<6> v6 = mv6BaseVelocity;
+  v6.slice<0,3>() *= 1.0 / mpCurrentMKF->mdTotalDepthMean;
+  mdMSDScaledVelocityMagnitude = sqrt(v6*v6);
 }
 
 // AssessTrackingQuality (:1618-1658) from the record of TrackMapOnDevice: the same arithmetic ran on the device from the same counters
