@@ -665,6 +665,57 @@ int mcp_track_motion_prior_host(int ncam, const double* se2 /*ncam x 6*/, const 
                                 const mcp_track_motion_params*, mcp_track_motion* out);
 int mcp_track_motion_update_host(const double start[12], const double refined[12], const mcp_track_motion_params*, mcp_track_motion* out);
 
+/* ---- Tracker::TrackFrame's lost branch in ONE submission ------------------------------------------ src/Tracker.cc:493-502, 526-552; src/Relocaliser.cc:61-120
+ * mcp_track_frame_motion with apply = 0 whose start pose the relocaliser makes on the device: one submission on the table's stream, one wait.
+ * Per camera c, in camera order: the relocaliser's SBI of the current frame is made from level 0 of targets[c] with reloc_blur INTO THE HANDLE'S
+ * OWN SBI (mcp_kf_make_sbi's bytes; the earlier one becomes `last`; mcp_kf_get_sbi reads it afterwards); its ZMSSD is taken against every
+ * candidate with cand_cam == c (mcp_sbi_score's bits); the winner is the first smallest in list order (strict <, Relocaliser.cc:113: an exact
+ * tie goes to the lower index); the SBI is aligned against the winner for reloc_iterations rounds (mcp_sbi_iterate's bits);
+ * cam_pose[c] = SE3fromSE2(se2, cams_sbi[c], cams_sbi[c]) * cand_cam_from_world[best] (the rotation with zero translation; an se2 that is
+ * exactly the identity gives exactly the candidate's pose).
+ * THE CANDIDATE LIST is passed per call and rides in the call's one upload.  An entry that is NULL, not a live keyframe handle, or without an
+ * SBI, or that is one of this frame's targets (whose SBI this very call rewrites), is skipped: its score reads DBL_MAX (as mcp_sbi_score)
+ * and it never wins.
+ * THE CAMERA USED: the first c in order with best[c] >= 0 and align_score[c] < max_score (strict, Relocaliser.cc:84).  base_from_world =
+ * cam_from_base[cam]^-1 * cam_pose[cam] (Tracker.cc:538) replaces the pose every later kernel reads.  DEVIATION: the reference stops at the
+ * first camera that recovers and never makes the later cameras' SBIs; here every camera's SBI is made and evaluated, `cam` says which was used.
+ * EVERYTHING ELSE is mcp_track_frame_motion's with apply = 0, word for word, started from that pose: the tracker's own SBIs are made and rolled,
+ * TrackMap runs with its bookkeeping; motion->velocity returns zeros (mv6BaseVelocity = Zeros, :549).  The caller sets try_coarse and the
+ * doubled coarse caps (mbJustRecoveredSoUseCoarse).
+ * NOBODY RECOVERS (no candidate, or no alignment under max_score): the reference runs no TrackMap and neither does the device -- the PVS
+ * kernel, behind a device-side word, marks every (row, camera) outside and all later launches see empty sets; still one wait.  recovered = 0,
+ * cam = -1, base_from_world returns as given bit for bit, finder states and the count column are untouched, *record reads zeros,
+ * motion->velocity returns as given; the tracker's SBIs have rolled and the relocaliser's are made.
+ * Cameras past ncam report best = -1 and zeros.
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, no SBI rolled, outputs untouched): mcp_track_frame_motion's; motion->apply != 0; NULL
+ * recover structs; ncand < 0; NULL candidate arrays with ncand > 0; a cand_cam outside 0 .. ncam-1; a candidate pose that is not finite;
+ * reloc_blur not positive and finite; reloc_iterations < 0; max_score not finite; a live candidate on another device than the table. */
+typedef struct mcp_track_recover_params {
+  double reloc_blur;       /* SmallBlurryImage's default, 2.5 */
+  int    reloc_iterations; /* 6, Relocaliser.cc:76 */
+  double max_score;        /* Relocaliser::sdRecoveryMaxScore, 1e5; the test is strict: score < max_score */
+} mcp_track_recover_params;
+typedef struct mcp_track_recover {
+  int recovered, cam;                       /* cam = first camera index, in order, that recovered; -1 */
+  int best[MCP_MAX_FRAME_CAMS];             /* index into the candidate list; -1: no candidate of this camera had an SBI (mpBestKF == NULL) */
+  double best_zmssd[MCP_MAX_FRAME_CAMS];
+  double se2[MCP_MAX_FRAME_CAMS][6], align_score[MCP_MAX_FRAME_CAMS];   /* as mcp_sbi_iterate; zeros when best < 0 */
+  double cam_pose[MCP_MAX_FRAME_CAMS][12];  /* mse3Best of that camera; zeros when best < 0 */
+  double base_from_world[12];               /* cam_from_base[cam]^-1 * cam_pose[cam]: the pose TrackMap started from; as given when !recovered */
+} mcp_track_recover;
+int mcp_track_frame_recover(mcp_map_points*, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                            const uint8_t* const* const* masks, const mcp_camera* cams, const mcp_camera* cams_sbi, double base_from_world[12],
+                            const double* cam_from_base, const mcp_track_map_params*, mcp_track_map_result*, const mcp_track_record_params*,
+                            mcp_track_record*, const mcp_track_motion_params*, mcp_track_motion*,
+                            int ncand, mcp_kf* const* cand_kf, const int* cand_cam /* camera index 0..ncam-1 */,
+                            const double* cand_cam_from_world /* ncand x 12 */, const mcp_track_recover_params*, mcp_track_recover*,
+                            double* scores /* ncand or NULL */);
+/* host restatement of the two poses (the source k_reloc_align / k_reloc_pick run, host compiler); needs no device.  Either output may be NULL.
+ * Refusals (-1, outputs untouched): NULL se2, camera, or candidate pose; a bad camera; out_base_from_world wanted without cam_from_base; an
+ * input that is not finite. */
+int mcp_track_recover_pose_host(const double se2[6], const mcp_camera* cam_sbi, const double cam_from_world_best[12], const double cam_from_base[12],
+                                double out_cam_pose[12], double out_base_from_world[12]);
+
 /* ---- MapMakerServerBase::ReFind_Common over the table in ONE submission ---------------------------- src/MapMakerServerBase.cc:921-1080
  * ReFindInSingleKeyFrame (every point of the map against a new keyframe), ReFindNewlyMade (every new point against every keyframe) and
  * ReFindFromFailureQueue all run ReFind_Common per (keyframe, point) pair.  The caller keeps the early-outs that read its own sets (:925-937:

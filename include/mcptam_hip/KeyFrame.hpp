@@ -358,6 +358,37 @@ class MapPointTable {
                                  nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord, &motionParams, pMotion));
     if (pResult) *pResult = r;
   }
+  /// Tracker::TrackFrame's lost branch (src/Tracker.cc:493-502, 526-552; src/Relocaliser.cc:61-120) in one call: the relocaliser over the
+  /// candidate keyframes, the recovered pose, TrackMap with its bookkeeping (mcp_track_frame_recover).  vCandidates: the map's keyframes
+  /// (nullptr: skipped), vCandCams: each one's camera index among vTargets, vCandPoses: each one's CamFromWorld, 12 doubles per entry;
+  /// motionParams.apply must be 0.  pRecover->recovered says whether TrackMap ran; pScores (nullptr: not wanted) gets one ZMSSD per entry.
+  void TrackFrameRecover(const std::vector<KeyFrame*>& vTargets, const std::vector<const uint8_t*>& vImages, const std::vector<int>& vStrides, bool bImagesOnDevice,
+                         const std::vector<mcp_camera>& vCams, const std::vector<mcp_camera>& vCamsSBI, double base_from_world[12], const std::vector<double>& vCamFromBase,
+                         const mcp_track_map_params& params, const mcp_track_record_params& recParams, const mcp_track_motion_params& motionParams,
+                         const std::vector<KeyFrame*>& vCandidates, const std::vector<int>& vCandCams, const std::vector<double>& vCandPoses,
+                         const mcp_track_recover_params& recoverParams, mcp_track_map_result* pResult, mcp_track_record* pRecord, mcp_track_motion* pMotion,
+                         mcp_track_recover* pRecover, std::vector<double>* pScores = nullptr) {
+    const int nc = (int)vTargets.size(), nk = (int)vCandidates.size();
+    if ((int)vCams.size() != nc || (int)vCamsSBI.size() != nc || (int)vCamFromBase.size() != 12*nc || (int)vCandCams.size() != nk || (int)vCandPoses.size() != 12*nk ||
+        (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !pRecord || !pMotion || !pRecover)
+      throw std::invalid_argument("MapPointTable::TrackFrameRecover: array sizes");
+    std::vector<mcp_kf*> h(nc), hk(nk > 0 ? nk : 1);
+    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    for (int i = 0; i < nk; ++i) hk[i] = vCandidates[i] ? vCandidates[i]->handle() : nullptr;
+    if (pScores) pScores->assign(nk, 0.0);
+    mcp_track_map_result r;
+    check(mcp_track_frame_recover(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
+                                  nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord, &motionParams, pMotion,
+                                  nk, hk.data(), nk ? vCandCams.data() : nullptr, nk ? vCandPoses.data() : nullptr, &recoverParams, pRecover,
+                                  pScores && nk ? pScores->data() : nullptr));
+    if (pResult) *pResult = r;
+  }
+  /// the two poses of a recovery on the host (mcp_track_recover_pose_host; needs no device): cam_pose = SE3fromSE2(se2) * cam_from_world_best,
+  /// base_from_world = cam_from_base^-1 * cam_pose
+  static void RecoverPoseHost(const double se2[6], const mcp_camera& camSBI, const double cam_from_world_best[12], const double cam_from_base[12], double cam_pose[12],
+                              double base_from_world[12]) {
+    check(mcp_track_recover_pose_host(se2, &camSBI, cam_from_world_best, cam_from_base, cam_pose, base_from_world));
+  }
   /// Tracker::Reset: every camera index forgets its SmallBlurryImages
   void MotionReset() { check(mcp_track_motion_reset(mpDev)); }
   /// the tracker's SBI of camera index nCam (nWhich 0: this frame's, 1: last frame's): 1200 bytes, 1200 floats, 2400 floats; nullptr: not wanted

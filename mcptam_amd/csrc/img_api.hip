@@ -24,6 +24,7 @@
 #include "refind_kernels.h"
 #include "track_record_kernels.h"
 #include "track_motion_kernels.h"
+#include "track_recover_kernels.h"
 #include "ba_bridge.h"
 #include "ba_select.h"
 
@@ -1161,6 +1162,16 @@ struct mcp_map_points {
     int reserve() { return (sets.alloc(2*MCP_MAX_FRAME_CAMS) || d_tabs.alloc(MCP_MAX_FRAME_CAMS) || h_tabs.alloc(MCP_MAX_FRAME_CAMS) || se2.alloc(8*MCP_MAX_FRAME_CAMS) || h_out.alloc(1)) ? -1 : 0; }
     void reset() { for (bool& h : have) h = false; }
   } mo;
+  // mcp_track_frame_recover: the relocaliser's SBI tables (blur 2.5; uploaded when they change), the candidates' scores (device | pinned, when
+  // the caller wants them), what k_reloc_align leaves per camera, the word that gates the PVS and the pinned report
+  struct Rc {
+    Buf<SbiTables> d_tabs; PinBuf<SbiTables> h_tabs; std::vector<SbiTables> tabs_last;
+    Buf<double> scores; PinBuf<double> h_scores; Buf<RelocCamOut> cam_out; Buf<int> gate; PinBuf<mcp_track_recover> h_out;
+    int reserve(int ncand, bool want_scores) {
+      return (d_tabs.alloc(MCP_MAX_FRAME_CAMS) || h_tabs.alloc(MCP_MAX_FRAME_CAMS) || scores.alloc((size_t)std::max(ncand, 1)) || (want_scores && h_scores.alloc((size_t)std::max(ncand, 1))) ||
+              cam_out.alloc(MCP_MAX_FRAME_CAMS) || gate.alloc(1) || h_out.alloc(1)) ? -1 : 0;
+    }
+  } rc;
   // mcp_map_refind: the packed inputs (pinned | device), the passes' scratch, the pinned results (RfOut | verdict bytes | measurements)
   struct Rf {
     PinBuf<char> in; Buf<char> dev; Buf<uint8_t> flags, vd; Buf<int> blk, first; Buf<RfItem> items; Buf<mcp_refind_meas> cand; PinBuf<char> out;
@@ -1394,9 +1405,10 @@ static size_t pvs_layout(int ncam, const int* caps, int n, PvsLayout* Y) {
 // FindPVS of the table's n > 0 rows, enqueued on its stream (m->pvs.reserve has been called): the lists, laid out as Y says, and the counts
 // per (camera, level) go to `lists` and `counts`, pinned or device memory.  The launches' errors are the caller's to collect (and to answer
 // with tab_last.clear()).
-// d_bfw != NULL: the pose is read from there (12 doubles in device memory, left by an earlier kernel of the stream) instead of bfw.
+// d_bfw != NULL: the pose is read from there (12 doubles in device memory, left by an earlier kernel of the stream) instead of bfw;
+// d_gate != NULL (with d_bfw): the marking pass runs behind that device-side word (k_pvs_mark_gated).
 static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double* cfb, const double* bfw, const PvsLayout& Y,
-                       mcp_pvs_entry* lists, int* counts, const double* d_bfw = nullptr) {
+                       mcp_pvs_entry* lists, int* counts, const double* d_bfw = nullptr, const int* d_gate = nullptr) {
   const int n = m->rows, nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
   std::vector<PvsCam> tab(ncam);
   for (int c = 0; c < ncam; ++c) {
@@ -1413,7 +1425,8 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
     ICK(hipMemcpyAsync(V.d_tab.p, V.h_tab.p, sizeof(PvsCam)*tab.size(), hipMemcpyHostToDevice, m->st));
     V.tab_last = tab;
   }
-  if (d_bfw) hipLaunchKernelGGL(k_pvs_mark_at, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
+  if (d_bfw && d_gate) hipLaunchKernelGGL(k_pvs_mark_gated, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, d_gate, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
+  else if (d_bfw) hipLaunchKernelGGL(k_pvs_mark_at, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
   else hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
   hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, n, nblk, (const signed char*)V.lvl.p,
                      (const mcp_pvs_entry*)V.ent.p, (const int*)V.blk_cnt.p, lists, counts);
@@ -1543,12 +1556,43 @@ static int motion_check(const std::string& who, int ncam, const mcp_camera* cams
   return 0;
 }
 
-// the body of mcp_track_map (rp == NULL: exactly its launches), of mcp_track_map_record (rp, rec checked by the caller) and of
+// what mcp_track_frame_recover adds to that: the candidate list, the relocaliser's parameters, its report and the scores
+struct RecoverArg {
+  int ncand; mcp_kf* const* kf; const int* cam; const double* cfw; const mcp_track_recover_params* p; mcp_track_recover* out; double* scores;
+};
+// its refusals; live[i]: candidate i is a live keyframe handle with an SBI that is none of the frame's targets (the others are skipped)
+static int recover_check(const std::string& who, const mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_track_motion_params* mp, const RecoverArg& rc,
+                         std::vector<uint8_t>& live) {
+  if (!rc.p || !rc.out) return img_fail(who + ": NULL recover parameters or recover result");
+  if (mp->apply) return img_fail(who + ": the motion model is not applied on a recovery frame (motion apply must be 0)");
+  if (rc.ncand < 0) return img_fail(who + ": negative candidate count");
+  if (rc.ncand > 0 && (!rc.kf || !rc.cam || !rc.cfw)) return img_fail(who + ": NULL candidate arrays");
+  if (!(rc.p->reloc_blur > 0) || !std::isfinite(rc.p->reloc_blur)) return img_fail(who + ": reloc_blur must be positive");
+  if (rc.p->reloc_iterations < 0) return img_fail(who + ": negative relocaliser iteration count");
+  if (!std::isfinite(rc.p->max_score)) return img_fail(who + ": max_score is not finite");
+  live.assign((size_t)rc.ncand, 0);
+  std::lock_guard<std::mutex> g(g_kf_mu);
+  for (int i = 0; i < rc.ncand; ++i) {
+    if (rc.cam[i] < 0 || rc.cam[i] >= ncam) return img_fail(who + ": candidate " + std::to_string(i) + " names a camera out of range");
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(rc.cfw[12*(size_t)i + k])) return img_fail(who + ": candidate " + std::to_string(i) + "'s pose is not finite");
+    if (!rc.kf[i] || g_kf_live.find(rc.kf[i]) == g_kf_live.end()) continue;
+    if (rc.kf[i]->device != m->device) return img_fail(who + ": candidate " + std::to_string(i) + " lives on another device than the table");
+    bool is_target = false;      // (a target's SBI is the one this call rewrites: it is no keyframe of the map)
+    for (int c = 0; c < ncam; ++c) is_target = is_target || rc.kf[i] == targets[c];
+    live[i] = (rc.kf[i]->has_sbi && !is_target) ? 1 : 0;
+  }
+  return 0;
+}
+
+// the body of mcp_track_map (rp == NULL: exactly its launches), of mcp_track_map_record (rp, rec checked by the caller), of
 // mcp_track_frame_motion (mo: k_frame_sbi and k_motion_prior between the pyramids' event and the PVS, which then reads the pose from the
-// parameter block, and k_motion_update behind the fine iterations; mo == NULL: no launch more or less than before)
+// parameter block, and k_motion_update behind the fine iterations; mo == NULL: no launch more or less than before) and of
+// mcp_track_frame_recover (rc, with mo: the four relocaliser kernels in front of k_frame_sbi -- k_reloc_pick leaves the recovered pose in the
+// parameter block before k_motion_prior reads it as the start -- and the PVS behind their gate; rc == NULL: no launch more or less than before)
 static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                          const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
-                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec, const MotionArg* mo = nullptr) {
+                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec, const MotionArg* mo = nullptr,
+                         const RecoverArg* rc = nullptr) {
   if (!m) return img_fail(who + ": NULL table");
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail(who + ": bad arguments");
   if (prm->coarse_max < 0 || prm->coarse_range < 0 || prm->coarse_min < 0 || prm->coarse_subpix_its < 0 || prm->max_patches < 0)
@@ -1561,6 +1605,9 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
     if (mo && !imgs && !targets[c]->has_image) return img_fail(who + ": camera " + std::to_string(c) + "'s target holds no frame and no images were given");
   }
   if (mo && motion_check(who, ncam, mo->cams_sbi, mo->p, mo->out)) return -1;
+  std::vector<uint8_t> cand_live;
+  if (rc && recover_check(who, m, ncam, targets, mo->p, *rc, cand_live)) return -1;
+  const int ncand = rc ? rc->ncand : 0;
   ICK(hipSetDevice(m->device));
   // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
   m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate();
@@ -1582,9 +1629,18 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   // (param block: cameras' search table | camera models | CamFromBase | BaseFromWorld + mu | override sigma x 2 | nonlinear flags x 2)
   const size_t o_tab = 0, o_cam = tm_align(sizeof(TmCam)*(size_t)ncam), o_cfb = o_cam + tm_align(sizeof(mcp_camera)*(size_t)ncam), o_pm = o_cfb + tm_align(96*(size_t)ncam);
   const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), o_cs = o_nl + tm_align(20);      // (| the SBI cameras, with a motion model)
-  const size_t blk = o_cs + (mo ? tm_align(sizeof(mcp_camera)*(size_t)ncam) : 0);
+  const size_t o_rc = o_cs + (mo ? tm_align(sizeof(mcp_camera)*(size_t)ncam) : 0);                            // (| the candidate list, on a recovery frame)
+  const size_t blk = o_rc + (rc ? tm_align(sizeof(RelocCand)*(size_t)std::max(ncand, 1)) : 0);
   if (m->tm.blk.alloc(blk) || m->tm.h_blk.alloc(blk)) return -1;
   if (mo && m->mo.reserve()) return -1;
+  if (rc) {
+    if (m->rc.reserve(ncand, rc->scores != nullptr)) return -1;
+    for (int c = 0; c < ncam; ++c) {      // both SBIs of every target handle, so that the roll below is a pointer swap
+      mcp_kf* k = targets[c];
+      if (k->sbi_small.alloc(SBI_N) || k->sbi_templ.alloc(SBI_N) || k->sbi_jacs.alloc(2*SBI_N) || k->sbi_last_small.alloc(SBI_N) || k->sbi_last_templ.alloc(SBI_N) ||
+          k->sbi_last_jacs.alloc(2*SBI_N)) return -1;
+    }
+  }
   const size_t n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK;
   if (rp) {
     if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
@@ -1609,6 +1665,26 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   std::memcpy(hb + o_cfb, cfb, 96*(size_t)ncam);
   std::memcpy(hb + o_pm, bfw, 96);
   if (mo) std::memcpy(hb + o_cs, mo->cams_sbi, sizeof(mcp_camera)*(size_t)ncam);
+  RelocMakeArgs rma; RelocCurArgs rca;
+  if (rc) {
+    // the relocaliser's SBI of every camera goes into the target handle's own (mcp_kf_make_sbi's roll: the one before becomes `last`), in
+    // camera order
+    std::memset(&rma, 0, sizeof rma); std::memset(&rca, 0, sizeof rca);
+    for (int c = 0; c < ncam; ++c) {
+      mcp_kf* k = targets[c];
+      if (k->has_sbi) { k->sbi_last_small.swap(k->sbi_small); k->sbi_last_templ.swap(k->sbi_templ); k->sbi_last_jacs.swap(k->sbi_jacs); k->has_last_sbi = true; }
+      k->has_sbi = true;
+      const Level& L0 = k->lev[0];
+      rma.c[c] = RelocMakeCam{L0.img.p, L0.w, L0.h, k->sbi_small.p, k->sbi_templ.p, k->sbi_jacs.p};
+      rca.templ[c] = k->sbi_templ.p;
+    }
+    RelocCand* cd = reinterpret_cast<RelocCand*>(hb + o_rc);
+    for (int i = 0; i < ncand; ++i) {
+      cd[i].templ = cand_live[i] ? rc->kf[i]->sbi_templ.p : nullptr; cd[i].jacs = cand_live[i] ? rc->kf[i]->sbi_jacs.p : nullptr;
+      cd[i].cam = rc->cam[i]; cd[i].pad = 0;
+      std::memcpy(cd[i].cfw, rc->cfw + 12*(size_t)i, 96);
+    }
+  }
   double* ov = reinterpret_cast<double*>(hb + o_ov); uint8_t* nl = hb + o_nl;
   for (int i = 0; i < 10; ++i) {
     ov[i] = i < 6 ? 0.0 : 1.0; nl[i] = 1;                                                 // coarse, Tracker.cc:1012-1020
@@ -1622,6 +1698,28 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   ICK(hipMemcpyAsync(m->tm.slots.p, m->tm.h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
   double* d_pm = reinterpret_cast<double*>(m->tm.blk.p + o_pm);
   const double* d_cfb = reinterpret_cast<const double*>(m->tm.blk.p + o_cfb);
+  if (rc) {
+    // 0a. the relocaliser: every camera's SBI, the candidates' scores, the winner's alignment and pose per camera, the recovered pose into
+    // the pose slot and the gate word
+    mcp_map_points::Rc& R = m->rc;
+    const mcp_track_recover_params& q = *rc->p;
+    std::vector<SbiTables> tabs(ncam);
+    for (int c = 0; c < ncam; ++c) sbi_tables(rma.c[c].w, rma.c[c].h, q.reloc_blur, tabs[c]);
+    if (R.tabs_last.size() != tabs.size() || std::memcmp(R.tabs_last.data(), tabs.data(), sizeof(SbiTables)*tabs.size()) != 0) {
+      std::memcpy(R.h_tabs.p, tabs.data(), sizeof(SbiTables)*tabs.size());
+      ICK(hipMemcpyAsync(R.d_tabs.p, R.h_tabs.p, sizeof(SbiTables)*tabs.size(), hipMemcpyHostToDevice, st));
+      R.tabs_last = tabs;
+    }
+    std::memset(R.h_out.p, 0, sizeof(mcp_track_recover));
+    const RelocCand* d_cand = reinterpret_cast<const RelocCand*>(m->tm.blk.p + o_rc);
+    hipLaunchKernelGGL(k_reloc_make, dim3(ncam), dim3(256), 0, st, rma, (const SbiTables*)R.d_tabs.p);
+    if (ncand > 0) hipLaunchKernelGGL(k_reloc_score, dim3((ncand + RELOC_TILE - 1)/RELOC_TILE), dim3(RELOC_TILE), 0, st, ncand, ncam, d_cand, rca, R.scores.p,
+                                      rc->scores ? R.h_scores.p : (double*)nullptr);
+    hipLaunchKernelGGL(k_reloc_align, dim3(ncam), dim3(256), 0, st, ncand, d_cand, (const double*)R.scores.p, rca, reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cs),
+                       q.reloc_iterations, R.cam_out.p);
+    hipLaunchKernelGGL(k_reloc_pick, dim3(1), dim3(64), 0, st, ncam, (const RelocCamOut*)R.cam_out.p, d_cfb, q.max_score, d_pm, R.gate.p, R.h_out.p);
+    ICK(hipGetLastError());
+  }
   if (mo) {
     // 0. the motion model: this frame's SBI of every camera (the one before becomes last frame's), its alignment, the prior into the pose slot
     mcp_map_points::Mo& M = m->mo;
@@ -1653,7 +1751,7 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   PvsLayout Y;
   pvs_layout(ncam, nullptr, n, &Y);
   if (n > 0) {
-    if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? d_pm : nullptr)) return -1;
+    if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? d_pm : nullptr, rc ? m->rc.gate.p : nullptr)) return -1;
   } else ICK(hipMemsetAsync(m->tm.counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
   // 2. the sets
   TmParams P; P.ncam = ncam; P.rows = n; P.try_coarse = prm->try_coarse ? 1 : 0; P.coarse_max = prm->coarse_max; P.coarse_range = prm->coarse_range;
@@ -1733,8 +1831,17 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   }
   m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
   std::memcpy(res->mu_last, R.mu, 48);
-  std::memcpy(bfw, R.pose, 96);
   if (mo) *mo->out = *m->mo.h_out.p;
+  if (rc) {
+    *rc->out = *m->rc.h_out.p;
+    if (rc->scores && ncand > 0) std::memcpy(rc->scores, m->rc.h_scores.p, sizeof(double)*(size_t)ncand);
+    if (rc->out->recovered) std::memset(mo->out->velocity, 0, sizeof mo->out->velocity);      // mv6BaseVelocity = Zeros, Tracker.cc:549
+    else {      // no TrackMap ran: the pose as given (bfw has not been written yet), no bookkeeping
+      std::memset(rec, 0, sizeof *rec);
+      return 0;
+    }
+  }
+  std::memcpy(bfw, R.pose, 96);
   return 0;
 }
 
@@ -1763,6 +1870,35 @@ int mcp_track_frame_motion(mcp_map_points* m, int ncam, mcp_kf* const* targets, 
   if (!mp || !out) return img_fail("mcp_track_frame_motion: NULL motion parameters or motion result");
   const MotionArg mo{cams_sbi, mp, out};
   return track_map_run("mcp_track_frame_motion", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec, &mo);
+}
+
+int mcp_track_frame_recover(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
+                            const uint8_t* const* const* masks, const mcp_camera* cams, const mcp_camera* cams_sbi, double bfw[12], const double* cfb,
+                            const mcp_track_map_params* prm, mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec,
+                            const mcp_track_motion_params* mp, mcp_track_motion* out, int ncand, mcp_kf* const* cand_kf, const int* cand_cam,
+                            const double* cand_cfw, const mcp_track_recover_params* rprm, mcp_track_recover* rout, double* scores) {
+  if (!m) return img_fail("mcp_track_frame_recover: NULL table");
+  if (!rp || !rec) return img_fail("mcp_track_frame_recover: NULL record parameters or record");
+  if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_frame_recover: a quality threshold is not finite");
+  if (!mp || !out) return img_fail("mcp_track_frame_recover: NULL motion parameters or motion result");
+  if (!rprm || !rout) return img_fail("mcp_track_frame_recover: NULL recover parameters or recover result");
+  const MotionArg mo{cams_sbi, mp, out};
+  const RecoverArg rc{ncand, cand_kf, cand_cam, cand_cfw, rprm, rout, scores};
+  return track_map_run("mcp_track_frame_recover", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec, &mo, &rc);
+}
+
+int mcp_track_recover_pose_host(const double se2[6], const mcp_camera* cam_sbi, const double cfw_best[12], const double cfb[12], double out_cam_pose[12],
+                                double out_bfw[12]) {
+  if (!se2 || !cfw_best) return img_fail("mcp_track_recover_pose_host: NULL alignment or candidate pose");
+  if (!cam_sbi || !cam_ok(cam_sbi)) return img_fail("mcp_track_recover_pose_host: NULL or bad SBI camera");
+  if (out_bfw && !cfb) return img_fail("mcp_track_recover_pose_host: base_from_world wanted without CamFromBase");
+  if (!finite6(se2)) return img_fail("mcp_track_recover_pose_host: the alignment is not finite");
+  for (int k = 0; k < 12; ++k) if (!std::isfinite(cfw_best[k]) || (cfb && !std::isfinite(cfb[k]))) return img_fail("mcp_track_recover_pose_host: a pose is not finite");
+  double pose[12];
+  recover_cam_pose(se2, cam_sbi, cfw_best, pose);
+  if (out_bfw) recover_base_pose(cfb, pose, out_bfw);
+  if (out_cam_pose) std::memcpy(out_cam_pose, pose, sizeof pose);
+  return 0;
 }
 
 int mcp_track_motion_reset(mcp_map_points* m) {

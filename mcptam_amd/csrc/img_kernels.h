@@ -1049,6 +1049,10 @@ k_sbi_make(const uint8_t* __restrict__ img, int iw, int ih, SbiTables tb, uint8_
   sbi_make_body(img, iw, ih, tb, small_out, templ_out, jacs_out, A, B, red);
 }
 
+// SmallBlurryImage::ZMSSD's statement per element (:122-134): the float difference, squared and added in double.  k_sbi_score and
+// k_reloc_score (track_recover_kernels.h) both add with this one, in raster order, so their scores carry the same bits
+__device__ __forceinline__ void sbi_zmssd_step(double& ssd, float mine, float other) { const double d = mine - other; ssd += d*d; }
+
 // one thread per candidate keyframe, raster-order double accumulation exactly as the scalar loop (so scores, and with them
 // the "first smallest" winner, are bit-identical); the 1200-float templates are a few kB each
 __global__ void __launch_bounds__(64)
@@ -1058,7 +1062,7 @@ k_sbi_score(const float* __restrict__ cur, const float* const* __restrict__ cand
   const float* o = cands[i];
   if (!o) { scores[i] = 1.7976931348623157e308; return; }
   double ssd = 0.0;
-  for (int p = 0; p < SBI_N; ++p) { const double d = cur[p] - o[p]; ssd += d*d; }
+  for (int p = 0; p < SBI_N; ++p) sbi_zmssd_step(ssd, cur[p], o[p]);
   scores[i] = ssd;
 }
 

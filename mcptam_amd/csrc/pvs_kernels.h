@@ -1,6 +1,6 @@
 // pvs_kernels.h -- Tracker::FindPVS over a device-resident map-point table (src/Tracker.cc:662-723), gfx950.
 //
-// One thread per (row, camera).  k_pvs_mark (k_pvs_mark_at: the same body with the pose read from device memory) runs the per-point part of FindPVS -- TrackerData::Project, the level-0 mask test,
+// One thread per (row, camera).  k_pvs_mark (k_pvs_mark_at: the same body with the pose read from device memory; k_pvs_mark_gated: that behind a device-side word) runs the per-point part of FindPVS -- TrackerData::Project, the level-0 mask test,
 // GetDerivsUnsafe, PatchFinder::CalcSearchLevelAndWarpMatrix -- through the same __device__ helpers the per-point search uses
 // (track_project / track_warp_level, img_kernels.h), so the results carry the search's bits; it leaves every accepted entry in a
 // (camera, row) slot and the per-workgroup counts of each level.  k_pvs_scatter (same stream, next launch) sums the counts of the
@@ -66,6 +66,26 @@ __global__ void __launch_bounds__(PVS_BLOCK)
 k_pvs_mark_at(const PvsCam* __restrict__ tab, const double* __restrict__ bfw12, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl,
               mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt) {
   __shared__ int cnt[MCP_LEVELS];
+  Se3 bfw;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) bfw.R[k] = bfw12[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) bfw.t[k] = bfw12[9 + k];
+  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt);
+}
+// k_pvs_mark_at behind a device-side word an earlier kernel of the stream left (mcp_track_frame_recover: k_reloc_pick).  *gate == 0: nobody
+// recovered, the reference runs no TrackMap -- every (row, camera) is marked outside and every count is zero, the empty-PVS case for all
+// later launches.  *gate != 0: k_pvs_mark_at's pass, the same body
+__global__ void __launch_bounds__(PVS_BLOCK)
+k_pvs_mark_gated(const int* __restrict__ gate, const PvsCam* __restrict__ tab, const double* __restrict__ bfw12, const PvsPoint* __restrict__ pts, int n, int nblk,
+                 signed char* __restrict__ lvl, mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt) {
+  __shared__ int cnt[MCP_LEVELS];
+  if (*gate == 0) {      // (uniform over the grid)
+    const int c = blockIdx.y, i = blockIdx.x*PVS_BLOCK + threadIdx.x;
+    if (i < n) lvl[(size_t)c*n + i] = (signed char)-1;
+    if (threadIdx.x < MCP_LEVELS) blk_cnt[((size_t)c*nblk + blockIdx.x)*MCP_LEVELS + threadIdx.x] = 0;
+    return;
+  }
   Se3 bfw;
 #pragma unroll
   for (int k = 0; k < 9; ++k) bfw.R[k] = bfw12[k];

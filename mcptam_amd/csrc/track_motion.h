@@ -2,7 +2,8 @@
 //
 // One source for the device (k_motion_prior / k_motion_update, track_motion_kernels.h) and for the host entries
 // (mcp_sbi_se3_from_se2, mcp_track_motion_prior_host, mcp_track_motion_update_host): SmallBlurryImage::SE3fromSE2, SO3 / SE3
-// logarithms, Tracker::FindAverageRotation, ApplyMotionModel's prior and UpdateMotionModel's velocity.  Plain C++ in double;
+// logarithms, Tracker::FindAverageRotation, ApplyMotionModel's prior and UpdateMotionModel's velocity; and the relocaliser's poses
+// (k_reloc_align / k_reloc_pick, track_recover_kernels.h; mcp_track_recover_pose_host).  Plain C++ in double;
 // host and device differ only in their math libraries (sin, cos, asin, acos).
 #pragma once
 #include "ba_device.h"
@@ -175,6 +176,32 @@ __host__ __device__ inline void motion_update(const double* start12, const doubl
   se3_compose(Rf, Si, D);
   double v[6]; se3_ln(D, v);
   for (int k = 0; k < 6; ++k) { v_new[k] = v[k]/p.dt; velocity[k] = (0.5*v_new[k] + 0.5*p.velocity[k])*0.9; }
+}
+
+// Relocaliser::AttemptRecovery's pose (src/Relocaliser.cc:80-82): mse3Best = SE3fromSE2(se2, cam, cam) * CamFromWorld of the best keyframe,
+// the rotation with zero translation, both cameras the 40x30 one of the current camera (ScoreKFs looks at keyframes of that camera only).
+// An SE2 that is exactly the identity gives exactly the keyframe's pose.
+__host__ __device__ inline void recover_cam_pose(const double* se2, const mcp_camera* cam_sbi, const double* cfw_best12, double* cam_pose12) {
+  if (se2[0] == 1.0 && se2[1] == 0.0 && se2[2] == 0.0 && se2[3] == 1.0 && se2[4] == 0.0 && se2[5] == 0.0) {
+    for (int k = 0; k < 12; ++k) cam_pose12[k] = cfw_best12[k];
+    return;
+  }
+  Se3 Rr, K, P;
+  sbi_se3_from_se2(se2, cam_sbi, cam_sbi, Rr.R);
+  Rr.t[0] = Rr.t[1] = Rr.t[2] = 0.0;
+  se3_of12_hd(cfw_best12, K); se3_compose(Rr, K, P);
+  se3_to12_hd(P, cam_pose12);
+}
+
+// Tracker::AttemptRecovery's base pose (src/Tracker.cc:538): mse3CamFromBase.inverse() * se3Best
+__host__ __device__ inline void recover_base_pose(const double* cfb12, const double* cam_pose12, double* bfw12) {
+  Se3 C, Ci, P, B;
+  se3_of12_hd(cfb12, C); se3_of12_hd(cam_pose12, P);
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Ci.R[3*i + j] = C.R[3*j + i];
+  double rt[3]; mat3t_vec(C.R, C.t, rt);
+  Ci.t[0] = -rt[0]; Ci.t[1] = -rt[1]; Ci.t[2] = -rt[2];
+  se3_compose(Ci, P, B);
+  se3_to12_hd(B, bfw12);
 }
 
 }  // namespace mcp

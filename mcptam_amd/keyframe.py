@@ -52,6 +52,7 @@ IMG_SYMBOLS = [
     "mcp_map_points_set_counts", "mcp_map_points_update_counts", "mcp_map_points_get_counts", "mcp_track_map_record", "mcp_track_map_notes_view",
     "mcp_track_map_meas_view",
     "mcp_track_frame_motion", "mcp_track_motion_reset", "mcp_track_motion_get_sbi", "mcp_track_motion_prior_host", "mcp_track_motion_update_host",
+    "mcp_track_frame_recover", "mcp_track_recover_pose_host",
 ]
 _BOUND = False
 

@@ -4,7 +4,9 @@ mcp_track_find_pvs, mcp_track_map).  The table holds, per row, what FindPVS read
 whole TrackMap of a frame from the table; track_map_record also leaves its bookkeeping (marks into the table's count column, level counters,
 quality, found measurements, scene depth), with track_record_restate / tracking_quality as the numpy restatements.  track_frame_motion is
 track_map_record started from the pose the tracker's motion model gives on the device (SmallBlurryImage rotation estimate, velocity), with
-so3_ln / se3_ln / average_rotation / motion_prior / motion_update as the numpy restatements."""
+so3_ln / se3_ln / average_rotation / motion_prior / motion_update as the numpy restatements.  track_frame_recover is the lost branch: the
+relocaliser (SmallBlurryImage scores over a candidate list, alignment against the winner, the recovered pose) on the device in front of the
+same frame, with recover_restate as the numpy restatement."""
 import ctypes
 import math
 
@@ -373,6 +375,41 @@ class MapPointTable:
         notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
         meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
         return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec, mo
+
+    # ---- TrackFrame's lost branch: relocaliser + TrackMap + its bookkeeping (include/mcp_img.h mcp_track_frame_recover) ----
+    def track_frame_recover(self, targets, cams, cams_sbi, base_from_world, cams_from_base, cand_kfs, cand_cams, cand_poses, reloc_blur=2.5,
+                            reloc_iterations=6, max_score=1e5, want_scores=True, velocity=None, use_rotation_estimator=True, sbi_iterations=6, blur=0.75,
+                            lost=True, want_items=True, min_patches=10, quality_coarse_min=20, quality_good=0.3, quality_bad=0.13, try_coarse=True, coarse_max=60,
+                            coarse_range=30, coarse_min=20, coarse_subpix_its=8, max_patches=1000, estimator="Tukey", seed=0, imgs=None, on_device=False,
+                            strides=None, copy=True):
+        """mcp_track_frame_recover: Tracker::AttemptRecovery with the relocaliser, then TrackMap with its bookkeeping from the recovered pose, in
+        one call.  cand_kfs: the map's keyframes (KeyFrame, None, or a raw handle value), cand_cams: each one's camera index among the
+        targets, cand_poses: each one's CamFromWorld ((R, t) pairs or an (n, 12) array).  The caller sets try_coarse and the doubled coarse
+        caps.  Returns track_frame_motion's tuple plus the TrackRecover report and the scores (None with want_scores=False)."""
+        L = _bind_track_recover(_bind_track_motion(_bind_track_record(_bind_track_map(self._L))))
+        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
+        css = cams_sbi if isinstance(cams_sbi, ctypes.Array) else camera_array(cams_sbi)
+        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
+                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
+        rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
+        mp = motion_params(velocity, 1.0, None, False, use_rotation_estimator, sbi_iterations, blur, ncam)
+        ncand, ch, cc, cp = _candidate_args(cand_kfs, cand_cams, cand_poses)
+        rq = TrackRecoverParams(float(reloc_blur), int(reloc_iterations), float(max_score))
+        res, rec, mo, rv = TrackMapResult(), TrackRecord(), TrackMotion(), TrackRecover()
+        scores = np.zeros(max(ncand, 1)) if want_scores else None
+        _chk(L.mcp_track_frame_recover(self._h, ncam, hs, ip, st, int(on_device), None, cs, ctypes.cast(css, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
+                                       ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec), ctypes.byref(mp), ctypes.byref(mo),
+                                       ncand, ctypes.cast(ch, ctypes.c_void_p), cc.ctypes.data, cp.ctypes.data, ctypes.byref(rq), ctypes.byref(rv),
+                                       scores.ctypes.data if want_scores else None), "track_frame_recover")
+        del keep
+
+        def views(fn, dtype, expect):
+            text = "track_frame_recover: view of camera %d has %%(got)d entries, the record says %%(expect)d: "
+            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
+        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
+        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
+        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
+        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec, mo, rv, (scores[:ncand] if want_scores else None)
 
     def motion_reset(self):
         """Tracker::Reset: every camera index forgets its SmallBlurryImages."""
@@ -888,3 +925,99 @@ def motion_update(start, refined, velocity, dt, apply=True):
     Rd = np.asarray(Rr) @ np.asarray(Rs).T
     v_new = se3_ln(Rd, np.asarray(tr) - Rd @ np.asarray(ts)) / dt
     return v_new, 0.9 * (0.5 * v_new + 0.5 * velocity)
+
+
+# ---- the lost branch: relocaliser + recovered pose (include/mcp_img.h mcp_track_frame_recover) and its numpy restatement ------------------
+TRACK_RECOVER_SYMBOLS = ["mcp_track_frame_recover", "mcp_track_recover_pose_host"]
+SCORE_SKIPPED = float(np.finfo(np.float64).max)      # DBL_MAX: the score of a skipped candidate, as mcp_sbi_score
+
+
+class TrackRecoverParams(ctypes.Structure):
+    _fields_ = [("reloc_blur", ctypes.c_double), ("reloc_iterations", ctypes.c_int), ("max_score", ctypes.c_double)]
+
+
+class TrackRecover(ctypes.Structure):
+    _fields_ = [("recovered", ctypes.c_int), ("cam", ctypes.c_int), ("best", ctypes.c_int * MAX_FRAME_CAMS), ("best_zmssd", ctypes.c_double * MAX_FRAME_CAMS),
+                ("se2", (ctypes.c_double * 6) * MAX_FRAME_CAMS), ("align_score", ctypes.c_double * MAX_FRAME_CAMS),
+                ("cam_pose", (ctypes.c_double * 12) * MAX_FRAME_CAMS), ("base_from_world", ctypes.c_double * 12)]
+
+
+def _bind_track_recover(L):
+    if getattr(L, "_track_recover_bound", False):
+        return L
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.mcp_track_frame_recover.argtypes = [vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]
+    L.mcp_track_recover_pose_host.argtypes = [vp, vp, vp, vp, vp, vp]
+    L._track_recover_bound = True
+    return L
+
+
+def _candidate_args(cand_kfs, cand_cams, cand_poses):
+    """(ncand, handle array, camera indices int32, poses (ncand, 12) float64) of a candidate list; a keyframe may be a KeyFrame, None or a raw
+    handle value."""
+    n = len(cand_kfs)
+    hs = (ctypes.c_void_p * max(n, 1))(*[k if k is None or isinstance(k, int) else k._h for k in cand_kfs])
+    cc = np.ascontiguousarray(cand_cams, dtype=np.int32).reshape(-1)
+    cp = cand_poses if isinstance(cand_poses, np.ndarray) else np.array([_pose12(*q) for q in cand_poses], dtype=np.float64).reshape(-1, 12)
+    cp = np.ascontiguousarray(cp, dtype=np.float64).reshape(-1, 12)
+    if len(cc) != n or len(cp) != n:
+        raise ValueError("candidate list: %d keyframes, %d camera indices, %d poses" % (n, len(cc), len(cp)))
+    if n == 0:
+        cc, cp = np.zeros(1, dtype=np.int32), np.zeros((1, 12))
+    return n, hs, cc, cp
+
+
+def recover_pose_host(se2, cam_sbi, cam_from_world_best, cam_from_base):
+    """mcp_track_recover_pose_host: se2 = 6 doubles [R row-major; t], cam_sbi: the 40x30 TaylorCamera, the two poses as 12 doubles.  Returns
+    (cam_pose, base_from_world), 12 doubles each."""
+    L = _bind_track_recover(lib())
+    se2 = np.ascontiguousarray(se2, dtype=np.float64).reshape(6)
+    k, c = np.ascontiguousarray(cam_from_world_best, dtype=np.float64).reshape(12), np.ascontiguousarray(cam_from_base, dtype=np.float64).reshape(12)
+    cs = cam_sbi.to_struct()
+    pose, bfw = np.zeros(12), np.zeros(12)
+    _chk(L.mcp_track_recover_pose_host(se2.ctypes.data, ctypes.byref(cs), k.ctypes.data, c.ctypes.data, pose.ctypes.data, bfw.ctypes.data), "track_recover_pose_host")
+    return pose, bfw
+
+
+def zmssd(cur, other):
+    """SmallBlurryImage::ZMSSD (src/SmallBlurryImage.cc:122-134): the float differences, squared and summed in double in raster order."""
+    d = (np.asarray(cur, dtype=np.float32).ravel() - np.asarray(other, dtype=np.float32).ravel()).astype(np.float64)
+    s = 0.0
+    for v in d * d:
+        s += v
+    return s
+
+
+def recover_restate(cur_templs, cand_templs, cand_cams, cand_poses, aligns, cams_sbi, cams_from_base, max_score=1e5, se3_from_se2=None, scores=None):
+    """Relocaliser::ScoreKFs / AttemptRecovery and Tracker::AttemptRecovery (src/Relocaliser.cc:61-120, src/Tracker.cc:526-552) restated.
+    cur_templs: the cameras' current templates; cand_templs: one template per candidate, None for a skipped one; cand_poses: (R, t) per
+    candidate; aligns(c, best) -> (se2 as 6 doubles, score): the alignment of camera c against candidate best; cams_sbi: the 40x30
+    TaylorCameras; cams_from_base: (R, t) per camera; se3_from_se2(R2, t2, cam, cam) -> 3x3 rotation, default the library's host entry;
+    scores: taken as given instead of summed here.  Returns dict(scores, best, best_zmssd, se2, align_score, cam_pose [(R, t) or None],
+    recovered, cam, base_from_world (R, t) or None)."""
+    if se3_from_se2 is None:
+        from .keyframe import sbi_se3_from_se2 as se3_from_se2
+    ncam, ncand = len(cur_templs), len(cand_cams)
+    if scores is None:
+        scores = np.array([SCORE_SKIPPED if cand_templs[i] is None else zmssd(cur_templs[cand_cams[i]], cand_templs[i]) for i in range(ncand)])
+    out = dict(scores=np.asarray(scores, dtype=np.float64), best=[-1] * ncam, best_zmssd=[0.0] * ncam, se2=np.zeros((ncam, 6)), align_score=[0.0] * ncam,
+               cam_pose=[None] * ncam, recovered=False, cam=-1, base_from_world=None)
+    for c in range(ncam):
+        b = SCORE_SKIPPED
+        for i in range(ncand):
+            if cand_cams[i] == c and cand_templs[i] is not None and out["scores"][i] < b:      # strict: the first smallest
+                b, out["best"][c] = out["scores"][i], i
+        k = out["best"][c]
+        if k < 0:
+            continue
+        se2, score = aligns(c, k)
+        se2 = np.asarray(se2, dtype=np.float64).reshape(6)
+        out["best_zmssd"][c], out["se2"][c], out["align_score"][c] = b, se2, score
+        Rk, tk = np.asarray(cand_poses[k][0], dtype=np.float64), np.asarray(cand_poses[k][1], dtype=np.float64)
+        Rr = np.eye(3) if np.array_equal(se2, [1, 0, 0, 1, 0, 0]) else se3_from_se2(se2[:4].reshape(2, 2), se2[4:], cams_sbi[c], cams_sbi[c])
+        out["cam_pose"][c] = (Rr @ Rk, Rr @ tk)
+        if not out["recovered"] and score < max_score:
+            Rc, tc = np.asarray(cams_from_base[c][0], dtype=np.float64), np.asarray(cams_from_base[c][1], dtype=np.float64)
+            Rp, tp = out["cam_pose"][c]
+            out["recovered"], out["cam"], out["base_from_world"] = True, c, (Rc.T @ Rp, Rc.T @ (tp - tc))
+    return out

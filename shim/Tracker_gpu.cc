@@ -466,7 +466,7 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
 // ---- the whole TrackMap from the table in one submission (include/mcp_img.h, mcp_track_map) --------------------------------------------
 // Replaces src/Tracker.cc:938-1075 (FindPVS of every camera, the shuffles, TestForCoarse, the coarse gate and iterations,
 // SetupFineTracking, the fine iterations).  Needs, in addition to the FindPVS members above, in class Tracker:
-//     void TrackMapOnDevice(...);      (its full declaration is with TrackFrameOnDevice below)
+//     bool TrackMapOnDevice(...);      (its full declaration is with TrackFrameOnDevice below)
 //     void UploadMapSources();
 // and the patch sources of the rows: UploadMapSources() below, after UploadMapTable() (option (a); with option (b) the same call goes
 // with each row update, as mcp_map_points_update_source).  Keys: the point's address >> 4, as TrackStageOnDevice uses.  Truncated to an
@@ -513,7 +513,11 @@ void Tracker::UploadMapSources()
 // With pMotion the same submission also runs the frame's pyramids (apImages / anStrides: one 8-bit image per camera, mvCurrCamNames order),
 // the tracker's SmallBlurryImages, CalcSBIRotation and ApplyMotionModel before TrackMap and UpdateMotionModel's velocity behind it
 // (mcp_track_frame_motion): see TrackFrameOnDevice below.  Without it: TrackMap alone from the pose and the pyramids as they stand.
-void Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uint8_t* const* apImages, const int* anStrides, mcp_track_motion* pMotionOut)
+// With pRecover (and pMotion with apply = 0) the submission starts with the relocaliser over pRecover's candidates and TrackMap runs from the pose
+// it finds, or not at all (mcp_track_frame_recover): see TrackFrameRecoverOnDevice below.  Returns false when nobody recovered: nothing was
+// tracked and nothing below the call is touched.
+bool Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uint8_t* const* apImages, const int* anStrides, mcp_track_motion* pMotionOut,
+                               const RecoverCandidates* pRecover, mcp_track_recover* pRecoverOut)
 {
   const int nCams = (int)mvCurrCamNames.size();
   std::vector<mcp_kf*> vKF(nCams);
@@ -537,7 +541,7 @@ void Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
   prm.try_coarse = !(Tracker::sbDisableCoarse || mdMSDScaledVelocityMagnitude < Tracker::sdCoarseMinVelocity || Tracker::snCoarseMax == 0);
   prm.coarse_max = Tracker::snCoarseMax;
   prm.coarse_range = Tracker::snCoarseRange;
-  if(mbJustRecoveredSoUseCoarse)
+  if(mbJustRecoveredSoUseCoarse || pRecover)                // (:549-550: a recovery sets the flag before its TrackMap)
   {
     prm.try_coarse = 1;
     prm.coarse_max *= 2;
@@ -566,16 +570,26 @@ void Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
     boost::mutex::scoped_lock lock(mMap.mMutex);
     UploadMapTable();                                   // rows and their counts
     UploadMapSources();
-    const int rc = pMotion ? mcp_track_frame_motion(mpMapTable, nCams, &vKF[0], apImages, anStrides, 0, NULL, &vCams[0], &vCamsSBI[0], adBfW, &vCfB[0], &prm, &res, &rprm,
+    mcp_track_recover_params qprm;
+    qprm.reloc_blur = 2.5;                                // SmallBlurryImage's default blur, KeyFrame::MakeSBI
+    qprm.reloc_iterations = 6;                            // src/Relocaliser.cc:76
+    qprm.max_score = Relocaliser::sdRecoveryMaxScore;
+    const int rc = pRecover ? mcp_track_frame_recover(mpMapTable, nCams, &vKF[0], apImages, anStrides, 0, NULL, &vCams[0], &vCamsSBI[0], adBfW, &vCfB[0], &prm, &res, &rprm,
+                                                      &mTrackRecord, pMotion, pMotionOut, (int)pRecover->vKF.size(), pRecover->vKF.empty() ? NULL : &pRecover->vKF[0],
+                                                      pRecover->vCam.empty() ? NULL : &pRecover->vCam[0], pRecover->vPose.empty() ? NULL : &pRecover->vPose[0],
+                                                      &qprm, pRecoverOut, NULL)
+                   : pMotion ? mcp_track_frame_motion(mpMapTable, nCams, &vKF[0], apImages, anStrides, 0, NULL, &vCams[0], &vCamsSBI[0], adBfW, &vCfB[0], &prm, &res, &rprm,
                                                     &mTrackRecord, pMotion, pMotionOut)
                            : mcp_track_map_record(mpMapTable, nCams, &vKF[0], NULL, NULL, 0, NULL, &vCams[0], adBfW, &vCfB[0], &prm, &res, &rprm, &mTrackRecord);
     if(rc != 0)
     {
       ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: "<<mcp_last_error());
       ros::shutdown();
-      return;
+      return false;
     }
   }
+  if(pRecover && !pRecoverOut->recovered)
+    return false;                                         // :496: no TrackMap, no AssessOverallTrackingQuality
   const mcp_track_record& rec = mTrackRecord;
   mbDidCoarse = res.did_coarse != 0;
   Matrix<3> m3R;
@@ -641,7 +655,7 @@ void Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
     {
       ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: scene depth of "<<camName<<" is not finite");
       ros::shutdown();
-      return;
+      return false;
     }
   }
   // the rest of RefreshSceneDepth (:1212-1226) stays on the host
@@ -657,26 +671,28 @@ void Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
   }
   ROS_ASSERT(nNum > 0);
   mpCurrentMKF->mdTotalDepthMean = dSumDepth/nNum;
+  return true;
 }
 
 // ---- TrackFrame's tracking branch in one submission (include/mcp_img.h, mcp_track_frame_motion) ------------------------------------------
 // Replaces, for a frame with a good map, src/Tracker.cc:303-330 (MakeKeyFrame_Lite and the SmallBlurryImages of every camera), :431-434
-// (ApplyMotionModel, TrackMap, UpdateMotionModel) with :1516-1555 and :1687-1749 behind them, and -- bRecovered, after AttemptRecovery has set
-// the pose -- :498 (TrackMap alone; the SBIs are still made and rolled, as TrackFrameSetup does every frame).  The tracker's SBIs live in the
+// (ApplyMotionModel, TrackMap, UpdateMotionModel) with :1516-1555 and :1687-1749 behind them.  The tracker's SBIs live in the
 // map table per camera index, so mmpSBIThisFrame / mmpSBILastFrame are not kept here; Tracker::Reset calls mcp_track_motion_reset(mpMapTable).
 // The caller keeps mbActive, the timing messages and everything after UpdateMotionModel (:436 on).  Needs in class Tracker:
-//     void TrackMapOnDevice(const mcp_track_motion_params* pMotion = NULL, const uint8_t* const* apImages = NULL, const int* anStrides = NULL,
-//                           mcp_track_motion* pMotionOut = NULL);
-//     void TrackFrameOnDevice(ImageBWMap& imFrames, bool bRecovered);
+//     struct RecoverCandidates { std::vector<mcp_kf*> vKF; std::vector<int> vCam; std::vector<double> vPose; };      // see TrackFrameRecoverOnDevice
+//     bool TrackMapOnDevice(const mcp_track_motion_params* pMotion = NULL, const uint8_t* const* apImages = NULL, const int* anStrides = NULL,
+//                           mcp_track_motion* pMotionOut = NULL, const RecoverCandidates* pRecover = NULL, mcp_track_recover* pRecoverOut = NULL);
+//     void FrameMotionParams(ImageBWMap& imFrames, bool bApply, mcp_track_motion_params& mprm, std::vector<const uint8_t*>& vImages, std::vector<int>& vStrides);
+//     void TrackFrameOnDevice(ImageBWMap& imFrames);
+//     bool TrackFrameRecoverOnDevice(ImageBWMap& imFrames);
 // Deviation: a process duration that is not positive is an error here (the reference divides by it).
-void Tracker::TrackFrameOnDevice(ImageBWMap& imFrames, bool bRecovered)
+void Tracker::FrameMotionParams(ImageBWMap& imFrames, bool bApply, mcp_track_motion_params& mprm, std::vector<const uint8_t*>& vImages, std::vector<int>& vStrides)
 {
   const int nCams = (int)mvCurrCamNames.size();
-  std::vector<const uint8_t*> vImages(nCams);
-  std::vector<int> vStrides(nCams);
-  mcp_track_motion_params mprm;
+  vImages.resize(nCams);
+  vStrides.resize(nCams);
   std::memset(&mprm, 0, sizeof mprm);
-  mprm.apply = bRecovered ? 0 : 1;
+  mprm.apply = bApply ? 1 : 0;
   mprm.use_rotation_estimator = Tracker::sbUseRotationEstimator ? 1 : 0;
   mprm.sbi_iterations = 6;                                     // :1700
   mprm.blur = Tracker::sdRotationEstimatorBlur;
@@ -690,17 +706,78 @@ void Tracker::TrackFrameOnDevice(ImageBWMap& imFrames, bool bRecovered)
     vStrides[c] = im.row_stride();
     mprm.cam_good[c] = mmTrackingQuality[mvCurrCamNames[c]] == GOOD ? 1 : 0;      // :1695
   }
+}
+
+void Tracker::TrackFrameOnDevice(ImageBWMap& imFrames)
+{
+  mcp_track_motion_params mprm;
+  std::vector<const uint8_t*> vImages;
+  std::vector<int> vStrides;
+  FrameMotionParams(imFrames, true, mprm, vImages, vStrides);
   mse3StartPose = mpCurrentMKF->mse3BaseFromWorld;              // :1518
   mcp_track_motion motion;
   TrackMapOnDevice(&mprm, &vImages[0], &vStrides[0], &motion);  // pose, cameras' poses, the record's bookkeeping, mdTotalDepthMean
-  if(bRecovered)
-    return;
   for(int k = 0; k < 6; ++k)
     mv6BaseVelocity[k] = motion.velocity[k];                    // :1547
   // :1552-1554: the velocity scaled by the mean scene depth, which mixes in the depths of cameras that were not refreshed: host
   Vector<6> v6 = mv6BaseVelocity;
   v6.slice<0,3>() *= 1.0 / mpCurrentMKF->mdTotalDepthMean;
   mdMSDScaledVelocityMagnitude = sqrt(v6*v6);
+}
+
+// ---- TrackFrame's lost branch in one submission (include/mcp_img.h, mcp_track_frame_recover) ---------------------------------------------
+// Replaces, for a frame with a map and a lost tracker, src/Tracker.cc:303-330 (the pyramids and the tracker's SmallBlurryImages), :496-498
+// (AttemptRecovery and TrackMap) with :526-552 and src/Relocaliser.cc:61-120 behind them: the relocaliser's SBI of every camera (into the
+// keyframes' device handles), ScoreKFs over every keyframe of the map that has a device handle, the alignment against the winner, SE3fromSE2 and
+// the pose products, then TrackMap from the recovered pose -- or no TrackMap when no camera recovered.  The candidates' poses are read here,
+// under the map lock, at every call: they change with every adjustment.  In TrackFrame:
+//     if(TrackFrameRecoverOnDevice(imFrames)) { AssessOverallTrackingQuality(); ReleasePointLock(); }
+// Deviation: the reference stops at the first camera that recovers; here every camera's relocaliser SBI is made and evaluated, and the first
+// camera in mvCurrCamNames order that recovered is used.  mRelocaliser is not called; its mse2 / mse3Best are not kept.
+bool Tracker::TrackFrameRecoverOnDevice(ImageBWMap& imFrames)
+{
+  mcp_track_motion_params mprm;
+  std::vector<const uint8_t*> vImages;
+  std::vector<int> vStrides;
+  FrameMotionParams(imFrames, false, mprm, vImages, vStrides);
+  RecoverCandidates cands;
+  {
+    boost::mutex::scoped_lock lock(mMap.mMutex);
+    for(MultiKeyFramePtrList::iterator it = mMap.mlpMultiKeyFrames.begin(); it != mMap.mlpMultiKeyFrames.end(); ++it)
+    {
+      MultiKeyFrame& mkf = *(*it);
+      for(KeyFramePtrMap::iterator jit = mkf.mmpKeyFrames.begin(); jit != mkf.mmpKeyFrames.end(); ++jit)
+      {
+        KeyFrame& kf = *(jit->second);
+        int c = 0;
+        while(c < (int)mvCurrCamNames.size() && mvCurrCamNames[c] != kf.mCamName)
+          ++c;
+        if(c == (int)mvCurrCamNames.size() || !kf.mpDev)         // "only look at same camera" (Relocaliser.cc:103); no device twin: skipped like a missing mpSBI
+          continue;
+        cands.vKF.push_back(kf.mpDev);
+        cands.vCam.push_back(c);
+        cands.vPose.resize(cands.vPose.size() + 12);
+        ToArray12(kf.mse3CamFromWorld, &cands.vPose[cands.vPose.size() - 12]);
+      }
+    }
+  }
+  mcp_track_motion motion;
+  mcp_track_recover recover;
+  if(!TrackMapOnDevice(&mprm, &vImages[0], &vStrides[0], &motion, &cands, &recover))
+    return false;                                               // :545-546
+  // :538, :548-550.  TrackMapOnDevice has set mse3BaseFromWorld to the refined pose and called UpdateCamsFromWorld
+  Matrix<3> m3R;
+  Vector<3> v3T;
+  for(int i = 0; i < 3; ++i)
+  {
+    for(int j = 0; j < 3; ++j)
+      m3R(i, j) = recover.base_from_world[3*i + j];
+    v3T[i] = recover.base_from_world[9 + i];
+  }
+  mse3StartPose = SE3<>(SO3<>(m3R), v3T);
+  mv6BaseVelocity = Zeros;
+  mbJustRecoveredSoUseCoarse = false;                           // the doubled caps were used by this very call
+  return true;
 }
 
 // AssessTrackingQuality (:1618-1658) from the record of TrackMapOnDevice: the same arithmetic ran on the device from the same counters
