@@ -250,6 +250,33 @@ int mcp_debug_pose_cut(const unsigned char* adjacency, int nf, int max_arcs, int
  * triangle meaningful inside the tiles of the factorisation plan, other entries 0), rhs (np) and J^T r (np) behind it;
  * np = 6 * free poses.  Returns np (buffers may be NULL to query it), < 0 on error. */
 int mcp_ba_debug_system(mcp_ba*, double lambda, double* S_rhs_b_out);
+/* the same for a batch of `nsys` systems (1..4) built by ONE launch chain with the lambda table lambdas[nsys], as a trial solve
+ * with speculative systems builds them: out holds nsys blocks of np*np + 2*np doubles (S, rhs, J^T r of system q).  Returns np
+ * (out may be NULL to query it); -1 with a message for an nsys the handle has no buffers for (mcp_ba_structure.max_systems). */
+int mcp_ba_debug_systems(mcp_ba*, int nsys, const double* lambdas, double* out);
+/* Which shape the structure build gave the map and which kernels the next linearisation and reduced-system build launch for it
+ * (read-only; prepares the handle if it is not prepared).  The solver takes its launch decisions from the same functions that fill
+ * lin_kernel, lin_generic and schur_kernel. */
+#define MCP_BA_LIN_NONE  0      /* no group: nothing is linearised by a group kernel */
+#define MCP_BA_LIN_QUAD  1      /* k_linearize_quad: groups of 16 points, four lanes per point, W blocks in LDS */
+#define MCP_BA_LIN_PIPE  2      /* k_linearize_pipe: one lane per point, one round ahead */
+#define MCP_BA_LIN_GROUP 3      /* k_linearize_group: one lane per point, plain loop */
+#define MCP_BA_SCHUR_NONE  0    /* no free point or no group: nothing is eliminated by a group kernel */
+#define MCP_BA_SCHUR_4     1    /* k_schur4: all systems of a batch in one workgroup per group (groups of at most 13 poses) */
+#define MCP_BA_SCHUR_GROUP 2    /* k_schur_group: one workgroup per group and system, 16-point chunks */
+typedef struct mcp_ba_structure {
+  int ngroup, grp_pts, nbig, nfl, np;   /* groups, points per group the layout allows (16 / 64), points on the generic path, free points, 6 x free poses */
+  int grp_points_max, grp_points_min;   /* most / fewest points in one group (0 without groups) */
+  int grp_poses_max;                    /* most poses in one group */
+  int grp_no_pose;                      /* groups without a pose (only generic-path points, or points no free pose sees) */
+  int grp_blk_max, grp_inc_max;         /* most staged pose-pair blocks / point-pose incidences of one group */
+  int lin_kernel;                       /* MCP_BA_LIN_* */
+  int lin_generic;                      /* nonzero: k_linearize also runs (generic-path points) */
+  int schur_kernel;                     /* MCP_BA_SCHUR_* */
+  int asm_long;                         /* nonzero: k_assemble_long instead of k_assemble */
+  int max_systems;                      /* most systems one batch may hold for this handle */
+} mcp_ba_structure;
+int mcp_ba_debug_structure(mcp_ba*, mcp_ba_structure* out);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,15 @@ class McpBaTiming(ctypes.Structure):
                 ("chol_flops_plan", ctypes.c_double), ("chol_chains", ctypes.c_int)]
 
 
+class McpBaStructure(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int) for f in (
+        "ngroup", "grp_pts", "nbig", "nfl", "np", "grp_points_max", "grp_points_min", "grp_poses_max", "grp_no_pose",
+        "grp_blk_max", "grp_inc_max", "lin_kernel", "lin_generic", "schur_kernel", "asm_long", "max_systems")]
+
+
+LIN_KERNEL_NAMES = ("none", "quad", "pipe", "group")          # MCP_BA_LIN_* of include/mcp_ba.h
+SCHUR_KERNEL_NAMES = ("none", "schur4", "schur_group")        # MCP_BA_SCHUR_*
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
 
 # every symbol include/mcp_ba.h declares (checked by the CPU test-suite)
@@ -58,7 +67,7 @@ BA_SYMBOLS = [
     "mcp_ba_num_outliers", "mcp_ba_get_outliers", "mcp_ba_sigma_squared", "mcp_ba_mean_chi_squared", "mcp_ba_max_cov",
     "mcp_ba_lambda", "mcp_ba_num_iter_logs", "mcp_ba_get_iter_logs", "mcp_ba_get_timing", "mcp_ba_set_allreduce",
     "mcp_ba_prepare", "mcp_ba_eval", "mcp_ba_robust_chi2", "mcp_ba_debug_solve", "mcp_dense_spd_solve",
-    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
+    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
     "mcp_ba_struct_cache_stats", "mcp_ba_struct_cache_near_hits", "mcp_ba_struct_cache_clear",
     "mcp_comm_unique_id", "mcp_comm_init", "mcp_comm_destroy", "mcp_ba_set_comm", "mcp_comm_allreduce", "mcp_comm_allreduce_lane",
 ]
@@ -105,6 +114,8 @@ def lib():
     L.mcp_chol_time.argtypes = [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]
     L.mcp_dense_spd_stress.argtypes = [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_int)]
     L.mcp_ba_debug_system.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p]
+    L.mcp_ba_debug_systems.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p]
+    L.mcp_ba_debug_structure.argtypes = [ctypes.c_void_p, ctypes.POINTER(McpBaStructure)]
     L.mcp_comm_unique_id.argtypes = [ctypes.c_void_p]
     L.mcp_comm_init.restype = ctypes.c_void_p
     L.mcp_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -337,6 +348,34 @@ class ChainBundle:
         if self._L.mcp_ba_debug_system(self._h, float(lam), _dp(out)) < 0:
             raise RuntimeError("mcp_ba_debug_system: " + last_error())
         return out[:n * n].reshape(n, n), out[n * n:n * n + n], out[n * n + n:]
+
+    def DebugSystems(self, lams):
+        """[(S, rhs, J^T r)] of the reduced pose systems of ONE batch with the damping factors `lams` (1 to 4 of them), built
+        by one launch chain as a trial solve with speculative systems builds them (test hook, mcp_ba_debug_systems)."""
+        lams = np.ascontiguousarray(lams, dtype=np.float64).reshape(-1)
+        n = self._L.mcp_ba_debug_systems(self._h, len(lams), _dp(lams), None)
+        if n < 0:
+            raise RuntimeError("mcp_ba_debug_systems: " + last_error())
+        per = n * n + 2 * n
+        out = np.zeros(max(len(lams), 1) * per)
+        if self._L.mcp_ba_debug_systems(self._h, len(lams), _dp(lams), _dp(out)) < 0:
+            raise RuntimeError("mcp_ba_debug_systems: " + last_error())
+        return [(out[q * per:q * per + n * n].reshape(n, n).copy(), out[q * per + n * n:q * per + n * n + n].copy(),
+                 out[q * per + n * n + n:(q + 1) * per].copy()) for q in range(len(lams))]
+
+    def DebugStructure(self):
+        """The shape the structure build gave the map and the kernels the next linearisation / reduced-system build launch for
+        it (read-only test hook, mcp_ba_debug_structure): the counts of mcp_ba_structure, `lin_kernel` as "quad" / "pipe" /
+        "group" / "none", `schur_kernel` as "schur4" / "schur_group" / "none", `lin_generic` and `asm_long` as bools."""
+        st = McpBaStructure()
+        if self._L.mcp_ba_debug_structure(self._h, ctypes.byref(st)) < 0:
+            raise RuntimeError("mcp_ba_debug_structure: " + last_error())
+        d = {f: int(getattr(st, f)) for f, _ in McpBaStructure._fields_}
+        d["lin_kernel"] = LIN_KERNEL_NAMES[d["lin_kernel"]]
+        d["schur_kernel"] = SCHUR_KERNEL_NAMES[d["schur_kernel"]]
+        d["lin_generic"] = bool(d["lin_generic"])
+        d["asm_long"] = bool(d["asm_long"])
+        return d
 
     def Compute(self, n_iter=None, user_lambda=-1.0):
         """int Compute(bool* pAbortSignal, int nNumIter, double dUserLambda); the abort flag is self.abort."""

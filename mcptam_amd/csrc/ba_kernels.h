@@ -290,14 +290,11 @@ __device__ inline void make_slot(int side, int link, const double* A /*2x3*/, co
 
 constexpr int LIN_BLOCK = 128;
 
-__global__ void __launch_bounds__(LIN_BLOCK)
-k_linearize(DevProblem P, int only_big, const double* __restrict__ pt_x, const double* __restrict__ first,
+// one measurement of a generic-path point: its blocks added to U, bp, V, g and W
+__device__ inline void linearize_one(const DevProblem& P, const int m, const double* __restrict__ pt_x, const double* __restrict__ first,
             const double* __restrict__ second, const double* __restrict__ sigma,
             double* __restrict__ U, double* __restrict__ bp, double* __restrict__ V,
             double* __restrict__ g, double* __restrict__ W) {
-  const int m = blockIdx.x*LIN_BLOCK + threadIdx.x;
-  if (m >= P.nmeas) return;
-  if (only_big && !P.sp_big[P.m_sp[m]]) return;
   const int pt = P.m_pt[m];
   const int oc = P.m_chain[m], sc = P.pt_chain[pt];
   const int olen = P.chain_len[oc], slen = P.chain_len[sc];
@@ -413,6 +410,29 @@ k_linearize(DevProblem P, int only_big, const double* __restrict__ pt_x, const d
     ++ia;
   }
 }
+// The generic path: the measurements of the points that see more than GRP_LMAX poses (sp_big), whose blocks do not fit a group's tile.
+// ONE wavefront walks those points in their sorted order, 64 measurements of a point at a time (sp_m: a point's measurements are
+// contiguous).  Every sum still goes through atomic adds, but all of them are issued by this one wavefront: adds to the same address
+// from different lanes of one instruction and from successive instructions reach the memory in an order that the program and the data
+// fix, not the timing, so two solves of the same map give the same bits (it used to be one thread per measurement over many workgroups,
+// whose adds arrived in any order).  Such points are few; a map without one never launches this.
+__global__ void __launch_bounds__(64)
+k_linearize(DevProblem P, const double* __restrict__ pt_x, const double* __restrict__ first,
+            const double* __restrict__ second, const double* __restrict__ sigma,
+            double* __restrict__ U, double* __restrict__ bp, double* __restrict__ V,
+            double* __restrict__ g, double* __restrict__ W) {
+  const int lane = threadIdx.x;
+  for (int base = 0; base < P.nsp; base += 64) {
+    const int sp = base + lane;
+    unsigned long long big = __ballot(sp < P.nsp && P.sp_big[sp] != 0);
+    for (; big; big &= big - 1) {
+      const int s = base + __builtin_ctzll(big);
+      const int m0 = P.sp_m[s], m1 = P.sp_m[s + 1];
+      for (int mb = m0; mb < m1; mb += 64)
+        if (mb + lane < m1) linearize_one(P, mb + lane, pt_x, first, second, sigma, U, bp, V, g, W);
+    }
+  }
+}
 
 // max |diag| of U and V  (computeLambdaInit [g2o])
 __global__ void __launch_bounds__(256)
@@ -497,48 +517,63 @@ __device__ inline bool inv_sym3(const double* V6, double lambda, double* I6) {
   return ok;
 }
 
-// point elimination: S -= W Vinv W^T, rhs -= W Vinv g.  One wave per free point.
+// point elimination of the generic-path points (sp_big): S -= W Vinv W^T, rhs -= W Vinv g.  ONE workgroup per system takes those points
+// one after the other in ascending free-point order; within a point every thread owns entries of its own (a point's incidences are
+// distinct poses, so no two items of a point share an address) and adds without atomics, and a barrier separates one point's adds from
+// the next point's: every entry is summed in a fixed order (it used to be one wavefront per point adding atomically in arrival order).
 __global__ void __launch_bounds__(256)
-k_schur(DevProblem P, int only_big, double lambda, const double* __restrict__ V, const double* __restrict__ g,
+k_schur(DevProblem P, double lambda, const double* __restrict__ V, const double* __restrict__ g,
         const double* __restrict__ W, double* __restrict__ Vinv, double* __restrict__ S,
         double* __restrict__ rhs, int* __restrict__ fail, SysBatch sb) {
   if (blockIdx.y) { const int q = blockIdx.y; lambda = sb.lambda[q]; Vinv += q*sb.vstride; S += q*sb.sstride; rhs += q*sb.sstride; fail += q; }
-  const int l = blockIdx.x*4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (l >= P.nfl) return;
-  if (only_big && !P.sp_big[P.l_sp[l]]) return;
-  double I6[6];
-  const bool ok = inv_sym3(V + 6*(size_t)l, lambda, I6);
-  if (lane == 0) {
-    if (!ok) atomicOr(fail, 1);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Vinv[6*(size_t)l + k] = I6[k];
-  }
-  const int i0 = P.l_i0[l], q = P.l_i1[l] - i0;
-  const double Vi[9] = { I6[0], I6[1], I6[2], I6[1], I6[3], I6[4], I6[2], I6[4], I6[5] };
-  const double g0 = g[3*(size_t)l], g1 = g[3*(size_t)l+1], g2 = g[3*(size_t)l+2];
+  __shared__ unsigned long long bigmask[4];
+  const int t = threadIdx.x;
   const int np = P.np;
-  // rhs: q*6 items
-  for (int it = lane; it < q*6; it += 64) {
-    const int a = it / 6, r = it % 6;
-    const double* Wa = W + 18*(size_t)(i0 + a) + 3*r;
-    const double y0 = Wa[0]*Vi[0] + Wa[1]*Vi[3] + Wa[2]*Vi[6];
-    const double y1 = Wa[0]*Vi[1] + Wa[1]*Vi[4] + Wa[2]*Vi[7];
-    const double y2 = Wa[0]*Vi[2] + Wa[1]*Vi[5] + Wa[2]*Vi[8];
-    unsafeAtomicAdd(rhs + 6*(size_t)P.inc_unk[i0 + a] + r, -(y0*g0 + y1*g1 + y2*g2));
-  }
-  const int items = q*q*36;
-  for (int it = lane; it < items; it += 64) {
-    const int pair = it / 36, e = it % 36;
-    const int a = pair / q, b = pair % q, r = e / 6, c = e % 6;
-    const int ua = P.inc_unk[i0 + a], ub = P.inc_unk[i0 + b];
-    if (ua < ub || (ua == ub && c > r)) continue;
-    const double* Wa = W + 18*(size_t)(i0 + a) + 3*r;
-    const double* Wb = W + 18*(size_t)(i0 + b) + 3*c;
-    const double y0 = Wa[0]*Vi[0] + Wa[1]*Vi[3] + Wa[2]*Vi[6];
-    const double y1 = Wa[0]*Vi[1] + Wa[1]*Vi[4] + Wa[2]*Vi[7];
-    const double y2 = Wa[0]*Vi[2] + Wa[1]*Vi[5] + Wa[2]*Vi[8];
-    unsafeAtomicAdd(S + (size_t)(6*ua + r)*np + 6*ub + c, -(y0*Wb[0] + y1*Wb[1] + y2*Wb[2]));
+  for (int base = 0; base < P.nfl; base += 256) {
+    const int lt = base + t;
+    const unsigned long long bm = __ballot(lt < P.nfl && P.sp_big[P.l_sp[lt]] != 0);
+    if ((t & 63) == 0) bigmask[t >> 6] = bm;
+    __syncthreads();
+    for (int w = 0; w < 4; ++w) {
+      for (unsigned long long mk = bigmask[w]; mk; mk &= mk - 1) {      // (read from LDS: the same trip count for every thread)
+        const int l = base + 64*w + __builtin_ctzll(mk);
+        double I6[6];
+        const bool ok = inv_sym3(V + 6*(size_t)l, lambda, I6);
+        if (t == 0) {
+          if (!ok) atomicOr(fail, 1);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) Vinv[6*(size_t)l + k] = I6[k];
+        }
+        const int i0 = P.l_i0[l], q = P.l_i1[l] - i0;
+        const double Vi[9] = { I6[0], I6[1], I6[2], I6[1], I6[3], I6[4], I6[2], I6[4], I6[5] };
+        const double g0 = g[3*(size_t)l], g1 = g[3*(size_t)l+1], g2 = g[3*(size_t)l+2];
+        // rhs: q*6 items
+        for (int it = t; it < q*6; it += 256) {
+          const int a = it / 6, r = it % 6;
+          const double* Wa = W + 18*(size_t)(i0 + a) + 3*r;
+          const double y0 = Wa[0]*Vi[0] + Wa[1]*Vi[3] + Wa[2]*Vi[6];
+          const double y1 = Wa[0]*Vi[1] + Wa[1]*Vi[4] + Wa[2]*Vi[7];
+          const double y2 = Wa[0]*Vi[2] + Wa[1]*Vi[5] + Wa[2]*Vi[8];
+          rhs[6*(size_t)P.inc_unk[i0 + a] + r] += -(y0*g0 + y1*g1 + y2*g2);
+        }
+        const int items = q*q*36;
+        for (int it = t; it < items; it += 256) {
+          const int pair = it / 36, e = it % 36;
+          const int a = pair / q, b = pair % q, r = e / 6, c = e % 6;
+          const int ua = P.inc_unk[i0 + a], ub = P.inc_unk[i0 + b];
+          if (ua < ub || (ua == ub && c > r)) continue;
+          const double* Wa = W + 18*(size_t)(i0 + a) + 3*r;
+          const double* Wb = W + 18*(size_t)(i0 + b) + 3*c;
+          const double y0 = Wa[0]*Vi[0] + Wa[1]*Vi[3] + Wa[2]*Vi[6];
+          const double y1 = Wa[0]*Vi[1] + Wa[1]*Vi[4] + Wa[2]*Vi[7];
+          const double y2 = Wa[0]*Vi[2] + Wa[1]*Vi[5] + Wa[2]*Vi[8];
+          S[(size_t)(6*ua + r)*np + 6*ub + c] += -(y0*Wb[0] + y1*Wb[1] + y2*Wb[2]);
+        }
+        __threadfence();
+        __syncthreads();      // the next point's adds read what this point's wrote
+      }
+    }
+    __syncthreads();          // (bigmask is rewritten by the next round)
   }
 }
 

@@ -881,6 +881,30 @@ struct mcp_ba {
     evt_log.clear();
   }
   int solve_chain(hipStream_t s, int n, int q0);
+  // Which kernels a prepared map takes.  linearize() and build_system() launch what these say and mcp_ba_debug_structure() reports
+  // what these say: one place, so that the report cannot drift from the launches.
+  // (the quad form keeps the group's W blocks in LDS beside the pose blocks: groups whose points see many poses -- 16 points x 16
+  //  incidences is 36 KB on top of up to 39 KB of pose blocks -- do not fit the 64 KB a launch gets by default and take the
+  //  one-lane-per-point kernel, which handles groups of any size up to 64 points)
+  size_t quad_lds_bytes() const { return ((size_t)std::max(grp_blk_max, 1)*36 + (size_t)std::max(grp_inc_max, 1)*18)*sizeof(double); }
+  int lin_kernel() const {
+    static const bool quad_on = [] { const char* e = getenv("MCP_BA_LIN_QUAD"); return !(e && atoi(e) == 0); }();
+    if (!ngroup) return MCP_BA_LIN_NONE;
+    if (grp_pts <= LIN_QUAD_PTS && quad_on && quad_lds_bytes() <= 58*1024) return MCP_BA_LIN_QUAD;      // (+ 5 KB of static LDS: tables and cameras)
+    if (lin_pipe && !getenv("MCP_BA_TEST_REFUSE_LAUNCH")) return MCP_BA_LIN_PIPE;
+    return MCP_BA_LIN_GROUP;
+  }
+  bool lin_generic() const { return nbig > 0 && P.nmeas > 0; }      // k_linearize for the points that touch more than GRP_LMAX poses
+  int schur_kernel() const { return !(nfl && ngroup) ? MCP_BA_SCHUR_NONE : (sch4_on && sch4_ok) ? MCP_BA_SCHUR_4 : MCP_BA_SCHUR_GROUP; }
+  // systems of one batch that the reduced-system, V^-1 and staging buffers of this handle have room for
+  int batch_capacity() const {
+    size_t c = MAX_SYS;
+    if (red_stride) c = std::min(c, d_red.n/red_stride);
+    if (vinv_stride) c = std::min(c, d_Vinv.n/vinv_stride);
+    if (nstage) c = std::min(c, d_stS.n/(nstage*36));
+    if (nrhs_rows) c = std::min(c, d_str.n/((size_t)nrhs_rows*6));
+    return (int)c;
+  }
   int linearize();
   int build_system(int nsys, SysBatch& sb, int q0 = 0, hipStream_t on = nullptr);
   int solve_trial(double lam, bool& ok2, double ni = 0);
@@ -2543,21 +2567,17 @@ int mcp_ba::linearize() {
       HIPCK(hipMemsetAsync(d_g.p, 0, (size_t)nfl*3*sizeof(double), st));
     }
     if (ninc) HIPCK(hipMemsetAsync(d_W.p, 0, (size_t)ninc*18*sizeof(double), st));
-    if (P.nmeas) hipLaunchKernelGGL(k_linearize, dim3((P.nmeas + LIN_BLOCK - 1)/LIN_BLOCK), dim3(LIN_BLOCK), 0, st, P, 1,
+    if (lin_generic()) hipLaunchKernelGGL(k_linearize, dim3(1), dim3(64), 0, st, P,      // (one wavefront: sums in a fixed order, ba_kernels.h)
                        d_pt[cur].p, d_first[cur].p, d_second[cur].p, sig(), d_ubig.p, d_ubig.p + n2, d_V.p, d_g.p, d_W.p);
   }
-  // (the quad form keeps the group's W blocks in LDS beside the pose blocks: groups whose points see many poses -- 16 points x 16
-  //  incidences is 36 KB on top of up to 39 KB of pose blocks -- do not fit the 64 KB a launch gets by default and take the
-  //  one-lane-per-point kernel, which handles groups of any size up to 64 points)
-  const size_t quad_lds = ((size_t)std::max(grp_blk_max, 1)*36 + (size_t)std::max(grp_inc_max, 1)*18)*sizeof(double);
-  static const bool quad_on = [] { const char* e = getenv("MCP_BA_LIN_QUAD"); return !(e && atoi(e) == 0); }();
-  if (ngroup && grp_pts <= LIN_QUAD_PTS && quad_on && quad_lds <= 58*1024)      // (+ 5 KB of static LDS: tables and cameras)
-    hipLaunchKernelGGL(k_linearize_quad, dim3(ngroup), dim3(64), quad_lds, st, P,
+  const int lk = lin_kernel();
+  if (lk == MCP_BA_LIN_QUAD)
+    hipLaunchKernelGGL(k_linearize_quad, dim3(ngroup), dim3(64), quad_lds_bytes(), st, P,
                        d_pt[cur].p, d_first[cur].p, d_second[cur].p, sig(), d_stU.p, d_stb.p, d_V.p, d_g.p, d_W.p, std::max(grp_blk_max, 1)*36, d_fail.p);
-  else if (ngroup && lin_pipe && !getenv("MCP_BA_TEST_REFUSE_LAUNCH"))
+  else if (lk == MCP_BA_LIN_PIPE)
     hipLaunchKernelGGL(k_linearize_pipe, dim3(ngroup), dim3(64), (size_t)std::max(grp_blk_max, 1)*36*sizeof(double), st, P,
                        d_pt[cur].p, d_first[cur].p, d_second[cur].p, sig(), d_stU.p, d_stb.p, d_V.p, d_g.p, d_W.p, d_fail.p);
-  else if (ngroup)
+  else if (lk == MCP_BA_LIN_GROUP)
     hipLaunchKernelGGL(k_linearize_group, dim3(ngroup), dim3(64), getenv("MCP_BA_TEST_REFUSE_LAUNCH") ? ((size_t)1 << 20) /* test hook: more LDS than a compute unit has */ : (size_t)std::max(grp_blk_max, 1)*36*sizeof(double), st, P,
                        d_pt[cur].p, d_first[cur].p, d_second[cur].p, sig(), d_stU.p, d_stb.p, d_V.p, d_g.p, d_W.p, d_fail.p);
   if (ngroup) note_launch("k_linearize_group / k_linearize_quad");
@@ -2590,9 +2610,10 @@ int mcp_ba::build_system(int nsys, SysBatch& sbfull, int q0, hipStream_t on) {
   double* Sq = d_red.p + q0*red_stride; double* Vq = d_Vinv.p + q0*vinv_stride;
   double* stSq = d_stS.p + q0*sb.ststride; double* strq = d_str.p + q0*sb.strstride; int* failq = d_fail.p + q0;
   if (main_stream) tic(ST_SCHUR);
-  if (nfl && ngroup && sch4_on && sch4_ok)      // every system of the batch in one workgroup per group (ba_schur4.h)
+  const int sk = schur_kernel();
+  if (sk == MCP_BA_SCHUR_4)      // every system of the batch in one workgroup per group (ba_schur4.h)
     hipLaunchKernelGGL(k_schur4, dim3(ngroup), dim3(256), S4_LDS_BYTES, s, P, nsys, (const int*)(sch4_order ? d_g_order.p : nullptr), (const double*)d_V.p, (const double*)d_g.p, (const double*)d_W.p, Vq, stSq, strq, failq, sb);
-  else if (nfl && ngroup) hipLaunchKernelGGL(k_schur_group, dim3(ngroup, nsys), dim3(256), SCH_LDS_BYTES, s, P, sb.lambda[0], d_V.p, d_g.p, d_W.p, Vq, stSq, strq, failq, sb);
+  else if (sk == MCP_BA_SCHUR_GROUP) hipLaunchKernelGGL(k_schur_group, dim3(ngroup, nsys), dim3(256), SCH_LDS_BYTES, s, P, sb.lambda[0], d_V.p, d_g.p, d_W.p, Vq, stSq, strq, failq, sb);
   if (nfl && ngroup) note_launch("k_schur4 / k_schur_group");
   else if (ngroup && nstage) {      // no free point: nothing is eliminated, the staged Schur blocks are zero
     HIPCK(hipMemsetAsync(stSq, 0, (size_t)nsys*nstage*36*sizeof(double), s));
@@ -2602,7 +2623,7 @@ int mcp_ba::build_system(int nsys, SysBatch& sbfull, int q0, hipStream_t on) {
                              (const double*)stSq, (const double*)strq, (const double*)Ubig(), Sq, sb);
   else if (np) hipLaunchKernelGGL(k_assemble, dim3(A.ntiles, nsys), dim3(ASM_NT), 0, s, A, np, (const double*)d_stU.p, (const double*)d_stb.p,
                              (const double*)stSq, (const double*)strq, (const double*)Ubig(), Sq, sb);
-  if (nfl && nbig) hipLaunchKernelGGL(k_schur, dim3((nfl + 3)/4, nsys), dim3(256), 0, s, P, 1, sb.lambda[0], d_V.p, d_g.p, d_W.p, Vq, Sq, Sq + (size_t)np*np, failq, sb);
+  if (nfl && nbig) hipLaunchKernelGGL(k_schur, dim3(1, nsys), dim3(256), 0, s, P, sb.lambda[0], d_V.p, d_g.p, d_W.p, Vq, Sq, Sq + (size_t)np*np, failq, sb);
   if (main_stream) toc();
 #ifdef MCP_SCH_PROF
   {
@@ -3702,31 +3723,65 @@ int mcp_ba_debug_solve(mcp_ba* h, double lambda, double* x_out) {
   return 0;
 }
 
-int mcp_ba_debug_system(mcp_ba* h, double lambda, double* out) {
+int mcp_ba_debug_systems(mcp_ba* h, int nsys, const double* lambdas, double* out) {
   if (h->dirty && h->prepare()) return -1;
   if (!out) return h->np;
-  if (h->m_total == 0 || h->nx_total() == 0) { set_err("mcp_ba_debug_system: empty problem"); return -1; }
+  if (h->m_total == 0 || h->nx_total() == 0) { set_err("mcp_ba_debug_systems: empty problem"); return -1; }
+  if (nsys < 1 || nsys > h->batch_capacity() || !lambdas) {
+    char msg[160]; snprintf(msg, sizeof msg, "mcp_ba_debug_systems: a batch of %d systems asked for, the handle has buffers for 1 to %d", nsys, h->batch_capacity());
+    set_err(msg); return -1;
+  }
   h->launch_chains(h->cur);
   h->launch_eval(h->cur, false, nullptr);
   if (h->robust && h->median_sigma(h->cur)) return -1;
   if (h->linearize()) return -1;
   h->sys_cur = 0; h->spec_ok = false; h->fail_clean = false;
   SysBatch sb; std::memset(&sb, 0, sizeof sb);
-  sb.lambda[0] = lambda; sb.lambda_init[0] = (h->rank == 0) ? lambda : 0.0;
+  for (int q = 0; q < nsys; ++q) { sb.lambda[q] = lambdas[q]; sb.lambda_init[q] = (h->rank == 0) ? lambdas[q] : 0.0; }
   HIPCK(hipMemsetAsync(h->d_fail.p, 0, 4*sizeof(int), h->st));
-  if (h->build_system(1, sb)) return -1;
-  const size_t n2 = (size_t)h->np*h->np;
+  if (h->build_system(nsys, sb)) return -1;
+  const size_t n2 = (size_t)h->np*h->np, per = n2 + 2*(size_t)h->np;
   // the entries outside the plan's tiles are never written by the assembly: report them as zeros
-  std::vector<double> full(n2 + 2*(size_t)h->np, 0.0), dev(n2 + 2*(size_t)h->np);
-  HIPCK(hipMemcpyAsync(dev.data(), h->d_red.p, dev.size()*8, hipMemcpyDeviceToHost, h->st));
-  HIPCK(hipStreamSynchronize(h->st));
-  for (int tpk : h->plan.all_tiles) {
-    const int ti = tpk >> 16, tj = tpk & 0xffff;
-    for (int r = 32*ti; r < std::min(32*ti + 32, h->np); ++r) for (int c = 32*tj; c < std::min(32*tj + 32, h->np); ++c) full[(size_t)r*h->np + c] = dev[(size_t)r*h->np + c];
+  std::vector<double> full(per, 0.0), dev(per);
+  for (int q = 0; q < nsys; ++q) {
+    HIPCK(hipMemcpyAsync(dev.data(), h->d_red.p + q*h->red_stride, per*8, hipMemcpyDeviceToHost, h->st));
+    HIPCK(hipStreamSynchronize(h->st));
+    std::fill(full.begin(), full.end(), 0.0);
+    for (int tpk : h->plan.all_tiles) {
+      const int ti = tpk >> 16, tj = tpk & 0xffff;
+      for (int r = 32*ti; r < std::min(32*ti + 32, h->np); ++r) for (int c = 32*tj; c < std::min(32*tj + 32, h->np); ++c) full[(size_t)r*h->np + c] = dev[(size_t)r*h->np + c];
+    }
+    for (int i = 0; i < 2*h->np; ++i) full[n2 + i] = dev[n2 + i];
+    std::memcpy(out + q*per, full.data(), per*8);
   }
-  for (int i = 0; i < 2*h->np; ++i) full[n2 + i] = dev[n2 + i];
-  std::memcpy(out, full.data(), full.size()*8);
   return h->np;
+}
+int mcp_ba_debug_system(mcp_ba* h, double lambda, double* out) { return mcp_ba_debug_systems(h, 1, &lambda, out); }
+
+int mcp_ba_debug_structure(mcp_ba* h, mcp_ba_structure* out) {
+  if (!out) { set_err("mcp_ba_debug_structure: no output block"); return -1; }
+  if (h->dirty && h->prepare()) return -1;
+  mcp_ba_structure r; std::memset(&r, 0, sizeof r);
+  r.ngroup = h->ngroup; r.grp_pts = h->grp_pts; r.nbig = h->nbig; r.nfl = h->nfl; r.np = h->np;
+  r.grp_blk_max = h->grp_blk_max; r.grp_inc_max = h->grp_inc_max;
+  if (h->ngroup > 0) {      // the groups as the kernels read them (a handle that adopted a cached structure holds them on the device only)
+    std::vector<int> sp0((size_t)h->ngroup + 1), gp((size_t)h->ngroup*GRP_LMAX);
+    HIPCK(hipStreamSynchronize(h->st));
+    HIPCK(hipMemcpy(sp0.data(), h->d_g_sp0.p, sp0.size()*sizeof(int), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(gp.data(), h->d_g_pose.p, gp.size()*sizeof(int), hipMemcpyDeviceToHost));
+    r.grp_points_min = sp0[1] - sp0[0];
+    for (int gi = 0; gi < h->ngroup; ++gi) {
+      const int npt = sp0[gi + 1] - sp0[gi];
+      int npl = 0; for (int k = 0; k < GRP_LMAX; ++k) if (gp[(size_t)gi*GRP_LMAX + k] >= 0) npl = k + 1;
+      r.grp_points_max = std::max(r.grp_points_max, npt); r.grp_points_min = std::min(r.grp_points_min, npt);
+      r.grp_poses_max = std::max(r.grp_poses_max, npl);
+      if (!npl) ++r.grp_no_pose;
+    }
+  }
+  r.lin_kernel = h->lin_kernel(); r.lin_generic = h->lin_generic() ? 1 : 0; r.schur_kernel = h->schur_kernel();
+  r.asm_long = (h->np && h->asm_long) ? 1 : 0; r.max_systems = h->batch_capacity();
+  *out = r;
+  return 0;
 }
 
 // reproducibility of the factorisation + back-substitution chain (test hook): see mcp_ba.h
