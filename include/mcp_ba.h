@@ -278,6 +278,41 @@ typedef struct mcp_ba_structure {
 } mcp_ba_structure;
 int mcp_ba_debug_structure(mcp_ba*, mcp_ba_structure* out);
 
+/* One route to the median of |chi2| the Huber kernel is scaled with (element [size/2] of the sorted array, MEstimator.h:194-204),
+ * fed an arbitrary chi2 array (test hook; prepares the handle if it is not prepared).  `chi2` holds exactly the handle's measurement
+ * count of values in DEVICE order (the order the kernels read, not add order) and replaces the chi2 of the current state;
+ * `prev_median` becomes the prediction the routes start from -- entry [3] of the current sigma block and the coarse bin the host
+ * keeps; a negative value means "no median seen yet".  The route then runs through the member functions the solver calls for it:
+ *   PLAIN  median_sigma(), one rank: two histogram passes, gather (SEL_GATHER_CAP), one-workgroup finish
+ *   RANKS  median_sigma() with a hook / communicator: all-reduced passes, slot table (MCP_BA_SELECT_CAP), remaining passes on overflow
+ *   RIDE   the tail of a trial (histograms around the prediction, all-reduce, scan), then median_sigma() as after its acceptance
+ *   SMALL  head_small(): one workgroup, at most SMALL_MEAS measurements
+ *   AHEAD  enqueue_head() + wait_head() (MCP_BA_HEAD_AHEAD=1), and median_sigma() if the head declines
+ *   LARGE  head_large() (MCP_BA_HEAD_LARGE=1)
+ * A route the handle is not configured for is refused with a message that names it; nothing is enqueued then.  Poses and points are
+ * not touched: a Compute() afterwards gives what it gives on a fresh handle. */
+#define MCP_BA_HEAD_PLAIN 0
+#define MCP_BA_HEAD_RANKS 1
+#define MCP_BA_HEAD_RIDE  2
+#define MCP_BA_HEAD_SMALL 3
+#define MCP_BA_HEAD_AHEAD 4
+#define MCP_BA_HEAD_LARGE 5
+typedef struct mcp_ba_head_report {
+  unsigned long long rank;       /* the rank selected: masked measurements + size/2 */
+  double median;                 /* as the route stored it */
+  double sigma[4];               /* the sigma block: raw sigma^2, limited sigma^2, its root, the median */
+  double robust_chi2;            /* SMALL, LARGE: the route's own sum; otherwise robust_chi2_plain */
+  double robust_chi2_plain;      /* k_robust_sum + k_final_sums over the same array at sigma[] */
+  double route_sigma[4];         /* AHEAD: the head's own sigma block, filled with the NaN pattern 0x7ff8000000c0ffee before the head ran */
+  int head_status;               /* AHEAD: the status word, 1 = sigma block written, 2 = declined; otherwise 0 */
+  int overflow;                  /* RANKS: the slot table overflowed; RIDE: the trial's scan said so; otherwise -1 */
+  int pred_ok;                   /* RIDE: the trial's scan found the median within one coarse bin of the prediction; otherwise -1 */
+  int select_overflow;           /* several ranks and the three-collective selection ran: its overflow flag; otherwise -1 */
+  int n_median_fast;             /* medians this call took from riding histograms (0 or 1) */
+  int declined;                  /* AHEAD with status 2, RIDE without a fast median: median_sigma()'s plain selection gave the result */
+} mcp_ba_head_report;
+int mcp_ba_debug_head(mcp_ba*, int route, const double* chi2, int n, double prev_median, mcp_ba_head_report* out);
+
 #ifdef __cplusplus
 }
 #endif

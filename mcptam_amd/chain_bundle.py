@@ -54,6 +54,14 @@ class McpBaStructure(ctypes.Structure):
         "grp_blk_max", "grp_inc_max", "lin_kernel", "lin_generic", "schur_kernel", "asm_long", "max_systems")]
 
 
+class McpBaHeadReport(ctypes.Structure):
+    _fields_ = [("rank", ctypes.c_ulonglong), ("median", ctypes.c_double), ("sigma", ctypes.c_double * 4),
+                ("robust_chi2", ctypes.c_double), ("robust_chi2_plain", ctypes.c_double), ("route_sigma", ctypes.c_double * 4),
+                ("head_status", ctypes.c_int), ("overflow", ctypes.c_int), ("pred_ok", ctypes.c_int),
+                ("select_overflow", ctypes.c_int), ("n_median_fast", ctypes.c_int), ("declined", ctypes.c_int)]
+
+
+HEAD_ROUTES = ("plain", "ranks", "ride", "small", "ahead", "large")      # MCP_BA_HEAD_* of include/mcp_ba.h
 LIN_KERNEL_NAMES = ("none", "quad", "pipe", "group")          # MCP_BA_LIN_* of include/mcp_ba.h
 SCHUR_KERNEL_NAMES = ("none", "schur4", "schur_group")        # MCP_BA_SCHUR_*
 
@@ -67,7 +75,7 @@ BA_SYMBOLS = [
     "mcp_ba_num_outliers", "mcp_ba_get_outliers", "mcp_ba_sigma_squared", "mcp_ba_mean_chi_squared", "mcp_ba_max_cov",
     "mcp_ba_lambda", "mcp_ba_num_iter_logs", "mcp_ba_get_iter_logs", "mcp_ba_get_timing", "mcp_ba_set_allreduce",
     "mcp_ba_prepare", "mcp_ba_eval", "mcp_ba_robust_chi2", "mcp_ba_debug_solve", "mcp_dense_spd_solve",
-    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
+    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_ba_debug_head", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
     "mcp_ba_struct_cache_stats", "mcp_ba_struct_cache_near_hits", "mcp_ba_struct_cache_clear",
     "mcp_comm_unique_id", "mcp_comm_init", "mcp_comm_destroy", "mcp_ba_set_comm", "mcp_comm_allreduce", "mcp_comm_allreduce_lane",
 ]
@@ -116,6 +124,7 @@ def lib():
     L.mcp_ba_debug_system.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p]
     L.mcp_ba_debug_systems.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p]
     L.mcp_ba_debug_structure.argtypes = [ctypes.c_void_p, ctypes.POINTER(McpBaStructure)]
+    L.mcp_ba_debug_head.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(McpBaHeadReport)]
     L.mcp_comm_unique_id.argtypes = [ctypes.c_void_p]
     L.mcp_comm_init.restype = ctypes.c_void_p
     L.mcp_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -375,6 +384,21 @@ class ChainBundle:
         d["schur_kernel"] = SCHUR_KERNEL_NAMES[d["schur_kernel"]]
         d["lin_generic"] = bool(d["lin_generic"])
         d["asm_long"] = bool(d["asm_long"])
+        return d
+
+    def DebugHead(self, route, chi2, prev_median):
+        """One route ("plain", "ranks", "ride", "small", "ahead", "large") to the Huber median over the chi2 array `chi2` (device
+        order, exactly the handle's measurement count) starting from the prediction `prev_median` (negative: none), run through
+        the member functions the solver calls for that route (test hook, mcp_ba_debug_head).  Returns the fields of
+        mcp_ba_head_report as a dict (`sigma` and `route_sigma` as float64 arrays); a route the handle is not configured for
+        raises with a message that names it."""
+        chi2 = np.ascontiguousarray(chi2, dtype=np.float64).reshape(-1)
+        rep = McpBaHeadReport()
+        if self._L.mcp_ba_debug_head(self._h, HEAD_ROUTES.index(route), _dp(chi2), len(chi2), float(prev_median), ctypes.byref(rep)) < 0:
+            raise RuntimeError("mcp_ba_debug_head: " + last_error())
+        d = {f: getattr(rep, f) for f, _ in McpBaHeadReport._fields_}
+        d["sigma"] = np.array(rep.sigma[:], dtype=np.float64)
+        d["route_sigma"] = np.array(rep.route_sigma[:], dtype=np.float64)
         return d
 
     def Compute(self, n_iter=None, user_lambda=-1.0):

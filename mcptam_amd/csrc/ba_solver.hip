@@ -852,6 +852,8 @@ struct mcp_ba {
   int select_kth(const double* x, int n, unsigned long long k, double* out_dev, bool huber_sigma = false);
   int select_gather_finish(const double* x, int n, const double* hist, SelState* state, double* out_dev, bool check_overflow);
   int median_sigma(int which);
+  int robust_total(hipStream_t s, int which, const double* sg, double* part, double* out, int off);
+  void take_trial_flags(int q) { tr_pred_ok[q] = h_res[MAIL_PRED_OK] != 0.0; tr_ovf[q] = h_res[MAIL_OVERFLOW] != 0.0; }      // what k_trial_post told the host about trial q's riding histograms
   int read_results(int count);
   int wait_mail(int q, unsigned long long ticket, int count);
   int enqueue_spec_trial(hipStream_t s, int q);
@@ -2434,6 +2436,14 @@ int mcp_ba::median_sigma(int w) {
   toc();
   return 0;
 }
+// activeRobustChi2 of state `w` at the sigma block `sg` on stream s: k_robust_sum's partial per EVAL_BLOCK values into `part`, then
+// k_final_sums' fixed order -> out[off]
+int mcp_ba::robust_total(hipStream_t s, int w, const double* sg, double* part, double* out, int off) {
+  const int nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
+  if (nbe) hipLaunchKernelGGL(k_robust_sum, dim3(nbe), dim3(EVAL_BLOCK), 0, s, P.nmeas, robust, (const double*)d_chi2[w].p, sg, part);
+  hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, s, nbe, (const double*)part, 0, (const double*)nullptr, 0, (const double*)nullptr, out, off, (const int*)nullptr);
+  return 0;
+}
 // waits for `ticket` in the mailbox of trial q (written by the trial's last kernel) and takes the forwarded block from there
 int mcp_ba::wait_mail(int q, unsigned long long ticket, int count) {
   const auto w0 = std::chrono::steady_clock::now();
@@ -2673,10 +2683,8 @@ int mcp_ba::head_small(int w, bool sum_aside) {
 // the iteration, which must not wait for the main stream's trial
 int mcp_ba::sum_aside() {
   if (sum_w < 0) return 0;
-  const int nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
   HIPCK(hipStreamWaitEvent(st2, ev_head, 0));
-  hipLaunchKernelGGL(k_robust_sum, dim3(nbe), dim3(EVAL_BLOCK), 0, st2, P.nmeas, robust, (const double*)d_chi2[sum_w].p, (const double*)sum_sig, d_parth.p);
-  hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st2, nbe, (const double*)d_parth.p, 0, (const double*)nullptr, 0, (const double*)nullptr, d_res.p, 24, (const int*)nullptr);
+  if (robust_total(st2, sum_w, sum_sig, d_parth.p, d_res.p, 24)) return -1;
   HIPCK(hipEventRecord(ev_sum, st2));
   sum_pending = true; sum_w = -1;
   return 0;
@@ -2931,7 +2939,7 @@ int mcp_ba::solve_trial(double lam, bool& ok2, double ni) {
     // the block (trial results [0..7], iteration-start block [24..28]) is already on its way to the host
     if (wait_mail(0, mail_ticket0, multi() ? MAIL_TICKET : 29)) return -1;
   } else if (read_results(MAIL_TICKET)) return -1;          // trial results [0..7] and, for compute(), the iteration-start block [24..28]
-  if (multi()) { tr_pred_ok[sys_cur] = h_res[MAIL_PRED_OK] != 0.0; tr_ovf[sys_cur] = h_res[MAIL_OVERFLOW] != 0.0; }
+  if (multi()) take_trial_flags(sys_cur);
   if (!nfl_total) h_res[1] = h_res[2] = 0.0;
   h_res[1] += h_res[6]; h_res[2] += h_res[7];
   if (h_res[3] >= 1e9) return persist_fallback(lam, ok2, ni);
@@ -2994,7 +3002,6 @@ int mcp_ba::compute(volatile unsigned char* abort_flag, int n_iter, double user_
       mark("iter", st);
       // preIteration + first robustify: sigma^2 from |chi2| at the iteration-start state
       constexpr int RS = 24;
-      const int nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
       // (small bundle: the head of this iteration was enqueued behind the trial that produced this state, before the host knew it
       //  would be accepted -- head_ahead(); all that is left is to make its sigma block the current one)
       bool head_done = (it > 0 && head_ahead_for == cur);
@@ -3020,8 +3027,7 @@ int mcp_ba::compute(volatile unsigned char* abort_flag, int n_iter, double user_
           // it is summed BESIDE the linearisation, on the second stream if there is one
           hipStream_t ss = (st2 && ev_sum) ? st2 : st;
           if (ss != st) HIPCK(hipStreamWaitEvent(ss, head_ev[q], 0));
-          if (nbe) hipLaunchKernelGGL(k_robust_sum, dim3(nbe), dim3(EVAL_BLOCK), 0, ss, P.nmeas, robust, (const double*)d_chi2[cur].p, (const double*)sig(), H.part);
-          hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, ss, nbe, (const double*)H.part, 0, (const double*)nullptr, 0, (const double*)nullptr, H.rs, 0, (const int*)nullptr);
+          if (robust_total(ss, cur, sig(), H.part, H.rs, 0)) return MCP_ERR_RUNTIME;
           if (ss != st) { HIPCK(hipEventRecord(ev_sum, ss)); sum_pending = true; }
           head_done = true; lin_done = true; ++dbg_head_ahead;
         } else { sig_idx = keep; ++dbg_head_miss; }
@@ -3036,11 +3042,10 @@ int mcp_ba::compute(volatile unsigned char* abort_flag, int n_iter, double user_
       else {
       if (robust) { if (median_sigma(cur)) return MCP_ERR_RUNTIME; }
       tic(ST_EVAL);
-      if (nbe) hipLaunchKernelGGL(k_robust_sum, dim3(nbe), dim3(EVAL_BLOCK), 0, st, P.nmeas, robust, (const double*)d_chi2[cur].p, (const double*)sig(), d_part0.p);
       // iteration-start robust chi2 and the sigma block go to d_res[24..28]; they are read back together with the first
       // trial's results (one host synchronisation less per iteration) -- except in the first iteration, whose lambda comes
       // from the diagonal of the freshly built system
-      hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st, nbe, (const double*)d_part0.p, 0, (const double*)nullptr, 0, (const double*)nullptr, d_res.p, RS, (const int*)nullptr);
+      if (robust_total(st, cur, sig(), d_part0.p, d_res.p, RS)) return MCP_ERR_RUNTIME;
       toc();
       }
       // several ranks: the sum over the ranks rides on the first trial's all-reduce (d_res[0..3] + d_res[4], see solve_trial);
@@ -3291,9 +3296,7 @@ int mcp_ba::final_stats(int nCounter) {
   if (use_head_large()) { if (head_large(cur, 0, d_res.p + 9)) return -2; }      // (the sigma block lands in d_res[9..12] too: no copy behind it)
   else {
   if (median_sigma(cur)) return -2;
-  const int nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
-  if (nbe) hipLaunchKernelGGL(k_robust_sum, dim3(nbe), dim3(EVAL_BLOCK), 0, st, P.nmeas, robust, (const double*)d_chi2[cur].p, (const double*)sig(), d_part0.p);
-  hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st, nbe, (const double*)d_part0.p, 0, (const double*)nullptr, 0, (const double*)nullptr, d_res.p, 0, (const int*)nullptr);
+  if (robust_total(st, cur, sig(), d_part0.p, d_res.p, 0)) return -2;
   if (allreduce(d_res.p, 1, 0, false, "final robust chi2")) return -2;
   HIPCK(hipMemcpyAsync(d_res.p + 9, sig(), 4*sizeof(double), hipMemcpyDeviceToDevice, st));
   }
@@ -3698,9 +3701,7 @@ int mcp_ba_robust_chi2(mcp_ba* h, double* sigma_sq_raw, double* chi2_sum) {
   h->launch_chains(h->cur);
   h->launch_eval(h->cur, false, nullptr);
   if (h->robust && h->median_sigma(h->cur)) return -1;
-  const int nbe = (n + EVAL_BLOCK - 1)/EVAL_BLOCK;
-  hipLaunchKernelGGL(k_robust_sum, dim3(nbe), dim3(EVAL_BLOCK), 0, h->st, n, h->robust, (const double*)h->d_chi2[h->cur].p, (const double*)h->sig(), h->d_part0.p);
-  hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, h->st, nbe, (const double*)h->d_part0.p, 0, (const double*)nullptr, 0, (const double*)nullptr, h->d_res.p, 0, (const int*)nullptr);
+  if (h->robust_total(h->st, h->cur, h->sig(), h->d_part0.p, h->d_res.p, 0)) return -1;
   if (h->allreduce(h->d_res.p, 1, 0, false, "robust chi2")) return -1;
   HIPCK(hipMemcpyAsync(h->d_res.p + 9, h->sig(), 4*sizeof(double), hipMemcpyDeviceToDevice, h->st));
   if (h->read_results(13)) return -1;
@@ -3780,6 +3781,109 @@ int mcp_ba_debug_structure(mcp_ba* h, mcp_ba_structure* out) {
   }
   r.lin_kernel = h->lin_kernel(); r.lin_generic = h->lin_generic() ? 1 : 0; r.schur_kernel = h->schur_kernel();
   r.asm_long = (h->np && h->asm_long) ? 1 : 0; r.max_systems = h->batch_capacity();
+  *out = r;
+  return 0;
+}
+
+// one route to the Huber median on a chi2 array of the caller's (test hook): see mcp_ba.h.  Every route is run through the member
+// functions compute() calls for it; nothing is launched from here but copies.
+int mcp_ba_debug_head(mcp_ba* h, int route, const double* chi2, int n, double prev_median, mcp_ba_head_report* out) {
+  static const char* const names[6] = { "plain", "ranks", "ride", "small", "ahead", "large" };
+  if (!chi2 || !out) { set_err("mcp_ba_debug_head: no chi2 array or no report block"); return -1; }
+  if (route < 0 || route > 5) { set_err("mcp_ba_debug_head: unknown route (MCP_BA_HEAD_PLAIN .. MCP_BA_HEAD_LARGE)"); return -1; }
+  if (h->dirty && h->prepare()) return -1;
+  HIPCK(hipSetDevice(h->device));
+  char msg[256];
+  if (n != h->P.nmeas) { snprintf(msg, sizeof msg, "mcp_ba_debug_head: chi2 holds %d values, the handle has %d measurements", n, h->P.nmeas); set_err(msg); return -1; }
+  const char* why = nullptr;
+  if (!h->robust) why = "the handle has no robust kernel";
+  else if (h->P.nmeas == 0 || h->m_total == 0) why = "the map has no measurement";
+  else if (route == MCP_BA_HEAD_PLAIN) { if (h->multi()) why = "an all-reduce hook or communicator is installed: the handle takes the multi-rank selection"; }
+  else if (route == MCP_BA_HEAD_RANKS) { if (!h->multi()) why = "no all-reduce hook or communicator is installed (or one rank without MCP_BA_FORCE_MULTI=1)"; }
+  else if (route == MCP_BA_HEAD_RIDE) {
+    if (!h->multi()) why = "no all-reduce hook or communicator is installed (or one rank without MCP_BA_FORCE_MULTI=1)";
+    else if (!h->sel_ride) why = "MCP_BA_SELECT_RIDE=0";
+    else if (!h->use_mailbox || !h->h_mail_dev) why = "MCP_BA_MAILBOX=0";
+  }
+  else if (route == MCP_BA_HEAD_SMALL) { if (!h->small_mode()) why = "not a small bundle (more than SMALL_MEAS measurements or SMALL_CHAINS chains, several ranks, or MCP_BA_SMALL=0)"; }
+  else if (route == MCP_BA_HEAD_AHEAD) { if (!h->large_heads()) why = "MCP_BA_HEAD_AHEAD is not set, or the map is a small bundle or has several ranks"; }
+  else if (!h->use_head_large()) why = "MCP_BA_HEAD_LARGE is not set, or the map is a small bundle or has several ranks";
+  if (why) { snprintf(msg, sizeof msg, "mcp_ba_debug_head: route %s refused: %s", names[route], why); set_err(msg); return -1; }
+
+  hipStream_t st = h->st;
+  const int w = h->cur;
+  if (h->join_sum()) return -1;
+  HIPCK(hipStreamSynchronize(st));
+  // the array, and the prediction the routes start from: the current median (sigma block [3]) and its coarse bin; a negative
+  // prev_median = no median seen yet (the state of a handle before its first iteration)
+  const bool seen = prev_median >= 0.0;
+  const double pm = seen ? prev_median : 0.0;
+  HIPCK(hipMemcpyAsync(h->d_chi2[w].p, chi2, (size_t)n*sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipMemcpyAsync(h->sig() + 3, &pm, sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCK(hipStreamSynchronize(st));
+  h->pred_bin = seen ? sel_coarse_bin(pm) : -1;
+  h->sel_src = -1;
+
+  mcp_ba_head_report r; std::memset(&r, 0, sizeof r);
+  r.rank = h->med_rank(); r.overflow = -1; r.pred_ok = -1; r.select_overflow = -1;
+  const int fast0 = h->timing.n_median_fast;
+  const double* sigp = nullptr;        // where the sigma block of the result lies
+  const double* medp = h->d_res.p + 8; // ... and the median as the route stored it
+  int own_off = -1;                    // d_res entry of the route's own robust chi2
+  unsigned long long nanbits = 0x7ff8000000c0ffeeull; double sentinel; std::memcpy(&sentinel, &nanbits, 8);
+  for (int i = 0; i < 4; ++i) r.route_sigma[i] = sentinel;
+  if (route == MCP_BA_HEAD_PLAIN || route == MCP_BA_HEAD_RANKS) {
+    if (h->median_sigma(w)) return -1;
+    sigp = h->sig();
+  } else if (route == MCP_BA_HEAD_RIDE) {
+    // the tail of a trial whose candidate state is the current one: digit histograms around the prediction, the trial's all-reduce,
+    // k_trial_post -> mailbox (the sums of the trial itself are empty here)
+    const unsigned long long ticket = ++h->mail_ticket;
+    if (h->multi_trial_tail(st, 0, 0, w, 0, h->d_part0.p, 0, nullptr, nullptr, h->d_res.p + 6, 6, false, h->h_mail_dev, MAIL_TICKET, ticket)) return -1;
+    if (h->wait_mail(0, ticket, MAIL_TICKET)) return -1;
+    h->take_trial_flags(0);
+    r.pred_ok = h->tr_pred_ok[0]; r.overflow = h->tr_ovf[0];
+    h->sel_src = 0;                    // ... and that trial was accepted
+    if (h->median_sigma(w)) return -1;
+    sigp = h->sig();
+  } else if (route == MCP_BA_HEAD_SMALL) {
+    if (h->head_small(w)) return -1;
+    sigp = h->sig(); own_off = 24;
+  } else if (route == MCP_BA_HEAD_LARGE) {
+    if (h->head_large(w, 24, nullptr)) return -1;
+    sigp = h->sig(); own_off = 24;
+  } else {
+    // the head a trial on the main stream carries (system 0 of the current parity); its sigma block is filled with a NaN pattern
+    // first, so that a head that declines can be seen to have written nothing
+    const int q = 0;
+    double* slot = h->sig_block(2 + h->head_par*MAX_SYS + q);
+    HIPCK(hipMemcpyAsync(slot, r.route_sigma, 4*sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (h->enqueue_head(st, q, w, false)) return -1;
+    const int hs = h->wait_head(q);
+    h->head_enq[q] = false; h->head_state[q] = -1;
+    if (hs < 0) return -1;
+    r.head_status = hs;
+    HIPCK(hipMemcpyAsync(r.route_sigma, slot, 4*sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (hs == 1) { sigp = slot; medp = h->hsc[h->head_par*MAX_SYS + q].out; }
+    else { if (h->median_sigma(w)) return -1; sigp = h->sig(); }      // (as compute() does when a head declines)
+  }
+  r.n_median_fast = h->timing.n_median_fast - fast0;
+  if (h->multi() && r.n_median_fast == 0) r.select_overflow = h->h_res[30] != 0.0;
+  if (route == MCP_BA_HEAD_RANKS) r.overflow = r.select_overflow;
+  r.declined = (route == MCP_BA_HEAD_AHEAD && r.head_status != 1) || (route == MCP_BA_HEAD_RIDE && r.n_median_fast == 0);
+  // the robust chi2 at the new sigma block by the separate kernels
+  if (h->robust_total(st, w, sigp, h->d_part0.p, h->d_res.p, 0)) return -1;
+  double own = 0.0;
+  HIPCK(hipMemcpyAsync(&r.robust_chi2_plain, h->d_res.p, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (own_off >= 0) HIPCK(hipMemcpyAsync(&own, h->d_res.p + own_off, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(r.sigma, sigp, 4*sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(&r.median, medp, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  r.robust_chi2 = own_off >= 0 ? own : r.robust_chi2_plain;
+  if (route == MCP_BA_HEAD_LARGE) { unsigned long long b; std::memcpy(&b, &own, 8); if (b == HL_FAILED_BITS) { set_err("mcp_ba_debug_head: the head (k_head_large) gave up at a barrier"); return -1; } }
+  if (!h->launch_err.empty()) { set_err("mcp_ba_debug_head: launch refused: " + h->launch_err); h->launch_err.clear(); return -1; }
   *out = r;
   return 0;
 }
