@@ -716,6 +716,37 @@ int mcp_track_frame_recover(mcp_map_points*, int ncam, mcp_kf* const* targets, c
 int mcp_track_recover_pose_host(const double se2[6], const mcp_camera* cam_sbi, const double cam_from_world_best[12], const double cam_from_base[12],
                                 double out_cam_pose[12], double out_base_from_world[12]);
 
+/* ---- Tracker::CalcPoseUpdate's pose covariance (mm6PoseCovariance) ----------------------------------------------- src/Tracker.cc:1441, 1498-1502
+ * info = sum over the found records with weight != 0 of w J^T J (J: the 2 x 6 Jacobian of the last fine iteration, rows scaled by
+ * sqrt_inv_noise) + 100 I (WLS<6>::add_prior(100), get_C_inv()); cov = its pseudo-inverse (TooN SVD<6>::get_pinv, condition number 1e9: the
+ * eigenvalue lambda_i is kept iff lambda_i 1e9 > lambda_max), by a cyclic Jacobi eigen-decomposition that ends after a sweep without a
+ * rotation and after MCP_POSE_COV_MAX_SWEEPS sweeps at the latest.  Both are exactly symmetric; TooN order [t; w], row-major.
+ * DEVIATION: the reference linearises at the pose it held before the last update; here that pose is rebuilt as exp(-mu_last) * refined (equal
+ * to rounding) and the Jacobians are formed from the records as the last re-projection left them (world position, cam_derivs).
+ * ORDER: records in tiles of 256 in record order, 64 at a time through a fixed butterfly, the four sums in order, the tiles in ascending order:
+ * the bits depend neither on the grid nor on the run.  mcp_track_pose_cov_host walks the same order under the host compiler (no GPU). */
+#define MCP_POSE_COV_MAX_SWEEPS 16
+typedef struct mcp_track_pose_cov_record {
+  int valid;       /* 1 filled; 0 no fine iterations ran (gate closed: nobody recovered); -1 non-finite sums: cov, eig and norm_fro are zeros */
+  int n_used;      /* found records with weight != 0 */
+  int rank, sweeps;   /* eigenvalues kept; sweeps that rotated */
+  double info[36], cov[36], eig[6], norm_fro;   /* eig: of info, descending; norm_fro: of cov (GetCurrentCovarianceNorm's first factor) */
+} mcp_track_pose_cov_record;
+/* on != 0: mcp_track_map, mcp_track_map_record, mcp_track_frame_motion and mcp_track_frame_recover append the covariance's two launches behind
+ * the fine iterations, in the same submission and behind the same wait; every other output keeps its bits.  Default off: no launch more. */
+int mcp_track_pose_cov_enable(mcp_map_points*, int on);
+/* the record of the last track call on the table: mcp_track_pose_cov's bits for that call's fine records, last weights, refined pose and
+ * mu_last.  -1 + mcp_last_error() unless that call succeeded with the switch on. */
+int mcp_track_pose_cov_last(const mcp_map_points*, mcp_track_pose_cov_record* out);
+/* the same two kernels on the caller's arrays (weights: one per record); max_workgroups = 0: the library's choice */
+int mcp_track_pose_cov(int n, const mcp_pose_point* pts, const double* weights, int ncam, const double* cam_from_base /* ncam x 12 */,
+                       const double refined[12], const double mu_last[6], int max_workgroups, mcp_track_pose_cov_record* out);
+int mcp_track_pose_cov_host(int n, const mcp_pose_point* pts, const double* weights, int ncam, const double* cam_from_base /* ncam x 12 */,
+                            const double refined[12], const double mu_last[6], mcp_track_pose_cov_record* out);
+/* for tests: the fine records, last weights and mu_last of the last successful track call on the table, as they stand on the device; *n
+ * receives the count (more than cap: -1, nothing copied).  Waits for the table's stream. */
+int mcp_debug_track_fine_records(const mcp_map_points*, int cap, mcp_pose_point* pts, double* weights, double mu_last[6], int* n);
+
 /* ---- MapMakerServerBase::ReFind_Common over the table in ONE submission ---------------------------- src/MapMakerServerBase.cc:921-1080
  * ReFindInSingleKeyFrame (every point of the map against a new keyframe), ReFindNewlyMade (every new point against every keyframe) and
  * ReFindFromFailureQueue all run ReFind_Common per (keyframe, point) pair.  The caller keeps the early-outs that read its own sets (:925-937:

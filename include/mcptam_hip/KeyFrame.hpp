@@ -391,6 +391,25 @@ class MapPointTable {
   }
   /// Tracker::Reset: every camera index forgets its SmallBlurryImages
   void MotionReset() { check(mcp_track_motion_reset(mpDev)); }
+  /// mm6PoseCovariance (src/Tracker.cc:1498-1502) from the one-call frames: with the switch on TrackMap / TrackMapRecord / TrackFrameMotion /
+  /// TrackFrameRecover append its two launches behind the fine iterations; PoseCovLast hands out the record of the last such call
+  void PoseCovEnable(bool bOn) { check(mcp_track_pose_cov_enable(mpDev, bOn ? 1 : 0)); }
+  mcp_track_pose_cov_record PoseCovLast() const { mcp_track_pose_cov_record r; check(mcp_track_pose_cov_last(mpDev, &r)); return r; }
+  /// the same two kernels on caller arrays (nMaxWorkgroups = 0: the library's choice), and the same source on the host (no device needed)
+  static mcp_track_pose_cov_record PoseCov(const std::vector<mcp_pose_point>& vPts, const std::vector<double>& vWeights, const std::vector<double>& vCamFromBase,
+                                           const double refined[12], const double mu_last[6], int nMaxWorkgroups = 0) {
+    if (vPts.size() != vWeights.size() || vCamFromBase.size() % 12 != 0) throw std::invalid_argument("PoseCov: one weight per record, 12 doubles per camera");
+    mcp_track_pose_cov_record r;
+    check(mcp_track_pose_cov((int)vPts.size(), vPts.data(), vWeights.data(), (int)(vCamFromBase.size()/12), vCamFromBase.data(), refined, mu_last, nMaxWorkgroups, &r));
+    return r;
+  }
+  static mcp_track_pose_cov_record PoseCovHost(const std::vector<mcp_pose_point>& vPts, const std::vector<double>& vWeights, const std::vector<double>& vCamFromBase,
+                                               const double refined[12], const double mu_last[6]) {
+    if (vPts.size() != vWeights.size() || vCamFromBase.size() % 12 != 0) throw std::invalid_argument("PoseCovHost: one weight per record, 12 doubles per camera");
+    mcp_track_pose_cov_record r;
+    check(mcp_track_pose_cov_host((int)vPts.size(), vPts.data(), vWeights.data(), (int)(vCamFromBase.size()/12), vCamFromBase.data(), refined, mu_last, &r));
+    return r;
+  }
   /// the tracker's SBI of camera index nCam (nWhich 0: this frame's, 1: last frame's): 1200 bytes, 1200 floats, 2400 floats; nullptr: not wanted
   void MotionSBI(int nCam, int nWhich, uint8_t* pSmall, float* pTemplate, float* pJacs) const { check(mcp_track_motion_get_sbi(mpDev, nCam, nWhich, pSmall, pTemplate, pJacs)); }
   /// nullptr with *pnCount == 0: the camera's list is empty -- or the last track / PVS call was no TrackMapRecord with that camera (mcp_last_error())

@@ -25,6 +25,7 @@
 #include "track_record_kernels.h"
 #include "track_motion_kernels.h"
 #include "track_recover_kernels.h"
+#include "track_cov_kernels.h"
 #include "ba_bridge.h"
 #include "ba_select.h"
 
@@ -1172,6 +1173,13 @@ struct mcp_map_points {
               cam_out.alloc(MCP_MAX_FRAME_CAMS) || gate.alloc(1) || h_out.alloc(1)) ? -1 : 0;
     }
   } rc;
+  // mcp_track_pose_cov_enable: the tile partials and counts, the pinned record; what mcp_debug_track_fine_records needs of the last call
+  struct Cv {
+    Buf<double> part; Buf<int> used; PinBuf<mcp_track_pose_cov_record> h_out;
+    bool on = false, ok = false, fine_ok = false; int n_fine = 0; double mu[6] = {};
+    int reserve(size_t nb) { const size_t tiles = (nb + COV_TILE - 1)/COV_TILE; return (part.alloc(COV_NPROD*tiles) || used.alloc(tiles) || h_out.alloc(1)) ? -1 : 0; }
+    void invalidate() { ok = false; fine_ok = false; }
+  } cv;
   // mcp_map_refind: the packed inputs (pinned | device), the passes' scratch, the pinned results (RfOut | verdict bytes | measurements)
   struct Rf {
     PinBuf<char> in; Buf<char> dev; Buf<uint8_t> flags, vd; Buf<int> blk, first; Buf<RfItem> items; Buf<mcp_refind_meas> cand; PinBuf<char> out;
@@ -1376,7 +1384,7 @@ struct Drain {
     if (!armed) return;
     (void)hipStreamSynchronize(m->st);
     if (lite) { (void)hipStreamSynchronize(lite[0]->st); (void)lite_batch_finish(ncam, lite); }
-    if (track) { m->pvs.tab_last.clear(); m->tm.invalidate(); }
+    if (track) { m->pvs.tab_last.clear(); m->tm.invalidate(); m->cv.invalidate(); }
     (void)hipGetLastError();
   }
 };
@@ -1436,7 +1444,7 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
 int mcp_track_find_pvs(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb,
                        const int* caps, mcp_pvs_entry* const* out, int* counts) {
   if (!m) return img_fail("mcp_track_find_pvs: NULL table");
-  m->pvs.invalidate(); m->tr.invalidate();
+  m->pvs.invalidate(); m->tr.invalidate(); m->cv.invalidate();
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !caps || !counts) return img_fail("mcp_track_find_pvs: bad arguments");
   for (int c = 0; c < ncam; ++c) {
     if (!targets[c] || !cam_ok(&cams[c]) || caps[c] < 0 || (out && !out[c])) return img_fail("mcp_track_find_pvs: bad arguments for camera " + std::to_string(c));
@@ -1584,6 +1592,97 @@ static int recover_check(const std::string& who, const mcp_map_points* m, int nc
   return 0;
 }
 
+// ---- the pose covariance of the last fine iteration (track_cov_kernels.h) -----------------------------------------------------------------
+// the two launches on `st`: the record count is n, or *n_dev where given; cap bounds it (the buffers' size) and the grid.  max_wg = 0: the
+// library's choice
+static int pose_cov_enqueue(hipStream_t st, int n, const int* n_dev, const int* gate, size_t cap, const mcp_pose_point* pts, const double* w, const double* d_cfb,
+                            const double* d_refined, const double* d_mu, int max_wg, double* part, int* used, mcp_track_pose_cov_record* h_out) {
+  const size_t tiles = std::max<size_t>((cap + COV_TILE - 1)/COV_TILE, 1);
+  const unsigned grid = (unsigned)std::min<size_t>(tiles, max_wg > 0 ? (size_t)max_wg : 256);
+  hipLaunchKernelGGL(k_pose_cov_tiles, dim3(grid), dim3(COV_TILE), 0, st, n, n_dev, gate, (int)cap, pts, w, d_cfb, d_refined, d_mu, part, used);
+  hipLaunchKernelGGL(k_pose_cov_finish, dim3(1), dim3(64), 0, st, n, n_dev, gate, (int)cap, (const double*)part, (const int*)used, h_out);
+  ICK(hipGetLastError());
+  return 0;
+}
+static int pose_cov_check(const std::string& who, int n, const mcp_pose_point* pts, const double* weights, int ncam, const double* cfb, const double* refined,
+                          const double* mu_last, const mcp_track_pose_cov_record* out) {
+  if (n < 0 || ncam < 1 || !cfb || !refined || !mu_last || !out || (n > 0 && (!pts || !weights))) return img_fail(who + ": bad arguments");
+  for (int i = 0; i < n; ++i) if (pts[i].cam < 0 || pts[i].cam >= ncam) return img_fail(who + ": camera index out of range");
+  return 0;
+}
+int mcp_track_pose_cov_host(int n, const mcp_pose_point* pts, const double* weights, int ncam, const double* cfb, const double refined[12], const double mu_last[6],
+                            mcp_track_pose_cov_record* out) {
+  if (pose_cov_check("mcp_track_pose_cov_host", n, pts, weights, ncam, cfb, refined, mu_last, out)) return -1;
+  double pose[12], sums[COV_NPROD];
+  cov_pose_before(refined, mu_last, pose);
+  for (int k = 0; k < COV_NPROD; ++k) sums[k] = 0.0;
+  int used = 0;
+  for (int first = 0; first < n; first += COV_TILE) {      // the tiles in ascending order, as k_pose_cov_finish adds them
+    double part[COV_NPROD];
+    used += cov_tile_host(n, first, pts, weights, pose, cfb, part);
+    for (int k = 0; k < COV_NPROD; ++k) sums[k] += part[k];
+  }
+  CovWork W;
+  cov_finish(sums, used, W, out);
+  return 0;
+}
+struct CovScratch { Buf<mcp_pose_point> pts; Buf<double> w, blk, part; Buf<int> used; PinBuf<mcp_track_pose_cov_record> h_out; };
+static CovScratch& cov_scratch() {      // one per (thread, device), as refine_scratch
+  static thread_local std::map<int, std::unique_ptr<CovScratch>> per_dev;
+  int dev = 0; (void)hipGetDevice(&dev);
+  std::unique_ptr<CovScratch>& p = per_dev[dev];
+  if (!p) p.reset(new CovScratch());
+  return *p;
+}
+int mcp_track_pose_cov(int n, const mcp_pose_point* pts, const double* weights, int ncam, const double* cfb, const double refined[12], const double mu_last[6],
+                       int max_workgroups, mcp_track_pose_cov_record* out) {
+  if (pose_cov_check("mcp_track_pose_cov", n, pts, weights, ncam, cfb, refined, mu_last, out)) return -1;
+  if (max_workgroups < 0) return img_fail("mcp_track_pose_cov: negative max_workgroups");
+  int ndev = 0; if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return img_fail("mcp_track_pose_cov: no HIP device");
+  CovScratch& cs = cov_scratch();
+  const size_t cap = (size_t)std::max(n, 1), tiles = (cap + COV_TILE - 1)/COV_TILE, nblk = 18 + 12*(size_t)ncam;      // (refined | mu | CamFromBase)
+  if (cs.pts.alloc(cap) || cs.w.alloc(cap) || cs.blk.alloc(nblk) || cs.part.alloc(COV_NPROD*tiles) || cs.used.alloc(tiles) || cs.h_out.alloc(1)) return -1;
+  std::vector<double> hb(nblk);
+  std::memcpy(hb.data(), refined, 96); std::memcpy(hb.data() + 12, mu_last, 48); std::memcpy(hb.data() + 18, cfb, 96*(size_t)ncam);
+  hipStream_t st = nullptr;
+  ICK(hipMemcpy(cs.blk.p, hb.data(), 8*nblk, hipMemcpyHostToDevice));
+  if (n > 0) {
+    ICK(hipMemcpy(cs.pts.p, pts, sizeof(mcp_pose_point)*(size_t)n, hipMemcpyHostToDevice));
+    ICK(hipMemcpy(cs.w.p, weights, 8*(size_t)n, hipMemcpyHostToDevice));
+  }
+  std::memset(cs.h_out.p, 0, sizeof(mcp_track_pose_cov_record));
+  if (pose_cov_enqueue(st, n, nullptr, nullptr, cap, cs.pts.p, cs.w.p, cs.blk.p + 18, cs.blk.p, cs.blk.p + 12, max_workgroups, cs.part.p, cs.used.p, cs.h_out.p)) return -1;
+  ICK(hipStreamSynchronize(st));
+  *out = *cs.h_out.p;
+  return 0;
+}
+int mcp_track_pose_cov_enable(mcp_map_points* m, int on) {
+  if (!m) return img_fail("mcp_track_pose_cov_enable: NULL table");
+  m->cv.on = on != 0;
+  return 0;
+}
+int mcp_track_pose_cov_last(const mcp_map_points* m, mcp_track_pose_cov_record* out) {
+  if (!m || !out) return img_fail("mcp_track_pose_cov_last: NULL table or record");
+  if (!m->cv.ok) return img_fail("mcp_track_pose_cov_last: the last track call on this table did not succeed with mcp_track_pose_cov_enable on");
+  *out = *m->cv.h_out.p;
+  return 0;
+}
+int mcp_debug_track_fine_records(const mcp_map_points* mc, int cap, mcp_pose_point* pts, double* weights, double mu_last[6], int* n) {
+  if (!mc || !n || !mu_last || cap < 0 || (cap > 0 && (!pts || !weights))) return img_fail("mcp_debug_track_fine_records: bad arguments");
+  if (!mc->cv.fine_ok) return img_fail("mcp_debug_track_fine_records: the last track call on this table did not succeed");
+  *n = mc->cv.n_fine;
+  if (mc->cv.n_fine > cap) return img_fail("mcp_debug_track_fine_records: " + std::to_string(mc->cv.n_fine) + " records, room for " + std::to_string(cap));
+  mcp_map_points* m = const_cast<mcp_map_points*>(mc);
+  ICK(hipSetDevice(m->device));
+  ICK(m->sync());
+  if (m->cv.n_fine > 0) {
+    ICK(hipMemcpy(pts, m->tm.frec.p, sizeof(mcp_pose_point)*(size_t)m->cv.n_fine, hipMemcpyDeviceToHost));
+    ICK(hipMemcpy(weights, m->tm.w.p, 8*(size_t)m->cv.n_fine, hipMemcpyDeviceToHost));
+  }
+  std::memcpy(mu_last, m->cv.mu, 48);
+  return 0;
+}
+
 // the body of mcp_track_map (rp == NULL: exactly its launches), of mcp_track_map_record (rp, rec checked by the caller), of
 // mcp_track_frame_motion (mo: k_frame_sbi and k_motion_prior between the pyramids' event and the PVS, which then reads the pose from the
 // parameter block, and k_motion_update behind the fine iterations; mo == NULL: no launch more or less than before) and of
@@ -1610,7 +1709,7 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   const int ncand = rc ? rc->ncand : 0;
   ICK(hipSetDevice(m->device));
   // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
-  m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate();
+  m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate(); m->cv.invalidate();
   const bool want_items = !rp || rp->want_items != 0;
   const int n = m->rows;
   const size_t NB = (size_t)ncam*std::max(n, 1);                   // bound of every per-item array: a camera's sets are distinct rows
@@ -1640,6 +1739,11 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
       if (k->sbi_small.alloc(SBI_N) || k->sbi_templ.alloc(SBI_N) || k->sbi_jacs.alloc(2*SBI_N) || k->sbi_last_small.alloc(SBI_N) || k->sbi_last_templ.alloc(SBI_N) ||
           k->sbi_last_jacs.alloc(2*SBI_N)) return -1;
     }
+  }
+  const bool cov = m->cv.on;                                         // mcp_track_pose_cov_enable: two launches behind the fine iterations
+  if (cov) {
+    if (m->cv.reserve(NB)) return -1;
+    std::memset(m->cv.h_out.p, 0, sizeof(mcp_track_pose_cov_record));        // (valid = 0 unless k_pose_cov_finish runs)
   }
   const size_t n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK;
   if (rp) {
@@ -1782,6 +1886,8 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, m->pts.row(),
                      m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
   if (iterate(NB, &ctl->n_fine, nullptr, m->tm.frec.p, 1)) return -1;
+  if (cov && pose_cov_enqueue(st, 0, &ctl->n_fine, rc ? m->rc.gate.p : nullptr, NB, m->tm.frec.p, m->tm.w.p, d_cfb, d_pm, d_pm + 12, 0, m->cv.part.p, m->cv.used.p,
+                              m->cv.h_out.p)) return -1;
   if (mo) {      // UpdateMotionModel, from the refined pose
     Pose12 start; std::memcpy(start.v, bfw, 96);
     hipLaunchKernelGGL(k_motion_update, dim3(1), dim3(64), 0, st, (const double*)d_pm, start, *mo->p, m->mo.h_out.p);
@@ -1831,6 +1937,7 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
   }
   m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
   std::memcpy(res->mu_last, R.mu, 48);
+  m->cv.ok = cov; m->cv.fine_ok = true; m->cv.n_fine = R.ctl.n_fine; std::memcpy(m->cv.mu, R.mu, 48);
   if (mo) *mo->out = *m->mo.h_out.p;
   if (rc) {
     *rc->out = *m->rc.h_out.p;

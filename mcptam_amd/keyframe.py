@@ -53,6 +53,7 @@ IMG_SYMBOLS = [
     "mcp_track_map_meas_view",
     "mcp_track_frame_motion", "mcp_track_motion_reset", "mcp_track_motion_get_sbi", "mcp_track_motion_prior_host", "mcp_track_motion_update_host",
     "mcp_track_frame_recover", "mcp_track_recover_pose_host",
+    "mcp_track_pose_cov_enable", "mcp_track_pose_cov_last", "mcp_track_pose_cov", "mcp_track_pose_cov_host", "mcp_debug_track_fine_records",
 ]
 _BOUND = False
 

@@ -424,6 +424,26 @@ class MapPointTable:
         return small, templ, jacs
 
 
+    # ---- the pose covariance of the last fine iteration (include/mcp_img.h mcp_track_pose_cov_enable) ----
+    def pose_cov_enable(self, on=True):
+        """With it on, track_map / track_map_record / track_frame_motion / track_frame_recover also leave mm6PoseCovariance (pose_cov_last)."""
+        _chk(_bind_track_cov(self._L).mcp_track_pose_cov_enable(self._h, int(bool(on))), "track_pose_cov_enable")
+
+    def pose_cov_last(self):
+        """The TrackPoseCov of the last track call on this table; raises unless that call succeeded with pose_cov_enable on."""
+        out = TrackPoseCov()
+        _chk(_bind_track_cov(self._L).mcp_track_pose_cov_last(self._h, ctypes.byref(out)), "track_pose_cov_last")
+        return out
+
+    def debug_fine_records(self):
+        """(records (POSE_POINT_DTYPE), weights, mu_last) of the last track call's fine iterations, copied from the device; for tests."""
+        from .keyframe import POSE_POINT_DTYPE
+        L = _bind_track_cov(self._L)
+        cap = max(MAX_FRAME_CAMS * max(self.rows, 1), 1)
+        pts, w, mu, n = np.zeros(cap, dtype=POSE_POINT_DTYPE), np.zeros(cap), np.zeros(6), ctypes.c_int(0)
+        _chk(L.mcp_debug_track_fine_records(self._h, cap, pts.ctypes.data, w.ctypes.data, mu.ctypes.data, ctypes.byref(n)), "debug_track_fine_records")
+        return pts[:n.value].copy(), w[:n.value].copy(), mu
+
 # ---- Tracker::TrackMap of a frame from the table (include/mcp_img.h mcp_track_map) ---------------------------------------------------
 TRACK_MAP_SYMBOLS = ["mcp_map_points_set_source", "mcp_map_points_update_source", "mcp_map_points_get_states", "mcp_track_map", "mcp_track_map_view",
                      "mcp_mix64", "mcp_track_shuffle_key"]
@@ -1021,3 +1041,118 @@ def recover_restate(cur_templs, cand_templs, cand_cams, cand_poses, aligns, cams
             Rp, tp = out["cam_pose"][c]
             out["recovered"], out["cam"], out["base_from_world"] = True, c, (Rc.T @ Rp, Rc.T @ (tp - tc))
     return out
+
+
+# ---- the pose covariance of the last fine iteration (include/mcp_img.h mcp_track_pose_cov) and its numpy restatement ----------------------
+TRACK_COV_SYMBOLS = ["mcp_track_pose_cov_enable", "mcp_track_pose_cov_last", "mcp_track_pose_cov", "mcp_track_pose_cov_host", "mcp_debug_track_fine_records"]
+POSE_COV_MAX_SWEEPS, POSE_COV_PRIOR, POSE_COV_CONDITION = 16, 100.0, 1e9
+
+
+class TrackPoseCov(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int), ("n_used", ctypes.c_int), ("rank", ctypes.c_int), ("sweeps", ctypes.c_int), ("info", ctypes.c_double * 36),
+                ("cov", ctypes.c_double * 36), ("eig", ctypes.c_double * 6), ("norm_fro", ctypes.c_double)]
+
+
+def _bind_track_cov(L):
+    if getattr(L, "_track_cov_bound", False):
+        return L
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.mcp_track_pose_cov_enable.argtypes = [vp, ip]
+    L.mcp_track_pose_cov_last.argtypes = [vp, vp]
+    L.mcp_track_pose_cov.argtypes = [ip, vp, vp, ip, vp, vp, vp, ip, vp]
+    L.mcp_track_pose_cov_host.argtypes = [ip, vp, vp, ip, vp, vp, vp, vp]
+    L.mcp_debug_track_fine_records.argtypes = [vp, ip, vp, vp, vp, vp]
+    L._track_cov_bound = True
+    return L
+
+
+def _cov_args(pts, weights, cams_from_base, refined, mu_last):
+    from .keyframe import POSE_POINT_DTYPE
+    pts = np.ascontiguousarray(pts, dtype=POSE_POINT_DTYPE)
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != len(pts):
+        raise ValueError("pose covariance: %d records, %d weights" % (len(pts), len(w)))
+    cfb = np.ascontiguousarray(cams_from_base, dtype=np.float64).reshape(-1, 12) if isinstance(cams_from_base, np.ndarray) else \
+        np.ascontiguousarray(np.stack([_pose12(*c) for c in cams_from_base]))
+    ref = np.ascontiguousarray(refined, dtype=np.float64).reshape(12) if isinstance(refined, np.ndarray) else _pose12(*refined).copy()
+    mu = np.ascontiguousarray(mu_last, dtype=np.float64).reshape(6)
+    return pts, w, cfb, ref, mu
+
+
+def pose_cov(pts, weights, cams_from_base, refined, mu_last, max_workgroups=0):
+    """mcp_track_pose_cov on the GPU: records (POSE_POINT_DTYPE), one weight per record, CamFromBase per camera ((R, t) pairs or (ncam, 12)),
+    the refined pose ((R, t) or 12 doubles) and the last update.  Returns the TrackPoseCov."""
+    pts, w, cfb, ref, mu = _cov_args(pts, weights, cams_from_base, refined, mu_last)
+    out = TrackPoseCov()
+    _chk(_bind_track_cov(lib()).mcp_track_pose_cov(len(pts), pts.ctypes.data, w.ctypes.data, len(cfb), cfb.ctypes.data, ref.ctypes.data, mu.ctypes.data,
+                                                   int(max_workgroups), ctypes.byref(out)), "track_pose_cov")
+    return out
+
+
+def pose_cov_host(pts, weights, cams_from_base, refined, mu_last):
+    """mcp_track_pose_cov_host: the same source under the host compiler, in the device's order; needs no GPU."""
+    pts, w, cfb, ref, mu = _cov_args(pts, weights, cams_from_base, refined, mu_last)
+    out = TrackPoseCov()
+    _chk(_bind_track_cov(lib()).mcp_track_pose_cov_host(len(pts), pts.ctypes.data, w.ctypes.data, len(cfb), cfb.ctypes.data, ref.ctypes.data, mu.ctypes.data,
+                                                        ctypes.byref(out)), "track_pose_cov_host")
+    return out
+
+
+def pose_cov_arrays(rec):
+    """(info 6x6, cov 6x6, eig) of a TrackPoseCov as numpy arrays."""
+    return np.array(rec.info).reshape(6, 6), np.array(rec.cov).reshape(6, 6), np.array(rec.eig)
+
+
+def pinv_truncated(info, condition=POSE_COV_CONDITION):
+    """TooN SVD::get_pinv of a symmetric matrix: eigenvalue i is kept iff lambda_i * condition > lambda_max.  Returns (pinv, eigenvalues
+    descending, rank)."""
+    lam, V = np.linalg.eigh(np.asarray(info, dtype=np.float64))
+    keep = lam * condition > lam.max()
+    P = (V[:, keep] / lam[keep]) @ V[:, keep].T
+    return 0.5 * (P + P.T), lam[::-1].copy(), int(keep.sum())
+
+
+def pose_jacobian(world_pos, cam_derivs, cam_from_base, pose):
+    """The 2 x 6 Jacobian of Tracker::CalcJacobian (TrackerData.h) at the pose (R, t): cam_derivs (2x2) * [dtheta; dphi] / d(xc) * Rc *
+    [I | -[xb]x], twist order [t; w]."""
+    R, t = pose
+    Rc, tc = np.asarray(cam_from_base[0], dtype=np.float64), np.asarray(cam_from_base[1], dtype=np.float64)
+    xb = np.asarray(R) @ np.asarray(world_pos, dtype=np.float64) + np.asarray(t)
+    x, y, z = Rc @ xb + tc
+    n2 = x * x + y * y
+    n = math.sqrt(n2)
+    S = np.zeros((2, 3))
+    if n != 0.0:
+        S[0] = [-z * x / (n * (n2 + z * z)), -z * y / (n * (n2 + z * z)), n / (n2 + z * z)]
+        S[1] = [-y / n2, x / n2, 0.0]
+    G = np.concatenate([np.eye(3), -_hat(xb)], axis=1)
+    return np.asarray(cam_derivs, dtype=np.float64).reshape(2, 2) @ S @ Rc @ G
+
+
+def pose_covariance_restate(pts, weights, cams_from_base, refined, mu_last, pose_before=None):
+    """mm6PoseCovariance (src/Tracker.cc:1441, 1498-1502) in numpy: the pose before the last update as exp(-mu_last) * refined (or given),
+    every found record's weighted Jacobian products summed with math.fsum, the prior 100 I, numpy.linalg.eigh with TooN's truncation.
+    cams_from_base: (R, t) per camera.  Returns dict(info, cov, eig, rank, n_used, pose_before)."""
+    if pose_before is None:
+        Re, te = se3_exp(-np.asarray(mu_last, dtype=np.float64))
+        Rr, tr = np.asarray(refined[0], dtype=np.float64), np.asarray(refined[1], dtype=np.float64)
+        pose_before = (Re @ Rr, Re @ tr + te)
+    terms = [[[] for _ in range(6)] for _ in range(6)]
+    n_used = 0
+    for p, w in zip(pts, weights):
+        if not p["found"] or w == 0.0:
+            continue
+        n_used += 1
+        J = float(p["sqrt_inv_noise"]) * pose_jacobian(p["world_pos"], p["cam_derivs"], cams_from_base[int(p["cam"])], pose_before)
+        for r in range(2):
+            for x in range(6):
+                for y in range(x + 1):
+                    terms[x][y].append(float(w) * J[r, x] * J[r, y])
+    info = np.zeros((6, 6))
+    for x in range(6):
+        for y in range(x + 1):
+            info[x, y] = info[y, x] = math.fsum(terms[x][y]) + (POSE_COV_PRIOR if x == y else 0.0)
+    if not np.all(np.isfinite(info)):
+        return dict(info=info, cov=np.zeros((6, 6)), eig=np.zeros(6), rank=0, n_used=n_used, pose_before=pose_before, valid=-1)
+    cov, eig, rank = pinv_truncated(info)
+    return dict(info=info, cov=cov, eig=eig, rank=rank, n_used=n_used, pose_before=pose_before, valid=1)

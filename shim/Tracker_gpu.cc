@@ -574,6 +574,7 @@ bool Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
     qprm.reloc_blur = 2.5;                                // SmallBlurryImage's default blur, KeyFrame::MakeSBI
     qprm.reloc_iterations = 6;                            // src/Relocaliser.cc:76
     qprm.max_score = Relocaliser::sdRecoveryMaxScore;
+    mcp_track_pose_cov_enable(mpMapTable, 1);             // mm6PoseCovariance rides in the same submission (two launches behind the fine iterations)
     const int rc = pRecover ? mcp_track_frame_recover(mpMapTable, nCams, &vKF[0], apImages, anStrides, 0, NULL, &vCams[0], &vCamsSBI[0], adBfW, &vCfB[0], &prm, &res, &rprm,
                                                       &mTrackRecord, pMotion, pMotionOut, (int)pRecover->vKF.size(), pRecover->vKF.empty() ? NULL : &pRecover->vKF[0],
                                                       pRecover->vCam.empty() ? NULL : &pRecover->vCam[0], pRecover->vPose.empty() ? NULL : &pRecover->vPose[0],
@@ -606,6 +607,20 @@ bool Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
   // mvIterationSets and the MapPoint counters from the notes, mv2Found from the measurements, the level maps and the scene depth from the record
   mvIterationSets.assign(nCams, TrackerDataPtrVector());
   mnNumInliers = rec.n_inliers;
+  // mm6PoseCovariance (:1498-1502) from the record the same wait brought back: SVD<6>(wls.get_C_inv()).get_pinv() of the last fine iteration.
+  // valid == -1 (non-finite sums) leaves zeros, as the record documents.  GetCurrentCovarianceNorm() keeps its host factor
+  // mnTotalAttempted / (double)mnNumInliers: mnTotalAttempted is what AssessTrackingQuality below left for the last camera it assessed (:1635).
+  mcp_track_pose_cov_record cov;
+  if(mcp_track_pose_cov_last(mpMapTable, &cov) != 0)
+  {
+    ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: "<<mcp_last_error());
+    ros::shutdown();
+    return false;
+  }
+  ROS_ASSERT(cov.valid != 1 || cov.n_used == rec.n_inliers);
+  for(int i = 0; i < 6; ++i)
+    for(int j = 0; j < 6; ++j)
+      mm6PoseCovariance(i, j) = cov.cov[6*i + j];
   for(int c = 0; c < nCams; ++c)
   {
     const std::string& camName = mvCurrCamNames[c];
