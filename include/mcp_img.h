@@ -793,6 +793,121 @@ int mcp_map_refind(mcp_map_points*, int n_targets, const mcp_refind_target* targ
  * NULL + mcp_last_error() when the last call was refused or ran over its cap */
 const mcp_refind_meas* mcp_map_refind_view(const mcp_map_points*, int* count);
 
+/* ---- The map graph on the device: MKFs, rig, per-point graph columns, the measurement store ------------ src/BundleAdjusterBase.cc:141-265
+ * The table above holds the MapPoint columns; the graph holds the edges: which keyframe (MKF slot, camera index) measures which point (table
+ * row), where and at which level -- KeyFrame::mmpMeasurements / MapPoint::mMMData.spMeasurementKFs as one store -- with the MKF poses, the rig
+ * (one CamFromBase per camera index, as BundleAdjusterMulti adds one pose per camera name) and mbFixed / mbBad / the patch source per point.
+ * A graph lives on its table's device and enqueues on its table's stream: a select that follows an mcp_ba_write_back or an
+ * mcp_map_points_update sees whole rows.  THE TABLE MUST OUTLIVE THE GRAPH: destroying the table first is the caller's error (as a destroyed
+ * mcp_kf is for the table's rows that name it, only that nothing guards this one).  Threading: as mcp_map_points_update -- the caller
+ * serialises the calls on one table and its graph.  All poses: R row-major 9 then t 3, finite.
+ * REFUSALS of every call below: -1 (NULL for create), mcp_last_error(), nothing enqueued, the graph unchanged. */
+#define MCP_MAP_MAX_MKFS 4096
+#define MCP_MKF_PRESENT 1     /* in Map::mlpMultiKeyFrames */
+#define MCP_MKF_FIXED   2     /* MultiKeyFrame::mbFixed    */
+#define MCP_MKF_BAD     4     /* MultiKeyFrame::mbBad      */
+#define MCP_GP_FIXED    1     /* MapPoint::mbFixed         */
+#define MCP_GP_BAD      2     /* MapPoint::mbBad -- not the table's `usable`, which is !mbBad && mbOptimized */
+typedef struct mcp_map_graph mcp_map_graph;
+mcp_map_graph* mcp_map_graph_create(mcp_map_points* table, int ncam /* 1..MCP_MAX_FRAME_CAMS */, const double* cam_from_base /* ncam x 12 */);
+void mcp_map_graph_destroy(mcp_map_graph*);
+/* MKF slots first .. first+count-1 (first + count <= MCP_MAP_MAX_MKFS) / the distinct slots[0..count): BaseFromWorld, flags (MCP_MKF_*),
+ * mbActive and mdSceneDepthMean per camera index.  A slot never written is not present.  The depth mean of an active keyframe must be finite
+ * and positive (others are stored as 0). */
+int mcp_map_graph_set_mkfs(mcp_map_graph*, int first, int count, const double* base_from_world /* count x 12 */, const int* flags,
+                           const uint8_t* kf_active /* count x ncam */, const double* kf_depth_mean /* count x ncam */);
+int mcp_map_graph_update_mkfs(mcp_map_graph*, int count, const int* slots, const double* base_from_world, const int* flags,
+                              const uint8_t* kf_active, const double* kf_depth_mean);
+/* graph columns of the distinct table rows rows[0..count): the patch source (MKF slot, camera index) and MCP_GP_* flags.  A row never
+ * written is bad.  src_mkf < 0 (no source) is allowed for fixed points only; a row past the table's size is refused. */
+int mcp_map_graph_update_points(mcp_map_graph*, int count, const int* rows, const int* src_mkf, const int* src_cam, const int* flags);
+/* appends measurements in the caller's order and returns the store index of the first new one.  uv: level-0 v2RootPos; source:
+ * Measurement::eSource as an int, stored and returned, not interpreted.  The caller guarantees one entry per (mkf, cam, row), as MeasPtrMap
+ * does: the library does not search for duplicates (mcp_map_graph_check says afterwards what the store holds).  Refused: a slot that is not
+ * present, cam outside 0..ncam-1, a row outside the table, level outside 0..MCP_LEVELS-1, a non-finite uv.  Capacity grows geometrically. */
+int mcp_map_graph_add_meas(mcp_map_graph*, int count, const int* mkf, const int* cam, const int* row, const double* uv /* count x 2 */,
+                           const int* level, const int* source);
+/* KeyFrame::EraseMeasurementOfPoint for the distinct keys (mkf, cam, row)[0..count): the matching live entries become dead (one thread per
+ * entry, binary search in the sorted keys).  Returns how many died (waits for the stream); a key that matches nothing is not an error. */
+int mcp_map_graph_erase_meas(mcp_map_graph*, int count, const int* mkf, const int* cam, const int* row);
+/* every entry of that MKF dies, the slot is no longer present; returns how many died */
+int mcp_map_graph_erase_mkf(mcp_map_graph*, int slot);
+/* stable removal of the dead entries.  STORE INDICES CHANGE: the index mcp_map_graph_add_meas returned and the `store` field of a
+ * measurement view taken before are void afterwards. */
+int mcp_map_graph_compact(mcp_map_graph*);
+/* read-backs; each waits for the stream.  alive: 1 / 0.  good_counts: MapPoint::mMMData.GoodMeasCount() (MapPoint.h:80-87) of table rows
+ * first .. first+count-1: the live entries of the row whose MKF is present and not bad.  check: for tests and adapters under development
+ * -- a host sort of the read-back keys; n_dup = live entries whose (mkf, cam, row) an earlier live entry has, n_dead = dead entries. */
+int mcp_map_graph_num_meas(mcp_map_graph*, int* live, int* stored);
+int mcp_map_graph_get_meas(mcp_map_graph*, int first, int count, int* mkf, int* cam, int* row, double* uv, int* level, int* source, uint8_t* alive);
+int mcp_map_graph_good_counts(mcp_map_graph*, int first, int count, int* out);
+int mcp_map_graph_check(mcp_map_graph*, int* n_dup, int* n_dead);
+
+/* ---- BundleAdjustRecent / BundleAdjustAll and the population of BundleAdjusterMulti::BundleAdjust in ONE submission -----------------------
+ * src/BundleAdjusterBase.cc:141-265, src/BundleAdjusterMulti.cc:81-200.  The call returns, in the library's pinned block, exactly the arrays
+ * mcp_ba_add_pose / mcp_ba_add_points / mcp_ba_add_measurements and mcp_ba_write_back take.  Six launches on the table's stream, one wait.
+ * RECENT: fewer present MKFs than recent_min_size -> status 1 (the caller sets mbBundleConverged_Recent).  MultiKeyFrame::Distance(newest, k)
+ *   for every other present MKF k, bad ones included (KeyFrame.cc:715-747, 903-927: the minimum over the pairs of active keyframes of
+ *   |dC| + mean_diff_fraction |dmean|, CamFromWorld = cam_from_base[c] * base_from_world, the mean-depth point (0,0,depth_mean) carried to the
+ *   world; DBL_MAX without such a pair).  The n_recent smallest in ascending (distance, slot) are `closest`; the adjust set is the newest MKF
+ *   plus those of them that are neither bad nor fixed.  A row is selected iff a live entry of an adjust-set MKF measures it, it is not bad and
+ *   its good count is >= 2.
+ * ALL: the adjust set is every present MKF that is not bad (its own FIXED flag travels); a row is selected iff it is not bad and (good >= 2 or
+ *   it is fixed).
+ * Good count: the live entries of the row whose MKF is present and not bad.  The FIXED SET is every present, not bad MKF outside the adjust set
+ *   with a live entry on a bundle row, or that is the source of a non-fixed bundle row.  Points gate: fewer than min_points bundle rows ->
+ *   status 2, empty views.
+ * VIEWS (valid until the next select on the graph): MKFs: the adjust set in ascending slot, then the fixed set in ascending slot; points: in
+ *   ascending row, x = CamFromWorld_src * world_pos[row] (the two products in that order) or, fixed, world_pos[row]; src_mkf is the index into
+ *   the MKF view (-1 for a fixed point, with has_fixed_points telling the adapter to add the world pose, BundleAdjusterMulti.cc:147-149);
+ *   measurements: the live entries whose row is in the bundle and whose MKF is present and not bad, in store order.
+ * DEVIATIONS from the reference: (1) these orders -- the reference's are pointer orders of std::set / std::map, so any fixed order is as good,
+ *   and this one makes two calls give the same bytes; (2) the slot, not the pointer, breaks a distance tie in `closest`; (3) fewer than n_recent
+ *   other MKFs give a shorter list (the reference indexes past the vector's end, :208-214); (4) a selected non-fixed row whose source MKF is
+ *   bad, absent or < 0 is DROPPED with its measurements and counted in n_dropped_source (the reference would hand AddPoint the id 0 that
+ *   mmBase_BundleID[] default-inserts) -- everything that depends on the selection (fixed set, gate, views) is decided after this rule;
+ *   (5) status 3 where the reference calls ROS_BREAK.
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, the views of the last call still valid): NULL handles or structs; an unknown mode; RECENT
+ *   with `newest` not present; n_recent outside 0..8; a negative gate; mean_diff_fraction not finite. */
+#define MCP_BUNDLE_ALL 0
+#define MCP_BUNDLE_RECENT 1
+typedef struct mcp_bundle_select_params {
+  int mode;              /* MCP_BUNDLE_ALL | MCP_BUNDLE_RECENT */
+  int newest;            /* RECENT: slot of mlpMultiKeyFrames.back() */
+  int n_recent;          /* snRecentNum (3) */
+  int recent_min_size;   /* snRecentMinSize (8) */
+  int min_points;        /* snMinMapPoints (10) */
+  double mean_diff_fraction;   /* KeyFrame::sdDistanceMeanDiffFraction (0.5) */
+} mcp_bundle_select_params;
+typedef struct mcp_bundle_select_result {
+  int status;            /* 0 selected; 1 map smaller than recent_min_size; 2 fewer than min_points;
+                            3 an MKF distance not finite or > 1e10 (the reference stops the process, KeyFrame.cc:734-744) */
+  int n_adjust, n_fixed, n_points, n_meas, has_fixed_points;
+  int n_dropped_source;  /* selected points left out because their source MKF is bad or absent */
+  int closest[8]; double closest_dist[8];   /* RECENT, status 0 or 2: NClosestMultiKeyFrames, before the bad / fixed filter; -1 past the end */
+} mcp_bundle_select_result;
+typedef struct mcp_bundle_mkf { int slot, fixed /* fixed in the bundle */; } mcp_bundle_mkf;
+typedef struct mcp_bundle_point { double x[3]; int row, src_mkf /* index into the MKF view */, src_cam, fixed; } mcp_bundle_point;
+typedef struct mcp_bundle_meas { double uv[2]; int mkf /* index into the MKF view */, cam, point /* index into the points view */, level, source,
+                                 store /* store index */; } mcp_bundle_meas;
+int mcp_map_bundle_select(mcp_map_graph*, const mcp_bundle_select_params*, mcp_bundle_select_result*);
+/* device time of the last select's submission (first memset to last launch, between two events on the stream), in ms; -1 unless it ran */
+int mcp_map_bundle_select_last_timing(const mcp_map_graph*, double* device_ms);
+/* zero-copy: the views of the last mcp_map_bundle_select on the graph (n_adjust + n_fixed, n_points, n_meas entries); NULL + count 0 when empty */
+const mcp_bundle_mkf*   mcp_map_bundle_mkfs_view(const mcp_map_graph*, int* count);
+const mcp_bundle_point* mcp_map_bundle_points_view(const mcp_map_graph*, int* count);
+const mcp_bundle_meas*  mcp_map_bundle_meas_view(const mcp_map_graph*, int* count);
+/* the same selection from host arrays, with the same bodies under the host compiler: needs no device, and gives the bytes the device gives.
+ * n_slots <= MCP_MAP_MAX_MKFS MKF columns as mcp_map_graph_set_mkfs takes them, the rig, n_rows point columns with world_pos (n_rows x 3), the
+ * n_store store columns with their alive flags.  out_*: caller's arrays of cap_* entries; a view that does not fit is a refusal found before
+ * anything is written (sizes n_slots / n_rows / n_store always fit).  Refusals as mcp_map_bundle_select's, outputs untouched. */
+int mcp_map_bundle_select_host(const mcp_bundle_select_params*, int ncam, const double* cam_from_base,
+                               int n_slots, const double* base_from_world, const int* mkf_flags, const uint8_t* kf_active, const double* kf_depth_mean,
+                               int n_rows, const double* world_pos, const int* src_mkf, const int* src_cam, const int* point_flags,
+                               int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row, const double* ms_uv, const int* ms_level,
+                               const int* ms_source, const uint8_t* ms_alive, mcp_bundle_select_result* res,
+                               int cap_mkfs, mcp_bundle_mkf* out_mkfs, int cap_points, mcp_bundle_point* out_points, int cap_meas, mcp_bundle_meas* out_meas);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,9 @@
+"""mcptam_amd: the HIP path of the multi-camera tracker and map maker.  The modules load the native library when first used, not on import."""
+
+
+def __getattr__(name):
+    # MapGraph and the selection's restatements, without importing numpy-heavy modules for callers that only want a submodule
+    if name in ("MapGraph", "bundle_select_ref", "bundle_select_host"):
+        from . import map_graph
+        return getattr(map_graph, name)
+    raise AttributeError("module 'mcptam_amd' has no attribute %r" % name)

@@ -28,6 +28,7 @@
 #include "track_cov_kernels.h"
 #include "ba_bridge.h"
 #include "ba_select.h"
+#include "map_graph_kernels.h"
 
 using namespace mcp;
 
@@ -2561,6 +2562,505 @@ const mcp_refind_meas* mcp_map_refind_view(const mcp_map_points* m, int* count) 
   if (!m || m->rf.view < 0) { img_fail("mcp_map_refind_view: the last mcp_map_refind on this table left no measurements to show"); return nullptr; }
   if (count) *count = m->rf.view;
   return m->rf.view > 0 ? reinterpret_cast<const mcp_refind_meas*>(m->rf.out.p + m->rf.meas_off) : nullptr;
+}
+
+}  // extern "C"
+
+// ---- the map graph (include/mcp_img.h mcp_map_graph_*, mcp_map_bundle_select; map_graph_kernels.h) ---------------------------------------
+struct mcp_map_graph {
+  mcp_map_points* m = nullptr;                        // the table: its device, its stream, its rows (it must outlive the graph)
+  MgRig rig;
+  Buf<MgMkf> slots; std::vector<int> h_flags;         // MCP_MAP_MAX_MKFS slots; the host's copy of their flags (what add_meas and select check)
+  Buf<MgPoint> pts; int prow = 0;                     // point columns: prow rows written or filled so far
+  Buf<MgMeas> store, store_alt; int n_store = 0, n_live = 0;
+  Buf<MgCtl> ctl; PinBuf<MgCtl> h_ctl;
+  // uploads: packed into pinned memory, copied on the table's stream; `staged` marks when the staging may be refilled
+  PinBuf<char> up_in; Buf<char> up_dev; hipEvent_t staged = nullptr; bool stage_busy = false;
+  std::vector<int> sorted_ids; std::vector<unsigned long long> keys;
+  // the select: marks (mkf_in | good | seen), verdicts, bundle indices, per-workgroup counts; the pinned views and result
+  Buf<int> marks, bidx, blk, mkf_bidx; Buf<uint8_t> adjust, sel, mkeep;
+  PinBuf<mcp_bundle_mkf> v_mkfs; PinBuf<mcp_bundle_point> v_points; PinBuf<mcp_bundle_meas> v_meas; PinBuf<mcp_bundle_select_result> h_res;
+  int n_mkfs = 0, n_points = 0, n_meas = 0;           // what the views hold
+  hipEvent_t t0 = nullptr, t1 = nullptr; bool timed = false;      // mcp_map_bundle_select_last_timing: around the last select's submission
+  ~mcp_map_graph() { if (m && m->st) (void)hipStreamSynchronize(m->st); for (hipEvent_t e : {staged, t0, t1}) if (e) (void)hipEventDestroy(e); }
+  int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
+  int sync() { ICK(hipStreamSynchronize(m->st)); stage_busy = false; m->stage_busy = false; return 0; }
+  // pinned + device staging of `bytes`, free to fill
+  int stage(size_t bytes) {
+    if (wait_staging()) return -1;
+    if (up_in.alloc(bytes)) return -1;
+    if (bytes > up_dev.n) { if (sync()) return -1; }       // the device staging is reallocated below
+    return up_dev.alloc(bytes);
+  }
+  int staged_now() { ICK(hipEventRecord(staged, m->st)); stage_busy = true; return 0; }
+  // the point columns cover `rows` rows: the ones that appear read as never written
+  int grow_points(int rows) {
+    if (rows <= prow) return 0;
+    if ((size_t)rows > pts.n || !pts.p) {
+      Buf<MgPoint> fresh;
+      if (fresh.alloc(std::max<size_t>({(size_t)rows, 2*pts.n, (size_t)1024}))) return -1;
+      if (prow) { ICK(hipMemcpyAsync(fresh.p, pts.p, sizeof(MgPoint)*(size_t)prow, hipMemcpyDeviceToDevice, m->st)); if (sync()) return -1; }
+      pts.swap(fresh);
+    }
+    hipLaunchKernelGGL(k_mg_points_fill, dim3((unsigned)((rows - prow + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, m->st, pts.p, prow, rows - prow);
+    ICK(hipGetLastError());
+    prow = rows;
+    return 0;
+  }
+  int grow_store(size_t need) {
+    if (need <= store.n && store.p) return 0;
+    Buf<MgMeas> fresh;
+    if (fresh.alloc(std::max<size_t>({need, 2*store.n, (size_t)1024}))) return -1;
+    if (n_store) { ICK(hipMemcpyAsync(fresh.p, store.p, sizeof(MgMeas)*(size_t)n_store, hipMemcpyDeviceToDevice, m->st)); }
+    if (store.p && sync()) return -1;                  // the old block is freed below, with nothing in flight on it
+    store.swap(fresh);
+    return 0;
+  }
+};
+
+static int mg_distinct(std::vector<int>& sorted, const int* ids, int count, const std::string& who, const char* what) {
+  sorted.assign(ids, ids + count);
+  std::sort(sorted.begin(), sorted.end());
+  for (int k = 1; k < count; ++k) if (sorted[k] == sorted[k - 1]) return img_fail(who + ": " + what + " " + std::to_string(sorted[k]) + " appears twice");
+  return 0;
+}
+
+static int mg_mkfs_upload(mcp_map_graph* g, const std::string& who, bool by_ids, int first, int count, const int* ids, const double* bfw, const int* flags,
+                          const uint8_t* act, const double* dep) {
+  if (!g) return img_fail(who + ": NULL graph");
+  if (count < 0 || (count > 0 && (!bfw || !flags || !act || !dep || (by_ids && !ids)))) return img_fail(who + ": bad arguments");
+  if (!by_ids && (first < 0 || (long long)first + count > MCP_MAP_MAX_MKFS)) return img_fail(who + ": more than MCP_MAP_MAX_MKFS (" + std::to_string(MCP_MAP_MAX_MKFS) + ") MKF slots");
+  const int nc = g->rig.ncam;
+  for (int k = 0; k < count; ++k) {
+    if (by_ids && (ids[k] < 0 || ids[k] >= MCP_MAP_MAX_MKFS)) return img_fail(who + ": slot " + std::to_string(ids[k]) + " is outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
+    if (!finite12(bfw + 12*(size_t)k)) return img_fail(who + ": entry " + std::to_string(k) + " has a non-finite pose");
+    if (flags[k] & ~(MCP_MKF_PRESENT | MCP_MKF_FIXED | MCP_MKF_BAD)) return img_fail(who + ": entry " + std::to_string(k) + " has unknown flags");
+    for (int c = 0; c < nc; ++c) {
+      const double d = dep[(size_t)k*nc + c];
+      if (act[(size_t)k*nc + c] && !(std::isfinite(d) && d > 0.0)) return img_fail(who + ": entry " + std::to_string(k) + ", camera " + std::to_string(c) + ": the depth mean of an active keyframe must be finite and positive");
+    }
+  }
+  if (by_ids && count && mg_distinct(g->sorted_ids, ids, count, who, "slot")) return -1;
+  if (count == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  const size_t o_ids = tm_align(sizeof(MgMkf)*(size_t)count), need = o_ids + sizeof(int)*(size_t)count;
+  if (g->stage(need)) return -1;
+  MgMkf* rec = reinterpret_cast<MgMkf*>(g->up_in.p); int* hid = reinterpret_cast<int*>(g->up_in.p + o_ids);
+  std::memset(g->up_in.p, 0, o_ids);
+  for (int k = 0; k < count; ++k) {
+    std::memcpy(rec[k].bfw, bfw + 12*(size_t)k, 96);
+    rec[k].flags = flags[k];
+    for (int c = 0; c < nc; ++c) { const bool a = act[(size_t)k*nc + c] != 0; rec[k].active[c] = a ? 1 : 0; rec[k].depth[c] = a ? dep[(size_t)k*nc + c] : 0.0; }
+    hid[k] = by_ids ? ids[k] : first + k;
+  }
+  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, need, hipMemcpyHostToDevice, g->m->st));
+  hipLaunchKernelGGL(k_mg_mkfs_scatter, dim3((unsigned)((count + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, g->m->st, g->slots.p, count,
+                     (const int*)(g->up_dev.p + o_ids), (const MgMkf*)g->up_dev.p);
+  ICK(hipGetLastError());
+  if (g->staged_now()) return -1;
+  for (int k = 0; k < count; ++k) g->h_flags[hid[k]] = flags[k];
+  return 0;
+}
+
+// the selection on host arrays: the host's statement of the six launches (the same __host__ __device__ bodies)
+namespace {
+struct MgHostIn {
+  int ncam; const double* cfb; int n_slots; const double* bfw; const int* mflags; const uint8_t* act; const double* dep;
+  int n_rows; const double* world; const int* src_mkf; const int* src_cam; const int* pflags;
+  int n_store; const int* ms_mkf; const int* ms_cam; const int* ms_row; const double* ms_uv; const int* ms_level; const int* ms_source; const uint8_t* ms_alive;
+};
+}
+static std::string mg_params_check(const mcp_bundle_select_params* p) {
+  if (!p) return "NULL params";
+  if (p->mode != MCP_BUNDLE_ALL && p->mode != MCP_BUNDLE_RECENT) return "unknown mode " + std::to_string(p->mode);
+  if (p->n_recent < 0 || p->n_recent > 8) return "n_recent outside 0..8";
+  if (p->recent_min_size < 0 || p->min_points < 0) return "a negative gate";
+  if (!std::isfinite(p->mean_diff_fraction)) return "mean_diff_fraction is not finite";
+  return "";
+}
+static void mg_host_select(const mcp_bundle_select_params& S, const MgHostIn& I, mcp_bundle_select_result& R, std::vector<mcp_bundle_mkf>& mk,
+                           std::vector<mcp_bundle_point>& pt, std::vector<mcp_bundle_meas>& ms) {
+  std::memset(&R, 0, sizeof R);
+  for (int k = 0; k < 8; ++k) R.closest[k] = -1;
+  MgRig rig; std::memset(&rig, 0, sizeof rig); rig.ncam = I.ncam;
+  for (int c = 0; c < I.ncam; ++c) mg_se3_of12(I.cfb + 12*(size_t)c, rig.cfb[c]);
+  const int P = I.n_slots, nc = I.ncam;
+  auto flags_of = [&](int k) { return k >= 0 && k < P ? I.mflags[k] : 0; };
+  std::vector<uint8_t> adjust(P, 0);
+  if (S.mode == MCP_BUNDLE_ALL) { for (int k = 0; k < P; ++k) adjust[k] = mg_mkf_ok(I.mflags[k]); }
+  else {
+    int n_present = 0;
+    for (int k = 0; k < P; ++k) n_present += (I.mflags[k] & MCP_MKF_PRESENT) ? 1 : 0;
+    if (n_present < S.recent_min_size) { R.status = 1; return; }
+    std::vector<std::pair<double, int>> d;
+    bool broken = false;
+    const int nw = S.newest;
+    for (int k = 0; k < P; ++k) {
+      if (k == nw || !(I.mflags[k] & MCP_MKF_PRESENT)) continue;
+      bool br;
+      d.emplace_back(mg_mkf_distance(rig, I.bfw + 12*(size_t)nw, I.act + (size_t)nw*nc, I.dep + (size_t)nw*nc, I.bfw + 12*(size_t)k, I.act + (size_t)k*nc,
+                                     I.dep + (size_t)k*nc, S.mean_diff_fraction, &br), k);
+      broken = broken || br;
+    }
+    if (broken) { R.status = 3; return; }
+    std::sort(d.begin(), d.end());
+    adjust[nw] = 1;
+    for (int r = 0; r < S.n_recent && r < (int)d.size(); ++r) {
+      R.closest[r] = d[r].second; R.closest_dist[r] = d[r].first;
+      const int f = I.mflags[d[r].second];
+      if (!(f & MCP_MKF_BAD) && !(f & MCP_MKF_FIXED)) adjust[d[r].second] = 1;
+    }
+  }
+  const int N = I.n_rows, M = I.n_store;
+  std::vector<int> good(N, 0), seen(N, 0), bidx(N, -1), mkf_in(P, 0);
+  for (int i = 0; i < M; ++i) {
+    if (!mg_edge_live(I.ms_alive[i], I.ms_mkf[i], I.ms_row[i], N) || I.ms_mkf[i] >= P) continue;
+    if (mg_mkf_ok(I.mflags[I.ms_mkf[i]])) ++good[I.ms_row[i]];
+    if (adjust[I.ms_mkf[i]]) seen[I.ms_row[i]] = 1;
+  }
+  int n_points = 0;
+  for (int i = 0; i < N; ++i) {
+    MgPoint Q; Q.src_mkf = I.src_mkf[i]; Q.src_cam = I.src_cam[i]; Q.flags = I.pflags[i]; Q.pad_ = 0;
+    if (!mg_row_selected(S.mode, Q.flags, good[i], seen[i])) continue;
+    const bool fixed = Q.flags & MCP_GP_FIXED;
+    if (!fixed && !(mg_source_in_range(Q, nc, P) && mg_mkf_ok(I.mflags[Q.src_mkf]))) { ++R.n_dropped_source; continue; }
+    if (fixed) R.has_fixed_points = 1; else mkf_in[Q.src_mkf] = 1;
+    bidx[i] = n_points++;
+  }
+  if (n_points < S.min_points) { R.status = 2; R.has_fixed_points = 0; return; }
+  std::vector<uint8_t> keep(M, 0);
+  for (int i = 0; i < M; ++i) {
+    if (!mg_edge_live(I.ms_alive[i], I.ms_mkf[i], I.ms_row[i], N) || I.ms_mkf[i] >= P) continue;
+    if (bidx[I.ms_row[i]] < 0 || !mg_mkf_ok(I.mflags[I.ms_mkf[i]])) continue;
+    keep[i] = 1; mkf_in[I.ms_mkf[i]] = 1;
+  }
+  std::vector<int> mkf_bidx(P, -1);
+  for (int k = 0; k < P; ++k) if (adjust[k]) { mkf_bidx[k] = (int)mk.size(); mk.push_back({k, (I.mflags[k] & MCP_MKF_FIXED) ? 1 : 0}); }
+  R.n_adjust = (int)mk.size();
+  for (int k = 0; k < P; ++k) if (!adjust[k] && mkf_in[k] && mg_mkf_ok(flags_of(k))) { mkf_bidx[k] = (int)mk.size(); mk.push_back({k, 1}); }
+  R.n_fixed = (int)mk.size() - R.n_adjust;
+  for (int i = 0; i < N; ++i) {
+    if (bidx[i] < 0) continue;
+    MgPoint Q; Q.src_mkf = I.src_mkf[i]; Q.src_cam = I.src_cam[i]; Q.flags = I.pflags[i]; Q.pad_ = 0;
+    const bool fixed = Q.flags & MCP_GP_FIXED;
+    mcp_bundle_point O;
+    mg_point_x(rig, Q, I.bfw + 12*(size_t)(fixed ? 0 : Q.src_mkf), I.world + 3*(size_t)i, O.x);
+    O.row = i; O.src_mkf = fixed ? -1 : mkf_bidx[Q.src_mkf]; O.src_cam = fixed ? -1 : Q.src_cam; O.fixed = fixed ? 1 : 0;
+    pt.push_back(O);
+  }
+  for (int i = 0; i < M; ++i) {
+    if (!keep[i]) continue;
+    mcp_bundle_meas O;
+    O.uv[0] = I.ms_uv[2*(size_t)i]; O.uv[1] = I.ms_uv[2*(size_t)i + 1]; O.mkf = mkf_bidx[I.ms_mkf[i]]; O.cam = I.ms_cam[i]; O.point = bidx[I.ms_row[i]];
+    O.level = I.ms_level[i]; O.source = I.ms_source[i]; O.store = i;
+    ms.push_back(O);
+  }
+  R.n_points = n_points; R.n_meas = (int)ms.size();
+}
+
+extern "C" {
+
+mcp_map_graph* mcp_map_graph_create(mcp_map_points* m, int ncam, const double* cfb) {
+  if (!m) { mcp_set_error("mcp_map_graph_create: NULL table"); return nullptr; }
+  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !cfb) { mcp_set_error("mcp_map_graph_create: ncam must be 1..MCP_MAX_FRAME_CAMS with one CamFromBase each"); return nullptr; }
+  for (int c = 0; c < ncam; ++c) if (!finite12(cfb + 12*(size_t)c)) { mcp_set_error("mcp_map_graph_create: a non-finite CamFromBase"); return nullptr; }
+  if (hipSetDevice(m->device) != hipSuccess) { mcp_set_error("hipSetDevice failed"); return nullptr; }
+  mcp_map_graph* g = new mcp_map_graph(); g->m = m;
+  std::memset(&g->rig, 0, sizeof g->rig); g->rig.ncam = ncam;
+  for (int c = 0; c < ncam; ++c) mg_se3_of12(cfb + 12*(size_t)c, g->rig.cfb[c]);
+  g->h_flags.assign(MCP_MAP_MAX_MKFS, 0);
+  const bool ok = !g->slots.alloc(MCP_MAP_MAX_MKFS) && !g->ctl.alloc(1) && !g->h_ctl.alloc(1) && !g->h_res.alloc(1) && !g->adjust.alloc(MCP_MAP_MAX_MKFS) &&
+                  !g->mkf_bidx.alloc(MCP_MAP_MAX_MKFS) && !g->v_mkfs.alloc(MCP_MAP_MAX_MKFS) && hipEventCreateWithFlags(&g->staged, hipEventDisableTiming) == hipSuccess &&
+                  hipEventCreate(&g->t0) == hipSuccess && hipEventCreate(&g->t1) == hipSuccess &&
+                  hipMemsetAsync(g->slots.p, 0, sizeof(MgMkf)*(size_t)MCP_MAP_MAX_MKFS, m->st) == hipSuccess && hipMemsetAsync(g->ctl.p, 0, sizeof(MgCtl), m->st) == hipSuccess;
+  if (!ok) { mcp_set_error("mcp_map_graph_create: allocation failed"); delete g; return nullptr; }
+  std::memset(g->h_res.p, 0, sizeof(mcp_bundle_select_result));
+  return g;
+}
+void mcp_map_graph_destroy(mcp_map_graph* g) { if (g) { (void)hipSetDevice(g->m->device); delete g; } }
+
+int mcp_map_graph_set_mkfs(mcp_map_graph* g, int first, int count, const double* bfw, const int* flags, const uint8_t* act, const double* dep) {
+  return mg_mkfs_upload(g, "mcp_map_graph_set_mkfs", false, first, count, nullptr, bfw, flags, act, dep);
+}
+int mcp_map_graph_update_mkfs(mcp_map_graph* g, int count, const int* slots, const double* bfw, const int* flags, const uint8_t* act, const double* dep) {
+  return mg_mkfs_upload(g, "mcp_map_graph_update_mkfs", true, 0, count, slots, bfw, flags, act, dep);
+}
+
+int mcp_map_graph_update_points(mcp_map_graph* g, int count, const int* rows, const int* src_mkf, const int* src_cam, const int* flags) {
+  const std::string who = "mcp_map_graph_update_points";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (count < 0 || (count > 0 && (!rows || !src_mkf || !src_cam || !flags))) return img_fail(who + ": bad arguments");
+  const int R = g->m->rows;
+  for (int k = 0; k < count; ++k) {
+    if (rows[k] < 0 || rows[k] >= R) return img_fail(who + ": row " + std::to_string(rows[k]) + " is outside the table (" + std::to_string(R) + " rows)");
+    if (flags[k] & ~(MCP_GP_FIXED | MCP_GP_BAD)) return img_fail(who + ": entry " + std::to_string(k) + " has unknown flags");
+    if (src_mkf[k] >= MCP_MAP_MAX_MKFS) return img_fail(who + ": entry " + std::to_string(k) + " names source slot " + std::to_string(src_mkf[k]));
+    if (src_mkf[k] < 0 && !(flags[k] & MCP_GP_FIXED)) return img_fail(who + ": entry " + std::to_string(k) + " has no source and is not fixed");
+    if (src_mkf[k] >= 0 && (src_cam[k] < 0 || src_cam[k] >= g->rig.ncam)) return img_fail(who + ": entry " + std::to_string(k) + " names source camera " + std::to_string(src_cam[k]));
+  }
+  if (count && mg_distinct(g->sorted_ids, rows, count, who, "row")) return -1;
+  if (count == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  const size_t o_ids = tm_align(sizeof(MgPoint)*(size_t)count), need = o_ids + sizeof(int)*(size_t)count;
+  if (g->stage(need) || g->grow_points(R)) return -1;
+  MgPoint* rec = reinterpret_cast<MgPoint*>(g->up_in.p);
+  for (int k = 0; k < count; ++k) { rec[k].src_mkf = src_mkf[k] < 0 ? -1 : src_mkf[k]; rec[k].src_cam = src_mkf[k] < 0 ? 0 : src_cam[k]; rec[k].flags = flags[k]; rec[k].pad_ = 0; }
+  std::memcpy(g->up_in.p + o_ids, rows, sizeof(int)*(size_t)count);
+  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, need, hipMemcpyHostToDevice, g->m->st));
+  hipLaunchKernelGGL(k_mg_points_scatter, dim3((unsigned)((count + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, g->m->st, g->pts.p, count,
+                     (const int*)(g->up_dev.p + o_ids), (const MgPoint*)g->up_dev.p);
+  ICK(hipGetLastError());
+  return g->staged_now();
+}
+
+int mcp_map_graph_add_meas(mcp_map_graph* g, int count, const int* mkf, const int* cam, const int* row, const double* uv, const int* level, const int* source) {
+  const std::string who = "mcp_map_graph_add_meas";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (count < 0 || (count > 0 && (!mkf || !cam || !row || !uv || !level || !source))) return img_fail(who + ": bad arguments");
+  if ((long long)g->n_store + count > 0x7fffffffLL) return img_fail(who + ": the store is full");
+  const int R = g->m->rows;
+  for (int k = 0; k < count; ++k) {
+    const std::string at = who + ": entry " + std::to_string(k);
+    if (mkf[k] < 0 || mkf[k] >= MCP_MAP_MAX_MKFS || !(g->h_flags[mkf[k]] & MCP_MKF_PRESENT)) return img_fail(at + " names MKF slot " + std::to_string(mkf[k]) + ", which is not present");
+    if (cam[k] < 0 || cam[k] >= g->rig.ncam) return img_fail(at + " names camera " + std::to_string(cam[k]));
+    if (row[k] < 0 || row[k] >= R) return img_fail(at + " names row " + std::to_string(row[k]) + ", the table has " + std::to_string(R));
+    if (level[k] < 0 || level[k] >= MCP_LEVELS) return img_fail(at + " has level " + std::to_string(level[k]));
+    if (!std::isfinite(uv[2*(size_t)k]) || !std::isfinite(uv[2*(size_t)k + 1])) return img_fail(at + " has a non-finite position");
+  }
+  const int first = g->n_store;
+  if (count == 0) return first;
+  ICK(hipSetDevice(g->m->device));
+  if (g->stage(sizeof(MgMeas)*(size_t)count) || g->grow_store((size_t)first + count)) return -1;
+  MgMeas* rec = reinterpret_cast<MgMeas*>(g->up_in.p);
+  for (int k = 0; k < count; ++k) {
+    rec[k].uv[0] = uv[2*(size_t)k]; rec[k].uv[1] = uv[2*(size_t)k + 1]; rec[k].mkf = mkf[k]; rec[k].cam = cam[k]; rec[k].row = row[k];
+    rec[k].level = level[k]; rec[k].source = source[k]; rec[k].alive = 1;
+  }
+  ICK(hipMemcpyAsync(g->store.p + first, g->up_in.p, sizeof(MgMeas)*(size_t)count, hipMemcpyHostToDevice, g->m->st));
+  if (g->staged_now()) return -1;
+  g->n_store += count; g->n_live += count;
+  return first;
+}
+
+// the erase kernel over the store, the count of the dead read back
+static int mg_erase_run(mcp_map_graph* g, const unsigned long long* d_keys, int n_keys, int slot) {
+  hipStream_t st = g->m->st;
+  ICK(hipMemsetAsync(&g->ctl.p->erased, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_mg_erase, dim3((unsigned)std::max(1, (g->n_store + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, st, g->store.p, g->n_store, d_keys, n_keys, slot, g->slots.p, g->ctl.p);
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(g->h_ctl.p, g->ctl.p, sizeof(MgCtl), hipMemcpyDeviceToHost, st));
+  if (g->sync()) return -1;
+  const int died = g->h_ctl.p->erased;
+  g->n_live -= died;
+  return died;
+}
+
+int mcp_map_graph_erase_meas(mcp_map_graph* g, int count, const int* mkf, const int* cam, const int* row) {
+  const std::string who = "mcp_map_graph_erase_meas";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (count < 0 || (count > 0 && (!mkf || !cam || !row))) return img_fail(who + ": bad arguments");
+  std::vector<unsigned long long>& keys = g->keys;
+  keys.resize(count);
+  for (int k = 0; k < count; ++k) {
+    if (mkf[k] < 0 || mkf[k] >= MCP_MAP_MAX_MKFS || cam[k] < 0 || cam[k] >= MCP_MAX_FRAME_CAMS || row[k] < 0) return img_fail(who + ": key " + std::to_string(k) + " is out of range");
+    keys[k] = mg_key(mkf[k], cam[k], row[k]);
+  }
+  std::sort(keys.begin(), keys.end());
+  for (int k = 1; k < count; ++k) if (keys[k] == keys[k - 1]) return img_fail(who + ": a key appears twice");
+  if (count == 0 || g->n_store == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  if (g->stage(8*(size_t)count)) return -1;
+  std::memcpy(g->up_in.p, keys.data(), 8*(size_t)count);
+  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, 8*(size_t)count, hipMemcpyHostToDevice, g->m->st));
+  return mg_erase_run(g, (const unsigned long long*)g->up_dev.p, count, -1);
+}
+
+int mcp_map_graph_erase_mkf(mcp_map_graph* g, int slot) {
+  if (!g) return img_fail("mcp_map_graph_erase_mkf: NULL graph");
+  if (slot < 0 || slot >= MCP_MAP_MAX_MKFS) return img_fail("mcp_map_graph_erase_mkf: slot " + std::to_string(slot) + " is outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
+  ICK(hipSetDevice(g->m->device));
+  const int died = mg_erase_run(g, nullptr, 0, slot);
+  if (died >= 0) g->h_flags[slot] &= ~MCP_MKF_PRESENT;
+  return died;
+}
+
+int mcp_map_graph_compact(mcp_map_graph* g) {
+  if (!g) return img_fail("mcp_map_graph_compact: NULL graph");
+  if (g->n_live == g->n_store) return 0;
+  ICK(hipSetDevice(g->m->device));
+  const int n = g->n_store, nblk = (n + MG_BLOCK - 1)/MG_BLOCK;
+  if (g->store_alt.n < g->store.n || g->blk.n < (size_t)nblk) { if (g->sync()) return -1; }
+  if (g->store_alt.alloc(g->store.n) || g->blk.alloc(nblk)) return -1;
+  hipLaunchKernelGGL(k_mg_compact_mark, dim3(nblk), dim3(MG_BLOCK), 0, g->m->st, (const MgMeas*)g->store.p, n, g->blk.p);
+  hipLaunchKernelGGL(k_mg_compact_scatter, dim3(nblk), dim3(MG_BLOCK), 0, g->m->st, (const MgMeas*)g->store.p, n, nblk, (const int*)g->blk.p, g->store_alt.p, g->n_live);
+  ICK(hipGetLastError());
+  g->store.swap(g->store_alt);
+  g->n_store = g->n_live;
+  return 0;
+}
+
+int mcp_map_graph_num_meas(mcp_map_graph* g, int* live, int* stored) {
+  if (!g) return img_fail("mcp_map_graph_num_meas: NULL graph");
+  if (!live || !stored) return img_fail("mcp_map_graph_num_meas: bad arguments");
+  ICK(hipSetDevice(g->m->device));
+  if (g->sync()) return -1;
+  *live = g->n_live; *stored = g->n_store;
+  return 0;
+}
+
+int mcp_map_graph_get_meas(mcp_map_graph* g, int first, int count, int* mkf, int* cam, int* row, double* uv, int* level, int* source, uint8_t* alive) {
+  if (!g) return img_fail("mcp_map_graph_get_meas: NULL graph");
+  if (first < 0 || count < 0 || (long long)first + count > g->n_store) return img_fail("mcp_map_graph_get_meas: bad range");
+  if (count == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  std::vector<MgMeas> tmp(count);
+  ICK(hipMemcpyAsync(tmp.data(), g->store.p + first, sizeof(MgMeas)*(size_t)count, hipMemcpyDeviceToHost, g->m->st));
+  if (g->sync()) return -1;
+  for (int k = 0; k < count; ++k) {
+    const MgMeas& E = tmp[k];
+    if (mkf) mkf[k] = E.mkf; if (cam) cam[k] = E.cam; if (row) row[k] = E.row; if (uv) { uv[2*(size_t)k] = E.uv[0]; uv[2*(size_t)k + 1] = E.uv[1]; }
+    if (level) level[k] = E.level; if (source) source[k] = E.source; if (alive) alive[k] = E.alive ? 1 : 0;
+  }
+  return 0;
+}
+
+int mcp_map_graph_good_counts(mcp_map_graph* g, int first, int count, int* out) {
+  if (!g) return img_fail("mcp_map_graph_good_counts: NULL graph");
+  const int R = g->m->rows;
+  if (first < 0 || count < 0 || (long long)first + count > R || (count > 0 && !out)) return img_fail("mcp_map_graph_good_counts: bad arguments");
+  if (count == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  if (g->marks.n < (size_t)R) { if (g->sync()) return -1; }
+  if (g->marks.alloc(R)) return -1;
+  hipStream_t st = g->m->st;
+  ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*(size_t)R, st));
+  if (g->n_store) {
+    hipLaunchKernelGGL(k_mg_edges_count, dim3((unsigned)((g->n_store + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, st, (const MgCtl*)nullptr, (const MgMeas*)g->store.p, g->n_store, R,
+                       (const MgMkf*)g->slots.p, (const uint8_t*)nullptr, g->marks.p, (int*)nullptr);
+    ICK(hipGetLastError());
+  }
+  ICK(hipMemcpyAsync(out, g->marks.p + first, sizeof(int)*(size_t)count, hipMemcpyDeviceToHost, st));
+  return g->sync();
+}
+
+int mcp_map_graph_check(mcp_map_graph* g, int* n_dup, int* n_dead) {
+  if (!g) return img_fail("mcp_map_graph_check: NULL graph");
+  if (!n_dup || !n_dead) return img_fail("mcp_map_graph_check: bad arguments");
+  *n_dup = 0; *n_dead = 0;
+  if (g->n_store == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  std::vector<MgMeas> tmp(g->n_store);
+  ICK(hipMemcpyAsync(tmp.data(), g->store.p, sizeof(MgMeas)*(size_t)g->n_store, hipMemcpyDeviceToHost, g->m->st));
+  if (g->sync()) return -1;
+  std::vector<unsigned long long> keys;
+  for (const MgMeas& E : tmp) { if (E.alive) keys.push_back(mg_key(E.mkf, E.cam, E.row)); else ++*n_dead; }
+  std::sort(keys.begin(), keys.end());
+  for (size_t k = 1; k < keys.size(); ++k) if (keys[k] == keys[k - 1]) ++*n_dup;
+  return 0;
+}
+
+int mcp_map_bundle_select(mcp_map_graph* g, const mcp_bundle_select_params* p, mcp_bundle_select_result* res) {
+  const std::string who = "mcp_map_bundle_select";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!res) return img_fail(who + ": NULL result");
+  const std::string bad = mg_params_check(p);
+  if (!bad.empty()) return img_fail(who + ": " + bad);
+  if (p->mode == MCP_BUNDLE_RECENT && (p->newest < 0 || p->newest >= MCP_MAP_MAX_MKFS || !(g->h_flags[p->newest] & MCP_MKF_PRESENT)))
+    return img_fail(who + ": the newest MKF (slot " + std::to_string(p->newest) + ") is not present");
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int R = m->rows, M = g->n_store;
+  const int nbr = std::max(1, (R + MG_BLOCK - 1)/MG_BLOCK), nbm = std::max(1, (M + MG_BLOCK - 1)/MG_BLOCK);
+  const size_t n_marks = (size_t)MCP_MAP_MAX_MKFS + 2*(size_t)std::max(R, 1);
+  // everything is allocated before the first enqueue (a block that grows is replaced with nothing in flight on the old one; the pinned views of
+  // the last call are replaced only here, past the refusals)
+  if (g->marks.n < n_marks || g->bidx.n < (size_t)R || g->sel.n < (size_t)R || g->mkeep.n < (size_t)M || g->blk.n < (size_t)(nbr + nbm) ||
+      g->v_points.n < (size_t)R || g->v_meas.n < (size_t)M) { if (g->sync()) return -1; }
+  if (g->marks.alloc(n_marks) || g->bidx.alloc(R) || g->sel.alloc(R) || g->mkeep.alloc(M) || g->blk.alloc((size_t)nbr + nbm) || g->v_points.alloc(R) || g->v_meas.alloc(M) ||
+      g->grow_points(R)) return -1;
+  g->n_mkfs = g->n_points = g->n_meas = 0; g->timed = false;
+  MgSelect S; S.mode = p->mode; S.newest = p->newest; S.n_recent = p->n_recent; S.recent_min_size = p->recent_min_size; S.min_points = p->min_points; S.frac = p->mean_diff_fraction;
+  int* mkf_in = g->marks.p; int* good = mkf_in + MCP_MAP_MAX_MKFS; int* seen = good + std::max(R, 1);
+  int* blk_rows = g->blk.p; int* blk_meas = blk_rows + nbr;
+  hipStream_t st = m->st;
+  const dim3 B(MG_BLOCK);
+  Drain drain{m, true};
+  ICK(hipEventRecord(g->t0, st));
+  ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*n_marks, st));
+  ICK(hipMemsetAsync(g->blk.p, 0, sizeof(int)*((size_t)nbr + nbm), st));
+  hipLaunchKernelGGL(k_mg_closest, dim3(1), B, 0, st, S, g->rig, (const MgMkf*)g->slots.p, g->adjust.p, g->ctl.p);
+  hipLaunchKernelGGL(k_mg_edges_count, dim3(nbm), B, 0, st, (const MgCtl*)g->ctl.p, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)g->adjust.p, good, seen);
+  hipLaunchKernelGGL(k_mg_rows_mark, dim3(nbr), B, 0, st, S, g->rig.ncam, g->ctl.p, (const MgMkf*)g->slots.p, (const MgPoint*)g->pts.p, R, (const int*)good, (const int*)seen,
+                     g->sel.p, mkf_in, blk_rows);
+  hipLaunchKernelGGL(k_mg_rank_mark, dim3(nbr + nbm), B, 0, st, (const MgCtl*)g->ctl.p, R, nbr, (const uint8_t*)g->sel.p, (const int*)blk_rows, g->bidx.p, (const MgMeas*)g->store.p, M,
+                     (const MgMkf*)g->slots.p, mkf_in, g->mkeep.p, blk_meas);
+  hipLaunchKernelGGL(k_mg_mkfs, dim3(1), B, 0, st, S, g->ctl.p, (const MgMkf*)g->slots.p, (const uint8_t*)g->adjust.p, (const int*)mkf_in, (const int*)blk_rows, nbr,
+                     (const int*)blk_meas, nbm, g->mkf_bidx.p, g->v_mkfs.p, g->h_res.p);
+  hipLaunchKernelGGL(k_mg_emit, dim3(nbr + nbm), B, 0, st, (const MgCtl*)g->ctl.p, g->rig, (const MgMkf*)g->slots.p, (const int*)g->mkf_bidx.p, (const MgPoint*)g->pts.p,
+                     (const PvsPoint*)m->pts.row(), R, nbr, (const int*)g->bidx.p, (const MgMeas*)g->store.p, M, (const uint8_t*)g->mkeep.p, (const int*)blk_meas, nbm,
+                     g->v_points.p, R, g->v_meas.p, M);
+  ICK(hipGetLastError());
+  ICK(hipEventRecord(g->t1, st));
+  if (g->sync()) return -1;
+  drain.armed = false; g->timed = true;
+  *res = *g->h_res.p;
+  g->n_mkfs = res->n_adjust + res->n_fixed; g->n_points = res->n_points; g->n_meas = res->n_meas;
+  return 0;
+}
+
+int mcp_map_bundle_select_last_timing(const mcp_map_graph* g, double* device_ms) {
+  if (!g || !device_ms) return img_fail("mcp_map_bundle_select_last_timing: bad arguments");
+  if (!g->timed) return img_fail("mcp_map_bundle_select_last_timing: the last mcp_map_bundle_select on this graph did not run");
+  float ms = 0.f;
+  ICK(hipEventElapsedTime(&ms, g->t0, g->t1));
+  *device_ms = ms;
+  return 0;
+}
+
+const mcp_bundle_mkf* mcp_map_bundle_mkfs_view(const mcp_map_graph* g, int* count) {
+  if (count) *count = 0;
+  if (!g) { img_fail("mcp_map_bundle_mkfs_view: NULL graph"); return nullptr; }
+  if (count) *count = g->n_mkfs;
+  return g->n_mkfs > 0 ? g->v_mkfs.p : nullptr;
+}
+const mcp_bundle_point* mcp_map_bundle_points_view(const mcp_map_graph* g, int* count) {
+  if (count) *count = 0;
+  if (!g) { img_fail("mcp_map_bundle_points_view: NULL graph"); return nullptr; }
+  if (count) *count = g->n_points;
+  return g->n_points > 0 ? g->v_points.p : nullptr;
+}
+const mcp_bundle_meas* mcp_map_bundle_meas_view(const mcp_map_graph* g, int* count) {
+  if (count) *count = 0;
+  if (!g) { img_fail("mcp_map_bundle_meas_view: NULL graph"); return nullptr; }
+  if (count) *count = g->n_meas;
+  return g->n_meas > 0 ? g->v_meas.p : nullptr;
+}
+
+int mcp_map_bundle_select_host(const mcp_bundle_select_params* p, int ncam, const double* cfb, int n_slots, const double* bfw, const int* mflags, const uint8_t* act,
+                               const double* dep, int n_rows, const double* world, const int* src_mkf, const int* src_cam, const int* pflags, int n_store, const int* ms_mkf,
+                               const int* ms_cam, const int* ms_row, const double* ms_uv, const int* ms_level, const int* ms_source, const uint8_t* ms_alive,
+                               mcp_bundle_select_result* res, int cap_mkfs, mcp_bundle_mkf* out_mkfs, int cap_points, mcp_bundle_point* out_points, int cap_meas,
+                               mcp_bundle_meas* out_meas) {
+  const std::string who = "mcp_map_bundle_select_host";
+  if (!res) return img_fail(who + ": NULL result");
+  const std::string bad = mg_params_check(p);
+  if (!bad.empty()) return img_fail(who + ": " + bad);
+  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !cfb || n_slots < 0 || n_slots > MCP_MAP_MAX_MKFS || n_rows < 0 || n_store < 0 || cap_mkfs < 0 || cap_points < 0 || cap_meas < 0 ||
+      (n_slots > 0 && (!bfw || !mflags || !act || !dep)) || (n_rows > 0 && (!world || !src_mkf || !src_cam || !pflags)) ||
+      (n_store > 0 && (!ms_mkf || !ms_cam || !ms_row || !ms_uv || !ms_level || !ms_source || !ms_alive)) || (cap_mkfs > 0 && !out_mkfs) || (cap_points > 0 && !out_points) ||
+      (cap_meas > 0 && !out_meas)) return img_fail(who + ": bad arguments");
+  if (p->mode == MCP_BUNDLE_RECENT && (p->newest < 0 || p->newest >= n_slots || !(mflags[p->newest] & MCP_MKF_PRESENT)))
+    return img_fail(who + ": the newest MKF (slot " + std::to_string(p->newest) + ") is not present");
+  MgHostIn I{ncam, cfb, n_slots, bfw, mflags, act, dep, n_rows, world, src_mkf, src_cam, pflags, n_store, ms_mkf, ms_cam, ms_row, ms_uv, ms_level, ms_source, ms_alive};
+  mcp_bundle_select_result R;
+  std::vector<mcp_bundle_mkf> mk; std::vector<mcp_bundle_point> pt; std::vector<mcp_bundle_meas> ms;
+  mg_host_select(*p, I, R, mk, pt, ms);
+  if ((int)mk.size() > cap_mkfs || (int)pt.size() > cap_points || (int)ms.size() > cap_meas) return img_fail(who + ": a view does not fit the caller's arrays");
+  *res = R;
+  if (!mk.empty()) std::memcpy(out_mkfs, mk.data(), sizeof(mcp_bundle_mkf)*mk.size());
+  if (!pt.empty()) std::memcpy(out_points, pt.data(), sizeof(mcp_bundle_point)*pt.size());
+  if (!ms.empty()) std::memcpy(out_meas, ms.data(), sizeof(mcp_bundle_meas)*ms.size());
+  return 0;
 }
 
 }  // extern "C"

@@ -54,6 +54,10 @@ IMG_SYMBOLS = [
     "mcp_track_frame_motion", "mcp_track_motion_reset", "mcp_track_motion_get_sbi", "mcp_track_motion_prior_host", "mcp_track_motion_update_host",
     "mcp_track_frame_recover", "mcp_track_recover_pose_host",
     "mcp_track_pose_cov_enable", "mcp_track_pose_cov_last", "mcp_track_pose_cov", "mcp_track_pose_cov_host", "mcp_debug_track_fine_records",
+    "mcp_map_graph_create", "mcp_map_graph_destroy", "mcp_map_graph_set_mkfs", "mcp_map_graph_update_mkfs", "mcp_map_graph_update_points",
+    "mcp_map_graph_add_meas", "mcp_map_graph_erase_meas", "mcp_map_graph_erase_mkf", "mcp_map_graph_compact", "mcp_map_graph_num_meas",
+    "mcp_map_graph_get_meas", "mcp_map_graph_good_counts", "mcp_map_graph_check", "mcp_map_bundle_select", "mcp_map_bundle_mkfs_view",
+    "mcp_map_bundle_points_view", "mcp_map_bundle_meas_view", "mcp_map_bundle_select_host", "mcp_map_bundle_select_last_timing",
 ]
 _BOUND = False
 

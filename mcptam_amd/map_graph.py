@@ -1,0 +1,461 @@
+"""ctypes binding of the device-resident map graph (include/mcp_img.h: mcp_map_graph_*, mcp_map_bundle_select): the MKF slots, the rig, the
+per-point graph columns and the measurement store next to a MapPointTable, and the one call that runs BundleAdjusterBase::BundleAdjustRecent /
+BundleAdjustAll on it and returns the arrays BundleAdjusterMulti::BundleAdjust populates its ChainBundle from.
+
+MapGraph is the class over the ABI; problem_arrays turns a multi-mode synth.Problem into the flat arrays every layer takes (slots = MKF
+indices, rows = point indices); bundle_select_host is mcp_map_bundle_select_host (no device); bundle_select_ref is the numpy restatement,
+written from the reference (src/BundleAdjusterBase.cc:141-265, src/BundleAdjusterMulti.cc:81-200, src/KeyFrame.cc:715-747, 903-927);
+selection_problem makes the synth.Problem a selection describes, which Problem.populate replays into a ChainBundle as it is."""
+import ctypes
+
+import numpy as np
+
+from . import chain_bundle as _cb
+from . import synth
+from .keyframe import _chk
+from .pvs import lib as _pvs_lib
+
+MAX_MKFS = 4096
+MAX_CAMS = 8
+MKF_PRESENT, MKF_FIXED, MKF_BAD = 1, 2, 4
+GP_FIXED, GP_BAD = 1, 2
+BUNDLE_ALL, BUNDLE_RECENT = 0, 1
+SRC_ROOT = 2          # Measurement::eSource values (include/mcptam/KeyFrame.h): stored and returned, not interpreted
+SRC_TRACKER = 0
+
+
+class SelectParams(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("newest", ctypes.c_int), ("n_recent", ctypes.c_int), ("recent_min_size", ctypes.c_int),
+                ("min_points", ctypes.c_int), ("mean_diff_fraction", ctypes.c_double)]
+
+
+class SelectResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("n_adjust", ctypes.c_int), ("n_fixed", ctypes.c_int), ("n_points", ctypes.c_int), ("n_meas", ctypes.c_int),
+                ("has_fixed_points", ctypes.c_int), ("n_dropped_source", ctypes.c_int), ("closest", ctypes.c_int * 8), ("closest_dist", ctypes.c_double * 8)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_[:7]}
+        d["closest"] = [int(v) for v in self.closest]
+        d["closest_dist"] = [float(v) for v in self.closest_dist]
+        return d
+
+
+MKF_DTYPE = np.dtype([("slot", "i4"), ("fixed", "i4")], align=True)
+POINT_DTYPE = np.dtype([("x", "f8", 3), ("row", "i4"), ("src_mkf", "i4"), ("src_cam", "i4"), ("fixed", "i4")], align=True)
+MEAS_DTYPE = np.dtype([("uv", "f8", 2), ("mkf", "i4"), ("cam", "i4"), ("point", "i4"), ("level", "i4"), ("source", "i4"), ("store", "i4")], align=True)
+STRUCT_SIZES = {"mcp_bundle_select_params": ctypes.sizeof(SelectParams), "mcp_bundle_select_result": ctypes.sizeof(SelectResult),
+                "mcp_bundle_mkf": MKF_DTYPE.itemsize, "mcp_bundle_point": POINT_DTYPE.itemsize, "mcp_bundle_meas": MEAS_DTYPE.itemsize}
+
+GRAPH_SYMBOLS = [
+    "mcp_map_graph_create", "mcp_map_graph_destroy", "mcp_map_graph_set_mkfs", "mcp_map_graph_update_mkfs", "mcp_map_graph_update_points",
+    "mcp_map_graph_add_meas", "mcp_map_graph_erase_meas", "mcp_map_graph_erase_mkf", "mcp_map_graph_compact", "mcp_map_graph_num_meas",
+    "mcp_map_graph_get_meas", "mcp_map_graph_good_counts", "mcp_map_graph_check", "mcp_map_bundle_select", "mcp_map_bundle_mkfs_view",
+    "mcp_map_bundle_points_view", "mcp_map_bundle_meas_view", "mcp_map_bundle_select_host", "mcp_map_bundle_select_last_timing",
+]
+
+_BOUND = False
+
+
+def lib():
+    global _BOUND
+    L = _pvs_lib()
+    if not _BOUND:
+        vp, ip = ctypes.c_void_p, ctypes.c_int
+        L.mcp_map_graph_create.restype = vp
+        L.mcp_map_graph_create.argtypes = [vp, ip, vp]
+        L.mcp_map_graph_destroy.argtypes = [vp]
+        L.mcp_map_graph_set_mkfs.argtypes = [vp, ip, ip, vp, vp, vp, vp]
+        L.mcp_map_graph_update_mkfs.argtypes = [vp, ip, vp, vp, vp, vp, vp]
+        L.mcp_map_graph_update_points.argtypes = [vp, ip, vp, vp, vp, vp]
+        L.mcp_map_graph_add_meas.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp]
+        L.mcp_map_graph_erase_meas.argtypes = [vp, ip, vp, vp, vp]
+        L.mcp_map_graph_erase_mkf.argtypes = [vp, ip]
+        L.mcp_map_graph_compact.argtypes = [vp]
+        L.mcp_map_graph_num_meas.argtypes = [vp, vp, vp]
+        L.mcp_map_graph_get_meas.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp, vp, vp]
+        L.mcp_map_graph_good_counts.argtypes = [vp, ip, ip, vp]
+        L.mcp_map_graph_check.argtypes = [vp, vp, vp]
+        L.mcp_map_bundle_select.argtypes = [vp, vp, vp]
+        L.mcp_map_bundle_select_last_timing.argtypes = [vp, vp]
+        for f in (L.mcp_map_bundle_mkfs_view, L.mcp_map_bundle_points_view, L.mcp_map_bundle_meas_view):
+            f.restype = vp
+            f.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+        L.mcp_map_bundle_select_host.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp]
+        _BOUND = True
+    return L
+
+
+def select_params(mode=BUNDLE_RECENT, newest=-1, n_recent=3, recent_min_size=8, min_points=10, mean_diff_fraction=0.5):
+    """BundleAdjusterBase's statics (snRecentNum, snRecentMinSize, snMinMapPoints) and KeyFrame::sdDistanceMeanDiffFraction at their defaults."""
+    return SelectParams(int(mode), int(newest), int(n_recent), int(recent_min_size), int(min_points), float(mean_diff_fraction))
+
+
+def _i32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if shape is not None and a.shape != shape:
+        raise ValueError("expected shape %s, got %s" % (shape, a.shape))
+    return a
+
+
+def _f64(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if shape is not None and a.shape != shape:
+        raise ValueError("expected shape %s, got %s" % (shape, a.shape))
+    return a
+
+
+def _u8(a, shape=None):
+    a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+    if shape is not None and a.shape != shape:
+        raise ValueError("expected shape %s, got %s" % (shape, a.shape))
+    return a
+
+
+def poses12(R, t):
+    """(n, 3, 3), (n, 3) -> (n, 12): R row-major then t."""
+    R, t = np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    return np.ascontiguousarray(np.concatenate([R.reshape(-1, 9), t.reshape(-1, 3)], axis=1))
+
+
+# ---- a Problem as the graph's flat arrays ------------------------------------------------------------------------------------------------
+def _compose(Ra, ta, Rb, tb):
+    """(Ra Rb, Ra tb + ta) over leading axes, each sum written out left to right."""
+    R = Ra[..., :, 0, None] * Rb[..., None, 0, :] + Ra[..., :, 1, None] * Rb[..., None, 1, :] + Ra[..., :, 2, None] * Rb[..., None, 2, :]
+    t = Ra[..., :, 0] * tb[..., None, 0] + Ra[..., :, 1] * tb[..., None, 1] + Ra[..., :, 2] * tb[..., None, 2]
+    return R, t + ta
+
+
+def _apply(R, t, v):
+    return R[..., :, 0] * v[..., None, 0] + R[..., :, 1] * v[..., None, 1] + R[..., :, 2] * v[..., None, 2] + t
+
+
+def problem_arrays(p, depth_mean=None):
+    """The flat arrays of a multi-mode synth.Problem: MKF columns (every MKF present, base_fixed as MCP_MKF_FIXED, every keyframe active),
+    the rig, point columns with world positions computed from pt_x (CamFromWorld_src^-1 * pt_x; a fixed point's pt_x is its world position),
+    the measurements in the Problem's order, all alive, the first measurement of a point from its source keyframe marked SRC_ROOT.
+    depth_mean: (P, C) or None for the mean depth of the points each keyframe measures (1 where it measures none)."""
+    assert p.mode == "multi"
+    P, C, N, M = p.n_mkf, len(p.cams), p.n_points, p.n_meas
+    a = dict(ncam=C, cam_from_base=poses12(p.cam_R, p.cam_t), base_from_world=poses12(p.base_R, p.base_t))
+    a["mkf_flags"] = (MKF_PRESENT | np.where(np.asarray(p.base_fixed, dtype=bool), MKF_FIXED, 0)).astype(np.int32)
+    a["kf_active"] = np.ones((P, C), dtype=np.uint8)
+    fx = np.asarray(p.pt_fixed, dtype=bool)
+    sm, sc = p.pt_src[:, 0].astype(np.int64), p.pt_src[:, 1].astype(np.int64)
+    Rs, ts = _compose(p.cam_R[sc], p.cam_t[sc], p.base_R[sm], p.base_t[sm])
+    world = np.einsum("nji,nj->ni", Rs, p.pt_x - ts)
+    world[fx] = p.pt_x[fx]
+    a["world_pos"] = np.ascontiguousarray(world)
+    a["src_mkf"] = np.where(fx, -1, sm).astype(np.int32)
+    a["src_cam"] = np.where(fx, 0, sc).astype(np.int32)
+    a["pt_flags"] = np.where(fx, GP_FIXED, 0).astype(np.int32)
+    a["ms_mkf"], a["ms_cam"], a["ms_row"] = _i32(p.ms_mkf), _i32(p.ms_cam), _i32(p.ms_pt)
+    a["ms_uv"], a["ms_level"] = _f64(p.ms_uv), _i32(p.ms_level)
+    root = (p.ms_mkf == p.pt_src[p.ms_pt, 0]) & (p.ms_cam == p.pt_src[p.ms_pt, 1]) & ~fx[p.ms_pt]
+    a["ms_source"] = np.where(root, SRC_ROOT, SRC_TRACKER).astype(np.int32)
+    a["ms_alive"] = np.ones(M, dtype=np.uint8)
+    if depth_mean is None:
+        Rk, tk = _compose(p.cam_R[p.ms_cam], p.cam_t[p.ms_cam], p.base_R[p.ms_mkf], p.base_t[p.ms_mkf])
+        z = np.abs(_apply(Rk, tk, world[p.ms_pt])[:, 2])
+        key = p.ms_mkf.astype(np.int64) * C + p.ms_cam
+        s = np.bincount(key, weights=z, minlength=P * C)
+        n = np.bincount(key, minlength=P * C)
+        depth_mean = np.where(n > 0, s / np.maximum(n, 1), 1.0).reshape(P, C)
+        depth_mean = np.where(depth_mean > 0, depth_mean, 1.0)
+    a["kf_depth_mean"] = _f64(depth_mean, (P, C))
+    return a
+
+
+def copy_arrays(a):
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in a.items()}
+
+
+# ---- mcp_map_bundle_select_host ------------------------------------------------------------------------------------------------------------
+def bundle_select_host(a, params):
+    """mcp_map_bundle_select_host over the flat arrays `a` (problem_arrays' keys): (SelectResult, mkfs, points, meas) with the views as
+    structured arrays (MKF_DTYPE, POINT_DTYPE, MEAS_DTYPE).  Needs no device.  A refusal raises RuntimeError."""
+    P, N, M, C = len(a["mkf_flags"]), len(a["pt_flags"]), len(a["ms_mkf"]), int(a["ncam"])
+    cfb, bfw = _f64(a["cam_from_base"], (C, 12)), _f64(a["base_from_world"], (P, 12))
+    mf, act, dep = _i32(a["mkf_flags"], (P,)), _u8(a["kf_active"], (P, C)), _f64(a["kf_depth_mean"], (P, C))
+    wp, sm, sc, pf = _f64(a["world_pos"], (N, 3)), _i32(a["src_mkf"], (N,)), _i32(a["src_cam"], (N,)), _i32(a["pt_flags"], (N,))
+    mm, mc, mr = _i32(a["ms_mkf"], (M,)), _i32(a["ms_cam"], (M,)), _i32(a["ms_row"], (M,))
+    uv, ml, msrc, al = _f64(a["ms_uv"], (M, 2)), _i32(a["ms_level"], (M,)), _i32(a["ms_source"], (M,)), _u8(a["ms_alive"], (M,))
+    res = SelectResult()
+    mk, pt, ms = np.zeros(max(P, 1), dtype=MKF_DTYPE), np.zeros(max(N, 1), dtype=POINT_DTYPE), np.zeros(max(M, 1), dtype=MEAS_DTYPE)
+    rc = lib().mcp_map_bundle_select_host(ctypes.addressof(params), C, cfb.ctypes.data, P, bfw.ctypes.data, mf.ctypes.data, act.ctypes.data, dep.ctypes.data,
+                                          N, wp.ctypes.data, sm.ctypes.data, sc.ctypes.data, pf.ctypes.data, M, mm.ctypes.data, mc.ctypes.data, mr.ctypes.data,
+                                          uv.ctypes.data, ml.ctypes.data, msrc.ctypes.data, al.ctypes.data, ctypes.addressof(res), P, mk.ctypes.data, N, pt.ctypes.data,
+                                          M, ms.ctypes.data)
+    _chk(rc, "map_bundle_select_host")
+    return res, mk[:res.n_adjust + res.n_fixed].copy(), pt[:res.n_points].copy(), ms[:res.n_meas].copy()
+
+
+# ---- the numpy restatement, from the reference -----------------------------------------------------------------------------------------------
+def mkf_distances(a, newest, mean_diff_fraction):
+    """MultiKeyFrame::Distance(newest, k) for every slot k (KeyFrame.cc:903-927 over KeyFrame::Distance, :715-747): (P,) distances (DBL_MAX
+    without a pair of active keyframes) and whether any pair's distance is one the reference stops the process on (:734-744)."""
+    C = int(a["ncam"])
+    cfb, bfw = _f64(a["cam_from_base"]).reshape(C, 12), _f64(a["base_from_world"])
+    P = len(bfw)
+    cR, ct = cfb[:, :9].reshape(C, 3, 3), cfb[:, 9:]
+    bR, bt = bfw[:, :9].reshape(P, 3, 3), bfw[:, 9:]
+    R, t = _compose(cR[None], ct[None], bR[:, None], bt[:, None])                   # (P, C): mse3CamFromWorld
+    Rt = np.swapaxes(R, -1, -2)
+    zero = np.zeros(3)
+    centre = -_apply(Rt, zero, t)                                                   # inverse().get_translation()
+    mean_c = np.zeros((P, C, 3)); mean_c[..., 2] = _f64(a["kf_depth_mean"])
+    mean_w = _apply(Rt, centre, mean_c)                                             # se3KF_inv * v3MeanInCam
+    act = _u8(a["kf_active"]).astype(bool)
+    dC = centre[:, None, :, :] - centre[newest][None, :, None, :]                   # (P, c1 of newest, c2 of k, 3)
+    dM = mean_w[:, None, :, :] - mean_w[newest][None, :, None, :]
+    with np.errstate(all="ignore"):
+        d = np.sqrt((dC * dC).sum(-1)) + np.sqrt((dM * dM).sum(-1)) * mean_diff_fraction
+    pair = act[newest][None, :, None] & act[:, None, :]
+    broken = pair & (~np.isfinite(d) | (d > 1e10))
+    d = np.where(pair & ~np.isnan(d), d, np.finfo(np.float64).max)
+    return d.reshape(P, -1).min(axis=1), broken.reshape(P, -1).any(axis=1)
+
+
+def bundle_select_ref(a, params):
+    """BundleAdjustAll / BundleAdjustRecent and the population loops of BundleAdjusterMulti::BundleAdjust over the flat arrays, in numpy, with
+    the documented deviations (orders by slot / row / store index, slot as the tie-breaker, the short closest list, the dropped-source rule,
+    status 3).  Returns (dict of the result's fields, mkfs, points, meas) as bundle_select_host does."""
+    S = params
+    P, N, M, C = len(a["mkf_flags"]), len(a["pt_flags"]), len(a["ms_mkf"]), int(a["ncam"])
+    mf = np.asarray(a["mkf_flags"])
+    present, mbad, mfixed = (mf & MKF_PRESENT) != 0, (mf & MKF_BAD) != 0, (mf & MKF_FIXED) != 0
+    ok = present & ~mbad
+    res = dict(status=0, n_adjust=0, n_fixed=0, n_points=0, n_meas=0, has_fixed_points=0, n_dropped_source=0, closest=[-1] * 8, closest_dist=[0.0] * 8)
+    empty = (np.zeros(0, dtype=MKF_DTYPE), np.zeros(0, dtype=POINT_DTYPE), np.zeros(0, dtype=MEAS_DTYPE))
+    if S.mode == BUNDLE_ALL:
+        adjust = ok.copy()                                                         # :154-162
+    else:
+        if int(present.sum()) < S.recent_min_size:                                 # :196-201
+            res["status"] = 1
+            return (res,) + empty
+        dist, broken = mkf_distances(a, S.newest, S.mean_diff_fraction)
+        others = present.copy(); others[S.newest] = False
+        if broken[others].any():
+            res["status"] = 3
+            return (res,) + empty
+        cand = np.flatnonzero(others)
+        order = cand[np.lexsort((cand, dist[cand]))][:S.n_recent]                  # NClosestMultiKeyFrames; fewer others: a shorter list
+        for r, k in enumerate(order):
+            res["closest"][r], res["closest_dist"][r] = int(k), float(dist[k])
+        adjust = np.zeros(P, dtype=bool)
+        adjust[S.newest] = True                                                    # :205-206
+        adjust[order[~mbad[order] & ~mfixed[order]]] = True                        # :208-215
+    mm, mr = np.asarray(a["ms_mkf"]).astype(np.int64), np.asarray(a["ms_row"]).astype(np.int64)
+    live = (np.asarray(a["ms_alive"]) != 0) & (mr >= 0) & (mr < N)
+    good = np.bincount(mr[live & ok[mm]], minlength=N)[:N]                         # GoodMeasCount, MapPoint.h:80-87
+    pf = np.asarray(a["pt_flags"])
+    pbad, pfixed = (pf & GP_BAD) != 0, (pf & GP_FIXED) != 0
+    if S.mode == BUNDLE_ALL:
+        sel = ~pbad & ((good >= 2) | pfixed)                                       # :170-176
+    else:
+        seen = np.zeros(N, dtype=bool)
+        seen[mr[live & adjust[mm]]] = True                                         # :218-240
+        sel = seen & ~pbad & (good >= 2)
+    sm, sc = np.asarray(a["src_mkf"]).astype(np.int64), np.asarray(a["src_cam"]).astype(np.int64)
+    src_ok = (sm >= 0) & (sm < P) & (sc >= 0) & (sc < C)
+    src_ok[src_ok] = ok[sm[src_ok]]
+    dropped = sel & ~pfixed & ~src_ok
+    res["n_dropped_source"] = int(dropped.sum())
+    sel &= ~dropped
+    rows = np.flatnonzero(sel)
+    if len(rows) < S.min_points:
+        res["status"] = 2
+        return (res,) + empty
+    keep = live & sel[np.clip(mr, 0, max(N - 1, 0))] & ok[mm]                      # BundleAdjusterMulti.cc:168-200
+    in_bundle = np.zeros(P, dtype=bool)
+    in_bundle[mm[keep]] = True                                                     # :243-261: the parents of spAffectedKeyFrames
+    in_bundle[sm[sel & ~pfixed]] = True                                            # the source MKF of a selected non-fixed row
+    fixed_set = in_bundle & ok & ~adjust
+    slots = np.concatenate([np.flatnonzero(adjust), np.flatnonzero(fixed_set)])
+    mkfs = np.zeros(len(slots), dtype=MKF_DTYPE)
+    mkfs["slot"] = slots
+    mkfs["fixed"] = np.concatenate([mfixed[adjust], np.ones(int(fixed_set.sum()), dtype=bool)])
+    mkf_idx = -np.ones(P, dtype=np.int64); mkf_idx[slots] = np.arange(len(slots))
+    pt_idx = -np.ones(N, dtype=np.int64); pt_idx[rows] = np.arange(len(rows))
+    points = np.zeros(len(rows), dtype=POINT_DTYPE)
+    fx = pfixed[rows]
+    points["row"], points["fixed"] = rows, fx
+    points["src_mkf"] = np.where(fx, -1, mkf_idx[np.where(fx, 0, sm[rows])])
+    points["src_cam"] = np.where(fx, -1, sc[rows])
+    cfb, bfw = _f64(a["cam_from_base"]).reshape(C, 12), _f64(a["base_from_world"])
+    wp = _f64(a["world_pos"])[rows]
+    k, c = np.where(fx, 0, sm[rows]), np.where(fx, 0, sc[rows])
+    R, t = _compose(cfb[c, :9].reshape(-1, 3, 3), cfb[c, 9:], bfw[k, :9].reshape(-1, 3, 3), bfw[k, 9:])   # kf.mse3CamFromWorld = CamFromBase * BaseFromWorld
+    points["x"] = np.where(fx[:, None], wp, _apply(R, t, wp))                       # BundleAdjusterMulti.cc:145-158
+    store = np.flatnonzero(keep)
+    meas = np.zeros(len(store), dtype=MEAS_DTYPE)
+    meas["uv"], meas["mkf"], meas["cam"] = _f64(a["ms_uv"])[store], mkf_idx[mm[store]], np.asarray(a["ms_cam"])[store]
+    meas["point"], meas["level"], meas["source"], meas["store"] = pt_idx[mr[store]], np.asarray(a["ms_level"])[store], np.asarray(a["ms_source"])[store], store
+    res.update(n_adjust=int(adjust.sum()), n_fixed=int(fixed_set.sum()), n_points=len(rows), n_meas=len(store), has_fixed_points=int(fx.any()))
+    return res, mkfs, points, meas
+
+
+def selection_problem(mkfs, points, meas, base_from_world, cam_from_base, cams):
+    """The multi-mode synth.Problem a selection describes: base_* of the bundle's MKFs (base_fixed = fixed in the bundle), pt_* and ms_* from
+    the views, and .window = dict(mkf=slots, adjust=the slots adjusted, points=rows, store=store indices).  Problem.populate replays it."""
+    bfw, cfb = _f64(base_from_world), _f64(cam_from_base).reshape(-1, 12)
+    slots = mkfs["slot"].astype(np.int64)
+    fx = points["fixed"] != 0
+    src = np.stack([np.where(fx, 0, points["src_mkf"]), np.where(fx, 0, points["src_cam"])], axis=1).astype(np.int32)
+    q = synth.Problem(cams=list(cams), mode="multi", n_mkf=len(slots), base_R=bfw[slots, :9].reshape(-1, 3, 3).copy(), base_t=bfw[slots, 9:].copy(),
+                      base_fixed=mkfs["fixed"] != 0, cam_R=cfb[:, :9].reshape(-1, 3, 3).copy(), cam_t=cfb[:, 9:].copy(), pt_x=np.ascontiguousarray(points["x"]),
+                      pt_src=src, pt_fixed=fx, ms_mkf=meas["mkf"].astype(np.int32), ms_cam=meas["cam"].astype(np.int32), ms_pt=meas["point"].astype(np.int32),
+                      ms_uv=np.ascontiguousarray(meas["uv"]), ms_level=meas["level"].astype(np.int32))
+    q.window = dict(mkf=slots, adjust=slots[mkfs["fixed"] == 0] if len(slots) else slots, points=points["row"].astype(np.int64), store=meas["store"].astype(np.int64))
+    return q
+
+
+# ---- the device graph ----------------------------------------------------------------------------------------------------------------------
+class MapGraph:
+    """The device-resident map graph of one MapPointTable (which must outlive it).  Slots are MKF indices, rows are the table's rows."""
+
+    def __init__(self, table, cam_from_base, cams=None):
+        self._L = lib()
+        self.table = table
+        self.cam_from_base = _f64(cam_from_base).reshape(-1, 12).copy()
+        self.ncam = len(self.cam_from_base)
+        self.cams = cams
+        self.base_from_world = np.zeros((MAX_MKFS, 12))          # the host's copy of the poses uploaded (what select() builds its Problem from)
+        self._h = self._L.mcp_map_graph_create(table._h, self.ncam, self.cam_from_base.ctypes.data)
+        if not self._h:
+            raise RuntimeError("mcp_map_graph_create failed: " + _cb.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mcp_map_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @classmethod
+    def from_problem(cls, table, p, depth_mean=None, arrays=None):
+        """The graph (and the table's rows) of a multi-mode synth.Problem: slots = MKF indices, rows = point indices, world positions computed
+        on the host from pt_x, measurements appended in the Problem's order.  arrays: problem_arrays(p) when the caller has them already."""
+        a = problem_arrays(p, depth_mean) if arrays is None else arrays
+        N = len(a["pt_flags"])
+        z = np.zeros((N, 3))
+        if N:
+            table.set(a["world_pos"], z, z, np.ones(N, dtype=np.uint8))
+        g = cls(table, a["cam_from_base"], cams=p.cams)
+        g.load_arrays(a)
+        return g
+
+    def load_arrays(self, a):
+        """MKF columns, point columns and the store from flat arrays (problem_arrays' keys); dead entries of `a` are added and erased."""
+        P, N, M = len(a["mkf_flags"]), len(a["pt_flags"]), len(a["ms_mkf"])
+        if P:
+            self.set_mkfs(a["base_from_world"], a["mkf_flags"], a["kf_active"], a["kf_depth_mean"])
+        if N:
+            self.update_points(np.arange(N), a["src_mkf"], a["src_cam"], a["pt_flags"])
+        if M:
+            self.add_meas(a["ms_mkf"], a["ms_cam"], a["ms_row"], a["ms_uv"], a["ms_level"], a["ms_source"])
+            dead = np.flatnonzero(np.asarray(a["ms_alive"]) == 0)
+            if len(dead):
+                died = self.erase_meas(np.asarray(a["ms_mkf"])[dead], np.asarray(a["ms_cam"])[dead], np.asarray(a["ms_row"])[dead])
+                assert died == len(dead), (died, len(dead))
+
+    def _mkf_args(self, n, base_from_world, flags, kf_active, kf_depth_mean):
+        return _f64(base_from_world, (n, 12)), _i32(flags, (n,)), _u8(kf_active, (n, self.ncam)), _f64(kf_depth_mean, (n, self.ncam))
+
+    def set_mkfs(self, base_from_world, flags, kf_active, kf_depth_mean, first=0):
+        n = len(flags)
+        b, f, a, d = self._mkf_args(n, base_from_world, flags, kf_active, kf_depth_mean)
+        _chk(self._L.mcp_map_graph_set_mkfs(self._h, int(first), n, b.ctypes.data, f.ctypes.data, a.ctypes.data, d.ctypes.data), "map_graph_set_mkfs")
+        self.base_from_world[first:first + n] = b
+
+    def update_mkfs(self, slots, base_from_world, flags, kf_active, kf_depth_mean):
+        s = _i32(slots)
+        n = len(s)
+        b, f, a, d = self._mkf_args(n, base_from_world, flags, kf_active, kf_depth_mean)
+        _chk(self._L.mcp_map_graph_update_mkfs(self._h, n, s.ctypes.data, b.ctypes.data, f.ctypes.data, a.ctypes.data, d.ctypes.data), "map_graph_update_mkfs")
+        self.base_from_world[s] = b
+
+    def update_points(self, rows, src_mkf, src_cam, flags):
+        r = _i32(rows)
+        n = len(r)
+        sm, sc, f = _i32(src_mkf, (n,)), _i32(src_cam, (n,)), _i32(flags, (n,))
+        _chk(self._L.mcp_map_graph_update_points(self._h, n, r.ctypes.data, sm.ctypes.data, sc.ctypes.data, f.ctypes.data), "map_graph_update_points")
+
+    def add_meas(self, mkf, cam, row, uv, level, source=None):
+        """Appends in the given order; returns the store index of the first new entry."""
+        m = _i32(mkf)
+        n = len(m)
+        c, r, u, l = _i32(cam, (n,)), _i32(row, (n,)), _f64(uv, (n, 2)), _i32(level, (n,))
+        s = np.zeros(n, dtype=np.int32) if source is None else _i32(source, (n,))
+        return _chk(self._L.mcp_map_graph_add_meas(self._h, n, m.ctypes.data, c.ctypes.data, r.ctypes.data, u.ctypes.data, l.ctypes.data, s.ctypes.data), "map_graph_add_meas")
+
+    def erase_meas(self, mkf, cam, row):
+        """KeyFrame::EraseMeasurementOfPoint for distinct keys; returns how many live entries died."""
+        m = _i32(mkf)
+        n = len(m)
+        c, r = _i32(cam, (n,)), _i32(row, (n,))
+        return _chk(self._L.mcp_map_graph_erase_meas(self._h, n, m.ctypes.data, c.ctypes.data, r.ctypes.data), "map_graph_erase_meas")
+
+    def erase_mkf(self, slot):
+        return _chk(self._L.mcp_map_graph_erase_mkf(self._h, int(slot)), "map_graph_erase_mkf")
+
+    def compact(self):
+        """Stable removal of the dead entries: store indices change."""
+        _chk(self._L.mcp_map_graph_compact(self._h), "map_graph_compact")
+
+    def num_meas(self):
+        live, stored = ctypes.c_int(0), ctypes.c_int(0)
+        _chk(self._L.mcp_map_graph_num_meas(self._h, ctypes.addressof(live), ctypes.addressof(stored)), "map_graph_num_meas")
+        return live.value, stored.value
+
+    def get_meas(self, first=0, count=None):
+        count = self.num_meas()[1] - first if count is None else int(count)
+        n = max(count, 1)
+        o = dict(mkf=np.zeros(n, np.int32), cam=np.zeros(n, np.int32), row=np.zeros(n, np.int32), uv=np.zeros((n, 2)), level=np.zeros(n, np.int32),
+                 source=np.zeros(n, np.int32), alive=np.zeros(n, np.uint8))
+        _chk(self._L.mcp_map_graph_get_meas(self._h, int(first), count, *[o[k].ctypes.data for k in ("mkf", "cam", "row", "uv", "level", "source", "alive")]), "map_graph_get_meas")
+        return {k: v[:count] for k, v in o.items()}
+
+    def good_counts(self, first=0, count=None):
+        count = self.table.rows - first if count is None else int(count)
+        out = np.zeros(max(count, 1), dtype=np.int32)
+        _chk(self._L.mcp_map_graph_good_counts(self._h, int(first), count, out.ctypes.data), "map_graph_good_counts")
+        return out[:count]
+
+    def check(self):
+        """(duplicates among the live entries, dead entries): a host sort of the read-back keys, for tests and adapters under development."""
+        d, x = ctypes.c_int(0), ctypes.c_int(0)
+        _chk(self._L.mcp_map_graph_check(self._h, ctypes.addressof(d), ctypes.addressof(x)), "map_graph_check")
+        return d.value, x.value
+
+    def views(self, copy=True):
+        """(mkfs, points, meas) of the last select: structured arrays over the library's pinned block (valid until the next select) or copies."""
+        out = []
+        for fn, dt in ((self._L.mcp_map_bundle_mkfs_view, MKF_DTYPE), (self._L.mcp_map_bundle_points_view, POINT_DTYPE), (self._L.mcp_map_bundle_meas_view, MEAS_DTYPE)):
+            cnt = ctypes.c_int(0)
+            ptr = fn(self._h, ctypes.byref(cnt))
+            v = np.frombuffer((ctypes.c_char * (cnt.value * dt.itemsize)).from_address(ptr), dtype=dt) if cnt.value else np.zeros(0, dtype=dt)
+            out.append(v.copy() if copy else v)
+        return tuple(out)
+
+    def last_timing(self):
+        """Device time of the last select's submission in ms (between two events on the table's stream)."""
+        ms = ctypes.c_double(0.0)
+        _chk(self._L.mcp_map_bundle_select_last_timing(self._h, ctypes.addressof(ms)), "map_bundle_select_last_timing")
+        return ms.value
+
+    def select_raw(self, params, copy=True):
+        """mcp_map_bundle_select: (SelectResult, mkfs, points, meas)."""
+        res = SelectResult()
+        _chk(self._L.mcp_map_bundle_select(self._h, ctypes.addressof(params), ctypes.addressof(res)), "map_bundle_select")
+        return (res,) + self.views(copy)
+
+    def select(self, mode=BUNDLE_RECENT, newest=-1, params=None, **kw):
+        """BundleAdjustRecent / BundleAdjustAll over the graph in one call: (SelectResult, synth.Problem or None when status != 0).  The Problem
+        holds base_* (base_fixed = fixed in the bundle), pt_*, ms_* and .window = dict(mkf=slots, adjust=..., points=rows, store=store indices);
+        Problem.populate(bundle) replays it.  kw: select_params' fields."""
+        params = select_params(mode, newest, **kw) if params is None else params
+        res, mkfs, points, meas = self.select_raw(params)
+        if res.status != 0:
+            return res, None
+        return res, selection_problem(mkfs, points, meas, self.base_from_world, self.cam_from_base, self.cams)

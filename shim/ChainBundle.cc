@@ -98,6 +98,19 @@ void ChainBundle::AddMeas(std::vector<int> vCams, int nPointIdx, Vector<2> v2Pos
   ROS_ASSERT_MSG(nRet == 0, "ChainBundle::AddMeas: %s", mcp_last_error());
 }
 
+void ChainBundle::AddPoints(int nCount, const double* pdX, const int* pnChains, int nStride, const int* pnChainLen, const unsigned char* pbFixed, int* pnIDsOut)
+{
+  int nRet = mcp_ba_add_points(mpHandle, nCount, pdX, pnChains, nStride, pnChainLen, pbFixed, pnIDsOut);
+  ROS_ASSERT_MSG(nRet == 0, "ChainBundle::AddPoints: %s", mcp_last_error());
+}
+
+void ChainBundle::AddMeasurements(int nCount, const int* pnChains, int nStride, const int* pnChainLen, const int* pnPointIDs, const double* pdUV,
+                                  const double* pdSigmaSq, const int* pnCamIndex)
+{
+  int nRet = mcp_ba_add_measurements(mpHandle, nCount, pnChains, nStride, pnChainLen, pnPointIDs, pdUV, pdSigmaSq, pnCamIndex);
+  ROS_ASSERT_MSG(nRet == 0, "ChainBundle::AddMeasurements: %s", mcp_last_error());
+}
+
 void ChainBundle::Initialize()
 {
   mvOutlierMeasurementIdx.clear();

@@ -26,6 +26,11 @@ public:
   int AddPose(TooN::SE3<> se3PoseFromRef, bool bFixed);
   int AddPoint(TooN::Vector<3> v3PointInCam, std::vector<int> vCams, bool bFixed);
   void AddMeas(std::vector<int> vCams, int nPointIdx, TooN::Vector<2> v2Pos, double dNoiseSigmaSquared, std::string cameraName);
+  /// Batched forms over flat arrays (mcp_ba_add_points / mcp_ba_add_measurements): what BundleAdjusterBase_gpu.cc fills from the
+  /// views of mcp_map_bundle_select.  pnCamIndex indexes the cameras in the order of the map the constructor was given.
+  void AddPoints(int nCount, const double* pdX, const int* pnChains, int nStride, const int* pnChainLen, const unsigned char* pbFixed, int* pnIDsOut);
+  void AddMeasurements(int nCount, const int* pnChains, int nStride, const int* pnChainLen, const int* pnPointIDs, const double* pdUV,
+                       const double* pdSigmaSq, const int* pnCamIndex);
 
   /// Kept for source compatibility (the reference's Compute calls it first); the handle prepares itself inside Compute.
   void Initialize();
