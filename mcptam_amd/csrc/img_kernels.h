@@ -604,7 +604,9 @@ __device__ __forceinline__ int pf_iterate(const uint8_t* __restrict__ limg, int 
       float fPixel = fTL*(float)q[0] + fTR*(float)q[1];
       fPixel = fPixel + fBL*(float)q[lw];
       fPixel = fPixel + fBR*(float)q[lw + 1];
-      const double d = (double)fPixel - (double)tmpl[8*sy + sx] + mean;
+      // `fPixel - mimTemplate[ir] + mdMeanDiff` (:456): float minus byte is a FLOAT subtraction, which rounds where the template is
+      // more than about twice as bright as the pixel; only then does the double come in
+      const double d = (double)(fPixel - (float)tmpl[8*sy + sx]) + mean;
       dprod[0][lane] = d*gx; dprod[1][lane] = d*gy; dprod[2][lane] = d;
     }
     __syncthreads();

@@ -662,6 +662,7 @@ def test_coarse_template_against_numpy_bilinear_warp():
     pixels may differ by one grey level -- nothing more, and almost nowhere."""
     from mcptam_amd import synth_img
     from oracle import OracleKeyFrame, oracle_track_search
+    from patch_border_cases import numpy_template
     sc = synth_img.make_tracking_scene(size=(320, 240))
     cam = sc["cam"]
     A, B = OracleKeyFrame(320, 240), OracleKeyFrame(320, 240)
@@ -673,16 +674,8 @@ def test_coarse_template_against_numpy_bilinear_warp():
     for i, p in enumerate(pts):
         if not out["in_image"][i] or out["template_bad"][i] or out["search_level"][i] < 0:
             continue
-        W = out["warp_inverse"][i].reshape(2, 2)
-        M = np.linalg.inv(W) * (1 << int(out["search_level"][i]))
-        I = imgs[p["source_level"]]
-        gx, gy = np.meshgrid(np.arange(8) - 4.0, np.arange(8) - 4.0)
-        px = p["center"][0] + M[0, 0]*gx + M[0, 1]*gy
-        py = p["center"][1] + M[1, 0]*gx + M[1, 1]*gy
-        lx, ly = np.floor(px).astype(int), np.floor(py).astype(int)
-        fx, fy = px - lx, py - ly
-        v = (1 - fy)*((1 - fx)*I[ly, lx] + fx*I[ly, lx + 1]) + fy*((1 - fx)*I[ly + 1, lx] + fx*I[ly + 1, lx + 1])
-        d = np.abs(np.floor(v + 1e-9).astype(int) - out["templ"][i].reshape(8, 8).astype(int))
+        v = numpy_template(out["warp_inverse"][i], out["search_level"][i], p["center"], imgs[p["source_level"]])
+        d = np.abs(v - out["templ"][i].reshape(8, 8).astype(int))
         assert d.max() <= 1
         tot += 64; diff += int((d > 0).sum())
     assert tot > 64*80 and diff <= 0.01*tot
@@ -695,6 +688,7 @@ def test_coarse_zmssd_search_against_numpy():
     accepted below 8*8*250 -- best corner, score and found flag of every tracked point."""
     from mcptam_amd import synth_img
     from oracle import OracleKeyFrame, oracle_track_search
+    from patch_border_cases import numpy_coarse_search
     sc = synth_img.make_tracking_scene(size=(320, 240))
     cam = sc["cam"]
     A, B = OracleKeyFrame(320, 240), OracleKeyFrame(320, 240)
@@ -710,29 +704,8 @@ def test_coarse_zmssd_search_against_numpy():
         if not out["searched"][i]:
             continue
         L = int(out["search_level"][i])
-        s = 1 << L
         T = out["templ"][i].astype(np.int64).reshape(8, 8)
-        SA, TT = int(T.sum()), int((T*T).sum())
-        px, py = int(out["image"][i][0])//s, int(out["image"][i][1])//s          # CVD::ir truncates; positions are positive
-        r = (rng_px + s - 1)//s
-        I = imgs[L]
-        h, w = I.shape
-        best, bp = MAXSSD + 1, None
-        for (cx, cy) in cors[L]:
-            if cy < max(py - r, 0) or cy > py + r or cx < max(px - r, 0) or cx > px + r:
-                continue
-            if (px - cx)**2 + (py - cy)**2 > r*r:
-                continue
-            if not (4 <= cx < w - 4 and 4 <= cy < h - 4):
-                ssd = MAXSSD + 1
-            else:
-                P = I[cy - 4:cy + 4, cx - 4:cx + 4]
-                SB = int(P.sum())
-                num = 2*SA*SB - SA*SA - SB*SB
-                q = abs(num)//64 * (1 if num >= 0 else -1)                            # C integer division
-                ssd = q + int((P*P).sum()) + TT - 2*int((P*T).sum())
-            if ssd < best:
-                best, bp = ssd, (int(cx), int(cy))
+        best, bp, _ = numpy_coarse_search(T, out["image"][i], L, rng_px, imgs[L], cors[L])
         assert int(out["score"][i]) == best, (i, out["score"][i], best)
         assert bool(out["found"][i]) == (best < MAXSSD)
         if out["found"][i]:
@@ -1030,6 +1003,7 @@ def test_subpixel_refinement_against_numpy():
     coarse ones."""
     from mcptam_amd import synth_img
     from oracle import OracleKeyFrame, oracle_track_search
+    from patch_border_cases import numpy_subpix
     sc = synth_img.make_tracking_scene(size=(320, 240))
     cam = sc["cam"]
     A, B = OracleKeyFrame(320, 240), OracleKeyFrame(320, 240)
@@ -1047,35 +1021,8 @@ def test_subpixel_refinement_against_numpy():
             continue
         assert fine["did_subpix"][i] and not coarse["did_subpix"][i]
         L = int(fine["search_level"][i]); s = 1 << L
-        I = imgs[L]; h, w = I.shape
-        T = fine["templ"][i].astype(np.float64).reshape(8, 8)
-        gx = 0.5*(T[1:7, 2:8] - T[1:7, 0:6])
-        gy = 0.5*(T[2:8, 1:7] - T[0:6, 1:7])
-        G = np.stack([gx.ravel(), gy.ravel(), np.ones(36)], axis=1)           # row-major over (y, x)
-        Hinv = np.linalg.inv(G.T @ G)
-        sp = np.array([(coarse["coarse_x"][i] + 0.5)*s - 0.5, (coarse["coarse_y"][i] + 0.5)*s - 0.5])
-        assert np.array_equal(sp, coarse["found_pos"][i])
-        mean, conv = 0.0, 0
-        for _ in range(its):
-            cx, cy = (sp[0] + 0.5)/s - 0.5, (sp[1] + 0.5)/s - 0.5
-            rx, ry = int(np.floor(cx + 0.5)), int(np.floor(cy + 0.5))         # round() of a positive number
-            if not (5 <= rx < w - 5 and 5 <= ry < h - 5):
-                conv = -1
-                break
-            bx, by = cx - 4, cy - 4
-            dX, dY = bx - np.floor(bx), by - np.floor(by)
-            f = np.float32
-            fTL, fTR, fBL, fBR = f((1 - dX)*(1 - dY)), f(dX*(1 - dY)), f((1 - dX)*dY), f(dX*dY)
-            x0, y0 = int(bx), int(by)
-            P = I[y0 + 1:y0 + 8, x0 + 1:x0 + 8].astype(np.float32)
-            pix = ((fTL*P[:6, :6] + fTR*P[:6, 1:7]) + fBL*P[1:7, :6]) + fBR*P[1:7, 1:7]      # float32, left to right
-            d = pix.astype(np.float64) - T[1:7, 1:7] + mean
-            up = Hinv @ (G.T @ d.ravel())
-            sp = sp - up[:2]*s
-            mean -= up[2]
-            if up[0]**2 + up[1]**2 < 0.03**2:
-                conv = 1
-                break
+        conv, sp, sp0 = numpy_subpix(fine["templ"][i], (coarse["coarse_x"][i], coarse["coarse_y"][i]), L, imgs[L], its)
+        assert np.array_equal(sp0, coarse["found_pos"][i])
         assert bool(fine["found"][i]) == (conv == 1), (i, conv)
         if conv == 1:
             assert np.abs(fine["found_pos"][i] - sp).max() < 1e-7, (i, fine["found_pos"][i], sp)
