@@ -293,17 +293,12 @@ class MapPointTable {
                                                         const std::vector<int>& vStrides, bool bImagesOnDevice, const std::vector<mcp_camera>& vCams,
                                                         double base_from_world[12], const std::vector<double>& vCamFromBase,
                                                         const mcp_track_map_params& params, mcp_track_map_result* pResult) {
-    const int nc = (int)vTargets.size();
-    if ((int)vCams.size() != nc || (int)vCamFromBase.size() != 12*nc || (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)))
-      throw std::invalid_argument("MapPointTable::TrackMap: array sizes");
-    std::vector<mcp_kf*> h(nc);
-    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    const Frame f("TrackMap", vTargets, vImages, vStrides, vCams, nullptr, vCamFromBase);
     mcp_track_map_result r;
-    check(mcp_track_map(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
-                        nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r));
+    check(mcp_track_map(mpDev, f.nc, f.h.data(), f.imgs, f.strides, bImagesOnDevice ? 1 : 0, nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r));
     if (pResult) *pResult = r;
-    std::vector<std::vector<mcp_track_map_item>> out(nc);
-    for (int c = 0; c < nc; ++c) {
+    std::vector<std::vector<mcp_track_map_item>> out(f.nc);
+    for (int c = 0; c < f.nc; ++c) {
       int n = 0;
       const mcp_track_map_item* it = mcp_track_map_view(mpDev, c, &n);
       out[c].assign(it, it + n);
@@ -330,14 +325,10 @@ class MapPointTable {
   void TrackMapRecord(const std::vector<KeyFrame*>& vTargets, const std::vector<const uint8_t*>& vImages, const std::vector<int>& vStrides, bool bImagesOnDevice,
                       const std::vector<mcp_camera>& vCams, double base_from_world[12], const std::vector<double>& vCamFromBase, const mcp_track_map_params& params,
                       const mcp_track_record_params& recParams, mcp_track_map_result* pResult, mcp_track_record* pRecord) {
-    const int nc = (int)vTargets.size();
-    if ((int)vCams.size() != nc || (int)vCamFromBase.size() != 12*nc || (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !pRecord)
-      throw std::invalid_argument("MapPointTable::TrackMapRecord: array sizes");
-    std::vector<mcp_kf*> h(nc);
-    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    const Frame f("TrackMapRecord", vTargets, vImages, vStrides, vCams, nullptr, vCamFromBase, pRecord != nullptr);
     mcp_track_map_result r;
-    check(mcp_track_map_record(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
-                               nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord));
+    check(mcp_track_map_record(mpDev, f.nc, f.h.data(), f.imgs, f.strides, bImagesOnDevice ? 1 : 0, nullptr, vCams.data(), base_from_world, vCamFromBase.data(), &params, &r,
+                               &recParams, pRecord));
     if (pResult) *pResult = r;
   }
   /// Tracker::TrackFrame's tracking branch (src/Tracker.cc:431-434) in one call: ApplyMotionModel with the SBI rotation estimate, TrackMap with
@@ -347,15 +338,10 @@ class MapPointTable {
                         const std::vector<mcp_camera>& vCams, const std::vector<mcp_camera>& vCamsSBI, double base_from_world[12], const std::vector<double>& vCamFromBase,
                         const mcp_track_map_params& params, const mcp_track_record_params& recParams, const mcp_track_motion_params& motionParams,
                         mcp_track_map_result* pResult, mcp_track_record* pRecord, mcp_track_motion* pMotion) {
-    const int nc = (int)vTargets.size();
-    if ((int)vCams.size() != nc || (int)vCamsSBI.size() != nc || (int)vCamFromBase.size() != 12*nc ||
-        (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !pRecord || !pMotion)
-      throw std::invalid_argument("MapPointTable::TrackFrameMotion: array sizes");
-    std::vector<mcp_kf*> h(nc);
-    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    const Frame f("TrackFrameMotion", vTargets, vImages, vStrides, vCams, &vCamsSBI, vCamFromBase, pRecord && pMotion);
     mcp_track_map_result r;
-    check(mcp_track_frame_motion(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
-                                 nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord, &motionParams, pMotion));
+    check(mcp_track_frame_motion(mpDev, f.nc, f.h.data(), f.imgs, f.strides, bImagesOnDevice ? 1 : 0, nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(),
+                                 &params, &r, &recParams, pRecord, &motionParams, pMotion));
     if (pResult) *pResult = r;
   }
   /// Tracker::TrackFrame's lost branch (src/Tracker.cc:493-502, 526-552; src/Relocaliser.cc:61-120) in one call: the relocaliser over the
@@ -368,19 +354,16 @@ class MapPointTable {
                          const std::vector<KeyFrame*>& vCandidates, const std::vector<int>& vCandCams, const std::vector<double>& vCandPoses,
                          const mcp_track_recover_params& recoverParams, mcp_track_map_result* pResult, mcp_track_record* pRecord, mcp_track_motion* pMotion,
                          mcp_track_recover* pRecover, std::vector<double>* pScores = nullptr) {
-    const int nc = (int)vTargets.size(), nk = (int)vCandidates.size();
-    if ((int)vCams.size() != nc || (int)vCamsSBI.size() != nc || (int)vCamFromBase.size() != 12*nc || (int)vCandCams.size() != nk || (int)vCandPoses.size() != 12*nk ||
-        (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !pRecord || !pMotion || !pRecover)
-      throw std::invalid_argument("MapPointTable::TrackFrameRecover: array sizes");
-    std::vector<mcp_kf*> h(nc), hk(nk > 0 ? nk : 1);
-    for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    const int nk = (int)vCandidates.size();
+    const Frame f("TrackFrameRecover", vTargets, vImages, vStrides, vCams, &vCamsSBI, vCamFromBase,
+                  (int)vCandCams.size() == nk && (int)vCandPoses.size() == 12*nk && pRecord && pMotion && pRecover);
+    std::vector<mcp_kf*> hk(nk > 0 ? nk : 1);
     for (int i = 0; i < nk; ++i) hk[i] = vCandidates[i] ? vCandidates[i]->handle() : nullptr;
     if (pScores) pScores->assign(nk, 0.0);
     mcp_track_map_result r;
-    check(mcp_track_frame_recover(mpDev, nc, h.data(), vImages.empty() ? nullptr : vImages.data(), vImages.empty() ? nullptr : vStrides.data(), bImagesOnDevice ? 1 : 0,
-                                  nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(), &params, &r, &recParams, pRecord, &motionParams, pMotion,
-                                  nk, hk.data(), nk ? vCandCams.data() : nullptr, nk ? vCandPoses.data() : nullptr, &recoverParams, pRecover,
-                                  pScores && nk ? pScores->data() : nullptr));
+    check(mcp_track_frame_recover(mpDev, f.nc, f.h.data(), f.imgs, f.strides, bImagesOnDevice ? 1 : 0, nullptr, vCams.data(), vCamsSBI.data(), base_from_world, vCamFromBase.data(),
+                                  &params, &r, &recParams, pRecord, &motionParams, pMotion, nk, hk.data(), nk ? vCandCams.data() : nullptr, nk ? vCandPoses.data() : nullptr,
+                                  &recoverParams, pRecover, pScores && nk ? pScores->data() : nullptr));
     if (pResult) *pResult = r;
   }
   /// the two poses of a recovery on the host (mcp_track_recover_pose_host; needs no device): cam_pose = SE3fromSE2(se2) * cam_from_world_best,
@@ -493,6 +476,19 @@ class MapPointTable {
     for (int k = 0; k < n; ++k) h[k] = vSources[k] ? vSources[k]->handle() : nullptr;
     return h;
   }
+  // what the one-call frames share: the size checks (who: the method's name in the refusal; bOwn: the method's own conditions hold), the
+  // target handles, the image and stride pointers (nullptr: the pyramids are current)
+  struct Frame {
+    int nc; std::vector<mcp_kf*> h; const uint8_t* const* imgs; const int* strides;
+    Frame(const char* who, const std::vector<KeyFrame*>& vTargets, const std::vector<const uint8_t*>& vImages, const std::vector<int>& vStrides,
+          const std::vector<mcp_camera>& vCams, const std::vector<mcp_camera>* pvCamsSBI, const std::vector<double>& vCamFromBase, bool bOwn = true)
+        : nc((int)vTargets.size()), h(vTargets.size()), imgs(vImages.empty() ? nullptr : vImages.data()), strides(vImages.empty() ? nullptr : vStrides.data()) {
+      if ((int)vCams.size() != nc || (pvCamsSBI && (int)pvCamsSBI->size() != nc) || (int)vCamFromBase.size() != 12*nc ||
+          (!vImages.empty() && ((int)vImages.size() != nc || (int)vStrides.size() != nc)) || !bOwn)
+        throw std::invalid_argument(std::string("MapPointTable::") + who + ": array sizes");
+      for (int c = 0; c < nc; ++c) h[c] = vTargets[c]->handle();
+    }
+  };
   static void sizes(int n, const std::vector<double>& a, const std::vector<double>& b, const std::vector<double>& c) {
     if ((int)a.size() != 3*n || (int)b.size() != 3*n || (int)c.size() != 3*n) throw std::invalid_argument("MapPointTable: array sizes");
   }

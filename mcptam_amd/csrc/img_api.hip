@@ -1317,6 +1317,15 @@ template <class T> static const T* cam_view(const T* list, const int* first, int
   return k > 0 ? list + first[cam] : nullptr;
 }
 
+// a small table built on the host for every call goes to the device only when it differs, byte for byte, from the last one uploaded
+template <class T> static int upload_when_changed(std::vector<T>& last, PinBuf<T>& pinned, Buf<T>& dev, const std::vector<T>& now, hipStream_t st) {
+  if (last.size() == now.size() && std::memcmp(last.data(), now.data(), sizeof(T)*now.size()) == 0) return 0;
+  std::memcpy(pinned.p, now.data(), sizeof(T)*now.size());
+  ICK(hipMemcpyAsync(dev.p, pinned.p, sizeof(T)*now.size(), hipMemcpyHostToDevice, st));
+  last = now;
+  return 0;
+}
+
 static int points_upload(mcp_map_points* m, const char* who, bool by_ids, int first, int count, const int* ids, const double* wp, const double* pr, const double* pd,
                          const uint8_t* us) {
   int top = 0;
@@ -1427,13 +1436,9 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
     C.mask0 = mask0_of(targets[c]); C.mask_w = targets[c]->lev[0].w; C.mask_h = targets[c]->lev[0].h;
     C.cap = Y.cap[c]; C.out_first = Y.first[c];
   }
-  // the cameras, their CamFromBase, masks and caps rarely change from frame to frame: their table is uploaded only when they do
+  // the cameras, their CamFromBase, masks and caps rarely change from frame to frame
   mcp_map_points::Pvs& V = m->pvs;
-  if (V.tab_last.size() != tab.size() || std::memcmp(V.tab_last.data(), tab.data(), sizeof(PvsCam)*tab.size()) != 0) {
-    std::memcpy(V.h_tab.p, tab.data(), sizeof(PvsCam)*tab.size());
-    ICK(hipMemcpyAsync(V.d_tab.p, V.h_tab.p, sizeof(PvsCam)*tab.size(), hipMemcpyHostToDevice, m->st));
-    V.tab_last = tab;
-  }
+  if (upload_when_changed(V.tab_last, V.h_tab, V.d_tab, tab, m->st)) return -1;
   if (d_bfw && d_gate) hipLaunchKernelGGL(k_pvs_mark_gated, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, d_gate, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
   else if (d_bfw) hipLaunchKernelGGL(k_pvs_mark_at, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
   else hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
@@ -1569,10 +1574,9 @@ static int motion_check(const std::string& who, int ncam, const mcp_camera* cams
 struct RecoverArg {
   int ncand; mcp_kf* const* kf; const int* cam; const double* cfw; const mcp_track_recover_params* p; mcp_track_recover* out; double* scores;
 };
-// its refusals; live[i]: candidate i is a live keyframe handle with an SBI that is none of the frame's targets (the others are skipped)
+// its refusals behind TrackFrame::check's NULL structs; live[i]: candidate i is a live keyframe handle with an SBI that is none of the frame's targets (the others are skipped)
 static int recover_check(const std::string& who, const mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_track_motion_params* mp, const RecoverArg& rc,
                          std::vector<uint8_t>& live) {
-  if (!rc.p || !rc.out) return img_fail(who + ": NULL recover parameters or recover result");
   if (mp->apply) return img_fail(who + ": the motion model is not applied on a recovery frame (motion apply must be 0)");
   if (rc.ncand < 0) return img_fail(who + ": negative candidate count");
   if (rc.ncand > 0 && (!rc.kf || !rc.cam || !rc.cfw)) return img_fail(who + ": NULL candidate arrays");
@@ -1684,96 +1688,96 @@ int mcp_debug_track_fine_records(const mcp_map_points* mc, int cap, mcp_pose_poi
   return 0;
 }
 
-// the body of mcp_track_map (rp == NULL: exactly its launches), of mcp_track_map_record (rp, rec checked by the caller), of
-// mcp_track_frame_motion (mo: k_frame_sbi and k_motion_prior between the pyramids' event and the PVS, which then reads the pose from the
-// parameter block, and k_motion_update behind the fine iterations; mo == NULL: no launch more or less than before) and of
-// mcp_track_frame_recover (rc, with mo: the four relocaliser kernels in front of k_frame_sbi -- k_reloc_pick leaves the recovered pose in the
-// parameter block before k_motion_prior reads it as the start -- and the PVS behind their gate; rc == NULL: no launch more or less than before)
-static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
-                         const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
-                         mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec, const MotionArg* mo = nullptr,
-                         const RecoverArg* rc = nullptr) {
-  if (!m) return img_fail(who + ": NULL table");
-  if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail(who + ": bad arguments");
-  if (prm->coarse_max < 0 || prm->coarse_range < 0 || prm->coarse_min < 0 || prm->coarse_subpix_its < 0 || prm->max_patches < 0)
-    return img_fail(who + ": negative cap, range or iteration count");
-  if (!est_ok(prm->estimator)) return img_fail(who + ": unknown M-estimator");
-  for (int c = 0; c < ncam; ++c) {
-    if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail(who + ": bad arguments for camera " + std::to_string(c));
-    if (target_on_table_device(who, m, c, targets[c])) return -1;
-    for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail(who + ": a keyframe appears twice in a frame with images");
-    if (mo && !imgs && !targets[c]->has_image) return img_fail(who + ": camera " + std::to_string(c) + "'s target holds no frame and no images were given");
+// ---- the one-call frames: mcp_track_map, mcp_track_map_record, mcp_track_frame_motion, mcp_track_frame_recover --------------------------
+// the parameter block of a frame: cameras' search table | camera models | CamFromBase | BaseFromWorld + mu | override sigma x 2 | nonlinear
+// flags x 2 | the SBI cameras (with a motion model) | the candidate list (on a recovery frame); at(): those places in the host's or the device's copy
+struct TmBlock { TmCam* tab; mcp_camera* cams; double* cfb; double* pm; double* ov; uint8_t* nl; mcp_camera* cams_sbi; RelocCand* cand; };
+struct TmBlockLayout {
+  size_t o_tab, o_cam, o_cfb, o_pm, o_ov, o_nl, o_cs, o_rc, total;
+  TmBlock at(uint8_t* b) const {
+    return TmBlock{reinterpret_cast<TmCam*>(b + o_tab), reinterpret_cast<mcp_camera*>(b + o_cam), reinterpret_cast<double*>(b + o_cfb), reinterpret_cast<double*>(b + o_pm),
+                   reinterpret_cast<double*>(b + o_ov), b + o_nl, reinterpret_cast<mcp_camera*>(b + o_cs), reinterpret_cast<RelocCand*>(b + o_rc)};
   }
-  if (mo && motion_check(who, ncam, mo->cams_sbi, mo->p, mo->out)) return -1;
-  std::vector<uint8_t> cand_live;
-  if (rc && recover_check(who, m, ncam, targets, mo->p, *rc, cand_live)) return -1;
-  const int ncand = rc ? rc->ncand : 0;
-  ICK(hipSetDevice(m->device));
-  // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
-  m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate(); m->cv.invalidate();
-  const bool want_items = !rp || rp->want_items != 0;
-  const int n = m->rows;
-  const size_t NB = (size_t)ncam*std::max(n, 1);                   // bound of every per-item array: a camera's sets are distinct rows
-  const bool coarse = prm->try_coarse && prm->coarse_max > 0;
-  const size_t n_coarse_max = coarse ? std::min(NB, (size_t)ncam*prm->coarse_max) : 0;
-  const bool regs = tm_regs_ok();
-  // everything is allocated before the first enqueue
-  if (m->ensure_states(ncam)) return -1;
-  if (m->tm.pvs.alloc(NB) || m->tm.counts.alloc((size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS) || m->tm.sel.alloc(NB) || m->tm.k0.alloc(NB) || m->tm.k1.alloc(NB) || m->tm.live.alloc(NB) ||
-      m->tm.ctl.alloc(1) || m->tm.slots.alloc(std::max<size_t>(m->slots.size(), 1)) || m->tm.h_slots.alloc(std::max<size_t>(m->slots.size(), 1)) ||
-      m->tm.crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm.frec.alloc(NB) || m->tm.w.alloc(NB) || m->tm.items.alloc(NB) || (want_items && m->tm.h_items.alloc(NB)) || m->tm.h_res.alloc(1) ||
-      m->pvs.reserve(ncam, n)) return -1;
-  if (NB > (size_t)PRR_THREADS*PRR_PPT || !regs) {
-    if (m->tm.J.alloc(12*NB) || m->tm.ex.alloc(2*NB) || m->tm.e2.alloc(NB)) return -1;
+};
+static TmBlockLayout tm_block_layout(int ncam, bool mo, bool rc, int ncand) {
+  TmBlockLayout L; const size_t cams = tm_align(sizeof(mcp_camera)*(size_t)ncam);
+  L.o_tab = 0; L.o_cam = tm_align(sizeof(TmCam)*(size_t)ncam); L.o_cfb = L.o_cam + cams; L.o_pm = L.o_cfb + tm_align(96*(size_t)ncam);
+  L.o_ov = L.o_pm + tm_align(18*8); L.o_nl = L.o_ov + tm_align(20*8); L.o_cs = L.o_nl + tm_align(20);
+  L.o_rc = L.o_cs + (mo ? cams : 0); L.total = L.o_rc + (rc ? tm_align(sizeof(RelocCand)*(size_t)std::max(ncand, 1)) : 0);
+  return L;
+}
+
+// a frame of one of the four entries and its stages in the order run() goes through them; each optional stage is entered only with its feature
+struct TrackFrame {
+  // what the caller gave.  record: the entry takes rp and rec (there once check() has passed); mo, rc: NULL in an entry without them
+  std::string who; mcp_map_points* m; int ncam; mcp_kf* const* targets; const uint8_t* const* imgs; const int* strides; int imgs_on_device;
+  const uint8_t* const* const* masks; const mcp_camera* cams; double* bfw; const double* cfb; const mcp_track_map_params* prm; mcp_track_map_result* res;
+  bool record; const mcp_track_record_params* rp; mcp_track_record* rec; const MotionArg* mo; const RecoverArg* rc;
+  // what the call derives once (derive(); cand_live: recover_check's; D, the device's parameter block: reserve()'s)
+  hipStream_t st; int n, ncand; size_t NB, n_coarse_max, n_tile, nslot; bool coarse, regs, cov, want_items; PvsLayout Y; TmBlockLayout L; TmParams P; TmCtl* ctl;
+  std::vector<uint8_t> cand_live; TmBlock D;
+  // what pack() leaves for the SBI kernels
+  RelocMakeArgs rma; RelocCurArgs rca; FrameSbiArgs fa; MotionFirst mfirst;
+
+  // every refusal, in the order the entries answer; nothing is enqueued and nothing changes before all of them pass
+  int check() {
+    if (!m) return img_fail(who + ": NULL table");
+    if (record && (!rp || !rec)) return img_fail(who + ": NULL record parameters or record");
+    if (record && (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad))) return img_fail(who + ": a quality threshold is not finite");
+    if (mo && (!mo->p || !mo->out)) return img_fail(who + ": NULL motion parameters or motion result");
+    if (rc && (!rc->p || !rc->out)) return img_fail(who + ": NULL recover parameters or recover result");
+    if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !prm || !res || (imgs && !strides)) return img_fail(who + ": bad arguments");
+    if (prm->coarse_max < 0 || prm->coarse_range < 0 || prm->coarse_min < 0 || prm->coarse_subpix_its < 0 || prm->max_patches < 0) return img_fail(who + ": negative cap, range or iteration count");
+    if (!est_ok(prm->estimator)) return img_fail(who + ": unknown M-estimator");
+    for (int c = 0; c < ncam; ++c) {
+      if (!targets[c] || !cam_ok(&cams[c]) || (imgs && !imgs[c])) return img_fail(who + ": bad arguments for camera " + std::to_string(c));
+      if (target_on_table_device(who, m, c, targets[c])) return -1;
+      for (int d = 0; imgs && d < c; ++d) if (targets[d] == targets[c]) return img_fail(who + ": a keyframe appears twice in a frame with images");
+      if (mo && !imgs && !targets[c]->has_image) return img_fail(who + ": camera " + std::to_string(c) + "'s target holds no frame and no images were given");
+    }
+    if (mo && motion_check(who, ncam, mo->cams_sbi, mo->p, mo->out)) return -1;
+    return rc ? recover_check(who, m, ncam, targets, mo->p, *rc, cand_live) : 0;
   }
-  // (param block: cameras' search table | camera models | CamFromBase | BaseFromWorld + mu | override sigma x 2 | nonlinear flags x 2)
-  const size_t o_tab = 0, o_cam = tm_align(sizeof(TmCam)*(size_t)ncam), o_cfb = o_cam + tm_align(sizeof(mcp_camera)*(size_t)ncam), o_pm = o_cfb + tm_align(96*(size_t)ncam);
-  const size_t o_ov = o_pm + tm_align(18*8), o_nl = o_ov + tm_align(20*8), o_cs = o_nl + tm_align(20);      // (| the SBI cameras, with a motion model)
-  const size_t o_rc = o_cs + (mo ? tm_align(sizeof(mcp_camera)*(size_t)ncam) : 0);                            // (| the candidate list, on a recovery frame)
-  const size_t blk = o_rc + (rc ? tm_align(sizeof(RelocCand)*(size_t)std::max(ncand, 1)) : 0);
-  if (m->tm.blk.alloc(blk) || m->tm.h_blk.alloc(blk)) return -1;
-  if (mo && m->mo.reserve()) return -1;
-  if (rc) {
-    if (m->rc.reserve(ncand, rc->scores != nullptr)) return -1;
-    for (int c = 0; c < ncam; ++c) {      // both SBIs of every target handle, so that the roll below is a pointer swap
+  void derive() {
+    st = m->st; n = m->rows; ncand = rc ? rc->ncand : 0; nslot = std::max<size_t>(m->slots.size(), 1);
+    want_items = !rp || rp->want_items != 0;
+    NB = (size_t)ncam*std::max(n, 1);                                // bound of every per-item array: a camera's sets are distinct rows
+    coarse = prm->try_coarse && prm->coarse_max > 0; n_coarse_max = coarse ? std::min(NB, (size_t)ncam*prm->coarse_max) : 0;
+    n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK; regs = tm_regs_ok();
+    cov = m->cv.on;                                                  // mcp_track_pose_cov_enable: two launches behind the fine iterations
+    pvs_layout(ncam, nullptr, n, &Y);                                // caps = rows: camera c's list at c * rows
+    L = tm_block_layout(ncam, mo != nullptr, rc != nullptr, ncand);
+    P.ncam = ncam; P.rows = n; P.try_coarse = prm->try_coarse ? 1 : 0; P.coarse_max = prm->coarse_max; P.coarse_range = prm->coarse_range;
+    P.coarse_subpix_its = prm->coarse_subpix_its; P.coarse_min = prm->coarse_min; P.max_patches = prm->max_patches; P.seed = prm->seed;
+  }
+  // every allocation, before the first enqueue
+  int reserve() {
+    if (m->ensure_states(ncam)) return -1;
+    if (m->tm.pvs.alloc(NB) || m->tm.counts.alloc((size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS) || m->tm.sel.alloc(NB) || m->tm.k0.alloc(NB) || m->tm.k1.alloc(NB) || m->tm.live.alloc(NB) ||
+        m->tm.ctl.alloc(1) || m->tm.slots.alloc(nslot) || m->tm.h_slots.alloc(nslot) || m->tm.crec.alloc(std::max<size_t>(n_coarse_max, 1)) || m->tm.frec.alloc(NB) || m->tm.w.alloc(NB) ||
+        m->tm.items.alloc(NB) || (want_items && m->tm.h_items.alloc(NB)) || m->tm.h_res.alloc(1) || m->pvs.reserve(ncam, n)) return -1;
+    if ((NB > (size_t)PRR_THREADS*PRR_PPT || !regs) && (m->tm.J.alloc(12*NB) || m->tm.ex.alloc(2*NB) || m->tm.e2.alloc(NB))) return -1;
+    if (m->tm.blk.alloc(L.total) || m->tm.h_blk.alloc(L.total)) return -1;
+    D = L.at(m->tm.blk.p); ctl = m->tm.ctl.p;
+    if (mo && m->mo.reserve()) return -1;
+    if (rc && m->rc.reserve(ncand, rc->scores != nullptr)) return -1;
+    for (int c = 0; rc && c < ncam; ++c) {      // both SBIs of every target handle, so that the roll in pack_recover() is a pointer swap
       mcp_kf* k = targets[c];
       if (k->sbi_small.alloc(SBI_N) || k->sbi_templ.alloc(SBI_N) || k->sbi_jacs.alloc(2*SBI_N) || k->sbi_last_small.alloc(SBI_N) || k->sbi_last_templ.alloc(SBI_N) ||
           k->sbi_last_jacs.alloc(2*SBI_N)) return -1;
     }
+    if (cov && m->cv.reserve(NB)) return -1;
+    if (cov) std::memset(m->cv.h_out.p, 0, sizeof(mcp_track_pose_cov_record));        // (valid = 0 unless k_pose_cov_finish runs)
+    if (rp) {
+      if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
+          m->tr.seg_start.alloc(MCP_MAX_FRAME_CAMS + 1) || m->tr.seg_rows.alloc(NB) || m->tr.seg_w.alloc(NB) || m->tr.cfw.alloc(12*MCP_MAX_FRAME_CAMS) || m->wb.depth.alloc(NB)) return -1;
+      std::memset(m->tr.h_rec.p, 0, sizeof(mcp_track_record));          // (the cameras past ncam read as zeros)
+    }
+    return 0;
   }
-  const bool cov = m->cv.on;                                         // mcp_track_pose_cov_enable: two launches behind the fine iterations
-  if (cov) {
-    if (m->cv.reserve(NB)) return -1;
-    std::memset(m->cv.h_out.p, 0, sizeof(mcp_track_pose_cov_record));        // (valid = 0 unless k_pose_cov_finish runs)
-  }
-  const size_t n_tile = (NB + TR_BLOCK - 1)/TR_BLOCK;
-  if (rp) {
-    if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
-        m->tr.seg_start.alloc(MCP_MAX_FRAME_CAMS + 1) || m->tr.seg_rows.alloc(NB) || m->tr.seg_w.alloc(NB) || m->tr.cfw.alloc(12*MCP_MAX_FRAME_CAMS) || m->wb.depth.alloc(NB)) return -1;
-    std::memset(m->tr.h_rec.p, 0, sizeof(mcp_track_record));          // (the cameras past ncam read as zeros)
-  }
-  mcp_kf* k0 = targets[0];
-  Drain drain{m, true, true, ncam, imgs ? targets : nullptr};
-  if (imgs) {
-    if (lite_batch_enqueue(ncam, targets, imgs, strides, imgs_on_device, masks)) return -1;
-    ICK(hipEventRecord(k0->ev, k0->st));
-    ICK(hipStreamWaitEvent(m->st, k0->ev, 0));
-  }
-  // the tables are built after the pyramids' launch: it rotates the level images of the targets
-  uint8_t* hb = m->tm.h_blk.p;
-  std::memset(hb, 0, blk);
-  TmCam* tab = reinterpret_cast<TmCam*>(hb + o_tab);
-  for (int c = 0; c < ncam; ++c) {
-    target_of(tab[c], targets[c], cams[c]); tab[c].cfb = se3_of12(cfb + 12*c);
-  }
-  std::memcpy(hb + o_cam, cams, sizeof(mcp_camera)*(size_t)ncam);
-  std::memcpy(hb + o_cfb, cfb, 96*(size_t)ncam);
-  std::memcpy(hb + o_pm, bfw, 96);
-  if (mo) std::memcpy(hb + o_cs, mo->cams_sbi, sizeof(mcp_camera)*(size_t)ncam);
-  RelocMakeArgs rma; RelocCurArgs rca;
-  if (rc) {
-    // the relocaliser's SBI of every camera goes into the target handle's own (mcp_kf_make_sbi's roll: the one before becomes `last`), in
-    // camera order
+  // a recovery frame's packing: the relocaliser's SBI of every camera goes into the target handle's own (mcp_kf_make_sbi's roll: the one
+  // before becomes `last`), in camera order; the candidates into the block
+  void pack_recover(RelocCand* cd) {
     std::memset(&rma, 0, sizeof rma); std::memset(&rca, 0, sizeof rca);
     for (int c = 0; c < ncam; ++c) {
       mcp_kf* k = targets[c];
@@ -1783,216 +1787,228 @@ static int track_map_run(const std::string& who, mcp_map_points* m, int ncam, mc
       rma.c[c] = RelocMakeCam{L0.img.p, L0.w, L0.h, k->sbi_small.p, k->sbi_templ.p, k->sbi_jacs.p};
       rca.templ[c] = k->sbi_templ.p;
     }
-    RelocCand* cd = reinterpret_cast<RelocCand*>(hb + o_rc);
     for (int i = 0; i < ncand; ++i) {
       cd[i].templ = cand_live[i] ? rc->kf[i]->sbi_templ.p : nullptr; cd[i].jacs = cand_live[i] ? rc->kf[i]->sbi_jacs.p : nullptr;
       cd[i].cam = rc->cam[i]; cd[i].pad = 0;
       std::memcpy(cd[i].cfw, rc->cfw + 12*(size_t)i, 96);
     }
   }
-  double* ov = reinterpret_cast<double*>(hb + o_ov); uint8_t* nl = hb + o_nl;
-  for (int i = 0; i < 10; ++i) {
-    ov[i] = i < 6 ? 0.0 : 1.0; nl[i] = 1;                                                 // coarse, Tracker.cc:1012-1020
-    ov[10 + i] = i < 6 ? 0.0 : 16.0; nl[10 + i] = (i == 0 || i == 4 || i == 9) ? 1 : 0;   // fine, :1063-1075
+  // a motion frame's: this frame's SBI set of every camera index (the one before becomes last frame's)
+  void pack_motion() {
+    mcp_map_points::Mo& M = m->mo;
+    std::memset(&fa, 0, sizeof fa); std::memset(&mfirst, 0, sizeof mfirst);
+    for (int c = 0; c < ncam; ++c) {
+      const Level& L0 = targets[c]->lev[0];
+      mfirst.v[c] = M.have[c] ? 0 : 1;
+      if (M.have[c]) M.cur[c] ^= 1;
+      M.have[c] = true;
+      FrameSbiCam& F = fa.c[c];
+      F.img = L0.img.p; F.w = L0.w; F.h = L0.h; F.first = mfirst.v[c]; F.align = motion_cam_used(*mo->p, c) ? 1 : 0;
+      F.cur = M.sets.p + 2*c + M.cur[c]; F.last = M.sets.p + 2*c + (M.cur[c] ^ 1);
+    }
   }
-  const size_t nslot = std::max<size_t>(m->slots.size(), 1);
-  std::memset(m->tm.h_slots.p, 0, sizeof(TmSlot)*nslot);
-  fill_slots(m, m->tm.h_slots.p);
-  hipStream_t st = m->st;
-  ICK(hipMemcpyAsync(m->tm.blk.p, hb, blk, hipMemcpyHostToDevice, st));
-  ICK(hipMemcpyAsync(m->tm.slots.p, m->tm.h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
-  double* d_pm = reinterpret_cast<double*>(m->tm.blk.p + o_pm);
-  const double* d_cfb = reinterpret_cast<const double*>(m->tm.blk.p + o_cfb);
-  if (rc) {
-    // 0a. the relocaliser: every camera's SBI, the candidates' scores, the winner's alignment and pose per camera, the recovered pose into
-    // the pose slot and the gate word
+  // the host's parameter block and the slots, with the two changes of state that go with them (the targets' SBI roll, Mo::cur / Mo::have):
+  // after the pyramids' launch, which rotates the level images the tables point at, and before the uploads
+  void pack() {
+    std::memset(m->tm.h_blk.p, 0, L.total);
+    const TmBlock H = L.at(m->tm.h_blk.p);
+    for (int c = 0; c < ncam; ++c) { target_of(H.tab[c], targets[c], cams[c]); H.tab[c].cfb = se3_of12(cfb + 12*c); }
+    std::memcpy(H.cams, cams, sizeof(mcp_camera)*(size_t)ncam);
+    std::memcpy(H.cfb, cfb, 96*(size_t)ncam); std::memcpy(H.pm, bfw, 96);
+    if (mo) std::memcpy(H.cams_sbi, mo->cams_sbi, sizeof(mcp_camera)*(size_t)ncam);
+    if (rc) pack_recover(H.cand);
+    for (int i = 0; i < 10; ++i) {
+      H.ov[i] = i < 6 ? 0.0 : 1.0; H.nl[i] = 1;                                                 // coarse, Tracker.cc:1012-1020
+      H.ov[10 + i] = i < 6 ? 0.0 : 16.0; H.nl[10 + i] = (i == 0 || i == 4 || i == 9) ? 1 : 0;   // fine, :1063-1075
+    }
+    std::memset(m->tm.h_slots.p, 0, sizeof(TmSlot)*nslot);
+    fill_slots(m, m->tm.h_slots.p);
+    if (mo) pack_motion();
+  }
+  // the relocaliser: every camera's SBI, the candidates' scores, the winner's alignment and pose per camera, the recovered pose into the pose
+  // slot (k_motion_prior reads it as the start) and the word that gates the PVS
+  int reloc_enqueue() {
     mcp_map_points::Rc& R = m->rc;
     const mcp_track_recover_params& q = *rc->p;
     std::vector<SbiTables> tabs(ncam);
     for (int c = 0; c < ncam; ++c) sbi_tables(rma.c[c].w, rma.c[c].h, q.reloc_blur, tabs[c]);
-    if (R.tabs_last.size() != tabs.size() || std::memcmp(R.tabs_last.data(), tabs.data(), sizeof(SbiTables)*tabs.size()) != 0) {
-      std::memcpy(R.h_tabs.p, tabs.data(), sizeof(SbiTables)*tabs.size());
-      ICK(hipMemcpyAsync(R.d_tabs.p, R.h_tabs.p, sizeof(SbiTables)*tabs.size(), hipMemcpyHostToDevice, st));
-      R.tabs_last = tabs;
-    }
+    if (upload_when_changed(R.tabs_last, R.h_tabs, R.d_tabs, tabs, st)) return -1;
     std::memset(R.h_out.p, 0, sizeof(mcp_track_recover));
-    const RelocCand* d_cand = reinterpret_cast<const RelocCand*>(m->tm.blk.p + o_rc);
     hipLaunchKernelGGL(k_reloc_make, dim3(ncam), dim3(256), 0, st, rma, (const SbiTables*)R.d_tabs.p);
-    if (ncand > 0) hipLaunchKernelGGL(k_reloc_score, dim3((ncand + RELOC_TILE - 1)/RELOC_TILE), dim3(RELOC_TILE), 0, st, ncand, ncam, d_cand, rca, R.scores.p,
+    if (ncand > 0) hipLaunchKernelGGL(k_reloc_score, dim3((ncand + RELOC_TILE - 1)/RELOC_TILE), dim3(RELOC_TILE), 0, st, ncand, ncam, (const RelocCand*)D.cand, rca, R.scores.p,
                                       rc->scores ? R.h_scores.p : (double*)nullptr);
-    hipLaunchKernelGGL(k_reloc_align, dim3(ncam), dim3(256), 0, st, ncand, d_cand, (const double*)R.scores.p, rca, reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cs),
-                       q.reloc_iterations, R.cam_out.p);
-    hipLaunchKernelGGL(k_reloc_pick, dim3(1), dim3(64), 0, st, ncam, (const RelocCamOut*)R.cam_out.p, d_cfb, q.max_score, d_pm, R.gate.p, R.h_out.p);
+    hipLaunchKernelGGL(k_reloc_align, dim3(ncam), dim3(256), 0, st, ncand, (const RelocCand*)D.cand, (const double*)R.scores.p, rca, (const mcp_camera*)D.cams_sbi, q.reloc_iterations, R.cam_out.p);
+    hipLaunchKernelGGL(k_reloc_pick, dim3(1), dim3(64), 0, st, ncam, (const RelocCamOut*)R.cam_out.p, (const double*)D.cfb, q.max_score, D.pm, R.gate.p, R.h_out.p);
     ICK(hipGetLastError());
+    return 0;
   }
-  if (mo) {
-    // 0. the motion model: this frame's SBI of every camera (the one before becomes last frame's), its alignment, the prior into the pose slot
+  // the motion model, in front of the PVS (which then reads the pose from the block): this frame's SBI of every camera, its alignment against
+  // last frame's, the prior into the pose slot
+  int motion_prior_enqueue() {
     mcp_map_points::Mo& M = m->mo;
-    const mcp_track_motion_params& mp = *mo->p;
     std::vector<SbiTables> tabs(ncam);
-    FrameSbiArgs fa; std::memset(&fa, 0, sizeof fa);
-    MotionFirst first; std::memset(&first, 0, sizeof first);
-    for (int c = 0; c < ncam; ++c) {
-      const Level& L0 = targets[c]->lev[0];
-      sbi_tables(L0.w, L0.h, mp.blur, tabs[c]);
-      first.v[c] = M.have[c] ? 0 : 1;
-      if (M.have[c]) M.cur[c] ^= 1;
-      M.have[c] = true;
-      FrameSbiCam& F = fa.c[c];
-      F.img = L0.img.p; F.w = L0.w; F.h = L0.h; F.first = first.v[c]; F.align = motion_cam_used(mp, c) ? 1 : 0;
-      F.cur = M.sets.p + 2*c + M.cur[c]; F.last = M.sets.p + 2*c + (M.cur[c] ^ 1);
-    }
-    if (M.tabs_last.size() != tabs.size() || std::memcmp(M.tabs_last.data(), tabs.data(), sizeof(SbiTables)*tabs.size()) != 0) {
-      std::memcpy(M.h_tabs.p, tabs.data(), sizeof(SbiTables)*tabs.size());
-      ICK(hipMemcpyAsync(M.d_tabs.p, M.h_tabs.p, sizeof(SbiTables)*tabs.size(), hipMemcpyHostToDevice, st));
-      M.tabs_last = tabs;
-    }
+    for (int c = 0; c < ncam; ++c) sbi_tables(fa.c[c].w, fa.c[c].h, mo->p->blur, tabs[c]);
+    if (upload_when_changed(M.tabs_last, M.h_tabs, M.d_tabs, tabs, st)) return -1;
     std::memset(M.h_out.p, 0, sizeof(mcp_track_motion));
-    hipLaunchKernelGGL(k_frame_sbi, dim3(ncam), dim3(256), 0, st, fa, (const SbiTables*)M.d_tabs.p, mp.sbi_iterations, M.se2.p);
-    hipLaunchKernelGGL(k_motion_prior, dim3(1), dim3(64), 0, st, ncam, (const double*)M.se2.p, first, reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cs), d_cfb, d_pm, mp, M.h_out.p);
+    hipLaunchKernelGGL(k_frame_sbi, dim3(ncam), dim3(256), 0, st, fa, (const SbiTables*)M.d_tabs.p, mo->p->sbi_iterations, M.se2.p);
+    hipLaunchKernelGGL(k_motion_prior, dim3(1), dim3(64), 0, st, ncam, (const double*)M.se2.p, mfirst, (const mcp_camera*)D.cams_sbi, (const double*)D.cfb, D.pm, *mo->p, M.h_out.p);
     ICK(hipGetLastError());
+    return 0;
   }
-  // 1. FindPVS, lists and counts in device memory (caps = rows; camera c's list at c * rows)
-  PvsLayout Y;
-  pvs_layout(ncam, nullptr, n, &Y);
-  if (n > 0) {
-    if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? d_pm : nullptr, rc ? m->rc.gate.p : nullptr)) return -1;
-  } else ICK(hipMemsetAsync(m->tm.counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
-  // 2. the sets
-  TmParams P; P.ncam = ncam; P.rows = n; P.try_coarse = prm->try_coarse ? 1 : 0; P.coarse_max = prm->coarse_max; P.coarse_range = prm->coarse_range;
-  P.coarse_subpix_its = prm->coarse_subpix_its; P.coarse_min = prm->coarse_min; P.max_patches = prm->max_patches; P.seed = prm->seed;
-  hipLaunchKernelGGL(k_tm_select, dim3(ncam), dim3(TM_SEL_NT), 0, st, P, (const mcp_pvs_entry*)m->tm.pvs.p, (const int*)m->tm.counts.p, m->src.row(),
-                     (const TmSlot*)m->tm.slots.p, m->tm.k0.p, m->tm.k1.p, m->tm.live.p, m->tm.sel.p, m->tm.ctl.p);
-  const TmCam* d_tab = reinterpret_cast<const TmCam*>(m->tm.blk.p + o_tab);
-  const mcp_camera* d_cams = reinterpret_cast<const mcp_camera*>(m->tm.blk.p + o_cam);
-  const double* d_ov = reinterpret_cast<const double*>(m->tm.blk.p + o_ov);
-  const uint8_t* d_nl = m->tm.blk.p + o_nl;
-  TmCtl* ctl = m->tm.ctl.p;
-  auto iterate = [&](size_t bound, const int* n_dev, const int* gate, mcp_pose_point* recs, int stage) -> int {
-    const double* o = d_ov + 10*stage; const uint8_t* f = d_nl + 10*stage;
-    if (regs) hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, d_pm + 12, m->tm.w.p, prm->estimator, ncam, n_dev, gate);
+  // FindPVS, lists and counts in device memory (on a recovery frame behind the relocaliser's gate), and the sets
+  int pvs_sets_enqueue() {
+    if (n > 0) {
+      if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? D.pm : nullptr, rc ? m->rc.gate.p : nullptr)) return -1;
+    } else ICK(hipMemsetAsync(m->tm.counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
+    hipLaunchKernelGGL(k_tm_select, dim3(ncam), dim3(TM_SEL_NT), 0, st, P, (const mcp_pvs_entry*)m->tm.pvs.p, (const int*)m->tm.counts.p, m->src.row(),
+                       (const TmSlot*)m->tm.slots.p, m->tm.k0.p, m->tm.k1.p, m->tm.live.p, m->tm.sel.p, ctl);
+    return 0;
+  }
+  // the searches of a round (stage 0: coarse, 1: fine) at the pose in the block
+  void search_enqueue(int stage, size_t bound, unsigned max_grid) {
+    hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(bound, max_grid)), dim3(64), 0, st, P, stage, (const TmCam*)D.tab, (const double*)D.pm, m->pts.row(),
+                       m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
+  }
+  // its ten pose iterations over at most `bound` records
+  int iterate_enqueue(int stage, size_t bound, const int* n_dev, const int* gate, mcp_pose_point* recs) {
+    const double* o = D.ov + 10*stage; const uint8_t* f = D.nl + 10*stage; const mcp_camera* d_cams = D.cams; const double* d_cfb = D.cfb;
+    if (regs) hipLaunchKernelGGL(k_pose_refine_regs, dim3(1), dim3(PRR_THREADS), PRR_DYN_LDS, st, 0, recs, d_cams, d_cfb, D.pm, 10, f, o, D.pm + 12, m->tm.w.p, prm->estimator, ncam, n_dev, gate);
     if (!regs || bound > (size_t)PRR_THREADS*PRR_PPT)      // (more records than the register-resident kernel holds, or no such kernel)
-      hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, 0, recs, d_cams, d_cfb, d_pm, 10, f, o, m->tm.J.p, m->tm.ex.p, m->tm.e2.p, d_pm + 12, m->tm.w.p,
+      hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, 0, recs, d_cams, d_cfb, D.pm, 10, f, o, m->tm.J.p, m->tm.ex.p, m->tm.e2.p, D.pm + 12, m->tm.w.p,
                          prm->estimator, n_dev, gate, regs ? PRR_THREADS*PRR_PPT : -1);
     ICK(hipGetLastError());
     return 0;
-  };
-  // 3-5. coarse search, the gate, the coarse iterations
-  if (coarse)
-    hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(n_coarse_max, 8192)), dim3(64), 0, st, P, 0, d_tab, (const double*)d_pm, m->pts.row(),
-                       m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
-  hipLaunchKernelGGL(k_tm_gate, dim3(1), dim3(1), 0, st, P, ctl);
-  if (coarse && iterate(n_coarse_max, &ctl->n_coarse, &ctl->did_coarse, m->tm.crec.p, 0)) return -1;
-  // 6-7. fine searches at the current pose, the fine iterations over [C_c, T_c, R_c]
-  hipLaunchKernelGGL(k_tm_search, dim3((unsigned)std::min<size_t>(NB, 16384)), dim3(64), 0, st, P, 1, d_tab, (const double*)d_pm, m->pts.row(),
-                     m->src.row(), (const TmSlot*)m->tm.slots.p, (const int*)m->tm.sel.p, m->state_ptrs(), ctl, m->tm.items.p, m->tm.crec.p, m->tm.frec.p, m->tm.w.p);
-  if (iterate(NB, &ctl->n_fine, nullptr, m->tm.frec.p, 1)) return -1;
-  if (cov && pose_cov_enqueue(st, 0, &ctl->n_fine, rc ? m->rc.gate.p : nullptr, NB, m->tm.frec.p, m->tm.w.p, d_cfb, d_pm, d_pm + 12, 0, m->cv.part.p, m->cv.used.p,
-                              m->cv.h_out.p)) return -1;
-  if (mo) {      // UpdateMotionModel, from the refined pose
-    Pose12 start; std::memcpy(start.v, bfw, 96);
-    hipLaunchKernelGGL(k_motion_update, dim3(1), dim3(64), 0, st, (const double*)d_pm, start, *mo->p, m->mo.h_out.p);
   }
-  if (rp) {
-    // the bookkeeping, from the items, the last weights and the refined pose where the iterations left them
+  // coarse search, the gate, the coarse iterations
+  int coarse_enqueue() {
+    if (coarse) search_enqueue(0, n_coarse_max, 8192);
+    hipLaunchKernelGGL(k_tm_gate, dim3(1), dim3(1), 0, st, P, ctl);
+    return coarse ? iterate_enqueue(0, n_coarse_max, &ctl->n_coarse, &ctl->did_coarse, m->tm.crec.p) : 0;
+  }
+  // fine searches at the current pose, the fine iterations over [C_c, T_c, R_c]
+  int fine_enqueue() {
+    search_enqueue(1, NB, 16384);
+    return iterate_enqueue(1, NB, &ctl->n_fine, nullptr, m->tm.frec.p);
+  }
+  int cov_enqueue() {      // mm6PoseCovariance of the last fine iteration
+    return pose_cov_enqueue(st, 0, &ctl->n_fine, rc ? m->rc.gate.p : nullptr, NB, m->tm.frec.p, m->tm.w.p, D.cfb, D.pm, D.pm + 12, 0, m->cv.part.p, m->cv.used.p, m->cv.h_out.p);
+  }
+  void motion_update_enqueue() {      // UpdateMotionModel, from the refined pose
+    Pose12 start; std::memcpy(start.v, bfw, 96);
+    hipLaunchKernelGGL(k_motion_update, dim3(1), dim3(64), 0, st, (const double*)D.pm, start, *mo->p, m->mo.h_out.p);
+  }
+  // the bookkeeping, from the items, the last weights and the refined pose where the iterations left them
+  int record_enqueue() {
     TrParams Q; Q.ncam = ncam; Q.lost = rp->lost ? 1 : 0; Q.min_patches = rp->min_patches; Q.coarse_min = rp->coarse_min; Q.good = rp->quality_good; Q.bad = rp->quality_bad;
     const unsigned grid = (unsigned)std::min<size_t>(n_tile, 2048);
     ICK(hipMemsetAsync(m->tr.acc.p, 0, sizeof(TrAcc), st));
-    hipLaunchKernelGGL(k_tr_mark, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, d_tab, (const double*)d_pm, (const mcp_track_map_item*)m->tm.items.p, (const double*)m->tm.w.p,
+    hipLaunchKernelGGL(k_tr_mark, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, (const TmCam*)D.tab, (const double*)D.pm, (const mcp_track_map_item*)m->tm.items.p, (const double*)m->tm.w.p,
                        m->cnt.row(), m->tr.h_notes.p, m->tr.flags.p, m->tr.tile.p, m->tr.acc.p, m->tr.cfw.p, &m->tr.h_rec.p->cam_from_world[0][0]);
     hipLaunchKernelGGL(k_tr_scatter, dim3(grid), dim3(TR_BLOCK), 0, st, Q, (const TmCtl*)ctl, (const mcp_track_map_item*)m->tm.items.p, (const uint8_t*)m->tr.flags.p,
                        (const int*)m->tr.tile.p, (const TrAcc*)m->tr.acc.p, m->cnt.row(), m->tr.h_meas.p, m->tr.seg_start.p, m->tr.seg_rows.p, m->tr.seg_w.p, m->tr.h_rec.p);
     hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)ncam), dim3(SD_BLOCK), 0, st, (const double*)m->tr.cfw.p, (const int*)nullptr, (const int*)m->tr.seg_start.p,
                        (const int*)m->tr.seg_rows.p, (const double*)m->tr.seg_w.p, m->pts.row(), m->wb.depth.p, &m->tr.h_rec.p->depth[0], (double*)nullptr);
     ICK(hipGetLastError());
+    return 0;
   }
-  if (!want_items) hipLaunchKernelGGL(k_tr_finish, dim3(1), dim3(64), 0, st, P, (const TmCtl*)ctl, (const double*)d_pm, (const int*)m->tm.counts.p, m->tm.h_res.p);
-  else hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm.w.p,
-                     (const mcp_track_map_item*)m->tm.items.p, m->tm.h_items.p,
-                     (const double*)d_pm, (const int*)m->tm.counts.p, m->tm.h_res.p);
-  ICK(hipGetLastError());
-  ICK(m->sync());
-  drain.armed = false;
-  if (imgs && lite_batch_finish(ncam, targets)) return -1;
-  const TmOut& R = *m->tm.h_res.p;
-  std::memset(res, 0, sizeof *res);
-  res->did_coarse = R.ctl.did_coarse; res->coarse_found = R.ctl.coarse_found;
-  int first = 0;
-  for (int c = 0; c < ncam; ++c) {
-    int off = Y.first[c];
-    for (int l = 0; l < MCP_LEVELS; ++l) {
-      res->pvs_counts[c][l] = R.counts[c][l];
-      m->pvs.first[c][l] = off; m->pvs.count[c][l] = R.counts[c][l]; off += R.counts[c][l];
+  void finish_enqueue() {      // the results into the pinned block, with the items where the caller wants them
+    if (!want_items) hipLaunchKernelGGL(k_tr_finish, dim3(1), dim3(64), 0, st, P, (const TmCtl*)ctl, (const double*)D.pm, (const int*)m->tm.counts.p, m->tm.h_res.p);
+    else hipLaunchKernelGGL(k_tm_finish, dim3((unsigned)std::min<size_t>((NB*(sizeof(mcp_track_map_item)/8) + 255)/256, 1024)), dim3(256), 0, st, P, (const TmCtl*)ctl, (const double*)m->tm.w.p,
+                            (const mcp_track_map_item*)m->tm.items.p, m->tm.h_items.p, (const double*)D.pm, (const int*)m->tm.counts.p, m->tm.h_res.p);
+  }
+  // what the synchronised stream left in pinned memory, into the caller's structs and the views' bookkeeping; bfw is written last
+  int collect() {
+    const TmOut& R = *m->tm.h_res.p;
+    std::memset(res, 0, sizeof *res);
+    res->did_coarse = R.ctl.did_coarse; res->coarse_found = R.ctl.coarse_found;
+    int first = 0;
+    for (int c = 0; c < ncam; ++c) {
+      int off = Y.first[c];
+      for (int l = 0; l < MCP_LEVELS; ++l) {
+        res->pvs_counts[c][l] = R.counts[c][l];
+        m->pvs.first[c][l] = off; m->pvs.count[c][l] = R.counts[c][l]; off += R.counts[c][l];
+      }
+      m->pvs.ok[c] = true;
+      for (int q = 0; q < 3; ++q) res->set_sizes[c][q] = R.ctl.sizes[c][q];
+      res->stale[c] = R.ctl.stale[c];
+      m->tm.first[c] = first; first += R.ctl.sizes[c][0] + R.ctl.sizes[c][1] + R.ctl.sizes[c][2];
     }
-    m->pvs.ok[c] = true;
-    for (int q = 0; q < 3; ++q) res->set_sizes[c][q] = R.ctl.sizes[c][q];
-    res->stale[c] = R.ctl.stale[c];
-    m->tm.first[c] = first; first += R.ctl.sizes[c][0] + R.ctl.sizes[c][1] + R.ctl.sizes[c][2];
-  }
-  m->tm.first[ncam] = first; m->tm.ncam = ncam; m->tm.items_ok = want_items;
-  if (rp) {
-    *rec = *m->tr.h_rec.p;
-    m->tr.meas_first[0] = 0;
-    for (int c = 0; c < ncam; ++c) m->tr.meas_first[c + 1] = m->tr.meas_first[c] + rec->n_meas[c];
-    m->tr.ncam = ncam; m->tr.ok = true;
-  }
-  m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
-  std::memcpy(res->mu_last, R.mu, 48);
-  m->cv.ok = cov; m->cv.fine_ok = true; m->cv.n_fine = R.ctl.n_fine; std::memcpy(m->cv.mu, R.mu, 48);
-  if (mo) *mo->out = *m->mo.h_out.p;
-  if (rc) {
-    *rc->out = *m->rc.h_out.p;
-    if (rc->scores && ncand > 0) std::memcpy(rc->scores, m->rc.h_scores.p, sizeof(double)*(size_t)ncand);
-    if (rc->out->recovered) std::memset(mo->out->velocity, 0, sizeof mo->out->velocity);      // mv6BaseVelocity = Zeros, Tracker.cc:549
-    else {      // no TrackMap ran: the pose as given (bfw has not been written yet), no bookkeeping
-      std::memset(rec, 0, sizeof *rec);
-      return 0;
+    m->tm.first[ncam] = first; m->tm.ncam = ncam; m->tm.items_ok = want_items;
+    if (rp) {
+      *rec = *m->tr.h_rec.p;
+      m->tr.meas_first[0] = 0;
+      for (int c = 0; c < ncam; ++c) m->tr.meas_first[c + 1] = m->tr.meas_first[c] + rec->n_meas[c];
+      m->tr.ncam = ncam; m->tr.ok = true;
     }
+    m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
+    std::memcpy(res->mu_last, R.mu, 48);
+    m->cv.ok = cov; m->cv.fine_ok = true; m->cv.n_fine = R.ctl.n_fine; std::memcpy(m->cv.mu, R.mu, 48);
+    if (mo) *mo->out = *m->mo.h_out.p;
+    if (rc) {
+      *rc->out = *m->rc.h_out.p;
+      if (rc->scores && ncand > 0) std::memcpy(rc->scores, m->rc.h_scores.p, sizeof(double)*(size_t)ncand);
+      if (rc->out->recovered) std::memset(mo->out->velocity, 0, sizeof mo->out->velocity);      // mv6BaseVelocity = Zeros, Tracker.cc:549
+      else { std::memset(rec, 0, sizeof *rec); return 0; }      // no TrackMap ran: the pose as given, no bookkeeping
+    }
+    std::memcpy(bfw, R.pose, 96);
+    return 0;
   }
-  std::memcpy(bfw, R.pose, 96);
-  return 0;
-}
+  int run() {
+    if (check()) return -1;
+    ICK(hipSetDevice(m->device));
+    // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
+    m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate(); m->cv.invalidate();
+    derive();
+    if (reserve()) return -1;
+    Drain drain{m, true, true, ncam, imgs ? targets : nullptr};
+    if (imgs) {
+      if (lite_batch_enqueue(ncam, targets, imgs, strides, imgs_on_device, masks)) return -1;
+      ICK(hipEventRecord(targets[0]->ev, targets[0]->st));
+      ICK(hipStreamWaitEvent(st, targets[0]->ev, 0));
+    }
+    pack();
+    ICK(hipMemcpyAsync(m->tm.blk.p, m->tm.h_blk.p, L.total, hipMemcpyHostToDevice, st));
+    ICK(hipMemcpyAsync(m->tm.slots.p, m->tm.h_slots.p, sizeof(TmSlot)*nslot, hipMemcpyHostToDevice, st));
+    if (rc && reloc_enqueue()) return -1;
+    if (mo && motion_prior_enqueue()) return -1;
+    if (pvs_sets_enqueue() || coarse_enqueue() || fine_enqueue()) return -1;
+    if (cov && cov_enqueue()) return -1;
+    if (mo) motion_update_enqueue();
+    if (rp && record_enqueue()) return -1;
+    finish_enqueue();
+    ICK(hipGetLastError());
+    ICK(m->sync());
+    drain.armed = false;
+    if (imgs && lite_batch_finish(ncam, targets)) return -1;
+    return collect();
+  }
+};
 
 int mcp_track_map(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                   const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
                   mcp_track_map_result* res) {
-  return track_map_run("mcp_track_map", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, nullptr, nullptr);
+  return TrackFrame{"mcp_track_map", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, false, nullptr, nullptr, nullptr, nullptr}.run();
 }
-
 int mcp_track_map_record(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                          const uint8_t* const* const* masks, const mcp_camera* cams, double bfw[12], const double* cfb, const mcp_track_map_params* prm,
                          mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec) {
-  if (!m) return img_fail("mcp_track_map_record: NULL table");
-  if (!rp || !rec) return img_fail("mcp_track_map_record: NULL record parameters or record");
-  if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_map_record: a quality threshold is not finite");
-  return track_map_run("mcp_track_map_record", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec);
+  return TrackFrame{"mcp_track_map_record", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, true, rp, rec, nullptr, nullptr}.run();
 }
-
 int mcp_track_frame_motion(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                            const uint8_t* const* const* masks, const mcp_camera* cams, const mcp_camera* cams_sbi, double bfw[12], const double* cfb,
                            const mcp_track_map_params* prm, mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec,
                            const mcp_track_motion_params* mp, mcp_track_motion* out) {
-  if (!m) return img_fail("mcp_track_frame_motion: NULL table");
-  if (!rp || !rec) return img_fail("mcp_track_frame_motion: NULL record parameters or record");
-  if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_frame_motion: a quality threshold is not finite");
-  if (!mp || !out) return img_fail("mcp_track_frame_motion: NULL motion parameters or motion result");
   const MotionArg mo{cams_sbi, mp, out};
-  return track_map_run("mcp_track_frame_motion", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec, &mo);
+  return TrackFrame{"mcp_track_frame_motion", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, true, rp, rec, &mo, nullptr}.run();
 }
-
 int mcp_track_frame_recover(mcp_map_points* m, int ncam, mcp_kf* const* targets, const uint8_t* const* imgs, const int* strides, int imgs_on_device,
                             const uint8_t* const* const* masks, const mcp_camera* cams, const mcp_camera* cams_sbi, double bfw[12], const double* cfb,
                             const mcp_track_map_params* prm, mcp_track_map_result* res, const mcp_track_record_params* rp, mcp_track_record* rec,
                             const mcp_track_motion_params* mp, mcp_track_motion* out, int ncand, mcp_kf* const* cand_kf, const int* cand_cam,
                             const double* cand_cfw, const mcp_track_recover_params* rprm, mcp_track_recover* rout, double* scores) {
-  if (!m) return img_fail("mcp_track_frame_recover: NULL table");
-  if (!rp || !rec) return img_fail("mcp_track_frame_recover: NULL record parameters or record");
-  if (!std::isfinite(rp->quality_good) || !std::isfinite(rp->quality_bad)) return img_fail("mcp_track_frame_recover: a quality threshold is not finite");
-  if (!mp || !out) return img_fail("mcp_track_frame_recover: NULL motion parameters or motion result");
-  if (!rprm || !rout) return img_fail("mcp_track_frame_recover: NULL recover parameters or recover result");
   const MotionArg mo{cams_sbi, mp, out};
   const RecoverArg rc{ncand, cand_kf, cand_cam, cand_cfw, rprm, rout, scores};
-  return track_map_run("mcp_track_frame_recover", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, rp, rec, &mo, &rc);
+  return TrackFrame{"mcp_track_frame_recover", m, ncam, targets, imgs, strides, imgs_on_device, masks, cams, bfw, cfb, prm, res, true, rp, rec, &mo, &rc}.run();
 }
 
 int mcp_track_recover_pose_host(const double se2[6], const mcp_camera* cam_sbi, const double cfw_best[12], const double cfb[12], double out_cam_pose[12],

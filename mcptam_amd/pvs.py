@@ -289,15 +289,39 @@ class MapPointTable:
                    max_patches=1000, estimator="Tukey", seed=0, imgs=None, on_device=False, strides=None, copy=True):
         """mcp_track_map: the whole TrackMap of a frame.  Returns (items per camera (TRACK_MAP_ITEM_DTYPE; copies unless copy=False: views of
         the library's pinned block), (R, t), TrackMapResult)."""
-        L = _bind_track_map(self._L)
-        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
-        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
-                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
+        return self._track_frame(_bind_track_map(self._L), "track_map", (targets, cams, base_from_world, cams_from_base, imgs, on_device, strides),
+                                 (try_coarse, coarse_max, coarse_range, coarse_min, coarse_subpix_its, max_patches, estimator, seed), copy)
+
+    def _track_frame(self, L, name, frame, search, copy, record=None, cams_sbi=None, more=()):
+        """What the four one-call frames share: L.mcp_<name> over frame (_frame_args' arguments) with the TrackMapParams of search, the 40x30
+        cameras behind the cameras where given, the TrackRecordParams of record (lost, want_items, min_patches, quality_coarse_min,
+        quality_good, quality_bad) and a TrackRecord behind the result where given, then `more`.  Returns track_map's tuple, or with record
+        track_map_record's."""
+        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(*frame)
+        prm = TrackMapParams(*[int(v) for v in search[:6]], MEST[search[6]] if isinstance(search[6], str) else int(search[6]), int(search[7]))
         res = TrackMapResult()
-        _chk(L.mcp_track_map(self._h, ncam, hs, ip, st, int(on_device), None, cs, b.ctypes.data, cfb.ctypes.data, ctypes.byref(prm), ctypes.byref(res)), "track_map")
+        args = [self._h, ncam, hs, ip, st, int(frame[5]), None, cs]
+        if cams_sbi is not None:
+            keep += (cams_sbi if isinstance(cams_sbi, ctypes.Array) else camera_array(cams_sbi),)
+            args.append(ctypes.cast(keep[-1], ctypes.c_void_p))
+        args += [b.ctypes.data, cfb.ctypes.data, ctypes.byref(prm), ctypes.byref(res)]
+        if record is not None:
+            lost, want_items, min_patches, quality_coarse_min, quality_good, quality_bad = record
+            rp, rec = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad)), TrackRecord()
+            args += [ctypes.byref(rp), ctypes.byref(rec)]
+        _chk(getattr(L, "mcp_" + name)(*args, *more), name)
         del keep
-        items = [_view(L.mcp_track_map_view, (self._h, c), TRACK_MAP_ITEM_DTYPE, copy=copy) for c in range(ncam)]
-        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res
+        pose = (b[:9].reshape(3, 3).copy(), b[9:].copy())
+        if record is None:
+            return [_view(L.mcp_track_map_view, (self._h, c), TRACK_MAP_ITEM_DTYPE, copy=copy) for c in range(ncam)], pose, res
+
+        def views(fn, dtype, expect):
+            text = name + ": view of camera %d has %%(got)d entries, the record says %%(expect)d: "
+            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
+        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
+        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
+        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
+        return items, pose, res, notes, meas, rec
 
     # ---- TrackMap with its bookkeeping (include/mcp_img.h mcp_track_map_record) ----
     def set_counts(self, inlier, outlier, first=0):
@@ -329,23 +353,10 @@ class MapPointTable:
         found measurements, the scene depth per camera.  quality_coarse_min is AssessTrackingQuality's snCoarseMin (coarse_min: the coarse
         gate's).  Returns (items per camera, or None with want_items=False; (R, t); TrackMapResult; notes per camera (TRACK_NOTE_DTYPE);
         measurements per camera (TRACK_MEAS_DTYPE); TrackRecord) -- copies unless copy=False."""
-        L = _bind_track_record(_bind_track_map(self._L))
-        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
-        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
-                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
-        rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
-        res, rec = TrackMapResult(), TrackRecord()
-        _chk(L.mcp_track_map_record(self._h, ncam, hs, ip, st, int(on_device), None, cs, b.ctypes.data, cfb.ctypes.data,
-                                    ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec)), "track_map_record")
-        del keep
-
-        def views(fn, dtype, expect):
-            text = "track_map_record: view of camera %d has %%(got)d entries, the record says %%(expect)d: "
-            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
-        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
-        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
-        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
-        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec
+        return self._track_frame(_bind_track_record(_bind_track_map(self._L)), "track_map_record",
+                                 (targets, cams, base_from_world, cams_from_base, imgs, on_device, strides),
+                                 (try_coarse, coarse_max, coarse_range, coarse_min, coarse_subpix_its, max_patches, estimator, seed), copy,
+                                 (lost, want_items, min_patches, quality_coarse_min, quality_good, quality_bad))
 
     # ---- TrackFrame's tracking branch: motion model + TrackMap + its bookkeeping (include/mcp_img.h mcp_track_frame_motion) ----
     def track_frame_motion(self, targets, cams, cams_sbi, base_from_world, cams_from_base, velocity=None, dt=1.0 / 30, cam_good=None, apply=True,
@@ -356,25 +367,12 @@ class MapPointTable:
         call.  base_from_world: last frame's pose (mse3StartPose); cams_sbi: the 40x30 camera per camera; velocity: mv6BaseVelocity [t; w];
         cam_good: per camera, was its tracking quality GOOD after the previous frame (default: all).  Returns track_map_record's tuple plus the
         TrackMotion report (start, prior, se2, sbi_score, cam_rot, sbi_rot, n_used, avg_rounds, first_frame, v_new, velocity)."""
-        L = _bind_track_motion(_bind_track_record(_bind_track_map(self._L)))
-        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
-        css = cams_sbi if isinstance(cams_sbi, ctypes.Array) else camera_array(cams_sbi)
-        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
-                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
-        rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
-        mp = motion_params(velocity, dt, cam_good, apply, use_rotation_estimator, sbi_iterations, blur, ncam)
-        res, rec, mo = TrackMapResult(), TrackRecord(), TrackMotion()
-        _chk(L.mcp_track_frame_motion(self._h, ncam, hs, ip, st, int(on_device), None, cs, ctypes.cast(css, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
-                                      ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec), ctypes.byref(mp), ctypes.byref(mo)), "track_frame_motion")
-        del keep
-
-        def views(fn, dtype, expect):
-            text = "track_frame_motion: view of camera %d has %%(got)d entries, the record says %%(expect)d: "
-            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
-        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
-        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
-        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
-        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec, mo
+        mp, mo = motion_params(velocity, dt, cam_good, apply, use_rotation_estimator, sbi_iterations, blur, len(targets)), TrackMotion()
+        return self._track_frame(_bind_track_motion(_bind_track_record(_bind_track_map(self._L))), "track_frame_motion",
+                                 (targets, cams, base_from_world, cams_from_base, imgs, on_device, strides),
+                                 (try_coarse, coarse_max, coarse_range, coarse_min, coarse_subpix_its, max_patches, estimator, seed), copy,
+                                 (lost, want_items, min_patches, quality_coarse_min, quality_good, quality_bad), cams_sbi,
+                                 (ctypes.byref(mp), ctypes.byref(mo))) + (mo,)
 
     # ---- TrackFrame's lost branch: relocaliser + TrackMap + its bookkeeping (include/mcp_img.h mcp_track_frame_recover) ----
     def track_frame_recover(self, targets, cams, cams_sbi, base_from_world, cams_from_base, cand_kfs, cand_cams, cand_poses, reloc_blur=2.5,
@@ -386,30 +384,17 @@ class MapPointTable:
         one call.  cand_kfs: the map's keyframes (KeyFrame, None, or a raw handle value), cand_cams: each one's camera index among the
         targets, cand_poses: each one's CamFromWorld ((R, t) pairs or an (n, 12) array).  The caller sets try_coarse and the doubled coarse
         caps.  Returns track_frame_motion's tuple plus the TrackRecover report and the scores (None with want_scores=False)."""
-        L = _bind_track_recover(_bind_track_motion(_bind_track_record(_bind_track_map(self._L))))
-        ncam, hs, cs, b, cfb, ip, st, keep = _frame_args(targets, cams, base_from_world, cams_from_base, imgs, on_device, strides)
-        css = cams_sbi if isinstance(cams_sbi, ctypes.Array) else camera_array(cams_sbi)
-        prm = TrackMapParams(int(try_coarse), int(coarse_max), int(coarse_range), int(coarse_min), int(coarse_subpix_its), int(max_patches),
-                             MEST[estimator] if isinstance(estimator, str) else int(estimator), int(seed))
-        rp = TrackRecordParams(int(bool(lost)), int(bool(want_items)), int(min_patches), int(quality_coarse_min), float(quality_good), float(quality_bad))
-        mp = motion_params(velocity, 1.0, None, False, use_rotation_estimator, sbi_iterations, blur, ncam)
+        mp, mo = motion_params(velocity, 1.0, None, False, use_rotation_estimator, sbi_iterations, blur, len(targets)), TrackMotion()
         ncand, ch, cc, cp = _candidate_args(cand_kfs, cand_cams, cand_poses)
-        rq = TrackRecoverParams(float(reloc_blur), int(reloc_iterations), float(max_score))
-        res, rec, mo, rv = TrackMapResult(), TrackRecord(), TrackMotion(), TrackRecover()
+        rq, rv = TrackRecoverParams(float(reloc_blur), int(reloc_iterations), float(max_score)), TrackRecover()
         scores = np.zeros(max(ncand, 1)) if want_scores else None
-        _chk(L.mcp_track_frame_recover(self._h, ncam, hs, ip, st, int(on_device), None, cs, ctypes.cast(css, ctypes.c_void_p), b.ctypes.data, cfb.ctypes.data,
-                                       ctypes.byref(prm), ctypes.byref(res), ctypes.byref(rp), ctypes.byref(rec), ctypes.byref(mp), ctypes.byref(mo),
-                                       ncand, ctypes.cast(ch, ctypes.c_void_p), cc.ctypes.data, cp.ctypes.data, ctypes.byref(rq), ctypes.byref(rv),
-                                       scores.ctypes.data if want_scores else None), "track_frame_recover")
-        del keep
-
-        def views(fn, dtype, expect):
-            text = "track_frame_recover: view of camera %d has %%(got)d entries, the record says %%(expect)d: "
-            return [_view(fn, (self._h, c), dtype, expect[c], copy, text % c) for c in range(ncam)]
-        items = views(L.mcp_track_map_view, TRACK_MAP_ITEM_DTYPE, rec.n_items) if want_items else None
-        notes = views(L.mcp_track_map_notes_view, TRACK_NOTE_DTYPE, rec.n_items)
-        meas = views(L.mcp_track_map_meas_view, TRACK_MEAS_DTYPE, rec.n_meas)
-        return items, (b[:9].reshape(3, 3).copy(), b[9:].copy()), res, notes, meas, rec, mo, rv, (scores[:ncand] if want_scores else None)
+        more = (ctypes.byref(mp), ctypes.byref(mo), ncand, ctypes.cast(ch, ctypes.c_void_p), cc.ctypes.data, cp.ctypes.data, ctypes.byref(rq), ctypes.byref(rv),
+                scores.ctypes.data if want_scores else None)
+        return self._track_frame(_bind_track_recover(_bind_track_motion(_bind_track_record(_bind_track_map(self._L)))), "track_frame_recover",
+                                 (targets, cams, base_from_world, cams_from_base, imgs, on_device, strides),
+                                 (try_coarse, coarse_max, coarse_range, coarse_min, coarse_subpix_its, max_patches, estimator, seed), copy,
+                                 (lost, want_items, min_patches, quality_coarse_min, quality_good, quality_bad), cams_sbi,
+                                 more) + (mo, rv, scores[:ncand] if want_scores else None)
 
     def motion_reset(self):
         """Tracker::Reset: every camera index forgets its SmallBlurryImages."""
