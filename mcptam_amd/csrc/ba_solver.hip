@@ -431,6 +431,7 @@ static void hash_block(const int* p, size_t n, size_t stride_ints, unsigned long
   }
   a = mix64(x); b = mix64(y);
 }
+namespace { struct SlotChunk; }      // (of the structure build, in front of prepare())
 
 struct mcp_ba {
   int device = 0;
@@ -842,9 +843,52 @@ struct mcp_ba {
     avec<unsigned short> m_mask;
     avec<double> m_u, m_v, m_om;
   };
+  // Prepare(): one StructBuild (below, in front of prepare()) and its stages in the order prepare() goes through them
+  struct StructBuild; struct BlockLayout;
   int prepare();
-  int prepare_legacy();
-  int finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point tlast, bool trace, const StructEntry* hit = nullptr);
+  int prepare_legacy(StructBuild& B);
+  bool head_small_lds();
+  bool cache_lookup(StructBuild& B);
+  void near_miss_search(StructBuild& B);
+  int adopt(StructBuild& B);
+  void take_scratch(StructBuild& B);
+  void count_pass(StructBuild& B);
+  void count_totals(StructBuild& B);
+  int activity(StructBuild& B);
+  int pose_cut_order(StructBuild& B);
+  int coupling_graph(StructBuild& B, std::vector<unsigned long long>& adj);
+  int number_unknowns(StructBuild& B);
+  void point_order(StructBuild& B);
+  void scatter_by_point(StructBuild& B);
+  void build_slots(StructBuild& B);
+  void build_slot_chunk(StructBuild& B, SlotChunk& C);
+  void concat_slots(StructBuild& B);
+  void make_groups(StructBuild& B);
+  int tile_pattern_and_plan(StructBuild& B);
+  void local_indices(StructBuild& B);
+  void staging_plan(StructBuild& B);
+  // ... leaves that both builders share
+  int agree(std::vector<double>& v, const char* what);
+  int agree_activity();
+  int agree_tile_pattern(std::vector<unsigned char>& pat, int ntc);
+  int too_many_free_poses();
+  // ... and finish_prepare()'s stages
+  int finish_prepare(StructBuild& B);
+  void launch_choices(StructBuild& B);
+  void schur_work(StructBuild& B);
+  void small_arrays(StructBuild& B, BlockLayout& L);
+  int layout_block(StructBuild& B, BlockLayout& L);
+  int upload_hit_numbers(StructBuild& B, BlockLayout& L);
+  int upload_cold(BlockLayout& L);
+  int make_cache_entry(StructBuild& B, BlockLayout& L);
+  void read_call_knobs();
+  int alloc_work_buffers(int nmeas, int nblk);
+  int head_scratch(int nmeas, int nblk);
+  int poison_test_aid();
+  int pinned_mailbox(int nblk);
+  int zero_fill();
+  int fill_param_blocks(int nmeas);
+  int publish(StructBuild& B);
   int upload_state();
   int download_state();
   void launch_chains(int which);
@@ -985,155 +1029,307 @@ static int chain_first_movable(const HChain& c, const std::vector<HPose>& poses)
   return -1;
 }
 
-int mcp_ba::prepare() {
-  HIPCK(hipSetDevice(device));
-  {
-    // k_head_small keeps its candidates in 112 KB of dynamic LDS: a device (or partition) that does not grant that runs small bundles through
-    // the general launches instead (the refusal used to fail every robust small-bundle solve).  Per device: asked once.
-    static std::mutex hs_mu; static std::map<int, bool> hs_ok;
-    std::lock_guard<std::mutex> lk(hs_mu);
-    auto it = hs_ok.find(device);
-    if (it == hs_ok.end()) {
-      const bool ok = hipFuncSetAttribute((const void*)k_head_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(HS_STASH*sizeof(double))) == hipSuccess;
-      (void)hipGetLastError();
-      it = hs_ok.emplace(device, ok).first;
-    }
-    if (!it->second) small_on = 0;
+namespace {
+typedef unsigned long long u64;
+// the phase timer of one Prepare() (MCP_BA_TRACE): both builders and finish_prepare() print their laps through it
+struct PrepTimer {
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); std::chrono::steady_clock::time_point tlast = t0;
+  const bool trace = getenv("MCP_BA_TRACE") != nullptr;
+  void operator()(const char* what) { if (!trace) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[mcp_ba prepare] %-22s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tlast).count()); tlast = n; }
+  double total_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+struct SMeas { int chain, cam, mi, pad_; double u, v, omega; };      // a measurement on its way to its sorted position (scatter_by_point)
+// what build_slots() makes of a contiguous range of sorted points, indices relative to the range (concat_slots() fixes them up)
+struct SlotChunk { int sp0 = 0, sp1 = 0; std::vector<int> slot_unk, slot_inc, inc_unk, slot_cnt, sp_ninc, q_n, q_data; std::vector<unsigned char> slot_first, inc_state; };
+// finish_prepare()'s passes over the measurements go to the worker pool from 32768 of them (this value, whatever MCP_BA_PREP_PAR_MIN says)
+int finish_threads(int nmeas) { return nmeas >= 32768 ? host_pool().size() : 1; }
+template <class F> void run_ranges(int T, const F& body) { if (T == 1) body(0); else host_pool().run(body); }
+
+// per (obs chain, src chain) activity mask, memoised in a dense table (chains are few: P*C for the Multi adapter) or, past 4096
+// chains, in a map behind a mutex.  Defined here so that the per-measurement call of both builders inlines.
+class PairMasks {
+ public:
+  PairMasks(const mcp_ba& s) : s_(s), nch_(s.chains.size()), dense_(nch_ <= 4096), table_(dense_ ? new std::atomic<unsigned short>[nch_*nch_] : nullptr) {
+    static_assert(sizeof(std::atomic<unsigned short>) == 2, "mask table is filled bytewise");
+    if (dense_) std::memset(static_cast<void*>(table_.get()), 0xff, nch_*nch_*sizeof(unsigned short));      // (no thread reads it before the pool starts)
   }
-  if (getenv("MCP_BA_PREPARE_LEGACY")) return prepare_legacy();
-  auto t0 = std::chrono::steady_clock::now();
-  auto tlast = t0; const bool trace = getenv("MCP_BA_TRACE") != nullptr;
-  auto lap = [&](const char* what) { if (!trace) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[mcp_ba prepare] %-22s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tlast).count()); tlast = n; };
+  unsigned short operator()(int oc, int sc) {
+    if (dense_) {
+      // (entries are written concurrently by the structure threads: every writer stores the same value, relaxed atomics)
+      std::atomic<unsigned short>& e = table_[(size_t)oc*nch_ + sc];
+      unsigned short v = e.load(std::memory_order_relaxed);
+      if (v == 0xffff) { v = compute(oc, sc); e.store(v, std::memory_order_relaxed); }
+      return v;
+    }
+    std::lock_guard<std::mutex> lk(mutex_);
+    auto key = std::make_pair(oc, sc);
+    auto it = cache_.find(key);
+    if (it != cache_.end()) return it->second;
+    const unsigned short mk = compute(oc, sc);
+    cache_[key] = mk; return mk;
+  }
+ private:
+  unsigned short compute(int oc, int sc) const {
+    unsigned short mk = 0;
+    const HChain& o = s_.chains[oc]; const HChain& s2 = s_.chains[sc];
+    for (int i = 0; i < o.len; ++i) if (!s_.poses[o.v[i]].fixed && !s_.move_together(o, s2, i)) mk |= (1 << i);
+    for (int i = 0; i < s2.len; ++i) if (!s_.poses[s2.v[i]].fixed && !s_.move_together(s2, o, i)) mk |= (1 << (MAXC + i));
+    return mk;
+  }
+  const mcp_ba& s_; const size_t nch_; const bool dense_; std::unique_ptr<std::atomic<unsigned short>[]> table_;
+  std::map<std::pair<int, int>, unsigned short> cache_; std::mutex mutex_;
+};
+
+// pose-pair co-visibility (a >= b, nfp x nfp) as the 16-row tile pattern of the reduced system, the diagonal tiles always present
+std::vector<unsigned char> cov_to_pattern(const std::vector<unsigned char>& cov, int nfp, int ntc) {
+  std::vector<unsigned char> pat((size_t)ntc*ntc, 0);
+  for (int a = 0; a < nfp; ++a) for (int b = 0; b <= a; ++b) {
+    if (!cov[(size_t)a*nfp + b]) continue;
+    const int ra0 = (6*a)/CH_NB, ra1 = (6*a + 5)/CH_NB, rb0 = (6*b)/CH_NB, rb1 = (6*b + 5)/CH_NB;
+    for (int ra = ra0; ra <= ra1; ++ra) for (int rb = rb0; rb <= rb1; ++rb) if (ra >= rb) pat[(size_t)ra*ntc + rb] = 1;
+  }
+  for (int i = 0; i < ntc; ++i) pat[(size_t)i*ntc + i] = 1;
+  return pat;
+}
+}
+
+// One Prepare() call: what it derives once and what its stages hand to each other, in the order the stages fill it.
+struct mcp_ba::StructBuild {
+  // LIFETIME FIRST: members are destroyed in reverse order of declaration, and everything below lives in what these three hold.
+  // scratch_lock (count_pass; the serial builder and a cache hit never take it) is taken before arena_lock (hold_arena) and released
+  // after it; arena_guard, declared last of the three, goes first: it waits for the stream's uploads out of the pinned arena and
+  // resets the arena while arena_lock is still held.  prepare() keeps the description until finish_prepare() has returned.
+  std::unique_lock<std::mutex> scratch_lock, arena_lock;
+  std::unique_ptr<ArenaGuard> arena_guard;
+  void hold_arena(hipStream_t st) { arena_lock = std::unique_lock<std::mutex>(pinned_arena().mutex()); arena_guard.reset(new ArenaGuard{st}); }
+  HostStruct H;
+  PrepTimer lap;
+  const int npose, npoint, nmeas; const size_t nch;
+  int T = 1;                                       // threads of the worker pool the structure is built on (1: on the caller's)
+  void par(const std::function<void(int)>& fn) const { if (T == 1) fn(0); else host_pool().run(fn); }
+  long lo_of(int tid, long n) const { return (long)(n*tid/T); }
+  std::shared_ptr<StructEntry> hit; std::vector<int> present;      // cache_lookup: the adopted entry; near miss: cached add index -> this map's add index, -1 = this map does not have it
+  bool refine = false, want_graph = false;
+  u64* seen_t = nullptr; int* cnt_t = nullptr; int* sig_t = nullptr; SMeas* sorted = nullptr;      // in PrepScratch
+  std::vector<int> seen_ids, cnt, smax, ssum, order, sp_of, sp_q0, sp_q;      // (sp_q0, sp_q: distinct pose unknowns touched by every sorted point)
+  std::vector<unsigned char> seen_over, chain_used, cov, inc_state, gcov;      // (cov: pose-pair co-visibility, a >= b)
+  std::unique_ptr<PairMasks> pair_mask; std::vector<SlotChunk> chunks;
+  StructBuild(const mcp_ba& s, bool serial) : npose((int)s.poses.size()), npoint((int)s.points.size()), nmeas((int)s.meas.size()), nch(s.chains.size()) {
+    static const int par_min = [] { const char* e = getenv("MCP_BA_PREP_PAR_MIN"); return e ? atoi(e) : 32768; }();      // measurements from which the structure is built on the worker pool
+    if (!serial && nmeas >= par_min) T = host_pool().size();
+  }
+};
+
+// k_head_small keeps its candidates in 112 KB of dynamic LDS: a device (or partition) that does not grant that runs small bundles through
+// the general launches instead (the refusal used to fail every robust small-bundle solve).  Per device: asked once.
+bool mcp_ba::head_small_lds() {
+  static std::mutex hs_mu; static std::map<int, bool> hs_ok;
+  std::lock_guard<std::mutex> lk(hs_mu);
+  auto it = hs_ok.find(device);
+  if (it == hs_ok.end()) {
+    const bool ok = hipFuncSetAttribute((const void*)k_head_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(HS_STASH*sizeof(double))) == hipSuccess;
+    (void)hipGetLastError();
+    it = hs_ok.emplace(device, ok).first;
+  }
+  return it->second;
+}
+
+int mcp_ba::prepare() {
+  // what a Prepare() leaves for Compute() starts from nothing here, whichever builder or cache path follows (med_rank() reads n_masked)
+  n_masked = 0; cache_insert = false; chol_segs.clear(); plan.persist_segs.clear();
   HIPCK(hipSetDevice(device));
-  const int npose = (int)poses.size(), npoint = (int)points.size(), nmeas = (int)meas.size();
-  const size_t nch = chains.size();
-  HostPool& pool = host_pool();
-  static const int par_min = [] { const char* e = getenv("MCP_BA_PREP_PAR_MIN"); return e ? atoi(e) : 32768; }();      // measurements from which the structure is built on the worker pool
-  const int T = (nmeas >= par_min) ? pool.size() : 1;
-  auto par = [&](const std::function<void(int)>& fn) { if (T == 1) fn(0); else pool.run(fn); };
-  auto lo_of = [&](int tid, long n) { return (long)(n*tid/T); };
-  lap("  entry");
-  // ---- the same topology as an earlier call's (structure cache, above)?  128-bit hash over what the structure is built from
-  cache_insert = false;
+  if (!head_small_lds()) small_on = 0;
+  const bool serial = getenv("MCP_BA_PREPARE_LEGACY") != nullptr;
+  StructBuild B(*this, serial);
+  if (serial) return prepare_legacy(B);
+  B.lap("  entry");
   { const char* e = getenv("MCP_BA_CHOL_CHAINS"); dissect_on = !(e && atoi(e) == 1); }
   { const char* e = getenv("MCP_BA_CHOL_ARCS"); chain_arcs = e ? atoi(e) : 6; }
-  if (StructCache::get().enabled() && !multi() && nmeas > 0) {
-    constexpr size_t HB = 8192;
-    const size_t nbm = ((size_t)nmeas + HB - 1)/HB;
-    std::vector<unsigned long long> ha(3*nbm + 4), hb(3*nbm + 4);
-    par([&](int tid) {
-      for (size_t b = (size_t)lo_of(tid, (long)nbm), e = (size_t)lo_of(tid + 1, (long)nbm); b < e; ++b) {
-        const size_t i0 = b*HB, n = std::min(HB, (size_t)nmeas - i0);
-        hash_block(meas_chain.data() + i0, n, 1, 1, ha[3*b], hb[3*b]);
-        hash_block(meas_point.data() + i0, n, 1, 2, ha[3*b + 1], hb[3*b + 1]);
-        hash_block(&meas[i0].cam, n, sizeof(HMeas)/sizeof(int), 3, ha[3*b + 2], hb[3*b + 2]);
-      }
-    });
-    static_assert(sizeof(HMeas) % sizeof(int) == 0 && sizeof(HPoint) % sizeof(int) == 0 && sizeof(HPose) % sizeof(int) == 0 && sizeof(HChain) == (1 + MCP_MAX_CHAIN)*sizeof(int), "strided hashing");
-    if (npose) hash_block(&poses[0].fixed, npose, sizeof(HPose)/sizeof(int), 4, ha[3*nbm], hb[3*nbm]);
-    if (nch) hash_block(&chains[0].len, nch*(1 + MCP_MAX_CHAIN), 1, 5, ha[3*nbm + 1], hb[3*nbm + 1]);
-    if (npoint) { hash_block(&points[0].fixed, npoint, sizeof(HPoint)/sizeof(int), 6, ha[3*nbm + 2], hb[3*nbm + 2]); hash_block(&points[0].chain, npoint, sizeof(HPoint)/sizeof(int), 7, ha[3*nbm + 3], hb[3*nbm + 3]); }
-    StructKey key;
-    for (size_t i = 0; i < ha.size(); ++i) { key.h0 = mix64(key.h0 ^ ha[i]) + i; key.h1 = mix64(key.h1 + hb[i]) ^ (i*0x9e3779b97f4a7c15ull); }
-    key.npose = npose; key.npoint = npoint; key.nmeas = nmeas; key.nchain = (int)nch; key.dev = device;
-    key.h1 = mix64(key.h1 ^ (unsigned long long)cams.size());          // (the camera table is part of the packed block's layout)
-    // (what else decides the structure: the grouping policy and its run-time switches)
-    const char* e_al = getenv("MCP_BA_ASM_LONG");
-    key.flags = grp_lmax_pol | (point_order_refine ? 32 : 0) | (sch4_on ? 64 : 0) | (env_on("MCP_BA_SCHUR4_ORDER", true) ? 128 : 0) | (group_points(npoint) << 8) |
-                ((e_al ? 1 + (atoi(e_al) != 0) : 0) << 16) | (dissect_on ? (chain_arcs & 7) << 18 : 0);
-    { const char* e = getenv("MCP_BA_TEST_CHOL_CUT"); if (e) key.flags ^= (unsigned)(atoi(e) & 0xff) << 21; }
-    cache_key = key;
-    {
-      // the same key without the measurements (near miss, below)
-      StructKey b = key; b.h0 = b.h1 = 0; b.nmeas = 0;
-      for (size_t i = 3*nbm, r = 0; i < ha.size(); ++i, ++r) { b.h0 = mix64(b.h0 ^ ha[i]) + r; b.h1 = mix64(b.h1 + hb[i]) ^ (r*0x9e3779b97f4a7c15ull); }      // (r, not i: the number of measurement blocks must not enter)
-      b.h1 = mix64(b.h1 ^ (unsigned long long)cams.size());
-      cache_base = b;
+  if (cache_lookup(B)) return adopt(B) ? -1 : finish_prepare(B);
+  count_pass(B);
+  if (activity(B) || pose_cut_order(B) || number_unknowns(B)) return -1;
+  point_order(B);
+  scatter_by_point(B);
+  build_slots(B);
+  concat_slots(B);
+  make_groups(B);
+  if (tile_pattern_and_plan(B)) return -1;
+  local_indices(B);
+  staging_plan(B);
+  return finish_prepare(B);
+}
+
+// ---- the same topology as an earlier call's (structure cache, above)?  128-bit hash over what the structure is built from, the
+// entry of that key or, failing that, of a superset of the measurements (near miss).  true: B.hit is to be adopted
+bool mcp_ba::cache_lookup(StructBuild& B) {
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas; const size_t nch = B.nch; PrepTimer& lap = B.lap;
+  if (!(StructCache::get().enabled() && !multi() && nmeas > 0)) return false;
+  constexpr size_t HB = 8192;
+  const size_t nbm = ((size_t)nmeas + HB - 1)/HB;
+  std::vector<unsigned long long> ha(3*nbm + 4), hb(3*nbm + 4);
+  B.par([&](int tid) {
+    for (size_t b = (size_t)B.lo_of(tid, (long)nbm), e = (size_t)B.lo_of(tid + 1, (long)nbm); b < e; ++b) {
+      const size_t i0 = b*HB, n = std::min(HB, (size_t)nmeas - i0);
+      hash_block(meas_chain.data() + i0, n, 1, 1, ha[3*b], hb[3*b]);
+      hash_block(meas_point.data() + i0, n, 1, 2, ha[3*b + 1], hb[3*b + 1]);
+      hash_block(&meas[i0].cam, n, sizeof(HMeas)/sizeof(int), 3, ha[3*b + 2], hb[3*b + 2]);
     }
-    n_masked = 0;
-    std::shared_ptr<StructEntry> hit = StructCache::get().find(key);
-    lap("  topology hash");
-    std::vector<int> present;          // near miss: cached add index -> this map's add index, -1 = this map does not have it
-    if (!hit && near_miss_on) {
-      // NEAR MISS (round 6): MCPTAM erases the measurements an adjustment flagged as outliers and adjusts again
-      // (/root/reference/src/MapMaker.cc:225-230, 283-287 -> MapMakerServerBase::HandleOutliers, src/MapMakerServerBase.cc:1198-1238:
-      // kf.EraseMeasurementOfPoint) -- the next ChainBundle holds the poses, points and chains of the call before and its measurements
-      // MINUS a few, in the same order.  If the cache holds such a superset and no pose or point loses its last measurement (activity,
-      // hence the unknowns, unchanged), its structure is adopted as on a hit; the erased measurements keep their place in the device
-      // arrays with weight 0.  Same mathematics as a cold Prepare() of the smaller map; the order of some floating-point sums differs
-      // (the cold build would group the points by their NEW observer sets), so the two agree to rounding, not bit for bit.
-      for (auto& c : StructCache::get().find_supersets(cache_base, nmeas)) {
-        const int nc2 = c->key.nmeas;
-        present.assign(nc2, -1);
-        const int* ep = c->add_point.data(); const int* ec = c->add_chain.data(); const int* em = c->add_cam.data();
-        const int* mp = meas_point.data(); const int* mc = meas_chain.data();
-        int j = 0;
-        for (int i = 0; i < nc2 && j < nmeas; ++i) if (ep[i] == mp[j] && ec[i] == mc[j] && em[i] == meas[j].cam) present[i] = j++;
-        if (j != nmeas) continue;
-        // activity: every point / pose that was active must still be (and none can have become active)
-        std::vector<unsigned char> pa(npoint, 0), cu(nch, 0), qa(npose, 0);
-        for (int i = 0; i < nmeas; ++i) { pa[mp[i]] = 1; cu[mc[i]] = 1; }
-        for (int i = 0; i < npoint; ++i) if (pa[i]) cu[points[i].chain] = 1;
-        for (size_t ch = 0; ch < nch; ++ch) if (cu[ch]) for (int k2 = 0; k2 < chains[ch].len; ++k2) qa[chains[ch].v[k2]] = 1;
-        bool same = true;
-        for (int i = 0; i < npoint && same; ++i) same = pa[i] == c->pt_active[i];
-        for (int i = 0; i < npose && same; ++i) same = qa[i] == c->pose_active[i];
-        if (!same) continue;
-        hit = c; n_masked = nc2 - nmeas;
-        StructCache::get().touch(c);
-        break;
-      }
-      lap("  near miss search");
-    }
-    if (hit) {
-      // adopt: the host-side results of the structure build, then the device block (finish_prepare)
-      for (int i = 0; i < npose; ++i) { poses[i].unk = hit->pose_unk[i]; poses[i].active = hit->pose_active[i]; }
-      for (int i = 0; i < npoint; ++i) { points[i].unk = hit->pt_unk[i]; points[i].active = hit->pt_active[i]; }
-      fp_pose = hit->fp_pose; fl_point = hit->fl_point; perm = hit->perm;
-      if (n_masked) for (auto& v : perm) v = present[v];          // sorted position -> THIS map's add index, -1 = erased here
-      nfp = hit->nfp; nfl = hit->nfl; np = hit->np; nx = hit->nx; nsp = hit->nsp; ninc = hit->ninc; nslot = hit->nslot; ngroup = hit->ngroup; nbig = hit->nbig;
-      grp_pts = hit->grp_pts; grp_blk_max = hit->grp_blk_max; grp_inc_max = hit->grp_inc_max; nrhs_rows = hit->nrhs_rows; nstage = hit->nstage;
-      m_total = n_masked ? (double)nmeas : hit->m_total; nfl_total = hit->nfl_total;
-      if (np > CH_SOLVE_MAX) { set_err("too many free poses for the dense reduced solve (6P > 6144)"); return -1; }
-      std::unique_lock<std::mutex> arena_lock(pinned_arena().mutex());
-      ArenaGuard arena_guard{st};
-      HostStruct H;
-      last_pat = hit->pat; chol_segs = hit->chol_segs;
-      plan.persist_segs = chol_segs;
-      if (np > 0) { if (plan.build(np, last_pat)) { set_err("Cholesky plan allocation failed"); return -1; } }
-      else plan.all_tiles.clear();
-      lap(n_masked ? "  adopted (near miss)" : "  adopted (cache hit)");
-      return finish_prepare(H, t0, tlast, trace, hit.get());
-    }
-    cache_insert = true;
+  });
+  static_assert(sizeof(HMeas) % sizeof(int) == 0 && sizeof(HPoint) % sizeof(int) == 0 && sizeof(HPose) % sizeof(int) == 0 && sizeof(HChain) == (1 + MCP_MAX_CHAIN)*sizeof(int), "strided hashing");
+  if (npose) hash_block(&poses[0].fixed, npose, sizeof(HPose)/sizeof(int), 4, ha[3*nbm], hb[3*nbm]);
+  if (nch) hash_block(&chains[0].len, nch*(1 + MCP_MAX_CHAIN), 1, 5, ha[3*nbm + 1], hb[3*nbm + 1]);
+  if (npoint) { hash_block(&points[0].fixed, npoint, sizeof(HPoint)/sizeof(int), 6, ha[3*nbm + 2], hb[3*nbm + 2]); hash_block(&points[0].chain, npoint, sizeof(HPoint)/sizeof(int), 7, ha[3*nbm + 3], hb[3*nbm + 3]); }
+  StructKey key;
+  for (size_t i = 0; i < ha.size(); ++i) { key.h0 = mix64(key.h0 ^ ha[i]) + i; key.h1 = mix64(key.h1 + hb[i]) ^ (i*0x9e3779b97f4a7c15ull); }
+  key.npose = npose; key.npoint = npoint; key.nmeas = nmeas; key.nchain = (int)nch; key.dev = device;
+  key.h1 = mix64(key.h1 ^ (unsigned long long)cams.size());          // (the camera table is part of the packed block's layout)
+  // (what else decides the structure: the grouping policy and its run-time switches)
+  const char* e_al = getenv("MCP_BA_ASM_LONG");
+  key.flags = grp_lmax_pol | (point_order_refine ? 32 : 0) | (sch4_on ? 64 : 0) | (env_on("MCP_BA_SCHUR4_ORDER", true) ? 128 : 0) | (group_points(npoint) << 8) |
+              ((e_al ? 1 + (atoi(e_al) != 0) : 0) << 16) | (dissect_on ? (chain_arcs & 7) << 18 : 0);
+  { const char* e = getenv("MCP_BA_TEST_CHOL_CUT"); if (e) key.flags ^= (unsigned)(atoi(e) & 0xff) << 21; }
+  cache_key = key;
+  {
+    // the same key without the measurements (near miss, below)
+    StructKey b = key; b.h0 = b.h1 = 0; b.nmeas = 0;
+    for (size_t i = 3*nbm, r = 0; i < ha.size(); ++i, ++r) { b.h0 = mix64(b.h0 ^ ha[i]) + r; b.h1 = mix64(b.h1 + hb[i]) ^ (r*0x9e3779b97f4a7c15ull); }      // (r, not i: the number of measurement blocks must not enter)
+    b.h1 = mix64(b.h1 ^ (unsigned long long)cams.size());
+    cache_base = b;
   }
-  // ---- one pass over the measurements in add order, a range per thread: which chains are used, and how many measurements of
-  // every point the range holds (private counters: no shared writes)
-  std::vector<unsigned char> chain_used(nch, 0);
-  struct SMeas { int chain, cam, mi, pad_; double u, v, omega; };
+  B.hit = StructCache::get().find(key);
+  lap("  topology hash");
+  if (!B.hit && near_miss_on) { near_miss_search(B); lap("  near miss search"); }
+  cache_insert = !B.hit;
+  return B.hit != nullptr;
+}
+
+void mcp_ba::near_miss_search(StructBuild& B) {
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas; const size_t nch = B.nch; std::vector<int>& present = B.present;
+  // NEAR MISS (round 6): MCPTAM erases the measurements an adjustment flagged as outliers and adjusts again
+  // (/root/reference/src/MapMaker.cc:225-230, 283-287 -> MapMakerServerBase::HandleOutliers, src/MapMakerServerBase.cc:1198-1238:
+  // kf.EraseMeasurementOfPoint) -- the next ChainBundle holds the poses, points and chains of the call before and its measurements
+  // MINUS a few, in the same order.  If the cache holds such a superset and no pose or point loses its last measurement (activity,
+  // hence the unknowns, unchanged), its structure is adopted as on a hit; the erased measurements keep their place in the device
+  // arrays with weight 0.  Same mathematics as a cold Prepare() of the smaller map; the order of some floating-point sums differs
+  // (the cold build would group the points by their NEW observer sets), so the two agree to rounding, not bit for bit.
+  for (auto& c : StructCache::get().find_supersets(cache_base, nmeas)) {
+    const int nc2 = c->key.nmeas;
+    present.assign(nc2, -1);
+    const int* ep = c->add_point.data(); const int* ec = c->add_chain.data(); const int* em = c->add_cam.data();
+    const int* mp = meas_point.data(); const int* mc = meas_chain.data();
+    int j = 0;
+    for (int i = 0; i < nc2 && j < nmeas; ++i) if (ep[i] == mp[j] && ec[i] == mc[j] && em[i] == meas[j].cam) present[i] = j++;
+    if (j != nmeas) continue;
+    // activity: every point / pose that was active must still be (and none can have become active)
+    std::vector<unsigned char> pa(npoint, 0), cu(nch, 0), qa(npose, 0);
+    for (int i = 0; i < nmeas; ++i) { pa[mp[i]] = 1; cu[mc[i]] = 1; }
+    for (int i = 0; i < npoint; ++i) if (pa[i]) cu[points[i].chain] = 1;
+    for (size_t ch = 0; ch < nch; ++ch) if (cu[ch]) for (int k2 = 0; k2 < chains[ch].len; ++k2) qa[chains[ch].v[k2]] = 1;
+    bool same = true;
+    for (int i = 0; i < npoint && same; ++i) same = pa[i] == c->pt_active[i];
+    for (int i = 0; i < npose && same; ++i) same = qa[i] == c->pose_active[i];
+    if (!same) continue;
+    B.hit = c; n_masked = nc2 - nmeas;
+    StructCache::get().touch(c);
+    break;
+  }
+}
+
+// adopt: the host-side results of the structure build; the device block follows in finish_prepare()
+int mcp_ba::adopt(StructBuild& B) {
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas; const StructEntry* hit = B.hit.get(); const std::vector<int>& present = B.present;
+  for (int i = 0; i < npose; ++i) { poses[i].unk = hit->pose_unk[i]; poses[i].active = hit->pose_active[i]; }
+  for (int i = 0; i < npoint; ++i) { points[i].unk = hit->pt_unk[i]; points[i].active = hit->pt_active[i]; }
+  fp_pose = hit->fp_pose; fl_point = hit->fl_point; perm = hit->perm;
+  if (n_masked) for (auto& v : perm) v = present[v];          // sorted position -> THIS map's add index, -1 = erased here
+  nfp = hit->nfp; nfl = hit->nfl; np = hit->np; nx = hit->nx; nsp = hit->nsp; ninc = hit->ninc; nslot = hit->nslot; ngroup = hit->ngroup; nbig = hit->nbig;
+  grp_pts = hit->grp_pts; grp_blk_max = hit->grp_blk_max; grp_inc_max = hit->grp_inc_max; nrhs_rows = hit->nrhs_rows; nstage = hit->nstage;
+  m_total = n_masked ? (double)nmeas : hit->m_total; nfl_total = hit->nfl_total;
+  if (too_many_free_poses()) return -1;
+  B.hold_arena(st);
+  last_pat = hit->pat; chol_segs = hit->chol_segs;
+  plan.persist_segs = chol_segs;
+  if (np > 0) { if (plan.build(np, last_pat)) { set_err("Cholesky plan allocation failed"); return -1; } }
+  else plan.all_tiles.clear();
+  B.lap(n_masked ? "  adopted (near miss)" : "  adopted (cache hit)");
+  return 0;
+}
+
+int mcp_ba::too_many_free_poses() {
+  if (np <= CH_SOLVE_MAX) return 0;
+  set_err("too many free poses for the dense reduced solve (6P > 6144)"); return -1;
+}
+
+// multi-rank agreement: a vector of doubles summed over the ranks (uploaded, all-reduced on lane 0, copied back)
+int mcp_ba::agree(std::vector<double>& v, const char* what) {
+  DevBuf<double> tmp;
+  if (tmp.upload(v, st)) return -1;
+  if (allreduce(tmp.p, v.size(), 0, true, what)) return -1;
+  HIPCK(hipMemcpy(v.data(), tmp.p, v.size()*sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+// ranks hold different measurement shards: agree on the active poses and the global counts
+int mcp_ba::agree_activity() {
+  const int npose = (int)poses.size();
+  std::vector<double> flags(npose + 2);
+  for (int i = 0; i < npose; ++i) flags[i] = poses[i].active;
+  flags[npose] = (double)meas.size();
+  double nfree = 0; for (const auto& p : points) if (p.active && !p.fixed) nfree += 1;
+  flags[npose + 1] = nfree;
+  if (agree(flags, "set-up: active poses and counts")) return -1;
+  for (int i = 0; i < npose; ++i) poses[i].active = flags[i] > 0;
+  m_total = flags[npose]; nfl_total = flags[npose + 1];
+  return 0;
+}
+// the union of every rank's co-visibility pattern: agreed once, used for the factorisation plan and for the
+// packed all-reduce of the reduced system (only structurally non-zero tiles travel over xGMI)
+int mcp_ba::agree_tile_pattern(std::vector<unsigned char>& pat, int ntc) {
+  std::vector<double> pd(pat.begin(), pat.end());
+  if (agree(pd, "set-up: tile pattern")) return -1;
+  for (size_t i = 0; i < pd.size(); ++i) pat[i] = pd[i] > 0;
+  std::vector<int> rt;
+  for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (pat[(size_t)i*ntc + j]) rt.push_back((i << 16) | j);
+  n_red_tiles = (int)rt.size();
+  if (d_red_tiles.upload(rt, st) || d_pack.alloc(MAX_SYS*((size_t)n_red_tiles*CH_NB*CH_NB + 2*(size_t)np))) return -1;
+  pack_stride = (size_t)n_red_tiles*CH_NB*CH_NB + 2*(size_t)np;
+  return 0;
+}
+
+// the process-wide scratch block, held from here to the end of the Prepare(): the per-thread counters of count_pass() and the sorted measurements
+void mcp_ba::take_scratch(StructBuild& B) {
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas, T = B.T;
   PrepScratch& scratch = prep_scratch();
-  std::unique_lock<std::mutex> scratch_lock(scratch.m);
+  B.scratch_lock = std::unique_lock<std::mutex>(scratch.m);
   // (with the secondary point order: per point also the largest observer pose and the sum of the observer poses -- the key of
   //  refine_point_order -- in the same private way: a first version added them up with atomics on shared arrays, 6 ms of cache-line
   //  ping-pong between the threads)
-  const bool refine = point_order_refine;
+  const bool refine = B.refine = point_order_refine;
   // (for the chains of the factorisation, below: per point the poses that see it, as a 64-bit set per thread -- the adapters add the
   //  measurements KeyFrame by KeyFrame, so a thread's range of the add order holds few distinct observers: each gets a bit as it is first
   //  met, whatever its pose index; a range with more than 64 of them is reported and the sets are taken again with atomics)
-  const bool want_graph = dissect_on && npose >= 96 && npose <= 1024 + 64;
-  typedef unsigned long long u64;
+  const bool want_graph = B.want_graph = dissect_on && npose >= 96 && npose <= 1024 + 64;
   scratch.reset(sizeof(int)*(size_t)(refine ? 3 : 1)*T*std::max(npoint, 1) + sizeof(SMeas)*(size_t)std::max(nmeas, 1) + (want_graph ? sizeof(u64)*(size_t)T*std::max(npoint, 1) : 0) + 512);
-  u64* const seen_t = want_graph ? scratch.take<u64>((size_t)T*std::max(npoint, 1)) : nullptr;
-  std::vector<int> seen_ids((size_t)T*64, -1), cobs; std::vector<unsigned char> seen_over(T, 0);
+  B.seen_t = want_graph ? scratch.take<u64>((size_t)T*std::max(npoint, 1)) : nullptr;
+  B.cnt_t = scratch.take<int>((size_t)T*std::max(npoint, 1));
+  B.sig_t = refine ? scratch.take<int>((size_t)2*T*std::max(npoint, 1)) : nullptr;      // [thread][max | sum][point]
+  B.sorted = scratch.take<SMeas>(std::max(nmeas, 1));
+}
+
+// ---- one pass over the measurements in add order, a range per thread: which chains are used, and how many measurements of
+// every point the range holds (private counters: no shared writes)
+void mcp_ba::count_pass(StructBuild& B) {
+  take_scratch(B);
+  const int npoint = B.npoint, nmeas = B.nmeas, T = B.T; const size_t nch = B.nch; const bool refine = B.refine, want_graph = B.want_graph;
+  u64* const seen_t = B.seen_t; int* const cnt_t = B.cnt_t; int* const sig_t = B.sig_t;
+  std::vector<unsigned char>& chain_used = B.chain_used; chain_used.assign(nch, 0);
+  std::vector<int>& seen_ids = B.seen_ids; std::vector<unsigned char>& seen_over = B.seen_over; std::vector<int> cobs;
+  seen_ids.assign((size_t)T*64, -1); seen_over.assign(T, 0);
   if (want_graph) { cobs.resize(nch); for (size_t c = 0; c < nch; ++c) { int one = -1, nmov = 0; for (int k = 0; k < chains[c].len; ++k) if (!poses[chains[c].v[k]].fixed) { one = chains[c].v[k]; ++nmov; } cobs[c] = nmov == 1 ? one : nmov ? -2 : -1; } }
-  int* const cnt_t = scratch.take<int>((size_t)T*std::max(npoint, 1));
-  int* const sig_t = refine ? scratch.take<int>((size_t)2*T*std::max(npoint, 1)) : nullptr;      // [thread][max | sum][point]
-  SMeas* const sorted = scratch.take<SMeas>(std::max(nmeas, 1));
   std::vector<int> ckey;
   if (refine) { ckey.resize(nch); for (size_t c = 0; c < nch; ++c) ckey[c] = chain_first_movable(chains[c], poses) + 1; }
   {
     std::vector<unsigned char> cu_all((size_t)T*nch, 0);
-    par([&](int tid) {
+    B.par([&](int tid) {
       unsigned char* cu = cu_all.data() + (size_t)tid*nch; int* ct = cnt_t + (size_t)tid*npoint;
       std::memset(ct, 0, sizeof(int)*(size_t)npoint);
       const int* mc = meas_chain.data(); const int* mp = meas_point.data();
@@ -1141,7 +1337,7 @@ int mcp_ba::prepare() {
         u64* sn = seen_t + (size_t)tid*npoint;
         std::memset(sn, 0, sizeof(u64)*(size_t)npoint);
         const int* co = cobs.data(); int* ids = &seen_ids[(size_t)tid*64]; int nids = 0, last_ob = -1, last_bit = 0; bool over = false;
-        for (long i = lo_of(tid, nmeas), e = lo_of(tid + 1, nmeas); i < e; ++i) {
+        for (long i = B.lo_of(tid, nmeas), e = B.lo_of(tid + 1, nmeas); i < e; ++i) {
           const int ob = co[mc[i]];
           if (ob < 0) { over |= ob == -2; continue; }
           if (ob != last_ob) {
@@ -1153,11 +1349,11 @@ int mcp_ba::prepare() {
         }
         seen_over[tid] = over;
       }
-      if (!refine) { for (long i = lo_of(tid, nmeas), e = lo_of(tid + 1, nmeas); i < e; ++i) { cu[mc[i]] = 1; ct[mp[i]]++; } return; }
+      if (!refine) { for (long i = B.lo_of(tid, nmeas), e = B.lo_of(tid + 1, nmeas); i < e; ++i) { cu[mc[i]] = 1; ct[mp[i]]++; } return; }
       int* mx = sig_t + (size_t)2*tid*npoint; int* sm = mx + npoint;
       std::memset(mx, 0, sizeof(int)*(size_t)2*npoint);
       const int* ck = ckey.data();
-      for (long i = lo_of(tid, nmeas), e = lo_of(tid + 1, nmeas); i < e; ++i) {
+      for (long i = B.lo_of(tid, nmeas), e = B.lo_of(tid + 1, nmeas); i < e; ++i) {
         const int c = mc[i], pt = mp[i], k = ck[c];
         cu[c] = 1; ct[pt]++;
         sm[pt] += k; if (k > mx[pt]) mx[pt] = k;
@@ -1165,11 +1361,17 @@ int mcp_ba::prepare() {
     });
     for (int t = 0; t < T; ++t) for (size_t c = 0; c < nch; ++c) chain_used[c] |= cu_all[(size_t)t*nch + c];
   }
-  // per point: total, and the rank at which every thread's measurements of it start (add order = thread order, then index order)
-  std::vector<int> cnt(npoint + 1, 0), smax, ssum;
+  count_totals(B);
+  B.lap("  counts (threads)");
+}
+// per point: total, and the rank at which every thread's measurements of it start (add order = thread order, then index order)
+void mcp_ba::count_totals(StructBuild& B) {
+  const int npoint = B.npoint, T = B.T; const bool refine = B.refine; int* const cnt_t = B.cnt_t; const int* const sig_t = B.sig_t;
+  std::vector<int>& cnt = B.cnt; std::vector<int>& smax = B.smax; std::vector<int>& ssum = B.ssum;
+  cnt.assign(npoint + 1, 0);
   if (refine) { smax.resize(std::max(npoint, 1)); ssum.resize(std::max(npoint, 1)); }
-  par([&](int tid) {
-    for (long p = lo_of(tid, npoint), e = lo_of(tid + 1, npoint); p < e; ++p) {
+  B.par([&](int tid) {
+    for (long p = B.lo_of(tid, npoint), e = B.lo_of(tid + 1, npoint); p < e; ++p) {
       int tot = 0;
       for (int t = 0; t < T; ++t) { int& c = cnt_t[(size_t)t*npoint + p]; const int v = c; c = tot; tot += v; }
       cnt[p + 1] = tot;
@@ -1180,181 +1382,167 @@ int mcp_ba::prepare() {
       }
     }
   });
-  lap("  counts (threads)");
+}
+
+// which points and poses take part (a point with a measurement, the poses of every chain in use), agreed between the ranks; the
+// free poses numbered in add order
+int mcp_ba::activity(StructBuild& B) {
+  const int npose = B.npose, npoint = B.npoint; const size_t nch = B.nch; const std::vector<int>& cnt = B.cnt; std::vector<unsigned char>& chain_used = B.chain_used;
   for (auto& p : poses) { p.active = 0; p.unk = -1; }
   for (int i = 0; i < npoint; ++i) { points[i].active = cnt[i + 1] > 0; points[i].unk = -1; if (points[i].active) chain_used[points[i].chain] = 1; }
   for (size_t c = 0; c < nch; ++c) if (chain_used[c]) for (int k = 0; k < chains[c].len; ++k) poses[chains[c].v[k]].active = 1;
-  m_total = (double)nmeas;
-  if (multi()) {
-    // ranks hold different measurement shards: agree on the active poses and the global count
-    std::vector<double> flags(npose + 2);
-    for (int i = 0; i < npose; ++i) flags[i] = poses[i].active;
-    flags[npose] = (double)nmeas;
-    double nfree = 0; for (const auto& p : points) if (p.active && !p.fixed) nfree += 1;
-    flags[npose + 1] = nfree;
-    DevBuf<double> tmp;
-    if (tmp.upload(flags, st)) return -1;
-    if (allreduce(tmp.p, flags.size(), 0, true, "set-up: active poses and counts")) return -1;
-    HIPCK(hipMemcpy(flags.data(), tmp.p, flags.size()*sizeof(double), hipMemcpyDeviceToHost));
-    for (int i = 0; i < npose; ++i) poses[i].active = flags[i] > 0;
-    m_total = flags[npose]; nfl_total = flags[npose + 1];
-  }
+  m_total = (double)B.nmeas;
+  if (multi() && agree_activity()) return -1;
   fp_pose.clear(); fl_point.clear();
   for (int i = 0; i < npose; ++i) if (poses[i].active && !poses[i].fixed) { poses[i].unk = (int)fp_pose.size(); fp_pose.push_back(i); }
-  chol_segs.clear();
-  if (want_graph && (int)fp_pose.size() >= 96 && (int)fp_pose.size() <= 1024) {
-    // ---- several chains instead of one (round 6; ba_cut.h has the search).  Here: the coupling graph -- per point the
-    // set of free poses that see or carry it (taken in the counting pass above), every pair of a set an edge.  Fixed points are taken
-    // as coupling their observers too (they do not): a superset only costs separator.  The plan checks the promise against the true
-    // tile pattern (CholPersist::build: chains that couple after all are factorised as one).
-    const int nf = (int)fp_pose.size(), W = (nf + 63)/64;
-    bool windows = true; for (int t = 0; t < T; ++t) windows = windows && !seen_over[t];
-    if (getenv("MCP_BA_TEST_CHOL_ATOMIC")) windows = false;      // (tests: the masks of an add order whose observers do not fit the windows)
-    std::vector<u64> pmask, adj((size_t)nf*W, 0), adj_t((size_t)T*nf*W, 0);
-    const int* mp = meas_point.data(); const int* mc = meas_chain.data();
-    if (!windows) {
-      pmask.assign((size_t)std::max(npoint, 1)*W, 0);
-      par([&](int tid) {
-        for (long i = lo_of(tid, nmeas), e = lo_of(tid + 1, nmeas); i < e; ++i) {
-          const HChain& oc = chains[mc[i]];
-          for (int k = 0; k < oc.len; ++k) { const int u = poses[oc.v[k]].unk; if (u >= 0) __atomic_fetch_or(&pmask[(size_t)mp[i]*W + (u >> 6)], 1ull << (u & 63), __ATOMIC_RELAXED); }
-        }
-      });
-    }
-    lap("  chains: point masks");
-    std::vector<int> unk_of(npose); for (int i = 0; i < npose; ++i) unk_of[i] = poses[i].unk;
-    par([&](int tid) {
-      u64* at = adj_t.data() + (size_t)tid*nf*W; u64 row[16];
-      // (many points are seen by the same poses: a set that was expanded a moment ago is not expanded again -- a small direct-mapped memory of rows)
-      constexpr int RMEM = 512; std::vector<u64> rmem((size_t)RMEM*W, 0);
-      const int* uo = unk_of.data();
-      for (long p = lo_of(tid, npoint), e = lo_of(tid + 1, npoint); p < e; ++p) {
-        if (!points[p].active) continue;
-        if (windows) {
-          for (int k = 0; k < W; ++k) row[k] = 0;
-          for (int t = 0; t < T; ++t) for (u64 m = seen_t[(size_t)t*npoint + p]; m; m &= m - 1) { const int u = uo[seen_ids[(size_t)t*64 + __builtin_ctzll(m)]]; if (u >= 0) row[u >> 6] |= 1ull << (u & 63); }
-        } else for (int k = 0; k < W; ++k) row[k] = pmask[(size_t)p*W + k];
-        const HChain& sc = chains[points[p].chain];
-        for (int k = 0; k < sc.len; ++k) { const int u = uo[sc.v[k]]; if (u >= 0) row[u >> 6] |= 1ull << (u & 63); }
-        u64 h = 0; for (int k = 0; k < W; ++k) h = (h ^ row[k])*0x9e3779b97f4a7c15ull;
-        u64* slot = &rmem[(size_t)(h >> 55)*W];
-        bool same = true; for (int k = 0; k < W; ++k) same = same && slot[k] == row[k];
-        if (same) continue;
-        for (int k = 0; k < W; ++k) slot[k] = row[k];
-        for (int k = 0; k < W; ++k) for (u64 m = row[k]; m; m &= m - 1) { u64* a = at + (size_t)(64*k + __builtin_ctzll(m))*W; for (int q = 0; q < W; ++q) a[q] |= row[q]; }
+  return 0;
+}
+
+static void trace_cut(const PoseCut& cut, int nf);
+// ---- several chains instead of one (round 6; ba_cut.h has the search): the coupling graph of the free poses, its cut,
+// the free poses renumbered chain by chain
+int mcp_ba::pose_cut_order(StructBuild& B) {
+  if (!(B.want_graph && (int)fp_pose.size() >= 96 && (int)fp_pose.size() <= 1024)) return 0;
+  const int nf = (int)fp_pose.size(), W = (nf + 63)/64;
+  std::vector<u64> adj((size_t)nf*W, 0);
+  if (coupling_graph(B, adj)) return -1;
+  PoseCut cut;
+  pose_cut(adj, nf, chain_arcs, B.T, [&](const std::function<void(int)>& fn) { B.par(fn); }, [&](const char* what) { B.lap(what); }, cut);
+  if (cut.relabelled || cut.taken) {
+    std::vector<int> fp2(nf);
+    for (int i = 0; i < nf; ++i) fp2[i] = fp_pose[cut.order[i]];
+    fp_pose.swap(fp2);
+    for (int u = 0; u < nf; ++u) poses[fp_pose[u]].unk = u;
+  }
+  chol_segs = cut.segs;
+  if (cut.taken) { const char* e = getenv("MCP_BA_TEST_CHOL_CUT"); if (e) chol_segs[1] = std::max(3, chol_segs[1] - atoi(e)); }      // (tests: the cut between the chains moved into the first one -- chains that couple: the plan must notice)
+  if (B.lap.trace) trace_cut(cut, nf);
+  B.lap("  pose order (chains)");
+  return 0;
+}
+
+// The coupling graph -- per point the set of free poses that see or carry it (taken in the counting pass), every pair of a set an
+// edge.  Fixed points are taken as coupling their observers too (they do not): a superset only costs separator.  The plan checks the
+// promise against the true tile pattern (CholPersist::build: chains that couple after all are factorised as one).
+int mcp_ba::coupling_graph(StructBuild& B, std::vector<u64>& adj) {
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas, T = B.T; const u64* const seen_t = B.seen_t; const std::vector<int>& seen_ids = B.seen_ids;
+  const int nf = (int)fp_pose.size(), W = (nf + 63)/64;
+  bool windows = true; for (int t = 0; t < T; ++t) windows = windows && !B.seen_over[t];
+  if (getenv("MCP_BA_TEST_CHOL_ATOMIC")) windows = false;      // (tests: the masks of an add order whose observers do not fit the windows)
+  std::vector<u64> pmask, adj_t((size_t)T*nf*W, 0);
+  const int* mp = meas_point.data(); const int* mc = meas_chain.data();
+  if (!windows) {
+    pmask.assign((size_t)std::max(npoint, 1)*W, 0);
+    B.par([&](int tid) {
+      for (long i = B.lo_of(tid, nmeas), e = B.lo_of(tid + 1, nmeas); i < e; ++i) {
+        const HChain& oc = chains[mc[i]];
+        for (int k = 0; k < oc.len; ++k) { const int u = poses[oc.v[k]].unk; if (u >= 0) __atomic_fetch_or(&pmask[(size_t)mp[i]*W + (u >> 6)], 1ull << (u & 63), __ATOMIC_RELAXED); }
       }
     });
-    for (int t = 0; t < T; ++t) for (size_t i = 0; i < adj.size(); ++i) adj[i] |= adj_t[(size_t)t*nf*W + i];
-    if (multi()) {
-      // ranks hold different shards of the measurements: the union of their graphs, so that every rank finds the same cut
-      std::vector<double> bits((size_t)nf*nf);
-      for (int u = 0; u < nf; ++u) for (int v = 0; v < nf; ++v) bits[(size_t)u*nf + v] = (double)((adj[(size_t)u*W + (v >> 6)] >> (v & 63)) & 1);
-      DevBuf<double> tmp;
-      if (tmp.upload(bits, st)) return -1;
-      if (allreduce(tmp.p, bits.size(), 0, true, "set-up: pose coupling graph")) return -1;
-      HIPCK(hipMemcpy(bits.data(), tmp.p, bits.size()*sizeof(double), hipMemcpyDeviceToHost));
-      for (int u = 0; u < nf; ++u) for (int v = 0; v < nf; ++v) if (bits[(size_t)u*nf + v] > 0) adj[(size_t)u*W + (v >> 6)] |= 1ull << (v & 63);
-    }
-    for (int u = 0; u < nf; ++u) adj[(size_t)u*W + (u >> 6)] &= ~(1ull << (u & 63));
-    PoseCut cut;
-    pose_cut(adj, nf, chain_arcs, T, par, [&](const char* what) { lap(what); }, cut);
-    if (cut.relabelled || cut.taken) {
-      std::vector<int> fp2(nf);
-      for (int i = 0; i < nf; ++i) fp2[i] = fp_pose[cut.order[i]];
-      fp_pose.swap(fp2);
-      for (int u = 0; u < nf; ++u) poses[fp_pose[u]].unk = u;
-    }
-    chol_segs = cut.segs;
-    if (cut.taken) { const char* e = getenv("MCP_BA_TEST_CHOL_CUT"); if (e) chol_segs[1] = std::max(3, chol_segs[1] - atoi(e)); }      // (tests: the cut between the chains moved into the first one -- chains that couple: the plan must notice)
-    if (trace) {
-      if (cut.looked_at_order) fprintf(stderr, "[mcp_ba prepare]   chains: couplings %.1f poses apart in add order, %.1f breadth-first -> %s\n", cut.dist_add, cut.dist_cm, cut.relabelled ? "relabelled" : "add order kept");
-      if (cut.found) { char arcs[192]; int o = 0; for (int i = 0; i < cut.k; ++i) o += snprintf(arcs + o, sizeof arcs - o, "%s%d", i ? " + " : "", cut.arc_len[i]);
-        fprintf(stderr, "[mcp_ba prepare]   chains: %d free poses; ring opened at %d, %d arcs of %s poses, gaps of %d (%d), separator %d (%d of them for what still coupled the arcs): %d block columns on the longest path of %d -> %s\n",
-                nf, cut.r, cut.k, arcs, cut.g_first, cut.g_last, cut.sep, cut.ncover, cut.steps, cut.t_all, cut.taken ? "chains + the separator's" : "one chain"); }
-      else fprintf(stderr, "[mcp_ba prepare]   chains: %d free poses; no cut found -> one chain\n", nf);
-    }
-    lap("  pose order (chains)");
   }
-  for (int i = 0; i < npoint; ++i) if (points[i].active && !points[i].fixed) { points[i].unk = (int)fl_point.size(); fl_point.push_back(i); }
+  B.lap("  chains: point masks");
+  std::vector<int> unk_of(npose); for (int i = 0; i < npose; ++i) unk_of[i] = poses[i].unk;
+  B.par([&](int tid) {
+    u64* at = adj_t.data() + (size_t)tid*nf*W; u64 row[16];
+    // (many points are seen by the same poses: a set that was expanded a moment ago is not expanded again -- a small direct-mapped memory of rows)
+    constexpr int RMEM = 512; std::vector<u64> rmem((size_t)RMEM*W, 0);
+    const int* uo = unk_of.data();
+    for (long p = B.lo_of(tid, npoint), e = B.lo_of(tid + 1, npoint); p < e; ++p) {
+      if (!points[p].active) continue;
+      if (windows) {
+        for (int k = 0; k < W; ++k) row[k] = 0;
+        for (int t = 0; t < T; ++t) for (u64 m = seen_t[(size_t)t*npoint + p]; m; m &= m - 1) { const int u = uo[seen_ids[(size_t)t*64 + __builtin_ctzll(m)]]; if (u >= 0) row[u >> 6] |= 1ull << (u & 63); }
+      } else for (int k = 0; k < W; ++k) row[k] = pmask[(size_t)p*W + k];
+      const HChain& sc = chains[points[p].chain];
+      for (int k = 0; k < sc.len; ++k) { const int u = uo[sc.v[k]]; if (u >= 0) row[u >> 6] |= 1ull << (u & 63); }
+      u64 h = 0; for (int k = 0; k < W; ++k) h = (h ^ row[k])*0x9e3779b97f4a7c15ull;
+      u64* slot = &rmem[(size_t)(h >> 55)*W];
+      bool same = true; for (int k = 0; k < W; ++k) same = same && slot[k] == row[k];
+      if (same) continue;
+      for (int k = 0; k < W; ++k) slot[k] = row[k];
+      for (int k = 0; k < W; ++k) for (u64 m = row[k]; m; m &= m - 1) { u64* a = at + (size_t)(64*k + __builtin_ctzll(m))*W; for (int q = 0; q < W; ++q) a[q] |= row[q]; }
+    }
+  });
+  for (int t = 0; t < T; ++t) for (size_t i = 0; i < adj.size(); ++i) adj[i] |= adj_t[(size_t)t*nf*W + i];
+  if (multi()) {
+    // ranks hold different shards of the measurements: the union of their graphs, so that every rank finds the same cut
+    std::vector<double> bits((size_t)nf*nf);
+    for (int u = 0; u < nf; ++u) for (int v = 0; v < nf; ++v) bits[(size_t)u*nf + v] = (double)((adj[(size_t)u*W + (v >> 6)] >> (v & 63)) & 1);
+    if (agree(bits, "set-up: pose coupling graph")) return -1;
+    for (int u = 0; u < nf; ++u) for (int v = 0; v < nf; ++v) if (bits[(size_t)u*nf + v] > 0) adj[(size_t)u*W + (v >> 6)] |= 1ull << (v & 63);
+  }
+  for (int u = 0; u < nf; ++u) adj[(size_t)u*W + (u >> 6)] &= ~(1ull << (u & 63));
+  return 0;
+}
+
+static void trace_cut(const PoseCut& cut, int nf) {
+  if (cut.looked_at_order) fprintf(stderr, "[mcp_ba prepare]   chains: couplings %.1f poses apart in add order, %.1f breadth-first -> %s\n", cut.dist_add, cut.dist_cm, cut.relabelled ? "relabelled" : "add order kept");
+  if (cut.found) { char arcs[192]; int o = 0; for (int i = 0; i < cut.k; ++i) o += snprintf(arcs + o, sizeof arcs - o, "%s%d", i ? " + " : "", cut.arc_len[i]);
+    fprintf(stderr, "[mcp_ba prepare]   chains: %d free poses; ring opened at %d, %d arcs of %s poses, gaps of %d (%d), separator %d (%d of them for what still coupled the arcs): %d block columns on the longest path of %d -> %s\n",
+            nf, cut.r, cut.k, arcs, cut.g_first, cut.g_last, cut.sep, cut.ncover, cut.steps, cut.t_all, cut.taken ? "chains + the separator's" : "one chain"); }
+  else fprintf(stderr, "[mcp_ba prepare]   chains: %d free poses; no cut found -> one chain\n", nf);
+}
+
+// the free points numbered, the sizes of the system; refused here if the reduced system is larger than the dense solver takes
+int mcp_ba::number_unknowns(StructBuild& B) {
+  for (int i = 0; i < B.npoint; ++i) if (points[i].active && !points[i].fixed) { points[i].unk = (int)fl_point.size(); fl_point.push_back(i); }
   nfp = (int)fp_pose.size(); nfl = (int)fl_point.size(); np = 6*nfp; nx = np + 3*nfl;
-  if (np > CH_SOLVE_MAX) { set_err("too many free poses for the dense reduced solve (6P > 6144)"); return -1; }
+  if (too_many_free_poses()) return -1;
   if (!multi()) nfl_total = nfl;
-  lap("activity");
+  B.lap("activity");
+  return 0;
+}
+
+// ---- point order: by the first free pose of the chain the point is expressed in (counting sort: stable)
+void mcp_ba::point_order(StructBuild& B) {
+  const int npoint = B.npoint; const bool refine = B.refine; std::vector<int>& cnt = B.cnt; std::vector<int>& order = B.order; const std::vector<int>& smax = B.smax; const std::vector<int>& ssum = B.ssum;
   for (int i = 0; i < npoint; ++i) cnt[i + 1] += cnt[i];        // measurements by point (add order kept inside a point): ranges
-  // ---- point order: by the first free pose of the chain the point is expressed in (counting sort: stable)
-  std::vector<int> order;
-  {
-    std::vector<int> pkey(npoint, -1), kc(nfp + 2, 0);
-    for (int i = 0; i < npoint; ++i) {
-      if (!points[i].active) continue;
-      const HChain& c = chains[points[i].chain];
-      int key = nfp;
-      for (int k = 0; k < c.len; ++k) if (poses[c.v[k]].unk >= 0) { key = poses[c.v[k]].unk; break; }
-      pkey[i] = key; kc[key + 1]++;
-    }
-    for (int k = 0; k <= nfp; ++k) kc[k + 1] += kc[k];
-    order.resize(kc[nfp + 1]);
-    for (int i = 0; i < npoint; ++i) if (pkey[i] >= 0) order[kc[pkey[i]]++] = i;
-    // ... and inside a pose by which poses see the point (refine_point_order; its keys were taken in the counting pass): buckets sorted
-    // by ranges of the pool (kc[k] is now the end of bucket k: thread ranges cut at bucket boundaries)
-    if (refine) {
-      par([&](int tid) {
-        const int k0 = (int)lo_of(tid, nfp + 1), k1 = (int)lo_of(tid + 1, nfp + 1);
-        const size_t i0 = k0 ? (size_t)kc[k0 - 1] : 0, i1 = k1 ? (size_t)kc[k1 - 1] : 0;
-        refine_point_order(order, pkey, smax.data(), ssum.data(), i0, i1);
-      });
-    }
+  std::vector<int> pkey(npoint, -1), kc(nfp + 2, 0);
+  for (int i = 0; i < npoint; ++i) {
+    if (!points[i].active) continue;
+    const HChain& c = chains[points[i].chain];
+    int key = nfp;
+    for (int k = 0; k < c.len; ++k) if (poses[c.v[k]].unk >= 0) { key = poses[c.v[k]].unk; break; }
+    pkey[i] = key; kc[key + 1]++;
+  }
+  for (int k = 0; k <= nfp; ++k) kc[k + 1] += kc[k];
+  order.resize(kc[nfp + 1]);
+  for (int i = 0; i < npoint; ++i) if (pkey[i] >= 0) order[kc[pkey[i]]++] = i;
+  // ... and inside a pose by which poses see the point (refine_point_order; its keys were taken in the counting pass): buckets sorted
+  // by ranges of the pool (kc[k] is now the end of bucket k: thread ranges cut at bucket boundaries)
+  if (refine) {
+    B.par([&](int tid) {
+      const int k0 = (int)B.lo_of(tid, nfp + 1), k1 = (int)B.lo_of(tid + 1, nfp + 1);
+      const size_t i0 = k0 ? (size_t)kc[k0 - 1] : 0, i1 = k1 ? (size_t)kc[k1 - 1] : 0;
+      refine_point_order(order, pkey, smax.data(), ssum.data(), i0, i1);
+    });
   }
   nsp = (int)order.size();
-  lap("  point order");
-  // per (obs chain, src chain) activity mask, memoised in a dense table (chains are few: P*C for the Multi adapter)
-  const bool dense_table = nch <= 4096;
-  // (entries are written concurrently by the structure threads below: every writer stores the same value, relaxed atomics)
-  std::unique_ptr<std::atomic<unsigned short>[]> mask_table(dense_table ? new std::atomic<unsigned short>[nch*nch] : nullptr);
-  static_assert(sizeof(std::atomic<unsigned short>) == 2, "mask table is filled bytewise");
-  if (dense_table) std::memset(static_cast<void*>(mask_table.get()), 0xff, nch*nch*sizeof(unsigned short));      // (no thread reads it before the pool starts)
-  std::map<std::pair<int, int>, unsigned short> mask_cache;
-  std::mutex mask_mutex;
-  auto compute_mask = [&](int oc, int sc) -> unsigned short {
-    unsigned short mk = 0;
-    const HChain& o = chains[oc]; const HChain& s2 = chains[sc];
-    for (int i = 0; i < o.len; ++i) if (!poses[o.v[i]].fixed && !move_together(o, s2, i)) mk |= (1 << i);
-    for (int i = 0; i < s2.len; ++i) if (!poses[s2.v[i]].fixed && !move_together(s2, o, i)) mk |= (1 << (MAXC + i));
-    return mk;
-  };
-  auto pair_mask = [&](int oc, int sc) -> unsigned short {
-    if (dense_table) {
-      std::atomic<unsigned short>& e = mask_table[(size_t)oc*nch + sc];
-      unsigned short v = e.load(std::memory_order_relaxed);
-      if (v == 0xffff) { v = compute_mask(oc, sc); e.store(v, std::memory_order_relaxed); }
-      return v;
-    }
-    std::lock_guard<std::mutex> lk(mask_mutex);
-    auto key = std::make_pair(oc, sc);
-    auto it = mask_cache.find(key);
-    if (it != mask_cache.end()) return it->second;
-    const unsigned short mk = compute_mask(oc, sc);
-    mask_cache[key] = mk; return mk;
-  };
-  std::unique_lock<std::mutex> arena_lock(pinned_arena().mutex());
-  ArenaGuard arena_guard{st};
-  HostStruct H;
+  B.lap("  point order");
+}
+
+// ---- every measurement to its final position, a range of the add order per thread (sequential reads, one scattered 40-byte
+// write each; the reference's adapters add measurements KeyFrame by KeyFrame, so a point's measurements lie far apart).
+// Measurements of a point are stored rotated by the point's position: neighbouring points (= neighbouring lanes of
+// k_linearize_group) share their observers, and walking the lists in the same order makes all lanes add to the same
+// LDS tile entries at the same time; a per-lane rotation spreads them over the observers.
+void mcp_ba::scatter_by_point(StructBuild& B) {
+  const int npoint = B.npoint, nmeas = B.nmeas; int* const cnt_t = B.cnt_t; SMeas* const sorted = B.sorted;
+  const std::vector<int>& cnt = B.cnt; const std::vector<int>& order = B.order; std::vector<int>& sp_of = B.sp_of;
+  B.pair_mask.reset(new PairMasks(*this));
+  B.hold_arena(st);
+  HostStruct& H = B.H;
   H.m_pt.resize(nmeas); H.m_chain.resize(nmeas); H.m_sp.resize(nmeas); H.slot_start.resize(nmeas + 1);
   H.m_cam.resize(nmeas); H.m_mask.resize(nmeas); H.m_u.resize(nmeas); H.m_v.resize(nmeas); H.m_om.resize(nmeas);
   H.l_i0.assign(nfl + 1, 0); H.l_i1.assign(nfl + 1, 0); H.l_sp.assign(nfl + 1, 0);
   H.sp_pt.resize(nsp); H.sp_m.assign(nsp + 1, 0); H.sp_i.assign(nsp + 1, 0); H.sp_big.assign(nsp, 0);
   perm.assign(nmeas, 0);
-  lap("  host arrays");
-  std::vector<int> sp_of(std::max(npoint, 1), -1);
+  B.lap("  host arrays");
+  sp_of.assign(std::max(npoint, 1), -1);
   for (int sp = 0; sp < nsp; ++sp) { H.sp_m[sp + 1] = H.sp_m[sp] + (cnt[order[sp] + 1] - cnt[order[sp]]); sp_of[order[sp]] = sp; }
-  // ---- every measurement to its final position, a range of the add order per thread (sequential reads, one scattered 40-byte
-  // write each; the reference's adapters add measurements KeyFrame by KeyFrame, so a point's measurements lie far apart).
-  // Measurements of a point are stored rotated by the point's position: neighbouring points (= neighbouring lanes of
-  // k_linearize_group) share their observers, and walking the lists in the same order makes all lanes add to the same
-  // LDS tile entries at the same time; a per-lane rotation spreads them over the observers.
-  par([&](int tid) {
+  B.par([&](int tid) {
     int* ct = cnt_t + (size_t)tid*npoint; const int* mp = meas_point.data(); const int* smp = H.sp_m.data();
-    for (long i = lo_of(tid, nmeas), e = lo_of(tid + 1, nmeas); i < e; ++i) {
+    for (long i = B.lo_of(tid, nmeas), e = B.lo_of(tid + 1, nmeas); i < e; ++i) {
       const int p = mp[i], r = ct[p]++, sp = sp_of[p], nm = cnt[p + 1] - cnt[p];
       int kk = (r - sp) % nm; if (kk < 0) kk += nm;                    // rank r sits at slot kk with (kk + sp) % nm == r
       const HMeas& m = meas[i];
@@ -1362,16 +1550,19 @@ int mcp_ba::prepare() {
       o.chain = m.chain; o.cam = m.cam; o.mi = (int)i; o.u = m.u; o.v = m.v; o.omega = m.omega;
     }
   });
-  lap("  by point, order");
-  // ---- slots, incidences and the poses of every point: contiguous ranges of sorted points per thread (balanced by measurement
-  // count), each into its own arrays with range-relative indices; concatenated below with the offsets fixed up
-  std::vector<unsigned char> cov((size_t)std::max(nfp, 1)*std::max(nfp, 1), 0);        // pose-pair co-visibility, a >= b
-  struct Chunk { int sp0 = 0, sp1 = 0; std::vector<int> slot_unk, slot_inc, inc_unk, slot_cnt, sp_ninc, q_n, q_data; std::vector<unsigned char> slot_first, inc_state; };
+  B.lap("  by point, order");
+}
+
+// ---- slots, incidences and the poses of every point: contiguous ranges of sorted points per thread (balanced by measurement
+// count), each into its own arrays with range-relative indices; concat_slots() puts them together with the offsets fixed up
+void mcp_ba::build_slots(StructBuild& B) {
+  const int nmeas = B.nmeas, T = B.T; HostStruct& H = B.H; std::vector<SlotChunk>& chunks = B.chunks;
+  B.cov.assign((size_t)std::max(nfp, 1)*std::max(nfp, 1), 0);
   // (eight chunks per thread (MCP_BA_PREP_CHUNKS), claimed one after the other: equal measurement counts are not equal times -- 1.0 to 1.6 ms per thread
-  //  at the metric size with one chunk each -- and the concatenation below is by chunk index, so who built a chunk changes nothing)
+  //  at the metric size with one chunk each -- and the concatenation is by chunk index, so who built a chunk changes nothing)
   static const int chunks_per_thread = [] { const char* e = getenv("MCP_BA_PREP_CHUNKS"); return e ? std::max(1, atoi(e)) : 8; }();
   const int NC = T > 1 ? chunks_per_thread*T : 1;
-  std::vector<Chunk> chunks(NC);
+  chunks.assign(NC, SlotChunk());
   const avec<int>& sp_m = H.sp_m;
   for (int t = 0; t < NC; ++t) {
     const long m0 = (long)nmeas*t/NC, m1 = (long)nmeas*(t + 1)/NC;
@@ -1380,154 +1571,146 @@ int mcp_ba::prepare() {
   }
   std::vector<double> thr_ms(T, 0.0);
   std::atomic<int> next_chunk{0};
-  par([&](int tid) {
+  B.par([&](int tid) {
     const auto tt0 = std::chrono::steady_clock::now();
     struct Stamp { double* d; std::chrono::steady_clock::time_point t; ~Stamp() { *d = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); } } stamp_{&thr_ms[tid], tt0};
-    for (int ci; (ci = next_chunk.fetch_add(1, std::memory_order_relaxed)) < NC;) {
-    Chunk& C = chunks[ci];
-    const size_t nm_chunk = (size_t)(sp_m[C.sp1] - sp_m[C.sp0]);
-    C.slot_unk.reserve(nm_chunk*2 + 16); C.slot_inc.reserve(nm_chunk*2 + 16); C.slot_first.reserve(nm_chunk*2 + 16);
-    C.inc_unk.reserve(nm_chunk + 16); C.inc_state.reserve(nm_chunk + 16); C.q_data.reserve(nm_chunk + 16);
-    C.sp_ninc.assign(C.sp1 - C.sp0, 0); C.q_n.assign(C.sp1 - C.sp0, 0); C.slot_cnt.assign(nm_chunk, 0);
-    std::vector<int> q; q.reserve(64);
-    unsigned char* covp = cov.data();
-    for (int sp = C.sp0; sp < C.sp1; ++sp) {
-      const int pt = order[sp];
-      const int lpt = points[pt].unk, pch = points[pt].chain;
-      const HChain& sc = chains[pch];
-      const int ibase = (int)C.inc_unk.size();
-      H.sp_pt[sp] = pt;
-      q.clear();
-      const int nm_pt = cnt[pt + 1] - cnt[pt];
-      int j = sp_m[sp];
-      for (int kk = 0; kk < nm_pt; ++kk, ++j) {
-        const SMeas& m = sorted[j];
-        perm[j] = m.mi;
-        H.m_pt[j] = pt; H.m_chain[j] = m.chain; H.m_cam[j] = (unsigned char)m.cam; H.m_u[j] = m.u; H.m_v[j] = m.v; H.m_om[j] = m.omega; H.m_sp[j] = sp;
-        const unsigned short mk = pair_mask(m.chain, pch);
-        H.m_mask[j] = mk;
-        int nsl = 0;
-        const HChain& oc = chains[m.chain];
-        for (unsigned bits = mk; bits; bits &= bits - 1) {
-          const int b = __builtin_ctz(bits);
-          const HChain& c = (b < MAXC) ? oc : sc;
-          const int u = poses[c.v[b & (MAXC - 1)]].unk;
-          C.slot_unk.push_back(u); ++nsl;
-          if (std::find(q.begin(), q.end(), u) == q.end()) q.push_back(u);
-          // slot_first: first contribution to its W block among the slots that write it through memory (every slot but
-          // the first source link, whose block is kept in registers by k_linearize_group); inc_mixed: both kinds occur
-          int inc = -1; unsigned char first = 0;
-          if (lpt >= 0) {
-            for (int t2 = ibase; t2 < (int)C.inc_unk.size(); ++t2) if (C.inc_unk[t2] == u) { inc = t2; break; }
-            if (inc < 0) { inc = (int)C.inc_unk.size(); C.inc_unk.push_back(u); C.inc_state.push_back(0); }
-            if (b == MAXC) C.inc_state[inc] |= 1;
-            else { if (!(C.inc_state[inc] & 2)) first = 1; C.inc_state[inc] |= 2; }
-          }
-          C.slot_inc.push_back(inc); C.slot_first.push_back(first);
+    for (int ci; (ci = next_chunk.fetch_add(1, std::memory_order_relaxed)) < NC;) build_slot_chunk(B, chunks[ci]);
+  });
+  B.lap("  slot threads");
+  if (B.lap.trace) { fprintf(stderr, "[mcp_ba prepare]   per-thread ms:"); for (double v : thr_ms) fprintf(stderr, " %.2f", v); fprintf(stderr, "\n"); }
+}
+
+void mcp_ba::build_slot_chunk(StructBuild& B, SlotChunk& C) {
+  HostStruct& H = B.H; const avec<int>& sp_m = H.sp_m; const std::vector<int>& order = B.order; const std::vector<int>& cnt = B.cnt;
+  const SMeas* const sorted = B.sorted; PairMasks& pair_mask = *B.pair_mask;
+  const size_t nm_chunk = (size_t)(sp_m[C.sp1] - sp_m[C.sp0]);
+  C.slot_unk.reserve(nm_chunk*2 + 16); C.slot_inc.reserve(nm_chunk*2 + 16); C.slot_first.reserve(nm_chunk*2 + 16);
+  C.inc_unk.reserve(nm_chunk + 16); C.inc_state.reserve(nm_chunk + 16); C.q_data.reserve(nm_chunk + 16);
+  C.sp_ninc.assign(C.sp1 - C.sp0, 0); C.q_n.assign(C.sp1 - C.sp0, 0); C.slot_cnt.assign(nm_chunk, 0);
+  std::vector<int> q; q.reserve(64);
+  unsigned char* covp = B.cov.data();
+  for (int sp = C.sp0; sp < C.sp1; ++sp) {
+    const int pt = order[sp];
+    const int lpt = points[pt].unk, pch = points[pt].chain;
+    const HChain& sc = chains[pch];
+    const int ibase = (int)C.inc_unk.size();
+    H.sp_pt[sp] = pt;
+    q.clear();
+    const int nm_pt = cnt[pt + 1] - cnt[pt];
+    int j = sp_m[sp];
+    for (int kk = 0; kk < nm_pt; ++kk, ++j) {
+      const SMeas& m = sorted[j];
+      perm[j] = m.mi;
+      H.m_pt[j] = pt; H.m_chain[j] = m.chain; H.m_cam[j] = (unsigned char)m.cam; H.m_u[j] = m.u; H.m_v[j] = m.v; H.m_om[j] = m.omega; H.m_sp[j] = sp;
+      const unsigned short mk = pair_mask(m.chain, pch);
+      H.m_mask[j] = mk;
+      int nsl = 0;
+      const HChain& oc = chains[m.chain];
+      for (unsigned bits = mk; bits; bits &= bits - 1) {
+        const int b = __builtin_ctz(bits);
+        const HChain& c = (b < MAXC) ? oc : sc;
+        const int u = poses[c.v[b & (MAXC - 1)]].unk;
+        C.slot_unk.push_back(u); ++nsl;
+        if (std::find(q.begin(), q.end(), u) == q.end()) q.push_back(u);
+        // slot_first: first contribution to its W block among the slots that write it through memory (every slot but
+        // the first source link, whose block is kept in registers by k_linearize_group); inc_mixed: both kinds occur
+        int inc = -1; unsigned char first = 0;
+        if (lpt >= 0) {
+          for (int t2 = ibase; t2 < (int)C.inc_unk.size(); ++t2) if (C.inc_unk[t2] == u) { inc = t2; break; }
+          if (inc < 0) { inc = (int)C.inc_unk.size(); C.inc_unk.push_back(u); C.inc_state.push_back(0); }
+          if (b == MAXC) C.inc_state[inc] |= 1;
+          else { if (!(C.inc_state[inc] & 2)) first = 1; C.inc_state[inc] |= 2; }
         }
-        C.slot_cnt[j - sp_m[C.sp0]] = nsl;
+        C.slot_inc.push_back(inc); C.slot_first.push_back(first);
       }
-      C.sp_ninc[sp - C.sp0] = (int)C.inc_unk.size() - ibase;
-      C.q_n[sp - C.sp0] = (int)q.size();
-      C.q_data.insert(C.q_data.end(), q.begin(), q.end());
-      if ((int)q.size() > GRP_LMAX) H.sp_big[sp] = 1;
-      for (int a : q) for (int b2 : q) if (a >= b2 && !__atomic_load_n(covp + (size_t)a*nfp + b2, __ATOMIC_RELAXED)) __atomic_store_n(covp + (size_t)a*nfp + b2, (unsigned char)1, __ATOMIC_RELAXED);
+      C.slot_cnt[j - sp_m[C.sp0]] = nsl;
+    }
+    C.sp_ninc[sp - C.sp0] = (int)C.inc_unk.size() - ibase;
+    C.q_n[sp - C.sp0] = (int)q.size();
+    C.q_data.insert(C.q_data.end(), q.begin(), q.end());
+    if ((int)q.size() > GRP_LMAX) H.sp_big[sp] = 1;
+    for (int a : q) for (int b2 : q) if (a >= b2 && !__atomic_load_n(covp + (size_t)a*nfp + b2, __ATOMIC_RELAXED)) __atomic_store_n(covp + (size_t)a*nfp + b2, (unsigned char)1, __ATOMIC_RELAXED);
+  }
+}
+
+// the chunks' arrays one behind the other, chunk by chunk on the pool, range-relative indices made global
+void mcp_ba::concat_slots(StructBuild& B) {
+  const int nmeas = B.nmeas, NC = (int)B.chunks.size(); HostStruct& H = B.H; const avec<int>& sp_m = H.sp_m; const std::vector<SlotChunk>& chunks = B.chunks;
+  const std::vector<int>& order = B.order; std::vector<int>& sp_q0 = B.sp_q0; std::vector<int>& sp_q = B.sp_q; std::vector<unsigned char>& inc_state = B.inc_state;
+  sp_q0.assign(nsp + 1, 0);
+  std::vector<size_t> soff(NC + 1, 0), ioff(NC + 1, 0), qoff(NC + 1, 0);
+  for (int t = 0; t < NC; ++t) { soff[t + 1] = soff[t] + chunks[t].slot_unk.size(); ioff[t + 1] = ioff[t] + chunks[t].inc_unk.size(); qoff[t + 1] = qoff[t] + chunks[t].q_data.size(); }
+  H.slot_unk.resize(soff[NC]); H.slot_inc.resize(soff[NC]); H.slot_first.resize(soff[NC]); H.inc_unk.resize(ioff[NC]); inc_state.resize(ioff[NC]); sp_q.resize(qoff[NC]);
+  std::atomic<int> next_chunk{0};
+  B.par([&](int) {
+    for (int tid; (tid = next_chunk.fetch_add(1, std::memory_order_relaxed)) < NC;) {
+    const SlotChunk& C = chunks[tid];
+    const int io = (int)ioff[tid];
+    int so = (int)soff[tid];
+    for (int j = sp_m[C.sp0]; j < sp_m[C.sp1]; ++j) { H.slot_start[j] = so; so += C.slot_cnt[j - sp_m[C.sp0]]; }
+    if (!C.slot_unk.empty()) {
+      std::memcpy(&H.slot_unk[soff[tid]], C.slot_unk.data(), C.slot_unk.size()*sizeof(int));
+      std::memcpy(&H.slot_first[soff[tid]], C.slot_first.data(), C.slot_first.size());
+      int* d = &H.slot_inc[soff[tid]];
+      for (size_t k = 0; k < C.slot_inc.size(); ++k) d[k] = C.slot_inc[k] < 0 ? -1 : C.slot_inc[k] + io;
+    }
+    if (!C.inc_unk.empty()) { std::memcpy(&H.inc_unk[ioff[tid]], C.inc_unk.data(), C.inc_unk.size()*sizeof(int)); std::memcpy(&inc_state[ioff[tid]], C.inc_state.data(), C.inc_state.size()); }
+    if (!C.q_data.empty()) std::memcpy(&sp_q[qoff[tid]], C.q_data.data(), C.q_data.size()*sizeof(int));
+    int ib = io, qb = (int)qoff[tid];
+    for (int sp = C.sp0; sp < C.sp1; ++sp) {
+      H.sp_i[sp] = ib; sp_q0[sp] = qb;
+      const int lpt = points[order[sp]].unk;
+      if (lpt >= 0) { H.l_i0[lpt] = ib; H.l_i1[lpt] = ib + C.sp_ninc[sp - C.sp0]; H.l_sp[lpt] = sp; }
+      ib += C.sp_ninc[sp - C.sp0]; qb += C.q_n[sp - C.sp0];
     }
     }
   });
-  lap("  slot threads");
-  if (trace) { fprintf(stderr, "[mcp_ba prepare]   per-thread ms:"); for (double v : thr_ms) fprintf(stderr, " %.2f", v); fprintf(stderr, "\n"); }
-  std::vector<int> sp_q0(nsp + 1, 0), sp_q;           // distinct pose unknowns touched by every sorted point
-  std::vector<unsigned char> inc_state;
-  {
-    std::vector<size_t> soff(NC + 1, 0), ioff(NC + 1, 0), qoff(NC + 1, 0);
-    for (int t = 0; t < NC; ++t) { soff[t + 1] = soff[t] + chunks[t].slot_unk.size(); ioff[t + 1] = ioff[t] + chunks[t].inc_unk.size(); qoff[t + 1] = qoff[t] + chunks[t].q_data.size(); }
-    H.slot_unk.resize(soff[NC]); H.slot_inc.resize(soff[NC]); H.slot_first.resize(soff[NC]); H.inc_unk.resize(ioff[NC]); inc_state.resize(ioff[NC]); sp_q.resize(qoff[NC]);
-    next_chunk.store(0);
-    par([&](int) {
-      for (int tid; (tid = next_chunk.fetch_add(1, std::memory_order_relaxed)) < NC;) {
-      const Chunk& C = chunks[tid];
-      const int io = (int)ioff[tid];
-      int so = (int)soff[tid];
-      for (int j = sp_m[C.sp0]; j < sp_m[C.sp1]; ++j) { H.slot_start[j] = so; so += C.slot_cnt[j - sp_m[C.sp0]]; }
-      if (!C.slot_unk.empty()) {
-        std::memcpy(&H.slot_unk[soff[tid]], C.slot_unk.data(), C.slot_unk.size()*sizeof(int));
-        std::memcpy(&H.slot_first[soff[tid]], C.slot_first.data(), C.slot_first.size());
-        int* d = &H.slot_inc[soff[tid]];
-        for (size_t k = 0; k < C.slot_inc.size(); ++k) d[k] = C.slot_inc[k] < 0 ? -1 : C.slot_inc[k] + io;
-      }
-      if (!C.inc_unk.empty()) { std::memcpy(&H.inc_unk[ioff[tid]], C.inc_unk.data(), C.inc_unk.size()*sizeof(int)); std::memcpy(&inc_state[ioff[tid]], C.inc_state.data(), C.inc_state.size()); }
-      if (!C.q_data.empty()) std::memcpy(&sp_q[qoff[tid]], C.q_data.data(), C.q_data.size()*sizeof(int));
-      int ib = io, qb = (int)qoff[tid];
-      for (int sp = C.sp0; sp < C.sp1; ++sp) {
-        H.sp_i[sp] = ib; sp_q0[sp] = qb;
-        const int lpt = points[order[sp]].unk;
-        if (lpt >= 0) { H.l_i0[lpt] = ib; H.l_i1[lpt] = ib + C.sp_ninc[sp - C.sp0]; H.l_sp[lpt] = sp; }
-        ib += C.sp_ninc[sp - C.sp0]; qb += C.q_n[sp - C.sp0];
-      }
-      }
-    });
-    sp_q0[nsp] = (int)qoff[NC];
-    H.sp_i[nsp] = (int)ioff[NC];
-    H.slot_start[nmeas] = (int)soff[NC];
-  }
+  sp_q0[nsp] = (int)qoff[NC];
+  H.sp_i[nsp] = (int)ioff[NC];
+  H.slot_start[nmeas] = (int)soff[NC];
   ninc = (int)H.inc_unk.size(); nslot = (int)H.slot_unk.size();
-  lap("sort+slots");
-  // ---- groups: consecutive points, <= grp_pts points and <= GRP_LMAX distinct poses (greedy, in order).  A map of few points
-  // (every BundleAdjustRecent window) gets quarter-size groups: four times the workgroups on a chip they do not fill anyway, a
-  // quarter of the per-group latency in the linearisation (four lanes per point) and in the Schur complement (one chunk per group)
+  B.lap("sort+slots");
+}
+
+// ---- groups: consecutive points, <= grp_pts points and <= GRP_LMAX distinct poses (greedy, in order).  A map of few points
+// (every BundleAdjustRecent window) gets quarter-size groups: four times the workgroups on a chip they do not fill anyway, a
+// quarter of the per-group latency in the linearisation (four lanes per point) and in the Schur complement (one chunk per group)
+void mcp_ba::make_groups(StructBuild& B) {
+  HostStruct& H = B.H; const std::vector<int>& sp_q0 = B.sp_q0; const std::vector<int>& sp_q = B.sp_q;
   grp_pts = group_points(nsp);
   nbig = 0;
-  {
-    std::vector<int> stamp(std::max(nfp, 1), -1), curset; curset.reserve(GRP_LMAX);
-    int start = 0, gid = 0;
-    auto close = [&](int end) {
-      if (end <= start) return;
-      std::sort(curset.begin(), curset.end());
-      H.g_sp0.push_back(start);
-      for (int k = 0; k < GRP_LMAX; ++k) H.g_pose.push_back(k < (int)curset.size() ? curset[k] : -1);
-      curset.clear(); start = end; ++gid;
-    };
-    for (int sp = 0; sp < nsp; ++sp) {
-      const bool big = H.sp_big[sp] != 0;                          // big points ride along with no poses
-      if (big) ++nbig;
-      const int* q = sp_q.data() + sp_q0[sp]; const int nq = big ? 0 : sp_q0[sp + 1] - sp_q0[sp];
-      int fresh = 0;
-      for (int k = 0; k < nq; ++k) if (stamp[q[k]] != gid) ++fresh;
-      if ((int)curset.size() + fresh > grp_lmax_pol || sp - start >= grp_pts) close(sp);
-      for (int k = 0; k < nq; ++k) if (stamp[q[k]] != gid) { stamp[q[k]] = gid; curset.push_back(q[k]); }
-    }
-    close(nsp);
-    H.g_sp0.push_back(nsp);
+  std::vector<int> stamp(std::max(nfp, 1), -1), curset; curset.reserve(GRP_LMAX);
+  int start = 0, gid = 0;
+  auto close = [&](int end) {
+    if (end <= start) return;
+    std::sort(curset.begin(), curset.end());
+    H.g_sp0.push_back(start);
+    for (int k = 0; k < GRP_LMAX; ++k) H.g_pose.push_back(k < (int)curset.size() ? curset[k] : -1);
+    curset.clear(); start = end; ++gid;
+  };
+  for (int sp = 0; sp < nsp; ++sp) {
+    const bool big = H.sp_big[sp] != 0;                          // big points ride along with no poses
+    if (big) ++nbig;
+    const int* q = sp_q.data() + sp_q0[sp]; const int nq = big ? 0 : sp_q0[sp + 1] - sp_q0[sp];
+    int fresh = 0;
+    for (int k = 0; k < nq; ++k) if (stamp[q[k]] != gid) ++fresh;
+    if ((int)curset.size() + fresh > grp_lmax_pol || sp - start >= grp_pts) close(sp);
+    for (int k = 0; k < nq; ++k) if (stamp[q[k]] != gid) { stamp[q[k]] = gid; curset.push_back(q[k]); }
   }
+  close(nsp);
+  H.g_sp0.push_back(nsp);
   ngroup = (int)H.g_sp0.size() - 1;
-  lap("groups");
-  // ---- tile occupancy of the reduced pose system: poses a, b interact iff some point touches both
+  B.lap("groups");
+}
+
+// ---- tile occupancy of the reduced pose system: poses a, b interact iff some point touches both; the factorisation's plan for it
+int mcp_ba::tile_pattern_and_plan(StructBuild& B) {
+  PrepTimer& lap = B.lap;
   if (np > 0) {
     const int ntc = (np + CH_NB - 1)/CH_NB;
-    std::vector<unsigned char> pat((size_t)ntc*ntc, 0);
-    for (int a = 0; a < nfp; ++a) for (int b = 0; b <= a; ++b) {
-      if (!cov[(size_t)a*nfp + b]) continue;
-      const int ra0 = (6*a)/CH_NB, ra1 = (6*a + 5)/CH_NB, rb0 = (6*b)/CH_NB, rb1 = (6*b + 5)/CH_NB;
-      for (int ra = ra0; ra <= ra1; ++ra) for (int rb = rb0; rb <= rb1; ++rb) if (ra >= rb) pat[(size_t)ra*ntc + rb] = 1;
-    }
-    for (int i = 0; i < ntc; ++i) pat[(size_t)i*ntc + i] = 1;
-    if (multi()) {
-      // the union of every rank's co-visibility pattern: agreed once, used for the factorisation plan and for the
-      // packed all-reduce of the reduced system (only structurally non-zero tiles travel over xGMI)
-      std::vector<double> pd(pat.begin(), pat.end());
-      DevBuf<double> tmp;
-      if (tmp.upload(pd, st)) return -1;
-      if (allreduce(tmp.p, pd.size(), 0, true, "set-up: tile pattern")) return -1;
-      HIPCK(hipMemcpy(pd.data(), tmp.p, pd.size()*sizeof(double), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < pd.size(); ++i) pat[i] = pd[i] > 0;
-      std::vector<int> rt;
-      for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (pat[(size_t)i*ntc + j]) rt.push_back((i << 16) | j);
-      n_red_tiles = (int)rt.size();
-      if (d_red_tiles.upload(rt, st) || d_pack.alloc(MAX_SYS*((size_t)n_red_tiles*CH_NB*CH_NB + 2*(size_t)np))) return -1;
-      pack_stride = (size_t)n_red_tiles*CH_NB*CH_NB + 2*(size_t)np;
-    }
-    if (trace) {
+    std::vector<unsigned char> pat = cov_to_pattern(B.cov, nfp, ntc);
+    if (multi() && agree_tile_pattern(pat, ntc)) return -1;
+    if (lap.trace) {
       std::string hs; std::vector<int> hd(ntc, 0); int tot = 0;
       for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (pat[(size_t)i*ntc + j]) { ++hd[i - j]; ++tot; }
       for (int d = 0; d < ntc; ++d) { char b[16]; snprintf(b, sizeof b, " %d", hd[d]); hs += b; }
@@ -1539,17 +1722,23 @@ int mcp_ba::prepare() {
     last_pat = std::move(pat);
     lap("  symbolic plan");
   } else { plan.all_tiles.clear(); last_pat.clear(); }
-  // ---- per group (threads over ranges of groups): local pose indices of slots and incidences, and which local pose pairs the
-  // group's points co-observe (one bit per pair of the 16 x 17 / 2)
+  return 0;
+}
+
+constexpr int NPAIR = GRP_LMAX*(GRP_LMAX + 1)/2;      // local pose pairs of a group
+static inline int ltri(int r, int c) { return r*(r + 1)/2 + c; }
+// ---- per group (threads over ranges of groups): local pose indices of slots and incidences, and which local pose pairs the
+// group's points co-observe (one bit per pair of the 16 x 17 / 2)
+void mcp_ba::local_indices(StructBuild& B) {
+  HostStruct& H = B.H; const avec<int>& sp_m = H.sp_m; const std::vector<int>& sp_q0 = B.sp_q0; const std::vector<int>& sp_q = B.sp_q;
+  const std::vector<unsigned char>& inc_state = B.inc_state; std::vector<unsigned char>& gcov = B.gcov;
   H.slot_lp.assign(nslot + 1, 0); H.inc_lp.assign(ninc + 1, 0); H.inc_mixed.assign(ninc + 1, 0);
-  constexpr int NPAIR = GRP_LMAX*(GRP_LMAX + 1)/2;
-  std::vector<unsigned char> gcov((size_t)std::max(ngroup, 1)*NPAIR, 0);
+  gcov.assign((size_t)std::max(ngroup, 1)*NPAIR, 0);
   H.g_blk0.assign(ngroup + 1, 0);
-  auto ltri = [](int r, int c) { return r*(r + 1)/2 + c; };
-  par([&](int tid) {
-    for (long i = lo_of(tid, ninc), e = lo_of(tid + 1, ninc); i < e; ++i) H.inc_mixed[i] = (inc_state[i] == 3);
+  B.par([&](int tid) {
+    for (long i = B.lo_of(tid, ninc), e = B.lo_of(tid + 1, ninc); i < e; ++i) H.inc_mixed[i] = (inc_state[i] == 3);
     std::vector<unsigned char> lpmap(std::max(nfp, 1), 0);
-    for (int gi = (int)lo_of(tid, ngroup), ge = (int)lo_of(tid + 1, ngroup); gi < ge; ++gi) {
+    for (int gi = (int)B.lo_of(tid, ngroup), ge = (int)B.lo_of(tid + 1, ngroup); gi < ge; ++gi) {
       const int* gp = &H.g_pose[(size_t)gi*GRP_LMAX];
       for (int k = 0; k < GRP_LMAX; ++k) if (gp[k] >= 0) lpmap[gp[k]] = (unsigned char)k;
       unsigned char* gc = &gcov[(size_t)gi*NPAIR];
@@ -1564,9 +1753,13 @@ int mcp_ba::prepare() {
       H.g_blk0[gi + 1] = nb;
     }
   });
-  lap("  local indices");
-  // ---- fixed-order assembly plan (ba_group.h): which local pose pairs every group stages, and for every global pose
-  // pair / pose the list of staged slots in ascending group order
+  B.lap("  local indices");
+}
+
+// ---- fixed-order assembly plan (ba_group.h): which local pose pairs every group stages, and for every global pose
+// pair / pose the list of staged slots in ascending group order
+void mcp_ba::staging_plan(StructBuild& B) {
+  HostStruct& H = B.H; const std::vector<unsigned char>& gcov = B.gcov; const bool trace = B.lap.trace;
   grp_blk_max = 0; grp_inc_max = 0;
   for (int gi = 0; gi < ngroup; ++gi) {
     grp_blk_max = std::max(grp_blk_max, H.g_blk0[gi + 1]); H.g_blk0[gi + 1] += H.g_blk0[gi];
@@ -1608,18 +1801,16 @@ int mcp_ba::prepare() {
     { std::vector<int> pos(H.po_start.begin(), H.po_start.end() - 1);
       for (int gi = 0; gi < ngroup; ++gi) for (int k = 0; k < GRP_LMAX; ++k) { const int u = H.g_pose[(size_t)gi*GRP_LMAX + k]; if (u >= 0) H.rhs_dst[(size_t)gi*GRP_LMAX + k] = pos[u]++; } }
   }
-  lap("pattern+plan");
-  if (trace) fprintf(stderr, "[mcp_ba prepare] %d groups, %zu staged blocks (%.1f per group, at most %d), %d host threads\n", ngroup, nstage, ngroup ? (double)nstage/ngroup : 0.0, grp_blk_max, T);
-  return finish_prepare(H, t0, tlast, trace);
+  B.lap("pattern+plan");
+  if (trace) fprintf(stderr, "[mcp_ba prepare] %d groups, %zu staged blocks (%.1f per group, at most %d), %d host threads\n", ngroup, nstage, ngroup ? (double)nstage/ngroup : 0.0, grp_blk_max, B.T);
 }
 
-int mcp_ba::prepare_legacy() {
-  cache_insert = false;            // (the serial builder neither consults nor fills the structure cache)
-  auto t0 = std::chrono::steady_clock::now();
-  auto tlast = t0; const bool trace = getenv("MCP_BA_TRACE") != nullptr;
-  auto lap = [&](const char* what) { if (!trace) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[mcp_ba prepare] %-22s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tlast).count()); tlast = n; };
-  HIPCK(hipSetDevice(device));
-  const int npose = (int)poses.size(), npoint = (int)points.size(), nmeas = (int)meas.size();
+// The serial reference builder (MCP_BA_PREPARE_LEGACY=1): an implementation of its own of everything between the activity and the
+// staging plan -- that independence is what the comparison with the threaded builder is worth -- on the leaves the two share above.
+// It neither consults nor fills the structure cache and keeps the poses in add order: one chain.
+int mcp_ba::prepare_legacy(StructBuild& B) {
+  PrepTimer& lap = B.lap; const bool trace = lap.trace;
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas;
   for (auto& p : poses) { p.active = 0; p.unk = -1; }
   for (auto& p : points) { p.active = 0; p.unk = -1; }
   for (const auto& m : meas) {
@@ -1629,25 +1820,12 @@ int mcp_ba::prepare_legacy() {
     for (int k = 0; k < sc.len; ++k) poses[sc.v[k]].active = 1;
   }
   m_total = (double)nmeas;
-  if (multi()) {
-    // ranks hold different measurement shards: agree on the active poses and the global count
-    std::vector<double> flags(npose + 2);
-    for (int i = 0; i < npose; ++i) flags[i] = poses[i].active;
-    flags[npose] = (double)nmeas;
-    double nfree = 0; for (const auto& p : points) if (p.active && !p.fixed) nfree += 1;
-    flags[npose + 1] = nfree;
-    DevBuf<double> tmp;
-    if (tmp.upload(flags, st)) return -1;
-    if (allreduce(tmp.p, flags.size(), 0, true, "set-up: active poses and counts")) return -1;
-    HIPCK(hipMemcpy(flags.data(), tmp.p, flags.size()*sizeof(double), hipMemcpyDeviceToHost));
-    for (int i = 0; i < npose; ++i) poses[i].active = flags[i] > 0;
-    m_total = flags[npose]; nfl_total = flags[npose + 1];
-  }
+  if (multi() && agree_activity()) return -1;
   fp_pose.clear(); fl_point.clear();
   for (int i = 0; i < npose; ++i) if (poses[i].active && !poses[i].fixed) { poses[i].unk = (int)fp_pose.size(); fp_pose.push_back(i); }
   for (int i = 0; i < npoint; ++i) if (points[i].active && !points[i].fixed) { points[i].unk = (int)fl_point.size(); fl_point.push_back(i); }
   nfp = (int)fp_pose.size(); nfl = (int)fl_point.size(); np = 6*nfp; nx = np + 3*nfl;
-  if (np > CH_SOLVE_MAX) { set_err("too many free poses for the dense reduced solve (6P > 6144)"); return -1; }
+  if (too_many_free_poses()) return -1;
   if (!multi()) nfl_total = nfl;
   lap("activity");
   // ---- measurements by point (add order kept inside a point)
@@ -1677,35 +1855,7 @@ int mcp_ba::prepare_legacy() {
     refine_point_order(order, pkey, smax.data(), ssum.data(), 0, order.size());
   }
   nsp = (int)order.size();
-  // per (obs chain, src chain) activity mask, memoised in a dense table (chains are few: P*C for the Multi adapter)
-  const size_t nch = chains.size();
-  const bool dense_table = nch <= 4096;
-  // (entries are written concurrently by the structure threads below: every writer stores the same value, relaxed atomics)
-  std::unique_ptr<std::atomic<unsigned short>[]> mask_table(dense_table ? new std::atomic<unsigned short>[nch*nch] : nullptr);
-  if (dense_table) for (size_t i = 0; i < nch*nch; ++i) mask_table[i].store(0xffff, std::memory_order_relaxed);
-  std::map<std::pair<int, int>, unsigned short> mask_cache;
-  std::mutex mask_mutex;
-  auto compute_mask = [&](int oc, int sc) -> unsigned short {
-    unsigned short mk = 0;
-    const HChain& o = chains[oc]; const HChain& s = chains[sc];
-    for (int i = 0; i < o.len; ++i) if (!poses[o.v[i]].fixed && !move_together(o, s, i)) mk |= (1 << i);
-    for (int i = 0; i < s.len; ++i) if (!poses[s.v[i]].fixed && !move_together(s, o, i)) mk |= (1 << (MAXC + i));
-    return mk;
-  };
-  auto pair_mask = [&](int oc, int sc) -> unsigned short {
-    if (dense_table) {
-      std::atomic<unsigned short>& e = mask_table[(size_t)oc*nch + sc];
-      unsigned short v = e.load(std::memory_order_relaxed);
-      if (v == 0xffff) { v = compute_mask(oc, sc); e.store(v, std::memory_order_relaxed); }
-      return v;
-    }
-    std::lock_guard<std::mutex> lk(mask_mutex);
-    auto key = std::make_pair(oc, sc);
-    auto it = mask_cache.find(key);
-    if (it != mask_cache.end()) return it->second;
-    const unsigned short mk = compute_mask(oc, sc);
-    mask_cache[key] = mk; return mk;
-  };
+  PairMasks pair_mask(*this);
   std::vector<int> m_pt(nmeas), m_chain(nmeas), m_sp(nmeas), slot_start(nmeas + 1, 0), slot_unk, slot_inc;
   std::vector<unsigned char> m_cam(nmeas), slot_first;
   std::vector<unsigned short> m_mask(nmeas);
@@ -1841,37 +1991,14 @@ int mcp_ba::prepare_legacy() {
   // ---- tile occupancy of the reduced pose system: poses a, b interact iff some point touches both
   if (np > 0) {
     const int ntc = (np + CH_NB - 1)/CH_NB;
-    std::vector<unsigned char> pat((size_t)ntc*ntc, 0);
-    {
-      std::vector<unsigned char> cov((size_t)nfp*nfp, 0);                  // pose-pair co-visibility, a >= b
-      for (int sp = 0; sp < nsp; ++sp) {
-        const std::vector<int>& q = sp_poses[sp];
-        for (int a : q) for (int b : q) if (a >= b) cov[(size_t)a*nfp + b] = 1;
-      }
-      for (int a = 0; a < nfp; ++a) for (int b = 0; b <= a; ++b) {
-        if (!cov[(size_t)a*nfp + b]) continue;
-        const int ra0 = (6*a)/CH_NB, ra1 = (6*a + 5)/CH_NB, rb0 = (6*b)/CH_NB, rb1 = (6*b + 5)/CH_NB;
-        for (int ra = ra0; ra <= ra1; ++ra) for (int rb = rb0; rb <= rb1; ++rb) if (ra >= rb) pat[(size_t)ra*ntc + rb] = 1;
-      }
+    std::vector<unsigned char> cov((size_t)nfp*nfp, 0);                  // pose-pair co-visibility, a >= b
+    for (int sp = 0; sp < nsp; ++sp) {
+      const std::vector<int>& q = sp_poses[sp];
+      for (int a : q) for (int b : q) if (a >= b) cov[(size_t)a*nfp + b] = 1;
     }
-    for (int i = 0; i < ntc; ++i) pat[(size_t)i*ntc + i] = 1;
-    if (multi()) {
-      // the union of every rank's co-visibility pattern: agreed once, used for the factorisation plan and for the
-      // packed all-reduce of the reduced system (only structurally non-zero tiles travel over xGMI)
-      std::vector<double> pd(pat.begin(), pat.end());
-      DevBuf<double> tmp;
-      if (tmp.upload(pd, st)) return -1;
-      if (allreduce(tmp.p, pd.size(), 0, true, "set-up: tile pattern")) return -1;
-      HIPCK(hipMemcpy(pd.data(), tmp.p, pd.size()*sizeof(double), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < pd.size(); ++i) pat[i] = pd[i] > 0;
-      std::vector<int> rt;
-      for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (pat[(size_t)i*ntc + j]) rt.push_back((i << 16) | j);
-      n_red_tiles = (int)rt.size();
-      if (d_red_tiles.upload(rt, st) || d_pack.alloc(MAX_SYS*((size_t)n_red_tiles*CH_NB*CH_NB + 2*(size_t)np))) return -1;
-      pack_stride = (size_t)n_red_tiles*CH_NB*CH_NB + 2*(size_t)np;
-    }
+    std::vector<unsigned char> pat = cov_to_pattern(cov, nfp, ntc);
+    if (multi() && agree_tile_pattern(pat, ntc)) return -1;
     lap("  covisibility");
-    chol_segs.clear(); plan.persist_segs.clear();      // (the serial builder keeps the poses in add order: one chain)
     if (plan.build(np, pat)) { set_err("Cholesky plan allocation failed"); return -1; }
     lap("  symbolic plan");
   } else plan.all_tiles.clear();
@@ -1940,63 +2067,56 @@ int mcp_ba::prepare_legacy() {
 
   lap("pattern+plan");
   if (trace) fprintf(stderr, "[mcp_ba prepare] %d groups, %zu staged blocks (%.1f per group, at most %d)\n", ngroup, nstage, ngroup ? (double)nstage/ngroup : 0.0, grp_blk_max);
-  std::unique_lock<std::mutex> arena_lock(pinned_arena().mutex());
-  ArenaGuard arena_guard{st};
-  HostStruct H;
+  B.hold_arena(st);
+  HostStruct& H = B.H;
 #define CP(x) H.x.assign(x.begin(), x.end())
   CP(m_pt); CP(m_chain); CP(m_sp); CP(slot_start); CP(slot_unk); CP(slot_inc); CP(l_i0); CP(l_i1); CP(l_sp); CP(inc_unk); CP(sp_pt); CP(sp_m); CP(sp_i);
   CP(g_sp0); CP(g_pose); CP(g_blk0); CP(pair_id); CP(pr_start); CP(blk_dst); CP(po_start); CP(rhs_dst); CP(m_cam); CP(slot_first); CP(sp_big); CP(slot_lp);
   CP(inc_lp); CP(inc_mixed); CP(blk_pair); CP(m_mask); CP(m_u); CP(m_v); CP(m_om);
 #undef CP
-  return finish_prepare(H, t0, tlast, trace);
+  return finish_prepare(B);
 }
 
-// allocation + upload of a finished host structure (common to both builders)
-int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point tlast, bool trace, const StructEntry* hit) {
+// The ~40 structure arrays go into ONE device block (d_struct; every d_* is an alias into it): one allocation, and one
+// host-to-device copy for all the small arrays together (staged through the pinned arena) -- the large per-measurement arrays,
+// which the builders wrote into the pinned arena already, are copied from where they lie.  This is that block as layout_block()
+// lays it out, with the small host arrays it is filled from.
+struct mcp_ba::BlockLayout {
+  struct Item { const void* src; size_t bytes, off; bool direct; };
+  std::vector<Item> items; std::vector<size_t> counts;      // (counts: what a cache hit replays the layout from)
+  size_t total = 0, staged = 0; char* base = nullptr;
+  static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+  std::vector<int> chain_len, chain_pose, pose_unk, pt_chain, pt_unk, sp_unk, g_order; std::vector<unsigned char> pt_fixed;
+  std::vector<int, NoInitAlloc<int>> m_last;
+};
+
+// allocation + upload of a finished host structure (common to both builders and to an adopted cache entry, B.hit)
+int mcp_ba::finish_prepare(StructBuild& B) {
   pending_entry.reset();          // (whatever an earlier, failed Prepare() of this handle left behind is not this call's to publish)
-  auto lap = [&](const char* what) { if (!trace) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[mcp_ba prepare] %-22s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tlast).count()); tlast = n; };
-  const int npose = (int)poses.size(), npoint = (int)points.size();
-  const int nmeas = hit ? hit->key.nmeas : (int)meas.size();          // (near miss: the device arrays keep the adopted structure's length)
-  std::vector<int> chain_len(chains.size()), chain_pose(chains.size()*MAXC), pose_unk(npose), pt_chain(npoint), pt_unk(npoint);
-  std::vector<unsigned char> pt_fixed(npoint);
-  for (size_t c = 0; c < chains.size(); ++c) { chain_len[c] = chains[c].len; for (int i = 0; i < MAXC; ++i) chain_pose[c*MAXC + i] = chains[c].v[i]; }
-  for (int i = 0; i < npose; ++i) pose_unk[i] = poses[i].unk;
-  for (int i = 0; i < npoint; ++i) { pt_chain[i] = points[i].chain; pt_unk[i] = points[i].unk; pt_fixed[i] = (unsigned char)points[i].fixed; }
+  const int nmeas = B.hit ? B.hit->key.nmeas : B.nmeas;          // (near miss: the device arrays keep the adopted structure's length)
+  const int nblk = (std::max(nmeas, nfl) + 255)/256 + 1;
+  BlockLayout L;
+  launch_choices(B);
+  if (layout_block(B, L)) return -1;
+  if (B.hit ? upload_hit_numbers(B, L) : upload_cold(L)) return -1;
+  B.lap("  upload enqueued");
+  if (!B.hit && cache_insert && make_cache_entry(B, L)) return -1;
+  read_call_knobs();
+  if (alloc_work_buffers(nmeas, nblk) || head_scratch(nmeas, nblk) || poison_test_aid() || pinned_mailbox(nblk) || zero_fill() || fill_param_blocks(nmeas)) return -1;
+  B.lap("alloc+upload");
+  return publish(B);
+}
+
+// which kernels the prepared map takes: k_schur4 or the general Schur kernel, the long-list assembly; the Schur launch's work counters
+void mcp_ba::launch_choices(StructBuild& B) {
+  const StructEntry* hit = B.hit.get(); const HostStruct& H = B.H;
   // k_schur4 holds a group's local tile as 5 x 5 16-row tiles: every group must fit S4_LMAX poses
   sch4_ok = ngroup > 0;
   if (hit) sch4_ok = hit->sch4_ok;
   else for (int gi = 0; gi < ngroup && sch4_ok; ++gi) if (H.g_pose[(size_t)gi*GRP_LMAX + S4_LMAX] >= 0) sch4_ok = false;
   schur_mfma = schur_flops = 0;
   if (hit) { schur_mfma = hit->schur_mfma; schur_flops = hit->schur_flops; }
-  else if ((prm.profile || cache_insert) && ngroup) {       // (a Prepare() that fills the structure cache computes it for whoever adopts the entry)
-    // the work of one system's Schur launch, for the bench line: non-empty 16-row tiles of every 16-point chunk -> tile pairs x 12
-    // instructions (k_schur4 skips empty tiles; k_schur_group multiplies every tile of the group's poses), and the structural flops
-    // (ranges of groups on the worker pool, partial sums added in thread order: integers in doubles, any order gives the same value)
-    HostPool& pool = host_pool();
-    const int T = (nmeas >= 32768) ? pool.size() : 1;
-    std::vector<double> pm(T, 0.0), pf(T, 0.0);
-    auto body = [&](int tid) {
-      double sm = 0, sf = 0;
-      for (int gi = (int)((long)ngroup*tid/T), ge = (int)((long)ngroup*(tid + 1)/T); gi < ge; ++gi) {
-        int npl = 0; for (int k = 0; k < GRP_LMAX; ++k) if (H.g_pose[(size_t)gi*GRP_LMAX + k] >= 0) npl = k + 1;
-        const int ntile = (6*npl + 15)/16;
-        for (int s0 = H.g_sp0[gi]; s0 < H.g_sp0[gi + 1]; s0 += 16) {
-          unsigned tm = 0;
-          for (int sp = s0; sp < std::min(s0 + 16, H.g_sp0[gi + 1]); ++sp) {
-            if (H.sp_big[sp]) continue;
-            const int k = H.sp_i[sp + 1] - H.sp_i[sp];
-            sf += 324.0*k*(k + 1)/2;
-            for (int i = H.sp_i[sp]; i < H.sp_i[sp + 1]; ++i) { tm |= 1u << ((6*H.inc_lp[i]) >> 4); tm |= 1u << ((6*H.inc_lp[i] + 5) >> 4); }
-          }
-          const int nt = (sch4_on && sch4_ok) ? __builtin_popcount(tm) : (tm ? ntile : 0);
-          sm += 12.0*nt*(nt + 1)/2;
-        }
-      }
-      pm[tid] = sm; pf[tid] = sf;
-    };
-    if (T == 1) body(0); else pool.run(body);
-    for (int t2 = 0; t2 < T; ++t2) { schur_mfma += pm[t2]; schur_flops += pf[t2]; }
-  }
+  else if ((prm.profile || cache_insert) && ngroup) schur_work(B);       // (a Prepare() that fills the structure cache computes it for whoever adopts the entry)
   if (hit) asm_long = hit->asm_long;
   else {
     // long lists of staged blocks per pose pair (mean >= 48: a handful of free poses that every group stages) go through k_assemble_long
@@ -2004,165 +2124,205 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
     asm_long = npairs > 0 && nstage >= 48*npairs;
     if (const char* e = getenv("MCP_BA_ASM_LONG")) asm_long = atoi(e) != 0 && npairs > 0;
   }
-  // The ~40 structure arrays go into ONE device block (d_struct; every d_* below is an alias into it): one allocation, and one
-  // host-to-device copy for all the small arrays together (staged through the pinned arena) -- the large per-measurement arrays,
-  // which the builders wrote into the pinned arena already, are copied from where they lie.
-  {
-    struct Item { const void* src; size_t bytes, off; bool direct; };
-    std::vector<Item> items; items.reserve(48);
-    size_t total = 0, staged = 0;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // (a cache hit brings no host arrays: the layout is replayed from the element counts the cold Prepare() recorded, in the same order)
-    std::vector<size_t> counts; counts.reserve(48);
-    size_t nadd = 0;
-    auto add = [&](auto& dbuf, const auto& vec, bool pinned) {
-      using E = typename std::remove_reference<decltype(vec)>::type::value_type;
-      const size_t cnt = hit ? hit->counts[nadd] : vec.size();
-      ++nadd;
-      const size_t bytes = cnt*sizeof(E);
-      dbuf.release();
-      dbuf.alias = true; dbuf.n = std::max<size_t>(cnt, 1); dbuf.p = reinterpret_cast<decltype(dbuf.p)>(total);      // (offset for now)
-      const bool direct = pinned && bytes >= 16384;
-      counts.push_back(cnt);
-      items.push_back({hit ? nullptr : (const void*)vec.data(), bytes, total, direct});
-      if (!direct) staged += al(std::max<size_t>(bytes, 1));
-      total += al(std::max<size_t>(bytes, 1));
-    };
-    add(d_cams, cams, false); add(d_chain_len, chain_len, false); add(d_chain_pose, chain_pose, false); add(d_pose_unk, pose_unk, false);
-    add(d_pt_chain, pt_chain, false); add(d_pt_unk, pt_unk, false); add(d_pt_fixed, pt_fixed, false);
-    add(d_m_pt, H.m_pt, true); add(d_m_chain, H.m_chain, true); add(d_m_cam, H.m_cam, true); add(d_m_mask, H.m_mask, true);
-    add(d_m_u, H.m_u, true); add(d_m_v, H.m_v, true); add(d_m_omega, H.m_om, true); add(d_slot_start, H.slot_start, true);
-    add(d_slot_unk, H.slot_unk, true); add(d_slot_inc, H.slot_inc, true); add(d_l_i0, H.l_i0, true); add(d_l_i1, H.l_i1, true);
-    add(d_inc_unk, H.inc_unk, true); add(d_fl_point, fl_point, false); add(d_sp_pt, H.sp_pt, true); add(d_sp_m, H.sp_m, true);
-    add(d_sp_i, H.sp_i, true); add(d_sp_big, H.sp_big, true); add(d_m_sp, H.m_sp, true); add(d_l_sp, H.l_sp, true);
-    add(d_g_sp0, H.g_sp0, true); add(d_g_pose, H.g_pose, true); add(d_slot_lp, H.slot_lp, true); add(d_slot_first, H.slot_first, true);
-    add(d_inc_lp, H.inc_lp, true); add(d_inc_mixed, H.inc_mixed, true); add(d_g_blk0, H.g_blk0, true); add(d_blk_pair, H.blk_pair, true);
-    add(d_asm_tiles, plan.all_tiles, false); add(d_pair_id, H.pair_id, true); add(d_pr_start, H.pr_start, true); add(d_blk_dst, H.blk_dst, true);
-    add(d_po_start, H.po_start, true); add(d_rhs_dst, H.rhs_dst, true);
-    // k_schur4: free-point index per sorted point (one index hop less at the head of every workgroup), and -- when the groups
-    // outnumber the workgroup slots of the device (2 per compute unit) -- the order in which they are launched: heaviest first
-    // (tile pairs x chunks), so that the second round of workgroups is made of the light ones and the launch ends evenly
-    std::vector<int> sp_unk(hit ? 0 : nsp), g_order;
-    if (!hit) for (int sp = 0; sp < nsp; ++sp) sp_unk[sp] = H.sp_big[sp] ? -1 : pt_unk[H.sp_pt[sp]];
-    sch4_order = hit ? hit->sch4_order : (sch4_on && sch4_ok && ngroup > 512 && env_on("MCP_BA_SCHUR4_ORDER", true));
-    if (sch4_order && !hit) {
-      std::vector<int> cost(ngroup);
-      for (int gi = 0; gi < ngroup; ++gi) {
-        int npl = 0; for (int k = 0; k < GRP_LMAX; ++k) if (H.g_pose[(size_t)gi*GRP_LMAX + k] >= 0) npl = k + 1;
-        const int nt = (6*npl + 15)/16;
-        cost[gi] = nt*(nt + 1)/2*((H.g_sp0[gi + 1] - H.g_sp0[gi] + 15)/16);
-      }
-      g_order.resize(ngroup);
-      for (int gi = 0; gi < ngroup; ++gi) g_order[gi] = gi;
-      std::stable_sort(g_order.begin(), g_order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-    }
-    std::vector<int, NoInitAlloc<int>> m_last(hit ? 0 : nmeas);
-    if (!hit) {
-      HostPool& pool = host_pool();
-      const int T = (nmeas >= 32768) ? pool.size() : 1;
-      auto body = [&](int tid) { for (long j = (long)nmeas*tid/T, e = (long)nmeas*(tid + 1)/T; j < e; ++j) { const int oc = H.m_chain[j]; m_last[j] = oc*MAXC + chains[oc].len - 1; } };
-      if (T == 1) body(0); else pool.run(body);
-    }
-    add(d_sp_unk, sp_unk, false); add(d_g_order, g_order, false); add(d_m_last, m_last, false);
-    if (d_struct.alloc(total)) return -1;
-    char* const base = d_struct.p;
-    auto fix = [&](auto& dbuf) { dbuf.p = reinterpret_cast<decltype(dbuf.p)>(base + reinterpret_cast<size_t>(dbuf.p)); };
-    fix(d_cams); fix(d_chain_len); fix(d_chain_pose); fix(d_pose_unk); fix(d_pt_chain); fix(d_pt_unk); fix(d_pt_fixed);
-    fix(d_m_pt); fix(d_m_chain); fix(d_m_cam); fix(d_m_mask); fix(d_m_u); fix(d_m_v); fix(d_m_omega); fix(d_slot_start);
-    fix(d_slot_unk); fix(d_slot_inc); fix(d_l_i0); fix(d_l_i1); fix(d_inc_unk); fix(d_fl_point); fix(d_sp_pt); fix(d_sp_m);
-    fix(d_sp_i); fix(d_sp_big); fix(d_m_sp); fix(d_l_sp); fix(d_g_sp0); fix(d_g_pose); fix(d_slot_lp); fix(d_slot_first);
-    fix(d_inc_lp); fix(d_inc_mixed); fix(d_g_blk0); fix(d_blk_pair); fix(d_asm_tiles); fix(d_pair_id); fix(d_pr_start); fix(d_blk_dst);
-    fix(d_po_start); fix(d_rhs_dst); fix(d_sp_unk); fix(d_g_order); fix(d_m_last);
-    if (hit) {
-      // the cached clone of the block, then this handle's own numbers over it: the cameras and the measurement values (u, v, the
-      // weight), gathered into sorted order through the permutation the structure build left
-      if (hit->dbytes != total) { set_err("structure cache: layout mismatch"); return -1; }
-      HIPCK(hipMemcpyAsync(base, hit->dblock, total, hipMemcpyDeviceToDevice, st));
-      const size_t nm = (size_t)nmeas;
-      double* vals = (double*)pinned_arena().alloc((3*nm + 1)*sizeof(double));
-      {
-        HostPool& pool = host_pool();
-        const int T = (nmeas >= 32768) ? pool.size() : 1;
-        const int* pm = perm.data(); const HMeas* ms = meas.data();
-        auto body = [&](int tid) {
-          for (size_t j = nm*tid/T, e = nm*(tid + 1)/T; j < e; ++j) {
-            if (pm[j] < 0) { vals[j] = 0.0; vals[nm + j] = 0.0; vals[2*nm + j] = 0.0; continue; }      // (near miss: a measurement this map does not have -- weight 0)
-            const HMeas& m = ms[pm[j]]; vals[j] = m.u; vals[nm + j] = m.v; vals[2*nm + j] = m.omega;
-          }
-        };
-        if (T == 1) body(0); else pool.run(body);
-      }
-      mcp_camera* cs = cams.empty() ? nullptr : (mcp_camera*)pinned_arena().alloc(cams.size()*sizeof(mcp_camera));
-      if (cs) std::memcpy(cs, cams.data(), cams.size()*sizeof(mcp_camera));
-      static_assert(sizeof(mcp_camera) % 8 == 0, "k_upload_set copies 8-byte words");
-      if (3*nm*sizeof(double) <= UPSET_MAX_BYTES && pinned_arena().is_pinned(vals) && (!cs || pinned_arena().is_pinned(cs))) {
-        UploadSet V; V.n = 0;             // a small bundle: the kernel reads the pinned values in place
-        if (nm) { upload_set_add(V, vals, d_m_u.p, nm*sizeof(double)); upload_set_add(V, vals + nm, d_m_v.p, nm*sizeof(double)); upload_set_add(V, vals + 2*nm, d_m_omega.p, nm*sizeof(double)); }
-        if (cs) upload_set_add(V, cs, d_cams.p, cams.size()*sizeof(mcp_camera));
-        upload_set_launch(V, st); note_launch("k_upload_set");
-      } else {
-        if (nm) {
-          HIPCK(hipMemcpyAsync(d_m_u.p, vals, nm*sizeof(double), hipMemcpyHostToDevice, st));
-          HIPCK(hipMemcpyAsync(d_m_v.p, vals + nm, nm*sizeof(double), hipMemcpyHostToDevice, st));
-          HIPCK(hipMemcpyAsync(d_m_omega.p, vals + 2*nm, nm*sizeof(double), hipMemcpyHostToDevice, st));
+}
+
+// the work of one system's Schur launch, for the bench line: non-empty 16-row tiles of every 16-point chunk -> tile pairs x 12
+// instructions (k_schur4 skips empty tiles; k_schur_group multiplies every tile of the group's poses), and the structural flops
+// (ranges of groups on the worker pool, partial sums added in thread order: integers in doubles, any order gives the same value)
+void mcp_ba::schur_work(StructBuild& B) {
+  const HostStruct& H = B.H;
+  const int T = finish_threads(B.nmeas);
+  std::vector<double> pm(T, 0.0), pf(T, 0.0);
+  auto body = [&](int tid) {
+    double sm = 0, sf = 0;
+    for (int gi = (int)((long)ngroup*tid/T), ge = (int)((long)ngroup*(tid + 1)/T); gi < ge; ++gi) {
+      int npl = 0; for (int k = 0; k < GRP_LMAX; ++k) if (H.g_pose[(size_t)gi*GRP_LMAX + k] >= 0) npl = k + 1;
+      const int ntile = (6*npl + 15)/16;
+      for (int s0 = H.g_sp0[gi]; s0 < H.g_sp0[gi + 1]; s0 += 16) {
+        unsigned tm = 0;
+        for (int sp = s0; sp < std::min(s0 + 16, H.g_sp0[gi + 1]); ++sp) {
+          if (H.sp_big[sp]) continue;
+          const int k = H.sp_i[sp + 1] - H.sp_i[sp];
+          sf += 324.0*k*(k + 1)/2;
+          for (int i = H.sp_i[sp]; i < H.sp_i[sp + 1]; ++i) { tm |= 1u << ((6*H.inc_lp[i]) >> 4); tm |= 1u << ((6*H.inc_lp[i] + 5) >> 4); }
         }
-        if (cs) HIPCK(hipMemcpyAsync(d_cams.p, cs, cams.size()*sizeof(mcp_camera), hipMemcpyHostToDevice, st));
+        const int nt = (sch4_on && sch4_ok) ? __builtin_popcount(tm) : (tm ? ntile : 0);
+        sm += 12.0*nt*(nt + 1)/2;
       }
     }
-    // the small ones: contiguous runs of staged items are contiguous in the device block too -- one copy per run
-    char* stage = (staged && !hit) ? (char*)pinned_arena().alloc(staged) : nullptr;
-    size_t so = 0;
-    for (size_t i = 0; i < items.size() && !hit; ) {
-      if (items[i].direct) { if (items[i].bytes) HIPCK(hipMemcpyAsync(base + items[i].off, items[i].src, items[i].bytes, hipMemcpyHostToDevice, st)); ++i; continue; }
-      const size_t run_off = items[i].off, run_so = so;
-      size_t run_bytes = 0;
-      for (; i < items.size() && !items[i].direct; ++i) {
-        if (items[i].bytes) std::memcpy(stage + so, items[i].src, items[i].bytes);
-        const size_t a = al(std::max<size_t>(items[i].bytes, 1)); so += a; run_bytes += a;
-      }
-      HIPCK(hipMemcpyAsync(base + run_off, stage + run_so, run_bytes, hipMemcpyHostToDevice, st));
+    pm[tid] = sm; pf[tid] = sf;
+  };
+  run_ranges(T, body);
+  for (int t2 = 0; t2 < T; ++t2) { schur_mfma += pm[t2]; schur_flops += pf[t2]; }
+}
+
+// the small arrays of the block that no builder made: chains, unknown numbers, and what k_schur4 and the trial kernels read
+void mcp_ba::small_arrays(StructBuild& B, BlockLayout& L) {
+  const StructEntry* hit = B.hit.get(); const HostStruct& H = B.H; const int npose = B.npose, npoint = B.npoint, nmeas = hit ? hit->key.nmeas : B.nmeas;
+  L.chain_len.resize(chains.size()); L.chain_pose.resize(chains.size()*MAXC); L.pose_unk.resize(npose); L.pt_chain.resize(npoint); L.pt_unk.resize(npoint); L.pt_fixed.resize(npoint);
+  for (size_t c = 0; c < chains.size(); ++c) { L.chain_len[c] = chains[c].len; for (int i = 0; i < MAXC; ++i) L.chain_pose[c*MAXC + i] = chains[c].v[i]; }
+  for (int i = 0; i < npose; ++i) L.pose_unk[i] = poses[i].unk;
+  for (int i = 0; i < npoint; ++i) { L.pt_chain[i] = points[i].chain; L.pt_unk[i] = points[i].unk; L.pt_fixed[i] = (unsigned char)points[i].fixed; }
+  // k_schur4: free-point index per sorted point (one index hop less at the head of every workgroup), and -- when the groups
+  // outnumber the workgroup slots of the device (2 per compute unit) -- the order in which they are launched: heaviest first
+  // (tile pairs x chunks), so that the second round of workgroups is made of the light ones and the launch ends evenly
+  L.sp_unk.resize(hit ? 0 : nsp);
+  if (!hit) for (int sp = 0; sp < nsp; ++sp) L.sp_unk[sp] = H.sp_big[sp] ? -1 : L.pt_unk[H.sp_pt[sp]];
+  sch4_order = hit ? hit->sch4_order : (sch4_on && sch4_ok && ngroup > 512 && env_on("MCP_BA_SCHUR4_ORDER", true));
+  if (sch4_order && !hit) {
+    std::vector<int> cost(ngroup);
+    for (int gi = 0; gi < ngroup; ++gi) {
+      int npl = 0; for (int k = 0; k < GRP_LMAX; ++k) if (H.g_pose[(size_t)gi*GRP_LMAX + k] >= 0) npl = k + 1;
+      const int nt = (6*npl + 15)/16;
+      cost[gi] = nt*(nt + 1)/2*((H.g_sp0[gi + 1] - H.g_sp0[gi] + 15)/16);
     }
-    lap("  upload enqueued");
-    if (!hit && cache_insert) {
-      // leave the results in the structure cache: host-side members + a device clone of the block (behind the uploads, on this stream;
-      // whoever adopts it waits for nothing: an entry becomes visible only after this Prepare()'s final synchronisation, below)
-      auto e = std::make_shared<StructEntry>();
-      e->key = cache_key; e->base = cache_base;
-      {   // (1.6 MB each at the metric size, the cameras through the 40-byte measurement records: 0.45 ms on one thread)
-        e->add_point.resize(nmeas); e->add_chain.resize(nmeas); e->add_cam.resize(nmeas);
-        HostPool& pool = host_pool();
-        const int T = (nmeas >= 32768) ? pool.size() : 1;
-        auto body = [&](int tid) {
-          const long j0 = (long)nmeas*tid/T, j1 = (long)nmeas*(tid + 1)/T;
-          if (j1 > j0) { std::memcpy(e->add_point.data() + j0, meas_point.data() + j0, (size_t)(j1 - j0)*sizeof(int)); std::memcpy(e->add_chain.data() + j0, meas_chain.data() + j0, (size_t)(j1 - j0)*sizeof(int)); }
-          for (long j = j0; j < j1; ++j) e->add_cam[j] = meas[j].cam;
-        };
-        if (T == 1) body(0); else pool.run(body);
-      }
-      e->pose_unk.resize(npose); e->pose_active.resize(npose); e->pt_unk.resize(npoint); e->pt_active.resize(npoint);
-      for (int i = 0; i < npose; ++i) { e->pose_unk[i] = poses[i].unk; e->pose_active[i] = (unsigned char)poses[i].active; }
-      for (int i = 0; i < npoint; ++i) { e->pt_unk[i] = points[i].unk; e->pt_active[i] = (unsigned char)points[i].active; }
-      e->fp_pose = fp_pose; e->fl_point = fl_point; e->perm = perm; e->pat = last_pat; e->chol_segs = chol_segs;
-      e->nfp = nfp; e->nfl = nfl; e->np = np; e->nx = nx; e->nsp = nsp; e->ninc = ninc; e->nslot = nslot; e->ngroup = ngroup; e->nbig = nbig;
-      e->grp_pts = grp_pts; e->grp_blk_max = grp_blk_max; e->grp_inc_max = grp_inc_max; e->nrhs_rows = nrhs_rows; e->nstage = nstage;
-      e->asm_long = asm_long; e->sch4_ok = sch4_ok; e->sch4_order = sch4_order; e->m_total = m_total; e->nfl_total = nfl_total;
-      e->schur_mfma = schur_mfma; e->schur_flops = schur_flops; e->counts = counts;
-      e->dblock = (char*)DevCache::get().take(std::max<size_t>(total, 1), &e->dcap, &e->ddev);
-      if (e->dblock) {
-        e->dbytes = total;
-        HIPCK(hipMemcpyAsync(e->dblock, base, total, hipMemcpyDeviceToDevice, st));
-        pending_entry = e;
-      }
-      lap("  cache entry");
-    }
+    L.g_order.resize(ngroup);
+    for (int gi = 0; gi < ngroup; ++gi) L.g_order[gi] = gi;
+    std::stable_sort(L.g_order.begin(), L.g_order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
   }
-  const size_t nc = chains.size();
-  for (int b = 0; b < NSTATE; ++b)
-    if (d_pose[b].alloc((size_t)npose*12) || d_pt[b].alloc((size_t)npoint*3) || d_first[b].alloc(nc*MAXC*12) ||
-        d_second[b].alloc(nc*MAXC*9) || d_last[b].alloc(nc*12) || d_chi2[b].alloc(nmeas)) return -1;
-  const size_t n2 = (size_t)np*np;
-  const int nblk = (std::max(nmeas, nfl) + 255)/256 + 1;
-  red_stride = n2 + 2*(size_t)np; vinv_stride = (size_t)nfl*6; spec_ok = false; sys_cur = 0;
+  L.m_last.resize(hit ? 0 : nmeas);
+  if (!hit) {
+    auto& m_last = L.m_last; const int T = finish_threads(nmeas);
+    run_ranges(T, [&](int tid) { for (long j = (long)nmeas*tid/T, e = (long)nmeas*(tid + 1)/T; j < e; ++j) { const int oc = H.m_chain[j]; m_last[j] = oc*MAXC + chains[oc].len - 1; } });
+  }
+}
+
+// every array's place in the block (the d_* become aliases into d_struct), in the one order that a cache hit replays from the
+// element counts the cold Prepare() recorded: a hit brings no host arrays
+int mcp_ba::layout_block(StructBuild& B, BlockLayout& L) {
+  const StructEntry* hit = B.hit.get(); const HostStruct& H = B.H;
+  small_arrays(B, L);
+  L.items.reserve(48); L.counts.reserve(48);
+  size_t& total = L.total; auto al = BlockLayout::al;
+  size_t nadd = 0;
+  auto add = [&](auto& dbuf, const auto& vec, bool pinned) {
+    using E = typename std::remove_reference<decltype(vec)>::type::value_type;
+    const size_t cnt = hit ? hit->counts[nadd] : vec.size();
+    ++nadd;
+    const size_t bytes = cnt*sizeof(E);
+    dbuf.release();
+    dbuf.alias = true; dbuf.n = std::max<size_t>(cnt, 1); dbuf.p = reinterpret_cast<decltype(dbuf.p)>(total);      // (offset for now)
+    const bool direct = pinned && bytes >= 16384;
+    L.counts.push_back(cnt);
+    L.items.push_back({hit ? nullptr : (const void*)vec.data(), bytes, total, direct});
+    if (!direct) L.staged += al(std::max<size_t>(bytes, 1));
+    total += al(std::max<size_t>(bytes, 1));
+  };
+  add(d_cams, cams, false); add(d_chain_len, L.chain_len, false); add(d_chain_pose, L.chain_pose, false); add(d_pose_unk, L.pose_unk, false);
+  add(d_pt_chain, L.pt_chain, false); add(d_pt_unk, L.pt_unk, false); add(d_pt_fixed, L.pt_fixed, false);
+  add(d_m_pt, H.m_pt, true); add(d_m_chain, H.m_chain, true); add(d_m_cam, H.m_cam, true); add(d_m_mask, H.m_mask, true);
+  add(d_m_u, H.m_u, true); add(d_m_v, H.m_v, true); add(d_m_omega, H.m_om, true); add(d_slot_start, H.slot_start, true);
+  add(d_slot_unk, H.slot_unk, true); add(d_slot_inc, H.slot_inc, true); add(d_l_i0, H.l_i0, true); add(d_l_i1, H.l_i1, true);
+  add(d_inc_unk, H.inc_unk, true); add(d_fl_point, fl_point, false); add(d_sp_pt, H.sp_pt, true); add(d_sp_m, H.sp_m, true);
+  add(d_sp_i, H.sp_i, true); add(d_sp_big, H.sp_big, true); add(d_m_sp, H.m_sp, true); add(d_l_sp, H.l_sp, true);
+  add(d_g_sp0, H.g_sp0, true); add(d_g_pose, H.g_pose, true); add(d_slot_lp, H.slot_lp, true); add(d_slot_first, H.slot_first, true);
+  add(d_inc_lp, H.inc_lp, true); add(d_inc_mixed, H.inc_mixed, true); add(d_g_blk0, H.g_blk0, true); add(d_blk_pair, H.blk_pair, true);
+  add(d_asm_tiles, plan.all_tiles, false); add(d_pair_id, H.pair_id, true); add(d_pr_start, H.pr_start, true); add(d_blk_dst, H.blk_dst, true);
+  add(d_po_start, H.po_start, true); add(d_rhs_dst, H.rhs_dst, true);
+  add(d_sp_unk, L.sp_unk, false); add(d_g_order, L.g_order, false); add(d_m_last, L.m_last, false);
+  if (d_struct.alloc(total)) return -1;
+  char* const base = L.base = d_struct.p;
+  auto fix = [&](auto& dbuf) { dbuf.p = reinterpret_cast<decltype(dbuf.p)>(base + reinterpret_cast<size_t>(dbuf.p)); };
+  fix(d_cams); fix(d_chain_len); fix(d_chain_pose); fix(d_pose_unk); fix(d_pt_chain); fix(d_pt_unk); fix(d_pt_fixed);
+  fix(d_m_pt); fix(d_m_chain); fix(d_m_cam); fix(d_m_mask); fix(d_m_u); fix(d_m_v); fix(d_m_omega); fix(d_slot_start);
+  fix(d_slot_unk); fix(d_slot_inc); fix(d_l_i0); fix(d_l_i1); fix(d_inc_unk); fix(d_fl_point); fix(d_sp_pt); fix(d_sp_m);
+  fix(d_sp_i); fix(d_sp_big); fix(d_m_sp); fix(d_l_sp); fix(d_g_sp0); fix(d_g_pose); fix(d_slot_lp); fix(d_slot_first);
+  fix(d_inc_lp); fix(d_inc_mixed); fix(d_g_blk0); fix(d_blk_pair); fix(d_asm_tiles); fix(d_pair_id); fix(d_pr_start); fix(d_blk_dst);
+  fix(d_po_start); fix(d_rhs_dst); fix(d_sp_unk); fix(d_g_order); fix(d_m_last);
+  return 0;
+}
+
+// a hit: the cached clone of the block, then this handle's own numbers over it: the cameras and the measurement values (u, v, the
+// weight), gathered into sorted order through the permutation the structure build left
+int mcp_ba::upload_hit_numbers(StructBuild& B, BlockLayout& L) {
+  const StructEntry* hit = B.hit.get(); const int nmeas = hit->key.nmeas;
+  if (hit->dbytes != L.total) { set_err("structure cache: layout mismatch"); return -1; }
+  HIPCK(hipMemcpyAsync(L.base, hit->dblock, L.total, hipMemcpyDeviceToDevice, st));
+  const size_t nm = (size_t)nmeas;
+  double* vals = (double*)pinned_arena().alloc((3*nm + 1)*sizeof(double));
+  {
+    const int T = finish_threads(nmeas);
+    const int* pm = perm.data(); const HMeas* ms = meas.data();
+    run_ranges(T, [&](int tid) {
+      for (size_t j = nm*tid/T, e = nm*(tid + 1)/T; j < e; ++j) {
+        if (pm[j] < 0) { vals[j] = 0.0; vals[nm + j] = 0.0; vals[2*nm + j] = 0.0; continue; }      // (near miss: a measurement this map does not have -- weight 0)
+        const HMeas& m = ms[pm[j]]; vals[j] = m.u; vals[nm + j] = m.v; vals[2*nm + j] = m.omega;
+      }
+    });
+  }
+  mcp_camera* cs = cams.empty() ? nullptr : (mcp_camera*)pinned_arena().alloc(cams.size()*sizeof(mcp_camera));
+  if (cs) std::memcpy(cs, cams.data(), cams.size()*sizeof(mcp_camera));
+  static_assert(sizeof(mcp_camera) % 8 == 0, "k_upload_set copies 8-byte words");
+  if (3*nm*sizeof(double) <= UPSET_MAX_BYTES && pinned_arena().is_pinned(vals) && (!cs || pinned_arena().is_pinned(cs))) {
+    UploadSet V; V.n = 0;             // a small bundle: the kernel reads the pinned values in place
+    if (nm) { upload_set_add(V, vals, d_m_u.p, nm*sizeof(double)); upload_set_add(V, vals + nm, d_m_v.p, nm*sizeof(double)); upload_set_add(V, vals + 2*nm, d_m_omega.p, nm*sizeof(double)); }
+    if (cs) upload_set_add(V, cs, d_cams.p, cams.size()*sizeof(mcp_camera));
+    upload_set_launch(V, st); note_launch("k_upload_set");
+  } else {
+    if (nm) {
+      HIPCK(hipMemcpyAsync(d_m_u.p, vals, nm*sizeof(double), hipMemcpyHostToDevice, st));
+      HIPCK(hipMemcpyAsync(d_m_v.p, vals + nm, nm*sizeof(double), hipMemcpyHostToDevice, st));
+      HIPCK(hipMemcpyAsync(d_m_omega.p, vals + 2*nm, nm*sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (cs) HIPCK(hipMemcpyAsync(d_cams.p, cs, cams.size()*sizeof(mcp_camera), hipMemcpyHostToDevice, st));
+  }
+  return 0;
+}
+
+// a cold build: the large arrays from where they lie in the pinned arena; the small ones staged: contiguous runs of staged items
+// are contiguous in the device block too -- one copy per run
+int mcp_ba::upload_cold(BlockLayout& L) {
+  const std::vector<BlockLayout::Item>& items = L.items; char* const base = L.base; auto al = BlockLayout::al;
+  char* stage = L.staged ? (char*)pinned_arena().alloc(L.staged) : nullptr;
+  size_t so = 0;
+  for (size_t i = 0; i < items.size(); ) {
+    if (items[i].direct) { if (items[i].bytes) HIPCK(hipMemcpyAsync(base + items[i].off, items[i].src, items[i].bytes, hipMemcpyHostToDevice, st)); ++i; continue; }
+    const size_t run_off = items[i].off, run_so = so;
+    size_t run_bytes = 0;
+    for (; i < items.size() && !items[i].direct; ++i) {
+      if (items[i].bytes) std::memcpy(stage + so, items[i].src, items[i].bytes);
+      const size_t a = al(std::max<size_t>(items[i].bytes, 1)); so += a; run_bytes += a;
+    }
+    HIPCK(hipMemcpyAsync(base + run_off, stage + run_so, run_bytes, hipMemcpyHostToDevice, st));
+  }
+  return 0;
+}
+
+// leave the results in the structure cache: host-side members + a device clone of the block (behind the uploads, on this stream;
+// whoever adopts it waits for nothing: an entry becomes visible only after this Prepare()'s final synchronisation, publish())
+int mcp_ba::make_cache_entry(StructBuild& B, BlockLayout& L) {
+  const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas; const size_t total = L.total;
+  auto e = std::make_shared<StructEntry>();
+  e->key = cache_key; e->base = cache_base;
+  {   // (1.6 MB each at the metric size, the cameras through the 40-byte measurement records: 0.45 ms on one thread)
+    e->add_point.resize(nmeas); e->add_chain.resize(nmeas); e->add_cam.resize(nmeas);
+    const int T = finish_threads(nmeas);
+    run_ranges(T, [&](int tid) {
+      const long j0 = (long)nmeas*tid/T, j1 = (long)nmeas*(tid + 1)/T;
+      if (j1 > j0) { std::memcpy(e->add_point.data() + j0, meas_point.data() + j0, (size_t)(j1 - j0)*sizeof(int)); std::memcpy(e->add_chain.data() + j0, meas_chain.data() + j0, (size_t)(j1 - j0)*sizeof(int)); }
+      for (long j = j0; j < j1; ++j) e->add_cam[j] = meas[j].cam;
+    });
+  }
+  e->pose_unk.resize(npose); e->pose_active.resize(npose); e->pt_unk.resize(npoint); e->pt_active.resize(npoint);
+  for (int i = 0; i < npose; ++i) { e->pose_unk[i] = poses[i].unk; e->pose_active[i] = (unsigned char)poses[i].active; }
+  for (int i = 0; i < npoint; ++i) { e->pt_unk[i] = points[i].unk; e->pt_active[i] = (unsigned char)points[i].active; }
+  e->fp_pose = fp_pose; e->fl_point = fl_point; e->perm = perm; e->pat = last_pat; e->chol_segs = chol_segs;
+  e->nfp = nfp; e->nfl = nfl; e->np = np; e->nx = nx; e->nsp = nsp; e->ninc = ninc; e->nslot = nslot; e->ngroup = ngroup; e->nbig = nbig;
+  e->grp_pts = grp_pts; e->grp_blk_max = grp_blk_max; e->grp_inc_max = grp_inc_max; e->nrhs_rows = nrhs_rows; e->nstage = nstage;
+  e->asm_long = asm_long; e->sch4_ok = sch4_ok; e->sch4_order = sch4_order; e->m_total = m_total; e->nfl_total = nfl_total;
+  e->schur_mfma = schur_mfma; e->schur_flops = schur_flops; e->counts = L.counts;
+  e->dblock = (char*)DevCache::get().take(std::max<size_t>(total, 1), &e->dcap, &e->ddev);
+  if (e->dblock) {
+    e->dbytes = total;
+    HIPCK(hipMemcpyAsync(e->dblock, L.base, total, hipMemcpyDeviceToDevice, st));
+    pending_entry = e;
+  }
+  B.lap("  cache entry");
+  return 0;
+}
+
+// per-call knobs of the LM driver (read at every Prepare(): a test sets them between two handles)
+void mcp_ba::read_call_knobs() {
   { const char* e = getenv("MCP_BA_SPECULATE"); if (e) speculate = atoi(e); }
   { const char* e = getenv("MCP_BA_SPECULATE_ADAPT"); if (e) spec_adapt = atoi(e); }
   { const char* e = getenv("MCP_BA_LIN_JOIN"); if (e) lin_join_full = atoi(e); }
@@ -2170,6 +2330,17 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
   { const char* e = getenv("MCP_BA_HEAD_LARGE"); if (e) head_large_on = atoi(e); }
   { const char* e = getenv("MCP_BA_GRAPH"); if (e) use_graph = atoi(e); }
   { const char* e = getenv("MCP_BA_SELECT_CAP"); if (e) sel_cap = std::max(1, atoi(e)); }
+}
+
+// the state buffers and the work buffers of the iteration, sized for this map
+int mcp_ba::alloc_work_buffers(int nmeas, int nblk) {
+  const int npose = (int)poses.size(), npoint = (int)points.size();
+  const size_t nc = chains.size();
+  for (int b = 0; b < NSTATE; ++b)
+    if (d_pose[b].alloc((size_t)npose*12) || d_pt[b].alloc((size_t)npoint*3) || d_first[b].alloc(nc*MAXC*12) ||
+        d_second[b].alloc(nc*MAXC*9) || d_last[b].alloc(nc*12) || d_chi2[b].alloc(nmeas)) return -1;
+  const size_t n2 = (size_t)np*np;
+  red_stride = n2 + 2*(size_t)np; vinv_stride = (size_t)nfl*6; spec_ok = false; sys_cur = 0;
   if (multi()) {
     if (d_seltab.alloc((size_t)world*sel_cap + world + 2)) return -1;
     for (int q = 0; q < MAX_SYS; ++q) if (d_trial[q].alloc(TRIAL_LEN) || d_trstate[q].alloc(SEL_PASSES + 1)) return -1;
@@ -2184,6 +2355,12 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
       d_xp_good.alloc(np) || d_xp_cand.alloc(np) || d_selvals.alloc(SEL_GATHER_CAP) || d_xl_good.alloc((size_t)nfl*3) || d_part0.alloc(nblk) || d_part1.alloc(nblk) ||
       d_part2.alloc(nblk) || d_parth.alloc(nblk) || d_res.alloc(32 + 8*MAX_SYS) || d_sigma.alloc(8*N_SIG) || d_hist.alloc((size_t)SEL_PASSES*SEL_BINS) ||
       d_selstate.alloc(SEL_PASSES + 1) || d_fail.alloc(4) || d_flags.alloc(nmeas) || d_cov.alloc(nfl)) return -1;
+  return 0;
+}
+
+// scratch of the iteration heads: k_head_large's block, and the per-trial heads' (ba_head.h)
+int mcp_ba::head_scratch(int nmeas, int nblk) {
+  const size_t nc = chains.size();
   if (head_large_on && robust && !multi() && nmeas > 0) {
     if (d_headl.alloc(sizeof(HeadLScratch))) return -1;
     headl_clean = false;                           // (the block may be a fresh one: zeroed in front of the first head)
@@ -2212,14 +2389,24 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
     for (int q = 0; q < MAX_SYS; ++q) { head_enq[q] = false; head_state[q] = -1; }
     acc_head_q = -1; start_blk = nullptr;
   }
-  if (const char* e = getenv("MCP_BA_DEBUG_POISON_RED")) {      // test aid: "q,lo,hi" -- the reduced-system buffer zeroed, doubles [lo, hi) of system q set to NaN
+  return 0;
+}
+
+// test aid, MCP_BA_DEBUG_POISON_RED="q,lo,hi": the reduced-system buffer zeroed, doubles [lo, hi) of system q set to NaN
+int mcp_ba::poison_test_aid() {
+  const size_t n2 = (size_t)np*np;
+  if (const char* e = getenv("MCP_BA_DEBUG_POISON_RED")) {
     int q = 0; long lo = 0, hi = 0;
     if (std::sscanf(e, "%d,%ld,%ld", &q, &lo, &hi) == 3 && q >= 0 && q < MAX_SYS && lo >= 0 && hi <= (long)(n2 + 2*(size_t)np) && lo < hi) {
       HIPCK(hipMemset(d_red.p, 0, MAX_SYS*(n2 + 2*(size_t)np)*sizeof(double)));
       HIPCK(hipMemset(d_red.p + q*(n2 + 2*(size_t)np) + lo, 0xFF, (size_t)(hi - lo)*sizeof(double)));
     }
   }
-  // pinned, device-visible: [0..31] read-back block, [32 + 32 q ..] mailbox of trial q (ticket at + MAIL_TICKET)
+  return 0;
+}
+
+// pinned, device-visible: [0..31] read-back block, [32 + 32 q ..] mailbox of trial q (ticket at + MAIL_TICKET); the buffers of the trial systems
+int mcp_ba::pinned_mailbox(int nblk) {
   if (!h_res) {
     h_res = (double*)mcp::PinnedCache::get().take(HRES*sizeof(double), hipHostMallocMapped | hipHostMallocCoherent);
     if (!h_res) { set_err("hipHostMalloc failed"); return -1; }
@@ -2229,7 +2416,12 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
   for (int q = 1; q < MAX_SYS; ++q)
     if (d_sxp[q].alloc(np) || d_sxl[q].alloc((size_t)nfl*3) || d_sp0[q].alloc(nblk) || d_sp1[q].alloc(nblk) || d_sp2[q].alloc(nblk)) return -1;
   if (!h_fail) { h_fail = (int*)mcp::PinnedCache::get().take(4*sizeof(int), hipHostMallocDefault); if (!h_fail) { set_err("hipHostMalloc failed"); return -1; } }
-  if (((size_t)np + (size_t)nfl*3)*sizeof(double) <= UPSET_MAX_BYTES) {      // x = 0 before the first solve, no sigma block yet: one launch
+  return 0;
+}
+
+// x = 0 before the first solve, no sigma block yet
+int mcp_ba::zero_fill() {
+  if (((size_t)np + (size_t)nfl*3)*sizeof(double) <= UPSET_MAX_BYTES) {      // (one launch)
     UploadSet Z; Z.n = 0;
     upload_set_add(Z, nullptr, d_xp_good.p, std::max<size_t>(np, 1)*sizeof(double));
     upload_set_add(Z, nullptr, d_xl_good.p, std::max<size_t>((size_t)nfl*3, 1)*sizeof(double));
@@ -2241,7 +2433,12 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
     HIPCK(hipMemsetAsync(d_sigma.p, 0, 16*sizeof(double), st));
   }
   sig_idx = 0;
+  return 0;
+}
 
+// the kernels' parameter blocks: the structure arrays' places in the block and the sizes (P), the assembly's (A)
+int mcp_ba::fill_param_blocks(int nmeas) {
+  const int npose = (int)poses.size(), npoint = (int)points.size(); const size_t nc = chains.size();
   P.cams = d_cams.p; P.ncam = (int)cams.size(); P.nchain = (int)nc; P.chain_len = d_chain_len.p; P.chain_pose = d_chain_pose.p;
   P.npose = npose; P.pose_unk = d_pose_unk.p; P.npoint = npoint; P.pt_chain = d_pt_chain.p; P.pt_unk = d_pt_unk.p;
   P.pt_fixed = d_pt_fixed.p; P.nmeas = nmeas; P.m_pt = d_m_pt.p; P.m_chain = d_m_chain.p; P.m_cam = d_m_cam.p;
@@ -2264,7 +2461,11 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
       sch_attr.fetch_or(bit, std::memory_order_relaxed);
     }
   }
-  lap("alloc+upload");
+  return 0;
+}
+
+// the state into its buffers, the one synchronisation of a Prepare(), and only then the cache entry for every other handle to see
+int mcp_ba::publish(StructBuild& B) {
   if (upload_state()) { pending_entry.reset(); return -1; }
   {
     const hipError_t es = hipStreamSynchronize(st);
@@ -2277,9 +2478,9 @@ int mcp_ba::finish_prepare(HostStruct& H, std::chrono::steady_clock::time_point 
     }
   }
   if (pending_entry) { StructCache::get().insert(pending_entry); pending_entry.reset(); }
-  lap("state");
+  B.lap("state");
   dirty = false;
-  timing.structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  timing.structure_ms += B.lap.total_ms();
   return 0;
 }
 

@@ -1106,6 +1106,42 @@ def test_a_map_that_lost_its_outliers_adopts_the_cached_structure_of_the_call_be
     assert lone["rc"] == 2 and chain_bundle.struct_cache_near_hits() == n1
 
 
+def test_a_near_miss_handle_prepared_again_by_the_serial_builder_forgets_its_masked_measurements(gpu_required, monkeypatch):
+    """What a Prepare() leaves for Compute() is reset at the top of every Prepare(), whichever path follows.  A handle that adopted a
+    superset's structure (near miss: n_masked erased measurements stay in the device arrays with weight 0, and the median of the
+    squared errors is taken at rank n_masked + m/2) and is then prepared again by the serial builder -- which builds the smaller map's
+    own arrays, nothing masked -- must solve exactly like a fresh handle under the serial builder: same arrays => same solve, bit for
+    bit, as in test_threaded_prepare_builds_the_serial_structure."""
+    from mcptam_amd import synth, chain_bundle
+    from helpers import collect
+    iters = 6
+    p = synth.make_config("c1")
+    chain_bundle.struct_cache_clear()
+    first = run_bundle(_gpu(p.cams, disable_convergence=True), p, iters)          # fills the cache with the full map
+    from collections import Counter
+    flagged = Counter(o[0] for o in first["outliers"])
+    per_point = p.n_meas // p.n_points
+    gone = [o for o in first["outliers"] if flagged[o[0]] < per_point]             # (a map that lost a point is built cold)
+    assert len(gone) > 0
+    q = synth.erase_measurements(p, gone, first["ids"])
+    n0 = chain_bundle.struct_cache_near_hits()
+    g = _gpu(q.cams, disable_convergence=True)
+    ids = q.populate(g)
+    g.Prepare()
+    assert chain_bundle.struct_cache_near_hits() == n0 + 1
+    monkeypatch.setenv("MCP_BA_PREPARE_LEGACY", "1")
+    g.SetComm(None)                                                                # marks the handle dirty; the map is unchanged
+    rc = g.Compute(iters)
+    R, t, X = collect(g, ids)
+    again = dict(rc=rc, logs=g.IterLogs(), outliers=g.GetOutlierMeasurements(), sigma_sq=g.GetSigmaSquared())
+    g.close()
+    fresh = run_bundle(_gpu(q.cams, disable_convergence=True), q, iters)
+    assert chain_bundle.struct_cache_near_hits() == n0 + 1
+    assert again["rc"] == fresh["rc"] == iters
+    assert again["logs"] == fresh["logs"] and again["sigma_sq"] == fresh["sigma_sq"] and again["outliers"] == fresh["outliers"]
+    assert np.array_equal(R, fresh["R"]) and np.array_equal(t, fresh["t"]) and np.array_equal(X, fresh["X"])
+
+
 @pytest.mark.parametrize("cfg,iters", [("tiny", 6), ("c1", 6), ("calib", 6), ("c2", 5), ("metric", 4), ("band", 5)])
 def test_cached_prepare_equals_a_cold_one(gpu_required, cfg, iters):
     """Structure cache (include/mcp_ba.h): a handle that brings the topology of an earlier Prepare() adopts that structure (host
