@@ -908,6 +908,67 @@ int mcp_map_bundle_select_host(const mcp_bundle_select_params*, int ncam, const 
                                const int* ms_source, const uint8_t* ms_alive, mcp_bundle_select_result* res,
                                int cap_mkfs, mcp_bundle_mkf* out_mkfs, int cap_points, mcp_bundle_point* out_points, int cap_meas, mcp_bundle_meas* out_meas);
 
+/* ---- The keyframe lists from the store, and AdjustAndUpdate's write-back over the graph in ONE submission --- src/BundleAdjusterMulti.cc:286-334
+ * mcp_ba_write_back and mcp_scene_depth_robust take the keyframe-major lists (seg_start / seg_rows / seg_weights) from the caller.  The calls
+ * below build them on the device from the graph's store and the table's count column, and keep the graph's poses and scene-depth means in step
+ * with what they write, so that a select -> solve -> write-back -> select cycle moves nothing list-sized over the link.
+ * THE LISTS.  A call names n_mkfs <= MCP_MAP_MAX_MKFS distinct present slots; keyframe j = i * ncam + c is (slots[i], camera index c), ncam the
+ *   graph's rig size.  List j holds, in ASCENDING STORE INDEX, the store entries that are alive, of MKF slots[i] and camera c, whose keyframe is
+ *   active (kf_active; an inactive keyframe has an empty list: MultiKeyFrame::RefreshSceneDepthRobust, src/KeyFrame.cc:851-869), whose row is a
+ *   row of the table and whose graph column is not MCP_GP_BAD (a row never written is bad) -- KeyFrame::GetPointDepthsAndWeights, :549-570.
+ *   seg_rows = the row; seg_weights = inlier / (inlier + outlier) of the table's count column, the sum and the quotient in double (rows never
+ *   set: (1, 0)).
+ *   ORDER: the reference's order is a pointer order (std::map over MapPoint*); store order is the one fixed here, and it JOINS THE SUMMATION
+ *   CONTRACT of mcp_scene_depth_robust above: the scene-depth kernel adds a list in list position, so one store gives one set of bits, whatever
+ *   the grid.  mean / sigma differ from the reference's sorted-order sums within the bound stated at mcp_scene_depth_robust; nothing else is inexact.
+ *   mcp_graph_compact keeps the order; entries appended later come later.
+ * Threading and streams: as the graph's other calls (the table's stream; the caller serialises).  Each call below is one submission and one
+ * wait, except the debug hook.  mcp_map_points_last_timing keeps its meaning for mcp_graph_refresh_depth and mcp_graph_write_back: the copy of
+ * the packed inputs (the call's slots: no list), the chain table + point kernel, and -- as depth_ms -- the list launches, the pose and depth
+ * stores and the scene-depth kernel. */
+
+/* MultiKeyFrame::RefreshSceneDepthRobust of the named MKFs at the graph's own poses (an MKF that enters the map, src/MapMakerServerBase.cc:219,
+ * 392): the lists, CamFromWorld_j = cam_from_base[c] * base_from_world(slots[i]), mcp_scene_depth_robust's kernel on them, and `mean` stored as
+ * the graph's depth mean of every keyframe with refreshed == 1 and a finite positive mean (all others keep their bytes).  depth_out: NULL or
+ * n_mkfs x ncam records; where refreshed == 0 only n and refreshed are written (as mcp_scene_depth_robust).  n_mkfs == 0 is allowed.
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, graph and table unchanged): NULL graph; n_mkfs negative or > MCP_MAP_MAX_MKFS; a slot out of
+ * range, not present, or repeated. */
+int mcp_graph_refresh_depth(mcp_map_graph*, int n_mkfs, const int* slots, mcp_scene_depth* depth_out);
+
+/* mcp_ba_write_back with the keyframe half taken from the graph.  POINTS: exactly mcp_ba_write_back's arguments, checks and kernels.
+ * KEYFRAMES: keyframe j = i * ncam + c is the chain {mkf_pose_ids[i], cam_pose_ids[c]} of the bundle (pose ids as mcp_ba_add_pose returned
+ * them).  On the table's stream, behind the one event on the solver's stream: the chain table, the points, the solver's current pose of
+ * mkf_pose_ids[i] copied into the graph's base_from_world of slots[i] (12 doubles, bit for bit), the lists, the scene depth with the chain
+ * products as poses (after the point step, as mcp_ba_write_back), and the depth-mean store of mcp_graph_refresh_depth.  One wait; the solver
+ * handle may be destroyed at once.  A select that follows sees the new poses and depth means: no mcp_map_graph_update_mkfs is needed.
+ * kf_cam_from_world_out: NULL or n_mkfs*ncam x 12; depth_out: NULL or n_mkfs*ncam; base_from_world_out: NULL or n_mkfs x 12.
+ * CONTRACT, NOT CHECKED: the caller added the graph's rig as the poses cam_pose_ids (BundleAdjusterMulti adds one pose per camera from the same
+ * CamFromBase).  Otherwise the select's distances go on using the graph's rig while the depths here use the solver's.
+ * REFUSALS (-1, mcp_last_error(), nothing enqueued, graph and table unchanged): those of mcp_ba_write_back for the handles and the point half;
+ * those of mcp_graph_refresh_depth for the slots; a pose id that is not a pose; a required pointer NULL with a positive count; a graph whose
+ * table is not on the solver's device.  n_mkfs == 0 and n_points == 0 are allowed. */
+int mcp_graph_write_back(mcp_ba*, mcp_map_graph*, int n_points, const int* point_ids, const int* rows, const int* src_chains, int chain_stride,
+                         const int* src_chain_len, double* world_pos_out, double* pixel_right_out, double* pixel_down_out,
+                         int n_mkfs, const int* slots, const int* mkf_pose_ids, const int* cam_pose_ids /* ncam */,
+                         double* kf_cam_from_world_out, mcp_scene_depth* depth_out, double* base_from_world_out);
+
+/* MKF slots first .. first+count-1 read back as mcp_map_graph_set_mkfs takes them (every pointer may be NULL: that column is skipped; the depth
+ * mean of an inactive keyframe reads 0); waits for the stream */
+int mcp_graph_get_mkfs(mcp_map_graph*, int first, int count, double* base_from_world, int* flags, uint8_t* kf_active, double* kf_depth_mean);
+
+/* test hook, read-only: the list launches alone, the lists copied out.  blocks: how many chunks the store is cut into, 1..64, or 0 for the
+ * grid the other calls use (the lists do not depend on it).  seg_start: n_mkfs*ncam + 1 entries; seg_rows / seg_weights: cap entries.  Returns
+ * the total; a total above cap is refused after seg_start has been written.  Two waits. */
+int mcp_graph_debug_kf_lists(mcp_map_graph*, int n_mkfs, const int* slots, int blocks, int* seg_start, int cap, int* seg_rows, double* seg_weights);
+
+/* the same lists from host arrays, by the same bodies under the host compiler: needs no device and gives the device's bytes.  kf_active:
+ * n_slots x ncam; point_flags: the n_point_rows <= n_rows graph columns written so far (the rows after them read as bad); inlier / outlier: the
+ * count column, n_rows.  Returns the total; refused (outputs but seg_start untouched): the slots as above, a total above cap, a count
+ * the table's column would refuse (inlier < 1 or outlier < 0). */
+int mcp_graph_kf_lists_host(int ncam, int n_slots, const int* mkf_flags, const uint8_t* kf_active, int n_rows, int n_point_rows, const int* point_flags,
+                            const int* inlier, const int* outlier, int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row,
+                            const uint8_t* ms_alive, int n_mkfs, const int* slots, int* seg_start /* n_mkfs*ncam + 1 */, int cap, int* seg_rows, double* seg_weights);
+
 #ifdef __cplusplus
 }
 #endif

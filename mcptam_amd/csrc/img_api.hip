@@ -29,6 +29,7 @@
 #include "ba_bridge.h"
 #include "ba_select.h"
 #include "map_graph_kernels.h"
+#include "map_graph_lists.h"
 
 using namespace mcp;
 
@@ -2306,6 +2307,80 @@ void sd_launch(mcp_map_points* m, int n_kf, const double* T, const int* slot, co
                      (const double*)(dev_in + L.seg_w), m->pts.row(), m->wb.depth.p, (mcp_scene_depth*)(out_pinned + L.sd),
                      want_depths ? (double*)(out_pinned + L.depths) : (double*)nullptr);
 }
+
+// what mcp_ba_write_back and mcp_graph_write_back share before anything is enqueued: the distinct pose chains of the call as slots of the
+// product table (the solver's own chains by number, a chain it does not know by its pose indices) and the checked points
+struct WbPlan {
+  mcp_ba* h; mcp_map_points* m; const std::string& who; int chain_stride;
+  std::vector<WbChain> chains; std::map<std::vector<int>, int> extra; std::vector<WbItem> items;
+  WbPlan(mcp_ba* h_, mcp_map_points* m_, const std::string& who_, int stride) : h(h_), m(m_), who(who_), chain_stride(stride) { m->wb.slot.assign((size_t)ba_bridge_num_chains(h), -1); }
+  int slot_of_solver(int c) {
+    int& s = m->wb.slot[c];
+    if (s < 0) { WbChain C; ba_bridge_chain(h, c, &C.len, C.v); s = (int)chains.size(); chains.push_back(C); }
+    return s;
+  }
+  int slot_of_chain(const int* ids, int len, const char* what, int k) {       // -1: refused
+    int v[MCP_MAX_CHAIN];
+    const int c = ba_bridge_lookup_chain(h, ids, len, v);
+    if (c == -2) { img_fail(who + ": " + what + " " + std::to_string(k) + " is not a chain of poses of this bundle (1.." + std::to_string(MCP_MAX_CHAIN) + " pose ids)"); return -1; }
+    if (c >= 0) return slot_of_solver(c);
+    std::vector<int> key(v, v + len);
+    auto it = extra.find(key);
+    if (it != extra.end()) return it->second;
+    WbChain C; C.len = len; for (int i = 0; i < MCP_MAX_CHAIN; ++i) C.v[i] = i < len ? v[i] : 0;
+    const int s = (int)chains.size(); chains.push_back(C); extra.emplace(key, s);
+    return s;
+  }
+  int slot_of_ids(const int* ids, int len, const char* what, int k) {         // ... of a chain in an array of chain_stride ids per entry
+    if (len > chain_stride) { img_fail(who + ": " + what + " " + std::to_string(k) + " is longer than chain_stride"); return -1; }
+    return slot_of_chain(ids, len, what, k);
+  }
+  int points(int n_points, const int* point_ids, const int* rows, const int* src_chains, const int* src_chain_len) {
+    items.resize((size_t)n_points);
+    if (m->wb.stamp == 0x7fffffff) { m->wb.stamp = 0; std::fill(m->wb.mark.begin(), m->wb.mark.end(), 0); }
+    const int stamp = ++m->wb.stamp;
+    if ((int)m->wb.mark.size() < m->rows) m->wb.mark.resize((size_t)m->rows, 0);
+    for (int k = 0; k < n_points; ++k) {
+      int idx, fixed, c;
+      if (ba_bridge_point(h, point_ids[k], &idx, &fixed, &c)) return img_fail(who + ": point_ids[" + std::to_string(k) + "] = " + std::to_string(point_ids[k]) + " is not a point of this bundle");
+      const int r = rows[k];
+      if (r < 0) return img_fail(who + ": rows[" + std::to_string(k) + "] is negative");
+      if (r >= m->rows || !m->has_rays[r]) return img_fail(who + ": row " + std::to_string(r) + " has no patch rays (mcp_map_points_set_rays)");
+      if (m->wb.mark[r] == stamp) return img_fail(who + ": row " + std::to_string(r) + " appears twice");
+      m->wb.mark[r] = stamp;
+      const int own = slot_of_solver(c);
+      int src = own;
+      if (src_chains && src_chain_len[k] != 0) {
+        src = slot_of_ids(src_chains + (size_t)chain_stride*k, src_chain_len[k], "src_chains of point", k);
+        if (src < 0) return -1;
+      }
+      items[k].pt = idx; items[k].row = r; items[k].own = own; items[k].src2_fixed = 2*src + (fixed ? 1 : 0);
+    }
+    return 0;
+  }
+};
+
+// the chain table and the point kernel of a write-back on the table's stream (inputs on the device); vo: the pinned vectors, or null
+void wb_launch_points(mcp_map_points* m, const BaDeviceState& S, int nslot, const WbChain* chains, double* T_host, int n_points, const WbItem* items, double* vo) {
+  hipLaunchKernelGGL(k_wb_chains, dim3((unsigned)((nslot + 63)/64)), dim3(64), 0, m->st, nslot, chains, S.pose, m->wb.T.p, T_host);
+  if (n_points)
+    hipLaunchKernelGGL(k_wb_points, dim3((unsigned)((n_points + WB_BLOCK - 1)/WB_BLOCK)), dim3(WB_BLOCK), 0, m->st, n_points, items, S.point,
+                       (const double*)m->wb.T.p, m->rays.row(), m->pts.row(), vo, vo ? vo + 3*(size_t)n_points : nullptr, vo ? vo + 6*(size_t)n_points : nullptr);
+}
+// the index of pose `id` in BaDeviceState::pose, -1 when `id` is not a pose.  (ba_bridge_lookup_chain fills its indices only for a chain the
+// solver does not number; a pose that is a one-pose chain of the bundle is read from that chain.)
+int wb_pose_index(const mcp_ba* h, int id) {
+  int v[MCP_MAX_CHAIN] = {0};
+  const int c = ba_bridge_lookup_chain(h, &id, 1, v);
+  if (c == -2) return -1;
+  if (c >= 0) { int len = 0; ba_bridge_chain(h, c, &len, v); }
+  return v[0];
+}
+void wb_copy_vec(const double* vo, int n_points, double* world_out, double* right_out, double* down_out) {
+  if (world_out) std::memcpy(world_out, vo, 24*(size_t)n_points);
+  if (right_out) std::memcpy(right_out, vo + 3*(size_t)n_points, 24*(size_t)n_points);
+  if (down_out) std::memcpy(down_out, vo + 6*(size_t)n_points, 24*(size_t)n_points);
+}
 }  // namespace
 
 extern "C" {
@@ -2389,54 +2464,14 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
   if (sd_check(who, m, n_kf, seg_start, seg_rows, seg_w, &total)) return -1;
   if (n_kf > 0 && (!kf_chains || !kf_chain_len)) return img_fail(who + ": kf_chains / kf_chain_len is NULL");
   if (((n_points > 0 && src_chains) || n_kf > 0) && chain_stride < 1) return img_fail(who + ": chain_stride must be positive");
-  // distinct chains of the call -> slots of the product table (the solver's own chains by number, a chain it does not know by its pose indices)
-  const int nsolver = ba_bridge_num_chains(h);
-  m->wb.slot.assign((size_t)nsolver, -1);
-  std::vector<WbChain> chains;
-  std::map<std::vector<int>, int> extra;
-  auto slot_of_solver = [&](int c) -> int {
-    int& s = m->wb.slot[c];
-    if (s < 0) { WbChain C; ba_bridge_chain(h, c, &C.len, C.v); s = (int)chains.size(); chains.push_back(C); }
-    return s;
-  };
-  auto slot_of_ids = [&](const int* ids, int len, const char* what, int k) -> int {      // -1: refused
-    if (len > chain_stride) { img_fail(who + ": " + what + " " + std::to_string(k) + " is longer than chain_stride"); return -1; }
-    int v[MCP_MAX_CHAIN];
-    const int c = ba_bridge_lookup_chain(h, ids, len, v);
-    if (c == -2) { img_fail(who + ": " + what + " " + std::to_string(k) + " is not a chain of poses of this bundle (1.." + std::to_string(MCP_MAX_CHAIN) + " pose ids)"); return -1; }
-    if (c >= 0) return slot_of_solver(c);
-    std::vector<int> key(v, v + len);
-    auto it = extra.find(key);
-    if (it != extra.end()) return it->second;
-    WbChain C; C.len = len; for (int i = 0; i < MCP_MAX_CHAIN; ++i) C.v[i] = i < len ? v[i] : 0;
-    const int s = (int)chains.size(); chains.push_back(C); extra.emplace(key, s);
-    return s;
-  };
-  std::vector<WbItem> items((size_t)n_points);
-  if (m->wb.stamp == 0x7fffffff) { m->wb.stamp = 0; std::fill(m->wb.mark.begin(), m->wb.mark.end(), 0); }
-  const int stamp = ++m->wb.stamp;
-  if ((int)m->wb.mark.size() < m->rows) m->wb.mark.resize((size_t)m->rows, 0);
-  for (int k = 0; k < n_points; ++k) {
-    int idx, fixed, c;
-    if (ba_bridge_point(h, point_ids[k], &idx, &fixed, &c)) return img_fail(who + ": point_ids[" + std::to_string(k) + "] = " + std::to_string(point_ids[k]) + " is not a point of this bundle");
-    const int r = rows[k];
-    if (r < 0) return img_fail(who + ": rows[" + std::to_string(k) + "] is negative");
-    if (r >= m->rows || !m->has_rays[r]) return img_fail(who + ": row " + std::to_string(r) + " has no patch rays (mcp_map_points_set_rays)");
-    if (m->wb.mark[r] == stamp) return img_fail(who + ": row " + std::to_string(r) + " appears twice");
-    m->wb.mark[r] = stamp;
-    const int own = slot_of_solver(c);
-    int src = own;
-    if (src_chains && src_chain_len[k] != 0) {
-      src = slot_of_ids(src_chains + (size_t)chain_stride*k, src_chain_len[k], "src_chains of point", k);
-      if (src < 0) return -1;
-    }
-    items[k].pt = idx; items[k].row = r; items[k].own = own; items[k].src2_fixed = 2*src + (fixed ? 1 : 0);
-  }
+  WbPlan plan(h, m, who, chain_stride);
+  if (plan.points(n_points, point_ids, rows, src_chains, src_chain_len)) return -1;
   std::vector<int> kf_slot((size_t)n_kf);
   for (int j = 0; j < n_kf; ++j) {
-    kf_slot[j] = slot_of_ids(kf_chains + (size_t)chain_stride*j, kf_chain_len[j], "kf_chains of keyframe", j);
+    kf_slot[j] = plan.slot_of_ids(kf_chains + (size_t)chain_stride*j, kf_chain_len[j], "kf_chains of keyframe", j);
     if (kf_slot[j] < 0) return -1;
   }
+  const std::vector<WbChain>& chains = plan.chains; const std::vector<WbItem>& items = plan.items;
   if (n_points == 0 && n_kf == 0) return 0;
   // ---- every check has passed: from here on things are enqueued ----
   ICK(hipSetDevice(m->device));
@@ -2460,13 +2495,8 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
   ICK(hipMemcpyAsync(m->wb.dev.p, hin, L.in_bytes, hipMemcpyHostToDevice, m->st));
   ICK(hipEventRecord(m->wb.t[1], m->st));
   const char* din = m->wb.dev.p; char* hout = m->wb.out.p;
-  hipLaunchKernelGGL(k_wb_chains, dim3((unsigned)((nslot + 63)/64)), dim3(64), 0, m->st, nslot, (const WbChain*)(din + L.chains), S.pose, m->wb.T.p,
-                     kf_cfw_out ? (double*)(hout + L.T) : (double*)nullptr);
-  if (n_points) {
-    double* vo = want_vec ? (double*)(hout + L.vec) : nullptr;
-    hipLaunchKernelGGL(k_wb_points, dim3((unsigned)((n_points + WB_BLOCK - 1)/WB_BLOCK)), dim3(WB_BLOCK), 0, m->st, n_points, (const WbItem*)(din + L.items), S.point,
-                       (const double*)m->wb.T.p, m->rays.row(), m->pts.row(), vo, vo ? vo + 3*(size_t)n_points : nullptr, vo ? vo + 6*(size_t)n_points : nullptr);
-  }
+  wb_launch_points(m, S, nslot, (const WbChain*)(din + L.chains), kf_cfw_out ? (double*)(hout + L.T) : (double*)nullptr, n_points, (const WbItem*)(din + L.items),
+                   want_vec ? (double*)(hout + L.vec) : (double*)nullptr);
   hipError_t le = hipGetLastError();
   (void)hipEventRecord(m->wb.t[2], m->st);
   if (n_kf) sd_launch(m, n_kf, (const double*)m->wb.T.p, (const int*)(din + L.kf_slot), din, L, hout, want_depths);
@@ -2476,12 +2506,7 @@ int mcp_ba_write_back(mcp_ba* h, mcp_map_points* m, int n_points, const int* poi
   if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
   if (se != hipSuccess) return img_fail(who + ": " + hipGetErrorString(se));
   m->wb.timed = true;
-  if (want_vec) {
-    const double* vo = (const double*)(hout + L.vec);
-    if (world_out) std::memcpy(world_out, vo, 24*(size_t)n_points);
-    if (right_out) std::memcpy(right_out, vo + 3*(size_t)n_points, 24*(size_t)n_points);
-    if (down_out) std::memcpy(down_out, vo + 6*(size_t)n_points, 24*(size_t)n_points);
-  }
+  if (want_vec) wb_copy_vec((const double*)(hout + L.vec), n_points, world_out, right_out, down_out);
   if (n_kf) {
     if (kf_cfw_out) for (int j = 0; j < n_kf; ++j) std::memcpy(kf_cfw_out + 12*(size_t)j, hout + L.T + 96*(size_t)kf_slot[j], 96);
     sd_copy_out(n_kf, (const mcp_scene_depth*)(hout + L.sd), depth_out);
@@ -2598,6 +2623,9 @@ struct mcp_map_graph {
   PinBuf<mcp_bundle_mkf> v_mkfs; PinBuf<mcp_bundle_point> v_points; PinBuf<mcp_bundle_meas> v_meas; PinBuf<mcp_bundle_select_result> h_res;
   int n_mkfs = 0, n_points = 0, n_meas = 0;           // what the views hold
   hipEvent_t t0 = nullptr, t1 = nullptr; bool timed = false;      // mcp_map_bundle_select_last_timing: around the last select's submission
+  // the keyframe lists (map_graph_lists.h): the call's slots (pinned | device), the (key, row) column, the count table, the lists, the
+  // keyframes' poses and the pinned results of mcp_graph_refresh_depth / mcp_graph_debug_kf_lists
+  PinBuf<char> l_in; Buf<char> l_dev; Buf<int2> l_key_row; Buf<int> l_table, l_start, l_rows; Buf<double> l_w, l_cfw; PinBuf<char> l_out;
   ~mcp_map_graph() { if (m && m->st) (void)hipStreamSynchronize(m->st); for (hipEvent_t e : {staged, t0, t1}) if (e) (void)hipEventDestroy(e); }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
   int sync() { ICK(hipStreamSynchronize(m->st)); stage_busy = false; m->stage_busy = false; return 0; }
@@ -3076,6 +3104,238 @@ int mcp_map_bundle_select_host(const mcp_bundle_select_params* p, int ncam, cons
   if (!mk.empty()) std::memcpy(out_mkfs, mk.data(), sizeof(mcp_bundle_mkf)*mk.size());
   if (!pt.empty()) std::memcpy(out_points, pt.data(), sizeof(mcp_bundle_point)*pt.size());
   if (!ms.empty()) std::memcpy(out_meas, ms.data(), sizeof(mcp_bundle_meas)*ms.size());
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- the keyframe lists from the store and the one-call write-back over the graph (include/mcp_img.h mcp_graph_*, map_graph_lists.h) -------
+namespace {
+// the call's slots: distinct, present.  pos_of (MCP_MAP_MAX_MKFS entries) receives the index of each in the call, -1 elsewhere
+int mgl_slots_check(const mcp_map_graph* g, const std::string& who, int n_mkfs, const int* slots, std::vector<int>& pos_of) {
+  if (n_mkfs < 0) return img_fail(who + ": negative MKF count");
+  if (n_mkfs > MCP_MAP_MAX_MKFS) return img_fail(who + ": more than MCP_MAP_MAX_MKFS (" + std::to_string(MCP_MAP_MAX_MKFS) + ") MKFs");
+  if (n_mkfs > 0 && !slots) return img_fail(who + ": slots is NULL");
+  if (g->n_store > MGL_MAX_STORE) return img_fail(who + ": the store is too long for the list passes");
+  pos_of.assign(MCP_MAP_MAX_MKFS, -1);
+  for (int i = 0; i < n_mkfs; ++i) {
+    const int s = slots[i];
+    if (s < 0 || s >= MCP_MAP_MAX_MKFS) return img_fail(who + ": slot " + std::to_string(s) + " is outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
+    if (!(g->h_flags[s] & MCP_MKF_PRESENT)) return img_fail(who + ": MKF slot " + std::to_string(s) + " is not present");
+    if (pos_of[s] >= 0) return img_fail(who + ": slot " + std::to_string(s) + " appears twice");
+    pos_of[s] = i;
+  }
+  return 0;
+}
+// the packed input of the list passes: slot -> index in the call | the call's slots | the solver's pose index of each (write-back only)
+struct MglIn {
+  size_t pos_of = 0, slots = 0, pose_idx = 0, bytes = 0;
+  explicit MglIn(int n_mkfs, size_t at = 0) {
+    size_t o = at;
+    pos_of = o; o = wb_align(o + sizeof(int)*(size_t)MCP_MAP_MAX_MKFS);
+    slots = o; o = wb_align(o + sizeof(int)*(size_t)n_mkfs);
+    pose_idx = o; o = wb_align(o + sizeof(int)*(size_t)n_mkfs);
+    bytes = o - at;
+  }
+  void fill(char* h, const std::vector<int>& pos, int n_mkfs, const int* sl, const int* pose) const {
+    std::memcpy(h + pos_of, pos.data(), sizeof(int)*(size_t)MCP_MAP_MAX_MKFS);
+    if (n_mkfs) std::memcpy(h + slots, sl, sizeof(int)*(size_t)n_mkfs);
+    if (n_mkfs && pose) std::memcpy(h + pose_idx, pose, sizeof(int)*(size_t)n_mkfs);
+  }
+};
+// every buffer of the list passes, sized from n_store, n_mkfs, ncam and nb before the first enqueue (a block that grows is replaced with
+// nothing in flight on the old one); the scene-depth scratch of the table with them
+int mgl_reserve(mcp_map_graph* g, int n_kf, int nb) {
+  const size_t M = (size_t)std::max(g->n_store, 1), K = (size_t)std::max(n_kf, 1);
+  if (g->l_key_row.n < M || g->l_rows.n < M || g->l_w.n < M || g->l_table.n < K*nb || g->l_start.n < K + 1 || g->l_cfw.n < 12*K || g->m->wb.depth.n < M) { if (g->sync()) return -1; }
+  return (g->l_key_row.alloc(M) || g->l_rows.alloc(M) || g->l_w.alloc(M) || g->l_table.alloc(K*nb) || g->l_start.alloc(K + 1) || g->l_cfw.alloc(12*K) || g->m->wb.depth.alloc(M) ||
+          g->grow_points(g->m->rows)) ? -1 : 0;
+}
+// the three list launches on the table's stream (behind one memset of the count table); d_pos_of: on the device
+void mgl_enqueue(mcp_map_graph* g, int n_kf, int nb, const int* d_pos_of) {
+  mcp_map_points* m = g->m;
+  const int M = g->n_store, chunk = mgl_chunk_len(M, nb);
+  (void)hipMemsetAsync(g->l_table.p, 0, sizeof(int)*(size_t)std::max(n_kf, 1)*nb, m->st);
+  hipLaunchKernelGGL(k_mgl_count, dim3(nb), dim3(MGL_BLOCK), 0, m->st, (const MgMeas*)g->store.p, M, chunk, g->rig.ncam, n_kf, m->rows, d_pos_of, (const MgMkf*)g->slots.p,
+                     (const MgPoint*)g->pts.p, g->l_key_row.p, g->l_table.p);
+  hipLaunchKernelGGL(k_mgl_scan, dim3(1), dim3(MGL_BLOCK), 0, m->st, nb, n_kf, g->l_table.p, g->l_start.p);
+  hipLaunchKernelGGL(k_mgl_scatter, dim3(nb), dim3(MGL_BLOCK), 0, m->st, (const int2*)g->l_key_row.p, M, chunk, n_kf, g->l_table.p, (const int*)g->l_start.p,
+                     (const int*)m->cnt.row(), g->l_rows.p, g->l_w.p);
+}
+// k_wb_scene_depth over the device-built lists (T: 12 doubles per pose, slot: pose of keyframe j or null), then the depth store into the slots
+void mgl_depth_enqueue(mcp_map_graph* g, int n_kf, const double* T, const int* slot, const int* d_slots, mcp_scene_depth* sd_pinned) {
+  mcp_map_points* m = g->m;
+  hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)n_kf), dim3(SD_BLOCK), 0, m->st, T, slot, (const int*)g->l_start.p, (const int*)g->l_rows.p, (const double*)g->l_w.p,
+                     m->pts.row(), m->wb.depth.p, sd_pinned, (double*)nullptr);
+  hipLaunchKernelGGL(k_mgl_depth_store, dim3((unsigned)((n_kf + MGL_BLOCK - 1)/MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, n_kf, g->rig.ncam, d_slots, (const mcp_scene_depth*)sd_pinned,
+                     g->slots.p);
+}
+}  // namespace
+
+extern "C" {
+
+int mcp_graph_get_mkfs(mcp_map_graph* g, int first, int count, double* bfw, int* flags, uint8_t* act, double* dep) {
+  if (!g) return img_fail("mcp_graph_get_mkfs: NULL graph");
+  if (first < 0 || count < 0 || (long long)first + count > MCP_MAP_MAX_MKFS) return img_fail("mcp_graph_get_mkfs: bad range");
+  if (count == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  std::vector<MgMkf> tmp((size_t)count);
+  ICK(hipMemcpyAsync(tmp.data(), g->slots.p + first, sizeof(MgMkf)*(size_t)count, hipMemcpyDeviceToHost, g->m->st));
+  if (g->sync()) return -1;
+  const int nc = g->rig.ncam;
+  for (int k = 0; k < count; ++k) {
+    if (bfw) std::memcpy(bfw + 12*(size_t)k, tmp[k].bfw, 96);
+    if (flags) flags[k] = tmp[k].flags;
+    for (int c = 0; c < nc; ++c) { if (act) act[(size_t)k*nc + c] = tmp[k].active[c]; if (dep) dep[(size_t)k*nc + c] = tmp[k].depth[c]; }
+  }
+  return 0;
+}
+
+int mcp_graph_debug_kf_lists(mcp_map_graph* g, int n_mkfs, const int* slots, int blocks, int* seg_start, int cap, int* seg_rows, double* seg_w) {
+  const std::string who = "mcp_graph_debug_kf_lists";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (blocks < 0 || blocks > MGL_MAX_BLOCKS) return img_fail(who + ": blocks outside 0.." + std::to_string(MGL_MAX_BLOCKS));
+  if (!seg_start || cap < 0 || (cap > 0 && (!seg_rows || !seg_w))) return img_fail(who + ": bad arguments");
+  std::vector<int> pos_of;
+  if (mgl_slots_check(g, who, n_mkfs, slots, pos_of)) return -1;
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int n_kf = n_mkfs*g->rig.ncam, nb = blocks ? blocks : mgl_default_blocks(g->n_store);
+  const MglIn L(n_mkfs);
+  const size_t o_rows = wb_align(sizeof(int)*((size_t)n_kf + 1)), o_w = wb_align(o_rows + sizeof(int)*(size_t)std::max(g->n_store, 1));
+  if (g->l_in.alloc(L.bytes) || g->l_dev.alloc(L.bytes) || g->l_out.alloc(o_w + 8*(size_t)std::max(g->n_store, 1)) || mgl_reserve(g, n_kf, nb)) return -1;
+  L.fill(g->l_in.p, pos_of, n_mkfs, slots, nullptr);
+  Drain drain{m, true};
+  ICK(hipMemcpyAsync(g->l_dev.p, g->l_in.p, L.bytes, hipMemcpyHostToDevice, m->st));
+  mgl_enqueue(g, n_kf, nb, (const int*)(g->l_dev.p + L.pos_of));
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(g->l_out.p, g->l_start.p, sizeof(int)*((size_t)n_kf + 1), hipMemcpyDeviceToHost, m->st));
+  if (g->sync()) return -1;
+  std::memcpy(seg_start, g->l_out.p, sizeof(int)*((size_t)n_kf + 1));
+  const int total = seg_start[n_kf];
+  if (total > cap) { drain.armed = false; return img_fail(who + ": the lists hold " + std::to_string(total) + " entries, the caller's arrays " + std::to_string(cap)); }
+  if (total) {
+    ICK(hipMemcpyAsync(g->l_out.p + o_rows, g->l_rows.p, sizeof(int)*(size_t)total, hipMemcpyDeviceToHost, m->st));
+    ICK(hipMemcpyAsync(g->l_out.p + o_w, g->l_w.p, 8*(size_t)total, hipMemcpyDeviceToHost, m->st));
+    if (g->sync()) return -1;
+    std::memcpy(seg_rows, g->l_out.p + o_rows, sizeof(int)*(size_t)total);
+    std::memcpy(seg_w, g->l_out.p + o_w, 8*(size_t)total);
+  }
+  drain.armed = false;
+  return total;
+}
+
+int mcp_graph_refresh_depth(mcp_map_graph* g, int n_mkfs, const int* slots, mcp_scene_depth* depth_out) {
+  const std::string who = "mcp_graph_refresh_depth";
+  if (!g) return img_fail(who + ": NULL graph");
+  std::vector<int> pos_of;
+  if (mgl_slots_check(g, who, n_mkfs, slots, pos_of)) return -1;
+  if (n_mkfs == 0) return 0;
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int n_kf = n_mkfs*g->rig.ncam, nb = mgl_default_blocks(g->n_store);
+  const MglIn L(n_mkfs);
+  if (g->l_in.alloc(L.bytes) || g->l_dev.alloc(L.bytes) || g->l_out.alloc(sizeof(mcp_scene_depth)*(size_t)n_kf) || mgl_reserve(g, n_kf, nb)) return -1;
+  L.fill(g->l_in.p, pos_of, n_mkfs, slots, nullptr);
+  mcp_scene_depth* sd = reinterpret_cast<mcp_scene_depth*>(g->l_out.p);
+  const int* d_slots = (const int*)(g->l_dev.p + L.slots);
+  Drain drain{m, true};
+  m->wb.invalidate();
+  ICK(hipEventRecord(m->wb.t[0], m->st));
+  ICK(hipMemcpyAsync(g->l_dev.p, g->l_in.p, L.bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->wb.t[1], m->st)); ICK(hipEventRecord(m->wb.t[2], m->st));
+  mgl_enqueue(g, n_kf, nb, (const int*)(g->l_dev.p + L.pos_of));
+  hipLaunchKernelGGL(k_mgl_cfw, dim3((unsigned)((n_kf + MGL_BLOCK - 1)/MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, g->rig, n_kf, d_slots, (const MgMkf*)g->slots.p, g->l_cfw.p, (double*)nullptr);
+  mgl_depth_enqueue(g, n_kf, (const double*)g->l_cfw.p, nullptr, d_slots, sd);
+  const hipError_t le = hipGetLastError();
+  (void)hipEventRecord(m->wb.t[3], m->st);
+  if (g->sync()) return -1;
+  drain.armed = false;
+  if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
+  m->wb.timed = true;
+  sd_copy_out(n_kf, sd, depth_out);
+  return 0;
+}
+
+int mcp_graph_write_back(mcp_ba* h, mcp_map_graph* g, int n_points, const int* point_ids, const int* rows, const int* src_chains, int chain_stride,
+                         const int* src_chain_len, double* world_out, double* right_out, double* down_out,
+                         int n_mkfs, const int* slots, const int* mkf_pose_ids, const int* cam_pose_ids,
+                         double* kf_cfw_out, mcp_scene_depth* depth_out, double* bfw_out) {
+  const std::string who = "mcp_graph_write_back";
+  if (!h) return img_fail(who + ": NULL solver handle");
+  if (!g) return img_fail(who + ": NULL graph");
+  mcp_map_points* m = g->m;
+  BaDeviceState S;
+  if (ba_bridge_state(h, who.c_str(), &S)) return -1;
+  if (S.device != m->device) return img_fail(who + ": the table lives on device " + std::to_string(m->device) + ", the solver on device " + std::to_string(S.device));
+  if (n_points < 0) return img_fail(who + ": negative point count");
+  if (n_points > 0 && (!point_ids || !rows)) return img_fail(who + ": point_ids / rows is NULL");
+  if (n_points > 0 && src_chains && !src_chain_len) return img_fail(who + ": src_chain_len is NULL");
+  if (n_points > 0 && src_chains && chain_stride < 1) return img_fail(who + ": chain_stride must be positive");
+  std::vector<int> pos_of;
+  if (mgl_slots_check(g, who, n_mkfs, slots, pos_of)) return -1;
+  if (n_mkfs > 0 && (!mkf_pose_ids || !cam_pose_ids)) return img_fail(who + ": mkf_pose_ids / cam_pose_ids is NULL");
+  const int nc = g->rig.ncam, n_kf = n_mkfs*nc;
+  std::vector<int> pose_idx((size_t)n_mkfs), kf_slot((size_t)n_kf);
+  for (int i = 0; i < n_mkfs; ++i) {
+    pose_idx[i] = wb_pose_index(h, mkf_pose_ids[i]);
+    if (pose_idx[i] < 0 || pose_idx[i] >= S.npose) return img_fail(who + ": mkf_pose_ids[" + std::to_string(i) + "] = " + std::to_string(mkf_pose_ids[i]) + " is not a pose of this bundle");
+  }
+  for (int c = 0; c < (n_mkfs ? nc : 0); ++c)
+    if (wb_pose_index(h, cam_pose_ids[c]) < 0) return img_fail(who + ": cam_pose_ids[" + std::to_string(c) + "] = " + std::to_string(cam_pose_ids[c]) + " is not a pose of this bundle");
+  WbPlan plan(h, m, who, chain_stride);
+  if (plan.points(n_points, point_ids, rows, src_chains, src_chain_len)) return -1;
+  for (int j = 0; j < n_kf; ++j) {
+    const int ids[2] = {mkf_pose_ids[j/nc], cam_pose_ids[j % nc]};
+    kf_slot[j] = plan.slot_of_chain(ids, 2, "the chain of keyframe", j);
+    if (kf_slot[j] < 0) return -1;
+  }
+  if (n_points == 0 && n_mkfs == 0) return 0;
+  // ---- every check has passed: from here on things are enqueued ----
+  ICK(hipSetDevice(m->device));
+  const int nslot = (int)plan.chains.size(), nb = mgl_default_blocks(g->n_store);
+  const bool want_vec = n_points > 0 && (world_out || right_out || down_out);
+  const WbLayout W(nslot, n_points, n_kf, 0, want_vec, false);                 // (its list fields stay empty: the lists are built on the device)
+  const MglIn L(n_mkfs, W.in_bytes);
+  const size_t in_bytes = W.in_bytes + L.bytes, o_bfw = W.out_bytes, out_bytes = o_bfw + 96*(size_t)n_mkfs;
+  if (m->wb.in.alloc(in_bytes) || m->wb.dev.alloc(in_bytes) || m->wb.out.alloc(out_bytes) || m->wb.T.alloc(12*(size_t)nslot) || mgl_reserve(g, n_kf, nb)) return -1;
+  char* hin = m->wb.in.p;
+  std::memcpy(hin + W.chains, plan.chains.data(), sizeof(WbChain)*(size_t)nslot);
+  if (n_points) std::memcpy(hin + W.items, plan.items.data(), sizeof(WbItem)*(size_t)n_points);
+  if (n_kf) std::memcpy(hin + W.kf_slot, kf_slot.data(), sizeof(int)*(size_t)n_kf);
+  L.fill(hin, pos_of, n_mkfs, slots, pose_idx.data());
+  Drain drain{m, true};
+  // the table's stream waits for whatever the solver's stream still has to write of the state
+  ICK(hipEventRecord(m->wb.ev, S.stream));
+  ICK(hipStreamWaitEvent(m->st, m->wb.ev, 0));
+  m->wb.invalidate();
+  ICK(hipEventRecord(m->wb.t[0], m->st));
+  ICK(hipMemcpyAsync(m->wb.dev.p, hin, in_bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipEventRecord(m->wb.t[1], m->st));
+  const char* din = m->wb.dev.p; char* hout = m->wb.out.p;
+  wb_launch_points(m, S, nslot, (const WbChain*)(din + W.chains), kf_cfw_out ? (double*)(hout + W.T) : (double*)nullptr, n_points, (const WbItem*)(din + W.items),
+                   want_vec ? (double*)(hout + W.vec) : (double*)nullptr);
+  hipError_t le = hipGetLastError();
+  (void)hipEventRecord(m->wb.t[2], m->st);
+  if (n_mkfs) {
+    const int* d_slots = (const int*)(din + L.slots);
+    hipLaunchKernelGGL(k_mgl_pose_store, dim3((unsigned)((12*n_mkfs + MGL_BLOCK - 1)/MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, n_mkfs, d_slots, (const int*)(din + L.pose_idx), S.pose,
+                       g->slots.p, bfw_out ? (double*)(hout + o_bfw) : (double*)nullptr);
+    mgl_enqueue(g, n_kf, nb, (const int*)(din + L.pos_of));
+    mgl_depth_enqueue(g, n_kf, (const double*)m->wb.T.p, (const int*)(din + W.kf_slot), d_slots, (mcp_scene_depth*)(hout + W.sd));
+  }
+  if (le == hipSuccess) le = hipGetLastError();
+  (void)hipEventRecord(m->wb.t[3], m->st);
+  if (g->sync()) return -1;                                           // the one wait: the solver's memory is not read after this
+  drain.armed = false;
+  if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
+  m->wb.timed = true;
+  if (want_vec) wb_copy_vec((const double*)(hout + W.vec), n_points, world_out, right_out, down_out);
+  if (n_mkfs) {
+    if (kf_cfw_out) for (int j = 0; j < n_kf; ++j) std::memcpy(kf_cfw_out + 12*(size_t)j, hout + W.T + 96*(size_t)kf_slot[j], 96);
+    sd_copy_out(n_kf, (const mcp_scene_depth*)(hout + W.sd), depth_out);
+    if (bfw_out) std::memcpy(bfw_out, hout + o_bfw, 96*(size_t)n_mkfs);
+  }
   return 0;
 }
 

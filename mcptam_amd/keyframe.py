@@ -58,6 +58,7 @@ IMG_SYMBOLS = [
     "mcp_map_graph_add_meas", "mcp_map_graph_erase_meas", "mcp_map_graph_erase_mkf", "mcp_map_graph_compact", "mcp_map_graph_num_meas",
     "mcp_map_graph_get_meas", "mcp_map_graph_good_counts", "mcp_map_graph_check", "mcp_map_bundle_select", "mcp_map_bundle_mkfs_view",
     "mcp_map_bundle_points_view", "mcp_map_bundle_meas_view", "mcp_map_bundle_select_host", "mcp_map_bundle_select_last_timing",
+    "mcp_graph_refresh_depth", "mcp_graph_write_back", "mcp_graph_debug_kf_lists", "mcp_graph_kf_lists_host", "mcp_graph_get_mkfs",
 ]
 _BOUND = False
 

@@ -5,7 +5,10 @@ BundleAdjustAll on it and returns the arrays BundleAdjusterMulti::BundleAdjust p
 MapGraph is the class over the ABI; problem_arrays turns a multi-mode synth.Problem into the flat arrays every layer takes (slots = MKF
 indices, rows = point indices); bundle_select_host is mcp_map_bundle_select_host (no device); bundle_select_ref is the numpy restatement,
 written from the reference (src/BundleAdjusterBase.cc:141-265, src/BundleAdjusterMulti.cc:81-200, src/KeyFrame.cc:715-747, 903-927);
-selection_problem makes the synth.Problem a selection describes, which Problem.populate replays into a ChainBundle as it is."""
+selection_problem makes the synth.Problem a selection describes, which Problem.populate replays into a ChainBundle as it is.
+
+The keyframe lists of AdjustAndUpdate's write-back come from the same store (mcp_graph_*): MapGraph.debug_kf_lists / refresh_depth / write_back
+on the device, kf_lists_host (mcp_graph_kf_lists_host, no device) and kf_lists_ref, the numpy restatement (src/KeyFrame.cc:549-570, 851-869)."""
 import ctypes
 
 import numpy as np
@@ -53,6 +56,9 @@ GRAPH_SYMBOLS = [
     "mcp_map_bundle_points_view", "mcp_map_bundle_meas_view", "mcp_map_bundle_select_host", "mcp_map_bundle_select_last_timing",
 ]
 
+GRAPH_LIST_SYMBOLS = ["mcp_graph_refresh_depth", "mcp_graph_write_back", "mcp_graph_debug_kf_lists", "mcp_graph_kf_lists_host", "mcp_graph_get_mkfs"]
+LIST_BLOCK, LIST_MAX_BLOCKS = 256, 64          # map_graph_lists.h: entries of a tile, chunks at the most (the default grid: one tile per chunk up to that)
+
 _BOUND = False
 
 
@@ -81,6 +87,11 @@ def lib():
             f.restype = vp
             f.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
         L.mcp_map_bundle_select_host.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, ip, vp]
+        L.mcp_graph_refresh_depth.argtypes = [vp, ip, vp, vp]
+        L.mcp_graph_write_back.argtypes = [vp, vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]
+        L.mcp_graph_debug_kf_lists.argtypes = [vp, ip, vp, ip, vp, ip, vp, vp]
+        L.mcp_graph_get_mkfs.argtypes = [vp, ip, ip, vp, vp, vp, vp]
+        L.mcp_graph_kf_lists_host.argtypes = [ip, ip, vp, vp, ip, ip, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, ip, vp, vp]
         _BOUND = True
     return L
 
@@ -187,6 +198,56 @@ def bundle_select_host(a, params):
                                           M, ms.ctypes.data)
     _chk(rc, "map_bundle_select_host")
     return res, mk[:res.n_adjust + res.n_fixed].copy(), pt[:res.n_points].copy(), ms[:res.n_meas].copy()
+
+
+# ---- the keyframe lists: mcp_graph_kf_lists_host and the numpy restatement ----------------------------------------------------------------------
+def _list_counts(a, n_rows):
+    """(inlier, outlier) of the n_rows table rows: a["inlier"] / a["outlier"] where given, (1, 0) otherwise."""
+    i = np.ones(n_rows, dtype=np.int32) if a.get("inlier") is None else _i32(a["inlier"], (n_rows,))
+    o = np.zeros(n_rows, dtype=np.int32) if a.get("outlier") is None else _i32(a["outlier"], (n_rows,))
+    return i, o
+
+
+def kf_lists_host(a, slots, n_rows=None):
+    """mcp_graph_kf_lists_host over the flat arrays `a` (problem_arrays' keys; optional "inlier" / "outlier" count columns, (1, 0) without):
+    (seg_start, seg_rows, seg_w) of the keyframes (slots[i], c).  n_rows: the table's rows when it has more than the len(a["pt_flags"]) graph
+    columns written.  Needs no device.  A refusal raises RuntimeError."""
+    P, Np, M, C = len(a["mkf_flags"]), len(a["pt_flags"]), len(a["ms_mkf"]), int(a["ncam"])
+    n_rows = Np if n_rows is None else int(n_rows)
+    mf, act, pf = _i32(a["mkf_flags"], (P,)), _u8(a["kf_active"], (P, C)), _i32(a["pt_flags"], (Np,))
+    inl, outl = _list_counts(a, n_rows)
+    mm, mc, mr, al = _i32(a["ms_mkf"], (M,)), _i32(a["ms_cam"], (M,)), _i32(a["ms_row"], (M,)), _u8(a["ms_alive"], (M,))
+    sl = _i32(slots)
+    ss = np.zeros(len(sl) * C + 1, dtype=np.int32)
+    sr, sw = np.zeros(max(M, 1), dtype=np.int32), np.zeros(max(M, 1))
+    tot = _chk(lib().mcp_graph_kf_lists_host(C, P, mf.ctypes.data, act.ctypes.data, n_rows, Np, pf.ctypes.data, inl.ctypes.data, outl.ctypes.data, M, mm.ctypes.data,
+                                             mc.ctypes.data, mr.ctypes.data, al.ctypes.data, len(sl), sl.ctypes.data, ss.ctypes.data, M, sr.ctypes.data, sw.ctypes.data),
+               "graph_kf_lists_host")
+    return ss, sr[:tot].copy(), sw[:tot].copy()
+
+
+def kf_lists_ref(a, slots, n_rows=None):
+    """KeyFrame::GetPointDepthsAndWeights (src/KeyFrame.cc:549-570) with the mbActive filter of MultiKeyFrame::RefreshSceneDepthRobust
+    (:851-869) over the flat arrays, in numpy: keyframe j = i * ncam + c is (slots[i], c); its list is the alive store entries of that keyframe,
+    if it is active, whose row is in the table and not bad (a row past the written graph columns is bad), in store order -- a stable argsort
+    over the keys of the kept entries.  Weights: inlier / (inlier + outlier), sum and quotient in double.  Returns (seg_start, seg_rows, seg_w) as kf_lists_host does."""
+    P, Np, C = len(a["mkf_flags"]), len(a["pt_flags"]), int(a["ncam"])
+    n_rows = Np if n_rows is None else int(n_rows)
+    sl = np.asarray(slots, dtype=np.int64)
+    pos = -np.ones(MAX_MKFS, dtype=np.int64)
+    pos[sl] = np.arange(len(sl))
+    mm, mc, mr = (np.asarray(a[k]).astype(np.int64) for k in ("ms_mkf", "ms_cam", "ms_row"))
+    ok = (np.asarray(a["ms_alive"]) != 0) & (mm >= 0) & (mm < MAX_MKFS) & (mc >= 0) & (mc < C) & (mr >= 0) & (mr < n_rows)
+    e = np.flatnonzero(ok)
+    act = np.zeros((MAX_MKFS, C), dtype=bool); act[:P] = np.asarray(a["kf_active"]).reshape(P, C) != 0
+    bad = np.ones(n_rows, dtype=bool); bad[:Np] = (np.asarray(a["pt_flags"]) & GP_BAD) != 0
+    e = e[(pos[mm[e]] >= 0) & act[mm[e], mc[e]] & ~bad[mr[e]]]
+    key = pos[mm[e]] * C + mc[e]
+    e = e[np.argsort(key, kind="stable")]
+    seg_start = np.concatenate([[0], np.cumsum(np.bincount(key, minlength=len(sl) * C))]).astype(np.int32)
+    inl, outl = _list_counts(a, n_rows)
+    rows = mr[e].astype(np.int32)
+    return seg_start, rows, inl[rows].astype(np.float64) / (inl[rows].astype(np.float64) + outl[rows].astype(np.float64))
 
 
 # ---- the numpy restatement, from the reference -----------------------------------------------------------------------------------------------
@@ -323,11 +384,15 @@ class MapGraph:
         self._h = self._L.mcp_map_graph_create(table._h, self.ncam, self.cam_from_base.ctypes.data)
         if not self._h:
             raise RuntimeError("mcp_map_graph_create failed: " + _cb.last_error())
+        table._open_graphs = getattr(table, "_open_graphs", 0) + 1     # the table's handle is destroyed after its last graph's (MapPointTable.close)
 
     def close(self):
         if getattr(self, "_h", None):
             self._L.mcp_map_graph_destroy(self._h)
             self._h = None
+            self.table._open_graphs -= 1
+            if self.table._open_graphs == 0 and getattr(self.table, "_close_pending", False):
+                self.table.close()
 
     def __del__(self):
         self.close()
@@ -443,6 +508,65 @@ class MapGraph:
         ms = ctypes.c_double(0.0)
         _chk(self._L.mcp_map_bundle_select_last_timing(self._h, ctypes.addressof(ms)), "map_bundle_select_last_timing")
         return ms.value
+
+    # ---- the keyframe lists and the write-back over the graph (mcp_graph_*) ----
+    def get_mkfs(self, first=0, count=MAX_MKFS):
+        """MKF slots first .. first+count-1 read back: dict(base_from_world (count, 12), flags, kf_active (count, ncam), kf_depth_mean)."""
+        n = max(int(count), 1)
+        o = dict(base_from_world=np.zeros((n, 12)), flags=np.zeros(n, dtype=np.int32), kf_active=np.zeros((n, self.ncam), dtype=np.uint8), kf_depth_mean=np.zeros((n, self.ncam)))
+        _chk(self._L.mcp_graph_get_mkfs(self._h, int(first), int(count), *[o[k].ctypes.data for k in ("base_from_world", "flags", "kf_active", "kf_depth_mean")]), "graph_get_mkfs")
+        return {k: v[:count] for k, v in o.items()}
+
+    def debug_kf_lists(self, slots, blocks=0):
+        """mcp_graph_debug_kf_lists: (seg_start, seg_rows, seg_w) of the keyframes (slots[i], c) as the device builds them; blocks: the chunk
+        count forced (1..LIST_MAX_BLOCKS), 0 for the default grid."""
+        sl = _i32(slots)
+        cap = max(self.num_meas()[1], 1)
+        ss = np.zeros(len(sl) * self.ncam + 1, dtype=np.int32)
+        sr, sw = np.zeros(cap, dtype=np.int32), np.zeros(cap)
+        tot = _chk(self._L.mcp_graph_debug_kf_lists(self._h, len(sl), sl.ctypes.data, int(blocks), ss.ctypes.data, cap, sr.ctypes.data, sw.ctypes.data), "graph_debug_kf_lists")
+        return ss, sr[:tot].copy(), sw[:tot].copy()
+
+    def refresh_depth(self, slots):
+        """mcp_graph_refresh_depth: MultiKeyFrame::RefreshSceneDepthRobust of the named MKFs at the graph's own poses; the means go into the
+        graph.  Returns the (len(slots) * ncam,) SCENE_DEPTH_DTYPE records."""
+        from .pvs import SCENE_DEPTH_DTYPE
+        sl = _i32(slots)
+        out = np.zeros(len(sl) * self.ncam, dtype=SCENE_DEPTH_DTYPE)
+        _chk(self._L.mcp_graph_refresh_depth(self._h, len(sl), sl.ctypes.data, out.ctypes.data), "graph_refresh_depth")
+        return out
+
+    def write_back(self, bundle, point_ids, rows, src_chains=None, src_chain_len=None, slots=(), mkf_pose_ids=(), cam_pose_ids=(), outputs=True):
+        """mcp_graph_write_back: AdjustAndUpdate from `bundle` into the table and the graph.  The point half is MapPointTable.write_back's;
+        keyframe i * ncam + c is the chain {mkf_pose_ids[i], cam_pose_ids[c]} and the graph's (slots[i], c).  Returns a dict: world_pos,
+        pixel_right_w, pixel_down_w (n, 3), kf_cam_from_world (n_kf, 12), depth (SCENE_DEPTH_DTYPE), base_from_world (n_mkfs, 12) -- or None
+        with outputs=False.  The adjusted poses (96 B per MKF) are fetched either way: the host's copy self.base_from_world follows."""
+        from .pvs import SCENE_DEPTH_DTYPE
+        pid, rw = _i32(point_ids), _i32(rows)
+        n = len(pid)
+        if len(rw) != n:
+            raise ValueError("write_back: point_ids and rows differ in length")
+        stride, sc, sl_ = 1, None, None
+        if src_chains is not None:
+            sc = np.ascontiguousarray(np.asarray(src_chains, dtype=np.int32).reshape(n, -1))
+            sl_ = _i32(src_chain_len, (n,))
+            stride = sc.shape[1]
+        s, mp, cp = _i32(slots), _i32(mkf_pose_ids), _i32(cam_pose_ids)
+        if len(mp) != len(s) or (len(s) and len(cp) != self.ncam):
+            raise ValueError("write_back: one pose id per slot and one per camera of the rig")
+        n_kf = len(s) * self.ncam
+        res = None
+        if outputs:
+            res = dict(world_pos=np.zeros((n, 3)), pixel_right_w=np.zeros((n, 3)), pixel_down_w=np.zeros((n, 3)), kf_cam_from_world=np.zeros((n_kf, 12)),
+                       depth=np.zeros(n_kf, dtype=SCENE_DEPTH_DTYPE), base_from_world=np.zeros((len(s), 12)))
+        bfw = res["base_from_world"] if outputs else np.zeros((len(s), 12))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        o = (lambda k: res[k].ctypes.data) if outputs else (lambda k: None)
+        _chk(self._L.mcp_graph_write_back(bundle._h, self._h, n, ptr(pid), ptr(rw), ptr(sc), stride, ptr(sl_), o("world_pos"), o("pixel_right_w"), o("pixel_down_w"),
+                                          len(s), ptr(s), ptr(mp), ptr(cp), o("kf_cam_from_world"), o("depth"), bfw.ctypes.data), "graph_write_back")
+        if len(s):
+            self.base_from_world[s] = bfw
+        return res
 
     def select_raw(self, params, copy=True):
         """mcp_map_bundle_select: (SelectResult, mkfs, points, meas)."""

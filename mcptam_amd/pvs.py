@@ -109,6 +109,9 @@ class MapPointTable:
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_open_graphs", 0) > 0:           # a map graph (map_graph.MapGraph) is still open on this table and reads it when it
+                self._close_pending = True                     # is destroyed: the table's handle goes when the last of them has been closed
+                return
             self._L.mcp_map_points_destroy(self._h)
             self._h = None
 

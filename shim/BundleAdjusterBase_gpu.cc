@@ -1,9 +1,11 @@
 // BundleAdjusterBase_gpu.cc -- BundleAdjustAll / BundleAdjustRecent and the population of BundleAdjusterMulti::BundleAdjust over the
-// device-resident map graph (include/mcp_img.h: mcp_map_graph_*, mcp_map_bundle_select).
+// device-resident map graph (include/mcp_img.h: mcp_map_graph_*, mcp_map_bundle_select), and AdjustAndUpdate's write-back over the same graph
+// (mcp_graph_write_back, mcp_graph_refresh_depth).
 //
 // Replaces src/BundleAdjusterBase.cc:141-184 (BundleAdjustAll) and :188-265 (BundleAdjustRecent) -- delete those two bodies -- and the
 // population loops of src/BundleAdjusterMulti.cc:81-200, which become BundleAdjusterMulti::BundleAdjustSelected below; the solve and the
 // outlier decoding behind them (:205-264) stay as they are, fed by the id vectors this file fills instead of the std::maps.
+// Replaces BundleAdjusterMulti::AdjustAndUpdate (src/BundleAdjusterMulti.cc:286-334) as well: one mcp_graph_write_back.
 // Header deltas:
 //   include/mcptam/Map.h, class Map:          mcp_map_points* mpMapTable; mcp_map_graph* mpMapGraph;      (created with the map, destroyed --
 //                                             graph first -- with it; the table is the tracker's, shim/Tracker_gpu.cc option (b))
@@ -11,8 +13,10 @@
 //   include/mcptam/KeyFrame.h, KeyFrame:      int mnCamIndex;      (index of mCamName in the rig the graph was created with)
 //   include/mcptam/MapPoint.h, MapPoint:      int mnTableRow;      (shim/MapMakerServerBase_gpu.cc has it already)
 //   include/mcptam/BundleAdjusterMulti.h:     std::vector<std::string> mvCamNames (the rig's camera names in graph order); std::vector<int> mvMKFBundleID,
-//                                             mvCamBundleID, mvPointBundleID, mvWriteBackRows, mvWriteBackKFChains; int SolveAndDecode(...): the body
-//                                             of src/BundleAdjusterMulti.cc:205-264 moved into a member, reading these vectors instead of the maps
+//                                             mvCamBundleID, mvPointBundleID, mvWriteBackRows, mvWriteBackSlots; int SolveAndDecode(...): the body
+//                                             of src/BundleAdjusterMulti.cc:205-264 moved into a member, reading these vectors instead of the maps;
+//                                             void AdjustAndUpdate(ChainBundle&) takes the bundle alone (the sets it walked are the vectors above)
+//   shim/ChainBundle.h:                       mcp_ba* Handle() { return mpHandle; }   (AdjustAndUpdate hands it to mcp_graph_write_back)
 //   include/mcptam/BundleAdjusterBase.h:      virtual int BundleAdjustSelected(const mcp_bundle_select_result&, std::vector<std::pair<KeyFrame*,
 //                                             MapPoint*> >& vOutliers, bool bRecent) = 0;   std::vector<MultiKeyFrame*> mvpSlotMKF;
 //                                             std::vector<MapPoint*> mvpRowPoint;  (slot -> MKF, row -> point: kept by the map maker)
@@ -40,6 +44,14 @@ void Pose12(const TooN::SE3<>& se3, double* a)
   for(int r = 0; r < 3; ++r)
     a[9 + r] = se3.get_translation()[r];
 }
+TooN::SE3<> SE3From12(const double* a)
+{
+  TooN::Matrix<3> m3;
+  for(int r = 0; r < 3; ++r)
+    for(int c = 0; c < 3; ++c)
+      m3(r, c) = a[3 * r + c];
+  return TooN::SE3<>(TooN::SO3<>(m3), TooN::makeVector(a[9], a[10], a[11]));
+}
 
 int RunSelect(Map& map, int nMode, MultiKeyFrame* pNewest, mcp_bundle_select_result& res)
 {
@@ -66,8 +78,8 @@ int RunSelect(Map& map, int nMode, MultiKeyFrame* pNewest, mcp_bundle_select_res
 
 // ---- where the graph is kept current (the map maker's side; each is a few lines next to the reference's own bookkeeping) -------------------
 // MultiKeyFrame enters the map (MapMakerServerBase::AddMultiKeyFrameFromTopOfQueue and the two initialisers): take a free slot, then mcp_map_graph_update_mkfs with its pose, flags and the mbActive / mdSceneDepthMean of its keyframes.
-// The same call after every adjustment that moved it (AdjustAndUpdate, src/BundleAdjusterMulti.cc:293-304), after RefreshSceneDepth, and when
-// mbFixed / mbBad change (MarkFurthestMultiKeyFrameAsBad).
+// The same call when mbFixed / mbBad / mbActive change (MarkFurthestMultiKeyFrameAsBad) or the host moves a pose itself.  NOT after an adjustment
+// and not after a scene-depth refresh: mcp_graph_write_back and mcp_graph_refresh_depth leave the poses and depth means they produce in the graph.
 void GraphUploadMKFs(Map& map, const std::vector<MultiKeyFrame*>& vpMKFs, const std::vector<std::string>& vCamNames)
 {
   const int n = (int)vpMKFs.size(), nc = (int)vCamNames.size();
@@ -246,19 +258,85 @@ int BundleAdjusterMulti::BundleAdjustSelected(const mcp_bundle_select_result& re
   }
   multiBundle.AddMeasurements(nMeas, vMeasChains.data(), 2, vMeasLen.data(), vMeasPoint.data(), vUV.data(), vSigmaSq.data(), vMeasCam.data());
 
-  // what mcp_ba_write_back takes comes from the same views: point_ids = mvPointBundleID, rows = points[i].row, and one kf_chain
-  // {mvMKFBundleID[i], mvCamBundleID[c]} per keyframe of the bundle's MKFs (AdjustAndUpdate, shim/ChainBundle.cc)
+  // what mcp_graph_write_back takes comes from the same views: point_ids = mvPointBundleID, rows = points[i].row, slots = mkfs[i].slot with
+  // mvMKFBundleID[i] as their pose ids and mvCamBundleID as the rig's.  No list is built here: the keyframes' lists come from the graph's store.
   mvWriteBackRows.resize(nPoints);
   for(int i = 0; i < nPoints; ++i)
     mvWriteBackRows[i] = pPoints[i].row;
-  mvWriteBackKFChains.clear();
+  mvWriteBackSlots.resize(nMKFs);
   for(int i = 0; i < nMKFs; ++i)
-    for(unsigned c = 0; c < mvCamNames.size(); ++c)
-    {
-      mvWriteBackKFChains.push_back(mvMKFBundleID[i]);
-      mvWriteBackKFChains.push_back(mvCamBundleID[c]);
-    }
+    mvWriteBackSlots[i] = pMKFs[i].slot;
 
   // from here on src/BundleAdjusterMulti.cc:205-264 as it stands, with the vectors above in place of the maps
   return SolveAndDecode(multiBundle, pMKFs, nMKFs, pPoints, nPoints, vOutliers);
+}
+
+// ---- AdjustAndUpdate (src/BundleAdjusterMulti.cc:286-334) in one call ------------------------------------------------------------------------
+// The reference refreshes every keyframe's pose, every point's position and pixel vectors, and the scene depth of every keyframe of the bundle's
+// MKFs.  mcp_graph_write_back does the three on the device: the points from the solver's state, the MKF poses copied into the graph, the
+// keyframes' lists built from the graph's store (alive, active keyframe, row not bad; weights from the table's count column), the scene depth on
+// them and the new depth means stored in the graph.  The walk over mmpMeasurements that built seg_start / seg_rows / seg_weights is gone, and so is
+// GraphUploadMKFs after an adjustment.  What comes back is what the host objects mirror: poses and depth statistics.
+void BundleAdjusterMulti::AdjustAndUpdate(ChainBundle& multiBundle)
+{
+  const int nMKFs = (int)mvWriteBackSlots.size(), nc = (int)mvCamNames.size(), nPoints = (int)mvWriteBackRows.size();
+  std::vector<double> vWorld(3 * nPoints), vRight(3 * nPoints), vDown(3 * nPoints), vCamFromWorld(12 * nMKFs * nc), vBaseFromWorld(12 * nMKFs);
+  std::vector<mcp_scene_depth> vDepth(nMKFs * nc);
+  if(mcp_graph_write_back(multiBundle.Handle(), mMap.mpMapGraph, nPoints, mvPointBundleID.data(), mvWriteBackRows.data(), NULL, 2, NULL, vWorld.data(),
+                          vRight.data(), vDown.data(), nMKFs, mvWriteBackSlots.data(), mvMKFBundleID.data(), mvCamBundleID.data(), vCamFromWorld.data(),
+                          vDepth.data(), vBaseFromWorld.data()) != 0)
+  {
+    ROS_ERROR_STREAM("mcp_graph_write_back: " << mcp_last_error());
+    return;
+  }
+  for(int i = 0; i < nMKFs; ++i)
+  {
+    MultiKeyFrame& mkf = *mvpSlotMKF[mvWriteBackSlots[i]];
+    mkf.mse3BaseFromWorld = SE3From12(&vBaseFromWorld[12 * i]);
+    for(int c = 0; c < nc; ++c)
+    {
+      KeyFramePtrMap::iterator kf_it = mkf.mmpKeyFrames.find(mvCamNames[c]);
+      if(kf_it == mkf.mmpKeyFrames.end())
+        continue;
+      KeyFrame& kf = *kf_it->second;
+      kf.mse3CamFromWorld = SE3From12(&vCamFromWorld[12 * (i * nc + c)]);
+      const mcp_scene_depth& d = vDepth[i * nc + c];
+      if(d.refreshed == 1)   // 0: three points or fewer, the keyframe is left alone (KeyFrame.cc:587-591)
+      {
+        kf.mdSceneDepthMean = d.mean;
+        kf.mdSceneDepthSigma = d.sigma;
+      }
+      else if(d.refreshed == -1)
+        ROS_BREAK();         // KeyFrame.cc:635-644
+    }
+  }
+  for(int i = 0; i < nPoints; ++i)
+  {
+    MapPoint& point = *mvpRowPoint[mvWriteBackRows[i]];
+    point.mv3WorldPos = TooN::makeVector(vWorld[3 * i], vWorld[3 * i + 1], vWorld[3 * i + 2]);
+    point.mv3PixelRight_W = TooN::makeVector(vRight[3 * i], vRight[3 * i + 1], vRight[3 * i + 2]);
+    point.mv3PixelDown_W = TooN::makeVector(vDown[3 * i], vDown[3 * i + 1], vDown[3 * i + 2]);
+    point.mbOptimized = true;
+  }
+}
+
+// MultiKeyFrame enters the map (src/MapMakerServerBase.cc:219, 392): MultiKeyFrame::RefreshSceneDepthRobust at its own pose, after GraphUploadMKFs
+// and GraphAddMeasurements have put it and its measurements into the graph.  One mcp_graph_refresh_depth; the graph keeps the new means.
+void GraphRefreshSceneDepth(Map& map, MultiKeyFrame& mkf, const std::vector<std::string>& vCamNames)
+{
+  const int nc = (int)vCamNames.size();
+  std::vector<mcp_scene_depth> vDepth(nc);
+  if(mcp_graph_refresh_depth(map.mpMapGraph, 1, &mkf.mnGraphSlot, vDepth.data()) != 0)
+  {
+    ROS_ERROR_STREAM("mcp_graph_refresh_depth: " << mcp_last_error());
+    return;
+  }
+  for(int c = 0; c < nc; ++c)
+  {
+    KeyFramePtrMap::iterator kf_it = mkf.mmpKeyFrames.find(vCamNames[c]);
+    if(kf_it == mkf.mmpKeyFrames.end() || vDepth[c].refreshed != 1)
+      continue;
+    kf_it->second->mdSceneDepthMean = vDepth[c].mean;
+    kf_it->second->mdSceneDepthSigma = vDepth[c].sigma;
+  }
 }
