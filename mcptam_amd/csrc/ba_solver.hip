@@ -488,18 +488,25 @@ struct mcp_ba {
   // system is applied and evaluated (pose/point update, chains, residuals, robust sums) on the stream that solved it, right
   // behind its back-substitution -- the host finds the result of a rejected trial's successor in its mailbox instead of
   // launching five dependent kernels and waiting.  Same kernels on the same inputs as a trial run in sequence: same numbers.
-  DevBuf<double> d_sxp[MAX_SYS], d_sxl[MAX_SYS], d_sp0[MAX_SYS], d_sp1[MAX_SYS], d_sp2[MAX_SYS];
-  bool pre_run[MAX_SYS] = {false, false, false, false}, ahead_enq[MAX_SYS] = {false, false, false, false}; unsigned long long pre_ticket[MAX_SYS] = {0, 0, 0, 0};
-  hipEvent_t ev_tr[MAX_SYS] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_wf[MAX_SYS] = {nullptr, nullptr, nullptr, nullptr};      // trial q evaluated ahead: its last reader of the linearisation (k_backsub) is through
+  // What belongs to ONE system q of the batch beyond its slices of d_red / d_Vinv: lane[q]
+  struct SpecLane {
+    DevBuf<double> xp, xl, p0, p1, p2;      // x of system q (pose part, point part) and the partial sums of its trial evaluated ahead
+    bool pre_run = false, ahead_enq = false; unsigned long long pre_ticket = 0;      // a trial ahead is wanted / still registered with the main stream; its mailbox ticket
+    hipEvent_t ev_tr = nullptr;             // its last kernel
+    hipEvent_t ev_wf = nullptr;             // trial q evaluated ahead: its last reader of the linearisation (k_backsub) is through
+    hipStream_t st_tr = nullptr;            // its own stream (MCP_BA_SPEC_TRIALS=2, below)
+    hipStream_t tr_stream = nullptr;        // where the trial ahead of system q was enqueued
+    hipEvent_t head_ev = nullptr; bool head_enq = false; int head_state = -1; unsigned long long head_ticket = 0;      // the per-trial iteration head (ba_head.h, below)
+    DevBuf<double> trial; DevBuf<SelState> trstate;      // trial buffer of the multi-rank tail (ba_trial.h) and the selection state k_trial_post leaves in it
+    int pred_ok = 0, ovf = 0;               // ... and what it told the host about the riding histograms
+  };
+  SpecLane lane[MAX_SYS];
   // MCP_BA_SPEC_TRIALS: 0 = trials strictly in sequence; 1 = one trial ahead on the stream that solved it; 2 (default since round 6)
   // = the steps of ALL speculatively solved systems are applied and evaluated as soon as their solutions exist, each on its own
-  // stream (st_tr[q], behind the speculative chain's event).  Round 3 measured 819 / 835 it/s (1) vs 733 / 743 (2) -- three trial
+  // stream (lane[q].st_tr, behind the speculative chain's event).  Round 3 measured 819 / 835 it/s (1) vs 733 / 743 (2) -- three trial
   // evaluations at once took the compute units from the trial the host was waiting for; with a trial's step in one launch and the
   // evaluation at 17 us the balance has turned: 1518 / 1519 / 1610 (1) vs 1543 / 1538 / 1629 (2), pairs within one run.
   int spec_trials = 2;
-  hipStream_t st_tr[MAX_SYS] = {nullptr, nullptr, nullptr, nullptr};
-  hipStream_t tr_stream[MAX_SYS] = {nullptr, nullptr, nullptr, nullptr};      // where the trial ahead of system q was enqueued
   // system
   DevBuf<double> d_ubig;    // [U (np*np) | bp (np)] contributions of the points outside the groups (> GRP_LMAX poses); only if nbig
   DevBuf<double> d_red;     // [S (np*np) | rhs (np) | bp = J^T r (np)]   (the all-reduced block)
@@ -524,9 +531,7 @@ struct mcp_ba {
   struct HeadScratch { unsigned int* hist = nullptr; double* vals = nullptr; double* part = nullptr; double* out = nullptr; double* rs = nullptr; };
   HeadScratch hsc[2*MAX_SYS]; DevBuf<double> d_headbuf;
   hipStream_t st_h = nullptr; bool st_h_own = false;      // the heads of trials evaluated ahead run here: the second stream stays free for the NEXT trial ahead
-  hipEvent_t head_ev[MAX_SYS] = {nullptr, nullptr, nullptr, nullptr};
-  bool head_enq[MAX_SYS] = {false, false, false, false}; int head_state[MAX_SYS] = {-1, -1, -1, -1};
-  unsigned long long head_ticket[MAX_SYS] = {0, 0, 0, 0}, head_ticket_ctr = 0;
+  unsigned long long head_ticket_ctr = 0;
   int head_par = 0, acc_head_q = -1, dbg_head_miss = 0;
   const double* start_blk = nullptr;      // the iteration-start block the first trial forwards to the host (nullptr: d_res[24..28])
   unsigned int* head_hist(int q) { return hsc[head_par*MAX_SYS + q].hist; }
@@ -578,13 +583,15 @@ struct mcp_ba {
   int sel_cap = 4096;           // candidates per rank slot (MCP_BA_SELECT_CAP)
   DevBuf<double> d_xp_cand;     // pose update of the trial in flight; swapped with d_xp_good (as d_xl with d_xl_good) when the solve succeeded
   DevBuf<double> d_part0, d_part1, d_part2, d_res, d_sigma, d_hist, d_cov;
+  // the initial lambda's maximum over the diagonals (initial_lambda): one partial maximum per 1024 entries, MAX_DIAG_PARTS at most, in d_part1
+  static constexpr int MAX_DIAG_PARTS = 256;
+  static int max_diag_parts(int np_, int nfl_) { return std::min(MAX_DIAG_PARTS, (std::max(np_, nfl_) + 1023)/1024); }
   // the head of an iteration of a large map in one launch (ba_headl.h, MCP_BA_HEAD_LARGE=1): scratch (left zeroed by every launch).  Default off:
   // measured equal to the six launches at the metric size (1611 / 1603 vs 1606 / 1611 it/s) -- 39 us alone on the device against ~50, but its 64
   // fat workgroups wait for room beside the trials evaluated ahead on the other stream, which six small launches slip past
   DevBuf<unsigned char> d_headl; bool headl_clean = false; int head_large_on = 0; int hl_grid = 0;
   bool use_head_large() const { return head_large_on && robust && !multi() && !small_mode() && P.nmeas > 0 && hl_grid > 0 && d_headl.p != nullptr; }
   int head_large(int w, int off, double* sig_copy2);
-  bool head_failed = false;
   bool hist_clean = false;          // the single-GPU median left its two histograms + counter zero (k_select_small's last act): no fill in front of the next one
   // The sigma block is double-buffered by median: a trial evaluated ahead on the speculative stream that nobody consumes may
   // still be reading its iteration's block when the next iteration's median writes the new one (the two streams only meet
@@ -636,13 +643,10 @@ struct mcp_ba {
   unsigned long long coll_seq[2] = {0, 0}; const char* coll_what[2] = {"none", "none"};
   int watchdog_fail(const char* where);
   int wait_stream(hipStream_t s, const char* what);
-  // trial buffers of the multi-rank tail (ba_trial.h) and the selection state k_trial_post leaves in them
-  DevBuf<double> d_trial[MAX_SYS]; DevBuf<SelState> d_trstate[MAX_SYS];
   int spec_delay = 0;
   int test_fail_trial = 0, test_trial_no = 0;      // MCP_BA_TEST_FAIL_TRIAL=k: the k-th trial of the handle's life is treated as a failed factorisation
   int sel_ride = 1;                // MCP_BA_SELECT_RIDE=0: the median never uses the histograms that rode on the trial's all-reduce
   int pred_bin = -1;               // first digit of the last median the host has seen (the prediction the trials histogram around)
-  int tr_pred_ok[MAX_SYS] = {0, 0, 0, 0}, tr_ovf[MAX_SYS] = {0, 0, 0, 0};
   int sel_src = -1;                // trial buffer whose histograms belong to the current state's chi2 (the accepted trial), or -1
 
   // profiling
@@ -657,30 +661,29 @@ struct mcp_ba {
     if (st2) (void)hipStreamSynchronize(st2);
     if (st3) (void)hipStreamSynchronize(st3);
     if (st_h) (void)hipStreamSynchronize(st_h);
-    for (int q = 0; q < MAX_SYS; ++q) if (st_tr[q]) (void)hipStreamSynchronize(st_tr[q]);
+    for (SpecLane& L : lane) if (L.st_tr) (void)hipStreamSynchronize(L.st_tr);
     (void)hipStreamSynchronize(nullptr);          // (synchronous copies and the debug hooks use the null stream)
   }
   ~mcp_ba() {
     // nothing of this handle may still be running when its mailbox goes back to the host allocator (a trial evaluated ahead writes there)
     drain();
-    for (int q = 0; q < MAX_SYS; ++q) if (st_tr[q] && !pooled) (void)hipStreamDestroy(st_tr[q]);
+    for (SpecLane& L : lane) {
+      if (L.st_tr && !pooled) (void)hipStreamDestroy(L.st_tr);
+      for (hipEvent_t e : {L.head_ev, L.ev_tr, L.ev_wf}) if (e) (void)hipEventDestroy(e);
+    }
     if (h_res) mcp::PinnedCache::get().put(h_res, HRES*sizeof(double), hipHostMallocMapped | hipHostMallocCoherent, device);
     if (h_exp) mcp::PinnedCache::get().put(h_exp, h_exp_cap, hipHostMallocMapped | hipHostMallocCoherent, device);
     if (h_fail) mcp::PinnedCache::get().put(h_fail, 4*sizeof(int), hipHostMallocDefault, device);
     for (auto e : ev_pool) (void)hipEventDestroy(e);
-    for (int q = 0; q <= MAX_SYS; ++q) if (chol_exec[q]) (void)hipGraphExecDestroy(chol_exec[q]);
     for (int q = 0; q <= MAX_SYS; ++q) for (int r = 0; r < MAX_SYS; ++r) if (chain_exec[q][r]) (void)hipGraphExecDestroy(chain_exec[q][r]);
     if (st2) { (void)hipStreamSynchronize(st2); if (!pooled) (void)hipStreamDestroy(st2); }
     if (st3) { (void)hipStreamSynchronize(st3); if (!pooled) (void)hipStreamDestroy(st3); }
     if (st_h && st_h_own) (void)hipStreamDestroy(st_h);
-    for (int q = 0; q < MAX_SYS; ++q) if (head_ev[q]) (void)hipEventDestroy(head_ev[q]);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_head) (void)hipEventDestroy(ev_head);
     if (ev_sum) (void)hipEventDestroy(ev_sum);
     if (ev_spec) (void)hipEventDestroy(ev_spec);
     if (ev_spec3) (void)hipEventDestroy(ev_spec3);
-    for (int q = 0; q < MAX_SYS; ++q) if (ev_tr[q]) (void)hipEventDestroy(ev_tr[q]);
-    for (int q = 0; q < MAX_SYS; ++q) if (ev_wf[q]) (void)hipEventDestroy(ev_wf[q]);
     if (st && !pooled) (void)hipStreamDestroy(st);
   }
   // everything the second stream still has in flight reads the current linearisation (W, V, g, staged blocks): the main stream
@@ -703,7 +706,7 @@ struct mcp_ba {
     // a full join also covers the trials evaluated ahead on those streams (enqueued after ev_spec was recorded): whatever the main
     // stream does next -- the next linearisation overwrites W, g, V; the next iteration's trials reuse the candidate states -- is
     // ordered behind them, used or not
-    if (q < 0) for (int k = 0; k < MAX_SYS; ++k) if (ahead_enq[k]) { HIPCK(hipStreamWaitEvent(st, ev_tr[k], 0)); ahead_enq[k] = false; }
+    if (q < 0) for (int k = 0; k < MAX_SYS; ++k) if (lane[k].ahead_enq) { HIPCK(hipStreamWaitEvent(st, lane[k].ev_tr, 0)); lane[k].ahead_enq = false; }
     return 0;
   }
 
@@ -715,7 +718,7 @@ struct mcp_ba {
   int join_spec_lin() {
     if (spec_pending) { HIPCK(hipStreamWaitEvent(st, ev_spec, 0)); spec_pending = false; }
     if (spec3_pending) { HIPCK(hipStreamWaitEvent(st, ev_spec3, 0)); spec3_pending = false; }
-    for (int k = 0; k < MAX_SYS; ++k) if (ahead_enq[k]) HIPCK(hipStreamWaitEvent(st, ev_wf[k], 0));
+    for (int k = 0; k < MAX_SYS; ++k) if (lane[k].ahead_enq) HIPCK(hipStreamWaitEvent(st, lane[k].ev_wf, 0));
     return 0;
   }
 
@@ -734,7 +737,6 @@ struct mcp_ba {
   int spec_now() const { return (spec_adapt && small_mode() && spec_hot <= 0) ? 0 : speculate; }
   int lin_join_full = 0;             // MCP_BA_LIN_JOIN=1: linearize() waits for everything the speculative stream has in flight (round 2's behaviour)
   int use_graph = 0;                 // MCP_BA_GRAPH=1: replay the factorisation chain from a captured hipGraph
-  hipGraphExec_t chol_exec[MAX_SYS + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipGraphExec_t chain_exec[MAX_SYS + 1][MAX_SYS] = {};      // [systems][first system]: factorisation + back-substitution of a sub-batch, captured once
   double* S() { return d_red.p + sys_cur*red_stride; }
   double* rhs() { return S() + (size_t)np*np; }
@@ -897,9 +899,27 @@ struct mcp_ba {
   int select_gather_finish(const double* x, int n, const double* hist, SelState* state, double* out_dev, bool check_overflow);
   int median_sigma(int which);
   int robust_total(hipStream_t s, int which, const double* sg, double* part, double* out, int off);
-  void take_trial_flags(int q) { tr_pred_ok[q] = h_res[MAIL_PRED_OK] != 0.0; tr_ovf[q] = h_res[MAIL_OVERFLOW] != 0.0; }      // what k_trial_post told the host about trial q's riding histograms
+  void take_trial_flags(int q) { lane[q].pred_ok = h_res[MAIL_PRED_OK] != 0.0; lane[q].ovf = h_res[MAIL_OVERFLOW] != 0.0; }      // what k_trial_post told the host about trial q's riding histograms
   int read_results(int count);
   int wait_mail(int q, unsigned long long ticket, int count);
+  // Where the step of ONE trial reads and writes (launch_trial_step).  Three callers fill it in: the trial on the main stream
+  // (enqueue_main_trial), a trial evaluated ahead on the stream that solved its system (enqueue_spec_trial), and the stale step
+  // after a failed factorisation (stale_step) -- same kernels on the same inputs whoever launches them: same numbers.
+  struct TrialIo {
+    hipStream_t s; int lane;                     // stream; the lane of a multi-rank tail's all-reduce
+    int q, slot;                                 // system of the batch, candidate state
+    double lam;
+    const double* rhs; const double* bp; const double* Vinv;      // of system q (stale: rhs is the solver's x of the last good solve)
+    double* xp; double* xl;                      // where x goes: pose part, point part (stale: xl is the point step that is applied)
+    double* p0; double* p1; double* p2;          // partial sums: robust chi2 | x (lambda x + b) | x^2 of the points (null: no such sum)
+    double* pose_parts; int pose_off;            // the pose parts of those two sums, and their place in the result block
+    double* res; const int* fail;                // result block; the failure flag of system q
+    double* mail; int mail_count; unsigned long long ticket;
+    bool main_block;                             // forwards the iteration-start block, joins the sum aside first, ST_UPDATE / ST_EVAL around it
+    bool record_wf;                              // lane[q].ev_wf behind the step: the linearisation's outputs are not read below it
+    bool stale;                                  // the point step is applied as it is (k_apply_point_step): no back-substitution, no step statistics
+  };
+  int launch_trial_step(const TrialIo& io);
   int enqueue_spec_trial(hipStream_t s, int q);
   int multi_trial_tail(hipStream_t s, int lane, int q, int slot, int nbe, const double* p0, int nbb, const double* p1, const double* p2,
                        const double* pose_parts, int pose_off, bool main_block, double* mail, int mail_count, unsigned long long ticket);
@@ -953,10 +973,50 @@ struct mcp_ba {
   }
   int linearize();
   int build_system(int nsys, SysBatch& sb, int q0 = 0, hipStream_t on = nullptr);
+  // one LM trial (solve_trial) and its stages in the order it goes through them
+  struct Deferred { int n1 = 0, n2 = 0, nsys = 0; bool ahead_single = false; };      // what a fresh batch leaves for behind the main trial: the other streams' chains, the trials ahead
   int solve_trial(double lam, bool& ok2, double ni = 0);
+  int start_batch(double lam, double ni, Deferred& df);
+  int solve_split(int nsys, int ov, SysBatch& sb, Deferred& df);
+  int solve_batched(int nsys, SysBatch& sb, Deferred& df);
+  int enqueue_main_trial(double lam, int& tr, bool& with_head);
+  int finish_deferred_chains(const Deferred& df);
+  int run_trials_ahead(const Deferred& df);
+  int collect_trial(int q, bool ahead, double lam, bool& ok2, double ni);
   int persist_fallback(double lam, bool& ok2, double ni);
+  // Compute(): what its iterations share (LmRun), one iteration (LmIter), and the stages in the order compute() goes through them
+  struct LmRun {
+    volatile unsigned char* abort_flag; int n_iter; double user_lambda;
+    double ni = 2; int conv_mag = 0, conv_res = 0;
+    std::chrono::steady_clock::time_point t_begin, t_first_end, t_loop_end;
+    bool terminate() const { return abort_flag && *abort_flag; }
+  };
+  struct LmIter {
+    int it; mcp_ba_iter_log lg;
+    bool head_done = false, lin_done = false, start_pending = true;
+    double currentChi = 0, tempChi = 0, rho = 0, ss_last = 0, trial_chi_raw = 0; int qmax = 0, accepted = 0;
+    std::chrono::steady_clock::time_point t0; std::string trace_line;      // (MCP_BA_TRACE=3)
+  };
+  static constexpr int RS = 24;      // the iteration-start block in d_res / h_res: robust chi2, then the sigma block
   int compute(volatile unsigned char* abort_flag, int n_iter, double user_lambda);
+  int begin_solve(LmRun& R);
+  int iteration_head(LmRun& R, LmIter& I);
+  int head_brought_along(LmIter& I);
+  int initial_lambda(LmRun& R, LmIter& I);
+  int take_start(LmIter& I);
+  int run_trial(LmRun& R, LmIter& I);
+  int stale_step(LmIter& I, double& scale, double& ss);
+  void schedule(LmRun& R, LmIter& I, bool ok2, double scale, double ss);
+  void post_iteration(LmRun& R, LmIter& I);
+  int end_solve(LmRun& R, int nCounter);
+  void dump_profiles();
+  // final statistics: sigma^2 and chi2 with the export | the outlier list | the depth covariance
   int final_stats(int nCounter);
+  int final_sigma_and_export(int nCounter);
+  void outlier_list();
+  int depth_covariance();
+  int robust_chi2_block(bool median, const char* what);
+  int state_ready(bool linearise);
 };
 
 // ------------------------------------------------------------------------------------------
@@ -2343,16 +2403,15 @@ int mcp_ba::alloc_work_buffers(int nmeas, int nblk) {
   red_stride = n2 + 2*(size_t)np; vinv_stride = (size_t)nfl*6; spec_ok = false; sys_cur = 0;
   if (multi()) {
     if (d_seltab.alloc((size_t)world*sel_cap + world + 2)) return -1;
-    for (int q = 0; q < MAX_SYS; ++q) if (d_trial[q].alloc(TRIAL_LEN) || d_trstate[q].alloc(SEL_PASSES + 1)) return -1;
+    for (int q = 0; q < MAX_SYS; ++q) if (lane[q].trial.alloc(TRIAL_LEN) || lane[q].trstate.alloc(SEL_PASSES + 1)) return -1;
   }
   sel_src = -1; pred_bin = -1;
-  for (int q = 0; q <= MAX_SYS; ++q) if (chol_exec[q]) { (void)hipGraphExecDestroy(chol_exec[q]); chol_exec[q] = nullptr; }      // plan and buffers may have changed
-  for (int q = 0; q <= MAX_SYS; ++q) for (int r = 0; r < MAX_SYS; ++r) if (chain_exec[q][r]) { (void)hipGraphExecDestroy(chain_exec[q][r]); chain_exec[q][r] = nullptr; }
+  for (int q = 0; q <= MAX_SYS; ++q) for (int r = 0; r < MAX_SYS; ++r) if (chain_exec[q][r]) { (void)hipGraphExecDestroy(chain_exec[q][r]); chain_exec[q][r] = nullptr; }      // plan and buffers may have changed
   hist_clean = false;                              // (the histogram block may be a fresh one)
   if ((nbig && d_ubig.alloc(n2 + np)) || d_stU.alloc(nstage*36) || d_stb.alloc((size_t)nrhs_rows*6) || d_stS.alloc(MAX_SYS*nstage*36) ||
       d_str.alloc(MAX_SYS*(size_t)nrhs_rows*6) || d_udiag.alloc(np) || d_red.alloc(MAX_SYS*(n2 + 2*(size_t)np)) || d_V.alloc((size_t)nfl*6) || d_g.alloc((size_t)nfl*3) ||
       d_W.alloc((size_t)ninc*18) || d_Vinv.alloc(MAX_SYS*(size_t)nfl*6) || d_xl.alloc((size_t)nfl*3) ||
-      d_xp_good.alloc(np) || d_xp_cand.alloc(np) || d_selvals.alloc(SEL_GATHER_CAP) || d_xl_good.alloc((size_t)nfl*3) || d_part0.alloc(nblk) || d_part1.alloc(nblk) ||
+      d_xp_good.alloc(np) || d_xp_cand.alloc(np) || d_selvals.alloc(SEL_GATHER_CAP) || d_xl_good.alloc((size_t)nfl*3) || d_part0.alloc(nblk) || d_part1.alloc(std::max(nblk, max_diag_parts(np, nfl))) ||
       d_part2.alloc(nblk) || d_parth.alloc(nblk) || d_res.alloc(32 + 8*MAX_SYS) || d_sigma.alloc(8*N_SIG) || d_hist.alloc((size_t)SEL_PASSES*SEL_BINS) ||
       d_selstate.alloc(SEL_PASSES + 1) || d_fail.alloc(4) || d_flags.alloc(nmeas) || d_cov.alloc(nfl)) return -1;
   return 0;
@@ -2386,7 +2445,7 @@ int mcp_ba::head_scratch(int nmeas, int nblk) {
         HIPCK(hipMemsetAsync(hsc[i].hist, 0, (HEAD_HIST + HEAD_CTL)*sizeof(unsigned int), st));       // (every head leaves them zero again)
       }
     } else d_headbuf.release();
-    for (int q = 0; q < MAX_SYS; ++q) { head_enq[q] = false; head_state[q] = -1; }
+    for (int q = 0; q < MAX_SYS; ++q) { lane[q].head_enq = false; lane[q].head_state = -1; }
     acc_head_q = -1; start_blk = nullptr;
   }
   return 0;
@@ -2414,7 +2473,7 @@ int mcp_ba::pinned_mailbox(int nblk) {
     void* dp = nullptr; HIPCK(hipHostGetDevicePointer(&dp, h_res, 0)); h_mail_dev = (double*)dp + 32;
   }
   for (int q = 1; q < MAX_SYS; ++q)
-    if (d_sxp[q].alloc(np) || d_sxl[q].alloc((size_t)nfl*3) || d_sp0[q].alloc(nblk) || d_sp1[q].alloc(nblk) || d_sp2[q].alloc(nblk)) return -1;
+    if (lane[q].xp.alloc(np) || lane[q].xl.alloc((size_t)nfl*3) || lane[q].p0.alloc(nblk) || lane[q].p1.alloc(nblk) || lane[q].p2.alloc(nblk)) return -1;
   if (!h_fail) { h_fail = (int*)mcp::PinnedCache::get().take(4*sizeof(int), hipHostMallocDefault); if (!h_fail) { set_err("hipHostMalloc failed"); return -1; } }
   return 0;
 }
@@ -2626,8 +2685,8 @@ int mcp_ba::median_sigma(int w) {
   // several ranks, and the state is the one an accepted trial left: that trial's all-reduce carried the first two digit histograms
   // of this very chi2 array (ba_trial.h) -- if its prediction held and the selected bin fits the gather table, the median costs
   // ONE collective and no host wait
-  if (multi() && sel_src >= 0 && tr_pred_ok[sel_src] && !tr_ovf[sel_src]) {
-    if (select_gather_finish(d_chi2[w].p, P.nmeas, d_trial[sel_src].p + TRIAL_HDR, d_trstate[sel_src].p, d_res.p + 8, false)) return -1;
+  if (multi() && sel_src >= 0 && lane[sel_src].pred_ok && !lane[sel_src].ovf) {
+    if (select_gather_finish(d_chi2[w].p, P.nmeas, lane[sel_src].trial.p + TRIAL_HDR, lane[sel_src].trstate.p, d_res.p + 8, false)) return -1;
     timing.n_median_fast++;
   } else if (select_kth(d_chi2[w].p, P.nmeas, k, d_res.p + 8, true)) return -1;
   sel_src = -1;
@@ -2651,7 +2710,7 @@ int mcp_ba::wait_mail(int q, unsigned long long ticket, int count) {
   struct Acc { mcp_ba* h; int q; std::chrono::steady_clock::time_point t; ~Acc() { h->dbg_wait_us[q ? 1 : 0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t).count(); } } acc_{this, q, w0};
   const double* box = h_res + 32 + 32*q;
   volatile unsigned long long* tk = (volatile unsigned long long*)(box + MAIL_TICKET);
-  hipStream_t watched = (q == 0) ? st : (tr_stream[q] ? tr_stream[q] : st2);
+  hipStream_t watched = (q == 0) ? st : (lane[q].tr_stream ? lane[q].tr_stream : st2);
   // The result is normally a few tens of microseconds away: poll hard for a while (a trial is ~70 us, a solve ~1 ms), then give
   // the core to whoever else wants it between polls -- a tracker thread beside the mapper (BASELINE c5) should not lose a core
   // to a solver that waits for a long factorisation or for another rank.  Every so often: has the stream died, drained without
@@ -2683,7 +2742,8 @@ int mcp_ba::wait_mail(int q, unsigned long long ticket, int count) {
 // digit histograms of its chi2, final sums into the trial buffer, ONE all-reduce, scan + result block (+ mailbox)   (ba_trial.h)
 int mcp_ba::multi_trial_tail(hipStream_t s, int lane, int q, int slot, int nbe, const double* p0, int nbb, const double* p1, const double* p2,
                              const double* pose_parts, int pose_off, bool main_block, double* mail, int mail_count, unsigned long long ticket) {
-  double* T = d_trial[q].p;
+  SpecLane& L = this->lane[q];      // (`lane` here is the collective's)
+  double* T = L.trial.p;
   HIPCK(hipMemsetAsync(T, 0, TRIAL_LEN*sizeof(double), s));
   const bool ride = robust && sel_ride && m_total > 0;       // (decided on GLOBAL quantities: the payload size must agree on every rank)
   if (ride) {
@@ -2694,52 +2754,70 @@ int mcp_ba::multi_trial_tail(hipStream_t s, int lane, int q, int slot, int nbe, 
   hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, s, nbe, p0, nbb, p1, nbb, p2, T, 0, (const int*)d_fail.p + q, (double*)nullptr, 0, 0ull,
                      rides ? (const double*)(d_res.p + 24) : (const double*)nullptr, 4);
   if (allreduce(T, ride ? TRIAL_LEN : TRIAL_HDR, lane, false, lane ? "trial evaluated ahead: result block + median histograms" : "trial: result block + median histograms")) return -1;
-  hipLaunchKernelGGL(k_trial_post, dim3(1), dim3(SEL_BLOCK), 0, s, T, d_trstate[q].p, (unsigned long long)(m_total/2), pred_bin, (double)sel_cap, ride ? 1 : 0,
+  hipLaunchKernelGGL(k_trial_post, dim3(1), dim3(SEL_BLOCK), 0, s, T, L.trstate.p, (unsigned long long)(m_total/2), pred_bin, (double)sel_cap, ride ? 1 : 0,
                      pose_parts, pose_off, main_block ? (const double*)(d_res.p + 24) : (const double*)nullptr, rides ? 1 : 0,
                      main_block ? d_res.p : (double*)nullptr, mail, mail_count, ticket);
   if (rides) start_rides = false;
   return 0;
 }
+// The step of one trial, launched from its description: x applied to the current state (one launch, or pose update + point
+// back-substitution), the chain transforms, the residuals with their robust partial sums, and the final sums into the result block
+// (several ranks: the trial tail with its one all-reduce).
+int mcp_ba::launch_trial_step(const TrialIo& io) {
+  hipStream_t s = io.s;
+  const int slot = io.slot;
+  const int nbb = (nfl*BS_TPP + BS_BLOCK - 1)/BS_BLOCK, nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
+  const int ncb = io.stale ? 0 : trial_chain_blocks();
+  if (io.main_block) tic(ST_UPDATE);
+  if (ncb) { hipLaunchKernelGGL(k_trial_apply, dim3(ncb + (nfl ? nbb : 0)), dim3(256), (size_t)P.npose*12*sizeof(double), s, P, ncb, io.lam, io.rhs, io.bp, (const double*)d_pose[cur].p, d_pose[slot].p, io.pose_parts, io.xp,
+                                d_first[slot].p, d_second[slot].p, d_last[slot].p, (const double*)d_g.p, (const double*)d_W.p, io.Vinv,
+                                (const double*)d_pt[cur].p, d_pt[slot].p, io.xl, io.p1, io.p2); note_launch("k_trial_apply"); }
+  else {
+    hipLaunchKernelGGL(k_update_poses, dim3(1), dim3(256), 0, s, P, io.lam, io.rhs, io.bp, (const double*)d_pose[cur].p, d_pose[slot].p, io.pose_parts, io.xp);
+    if (nfl && io.stale) hipLaunchKernelGGL(k_apply_point_step, dim3((nfl + 255)/256), dim3(256), 0, s, P, (const double*)io.xl, (const double*)d_pt[cur].p, d_pt[slot].p);
+    else if (nfl) hipLaunchKernelGGL(k_backsub, dim3(nbb), dim3(BS_BLOCK), 0, s, P, io.lam, io.rhs, (const double*)d_g.p, (const double*)d_W.p,
+                                     io.Vinv, (const double*)d_pt[cur].p, d_pt[slot].p, io.xl, io.p1, io.p2);
+  }
+  if (io.main_block) { toc(); tic(ST_EVAL); }
+  if (io.record_wf) HIPCK(hipEventRecord(lane[io.q].ev_wf, s));      // the linearisation's outputs are not read below this line (join_spec_lin)
+  if (P.nchain && !ncb) hipLaunchKernelGGL(k_chains, dim3((P.nchain + 63)/64), dim3(64), 0, s, P, (const double*)d_pose[slot].p, d_first[slot].p, d_second[slot].p, d_last[slot].p);
+  if (nbe) hipLaunchKernelGGL((k_eval<true>), dim3(nbe), dim3(EVAL_BLOCK), 0, s, P, (const double*)d_pt[slot].p, (const double*)d_last[slot].p, d_chi2[slot].p, (double*)nullptr,
+                              (const double*)sig(), io.p0);
+  const double* p1 = (nfl && !io.stale) ? io.p1 : nullptr; const double* p2 = (nfl && !io.stale) ? io.p2 : nullptr;
+  const int nbs = p1 ? nbb : 0;
+  if (multi() && !io.stale) {
+    // (several ranks: the sums are rank-local until the trial's all-reduce; k_trial_post writes the block and the mailbox)
+    if (multi_trial_tail(s, io.lane, io.q, slot, nbe, io.p0, nbs, p1, p2, io.pose_parts, io.pose_off, io.main_block, io.mail, io.mail_count, io.ticket)) return -1;
+  } else {
+    if (io.main_block && join_sum()) return -1;      // (this launch forwards d_res[24..28], the head of the iteration, to the host)
+    hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, s, nbe, (const double*)io.p0, nbs, p1, nbs, p2, io.res, 0, io.fail,
+                       io.mail, io.mail_count, io.ticket, (const double*)nullptr, 0, io.main_block ? start_blk : (const double*)nullptr);
+    if (io.main_block && !nfl) HIPCK(hipMemsetAsync(d_res.p + 1, 0, 2*sizeof(double), s));
+  }
+  if (io.main_block) toc();
+  return 0;
+}
 // the step of speculative system q applied and evaluated on stream s (which has just solved it): candidate state cand(q), its own
 // scratch, result block d_res[32 + 8 q ..] -> mailbox q.
 int mcp_ba::enqueue_spec_trial(hipStream_t s, int q) {
-  tr_stream[q] = s;
+  SpecLane& L = lane[q];
+  L.tr_stream = s;
   const int slot = cand(q);
-  const double lam = batch_lambda[q];
-  double* Sq = d_red.p + q*red_stride; double* rhsq = Sq + (size_t)np*np;
-  double* resq = d_res.p + 32 + 8*q;
-  const bool small = small_mode();
-  const int nbb = (nfl*BS_TPP + BS_BLOCK - 1)/BS_BLOCK;
-  const int ncb = trial_chain_blocks();
-  if (ncb) { hipLaunchKernelGGL(k_trial_apply, dim3(ncb + (nfl ? nbb : 0)), dim3(256), (size_t)P.npose*12*sizeof(double), s, P, ncb, lam, (const double*)rhsq, (const double*)(rhsq + np), (const double*)d_pose[cur].p, d_pose[slot].p, resq + 4, d_sxp[q].p,
-                                d_first[slot].p, d_second[slot].p, d_last[slot].p, (const double*)d_g.p, (const double*)d_W.p, (const double*)(d_Vinv.p + q*vinv_stride),
-                                (const double*)d_pt[cur].p, d_pt[slot].p, d_sxl[q].p, d_sp1[q].p, d_sp2[q].p); note_launch("k_trial_apply"); }
-  else {
-  hipLaunchKernelGGL(k_update_poses, dim3(1), dim3(256), 0, s, P, lam, (const double*)rhsq, (const double*)(rhsq + np), (const double*)d_pose[cur].p, d_pose[slot].p, resq + 4, d_sxp[q].p);
-  if (nfl) hipLaunchKernelGGL(k_backsub, dim3(nbb), dim3(BS_BLOCK), 0, s, P, lam, (const double*)rhsq, (const double*)d_g.p, (const double*)d_W.p,
-                              (const double*)(d_Vinv.p + q*vinv_stride), (const double*)d_pt[cur].p, d_pt[slot].p, d_sxl[q].p, d_sp1[q].p, d_sp2[q].p);
-  }
-  HIPCK(hipEventRecord(ev_wf[q], s));                     // the linearisation's outputs are not read below this line (join_spec_lin)
-  if (P.nchain && !ncb) hipLaunchKernelGGL(k_chains, dim3((P.nchain + 63)/64), dim3(64), 0, s, P, (const double*)d_pose[slot].p, d_first[slot].p, d_second[slot].p, d_last[slot].p);
-  const int nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
-  const bool with_head = head_ahead_want && !small && large_heads() && large_head_ahead != 2 && nbe > 0;      // (MCP_BA_HEAD_AHEAD=2: only the main stream's trial carries a head)
-  if (nbe) hipLaunchKernelGGL((k_eval<true>), dim3(nbe), dim3(EVAL_BLOCK), 0, s, P, (const double*)d_pt[slot].p, (const double*)d_last[slot].p, d_chi2[slot].p, (double*)nullptr,
-                              (const double*)sig(), d_sp0[q].p);
-  pre_ticket[q] = ++mail_ticket;
-  if (multi()) {
-    if (multi_trial_tail(s, 1, q, slot, nbe, d_sp0[q].p, nbb, nfl ? d_sp1[q].p : nullptr, nfl ? d_sp2[q].p : nullptr, resq + 4, 4, false, h_mail_dev + 32*q, MAIL_TICKET, pre_ticket[q])) return -1;
-  } else
-  hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, s, nbe, (const double*)d_sp0[q].p, nbb, (const double*)(nfl ? d_sp1[q].p : nullptr),
-                     nbb, (const double*)(nfl ? d_sp2[q].p : nullptr), resq, 0, (const int*)d_fail.p + q, h_mail_dev + 32*q, 6, pre_ticket[q]);
-  HIPCK(hipEventRecord(ev_tr[q], s));
-  pre_run[q] = true; ahead_enq[q] = true;
+  double* rhsq = d_red.p + q*red_stride + (size_t)np*np; double* resq = d_res.p + 32 + 8*q;
+  const bool with_head = head_ahead_want && !small_mode() && large_heads() && large_head_ahead != 2 && P.nmeas > 0;      // (MCP_BA_HEAD_AHEAD=2: only the main stream's trial carries a head)
+  L.pre_ticket = ++mail_ticket;
+  const TrialIo io{s, 1, q, slot, batch_lambda[q], rhsq, rhsq + np, d_Vinv.p + q*vinv_stride, L.xp.p, L.xl.p, L.p0.p, L.p1.p, L.p2.p,
+                   resq + 4, 4, resq, d_fail.p + q, h_mail_dev + 32*q, multi() ? MAIL_TICKET : 6, L.pre_ticket, false, true, false};
+  if (launch_trial_step(io)) return -1;
+  HIPCK(hipEventRecord(L.ev_tr, s));
+  L.pre_run = true; L.ahead_enq = true;
   if (with_head) { if (enqueue_head(s, q, slot, true)) return -1; }
   return 0;
 }
 // the iteration has decided (or starts a new solve): a trial evaluated ahead that nobody asked for is simply never looked at
 // (at most one is in flight -- see run_ahead -- and it is done before the next linearisation wants its buffers)
 int mcp_ba::cancel_spec_trials() {
-  for (int q = 0; q < MAX_SYS; ++q) pre_run[q] = false;
+  for (int q = 0; q < MAX_SYS; ++q) lane[q].pre_run = false;
   return 0;
 }
 // One trial ahead: when the host turns to trial q - 1, the step of system q (if it was solved speculatively on another stream) is
@@ -2748,12 +2826,12 @@ int mcp_ba::run_ahead(int q) {
   if (!spec_trials || !use_mailbox || prm.profile) return 0;
   if (multi() && overlap_spec != 1) return 0;       // (the speculative lane belongs to the second stream)
   if (!spec_pending && !spec3_pending && q >= spec2_from) { /* its stream has been joined already: still valid to use it */ }
-  if (q < spec2_from || q >= batch_n || pre_run[q]) return 0;
-  if (spec_trials >= 2 && !multi() && st_tr[q] && q > spec2_from) {      // (the first one stays on the chain's own stream: hardware queues are few)
+  if (q < spec2_from || q >= batch_n || lane[q].pre_run) return 0;
+  if (spec_trials >= 2 && !multi() && lane[q].st_tr && q > spec2_from) {      // (the first one stays on the chain's own stream: hardware queues are few)
     // its own stream, ordered behind the chain that produced system q: the trials ahead run side by side
     hipEvent_t done = (q >= spec3_from) ? ev_spec3 : ev_spec;
-    HIPCK(hipStreamWaitEvent(st_tr[q], done, 0));
-    return enqueue_spec_trial(st_tr[q], q);
+    HIPCK(hipStreamWaitEvent(lane[q].st_tr, done, 0));
+    return enqueue_spec_trial(lane[q].st_tr, q);
   }
   return enqueue_spec_trial(q >= spec3_from ? st3 : st2, q);
 }
@@ -2902,7 +2980,7 @@ int mcp_ba::join_sum() {
 // looked at: it went to the sigma block of the other parity (which nobody reads: the trials of the last iteration that may still
 // have been evaluating with it are waited for below) and to d_res[24..28], which the host has already taken for this iteration.
 int mcp_ba::head_ahead(int w) {
-  for (int q = 1; q < MAX_SYS; ++q) if (ev_tr[q]) HIPCK(hipStreamWaitEvent(st, ev_tr[q], 0));
+  for (int q = 1; q < MAX_SYS; ++q) if (lane[q].ev_tr) HIPCK(hipStreamWaitEvent(st, lane[q].ev_tr, 0));
   if (head_small(w, true)) return -1;                // (flips to the fresh sigma block)
   if (robust) flip_sig();                            // ... which becomes the current one only if the trial is accepted (compute())
   head_ahead_for = w;
@@ -2918,18 +2996,18 @@ int mcp_ba::head_ahead(int w) {
 // the linearisation on the second stream (compute()).
 int mcp_ba::enqueue_head(hipStream_t s_trial, int q, int w, bool side) {
   HeadScratch& H = hsc[head_par*MAX_SYS + q];
-  // a trial evaluated ahead: its head forks off its last kernel (ev_tr[q]) onto the head stream -- on the second stream it would sit in
+  // a trial evaluated ahead: its head forks off its last kernel (lane[q].ev_tr) onto the head stream -- on the second stream it would sit in
   // front of the next trial ahead (measured: +38 us per rejected trial, more than the heads save)
   hipStream_t s = (side && st_h) ? st_h : s_trial;
-  if (s != s_trial) HIPCK(hipStreamWaitEvent(s, ev_tr[q], 0));
-  head_ticket[q] = ++head_ticket_ctr;
+  if (s != s_trial) HIPCK(hipStreamWaitEvent(s, lane[q].ev_tr, 0));
+  lane[q].head_ticket = ++head_ticket_ctr;
   hipLaunchKernelGGL(k_head_hist, dim3(HEAD_GRID), dim3(HEAD_THREADS), 0, s, P.nmeas, (const double*)d_chi2[w].p, (const double*)sig(), H.hist);
   hipLaunchKernelGGL(k_head_finish, dim3(HEAD_GRID), dim3(HEAD_THREADS), 0, s, P.nmeas, (const double*)d_chi2[w].p, H.hist, H.vals, (const double*)sig(),
                      med_rank(), m_total, prm.min_mestimator_sigma*prm.min_mestimator_sigma,
-                     sig_block(2 + head_par*MAX_SYS + q), H.rs + 1, H.out, h_mail_dev - 32 + HEAD_MAIL + 2*q, head_ticket[q]);
+                     sig_block(2 + head_par*MAX_SYS + q), H.rs + 1, H.out, h_mail_dev - 32 + HEAD_MAIL + 2*q, lane[q].head_ticket);
   note_launch("k_head_finish");
-  HIPCK(hipEventRecord(head_ev[q], s));
-  head_enq[q] = true; head_state[q] = w;
+  HIPCK(hipEventRecord(lane[q].head_ev, s));
+  lane[q].head_enq = true; lane[q].head_state = w;
   return 0;
 }
 // the status word of trial q's head: 1 = its sigma block is written, 2 = it could not (prediction missed: plain selection), -1 = error
@@ -2937,7 +3015,7 @@ int mcp_ba::wait_head(int q) {
   const double* box = h_res + HEAD_MAIL + 2*q;
   volatile unsigned long long* tk = (volatile unsigned long long*)(box + 1);
   const auto w0 = std::chrono::steady_clock::now();
-  for (unsigned long long spins = 0; __atomic_load_n(tk, __ATOMIC_ACQUIRE) != head_ticket[q]; ++spins) {
+  for (unsigned long long spins = 0; __atomic_load_n(tk, __ATOMIC_ACQUIRE) != lane[q].head_ticket; ++spins) {
     if ((spins & 0xfff) == 0xfff) {
       if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count() > timeout_ms) return watchdog_fail("the status word of an iteration head");
       std::this_thread::yield();
@@ -2965,184 +3043,160 @@ int mcp_ba::solve_chain(hipStream_t s, int n, int q0) {
     }
     if (ex) { HIPCK(hipGraphLaunch(ex, s)); return 0; }
   }
+  const bool timed = (s == st);      // (the profile's stage events live on the main stream)
+  if (timed) tic(ST_CHOL);
   chol_factor(s, plan, d_red.p, d_fail.p, n, red_stride, q0);
+  if (timed) { toc(); tic(ST_SOLVE); }
   chol_back(s, plan, d_red.p, n, red_stride, q0);
+  if (timed) toc();
   return 0;
 }
 
 // on return h_res: [0] robust chi2 of the trial, [1] sum x(lambda x + b), [2] sum x^2
 int mcp_ba::solve_trial(double lam, bool& ok2, double ni) {
-  int defer_n1 = 0, defer_n2 = 0, defer_nsys = 0;
+  Deferred df;
   head_ahead_for = -1;
-  bool ahead_single = false;      // whole batch solved on the main stream: the speculative systems' trials can still be evaluated ahead on the second
   if (spec_ok && sys_cur + 1 < batch_n && batch_lambda[sys_cur + 1] == lam) {
     // an earlier trial of this iteration already built and solved this system speculatively (possibly on the second stream)
     ++sys_cur;
     timing.n_spec_hits++;
-    if (pre_run[sys_cur]) {
-      // ... and its step has been applied and evaluated there as well: the result is in (or on its way to) the trial's mailbox
-      const int q = sys_cur;
-      last_tr = cand(q); last_xp = &d_sxp[q]; last_xl = &d_sxl[q];
-      if (run_ahead(q + 1)) return -1;
-      if (wait_mail(q, pre_ticket[q], multi() ? MAIL_TICKET : 6)) return -1;
-      if (multi()) { tr_pred_ok[q] = h_res[MAIL_PRED_OK] != 0.0; tr_ovf[q] = h_res[MAIL_OVERFLOW] != 0.0; }
-      pre_run[q] = false;
-      HIPCK(hipStreamWaitEvent(st, ev_tr[q], 0));         // whatever the main stream does next with the trial's state comes after the kernels that made it
-      mark("pre_used", st);
-      ++dbg_pre;
-      if (!nfl_total) h_res[1] = h_res[2] = 0.0;
-      h_res[1] += h_res[4]; h_res[2] += h_res[5];
-      if (h_res[3] >= 1e9) return persist_fallback(lam, ok2, ni);
-      ok2 = (h_res[3] == 0.0);
-      timing.n_trials++;
-      return 0;
-    }
+    // ... and its step has been applied and evaluated there as well: the result is in (or on its way to) the trial's mailbox
+    if (lane[sys_cur].pre_run) return collect_trial(sys_cur, true, lam, ok2, ni);
     if (join_spec(sys_cur)) return -1;
-  } else {
-    sys_cur = 0;
-    // the lambdas of the rejection branch of the LM schedule: lambda *= ni; ni *= 2 (same operations as compute())
-    const int nsys = (ni > 0) ? 1 + std::max(0, std::min(spec_now(), MAX_SYS - 1)) : 1;
-    SysBatch sb; std::memset(&sb, 0, sizeof sb);
-    { double l = lam, f = ni; for (int q = 0; q < nsys; ++q) { batch_lambda[q] = sb.lambda[q] = l; sb.lambda_init[q] = (rank == 0) ? l : 0.0; l *= f; f *= 2; } }
-    batch_n = nsys;
-    if (cancel_spec_trials()) return -1;   // (a re-solve inside an iteration: nothing of the previous batch is wanted any more)
-    if (join_spec()) return -1;            // (... and its stragglers first)
-    if (!fail_clean) HIPCK(hipMemsetAsync(d_fail.p, 0, 4*sizeof(int), st));
-    fail_clean = false;
-    // One rank, one-launch factorisation: every system of the batch has its own critical workgroup, four systems take the time of
-    // one, so the batch stays on the main stream (measured: 990 vs 940 LM it/s; MCP_BA_OVERLAP=1 splits it as the per-step kernels
-    // want it).  Several ranks: one speculative stream, the one lane 1 belongs to.
-    const int ov_single = (overlap_auto && plan.use_persist && plan.persist.ok) ? 0 : overlap_spec;
-    const int ov = multi() ? std::min(overlap_spec, 1) : ov_single;
-    const bool split = ov && nsys > 1 && np > 0 && st2;
-    if (split) {
-      // system 0 -- the one this trial needs -- alone on the main stream; the speculative systems behind the fork on the second
-      // stream.  Same kernels on the same data as the batched path: the numbers do not depend on which stream produced them.
-      // main_sys systems stay on the main stream: 1 = only the trial's own; 2 = also the first speculative one, so that a second trial
-      // never waits for the other stream (its system comes out of the same launches as the first trial's)
-      const int n1 = std::min(std::max(main_sys, 1), nsys - 1);
-      HIPCK(hipEventRecord(ev_fork, st));
-      plan.persist.batch_sys = nsys;
-      mark("fork", st);
-      if (build_system(n1, sb, 0, st)) return -1;
-      mark("main_built", st);
-      // MCP_BA_SPEC_DELAY=1: the speculative systems' Schur complements start only when the trial's own is through (they share the
-      // compute units otherwise: 85 us alone, 170 us side by side) -- the first trial sooner, a rejected trial's successor later
-      if (spec_delay) HIPCK(hipEventRecord(ev_fork, st));
-      // host enqueue order: the other streams' Schur complements right away (they start at the fork on the device and run beside
-      // the main stream's), their factorisation chains only after this trial's own chain and tail (below) -- the main stream never
-      // runs dry behind the ~45 launches of another chain
-      defer_n2 = (ov >= 2 && nsys - n1 > 1 && st3) ? 1 : nsys - n1;       // systems on the second stream
-      HIPCK(hipStreamWaitEvent(st2, ev_fork, 0));
-      mark("spec_start", st2);
-      if (build_system(defer_n2, sb, n1, st2)) return -1;
-      mark("spec_built", st2);
-      if (n1 + defer_n2 < nsys) { HIPCK(hipStreamWaitEvent(st3, ev_fork, 0)); if (build_system(nsys - n1 - defer_n2, sb, n1 + defer_n2, st3)) return -1; }
-      if (use_graph && !prm.profile) { if (solve_chain(st, n1, 0)) return -1; }
-      else {
-        tic(ST_CHOL); chol_factor(st, plan, d_red.p, d_fail.p, n1, red_stride, 0); toc();
-        tic(ST_SOLVE); chol_back(st, plan, d_red.p, n1, red_stride, 0); toc();
-      }
-      defer_n1 = n1; defer_nsys = nsys;
-    } else {
-    plan.persist.batch_sys = nsys;
-    if (build_system(nsys, sb)) return -1;
-    if (np) {
-      if (use_graph && !prm.profile) {
-        // the ~40 dependent launches of one factorisation + back-substitution replayed from a captured graph
-        // (arguments never change between solves: same buffers, same plan); one graph per batch width
-        if (!chol_exec[nsys]) {
-          hipGraph_t g = nullptr;
-          if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            chol_factor(st, plan, d_red.p, d_fail.p, nsys, red_stride);
-            chol_back(st, plan, d_red.p, nsys, red_stride);
-            if (hipStreamEndCapture(st, &g) != hipSuccess || !g || hipGraphInstantiate(&chol_exec[nsys], g, nullptr, nullptr, 0) != hipSuccess) { chol_exec[nsys] = nullptr; use_graph = 0; }
-            if (g) (void)hipGraphDestroy(g);
-          } else use_graph = 0;
-          (void)hipGetLastError();
-        }
-        if (chol_exec[nsys]) HIPCK(hipGraphLaunch(chol_exec[nsys], st));
-        else { chol_factor(st, plan, S(), d_fail.p, nsys, red_stride); chol_back(st, plan, S(), nsys, red_stride); }
-      } else {
-        tic(ST_CHOL); chol_factor(st, plan, S(), d_fail.p, nsys, red_stride); toc();
-        tic(ST_SOLVE); chol_back(st, plan, S(), nsys, red_stride); toc();
-      }
-      if (st2 && nsys > 1 && !multi() && spec_trials && use_mailbox && !prm.profile) {
-        // every system of the batch is solved: while this trial runs on the main stream, the next one's step is applied and evaluated
-        // on the second stream (enqueue_spec_trial), so that a rejection finds its result waiting
-        HIPCK(hipEventRecord(ev_fork, st)); HIPCK(hipStreamWaitEvent(st2, ev_fork, 0));
-        spec2_from = 1; spec3_from = MAX_SYS; ahead_single = true;
-      }
-    }
-    }
-    spec_ok = (nsys > 1);
-    timing.n_solves++;
-  }
+  } else if (start_batch(lam, ni, df)) return -1;
   mark("solved", st);
-  const int tr = cand(sys_cur); last_tr = tr; last_xp = &d_xp_cand; last_xl = &d_xl;
-  const double* bp_glob = bp();
-  tic(ST_UPDATE);
-  const bool small = small_mode();
-  const int nbb = (nfl*BS_TPP + BS_BLOCK - 1)/BS_BLOCK;
-  const int ncb = trial_chain_blocks();
-  if (ncb) { hipLaunchKernelGGL(k_trial_apply, dim3(ncb + (nfl ? nbb : 0)), dim3(256), (size_t)P.npose*12*sizeof(double), st, P, ncb, lam, (const double*)rhs(), bp_glob, (const double*)d_pose[cur].p, d_pose[tr].p, d_res.p + 6, d_xp_cand.p,
-                                d_first[tr].p, d_second[tr].p, d_last[tr].p, (const double*)d_g.p, (const double*)d_W.p, (const double*)Vinv(),
-                                (const double*)d_pt[cur].p, d_pt[tr].p, d_xl.p, d_part1.p, d_part2.p); note_launch("k_trial_apply"); }
-  else {
-  hipLaunchKernelGGL(k_update_poses, dim3(1), dim3(256), 0, st, P, lam, rhs(), bp_glob, d_pose[cur].p, d_pose[tr].p, d_res.p + 6, d_xp_cand.p);
-  if (nfl) hipLaunchKernelGGL(k_backsub, dim3(nbb), dim3(BS_BLOCK), 0, st, P, lam, rhs(), d_g.p, d_W.p, Vinv(),
-                              d_pt[cur].p, d_pt[tr].p, d_xl.p, d_part1.p, d_part2.p);
-  }
-  toc();
-  tic(ST_EVAL);
-  if (!ncb) launch_chains(tr);
-  const int nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
-  const bool mailbox = use_mailbox && !prm.profile;
-  mail_ticket0 = ++mail_ticket;
-  const bool with_head = head_ahead_want && mailbox && !small && large_heads();
-  launch_eval(tr, true, nullptr);
-  if (multi()) {
-    // (several ranks: the sums are rank-local until the trial's all-reduce; k_trial_post writes the block and the mailbox)
-    if (multi_trial_tail(st, 0, sys_cur, tr, nbe, d_part0.p, nbb, nfl ? d_part1.p : nullptr, nfl ? d_part2.p : nullptr, d_res.p + 6, 6, true,
-                         mailbox ? h_mail_dev : (double*)nullptr, MAIL_TICKET, mail_ticket0)) return -1;
-  } else {
-    if (join_sum()) return -1;                       // (this launch forwards d_res[24..28], the head of the iteration, to the host)
-    hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st, nbe, (const double*)d_part0.p, nbb, (const double*)(nfl ? d_part1.p : nullptr),
-                       nbb, (const double*)(nfl ? d_part2.p : nullptr), d_res.p, 0, (const int*)d_fail.p + sys_cur,
-                       mailbox ? h_mail_dev : (double*)nullptr, 29, mail_ticket0, (const double*)nullptr, 0, start_blk);
-    if (!nfl) HIPCK(hipMemsetAsync(d_res.p + 1, 0, 2*sizeof(double), st));
-  }
-  toc();
+  int tr = 0; bool with_head = false;
+  if (enqueue_main_trial(lam, tr, with_head)) return -1;
   mark("trial_end", st);
-  if (head_ahead_want && mailbox && !multi() && small) { if (head_ahead(tr)) return -1; mark("head_ahead", st); }
-  if (defer_nsys) {
-    const int n2 = defer_n2;
-    if (solve_chain(st2, n2, defer_n1)) return -1;
-    mark("spec_done", st2);
-    HIPCK(hipEventRecord(ev_spec, st2));
-    spec_pending = true; spec2_from = defer_n1; spec3_from = defer_n1 + n2;
-    if (defer_n1 + n2 < defer_nsys) {
-      const int n3 = defer_nsys - defer_n1 - n2;
-      if (solve_chain(st3, n3, defer_n1 + n2)) return -1;
-      HIPCK(hipEventRecord(ev_spec3, st3));
-      spec3_pending = true;
-    }
-  }
-  if (defer_nsys) {
-    if (run_ahead(1)) return -1;
-    if (spec_trials >= 2 && !multi()) for (int q = 2; q < defer_nsys; ++q) if (run_ahead(q)) return -1;
-  } else if (ahead_single) { if (run_ahead(1)) return -1; }
+  const bool mailbox = use_mailbox && !prm.profile;
+  if (head_ahead_want && mailbox && !multi() && small_mode()) { if (head_ahead(tr)) return -1; mark("head_ahead", st); }
+  if (finish_deferred_chains(df)) return -1;
+  if (run_trials_ahead(df)) return -1;
   // (the head of this trial's state goes out AFTER the next trial ahead has been handed to the second stream: the device needs ~70 us
   //  for the trial's own kernels, the host ~4 us per launch -- the trial ahead must not wait for the host to get through the head's)
   if (with_head && mailbox && !multi()) { if (enqueue_head(st, sys_cur, tr, false)) return -1; mark("head_ahead", st); }
   if (sum_aside()) return -1;
-  if (mailbox) {
+  return collect_trial(sys_cur, false, lam, ok2, ni);
+}
+// a fresh batch: the system of this lambda and, speculatively, those of the lambdas a rejection would ask for next -- built and
+// solved together on the main stream, or split over the streams
+int mcp_ba::start_batch(double lam, double ni, Deferred& df) {
+  sys_cur = 0;
+  // the lambdas of the rejection branch of the LM schedule: lambda *= ni; ni *= 2 (same operations as schedule())
+  const int nsys = (ni > 0) ? 1 + std::max(0, std::min(spec_now(), MAX_SYS - 1)) : 1;
+  SysBatch sb; std::memset(&sb, 0, sizeof sb);
+  { double l = lam, f = ni; for (int q = 0; q < nsys; ++q) { batch_lambda[q] = sb.lambda[q] = l; sb.lambda_init[q] = (rank == 0) ? l : 0.0; l *= f; f *= 2; } }
+  batch_n = nsys;
+  if (cancel_spec_trials()) return -1;   // (a re-solve inside an iteration: nothing of the previous batch is wanted any more)
+  if (join_spec()) return -1;            // (... and its stragglers first)
+  if (!fail_clean) HIPCK(hipMemsetAsync(d_fail.p, 0, 4*sizeof(int), st));
+  fail_clean = false;
+  // One rank, one-launch factorisation: every system of the batch has its own critical workgroup, four systems take the time of
+  // one, so the batch stays on the main stream (measured: 990 vs 940 LM it/s; MCP_BA_OVERLAP=1 splits it as the per-step kernels
+  // want it).  Several ranks: one speculative stream, the one lane 1 belongs to.
+  const int ov_single = (overlap_auto && plan.use_persist && plan.persist.ok) ? 0 : overlap_spec;
+  const int ov = multi() ? std::min(overlap_spec, 1) : ov_single;
+  const bool split = ov && nsys > 1 && np > 0 && st2;
+  if (split ? solve_split(nsys, ov, sb, df) : solve_batched(nsys, sb, df)) return -1;
+  spec_ok = (nsys > 1);
+  timing.n_solves++;
+  return 0;
+}
+// system 0 -- the one this trial needs -- alone on the main stream; the speculative systems behind the fork on the second
+// stream.  Same kernels on the same data as the batched path: the numbers do not depend on which stream produced them.
+int mcp_ba::solve_split(int nsys, int ov, SysBatch& sb, Deferred& df) {
+  // main_sys systems stay on the main stream: 1 = only the trial's own; 2 = also the first speculative one, so that a second trial
+  // never waits for the other stream (its system comes out of the same launches as the first trial's)
+  const int n1 = std::min(std::max(main_sys, 1), nsys - 1);
+  HIPCK(hipEventRecord(ev_fork, st));
+  plan.persist.batch_sys = nsys;
+  mark("fork", st);
+  if (build_system(n1, sb, 0, st)) return -1;
+  mark("main_built", st);
+  // MCP_BA_SPEC_DELAY=1: the speculative systems' Schur complements start only when the trial's own is through (they share the
+  // compute units otherwise: 85 us alone, 170 us side by side) -- the first trial sooner, a rejected trial's successor later
+  if (spec_delay) HIPCK(hipEventRecord(ev_fork, st));
+  // host enqueue order: the other streams' Schur complements right away (they start at the fork on the device and run beside
+  // the main stream's), their factorisation chains only after this trial's own chain and tail (finish_deferred_chains) -- the main
+  // stream never runs dry behind the ~45 launches of another chain
+  const int n2 = (ov >= 2 && nsys - n1 > 1 && st3) ? 1 : nsys - n1;       // systems on the second stream
+  HIPCK(hipStreamWaitEvent(st2, ev_fork, 0));
+  mark("spec_start", st2);
+  if (build_system(n2, sb, n1, st2)) return -1;
+  mark("spec_built", st2);
+  if (n1 + n2 < nsys) { HIPCK(hipStreamWaitEvent(st3, ev_fork, 0)); if (build_system(nsys - n1 - n2, sb, n1 + n2, st3)) return -1; }
+  if (solve_chain(st, n1, 0)) return -1;
+  df.n1 = n1; df.n2 = n2; df.nsys = nsys;
+  return 0;
+}
+// the whole batch on the main stream
+int mcp_ba::solve_batched(int nsys, SysBatch& sb, Deferred& df) {
+  plan.persist.batch_sys = nsys;
+  if (build_system(nsys, sb)) return -1;
+  if (!np) return 0;
+  if (solve_chain(st, nsys, 0)) return -1;
+  if (st2 && nsys > 1 && !multi() && spec_trials && use_mailbox && !prm.profile) {
+    // every system of the batch is solved: while this trial runs on the main stream, the next one's step is applied and evaluated
+    // on the second stream (enqueue_spec_trial), so that a rejection finds its result waiting
+    HIPCK(hipEventRecord(ev_fork, st)); HIPCK(hipStreamWaitEvent(st2, ev_fork, 0));
+    spec2_from = 1; spec3_from = MAX_SYS; df.ahead_single = true;
+  }
+  return 0;
+}
+// the step of system sys_cur on the main stream: candidate state cand(sys_cur), the handle's own scratch, result block d_res[0..]
+// -> mailbox 0 with the iteration-start block
+int mcp_ba::enqueue_main_trial(double lam, int& tr, bool& with_head) {
+  tr = cand(sys_cur); last_tr = tr; last_xp = &d_xp_cand; last_xl = &d_xl;
+  const bool mailbox = use_mailbox && !prm.profile;
+  mail_ticket0 = ++mail_ticket;
+  with_head = head_ahead_want && mailbox && !small_mode() && large_heads();
+  const TrialIo io{st, 0, sys_cur, tr, lam, rhs(), bp(), Vinv(), d_xp_cand.p, d_xl.p, d_part0.p, d_part1.p, d_part2.p,
+                   d_res.p + 6, 6, d_res.p, d_fail.p + sys_cur, mailbox ? h_mail_dev : (double*)nullptr, multi() ? MAIL_TICKET : 29, mail_ticket0, true, false, false};
+  return launch_trial_step(io);
+}
+// the factorisation chains of the systems a split batch left on the other streams: behind the main trial in the host's order
+int mcp_ba::finish_deferred_chains(const Deferred& df) {
+  if (!df.nsys) return 0;
+  if (solve_chain(st2, df.n2, df.n1)) return -1;
+  mark("spec_done", st2);
+  HIPCK(hipEventRecord(ev_spec, st2));
+  spec_pending = true; spec2_from = df.n1; spec3_from = df.n1 + df.n2;
+  if (df.n1 + df.n2 < df.nsys) {
+    if (solve_chain(st3, df.nsys - df.n1 - df.n2, df.n1 + df.n2)) return -1;
+    HIPCK(hipEventRecord(ev_spec3, st3));
+    spec3_pending = true;
+  }
+  return 0;
+}
+// the steps of the speculative systems of a fresh batch, evaluated ahead (run_ahead decides which of them, and where)
+int mcp_ba::run_trials_ahead(const Deferred& df) {
+  if (df.nsys) {
+    if (run_ahead(1)) return -1;
+    if (spec_trials >= 2 && !multi()) for (int q = 2; q < df.nsys; ++q) if (run_ahead(q)) return -1;
+  } else if (df.ahead_single) { if (run_ahead(1)) return -1; }
+  return 0;
+}
+// The one place that takes a trial's result block on the host: system q's, from the mailbox of the trial evaluated ahead
+// (pose parts at [4..5]) or from the main stream's mailbox / read-back (pose parts at [6..7], the iteration-start block behind them).
+int mcp_ba::collect_trial(int q, bool ahead, double lam, bool& ok2, double ni) {
+  if (ahead) {
+    last_tr = cand(q); last_xp = &lane[q].xp; last_xl = &lane[q].xl;
+    if (run_ahead(q + 1)) return -1;
+    if (wait_mail(q, lane[q].pre_ticket, multi() ? MAIL_TICKET : 6)) return -1;
+  } else if (use_mailbox && !prm.profile) {
     // the block (trial results [0..7], iteration-start block [24..28]) is already on its way to the host
     if (wait_mail(0, mail_ticket0, multi() ? MAIL_TICKET : 29)) return -1;
   } else if (read_results(MAIL_TICKET)) return -1;          // trial results [0..7] and, for compute(), the iteration-start block [24..28]
-  if (multi()) take_trial_flags(sys_cur);
+  if (multi()) take_trial_flags(q);
+  if (ahead) {
+    lane[q].pre_run = false;
+    HIPCK(hipStreamWaitEvent(st, lane[q].ev_tr, 0));         // whatever the main stream does next with the trial's state comes after the kernels that made it
+    mark("pre_used", st);
+    ++dbg_pre;
+  }
+  const int pose_at = ahead ? 4 : 6;
   if (!nfl_total) h_res[1] = h_res[2] = 0.0;
-  h_res[1] += h_res[6]; h_res[2] += h_res[7];
+  h_res[1] += h_res[pose_at]; h_res[2] += h_res[pose_at + 1];
   if (h_res[3] >= 1e9) return persist_fallback(lam, ok2, ni);
   ok2 = (h_res[3] == 0.0);
   timing.n_trials++;
@@ -3173,236 +3227,252 @@ int mcp_ba::persist_fallback(double lam, bool& ok2, double ni) {
   return solve_trial(lam, ok2, ni);
 }
 
+// Levenberg-Marquardt as g2o runs it for ChainBundle (OptimizationAlgorithmLevenberg::solve): per iteration the head (sigma^2 and
+// robust chi2 at the iteration-start state), the linearisation, and trials until one is accepted
 int mcp_ba::compute(volatile unsigned char* abort_flag, int n_iter, double user_lambda) {
-  auto t_begin = std::chrono::steady_clock::now();
-  HIPCK(hipSetDevice(device));
-  (void)hipGetLastError(); launch_err.clear(); plan.launch_failed = nullptr;      // (launch checks below are about THIS solve)
-  std::memset(&timing, 0, sizeof timing);
-  evs.clear(); ev_used = 0;
-  if (n_iter < 0) n_iter = prm.max_iterations;      // 0 runs nothing, as g2o optimize(0) (-> -1 unless externally aborted)
-  auto terminate = [&]() { return abort_flag && *abort_flag; };
-  // Initialize(), ChainBundle.cc:1284-1298
-  outliers.clear(); logs.clear();
-  int conv_mag = 0, conv_res = 0;
-  auto t_first_end = t_begin;
-  static const bool trace_compute = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
-  if (dirty) { if (prepare()) return MCP_ERR_RUNTIME; }
-  timing.schur_mfma_per_system = schur_mfma; timing.schur_flops_structural = schur_flops;
-  timing.chol_flops_plan = (np > 0 && plan.persist.ok) ? plan.persist.flops : 0.0;
-  timing.chol_chains = (np > 0 && plan.persist.ok) ? plan.persist.nseg : 0;
-  converged = 0; total_iterations = 0; spec_hot = 0;
+  LmRun R; R.abort_flag = abort_flag; R.n_iter = n_iter; R.user_lambda = user_lambda;
+  if (begin_solve(R)) return MCP_ERR_RUNTIME;
   int nCounter = 0;
   // emptiness is decided on the GLOBAL totals: a rank whose shard holds no measurement (or no free point) still runs every
   // kernel with zero-size inputs and joins every collective, or the other ranks would wait in them for ever
   if (nx_total() == 0 || m_total == 0) { nCounter = -1; if (P.nmeas) { launch_chains(cur); launch_eval(cur, false, nullptr); } }
   else {
     tic(ST_EVAL); launch_chains(cur); launch_eval(cur, false, nullptr); toc();
-    double ni = 2; bool ok = true; int cj = 0;
-    for (int it = 0; it < n_iter && !terminate() && ok; ++it) {
-      mcp_ba_iter_log lg; std::memset(&lg, 0, sizeof lg);
+    bool ok = true;
+    for (int it = 0; it < R.n_iter && !R.terminate() && ok; ++it) {
+      LmIter I; I.it = it; std::memset(&I.lg, 0, sizeof I.lg);
       mark("iter", st);
-      // preIteration + first robustify: sigma^2 from |chi2| at the iteration-start state
-      constexpr int RS = 24;
-      // (small bundle: the head of this iteration was enqueued behind the trial that produced this state, before the host knew it
-      //  would be accepted -- head_ahead(); all that is left is to make its sigma block the current one)
-      bool head_done = (it > 0 && head_ahead_for == cur);
-      head_ahead_for = -1;
-      if (head_done) { if (robust) flip_sig(); ++dbg_head_ahead; }
-      start_blk = nullptr;
-      bool lin_done = false;
-      if (it > 0 && large_heads() && acc_head_q >= 0 && head_enq[acc_head_q] && head_state[acc_head_q] == cur) {
-        // The accepted trial brought its head along (enqueue_head).  The linearisation goes out behind it AT ONCE, on the assumption that
-        // the head could finish the median (it nearly always can); only then does the host look at the head's status word -- if the
-        // prediction missed (nothing was written to the block), the plain selection runs and the linearisation is simply redone.
-        const int q = acc_head_q, keep = sig_idx;
-        HeadScratch& H = hsc[head_par*MAX_SYS + q];
-        HIPCK(hipStreamWaitEvent(st, head_ev[q], 0));          // (a trial evaluated ahead: its head ran on the head stream)
-        sig_idx = 2 + head_par*MAX_SYS + q;
-        start_rides = false;
-        if (linearize()) return MCP_ERR_RUNTIME;
-        const int hs = wait_head(q);
-        if (hs < 0) return MCP_ERR_RUNTIME;
-        if (hs == 1) {
-          start_blk = H.rs;
-          // the robust chi2 of the new current state at the new sigma: the host's business (it arrives with the first trial's result), so
-          // it is summed BESIDE the linearisation, on the second stream if there is one
-          hipStream_t ss = (st2 && ev_sum) ? st2 : st;
-          if (ss != st) HIPCK(hipStreamWaitEvent(ss, head_ev[q], 0));
-          if (robust_total(ss, cur, sig(), H.part, H.rs, 0)) return MCP_ERR_RUNTIME;
-          if (ss != st) { HIPCK(hipEventRecord(ev_sum, ss)); sum_pending = true; }
-          head_done = true; lin_done = true; ++dbg_head_ahead;
-        } else { sig_idx = keep; ++dbg_head_miss; }
-      }
-      acc_head_q = -1;
-      for (int q = 0; q < MAX_SYS; ++q) head_enq[q] = false;      // (what this iteration's trials enqueue goes to the other parity's slots)
-      head_par = it & 1;
-      head_ahead_want = (small_mode() || large_heads()) && use_mailbox && !prm.profile && it + 1 < n_iter;
-      if (head_done) { }
-      else if (small_mode()) { if (head_small(cur)) return MCP_ERR_RUNTIME; }
-      else if (use_head_large()) { if (head_large(cur, RS, nullptr)) return MCP_ERR_RUNTIME; }
-      else {
-      if (robust) { if (median_sigma(cur)) return MCP_ERR_RUNTIME; }
-      tic(ST_EVAL);
-      // iteration-start robust chi2 and the sigma block go to d_res[24..28]; they are read back together with the first
-      // trial's results (one host synchronisation less per iteration) -- except in the first iteration, whose lambda comes
-      // from the diagonal of the freshly built system
-      if (robust_total(st, cur, sig(), d_part0.p, d_res.p, RS)) return MCP_ERR_RUNTIME;
-      toc();
-      }
-      // several ranks: the sum over the ranks rides on the first trial's all-reduce (d_res[0..3] + d_res[4], see solve_trial);
-      // the first iteration needs it before its first trial
-      if (it == 0) { if (allreduce(d_res.p + RS, 1, 0, false, "iteration-start chi2")) return MCP_ERR_RUNTIME; }
-      start_rides = (it > 0 && multi());
-      if (!lin_done) { if (linearize()) return MCP_ERR_RUNTIME; }
-      if (it == 0 && !(user_lambda > 0)) {
-        // computeLambdaInit [g2o]: 1e-5 * max |H_jj| over the pose and point diagonals; the pose diagonal is summed from
-        // the staged blocks (and over the ranks), the point diagonals are rank-local (maximum over ranks taken below)
-        if (np && asm_long) hipLaunchKernelGGL(k_udiag_long, dim3((np*ASML_LPE + 255)/256), dim3(256), 0, st, A, np, (const double*)d_stU.p, (const double*)Ubig(), d_udiag.p);
-        else if (np) hipLaunchKernelGGL(k_udiag, dim3((np + 255)/256), dim3(256), 0, st, A, np, (const double*)d_stU.p, (const double*)Ubig(), d_udiag.p);
-        if (multi() && np) { if (allreduce(d_udiag.p, np, 0, false, "pose diagonal for the initial lambda")) return MCP_ERR_RUNTIME; }
-        const int nbm = std::min(256, (std::max(np, nfl) + 1023)/1024);
-        if (nbm > 1) {          // (d_part1: the trials' partial sums live there later; nothing of this iteration has used it yet)
-          hipLaunchKernelGGL(k_max_diag_part, dim3(nbm), dim3(256), 0, st, np, (const double*)d_udiag.p, 1, nfl, (const double*)d_V.p, d_part1.p);
-          hipLaunchKernelGGL(k_max_of, dim3(1), dim3(256), 0, st, nbm, (const double*)d_part1.p, d_res.p + 5);
-        } else
-        hipLaunchKernelGGL(k_max_diag, dim3(1), dim3(256), 0, st, np, (const double*)d_udiag.p, 1, nfl, (const double*)d_V.p, d_res.p + 5);
-      }
-      static_assert(RS + 1 == 25, "median_sigma() writes the sigma block to d_res + 25");
-      double currentChi = 0, tempChi = 0;
-      bool start_pending = true;
-      auto take_start = [&]() {
-        currentChi = tempChi = h_res[RS];
-        { unsigned long long b; std::memcpy(&b, &h_res[RS], 8); if (b == HL_FAILED_BITS) head_failed = true; }
-        if (robust) { sigma_sq = h_res[RS + 1]; sigma_sq_lim = h_res[RS + 2]; pred_bin = sel_coarse_bin(h_res[RS + 4]); }
-        lg.chi2_start = currentChi; lg.sigma_sq = sigma_sq;
-        start_pending = false;
-      };
-      if (it == 0) { if (read_results(RS + 5)) return MCP_ERR_RUNTIME; take_start(); }
-      if (head_failed) { head_failed = false; set_err("the head of an iteration (k_head_large) gave up at a barrier"); return MCP_ERR_RUNTIME; }
-      if (it == 0) {
-        if (user_lambda > 0) lambda = user_lambda;
-        else {
-          double md = h_res[5];
-          if (multi()) {   // max over ranks of the V diagonals (U is already global)
-            if (world > 8) { set_err("more than 8 ranks"); return MCP_ERR_RUNTIME; }
-            std::vector<double> slots(world, 0.0); slots[rank] = md;
-            HIPCK(hipMemcpyAsync(d_res.p + 16, slots.data(), world*sizeof(double), hipMemcpyHostToDevice, st));
-            if (allreduce(d_res.p + 16, world, 0, true, "initial lambda")) return MCP_ERR_RUNTIME;
-            HIPCK(hipMemcpy(slots.data(), d_res.p + 16, world*sizeof(double), hipMemcpyDeviceToHost));
-            for (double v : slots) md = std::max(md, v);
-          }
-          lambda = 1e-5*md;
-        }
-        ni = 2;
-      }
-      double rho = 0; int qmax = 0; int accepted = 0; double ss_last = 0; double trial_chi_raw = currentChi;
-      static const bool trace_trials = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 3; }();
-      const auto it_t0 = std::chrono::steady_clock::now();
-      std::string it_line;
+      if (iteration_head(R, I)) return MCP_ERR_RUNTIME;
+      if (it == 0 && initial_lambda(R, I)) return MCP_ERR_RUNTIME;
+      I.t0 = std::chrono::steady_clock::now();
       do {
-        bool ok2 = true;
-        const int pre0 = dbg_pre;
-        if (solve_trial(lambda, ok2, ni)) return MCP_ERR_RUNTIME;
-        if (trace_trials) { char b[64]; snprintf(b, sizeof b, " %s%.0f", dbg_pre != pre0 ? "a" : (sys_cur ? "s" : "m"), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - it_t0).count()); it_line += b; }
-        if (start_pending) take_start();
-        if (head_failed) { head_failed = false; set_err("the head of an iteration (k_head_large) gave up at a barrier"); return MCP_ERR_RUNTIME; }
-        if (test_fail_trial > 0 && ++test_trial_no == test_fail_trial) ok2 = false;      // (test hook: this trial's factorisation "failed")
-        double scale, ss;
-        trial_chi_raw = h_res[0];
-        if (ok2) {
-          tempChi = h_res[0]; scale = h_res[1]; ss = h_res[2];
-          // the solver's x of the last successful solve (what a later failed solve falls back on): swap, no copy
-          std::swap(d_xp_good.p, last_xp->p); std::swap(d_xp_good.n, last_xp->n);
-          std::swap(d_xl_good.p, last_xl->p); std::swap(d_xl_good.n, last_xl->n);
-        } else {
-          // CHOLMOD-failure analogue: the solver's x keeps its previous content [g2o]; recompute the
-          // scale terms from it with the current lambda and b
-          tempChi = DBL_MAX;
-          scale = 0; ss = 0;
-          head_ahead_for = -1;                       // (the state is about to be rewritten with the stale step)
-          for (int q = 0; q < MAX_SYS; ++q) head_enq[q] = false;
-          std::vector<double> xp(np), xl((size_t)nfl*3), bpv(np), gv((size_t)nfl*3);
-          if (np) { HIPCK(hipMemcpy(xp.data(), d_xp_good.p, (size_t)np*8, hipMemcpyDeviceToHost)); HIPCK(hipMemcpy(bpv.data(), bp(), (size_t)np*8, hipMemcpyDeviceToHost)); }
-          if (nfl) { HIPCK(hipMemcpy(xl.data(), d_xl_good.p, (size_t)nfl*24, hipMemcpyDeviceToHost)); HIPCK(hipMemcpy(gv.data(), d_g.p, (size_t)nfl*24, hipMemcpyDeviceToHost)); }
-          for (int j = 0; j < np; ++j) { scale += xp[j]*(lambda*xp[j] + bpv[j]); ss += xp[j]*xp[j]; }
-          double sl = 0, sq = 0;
-          for (size_t j = 0; j < xl.size(); ++j) { sl += xl[j]*(lambda*xl[j] + gv[j]); sq += xl[j]*xl[j]; }
-          if (multi()) {   // point parts are rank-local
-            double v2[2] = { sl, sq };
-            HIPCK(hipMemcpy(d_res.p + 16, v2, 16, hipMemcpyHostToDevice));
-            if (allreduce(d_res.p + 16, 2, 0, true, "step statistics after a failed factorisation")) return MCP_ERR_RUNTIME;
-            HIPCK(hipMemcpy(v2, d_res.p + 16, 16, hipMemcpyDeviceToHost)); sl = v2[0]; sq = v2[1];
-          }
-          scale += sl; ss += sq;
-          // g2o goes on with update(_solver->x()) -- the solver's x is what the last successful solve left -- and computeActiveErrors:
-          // the edges then hold the errors of (current state (+) stale x), which is what the residual action reads if this was the
-          // iteration's last trial (OptimizationAlgorithmLevenberg::solve [3P-memory]; ChainBundle.cc:1096-1116).  Same here.
-          {
-            const int tr = last_tr;
-            hipLaunchKernelGGL(k_update_poses, dim3(1), dim3(256), 0, st, P, lambda, (const double*)d_xp_good.p, (const double*)bp(), (const double*)d_pose[cur].p, d_pose[tr].p, d_res.p + 6, d_xp_cand.p);
-            if (nfl) hipLaunchKernelGGL(k_apply_point_step, dim3((nfl + 255)/256), dim3(256), 0, st, P, (const double*)d_xl_good.p, (const double*)d_pt[cur].p, d_pt[tr].p);
-            launch_chains(tr);
-            launch_eval(tr, true, nullptr);
-            const int nbe2 = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
-            hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st, nbe2, (const double*)d_part0.p, 0, (const double*)nullptr, 0, (const double*)nullptr, d_res.p, 0, (const int*)nullptr);
-            if (allreduce(d_res.p, 1, 0, false, "chi2 of the stale step after a failed factorisation")) return MCP_ERR_RUNTIME;
-            if (read_results(1)) return MCP_ERR_RUNTIME;
-            trial_chi_raw = h_res[0];
-            sel_src = -1;
-          }
-        }
-        ss_last = ss;
-        rho = currentChi - tempChi;
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - std::pow((2*rho - 1), 3);
-          alpha = std::min(alpha, 2./3.);
-          const double sf = std::max(1./3., alpha);
-          lambda *= sf; ni = 2; currentChi = tempChi; accepted = 1;
-          cur = last_tr;                             // discardTop: the trial state becomes current
-          acc_head_q = ok2 ? sys_cur : -1;           // (its head, if one was enqueued behind it, is for exactly this state)
-          // ... and the digit histograms that rode on its all-reduce describe the new chi2 array -- unless the factorisation had failed:
-          // then the accepted state is the STALE step's (negative scale), whose chi2 never rode on anything
-          sel_src = (multi() && ok2) ? sys_cur : -1;
-        } else {
-          lambda *= ni; ni *= 2; accepted = 0;       // pop: the current buffers were never touched
-          spec_hot = 4;                              // (small bundles: from here on the rejection branch's systems are solved ahead again)
-        }
-        ++qmax;
-      } while (rho < 0 && qmax < prm.max_trials_after_failure && !terminate());
-      if (trace_trials) fprintf(stderr, "[mcp_ba trials] it %d: results at (us; m = solved for this trial, a = evaluated ahead, s = system of the batch, trial run now)%s\n", it, it_line.c_str());
+        if (run_trial(R, I)) return MCP_ERR_RUNTIME;
+      } while (I.rho < 0 && I.qmax < prm.max_trials_after_failure && !R.terminate());
       if (cancel_spec_trials()) return MCP_ERR_RUNTIME;
-      ok = !(qmax == prm.max_trials_after_failure || rho == 0);
-      ++cj;
-      // post-iteration actions
-      const double rms = std::sqrt(ss_last/(double)nx_total());
-      if (rms < prm.update_rms_limit && !prm.disable_convergence) { conv_mag = 1; if (abort_flag) *abort_flag = 1; }
-      {
-        // activeRobustChi2 of whatever errors the edges hold: the last trial's (or, when verbose, the
-        // recomputed errors of the current state)
-        // (an accepted trial's errors ARE the edges' errors; only after a failed factorisation whose stale step was accepted --
-        // negative scale -- does that differ from the schedule's currentChi, which is DBL_MAX then)
-        double curchi = accepted ? trial_chi_raw : (verbose ? currentChi : trial_chi_raw);
-        const double pct = (last_chi2_action - curchi)/last_chi2_action;
-        if (!prm.disable_convergence) {
-          if (pct >= 0 && pct <= prm.update_percent_limit) { conv_res = 1; if (abort_flag) *abort_flag = 1; }
-          else if (curchi == 0) { conv_res = 1; if (abort_flag) *abort_flag = 1; }
-        }
-        last_chi2_action = curchi;
-        lg.chi2_end = curchi;
-      }
-      if (qmax == 1 && spec_hot > 0) --spec_hot;     // (an iteration that accepted its first trial)
-      total_iterations += qmax;
-      lg.lambda_end = lambda; lg.trials = qmax; lg.accepted = accepted; lg.rms_update = rms;
-      logs.push_back(lg);
-      if (it == 0) t_first_end = std::chrono::steady_clock::now();
+      ok = !(I.qmax == prm.max_trials_after_failure || I.rho == 0);
+      post_iteration(R, I);
+      ++nCounter;
     }
-    nCounter = cj;
   }
-  const auto t_loop_end = std::chrono::steady_clock::now();
-  if (join_spec()) return MCP_ERR_RUNTIME;
-  if (join_sum()) return MCP_ERR_RUNTIME;
+  R.t_loop_end = std::chrono::steady_clock::now();
+  return end_solve(R, nCounter);
+}
+// Initialize(), ChainBundle.cc:1284-1298
+int mcp_ba::begin_solve(LmRun& R) {
+  R.t_begin = R.t_first_end = std::chrono::steady_clock::now();
+  HIPCK(hipSetDevice(device));
+  (void)hipGetLastError(); launch_err.clear(); plan.launch_failed = nullptr;      // (launch checks below are about THIS solve)
+  std::memset(&timing, 0, sizeof timing);
+  evs.clear(); ev_used = 0;
+  if (R.n_iter < 0) R.n_iter = prm.max_iterations;      // 0 runs nothing, as g2o optimize(0) (-> -1 unless externally aborted)
+  outliers.clear(); logs.clear();
+  if (dirty) { if (prepare()) return MCP_ERR_RUNTIME; }
+  timing.schur_mfma_per_system = schur_mfma; timing.schur_flops_structural = schur_flops;
+  timing.chol_flops_plan = (np > 0 && plan.persist.ok) ? plan.persist.flops : 0.0;
+  timing.chol_chains = (np > 0 && plan.persist.ok) ? plan.persist.nseg : 0;
+  converged = 0; total_iterations = 0; spec_hot = 0;
+  return 0;
+}
+// preIteration + first robustify: sigma^2 from |chi2| at the iteration-start state, its robust chi2, and the linearisation there.
+// Three cases: the head is already on the main stream (small bundle: enqueued behind the trial that produced this state, before the
+// host knew it would be accepted -- head_ahead(); all that is left is to make its sigma block the current one), the accepted trial
+// brought its head along (large map, head_brought_along), or the plain head.
+int mcp_ba::iteration_head(LmRun& R, LmIter& I) {
+  const int it = I.it;
+  I.head_done = (it > 0 && head_ahead_for == cur);
+  head_ahead_for = -1;
+  if (I.head_done) { if (robust) flip_sig(); ++dbg_head_ahead; }
+  start_blk = nullptr;
+  if (it > 0 && large_heads() && acc_head_q >= 0 && lane[acc_head_q].head_enq && lane[acc_head_q].head_state == cur) { if (head_brought_along(I)) return MCP_ERR_RUNTIME; }
+  acc_head_q = -1;
+  for (int q = 0; q < MAX_SYS; ++q) lane[q].head_enq = false;      // (what this iteration's trials enqueue goes to the other parity's slots)
+  head_par = it & 1;
+  head_ahead_want = (small_mode() || large_heads()) && use_mailbox && !prm.profile && it + 1 < R.n_iter;
+  if (I.head_done) { }
+  else if (small_mode()) { if (head_small(cur)) return MCP_ERR_RUNTIME; }
+  else if (use_head_large()) { if (head_large(cur, RS, nullptr)) return MCP_ERR_RUNTIME; }
+  else {
+    if (robust) { if (median_sigma(cur)) return MCP_ERR_RUNTIME; }
+    tic(ST_EVAL);
+    // iteration-start robust chi2 and the sigma block go to d_res[24..28]; they are read back together with the first
+    // trial's results (one host synchronisation less per iteration) -- except in the first iteration, whose lambda comes
+    // from the diagonal of the freshly built system
+    if (robust_total(st, cur, sig(), d_part0.p, d_res.p, RS)) return MCP_ERR_RUNTIME;
+    toc();
+  }
+  // several ranks: the sum over the ranks rides on the first trial's all-reduce (d_res[0..3] + d_res[4], see multi_trial_tail);
+  // the first iteration needs it before its first trial
+  if (it == 0) { if (allreduce(d_res.p + RS, 1, 0, false, "iteration-start chi2")) return MCP_ERR_RUNTIME; }
+  start_rides = (it > 0 && multi());
+  if (!I.lin_done) { if (linearize()) return MCP_ERR_RUNTIME; }
+  return 0;
+}
+// The accepted trial brought its head along (enqueue_head).  The linearisation goes out behind it AT ONCE, on the assumption that
+// the head could finish the median (it nearly always can); only then does the host look at the head's status word -- if the
+// prediction missed (nothing was written to the block), the plain selection runs and the linearisation is simply redone.
+int mcp_ba::head_brought_along(LmIter& I) {
+  const int q = acc_head_q, keep = sig_idx;
+  HeadScratch& H = hsc[head_par*MAX_SYS + q];
+  HIPCK(hipStreamWaitEvent(st, lane[q].head_ev, 0));          // (a trial evaluated ahead: its head ran on the head stream)
+  sig_idx = 2 + head_par*MAX_SYS + q;
+  start_rides = false;
+  if (linearize()) return MCP_ERR_RUNTIME;
+  const int hs = wait_head(q);
+  if (hs < 0) return MCP_ERR_RUNTIME;
+  if (hs != 1) { sig_idx = keep; ++dbg_head_miss; return 0; }
+  start_blk = H.rs;
+  // the robust chi2 of the new current state at the new sigma: the host's business (it arrives with the first trial's result), so
+  // it is summed BESIDE the linearisation, on the second stream if there is one
+  hipStream_t ss = (st2 && ev_sum) ? st2 : st;
+  if (ss != st) HIPCK(hipStreamWaitEvent(ss, lane[q].head_ev, 0));
+  if (robust_total(ss, cur, sig(), H.part, H.rs, 0)) return MCP_ERR_RUNTIME;
+  if (ss != st) { HIPCK(hipEventRecord(ev_sum, ss)); sum_pending = true; }
+  I.head_done = true; I.lin_done = true; ++dbg_head_ahead;
+  return 0;
+}
+// the first iteration: its start block is read back at once, and lambda comes from the diagonal of the freshly built system
+// computeLambdaInit [g2o]: 1e-5 * max |H_jj| over the pose and point diagonals; the pose diagonal is summed from
+// the staged blocks (and over the ranks), the point diagonals are rank-local (maximum over ranks taken on the host)
+int mcp_ba::initial_lambda(LmRun& R, LmIter& I) {
+  if (!(R.user_lambda > 0)) {
+    if (np && asm_long) hipLaunchKernelGGL(k_udiag_long, dim3((np*ASML_LPE + 255)/256), dim3(256), 0, st, A, np, (const double*)d_stU.p, (const double*)Ubig(), d_udiag.p);
+    else if (np) hipLaunchKernelGGL(k_udiag, dim3((np + 255)/256), dim3(256), 0, st, A, np, (const double*)d_stU.p, (const double*)Ubig(), d_udiag.p);
+    if (multi() && np) { if (allreduce(d_udiag.p, np, 0, false, "pose diagonal for the initial lambda")) return MCP_ERR_RUNTIME; }
+    const int nbm = max_diag_parts(np, nfl);
+    if (nbm > 1) {          // (d_part1: the trials' partial sums live there later; nothing of this iteration has used it yet)
+      hipLaunchKernelGGL(k_max_diag_part, dim3(nbm), dim3(256), 0, st, np, (const double*)d_udiag.p, 1, nfl, (const double*)d_V.p, d_part1.p);
+      hipLaunchKernelGGL(k_max_of, dim3(1), dim3(256), 0, st, nbm, (const double*)d_part1.p, d_res.p + 5);
+    } else
+      hipLaunchKernelGGL(k_max_diag, dim3(1), dim3(256), 0, st, np, (const double*)d_udiag.p, 1, nfl, (const double*)d_V.p, d_res.p + 5);
+  }
+  if (read_results(RS + 5)) return MCP_ERR_RUNTIME;
+  if (take_start(I)) return MCP_ERR_RUNTIME;
+  R.ni = 2;
+  if (R.user_lambda > 0) { lambda = R.user_lambda; return 0; }
+  double md = h_res[5];
+  if (multi()) {   // max over ranks of the V diagonals (U is already global)
+    if (world > 8) { set_err("more than 8 ranks"); return MCP_ERR_RUNTIME; }
+    std::vector<double> slots(world, 0.0); slots[rank] = md;
+    HIPCK(hipMemcpyAsync(d_res.p + 16, slots.data(), world*sizeof(double), hipMemcpyHostToDevice, st));
+    if (allreduce(d_res.p + 16, world, 0, true, "initial lambda")) return MCP_ERR_RUNTIME;
+    HIPCK(hipMemcpy(slots.data(), d_res.p + 16, world*sizeof(double), hipMemcpyDeviceToHost));
+    for (double v : slots) md = std::max(md, v);
+  }
+  lambda = 1e-5*md;
+  return 0;
+}
+// the iteration-start block has reached the host (read back in the first iteration, with the first trial's results afterwards)
+int mcp_ba::take_start(LmIter& I) {
+  static_assert(RS + 1 == 25, "median_sigma() writes the sigma block to d_res + 25");
+  I.currentChi = I.tempChi = h_res[RS];
+  if (robust) { sigma_sq = h_res[RS + 1]; sigma_sq_lim = h_res[RS + 2]; pred_bin = sel_coarse_bin(h_res[RS + 4]); }
+  I.lg.chi2_start = I.currentChi; I.lg.sigma_sq = sigma_sq;
+  I.start_pending = false;
+  unsigned long long b; std::memcpy(&b, &h_res[RS], 8);
+  if (b == HL_FAILED_BITS) { set_err("the head of an iteration (k_head_large) gave up at a barrier"); return MCP_ERR_RUNTIME; }
+  return 0;
+}
+// one trial at the current lambda, and what the schedule makes of it
+int mcp_ba::run_trial(LmRun& R, LmIter& I) {
+  static const bool trace_trials = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 3; }();
+  bool ok2 = true;
+  const int pre0 = dbg_pre;
+  if (solve_trial(lambda, ok2, R.ni)) return MCP_ERR_RUNTIME;
+  if (trace_trials) { char b[64]; snprintf(b, sizeof b, " %s%.0f", dbg_pre != pre0 ? "a" : (sys_cur ? "s" : "m"), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - I.t0).count()); I.trace_line += b; }
+  if (I.start_pending && take_start(I)) return MCP_ERR_RUNTIME;
+  if (test_fail_trial > 0 && ++test_trial_no == test_fail_trial) ok2 = false;      // (test hook: this trial's factorisation "failed")
+  double scale = 0, ss = 0;
+  I.trial_chi_raw = h_res[0];
+  if (ok2) {
+    I.tempChi = h_res[0]; scale = h_res[1]; ss = h_res[2];
+    // the solver's x of the last successful solve (what a later failed solve falls back on): swap, no copy
+    std::swap(d_xp_good.p, last_xp->p); std::swap(d_xp_good.n, last_xp->n);
+    std::swap(d_xl_good.p, last_xl->p); std::swap(d_xl_good.n, last_xl->n);
+  } else {
+    I.tempChi = DBL_MAX;
+    if (stale_step(I, scale, ss)) return MCP_ERR_RUNTIME;
+  }
+  schedule(R, I, ok2, scale, ss);
+  return 0;
+}
+// CHOLMOD-failure analogue: the solver's x keeps its previous content [g2o]; recompute the scale terms from it with the current
+// lambda and b, and apply it
+int mcp_ba::stale_step(LmIter& I, double& scale, double& ss) {
+  scale = 0; ss = 0;
+  head_ahead_for = -1;                       // (the state is about to be rewritten with the stale step)
+  for (int q = 0; q < MAX_SYS; ++q) lane[q].head_enq = false;
+  std::vector<double> xp(np), xl((size_t)nfl*3), bpv(np), gv((size_t)nfl*3);
+  if (np) { HIPCK(hipMemcpy(xp.data(), d_xp_good.p, (size_t)np*8, hipMemcpyDeviceToHost)); HIPCK(hipMemcpy(bpv.data(), bp(), (size_t)np*8, hipMemcpyDeviceToHost)); }
+  if (nfl) { HIPCK(hipMemcpy(xl.data(), d_xl_good.p, (size_t)nfl*24, hipMemcpyDeviceToHost)); HIPCK(hipMemcpy(gv.data(), d_g.p, (size_t)nfl*24, hipMemcpyDeviceToHost)); }
+  for (int j = 0; j < np; ++j) { scale += xp[j]*(lambda*xp[j] + bpv[j]); ss += xp[j]*xp[j]; }
+  double sl = 0, sq = 0;
+  for (size_t j = 0; j < xl.size(); ++j) { sl += xl[j]*(lambda*xl[j] + gv[j]); sq += xl[j]*xl[j]; }
+  if (multi()) {   // point parts are rank-local
+    double v2[2] = { sl, sq };
+    HIPCK(hipMemcpy(d_res.p + 16, v2, 16, hipMemcpyHostToDevice));
+    if (allreduce(d_res.p + 16, 2, 0, true, "step statistics after a failed factorisation")) return MCP_ERR_RUNTIME;
+    HIPCK(hipMemcpy(v2, d_res.p + 16, 16, hipMemcpyDeviceToHost)); sl = v2[0]; sq = v2[1];
+  }
+  scale += sl; ss += sq;
+  // g2o goes on with update(_solver->x()) -- the solver's x is what the last successful solve left -- and computeActiveErrors:
+  // the edges then hold the errors of (current state (+) stale x), which is what the residual action reads if this was the
+  // iteration's last trial (OptimizationAlgorithmLevenberg::solve [3P-memory]; ChainBundle.cc:1096-1116).  Same here.
+  const TrialIo io{st, 0, sys_cur, last_tr, lambda, d_xp_good.p, bp(), nullptr, d_xp_cand.p, d_xl_good.p, d_part0.p, nullptr, nullptr,
+                   d_res.p + 6, 6, d_res.p, nullptr, nullptr, 0, 0ull, false, false, true};
+  if (launch_trial_step(io)) return MCP_ERR_RUNTIME;
+  if (allreduce(d_res.p, 1, 0, false, "chi2 of the stale step after a failed factorisation")) return MCP_ERR_RUNTIME;
+  if (read_results(1)) return MCP_ERR_RUNTIME;
+  I.trial_chi_raw = h_res[0];
+  sel_src = -1;
+  return 0;
+}
+// the gain ratio of the trial and the LM schedule's answer to it: accept (the trial state becomes current) or raise lambda
+void mcp_ba::schedule(LmRun& R, LmIter& I, bool ok2, double scale, double ss) {
+  I.ss_last = ss;
+  I.rho = I.currentChi - I.tempChi;
+  scale += 1e-3;
+  I.rho /= scale;
+  if (I.rho > 0 && std::isfinite(I.tempChi)) {
+    double alpha = 1. - std::pow((2*I.rho - 1), 3);
+    alpha = std::min(alpha, 2./3.);
+    const double sf = std::max(1./3., alpha);
+    lambda *= sf; R.ni = 2; I.currentChi = I.tempChi; I.accepted = 1;
+    cur = last_tr;                             // discardTop: the trial state becomes current
+    acc_head_q = ok2 ? sys_cur : -1;           // (its head, if one was enqueued behind it, is for exactly this state)
+    // ... and the digit histograms that rode on its all-reduce describe the new chi2 array -- unless the factorisation had failed:
+    // then the accepted state is the STALE step's (negative scale), whose chi2 never rode on anything
+    sel_src = (multi() && ok2) ? sys_cur : -1;
+  } else {
+    lambda *= R.ni; R.ni *= 2; I.accepted = 0;       // pop: the current buffers were never touched
+    spec_hot = 4;                              // (small bundles: from here on the rejection branch's systems are solved ahead again)
+  }
+  ++I.qmax;
+}
+// post-iteration actions: the convergence tests on the update and on the residual, the iteration's log entry
+void mcp_ba::post_iteration(LmRun& R, LmIter& I) {
+  if (!I.trace_line.empty()) fprintf(stderr, "[mcp_ba trials] it %d: results at (us; m = solved for this trial, a = evaluated ahead, s = system of the batch, trial run now)%s\n", I.it, I.trace_line.c_str());
+  const double rms = std::sqrt(I.ss_last/(double)nx_total());
+  if (rms < prm.update_rms_limit && !prm.disable_convergence) { R.conv_mag = 1; if (R.abort_flag) *R.abort_flag = 1; }
+  // activeRobustChi2 of whatever errors the edges hold: the last trial's (or, when verbose, the
+  // recomputed errors of the current state)
+  // (an accepted trial's errors ARE the edges' errors; only after a failed factorisation whose stale step was accepted --
+  // negative scale -- does that differ from the schedule's currentChi, which is DBL_MAX then)
+  const double curchi = I.accepted ? I.trial_chi_raw : (verbose ? I.currentChi : I.trial_chi_raw);
+  const double pct = (last_chi2_action - curchi)/last_chi2_action;
+  if (!prm.disable_convergence) {
+    if (pct >= 0 && pct <= prm.update_percent_limit) { R.conv_res = 1; if (R.abort_flag) *R.abort_flag = 1; }
+    else if (curchi == 0) { R.conv_res = 1; if (R.abort_flag) *R.abort_flag = 1; }
+  }
+  last_chi2_action = curchi;
+  I.lg.chi2_end = curchi;
+  if (I.qmax == 1 && spec_hot > 0) --spec_hot;     // (an iteration that accepted its first trial)
+  total_iterations += I.qmax;
+  I.lg.lambda_end = lambda; I.lg.trials = I.qmax; I.lg.accepted = I.accepted; I.lg.rms_update = rms;
+  logs.push_back(I.lg);
+  if (I.it == 0) R.t_first_end = std::chrono::steady_clock::now();
+}
+// MCP_BA_EVT=1: what the solve's scheduling did, the device-side profiles of the head kernels (if compiled in), the time stamps
+void mcp_ba::dump_profiles() {
   if (evt_debug) { fprintf(stderr, "[evt] iteration heads enqueued ahead and used: %d (median prediction missed: %d)\n", dbg_head_ahead, dbg_head_miss); dbg_head_ahead = 0; dbg_head_miss = 0; }
 #ifdef MCP_HL_PROF
   if (evt_debug) {
@@ -3426,13 +3496,21 @@ int mcp_ba::compute(volatile unsigned char* abort_flag, int n_iter, double user_
 #endif
   if (evt_debug) { fprintf(stderr, "[evt] trials evaluated ahead and used: %d; host wait on mailbox: own trials %.0f us, ahead trials %.0f us\n", dbg_pre, dbg_wait_us[0], dbg_wait_us[1]); dbg_pre = 0; dbg_wait_us[0] = dbg_wait_us[1] = 0; }
   evt_flush();
+}
+// the final statistics, the return code (as g2o optimize(): iterations run, -1 for none unless aborted from outside), the state
+// back on the host, and what the launches and the stage events of this solve reported
+int mcp_ba::end_solve(LmRun& R, int nCounter) {
+  static const bool trace_compute = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
+  if (join_spec()) return MCP_ERR_RUNTIME;
+  if (join_sum()) return MCP_ERR_RUNTIME;
+  dump_profiles();
   int rc = final_stats(nCounter);
   const auto t_stats_end = std::chrono::steady_clock::now();
   if (rc == MCP_ERR_RUNTIME) return rc;
-  converged = (conv_mag || conv_res);
-  bool external_abort = terminate() && !converged;
+  converged = (R.conv_mag || R.conv_res);
+  const bool external_abort = R.terminate() && !converged;
   if (nCounter == 0 && !external_abort) rc = -1;
-  else if (nCounter == 0 && terminate()) rc = 0;
+  else if (nCounter == 0 && R.terminate()) rc = 0;
   else rc = nCounter;
   if (download_state()) return MCP_ERR_RUNTIME;
   // A launch the runtime refused (a configuration a kernel cannot run with) leaves no trace in the stream: the state simply stays
@@ -3450,19 +3528,47 @@ int mcp_ba::compute(volatile unsigned char* abort_flag, int n_iter, double user_
     timing.eval_ms = acc[ST_EVAL]; timing.select_ms = acc[ST_SELECT]; timing.linearize_ms = acc[ST_LIN];
     timing.schur_ms = acc[ST_SCHUR]; timing.cholesky_ms = acc[ST_CHOL]; timing.solve_ms = acc[ST_SOLVE]; timing.update_ms = acc[ST_UPDATE];
   }
-  timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  timing.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R.t_begin).count();
   if (trace_compute) {
     auto ms = [&](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     fprintf(stderr, "[compute] %d iterations: to the end of the first %.3f ms, the others %.3f ms, final statistics + export %.3f ms, state and outliers on the host %.3f ms; total %.3f ms\n",
-            nCounter, ms(t_begin, t_first_end), ms(t_first_end, t_loop_end), ms(t_loop_end, t_stats_end), ms(t_stats_end, std::chrono::steady_clock::now()), timing.total_ms);
+            nCounter, ms(R.t_begin, R.t_first_end), ms(R.t_first_end, R.t_loop_end), ms(R.t_loop_end, t_stats_end), ms(t_stats_end, std::chrono::steady_clock::now()), timing.total_ms);
   }
   return rc;
 }
-
 // ChainBundle.cc:1339-1345 (final sigma^2), :1368-1399 (Tukey outliers), :1401-1448 (depth covariance)
 int mcp_ba::final_stats(int nCounter) {
   exported = false;
   if (m_total == 0 || dirty) { max_cov = 0; return 0; }
+  if (final_sigma_and_export(nCounter)) return -2;
+  if (robust) { sigma_sq = h_res[9]; sigma_sq_lim = h_res[10]; }
+  mean_chi2 = h_res[0]/m_total;
+  if (nCounter == 0) return 0;
+  if (tukey) outlier_list();
+  // depth covariance only when fewer than 3 free poses (:1419)
+  if (nfp < 3 && nCounter > 0) return depth_covariance();
+  max_cov = 0;                                                    // :1444-1448
+  return 0;
+}
+// RobustKernelData::RecomputeNow and activeRobustChi2 of the current state: the robust chi2 (summed over the ranks) to d_res[0], the
+// median to d_res[8], the sigma block to d_res[9..12]
+int mcp_ba::robust_chi2_block(bool median, const char* what) {
+  if (median && median_sigma(cur)) return -1;
+  if (robust_total(st, cur, sig(), d_part0.p, d_res.p, 0)) return -1;
+  if (allreduce(d_res.p, 1, 0, false, what)) return -1;
+  HIPCK(hipMemcpyAsync(d_res.p + 9, sig(), 4*sizeof(double), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+// the debug entry points' way to a state whose chains, chi2 and sigma block (and linearisation) are current
+int mcp_ba::state_ready(bool linearise) {
+  launch_chains(cur);
+  launch_eval(cur, false, nullptr);
+  if (robust && median_sigma(cur)) return -1;
+  if (linearise && linearize()) return -1;
+  return 0;
+}
+// final sigma^2, median and robust chi2 -> h_res[0], [9..12]; the Tukey flags and the state exported to pinned memory
+int mcp_ba::final_sigma_and_export(int nCounter) {
   // Behind the kernels that leave the median in the result block, and BEFORE the one wait for that block: the Tukey flags (threshold from the
   // median on the device) and the state, both written to pinned host memory by kernels -- one wait at the end of a solve instead of three,
   // no copy into pageable memory.
@@ -3495,12 +3601,7 @@ int mcp_ba::final_stats(int nCounter) {
   } else {
   const auto tf0 = std::chrono::steady_clock::now();
   if (use_head_large()) { if (head_large(cur, 0, d_res.p + 9)) return -2; }      // (the sigma block lands in d_res[9..12] too: no copy behind it)
-  else {
-  if (median_sigma(cur)) return -2;
-  if (robust_total(st, cur, sig(), d_part0.p, d_res.p, 0)) return -2;
-  if (allreduce(d_res.p, 1, 0, false, "final robust chi2")) return -2;
-  HIPCK(hipMemcpyAsync(d_res.p + 9, sig(), 4*sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
+  else if (robust_chi2_block(true, "final robust chi2")) return -2;
   if (enqueue_export(12)) return -2;
   const auto tf1 = std::chrono::steady_clock::now();
   if (read_results(13)) return -2;
@@ -3509,105 +3610,99 @@ int mcp_ba::final_stats(int nCounter) {
   { static const bool tr = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
     if (tr) fprintf(stderr, "[final] median + sums + export enqueued in %.3f ms, waited for %.3f ms\n", std::chrono::duration<double, std::milli>(tf1 - tf0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf1).count()); }
   }
-  if (robust) { sigma_sq = h_res[9]; sigma_sq_lim = h_res[10]; }
-  mean_chi2 = h_res[0]/m_total;
-  const double median = h_res[12];
-  if (nCounter == 0) return 0;
-  if (tukey) {
-    double s = 1.4826*(1 + 5.0/mest_denom(m_total))*std::sqrt(median);     // Tukey::FindSigmaSquared, MEstimator.h:109-124
-    s = 4.6851*s;
-    double s2 = s*s;
-    const double mins = prm.min_mestimator_sigma*prm.min_mestimator_sigma;
-    if (s2 < mins) s2 = mins;
-    (void)s2;                                      // (the flags were taken on the device with this very threshold: k_tukey_flags_dev, above)
-    // The flags arrive as one bit per measurement in the structure's order.  Set bits only are visited: structure order -> add order
-    // through a bit map of the add indices (the list is in add order, as the reference's walk over its edges), then the three
-    // numbers of every outlier with the look-ups requested a few entries ahead -- each is a miss in a 16 MB array on a cold cache.
-    // (Round 6: byte flags walked one by one + the list built on demand misses took 2.3 ms of a 15 ms call at the metric size.)
-    const auto tq0 = std::chrono::steady_clock::now();
-    const unsigned long long* mk = reinterpret_cast<const unsigned long long*>(h_exp + exp_state);
-    const int nw = (P.nmeas + 63)/64;
-    std::vector<unsigned long long> addmask((meas.size() + 63)/64, 0ull);
-    size_t nout = 0;
-    for (int w = 0; w < nw; ++w) {
-      unsigned long long bts = mk[w];
-      while (bts) {
-        const int j = w*64 + __builtin_ctzll(bts); bts &= bts - 1;
-        const int a = perm[j];
-        if (a >= 0) { addmask[(size_t)a >> 6] |= 1ull << (a & 63); ++nout; }      // (perm < 0: a measurement this map does not have -- near miss; its chi2 is 0)
-      }
+  return 0;
+}
+// the Tukey outliers (ChainBundle.cc:1368-1399) from the flag bits of the export: k_tukey_flags_dev took them on the device with the
+// threshold of Tukey::FindSigmaSquared (MEstimator.h:109-124) at the final median
+void mcp_ba::outlier_list() {
+  const size_t exp_state = (poses.size()*12 + points.size()*3)*sizeof(double);
+  // The flags arrive as one bit per measurement in the structure's order.  Set bits only are visited: structure order -> add order
+  // through a bit map of the add indices (the list is in add order, as the reference's walk over its edges), then the three
+  // numbers of every outlier with the look-ups requested a few entries ahead -- each is a miss in a 16 MB array on a cold cache.
+  // (Round 6: byte flags walked one by one + the list built on demand misses took 2.3 ms of a 15 ms call at the metric size.)
+  const auto tq0 = std::chrono::steady_clock::now();
+  const unsigned long long* mk = reinterpret_cast<const unsigned long long*>(h_exp + exp_state);
+  const int nw = (P.nmeas + 63)/64;
+  std::vector<unsigned long long> addmask((meas.size() + 63)/64, 0ull);
+  size_t nout = 0;
+  for (int w = 0; w < nw; ++w) {
+    unsigned long long bts = mk[w];
+    while (bts) {
+      const int j = w*64 + __builtin_ctzll(bts); bts &= bts - 1;
+      const int a = perm[j];
+      if (a >= 0) { addmask[(size_t)a >> 6] |= 1ull << (a & 63); ++nout; }      // (perm < 0: a measurement this map does not have -- near miss; its chi2 is 0)
     }
-    const auto tq1 = std::chrono::steady_clock::now();
-    std::vector<int> idx; idx.reserve(nout);
-    for (size_t w = 0; w < addmask.size(); ++w) {
-      unsigned long long bts = addmask[w];
-      while (bts) { idx.push_back((int)(w*64 + __builtin_ctzll(bts))); bts &= bts - 1; }
-    }
-    const auto tq2 = std::chrono::steady_clock::now();
-    outliers.resize(3*idx.size());
-    const size_t no = idx.size();
-    constexpr size_t AHEAD = 16;
-    for (size_t k = 0; k < std::min(no, AHEAD); ++k) __builtin_prefetch(&meas[idx[k]]);
-    for (size_t k = 0; k < std::min(no, AHEAD/2); ++k) __builtin_prefetch(&points[meas[idx[k]].point]);
-    for (size_t k = 0; k < no; ++k) {
-      if (k + AHEAD < no) __builtin_prefetch(&meas[idx[k + AHEAD]]);
-      if (k + AHEAD/2 < no) __builtin_prefetch(&points[meas[idx[k + AHEAD/2]].point]);
-      const HMeas& m = meas[idx[k]];
-      outliers[3*k] = points[m.point].id;
-      outliers[3*k + 1] = poses[chains[m.chain].v[0]].id;      // vertices().front(), :1394
-      outliers[3*k + 2] = m.cam;
-    }
-    { static const bool tr = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
-      auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-      if (tr) fprintf(stderr, "[final] outliers: set bits to add order %.3f ms, index list %.3f ms, %zu triples %.3f ms\n", ms(tq0, tq1), ms(tq1, tq2), no, ms(tq2, std::chrono::steady_clock::now())); }
   }
-  // depth covariance only when fewer than 3 free poses (:1419); Hessian of the last buildSystem, no lambda
-  if (nfp < 3 && nCounter > 0) {
-    // (several ranks: S is the all-reduced system, every rank inverts it, the point covariances are rank-local and their
-    // median is the global order statistic -- same collectives on every rank, nfp and nfl_total are global)
-    bool okm = true;
-    sys_cur = 0; spec_ok = false;
-    SysBatch sb; std::memset(&sb, 0, sizeof sb);
-    if (join_spec()) return -2;
-    HIPCK(hipMemsetAsync(d_fail.p, 0, 4*sizeof(int), st));
-    if (build_system(1, sb)) return -2;
-    const size_t n2 = (size_t)np*np;
-    hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st, 0, (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)nullptr, d_res.p, 0, (const int*)d_fail.p);
-    if (allreduce(d_res.p + 3, 1, 0, false, "covariance: failure flag")) return -2;
-    std::vector<double> Sh(n2 + 1), Sinv(n2 + 1, 0.0);
-    if (np) HIPCK(hipMemcpyAsync(Sh.data(), S(), n2*8, hipMemcpyDeviceToHost, st));
-    HIPCK(hipMemcpyAsync(h_res + 3, d_res.p + 3, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCK(hipStreamSynchronize(st));
-    if (h_res[3] != 0.0) okm = false;
-    if (okm && np) {
-      // <= 12x12 control-plane inverse on the host (lower triangle of S is valid)
-      std::vector<double> L(n2, 0.0);
-      for (int i = 0; i < np && okm; ++i) for (int j = 0; j <= i; ++j) {
-        double sacc = Sh[(size_t)i*np + j];
-        for (int k = 0; k < j; ++k) sacc -= L[(size_t)i*np + k]*L[(size_t)j*np + k];
-        if (i == j) { if (!(sacc > 0)) { okm = false; break; } L[(size_t)i*np + j] = std::sqrt(sacc); }
-        else L[(size_t)i*np + j] = sacc/L[(size_t)j*np + j];
-      }
-      for (int c = 0; c < np && okm; ++c) {
-        std::vector<double> e(np, 0.0); e[c] = 1;
-        for (int i = 0; i < np; ++i) { double sacc = e[i]; for (int k = 0; k < i; ++k) sacc -= L[(size_t)i*np + k]*e[k]; e[i] = sacc/L[(size_t)i*np + i]; }
-        for (int i = np - 1; i >= 0; --i) { double sacc = e[i]; for (int k = i + 1; k < np; ++k) sacc -= L[(size_t)k*np + i]*e[k]; e[i] = sacc/L[(size_t)i*np + i]; }
-        for (int i = 0; i < np; ++i) Sinv[(size_t)i*np + c] = e[i];
-      }
+  const auto tq1 = std::chrono::steady_clock::now();
+  std::vector<int> idx; idx.reserve(nout);
+  for (size_t w = 0; w < addmask.size(); ++w) {
+    unsigned long long bts = addmask[w];
+    while (bts) { idx.push_back((int)(w*64 + __builtin_ctzll(bts))); bts &= bts - 1; }
+  }
+  const auto tq2 = std::chrono::steady_clock::now();
+  outliers.resize(3*idx.size());
+  const size_t no = idx.size();
+  constexpr size_t AHEAD = 16;
+  for (size_t k = 0; k < std::min(no, AHEAD); ++k) __builtin_prefetch(&meas[idx[k]]);
+  for (size_t k = 0; k < std::min(no, AHEAD/2); ++k) __builtin_prefetch(&points[meas[idx[k]].point]);
+  for (size_t k = 0; k < no; ++k) {
+    if (k + AHEAD < no) __builtin_prefetch(&meas[idx[k + AHEAD]]);
+    if (k + AHEAD/2 < no) __builtin_prefetch(&points[meas[idx[k + AHEAD/2]].point]);
+    const HMeas& m = meas[idx[k]];
+    outliers[3*k] = points[m.point].id;
+    outliers[3*k + 1] = poses[chains[m.chain].v[0]].id;      // vertices().front(), :1394
+    outliers[3*k + 2] = m.cam;
+  }
+  { static const bool tr = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (tr) fprintf(stderr, "[final] outliers: set bits to add order %.3f ms, index list %.3f ms, %zu triples %.3f ms\n", ms(tq0, tq1), ms(tq1, tq2), no, ms(tq2, std::chrono::steady_clock::now())); }
+}
+// the depth covariance (ChainBundle.cc:1401-1448): Hessian of the last buildSystem, no lambda
+int mcp_ba::depth_covariance() {
+  // (several ranks: S is the all-reduced system, every rank inverts it, the point covariances are rank-local and their
+  // median is the global order statistic -- same collectives on every rank, nfp and nfl_total are global)
+  bool okm = true;
+  sys_cur = 0; spec_ok = false;
+  SysBatch sb; std::memset(&sb, 0, sizeof sb);
+  if (join_spec()) return -2;
+  HIPCK(hipMemsetAsync(d_fail.p, 0, 4*sizeof(int), st));
+  if (build_system(1, sb)) return -2;
+  const size_t n2 = (size_t)np*np;
+  hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, st, 0, (const double*)nullptr, 0, (const double*)nullptr, 0, (const double*)nullptr, d_res.p, 0, (const int*)d_fail.p);
+  if (allreduce(d_res.p + 3, 1, 0, false, "covariance: failure flag")) return -2;
+  std::vector<double> Sh(n2 + 1), Sinv(n2 + 1, 0.0);
+  if (np) HIPCK(hipMemcpyAsync(Sh.data(), S(), n2*8, hipMemcpyDeviceToHost, st));
+  HIPCK(hipMemcpyAsync(h_res + 3, d_res.p + 3, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  if (h_res[3] != 0.0) okm = false;
+  if (okm && np) {
+    // <= 12x12 control-plane inverse on the host (lower triangle of S is valid)
+    std::vector<double> L(n2, 0.0);
+    for (int i = 0; i < np && okm; ++i) for (int j = 0; j <= i; ++j) {
+      double sacc = Sh[(size_t)i*np + j];
+      for (int k = 0; k < j; ++k) sacc -= L[(size_t)i*np + k]*L[(size_t)j*np + k];
+      if (i == j) { if (!(sacc > 0)) { okm = false; break; } L[(size_t)i*np + j] = std::sqrt(sacc); }
+      else L[(size_t)i*np + j] = sacc/L[(size_t)j*np + j];
     }
-    if (okm) {
-      if (nfl_total > 0) {
-        DevBuf<double> dSinv;
-        std::vector<double> tmp(Sinv.begin(), Sinv.begin() + std::max<size_t>(n2, 1));
-        if (dSinv.upload(tmp, st)) return -2;
-        if (nfl) hipLaunchKernelGGL(k_point_cov22, dim3((nfl + 63)/64), dim3(64), 0, st, P, (const double*)d_Vinv.p, (const double*)d_W.p, (const double*)dSinv.p, d_cov.p);
-        if (select_kth(d_cov.p, nfl, (unsigned long long)(nfl_total/2), d_res.p + 8)) return -2;
-        HIPCK(hipMemcpyAsync(h_res, d_res.p + 8, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        max_cov = h_res[0];
-      } else max_cov = DBL_MAX;                                   // :1441
-    } else max_cov = 0;                                           // :1447
-  } else max_cov = 0;                                             // :1444-1448
+    for (int c = 0; c < np && okm; ++c) {
+      std::vector<double> e(np, 0.0); e[c] = 1;
+      for (int i = 0; i < np; ++i) { double sacc = e[i]; for (int k = 0; k < i; ++k) sacc -= L[(size_t)i*np + k]*e[k]; e[i] = sacc/L[(size_t)i*np + i]; }
+      for (int i = np - 1; i >= 0; --i) { double sacc = e[i]; for (int k = i + 1; k < np; ++k) sacc -= L[(size_t)k*np + i]*e[k]; e[i] = sacc/L[(size_t)i*np + i]; }
+      for (int i = 0; i < np; ++i) Sinv[(size_t)i*np + c] = e[i];
+    }
+  }
+  if (okm) {
+    if (nfl_total > 0) {
+      DevBuf<double> dSinv;
+      std::vector<double> tmp(Sinv.begin(), Sinv.begin() + std::max<size_t>(n2, 1));
+      if (dSinv.upload(tmp, st)) return -2;
+      if (nfl) hipLaunchKernelGGL(k_point_cov22, dim3((nfl + 63)/64), dim3(64), 0, st, P, (const double*)d_Vinv.p, (const double*)d_W.p, (const double*)dSinv.p, d_cov.p);
+      if (select_kth(d_cov.p, nfl, (unsigned long long)(nfl_total/2), d_res.p + 8)) return -2;
+      HIPCK(hipMemcpyAsync(h_res, d_res.p + 8, sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCK(hipStreamSynchronize(st));
+      max_cov = h_res[0];
+    } else max_cov = DBL_MAX;                                   // :1441
+  } else max_cov = 0;                                           // :1447
   return 0;
 }
 
@@ -3652,15 +3747,15 @@ mcp_ba* mcp_ba_create(const mcp_camera* cams, int ncam, int use_robust, int use_
   { const char* e = getenv("MCP_BA_SMALL"); if (e) h->small_on = atoi(e); }
   { const char* e = getenv("MCP_BA_SELECT_RIDE"); if (e) h->sel_ride = atoi(e); }
   { const char* e = getenv("MCP_BA_TIMEOUT_MS"); if (e && atof(e) > 0) h->timeout_ms = atof(e); }
-  for (int q = 0; q < mcp::MAX_SYS; ++q) if (hipEventCreateWithFlags(&h->ev_tr[q], hipEventDisableTiming) != hipSuccess ||
-                                              hipEventCreateWithFlags(&h->ev_wf[q], hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); delete h; return nullptr; }
+  for (int q = 0; q < mcp::MAX_SYS; ++q) if (hipEventCreateWithFlags(&h->lane[q].ev_tr, hipEventDisableTiming) != hipSuccess ||
+                                              hipEventCreateWithFlags(&h->lane[q].ev_wf, hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); delete h; return nullptr; }
   // (the runtime multiplexes streams onto a handful of hardware queues -- GPU_MAX_HW_QUEUES, 4 by default: main, speculative and two
   // trial streams use them up; a third stream for MCP_BA_OVERLAP=2 is only created when asked for)
   if (h->pooled) {
-    if (h->spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) h->st_tr[q] = pool->tr[q];
+    if (h->spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) h->lane[q].st_tr = pool->tr[q];
     if (h->overlap_spec) { h->st2 = pool->spec; if (h->overlap_spec >= 2) h->st3 = pool->spec3; }
   } else {
-    if (h->spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) if (hipStreamCreateWithFlags(&h->st_tr[q], hipStreamNonBlocking) != hipSuccess) { set_err("hipStreamCreate failed"); delete h; return nullptr; }
+    if (h->spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) if (hipStreamCreateWithFlags(&h->lane[q].st_tr, hipStreamNonBlocking) != hipSuccess) { set_err("hipStreamCreate failed"); delete h; return nullptr; }
     if (h->overlap_spec && (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess || (h->overlap_spec >= 2 && hipStreamCreateWithFlags(&h->st3, hipStreamNonBlocking) != hipSuccess))) { set_err("second stream could not be created"); delete h; return nullptr; }
   }
   if (h->large_head_ahead) {
@@ -3668,7 +3763,7 @@ mcp_ba* mcp_ba_create(const mcp_camera* cams, int ncam, int use_robust, int use_
     if (h->pooled && pool->spec3 && pool->spec3 != h->st3) h->st_h = pool->spec3;
     else if (hipStreamCreateWithFlags(&h->st_h, hipStreamNonBlocking) == hipSuccess) h->st_h_own = true;
     else { (void)hipGetLastError(); h->st_h = nullptr; }
-    for (int q = 0; q < mcp::MAX_SYS; ++q) if (hipEventCreateWithFlags(&h->head_ev[q], hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); delete h; return nullptr; }
+    for (int q = 0; q < mcp::MAX_SYS; ++q) if (hipEventCreateWithFlags(&h->lane[q].head_ev, hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); delete h; return nullptr; }
   }
   if (h->overlap_spec && (
                           hipEventCreateWithFlags(&h->ev_spec3, hipEventDisableTiming) != hipSuccess ||
@@ -3899,12 +3994,8 @@ int mcp_ba_robust_chi2(mcp_ba* h, double* sigma_sq_raw, double* chi2_sum) {
   if (h->dirty && h->prepare()) return -1;
   const int n = h->P.nmeas;
   if (n == 0) return -1;
-  h->launch_chains(h->cur);
-  h->launch_eval(h->cur, false, nullptr);
-  if (h->robust && h->median_sigma(h->cur)) return -1;
-  if (h->robust_total(h->st, h->cur, h->sig(), h->d_part0.p, h->d_res.p, 0)) return -1;
-  if (h->allreduce(h->d_res.p, 1, 0, false, "robust chi2")) return -1;
-  HIPCK(hipMemcpyAsync(h->d_res.p + 9, h->sig(), 4*sizeof(double), hipMemcpyDeviceToDevice, h->st));
+  if (h->state_ready(false)) return -1;
+  if (h->robust_chi2_block(false, "robust chi2")) return -1;
   if (h->read_results(13)) return -1;
   if (sigma_sq_raw) *sigma_sq_raw = h->h_res[9];
   if (chi2_sum) *chi2_sum = h->h_res[0];
@@ -3913,10 +4004,7 @@ int mcp_ba_robust_chi2(mcp_ba* h, double* sigma_sq_raw, double* chi2_sum) {
 int mcp_ba_debug_solve(mcp_ba* h, double lambda, double* x_out) {
   if (h->dirty && h->prepare()) return -1;
   if (h->P.nmeas == 0 || h->nx == 0) { set_err("mcp_ba_debug_solve: empty problem"); return -1; }
-  h->launch_chains(h->cur);
-  h->launch_eval(h->cur, false, nullptr);
-  if (h->robust && h->median_sigma(h->cur)) return -1;
-  if (h->linearize()) return -1;
+  if (h->state_ready(true)) return -1;
   bool ok2 = true;
   if (h->solve_trial(lambda, ok2)) return -1;
   if (!ok2) { set_err("mcp_ba_debug_solve: system not positive definite"); return -1; }
@@ -3933,10 +4021,7 @@ int mcp_ba_debug_systems(mcp_ba* h, int nsys, const double* lambdas, double* out
     char msg[160]; snprintf(msg, sizeof msg, "mcp_ba_debug_systems: a batch of %d systems asked for, the handle has buffers for 1 to %d", nsys, h->batch_capacity());
     set_err(msg); return -1;
   }
-  h->launch_chains(h->cur);
-  h->launch_eval(h->cur, false, nullptr);
-  if (h->robust && h->median_sigma(h->cur)) return -1;
-  if (h->linearize()) return -1;
+  if (h->state_ready(true)) return -1;
   h->sys_cur = 0; h->spec_ok = false; h->fail_clean = false;
   SysBatch sb; std::memset(&sb, 0, sizeof sb);
   for (int q = 0; q < nsys; ++q) { sb.lambda[q] = lambdas[q]; sb.lambda_init[q] = (h->rank == 0) ? lambdas[q] : 0.0; }
@@ -4043,7 +4128,7 @@ int mcp_ba_debug_head(mcp_ba* h, int route, const double* chi2, int n, double pr
     if (h->multi_trial_tail(st, 0, 0, w, 0, h->d_part0.p, 0, nullptr, nullptr, h->d_res.p + 6, 6, false, h->h_mail_dev, MAIL_TICKET, ticket)) return -1;
     if (h->wait_mail(0, ticket, MAIL_TICKET)) return -1;
     h->take_trial_flags(0);
-    r.pred_ok = h->tr_pred_ok[0]; r.overflow = h->tr_ovf[0];
+    r.pred_ok = h->lane[0].pred_ok; r.overflow = h->lane[0].ovf;
     h->sel_src = 0;                    // ... and that trial was accepted
     if (h->median_sigma(w)) return -1;
     sigp = h->sig();
@@ -4062,7 +4147,7 @@ int mcp_ba_debug_head(mcp_ba* h, int route, const double* chi2, int n, double pr
     HIPCK(hipStreamSynchronize(st));
     if (h->enqueue_head(st, q, w, false)) return -1;
     const int hs = h->wait_head(q);
-    h->head_enq[q] = false; h->head_state[q] = -1;
+    h->lane[q].head_enq = false; h->lane[q].head_state = -1;
     if (hs < 0) return -1;
     r.head_status = hs;
     HIPCK(hipMemcpyAsync(r.route_sigma, slot, 4*sizeof(double), hipMemcpyDeviceToHost, st));

@@ -988,6 +988,49 @@ def test_scheduling_knobs_do_not_change_a_single_bit(gpu_required, env, monkeypa
     assert base["outliers"] == alt["outliers"] and base["sigma_sq"] == alt["sigma_sq"] and base["lam"] == alt["lam"]
 
 
+_GENERAL_MAPS = {"tiny120": (lambda synth: synth.make_config("tiny", n_points=120), 12), "ring": (lambda synth: synth.make_config("ring"), 10)}
+_general_base = {}
+
+
+def _general_sequence_base(name):
+    """The map and its default-knob run through the general launch sequence (MCP_BA_SMALL=0 is set by the caller), computed once."""
+    if name not in _general_base:
+        from mcptam_amd import synth
+        make, iters = _GENERAL_MAPS[name]
+        p = make(synth)
+        g = _gpu(p.cams, disable_convergence=True)
+        _general_base[name] = (p, iters, run_bundle(g, p, iters), g.Timing())
+    return _general_base[name]
+
+
+@pytest.mark.parametrize("env", [dict(MCP_BA_OVERLAP="1"), dict(MCP_BA_OVERLAP="1", MCP_BA_SPEC_TRIALS="1"), dict(MCP_BA_OVERLAP="1", MCP_BA_SPEC_TRIALS="0"),
+                                 dict(MCP_BA_OVERLAP="2", MCP_BA_MAIN_SYS="2"), dict(MCP_BA_OVERLAP="1", MCP_BA_TRIAL_FUSE="0"), dict(MCP_BA_TRIAL_FUSE="0"),
+                                 dict(MCP_BA_MAILBOX="0"), dict(MCP_BA_SPECULATE="0"), dict(MCP_BA_GRAPH="1"), dict(MCP_BA_OVERLAP="1", MCP_BA_HEAD_AHEAD="1"),
+                                 dict(MCP_BA_HEAD_LARGE="1"), dict(MCP_BA_FORCE_MULTI="1"), dict(MCP_BA_FORCE_MULTI="1", MCP_BA_OVERLAP="1")],
+                         ids=lambda e: ",".join("%s=%s" % (k[7:], v) for k, v in e.items()))
+@pytest.mark.parametrize("name", ["tiny120", "ring"])
+def test_general_launch_sequence_on_small_maps_does_not_change_a_single_bit(gpu_required, name, env, monkeypatch):
+    """The knob test above runs on the metric map, which by default never splits a batch over two streams.  Here the general
+    (non-small: MCP_BA_SMALL=0) sequence of launches runs on two small maps whose iterations reject trials -- a robust bundle of 480
+    measurements and a ring of 24 000 with a several-chain plan -- under the knobs, alone and in the pairs that reach a branch of
+    their own: the split batch with every trial ahead, one, or none; two systems on the main stream; the step in three launches; no
+    mailbox; no speculation; graph replay; the per-trial and the one-launch iteration head; the multi-rank machine over one rank
+    (identity hook) with and without the split.  Scheduling only: everything a run returns equals the default run's, bit for bit."""
+    monkeypatch.setenv("MCP_BA_SMALL", "0")
+    p, iters, base, base_tm = _general_sequence_base(name)
+    assert max(l["trials"] for l in base["logs"]) >= 3 and base_tm["n_spec_hits"] > 0, "the run must reject trials and consume speculative systems for this to mean anything"
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    g = _gpu(p.cams, disable_convergence=True)
+    if "MCP_BA_FORCE_MULTI" in env:
+        g.SetAllReduce(lambda ptr, count, stream: None, 0, 1)
+    alt = run_bundle(g, p, iters)
+    assert base["rc"] == alt["rc"]
+    assert base["logs"] == alt["logs"]
+    assert np.array_equal(base["R"], alt["R"]) and np.array_equal(base["t"], alt["t"]) and np.array_equal(base["X"], alt["X"])
+    assert base["outliers"] == alt["outliers"] and base["sigma_sq"] == alt["sigma_sq"] and base["lam"] == alt["lam"]
+
+
 @pytest.mark.parametrize("cfg,iters", [("c2", 6), ("metric", 6)])
 def test_pipelined_linearisation_agrees_with_the_plain_loop(gpu_required, cfg, iters, monkeypatch):
     """k_linearize_pipe issues every load of a measurement at the head of its round and lets the W block of the round before leave
