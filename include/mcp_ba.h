@@ -313,6 +313,35 @@ typedef struct mcp_ba_head_report {
 } mcp_ba_head_report;
 int mcp_ba_debug_head(mcp_ba*, int route, const double* chi2, int n, double prev_median, mcp_ba_head_report* out);
 
+/* The step of ONE LM trial at damping `lambda` from the current state, on the main stream (test hook; prepares the handle if it is not
+ * prepared, then brings chains, chi2, sigma block and linearisation of the current state up to date).  The step goes through the
+ * member functions the solver calls for it: the description of a trial as the main stream's trial fills it in, then launch_trial_step.
+ *   x == NULL   the solver's own step: system 0 is built and solved as a trial of Compute() does it, then pose update, point
+ *               back-substitution, chain transforms, residuals and the final sums (one launch or the separate kernels: report.ncb);
+ *   x != NULL   a given step of mcp_ba_prepare() doubles (free poses in id order, 6 each, then free points, 3 each), applied the way
+ *               the step after a failed factorisation is applied: pose update, point step as it is, chain transforms, residuals.  No
+ *               step statistics then (the six sums of the report are 0).
+ * n_poses, n_points, n_meas: the counts the caller sized poses_out, points_out and chi2_out for; other counts than the handle's are
+ * refused with a message before anything runs.
+ * Outputs (each may be NULL): x_out, the step that was applied as the kernels kept it (same layout as x); poses_out, the trial poses
+ * of ALL poses in add order, 12 doubles each (R row-major, then t); points_out, the trial points of ALL points in add order; chi2_out,
+ * the trial chi2 per measurement in ADD order (as mcp_ba_eval).  Before the step, everything it is to write (the candidate state's free
+ * poses and points, chain transforms and chi2, x, the partial sums) is filled with NaNs: what a kernel leaves out shows as NaN, not as
+ * whatever an earlier handle left in the block.  The handle's current state is not touched and nothing is accepted: a
+ * Compute() afterwards gives what it gives on a fresh handle.  A handle with several ranks is refused with a message. */
+typedef struct mcp_ba_trial_report {
+  double robust_chi2;                     /* the result block's robust chi2 sum of the trial state */
+  double scale_pose, scale_point, scale;  /* sum x (lambda x + b): pose part, point part, and the total the LM schedule takes */
+  double ss_pose, ss_point, ss;           /* sum x^2, likewise */
+  int ncb;                                /* chain workgroups of the one-launch step, 0 = the separate kernels */
+  int nbb;                                /* workgroups of the point back-substitution (its partial sums) */
+  int nchain, npose, npoint, nfl, np, nmeas;
+  int small_mode;                         /* the map runs as a small bundle (ba_small.h) */
+  int given_step;                         /* x != NULL */
+} mcp_ba_trial_report;
+int mcp_ba_debug_trial(mcp_ba*, double lambda, const double* x, int n_poses, int n_points, int n_meas, double* x_out,
+                       double* poses_out, double* points_out, double* chi2_out, mcp_ba_trial_report* out);
+
 #ifdef __cplusplus
 }
 #endif

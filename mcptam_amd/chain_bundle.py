@@ -61,6 +61,11 @@ class McpBaHeadReport(ctypes.Structure):
                 ("select_overflow", ctypes.c_int), ("n_median_fast", ctypes.c_int), ("declined", ctypes.c_int)]
 
 
+class McpBaTrialReport(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_double) for f in ("robust_chi2", "scale_pose", "scale_point", "scale", "ss_pose", "ss_point", "ss")] + \
+               [(f, ctypes.c_int) for f in ("ncb", "nbb", "nchain", "npose", "npoint", "nfl", "np", "nmeas", "small_mode", "given_step")]
+
+
 HEAD_ROUTES = ("plain", "ranks", "ride", "small", "ahead", "large")      # MCP_BA_HEAD_* of include/mcp_ba.h
 LIN_KERNEL_NAMES = ("none", "quad", "pipe", "group")          # MCP_BA_LIN_* of include/mcp_ba.h
 SCHUR_KERNEL_NAMES = ("none", "schur4", "schur_group")        # MCP_BA_SCHUR_*
@@ -75,7 +80,7 @@ BA_SYMBOLS = [
     "mcp_ba_num_outliers", "mcp_ba_get_outliers", "mcp_ba_sigma_squared", "mcp_ba_mean_chi_squared", "mcp_ba_max_cov",
     "mcp_ba_lambda", "mcp_ba_num_iter_logs", "mcp_ba_get_iter_logs", "mcp_ba_get_timing", "mcp_ba_set_allreduce",
     "mcp_ba_prepare", "mcp_ba_eval", "mcp_ba_robust_chi2", "mcp_ba_debug_solve", "mcp_dense_spd_solve",
-    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_ba_debug_head", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
+    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_ba_debug_head", "mcp_ba_debug_trial", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
     "mcp_ba_struct_cache_stats", "mcp_ba_struct_cache_near_hits", "mcp_ba_struct_cache_clear",
     "mcp_comm_unique_id", "mcp_comm_init", "mcp_comm_destroy", "mcp_ba_set_comm", "mcp_comm_allreduce", "mcp_comm_allreduce_lane",
 ]
@@ -125,6 +130,7 @@ def lib():
     L.mcp_ba_debug_systems.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p]
     L.mcp_ba_debug_structure.argtypes = [ctypes.c_void_p, ctypes.POINTER(McpBaStructure)]
     L.mcp_ba_debug_head.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER(McpBaHeadReport)]
+    L.mcp_ba_debug_trial.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p, c_double_p, ctypes.POINTER(McpBaTrialReport)]
     L.mcp_comm_unique_id.argtypes = [ctypes.c_void_p]
     L.mcp_comm_init.restype = ctypes.c_void_p
     L.mcp_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -291,6 +297,7 @@ class ChainBundle:
             raise RuntimeError("mcp_ba_create failed: " + last_error())
         self.abort = ctypes.c_ubyte(0)      # the caller's mbBundleAbortRequested
         self._hook = None
+        self._n_added = [0, 0, 0]            # poses, points, measurements added so far (sizes of DebugTrial's outputs)
         self.abi_seconds = 0.0               # time spent inside the library's Add* entries (what a native caller pays; the rest is Python)
         self.abi_read_seconds = 0.0          # ... and inside its Get* entries
 
@@ -310,17 +317,20 @@ class ChainBundle:
     def AddPose(self, R, t, fixed):
         R = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
         t = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        self._n_added[0] += 1
         return self._L.mcp_ba_add_pose(self._h, _dp(R), _dp(t), int(fixed))
 
     def AddPoint(self, x, chain, fixed):
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(3)
         c = np.ascontiguousarray(chain, dtype=np.int32)
+        self._n_added[1] += 1
         return self._check(self._L.mcp_ba_add_point(self._h, _dp(x), _ip(c), len(c), int(fixed)), "AddPoint")
 
     def AddMeas(self, chain, point_id, uv, sigma_sq, cam_index):
         c = np.ascontiguousarray(chain, dtype=np.int32)
         uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(2)
         self._check(self._L.mcp_ba_add_meas(self._h, _ip(c), len(c), int(point_id), _dp(uv), float(sigma_sq), int(cam_index)), "AddMeas")
+        self._n_added[2] += 1
 
     def AddPointBatch(self, x, chains, chain_len, fixed):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -333,6 +343,7 @@ class ChainBundle:
                                        fixed.ctypes.data_as(c_ubyte_p), _ip(ids))
         self.abi_seconds += time.perf_counter() - t0
         self._check(rc, "AddPointBatch")
+        self._n_added[1] += x.shape[0]
         return ids
 
     def AddMeasBatch(self, chains, chain_len, point_ids, uv, sigma_sq, cam_index):
@@ -347,6 +358,7 @@ class ChainBundle:
                                              _ip(point_ids), _dp(uv), _dp(sigma_sq), _ip(cam_index))
         self.abi_seconds += time.perf_counter() - t0
         self._check(rc, "AddMeasBatch")
+        self._n_added[2] += uv.shape[0]
 
     def DebugSystem(self, lam):
         """(S, rhs, J^T r) of the reduced pose system at the current state (test hook, mcp_ba_debug_system)."""
@@ -399,6 +411,33 @@ class ChainBundle:
         d = {f: getattr(rep, f) for f, _ in McpBaHeadReport._fields_}
         d["sigma"] = np.array(rep.sigma[:], dtype=np.float64)
         d["route_sigma"] = np.array(rep.route_sigma[:], dtype=np.float64)
+        return d
+
+    def DebugTrial(self, lam, x=None):
+        """The step of one LM trial at damping `lam` from the current state, through the member functions Compute() runs it with
+        (test hook, mcp_ba_debug_trial): the solver's own step, or the given step `x` (Prepare() doubles: free poses, then free
+        points) applied as the step after a failed factorisation is.  Nothing is accepted.  Returns a dict: `x` the step that was
+        applied, `poses` (npose, 12) the trial poses of all poses in add order (R row-major, then t), `points` (npoint, 3) the trial
+        points in add order, `chi2` per measurement in add order, the sums `robust_chi2`, `scale` / `scale_pose` / `scale_point`
+        (sum x (lam x + b)) and `ss` / `ss_pose` / `ss_point` (sum x^2), and the report `ncb` (chain workgroups of the one-launch
+        step, 0 = the separate kernels), `nbb`, `nchain`, `npose`, `npoint`, `nfl`, `np`, `nmeas`, `small_mode`, `given_step`."""
+        rep = McpBaTrialReport()
+        nx = self.Prepare()
+        xin = None
+        if x is not None:
+            xin = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            if len(xin) != nx:
+                raise ValueError("DebugTrial: the step has %d entries, the map %d unknowns" % (len(xin), nx))
+        n_pose, n_point, n_meas = self._n_added      # (the sizes of the outputs: what this object has added; the library checks them against its own)
+        xo, ps, pt, c2 = np.zeros(nx), np.zeros((n_pose, 12)), np.zeros((n_point, 3)), np.zeros(n_meas)
+        rc = self._L.mcp_ba_debug_trial(self._h, float(lam), None if xin is None else _dp(xin), n_pose, n_point, n_meas, _dp(xo), _dp(ps), _dp(pt), _dp(c2), ctypes.byref(rep))
+        if rc < 0:
+            raise RuntimeError("mcp_ba_debug_trial: " + last_error())
+        d = {f: getattr(rep, f) for f, _ in McpBaTrialReport._fields_}
+        d["small_mode"] = bool(d["small_mode"])
+        d["given_step"] = bool(d["given_step"])
+        assert [d["npose"], d["npoint"], d["nmeas"]] == [n_pose, n_point, n_meas], d
+        d.update(x=xo, poses=ps, points=pt, chi2=c2)
         return d
 
     def Compute(self, n_iter=None, user_lambda=-1.0):

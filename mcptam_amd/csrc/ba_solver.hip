@@ -700,6 +700,7 @@ struct mcp_ba {
     if (small_mode()) return 1;
     return trial_fuse ? std::max(1, (P.nchain + TA_CHAINS - 1)/TA_CHAINS) : 0;
   }
+  int backsub_blocks() const { return (nfl*BS_TPP + BS_BLOCK - 1)/BS_BLOCK; }      // workgroups of the point back-substitution: BS_TPP lanes per free point
   int join_spec(int q = -1) {
     if (spec_pending && (q < 0 || (q >= spec2_from && q < spec3_from))) { HIPCK(hipStreamWaitEvent(st, ev_spec, 0)); spec_pending = false; }
     if (spec3_pending && (q < 0 || q >= spec3_from)) { HIPCK(hipStreamWaitEvent(st, ev_spec3, 0)); spec3_pending = false; }
@@ -2766,7 +2767,7 @@ int mcp_ba::multi_trial_tail(hipStream_t s, int lane, int q, int slot, int nbe, 
 int mcp_ba::launch_trial_step(const TrialIo& io) {
   hipStream_t s = io.s;
   const int slot = io.slot;
-  const int nbb = (nfl*BS_TPP + BS_BLOCK - 1)/BS_BLOCK, nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
+  const int nbb = backsub_blocks(), nbe = (P.nmeas + EVAL_BLOCK - 1)/EVAL_BLOCK;
   const int ncb = io.stale ? 0 : trial_chain_blocks();
   if (io.main_block) tic(ST_UPDATE);
   if (ncb) { hipLaunchKernelGGL(k_trial_apply, dim3(ncb + (nfl ? nbb : 0)), dim3(256), (size_t)P.npose*12*sizeof(double), s, P, ncb, io.lam, io.rhs, io.bp, (const double*)d_pose[cur].p, d_pose[slot].p, io.pose_parts, io.xp,
@@ -4170,6 +4171,94 @@ int mcp_ba_debug_head(mcp_ba* h, int route, const double* chi2, int n, double pr
   r.robust_chi2 = own_off >= 0 ? own : r.robust_chi2_plain;
   if (route == MCP_BA_HEAD_LARGE) { unsigned long long b; std::memcpy(&b, &own, 8); if (b == HL_FAILED_BITS) { set_err("mcp_ba_debug_head: the head (k_head_large) gave up at a barrier"); return -1; } }
   if (!h->launch_err.empty()) { set_err("mcp_ba_debug_head: launch refused: " + h->launch_err); h->launch_err.clear(); return -1; }
+  *out = r;
+  return 0;
+}
+
+// the step of one trial from the current state (test hook): see mcp_ba.h.  The solver's own step is solve_trial() with no speculative
+// systems (enqueue_main_trial -> launch_trial_step); a given step is the description stale_step() fills in, with buffers of this call
+// in place of the last good solve's, so that nothing the handle keeps is written.
+int mcp_ba_debug_trial(mcp_ba* h, double lambda, const double* x, int n_poses, int n_points, int n_meas, double* x_out,
+                       double* poses_out, double* points_out, double* chi2_out, mcp_ba_trial_report* out) {
+  if (!out) { set_err("mcp_ba_debug_trial: no report block"); return -1; }
+  if (h->dirty && h->prepare()) return -1;
+  HIPCK(hipSetDevice(h->device));
+  if (h->multi()) { set_err("mcp_ba_debug_trial: refused: an all-reduce hook or communicator is installed (the hook runs one rank's trial on the main stream)"); return -1; }
+  if (h->P.nmeas == 0 || h->nx == 0) { set_err("mcp_ba_debug_trial: empty problem"); return -1; }
+  if (n_poses != (int)h->poses.size() || n_points != (int)h->points.size() || n_meas != (int)h->meas.size()) {
+    char msg[224]; snprintf(msg, sizeof msg, "mcp_ba_debug_trial: outputs sized for %d poses, %d points, %d measurements, the handle has %d, %d, %d",
+                            n_poses, n_points, n_meas, (int)h->poses.size(), (int)h->points.size(), (int)h->meas.size());
+    set_err(msg); return -1;
+  }
+  hipStream_t st = h->st;
+  const int np = h->np, nfl = h->nfl;
+  if (h->cancel_spec_trials() || h->join_spec() || h->join_sum()) return -1;
+  h->head_ahead_want = false; h->head_ahead_for = -1;      // (no head of a next iteration rides behind this trial)
+  if (h->state_ready(true)) return -1;
+  mcp_ba_trial_report r; std::memset(&r, 0, sizeof r);
+  r.ncb = x ? 0 : h->trial_chain_blocks(); r.nbb = nfl ? h->backsub_blocks() : 0;
+  r.nchain = h->P.nchain; r.npose = h->P.npose; r.npoint = h->P.npoint; r.nfl = nfl; r.np = np; r.nmeas = (int)h->meas.size();
+  r.small_mode = h->small_mode() ? 1 : 0; r.given_step = x ? 1 : 0;
+  // What the step is to write is filled with NaNs first (all bits set), so that an entry a kernel leaves out cannot pass for written --
+  // the blocks of a handle come from a process-wide cache and may hold the results of the handle before: the candidate state's chain
+  // transforms and chi2, its FREE poses and points (the fixed ones stay: every candidate state holds them), x as the kernels keep
+  // it, and the partial sums.  A trial of Compute() rewrites all of it before it reads any of it.
+  {
+    const int s0 = h->cand(0);
+    auto nans = [&](double* p, size_t n) { return (p && n) ? hipMemsetAsync(p, 0xFF, n*sizeof(double), st) : hipSuccess; };
+    HIPCK(nans(h->d_first[s0].p, h->d_first[s0].n)); HIPCK(nans(h->d_second[s0].p, h->d_second[s0].n)); HIPCK(nans(h->d_last[s0].p, h->d_last[s0].n));
+    HIPCK(nans(h->d_chi2[s0].p, h->d_chi2[s0].n));
+    HIPCK(nans(h->d_xp_cand.p, h->d_xp_cand.n)); HIPCK(nans(h->d_xl.p, h->d_xl.n));
+    HIPCK(nans(h->d_part0.p, h->d_part0.n)); HIPCK(nans(h->d_part1.p, h->d_part1.n)); HIPCK(nans(h->d_part2.p, h->d_part2.n));
+    std::vector<double> ps(h->poses.size()*12), pt(h->points.size()*3);
+    if (!ps.empty()) HIPCK(hipMemcpyAsync(ps.data(), h->d_pose[s0].p, ps.size()*8, hipMemcpyDeviceToHost, st));
+    if (!pt.empty()) HIPCK(hipMemcpyAsync(pt.data(), h->d_pt[s0].p, pt.size()*8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < h->poses.size(); ++i) if (h->poses[i].unk >= 0) std::memset(&ps[i*12], 0xFF, 96);
+    for (size_t i = 0; i < h->points.size(); ++i) if (h->points[i].unk >= 0) std::memset(&pt[i*3], 0xFF, 24);
+    if (!ps.empty()) HIPCK(hipMemcpyAsync(h->d_pose[s0].p, ps.data(), ps.size()*8, hipMemcpyHostToDevice, st));
+    if (!pt.empty()) HIPCK(hipMemcpyAsync(h->d_pt[s0].p, pt.data(), pt.size()*8, hipMemcpyHostToDevice, st));
+    HIPCK(hipStreamSynchronize(st));
+  }
+  DevBuf<double> gxp, gxl;                           // a given step lives here until the stream has drained
+  const double* xl_dev = h->d_xl.p;
+  int slot;
+  if (!x) {
+    bool ok2 = true;
+    if (h->solve_trial(lambda, ok2)) return -1;
+    if (!ok2) { set_err("mcp_ba_debug_trial: system not positive definite"); return -1; }
+    slot = h->last_tr;
+    r.scale = h->h_res[1]; r.ss = h->h_res[2];
+    double raw[8];
+    HIPCK(hipMemcpyAsync(raw, h->d_res.p, sizeof raw, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    r.robust_chi2 = raw[0];
+    r.scale_point = nfl ? raw[1] : 0.0; r.ss_point = nfl ? raw[2] : 0.0;
+    r.scale_pose = raw[6]; r.ss_pose = raw[7];
+  } else {
+    if (gxp.alloc((size_t)np) || gxl.alloc((size_t)nfl*3)) return -1;
+    if (np) HIPCK(hipMemcpyAsync(gxp.p, x, (size_t)np*8, hipMemcpyHostToDevice, st));
+    if (nfl) HIPCK(hipMemcpyAsync(gxl.p, x + np, (size_t)nfl*24, hipMemcpyHostToDevice, st));
+    HIPCK(hipStreamSynchronize(st));
+    h->sys_cur = 0; h->spec_ok = false;
+    slot = h->cand(0);
+    const mcp_ba::TrialIo io{st, 0, h->sys_cur, slot, lambda, gxp.p, h->bp(), nullptr, h->d_xp_cand.p, gxl.p, h->d_part0.p, nullptr, nullptr,
+                             h->d_res.p + 6, 6, h->d_res.p, nullptr, nullptr, 0, 0ull, false, false, true};
+    if (h->launch_trial_step(io)) return -1;
+    if (h->read_results(1)) return -1;
+    r.robust_chi2 = h->h_res[0];
+    xl_dev = gxl.p;
+  }
+  const size_t nps = (size_t)h->P.npose*12, npt = (size_t)h->P.npoint*3; const int n = h->P.nmeas;
+  std::vector<double> c(chi2_out ? n : 0);
+  if (x_out && np) HIPCK(hipMemcpyAsync(x_out, h->d_xp_cand.p, (size_t)np*8, hipMemcpyDeviceToHost, st));
+  if (x_out && nfl) HIPCK(hipMemcpyAsync(x_out + np, xl_dev, (size_t)nfl*24, hipMemcpyDeviceToHost, st));
+  if (poses_out && nps) HIPCK(hipMemcpyAsync(poses_out, h->d_pose[slot].p, nps*8, hipMemcpyDeviceToHost, st));
+  if (points_out && npt) HIPCK(hipMemcpyAsync(points_out, h->d_pt[slot].p, npt*8, hipMemcpyDeviceToHost, st));
+  if (chi2_out) HIPCK(hipMemcpyAsync(c.data(), h->d_chi2[slot].p, (size_t)n*8, hipMemcpyDeviceToHost, st));
+  HIPCK(hipStreamSynchronize(st));
+  if (chi2_out) for (int j = 0; j < n; ++j) { const int i = h->perm[j]; if (i >= 0) chi2_out[i] = c[j]; }      // (near miss: not a measurement of this map)
+  if (!h->launch_err.empty()) { set_err("mcp_ba_debug_trial: launch refused: " + h->launch_err); h->launch_err.clear(); return -1; }
   *out = r;
   return 0;
 }

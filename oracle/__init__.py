@@ -63,6 +63,7 @@ def lib():
         L.orc_ba_numeric_jacobian.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, c_double_p, c_double_p, c_double_p]
         L.orc_ba_debug_solve.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p, c_double_p]
         L.orc_ba_debug_system.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p]
+        L.orc_ba_debug_rhs.argtypes = [ctypes.c_void_p, c_double_p]
         L.orc_ba_debug_robust_chi2.argtypes = [ctypes.c_void_p, c_double_p]
         L.orc_ba_debug_robust_chi2.restype = ctypes.c_double
         L.orc_cam_project.argtypes = [ctypes.c_void_p, c_double_p, c_double_p, c_double_p]
@@ -244,6 +245,12 @@ class OracleBundle:
         if self._L.orc_ba_debug_system(self._h, float(lam), _dp(out)) < 0:
             raise RuntimeError("orc_ba_debug_system: a point block is not positive definite")
         return out[:n * n].reshape(n, n), out[n * n:n * n + n], out[n * n + n:]
+
+    def DebugRhs(self):
+        """b = (J^T r of the free poses | of the free points) at the current state: the right-hand side of (H + lambda I) x = b."""
+        b = np.zeros(self.Prepare())
+        assert self._L.orc_ba_debug_rhs(self._h, _dp(b)) == 0
+        return b
 
     def DebugRobustChi2(self):
         s = ctypes.c_double(0)

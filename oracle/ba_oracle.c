@@ -865,6 +865,13 @@ int orc_ba_debug_system(orc_ba* h, double lambda, double* out) {
   memcpy(out + (size_t)np*np + np, h->bp, sizeof(double)*np);
   return rc ? -1 : np;
 }
+int orc_ba_debug_rhs(orc_ba* h, double* b) {
+  if (!h->prepared) orc_ba_prepare(h);
+  compute_active_errors(h); h->need_recompute = 1; (void)active_robust_chi2(h);
+  build_system(h);
+  gather_b(h); memcpy(b, h->ball, sizeof(double)*h->nx);
+  return 0;
+}
 double orc_ba_debug_robust_chi2(orc_ba* h, double* sigma_sq_raw) {
   if (!h->prepared) orc_ba_prepare(h);
   compute_active_errors(h); h->need_recompute = 1;

@@ -120,6 +120,9 @@ int  orc_ba_debug_solve(orc_ba*, double lambda, double* x_schur, double* x_dense
 /* reduced pose system at the current state: out = [S (np*np, symmetric) | rhs (np) | pose part of J^T r (np)]; returns np
  * (out may be NULL to query it), -1 if a point block is not positive definite */
 int  orc_ba_debug_system(orc_ba*, double lambda, double* out);
+/* b = (J^T r of the free poses, np entries | of the free points, 3 each) at the current state (sigma recomputed): the right-hand
+ * side of (H + lambda I) x = b as the system build leaves it.  b has orc_ba_prepare() entries.  returns 0 */
+int  orc_ba_debug_rhs(orc_ba*, double* b);
 /* robust chi2 sum at current state with freshly recomputed sigma */
 double orc_ba_debug_robust_chi2(orc_ba*, double* sigma_sq_raw);
 

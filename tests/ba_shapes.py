@@ -245,6 +245,37 @@ def calib_cut(n_points):
     return q
 
 
+CHAIN_SEAMS = (64, 65, 128, 129)      # pose chains of a map against the 64 chains a chain workgroup of the one-launch trial step takes
+POSE_COUNT_SEAMS = (255, 256, 257)     # poses of a map against the 256 poses such a workgroup keeps in LDS
+
+
+def chain_design(name, n_chains):
+    """A map with exactly n_chains pose chains: every (keyframe, camera) pair of n_chains // 2 keyframes with two cameras is a chain
+    (pair j = keyframe j // 2, camera j % 2; point j is measured from pairs j, j + 21 and j + 42, so every pair measures three
+    points), and for an odd count one fixed point, which brings the world chain."""
+    pairs = n_chains // 2 * 2
+    d = MapDesign(name, pairs // 2, 2)
+    for j in range(pairs):
+        d.points.append(PointDesign((0, 0), [(((j + 21 * m) % pairs) // 2, ((j + 21 * m) % pairs) % 2) for m in range(3)]))
+    if n_chains % 2:
+        d.points.append(PointDesign((0, 0), [(1, 0), (2, 1), (3, 0)], fixed=True))
+    return d
+
+
+def pose_count_design(name, n_poses):
+    """A map with exactly n_poses poses: n_poses - 1 keyframes (keyframe 0 fixed) and the pose of the one camera.  128 points in
+    the fixed keyframe's frame; keyframe k measures points k + 0, 7, 29, 53, 71 and 101 (mod 128): every free keyframe has a pose
+    block that six measurements determine, and a point touches 12 poses at most."""
+    d = MapDesign(name, n_poses - 1, 1)
+    obs = [[] for _ in range(128)]
+    for k in range(n_poses - 1):
+        for off in (0, 7, 29, 53, 71, 101):
+            obs[(k + off) % 128].append((k, 0))
+    for i in range(128):
+        d.points.append(PointDesign((0, 0), obs[i]))
+    return d
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the committed maps, by name (built once per process)
 
@@ -267,13 +298,16 @@ def _designs():
 
 DESIGNS = _designs()
 MAP_NAMES = tuple(DESIGNS) + ("calib17", "calib65")
+# the maps of the trial-step tests (ba_trial_cases.py): kept out of MAP_NAMES, the pose-count maps have 1500 pose unknowns
+TRIAL_DESIGNS = dict([("chains%d" % n, lambda n=n: chain_design("chains%d" % n, n)) for n in CHAIN_SEAMS] +
+                     [("poses%d" % n, lambda n=n: pose_count_design("poses%d" % n, n)) for n in POSE_COUNT_SEAMS])
 _MAPS = {}
 
 
 def get_map(name):
     """The committed map `name` (a synth.Problem; `.design` is its MapDesign, None for the cut calibration maps)."""
     if name not in _MAPS:
-        _MAPS[name] = calib_cut(int(name[5:])) if name.startswith("calib") else build(DESIGNS[name]())
+        _MAPS[name] = calib_cut(int(name[5:])) if name.startswith("calib") else build((DESIGNS.get(name) or TRIAL_DESIGNS[name])())
     return _MAPS[name]
 
 
