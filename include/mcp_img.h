@@ -969,6 +969,78 @@ int mcp_graph_kf_lists_host(int ncam, int n_slots, const int* mkf_flags, const u
                             const int* inlier, const int* outlier, int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row,
                             const uint8_t* ms_alive, int n_mkfs, const int* slots, int* seg_start /* n_mkfs*ncam + 1 */, int cap, int* seg_rows, double* seg_weights);
 
+/* ---- Measurement parcels: the tracker's and ReFind's measurements into the store without a host hop ---- src/Tracker.cc:1237-1274, src/MapMaker.cc:389-423
+ * mcp_track_map_record / mcp_track_frame_motion / mcp_track_frame_recover and mcp_map_refind leave their measurements in pinned blocks that
+ * kernels wrote.  A PARCEL takes such a list into device memory of its own -- with, per entry, the key (mcp_map_points_set_source) the entry's
+ * row held at that moment, read on the device -- and keeps it while the tracker goes on rewriting the pinned blocks.  The COMMIT, whenever the
+ * map maker gets to the MultiKeyFrame, appends the entries that are still good to a graph's store, judged by the map as it is THEN.
+ * A parcel lives on its table's device and enqueues on its table's stream; THE TABLE MUST OUTLIVE IT (as it must a graph).  The caller
+ * serialises the calls on one table, its graphs and its parcels.  A fill replaces the parcel's contents; capacity grows geometrically (a fill
+ * that outgrows the block waits for the stream first, every other fill is enqueued without a wait).
+ * ENTRY: lane = which of the commit's lanes the entry belongs to; row, level, uv (level-0 coordinates) as the store keeps them; key = the row's
+ *   key when the parcel was filled.
+ * from_track: the measurement lists of the last successful track call with bookkeeping on the table (the three named above), exactly the bytes
+ *   mcp_track_map_meas_view shows: lane = camera index, cameras ascending, a camera's entries in item order, uv = found_pos.  The sets C, T, R of
+ *   a camera are disjoint (the PVS lists a row once, C takes the smallest keys of levels 3 and 2, T and R only keys above those: k_tm_select),
+ *   so (lane, row) is unique in the parcel.  ORDER: the count is the host's (the record's n_meas), the fill is one launch on the table's
+ *   stream, which is the stream k_tr_scatter writes the pinned list on; a later track call rewrites the list by launches on the same stream,
+ *   behind the fill -- stream order, no wait.  (A later call that has to REPLACE the pinned block by a larger one waits for the stream first.)
+ *   Refused unless the last track / PVS call on the table was such a call.
+ * from_refind: the FOUND pairs of the last mcp_map_refind on the table, in ascending pair index (mcp_map_refind_view's bytes): lane = target,
+ *   uv = root_pos.  The same order argument holds.  Refused when that call was refused or ran over its cap.
+ * from_host: the caller's arrays in the caller's order (a keyframe that arrives over the wire); the keys are gathered on the device.  Refused:
+ *   a row outside the table, a level outside 0..MCP_LEVELS-1, a non-finite uv, a negative lane.
+ * All three return the entry count.  get: the entries read back (waits); cap below the size is refused.
+ * REFUSALS: -1 (NULL for create), mcp_last_error(), nothing enqueued, the parcel unchanged. */
+typedef struct mcp_meas_parcel mcp_meas_parcel;
+typedef struct mcp_parcel_entry { double uv[2]; int lane, row, key, level; } mcp_parcel_entry;   /* 32 B */
+mcp_meas_parcel* mcp_meas_parcel_create(mcp_map_points* table);
+void mcp_meas_parcel_destroy(mcp_meas_parcel*);
+int  mcp_meas_parcel_from_track (mcp_meas_parcel*);
+int  mcp_meas_parcel_from_refind(mcp_meas_parcel*);
+int  mcp_meas_parcel_from_host  (mcp_meas_parcel*, int n, const int* lane, const int* row, const double* uv /* n x 2 */, const int* level);
+int  mcp_meas_parcel_size(const mcp_meas_parcel*);
+int  mcp_meas_parcel_get (const mcp_meas_parcel*, int cap, mcp_parcel_entry* out);
+
+/* THE COMMIT.  lane_mkf[l] / lane_cam[l]: the MKF slot and camera index lane l's entries are measurements of; lane_mkf[l] < 0 withholds the lane
+ * (an inactive camera, a ReFind target the caller leaves out; its lane_cam is not looked at).  Entry e gets the first verdict that applies:
+ *   MCP_PARCEL_SKIPPED  lane_mkf[e.lane] < 0
+ *   MCP_PARCEL_STALE    e.row is past the table's rows, or the row's key is no longer e.key: the row was recycled for another point (nothing of
+ *                       the new point is read beyond its key)
+ *   MCP_PARCEL_BAD      the row's graph column is MCP_GP_BAD (a row never written is bad): td.mPoint.mbBad in RecordMeasurements and the sweep
+ *                       of AddMultiKeyFrameFromTopOfQueue (src/MapMaker.cc:407-418)
+ *   MCP_PARCEL_CROSS    !cross_camera and the row has no source MKF or its source camera is not lane_cam[e.lane] (src/Tracker.cc:1256)
+ *   MCP_PARCEL_APPENDED otherwise: the store entry {uv, lane_mkf, lane_cam, row, level, params.source, alive} goes to store index
+ *                       first + (its position among the appended entries in parcel order).
+ * The five counters sum to the parcel's size; lane_appended[l] (NULL, or n_lanes ints) counts the appended entries per lane.  The appended
+ * bytes are those mcp_map_graph_add_meas stores for the same surviving entries in the same order; as there, the caller guarantees that no
+ * (mkf, cam, row) is in the store already.  The store is grown to hold every entry of the parcel before anything is enqueued; then one copy of
+ * the lane tables, two launches on the table's stream, one wait.  A committed parcel is marked: committing it again without a refill is refused.
+ * An empty parcel commits with nothing enqueued.
+ * REFUSALS (-1, mcp_last_error(), graph, store and parcel unchanged): NULL handles or structs; a parcel of another table; a parcel never
+ * filled or committed already; n_lanes < 0 or lane tables NULL with n_lanes > 0; an entry whose lane is >= n_lanes (a host fill's largest lane
+ * is known to the host and refused before anything is enqueued; a device fill's is read back with the result -- the launches then append
+ * nothing); a lane_mkf >= 0 that is not a present slot, or whose lane_cam is outside the rig; a store that would pass INT_MAX. */
+#define MCP_PARCEL_APPENDED 0
+#define MCP_PARCEL_SKIPPED  1
+#define MCP_PARCEL_STALE    2
+#define MCP_PARCEL_BAD      3
+#define MCP_PARCEL_CROSS    4
+typedef struct mcp_parcel_commit_params { int cross_camera; /* GVar CrossCamera (1) */ int source; /* Measurement::eSource, stored as given */ } mcp_parcel_commit_params;
+typedef struct mcp_parcel_commit_result { int first, n_appended, n_skipped_lane, n_stale, n_bad, n_cross; } mcp_parcel_commit_result;
+typedef struct mcp_store_entry { double uv[2]; int mkf, cam, row, level, source, alive; } mcp_store_entry;   /* a store entry as the device holds it, 40 B */
+int mcp_meas_parcel_commit(mcp_map_graph*, mcp_meas_parcel*, int n_lanes, const int* lane_mkf, const int* lane_cam,
+                           const mcp_parcel_commit_params*, mcp_parcel_commit_result*, int* lane_appended /* n_lanes or NULL */);
+
+/* the same verdicts from host arrays, by the same body under the host compiler: needs no device and gives the device's bytes.  keys: the
+ * table's key column now, n_rows; point_flags / src_mkf / src_cam: the n_point_rows <= n_rows graph columns written so far (rows after them
+ * read as bad).  verdict: NULL or n bytes; appended: NULL or room for n records (the appended ones, in order); res->first = first.  Returns
+ * n_appended.  Refused (outputs untouched): negative counts, a NULL array with a positive count, an entry lane outside 0..n_lanes-1. */
+int mcp_parcel_commit_host(int n, const mcp_parcel_entry* entries, int n_rows, const int* keys, int n_point_rows, const int* point_flags,
+                           const int* src_mkf, const int* src_cam, int n_lanes, const int* lane_mkf, const int* lane_cam,
+                           const mcp_parcel_commit_params*, int first, uint8_t* verdict, mcp_store_entry* appended,
+                           mcp_parcel_commit_result* res, int* lane_appended /* n_lanes or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

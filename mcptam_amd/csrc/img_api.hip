@@ -30,6 +30,7 @@
 #include "ba_select.h"
 #include "map_graph_kernels.h"
 #include "map_graph_lists.h"
+#include "map_graph_parcel.h"
 
 using namespace mcp;
 
@@ -1094,6 +1095,9 @@ struct mcp_map_points {
   // staging may be refilled.  One event serialises every upload, so one pair of blocks serves all columns.
   PinBuf<char> up_in; Buf<char> up_dev;
   hipEvent_t staged = nullptr; bool stage_busy = false;
+  // a measurement parcel's fill (mcp_meas_parcel_from_track / _from_refind) may still be reading tr.h_meas / rf.out: a call that has to replace
+  // one of them by a larger block waits for the stream first (rewriting them is ordered behind the fill by the stream)
+  bool parcel_reads = false;
   std::vector<int> sorted_ids;                       // duplicate check of the uploads by id
   // the source keyframes as (handle, serial).  Slots are reference-counted by the rows that name them (row_slot: the host's copy of each
   // row's slot1); a slot no row names is released and its index reused, so the table walked per call stays as long as the keyframes the
@@ -1193,7 +1197,7 @@ struct mcp_map_points {
     for (hipEvent_t e : wb.t) if (e) (void)hipEventDestroy(e); }
   TmStates state_ptrs() const { TmStates S; for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c) S.s[c] = states[c].row(); return S; }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
-  hipError_t sync() { const hipError_t e = hipStreamSynchronize(st); if (e == hipSuccess) stage_busy = false; return e; }      // (nothing staged is in flight after it)
+  hipError_t sync() { const hipError_t e = hipStreamSynchronize(st); if (e == hipSuccess) { stage_busy = false; parcel_reads = false; } return e; }      // (nothing staged is in flight after it)
   // every live column (or `only` this one, about to come to life) gets a block of new_cap rows where it has less, the rows so far copied over
   int reserve(size_t new_cap, Column* only = nullptr) {
     std::vector<Buf<char>> fresh(cols.size());
@@ -1770,6 +1774,7 @@ struct TrackFrame {
     if (cov && m->cv.reserve(NB)) return -1;
     if (cov) std::memset(m->cv.h_out.p, 0, sizeof(mcp_track_pose_cov_record));        // (valid = 0 unless k_pose_cov_finish runs)
     if (rp) {
+      if (m->parcel_reads && m->tr.h_meas.n < NB) ICK(m->sync());       // (a parcel's fill may still read the block replaced below)
       if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
           m->tr.seg_start.alloc(MCP_MAX_FRAME_CAMS + 1) || m->tr.seg_rows.alloc(NB) || m->tr.seg_w.alloc(NB) || m->tr.cfw.alloc(12*MCP_MAX_FRAME_CAMS) || m->wb.depth.alloc(NB)) return -1;
       std::memset(m->tr.h_rec.p, 0, sizeof(mcp_track_record));          // (the cameras past ncam read as zeros)
@@ -2551,6 +2556,7 @@ int mcp_map_refind(mcp_map_points* m, int n_targets, const mcp_refind_target* ta
   // pinned results: RfOut | verdict bytes | measurements
   const size_t r_vd = tm_align(sizeof(RfOut)), r_ms = r_vd + tm_align((size_t)n), rblk = r_ms + sizeof(mcp_refind_meas)*(size_t)std::max(room, 1);
   // everything is allocated before the first enqueue
+  if (m->parcel_reads && m->rf.out.n < rblk) ICK(m->sync());            // (a parcel's fill may still read the block replaced below)
   if (m->rf.in.alloc(blk) || m->rf.dev.alloc(blk) || m->rf.out.alloc(rblk) || m->rf.flags.alloc(n) || m->rf.vd.alloc(n) || m->rf.blk.alloc(2*(size_t)nblk) ||
       m->rf.items.alloc(n) || m->rf.first.alloc(n) || m->rf.cand.alloc(n)) return -1;
   char* hb = m->rf.in.p;
@@ -2626,9 +2632,11 @@ struct mcp_map_graph {
   // the keyframe lists (map_graph_lists.h): the call's slots (pinned | device), the (key, row) column, the count table, the lists, the
   // keyframes' poses and the pinned results of mcp_graph_refresh_depth / mcp_graph_debug_kf_lists
   PinBuf<char> l_in; Buf<char> l_dev; Buf<int2> l_key_row; Buf<int> l_table, l_start, l_rows; Buf<double> l_w, l_cfw; PinBuf<char> l_out;
+  // the commit of a measurement parcel (map_graph_parcel.h): verdict bytes, per-workgroup counts, the result block (MgpCtl | per-lane counts: device, pinned)
+  Buf<uint8_t> pc_vd; Buf<int> pc_blk; Buf<char> pc_dev; PinBuf<char> pc_out;
   ~mcp_map_graph() { if (m && m->st) (void)hipStreamSynchronize(m->st); for (hipEvent_t e : {staged, t0, t1}) if (e) (void)hipEventDestroy(e); }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
-  int sync() { ICK(hipStreamSynchronize(m->st)); stage_busy = false; m->stage_busy = false; return 0; }
+  int sync() { ICK(hipStreamSynchronize(m->st)); stage_busy = false; m->stage_busy = false; m->parcel_reads = false; return 0; }
   // pinned + device staging of `bytes`, free to fill
   int stage(size_t bytes) {
     if (wait_staging()) return -1;
@@ -3336,6 +3344,185 @@ int mcp_graph_write_back(mcp_ba* h, mcp_map_graph* g, int n_points, const int* p
     sd_copy_out(n_kf, (const mcp_scene_depth*)(hout + W.sd), depth_out);
     if (bfw_out) std::memcpy(bfw_out, hout + o_bfw, 96*(size_t)n_mkfs);
   }
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- measurement parcels (include/mcp_img.h mcp_meas_parcel_*, map_graph_parcel.h) ---------------------------------------------------------
+struct mcp_meas_parcel {
+  mcp_map_points* m = nullptr;                        // the table: its device, its stream, its key column (it must outlive the parcel)
+  Buf<mcp_parcel_entry> ent; int n = 0;
+  Buf<int> max_lane;                                  // the largest lane of the fill, for the commit's launches (-1: none)
+  int h_max_lane = -1; bool lane_known = true;        // ... on the host: known for a host fill, read back by the commit for a device fill
+  bool filled = false, committed = false;
+  PinBuf<mcp_parcel_entry> up_in; hipEvent_t staged = nullptr; bool stage_busy = false;      // from_host: packed here, copied on the table's stream
+  ~mcp_meas_parcel() { if (m && m->st) (void)hipStreamSynchronize(m->st); if (staged) (void)hipEventDestroy(staged); }
+  // room for `need` entries, contents not kept (a fill replaces them); a block that grows is replaced with nothing in flight on the old one
+  int reserve(size_t need) {
+    if (need <= ent.n && ent.p) return 0;
+    if (ent.p) ICK(m->sync());
+    return ent.alloc(std::max<size_t>({need, 2*ent.n, (size_t)1024}));
+  }
+  int filled_now(int count, int top, bool known) {
+    n = count; h_max_lane = top; lane_known = known; filled = true; committed = false;
+    return count;
+  }
+};
+
+extern "C" {
+
+mcp_meas_parcel* mcp_meas_parcel_create(mcp_map_points* m) {
+  if (!m) { mcp_set_error("mcp_meas_parcel_create: NULL table"); return nullptr; }
+  if (hipSetDevice(m->device) != hipSuccess) { mcp_set_error("hipSetDevice failed"); return nullptr; }
+  mcp_meas_parcel* p = new mcp_meas_parcel(); p->m = m;
+  const bool ok = !p->max_lane.alloc(1) && hipEventCreateWithFlags(&p->staged, hipEventDisableTiming) == hipSuccess &&
+                  hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st) == hipSuccess;
+  if (!ok) { mcp_set_error("mcp_meas_parcel_create: allocation failed"); delete p; return nullptr; }
+  return p;
+}
+void mcp_meas_parcel_destroy(mcp_meas_parcel* p) { if (p) { (void)hipSetDevice(p->m->device); delete p; } }
+
+int mcp_meas_parcel_from_track(mcp_meas_parcel* p) {
+  const std::string who = "mcp_meas_parcel_from_track";
+  if (!p) return img_fail(who + ": NULL parcel");
+  mcp_map_points* m = p->m;
+  if (!m->tr.ok) return img_fail(who + ": the last track / PVS call on this table was no successful mcp_track_map_record, mcp_track_frame_motion or mcp_track_frame_recover");
+  const int ncam = m->tr.ncam, n = m->tr.meas_first[ncam];
+  ICK(hipSetDevice(m->device));
+  if (p->reserve((size_t)n)) return -1;
+  ICK(hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st));
+  if (n > 0) {
+    MgpFirst F; std::memset(&F, 0, sizeof F);
+    for (int c = 0; c <= ncam; ++c) F.v[c] = m->tr.meas_first[c];
+    hipLaunchKernelGGL(k_mgp_from_track, dim3((unsigned)((n + MGP_BLOCK - 1)/MGP_BLOCK)), dim3(MGP_BLOCK), 0, m->st, (const mcp_track_meas*)m->tr.h_meas.p, n, ncam, F,
+                       (const TmSrc*)m->src.row(), m->rows, p->ent.p, p->max_lane.p);
+    ICK(hipGetLastError());
+    m->parcel_reads = true;
+  }
+  return p->filled_now(n, -1, n == 0);
+}
+
+int mcp_meas_parcel_from_refind(mcp_meas_parcel* p) {
+  const std::string who = "mcp_meas_parcel_from_refind";
+  if (!p) return img_fail(who + ": NULL parcel");
+  mcp_map_points* m = p->m;
+  if (m->rf.view < 0) return img_fail(who + ": the last mcp_map_refind on this table left no measurements to take");
+  const int n = m->rf.view;
+  ICK(hipSetDevice(m->device));
+  if (p->reserve((size_t)n)) return -1;
+  ICK(hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st));
+  if (n > 0) {
+    hipLaunchKernelGGL(k_mgp_from_refind, dim3((unsigned)((n + MGP_BLOCK - 1)/MGP_BLOCK)), dim3(MGP_BLOCK), 0, m->st, reinterpret_cast<const mcp_refind_meas*>(m->rf.out.p + m->rf.meas_off), n,
+                       (const TmSrc*)m->src.row(), m->rows, p->ent.p, p->max_lane.p);
+    ICK(hipGetLastError());
+    m->parcel_reads = true;
+  }
+  return p->filled_now(n, -1, n == 0);
+}
+
+int mcp_meas_parcel_from_host(mcp_meas_parcel* p, int n, const int* lane, const int* row, const double* uv, const int* level) {
+  const std::string who = "mcp_meas_parcel_from_host";
+  if (!p) return img_fail(who + ": NULL parcel");
+  if (n < 0 || (n > 0 && (!lane || !row || !uv || !level))) return img_fail(who + ": bad arguments");
+  mcp_map_points* m = p->m;
+  const int R = m->rows;
+  int top = -1;
+  for (int k = 0; k < n; ++k) {
+    const std::string at = who + ": entry " + std::to_string(k);
+    if (lane[k] < 0) return img_fail(at + " names lane " + std::to_string(lane[k]));
+    if (row[k] < 0 || row[k] >= R) return img_fail(at + " names row " + std::to_string(row[k]) + ", the table has " + std::to_string(R));
+    if (level[k] < 0 || level[k] >= MCP_LEVELS) return img_fail(at + " has level " + std::to_string(level[k]));
+    if (!std::isfinite(uv[2*(size_t)k]) || !std::isfinite(uv[2*(size_t)k + 1])) return img_fail(at + " has a non-finite position");
+    top = std::max(top, lane[k]);
+  }
+  ICK(hipSetDevice(m->device));
+  if (p->stage_busy) { ICK(hipEventSynchronize(p->staged)); p->stage_busy = false; }
+  if (p->up_in.alloc((size_t)n) || p->reserve((size_t)n)) return -1;
+  ICK(hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st));
+  if (n > 0) {
+    mcp_parcel_entry* rec = p->up_in.p;
+    for (int k = 0; k < n; ++k) { rec[k].uv[0] = uv[2*(size_t)k]; rec[k].uv[1] = uv[2*(size_t)k + 1]; rec[k].lane = lane[k]; rec[k].row = row[k]; rec[k].key = 0; rec[k].level = level[k]; }
+    ICK(hipMemcpyAsync(p->ent.p, rec, sizeof(mcp_parcel_entry)*(size_t)n, hipMemcpyHostToDevice, m->st));
+    hipLaunchKernelGGL(k_mgp_keys, dim3((unsigned)((n + MGP_BLOCK - 1)/MGP_BLOCK)), dim3(MGP_BLOCK), 0, m->st, p->ent.p, n, (const TmSrc*)m->src.row(), R);
+    ICK(hipGetLastError());
+    ICK(hipEventRecord(p->staged, m->st)); p->stage_busy = true;
+  }
+  return p->filled_now(n, top, true);
+}
+
+int mcp_meas_parcel_size(const mcp_meas_parcel* p) {
+  if (!p) return img_fail("mcp_meas_parcel_size: NULL parcel");
+  return p->n;
+}
+
+int mcp_meas_parcel_get(const mcp_meas_parcel* p, int cap, mcp_parcel_entry* out) {
+  if (!p) return img_fail("mcp_meas_parcel_get: NULL parcel");
+  if (cap < p->n || (p->n > 0 && !out)) return img_fail("mcp_meas_parcel_get: the parcel holds " + std::to_string(p->n) + " entries, the caller's array " + std::to_string(cap));
+  mcp_map_points* m = p->m;
+  ICK(hipSetDevice(m->device));
+  if (p->n > 0) ICK(hipMemcpyAsync(out, p->ent.p, sizeof(mcp_parcel_entry)*(size_t)p->n, hipMemcpyDeviceToHost, m->st));
+  ICK(m->sync());
+  return p->n;
+}
+
+int mcp_meas_parcel_commit(mcp_map_graph* g, mcp_meas_parcel* p, int n_lanes, const int* lane_mkf, const int* lane_cam, const mcp_parcel_commit_params* prm,
+                           mcp_parcel_commit_result* res, int* lane_appended) {
+  const std::string who = "mcp_meas_parcel_commit";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!p) return img_fail(who + ": NULL parcel");
+  if (!prm || !res) return img_fail(who + ": NULL params or result");
+  if (p->m != g->m) return img_fail(who + ": the parcel belongs to another table than the graph");
+  if (!p->filled) return img_fail(who + ": the parcel was never filled");
+  if (p->committed) return img_fail(who + ": the parcel was committed already; a second commit without a refill would duplicate every entry");
+  if (n_lanes < 0 || (n_lanes > 0 && (!lane_mkf || !lane_cam))) return img_fail(who + ": bad lane tables");
+  for (int l = 0; l < n_lanes; ++l) {
+    if (lane_mkf[l] < 0) continue;
+    if (lane_mkf[l] >= MCP_MAP_MAX_MKFS || !(g->h_flags[lane_mkf[l]] & MCP_MKF_PRESENT)) return img_fail(who + ": lane " + std::to_string(l) + " names MKF slot " + std::to_string(lane_mkf[l]) + ", which is not present");
+    if (lane_cam[l] < 0 || lane_cam[l] >= g->rig.ncam) return img_fail(who + ": lane " + std::to_string(l) + " names camera " + std::to_string(lane_cam[l]));
+  }
+  const int n = p->n, first = g->n_store;
+  if (p->lane_known && p->h_max_lane >= n_lanes) return img_fail(who + ": the parcel holds an entry of lane " + std::to_string(p->h_max_lane) + ", the call has " + std::to_string(n_lanes) + " lanes");
+  if ((long long)first + n > 0x7fffffffLL) return img_fail(who + ": the store is full");
+  if (n == 0) {
+    std::memset(res, 0, sizeof *res); res->first = first;
+    for (int l = 0; lane_appended && l < n_lanes; ++l) lane_appended[l] = 0;
+    p->committed = true;
+    return 0;
+  }
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int R = m->rows, nblk = (n + MGP_BLOCK - 1)/MGP_BLOCK;
+  // staging: lane_mkf | lane_cam up; MgpCtl | lane_appended down.  Everything is allocated before the first enqueue.
+  const size_t o_cam = tm_align(sizeof(int)*(size_t)std::max(n_lanes, 1)), up = 2*o_cam, o_lanes = tm_align(sizeof(MgpCtl)), down = o_lanes + sizeof(int)*(size_t)std::max(n_lanes, 1);
+  if (g->pc_vd.n < (size_t)n || g->pc_blk.n < (size_t)nblk || g->pc_dev.n < down || g->pc_out.n < down) { if (g->sync()) return -1; }
+  if (g->pc_vd.alloc(n) || g->pc_blk.alloc(nblk) || g->pc_dev.alloc(down) || g->pc_out.alloc(down)) return -1;
+  if (g->stage(up) || g->grow_store((size_t)first + n) || g->grow_points(R)) return -1;
+  std::memset(g->up_in.p, 0, up);
+  if (n_lanes) { std::memcpy(g->up_in.p, lane_mkf, sizeof(int)*(size_t)n_lanes); std::memcpy(g->up_in.p + o_cam, lane_cam, sizeof(int)*(size_t)n_lanes); }
+  hipStream_t st = m->st;
+  MgpCommit Q; Q.n = n; Q.n_lanes = n_lanes; Q.cross_camera = prm->cross_camera ? 1 : 0; Q.source = prm->source; Q.first = first; Q.cap = (long long)g->store.n;
+  const int* d_mkf = (const int*)g->up_dev.p; const int* d_cam = (const int*)(g->up_dev.p + o_cam);
+  MgpCtl* d_ctl = reinterpret_cast<MgpCtl*>(g->pc_dev.p); int* d_lanes = reinterpret_cast<int*>(g->pc_dev.p + o_lanes);
+  Drain drain{m, true};
+  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, up, hipMemcpyHostToDevice, st));
+  ICK(hipMemsetAsync(g->pc_dev.p, 0, down, st));
+  hipLaunchKernelGGL(k_mgp_judge, dim3(nblk), dim3(MGP_BLOCK), 0, st, Q, (const mcp_parcel_entry*)p->ent.p, d_mkf, d_cam, (const TmSrc*)m->src.row(), R, (const MgPoint*)g->pts.p, g->prow,
+                     (const int*)p->max_lane.p, g->pc_vd.p, g->pc_blk.p, d_ctl, d_lanes);
+  hipLaunchKernelGGL(k_mgp_append, dim3(nblk), dim3(MGP_BLOCK), 0, st, Q, (const mcp_parcel_entry*)p->ent.p, d_mkf, d_cam, (const uint8_t*)g->pc_vd.p, (const int*)g->pc_blk.p, nblk,
+                     (const int*)p->max_lane.p, reinterpret_cast<mcp_store_entry*>(g->store.p));
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(g->pc_out.p, g->pc_dev.p, down, hipMemcpyDeviceToHost, st));
+  if (g->sync()) return -1;                            // the one wait
+  drain.armed = false;
+  const MgpCtl& C = *reinterpret_cast<const MgpCtl*>(g->pc_out.p);
+  p->h_max_lane = C.max_lane; p->lane_known = true;
+  if (C.refused) return img_fail(who + ": the parcel holds an entry of lane " + std::to_string(C.max_lane) + ", the call has " + std::to_string(n_lanes) + " lanes");
+  res->first = first; res->n_appended = C.counts[MCP_PARCEL_APPENDED]; res->n_skipped_lane = C.counts[MCP_PARCEL_SKIPPED]; res->n_stale = C.counts[MCP_PARCEL_STALE];
+  res->n_bad = C.counts[MCP_PARCEL_BAD]; res->n_cross = C.counts[MCP_PARCEL_CROSS];
+  if (lane_appended && n_lanes) std::memcpy(lane_appended, g->pc_out.p + o_lanes, sizeof(int)*(size_t)n_lanes);
+  g->n_store += res->n_appended; g->n_live += res->n_appended;
+  p->committed = true;
   return 0;
 }
 

@@ -59,6 +59,8 @@ IMG_SYMBOLS = [
     "mcp_map_graph_get_meas", "mcp_map_graph_good_counts", "mcp_map_graph_check", "mcp_map_bundle_select", "mcp_map_bundle_mkfs_view",
     "mcp_map_bundle_points_view", "mcp_map_bundle_meas_view", "mcp_map_bundle_select_host", "mcp_map_bundle_select_last_timing",
     "mcp_graph_refresh_depth", "mcp_graph_write_back", "mcp_graph_debug_kf_lists", "mcp_graph_kf_lists_host", "mcp_graph_get_mkfs",
+    "mcp_meas_parcel_create", "mcp_meas_parcel_destroy", "mcp_meas_parcel_from_track", "mcp_meas_parcel_from_refind", "mcp_meas_parcel_from_host",
+    "mcp_meas_parcel_size", "mcp_meas_parcel_get", "mcp_meas_parcel_commit", "mcp_parcel_commit_host",
 ]
 _BOUND = False
 

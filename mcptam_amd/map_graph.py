@@ -8,7 +8,12 @@ written from the reference (src/BundleAdjusterBase.cc:141-265, src/BundleAdjuste
 selection_problem makes the synth.Problem a selection describes, which Problem.populate replays into a ChainBundle as it is.
 
 The keyframe lists of AdjustAndUpdate's write-back come from the same store (mcp_graph_*): MapGraph.debug_kf_lists / refresh_depth / write_back
-on the device, kf_lists_host (mcp_graph_kf_lists_host, no device) and kf_lists_ref, the numpy restatement (src/KeyFrame.cc:549-570, 851-869)."""
+on the device, kf_lists_host (mcp_graph_kf_lists_host, no device) and kf_lists_ref, the numpy restatement (src/KeyFrame.cc:549-570, 851-869).
+
+Measurement parcels (mcp_meas_parcel_*) feed the store from the device: MeasParcel takes the measurements of a track call, a ReFind or the
+caller into device memory with the keys of their rows, MapGraph.commit_parcel appends the ones that are still good when the map maker gets to
+them; parcel_commit_host (mcp_parcel_commit_host, no device) and parcel_commit_ref, the numpy restatement (src/Tracker.cc:1237-1274,
+src/MapMaker.cc:407-418), state the verdicts."""
 import ctypes
 
 import numpy as np
@@ -59,6 +64,31 @@ GRAPH_SYMBOLS = [
 GRAPH_LIST_SYMBOLS = ["mcp_graph_refresh_depth", "mcp_graph_write_back", "mcp_graph_debug_kf_lists", "mcp_graph_kf_lists_host", "mcp_graph_get_mkfs"]
 LIST_BLOCK, LIST_MAX_BLOCKS = 256, 64          # map_graph_lists.h: entries of a tile, chunks at the most (the default grid: one tile per chunk up to that)
 
+# measurement parcels (include/mcp_img.h mcp_meas_parcel_*, map_graph_parcel.h)
+PARCEL_SYMBOLS = ["mcp_meas_parcel_create", "mcp_meas_parcel_destroy", "mcp_meas_parcel_from_track", "mcp_meas_parcel_from_refind", "mcp_meas_parcel_from_host",
+                  "mcp_meas_parcel_size", "mcp_meas_parcel_get", "mcp_meas_parcel_commit", "mcp_parcel_commit_host"]
+PARCEL_APPENDED, PARCEL_SKIPPED, PARCEL_STALE, PARCEL_BAD, PARCEL_CROSS = range(5)
+PARCEL_BLOCK = 256                            # map_graph_parcel.h: entries of a workgroup
+SRC_REFIND = 1                                # Measurement::eSource (include/mcptam/KeyFrame.h): SRC_TRACKER, SRC_REFIND, SRC_ROOT, SRC_TRAIL, SRC_EPIPOLAR
+PARCEL_ENTRY_DTYPE = np.dtype([("uv", "f8", 2), ("lane", "i4"), ("row", "i4"), ("key", "i4"), ("level", "i4")], align=True)
+STORE_ENTRY_DTYPE = np.dtype([("uv", "f8", 2), ("mkf", "i4"), ("cam", "i4"), ("row", "i4"), ("level", "i4"), ("source", "i4"), ("alive", "i4")], align=True)
+
+
+class ParcelCommitParams(ctypes.Structure):
+    _fields_ = [("cross_camera", ctypes.c_int), ("source", ctypes.c_int)]
+
+
+class ParcelCommitResult(ctypes.Structure):
+    _fields_ = [("first", ctypes.c_int), ("n_appended", ctypes.c_int), ("n_skipped_lane", ctypes.c_int), ("n_stale", ctypes.c_int), ("n_bad", ctypes.c_int),
+                ("n_cross", ctypes.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+PARCEL_STRUCT_SIZES = {"mcp_parcel_entry": PARCEL_ENTRY_DTYPE.itemsize, "mcp_store_entry": STORE_ENTRY_DTYPE.itemsize,
+                       "mcp_parcel_commit_params": ctypes.sizeof(ParcelCommitParams), "mcp_parcel_commit_result": ctypes.sizeof(ParcelCommitResult)}
+
 _BOUND = False
 
 
@@ -92,6 +122,16 @@ def lib():
         L.mcp_graph_debug_kf_lists.argtypes = [vp, ip, vp, ip, vp, ip, vp, vp]
         L.mcp_graph_get_mkfs.argtypes = [vp, ip, ip, vp, vp, vp, vp]
         L.mcp_graph_kf_lists_host.argtypes = [ip, ip, vp, vp, ip, ip, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp, vp, ip, vp, vp]
+        L.mcp_meas_parcel_create.restype = vp
+        L.mcp_meas_parcel_create.argtypes = [vp]
+        L.mcp_meas_parcel_destroy.argtypes = [vp]
+        L.mcp_meas_parcel_from_track.argtypes = [vp]
+        L.mcp_meas_parcel_from_refind.argtypes = [vp]
+        L.mcp_meas_parcel_from_host.argtypes = [vp, ip, vp, vp, vp, vp]
+        L.mcp_meas_parcel_size.argtypes = [vp]
+        L.mcp_meas_parcel_get.argtypes = [vp, ip, vp]
+        L.mcp_meas_parcel_commit.argtypes = [vp, vp, ip, vp, vp, vp, vp, vp]
+        L.mcp_parcel_commit_host.argtypes = [ip, vp, ip, vp, ip, vp, vp, vp, ip, vp, vp, vp, ip, vp, vp, vp, vp]
         _BOUND = True
     return L
 
@@ -248,6 +288,78 @@ def kf_lists_ref(a, slots, n_rows=None):
     inl, outl = _list_counts(a, n_rows)
     rows = mr[e].astype(np.int32)
     return seg_start, rows, inl[rows].astype(np.float64) / (inl[rows].astype(np.float64) + outl[rows].astype(np.float64))
+
+
+# ---- the commit of a measurement parcel: mcp_parcel_commit_host and the numpy restatement --------------------------------------------------
+def parcel_entries(lane, row, uv, level, key=None):
+    """PARCEL_ENTRY_DTYPE records from columns (key: zeros when not given)."""
+    n = len(np.asarray(lane))
+    e = np.zeros(n, dtype=PARCEL_ENTRY_DTYPE)
+    e["lane"], e["row"], e["level"] = _i32(lane, (n,)), _i32(row, (n,)), _i32(level, (n,))
+    e["uv"] = _f64(uv).reshape(n, 2)
+    if key is not None:
+        e["key"] = _i32(key, (n,))
+    return e
+
+
+def _parcel_args(entries, keys, pt_flags, src_mkf, src_cam, lane_mkf, lane_cam):
+    e = np.ascontiguousarray(entries, dtype=PARCEL_ENTRY_DTYPE)
+    k, pf = _i32(keys), _i32(pt_flags)
+    sm, sc = _i32(src_mkf, pf.shape), _i32(src_cam, pf.shape)
+    lm = _i32(lane_mkf)
+    return e, k, pf, sm, sc, lm, _i32(lane_cam, lm.shape)
+
+
+def parcel_commit_host(entries, keys, pt_flags, src_mkf, src_cam, lane_mkf, lane_cam, cross_camera=1, source=SRC_TRACKER, first=0):
+    """mcp_parcel_commit_host: the commit of parcel `entries` (PARCEL_ENTRY_DTYPE) against a map given as plain arrays -- keys: the table's key
+    column now; pt_flags / src_mkf / src_cam: the graph columns written so far (rows past them are bad).  Returns (verdicts uint8 (n,),
+    dict of mcp_parcel_commit_result, appended records (STORE_ENTRY_DTYPE), lane_appended).  Needs no device.  A refusal raises RuntimeError."""
+    e, k, pf, sm, sc, lm, lc = _parcel_args(entries, keys, pt_flags, src_mkf, src_cam, lane_mkf, lane_cam)
+    n, L = len(e), len(lm)
+    prm, res = ParcelCommitParams(int(cross_camera), int(source)), ParcelCommitResult()
+    vd, out, la = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=STORE_ENTRY_DTYPE), np.zeros(max(L, 1), dtype=np.int32)
+    got = _chk(lib().mcp_parcel_commit_host(n, e.ctypes.data, len(k), k.ctypes.data, len(pf), pf.ctypes.data, sm.ctypes.data, sc.ctypes.data, L, lm.ctypes.data, lc.ctypes.data,
+                                            ctypes.addressof(prm), int(first), vd.ctypes.data, out.ctypes.data, ctypes.addressof(res), la.ctypes.data), "parcel_commit_host")
+    return vd[:n], res.as_dict(), out[:got].copy(), la[:L]
+
+
+def parcel_commit_ref(entries, keys, pt_flags, src_mkf, src_cam, lane_mkf, lane_cam, cross_camera=1, source=SRC_TRACKER, first=0):
+    """The commit in numpy, from the reference: Tracker::RecordMeasurements (src/Tracker.cc:1237-1274: the mbBad and CrossCamera tests) and the
+    sweep of AddMultiKeyFrameFromTopOfQueue (src/MapMaker.cc:407-418), with the two rules a row-indexed table adds in front (a withheld lane;
+    a row recycled for another point).  Per entry the first verdict that applies; the appended records in parcel order.  Returns what
+    parcel_commit_host returns."""
+    e, k, pf, sm, sc, lm, lc = _parcel_args(entries, keys, pt_flags, src_mkf, src_cam, lane_mkf, lane_cam)
+    n, R, Rp = len(e), len(k), len(pf)
+    lane, row = e["lane"].astype(np.int64), e["row"].astype(np.int64)
+    if n and (lane.min() < 0 or lane.max() >= len(lm)):
+        raise ValueError("parcel_commit_ref: an entry names a lane outside the lane tables")
+    vd = np.full(n, PARCEL_APPENDED, dtype=np.uint8)
+    open_ = np.ones(n, dtype=bool)                         # no verdict yet
+
+    def rule(cond, verdict):
+        hit = open_ & cond
+        vd[hit] = verdict
+        open_[hit] = False
+    mkf_of = lm[lane] if n else np.zeros(0, dtype=np.int32)
+    rule(mkf_of < 0, PARCEL_SKIPPED)
+    in_table = (row >= 0) & (row < R)
+    key_now = np.where(in_table, k[np.clip(row, 0, max(R - 1, 0))] if R else 0, 0)
+    rule(~in_table | (key_now != e["key"]), PARCEL_STALE)
+    has_col = row < Rp
+    rp = np.clip(row, 0, max(Rp - 1, 0))
+    bad = ~has_col | ((pf[rp] & GP_BAD) != 0 if Rp else True)
+    rule(bad, PARCEL_BAD)
+    if not cross_camera:
+        cross = (sm[rp] < 0) | (sc[rp] != lc[lane]) if Rp else np.ones(n, dtype=bool)
+        rule(cross, PARCEL_CROSS)
+    keep = np.flatnonzero(vd == PARCEL_APPENDED)
+    out = np.zeros(len(keep), dtype=STORE_ENTRY_DTYPE)
+    out["uv"], out["mkf"], out["cam"], out["row"], out["level"] = e["uv"][keep], lm[lane[keep]], lc[lane[keep]], e["row"][keep], e["level"][keep]
+    out["source"], out["alive"] = int(source), 1
+    cnt = np.bincount(vd, minlength=5)
+    res = dict(first=int(first), n_appended=int(cnt[PARCEL_APPENDED]), n_skipped_lane=int(cnt[PARCEL_SKIPPED]), n_stale=int(cnt[PARCEL_STALE]), n_bad=int(cnt[PARCEL_BAD]),
+               n_cross=int(cnt[PARCEL_CROSS]))
+    return vd, res, out, np.bincount(lane[keep], minlength=len(lm)).astype(np.int32)[:len(lm)]
 
 
 # ---- the numpy restatement, from the reference -----------------------------------------------------------------------------------------------
@@ -568,6 +680,18 @@ class MapGraph:
             self.base_from_world[s] = bfw
         return res
 
+    def commit_parcel(self, parcel, lane_mkf, lane_cam, cross_camera=1, source=SRC_TRACKER):
+        """mcp_meas_parcel_commit: the entries of `parcel` that are still good, judged by the map as it is now, appended to the store in parcel
+        order.  lane_mkf / lane_cam: the MKF slot (< 0: the lane is withheld) and camera index of each lane.  Returns (dict of
+        mcp_parcel_commit_result, lane_appended)."""
+        lm = _i32(lane_mkf)
+        lc = _i32(lane_cam, lm.shape)
+        prm, res = ParcelCommitParams(int(cross_camera), int(source)), ParcelCommitResult()
+        la = np.zeros(max(len(lm), 1), dtype=np.int32)
+        _chk(self._L.mcp_meas_parcel_commit(self._h, parcel._h, len(lm), lm.ctypes.data, lc.ctypes.data, ctypes.addressof(prm), ctypes.addressof(res), la.ctypes.data),
+             "meas_parcel_commit")
+        return res.as_dict(), la[:len(lm)]
+
     def select_raw(self, params, copy=True):
         """mcp_map_bundle_select: (SelectResult, mkfs, points, meas)."""
         res = SelectResult()
@@ -583,3 +707,69 @@ class MapGraph:
         if res.status != 0:
             return res, None
         return res, selection_problem(mkfs, points, meas, self.base_from_world, self.cam_from_base, self.cams)
+
+
+class MeasParcel:
+    """A measurement parcel of one MapPointTable (which must outlive it): the measurements of a track call, a ReFind or the caller, kept in
+    device memory with the keys their rows held when the parcel was filled, until MapGraph.commit_parcel appends them to a store."""
+
+    def __init__(self, table):
+        self._L = lib()
+        self.table = table
+        self._h = self._L.mcp_meas_parcel_create(table._h)
+        if not self._h:
+            raise RuntimeError("mcp_meas_parcel_create failed: " + _cb.last_error())
+        table._open_graphs = getattr(table, "_open_graphs", 0) + 1     # as a graph: the table's handle is destroyed after the last parcel's
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.mcp_meas_parcel_destroy(self._h)
+            self._h = None
+            self.table._open_graphs -= 1
+            if self.table._open_graphs == 0 and getattr(self.table, "_close_pending", False):
+                self.table.close()
+
+    def __del__(self):
+        self.close()
+
+    @classmethod
+    def from_track(cls, table):
+        """A new parcel filled from the last track call with bookkeeping on `table`."""
+        p = cls(table)
+        p.fill_from_track()
+        return p
+
+    @classmethod
+    def from_refind(cls, table):
+        """A new parcel filled from the FOUND pairs of the last refind on `table`."""
+        p = cls(table)
+        p.fill_from_refind()
+        return p
+
+    @classmethod
+    def from_host(cls, table, lane, row, uv, level):
+        p = cls(table)
+        p.fill_from_host(lane, row, uv, level)
+        return p
+
+    def fill_from_track(self):
+        return _chk(self._L.mcp_meas_parcel_from_track(self._h), "meas_parcel_from_track")
+
+    def fill_from_refind(self):
+        return _chk(self._L.mcp_meas_parcel_from_refind(self._h), "meas_parcel_from_refind")
+
+    def fill_from_host(self, lane, row, uv, level):
+        ln = _i32(lane)
+        n = len(ln)
+        r, u, lv = _i32(row, (n,)), _f64(uv).reshape(n, 2), _i32(level, (n,))
+        return _chk(self._L.mcp_meas_parcel_from_host(self._h, n, ln.ctypes.data, r.ctypes.data, u.ctypes.data, lv.ctypes.data), "meas_parcel_from_host")
+
+    def __len__(self):
+        return _chk(self._L.mcp_meas_parcel_size(self._h), "meas_parcel_size")
+
+    def entries(self):
+        """The entries read back (PARCEL_ENTRY_DTYPE); waits for the table's stream."""
+        n = len(self)
+        out = np.zeros(max(n, 1), dtype=PARCEL_ENTRY_DTYPE)
+        _chk(self._L.mcp_meas_parcel_get(self._h, n, out.ctypes.data), "meas_parcel_get")
+        return out[:n]

@@ -10,6 +10,7 @@
 //   include/mcptam/Map.h, class Map:          mcp_map_points* mpMapTable; mcp_map_graph* mpMapGraph;      (created with the map, destroyed --
 //                                             graph first -- with it; the table is the tracker's, shim/Tracker_gpu.cc option (b))
 //   include/mcptam/KeyFrame.h, MultiKeyFrame: int mnGraphSlot;     (-1 until the MKF enters the map; slots of trashed MKFs are reused)
+//                                             mcp_meas_parcel* mpMeasParcel;   (the tracker's measurements of a queued MKF, GraphCommitTrackerParcel)
 //   include/mcptam/KeyFrame.h, KeyFrame:      int mnCamIndex;      (index of mCamName in the rig the graph was created with)
 //   include/mcptam/MapPoint.h, MapPoint:      int mnTableRow;      (shim/MapMakerServerBase_gpu.cc has it already)
 //   include/mcptam/BundleAdjusterMulti.h:     std::vector<std::string> mvCamNames (the rig's camera names in graph order); std::vector<int> mvMKFBundleID,
@@ -31,7 +32,10 @@
 #include <mcptam/KeyFrame.h>
 #include <mcptam/LevelHelpers.h>
 #include <mcp_img.h>
+#include <gvars3/instances.h>
 #include <ros/ros.h>
+
+using namespace GVars3;
 
 namespace
 {
@@ -129,8 +133,9 @@ void GraphUploadPoints(Map& map, const std::vector<MapPoint*>& vpPoints)
     ROS_ERROR_STREAM("mcp_map_graph_update_points: " << mcp_last_error());
 }
 
-// KeyFrame::AddMeasurement, batched by the caller that makes many (ReFindBatch, AddStereoMapPoints, the tracker's
-// measurements of a new MKF): one append.  MeasPtrMap guarantees one entry per (keyframe, point), which is what the store relies on.
+// KeyFrame::AddMeasurement, batched by the caller that makes many from host data (AddStereoMapPoints, the initialisers): one append.
+// MeasPtrMap guarantees one entry per (keyframe, point), which is what the store relies on.  The tracker's measurements of a new MKF and
+// ReFindBatch's do not come through here any more: their lists are on the device already (GraphCommitTrackerParcel / GraphCommitReFindParcel).
 void GraphAddMeasurements(Map& map, const std::vector<std::pair<KeyFrame*, MapPoint*> >& vPairs)
 {
   const int n = (int)vPairs.size();
@@ -150,6 +155,72 @@ void GraphAddMeasurements(Map& map, const std::vector<std::pair<KeyFrame*, MapPo
   }
   if(mcp_map_graph_add_meas(map.mpMapGraph, n, vMKF.data(), vCam.data(), vRow.data(), vUV.data(), vLevel.data(), vSource.data()) < 0)
     ROS_ERROR_STREAM("mcp_map_graph_add_meas: " << mcp_last_error());
+}
+
+// The tracker's measurements of an MKF that enters the map (MapMakerServerBase::AddMultiKeyFrameFromTopOfQueue, after GraphUploadMKFs has
+// given it its slot): the parcel Tracker::RecordMeasurements filled when the MKF was made (shim/Tracker_gpu.cc) is committed as the map
+// stands NOW -- the device drops the entries of points that went bad or whose row was given to another point while the MKF waited in the
+// queue, which is the sweep of src/MapMaker.cc:407-418 -- instead of walking mmpMeasurements through GraphAddMeasurements.  The host's
+// Measurement objects stay (the early-outs of ReFind read them); the host's sweep over them stays too, and must agree: it is checked here.
+// Header delta, MultiKeyFrame: mcp_meas_parcel* mpMeasParcel (NULL until RecordMeasurements; destroyed with the MKF, before the table).
+// Lane c is camera index c of the rig; a camera the MKF has no active keyframe of is withheld.
+void GraphCommitTrackerParcel(Map& map, MultiKeyFrame& mkf, const std::vector<std::string>& vCamNames)
+{
+  if(!mkf.mpMeasParcel)
+    return;
+  static gvar3<int> gvnCrossCamera("CrossCamera", 1, HIDDEN|SILENT);
+  const int nc = (int)vCamNames.size();
+  std::vector<int> vLaneMKF(nc, -1), vLaneCam(nc), vAppended(nc, 0);
+  int nHost = 0;
+  for(int c = 0; c < nc; ++c)
+  {
+    vLaneCam[c] = c;
+    KeyFramePtrMap::iterator kf_it = mkf.mmpKeyFrames.find(vCamNames[c]);
+    if(kf_it == mkf.mmpKeyFrames.end() || !kf_it->second->mbActive)
+      continue;
+    vLaneMKF[c] = mkf.mnGraphSlot;
+    nHost += (int)kf_it->second->mmpMeasurements.size();
+  }
+  mcp_parcel_commit_params params;
+  params.cross_camera = *gvnCrossCamera;
+  params.source = (int)Measurement::SRC_TRACKER;
+  mcp_parcel_commit_result res;
+  if(mcp_meas_parcel_commit(map.mpMapGraph, mkf.mpMeasParcel, nc, vLaneMKF.data(), vLaneCam.data(), &params, &res, vAppended.data()) != 0)
+  {
+    ROS_ERROR_STREAM("mcp_meas_parcel_commit: " << mcp_last_error());
+    return;
+  }
+  if(res.n_appended != nHost)
+    ROS_WARN_STREAM("GraphCommitTrackerParcel: the device appended " << res.n_appended << " measurements (" << res.n_stale << " stale, " << res.n_bad << " bad), the keyframes hold " << nHost);
+  mcp_meas_parcel_destroy(mkf.mpMeasParcel);
+  mkf.mpMeasParcel = NULL;
+}
+
+// The measurements of one ReFind batch (MapMakerServerBase::ReFindBatch, shim/MapMakerServerBase_gpu.cc): the FOUND pairs the call left in its
+// pinned block go to the store through the map maker's own parcel, one lane per target keyframe.
+void GraphCommitReFindParcel(Map& map, mcp_meas_parcel* pParcel, const std::vector<KeyFrame*>& vTargets, int nExpected)
+{
+  static gvar3<int> gvnCrossCamera("CrossCamera", 1, HIDDEN|SILENT);
+  if(mcp_meas_parcel_from_refind(pParcel) < 0)
+  {
+    ROS_ERROR_STREAM("mcp_meas_parcel_from_refind: " << mcp_last_error());
+    return;
+  }
+  const int n = (int)vTargets.size();
+  std::vector<int> vLaneMKF(n), vLaneCam(n);
+  for(int t = 0; t < n; ++t)
+  {
+    vLaneMKF[t] = vTargets[t]->mpParent->mnGraphSlot;      // (-1 while the MKF is not in the map: the lane is withheld)
+    vLaneCam[t] = vTargets[t]->mnCamIndex;
+  }
+  mcp_parcel_commit_params params;
+  params.cross_camera = *gvnCrossCamera;
+  params.source = (int)Measurement::SRC_REFIND;
+  mcp_parcel_commit_result res;
+  if(mcp_meas_parcel_commit(map.mpMapGraph, pParcel, n, vLaneMKF.data(), vLaneCam.data(), &params, &res, NULL) != 0)
+    ROS_ERROR_STREAM("mcp_meas_parcel_commit: " << mcp_last_error());
+  else if(res.n_appended != nExpected)
+    ROS_WARN_STREAM("GraphCommitReFindParcel: the device appended " << res.n_appended << " of " << nExpected << " measurements");
 }
 
 // KeyFrame::EraseMeasurementOfPoint (src/KeyFrame.cc:749 on) as HandleOutliers (src/MapMakerServerBase.cc:1198-1238) and
@@ -321,7 +392,7 @@ void BundleAdjusterMulti::AdjustAndUpdate(ChainBundle& multiBundle)
 }
 
 // MultiKeyFrame enters the map (src/MapMakerServerBase.cc:219, 392): MultiKeyFrame::RefreshSceneDepthRobust at its own pose, after GraphUploadMKFs
-// and GraphAddMeasurements have put it and its measurements into the graph.  One mcp_graph_refresh_depth; the graph keeps the new means.
+// and GraphCommitTrackerParcel (GraphAddMeasurements for an initialiser's) have put it and its measurements into the graph.  One mcp_graph_refresh_depth; the graph keeps the new means.
 void GraphRefreshSceneDepth(Map& map, MultiKeyFrame& mkf, const std::vector<std::string>& vCamNames)
 {
   const int nc = (int)vCamNames.size();

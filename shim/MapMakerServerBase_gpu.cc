@@ -11,7 +11,8 @@
 // mcp_patch_sequences, the re-find loops to mcp_map_refind, which reads the points from the resident map-point table (include/mcp_img.h).
 // The map-side bookkeeping (measurement maps, never-retry sets, failure queue) is the reference's, unchanged.
 // Needs KeyFrame::mpDev (shim/KeyFrame_gpu.cc), shim/CameraExport.h, and the table with MapPoint::mnTableRow (shim/Tracker_gpu.cc: the map
-// maker holds the same mcp_map_points* as mpMapTable).
+// maker holds the same mcp_map_points* as mpMapTable), and in class MapMakerServerBase: mcp_meas_parcel* mpReFindParcel
+// (mcp_meas_parcel_create(mpMapTable) where the table is handed over; mcp_meas_parcel_destroy before the table goes).
 #include <mcptam/MapMakerServerBase.h>
 #include <mcptam/MapPoint.h>
 #include <mcptam/KeyFrame.h>
@@ -65,6 +66,8 @@ int KeyOf(const MapPoint* pPoint)   // identity of a MapPoint object (the refere
   return (int)(reinterpret_cast<uintptr_t>(pPoint) >> 4);
 }
 }  // namespace
+
+void GraphCommitReFindParcel(Map& map, mcp_meas_parcel* pParcel, const std::vector<KeyFrame*>& vTargets, int nExpected);      // shim/BundleAdjusterBase_gpu.cc
 
 // ---- AddPointEpipolar, first loop (:745-795): every hypothesised position along the epipolar arc through ONE finder, in order.
 // vMapPointPositions: (world position, position in the target camera) per step, as built at :706-723; `point` is the probe MapPoint
@@ -250,6 +253,11 @@ int MapMakerServerBase::ReFindBatch(std::vector<std::pair<KeyFrame*, MapPoint*> 
       ROS_BREAK();
     kf.AddMeasurement(&point, pMeas);
   }
+  // the same measurements into the map graph's store, from the pinned block on the device (shim/BundleAdjusterBase_gpu.cc): a parcel the map
+  // maker keeps (mpReFindParcel, created next to mpMapTable, destroyed before it), one lane per target keyframe.  The Measurement objects
+  // above stay: the early-outs at the top of this function read them.
+  if(nMeas > 0)
+    GraphCommitReFindParcel(mMap, mpReFindParcel, vKFs, nMeas);
   return nMeas;
 }
 

@@ -689,6 +689,52 @@ bool Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
   return true;
 }
 
+// ---- RecordMeasurements of a frame tracked on the device (src/Tracker.cc:1237-1274) -------------------------------------------------------
+// Runs when the tracker has decided to hand the current MKF to the map maker, behind the TrackMapOnDevice of the same frame, so the
+// measurement views still show that frame.  Two things happen:
+//   * the Measurement objects of the keyframes, as before, from the views (camera c's found items in item order) -- the map maker's own
+//     bookkeeping and the early-outs of ReFind read them;
+//   * the same list goes into a measurement parcel that the MKF owns (MultiKeyFrame::mpMeasParcel), ON THE DEVICE and without a wait: the MKF
+//     now waits in the map maker's queue while this tracker goes on tracking on the same table and overwrites the views.  The map maker
+//     commits the parcel when the MKF enters the map (GraphCommitTrackerParcel, shim/BundleAdjusterBase_gpu.cc); what happened to the points
+//     in between is judged there, on the device.
+// An MKF that never reaches the map destroys its parcel with itself.
+void Tracker::RecordMeasurements()
+{
+  static gvar3<int> gvnCrossCamera("CrossCamera", 1, HIDDEN|SILENT);
+  const bool bCrossCamera = *gvnCrossCamera != 0;
+  const int nCams = (int)mvCurrCamNames.size();
+  for(int c = 0; c < nCams; ++c)
+  {
+    const std::string& camName = mvCurrCamNames[c];
+    KeyFrame& kf = *mpCurrentMKF->mmpKeyFrames[camName];
+    int nMeas = 0;
+    const mcp_track_meas* pMeas = mcp_track_map_meas_view(mpMapTable, c, &nMeas);
+    for(int k = 0; k < nMeas; ++k)
+    {
+      const mcp_track_meas& m = pMeas[k];
+      MapPoint& point = *mvMapTableRows[m.row];
+      if(point.mbBad)
+        continue;
+      if(!bCrossCamera && point.mpPatchSourceKF->mCamName != camName)
+        continue;
+      Measurement* pNew = new Measurement;
+      pNew->eSource = Measurement::SRC_TRACKER;
+      pNew->nLevel = m.level;
+      pNew->bSubPix = m.subpix != 0;
+      pNew->v2RootPos = makeVector(m.found_pos[0], m.found_pos[1]);
+      kf.AddMeasurement(&point, pNew);
+    }
+  }
+  if(!mpCurrentMKF->mpMeasParcel)
+    mpCurrentMKF->mpMeasParcel = mcp_meas_parcel_create(mpMapTable);
+  if(!mpCurrentMKF->mpMeasParcel || mcp_meas_parcel_from_track(mpCurrentMKF->mpMeasParcel) < 0)
+  {
+    ROS_FATAL_STREAM("Tracker::RecordMeasurements: "<<mcp_last_error());
+    ros::shutdown();
+  }
+}
+
 // ---- TrackFrame's tracking branch in one submission (include/mcp_img.h, mcp_track_frame_motion) ------------------------------------------
 // Replaces, for a frame with a good map, src/Tracker.cc:303-330 (MakeKeyFrame_Lite and the SmallBlurryImages of every camera), :431-434
 // (ApplyMotionModel, TrackMap, UpdateMotionModel) with :1516-1555 and :1687-1749 behind them.  The tracker's SBIs live in the
