@@ -264,6 +264,10 @@ int mcp_ba_debug_systems(mcp_ba*, int nsys, const double* lambdas, double* out);
 #define MCP_BA_SCHUR_NONE  0    /* no free point or no group: nothing is eliminated by a group kernel */
 #define MCP_BA_SCHUR_4     1    /* k_schur4: all systems of a batch in one workgroup per group (groups of at most 13 poses) */
 #define MCP_BA_SCHUR_GROUP 2    /* k_schur_group: one workgroup per group and system, 16-point chunks */
+#define MCP_BA_ASM_NONE  0      /* no free pose: no reduced system */
+#define MCP_BA_ASM_PAIR  1      /* k_assemble: one wavefront per 6 x 6 pose block and system (MCP_BA_ASM_PAIR=0 forces the tiles) */
+#define MCP_BA_ASM_TILES 2      /* k_assemble_tiles: one workgroup per 32 x 32 tile; always with generic-path points (nbig > 0) */
+#define MCP_BA_ASM_LONG  3      /* k_assemble_long: eight lanes per entry (long lists of staged blocks) */
 typedef struct mcp_ba_structure {
   int ngroup, grp_pts, nbig, nfl, np;   /* groups, points per group the layout allows (16 / 64), points on the generic path, free points, 6 x free poses */
   int grp_points_max, grp_points_min;   /* most / fewest points in one group (0 without groups) */
@@ -273,8 +277,9 @@ typedef struct mcp_ba_structure {
   int lin_kernel;                       /* MCP_BA_LIN_* */
   int lin_generic;                      /* nonzero: k_linearize also runs (generic-path points) */
   int schur_kernel;                     /* MCP_BA_SCHUR_* */
-  int asm_long;                         /* nonzero: k_assemble_long instead of k_assemble */
+  int asm_long;                         /* nonzero: k_assemble_long (asm_kernel == MCP_BA_ASM_LONG) */
   int max_systems;                      /* most systems one batch may hold for this handle */
+  int asm_kernel;                       /* MCP_BA_ASM_* */
 } mcp_ba_structure;
 int mcp_ba_debug_structure(mcp_ba*, mcp_ba_structure* out);
 

@@ -51,7 +51,7 @@ class McpBaTiming(ctypes.Structure):
 class McpBaStructure(ctypes.Structure):
     _fields_ = [(f, ctypes.c_int) for f in (
         "ngroup", "grp_pts", "nbig", "nfl", "np", "grp_points_max", "grp_points_min", "grp_poses_max", "grp_no_pose",
-        "grp_blk_max", "grp_inc_max", "lin_kernel", "lin_generic", "schur_kernel", "asm_long", "max_systems")]
+        "grp_blk_max", "grp_inc_max", "lin_kernel", "lin_generic", "schur_kernel", "asm_long", "max_systems", "asm_kernel")]
 
 
 class McpBaHeadReport(ctypes.Structure):
@@ -69,6 +69,7 @@ class McpBaTrialReport(ctypes.Structure):
 HEAD_ROUTES = ("plain", "ranks", "ride", "small", "ahead", "large")      # MCP_BA_HEAD_* of include/mcp_ba.h
 LIN_KERNEL_NAMES = ("none", "quad", "pipe", "group")          # MCP_BA_LIN_* of include/mcp_ba.h
 SCHUR_KERNEL_NAMES = ("none", "schur4", "schur_group")        # MCP_BA_SCHUR_*
+ASM_KERNEL_NAMES = ("none", "pair", "tiles", "long")          # MCP_BA_ASM_*
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
 
@@ -387,7 +388,8 @@ class ChainBundle:
     def DebugStructure(self):
         """The shape the structure build gave the map and the kernels the next linearisation / reduced-system build launch for
         it (read-only test hook, mcp_ba_debug_structure): the counts of mcp_ba_structure, `lin_kernel` as "quad" / "pipe" /
-        "group" / "none", `schur_kernel` as "schur4" / "schur_group" / "none", `lin_generic` and `asm_long` as bools."""
+        "group" / "none", `schur_kernel` as "schur4" / "schur_group" / "none", `asm_kernel` as
+        "pair" (k_assemble) / "tiles" (k_assemble_tiles) / "long" (k_assemble_long) / "none", `lin_generic` and `asm_long` as bools."""
         st = McpBaStructure()
         if self._L.mcp_ba_debug_structure(self._h, ctypes.byref(st)) < 0:
             raise RuntimeError("mcp_ba_debug_structure: " + last_error())
@@ -396,6 +398,7 @@ class ChainBundle:
         d["schur_kernel"] = SCHUR_KERNEL_NAMES[d["schur_kernel"]]
         d["lin_generic"] = bool(d["lin_generic"])
         d["asm_long"] = bool(d["asm_long"])
+        d["asm_kernel"] = ASM_KERNEL_NAMES[d["asm_kernel"]]
         return d
 
     def DebugHead(self, route, chi2, prev_median):

@@ -11,7 +11,8 @@
 //                       and flushed once per group.
 //   k_schur_group     : S -= W V^-1 W^T as a dense zero-filled (96 x 3*16)(3*16 x 96) product
 //                       per 16-point chunk on the fp64 matrix cores (v_mfma_f64_16x16x4).
-//   k_assemble        : the reduced system, tile by tile, from the groups' staged blocks.
+//   k_assemble        : the reduced system, pose block by pose block, from the groups' staged blocks
+//                       (k_assemble_tiles: tile by tile, the fall-back; k_assemble_long: long lists).
 //
 // Fixed-order accumulation (hard part 2): a group never adds into the global system.  It writes the
 // structurally non-zero 6x6 blocks of its local tile (which local pose pairs those are is known at Prepare()) to its own
@@ -863,7 +864,22 @@ struct AsmPlan {
   const int* pair_id;             // [nfp*nfp] (a, b), a >= b  ->  pair index or -1
   const int* pr_start;            // [npairs+1] staged blocks of the pair: [pr_start[p], pr_start[p+1]), ascending group
   const int* po_start;            // [nfp+1] staged rhs rows of the pose, ascending group
+  int ntasks, nwalk;              // k_assemble's task table (int4 per task, below; longest list first; the first nwalk have a list to walk), or 0: the map takes another kernel
+  const int4* tasks;
 };
+
+// A task of k_assemble is one 6 x 6 pose block (a, b) of S or ten poses of the right-hand-side row.  The block's entries lie in
+// up to four 32 x 32 tiles (it straddles a tile seam when 6a or 6b is 30 mod 32 ...): `mask` says which of these quadrants are
+// tiles of the factorisation plan -- bit 2*(row tile differs from 6a's) + (column tile differs from 6b's) -- and only those
+// are written, so the kernel writes exactly the entries k_assemble_tiles writes.  A task is an int4 {word, k0, n, 0}: the
+// block's list of staged blocks [k0, k0 + n) straight from the table (no hop through pair_id and pr_start); the tasks without a
+// list -- fill-in tiles, structural zeros, the upper part of diagonal tiles: most of them -- sort to the end of the table and go
+// ASMP_ZB to a workgroup.
+constexpr int ASMP_ZB = 8;
+constexpr int ASMP_POSE_BITS = 11;                       // a, b < 2048 (6P <= 6144: at most 1024 free poses)
+constexpr int ASMP_RHS = 1 << (2*ASMP_POSE_BITS + 4);    // right-hand-side task: poses a .. a + ASMP_RHS_POSES - 1
+constexpr int ASMP_RHS_POSES = 10;                       // (60 of a wavefront's 64 lanes: lane = pose*6 + r)
+__host__ __device__ inline int asmp_task(int a, int b, int mask) { return a | (b << ASMP_POSE_BITS) | (mask << 2*ASMP_POSE_BITS); }
 
 #ifndef ASM_NT
 #define ASM_NT 1024      // one entry of the 32 x 32 tile per thread: every entry's walk over its staged contributions is a chain of memory round trips,
@@ -871,7 +887,7 @@ struct AsmPlan {
 // (Round 5 measured one thread per entry for ALL systems of a batch -- the pose-pose sum and the list walk shared, a quarter of the
 //  workgroups: 2.87 vs 2.34 ms of Schur + assembly per 20 iterations.  Fewer, longer walks hide less latency; dropped.)
 __global__ void __launch_bounds__(ASM_NT)
-k_assemble(AsmPlan A, int np, const double* __restrict__ stU, const double* __restrict__ stb,
+k_assemble_tiles(AsmPlan A, int np, const double* __restrict__ stU, const double* __restrict__ stb,
            const double* __restrict__ stS, const double* __restrict__ str,
            const double* __restrict__ Ubig /* dense np x np + np contributions of the points outside the groups, or null */,
            double* __restrict__ S, SysBatch sb) {
@@ -932,6 +948,86 @@ k_assemble(AsmPlan A, int np, const double* __restrict__ stU, const double* __re
     }
     S[(size_t)row*np + col] = v;
   }
+}
+
+// ---- the same sums, one wavefront per 6 x 6 pose block and system.  k_assemble_tiles gives a wavefront two rows of a tile: 64
+// entries of 5-6 different pose blocks, so every load of its walk touches ~12 cache lines with 48 useful bytes each, and a diagonal
+// tile's sixteen wavefronts push ~15 k line requests through one compute unit.  Here lane l < 36 is entry (l/6, l%6) of ONE block and
+// reads stU / stS[(k0 + j)*36 + l]: a load is 288 contiguous bytes, sixteen contributions are in flight, and the blocks of a
+// tile are spread over the device.  Every entry is the same chain of additions as above (u and w from 0.0 in list order, u - w,
+// lambda on the diagonal): bit-identical.  The task table (mcp_ba::asm_task_table) covers every entry k_assemble_tiles writes.
+// u += pu[0], pu[STRIDE], ... and w += pw[...] over n terms in order; 2 x 16 loads in flight, then 2 x 4, then one by one
+template <int STRIDE>
+__device__ inline void asm_walk2(const double* __restrict__ pu, const double* __restrict__ pw, int n, double& u, double& w) {
+  int k = 0;
+  for (; k + 16 <= n; k += 16, pu += 16*STRIDE, pw += 16*STRIDE) {
+    double uu[16], ww[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { uu[j] = pu[STRIDE*j]; ww[j] = pw[STRIDE*j]; }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { u += uu[j]; w += ww[j]; }
+  }
+  for (; k + 4 <= n; k += 4, pu += 4*STRIDE, pw += 4*STRIDE) {
+    const double u0 = pu[0], u1 = pu[STRIDE], u2 = pu[2*STRIDE], u3 = pu[3*STRIDE];
+    const double w0 = pw[0], w1 = pw[STRIDE], w2 = pw[2*STRIDE], w3 = pw[3*STRIDE];
+    u += u0; u += u1; u += u2; u += u3;
+    w += w0; w += w1; w += w2; w += w3;
+  }
+  for (; k < n; ++k, pu += STRIDE, pw += STRIDE) { u += pu[0]; w += pw[0]; }
+}
+// A workgroup is one task, wavefront q of it system q of the batch (64 x nsys threads): the systems share the pose part (stU,
+// stb), and wavefronts of one workgroup that ask for the same lines side by side are served by one fetch.  Measured at the metric
+// size, four systems (profiles/r06/README.md): four tasks per workgroup on a grid (tasks/4, nsys), list bounds through pair_id
+// and pr_start 21.5 us, 82 MB fetched; a task's systems in one workgroup 19.0 us, 52 MB; list bounds in the task and the tasks
+// without a list ASMP_ZB to a workgroup 15.0 us (51 MB; k_assemble_tiles: 31.4 us, 96 MB): what was left after the lines were
+// coalesced was the number of wavefronts and their dependent hops, most of them for blocks that are written as zeros.
+__device__ inline void asmp_store(int word, int lane, int np, double u, double w, double lam, double* __restrict__ S) {
+  const int a = word & ((1 << ASMP_POSE_BITS) - 1), b = (word >> ASMP_POSE_BITS) & ((1 << ASMP_POSE_BITS) - 1), mask = (word >> 2*ASMP_POSE_BITS) & 15;
+  const int r = lane/6, c = lane - 6*r, row = 6*a + r, col = 6*b + c;
+  const int quad = 2*((row >> 5) != ((6*a) >> 5)) + ((col >> 5) != ((6*b) >> 5));
+  if (!((mask >> quad) & 1)) return;                     // not a tile of the plan: nothing reads there, k_assemble_tiles writes nothing
+  double v = 0.0;
+  if (col <= row) {                                      // (the upper part of a diagonal tile is never read: zero)
+    v = u - w;
+    if (row == col) v += lam;
+  }
+  S[(size_t)row*np + col] = v;
+}
+__global__ void __launch_bounds__(64*MAX_SYS)
+k_assemble(AsmPlan A, int np, const double* __restrict__ stU, const double* __restrict__ stb,
+           const double* __restrict__ stS, const double* __restrict__ str, double* __restrict__ S, SysBatch sb) {
+  const int q = (int)threadIdx.x >> 6, lane = threadIdx.x & 63;
+  S += q*sb.sstride; stS += q*sb.ststride; str += q*sb.strstride;
+  const double lam = sb.lambda_init[q];
+  if ((int)blockIdx.x >= A.nwalk) {                      // ASMP_ZB tasks without a list: u = w = 0.0
+    if (lane >= 36) return;
+    const int t0 = A.nwalk + ((int)blockIdx.x - A.nwalk)*ASMP_ZB;
+    int word[ASMP_ZB];
+#pragma unroll
+    for (int i = 0; i < ASMP_ZB; ++i) word[i] = t0 + i < A.ntasks ? A.tasks[t0 + i].x : -1;
+#pragma unroll
+    for (int i = 0; i < ASMP_ZB; ++i) if (word[i] >= 0) asmp_store(word[i], lane, np, 0.0, 0.0, lam, S);
+    return;
+  }
+  const int4 task = A.tasks[blockIdx.x];
+  if (task.x & ASMP_RHS) {                               // right-hand side and, behind it, the plain J^T r
+    const int a = (task.x & ((1 << ASMP_POSE_BITS) - 1)) + lane/6, r = lane%6;
+    if (lane >= 6*ASMP_RHS_POSES || a >= A.nfp) return;
+    const int k0 = A.po_start[a], n = A.po_start[a + 1] - k0;
+    double b = 0.0, sr = 0.0;
+    asm_walk2<6>(stb + (size_t)k0*6 + r, str + (size_t)k0*6 + r, n, b, sr);
+    const int col = 6*a + r;
+    const size_t n2 = (size_t)np*np;
+    S[n2 + col] = b - sr;
+    S[n2 + np + col] = b;
+    return;
+  }
+  if (lane >= 36) return;
+  double u = 0.0, w = 0.0;
+  // (a list belongs to a block a >= b; of a diagonal block only c <= r carries a sum)
+  const int a = task.x & ((1 << ASMP_POSE_BITS) - 1), b = (task.x >> ASMP_POSE_BITS) & ((1 << ASMP_POSE_BITS) - 1);
+  if (a != b || lane%6 <= lane/6) asm_walk2<36>(stU + (size_t)task.y*36 + lane, stS + (size_t)task.y*36 + lane, task.z, u, w);
+  asmp_store(task.x, lane, np, u, w, lam, S);
 }
 
 // ---- the same assembly for systems whose entries are sums of MANY staged contributions -- a BundleAdjustRecent window: a handful of

@@ -369,7 +369,7 @@ struct StructEntry {
   std::vector<unsigned char> pose_active, pt_active, pat;
   std::vector<int> chol_segs;
   int nfp = 0, nfl = 0, np = 0, nx = 0, nsp = 0, ninc = 0, nslot = 0, ngroup = 0, nbig = 0, grp_pts = 0, grp_blk_max = 0, grp_inc_max = 0, nrhs_rows = 0;
-  size_t nstage = 0; bool asm_long = false, sch4_ok = false, sch4_order = false;
+  size_t nstage = 0; bool asm_long = false, sch4_ok = false, sch4_order = false; int n_asm_walk = 0;
   double m_total = 0, nfl_total = 0, schur_mfma = 0, schur_flops = 0;
   std::vector<size_t> counts;            // element count of every array of the packed block, in layout order
   // for the adoption of this structure by a map that holds the same poses, points and chains and a SUBSET of these measurements (the
@@ -512,7 +512,7 @@ struct mcp_ba {
   DevBuf<double> d_red;     // [S (np*np) | rhs (np) | bp = J^T r (np)]   (the all-reduced block)
   // staged local tiles of the groups and the assembly plan (ba_group.h: fixed-order accumulation)
   DevBuf<double> d_stU, d_stb, d_stS, d_str, d_udiag;
-  DevBuf<int> d_g_blk0, d_asm_tiles, d_pair_id, d_pr_start, d_blk_dst, d_po_start, d_rhs_dst;
+  DevBuf<int> d_g_blk0, d_asm_tiles, d_pair_id, d_pr_start, d_blk_dst, d_po_start, d_rhs_dst, d_asm_tasks;
   DevBuf<unsigned char> d_blk_pair;
   int grp_blk_max = 0;            // most staged blocks of any group (sizes the LDS tile of k_linearize_group)
   int head_ahead_for = -1;        // state buffer whose iteration head is already on the main stream (small bundles), or -1
@@ -573,6 +573,8 @@ struct mcp_ba {
   DevBuf<int> d_g_order, d_sp_unk;              // launch order of the groups in k_schur4 (heaviest first; only when they outnumber the slots), free-point index per sorted point
   bool sch4_order = false;
   bool asm_long = false;          // the pose pairs' lists of staged blocks are long (a few free poses staged by every group): k_assemble_long
+  bool asm_pair = false;          // k_assemble (a wavefront per pose block, task table d_asm_tasks) instead of k_assemble_tiles: not with asm_long or nbig; MCP_BA_ASM_PAIR=0 forces the tiles
+  int n_asm_tasks = 0, n_asm_walk = 0;      // tasks of the table, those with a list to walk (0 when the structure takes k_assemble_long or has generic-path points: no table)
   int grp_inc_max = 0;            // most point-pose incidences of any group (the W area of k_linearize_quad)
   size_t nstage = 0;        // staged 6x6 blocks over all groups
   int nrhs_rows = 0;        // staged rhs rows (6 doubles each) over all groups
@@ -2147,7 +2149,7 @@ struct mcp_ba::BlockLayout {
   std::vector<Item> items; std::vector<size_t> counts;      // (counts: what a cache hit replays the layout from)
   size_t total = 0, staged = 0; char* base = nullptr;
   static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-  std::vector<int> chain_len, chain_pose, pose_unk, pt_chain, pt_unk, sp_unk, g_order; std::vector<unsigned char> pt_fixed;
+  std::vector<int> chain_len, chain_pose, pose_unk, pt_chain, pt_unk, sp_unk, g_order, asm_tasks; std::vector<unsigned char> pt_fixed;
   std::vector<int, NoInitAlloc<int>> m_last;
 };
 
@@ -2178,6 +2180,7 @@ void mcp_ba::launch_choices(StructBuild& B) {
   schur_mfma = schur_flops = 0;
   if (hit) { schur_mfma = hit->schur_mfma; schur_flops = hit->schur_flops; }
   else if ((prm.profile || cache_insert) && ngroup) schur_work(B);       // (a Prepare() that fills the structure cache computes it for whoever adopts the entry)
+  n_asm_walk = hit ? hit->n_asm_walk : 0;          // (a cold build counts them in small_arrays())
   if (hit) asm_long = hit->asm_long;
   else {
     // long lists of staged blocks per pose pair (mean >= 48: a handful of free poses that every group stages) go through k_assemble_long
@@ -2185,6 +2188,55 @@ void mcp_ba::launch_choices(StructBuild& B) {
     asm_long = npairs > 0 && nstage >= 48*npairs;
     if (const char* e = getenv("MCP_BA_ASM_LONG")) asm_long = atoi(e) != 0 && npairs > 0;
   }
+  // a wavefront per pose block (k_assemble) unless the lists are long or generic-path points add Ubig entry by entry; the task table
+  // belongs to the structure (a cache entry holds it whatever the knob said when it was built), the knob to this Prepare()
+  asm_pair = np > 0 && !asm_long && !nbig && env_on("MCP_BA_ASM_PAIR", true);
+}
+
+// k_assemble's task table (ba_group.h: asmp_task), from the staging plan and the tiles of the factorisation plan: one task for every
+// 6 x 6 pose block with an entry k_assemble_tiles writes -- blocks (a, b), a >= b, in or across plan tiles, with or without staged
+// contributions (fill-in tiles, structural zeros); the blocks a < b inside diagonal tiles (zeros) -- and one per ten poses of the
+// right-hand-side row (its tiles are all in the plan).  Longest list first, so that the launch ends on short tasks.
+static int asm_task_table(int nfp, int np, const int* pair_id, const int* pr_start, const int* po_start, const std::vector<int>& tiles, std::vector<int>& tasks) {
+  tasks.clear();
+  if (nfp <= 0 || nfp >= (1 << ASMP_POSE_BITS)) return 0;
+  const int ntc = (np + CH_NB - 1)/CH_NB, ntr = np/CH_NB + 1;
+  static_assert(CH_NB == 32, "k_assemble's quadrant test shifts by 5");
+  std::vector<unsigned char> in_plan((size_t)ntr*ntc, 0);
+  for (int t : tiles) in_plan[(size_t)(t >> 16)*ntc + (t & 0xffff)] = 1;
+  auto tile = [&](int ti, int tj) { return ti >= tj && in_plan[(size_t)ti*ntc + tj]; };
+  std::vector<int> word, first, len;
+  for (int a = 0; a < nfp; ++a) {
+    const int ti0 = (6*a)/CH_NB, ti1 = (6*a + 5)/CH_NB;
+    for (int b = 0; b < nfp; ++b) {
+      const int tj0 = (6*b)/CH_NB, tj1 = (6*b + 5)/CH_NB;
+      int mask = tile(ti0, tj0) ? 1 : 0;
+      if (tj1 != tj0 && tile(ti0, tj1)) mask |= 2;
+      if (ti1 != ti0 && tile(ti1, tj0)) mask |= 4;
+      if (ti1 != ti0 && tj1 != tj0 && tile(ti1, tj1)) mask |= 8;
+      if (!mask) continue;
+      const int pid = a >= b ? pair_id[(size_t)a*nfp + b] : -1;
+      word.push_back(asmp_task(a, b, mask)); first.push_back(pid >= 0 ? pr_start[pid] : 0); len.push_back(pid >= 0 ? pr_start[pid + 1] - pr_start[pid] : 0);
+    }
+  }
+  for (int a = 0; a < nfp; a += ASMP_RHS_POSES) {
+    int n = 0;
+    for (int p = a; p < std::min(a + ASMP_RHS_POSES, nfp); ++p) n = std::max(n, po_start[p + 1] - po_start[p]);
+    word.push_back(asmp_task(a, 0, 0) | ASMP_RHS); first.push_back(0); len.push_back(std::max(n, 1));      // (never among the tasks without a list)
+  }
+  // (stable counting sort by descending length)
+  int lmax = 0; for (int n : len) lmax = std::max(lmax, n);
+  std::vector<int> pos(lmax + 2, 0);
+  for (int n : len) pos[lmax - n + 1]++;
+  for (int i = 0; i <= lmax; ++i) pos[i + 1] += pos[i];
+  tasks.resize(4*word.size());          // int4 {word, first staged block, blocks, 0}
+  int nwalk = 0;
+  for (size_t i = 0; i < word.size(); ++i) {
+    int* t = &tasks[4*(size_t)pos[lmax - len[i]]++];
+    t[0] = word[i]; t[1] = first[i]; t[2] = (word[i] & ASMP_RHS) ? 0 : len[i]; t[3] = 0;
+    if (len[i] > 0) ++nwalk;
+  }
+  return nwalk;
 }
 
 // the work of one system's Schur launch, for the bench line: non-empty 16-row tiles of every 16-point chunk -> tile pairs x 12
@@ -2241,6 +2293,8 @@ void mcp_ba::small_arrays(StructBuild& B, BlockLayout& L) {
     for (int gi = 0; gi < ngroup; ++gi) L.g_order[gi] = gi;
     std::stable_sort(L.g_order.begin(), L.g_order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
   }
+  // k_assemble's tasks (a structure that takes k_assemble_long or has generic-path points gets none; neither depends on a knob of this call alone)
+  if (!hit && np > 0 && !asm_long && !nbig) n_asm_walk = asm_task_table(nfp, np, H.pair_id.data(), H.pr_start.data(), H.po_start.data(), plan.all_tiles, L.asm_tasks);
   L.m_last.resize(hit ? 0 : nmeas);
   if (!hit) {
     auto& m_last = L.m_last; const int T = finish_threads(nmeas);
@@ -2281,6 +2335,8 @@ int mcp_ba::layout_block(StructBuild& B, BlockLayout& L) {
   add(d_asm_tiles, plan.all_tiles, false); add(d_pair_id, H.pair_id, true); add(d_pr_start, H.pr_start, true); add(d_blk_dst, H.blk_dst, true);
   add(d_po_start, H.po_start, true); add(d_rhs_dst, H.rhs_dst, true);
   add(d_sp_unk, L.sp_unk, false); add(d_g_order, L.g_order, false); add(d_m_last, L.m_last, false);
+  add(d_asm_tasks, L.asm_tasks, false); n_asm_tasks = (int)(L.counts.back()/4);
+  asm_pair = asm_pair && n_asm_tasks > 0;
   if (d_struct.alloc(total)) return -1;
   char* const base = L.base = d_struct.p;
   auto fix = [&](auto& dbuf) { dbuf.p = reinterpret_cast<decltype(dbuf.p)>(base + reinterpret_cast<size_t>(dbuf.p)); };
@@ -2289,7 +2345,7 @@ int mcp_ba::layout_block(StructBuild& B, BlockLayout& L) {
   fix(d_slot_unk); fix(d_slot_inc); fix(d_l_i0); fix(d_l_i1); fix(d_inc_unk); fix(d_fl_point); fix(d_sp_pt); fix(d_sp_m);
   fix(d_sp_i); fix(d_sp_big); fix(d_m_sp); fix(d_l_sp); fix(d_g_sp0); fix(d_g_pose); fix(d_slot_lp); fix(d_slot_first);
   fix(d_inc_lp); fix(d_inc_mixed); fix(d_g_blk0); fix(d_blk_pair); fix(d_asm_tiles); fix(d_pair_id); fix(d_pr_start); fix(d_blk_dst);
-  fix(d_po_start); fix(d_rhs_dst); fix(d_sp_unk); fix(d_g_order); fix(d_m_last);
+  fix(d_po_start); fix(d_rhs_dst); fix(d_sp_unk); fix(d_g_order); fix(d_m_last); fix(d_asm_tasks);
   return 0;
 }
 
@@ -2370,7 +2426,7 @@ int mcp_ba::make_cache_entry(StructBuild& B, BlockLayout& L) {
   e->fp_pose = fp_pose; e->fl_point = fl_point; e->perm = perm; e->pat = last_pat; e->chol_segs = chol_segs;
   e->nfp = nfp; e->nfl = nfl; e->np = np; e->nx = nx; e->nsp = nsp; e->ninc = ninc; e->nslot = nslot; e->ngroup = ngroup; e->nbig = nbig;
   e->grp_pts = grp_pts; e->grp_blk_max = grp_blk_max; e->grp_inc_max = grp_inc_max; e->nrhs_rows = nrhs_rows; e->nstage = nstage;
-  e->asm_long = asm_long; e->sch4_ok = sch4_ok; e->sch4_order = sch4_order; e->m_total = m_total; e->nfl_total = nfl_total;
+  e->asm_long = asm_long; e->n_asm_walk = n_asm_walk; e->sch4_ok = sch4_ok; e->sch4_order = sch4_order; e->m_total = m_total; e->nfl_total = nfl_total;
   e->schur_mfma = schur_mfma; e->schur_flops = schur_flops; e->counts = L.counts;
   e->dblock = (char*)DevCache::get().take(std::max<size_t>(total, 1), &e->dcap, &e->ddev);
   if (e->dblock) {
@@ -2510,7 +2566,7 @@ int mcp_ba::fill_param_blocks(int nmeas) {
   P.slot_first = d_slot_first.p; P.inc_lp = d_inc_lp.p; P.inc_mixed = d_inc_mixed.p;
   P.g_blk0 = d_g_blk0.p; P.blk_pair = d_blk_pair.p; P.blk_dst = d_blk_dst.p; P.rhs_dst = d_rhs_dst.p; P.sp_unk = d_sp_unk.p; P.m_last = d_m_last.p;
   A.nfp = nfp; A.ntiles = (int)plan.all_tiles.size(); A.tiles = d_asm_tiles.p; A.pair_id = d_pair_id.p;
-  A.pr_start = d_pr_start.p; A.po_start = d_po_start.p;
+  A.pr_start = d_pr_start.p; A.po_start = d_po_start.p; A.ntasks = n_asm_tasks; A.nwalk = n_asm_walk; A.tasks = (const int4*)d_asm_tasks.p;
   // the staging arrays of a group that stages nothing for a slot are never read; slots are always fully written
   // before k_assemble runs, so they need no clearing either
   {   // (function attributes are per device: once, not once per Prepare())
@@ -2911,7 +2967,9 @@ int mcp_ba::build_system(int nsys, SysBatch& sbfull, int q0, hipStream_t on) {
   }
   if (np && asm_long) hipLaunchKernelGGL(k_assemble_long, dim3(A.ntiles*32, nsys), dim3(32*ASML_LPE), 0, s, A, np, (const double*)d_stU.p, (const double*)d_stb.p,
                              (const double*)stSq, (const double*)strq, (const double*)Ubig(), Sq, sb);
-  else if (np) hipLaunchKernelGGL(k_assemble, dim3(A.ntiles, nsys), dim3(ASM_NT), 0, s, A, np, (const double*)d_stU.p, (const double*)d_stb.p,
+  else if (np && asm_pair) hipLaunchKernelGGL(k_assemble, dim3(A.nwalk + (A.ntasks - A.nwalk + ASMP_ZB - 1)/ASMP_ZB), dim3(64*nsys), 0, s, A, np, (const double*)d_stU.p, (const double*)d_stb.p,
+                             (const double*)stSq, (const double*)strq, Sq, sb);
+  else if (np) hipLaunchKernelGGL(k_assemble_tiles, dim3(A.ntiles, nsys), dim3(ASM_NT), 0, s, A, np, (const double*)d_stU.p, (const double*)d_stb.p,
                              (const double*)stSq, (const double*)strq, (const double*)Ubig(), Sq, sb);
   if (nfl && nbig) hipLaunchKernelGGL(k_schur, dim3(1, nsys), dim3(256), 0, s, P, sb.lambda[0], d_V.p, d_g.p, d_W.p, Vq, Sq, Sq + (size_t)np*np, failq, sb);
   if (main_stream) toc();
@@ -4068,6 +4126,7 @@ int mcp_ba_debug_structure(mcp_ba* h, mcp_ba_structure* out) {
   }
   r.lin_kernel = h->lin_kernel(); r.lin_generic = h->lin_generic() ? 1 : 0; r.schur_kernel = h->schur_kernel();
   r.asm_long = (h->np && h->asm_long) ? 1 : 0; r.max_systems = h->batch_capacity();
+  r.asm_kernel = !h->np ? MCP_BA_ASM_NONE : h->asm_long ? MCP_BA_ASM_LONG : h->asm_pair ? MCP_BA_ASM_PAIR : MCP_BA_ASM_TILES;
   *out = r;
   return 0;
 }
