@@ -605,7 +605,7 @@ struct CholPlan {
       d_step_tiles = (int*)(arena + o_step); d_row_start = (int*)(arena + o_rs); d_row_tiles = (int*)(arena + o_rt); d_all_tiles = (int*)(arena + o_all);
       d_diag = (double*)(arena + o_diag);
     }
-    { const char* e = getenv("MCP_BA_CHOL_PERSIST"); use_persist = !(e && atoi(e) == 0); }
+    use_persist = knobs::chol_persist();
     // (a reduced system of one or two tiles -- the BundleAdjustRecent window, <= 5 free poses -- is two launches either way: no plan for it)
     if (use_persist && ntc >= persist_min_ntc && persist.build(n, pattern, pattern.empty() ? std::vector<int>() : all_tiles, persist_segs)) return -1;
     return 0;
@@ -613,7 +613,7 @@ struct CholPlan {
   size_t tile_updates() const { return step_tiles.size(); }
   // one tile, 16-byte panel stores off (the fused path lives in the plain store branch): factorisation and back-substitution in one launch
   bool fuse_single() const { return ntc == 1 && n < CH_NB /* the right-hand-side row lies in the same tile */ && !(CH_PSTORE16 && !(n & 1)) && fuse_single_on; }
-  bool fuse_single_on = [] { const char* e = getenv("MCP_BA_CHOL_FUSE1"); return !(e && atoi(e) == 0); }();
+  bool fuse_single_on = knobs::chol_fuse1();
 };
 
 // factor S (n x n, lower) with the rhs in row n: afterwards row n holds y = L^-1 rhs

@@ -1161,9 +1161,9 @@ inline CpDevice& cp_device(int dev = -1) {
          hipFuncSetAttribute((const void*)k_chol_back2, hipFuncAttributeMaxDynamicSharedMemorySize, (6*CP_TILE + 700 + CH_SOLVE_MAX + 64)*(int)sizeof(double) + (CH_SOLVE_MAX/CH_NB + 4)*8*(int)sizeof(int)) == hipSuccess;
   if (d.ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_chol_persist, CP_THREADS, (size_t)CP_LDS_DOUBLES*sizeof(double) + 40*CP_STEP_INTS*sizeof(int)) == hipSuccess &&
       hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) { d.capacity = nb*ncu; d.ncu = ncu; }
-  if (const char* e = getenv("MCP_BA_CHOL_CAPACITY")) d.capacity = atoi(e);      // (test hook: pretend to be a partition of that many workgroup slots)
+  d.capacity = knobs::chol_capacity(d.capacity);      // (test hook: pretend to be a partition of that many workgroup slots)
   (void)hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev);
-  double ms = 20.0; if (const char* e = getenv("MCP_BA_CHOL_DEADLINE_MS")) ms = std::max(0.01, atof(e));
+  const double ms = knobs::chol_deadline_ms();
   const long long ticks = (long long)(ms*rate_khz);
   if (d.ok) d.ok = hipMemcpyToSymbol(HIP_SYMBOL(cp_deadline), &ticks, sizeof ticks) == hipSuccess;
   (void)hipGetLastError();
@@ -1354,12 +1354,12 @@ struct CholPersist {
     off += lt_bytes; off += bt_bytes;
     d_x = (double*)(arena + off); off += vec_bytes;
     d_f = (double*)(arena + off); off += vec_bytes;
+    const knobs::CholPersistKnobs kn;
     {
       // enough workers to hold a few block columns' worth of tiles at once (a column's far tile, its row's band tiles and the late product
       // work side by side; the columns ahead are being summed while they wait), at most 126 so that four systems are resident together
-      const char* e = getenv("MCP_BA_CHOL_WORKERS");
       const int per_col = (nhelpers + ntc - 1)/std::max(ntc, 1);
-      nworkers = e && atoi(e) > 0 ? atoi(e) : std::max(16, std::min(126, 10*per_col));
+      nworkers = kn.workers > 0 ? kn.workers : std::max(16, std::min(126, 10*per_col));
       nworkers = std::min(nworkers, std::max(nhelpers, 1));
       // ... and no more than the device holds beside a reserve of an eighth of its slots (what else is running -- the tracker thread's
       // frames, the speculative stream -- finds room; a second handle's factorisation shares the workers' slots and both go on)
@@ -1367,9 +1367,7 @@ struct CholPersist {
       if (!dv.ok || dv.disabled || dv.capacity < 2*max_sys) { release(); return 0; }       // (no one-launch plan on this device: ok stays false, the per-step kernels run)
       nworkers = std::max(1, std::min(nworkers, (dv.capacity - dv.capacity/8)/max_sys - nseg));
     }
-    { const char* e = getenv("MCP_BA_CHOL_SPREAD"); spread = !(e && atoi(e) == 0) && !getenv("MCP_BA_CHOL_WORKERS"); }
-    { const char* e = getenv("MCP_BA_CHOL_BACK_CHAINS"); back_chains = !(e && atoi(e) == 0); }
-    { const char* e = getenv("MCP_BA_TEST_PERSIST_FAIL"); test_fail_launch = e ? atoi(e) : -1; n_launch = 0; }
+    spread = kn.spread; back_chains = kn.back_chains; test_fail_launch = kn.test_fail_launch; n_launch = 0;
     ok = true;
     return 0;
   }

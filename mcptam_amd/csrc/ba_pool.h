@@ -11,6 +11,7 @@
 // mcp_ba_destroy after it has waited for the handle's streams).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "mcp_knobs.h"
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -38,7 +39,7 @@ class DevCache {
     int cls; const size_t cb = class_bytes(bytes, &cls);
     int dev = 0; (void)hipGetDevice(&dev);
     if (dev_out) *dev_out = dev;
-    if (enabled_ && cls < NCLS && dev < NDEV) {      // (a device ordinal beyond the table -- CPX mode exposes up to 64 -- bypasses the cache: plain hipMalloc / hipFree)
+    if (k_.enabled && cls < NCLS && dev < NDEV) {      // (a device ordinal beyond the table -- CPX mode exposes up to 64 -- bypasses the cache: plain hipMalloc / hipFree)
       std::lock_guard<std::mutex> lk(mu_);
       auto& v = free_[dev][cls];
       if (!v.empty()) { void* p = v.back(); v.pop_back(); cached_[dev] -= cb; *cap = cb; poison(p, cb, cls); return p; }
@@ -59,9 +60,9 @@ class DevCache {
     if (dev < 0) dev = cur;
     if (!quiesced()) { if (dev != cur) (void)hipSetDevice(dev); (void)hipDeviceSynchronize(); if (dev != cur) (void)hipSetDevice(cur); }
     int cls; const size_t cb = class_bytes(cap, &cls);
-    if (enabled_ && cb == cap && cls < NCLS && dev < NDEV) {
+    if (k_.enabled && cb == cap && cls < NCLS && dev < NDEV) {
       std::lock_guard<std::mutex> lk(mu_);
-      if (cached_[dev] + cb <= budget_) { free_[dev][cls].push_back(p); cached_[dev] += cb; return; }
+      if (cached_[dev] + cb <= k_.budget) { free_[dev][cls].push_back(p); cached_[dev] += cb; return; }
     }
     (void)hipFree(p);
   }
@@ -75,32 +76,24 @@ class DevCache {
   // the calling thread has waited for everything that could touch the blocks it is about to put()
   struct Quiesced { Quiesced() { ++depth(); } ~Quiesced() { --depth(); } };
  private:
-  // test aid (MCP_DEV_CACHE_POISON=1): every block is handed out filled with 0xFF -- NaNs, index -1 -- so that a read of something
-  // never written shows instead of passing on whatever the block held; MCP_DEV_CACHE_POISON_CLASS=c: only size class c, the others
-  // zero-filled (to find which buffer it is); MCP_DEV_CACHE_LOG=1 lists the classes handed out
+  // test aid (MCP_DEV_CACHE_POISON and its kin, mcp_knobs.h)
   void poison(void* p, size_t cb, int cls) {
     const int nth = ++count_;
-    if (log_) fprintf(stderr, "[dev cache] take #%d class %d (%zu bytes)\n", nth, cls, cb);
-    if (!poison_) return;
-    const bool hit = (poison_nth_ > 0) ? (nth == poison_nth_) : (poison_cls_ < 0 || poison_cls_ == cls);
+    if (k_.log) fprintf(stderr, "[dev cache] take #%d class %d (%zu bytes)\n", nth, cls, cb);
+    if (!k_.poison) return;
+    const bool hit = (k_.poison_nth > 0) ? (nth == k_.poison_nth) : (k_.poison_cls < 0 || k_.poison_cls == cls);
     (void)hipMemset(p, hit ? 0xFF : 0x00, cb);
     (void)hipDeviceSynchronize();          // (the solver's streams do not wait for the null stream)
   }
   static int& depth() { static thread_local int d = 0; return d; }
   static bool quiesced() { return depth() > 0; }
-  DevCache() {
-    if (const char* e = getenv("MCP_DEV_CACHE_POISON")) poison_ = atoi(e) != 0;
-    if (const char* e = getenv("MCP_DEV_CACHE_POISON_CLASS")) poison_cls_ = atoi(e);
-    if (const char* e = getenv("MCP_DEV_CACHE_POISON_NTH")) poison_nth_ = atoi(e);      // only the n-th block handed out
-    if (const char* e = getenv("MCP_DEV_CACHE_LOG")) log_ = atoi(e) != 0;
-    if (const char* e = getenv("MCP_DEV_CACHE_MB")) { const long mb = atol(e); if (mb <= 0) enabled_ = false; else budget_ = (size_t)mb << 20; }
-  }
+  DevCache() = default;
   static constexpr int NDEV = 64, NCLS = 4*40;      // free lists by the REAL device ordinal (no masking: ordinal 16 is not device 0)
   std::mutex mu_;
   std::vector<void*> free_[NDEV][NCLS];
   size_t cached_[NDEV] = {0};
-  size_t budget_ = (size_t)2 << 30;        // per device; MCP_DEV_CACHE_MB overrides (0 = no caching)
-  bool enabled_ = true, poison_ = false, log_ = false; int poison_cls_ = -1, poison_nth_ = 0; std::atomic<int> count_{0};
+  const knobs::DevCacheKnobs k_;      // (read once per process: the cache is made at its first use)
+  std::atomic<int> count_{0};
 };
 
 // small pinned, device-mapped host blocks (the read-back block + trial mailboxes of a handle): hipHostMalloc/hipHostFree cost

@@ -27,6 +27,7 @@
 
 #include "../../include/mcp_ba.h"
 #include "ba_pool.h"
+#include "mcp_knobs.h"
 #include "ba_kernels.h"
 #include "ba_select.h"
 #include "ba_chol.h"
@@ -123,7 +124,7 @@ static int usable_cores() {
 // with everything on one node (profiles/r06/README.md).  MCP_BA_HOST_NUMA=0 leaves the workers unpinned.
 static bool numa_node_cpus(cpu_set_t* out) {
   CPU_ZERO(out);
-  if (const char* e = getenv("MCP_BA_HOST_NUMA")) if (atoi(e) == 0) return false;
+  if (!knobs::host_numa()) return false;
   const int cpu = sched_getcpu();
   if (cpu < 0) return false;
   cpu_set_t allowed; CPU_ZERO(&allowed);
@@ -242,10 +243,9 @@ template <class T> struct ArenaAlloc {
 template <class T> using avec = std::vector<T, ArenaAlloc<T>>;
 // end of a build (any exit path): the copies out of the arena have to be done before it is handed to the next build
 struct ArenaGuard { hipStream_t st; ~ArenaGuard() { if (st) (void)hipStreamSynchronize(st); pinned_arena().reset(); } };
-// MCP_BA_HOST_THREADS: worker threads of the structure build (default: up to 16 of the cores this process may use; measured on a
-// 256-thread host, cold Prepare() of the metric map: see profiles/r06/README.md)
+// MCP_BA_HOST_THREADS: worker threads of the structure build
 static HostPool& host_pool() {
-  static HostPool p([] { const char* e = getenv("MCP_BA_HOST_THREADS"); const int want = e ? atoi(e) : 16; return std::min(std::max(want, 1), usable_cores()); }());
+  static HostPool p(knobs::host_threads(usable_cores()));
   return p;
 }
 
@@ -304,7 +304,7 @@ static SolverStreams& solver_streams(int device) {
   SolverStreams& P = pools[device];
   if (P.ok) return P;
   if (hipStreamCreateWithFlags(&P.main, hipStreamNonBlocking) != hipSuccess) return P;
-  const bool calibrate = [] { const char* e = getenv("MCP_BA_STREAM_CALIBRATE"); return e ? atoi(e) != 0 : true; }();
+  const bool calibrate = knobs::stream_calibrate();
   hipEvent_t e0 = nullptr, e1 = nullptr, ej = nullptr;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventCreateWithFlags(&ej, hipEventDisableTiming);
   int rate_khz = 100000; (void)hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, device);      // wall_clock64 ticks per ms
@@ -323,7 +323,7 @@ static SolverStreams& solver_streams(int device) {
       if (hipEventSynchronize(e1) != hipSuccess) return true;
       float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) best = std::min(best, ms);
     }
-    if (getenv("MCP_BA_TRACE")) fprintf(stderr, "[mcp_ba streams]   candidate: two 150 us kernels took %.0f us\n", best*1e3);
+    if (knobs::trace_level()) fprintf(stderr, "[mcp_ba streams]   candidate: two 150 us kernels took %.0f us\n", best*1e3);
     return best < 0.230f;                  // together ~0.16 ms, in sequence ~0.31 ms
   };
   // up to 12 candidates for the 4 side streams (speculative chain, a second one for MCP_BA_OVERLAP=2, two trial streams); the ones that
@@ -331,7 +331,7 @@ static SolverStreams& solver_streams(int device) {
   hipStream_t* want[4] = { &P.spec, &P.tr[2], &P.tr[3], &P.spec3 };
   int got = 0;
   // MCP_BA_SPEC_CUS=n (experiment): the side streams may only use the first n compute units (hipExtStreamCreateWithCUMask)
-  const int spec_cus = [] { const char* e = getenv("MCP_BA_SPEC_CUS"); return e ? atoi(e) : 0; }();
+  const int spec_cus = knobs::spec_cus();
   for (int c = 0; c < 12 && got < 4; ++c) {
     hipStream_t s2 = nullptr;
     if (spec_cus > 0) {
@@ -347,7 +347,7 @@ static SolverStreams& solver_streams(int device) {
   if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (ej) (void)hipEventDestroy(ej);
   (void)hipGetLastError();
   P.ok = P.main && P.spec;
-  if (getenv("MCP_BA_TRACE")) fprintf(stderr, "[mcp_ba streams] device %d: %d side streams overlap with the main stream%s\n", device, got, calibrate ? "" : " (not measured)");
+  if (knobs::trace_level()) fprintf(stderr, "[mcp_ba streams] device %d: %d side streams overlap with the main stream%s\n", device, got, calibrate ? "" : " (not measured)");
   return P;
 }
 
@@ -416,9 +416,9 @@ class StructCache {
   void clear() { std::vector<std::shared_ptr<StructEntry>> d; { std::lock_guard<std::mutex> lk(mu_); d.assign(lru_.begin(), lru_.end()); lru_.clear(); } }
   void stats(long long* h, long long* m) { std::lock_guard<std::mutex> lk(mu_); *h = hits_; *m = misses_; }
  private:
-  StructCache() { if (const char* e = getenv("MCP_BA_STRUCT_CACHE_MB")) budget_ = (size_t)std::max(0L, atol(e)) << 20; if (const char* e = getenv("MCP_BA_STRUCT_CACHE")) if (atoi(e) == 0) budget_ = 0; }
+  StructCache() = default;
   std::mutex mu_; std::list<std::shared_ptr<StructEntry>> lru_;
-  size_t budget_ = (size_t)512 << 20; int max_entries_ = 32; long long hits_ = 0, misses_ = 0, near_ = 0;
+  const size_t budget_ = knobs::struct_cache_bytes(); int max_entries_ = 32; long long hits_ = 0, misses_ = 0, near_ = 0;
 };
 // two independent 64-bit hashes of an int array, block by block (the value does not depend on how the work is split over threads)
 static inline unsigned long long mix64(unsigned long long x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33; return x; }
@@ -434,15 +434,17 @@ static void hash_block(const int* p, size_t n, size_t stride_ints, unsigned long
 namespace { struct SlotChunk; }      // (of the structure build, in front of prepare())
 
 struct mcp_ba {
+  // every run-time switch of the handle (mcp_knobs.h): hk as mcp_ba_create found the environment, pk as the handle's latest Prepare() did
+  knobs::HandleKnobs hk;
+  knobs::PrepareKnobs pk;
   int device = 0;
   hipStream_t st = nullptr;
   bool pooled = false;             // the streams belong to the device's pool (solver_streams): never destroyed by a handle
   // second stream: the speculative systems of a solve are built and factored here while the main stream already factors the
   // system the trial needs (both chains are latency-bound and overlap); ev_fork / ev_spec order the two
-  // (MCP_BA_OVERLAP: 0 = one stream, 1 = the speculative systems together on a second stream, 2 = system 1 on the second and
-  // systems 2.. on a third stream, so that the system the SECOND trial needs is ready as early as the first one's)
+  // (MCP_BA_OVERLAP, hk.overlap_spec)
   hipStream_t st2 = nullptr, st3 = nullptr; hipEvent_t ev_fork = nullptr, ev_spec = nullptr, ev_spec3 = nullptr;
-  bool spec_pending = false, spec3_pending = false; int spec2_from = 1, spec3_from = MAX_SYS; int overlap_spec = 1, main_sys = 1; bool overlap_auto = true;
+  bool spec_pending = false, spec3_pending = false; int spec2_from = 1, spec3_from = MAX_SYS;
   std::vector<mcp_camera> cams;
   int robust = 1, tukey = 1, verbose = 0;
   mcp_ba_params prm;
@@ -501,12 +503,6 @@ struct mcp_ba {
     int pred_ok = 0, ovf = 0;               // ... and what it told the host about the riding histograms
   };
   SpecLane lane[MAX_SYS];
-  // MCP_BA_SPEC_TRIALS: 0 = trials strictly in sequence; 1 = one trial ahead on the stream that solved it; 2 (default since round 6)
-  // = the steps of ALL speculatively solved systems are applied and evaluated as soon as their solutions exist, each on its own
-  // stream (lane[q].st_tr, behind the speculative chain's event).  Round 3 measured 819 / 835 it/s (1) vs 733 / 743 (2) -- three trial
-  // evaluations at once took the compute units from the trial the host was waiting for; with a trial's step in one launch and the
-  // evaluation at 17 us the balance has turned: 1518 / 1519 / 1610 (1) vs 1543 / 1538 / 1629 (2), pairs within one run.
-  int spec_trials = 2;
   // system
   DevBuf<double> d_ubig;    // [U (np*np) | bp (np)] contributions of the points outside the groups (> GRP_LMAX poses); only if nbig
   DevBuf<double> d_red;     // [S (np*np) | rhs (np) | bp = J^T r (np)]   (the all-reduced block)
@@ -518,16 +514,7 @@ struct mcp_ba {
   int head_ahead_for = -1;        // state buffer whose iteration head is already on the main stream (small bundles), or -1
   bool head_ahead_want = false; int dbg_head_ahead = 0;
   int head_ahead(int w);
-  // The same for maps beyond the small-bundle limit (round 6, MCP_BA_HEAD_AHEAD; ba_head.h): EVERY trial of an iteration -- the one on
-  // the main stream and the ones evaluated ahead on the second -- counts the digit histograms of its |chi2| while it evaluates them
-  // and is followed by ONE kernel that finishes the median and writes the sigma block of the iteration its acceptance would start,
-  // each trial into its own scratch and its own sigma / start block: slot [parity of the iteration][q].  The accepted trial's blocks
-  // become the current ones (sig_idx, start_blk); the others are never looked at.
-  // MEASURED (profiles/r06/README.md): with the heads on, a one-trial iteration reaches its linearisation 11 us after it starts (65 without)
-  // and every iteration finds its sigma^2 ready -- but the two extra launches + events per trial on the host and the heads' kernels
-  // beside the trials' cost more than that saves on the metric map: 1290-1335 it/s with them, 1335-1385 without, same box and run.
-  // So the default is OFF; MCP_BA_HEAD_AHEAD=1 switches every trial's head on, =2 only the main stream's.  Bit-identical either way.
-  int large_head_ahead = 0;
+  // The same for maps beyond the small-bundle limit: the per-trial heads of ba_head.h (MCP_BA_HEAD_AHEAD, hk.large_head_ahead)
   struct HeadScratch { unsigned int* hist = nullptr; double* vals = nullptr; double* part = nullptr; double* out = nullptr; double* rs = nullptr; };
   HeadScratch hsc[2*MAX_SYS]; DevBuf<double> d_headbuf;
   hipStream_t st_h = nullptr; bool st_h_own = false;      // the heads of trials evaluated ahead run here: the second stream stays free for the NEXT trial ahead
@@ -537,27 +524,19 @@ struct mcp_ba {
   unsigned int* head_hist(int q) { return hsc[head_par*MAX_SYS + q].hist; }
   int enqueue_head(hipStream_t s, int q, int w, bool side);
   int wait_head(int q);
-  bool large_heads() const { return large_head_ahead && robust && !multi() && !small_mode() && d_headbuf.p != nullptr; }
+  bool large_heads() const { return hk.large_head_ahead && robust && !multi() && !small_mode() && d_headbuf.p != nullptr; }
   int head_small(int w, bool sum_aside = false);
   int join_sum();
   int sum_aside(); int sum_w = -1; const double* sum_sig = nullptr;
   hipEvent_t ev_head = nullptr, ev_sum = nullptr; bool sum_pending = false;
   DevBuf<double> d_parth;         // partial sums of the robust chi2 taken on the second stream (head_small)
-  int small_on = 1;               // MCP_BA_SMALL=0: a small bundle runs the same launches as a large one (ba_small.h)
-  bool small_mode_for(int nmeas_, int nchain_) const { return small_on && !multi() && nmeas_ > 0 && nmeas_ <= SMALL_MEAS && nchain_ <= SMALL_CHAINS; }
+  bool small_mode_for(int nmeas_, int nchain_) const { return hk.small_on && !multi() && nmeas_ > 0 && nmeas_ <= SMALL_MEAS && nchain_ <= SMALL_CHAINS; }
   bool small_mode() const { return small_mode_for(P.nmeas, P.nchain); }
   int grp_pts = GRP_PTS;          // points per group: GRP_PTS, or LIN_QUAD_PTS for a map of few points (k_linearize_quad: four lanes per point)
-  static int group_points(int nsp) {
-    const char* e = getenv("MCP_BA_SMALL_POINTS"); const int small_pts = e ? atoi(e) : 16384;      // (0: the large-map layout for every map)
-    return (nsp <= small_pts) ? LIN_QUAD_PTS : GRP_PTS;
-  }
+  int group_points(int nsp) const { return (nsp <= pk.small_points) ? LIN_QUAD_PTS : GRP_PTS; }
+  int grp_lmax_pol() const { return hk.group_lmax13 ? S4_LMAX : GRP_LMAX; }      // poses at which a group is closed
   bool fail_clean = false;        // d_fail was cleared by the linearisation kernel and no system has been built since
-  // round 5 (ba_schur4.h): all systems of a batch in one Schur workgroup.  Groups are closed at S4_LMAX poses (a single point
-  // that sees more keeps its group beyond that: then no group of the map takes the new kernel, sch4_ok = false)
-  static bool env_on(const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; }
-  bool point_order_refine = env_on("MCP_BA_POINT_ORDER", true);     // secondary point order (refine_point_order)
-  int grp_lmax_pol = env_on("MCP_BA_GROUP_LMAX13", true) ? S4_LMAX : GRP_LMAX;
-  bool sch4_on = env_on("MCP_BA_SCHUR4", true), sch4_ok = false;
+  bool sch4_ok = false;           // every group of the map fits k_schur4 (hk.sch4_on; launch_choices)
   double schur_mfma = 0, schur_flops = 0;       // (profile only) what one system's Schur launch executes / stands for: mcp_ba_timing
   std::vector<unsigned char> last_pat;          // tile occupancy the factorisation plan was built from (kept for the structure cache)
   std::string launch_err;          // first launch of this solve that the runtime refused: "kernel: reason" (note_launch)
@@ -566,10 +545,9 @@ struct mcp_ba {
   StructKey cache_key, cache_base; bool cache_insert = false;      // a cold Prepare() of a cacheable map leaves its results in the structure cache
   // near miss: the structure of a superset of this map's measurements was adopted; the n_masked measurements this map lacks stay in the
   // device arrays with weight 0 (chi2 = 0: they sit below every real value in the median's order, contribute nothing anywhere else)
-  int n_masked = 0; int near_miss_on = 1;      // MCP_BA_NEAR_MISS=0: a map that lost measurements is built cold
+  int n_masked = 0;
   unsigned long long med_rank() const { return (unsigned long long)n_masked + (unsigned long long)(m_total/2); }      // vErrorSquared[size/2] among the real measurements
   DevBuf<int> d_m_last;                         // observer chain's last link per measurement (k_linearize_pipe)
-  bool lin_pipe = env_on("MCP_BA_LIN_PIPE", true);
   DevBuf<int> d_g_order, d_sp_unk;              // launch order of the groups in k_schur4 (heaviest first; only when they outnumber the slots), free-point index per sorted point
   bool sch4_order = false;
   bool asm_long = false;          // the pose pairs' lists of staged blocks are long (a few free poses staged by every group): k_assemble_long
@@ -581,18 +559,15 @@ struct mcp_ba {
   AsmPlan A;
   DevBuf<double> d_V, d_g, d_W, d_Vinv, d_xl, d_xp_good, d_xl_good, d_err;
   DevBuf<double> d_selvals;     // candidates of the single-GPU selection (SEL_GATHER_CAP)
-  DevBuf<double> d_seltab;      // multi-rank selection: [world x sel_cap candidates][overflow flag][world counts][gather counter]
-  int sel_cap = 4096;           // candidates per rank slot (MCP_BA_SELECT_CAP)
+  DevBuf<double> d_seltab;      // multi-rank selection: [world x pk.sel_cap candidates][overflow flag][world counts][gather counter]
   DevBuf<double> d_xp_cand;     // pose update of the trial in flight; swapped with d_xp_good (as d_xl with d_xl_good) when the solve succeeded
   DevBuf<double> d_part0, d_part1, d_part2, d_res, d_sigma, d_hist, d_cov;
   // the initial lambda's maximum over the diagonals (initial_lambda): one partial maximum per 1024 entries, MAX_DIAG_PARTS at most, in d_part1
   static constexpr int MAX_DIAG_PARTS = 256;
   static int max_diag_parts(int np_, int nfl_) { return std::min(MAX_DIAG_PARTS, (std::max(np_, nfl_) + 1023)/1024); }
-  // the head of an iteration of a large map in one launch (ba_headl.h, MCP_BA_HEAD_LARGE=1): scratch (left zeroed by every launch).  Default off:
-  // measured equal to the six launches at the metric size (1611 / 1603 vs 1606 / 1611 it/s) -- 39 us alone on the device against ~50, but its 64
-  // fat workgroups wait for room beside the trials evaluated ahead on the other stream, which six small launches slip past
-  DevBuf<unsigned char> d_headl; bool headl_clean = false; int head_large_on = 0; int hl_grid = 0;
-  bool use_head_large() const { return head_large_on && robust && !multi() && !small_mode() && P.nmeas > 0 && hl_grid > 0 && d_headl.p != nullptr; }
+  // the head of an iteration of a large map in one launch (ba_headl.h, MCP_BA_HEAD_LARGE=1, pk.head_large_on): scratch (left zeroed by every launch)
+  DevBuf<unsigned char> d_headl; bool headl_clean = false; int hl_grid = 0;
+  bool use_head_large() const { return pk.head_large_on && robust && !multi() && !small_mode() && P.nmeas > 0 && hl_grid > 0 && d_headl.p != nullptr; }
   int head_large(int w, int off, double* sig_copy2);
   bool hist_clean = false;          // the single-GPU median left its two histograms + counter zero (k_select_small's last act): no fill in front of the next one
   // The sigma block is double-buffered by median: a trial evaluated ahead on the speculative stream that nobody consumes may
@@ -619,7 +594,7 @@ struct mcp_ba {
     if (!h_exp) { set_err("hipHostMalloc failed"); return -1; }
     return 0;
   }
-  unsigned long long mail_ticket = 0; int use_mailbox = 1; double* h_mail_dev = nullptr;
+  unsigned long long mail_ticket = 0; double* h_mail_dev = nullptr;
   int* h_fail = nullptr;    // pinned
 
   // robust data
@@ -634,20 +609,12 @@ struct mcp_ba {
   // multi-rank
   mcp_allreduce_fn hook = nullptr; void* hook_user = nullptr; int rank = 0, world = 1;
   mcp_comm* comm = nullptr;        // native RCCL transport (takes precedence over the hook)
-  // MCP_BA_FORCE_MULTI=1: a one-rank communicator / hook is driven through the whole multi-rank machine (packed tiles, per-lane
-  // collectives, riding histograms) -- sums over one rank are exact, so the result must equal the plain single-rank solve bit for
-  // bit; the GPU suite uses it to run the two-lane RCCL path on the one device a test box has
-  int force_multi = 0;
-  bool multi() const { return (world > 1 || force_multi) && (hook || comm); }
-  // every host-side wait of the solve is bounded (MCP_BA_TIMEOUT_MS, default 60 s): a rank that dies inside a collective leaves the
-  // others waiting on a kernel that never ends, which must surface as MCP_ERR_RUNTIME with the place, not as a hang
-  double timeout_ms = 60000.0;
+  bool multi() const { return (world > 1 || hk.force_multi) && (hook || comm); }
+  // (every host-side wait of the solve is bounded: hk.timeout_ms)
   unsigned long long coll_seq[2] = {0, 0}; const char* coll_what[2] = {"none", "none"};
   int watchdog_fail(const char* where);
   int wait_stream(hipStream_t s, const char* what);
-  int spec_delay = 0;
-  int test_fail_trial = 0, test_trial_no = 0;      // MCP_BA_TEST_FAIL_TRIAL=k: the k-th trial of the handle's life is treated as a failed factorisation
-  int sel_ride = 1;                // MCP_BA_SELECT_RIDE=0: the median never uses the histograms that rode on the trial's all-reduce
+  int test_trial_no = 0;           // trials of the handle's life so far (hk.test_fail_trial)
   int pred_bin = -1;               // first digit of the last median the host has seen (the prediction the trials histogram around)
   int sel_src = -1;                // trial buffer whose histograms belong to the current state's chi2 (the accepted trial), or -1
 
@@ -692,15 +659,12 @@ struct mcp_ba {
   // must not overwrite any of it, nor consume a speculative solution, before that work is done
   // q < 0: everything; otherwise only the stream that produces system q of the batch
   // The step of a trial in one launch (ba_small.h k_trial_apply): chain workgroups of that launch, 0 = the separate kernels (a map with
-  // more poses than a chain workgroup keeps in LDS; MCP_BA_TRIAL_FUSE=0).  Small bundles: one workgroup for all chains, as before.
-  int trial_fuse = 1;
-  int dissect_on = 1;                // MCP_BA_CHOL_CHAINS=1: one chain (the poses in add order), see prepare()
-  int chain_arcs = 6;                // MCP_BA_CHOL_ARCS=k: the cut has k arcs at most (2 ... 6)
+  // more poses than a chain workgroup keeps in LDS; pk.trial_fuse = 0).  Small bundles: one workgroup for all chains, as before.
   std::vector<int> chol_segs;        // first tile of every chain of the factorisation plan (empty: one)
   int trial_chain_blocks() const {
     if (P.npose > TA_MAX_POSES) return 0;
     if (small_mode()) return 1;
-    return trial_fuse ? std::max(1, (P.nchain + TA_CHAINS - 1)/TA_CHAINS) : 0;
+    return pk.trial_fuse ? std::max(1, (P.nchain + TA_CHAINS - 1)/TA_CHAINS) : 0;
   }
   int backsub_blocks() const { return (nfl*BS_TPP + BS_BLOCK - 1)/BS_BLOCK; }      // workgroups of the point back-substitution: BS_TPP lanes per free point
   int join_spec(int q = -1) {
@@ -732,14 +696,8 @@ struct mcp_ba {
   size_t red_stride = 0, vinv_stride = 0, pack_stride = 0;
   bool start_rides = false;        // the iteration-start chi2 still has to be summed over the ranks
   int sys_cur = 0; bool spec_ok = false; int batch_n = 0; double batch_lambda[MAX_SYS] = {0, 0, 0, 0};
-  int speculate = 3;                 // speculative systems per solve at most; MCP_BA_SPECULATE=0 turns them off
-  // Small bundles (ba_small.h) speculate only while trials are being rejected: a BundleAdjustRecent window accepts every first trial, and the
-  // three systems solved beside it were 16 launches per iteration for nobody (compute 1.09 -> 1.01 ms without them).  A rejection arms the
-  // speculation for the re-solve that follows and the next iterations; MCP_BA_SPECULATE_ADAPT=0: always, as large bundles do.
-  int spec_adapt = 1, spec_hot = 0;
-  int spec_now() const { return (spec_adapt && small_mode() && spec_hot <= 0) ? 0 : speculate; }
-  int lin_join_full = 0;             // MCP_BA_LIN_JOIN=1: linearize() waits for everything the speculative stream has in flight (round 2's behaviour)
-  int use_graph = 0;                 // MCP_BA_GRAPH=1: replay the factorisation chain from a captured hipGraph
+  int spec_hot = 0;                  // small bundles: a rejection armed the speculation (pk.spec_adapt)
+  int spec_now() const { return (pk.spec_adapt && small_mode() && spec_hot <= 0) ? 0 : pk.speculate; }
   hipGraphExec_t chain_exec[MAX_SYS + 1][MAX_SYS] = {};      // [systems][first system]: factorisation + back-substitution of a sub-batch, captured once
   double* S() { return d_red.p + sys_cur*red_stride; }
   double* rhs() { return S() + (size_t)np*np; }
@@ -886,7 +844,6 @@ struct mcp_ba {
   int upload_hit_numbers(StructBuild& B, BlockLayout& L);
   int upload_cold(BlockLayout& L);
   int make_cache_entry(StructBuild& B, BlockLayout& L);
-  void read_call_knobs();
   int alloc_work_buffers(int nmeas, int nblk);
   int head_scratch(int nmeas, int nblk);
   int poison_test_aid();
@@ -931,11 +888,10 @@ struct mcp_ba {
   unsigned long long mail_ticket0 = 0;
   int dbg_pre = 0; double dbg_wait_us[2] = {0, 0};
   DevBuf<double>* last_xp = nullptr; DevBuf<double>* last_xl = nullptr;     // where the last trial left the solver's x (pose part, point part)
-  // MCP_BA_EVT=1: device time stamps (timing events) of the phases of every iteration on both streams, printed to stderr
-  int evt_debug = 0; std::vector<std::pair<const char*, hipEvent_t>> evt_log;
-  void mark(const char* what, hipStream_t s) { if (!evt_debug) return; hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; (void)hipEventRecord(e, s); evt_log.push_back({what, e}); }
+  std::vector<std::pair<const char*, hipEvent_t>> evt_log;      // (MCP_BA_EVT, hk.evt_debug)
+  void mark(const char* what, hipStream_t s) { if (!hk.evt_debug) return; hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; (void)hipEventRecord(e, s); evt_log.push_back({what, e}); }
   void evt_flush() {
-    if (!evt_debug || evt_log.empty()) return;
+    if (!hk.evt_debug || evt_log.empty()) return;
     (void)hipDeviceSynchronize();
     size_t base = 0;
     for (size_t i = 0; i < evt_log.size(); ++i) {
@@ -957,14 +913,14 @@ struct mcp_ba {
   //  one-lane-per-point kernel, which handles groups of any size up to 64 points)
   size_t quad_lds_bytes() const { return ((size_t)std::max(grp_blk_max, 1)*36 + (size_t)std::max(grp_inc_max, 1)*18)*sizeof(double); }
   int lin_kernel() const {
-    static const bool quad_on = [] { const char* e = getenv("MCP_BA_LIN_QUAD"); return !(e && atoi(e) == 0); }();
+    static const bool quad_on = knobs::lin_quad();
     if (!ngroup) return MCP_BA_LIN_NONE;
     if (grp_pts <= LIN_QUAD_PTS && quad_on && quad_lds_bytes() <= 58*1024) return MCP_BA_LIN_QUAD;      // (+ 5 KB of static LDS: tables and cameras)
-    if (lin_pipe && !getenv("MCP_BA_TEST_REFUSE_LAUNCH")) return MCP_BA_LIN_PIPE;
+    if (hk.lin_pipe && !knobs::test_refuse_launch()) return MCP_BA_LIN_PIPE;
     return MCP_BA_LIN_GROUP;
   }
   bool lin_generic() const { return nbig > 0 && P.nmeas > 0; }      // k_linearize for the points that touch more than GRP_LMAX poses
-  int schur_kernel() const { return !(nfl && ngroup) ? MCP_BA_SCHUR_NONE : (sch4_on && sch4_ok) ? MCP_BA_SCHUR_4 : MCP_BA_SCHUR_GROUP; }
+  int schur_kernel() const { return !(nfl && ngroup) ? MCP_BA_SCHUR_NONE : (hk.sch4_on && sch4_ok) ? MCP_BA_SCHUR_4 : MCP_BA_SCHUR_GROUP; }
   // systems of one batch that the reduced-system, V^-1 and staging buffers of this handle have room for
   int batch_capacity() const {
     size_t c = MAX_SYS;
@@ -1028,7 +984,7 @@ struct mcp_ba {
 int mcp_ba::watchdog_fail(const char* where) {
   char msg[384];
   std::snprintf(msg, sizeof msg, "rank %d of %d: no progress within %.0f ms while waiting for %s (last collectives: main lane #%llu '%s', "
-                "speculative lane #%llu '%s')", rank, world, timeout_ms, where, coll_seq[0], coll_what[0], coll_seq[1], coll_what[1]);
+                "speculative lane #%llu '%s')", rank, world, hk.timeout_ms, where, coll_seq[0], coll_what[0], coll_seq[1], coll_what[1]);
   set_err(msg);
   if (comm && !comm->dead) {
     comm->dead = true;
@@ -1046,7 +1002,7 @@ int mcp_ba::wait_stream(hipStream_t s, const char* what) {
     if (e != hipErrorNotReady) { set_err(std::string("stream failed while waiting for ") + what + ": " + hipGetErrorString(e)); return -1; }
     if (spins > 2000) {
       std::this_thread::yield();
-      if ((spins & 0xff) == 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > timeout_ms) return watchdog_fail(what);
+      if ((spins & 0xff) == 0 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > hk.timeout_ms) return watchdog_fail(what);
     }
   }
 }
@@ -1097,7 +1053,7 @@ typedef unsigned long long u64;
 // the phase timer of one Prepare() (MCP_BA_TRACE): both builders and finish_prepare() print their laps through it
 struct PrepTimer {
   const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); std::chrono::steady_clock::time_point tlast = t0;
-  const bool trace = getenv("MCP_BA_TRACE") != nullptr;
+  const bool trace = knobs::trace_level() >= 1;
   void operator()(const char* what) { if (!trace) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[mcp_ba prepare] %-22s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - tlast).count()); tlast = n; }
   double total_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
@@ -1178,7 +1134,7 @@ struct mcp_ba::StructBuild {
   std::vector<unsigned char> seen_over, chain_used, cov, inc_state, gcov;      // (cov: pose-pair co-visibility, a >= b)
   std::unique_ptr<PairMasks> pair_mask; std::vector<SlotChunk> chunks;
   StructBuild(const mcp_ba& s, bool serial) : npose((int)s.poses.size()), npoint((int)s.points.size()), nmeas((int)s.meas.size()), nch(s.chains.size()) {
-    static const int par_min = [] { const char* e = getenv("MCP_BA_PREP_PAR_MIN"); return e ? atoi(e) : 32768; }();      // measurements from which the structure is built on the worker pool
+    static const int par_min = knobs::prep_par_min();
     if (!serial && nmeas >= par_min) T = host_pool().size();
   }
 };
@@ -1201,13 +1157,12 @@ int mcp_ba::prepare() {
   // what a Prepare() leaves for Compute() starts from nothing here, whichever builder or cache path follows (med_rank() reads n_masked)
   n_masked = 0; cache_insert = false; chol_segs.clear(); plan.persist_segs.clear();
   HIPCK(hipSetDevice(device));
-  if (!head_small_lds()) small_on = 0;
-  const bool serial = getenv("MCP_BA_PREPARE_LEGACY") != nullptr;
-  StructBuild B(*this, serial);
-  if (serial) return prepare_legacy(B);
+  if (!head_small_lds()) hk.small_on = 0;
+  pk.read_build();
+  StructBuild B(*this, pk.legacy);
+  if (pk.legacy) return prepare_legacy(B);
   B.lap("  entry");
-  { const char* e = getenv("MCP_BA_CHOL_CHAINS"); dissect_on = !(e && atoi(e) == 1); }
-  { const char* e = getenv("MCP_BA_CHOL_ARCS"); chain_arcs = e ? atoi(e) : 6; }
+  pk.read_chains();
   if (cache_lookup(B)) return adopt(B) ? -1 : finish_prepare(B);
   count_pass(B);
   if (activity(B) || pose_cut_order(B) || number_unknowns(B)) return -1;
@@ -1247,10 +1202,7 @@ bool mcp_ba::cache_lookup(StructBuild& B) {
   key.npose = npose; key.npoint = npoint; key.nmeas = nmeas; key.nchain = (int)nch; key.dev = device;
   key.h1 = mix64(key.h1 ^ (unsigned long long)cams.size());          // (the camera table is part of the packed block's layout)
   // (what else decides the structure: the grouping policy and its run-time switches)
-  const char* e_al = getenv("MCP_BA_ASM_LONG");
-  key.flags = grp_lmax_pol | (point_order_refine ? 32 : 0) | (sch4_on ? 64 : 0) | (env_on("MCP_BA_SCHUR4_ORDER", true) ? 128 : 0) | (group_points(npoint) << 8) |
-              ((e_al ? 1 + (atoi(e_al) != 0) : 0) << 16) | (dissect_on ? (chain_arcs & 7) << 18 : 0);
-  { const char* e = getenv("MCP_BA_TEST_CHOL_CUT"); if (e) key.flags ^= (unsigned)(atoi(e) & 0xff) << 21; }
+  key.flags = pk.structure_flags(hk, grp_lmax_pol(), group_points(npoint));
   cache_key = key;
   {
     // the same key without the measurements (near miss, below)
@@ -1261,7 +1213,7 @@ bool mcp_ba::cache_lookup(StructBuild& B) {
   }
   B.hit = StructCache::get().find(key);
   lap("  topology hash");
-  if (!B.hit && near_miss_on) { near_miss_search(B); lap("  near miss search"); }
+  if (!B.hit && hk.near_miss_on) { near_miss_search(B); lap("  near miss search"); }
   cache_insert = !B.hit;
   return B.hit != nullptr;
 }
@@ -1366,11 +1318,11 @@ void mcp_ba::take_scratch(StructBuild& B) {
   // (with the secondary point order: per point also the largest observer pose and the sum of the observer poses -- the key of
   //  refine_point_order -- in the same private way: a first version added them up with atomics on shared arrays, 6 ms of cache-line
   //  ping-pong between the threads)
-  const bool refine = B.refine = point_order_refine;
+  const bool refine = B.refine = hk.point_order_refine;
   // (for the chains of the factorisation, below: per point the poses that see it, as a 64-bit set per thread -- the adapters add the
   //  measurements KeyFrame by KeyFrame, so a thread's range of the add order holds few distinct observers: each gets a bit as it is first
   //  met, whatever its pose index; a range with more than 64 of them is reported and the sets are taken again with atomics)
-  const bool want_graph = B.want_graph = dissect_on && npose >= 96 && npose <= 1024 + 64;
+  const bool want_graph = B.want_graph = pk.dissect_on && npose >= 96 && npose <= 1024 + 64;
   scratch.reset(sizeof(int)*(size_t)(refine ? 3 : 1)*T*std::max(npoint, 1) + sizeof(SMeas)*(size_t)std::max(nmeas, 1) + (want_graph ? sizeof(u64)*(size_t)T*std::max(npoint, 1) : 0) + 512);
   B.seen_t = want_graph ? scratch.take<u64>((size_t)T*std::max(npoint, 1)) : nullptr;
   B.cnt_t = scratch.take<int>((size_t)T*std::max(npoint, 1));
@@ -1470,7 +1422,7 @@ int mcp_ba::pose_cut_order(StructBuild& B) {
   std::vector<u64> adj((size_t)nf*W, 0);
   if (coupling_graph(B, adj)) return -1;
   PoseCut cut;
-  pose_cut(adj, nf, chain_arcs, B.T, [&](const std::function<void(int)>& fn) { B.par(fn); }, [&](const char* what) { B.lap(what); }, cut);
+  pose_cut(adj, nf, pk.chain_arcs, B.T, [&](const std::function<void(int)>& fn) { B.par(fn); }, [&](const char* what) { B.lap(what); }, cut);
   if (cut.relabelled || cut.taken) {
     std::vector<int> fp2(nf);
     for (int i = 0; i < nf; ++i) fp2[i] = fp_pose[cut.order[i]];
@@ -1478,7 +1430,7 @@ int mcp_ba::pose_cut_order(StructBuild& B) {
     for (int u = 0; u < nf; ++u) poses[fp_pose[u]].unk = u;
   }
   chol_segs = cut.segs;
-  if (cut.taken) { const char* e = getenv("MCP_BA_TEST_CHOL_CUT"); if (e) chol_segs[1] = std::max(3, chol_segs[1] - atoi(e)); }      // (tests: the cut between the chains moved into the first one -- chains that couple: the plan must notice)
+  if (cut.taken && pk.chol_cut.set) chol_segs[1] = std::max(3, chol_segs[1] - pk.chol_cut.v);      // (tests: the cut between the chains moved into the first one -- chains that couple: the plan must notice)
   if (B.lap.trace) trace_cut(cut, nf);
   B.lap("  pose order (chains)");
   return 0;
@@ -1491,7 +1443,7 @@ int mcp_ba::coupling_graph(StructBuild& B, std::vector<u64>& adj) {
   const int npose = B.npose, npoint = B.npoint, nmeas = B.nmeas, T = B.T; const u64* const seen_t = B.seen_t; const std::vector<int>& seen_ids = B.seen_ids;
   const int nf = (int)fp_pose.size(), W = (nf + 63)/64;
   bool windows = true; for (int t = 0; t < T; ++t) windows = windows && !B.seen_over[t];
-  if (getenv("MCP_BA_TEST_CHOL_ATOMIC")) windows = false;      // (tests: the masks of an add order whose observers do not fit the windows)
+  if (pk.chol_atomic) windows = false;      // (tests: the masks of an add order whose observers do not fit the windows)
   std::vector<u64> pmask, adj_t((size_t)T*nf*W, 0);
   const int* mp = meas_point.data(); const int* mc = meas_chain.data();
   if (!windows) {
@@ -1623,7 +1575,7 @@ void mcp_ba::build_slots(StructBuild& B) {
   B.cov.assign((size_t)std::max(nfp, 1)*std::max(nfp, 1), 0);
   // (eight chunks per thread (MCP_BA_PREP_CHUNKS), claimed one after the other: equal measurement counts are not equal times -- 1.0 to 1.6 ms per thread
   //  at the metric size with one chunk each -- and the concatenation is by chunk index, so who built a chunk changes nothing)
-  static const int chunks_per_thread = [] { const char* e = getenv("MCP_BA_PREP_CHUNKS"); return e ? std::max(1, atoi(e)) : 8; }();
+  static const int chunks_per_thread = knobs::prep_chunks();
   const int NC = T > 1 ? chunks_per_thread*T : 1;
   chunks.assign(NC, SlotChunk());
   const avec<int>& sp_m = H.sp_m;
@@ -1757,7 +1709,7 @@ void mcp_ba::make_groups(StructBuild& B) {
     const int* q = sp_q.data() + sp_q0[sp]; const int nq = big ? 0 : sp_q0[sp + 1] - sp_q0[sp];
     int fresh = 0;
     for (int k = 0; k < nq; ++k) if (stamp[q[k]] != gid) ++fresh;
-    if ((int)curset.size() + fresh > grp_lmax_pol || sp - start >= grp_pts) close(sp);
+    if ((int)curset.size() + fresh > grp_lmax_pol() || sp - start >= grp_pts) close(sp);
     for (int k = 0; k < nq; ++k) if (stamp[q[k]] != gid) { stamp[q[k]] = gid; curset.push_back(q[k]); }
   }
   close(nsp);
@@ -1909,7 +1861,7 @@ int mcp_ba::prepare_legacy(StructBuild& B) {
     order.push_back(i);
   }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pkey[a] < pkey[b]; });
-  if (point_order_refine) {      // (the same secondary order as the threaded builder's)
+  if (hk.point_order_refine) {      // (the same secondary order as the threaded builder's)
     std::vector<int> smax(std::max(npoint, 1), 0), ssum(std::max(npoint, 1), 0);
     for (int i = 0; i < nmeas; ++i) {
       const int k = chain_first_movable(chains[meas[i].chain], poses) + 1;
@@ -2043,7 +1995,7 @@ int mcp_ba::prepare_legacy(StructBuild& B) {
       if (sp_big[sp]) ++nbig;
       std::vector<int> merged = curset;
       for (int u : q) if (std::find(merged.begin(), merged.end(), u) == merged.end()) merged.push_back(u);
-      if ((int)merged.size() > grp_lmax_pol || sp - start >= grp_pts) { close(sp); merged = q; }
+      if ((int)merged.size() > grp_lmax_pol() || sp - start >= grp_pts) { close(sp); merged = q; }
       curset = merged;
     }
     close(nsp);
@@ -2164,7 +2116,7 @@ int mcp_ba::finish_prepare(StructBuild& B) {
   if (B.hit ? upload_hit_numbers(B, L) : upload_cold(L)) return -1;
   B.lap("  upload enqueued");
   if (!B.hit && cache_insert && make_cache_entry(B, L)) return -1;
-  read_call_knobs();
+  pk.read_call();
   if (alloc_work_buffers(nmeas, nblk) || head_scratch(nmeas, nblk) || poison_test_aid() || pinned_mailbox(nblk) || zero_fill() || fill_param_blocks(nmeas)) return -1;
   B.lap("alloc+upload");
   return publish(B);
@@ -2186,11 +2138,11 @@ void mcp_ba::launch_choices(StructBuild& B) {
     // long lists of staged blocks per pose pair (mean >= 48: a handful of free poses that every group stages) go through k_assemble_long
     const size_t npairs = H.pr_start.empty() ? 0 : H.pr_start.size() - 1;
     asm_long = npairs > 0 && nstage >= 48*npairs;
-    if (const char* e = getenv("MCP_BA_ASM_LONG")) asm_long = atoi(e) != 0 && npairs > 0;
+    if (pk.asm_long.set) asm_long = pk.asm_long.v != 0 && npairs > 0;
   }
   // a wavefront per pose block (k_assemble) unless the lists are long or generic-path points add Ubig entry by entry; the task table
   // belongs to the structure (a cache entry holds it whatever the knob said when it was built), the knob to this Prepare()
-  asm_pair = np > 0 && !asm_long && !nbig && env_on("MCP_BA_ASM_PAIR", true);
+  asm_pair = np > 0 && !asm_long && !nbig && pk.asm_pair;
 }
 
 // k_assemble's task table (ba_group.h: asmp_task), from the staging plan and the tiles of the factorisation plan: one task for every
@@ -2259,7 +2211,7 @@ void mcp_ba::schur_work(StructBuild& B) {
           sf += 324.0*k*(k + 1)/2;
           for (int i = H.sp_i[sp]; i < H.sp_i[sp + 1]; ++i) { tm |= 1u << ((6*H.inc_lp[i]) >> 4); tm |= 1u << ((6*H.inc_lp[i] + 5) >> 4); }
         }
-        const int nt = (sch4_on && sch4_ok) ? __builtin_popcount(tm) : (tm ? ntile : 0);
+        const int nt = (hk.sch4_on && sch4_ok) ? __builtin_popcount(tm) : (tm ? ntile : 0);
         sm += 12.0*nt*(nt + 1)/2;
       }
     }
@@ -2281,7 +2233,7 @@ void mcp_ba::small_arrays(StructBuild& B, BlockLayout& L) {
   // (tile pairs x chunks), so that the second round of workgroups is made of the light ones and the launch ends evenly
   L.sp_unk.resize(hit ? 0 : nsp);
   if (!hit) for (int sp = 0; sp < nsp; ++sp) L.sp_unk[sp] = H.sp_big[sp] ? -1 : L.pt_unk[H.sp_pt[sp]];
-  sch4_order = hit ? hit->sch4_order : (sch4_on && sch4_ok && ngroup > 512 && env_on("MCP_BA_SCHUR4_ORDER", true));
+  sch4_order = hit ? hit->sch4_order : (hk.sch4_on && sch4_ok && ngroup > 512 && pk.schur4_order);
   if (sch4_order && !hit) {
     std::vector<int> cost(ngroup);
     for (int gi = 0; gi < ngroup; ++gi) {
@@ -2438,17 +2390,6 @@ int mcp_ba::make_cache_entry(StructBuild& B, BlockLayout& L) {
   return 0;
 }
 
-// per-call knobs of the LM driver (read at every Prepare(): a test sets them between two handles)
-void mcp_ba::read_call_knobs() {
-  { const char* e = getenv("MCP_BA_SPECULATE"); if (e) speculate = atoi(e); }
-  { const char* e = getenv("MCP_BA_SPECULATE_ADAPT"); if (e) spec_adapt = atoi(e); }
-  { const char* e = getenv("MCP_BA_LIN_JOIN"); if (e) lin_join_full = atoi(e); }
-  { const char* e = getenv("MCP_BA_TRIAL_FUSE"); if (e) trial_fuse = atoi(e); }
-  { const char* e = getenv("MCP_BA_HEAD_LARGE"); if (e) head_large_on = atoi(e); }
-  { const char* e = getenv("MCP_BA_GRAPH"); if (e) use_graph = atoi(e); }
-  { const char* e = getenv("MCP_BA_SELECT_CAP"); if (e) sel_cap = std::max(1, atoi(e)); }
-}
-
 // the state buffers and the work buffers of the iteration, sized for this map
 int mcp_ba::alloc_work_buffers(int nmeas, int nblk) {
   const int npose = (int)poses.size(), npoint = (int)points.size();
@@ -2459,7 +2400,7 @@ int mcp_ba::alloc_work_buffers(int nmeas, int nblk) {
   const size_t n2 = (size_t)np*np;
   red_stride = n2 + 2*(size_t)np; vinv_stride = (size_t)nfl*6; spec_ok = false; sys_cur = 0;
   if (multi()) {
-    if (d_seltab.alloc((size_t)world*sel_cap + world + 2)) return -1;
+    if (d_seltab.alloc((size_t)world*pk.sel_cap + world + 2)) return -1;
     for (int q = 0; q < MAX_SYS; ++q) if (lane[q].trial.alloc(TRIAL_LEN) || lane[q].trstate.alloc(SEL_PASSES + 1)) return -1;
   }
   sel_src = -1; pred_bin = -1;
@@ -2477,7 +2418,7 @@ int mcp_ba::alloc_work_buffers(int nmeas, int nblk) {
 // scratch of the iteration heads: k_head_large's block, and the per-trial heads' (ba_head.h)
 int mcp_ba::head_scratch(int nmeas, int nblk) {
   const size_t nc = chains.size();
-  if (head_large_on && robust && !multi() && nmeas > 0) {
+  if (pk.head_large_on && robust && !multi() && nmeas > 0) {
     if (d_headl.alloc(sizeof(HeadLScratch))) return -1;
     headl_clean = false;                           // (the block may be a fresh one: zeroed in front of the first head)
     if (!hl_grid) {
@@ -2491,7 +2432,7 @@ int mcp_ba::head_scratch(int nmeas, int nblk) {
     // scratch of the per-trial iteration heads (ba_head.h): per slot [parity][q] the digit histograms + counters, the candidates,
     // the robust chi2's partial sums, the median and the iteration-start block
     for (auto& H : hsc) H = HeadScratch();
-    if (large_head_ahead && robust && !multi() && !small_mode_for(nmeas, (int)nc) && nmeas > 0) {
+    if (hk.large_head_ahead && robust && !multi() && !small_mode_for(nmeas, (int)nc) && nmeas > 0) {
       auto al = [](size_t x) { return (x + 31) & ~(size_t)31; };
       const size_t n_hist = al((HEAD_HIST + HEAD_CTL + 1)/2), n_vals = al(HEAD_CAND), n_part = al(std::max<size_t>(nblk, 1)), per = n_hist + n_vals + n_part + 32;
       if (d_headbuf.alloc(per*2*MAX_SYS)) return -1;
@@ -2511,9 +2452,9 @@ int mcp_ba::head_scratch(int nmeas, int nblk) {
 // test aid, MCP_BA_DEBUG_POISON_RED="q,lo,hi": the reduced-system buffer zeroed, doubles [lo, hi) of system q set to NaN
 int mcp_ba::poison_test_aid() {
   const size_t n2 = (size_t)np*np;
-  if (const char* e = getenv("MCP_BA_DEBUG_POISON_RED")) {
+  {
     int q = 0; long lo = 0, hi = 0;
-    if (std::sscanf(e, "%d,%ld,%ld", &q, &lo, &hi) == 3 && q >= 0 && q < MAX_SYS && lo >= 0 && hi <= (long)(n2 + 2*(size_t)np) && lo < hi) {
+    if (knobs::debug_poison_red(&q, &lo, &hi) && q >= 0 && q < MAX_SYS && lo >= 0 && hi <= (long)(n2 + 2*(size_t)np) && lo < hi) {
       HIPCK(hipMemset(d_red.p, 0, MAX_SYS*(n2 + 2*(size_t)np)*sizeof(double)));
       HIPCK(hipMemset(d_red.p + q*(n2 + 2*(size_t)np) + lo, 0xFF, (size_t)(hi - lo)*sizeof(double)));
     }
@@ -2664,7 +2605,7 @@ void mcp_ba::launch_eval(int w, bool sum, double* err_out) {
 
 // exact k-th smallest |x| (global over ranks when a hook is installed); result left at out_dev[0]
 int mcp_ba::select_kth(const double* x, int n, unsigned long long k, double* out_dev, bool huber_sigma) {
-  static const int grid_max = [] { const char* e = getenv("MCP_BA_SELECT_GRID"); return e ? std::max(1, atoi(e)) : 1024; }();
+  static const int grid_max = knobs::select_grid();
   const int grid = std::max(1, std::min(grid_max, (n + SEL_BLOCK*4 - 1)/(SEL_BLOCK*4)));
   if (!multi()) {
     // single GPU: two full histogram passes, gather, one-workgroup finish (which also writes the Huber sigma block if asked)
@@ -2679,7 +2620,7 @@ int mcp_ba::select_kth(const double* x, int n, unsigned long long k, double* out
     return 0;
   }
   // several ranks: two all-reduced histogram passes, then the few candidates of every rank are gathered through a
-  // zero-filled (ranks x sel_cap) table summed over the ranks, and each rank finishes locally: 3 collectives
+  // zero-filled (ranks x pk.sel_cap) table summed over the ranks, and each rank finishes locally: 3 collectives
   hist_clean = false;
   HIPCK(hipMemsetAsync(d_hist.p, 0, (size_t)SEL_PASSES*SEL_BINS*sizeof(double), st));
   for (int p = 0; p < 2; ++p) {
@@ -2702,12 +2643,12 @@ int mcp_ba::select_kth(const double* x, int n, unsigned long long k, double* out
 // wait) and skip the finish if it is up; without it the caller knows from the summed histogram that no slot can overflow.
 int mcp_ba::select_gather_finish(const double* x, int n, const double* hist, SelState* state, double* out_dev, bool check_overflow) {
   const int grid = std::max(1, std::min(1024, (n + SEL_BLOCK*4 - 1)/(SEL_BLOCK*4)));
-  const size_t tab = (size_t)world*sel_cap;              // [tab] overflow flag, [tab+1 .. tab+world] counts, [tab+world+1] gather counter
+  const size_t tab = (size_t)world*pk.sel_cap;              // [tab] overflow flag, [tab+1 .. tab+world] counts, [tab+world+1] gather counter
   HIPCK(hipMemsetAsync(d_seltab.p, 0, (tab + world + 2)*sizeof(double), st));
   unsigned int* cnt = reinterpret_cast<unsigned int*>(d_seltab.p + tab + world + 1);
   hipLaunchKernelGGL(k_select_gather_slot, dim3(grid), dim3(SEL_BLOCK), 0, st, n, x, hist, state, cnt,
-                     d_seltab.p + (size_t)rank*sel_cap, sel_cap, rank == 0 ? d_seltab.p + tab : (double*)nullptr);
-  hipLaunchKernelGGL(k_select_publish, dim3(1), dim3(64), 0, st, (const unsigned int*)cnt, sel_cap, d_seltab.p + tab + 1 + rank);
+                     d_seltab.p + (size_t)rank*pk.sel_cap, pk.sel_cap, rank == 0 ? d_seltab.p + tab : (double*)nullptr);
+  hipLaunchKernelGGL(k_select_publish, dim3(1), dim3(64), 0, st, (const unsigned int*)cnt, pk.sel_cap, d_seltab.p + tab + 1 + rank);
   if (allreduce(d_seltab.p, tab + 1 + world, 0, false, "median: candidate gather")) return -1;
   if (check_overflow) {
     HIPCK(hipMemcpyAsync(h_res + 30, d_seltab.p + tab, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2715,7 +2656,7 @@ int mcp_ba::select_gather_finish(const double* x, int n, const double* hist, Sel
     if (h_res[30] != 0.0) return 0;
   }
   hipLaunchKernelGGL(k_select_small, dim3(1), dim3(1024), 0, st, n, x, (const unsigned int*)cnt, (const double*)d_seltab.p, (const SelState*)state,
-                     m_total, 0.0, out_dev, (double*)nullptr, (double*)nullptr, (const double*)(d_seltab.p + tab + 1), world, sel_cap);
+                     m_total, 0.0, out_dev, (double*)nullptr, (double*)nullptr, (const double*)(d_seltab.p + tab + 1), world, pk.sel_cap);
   return 0;
 }
 // median + sigma block + robust chi2 of buffer `w` in one launch (ba_headl.h): the sigma block to sig() and d_res[25..28] (and to
@@ -2771,7 +2712,7 @@ int mcp_ba::wait_mail(int q, unsigned long long ticket, int count) {
   // The result is normally a few tens of microseconds away: poll hard for a while (a trial is ~70 us, a solve ~1 ms), then give
   // the core to whoever else wants it between polls -- a tracker thread beside the mapper (BASELINE c5) should not lose a core
   // to a solver that waits for a long factorisation or for another rank.  Every so often: has the stream died, drained without
-  // delivering, or made no progress for timeout_ms?
+  // delivering, or made no progress for hk.timeout_ms?
   constexpr unsigned long long HARD_SPINS = 1ull << 16;
   for (unsigned long long spins = 0; __atomic_load_n(tk, __ATOMIC_ACQUIRE) != ticket; ++spins) {
     if (spins >= HARD_SPINS) {
@@ -2781,7 +2722,7 @@ int mcp_ba::wait_mail(int q, unsigned long long ticket, int count) {
         if (e == hipSuccess && q > 0 && st3) e = hipStreamQuery(st3);
         if (e == hipSuccess) { if (__atomic_load_n(tk, __ATOMIC_ACQUIRE) == ticket) break; set_err("mailbox ticket never arrived"); return -1; }
         if (e != hipErrorNotReady) { set_err(std::string("stream failed while waiting for a trial: ") + hipGetErrorString(e)); return -1; }
-        if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count() > timeout_ms)
+        if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count() > hk.timeout_ms)
           return watchdog_fail(q ? "the result of a trial evaluated ahead (speculative lane)" : "the result of a trial (main lane)");
       }
     } else {
@@ -2802,7 +2743,7 @@ int mcp_ba::multi_trial_tail(hipStream_t s, int lane, int q, int slot, int nbe, 
   SpecLane& L = this->lane[q];      // (`lane` here is the collective's)
   double* T = L.trial.p;
   HIPCK(hipMemsetAsync(T, 0, TRIAL_LEN*sizeof(double), s));
-  const bool ride = robust && sel_ride && m_total > 0;       // (decided on GLOBAL quantities: the payload size must agree on every rank)
+  const bool ride = robust && hk.sel_ride && m_total > 0;       // (decided on GLOBAL quantities: the payload size must agree on every rank)
   if (ride) {
     const int grid = std::max(1, std::min(256, (P.nmeas + SEL_BLOCK*8 - 1)/(SEL_BLOCK*8)));
     hipLaunchKernelGGL(k_select_hist2, dim3(grid), dim3(SEL_BLOCK), 0, s, P.nmeas, (const double*)d_chi2[slot].p, pred_bin, T + TRIAL_HDR);
@@ -2811,7 +2752,7 @@ int mcp_ba::multi_trial_tail(hipStream_t s, int lane, int q, int slot, int nbe, 
   hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, s, nbe, p0, nbb, p1, nbb, p2, T, 0, (const int*)d_fail.p + q, (double*)nullptr, 0, 0ull,
                      rides ? (const double*)(d_res.p + 24) : (const double*)nullptr, 4);
   if (allreduce(T, ride ? TRIAL_LEN : TRIAL_HDR, lane, false, lane ? "trial evaluated ahead: result block + median histograms" : "trial: result block + median histograms")) return -1;
-  hipLaunchKernelGGL(k_trial_post, dim3(1), dim3(SEL_BLOCK), 0, s, T, L.trstate.p, (unsigned long long)(m_total/2), pred_bin, (double)sel_cap, ride ? 1 : 0,
+  hipLaunchKernelGGL(k_trial_post, dim3(1), dim3(SEL_BLOCK), 0, s, T, L.trstate.p, (unsigned long long)(m_total/2), pred_bin, (double)pk.sel_cap, ride ? 1 : 0,
                      pose_parts, pose_off, main_block ? (const double*)(d_res.p + 24) : (const double*)nullptr, rides ? 1 : 0,
                      main_block ? d_res.p : (double*)nullptr, mail, mail_count, ticket);
   if (rides) start_rides = false;
@@ -2861,7 +2802,7 @@ int mcp_ba::enqueue_spec_trial(hipStream_t s, int q) {
   L.tr_stream = s;
   const int slot = cand(q);
   double* rhsq = d_red.p + q*red_stride + (size_t)np*np; double* resq = d_res.p + 32 + 8*q;
-  const bool with_head = head_ahead_want && !small_mode() && large_heads() && large_head_ahead != 2 && P.nmeas > 0;      // (MCP_BA_HEAD_AHEAD=2: only the main stream's trial carries a head)
+  const bool with_head = head_ahead_want && !small_mode() && large_heads() && hk.large_head_ahead != 2 && P.nmeas > 0;      // (MCP_BA_HEAD_AHEAD=2: only the main stream's trial carries a head)
   L.pre_ticket = ++mail_ticket;
   const TrialIo io{s, 1, q, slot, batch_lambda[q], rhsq, rhsq + np, d_Vinv.p + q*vinv_stride, L.xp.p, L.xl.p, L.p0.p, L.p1.p, L.p2.p,
                    resq + 4, 4, resq, d_fail.p + q, h_mail_dev + 32*q, multi() ? MAIL_TICKET : 6, L.pre_ticket, false, true, false};
@@ -2880,11 +2821,11 @@ int mcp_ba::cancel_spec_trials() {
 // One trial ahead: when the host turns to trial q - 1, the step of system q (if it was solved speculatively on another stream) is
 // applied and evaluated there already, so that a rejection of q - 1 finds q's result waiting.
 int mcp_ba::run_ahead(int q) {
-  if (!spec_trials || !use_mailbox || prm.profile) return 0;
-  if (multi() && overlap_spec != 1) return 0;       // (the speculative lane belongs to the second stream)
+  if (!hk.spec_trials || !hk.use_mailbox || prm.profile) return 0;
+  if (multi() && hk.overlap_spec != 1) return 0;       // (the speculative lane belongs to the second stream)
   if (!spec_pending && !spec3_pending && q >= spec2_from) { /* its stream has been joined already: still valid to use it */ }
   if (q < spec2_from || q >= batch_n || lane[q].pre_run) return 0;
-  if (spec_trials >= 2 && !multi() && lane[q].st_tr && q > spec2_from) {      // (the first one stays on the chain's own stream: hardware queues are few)
+  if (hk.spec_trials >= 2 && !multi() && lane[q].st_tr && q > spec2_from) {      // (the first one stays on the chain's own stream: hardware queues are few)
     // its own stream, ordered behind the chain that produced system q: the trials ahead run side by side
     hipEvent_t done = (q >= spec3_from) ? ev_spec3 : ev_spec;
     HIPCK(hipStreamWaitEvent(lane[q].st_tr, done, 0));
@@ -2901,7 +2842,7 @@ int mcp_ba::read_results(int count) {
 // buildSystem at the current state (sigma block must be current)
 int mcp_ba::linearize() {
   mark("lin_wait", st);
-  if ((lin_join_full ? join_spec() : join_spec_lin())) return -1;        // the second stream may still be reading the previous linearisation
+  if ((pk.lin_join_full ? join_spec() : join_spec_lin())) return -1;        // the second stream may still be reading the previous linearisation
   mark("lin_go", st);
   spec_ok = false;                   // a speculative solve belongs to the linearisation it was built from
   tic(ST_LIN);
@@ -2924,7 +2865,7 @@ int mcp_ba::linearize() {
     hipLaunchKernelGGL(k_linearize_pipe, dim3(ngroup), dim3(64), (size_t)std::max(grp_blk_max, 1)*36*sizeof(double), st, P,
                        d_pt[cur].p, d_first[cur].p, d_second[cur].p, sig(), d_stU.p, d_stb.p, d_V.p, d_g.p, d_W.p, d_fail.p);
   else if (lk == MCP_BA_LIN_GROUP)
-    hipLaunchKernelGGL(k_linearize_group, dim3(ngroup), dim3(64), getenv("MCP_BA_TEST_REFUSE_LAUNCH") ? ((size_t)1 << 20) /* test hook: more LDS than a compute unit has */ : (size_t)std::max(grp_blk_max, 1)*36*sizeof(double), st, P,
+    hipLaunchKernelGGL(k_linearize_group, dim3(ngroup), dim3(64), knobs::test_refuse_launch() ? ((size_t)1 << 20) /* test hook: more LDS than a compute unit has */ : (size_t)std::max(grp_blk_max, 1)*36*sizeof(double), st, P,
                        d_pt[cur].p, d_first[cur].p, d_second[cur].p, sig(), d_stU.p, d_stb.p, d_V.p, d_g.p, d_W.p, d_fail.p);
   if (ngroup) note_launch("k_linearize_group / k_linearize_quad");
   fail_clean = ngroup > 0;            // (the group kernel has cleared the failure flags: the first solve of this linearisation needs no fill)
@@ -2979,7 +2920,7 @@ int mcp_ba::build_system(int nsys, SysBatch& sbfull, int q0, hipStream_t on) {
     unsigned long long pr[64]; hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_sch_prof), sizeof pr);
     double a[8] = {0}; int cnt = 0;
     for (int b2 = 0; b2 < 8; ++b2) { const unsigned long long* q = pr + 8*b2; if (!q[0]) continue; for (int i2 = 0; i2 < 8; ++i2) a[i2] += (double)q[i2]; ++cnt; }
-    if (cnt && sch4_on && sch4_ok)
+    if (cnt && hk.sch4_on && sch4_ok)
       fprintf(stderr, "[sch4 prof] prologue %.0f  clear+scatter %.0f  barrier %.0f  prefetch+mfma %.0f  barrier %.0f  flush %.0f  (cycles of wavefront 0, %d systems, %d groups)\n",
               a[0]/cnt, a[1]/cnt, a[2]/cnt, a[3]/cnt, a[4]/cnt, a[5]/cnt, nsys, cnt);
     else if (cnt) fprintf(stderr, "[sch prof] prologue %.0f  inverse+barrier %.0f  scatter %.0f  prefetch+barrier %.0f  mfma %.0f  rhs %.0f  barrier+clear %.0f  flush %.0f  (cycles, %d systems, %d groups)\n",
@@ -3076,7 +3017,7 @@ int mcp_ba::wait_head(int q) {
   const auto w0 = std::chrono::steady_clock::now();
   for (unsigned long long spins = 0; __atomic_load_n(tk, __ATOMIC_ACQUIRE) != lane[q].head_ticket; ++spins) {
     if ((spins & 0xfff) == 0xfff) {
-      if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count() > timeout_ms) return watchdog_fail("the status word of an iteration head");
+      if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count() > hk.timeout_ms) return watchdog_fail("the status word of an iteration head");
       std::this_thread::yield();
     }
   }
@@ -3088,16 +3029,16 @@ int mcp_ba::wait_head(int q) {
 // MCP_BA_GRAPH=1 -- one launch of a graph captured the first time this sub-batch shape occurs (same buffers, same plan every time).
 // With two chains in flight the host's enqueue rate decides when the second one can start; a graph hands it over at once.
 int mcp_ba::solve_chain(hipStream_t s, int n, int q0) {
-  if (use_graph && !prm.profile) {
+  if (pk.use_graph && !prm.profile) {
     hipGraphExec_t& ex = chain_exec[n][q0];
     if (!ex) {
       hipGraph_t g = nullptr;
       if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
         chol_factor(s, plan, d_red.p, d_fail.p, n, red_stride, q0);
         chol_back(s, plan, d_red.p, n, red_stride, q0);
-        if (hipStreamEndCapture(s, &g) != hipSuccess || !g || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) { ex = nullptr; use_graph = 0; }
+        if (hipStreamEndCapture(s, &g) != hipSuccess || !g || hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) != hipSuccess) { ex = nullptr; pk.use_graph = 0; }
         if (g) (void)hipGraphDestroy(g);
-      } else use_graph = 0;
+      } else pk.use_graph = 0;
       (void)hipGetLastError();
     }
     if (ex) { HIPCK(hipGraphLaunch(ex, s)); return 0; }
@@ -3127,7 +3068,7 @@ int mcp_ba::solve_trial(double lam, bool& ok2, double ni) {
   int tr = 0; bool with_head = false;
   if (enqueue_main_trial(lam, tr, with_head)) return -1;
   mark("trial_end", st);
-  const bool mailbox = use_mailbox && !prm.profile;
+  const bool mailbox = hk.use_mailbox && !prm.profile;
   if (head_ahead_want && mailbox && !multi() && small_mode()) { if (head_ahead(tr)) return -1; mark("head_ahead", st); }
   if (finish_deferred_chains(df)) return -1;
   if (run_trials_ahead(df)) return -1;
@@ -3153,8 +3094,8 @@ int mcp_ba::start_batch(double lam, double ni, Deferred& df) {
   // One rank, one-launch factorisation: every system of the batch has its own critical workgroup, four systems take the time of
   // one, so the batch stays on the main stream (measured: 990 vs 940 LM it/s; MCP_BA_OVERLAP=1 splits it as the per-step kernels
   // want it).  Several ranks: one speculative stream, the one lane 1 belongs to.
-  const int ov_single = (overlap_auto && plan.use_persist && plan.persist.ok) ? 0 : overlap_spec;
-  const int ov = multi() ? std::min(overlap_spec, 1) : ov_single;
+  const int ov_single = (hk.overlap_auto && plan.use_persist && plan.persist.ok) ? 0 : hk.overlap_spec;
+  const int ov = multi() ? std::min(hk.overlap_spec, 1) : ov_single;
   const bool split = ov && nsys > 1 && np > 0 && st2;
   if (split ? solve_split(nsys, ov, sb, df) : solve_batched(nsys, sb, df)) return -1;
   spec_ok = (nsys > 1);
@@ -3164,9 +3105,9 @@ int mcp_ba::start_batch(double lam, double ni, Deferred& df) {
 // system 0 -- the one this trial needs -- alone on the main stream; the speculative systems behind the fork on the second
 // stream.  Same kernels on the same data as the batched path: the numbers do not depend on which stream produced them.
 int mcp_ba::solve_split(int nsys, int ov, SysBatch& sb, Deferred& df) {
-  // main_sys systems stay on the main stream: 1 = only the trial's own; 2 = also the first speculative one, so that a second trial
+  // hk.main_sys systems stay on the main stream: 1 = only the trial's own; 2 = also the first speculative one, so that a second trial
   // never waits for the other stream (its system comes out of the same launches as the first trial's)
-  const int n1 = std::min(std::max(main_sys, 1), nsys - 1);
+  const int n1 = std::min(std::max(hk.main_sys, 1), nsys - 1);
   HIPCK(hipEventRecord(ev_fork, st));
   plan.persist.batch_sys = nsys;
   mark("fork", st);
@@ -3174,7 +3115,7 @@ int mcp_ba::solve_split(int nsys, int ov, SysBatch& sb, Deferred& df) {
   mark("main_built", st);
   // MCP_BA_SPEC_DELAY=1: the speculative systems' Schur complements start only when the trial's own is through (they share the
   // compute units otherwise: 85 us alone, 170 us side by side) -- the first trial sooner, a rejected trial's successor later
-  if (spec_delay) HIPCK(hipEventRecord(ev_fork, st));
+  if (hk.spec_delay) HIPCK(hipEventRecord(ev_fork, st));
   // host enqueue order: the other streams' Schur complements right away (they start at the fork on the device and run beside
   // the main stream's), their factorisation chains only after this trial's own chain and tail (finish_deferred_chains) -- the main
   // stream never runs dry behind the ~45 launches of another chain
@@ -3194,7 +3135,7 @@ int mcp_ba::solve_batched(int nsys, SysBatch& sb, Deferred& df) {
   if (build_system(nsys, sb)) return -1;
   if (!np) return 0;
   if (solve_chain(st, nsys, 0)) return -1;
-  if (st2 && nsys > 1 && !multi() && spec_trials && use_mailbox && !prm.profile) {
+  if (st2 && nsys > 1 && !multi() && hk.spec_trials && hk.use_mailbox && !prm.profile) {
     // every system of the batch is solved: while this trial runs on the main stream, the next one's step is applied and evaluated
     // on the second stream (enqueue_spec_trial), so that a rejection finds its result waiting
     HIPCK(hipEventRecord(ev_fork, st)); HIPCK(hipStreamWaitEvent(st2, ev_fork, 0));
@@ -3206,7 +3147,7 @@ int mcp_ba::solve_batched(int nsys, SysBatch& sb, Deferred& df) {
 // -> mailbox 0 with the iteration-start block
 int mcp_ba::enqueue_main_trial(double lam, int& tr, bool& with_head) {
   tr = cand(sys_cur); last_tr = tr; last_xp = &d_xp_cand; last_xl = &d_xl;
-  const bool mailbox = use_mailbox && !prm.profile;
+  const bool mailbox = hk.use_mailbox && !prm.profile;
   mail_ticket0 = ++mail_ticket;
   with_head = head_ahead_want && mailbox && !small_mode() && large_heads();
   const TrialIo io{st, 0, sys_cur, tr, lam, rhs(), bp(), Vinv(), d_xp_cand.p, d_xl.p, d_part0.p, d_part1.p, d_part2.p,
@@ -3231,7 +3172,7 @@ int mcp_ba::finish_deferred_chains(const Deferred& df) {
 int mcp_ba::run_trials_ahead(const Deferred& df) {
   if (df.nsys) {
     if (run_ahead(1)) return -1;
-    if (spec_trials >= 2 && !multi()) for (int q = 2; q < df.nsys; ++q) if (run_ahead(q)) return -1;
+    if (hk.spec_trials >= 2 && !multi()) for (int q = 2; q < df.nsys; ++q) if (run_ahead(q)) return -1;
   } else if (df.ahead_single) { if (run_ahead(1)) return -1; }
   return 0;
 }
@@ -3242,7 +3183,7 @@ int mcp_ba::collect_trial(int q, bool ahead, double lam, bool& ok2, double ni) {
     last_tr = cand(q); last_xp = &lane[q].xp; last_xl = &lane[q].xl;
     if (run_ahead(q + 1)) return -1;
     if (wait_mail(q, lane[q].pre_ticket, multi() ? MAIL_TICKET : 6)) return -1;
-  } else if (use_mailbox && !prm.profile) {
+  } else if (hk.use_mailbox && !prm.profile) {
     // the block (trial results [0..7], iteration-start block [24..28]) is already on its way to the host
     if (wait_mail(0, mail_ticket0, multi() ? MAIL_TICKET : 29)) return -1;
   } else if (read_results(MAIL_TICKET)) return -1;          // trial results [0..7] and, for compute(), the iteration-start block [24..28]
@@ -3346,7 +3287,7 @@ int mcp_ba::iteration_head(LmRun& R, LmIter& I) {
   acc_head_q = -1;
   for (int q = 0; q < MAX_SYS; ++q) lane[q].head_enq = false;      // (what this iteration's trials enqueue goes to the other parity's slots)
   head_par = it & 1;
-  head_ahead_want = (small_mode() || large_heads()) && use_mailbox && !prm.profile && it + 1 < R.n_iter;
+  head_ahead_want = (small_mode() || large_heads()) && hk.use_mailbox && !prm.profile && it + 1 < R.n_iter;
   if (I.head_done) { }
   else if (small_mode()) { if (head_small(cur)) return MCP_ERR_RUNTIME; }
   else if (use_head_large()) { if (head_large(cur, RS, nullptr)) return MCP_ERR_RUNTIME; }
@@ -3433,13 +3374,13 @@ int mcp_ba::take_start(LmIter& I) {
 }
 // one trial at the current lambda, and what the schedule makes of it
 int mcp_ba::run_trial(LmRun& R, LmIter& I) {
-  static const bool trace_trials = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 3; }();
+  static const bool trace_trials = knobs::trace_level() >= 3;
   bool ok2 = true;
   const int pre0 = dbg_pre;
   if (solve_trial(lambda, ok2, R.ni)) return MCP_ERR_RUNTIME;
   if (trace_trials) { char b[64]; snprintf(b, sizeof b, " %s%.0f", dbg_pre != pre0 ? "a" : (sys_cur ? "s" : "m"), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - I.t0).count()); I.trace_line += b; }
   if (I.start_pending && take_start(I)) return MCP_ERR_RUNTIME;
-  if (test_fail_trial > 0 && ++test_trial_no == test_fail_trial) ok2 = false;      // (test hook: this trial's factorisation "failed")
+  if (hk.test_fail_trial > 0 && ++test_trial_no == hk.test_fail_trial) ok2 = false;      // (test hook: this trial's factorisation "failed")
   double scale = 0, ss = 0;
   I.trial_chi_raw = h_res[0];
   if (ok2) {
@@ -3532,9 +3473,9 @@ void mcp_ba::post_iteration(LmRun& R, LmIter& I) {
 }
 // MCP_BA_EVT=1: what the solve's scheduling did, the device-side profiles of the head kernels (if compiled in), the time stamps
 void mcp_ba::dump_profiles() {
-  if (evt_debug) { fprintf(stderr, "[evt] iteration heads enqueued ahead and used: %d (median prediction missed: %d)\n", dbg_head_ahead, dbg_head_miss); dbg_head_ahead = 0; dbg_head_miss = 0; }
+  if (hk.evt_debug) { fprintf(stderr, "[evt] iteration heads enqueued ahead and used: %d (median prediction missed: %d)\n", dbg_head_ahead, dbg_head_miss); dbg_head_ahead = 0; dbg_head_miss = 0; }
 #ifdef MCP_HL_PROF
-  if (evt_debug) {
+  if (hk.evt_debug) {
     (void)hipDeviceSynchronize();
     long long pr[16]; (void)hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_hl_prof), sizeof pr);
     fprintf(stderr, "[hl prof] workgroup 0 (10 ns ticks): A %lld | barrier %lld | B %lld | barrier %lld | C %lld | barrier %lld | D %lld | barrier %lld | E %lld | last workgroup done +%lld\n",
@@ -3546,20 +3487,20 @@ void mcp_ba::dump_profiles() {
   }
 #endif
 #ifdef MCP_HS_PROF
-  if (evt_debug) {
+  if (hk.evt_debug) {
     (void)hipDeviceSynchronize();
     unsigned long long pr[16]; (void)hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_hs_prof), sizeof pr);
     fprintf(stderr, "[hs prof] sweep1 %llu  find0 %llu  (sweep1b) %llu  find1 %llu  sweep2 %llu  lds-select %llu  sigma %llu  sum-sweep %llu  final %llu  (clock64 ticks; %llu candidates)\n",
             pr[1] - pr[0], pr[2] - pr[1], pr[3] - pr[2], pr[4] - pr[3], pr[5] - pr[4], pr[6] - pr[5], pr[7] - pr[6], pr[8] - pr[7], pr[9] - pr[8], pr[10]);
   }
 #endif
-  if (evt_debug) { fprintf(stderr, "[evt] trials evaluated ahead and used: %d; host wait on mailbox: own trials %.0f us, ahead trials %.0f us\n", dbg_pre, dbg_wait_us[0], dbg_wait_us[1]); dbg_pre = 0; dbg_wait_us[0] = dbg_wait_us[1] = 0; }
+  if (hk.evt_debug) { fprintf(stderr, "[evt] trials evaluated ahead and used: %d; host wait on mailbox: own trials %.0f us, ahead trials %.0f us\n", dbg_pre, dbg_wait_us[0], dbg_wait_us[1]); dbg_pre = 0; dbg_wait_us[0] = dbg_wait_us[1] = 0; }
   evt_flush();
 }
 // the final statistics, the return code (as g2o optimize(): iterations run, -1 for none unless aborted from outside), the state
 // back on the host, and what the launches and the stage events of this solve reported
 int mcp_ba::end_solve(LmRun& R, int nCounter) {
-  static const bool trace_compute = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
+  static const bool trace_compute = knobs::trace_level() >= 2;
   if (join_spec()) return MCP_ERR_RUNTIME;
   if (join_sum()) return MCP_ERR_RUNTIME;
   dump_profiles();
@@ -3666,7 +3607,7 @@ int mcp_ba::final_sigma_and_export(int nCounter) {
   if (read_results(13)) return -2;
   { unsigned long long b; std::memcpy(&b, &h_res[0], 8); if (b == HL_FAILED_BITS) { set_err("the final statistics (k_head_large) gave up at a barrier"); return -2; } }
   exported = true;
-  { static const bool tr = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
+  { static const bool tr = knobs::trace_level() >= 2;
     if (tr) fprintf(stderr, "[final] median + sums + export enqueued in %.3f ms, waited for %.3f ms\n", std::chrono::duration<double, std::milli>(tf1 - tf0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf1).count()); }
   }
   return 0;
@@ -3712,7 +3653,7 @@ void mcp_ba::outlier_list() {
     outliers[3*k + 1] = poses[chains[m.chain].v[0]].id;      // vertices().front(), :1394
     outliers[3*k + 2] = m.cam;
   }
-  { static const bool tr = [] { const char* e = getenv("MCP_BA_TRACE"); return e && atoi(e) >= 2; }();
+  { static const bool tr = knobs::trace_level() >= 2;
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     if (tr) fprintf(stderr, "[final] outliers: set bits to add order %.3f ms, index list %.3f ms, %zu triples %.3f ms\n", ms(tq0, tq1), ms(tq1, tq2), no, ms(tq2, std::chrono::steady_clock::now())); }
 }
@@ -3789,42 +3730,28 @@ mcp_ba* mcp_ba_create(const mcp_camera* cams, int ncam, int use_robust, int use_
   h->cams.assign(cams, cams + ncam);
   std::memset(&h->timing, 0, sizeof h->timing);
   std::memset(&h->P, 0, sizeof h->P);
-  const bool use_pool = [] { const char* e = getenv("MCP_BA_STREAM_POOL"); return e ? atoi(e) != 0 : true; }();
-  SolverStreams* pool = use_pool ? &solver_streams(dev) : nullptr;
+  SolverStreams* pool = h->hk.stream_pool ? &solver_streams(dev) : nullptr;
   if (pool && pool->ok) { h->pooled = true; h->st = pool->main; }
   else if (hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) { set_err("hipStreamCreate failed"); delete h; return nullptr; }
-  { const char* e = getenv("MCP_BA_OVERLAP"); if (e) { h->overlap_spec = atoi(e); h->overlap_auto = false; } }
-  { const char* e = getenv("MCP_BA_MAILBOX"); if (e) h->use_mailbox = atoi(e); }
-  { const char* e = getenv("MCP_BA_MAIN_SYS"); if (e) h->main_sys = atoi(e); }
-  { const char* e = getenv("MCP_BA_EVT"); if (e) h->evt_debug = atoi(e); }
-  { const char* e = getenv("MCP_BA_SPEC_TRIALS"); if (e) h->spec_trials = atoi(e); }
-  { const char* e = getenv("MCP_BA_HEAD_AHEAD"); if (e) h->large_head_ahead = atoi(e); }
-  { const char* e = getenv("MCP_BA_NEAR_MISS"); if (e) h->near_miss_on = atoi(e); }
-  { const char* e = getenv("MCP_BA_FORCE_MULTI"); if (e) h->force_multi = atoi(e); }
-  { const char* e = getenv("MCP_BA_TEST_FAIL_TRIAL"); if (e) h->test_fail_trial = atoi(e); }
-  { const char* e = getenv("MCP_BA_SPEC_DELAY"); if (e) h->spec_delay = atoi(e); }
-  { const char* e = getenv("MCP_BA_SMALL"); if (e) h->small_on = atoi(e); }
-  { const char* e = getenv("MCP_BA_SELECT_RIDE"); if (e) h->sel_ride = atoi(e); }
-  { const char* e = getenv("MCP_BA_TIMEOUT_MS"); if (e && atof(e) > 0) h->timeout_ms = atof(e); }
   for (int q = 0; q < mcp::MAX_SYS; ++q) if (hipEventCreateWithFlags(&h->lane[q].ev_tr, hipEventDisableTiming) != hipSuccess ||
                                               hipEventCreateWithFlags(&h->lane[q].ev_wf, hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); delete h; return nullptr; }
   // (the runtime multiplexes streams onto a handful of hardware queues -- GPU_MAX_HW_QUEUES, 4 by default: main, speculative and two
   // trial streams use them up; a third stream for MCP_BA_OVERLAP=2 is only created when asked for)
   if (h->pooled) {
-    if (h->spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) h->lane[q].st_tr = pool->tr[q];
-    if (h->overlap_spec) { h->st2 = pool->spec; if (h->overlap_spec >= 2) h->st3 = pool->spec3; }
+    if (h->hk.spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) h->lane[q].st_tr = pool->tr[q];
+    if (h->hk.overlap_spec) { h->st2 = pool->spec; if (h->hk.overlap_spec >= 2) h->st3 = pool->spec3; }
   } else {
-    if (h->spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) if (hipStreamCreateWithFlags(&h->lane[q].st_tr, hipStreamNonBlocking) != hipSuccess) { set_err("hipStreamCreate failed"); delete h; return nullptr; }
-    if (h->overlap_spec && (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess || (h->overlap_spec >= 2 && hipStreamCreateWithFlags(&h->st3, hipStreamNonBlocking) != hipSuccess))) { set_err("second stream could not be created"); delete h; return nullptr; }
+    if (h->hk.spec_trials >= 2) for (int q = 2; q < mcp::MAX_SYS; ++q) if (hipStreamCreateWithFlags(&h->lane[q].st_tr, hipStreamNonBlocking) != hipSuccess) { set_err("hipStreamCreate failed"); delete h; return nullptr; }
+    if (h->hk.overlap_spec && (hipStreamCreateWithFlags(&h->st2, hipStreamNonBlocking) != hipSuccess || (h->hk.overlap_spec >= 2 && hipStreamCreateWithFlags(&h->st3, hipStreamNonBlocking) != hipSuccess))) { set_err("second stream could not be created"); delete h; return nullptr; }
   }
-  if (h->large_head_ahead) {
+  if (h->hk.large_head_ahead) {
     // the head stream: the pool's fourth side stream (measured to overlap with the main one if a hardware queue was left), else an own one
     if (h->pooled && pool->spec3 && pool->spec3 != h->st3) h->st_h = pool->spec3;
     else if (hipStreamCreateWithFlags(&h->st_h, hipStreamNonBlocking) == hipSuccess) h->st_h_own = true;
     else { (void)hipGetLastError(); h->st_h = nullptr; }
     for (int q = 0; q < mcp::MAX_SYS; ++q) if (hipEventCreateWithFlags(&h->lane[q].head_ev, hipEventDisableTiming) != hipSuccess) { set_err("hipEventCreate failed"); delete h; return nullptr; }
   }
-  if (h->overlap_spec && (
+  if (h->hk.overlap_spec && (
                           hipEventCreateWithFlags(&h->ev_spec3, hipEventDisableTiming) != hipSuccess ||
                           hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
                           hipEventCreateWithFlags(&h->ev_spec, hipEventDisableTiming) != hipSuccess ||
@@ -3868,7 +3795,7 @@ int mcp_ba_add_meas(mcp_ba* h, const int* chain, int n, int point_id, const doub
 }
 int mcp_ba_add_points(mcp_ba* h, int count, const double* x, const int* chains, int stride, const int* chain_len,
                       const unsigned char* fixed, int* ids_out) {
-  static const bool trace = getenv("MCP_BA_TRACE") != nullptr;
+  static const bool trace = knobs::trace_level() >= 1;
   const auto t0 = std::chrono::steady_clock::now();
   // (reserve(size + count) allocates exactly that much with libstdc++ -- an adapter adding points in many small batches would
   //  reallocate and copy the whole arrays every call; grow geometrically instead, and only when the batch does not fit)
@@ -3890,7 +3817,7 @@ int mcp_ba_add_measurements(mcp_ba* h, int count, const int* chains, int stride,
   // resolved read-only by the threads; rows with a new chain are completed afterwards in row order, so chains are numbered as
   // a serial replay numbers them.
   if (count <= 0) return 0;
-  static const bool trace = getenv("MCP_BA_TRACE") != nullptr;
+  static const bool trace = knobs::trace_level() >= 1;
   const auto t0 = std::chrono::steady_clock::now();
   struct Tr { bool on; int n; std::chrono::steady_clock::time_point t0; double sized = 0; ~Tr() { if (on) fprintf(stderr, "[mcp_ba add] %d measurements %.3f ms (arrays sized after %.3f)\n", n, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), sized); } } tr{trace, count, t0};
   const size_t n0 = h->meas.size();
@@ -4148,8 +4075,8 @@ int mcp_ba_debug_head(mcp_ba* h, int route, const double* chi2, int n, double pr
   else if (route == MCP_BA_HEAD_RANKS) { if (!h->multi()) why = "no all-reduce hook or communicator is installed (or one rank without MCP_BA_FORCE_MULTI=1)"; }
   else if (route == MCP_BA_HEAD_RIDE) {
     if (!h->multi()) why = "no all-reduce hook or communicator is installed (or one rank without MCP_BA_FORCE_MULTI=1)";
-    else if (!h->sel_ride) why = "MCP_BA_SELECT_RIDE=0";
-    else if (!h->use_mailbox || !h->h_mail_dev) why = "MCP_BA_MAILBOX=0";
+    else if (!h->hk.sel_ride) why = "MCP_BA_SELECT_RIDE=0";
+    else if (!h->hk.use_mailbox || !h->h_mail_dev) why = "MCP_BA_MAILBOX=0";
   }
   else if (route == MCP_BA_HEAD_SMALL) { if (!h->small_mode()) why = "not a small bundle (more than SMALL_MEAS measurements or SMALL_CHAINS chains, several ranks, or MCP_BA_SMALL=0)"; }
   else if (route == MCP_BA_HEAD_AHEAD) { if (!h->large_heads()) why = "MCP_BA_HEAD_AHEAD is not set, or the map is a small bundle or has several ranks"; }
@@ -4532,8 +4459,8 @@ int mcp_dense_spd_solve(const double* A, int n, const double* b, double* x) {
   CholPlan plan;
   std::vector<unsigned char> pattern;
 #ifdef MCP_CHOL_PROF
-  if (const char* e = getenv("MCP_CHOL_TEST_BAND")) {      // profiling only: a banded + bordered tile pattern like a loop trajectory's (results are not checked)
-    const int bw = atoi(e), ntc = (n + CH_NB - 1)/CH_NB;
+  if (int bw = 0; knobs::chol_test_band(&bw)) {      // profiling only: a banded + bordered tile pattern like a loop trajectory's (results are not checked)
+    const int ntc = (n + CH_NB - 1)/CH_NB;
     pattern.assign((size_t)ntc*ntc, 0);
     for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (i - j <= bw || i >= ntc - bw) pattern[(size_t)i*ntc + j] = 1;
   }

@@ -27,6 +27,7 @@
 #include "track_recover_kernels.h"
 #include "track_cov_kernels.h"
 #include "ba_bridge.h"
+#include "mcp_knobs.h"
 #include "ba_select.h"
 #include "map_graph_kernels.h"
 #include "map_graph_lists.h"
@@ -252,7 +253,7 @@ static int lite_batch_enqueue(int ncam, mcp_kf* const* kfs, const uint8_t* const
   }
   if (ride && (*ride)(B)) return -1;
   const int up = (B.up_n8[0] > 0 || B.up_n8[1] > 0 || B.up_n8[2] > 0 || B.up_n8[3] > 0) ? 1 : 0;
-  static const bool one_launch = [] { const char* e = getenv("MCP_IMG_ROW_TABLES"); return e ? atoi(e) != 0 : true; }();      // (0: k_row_count + k_row_compact, the round-5 pair)
+  static const bool one_launch = mcp::knobs::img_row_tables();      // (0: k_row_count + k_row_compact, the round-5 pair)
   if (one_launch) hipLaunchKernelGGL(k_row_tables, dim3((maxh + 3)/4, MCP_LEVELS, ncam + up), dim3(256), 0, st, B);
   else {
     hipLaunchKernelGGL(k_row_count, dim3((maxh + 3)/4, MCP_LEVELS, ncam + up), dim3(256), 0, st, B);
@@ -454,7 +455,7 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
   RefineScratch& rs = refine_scratch();
   const RefineBlock O(n_iter, ncam);
   const size_t blk = O.bytes;
-  static const int use_regs = [] { const char* e = getenv("MCP_TRACK_REFINE_REGS"); return e ? atoi(e) : 1; }();
+  static const int use_regs = mcp::knobs::track_refine_regs();
   static thread_local unsigned long long regs_refused_mask = 0;      // devices that took the attribute and then refused the launch
   int cur_dev = 0; (void)hipGetDevice(&cur_dev);
   const unsigned long long dbit = 1ull << (cur_dev & 63);
@@ -462,7 +463,7 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
   bool regs = use_regs && regs_ok && n <= PRR_THREADS*PRR_PPT && ncam <= PRR_CAMS;          // the points fit the register-resident kernel, the rig its LDS
   // many points: the iterations over several workgroups (k_pose_refine_multi); MCP_TRACK_REFINE_MULTI = 0 never, 1 whenever the
   // points do not fit the register-resident kernel (default), 2 always
-  const int use_multi = [] { const char* e = getenv("MCP_TRACK_REFINE_MULTI"); return e ? atoi(e) : 1; }();
+  const int use_multi = mcp::knobs::track_refine_multi();
   const bool multi = n_iter <= PRM_MAX_ITER && ((use_multi == 2 && n >= 64) || (use_multi == 1 && !regs && n > PRR_THREADS*PRR_PPT));
   if (multi) regs = false;
   rs.last_multi = multi;
@@ -501,12 +502,12 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
   if (multi) {
     if (rs.dprm.alloc(1)) return -1;
     ICK(hipMemsetAsync(rs.dprm.p, 0, sizeof(PrmScratch), st));
-    const int ppw = [] { const char* e = getenv("MCP_TRACK_REFINE_PPW"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();      // points per workgroup (measured at 8000 points: 128: 407 us, 256: 337, 512: 311, 1024: 322)
+    const int ppw = mcp::knobs::track_refine_ppw();      // points per workgroup
     const int nwg = std::max(1, std::min(PRM_MAX_WG, (n + ppw - 1)/ppw));
     // the median: per-digit global histograms (default), or -- MCP_TRACK_REFINE_GATHER=1, up to 16k points -- all squared errors through
     // every workgroup's LDS with one barrier.  Measured at 8000 points in 16 workgroups: 311 us vs 322 us per ten iterations; the
     // redundant 8000-key selection in every workgroup costs what the two extra barriers of the histogram form cost.
-    const bool gather = n <= PRM_GATHER_MAX && [] { const char* e = getenv("MCP_TRACK_REFINE_GATHER"); return e ? atoi(e) != 0 : false; }();
+    const bool gather = n <= PRM_GATHER_MAX && mcp::knobs::track_refine_gather();
     size_t dyn = 0;
     if (gather) {
       if (rs.de2all.alloc(2*(size_t)n)) return -1;
@@ -586,7 +587,7 @@ static int refine_collect(int n, int n_iter, int ncam, int est, hipStream_t st, 
     return 0;
   };
   if (fetch()) return -1;
-  if (*prm_err || (rs.last_multi && getenv("MCP_TRACK_TEST_PRM_GIVEUP"))) {
+  if (*prm_err || (rs.last_multi && mcp::knobs::track_test_prm_giveup())) {
     // a workgroup gave up waiting for the others: the frame is not lost, one workgroup redoes the iterations
     if (refine_redo_single(n, n_iter, ncam, est, st) || fetch()) return -1;
   }
@@ -1555,8 +1556,7 @@ int mcp_map_points_get_states(const mcp_map_points* m, int cam, int first, int c
 // mcp_track_map may use the register-resident pose kernel (MCP_TRACK_REFINE_REGS is read at every call here)
 static bool tm_regs_ok() {
   int dev = 0; (void)hipGetDevice(&dev);
-  const char* e = getenv("MCP_TRACK_REFINE_REGS");
-  return pose_regs_attr(dev) && (e ? atoi(e) != 0 : true);
+  return pose_regs_attr(dev) && mcp::knobs::track_refine_regs() != 0;
 }
 
 // what mcp_track_frame_motion adds to the frame: the 40x30 cameras, the motion model's inputs and its report
