@@ -819,7 +819,8 @@ int mcp_map_graph_set_mkfs(mcp_map_graph*, int first, int count, const double* b
 int mcp_map_graph_update_mkfs(mcp_map_graph*, int count, const int* slots, const double* base_from_world, const int* flags,
                               const uint8_t* kf_active, const double* kf_depth_mean);
 /* graph columns of the distinct table rows rows[0..count): the patch source (MKF slot, camera index) and MCP_GP_* flags.  A row never
- * written is bad.  src_mkf < 0 (no source) is allowed for fixed points only; a row past the table's size is refused. */
+ * written is bad.  src_mkf < 0 (no source) is allowed for fixed points only; a row past the table's size is refused.  A row written here
+ * loses its pending mark (mcp_map_cull_sweep's report, below): the host knows what it writes. */
 int mcp_map_graph_update_points(mcp_map_graph*, int count, const int* rows, const int* src_mkf, const int* src_cam, const int* flags);
 /* appends measurements in the caller's order and returns the store index of the first new one.  uv: level-0 v2RootPos; source:
  * Measurement::eSource as an int, stored and returned, not interpreted.  The caller guarantees one entry per (mkf, cam, row), as MeasPtrMap
@@ -1040,6 +1041,96 @@ int mcp_parcel_commit_host(int n, const mcp_parcel_entry* entries, int n_rows, c
                            const int* src_mkf, const int* src_cam, int n_lanes, const int* lane_mkf, const int* lane_cam,
                            const mcp_parcel_commit_params*, int first, uint8_t* verdict, mcp_store_entry* appended,
                            mcp_parcel_commit_result* res, int* lane_appended /* n_lanes or NULL */);
+
+/* ---- Outliers and bad points on the device ---------------- src/MapMakerServerBase.cc:1198-1238, src/MapMakerClientBase.cc:73-108, src/Map.cc:93-116
+ * What the map maker does with an adjustment's outliers (MapMakerServerBase::HandleOutliers) and the point half of MapMaker::HandleBadEntities
+ * (MarkDanglersAsBad, MarkOutliersAsBad, Map::MoveBadPointsToTrash), over what the graph and its table hold already: the store with `source`
+ * and `alive`, the MKF flags, the point flags, the table's (inlier, outlier) column and its `usable` byte.  What comes back is outlier-sized or
+ * bad-point-sized, never map-sized.  The graph's conventions hold: the table's stream, the caller serialises, every result an integer, counts
+ * per workgroup and ranks by index, so nothing depends on the order workgroups are dispatched in.  Only these calls read a meaning into the
+ * store's `source`: Measurement::eSource (include/mcptam/KeyFrame.h:109); every other call stores and returns it as given.
+ * REFUSALS of every call below: -1 (NULL for the view), mcp_last_error(), nothing enqueued, graph, store and table unchanged, outputs untouched. */
+#define MCP_SRC_TRACKER  0
+#define MCP_SRC_REFIND   1
+#define MCP_SRC_ROOT     2
+#define MCP_SRC_TRAIL    3
+#define MCP_SRC_EPIPOLAR 4
+
+/* HandleOutliers.  keys (mkf slot, cam, row)[0..n) in the order the solver listed its outliers (mcp_ba_get_outliers, decoded by the adapter).
+ * THE ORDER MATTERS: the reference re-reads GoodMeasCount() after every erasure, so entry i is judged on the state entries 0..i-1 left.  Good
+ * count: mcp_map_graph_good_counts' -- the live entries of the row whose MKF is present and not bad.  Entry i gets the first verdict that applies:
+ *   MCP_CULL_MISSING      no live store entry has the key; or the row is outside the table or was never written, or the slot is not present.
+ *                         No effect.  (DEVIATION: the reference would dereference the NULL that kf.mmpMeasurements[&point] default-inserts.)
+ *   MCP_CULL_FIXED        the row is MCP_GP_FIXED.  No effect; n_fixed_rows counts the distinct such rows (spFixedOutliers).
+ *   MCP_CULL_POINT_BAD    the row's good count is <= bad_good_count, or the entry's source is MCP_SRC_ROOT -- whether or not the row is bad
+ *                         already (:1216-1220).  The row's column gets MCP_GP_BAD; the entry stays alive, as in the reference: the sweep erases it.
+ *   MCP_CULL_RETRY        the row is not bad and the source is MCP_SRC_TRACKER or MCP_SRC_EPIPOLAR.  The entry dies; the row's good count drops
+ *                         by one iff the entry's MKF is present and not bad.  (The adapter puts the pair on mlFailureQueue.)
+ *   MCP_CULL_NEVER_RETRY  the row is not bad and the source is anything else.  As RETRY.  (The adapter inserts the keyframe into spNeverRetryKFs.)
+ *   MCP_CULL_ALREADY_BAD  otherwise.  No effect.
+ * verdict_out: NULL or n bytes.  The six counters sum to n; n_rows_marked: the distinct rows this call turned from not bad to bad (they are
+ * reported by the next sweep).  A row never written reads (no source, bad, not fixed), which mcp_map_graph_update_points refuses to write: that
+ * is how it is told.  The caller guarantees one live entry per key, as for mcp_map_graph_add_meas; of several, the one stored last is judged.
+ * SHAPE: one copy of the packed keys (sorted by key with their list index for the match; sorted by (row, list index) for the walk), three
+ * launches on the table's stream, one wait: k_mg_edges_count (the good counts), k_mgc_match (one thread per store entry, binary search in the
+ * sorted keys), k_mgc_judge (one thread per row that has outliers walks them in list order -- rows are independent, only the walk within a row
+ * is serial -- and tallies).  The launch boundaries are the grid-wide facts: matches and good counts are complete before a row is judged.
+ * n == 0 enqueues nothing.
+ * REFUSED: NULL graph, params or result; n < 0; a NULL key array with n > 0; a negative bad_good_count; a cam outside the rig; a slot outside
+ * 0..MCP_MAP_MAX_MKFS-1; a repeated key (the solver lists a measurement once). */
+#define MCP_CULL_MISSING      0
+#define MCP_CULL_FIXED        1
+#define MCP_CULL_POINT_BAD    2
+#define MCP_CULL_RETRY        3
+#define MCP_CULL_NEVER_RETRY  4
+#define MCP_CULL_ALREADY_BAD  5
+typedef struct mcp_cull_outliers_params { int bad_good_count; /* 2: GoodMeasCount() <= 2, src/MapMakerServerBase.cc:1216 */ } mcp_cull_outliers_params;
+typedef struct mcp_cull_outliers_result { int n_missing, n_fixed, n_point_bad, n_retry, n_never_retry, n_already_bad, n_fixed_rows, n_rows_marked; } mcp_cull_outliers_result;
+int mcp_map_cull_outliers(mcp_map_graph*, int n, const int* mkf, const int* cam, const int* row, const mcp_cull_outliers_params*,
+                          uint8_t* verdict_out /* n or NULL */, mcp_cull_outliers_result*);
+
+/* THE SWEEP: danglers, tracker outliers, bad points to the trash.  Over every row of the table whose graph column is not bad, in this order:
+ *   danglers          only if params.danglers and at least two MKF slots are present (bad ones count: the adapter has erased the trashed MKFs
+ *                     with mcp_map_graph_erase_mkf before, as HandleBadEntities does first): a row that is not fixed with good count < 2 goes bad
+ *   tracker outliers  a row that is not fixed with outlier > min_outliers and outlier > inlier * outlier_multiplier (the table's count column;
+ *                     the product and the comparison in double, as the reference's int * double) goes bad
+ * Then for every bad row, whoever marked it (a row never written is bad): its live store entries die (MapPoint::EraseAllMeasurements) and the
+ * `usable` byte of its table row is cleared, so mcp_track_find_pvs drops it without a table upload.
+ * REPORT: mcp_map_cull_rows_view gives, in pinned memory and ascending row, the rows THE DEVICE turned bad since the last sweep -- by
+ * mcp_map_cull_outliers calls since then and by this sweep; the host moves exactly these MapPoints to the trash.  Rows the host marked bad itself
+ * through mcp_map_graph_update_points it knows already: they are swept, not reported.  The graph keeps a pending mark per row for this (the
+ * fourth word of the row's graph column): set by mcp_map_cull_outliers, cleared by the sweep once the report is built and by
+ * mcp_map_graph_update_points for the rows it writes, so a row recycled for a new point starts clean.  A row never written is never reported.
+ * The view is valid until the next sweep on the graph; NULL + count 0 when nothing is reported.
+ * n_danglers + n_tracker_outliers: the rows this call marked (a row that is both counts as a dangler); n_bad_rows: every bad row of the table
+ * after the marks; n_meas_erased: the entries that died.  One submission (three launches: good counts, rows, report + store) and one wait; the
+ * good counts and the row marks are complete before a store entry is judged; the report is compacted by rank (mg_rank).
+ * REFUSED: NULL handles or structs; a negative min_outliers; a multiplier that is not finite. */
+typedef struct mcp_cull_sweep_params {
+  int min_outliers;            /* MapMakerClientBase::snMinOutliers (20) */
+  int danglers;                /* 1: run MarkDanglersAsBad */
+  double outlier_multiplier;   /* MapMakerClientBase::sdOutlierMultiplier (1.0) */
+} mcp_cull_sweep_params;
+typedef struct mcp_cull_sweep_result { int n_danglers, n_tracker_outliers, n_reported, n_bad_rows, n_meas_erased; } mcp_cull_sweep_result;
+int mcp_map_cull_sweep(mcp_map_graph*, const mcp_cull_sweep_params*, mcp_cull_sweep_result*);
+const int* mcp_map_cull_rows_view(const mcp_map_graph*, int* count);
+/* device time in ms of the last mcp_map_cull_outliers / mcp_map_cull_sweep submission on the graph (between two events on the stream, as
+ * mcp_map_bundle_select_last_timing); -1 for a call that has not run (or, outliers, whose last call had n == 0).  Either pointer may be NULL. */
+int mcp_map_cull_last_timing(const mcp_map_graph*, double* outliers_ms, double* sweep_ms);
+
+/* the same two calls from host arrays, by the same bodies under the host compiler: they need no device and give the device's bytes.  MKF flags
+ * as mcp_map_bundle_select_host takes them (n_slots <= MCP_MAP_MAX_MKFS); the n_point_rows <= n_rows graph columns written so far as
+ * mcp_graph_kf_lists_host takes them (rows after them read as never written); the store columns with their alive flags.  IN PLACE: point_flags,
+ * pending (n_point_rows bytes), ms_alive, usable (n_rows bytes).  inlier / outlier: the count column, n_rows.  rows_out: room for cap_rows rows;
+ * a report that does not fit is a refusal found before anything is written (n_rows always fits).  mcp_map_cull_sweep_host returns n_reported.
+ * Refusals as the device calls', plus negative counts, a NULL array with a positive count, n_point_rows > n_rows, n_slots > MCP_MAP_MAX_MKFS. */
+int mcp_map_cull_outliers_host(int n, const int* mkf, const int* cam, const int* row, const mcp_cull_outliers_params*, int ncam,
+                               int n_slots, const int* mkf_flags, int n_rows, int n_point_rows, const int* src_mkf, int* point_flags, uint8_t* pending,
+                               int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row, const int* ms_source, uint8_t* ms_alive,
+                               uint8_t* verdict_out /* n or NULL */, mcp_cull_outliers_result*);
+int mcp_map_cull_sweep_host(const mcp_cull_sweep_params*, int n_slots, const int* mkf_flags, int n_rows, int n_point_rows, int* point_flags,
+                            uint8_t* pending, const int* inlier, const int* outlier, uint8_t* usable, int n_store, const int* ms_mkf,
+                            const int* ms_row, uint8_t* ms_alive, mcp_cull_sweep_result*, int cap_rows, int* rows_out);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@
 #include "map_graph_kernels.h"
 #include "map_graph_lists.h"
 #include "map_graph_parcel.h"
+#include "map_graph_cull.h"
 
 using namespace mcp;
 
@@ -2634,7 +2635,17 @@ struct mcp_map_graph {
   PinBuf<char> l_in; Buf<char> l_dev; Buf<int2> l_key_row; Buf<int> l_table, l_start, l_rows; Buf<double> l_w, l_cfw; PinBuf<char> l_out;
   // the commit of a measurement parcel (map_graph_parcel.h): verdict bytes, per-workgroup counts, the result block (MgpCtl | per-lane counts: device, pinned)
   Buf<uint8_t> pc_vd; Buf<int> pc_blk; Buf<char> pc_dev; PinBuf<char> pc_out;
-  ~mcp_map_graph() { if (m && m->st) (void)hipStreamSynchronize(m->st); for (hipEvent_t e : {staged, t0, t1}) if (e) (void)hipEventDestroy(e); }
+  // outliers and bad points (map_graph_cull.h): the store index of each key, verdict and report bytes, the counters (device, pinned with the
+  // verdicts behind them), the pinned report of the last sweep; the events of mcp_map_cull_last_timing ([0], [1]: outliers; [2], [3]: sweep).
+  // The good counts go through `marks`, the per-workgroup counts through `blk`, as a select's do.
+  Buf<int> c_match; Buf<uint8_t> c_vd, c_rep; Buf<MgcCtl> c_ctl; PinBuf<char> c_out; PinBuf<int> c_rows; int c_nrows = 0;
+  hipEvent_t c_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool c_timed[2] = {false, false};
+  std::vector<std::pair<unsigned long long, int>> c_keys; std::vector<MgcRun> c_runs;
+  ~mcp_map_graph() {
+    if (m && m->st) (void)hipStreamSynchronize(m->st);
+    for (hipEvent_t e : {staged, t0, t1, c_ev[0], c_ev[1], c_ev[2], c_ev[3]}) if (e) (void)hipEventDestroy(e);
+  }
+  int cull_ready() { for (hipEvent_t& e : c_ev) if (!e) ICK(hipEventCreate(&e)); return c_ctl.alloc(1); }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
   int sync() { ICK(hipStreamSynchronize(m->st)); stage_busy = false; m->stage_busy = false; m->parcel_reads = false; return 0; }
   // pinned + device staging of `bytes`, free to fill
@@ -2772,7 +2783,7 @@ static void mg_host_select(const mcp_bundle_select_params& S, const MgHostIn& I,
   }
   int n_points = 0;
   for (int i = 0; i < N; ++i) {
-    MgPoint Q; Q.src_mkf = I.src_mkf[i]; Q.src_cam = I.src_cam[i]; Q.flags = I.pflags[i]; Q.pad_ = 0;
+    MgPoint Q; Q.src_mkf = I.src_mkf[i]; Q.src_cam = I.src_cam[i]; Q.flags = I.pflags[i]; Q.pending = 0;
     if (!mg_row_selected(S.mode, Q.flags, good[i], seen[i])) continue;
     const bool fixed = Q.flags & MCP_GP_FIXED;
     if (!fixed && !(mg_source_in_range(Q, nc, P) && mg_mkf_ok(I.mflags[Q.src_mkf]))) { ++R.n_dropped_source; continue; }
@@ -2793,7 +2804,7 @@ static void mg_host_select(const mcp_bundle_select_params& S, const MgHostIn& I,
   R.n_fixed = (int)mk.size() - R.n_adjust;
   for (int i = 0; i < N; ++i) {
     if (bidx[i] < 0) continue;
-    MgPoint Q; Q.src_mkf = I.src_mkf[i]; Q.src_cam = I.src_cam[i]; Q.flags = I.pflags[i]; Q.pad_ = 0;
+    MgPoint Q; Q.src_mkf = I.src_mkf[i]; Q.src_cam = I.src_cam[i]; Q.flags = I.pflags[i]; Q.pending = 0;
     const bool fixed = Q.flags & MCP_GP_FIXED;
     mcp_bundle_point O;
     mg_point_x(rig, Q, I.bfw + 12*(size_t)(fixed ? 0 : Q.src_mkf), I.world + 3*(size_t)i, O.x);
@@ -2856,7 +2867,7 @@ int mcp_map_graph_update_points(mcp_map_graph* g, int count, const int* rows, co
   const size_t o_ids = tm_align(sizeof(MgPoint)*(size_t)count), need = o_ids + sizeof(int)*(size_t)count;
   if (g->stage(need) || g->grow_points(R)) return -1;
   MgPoint* rec = reinterpret_cast<MgPoint*>(g->up_in.p);
-  for (int k = 0; k < count; ++k) { rec[k].src_mkf = src_mkf[k] < 0 ? -1 : src_mkf[k]; rec[k].src_cam = src_mkf[k] < 0 ? 0 : src_cam[k]; rec[k].flags = flags[k]; rec[k].pad_ = 0; }
+  for (int k = 0; k < count; ++k) { rec[k].src_mkf = src_mkf[k] < 0 ? -1 : src_mkf[k]; rec[k].src_cam = src_mkf[k] < 0 ? 0 : src_cam[k]; rec[k].flags = flags[k]; rec[k].pending = 0; }      // (a row that is written starts without a pending mark: mcp_map_cull_*)
   std::memcpy(g->up_in.p + o_ids, rows, sizeof(int)*(size_t)count);
   ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, need, hipMemcpyHostToDevice, g->m->st));
   hipLaunchKernelGGL(k_mg_points_scatter, dim3((unsigned)((count + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, g->m->st, g->pts.p, count,
@@ -3523,6 +3534,131 @@ int mcp_meas_parcel_commit(mcp_map_graph* g, mcp_meas_parcel* p, int n_lanes, co
   if (lane_appended && n_lanes) std::memcpy(lane_appended, g->pc_out.p + o_lanes, sizeof(int)*(size_t)n_lanes);
   g->n_store += res->n_appended; g->n_live += res->n_appended;
   p->committed = true;
+  return 0;
+}
+
+}  // extern "C"
+
+// ---- outliers and bad points on the device (include/mcp_img.h mcp_map_cull_*; map_graph_cull.h) ---------------------------------------------
+extern "C" {
+
+int mcp_map_cull_outliers(mcp_map_graph* g, int n, const int* mkf, const int* cam, const int* row, const mcp_cull_outliers_params* prm, uint8_t* verdict_out,
+                          mcp_cull_outliers_result* res) {
+  const std::string who = "mcp_map_cull_outliers";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!prm || !res) return img_fail(who + ": NULL params or result");
+  if (n < 0 || (n > 0 && (!mkf || !cam || !row))) return img_fail(who + ": bad arguments");
+  if (prm->bad_good_count < 0) return img_fail(who + ": a negative bad_good_count");
+  std::vector<std::pair<unsigned long long, int>>& keys = g->c_keys;
+  std::vector<MgcRun>& runs = g->c_runs;
+  keys.resize(n); runs.resize(n);
+  for (int k = 0; k < n; ++k) {
+    if (mkf[k] < 0 || mkf[k] >= MCP_MAP_MAX_MKFS) return img_fail(who + ": key " + std::to_string(k) + " names slot " + std::to_string(mkf[k]) + ", outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
+    if (cam[k] < 0 || cam[k] >= g->rig.ncam) return img_fail(who + ": key " + std::to_string(k) + " names camera " + std::to_string(cam[k]) + ", the rig has " + std::to_string(g->rig.ncam));
+    keys[k] = std::make_pair(mgc_key(mkf[k], cam[k], row[k]), k);
+    runs[k].row = row[k]; runs[k].idx = k;
+  }
+  std::sort(keys.begin(), keys.end());
+  for (int k = 1; k < n; ++k) if (keys[k].first == keys[k - 1].first) return img_fail(who + ": a key appears twice (list entries " + std::to_string(keys[k - 1].second) + " and " + std::to_string(keys[k].second) + ")");
+  if (n == 0) { std::memset(res, 0, sizeof *res); g->c_timed[0] = false; return 0; }
+  std::sort(runs.begin(), runs.end(), [](const MgcRun& a, const MgcRun& b) { return a.row != b.row ? a.row < b.row : a.idx < b.idx; });
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int R = m->rows, M = g->n_store;
+  // staging: sorted keys | their list indices | the runs up; MgcCtl | verdict bytes down.  Everything is allocated before the first enqueue.
+  const size_t o_idx = tm_align(8*(size_t)n), o_runs = o_idx + tm_align(sizeof(int)*(size_t)n), up = o_runs + sizeof(MgcRun)*(size_t)n, o_vd = tm_align(sizeof(MgcCtl)), down = o_vd + (size_t)n;
+  if (g->cull_ready()) return -1;
+  if (g->marks.n < (size_t)R || g->c_match.n < (size_t)n || g->c_vd.n < (size_t)n || g->c_out.n < down) { if (g->sync()) return -1; }
+  if (g->marks.alloc(R) || g->c_match.alloc(n) || g->c_vd.alloc(n) || g->c_out.alloc(down) || g->stage(up) || g->grow_points(R)) return -1;
+  unsigned long long* hk = reinterpret_cast<unsigned long long*>(g->up_in.p); int* hi = reinterpret_cast<int*>(g->up_in.p + o_idx);
+  for (int k = 0; k < n; ++k) { hk[k] = keys[k].first; hi[k] = keys[k].second; }
+  std::memcpy(g->up_in.p + o_runs, runs.data(), sizeof(MgcRun)*(size_t)n);
+  hipStream_t st = m->st;
+  const dim3 B(MGC_BLOCK);
+  g->c_timed[0] = false;
+  Drain drain{m, true};
+  ICK(hipEventRecord(g->c_ev[0], st));
+  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, up, hipMemcpyHostToDevice, st));
+  if (R) ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*(size_t)R, st));
+  ICK(hipMemsetAsync(g->c_match.p, 0xff, sizeof(int)*(size_t)n, st));
+  ICK(hipMemsetAsync(g->c_ctl.p, 0, sizeof(MgcCtl), st));
+  if (M) {
+    const dim3 G((unsigned)((M + MGC_BLOCK - 1)/MGC_BLOCK));
+    hipLaunchKernelGGL(k_mg_edges_count, G, B, 0, st, (const MgCtl*)nullptr, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)nullptr, g->marks.p, (int*)nullptr);
+    hipLaunchKernelGGL(k_mgc_match, G, B, 0, st, (const MgMeas*)g->store.p, M, (const unsigned long long*)g->up_dev.p, (const int*)(g->up_dev.p + o_idx), n, g->c_match.p);
+  }
+  hipLaunchKernelGGL(k_mgc_judge, dim3((unsigned)((n + MGC_BLOCK - 1)/MGC_BLOCK)), B, 0, st, n, (const MgcRun*)(g->up_dev.p + o_runs), (const int*)g->c_match.p, g->store.p,
+                     (const MgMkf*)g->slots.p, g->pts.p, g->prow, R, (const int*)g->marks.p, prm->bad_good_count, g->c_vd.p, g->c_ctl.p);
+  ICK(hipGetLastError());
+  ICK(hipEventRecord(g->c_ev[1], st));
+  ICK(hipMemcpyAsync(g->c_out.p, g->c_ctl.p, sizeof(MgcCtl), hipMemcpyDeviceToHost, st));
+  ICK(hipMemcpyAsync(g->c_out.p + o_vd, g->c_vd.p, (size_t)n, hipMemcpyDeviceToHost, st));
+  if (g->sync()) return -1;                            // the one wait
+  drain.armed = false; g->c_timed[0] = true;
+  const MgcCtl& C = *reinterpret_cast<const MgcCtl*>(g->c_out.p);
+  res->n_missing = C.verdicts[MCP_CULL_MISSING]; res->n_fixed = C.verdicts[MCP_CULL_FIXED]; res->n_point_bad = C.verdicts[MCP_CULL_POINT_BAD]; res->n_retry = C.verdicts[MCP_CULL_RETRY];
+  res->n_never_retry = C.verdicts[MCP_CULL_NEVER_RETRY]; res->n_already_bad = C.verdicts[MCP_CULL_ALREADY_BAD]; res->n_fixed_rows = C.fixed_rows; res->n_rows_marked = C.rows_marked;
+  g->n_live -= res->n_retry + res->n_never_retry;
+  if (verdict_out) std::memcpy(verdict_out, g->c_out.p + o_vd, (size_t)n);
+  return 0;
+}
+
+int mcp_map_cull_sweep(mcp_map_graph* g, const mcp_cull_sweep_params* prm, mcp_cull_sweep_result* res) {
+  const std::string who = "mcp_map_cull_sweep";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!prm || !res) return img_fail(who + ": NULL params or result");
+  if (prm->min_outliers < 0) return img_fail(who + ": a negative min_outliers");
+  if (!std::isfinite(prm->outlier_multiplier)) return img_fail(who + ": outlier_multiplier is not finite");
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int R = m->rows, M = g->n_store;
+  const int nbr = std::max(1, (R + MGC_BLOCK - 1)/MGC_BLOCK), nbm = (M + MGC_BLOCK - 1)/MGC_BLOCK;
+  if (g->cull_ready()) return -1;
+  if (g->marks.n < (size_t)R || g->c_rep.n < (size_t)R || g->blk.n < (size_t)nbr || g->c_out.n < sizeof(MgcCtl) || g->c_rows.n < (size_t)R) { if (g->sync()) return -1; }
+  if (g->marks.alloc(R) || g->c_rep.alloc(R) || g->blk.alloc(nbr) || g->c_out.alloc(sizeof(MgcCtl)) || g->c_rows.alloc(R) || g->grow_points(R)) return -1;
+  int n_present = 0;
+  for (int f : g->h_flags) n_present += (f & MCP_MKF_PRESENT) ? 1 : 0;
+  MgcSweep Q; Q.min_outliers = prm->min_outliers; Q.danglers_on = (prm->danglers && n_present >= 2) ? 1 : 0; Q.multiplier = prm->outlier_multiplier;
+  hipStream_t st = m->st;
+  const dim3 B(MGC_BLOCK);
+  g->c_timed[1] = false; g->c_nrows = 0;
+  Drain drain{m, true};
+  ICK(hipEventRecord(g->c_ev[2], st));
+  if (R) ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*(size_t)R, st));
+  ICK(hipMemsetAsync(g->c_ctl.p, 0, sizeof(MgcCtl), st));
+  if (M) hipLaunchKernelGGL(k_mg_edges_count, dim3((unsigned)nbm), B, 0, st, (const MgCtl*)nullptr, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)nullptr, g->marks.p, (int*)nullptr);
+  hipLaunchKernelGGL(k_mgc_sweep_rows, dim3((unsigned)nbr), B, 0, st, Q, g->pts.p, g->prow, R, (const int*)g->marks.p, (const int*)m->cnt.row(), m->pts.row(), g->c_rep.p, g->blk.p, g->c_ctl.p);
+  hipLaunchKernelGGL(k_mgc_sweep_emit, dim3((unsigned)(nbr + nbm)), B, 0, st, R, g->prow, nbr, (const uint8_t*)g->c_rep.p, (const int*)g->blk.p, g->c_rows.p, R, g->store.p, M,
+                     (const MgPoint*)g->pts.p, g->c_ctl.p);
+  ICK(hipGetLastError());
+  ICK(hipEventRecord(g->c_ev[3], st));
+  ICK(hipMemcpyAsync(g->c_out.p, g->c_ctl.p, sizeof(MgcCtl), hipMemcpyDeviceToHost, st));
+  if (g->sync()) return -1;                            // the one wait
+  drain.armed = false; g->c_timed[1] = true;
+  const MgcCtl& C = *reinterpret_cast<const MgcCtl*>(g->c_out.p);
+  res->n_danglers = C.danglers; res->n_tracker_outliers = C.tracker; res->n_reported = C.reported; res->n_bad_rows = C.bad_rows; res->n_meas_erased = C.erased;
+  g->n_live -= C.erased; g->c_nrows = C.reported;
+  return 0;
+}
+
+const int* mcp_map_cull_rows_view(const mcp_map_graph* g, int* count) {
+  if (count) *count = 0;
+  if (!g) { img_fail("mcp_map_cull_rows_view: NULL graph"); return nullptr; }
+  if (count) *count = g->c_nrows;
+  return g->c_nrows > 0 ? g->c_rows.p : nullptr;
+}
+
+int mcp_map_cull_last_timing(const mcp_map_graph* g, double* outliers_ms, double* sweep_ms) {
+  if (!g) return img_fail("mcp_map_cull_last_timing: NULL graph");
+  double* out[2] = {outliers_ms, sweep_ms};
+  for (int k = 0; k < 2; ++k) {
+    if (!out[k]) continue;
+    *out[k] = -1.0;
+    if (!g->c_timed[k]) continue;
+    float ms = 0.f;
+    ICK(hipEventElapsedTime(&ms, g->c_ev[2*k], g->c_ev[2*k + 1]));
+    *out[k] = ms;
+  }
   return 0;
 }
 

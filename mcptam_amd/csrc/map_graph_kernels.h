@@ -28,7 +28,7 @@ constexpr int MG_BLOCK = 256;
 constexpr int MG_MAX_MKFS = MCP_MAP_MAX_MKFS;
 
 struct MgMkf { double bfw[12]; double depth[MCP_MAX_FRAME_CAMS]; int flags; uint8_t active[MCP_MAX_FRAME_CAMS]; int pad_; };      // one slot (176 B)
-struct MgPoint { int src_mkf, src_cam, flags, pad_; };                                                                            // one row (16 B)
+struct MgPoint { int src_mkf, src_cam, flags, pending; };      // one row (16 B); pending: the device turned the row bad and no sweep has reported it yet (map_graph_cull.h)
 struct MgMeas { double uv[2]; int mkf, cam, row, level, source, alive; };                                                         // one store entry (40 B)
 struct MgRig { Se3 cfb[MCP_MAX_FRAME_CAMS]; int ncam; };
 
@@ -121,7 +121,7 @@ k_mg_points_scatter(MgPoint* __restrict__ rows, int count, const int* __restrict
 __global__ void __launch_bounds__(MG_BLOCK)
 k_mg_points_fill(MgPoint* __restrict__ rows, int first, int count) {
   const int k = blockIdx.x*MG_BLOCK + threadIdx.x;
-  if (k < count) { MgPoint P; P.src_mkf = -1; P.src_cam = 0; P.flags = MCP_GP_BAD; P.pad_ = 0; rows[first + k] = P; }
+  if (k < count) { MgPoint P; P.src_mkf = -1; P.src_cam = 0; P.flags = MCP_GP_BAD; P.pending = 0; rows[first + k] = P; }
 }
 
 // ---- erase and compact -----------------------------------------------------------------------------------------------------------------

@@ -61,6 +61,7 @@ IMG_SYMBOLS = [
     "mcp_graph_refresh_depth", "mcp_graph_write_back", "mcp_graph_debug_kf_lists", "mcp_graph_kf_lists_host", "mcp_graph_get_mkfs",
     "mcp_meas_parcel_create", "mcp_meas_parcel_destroy", "mcp_meas_parcel_from_track", "mcp_meas_parcel_from_refind", "mcp_meas_parcel_from_host",
     "mcp_meas_parcel_size", "mcp_meas_parcel_get", "mcp_meas_parcel_commit", "mcp_parcel_commit_host",
+    "mcp_map_cull_outliers", "mcp_map_cull_sweep", "mcp_map_cull_rows_view", "mcp_map_cull_last_timing", "mcp_map_cull_outliers_host", "mcp_map_cull_sweep_host",
 ]
 _BOUND = False
 

@@ -13,7 +13,12 @@ on the device, kf_lists_host (mcp_graph_kf_lists_host, no device) and kf_lists_r
 Measurement parcels (mcp_meas_parcel_*) feed the store from the device: MeasParcel takes the measurements of a track call, a ReFind or the
 caller into device memory with the keys of their rows, MapGraph.commit_parcel appends the ones that are still good when the map maker gets to
 them; parcel_commit_host (mcp_parcel_commit_host, no device) and parcel_commit_ref, the numpy restatement (src/Tracker.cc:1237-1274,
-src/MapMaker.cc:407-418), state the verdicts."""
+src/MapMaker.cc:407-418), state the verdicts.
+
+Outliers and bad points (mcp_map_cull_*): MapGraph.cull_outliers is MapMakerServerBase::HandleOutliers over the store, MapGraph.cull_sweep the
+point half of MapMaker::HandleBadEntities (danglers, tracker outliers, the bad points' measurements erased, their rows unusable, the rows the
+device turned bad reported); cull_outliers_host / cull_sweep_host are the host twins (no device) and cull_outliers_ref / cull_sweep_ref the
+numpy restatements (src/MapMakerServerBase.cc:1198-1238, src/MapMakerClientBase.cc:73-108, src/Map.cc:93-116)."""
 import ctypes
 
 import numpy as np
@@ -89,6 +94,39 @@ class ParcelCommitResult(ctypes.Structure):
 PARCEL_STRUCT_SIZES = {"mcp_parcel_entry": PARCEL_ENTRY_DTYPE.itemsize, "mcp_store_entry": STORE_ENTRY_DTYPE.itemsize,
                        "mcp_parcel_commit_params": ctypes.sizeof(ParcelCommitParams), "mcp_parcel_commit_result": ctypes.sizeof(ParcelCommitResult)}
 
+# outliers and bad points (include/mcp_img.h mcp_map_cull_*, map_graph_cull.h)
+CULL_SYMBOLS = ["mcp_map_cull_outliers", "mcp_map_cull_sweep", "mcp_map_cull_rows_view", "mcp_map_cull_last_timing", "mcp_map_cull_outliers_host",
+                "mcp_map_cull_sweep_host"]
+SRC_TRAIL, SRC_EPIPOLAR = 3, 4
+CULL_MISSING, CULL_FIXED, CULL_POINT_BAD, CULL_RETRY, CULL_NEVER_RETRY, CULL_ALREADY_BAD = range(6)
+CULL_BLOCK = 256                              # map_graph_cull.h: keys, rows or entries of a workgroup
+
+
+class CullOutliersParams(ctypes.Structure):
+    _fields_ = [("bad_good_count", ctypes.c_int)]
+
+
+class CullOutliersResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("n_missing", "n_fixed", "n_point_bad", "n_retry", "n_never_retry", "n_already_bad", "n_fixed_rows", "n_rows_marked")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class CullSweepParams(ctypes.Structure):
+    _fields_ = [("min_outliers", ctypes.c_int), ("danglers", ctypes.c_int), ("outlier_multiplier", ctypes.c_double)]
+
+
+class CullSweepResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("n_danglers", "n_tracker_outliers", "n_reported", "n_bad_rows", "n_meas_erased")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+CULL_STRUCT_SIZES = {"mcp_cull_outliers_params": ctypes.sizeof(CullOutliersParams), "mcp_cull_outliers_result": ctypes.sizeof(CullOutliersResult),
+                     "mcp_cull_sweep_params": ctypes.sizeof(CullSweepParams), "mcp_cull_sweep_result": ctypes.sizeof(CullSweepResult)}
+
 _BOUND = False
 
 
@@ -132,6 +170,13 @@ def lib():
         L.mcp_meas_parcel_get.argtypes = [vp, ip, vp]
         L.mcp_meas_parcel_commit.argtypes = [vp, vp, ip, vp, vp, vp, vp, vp]
         L.mcp_parcel_commit_host.argtypes = [ip, vp, ip, vp, ip, vp, vp, vp, ip, vp, vp, vp, ip, vp, vp, vp, vp]
+        L.mcp_map_cull_outliers.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp]
+        L.mcp_map_cull_sweep.argtypes = [vp, vp, vp]
+        L.mcp_map_cull_rows_view.restype = vp
+        L.mcp_map_cull_rows_view.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+        L.mcp_map_cull_last_timing.argtypes = [vp, vp, vp]
+        L.mcp_map_cull_outliers_host.argtypes = [ip, vp, vp, vp, vp, ip, ip, vp, ip, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
+        L.mcp_map_cull_sweep_host.argtypes = [vp, ip, vp, ip, ip, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp]
         _BOUND = True
     return L
 
@@ -360,6 +405,146 @@ def parcel_commit_ref(entries, keys, pt_flags, src_mkf, src_cam, lane_mkf, lane_
     res = dict(first=int(first), n_appended=int(cnt[PARCEL_APPENDED]), n_skipped_lane=int(cnt[PARCEL_SKIPPED]), n_stale=int(cnt[PARCEL_STALE]), n_bad=int(cnt[PARCEL_BAD]),
                n_cross=int(cnt[PARCEL_CROSS]))
     return vd, res, out, np.bincount(lane[keep], minlength=len(lm)).astype(np.int32)[:len(lm)]
+
+
+# ---- outliers and bad points: the host twins and the numpy restatements -------------------------------------------------------------------------
+def _cull_state(a, n_rows=None):
+    """The arrays the two calls read and write, copied out of the flat arrays `a` (problem_arrays' keys; optional "pending", "inlier", "outlier",
+    "usable"): n_rows table rows (default: the len(a["pt_flags"]) graph columns written), pending 0, counts (1, 0) and usable 1 where not given."""
+    Np = len(a["pt_flags"])
+    n_rows = Np if n_rows is None else int(n_rows)
+    inl, outl = _list_counts(a, n_rows)
+    b = dict(ncam=int(a["ncam"]), n_rows=n_rows, mkf_flags=_i32(a["mkf_flags"]).copy(), src_mkf=_i32(a["src_mkf"], (Np,)).copy(), pt_flags=_i32(a["pt_flags"]).copy(),
+             pending=(np.zeros(Np, dtype=np.uint8) if a.get("pending") is None else _u8(a["pending"], (Np,)).copy()), inlier=inl.copy(), outlier=outl.copy(),
+             usable=(np.ones(n_rows, dtype=np.uint8) if a.get("usable") is None else _u8(a["usable"], (n_rows,)).copy()))
+    M = len(a["ms_mkf"])
+    for k in ("ms_mkf", "ms_cam", "ms_row", "ms_source"):
+        b[k] = _i32(a[k], (M,)).copy()
+    b["ms_alive"] = _u8(a["ms_alive"], (M,)).copy()
+    return b
+
+
+def _cull_merge(a, b):
+    """`a` with the columns a cull call changed taken from the state b."""
+    out = copy_arrays(a)
+    for k in ("pt_flags", "pending", "usable", "ms_alive"):
+        out[k] = b[k]
+    return out
+
+
+def _cull_keys(mkf, cam, row):
+    m = _i32(mkf)
+    return m, _i32(cam, m.shape), _i32(row, m.shape)
+
+
+def cull_outliers_host(a, mkf, cam, row, bad_good_count=2, n_rows=None):
+    """mcp_map_cull_outliers_host over the flat arrays `a` (see _cull_state) for the outlier keys in list order: (dict of
+    mcp_cull_outliers_result, verdicts uint8 (n,), the arrays afterwards -- a copy of `a` with pt_flags, pending, usable, ms_alive as the call
+    leaves them).  Needs no device.  A refusal raises RuntimeError."""
+    b = _cull_state(a, n_rows)
+    m, c, r = _cull_keys(mkf, cam, row)
+    n = len(m)
+    prm, res = CullOutliersParams(int(bad_good_count)), CullOutliersResult()
+    vd = np.zeros(max(n, 1), dtype=np.uint8)
+    _chk(lib().mcp_map_cull_outliers_host(n, m.ctypes.data, c.ctypes.data, r.ctypes.data, ctypes.addressof(prm), b["ncam"], len(b["mkf_flags"]), b["mkf_flags"].ctypes.data,
+                                          b["n_rows"], len(b["pt_flags"]), b["src_mkf"].ctypes.data, b["pt_flags"].ctypes.data, b["pending"].ctypes.data, len(b["ms_mkf"]),
+                                          b["ms_mkf"].ctypes.data, b["ms_cam"].ctypes.data, b["ms_row"].ctypes.data, b["ms_source"].ctypes.data, b["ms_alive"].ctypes.data,
+                                          vd.ctypes.data, ctypes.addressof(res)), "map_cull_outliers_host")
+    return res.as_dict(), vd[:n], _cull_merge(a, b)
+
+
+def cull_sweep_host(a, min_outliers=20, outlier_multiplier=1.0, danglers=True, n_rows=None):
+    """mcp_map_cull_sweep_host over the flat arrays `a`: (dict of mcp_cull_sweep_result, the reported rows ascending, the arrays afterwards).
+    Needs no device.  A refusal raises RuntimeError."""
+    b = _cull_state(a, n_rows)
+    prm, res = CullSweepParams(int(min_outliers), int(bool(danglers)), float(outlier_multiplier)), CullSweepResult()
+    rows = np.zeros(max(b["n_rows"], 1), dtype=np.int32)
+    got = _chk(lib().mcp_map_cull_sweep_host(ctypes.addressof(prm), len(b["mkf_flags"]), b["mkf_flags"].ctypes.data, b["n_rows"], len(b["pt_flags"]), b["pt_flags"].ctypes.data,
+                                             b["pending"].ctypes.data, b["inlier"].ctypes.data, b["outlier"].ctypes.data, b["usable"].ctypes.data, len(b["ms_mkf"]),
+                                             b["ms_mkf"].ctypes.data, b["ms_row"].ctypes.data, b["ms_alive"].ctypes.data, ctypes.addressof(res), b["n_rows"], rows.ctypes.data),
+               "map_cull_sweep_host")
+    return res.as_dict(), rows[:got].copy(), _cull_merge(a, b)
+
+
+def _cull_good(b):
+    """GoodMeasCount() of every table row (MapPoint.h:80-87): the live measurements whose MKF is in the map and not bad."""
+    mf = np.zeros(MAX_MKFS, dtype=np.int64); mf[:len(b["mkf_flags"])] = b["mkf_flags"]
+    ok = ((mf & MKF_PRESENT) != 0) & ((mf & MKF_BAD) == 0)
+    mm, mr = b["ms_mkf"].astype(np.int64), b["ms_row"].astype(np.int64)
+    live = (b["ms_alive"] != 0) & (mr >= 0) & (mr < b["n_rows"]) & (mm >= 0) & (mm < MAX_MKFS)
+    return np.bincount(mr[live & ok[np.clip(mm, 0, MAX_MKFS - 1)]], minlength=b["n_rows"])[:b["n_rows"]], ok, mf
+
+
+def cull_outliers_ref(a, mkf, cam, row, bad_good_count=2, n_rows=None):
+    """MapMakerServerBase::HandleOutliers (src/MapMakerServerBase.cc:1198-1238) as its loop reads: one outlier after the other in the list's
+    order, GoodMeasCount() counted afresh from the store each time.  On top of it the rules a row-indexed store adds: a key without a live
+    measurement, a row outside the table or never written (no source, bad, not fixed) or a slot that is not in the map is MISSING.  Returns what
+    cull_outliers_host returns."""
+    b = _cull_state(a, n_rows)
+    m, c, r = _cull_keys(mkf, cam, row)
+    n, Np = len(m), len(b["pt_flags"])
+    if n and (m.min() < 0 or m.max() >= MAX_MKFS or c.min() < 0 or c.max() >= b["ncam"]):
+        raise ValueError("cull_outliers_ref: a key names a slot or a camera out of range")
+    if len({(int(x), int(y), int(z)) for x, y, z in zip(m, c, r)}) != n:
+        raise ValueError("cull_outliers_ref: a key appears twice")
+    where = {}
+    for i in np.flatnonzero(b["ms_alive"]):
+        where[(int(b["ms_mkf"][i]), int(b["ms_cam"][i]), int(b["ms_row"][i]))] = int(i)        # kf.mmpMeasurements[&point]
+    flags, alive = b["pt_flags"], b["ms_alive"]
+    vd = np.zeros(n, dtype=np.uint8)
+    fixed_rows, bad_points = set(), set()
+    mf = _cull_good(b)[2]
+    for i in range(n):
+        k, p = int(m[i]), int(r[i])
+        e = where.get((k, int(c[i]), p))
+        written = 0 <= p < Np and (b["src_mkf"][p] >= 0 or (flags[p] & GP_FIXED))
+        if e is None or not alive[e] or not written or not (mf[k] & MKF_PRESENT):
+            vd[i] = CULL_MISSING
+        elif flags[p] & GP_FIXED:                                                  # :1210-1214
+            fixed_rows.add(p)
+            vd[i] = CULL_FIXED
+        elif _cull_good(b)[0][p] <= bad_good_count or b["ms_source"][e] == SRC_ROOT:   # :1216-1220
+            if not flags[p] & GP_BAD:
+                bad_points.add(p)
+                b["pending"][p] = 1
+            flags[p] |= GP_BAD
+            vd[i] = CULL_POINT_BAD
+        elif not flags[p] & GP_BAD:                                                 # :1221-1235
+            vd[i] = CULL_RETRY if b["ms_source"][e] in (SRC_TRACKER, SRC_EPIPOLAR) else CULL_NEVER_RETRY
+            alive[e] = 0                                                            # kf.EraseMeasurementOfPoint, spMeasurementKFs.erase
+        else:
+            vd[i] = CULL_ALREADY_BAD
+    cnt = np.bincount(vd, minlength=6)
+    res = dict(n_missing=int(cnt[0]), n_fixed=int(cnt[1]), n_point_bad=int(cnt[2]), n_retry=int(cnt[3]), n_never_retry=int(cnt[4]), n_already_bad=int(cnt[5]),
+               n_fixed_rows=len(fixed_rows), n_rows_marked=len(bad_points))
+    return res, vd, _cull_merge(a, b)
+
+
+def cull_sweep_ref(a, min_outliers=20, outlier_multiplier=1.0, danglers=True, n_rows=None):
+    """MarkDanglersAsBad, MarkOutliersAsBad (src/MapMakerClientBase.cc:73-108) and Map::MoveBadPointsToTrash (src/Map.cc:93-116) over the flat
+    arrays, in numpy; the report is the rows these two marked plus the bad rows whose pending mark an earlier cull_outliers left.  Rows past the
+    graph columns written are bad and never reported.  Returns what cull_sweep_host returns."""
+    b = _cull_state(a, n_rows)
+    R, Np = b["n_rows"], len(b["pt_flags"])
+    good, _, mf = _cull_good(b)
+    fl = b["pt_flags"]
+    bad0, fixed = (fl & GP_BAD) != 0, (fl & GP_FIXED) != 0
+    dang = np.zeros(Np, dtype=bool)
+    if danglers and int(((mf & MKF_PRESENT) != 0).sum()) >= 2:                      # mlpMultiKeyFrames.size() < 2: return
+        dang = ~bad0 & ~fixed & (good[:Np] < 2)
+    o, i = b["outlier"][:Np], b["inlier"][:Np]
+    trk = ~bad0 & ~dang & ~fixed & (o > min_outliers) & (o.astype(np.float64) > i.astype(np.float64) * float(outlier_multiplier))
+    rows = np.flatnonzero(dang | trk | (bad0 & (b["pending"] != 0))).astype(np.int32)
+    fl[dang | trk] |= GP_BAD
+    b["pending"][:] = 0
+    bad = np.ones(R, dtype=bool); bad[:Np] = (fl & GP_BAD) != 0
+    b["usable"][bad] = 0
+    mr = b["ms_row"].astype(np.int64)
+    dies = (b["ms_alive"] != 0) & (mr >= 0) & (mr < R)
+    dies[dies] = bad[mr[dies]]                                                     # MapPoint::EraseAllMeasurements
+    b["ms_alive"][dies] = 0
+    res = dict(n_danglers=int(dang.sum()), n_tracker_outliers=int(trk.sum()), n_reported=len(rows), n_bad_rows=int(bad.sum()), n_meas_erased=int(dies.sum()))
+    return res, rows, _cull_merge(a, b)
 
 
 # ---- the numpy restatement, from the reference -----------------------------------------------------------------------------------------------
@@ -691,6 +876,38 @@ class MapGraph:
         _chk(self._L.mcp_meas_parcel_commit(self._h, parcel._h, len(lm), lm.ctypes.data, lc.ctypes.data, ctypes.addressof(prm), ctypes.addressof(res), la.ctypes.data),
              "meas_parcel_commit")
         return res.as_dict(), la[:len(lm)]
+
+    # ---- outliers and bad points (mcp_map_cull_*) ----
+    def cull_outliers(self, mkf, cam, row, bad_good_count=2):
+        """mcp_map_cull_outliers: MapMakerServerBase::HandleOutliers for the keys (mkf slot, cam, row) in the solver's order.  Returns (dict of
+        mcp_cull_outliers_result, verdicts uint8 (n,): CULL_*)."""
+        m, c, r = _cull_keys(mkf, cam, row)
+        n = len(m)
+        prm, res = CullOutliersParams(int(bad_good_count)), CullOutliersResult()
+        vd = np.zeros(max(n, 1), dtype=np.uint8)
+        _chk(self._L.mcp_map_cull_outliers(self._h, n, m.ctypes.data, c.ctypes.data, r.ctypes.data, ctypes.addressof(prm), vd.ctypes.data, ctypes.addressof(res)), "map_cull_outliers")
+        return res.as_dict(), vd[:n]
+
+    def cull_sweep(self, min_outliers=20, outlier_multiplier=1.0, danglers=True):
+        """mcp_map_cull_sweep: danglers and tracker outliers marked bad, the measurements of every bad row erased, its table row made unusable.
+        Returns (dict of mcp_cull_sweep_result, the rows the device turned bad since the last sweep, ascending: a copy of the pinned view)."""
+        prm, res = CullSweepParams(int(min_outliers), int(bool(danglers)), float(outlier_multiplier)), CullSweepResult()
+        _chk(self._L.mcp_map_cull_sweep(self._h, ctypes.addressof(prm), ctypes.addressof(res)), "map_cull_sweep")
+        return res.as_dict(), self.cull_rows()
+
+    def cull_rows(self):
+        """The report of the last sweep (mcp_map_cull_rows_view), copied."""
+        cnt = ctypes.c_int(0)
+        ptr = self._L.mcp_map_cull_rows_view(self._h, ctypes.byref(cnt))
+        if not cnt.value:
+            return np.zeros(0, dtype=np.int32)
+        return np.frombuffer((ctypes.c_char * (4 * cnt.value)).from_address(ptr), dtype=np.int32).copy()
+
+    def cull_last_timing(self):
+        """(outliers_ms, sweep_ms): device time of the last submission of each call, -1 for one that has not run."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _chk(self._L.mcp_map_cull_last_timing(self._h, ctypes.addressof(a), ctypes.addressof(b)), "map_cull_last_timing")
+        return a.value, b.value
 
     def select_raw(self, params, copy=True):
         """mcp_map_bundle_select: (SelectResult, mkfs, points, meas)."""

@@ -116,7 +116,8 @@ void GraphEraseMKF(Map& map, MultiKeyFrame& mkf)
   mkf.mnGraphSlot = -1;
 }
 
-// MapPoint created, its source set, mbFixed / mbBad changed (AddStereoMapPoints, AddInitDepthMapPoints, HandleBadPoints): the graph columns of its row.  Its MapPoint columns go to the table as before.
+// MapPoint created, its source set, mbFixed / mbBad changed by the host (AddStereoMapPoints, AddInitDepthMapPoints, HandleBadPoints): the graph columns of its row.
+// Not for the rows HandleOutliers / HandleBadEntities turn bad: the device marks those itself (mcp_map_cull_*) and reports them.  Its MapPoint columns go to the table as before.
 void GraphUploadPoints(Map& map, const std::vector<MapPoint*>& vpPoints)
 {
   const int n = (int)vpPoints.size();
@@ -223,8 +224,9 @@ void GraphCommitReFindParcel(Map& map, mcp_meas_parcel* pParcel, const std::vect
     ROS_WARN_STREAM("GraphCommitReFindParcel: the device appended " << res.n_appended << " of " << nExpected << " measurements");
 }
 
-// KeyFrame::EraseMeasurementOfPoint (src/KeyFrame.cc:749 on) as HandleOutliers (src/MapMakerServerBase.cc:1198-1238) and
-// AddMultiKeyFrameFromTopOfQueue use it: one call for the whole list.  mcp_map_graph_compact when the dead entries pass a share of the
+// KeyFrame::EraseMeasurementOfPoint (src/KeyFrame.cc:749 on) as AddMultiKeyFrameFromTopOfQueue uses it: one call for the whole list.
+// (HandleOutliers, src/MapMakerServerBase.cc:1198-1238, no longer comes through here: mcp_map_cull_outliers erases on the device what it
+// judges, shim/MapMakerServerBase_gpu.cc.)  mcp_map_graph_compact when the dead entries pass a share of the
 // store (store indices change: nothing on this side keeps one across calls).
 void GraphEraseMeasurements(Map& map, const std::vector<std::pair<KeyFrame*, MapPoint*> >& vPairs)
 {

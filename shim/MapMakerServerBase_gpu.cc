@@ -13,7 +13,11 @@
 // Needs KeyFrame::mpDev (shim/KeyFrame_gpu.cc), shim/CameraExport.h, and the table with MapPoint::mnTableRow (shim/Tracker_gpu.cc: the map
 // maker holds the same mcp_map_points* as mpMapTable), and in class MapMakerServerBase: mcp_meas_parcel* mpReFindParcel
 // (mcp_meas_parcel_create(mpMapTable) where the table is handed over; mcp_meas_parcel_destroy before the table goes).
+// At the end of this file: HandleOutliers (:1198-1238) and MapMaker::HandleBadEntities (src/MapMaker.cc:477-492) over mcp_map_cull_outliers /
+// mcp_map_cull_sweep -- delete those two bodies too.
 #include <mcptam/MapMakerServerBase.h>
+#include <mcptam/MapMaker.h>
+#include <mcptam/BundleAdjusterBase.h>
 #include <mcptam/MapPoint.h>
 #include <mcptam/KeyFrame.h>
 #include <mcptam/LevelHelpers.h>
@@ -424,4 +428,141 @@ void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, i
         vKept.push_back(level.vCandidates[i]);
     level.vCandidates = vKept;
   }
+}
+
+// ---- HandleOutliers (:1198-1238) in ONE call on the map graph ------------------------------------------------------------------------------------
+// The reference walks the outlier list and re-reads GoodMeasCount() after every erasure; mcp_map_cull_outliers does that walk on the device (the
+// store knows every measurement's source and which are alive, the graph the flags) and hands back one verdict byte per outlier.  Nothing
+// map-sized crosses the link: the list goes up, the verdicts come down.  The verdicts drive what only the host has: mlFailureQueue,
+// spNeverRetryKFs, the Measurement objects and bTransferred / vOutliersRemoved.  The host's own walk over its MapPoint objects runs alongside
+// (it costs a list walk) and must agree; a disagreement is warned about, in the manner of GraphCommitTrackerParcel, and the device's verdict is
+// the one applied, because the next select reads the device's store.
+void MapMakerServerBase::HandleOutliers(std::vector<std::pair<KeyFrame*, MapPoint*> >& vOutliers)
+{
+  const int n = (int)vOutliers.size();
+  std::vector<int> vMKF(n), vCam(n), vRow(n);
+  for(int i = 0; i < n; ++i)
+  {
+    vMKF[i] = vOutliers[i].first->mpParent->mnGraphSlot;
+    vCam[i] = vOutliers[i].first->mnCamIndex;
+    vRow[i] = vOutliers[i].second->mnTableRow;
+  }
+  mcp_cull_outliers_params params;
+  params.bad_good_count = 2;
+  mcp_cull_outliers_result res;
+  std::vector<uint8_t> vVerdict(n);
+  if(mcp_map_cull_outliers(mMap.mpMapGraph, n, vMKF.data(), vCam.data(), vRow.data(), &params, vVerdict.data(), &res) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_cull_outliers: " << mcp_last_error());   // (a repeated key or a slot out of range: the solver's list is broken)
+    ROS_BREAK();
+  }
+
+  std::vector<std::pair<KeyFrame*, MapPoint*> > vOutliersRemoved;
+  int nDisagree = 0;
+  for(int i = 0; i < n; ++i)
+  {
+    KeyFrame& kf = *(vOutliers[i].first);
+    MapPoint& point = *(vOutliers[i].second);
+    MeasPtrMap::iterator meas_it = kf.mmpMeasurements.find(&point);
+    // the host's own verdict, from its objects as they stand (the reference's tests in the reference's order)
+    int nHost = MCP_CULL_ALREADY_BAD;
+    if(meas_it == kf.mmpMeasurements.end())
+      nHost = MCP_CULL_MISSING;
+    else if(point.mbFixed)
+      nHost = MCP_CULL_FIXED;
+    else if(point.mMMData.GoodMeasCount() <= 2 || meas_it->second->eSource == Measurement::SRC_ROOT)
+      nHost = MCP_CULL_POINT_BAD;
+    else if(!point.mbBad)
+      nHost = (meas_it->second->eSource == Measurement::SRC_TRACKER || meas_it->second->eSource == Measurement::SRC_EPIPOLAR) ? MCP_CULL_RETRY : MCP_CULL_NEVER_RETRY;
+    if(nHost != vVerdict[i])
+      ++nDisagree;
+
+    switch(vVerdict[i])
+    {
+      case MCP_CULL_POINT_BAD:
+        point.mbBad = true;     // (its row is bad on the device already; the sweep reports it, and HandleBadEntities moves it to the trash)
+        break;
+      case MCP_CULL_RETRY:
+      case MCP_CULL_NEVER_RETRY:
+      {
+        if(meas_it == kf.mmpMeasurements.end())
+          break;                // (counted as a disagreement above)
+        if(vVerdict[i] == MCP_CULL_RETRY)
+          mlFailureQueue.push_back(vOutliers[i]);
+        else
+          point.mMMData.spNeverRetryKFs.insert(&kf);
+        const bool bTransferred = meas_it->second->bTransferred;
+        kf.EraseMeasurementOfPoint(&point);
+        point.mMMData.spMeasurementKFs.erase(&kf);
+        if(bTransferred)
+          vOutliersRemoved.push_back(vOutliers[i]);
+        break;
+      }
+      default:                  // MISSING, FIXED, ALREADY_BAD: nothing changes
+        break;
+    }
+  }
+  vOutliers.swap(vOutliersRemoved);
+
+  ROS_INFO_STREAM("======== Number of outlier fixed points: " << res.n_fixed_rows);
+  if(res.n_rows_marked > 0)
+    ROS_INFO_STREAM("======== Handle outlier measurements marked " << res.n_rows_marked << " points as bad");
+  if(nDisagree > 0 || res.n_missing > 0)
+    ROS_WARN_STREAM("HandleOutliers: the host's walk disagrees with the device on " << nDisagree << " of " << n << " outliers (" << res.n_missing << " without a live store entry)");
+}
+
+// ---- MapMaker::HandleBadEntities (src/MapMaker.cc:477-492): the point half in ONE call --------------------------------------------------------------
+// MarkDanglersAsBad, MarkOutliersAsBad and Map::MoveBadPointsToTrash read GoodMeasCount() and the tracker's counts of every point: the store
+// and the table's count column, both on the device.  mcp_map_cull_sweep marks the rows, erases the measurements of every bad row (whoever
+// marked it), clears the table's usable byte (the tracker's next FindPVS drops the point without a table upload) and reports the rows the
+// DEVICE turned bad since the last sweep; the points the host marked bad itself (mbBad set here and uploaded with GraphUploadPoints) it finds
+// in its own list.  Trashed MKFs are erased from the graph first, as the reference moves them first: a bad MKF still counts as present for the
+// dangler rule's "two MKFs" until then.  mcp_map_graph_compact stays where it was: after the sweep, when the dead entries pass a share.
+void MapMaker::HandleBadEntities()
+{
+  for(MultiKeyFramePtrList::iterator it = mMap.mlpMultiKeyFrames.begin(); it != mMap.mlpMultiKeyFrames.end(); ++it)
+    if((*it)->mbBad && (*it)->mnGraphSlot >= 0)
+    {
+      mcp_map_graph_erase_mkf(mMap.mpMapGraph, (*it)->mnGraphSlot);
+      (*it)->mnGraphSlot = -1;
+    }
+  mMap.MoveBadMultiKeyFramesToTrash();
+  mMap.MoveDeletedMultiKeyFramesToTrash();
+
+  mcp_cull_sweep_params params;
+  params.min_outliers = MapMakerClientBase::snMinOutliers;
+  params.outlier_multiplier = MapMakerClientBase::sdOutlierMultiplier;
+  params.danglers = 1;
+  mcp_cull_sweep_result res;
+  if(mcp_map_cull_sweep(mMap.mpMapGraph, &params, &res) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_cull_sweep: " << mcp_last_error());
+    ROS_BREAK();
+  }
+  int nRows = 0;
+  const int* pRows = mcp_map_cull_rows_view(mMap.mpMapGraph, &nRows);
+  for(int i = 0; i < nRows; ++i)
+  {
+    MapPoint* pPoint = mBundleAdjuster.mvpRowPoint[pRows[i]];
+    if(pPoint)
+      pPoint->mbBad = true;     // (MoveBadPointsToTrash below erases its Measurement objects and moves it; its row is free for reuse after EmptyTrash)
+  }
+  if(res.n_tracker_outliers > 0)
+    ROS_INFO_STREAM("======== Handle outlier based on tracker marked " << res.n_tracker_outliers << " points as bad");
+
+  // the host's list must now hold exactly the device's bad rows: every mbBad point is a bad row there, and no other written row is bad
+  int nHostBad = 0;
+  for(MapPointPtrList::iterator it = mMap.mlpPoints.begin(); it != mMap.mlpPoints.end(); ++it)
+    nHostBad += (*it)->mbBad ? 1 : 0;
+  mMap.MoveBadPointsToTrash();
+  mMap.MoveDeletedPointsToTrash();
+  if(nHostBad < res.n_reported)
+    ROS_WARN_STREAM("HandleBadEntities: the device reported " << res.n_reported << " rows, the host's list holds " << nHostBad << " bad points");
+
+  int nLive = 0, nStored = 0;
+  if(mcp_map_graph_num_meas(mMap.mpMapGraph, &nLive, &nStored) == 0 && nStored - nLive > nStored / 4)
+    mcp_map_graph_compact(mMap.mpMapGraph);
+
+  EraseBadEntitiesFromQueues();
+  mMap.EmptyTrash();
 }
