@@ -1132,6 +1132,110 @@ int mcp_map_cull_sweep_host(const mcp_cull_sweep_params*, int n_slots, const int
                             uint8_t* pending, const int* inlier, const int* outlier, uint8_t* usable, int n_store, const int* ms_mkf,
                             const int* ms_row, uint8_t* ms_alive, mcp_cull_sweep_result*, int cap_rows, int* rows_out);
 
+/* ---- Closest-keyframe queries and the removal of an MKF on the device ---- src/MapMakerBase.cc:90-339, src/MapMakerClientBase.cc:111-226,
+ *                                                                           src/MapMakerServerBase.cc:264-318, src/Map.cc:119-187
+ * ONE CALL for ClosestKeyFrame, ClosestKeyFramesWithinDist, NClosestKeyFrames, ClosestMultiKeyFrame, NClosestMultiKeyFrames and
+ * FurthestMultiKeyFrame over the graph's own columns (poses, active bytes, depth means, flags, the store): at most MCP_NB_MAX items come back,
+ * never a map-sized array.  The graph's conventions hold: the table's stream, the caller serialises, one wait, every atomic adds or ors an
+ * integer, nothing depends on the order workgroups are dispatched in.
+ * SOURCE: src_slot >= 0, a present slot; or -1, the external MKF of the params (the tracker's current MKF, which is not in the map): its pose,
+ *   active bytes and depth means as mcp_map_graph_set_mkfs takes one entry.  KF kind: the source keyframe is (source, src_cam).
+ * CANDIDATES, MKF kind: every present slot other than src_slot, bad ones included (the reference walks mlpMultiKeyFrames); `flags` travels
+ *   with an item so that the adapter can skip them after the list is cut, as AddStereoMapPoints does.
+ * CANDIDATES, KF kind: every (slot, cam) of a present slot with kf_active[cam] set, other than the source keyframe itself.  MCP_NB_ONLY_SELF:
+ *   the other keyframes of the source's own MKF; MCP_NB_ONLY_OTHER: every MKF but the source's; same_cam: cam == src_cam.  With src_slot == -1
+ *   the own MKF is the external one: its siblings are candidates (slot -1, cam) with its pose, active bytes and depths.
+ * DISTANCE: KeyFrame::Distance / MultiKeyFrame::Distance (src/KeyFrame.cc:715-747, 903-927) exactly as mcp_map_bundle_select computes them,
+ *   CamFromWorld = cam_from_base[c] * base_from_world.  An MKF pair without a pair of active keyframes gives DBL_MAX: a candidate like any
+ *   other, not an error.  A distance that is not finite or > 1e10 (the value the reference stops the process on) gives status 3 and count 0.
+ * ORDER: MCP_NB_NEAREST ascending (dist, slot, cam), MCP_NB_FURTHEST descending dist with ties to the smaller (slot, cam), where a candidate
+ *   at distance 0 is never furthest (FurthestMultiKeyFrame starts at 0 and compares with >).  Of these the ones with dist <= max_dist are
+ *   kept (+inf: all), and of those the first n_max.  count may be 0: a result, not an error.  n_candidates: the candidates before max_dist.
+ * n_meas (want_meas): the alive store entries whose mkf is the item's slot (MKF kind: MultiKeyFrame::NumMeasurements) or whose (mkf, cam) is
+ *   the item's keyframe (KF kind: mmpMeasurements.size()); counted for the `count` winners only; -1 without want_meas; items past count: zeros.
+ * DEVIATIONS: (1) the graph's only record that a keyframe exists is kf_active; inactive keyframes are deleted before an MKF enters the map
+ *   (ProcessIncomingKeyFrames), so this is the reference's set.  (2) slot and cam break ties where the reference's partial_sort compares
+ *   pointers.  (3) max_dist applies under MCP_NB_FURTHEST too (the reference has no such query).
+ * SHAPE: k_mgn_dist (a grid over (slot, cam): one candidate per thread, its distance and candidate byte into a scratch the graph owns -- the
+ *   32768 + 8 keyframes do not fit a workgroup's LDS), k_mgn_select (one workgroup, at most n_max rounds of a strided arg-min / arg-max with
+ *   an LDS tree, the winner marked taken), with want_meas k_mgn_count (one thread per store entry, a ballot per winner, lane 0 adds).
+ * REFUSALS (-1, mcp_last_error() starting "mcp_map_neighbours", nothing enqueued, outputs untouched): NULL graph, params or result; unknown
+ *   kind / region / order; src_slot neither -1 nor a present slot; KF kind: src_cam outside the rig, or the source keyframe not active;
+ *   MCP_NB_ONLY_SELF with same_cam; n_max outside 1..MCP_NB_MAX; max_dist NaN or negative; mean_diff_fraction not finite; an external pose
+ *   or active depth that is not finite, an active depth that is not positive. */
+#define MCP_NB_MKF 0          /* MultiKeyFrame::Distance: the minimum over the pairs of active keyframes      */
+#define MCP_NB_KF  1          /* KeyFrame::Distance from keyframe (source, src_cam) to every other keyframe   */
+#define MCP_NB_ALL        0   /* KeyFrameRegion (KF kind): KF_ALL, KF_ONLY_SELF, KF_ONLY_OTHER                */
+#define MCP_NB_ONLY_SELF  1
+#define MCP_NB_ONLY_OTHER 2
+#define MCP_NB_NEAREST  0
+#define MCP_NB_FURTHEST 1
+#define MCP_NB_MAX 32
+typedef struct mcp_neigh_params {
+  int kind, region, order;
+  int src_slot;                /* >= 0: a present slot; -1: the external MKF below */
+  int src_cam;                 /* KF kind */
+  int same_cam;                /* KF kind: only candidates with cam == src_cam (bSameCamName) */
+  int n_max;                   /* 1..MCP_NB_MAX */
+  int want_meas;               /* 1: fill n_meas of every item */
+  double max_dist;             /* keep dist <= max_dist; +inf: no threshold */
+  double mean_diff_fraction;   /* KeyFrame::sdDistanceMeanDiffFraction */
+  double ext_base_from_world[12]; uint8_t ext_active[MCP_MAX_FRAME_CAMS]; double ext_depth_mean[MCP_MAX_FRAME_CAMS];
+} mcp_neigh_params;
+typedef struct mcp_neigh_item { double dist; int slot, cam /* -1: MKF kind */, flags /* MCP_MKF_* of the slot; 0 for slot -1 */, n_meas; } mcp_neigh_item;
+typedef struct mcp_neigh_result { int status /* 0; 3 */, count, n_candidates, pad_; mcp_neigh_item item[MCP_NB_MAX]; } mcp_neigh_result;
+int mcp_map_neighbours(mcp_map_graph*, const mcp_neigh_params*, mcp_neigh_result*);
+/* device time in ms of the last mcp_map_neighbours submission on the graph (two events on the stream); -1 before the first that ran */
+int mcp_map_neighbours_last_timing(const mcp_map_graph*, double* device_ms);
+/* the same query from host arrays by the same bodies under the host compiler (no device; the device's bytes): the rig, n_slots MKF columns as
+ * mcp_map_bundle_select_host takes them, the store's mkf / cam / alive columns (read with want_meas only). */
+int mcp_map_neighbours_host(const mcp_neigh_params*, int ncam, const double* cam_from_base, int n_slots, const double* base_from_world,
+                            const int* mkf_flags, const uint8_t* kf_active, const double* kf_depth_mean,
+                            int n_store, const int* ms_mkf, const int* ms_cam, const uint8_t* ms_alive, mcp_neigh_result*);
+
+/* THE REMOVAL OF AN MKF: MarkFurthestMultiKeyFrameAsBad (src/MapMakerServerBase.cc:264-318) and the MKF half of HandleBadEntities
+ * (Map::MoveBadMultiKeyFramesToTrash / MoveDeletedMultiKeyFramesToTrash) in one submission.
+ *   victim      params.slot, or with slot == -1 the MCP_NB_FURTHEST MKF from furthest_from (the query above, MKF kind, n_max 1); without one
+ *               (no other MKF at a distance > 0) status is 1 and nothing changes; a broken distance: status 3 and nothing changes.
+ *   the marks   the victim gets MCP_MKF_BAD.  With mark_points, a row of the written graph columns with a live entry of the victim goes bad
+ *               if (a) it is not fixed and its live entries (every one, whatever its MKF's flags: spMeasurementKFs.size()) number <= max_kfs,
+ *               or (b) its patch source is that very keyframe (src_mkf == victim and src_cam == the entry's cam).  Such a row gets MCP_GP_BAD
+ *               and the pending mark, so the next mcp_map_cull_sweep reports it, erases its entries and clears its usable byte, as it does
+ *               for the rows of mcp_map_cull_outliers.  The counts are those on entry (the reference erases nothing inside its loop), so the
+ *               rule does not depend on any order.  n_rows_marked: rows turned from not bad to bad; n_by_source: those of them for which
+ *               (b) holds; n_by_count: the others.  A row that was bad already counts nowhere and keeps its pending state.
+ *   the fixed   if the victim is MCP_MKF_FIXED, the nearest other present MKF to it (MCP_NB_NEAREST, MKF kind, bad included, as
+ *               ClosestMultiKeyFrame) gets MCP_MKF_FIXED; new_fixed names it, -1 if there is none or the victim is not fixed.  (A broken
+ *               distance in that query matters only then: status 3, nothing changes.)
+ *   the erase   then, with erase, the victim's live entries die and the slot leaves the map: what mcp_map_graph_erase_mkf does.
+ * SHAPE: [slot == -1: k_mgn_dist, k_mgn_select] k_mgn_dist, k_mgn_select (the hand-over, its source read from the device), k_mgn_decide (one
+ * thread: victim, status, the MKF flags), [mark_points: k_mgn_rows_count: the live entries per row by integer atomicAdd, the rows whose
+ * source keyframe is the victim's], k_mgn_mark (one thread per store entry: atomicOr on the row's flag word, whoever sees the old value
+ * without MCP_GP_BAD counts the row), [erase: k_mg_erase]; one wait.
+ * REFUSALS (-1, mcp_last_error() starting "mcp_map_mkf_cull", nothing enqueued, graph and outputs untouched): NULL graph, params or result; a
+ * victim or furthest_from that is not a present slot; a negative max_kfs; mean_diff_fraction not finite. */
+typedef struct mcp_mkf_cull_params {
+  int slot;                    /* >= 0: the victim; -1: FurthestMultiKeyFrame(furthest_from) */
+  int furthest_from;           /* used when slot == -1 */
+  int mark_points;             /* 1: the point rule of MarkFurthestMultiKeyFrameAsBad; 0: only trash the MKF (mbDeleted) */
+  int max_kfs;                 /* 2: spMeasurementKFs.size() <= 2 */
+  int erase;                   /* 1: the victim's entries die and the slot leaves the map, after the marks */
+  double mean_diff_fraction;
+} mcp_mkf_cull_params;
+typedef struct mcp_mkf_cull_result {
+  int status /* 0; 1: no victim; 3: broken distance */, victim /* -1 unless status 0 */, victim_dist_valid /* 1 when slot was -1 */; double victim_dist;
+  int n_victim_meas, n_rows_marked, n_by_count, n_by_source, new_fixed, n_meas_erased;
+} mcp_mkf_cull_result;
+int mcp_map_mkf_cull(mcp_map_graph*, const mcp_mkf_cull_params*, mcp_mkf_cull_result*);
+/* device time in ms of the last mcp_map_mkf_cull submission on the graph; -1 before the first that ran */
+int mcp_map_mkf_cull_last_timing(const mcp_map_graph*, double* device_ms);
+/* the same from host arrays, IN PLACE (mkf_flags, point_flags, pending, ms_alive), as mcp_map_cull_outliers_host takes them plus the MKF pose,
+ * active and depth columns. */
+int mcp_map_mkf_cull_host(const mcp_mkf_cull_params*, int ncam, const double* cam_from_base, int n_slots, const double* base_from_world, int* mkf_flags,
+                          const uint8_t* kf_active, const double* kf_depth_mean, int n_rows, int n_point_rows, const int* src_mkf, const int* src_cam,
+                          int* point_flags, uint8_t* pending, int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row, uint8_t* ms_alive,
+                          mcp_mkf_cull_result*);
+
 #ifdef __cplusplus
 }
 #endif

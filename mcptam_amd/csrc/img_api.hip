@@ -33,6 +33,7 @@
 #include "map_graph_lists.h"
 #include "map_graph_parcel.h"
 #include "map_graph_cull.h"
+#include "map_graph_neigh.h"
 
 using namespace mcp;
 
@@ -2641,9 +2642,21 @@ struct mcp_map_graph {
   Buf<int> c_match; Buf<uint8_t> c_vd, c_rep; Buf<MgcCtl> c_ctl; PinBuf<char> c_out; PinBuf<int> c_rows; int c_nrows = 0;
   hipEvent_t c_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool c_timed[2] = {false, false};
   std::vector<std::pair<unsigned long long, int>> c_keys; std::vector<MgcRun> c_runs;
+  // the neighbour queries and the removal of an MKF (map_graph_neigh.h): the host's copy of the active bytes (what a query's refusals check),
+  // the scratch of distances and candidate bytes, the two queries' hand-offs and results (device), the external MKF, the removal's block,
+  // the pinned results; the events of mcp_map_neighbours_last_timing / mcp_map_mkf_cull_last_timing.  The live counts of a removal go through `marks`.
+  std::vector<uint8_t> h_act;
+  Buf<double> n_dist; Buf<uint8_t> n_cand; Buf<MgnCtl> n_ctl; Buf<mcp_neigh_result> n_res; Buf<MgMkf> n_ext; Buf<MgnCull> n_cc; PinBuf<char> n_out;
+  hipEvent_t n_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool n_timed[2] = {false, false};      // [0], [1]: a query; [2], [3]: a removal
   ~mcp_map_graph() {
     if (m && m->st) (void)hipStreamSynchronize(m->st);
-    for (hipEvent_t e : {staged, t0, t1, c_ev[0], c_ev[1], c_ev[2], c_ev[3]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {staged, t0, t1, c_ev[0], c_ev[1], c_ev[2], c_ev[3], n_ev[0], n_ev[1], n_ev[2], n_ev[3]}) if (e) (void)hipEventDestroy(e);
+  }
+  int neigh_ready() {
+    for (hipEvent_t& e : n_ev) if (!e) ICK(hipEventCreate(&e));
+    const size_t n_idx = (size_t)(MCP_MAP_MAX_MKFS + 1)*MCP_MAX_FRAME_CAMS;
+    return (n_dist.alloc(n_idx) || n_cand.alloc(n_idx) || n_ctl.alloc(2) || n_res.alloc(2) || n_ext.alloc(1) || n_cc.alloc(1) ||
+            n_out.alloc(2*sizeof(mcp_neigh_result) + sizeof(MgnCull))) ? -1 : 0;
   }
   int cull_ready() { for (hipEvent_t& e : c_ev) if (!e) ICK(hipEventCreate(&e)); return c_ctl.alloc(1); }
   int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
@@ -2721,7 +2734,7 @@ static int mg_mkfs_upload(mcp_map_graph* g, const std::string& who, bool by_ids,
                      (const int*)(g->up_dev.p + o_ids), (const MgMkf*)g->up_dev.p);
   ICK(hipGetLastError());
   if (g->staged_now()) return -1;
-  for (int k = 0; k < count; ++k) g->h_flags[hid[k]] = flags[k];
+  for (int k = 0; k < count; ++k) { g->h_flags[hid[k]] = flags[k]; std::memcpy(&g->h_act[(size_t)hid[k]*MCP_MAX_FRAME_CAMS], rec[k].active, MCP_MAX_FRAME_CAMS); }
   return 0;
 }
 
@@ -2832,6 +2845,7 @@ mcp_map_graph* mcp_map_graph_create(mcp_map_points* m, int ncam, const double* c
   std::memset(&g->rig, 0, sizeof g->rig); g->rig.ncam = ncam;
   for (int c = 0; c < ncam; ++c) mg_se3_of12(cfb + 12*(size_t)c, g->rig.cfb[c]);
   g->h_flags.assign(MCP_MAP_MAX_MKFS, 0);
+  g->h_act.assign((size_t)MCP_MAP_MAX_MKFS*MCP_MAX_FRAME_CAMS, 0);
   const bool ok = !g->slots.alloc(MCP_MAP_MAX_MKFS) && !g->ctl.alloc(1) && !g->h_ctl.alloc(1) && !g->h_res.alloc(1) && !g->adjust.alloc(MCP_MAP_MAX_MKFS) &&
                   !g->mkf_bidx.alloc(MCP_MAP_MAX_MKFS) && !g->v_mkfs.alloc(MCP_MAP_MAX_MKFS) && hipEventCreateWithFlags(&g->staged, hipEventDisableTiming) == hipSuccess &&
                   hipEventCreate(&g->t0) == hipSuccess && hipEventCreate(&g->t1) == hipSuccess &&
@@ -2909,7 +2923,7 @@ int mcp_map_graph_add_meas(mcp_map_graph* g, int count, const int* mkf, const in
 static int mg_erase_run(mcp_map_graph* g, const unsigned long long* d_keys, int n_keys, int slot) {
   hipStream_t st = g->m->st;
   ICK(hipMemsetAsync(&g->ctl.p->erased, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_mg_erase, dim3((unsigned)std::max(1, (g->n_store + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, st, g->store.p, g->n_store, d_keys, n_keys, slot, g->slots.p, g->ctl.p);
+  hipLaunchKernelGGL(k_mg_erase, dim3((unsigned)std::max(1, (g->n_store + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, st, g->store.p, g->n_store, d_keys, n_keys, slot, g->slots.p, g->ctl.p, (const int*)nullptr);
   ICK(hipGetLastError());
   ICK(hipMemcpyAsync(g->h_ctl.p, g->ctl.p, sizeof(MgCtl), hipMemcpyDeviceToHost, st));
   if (g->sync()) return -1;
@@ -3660,6 +3674,144 @@ int mcp_map_cull_last_timing(const mcp_map_graph* g, double* outliers_ms, double
     *out[k] = ms;
   }
   return 0;
+}
+
+}  // extern "C"
+
+// ---- the neighbour queries and the removal of an MKF (include/mcp_img.h mcp_map_neighbours, mcp_map_mkf_cull; map_graph_neigh.h) -------------
+namespace {
+// the two launches of one query on the table's stream, into entry q of the graph's hand-offs and results (zeroed here).  src_from: see k_mgn_dist
+int mgn_enqueue(mcp_map_graph* g, const MgnQuery& Q, int q, const int* src_from) {
+  hipStream_t st = g->m->st;
+  ICK(hipMemsetAsync(g->n_ctl.p + q, 0, sizeof(MgnCtl), st));
+  ICK(hipMemsetAsync(g->n_res.p + q, 0, sizeof(mcp_neigh_result), st));
+  int n_slots = MCP_MAP_MAX_MKFS;                      // the slots up to the last present one: nothing above them is a candidate
+  while (n_slots > 0 && !(g->h_flags[n_slots - 1] & MCP_MKF_PRESENT)) --n_slots;
+  const int n_idx = mgn_indices(Q.kind, n_slots);
+  hipLaunchKernelGGL(k_mgn_dist, dim3((unsigned)((n_idx + MGN_BLOCK - 1)/MGN_BLOCK)), dim3(MGN_BLOCK), 0, st, Q, n_idx, g->rig, (const MgMkf*)g->slots.p, (const MgMkf*)g->n_ext.p, src_from,
+                     g->n_dist.p, g->n_cand.p, g->n_ctl.p + q);
+  hipLaunchKernelGGL(k_mgn_select, dim3(1), dim3(MGN_BLOCK), 0, st, Q, n_idx, (const MgMkf*)g->slots.p, (const double*)g->n_dist.p, (const uint8_t*)g->n_cand.p, g->n_ctl.p + q, g->n_res.p + q);
+  ICK(hipGetLastError());
+  return 0;
+}
+int mgn_timing(const mcp_map_graph* g, int k, double* device_ms) {
+  *device_ms = -1.0;
+  if (!g->n_timed[k]) return 0;
+  float ms = 0.f;
+  ICK(hipEventElapsedTime(&ms, g->n_ev[2*k], g->n_ev[2*k + 1]));
+  *device_ms = ms;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mcp_map_neighbours(mcp_map_graph* g, const mcp_neigh_params* p, mcp_neigh_result* res) {
+  const std::string who = "mcp_map_neighbours";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!res) return img_fail(who + ": NULL result");
+  std::string bad = mgn_params_check(p, g->rig.ncam);
+  if (bad.empty()) bad = mgn_source_check(p, p->src_slot >= 0 ? g->h_flags[p->src_slot] : 0, p->src_slot >= 0 ? &g->h_act[(size_t)p->src_slot*MCP_MAX_FRAME_CAMS] : nullptr);
+  if (!bad.empty()) return img_fail(who + ": " + bad);
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const MgnQuery Q = mgn_query(*p);
+  const bool ext = p->src_slot < 0;
+  if (g->n_dist.n == 0 && g->sync()) return -1;        // (the scratch is allocated once, with nothing in flight)
+  if (g->neigh_ready() || (ext && g->stage(sizeof(MgMkf)))) return -1;
+  if (ext) {
+    MgMkf* rec = reinterpret_cast<MgMkf*>(g->up_in.p);
+    std::memset(rec, 0, sizeof(MgMkf));
+    std::memcpy(rec->bfw, p->ext_base_from_world, 96);
+    for (int c = 0; c < g->rig.ncam; ++c) { const bool a = p->ext_active[c] != 0; rec->active[c] = a ? 1 : 0; rec->depth[c] = a ? p->ext_depth_mean[c] : 0.0; }
+  }
+  hipStream_t st = m->st;
+  g->n_timed[0] = false;
+  Drain drain{m, true};
+  ICK(hipEventRecord(g->n_ev[0], st));
+  if (ext) { ICK(hipMemcpyAsync(g->n_ext.p, g->up_in.p, sizeof(MgMkf), hipMemcpyHostToDevice, st)); if (g->staged_now()) return -1; }
+  if (mgn_enqueue(g, Q, 0, nullptr)) return -1;
+  if (Q.want_meas && g->n_store) {
+    hipLaunchKernelGGL(k_mgn_count, dim3((unsigned)((g->n_store + MGN_BLOCK - 1)/MGN_BLOCK)), dim3(MGN_BLOCK), 0, st, Q.kind, (const MgMeas*)g->store.p, g->n_store, g->n_res.p);
+    ICK(hipGetLastError());
+  }
+  ICK(hipEventRecord(g->n_ev[1], st));
+  ICK(hipMemcpyAsync(g->n_out.p, g->n_res.p, sizeof(mcp_neigh_result), hipMemcpyDeviceToHost, st));
+  if (g->sync()) return -1;                            // the one wait
+  drain.armed = false; g->n_timed[0] = true;
+  std::memcpy(res, g->n_out.p, sizeof(mcp_neigh_result));
+  return 0;
+}
+
+int mcp_map_neighbours_last_timing(const mcp_map_graph* g, double* device_ms) {
+  if (!g || !device_ms) return img_fail("mcp_map_neighbours_last_timing: bad arguments");
+  return mgn_timing(g, 0, device_ms);
+}
+
+int mcp_map_mkf_cull(mcp_map_graph* g, const mcp_mkf_cull_params* p, mcp_mkf_cull_result* res) {
+  const std::string who = "mcp_map_mkf_cull";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!p || !res) return img_fail(who + ": NULL params or result");
+  auto present = [&](int k) { return k >= 0 && k < MCP_MAP_MAX_MKFS && (g->h_flags[k] & MCP_MKF_PRESENT); };
+  if (p->slot != -1 && !present(p->slot)) return img_fail(who + ": the victim (slot " + std::to_string(p->slot) + ") is not a present slot");
+  if (p->slot == -1 && !present(p->furthest_from)) return img_fail(who + ": furthest_from (slot " + std::to_string(p->furthest_from) + ") is not a present slot");
+  if (p->max_kfs < 0) return img_fail(who + ": a negative max_kfs");
+  if (!std::isfinite(p->mean_diff_fraction)) return img_fail(who + ": mean_diff_fraction is not finite");
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  const int R = m->rows, M = g->n_store;
+  const size_t n_marks = 2*(size_t)std::max(R, 1);
+  if ((g->n_dist.n == 0 || g->marks.n < n_marks) && g->sync()) return -1;      // (a block that grows is replaced with nothing in flight on the old one)
+  if (g->neigh_ready() || g->marks.alloc(n_marks) || g->grow_points(R)) return -1;
+  MgnQuery Q;
+  Q.kind = MCP_NB_MKF; Q.region = MCP_NB_ALL; Q.src_cam = 0; Q.same_cam = 0; Q.n_max = 1; Q.want_meas = 0; Q.max_dist = HUGE_VAL; Q.frac = p->mean_diff_fraction;
+  MgnCullIn P; P.slot = p->slot; P.mark_points = p->mark_points ? 1 : 0; P.max_kfs = p->max_kfs; P.erase = p->erase ? 1 : 0;
+  int* live = g->marks.p; int* by_src = live + std::max(R, 1);
+  hipStream_t st = m->st;
+  const dim3 B(MGN_BLOCK), GM((unsigned)std::max(1, (M + MGN_BLOCK - 1)/MGN_BLOCK));
+  g->n_timed[1] = false;
+  Drain drain{m, true};
+  ICK(hipEventRecord(g->n_ev[2], st));
+  ICK(hipMemsetAsync(g->n_cc.p, 0, sizeof(MgnCull), st));
+  ICK(hipMemsetAsync(&g->ctl.p->erased, 0, sizeof(int), st));
+  const mcp_neigh_result* far = nullptr;
+  if (p->slot == -1) {                                 // FurthestMultiKeyFrame(furthest_from)
+    Q.order = MCP_NB_FURTHEST; Q.src_slot = p->furthest_from;
+    if (mgn_enqueue(g, Q, 0, nullptr)) return -1;
+    far = g->n_res.p;
+  }
+  Q.order = MCP_NB_NEAREST; Q.src_slot = p->slot;      // ClosestMultiKeyFrame(victim): used if the victim is fixed
+  if (mgn_enqueue(g, Q, 1, far ? &g->n_ctl.p->first_slot : nullptr)) return -1;
+  hipLaunchKernelGGL(k_mgn_decide, dim3(1), dim3(64), 0, st, P, far, (const mcp_neigh_result*)(g->n_res.p + 1), g->slots.p, g->n_cc.p);
+  if (P.mark_points && M) {
+    ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*n_marks, st));
+    hipLaunchKernelGGL(k_mgn_rows_count, GM, B, 0, st, (const MgnCull*)g->n_cc.p, (const MgMeas*)g->store.p, M, R, g->prow, (const MgPoint*)g->pts.p, live, by_src);
+  }
+  if (M) hipLaunchKernelGGL(k_mgn_mark, GM, B, 0, st, P, g->n_cc.p, (const MgMeas*)g->store.p, M, R, g->prow, g->pts.p, (const int*)live, (const int*)by_src);
+  if (P.erase) hipLaunchKernelGGL(k_mg_erase, GM, dim3(MG_BLOCK), 0, st, g->store.p, M, (const unsigned long long*)nullptr, 0, -1, g->slots.p, g->ctl.p, (const int*)&g->n_cc.p->victim);
+  ICK(hipGetLastError());
+  ICK(hipEventRecord(g->n_ev[3], st));
+  ICK(hipMemcpyAsync(g->n_out.p, g->n_cc.p, sizeof(MgnCull), hipMemcpyDeviceToHost, st));
+  ICK(hipMemcpyAsync(g->h_ctl.p, g->ctl.p, sizeof(MgCtl), hipMemcpyDeviceToHost, st));
+  if (g->sync()) return -1;                            // the one wait
+  drain.armed = false; g->n_timed[1] = true;
+  const MgnCull& C = *reinterpret_cast<const MgnCull*>(g->n_out.p);
+  std::memset(res, 0, sizeof *res);
+  res->status = C.status; res->victim = C.victim; res->victim_dist_valid = C.dist_valid; res->victim_dist = C.dist; res->new_fixed = C.new_fixed;
+  if (C.status == 0) {
+    res->n_victim_meas = C.n_victim_meas; res->n_rows_marked = C.n_rows_marked; res->n_by_count = C.n_by_count; res->n_by_source = C.n_by_source;
+    res->n_meas_erased = P.erase ? g->h_ctl.p->erased : 0;
+    g->n_live -= res->n_meas_erased;
+    g->h_flags[C.victim] |= MCP_MKF_BAD;
+    if (C.new_fixed >= 0) g->h_flags[C.new_fixed] |= MCP_MKF_FIXED;
+    if (P.erase) g->h_flags[C.victim] &= ~MCP_MKF_PRESENT;
+  }
+  return 0;
+}
+
+int mcp_map_mkf_cull_last_timing(const mcp_map_graph* g, double* device_ms) {
+  if (!g || !device_ms) return img_fail("mcp_map_mkf_cull_last_timing: bad arguments");
+  return mgn_timing(g, 1, device_ms);
 }
 
 }  // extern "C"

@@ -20,7 +20,8 @@
 #pragma once
 #include <cfloat>
 #include "ba_device.h"
-#include "stereo_kernels.h"      // se3_inverse
+#include "stereo_kernels.h"
+#include "map_graph_dist.h"      // se3_inverse, MgRig, the keyframe distances
 
 namespace mcp {
 
@@ -30,7 +31,6 @@ constexpr int MG_MAX_MKFS = MCP_MAP_MAX_MKFS;
 struct MgMkf { double bfw[12]; double depth[MCP_MAX_FRAME_CAMS]; int flags; uint8_t active[MCP_MAX_FRAME_CAMS]; int pad_; };      // one slot (176 B)
 struct MgPoint { int src_mkf, src_cam, flags, pending; };      // one row (16 B); pending: the device turned the row bad and no sweep has reported it yet (map_graph_cull.h)
 struct MgMeas { double uv[2]; int mkf, cam, row, level, source, alive; };                                                         // one store entry (40 B)
-struct MgRig { Se3 cfb[MCP_MAX_FRAME_CAMS]; int ncam; };
 
 // what the launches of one select hand to each other
 struct MgCtl {
@@ -40,46 +40,7 @@ struct MgCtl {
 };
 
 __host__ __device__ inline bool mg_mkf_ok(int flags) { return (flags & MCP_MKF_PRESENT) && !(flags & MCP_MKF_BAD); }
-__host__ __device__ inline void mg_se3_of12(const double* a, Se3& T) {
-  for (int k = 0; k < 9; ++k) T.R[k] = a[k];
-  for (int k = 0; k < 3; ++k) T.t[k] = a[9 + k];
-}
-
-// KeyFrame::Distance (KeyFrame.cc:715-747) from the two CamFromWorld and mean scene depths; *broken: the value the reference stops the process on
-__host__ __device__ inline double mg_kf_distance(const Se3& cfw1, double depth1, const Se3& cfw2, double depth2, double frac, bool* broken) {
-  Se3 i1, i2;
-  se3_inverse(cfw1, i1); se3_inverse(cfw2, i2);
-  const double m1c[3] = {0.0, 0.0, depth1}, m2c[3] = {0.0, 0.0, depth2};
-  double m1[3], m2[3];
-  se3_apply(i1, m1c, m1); se3_apply(i2, m2c, m2);
-  const double d[3] = {i2.t[0] - i1.t[0], i2.t[1] - i1.t[1], i2.t[2] - i1.t[2]};
-  const double e[3] = {m2[0] - m1[0], m2[1] - m1[1], m2[2] - m1[2]};
-  const double dist = sqrt(d[0]*d[0] + d[1]*d[1] + d[2]*d[2]) + sqrt(e[0]*e[0] + e[1]*e[1] + e[2]*e[2])*frac;
-  *broken = !(dist - dist == 0.0) || dist > 1e10;      // (!isfinite, spelled for both compilers)
-  return dist;
-}
-
-// MultiKeyFrame::Distance (KeyFrame.cc:903-927): the minimum over the pairs of active keyframes; DBL_MAX when there is no such pair
-__host__ __device__ inline double mg_mkf_distance(const MgRig& rig, const double* bfw_a, const uint8_t* act_a, const double* dep_a,
-                                                  const double* bfw_b, const uint8_t* act_b, const double* dep_b, double frac, bool* broken) {
-  Se3 A, B;
-  mg_se3_of12(bfw_a, A); mg_se3_of12(bfw_b, B);
-  double best = DBL_MAX;
-  *broken = false;
-  for (int c1 = 0; c1 < rig.ncam; ++c1) {
-    if (!act_a[c1]) continue;
-    Se3 w1; se3_compose(rig.cfb[c1], A, w1);
-    for (int c2 = 0; c2 < rig.ncam; ++c2) {
-      if (!act_b[c2]) continue;
-      Se3 w2; se3_compose(rig.cfb[c2], B, w2);
-      bool br;
-      const double d = mg_kf_distance(w1, dep_a[c1], w2, dep_b[c2], frac, &br);
-      if (br) *broken = true;
-      if (d < best) best = d;
-    }
-  }
-  return best;
-}
+// (MgRig, mg_se3_of12, mg_kf_distance, mg_mkf_distance: map_graph_dist.h)
 
 // BundleAdjusterBase.cc:170-176 (ALL) and :231-237 (RECENT): is the row taken (before the source rule)
 __host__ __device__ inline bool mg_row_selected(int mode, int pflags, int good, int seen) {
@@ -125,9 +86,12 @@ k_mg_points_fill(MgPoint* __restrict__ rows, int first, int count) {
 }
 
 // ---- erase and compact -----------------------------------------------------------------------------------------------------------------
-// one thread per entry: a live entry whose key is among the sorted keys (binary search) -- or, keys == NULL, whose MKF is `slot` -- dies
+// one thread per entry: a live entry whose key is among the sorted keys (binary search) -- or, keys == NULL, whose MKF is `slot` -- dies.
+// slot_from: NULL, or where an earlier launch left the slot (mcp_map_mkf_cull; < 0: there is none and nothing dies)
 __global__ void __launch_bounds__(MG_BLOCK)
-k_mg_erase(MgMeas* __restrict__ store, int n, const unsigned long long* __restrict__ keys, int n_keys, int slot, MgMkf* __restrict__ slots, MgCtl* __restrict__ ctl) {
+k_mg_erase(MgMeas* __restrict__ store, int n, const unsigned long long* __restrict__ keys, int n_keys, int slot, MgMkf* __restrict__ slots, MgCtl* __restrict__ ctl,
+           const int* __restrict__ slot_from) {
+  if (slot_from) { slot = *slot_from; if (slot < 0) return; }      // (uniform over the grid)
   const int i = blockIdx.x*MG_BLOCK + threadIdx.x;
   bool dies = false;
   if (i < n && store[i].alive) {

@@ -14,6 +14,7 @@
 // Hand-offs are kernel boundaries on one stream; no workgroup waits for another.
 #pragma once
 #include "img_kernels.h"
+#include "map_graph_dist.h"      // se3_inverse
 
 namespace mcp {
 
@@ -36,14 +37,7 @@ __host__ __device__ inline double dot3(const double* a, const double* b) { retur
 __host__ __device__ inline void normalize3(double* v) { const double n = sqrt(dot3(v, v)); v[0] /= n; v[1] /= n; v[2] /= n; }   // TooN normalize
 __host__ __device__ inline void cross3(const double* a, const double* b, double* o) {
   const double x = a[1]*b[2] - a[2]*b[1], y = a[2]*b[0] - a[0]*b[2], z = a[0]*b[1] - a[1]*b[0]; o[0] = x; o[1] = y; o[2] = z; }
-__host__ __device__ inline void se3_inverse(const Se3& A, Se3& B) {         // TooN SE3::inverse: (R^T, -(R^T t))
-  double t[3]; mat3t_vec(A.R, A.t, t);
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) B.R[3*r + c] = A.R[3*c + r];
-  B.t[0] = -t[0]; B.t[1] = -t[1]; B.t[2] = -t[2];
-}
+// (se3_inverse: map_graph_dist.h)
 
 // The epipolar arc of one candidate against one target (:611-723) and the probe MapPoint's NC vectors (:726-738).
 struct StereoArc {

@@ -62,6 +62,7 @@ IMG_SYMBOLS = [
     "mcp_meas_parcel_create", "mcp_meas_parcel_destroy", "mcp_meas_parcel_from_track", "mcp_meas_parcel_from_refind", "mcp_meas_parcel_from_host",
     "mcp_meas_parcel_size", "mcp_meas_parcel_get", "mcp_meas_parcel_commit", "mcp_parcel_commit_host",
     "mcp_map_cull_outliers", "mcp_map_cull_sweep", "mcp_map_cull_rows_view", "mcp_map_cull_last_timing", "mcp_map_cull_outliers_host", "mcp_map_cull_sweep_host",
+    "mcp_map_neighbours", "mcp_map_neighbours_last_timing", "mcp_map_neighbours_host", "mcp_map_mkf_cull", "mcp_map_mkf_cull_last_timing", "mcp_map_mkf_cull_host",
 ]
 _BOUND = False
 

@@ -18,7 +18,14 @@ src/MapMaker.cc:407-418), state the verdicts.
 Outliers and bad points (mcp_map_cull_*): MapGraph.cull_outliers is MapMakerServerBase::HandleOutliers over the store, MapGraph.cull_sweep the
 point half of MapMaker::HandleBadEntities (danglers, tracker outliers, the bad points' measurements erased, their rows unusable, the rows the
 device turned bad reported); cull_outliers_host / cull_sweep_host are the host twins (no device) and cull_outliers_ref / cull_sweep_ref the
-numpy restatements (src/MapMakerServerBase.cc:1198-1238, src/MapMakerClientBase.cc:73-108, src/Map.cc:93-116)."""
+numpy restatements (src/MapMakerServerBase.cc:1198-1238, src/MapMakerClientBase.cc:73-108, src/Map.cc:93-116).
+
+Closest-keyframe queries and the removal of an MKF (mcp_map_neighbours, mcp_map_mkf_cull): MapGraph.neighbours is the one call behind
+closest_multi_keyframe, n_closest_multi_keyframes, furthest_multi_keyframe, closest_keyframe, closest_keyframes_within_dist and
+n_closest_keyframes (src/MapMakerBase.cc:90-339) and the tracker's need_new_multi_keyframe / is_distance_to_nearest_mkf_excessive
+(src/MapMakerClientBase.cc:111-226); MapGraph.cull_mkf is MarkFurthestMultiKeyFrameAsBad with the MKF half of HandleBadEntities
+(src/MapMakerServerBase.cc:264-318, src/Map.cc:119-187); neighbours_host / cull_mkf_host are the host twins (no device), neighbours_ref /
+cull_mkf_ref the numpy restatements."""
 import ctypes
 
 import numpy as np
@@ -127,6 +134,55 @@ class CullSweepResult(ctypes.Structure):
 CULL_STRUCT_SIZES = {"mcp_cull_outliers_params": ctypes.sizeof(CullOutliersParams), "mcp_cull_outliers_result": ctypes.sizeof(CullOutliersResult),
                      "mcp_cull_sweep_params": ctypes.sizeof(CullSweepParams), "mcp_cull_sweep_result": ctypes.sizeof(CullSweepResult)}
 
+# closest-keyframe queries and the removal of an MKF (include/mcp_img.h mcp_map_neighbours, mcp_map_mkf_cull; map_graph_neigh.h)
+NEIGH_SYMBOLS = ["mcp_map_neighbours", "mcp_map_neighbours_last_timing", "mcp_map_neighbours_host", "mcp_map_mkf_cull", "mcp_map_mkf_cull_last_timing",
+                 "mcp_map_mkf_cull_host"]
+NB_MKF, NB_KF = 0, 1
+NB_ALL, NB_ONLY_SELF, NB_ONLY_OTHER = 0, 1, 2
+NB_NEAREST, NB_FURTHEST = 0, 1
+NB_MAX = 32
+NEIGH_BLOCK = 256                             # map_graph_neigh.h: candidates or entries of a workgroup
+DBL_MAX = float(np.finfo(np.float64).max)
+NEIGH_ITEM_DTYPE = np.dtype([("dist", "f8"), ("slot", "i4"), ("cam", "i4"), ("flags", "i4"), ("n_meas", "i4")], align=True)
+
+
+class NeighParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("kind", "region", "order", "src_slot", "src_cam", "same_cam", "n_max", "want_meas")] + \
+               [("max_dist", ctypes.c_double), ("mean_diff_fraction", ctypes.c_double), ("ext_base_from_world", ctypes.c_double * 12),
+                ("ext_active", ctypes.c_uint8 * MAX_CAMS), ("ext_depth_mean", ctypes.c_double * MAX_CAMS)]
+
+
+class NeighItem(ctypes.Structure):
+    _fields_ = [("dist", ctypes.c_double), ("slot", ctypes.c_int), ("cam", ctypes.c_int), ("flags", ctypes.c_int), ("n_meas", ctypes.c_int)]
+
+
+class NeighResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("count", ctypes.c_int), ("n_candidates", ctypes.c_int), ("pad_", ctypes.c_int), ("item", NeighItem * NB_MAX)]
+
+    def as_dict(self):
+        return dict(status=int(self.status), count=int(self.count), n_candidates=int(self.n_candidates))
+
+    def items(self):
+        """The `count` winners as a NEIGH_ITEM_DTYPE array (a copy)."""
+        return np.frombuffer(bytes(self), dtype=NEIGH_ITEM_DTYPE, offset=NeighResult.item.offset)[:self.count].copy()
+
+
+class MkfCullParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("slot", "furthest_from", "mark_points", "max_kfs", "erase")] + [("mean_diff_fraction", ctypes.c_double)]
+
+
+class MkfCullResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int), ("victim", ctypes.c_int), ("victim_dist_valid", ctypes.c_int), ("victim_dist", ctypes.c_double)] + \
+               [(k, ctypes.c_int) for k in ("n_victim_meas", "n_rows_marked", "n_by_count", "n_by_source", "new_fixed", "n_meas_erased")]
+
+    def as_dict(self):
+        return {k: (float if k == "victim_dist" else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
+NEIGH_STRUCT_SIZES = {"mcp_neigh_params": ctypes.sizeof(NeighParams), "mcp_neigh_item": ctypes.sizeof(NeighItem), "mcp_neigh_result": ctypes.sizeof(NeighResult),
+                      "mcp_mkf_cull_params": ctypes.sizeof(MkfCullParams), "mcp_mkf_cull_result": ctypes.sizeof(MkfCullResult)}
+assert NEIGH_ITEM_DTYPE.itemsize == ctypes.sizeof(NeighItem)
+
 _BOUND = False
 
 
@@ -177,6 +233,12 @@ def lib():
         L.mcp_map_cull_last_timing.argtypes = [vp, vp, vp]
         L.mcp_map_cull_outliers_host.argtypes = [ip, vp, vp, vp, vp, ip, ip, vp, ip, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
         L.mcp_map_cull_sweep_host.argtypes = [vp, ip, vp, ip, ip, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, ip, vp]
+        L.mcp_map_neighbours.argtypes = [vp, vp, vp]
+        L.mcp_map_neighbours_last_timing.argtypes = [vp, vp]
+        L.mcp_map_neighbours_host.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp]
+        L.mcp_map_mkf_cull.argtypes = [vp, vp, vp]
+        L.mcp_map_mkf_cull_last_timing.argtypes = [vp, vp]
+        L.mcp_map_mkf_cull_host.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, ip, ip, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]
         _BOUND = True
     return L
 
@@ -547,6 +609,209 @@ def cull_sweep_ref(a, min_outliers=20, outlier_multiplier=1.0, danglers=True, n_
     return res, rows, _cull_merge(a, b)
 
 
+# ---- closest-keyframe queries and the removal of an MKF: parameters, the host twins, the numpy restatements -------------------------------------
+def neigh_params(kind=NB_MKF, region=NB_ALL, order=NB_NEAREST, src_slot=-1, src_cam=0, same_cam=False, n_max=1, want_meas=False, max_dist=np.inf,
+                 mean_diff_fraction=0.5, ext=None):
+    """mcp_neigh_params.  ext: the external MKF (src_slot == -1) as dict(base_from_world (12,), kf_active (ncam,), kf_depth_mean (ncam,))."""
+    p = NeighParams(int(kind), int(region), int(order), int(src_slot), int(src_cam), int(bool(same_cam)), int(n_max), int(bool(want_meas)), float(max_dist),
+                    float(mean_diff_fraction))
+    if ext is not None:
+        b, a, d = _f64(ext["base_from_world"]).reshape(12), np.asarray(ext["kf_active"]).reshape(-1), _f64(ext["kf_depth_mean"]).reshape(-1)
+        if len(a) > MAX_CAMS or len(a) != len(d):
+            raise ValueError("neigh_params: the external MKF has one active byte and one depth mean per camera of the rig")
+        for k in range(12):
+            p.ext_base_from_world[k] = b[k]
+        for c in range(len(a)):
+            p.ext_active[c], p.ext_depth_mean[c] = int(a[c] != 0), d[c]
+    return p
+
+
+def _as_neigh_params(params):
+    return params if isinstance(params, NeighParams) else neigh_params(**params)
+
+
+def _mkf_columns(a):
+    P, C = len(a["mkf_flags"]), int(a["ncam"])
+    return (C, P, _f64(a["cam_from_base"], (C, 12)), _f64(a["base_from_world"], (P, 12)), _i32(a["mkf_flags"], (P,)), _u8(a["kf_active"], (P, C)),
+            _f64(a["kf_depth_mean"], (P, C)))
+
+
+def neighbours_host(a, params, raw=False):
+    """mcp_map_neighbours_host over the flat arrays `a` (problem_arrays' keys): (dict of status / count / n_candidates, the winners as a
+    NEIGH_ITEM_DTYPE array), or with raw the NeighResult itself.  params: a NeighParams or neigh_params' keywords.  Needs no device.  A refusal
+    raises RuntimeError."""
+    p = _as_neigh_params(params)
+    C, P, cfb, bfw, mf, act, dep = _mkf_columns(a)
+    M = len(a["ms_mkf"])
+    mm, mc, al = _i32(a["ms_mkf"], (M,)), _i32(a["ms_cam"], (M,)), _u8(a["ms_alive"], (M,))
+    res = NeighResult()
+    _chk(lib().mcp_map_neighbours_host(ctypes.addressof(p), C, cfb.ctypes.data, P, bfw.ctypes.data, mf.ctypes.data, act.ctypes.data, dep.ctypes.data, M, mm.ctypes.data,
+                                       mc.ctypes.data, al.ctypes.data, ctypes.addressof(res)), "map_neighbours_host")
+    return res if raw else (res.as_dict(), res.items())
+
+
+def _cull_mkf_state(a):
+    """The columns mcp_map_mkf_cull changes, copied out of `a`: (mkf_flags, pt_flags, pending, ms_alive)."""
+    Np = len(a["pt_flags"])
+    return (_i32(a["mkf_flags"]).copy(), _i32(a["pt_flags"]).copy(), (np.zeros(Np, dtype=np.uint8) if a.get("pending") is None else _u8(a["pending"], (Np,)).copy()),
+            _u8(a["ms_alive"]).copy())
+
+
+def _cull_mkf_merge(a, mf, pf, pend, alive):
+    out = copy_arrays(a)
+    out["mkf_flags"], out["pt_flags"], out["pending"], out["ms_alive"] = mf, pf, pend, alive
+    return out
+
+
+def cull_mkf_host(a, slot=-1, furthest_from=-1, mark_points=True, max_kfs=2, erase=True, mean_diff_fraction=0.5, n_rows=None):
+    """mcp_map_mkf_cull_host over the flat arrays `a`: (dict of mcp_mkf_cull_result, the arrays afterwards -- a copy of `a` with mkf_flags,
+    pt_flags, pending and ms_alive as the call leaves them).  Needs no device.  A refusal raises RuntimeError."""
+    C, P, cfb, bfw, _, act, dep = _mkf_columns(a)
+    mf, pf, pend, alive = _cull_mkf_state(a)
+    Np, M = len(pf), len(alive)
+    n_rows = int(a.get("n_rows", Np)) if n_rows is None else int(n_rows)
+    sm, sc = _i32(a["src_mkf"], (Np,)), _i32(a["src_cam"], (Np,))
+    mm, mc, mr = _i32(a["ms_mkf"], (M,)), _i32(a["ms_cam"], (M,)), _i32(a["ms_row"], (M,))
+    prm, res = MkfCullParams(int(slot), int(furthest_from), int(bool(mark_points)), int(max_kfs), int(bool(erase)), float(mean_diff_fraction)), MkfCullResult()
+    _chk(lib().mcp_map_mkf_cull_host(ctypes.addressof(prm), C, cfb.ctypes.data, P, bfw.ctypes.data, mf.ctypes.data, act.ctypes.data, dep.ctypes.data, n_rows, Np, sm.ctypes.data,
+                                     sc.ctypes.data, pf.ctypes.data, pend.ctypes.data, M, mm.ctypes.data, mc.ctypes.data, mr.ctypes.data, alive.ctypes.data,
+                                     ctypes.addressof(res)), "map_mkf_cull_host")
+    return res.as_dict(), _cull_mkf_merge(a, mf, pf, pend, alive)
+
+
+def _kf_frames(cfb, bfw, dep):
+    """Per (MKF, camera): the camera centre and the mean scene point in the world, each product and sum in the order KeyFrame::Distance's
+    callers take them (CamFromWorld = CamFromBase * BaseFromWorld; inverse(); inverse * (0, 0, depth)).  bfw (n, 12), dep (n, C) -> two (n, C, 3)."""
+    C = len(cfb)
+    cR, ct = cfb[:, :9].reshape(C, 3, 3)[None], cfb[:, 9:][None]
+    bR, bt = bfw[:, :9].reshape(-1, 3, 3)[:, None], bfw[:, 9:][:, None]
+    R = [[cR[..., i, 0] * bR[..., 0, j] + cR[..., i, 1] * bR[..., 1, j] + cR[..., i, 2] * bR[..., 2, j] for j in range(3)] for i in range(3)]
+    t = [cR[..., i, 0] * bt[..., 0] + cR[..., i, 1] * bt[..., 1] + cR[..., i, 2] * bt[..., 2] + ct[..., i] for i in range(3)]
+    with np.errstate(all="ignore"):
+        centre = [-(R[0][i] * t[0] + R[1][i] * t[1] + R[2][i] * t[2]) for i in range(3)]            # -(R^T t)
+        mean = [R[0][i] * 0.0 + R[1][i] * 0.0 + R[2][i] * dep + centre[i] for i in range(3)]        # R^T (0, 0, depth) + centre
+    return np.stack(centre, axis=-1), np.stack(mean, axis=-1)
+
+
+def _kf_dist(c1, m1, c2, m2, frac):
+    """KeyFrame::Distance (src/KeyFrame.cc:715-747) from centres and mean points (..., 3), 1: the source, 2: the candidate."""
+    with np.errstate(all="ignore"):
+        d, e = c2 - c1, m2 - m1
+        return np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]) + \
+            np.sqrt(e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1] + e[..., 2] * e[..., 2]) * frac
+
+
+def neighbours_ref(a, params):
+    """The reference's closest-keyframe queries (src/MapMakerBase.cc:90-339 over src/KeyFrame.cc:715-747, 903-927) in numpy, over the flat
+    arrays, with the documented deviations ((slot, cam) as the tie-breaker, kf_active as the record that a keyframe exists, status 3).  The
+    external MKF is row 0 of every column here, slot -1.  Returns what neighbours_host returns."""
+    p = _as_neigh_params(params)
+    C, P, cfb, bfw, mf, act, dep = _mkf_columns(a)
+    kf = p.kind == NB_KF
+    ext = p.src_slot == -1
+    bfw = np.concatenate([np.array(p.ext_base_from_world, dtype=np.float64).reshape(1, 12), bfw])
+    ea = np.array(p.ext_active[:C], dtype=np.uint8) != 0
+    act = np.concatenate([ea.reshape(1, C), act != 0])
+    dep = np.concatenate([np.where(ea, np.array(p.ext_depth_mean[:C]), 0.0).reshape(1, C), np.where(act[1:], dep, 0.0)])
+    flags = np.concatenate([[0], mf]).astype(np.int64)
+    present = (flags & MKF_PRESENT) != 0
+    slot = np.arange(-1, P)
+    centre, mean = _kf_frames(cfb, bfw, dep)
+    s = p.src_slot + 1
+    if kf:
+        own = (slot == p.src_slot)[:, None]
+        cam = np.arange(C)[None, :]
+        cand = (present[:, None] | (own & ext)) & act & ~(own & (cam == p.src_cam))
+        if p.region == NB_ONLY_SELF:
+            cand &= own
+        if p.region == NB_ONLY_OTHER:
+            cand &= ~own
+        if p.same_cam:
+            cand &= cam == p.src_cam
+        j, c = np.nonzero(cand)                                                     # ascending (slot, cam)
+        d = _kf_dist(centre[s, p.src_cam], mean[s, p.src_cam], centre[j, c], mean[j, c], p.mean_diff_fraction)
+        broken = ~np.isfinite(d) | (d > 1e10)
+    else:
+        j = np.flatnonzero(present & (slot != p.src_slot) & (slot >= 0))
+        c = np.zeros(len(j), dtype=np.int64)
+        pd = _kf_dist(centre[s][None, :, None, :], mean[s][None, :, None, :], centre[j][:, None, :, :], mean[j][:, None, :, :], p.mean_diff_fraction)   # (n, c1, c2)
+        pair = act[s][None, :, None] & act[j][:, None, :]
+        broken = (pair & (~np.isfinite(pd) | (pd > 1e10))).reshape(len(j), C * C).any(axis=1)
+        d = np.where(pair & ~np.isnan(pd), pd, DBL_MAX).reshape(len(j), C * C).min(axis=1)
+    res = dict(status=0, count=0, n_candidates=len(j))
+    if broken.any():
+        res["status"] = 3
+        return res, np.zeros(0, dtype=NEIGH_ITEM_DTYPE)
+    ok = d <= p.max_dist
+    if p.order == NB_FURTHEST:
+        ok &= d > 0.0
+    k = np.flatnonzero(ok)
+    k = k[np.lexsort((c[k], j[k], d[k] if p.order == NB_NEAREST else -d[k]))][:p.n_max]
+    items = np.zeros(len(k), dtype=NEIGH_ITEM_DTYPE)
+    items["dist"], items["slot"], items["cam"], items["flags"], items["n_meas"] = d[k], slot[j[k]], (c[k] if kf else -1), flags[j[k]], -1
+    if p.want_meas:
+        al = np.asarray(a["ms_alive"]) != 0
+        mm, mc = np.asarray(a["ms_mkf"]), np.asarray(a["ms_cam"])
+        items["n_meas"] = [int((al & (mm == it["slot"]) & ((mc == it["cam"]) if kf else True)).sum()) for it in items]
+    res["count"] = len(k)
+    return res, items
+
+
+def cull_mkf_ref(a, slot=-1, furthest_from=-1, mark_points=True, max_kfs=2, erase=True, mean_diff_fraction=0.5, n_rows=None):
+    """MarkFurthestMultiKeyFrameAsBad (src/MapMakerServerBase.cc:264-318) and what Map::MoveBadMultiKeyFramesToTrash (src/Map.cc:119-187)
+    does to the victim's measurements, over the flat arrays, as the reference's loops read: the victim's keyframes, their measurements, the
+    point rule on the counts on entry.  Returns what cull_mkf_host returns."""
+    mf, pf, pend, alive = _cull_mkf_state(a)
+    Np, M = len(pf), len(alive)
+    n_rows = int(a.get("n_rows", Np)) if n_rows is None else int(n_rows)
+    res = dict(status=0, victim=-1, victim_dist_valid=0, victim_dist=0.0, n_victim_meas=0, n_rows_marked=0, n_by_count=0, n_by_source=0, new_fixed=-1, n_meas_erased=0)
+    victim = int(slot)
+    dist, valid = 0.0, 0
+    if victim == -1:                                                                # FurthestMultiKeyFrame
+        r, it = neighbours_ref(a, dict(kind=NB_MKF, order=NB_FURTHEST, src_slot=furthest_from, mean_diff_fraction=mean_diff_fraction))
+        if r["status"] != 0 or r["count"] == 0:
+            res["status"] = 3 if r["status"] else 1
+            return res, _cull_mkf_merge(a, mf, pf, pend, alive)
+        victim, dist, valid = int(it["slot"][0]), float(it["dist"][0]), 1
+    new_fixed = -1
+    if mf[victim] & MKF_FIXED:                                                      # :313-317
+        r, it = neighbours_ref(a, dict(kind=NB_MKF, order=NB_NEAREST, src_slot=victim, mean_diff_fraction=mean_diff_fraction))
+        if r["status"] != 0:
+            res["status"] = 3
+            return res, _cull_mkf_merge(a, mf, pf, pend, alive)
+        if r["count"]:
+            new_fixed = int(it["slot"][0])
+    mm, mc, mr = (np.asarray(a[k]).astype(np.int64) for k in ("ms_mkf", "ms_cam", "ms_row"))
+    sm, sc = np.asarray(a["src_mkf"]), np.asarray(a["src_cam"])
+    live = (alive != 0) & (mr >= 0) & (mr < n_rows) & (mm >= 0) & (mm < MAX_MKFS)
+    size = np.bincount(mr[live], minlength=max(n_rows, 1))                          # spMeasurementKFs.size() on entry
+    was_bad = (pf & GP_BAD) != 0
+    for i in np.flatnonzero(live & (mm == victim)):
+        res["n_victim_meas"] += 1
+        r = int(mr[i])
+        if not mark_points or r >= Np:
+            continue
+        by_source = sm[r] == victim and sc[r] == mc[i]
+        if (size[r] <= max_kfs and not pf[r] & GP_FIXED) or by_source:              # :281-283
+            pf[r] |= GP_BAD
+    marked = np.flatnonzero(((pf & GP_BAD) != 0) & ~was_bad)
+    pend[marked] = 1
+    src_rows = set(int(mr[i]) for i in np.flatnonzero(live & (mm == victim) & (mr < Np)) if sm[mr[i]] == victim and sc[mr[i]] == mc[i])
+    res["n_rows_marked"] = len(marked)
+    res["n_by_source"] = sum(1 for r in marked if int(r) in src_rows)
+    res["n_by_count"] = len(marked) - res["n_by_source"]
+    mf[victim] |= MKF_BAD
+    if new_fixed >= 0:
+        mf[new_fixed] |= MKF_FIXED
+    if erase:
+        dies = (alive != 0) & (mm == victim)
+        res["n_meas_erased"] = int(dies.sum())
+        alive[dies] = 0
+        mf[victim] &= ~MKF_PRESENT
+    res.update(victim=victim, victim_dist_valid=valid, victim_dist=dist, new_fixed=new_fixed)
+    return res, _cull_mkf_merge(a, mf, pf, pend, alive)
+
+
 # ---- the numpy restatement, from the reference -----------------------------------------------------------------------------------------------
 def mkf_distances(a, newest, mean_diff_fraction):
     """MultiKeyFrame::Distance(newest, k) for every slot k (KeyFrame.cc:903-927 over KeyFrame::Distance, :715-747): (P,) distances (DBL_MAX
@@ -908,6 +1173,90 @@ class MapGraph:
         a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
         _chk(self._L.mcp_map_cull_last_timing(self._h, ctypes.addressof(a), ctypes.addressof(b)), "map_cull_last_timing")
         return a.value, b.value
+
+    # ---- closest-keyframe queries and the removal of an MKF (mcp_map_neighbours, mcp_map_mkf_cull) ----
+    def neighbours(self, params=None, raw=False, **kw):
+        """mcp_map_neighbours: (dict of status / count / n_candidates, the winners as a NEIGH_ITEM_DTYPE array), or with raw the NeighResult
+        itself.  params: a NeighParams, or neigh_params' keywords."""
+        p = _as_neigh_params(kw if params is None else params)
+        res = NeighResult()
+        _chk(self._L.mcp_map_neighbours(self._h, ctypes.addressof(p), ctypes.addressof(res)), "map_neighbours")
+        return res if raw else (res.as_dict(), res.items())
+
+    def neighbours_last_timing(self):
+        """Device time of the last neighbours() submission in ms; -1 before the first."""
+        ms = ctypes.c_double(0.0)
+        _chk(self._L.mcp_map_neighbours_last_timing(self._h, ctypes.addressof(ms)), "map_neighbours_last_timing")
+        return ms.value
+
+    def n_closest_multi_keyframes(self, n, src_slot=-1, ext=None, want_meas=False, mean_diff_fraction=0.5):
+        """MapMakerBase::NClosestMultiKeyFrames: the items, nearest first (bad MKFs included, with their flags)."""
+        return self.neighbours(kind=NB_MKF, order=NB_NEAREST, src_slot=src_slot, ext=ext, n_max=n, want_meas=want_meas, mean_diff_fraction=mean_diff_fraction)[1]
+
+    def closest_multi_keyframe(self, src_slot=-1, ext=None, **kw):
+        """MapMakerBase::ClosestMultiKeyFrame: the item, or None where the reference asserts."""
+        it = self.n_closest_multi_keyframes(1, src_slot, ext, **kw)
+        return it[0] if len(it) else None
+
+    def furthest_multi_keyframe(self, src_slot=-1, ext=None, mean_diff_fraction=0.5):
+        """MapMakerBase::FurthestMultiKeyFrame: the item, or None (no other MKF at a distance > 0)."""
+        it = self.neighbours(kind=NB_MKF, order=NB_FURTHEST, src_slot=src_slot, ext=ext, n_max=1, mean_diff_fraction=mean_diff_fraction)[1]
+        return it[0] if len(it) else None
+
+    def n_closest_keyframes(self, n, src_slot, src_cam, region=NB_ALL, same_cam=False, ext=None, max_dist=np.inf, want_meas=False, mean_diff_fraction=0.5):
+        """MapMakerBase::NClosestKeyFrames: the items, nearest first."""
+        return self.neighbours(kind=NB_KF, order=NB_NEAREST, src_slot=src_slot, src_cam=src_cam, region=region, same_cam=same_cam, ext=ext, n_max=n, max_dist=max_dist,
+                               want_meas=want_meas, mean_diff_fraction=mean_diff_fraction)[1]
+
+    def closest_keyframes_within_dist(self, src_slot, src_cam, max_dist, n_max=NB_MAX, region=NB_ALL, **kw):
+        """MapMakerBase::ClosestKeyFramesWithinDist: at most n_max keyframes with distance <= max_dist, nearest first."""
+        return self.n_closest_keyframes(n_max, src_slot, src_cam, region=region, max_dist=max_dist, **kw)
+
+    def closest_keyframe(self, src_slot, src_cam, region=NB_ALL, same_cam=False, **kw):
+        """MapMakerBase::ClosestKeyFrame: the item, or None (the reference returns NULL)."""
+        it = self.n_closest_keyframes(1, src_slot, src_cam, region=region, same_cam=same_cam, **kw)
+        return it[0] if len(it) else None
+
+    def need_new_multi_keyframe(self, ext, total_depth_mean, n_present, max_scaled_dist=0.1, mean_diff_fraction=0.5):
+        """MapMakerClientBase::NeedNewMultiKeyFrame(mkf) without the queue (src/MapMakerClientBase.cc:125-147): ext is the tracker's MKF,
+        total_depth_mean its mdTotalDepthMean, n_present mlpMultiKeyFrames.size(), max_scaled_dist sdMaxScaledMKFDist."""
+        it = self.closest_multi_keyframe(ext=ext, mean_diff_fraction=mean_diff_fraction)
+        if it is None:
+            raise ValueError("need_new_multi_keyframe: the map holds no MKF")
+        dist = float(it["dist"]) * (1.0 / total_depth_mean)
+        size = 1 if n_present == 2 else n_present
+        return dist > max_scaled_dist * (1.0 - (1.0 / (0.5 + size)))
+
+    def need_new_multi_keyframe_by_meas(self, ext, n_meas, mean_diff_fraction=0.5):
+        """MapMakerClientBase::NeedNewMultiKeyFrame(mkf, nNumMeas) without the queue (:163-177): fewer measurements than 70% of the mean of
+        the three closest MKFs'."""
+        it = self.n_closest_multi_keyframes(3, ext=ext, want_meas=True, mean_diff_fraction=mean_diff_fraction)
+        if not len(it):
+            raise ValueError("need_new_multi_keyframe_by_meas: the map holds no MKF")
+        return n_meas < 0.7 * (float(int(it["n_meas"].sum())) / len(it))
+
+    def is_distance_to_nearest_mkf_excessive(self, ext, total_depth_mean_of, max_scaled_dist=0.1, mean_diff_fraction=0.5):
+        """MapMakerClientBase::IsDistanceToNearestMultiKeyFrameExcessive (:203-211).  total_depth_mean_of: slot -> mdTotalDepthMean of that MKF
+        (a callable, or something indexed by slot): the graph holds the keyframes' means, not the MKF's."""
+        it = self.closest_multi_keyframe(ext=ext, mean_diff_fraction=mean_diff_fraction)
+        if it is None:
+            raise ValueError("is_distance_to_nearest_mkf_excessive: the map holds no MKF")
+        tdm = total_depth_mean_of(int(it["slot"])) if callable(total_depth_mean_of) else total_depth_mean_of[int(it["slot"])]
+        return float(it["dist"]) * (1.0 / tdm) > max_scaled_dist * 3
+
+    def cull_mkf(self, slot=-1, furthest_from=-1, mark_points=True, max_kfs=2, erase=True, mean_diff_fraction=0.5):
+        """mcp_map_mkf_cull: MarkFurthestMultiKeyFrameAsBad (slot == -1: the victim is the furthest MKF from furthest_from) and the removal of the
+        victim from the store and the map, in one submission.  Returns the dict of mcp_mkf_cull_result.  The rows it marks are reported by the
+        next cull_sweep."""
+        prm, res = MkfCullParams(int(slot), int(furthest_from), int(bool(mark_points)), int(max_kfs), int(bool(erase)), float(mean_diff_fraction)), MkfCullResult()
+        _chk(self._L.mcp_map_mkf_cull(self._h, ctypes.addressof(prm), ctypes.addressof(res)), "map_mkf_cull")
+        return res.as_dict()
+
+    def cull_mkf_last_timing(self):
+        """Device time of the last cull_mkf() submission in ms; -1 before the first."""
+        ms = ctypes.c_double(0.0)
+        _chk(self._L.mcp_map_mkf_cull_last_timing(self._h, ctypes.addressof(ms)), "map_mkf_cull_last_timing")
+        return ms.value
 
     def select_raw(self, params, copy=True):
         """mcp_map_bundle_select: (SelectResult, mkfs, points, meas)."""

@@ -14,7 +14,7 @@
 // maker holds the same mcp_map_points* as mpMapTable), and in class MapMakerServerBase: mcp_meas_parcel* mpReFindParcel
 // (mcp_meas_parcel_create(mpMapTable) where the table is handed over; mcp_meas_parcel_destroy before the table goes).
 // At the end of this file: HandleOutliers (:1198-1238) and MapMaker::HandleBadEntities (src/MapMaker.cc:477-492) over mcp_map_cull_outliers /
-// mcp_map_cull_sweep -- delete those two bodies too.
+// mcp_map_cull_sweep, and MarkFurthestMultiKeyFrameAsBad (:264-318) over mcp_map_mkf_cull -- delete those three bodies too.
 #include <mcptam/MapMakerServerBase.h>
 #include <mcptam/MapMaker.h>
 #include <mcptam/BundleAdjusterBase.h>
@@ -327,8 +327,11 @@ void MapMakerServerBase::ReFindFromFailureQueue()
 
 // ---- AddStereoMapPoints (:452-496) with one mcp_stereo_points call per source keyframe and level: ThinCandidates before every target, the arc,
 // both PatchFinder loops, the selection, ReprojectPoint and the nLimit counter run on the device in one submission (include/mcp_img.h).  The
-// host keeps what needs the map: ClosestKeyFramesWithinDist, the mbBad / CrossCamera / sbOnlyFirstCameraGeneratesPoints skips (a skipped target
-// neither thins nor creates), and building the MapPoints and Measurements from the records, in the reference's creation order.
+// targets come from the map graph: mcp_map_neighbours (keyframe kind, n_max = snMaxTriangulationKFs, max_dist as :463-470) is
+// ClosestKeyFramesWithinDist over the graph's poses, active bytes and depth means -- at most n_max items come back, each with its MKF's flags.
+// The host keeps the mbBad / CrossCamera / sbOnlyFirstCameraGeneratesPoints skips (a skipped target neither thins nor creates; a bad MKF is a
+// candidate of the query, as in the reference's walk, and is skipped here after the list is cut), and building the MapPoints and Measurements
+// from the records, in the reference's creation order.
 void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, int nLimit, double dDistThresh, KeyFrameRegion region)
 {
   static gvar3<int> gvnCrossCamera("CrossCamera", 1, HIDDEN|SILENT);
@@ -339,15 +342,37 @@ void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, i
     KeyFrame& kfSrc = *(it->second);
     Level& level = kfSrc.maLevels[nLevel];
     const double dDistThreshUsed = dDistThresh < 0 ? 1000 : dDistThresh;
-    std::vector<KeyFrame*> vpAll = ClosestKeyFramesWithinDist(kfSrc, dDistThreshUsed, MapMakerServerBase::snMaxTriangulationKFs, region);
-    std::vector<KeyFrame*> vpTargets;
-    for(unsigned j = 0; j < vpAll.size(); ++j)
+    mcp_neigh_params nbParams;
+    std::memset(&nbParams, 0, sizeof nbParams);
+    nbParams.kind = MCP_NB_KF;
+    nbParams.region = region == KF_ONLY_SELF ? MCP_NB_ONLY_SELF : (region == KF_ONLY_OTHER ? MCP_NB_ONLY_OTHER : MCP_NB_ALL);
+    nbParams.order = MCP_NB_NEAREST;
+    nbParams.src_slot = mkfSrc.mnGraphSlot;      // (the source MKF entered the map, and the graph, before its points are made)
+    nbParams.src_cam = kfSrc.mnCamIndex;
+    nbParams.n_max = std::min((int)MapMakerServerBase::snMaxTriangulationKFs, MCP_NB_MAX);
+    nbParams.max_dist = dDistThreshUsed;
+    nbParams.mean_diff_fraction = KeyFrame::sdDistanceMeanDiffFraction;
+    mcp_neigh_result nbRes;
+    if(mcp_map_neighbours(mMap.mpMapGraph, &nbParams, &nbRes) != 0)
     {
-      if(vpAll[j]->mpParent->mbBad)
+      ROS_FATAL_STREAM("mcp_map_neighbours: " << mcp_last_error());
+      ROS_BREAK();
+    }
+    if(nbRes.status == 3)     // KeyFrame::Distance's ROS_BREAK, src/KeyFrame.cc:734-744
+    {
+      ROS_FATAL("AddStereoMapPoints: a keyframe distance is not finite or larger than 1e10");
+      ROS_BREAK();
+    }
+    std::vector<KeyFrame*> vpTargets;
+    for(int j = 0; j < nbRes.count; ++j)
+    {
+      const mcp_neigh_item& item = nbRes.item[j];
+      if(item.flags & MCP_MKF_BAD)     // vpAll[j]->mpParent->mbBad
         continue;
-      if(!*gvnCrossCamera && kfSrc.mCamName != vpAll[j]->mCamName)     // AddPointEpipolar's first check: the target creates nothing
+      if(!*gvnCrossCamera && kfSrc.mnCamIndex != item.cam)     // AddPointEpipolar's first check: the target creates nothing
         continue;
-      vpTargets.push_back(vpAll[j]);
+      MultiKeyFrame* pMKF = mBundleAdjuster.mvpSlotMKF[item.slot];
+      vpTargets.push_back(pMKF->mmpKeyFrames[mBundleAdjuster.mvCamNames[item.cam]]);
     }
     TaylorCamera& cameraSrc = mmCameraModels[kfSrc.mCamName];
     const mcp_camera camSrc = mcptam_hip::CameraExport::Make(cameraSrc);
@@ -565,4 +590,39 @@ void MapMaker::HandleBadEntities()
 
   EraseBadEntitiesFromQueues();
   mMap.EmptyTrash();
+}
+
+// ---- MarkFurthestMultiKeyFrameAsBad (:264-318) in ONE call ------------------------------------------------------------------------------------------
+// FurthestMultiKeyFrame, the walk over every measurement of the victim's keyframes, the point rule (:281-283) and ClosestMultiKeyFrame for the
+// fixed hand-over all read what the graph holds: mcp_map_mkf_cull picks the victim, marks it MCP_MKF_BAD, marks the rows (they get the pending
+// mark: the sweep of HandleBadEntities reports them, and that body sets mbBad on the MapPoints), moves MCP_MKF_FIXED and, with erase, takes the
+// victim's entries and its slot out of the graph -- what HandleBadEntities' mcp_map_graph_erase_mkf did for it.  The host repeats the two flags
+// on its objects; Map::MoveBadMultiKeyFramesToTrash then trashes the MKF as before.
+void MapMakerServerBase::MarkFurthestMultiKeyFrameAsBad(MultiKeyFrame& mkf)
+{
+  mcp_mkf_cull_params params;
+  params.slot = -1;
+  params.furthest_from = mkf.mnGraphSlot;
+  params.mark_points = 1;
+  params.max_kfs = 2;
+  params.erase = 1;
+  params.mean_diff_fraction = KeyFrame::sdDistanceMeanDiffFraction;
+  mcp_mkf_cull_result res;
+  if(mcp_map_mkf_cull(mMap.mpMapGraph, &params, &res) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_mkf_cull: " << mcp_last_error());
+    ROS_BREAK();
+  }
+  if(res.status != 0)     // 1: FurthestMultiKeyFrame's ROS_ASSERT (no other MKF at a distance > 0); 3: KeyFrame::Distance's ROS_BREAK
+  {
+    ROS_FATAL_STREAM("MarkFurthestMultiKeyFrameAsBad: no victim, status " << res.status);
+    ROS_BREAK();
+  }
+  MultiKeyFrame* pFurthestMKF = mBundleAdjuster.mvpSlotMKF[res.victim];
+  pFurthestMKF->mbBad = true;
+  pFurthestMKF->mnGraphSlot = -1;     // (erased: HandleBadEntities has nothing left to erase for it)
+  if(res.new_fixed >= 0)
+    mBundleAdjuster.mvpSlotMKF[res.new_fixed]->mbFixed = true;
+  ROS_INFO_STREAM("MarkFurthestMultiKeyFrameAsBad: slot " << res.victim << " at distance " << res.victim_dist << ", " << res.n_victim_meas << " measurements, "
+                  << res.n_rows_marked << " points go bad (" << res.n_by_count << " by count, " << res.n_by_source << " by source)");
 }

@@ -477,8 +477,9 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
 // The bookkeeping TrackMap leaves behind comes from the same submission (mcp_track_map_record with want_items = 0): the level counters and
 // the per-camera quality arithmetic, the inlier / outlier marks (applied to the table's count column on the device; the host repeats them
 // on the MapPoints from the 8-byte notes, so that the next UploadMapTable sends the same numbers up again), the found measurements (32
-// bytes each) and RefreshSceneDepth (:1085, :1180-1228) of every camera.  No 320-byte item crosses.  The host keeps mdTotalDepthMean,
-// IsDistanceToNearestMultiKeyFrameExcessive and mnLostFrames, and AssessOverallTrackingQuality's heuristics on top of rec.quality[].
+// bytes each) and RefreshSceneDepth (:1085, :1180-1228) of every camera.  No 320-byte item crosses.  The host keeps mdTotalDepthMean
+// and mnLostFrames, and AssessOverallTrackingQuality's heuristics on top of rec.quality[]; IsDistanceToNearestMultiKeyFrameExcessive is a
+// query of the map graph (IsDistanceToNearestMultiKeyFrameExcessiveOnDevice below).
 // Needs in class Tracker:   mcp_track_record mTrackRecord;   (the last frame's record, read by AssessTrackingQuality below)
 // Deviations: mv3Cam of the tracked points, and with it the depths of RefreshSceneDepth, are the final pose's (the reference leaves the
 // value of the last ProjectAndDerivs).  mv2Image / mm2CamDerivs of the TrackerData keep FindPVS's values of the prior pose: nothing after
@@ -733,6 +734,46 @@ void Tracker::RecordMeasurements()
     ROS_FATAL_STREAM("Tracker::RecordMeasurements: "<<mcp_last_error());
     ros::shutdown();
   }
+}
+
+// ---- IsDistanceToNearestMultiKeyFrameExcessive (src/MapMakerClientBase.cc:203-211) over the map graph ------------------------------------
+// Replaces the call mMapMaker.IsDistanceToNearestMultiKeyFrameExcessive(*mpCurrentMKF) in AssessOverallTrackingQuality.  The current MKF is
+// not in the map: it goes with the call as the external MKF of mcp_map_neighbours (pose, mbActive and mdSceneDepthMean per camera index), and
+// ClosestMultiKeyFrame over mlpMultiKeyFrames becomes one item.  The closest MKF's mdTotalDepthMean is the host's (the graph holds the
+// keyframes' means).  Needs in class Tracker:   bool IsDistanceToNearestMultiKeyFrameExcessiveOnDevice();
+// NeedNewMultiKeyFrame's map side is the same query (the queue side, ClosestMultiKeyFrameInQueue, stays with MapMakerClientBase).
+bool Tracker::IsDistanceToNearestMultiKeyFrameExcessiveOnDevice()
+{
+  mcp_neigh_params params;
+  std::memset(&params, 0, sizeof params);
+  params.kind = MCP_NB_MKF;
+  params.order = MCP_NB_NEAREST;
+  params.src_slot = -1;
+  params.n_max = 1;
+  params.max_dist = std::numeric_limits<double>::infinity();
+  params.mean_diff_fraction = KeyFrame::sdDistanceMeanDiffFraction;
+  ToArray12(mpCurrentMKF->mse3BaseFromWorld, params.ext_base_from_world);
+  for(unsigned c = 0; c < mvCurrCamNames.size(); ++c)
+  {
+    KeyFramePtrMap::iterator kf_it = mpCurrentMKF->mmpKeyFrames.find(mvCurrCamNames[c]);
+    const bool bActive = kf_it != mpCurrentMKF->mmpKeyFrames.end() && kf_it->second->mbActive;
+    params.ext_active[c] = bActive ? 1 : 0;
+    params.ext_depth_mean[c] = bActive ? kf_it->second->mdSceneDepthMean : 0.0;
+  }
+  mcp_neigh_result res;
+  if(mcp_map_neighbours(mMap.mpMapGraph, &params, &res) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_neighbours: " << mcp_last_error());
+    ROS_BREAK();
+  }
+  if(res.status == 3 || res.count == 0)     // KeyFrame::Distance's ROS_BREAK; ClosestMultiKeyFrame's ROS_ASSERT on an empty map
+  {
+    ROS_FATAL_STREAM("IsDistanceToNearestMultiKeyFrameExcessive: no closest MKF, status " << res.status);
+    ROS_BREAK();
+  }
+  MultiKeyFrame* pClosestMKF = mMapMaker.GraphSlotMKF(res.item[0].slot);     // (the bundle adjuster's mvpSlotMKF, behind an accessor)
+  const double dDist = res.item[0].dist * (1.0 / pClosestMKF->mdTotalDepthMean);     // scale by depth
+  return dDist > MapMakerClientBase::sdMaxScaledMKFDist * 3;
 }
 
 // ---- TrackFrame's tracking branch in one submission (include/mcp_img.h, mcp_track_frame_motion) ------------------------------------------
