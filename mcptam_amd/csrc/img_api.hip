@@ -2616,85 +2616,155 @@ const mcp_refind_meas* mcp_map_refind_view(const mcp_map_points* m, int* count) 
 }  // extern "C"
 
 // ---- the map graph (include/mcp_img.h mcp_map_graph_*, mcp_map_bundle_select; map_graph_kernels.h) ---------------------------------------
-struct mcp_map_graph {
-  mcp_map_points* m = nullptr;                        // the table: its device, its stream, its rows (it must outlive the graph)
-  MgRig rig;
-  Buf<MgMkf> slots; std::vector<int> h_flags;         // MCP_MAP_MAX_MKFS slots; the host's copy of their flags (what add_meas and select check)
-  Buf<MgPoint> pts; int prow = 0;                     // point columns: prow rows written or filled so far
-  Buf<MgMeas> store, store_alt; int n_store = 0, n_live = 0;
-  Buf<MgCtl> ctl; PinBuf<MgCtl> h_ctl;
-  // uploads: packed into pinned memory, copied on the table's stream; `staged` marks when the staging may be refilled
-  PinBuf<char> up_in; Buf<char> up_dev; hipEvent_t staged = nullptr; bool stage_busy = false;
-  std::vector<int> sorted_ids; std::vector<unsigned long long> keys;
-  // the select: marks (mkf_in | good | seen), verdicts, bundle indices, per-workgroup counts; the pinned views and result
-  Buf<int> marks, bidx, blk, mkf_bidx; Buf<uint8_t> adjust, sel, mkeep;
-  PinBuf<mcp_bundle_mkf> v_mkfs; PinBuf<mcp_bundle_point> v_points; PinBuf<mcp_bundle_meas> v_meas; PinBuf<mcp_bundle_select_result> h_res;
-  int n_mkfs = 0, n_points = 0, n_meas = 0;           // what the views hold
-  hipEvent_t t0 = nullptr, t1 = nullptr; bool timed = false;      // mcp_map_bundle_select_last_timing: around the last select's submission
-  // the keyframe lists (map_graph_lists.h): the call's slots (pinned | device), the (key, row) column, the count table, the lists, the
-  // keyframes' poses and the pinned results of mcp_graph_refresh_depth / mcp_graph_debug_kf_lists
-  PinBuf<char> l_in; Buf<char> l_dev; Buf<int2> l_key_row; Buf<int> l_table, l_start, l_rows; Buf<double> l_w, l_cfw; PinBuf<char> l_out;
-  // the commit of a measurement parcel (map_graph_parcel.h): verdict bytes, per-workgroup counts, the result block (MgpCtl | per-lane counts: device, pinned)
-  Buf<uint8_t> pc_vd; Buf<int> pc_blk; Buf<char> pc_dev; PinBuf<char> pc_out;
-  // outliers and bad points (map_graph_cull.h): the store index of each key, verdict and report bytes, the counters (device, pinned with the
-  // verdicts behind them), the pinned report of the last sweep; the events of mcp_map_cull_last_timing ([0], [1]: outliers; [2], [3]: sweep).
-  // The good counts go through `marks`, the per-workgroup counts through `blk`, as a select's do.
-  Buf<int> c_match; Buf<uint8_t> c_vd, c_rep; Buf<MgcCtl> c_ctl; PinBuf<char> c_out; PinBuf<int> c_rows; int c_nrows = 0;
-  hipEvent_t c_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool c_timed[2] = {false, false};
-  std::vector<std::pair<unsigned long long, int>> c_keys; std::vector<MgcRun> c_runs;
-  // the neighbour queries and the removal of an MKF (map_graph_neigh.h): the host's copy of the active bytes (what a query's refusals check),
-  // the scratch of distances and candidate bytes, the two queries' hand-offs and results (device), the external MKF, the removal's block,
-  // the pinned results; the events of mcp_map_neighbours_last_timing / mcp_map_mkf_cull_last_timing.  The live counts of a removal go through `marks`.
-  std::vector<uint8_t> h_act;
-  Buf<double> n_dist; Buf<uint8_t> n_cand; Buf<MgnCtl> n_ctl; Buf<mcp_neigh_result> n_res; Buf<MgMkf> n_ext; Buf<MgnCull> n_cc; PinBuf<char> n_out;
-  hipEvent_t n_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool n_timed[2] = {false, false};      // [0], [1]: a query; [2], [3]: a removal
-  ~mcp_map_graph() {
-    if (m && m->st) (void)hipStreamSynchronize(m->st);
-    for (hipEvent_t e : {staged, t0, t1, c_ev[0], c_ev[1], c_ev[2], c_ev[3], n_ev[0], n_ev[1], n_ev[2], n_ev[3]}) if (e) (void)hipEventDestroy(e);
-  }
-  int neigh_ready() {
-    for (hipEvent_t& e : n_ev) if (!e) ICK(hipEventCreate(&e));
-    const size_t n_idx = (size_t)(MCP_MAP_MAX_MKFS + 1)*MCP_MAX_FRAME_CAMS;
-    return (n_dist.alloc(n_idx) || n_cand.alloc(n_idx) || n_ctl.alloc(2) || n_res.alloc(2) || n_ext.alloc(1) || n_cc.alloc(1) ||
-            n_out.alloc(2*sizeof(mcp_neigh_result) + sizeof(MgnCull))) ? -1 : 0;
-  }
-  int cull_ready() { for (hipEvent_t& e : c_ev) if (!e) ICK(hipEventCreate(&e)); return c_ctl.alloc(1); }
-  int wait_staging() { if (stage_busy) { ICK(hipEventSynchronize(staged)); stage_busy = false; } return 0; }
-  int sync() { ICK(hipStreamSynchronize(m->st)); stage_busy = false; m->stage_busy = false; m->parcel_reads = false; return 0; }
-  // pinned + device staging of `bytes`, free to fill
-  int stage(size_t bytes) {
-    if (wait_staging()) return -1;
-    if (up_in.alloc(bytes)) return -1;
-    if (bytes > up_dev.n) { if (sync()) return -1; }       // the device staging is reallocated below
-    return up_dev.alloc(bytes);
-  }
-  int staged_now() { ICK(hipEventRecord(staged, m->st)); stage_busy = true; return 0; }
-  // the point columns cover `rows` rows: the ones that appear read as never written
-  int grow_points(int rows) {
-    if (rows <= prow) return 0;
-    if ((size_t)rows > pts.n || !pts.p) {
-      Buf<MgPoint> fresh;
-      if (fresh.alloc(std::max<size_t>({(size_t)rows, 2*pts.n, (size_t)1024}))) return -1;
-      if (prow) { ICK(hipMemcpyAsync(fresh.p, pts.p, sizeof(MgPoint)*(size_t)prow, hipMemcpyDeviceToDevice, m->st)); if (sync()) return -1; }
-      pts.swap(fresh);
-    }
-    hipLaunchKernelGGL(k_mg_points_fill, dim3((unsigned)((rows - prow + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, m->st, pts.p, prow, rows - prow);
-    ICK(hipGetLastError());
-    prow = rows;
-    return 0;
-  }
-  int grow_store(size_t need) {
-    if (need <= store.n && store.p) return 0;
-    Buf<MgMeas> fresh;
-    if (fresh.alloc(std::max<size_t>({need, 2*store.n, (size_t)1024}))) return -1;
-    if (n_store) { ICK(hipMemcpyAsync(fresh.p, store.p, sizeof(MgMeas)*(size_t)n_store, hipMemcpyDeviceToDevice, m->st)); }
-    if (store.p && sync()) return -1;                  // the old block is freed below, with nothing in flight on it
-    store.swap(fresh);
+// "A block that grows is replaced with nothing in flight on the old one."  Buf::alloc and PinBuf::alloc free the old block at once, so a call
+// constructs one of these before its first enqueue and passes every block it needs through it.  The first block that has to grow waits for
+// the table's stream (the owner's sync(): once per call, and only then); after that it and the later ones are allocated.  Whatever the call
+// enqueues between two growths it reports with enqueued(), and the next growth waits again.
+template <class Owner> struct Grow {
+  Owner* o; bool idle = false;
+  explicit Grow(Owner* owner) : o(owner) {}
+  int wait() { if (!idle) { if (o->sync()) return -1; idle = true; } return 0; }
+  void enqueued() { idle = false; }
+  template <class B> int grow(B& b, size_t count) { return std::max<size_t>(count, 1) <= b.n ? 0 : (wait() || b.alloc(count)) ? -1 : 0; }
+  // room for `need` elements by the doubling rule of the point columns, the store and a parcel's entries; the first `keep` are copied over
+  template <class T> int regrow(Buf<T>& b, size_t need, size_t keep) {
+    if (need <= b.n && b.p) return 0;
+    const size_t bigger = std::max<size_t>({need, 2*b.n, (size_t)1024});
+    if (!keep) return (b.p && wait()) ? -1 : b.alloc(bigger);
+    Buf<T> fresh;
+    if (fresh.alloc(bigger)) return -1;
+    ICK(hipMemcpyAsync(fresh.p, b.p, sizeof(T)*keep, hipMemcpyDeviceToDevice, o->m->st));
+    enqueued();
+    if (wait()) return -1;                             // the old block is freed below, with nothing in flight on it
+    b.swap(fresh);
     return 0;
   }
 };
 
-static int mg_distinct(std::vector<int>& sorted, const int* ids, int count, const std::string& who, const char* what) {
+// a pair of events around a call's submission, created on first use; timed: the last such call ran to its wait
+struct MgTimer {
+  hipEvent_t ev[2] = {nullptr, nullptr}; bool timed = false;
+  ~MgTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  int begin(hipStream_t st) { timed = false; for (hipEvent_t& e : ev) if (!e) ICK(hipEventCreate(&e)); ICK(hipEventRecord(ev[0], st)); return 0; }
+  int end(hipStream_t st) { ICK(hipEventRecord(ev[1], st)); return 0; }
+  int ms(double* out) const {                          // -1.0 when the last call did not run
+    *out = -1.0;
+    if (!timed) return 0;
+    float f = 0.f;
+    ICK(hipEventElapsedTime(&f, ev[0], ev[1]));
+    *out = f;
+    return 0;
+  }
+};
+
+// every launch of the map graph but the list passes' (MGL_BLOCK: a tile of the list algorithm) runs workgroups of MG_BLOCK threads
+static_assert(MGP_BLOCK == MG_BLOCK && MGC_BLOCK == MG_BLOCK && MGN_BLOCK == MG_BLOCK, "the map-graph kernels share one workgroup size");
+static int mg_grid(long long n, int block = MG_BLOCK) { return (int)((n + block - 1)/block); }      // (empty for n == 0: the launch is skipped or n is positive)
+static int mg_grid1(long long n) { return std::max(1, mg_grid(n)); }
+
+struct mcp_map_graph {
+  mcp_map_points* m = nullptr;                        // the table: its device, its stream, its rows (it must outlive the graph)
+  MgRig rig;
+  Buf<MgMkf> slots;                                   // MCP_MAP_MAX_MKFS slots
+  // the host's copy of their flags and active bytes (what add_meas, select and a query's refusals check)
+  struct Mirror {
+    std::vector<int> flags = std::vector<int>(MCP_MAP_MAX_MKFS, 0);
+    std::vector<uint8_t> act = std::vector<uint8_t>((size_t)MCP_MAP_MAX_MKFS*MCP_MAX_FRAME_CAMS, 0);
+    bool present(int k) const { return k >= 0 && k < MCP_MAP_MAX_MKFS && (flags[k] & MCP_MKF_PRESENT); }
+    int n_present() const { int n = 0; for (int f : flags) n += (f & MCP_MKF_PRESENT) ? 1 : 0; return n; }
+    int top_present() const { int k = MCP_MAP_MAX_MKFS - 1; while (k >= 0 && !(flags[k] & MCP_MKF_PRESENT)) --k; return k; }      // -1: none
+    int flags_of(int k) const { return flags[k]; }
+    const uint8_t* active(int k) const { return &act[(size_t)k*MCP_MAX_FRAME_CAMS]; }
+    void set(int k, int f, const uint8_t* a = nullptr) { flags[k] = f; if (a) std::memcpy(&act[(size_t)k*MCP_MAX_FRAME_CAMS], a, MCP_MAX_FRAME_CAMS); }      // (a null: the active bytes stay)
+  } mirror;
+  Buf<MgPoint> pts; int prow = 0;                     // point columns: prow rows written or filled so far
+  Buf<MgMeas> store, store_alt; int n_store = 0, n_live = 0;
+  Buf<MgCtl> ctl; PinBuf<MgCtl> h_ctl;
+  // uploads: packed into pinned memory, copied on the table's stream; `done` marks when the staging may be refilled
+  struct Stage { PinBuf<char> in; Buf<char> dev; hipEvent_t done = nullptr; bool busy = false; } up;
+  std::vector<int> sorted_ids; std::vector<unsigned long long> keys;
+  // scratch every call family sizes for itself: marks (a select's mkf_in | good | seen; good counts; a removal's live | by_src) and the
+  // per-workgroup counts
+  Buf<int> marks, blk;
+  // the select: verdicts, bundle indices; the pinned views and result, what the views hold; mcp_map_bundle_select_last_timing: around the
+  // last select's submission
+  struct Sel {
+    Buf<int> bidx, mkf_bidx; Buf<uint8_t> adjust, rows, mkeep;
+    PinBuf<mcp_bundle_mkf> v_mkfs; PinBuf<mcp_bundle_point> v_points; PinBuf<mcp_bundle_meas> v_meas; PinBuf<mcp_bundle_select_result> h_res;
+    int n_mkfs = 0, n_points = 0, n_meas = 0;
+    MgTimer t;
+  } sel;
+  // the keyframe lists (map_graph_lists.h): the call's slots (pinned | device), the (key, row) column, the count table, the lists, the
+  // keyframes' poses and the pinned results of mcp_graph_refresh_depth / mcp_graph_debug_kf_lists
+  struct Lists { PinBuf<char> in; Buf<char> dev; Buf<int2> key_row; Buf<int> table, start, rows; Buf<double> w, cfw; PinBuf<char> out; } lists;
+  // the commit of a measurement parcel (map_graph_parcel.h): verdict bytes, per-workgroup counts, the result block (MgpCtl | per-lane counts: device, pinned)
+  struct Commit { Buf<uint8_t> vd; Buf<int> blk; Buf<char> dev; PinBuf<char> out; } commit;
+  // outliers and bad points (map_graph_cull.h): the store index of each key, verdict and report bytes, the counters (device, pinned with the
+  // verdicts behind them), the pinned report of the last sweep; the timers of mcp_map_cull_last_timing.
+  // The good counts go through `marks`, the per-workgroup counts through `blk`, as a select's do.
+  struct Cull {
+    Buf<int> match; Buf<uint8_t> vd, rep; Buf<MgcCtl> ctl; PinBuf<char> out; PinBuf<int> rows; int nrows = 0;
+    MgTimer t_outliers, t_sweep;
+    std::vector<std::pair<unsigned long long, int>> keys; std::vector<MgcRun> runs;
+  } cull;
+  // the neighbour queries and the removal of an MKF (map_graph_neigh.h): the scratch of distances and candidate bytes, the two queries'
+  // hand-offs and results (device), the external MKF, the removal's block, the pinned results; the timers of
+  // mcp_map_neighbours_last_timing / mcp_map_mkf_cull_last_timing.  The live counts of a removal go through `marks`.
+  struct Neigh {
+    Buf<double> dist; Buf<uint8_t> cand; Buf<MgnCtl> ctl; Buf<mcp_neigh_result> res; Buf<MgMkf> ext; Buf<MgnCull> cc; PinBuf<char> out;
+    MgTimer t_query, t_remove;
+  } neigh;
+  using Guard = Grow<mcp_map_graph>;
+  ~mcp_map_graph() {                                  // (the timers destroy their events after this wait)
+    if (m && m->st) (void)hipStreamSynchronize(m->st);
+    if (up.done) (void)hipEventDestroy(up.done);
+  }
+  int wait_staging() { if (up.busy) { ICK(hipEventSynchronize(up.done)); up.busy = false; } return 0; }
+  int sync() { ICK(hipStreamSynchronize(m->st)); up.busy = false; m->stage_busy = false; m->parcel_reads = false; return 0; }
+  // the one wait of a call: past it nothing is in flight, so its Drain has nothing left to do and its timer (if it has one) may be read
+  int one_wait(Drain& drain, MgTimer* t = nullptr) { if (sync()) return -1; drain.armed = false; if (t) t->timed = true; return 0; }
+  // pinned + device staging of `bytes`, free to fill
+  int stage(Guard& G, size_t bytes) { return (wait_staging() || G.grow(up.in, bytes) || G.grow(up.dev, bytes)) ? -1 : 0; }
+  int staged_now() { ICK(hipEventRecord(up.done, m->st)); up.busy = true; return 0; }
+  // the point columns cover `rows` rows: the ones that appear read as never written
+  int grow_points(Guard& G, int rows) {
+    if (rows <= prow) return 0;
+    if (G.regrow(pts, (size_t)rows, (size_t)prow)) return -1;
+    hipLaunchKernelGGL(k_mg_points_fill, dim3(mg_grid(rows - prow)), dim3(MG_BLOCK), 0, m->st, pts.p, prow, rows - prow);
+    ICK(hipGetLastError());
+    G.enqueued();
+    prow = rows;
+    return 0;
+  }
+  int grow_store(Guard& G, size_t need) { return G.regrow(store, need, (size_t)n_store); }
+  // the fixed-size scratch of the queries and the removal
+  int neigh_reserve(Guard& G) {
+    const size_t n_idx = (size_t)(MCP_MAP_MAX_MKFS + 1)*MCP_MAX_FRAME_CAMS;
+    return (G.grow(neigh.dist, n_idx) || G.grow(neigh.cand, n_idx) || G.grow(neigh.ctl, 2) || G.grow(neigh.res, 2) || G.grow(neigh.ext, 1) || G.grow(neigh.cc, 1) ||
+            G.grow(neigh.out, 2*sizeof(mcp_neigh_result) + sizeof(MgnCull))) ? -1 : 0;
+  }
+  // the good count of every row into marks[0 .. R) (zeroed by the caller): k_mg_edges_count without a select's hand-off
+  void good_counts_enqueue(int R) {
+    hipLaunchKernelGGL(k_mg_edges_count, dim3(mg_grid(n_store)), dim3(MG_BLOCK), 0, m->st, (const MgCtl*)nullptr, (const MgMeas*)store.p, n_store, R, (const MgMkf*)slots.p,
+                       (const uint8_t*)nullptr, marks.p, (int*)nullptr);
+  }
+  // `count` elements of a device block in a host vector, waited for
+  template <class T> int read_back(std::vector<T>& out, const T* from, size_t count) {
+    out.resize(count);
+    ICK(hipMemcpyAsync(out.data(), from, sizeof(T)*count, hipMemcpyDeviceToHost, m->st));
+    return sync();
+  }
+};
+
+// what a measurement from host arrays must have, whichever call takes it (at: "<call>: entry <k>"): a row of the table, a pyramid level, a finite position
+static int mg_entry_check(const std::string& at, int row, int R, int level, const double* uv) {
+  if (row < 0 || row >= R) return img_fail(at + " names row " + std::to_string(row) + ", the table has " + std::to_string(R));
+  if (level < 0 || level >= MCP_LEVELS) return img_fail(at + " has level " + std::to_string(level));
+  if (!std::isfinite(uv[0]) || !std::isfinite(uv[1])) return img_fail(at + " has a non-finite position");
+  return 0;
+}
+
+static int mg_distinct(std::vector<int>& sorted,const int* ids, int count, const std::string& who, const char* what) {
   sorted.assign(ids, ids + count);
   std::sort(sorted.begin(), sorted.end());
   for (int k = 1; k < count; ++k) if (sorted[k] == sorted[k - 1]) return img_fail(who + ": " + what + " " + std::to_string(sorted[k]) + " appears twice");
@@ -2720,21 +2790,21 @@ static int mg_mkfs_upload(mcp_map_graph* g, const std::string& who, bool by_ids,
   if (count == 0) return 0;
   ICK(hipSetDevice(g->m->device));
   const size_t o_ids = tm_align(sizeof(MgMkf)*(size_t)count), need = o_ids + sizeof(int)*(size_t)count;
-  if (g->stage(need)) return -1;
-  MgMkf* rec = reinterpret_cast<MgMkf*>(g->up_in.p); int* hid = reinterpret_cast<int*>(g->up_in.p + o_ids);
-  std::memset(g->up_in.p, 0, o_ids);
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, need)) return -1;
+  MgMkf* rec = reinterpret_cast<MgMkf*>(g->up.in.p); int* hid = reinterpret_cast<int*>(g->up.in.p + o_ids);
+  std::memset(g->up.in.p, 0, o_ids);
   for (int k = 0; k < count; ++k) {
     std::memcpy(rec[k].bfw, bfw + 12*(size_t)k, 96);
     rec[k].flags = flags[k];
     for (int c = 0; c < nc; ++c) { const bool a = act[(size_t)k*nc + c] != 0; rec[k].active[c] = a ? 1 : 0; rec[k].depth[c] = a ? dep[(size_t)k*nc + c] : 0.0; }
     hid[k] = by_ids ? ids[k] : first + k;
   }
-  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, need, hipMemcpyHostToDevice, g->m->st));
-  hipLaunchKernelGGL(k_mg_mkfs_scatter, dim3((unsigned)((count + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, g->m->st, g->slots.p, count,
-                     (const int*)(g->up_dev.p + o_ids), (const MgMkf*)g->up_dev.p);
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, need, hipMemcpyHostToDevice, g->m->st));
+  hipLaunchKernelGGL(k_mg_mkfs_scatter, dim3(mg_grid(count)), dim3(MG_BLOCK), 0, g->m->st, g->slots.p, count, (const int*)(g->up.dev.p + o_ids), (const MgMkf*)g->up.dev.p);
   ICK(hipGetLastError());
   if (g->staged_now()) return -1;
-  for (int k = 0; k < count; ++k) { g->h_flags[hid[k]] = flags[k]; std::memcpy(&g->h_act[(size_t)hid[k]*MCP_MAX_FRAME_CAMS], rec[k].active, MCP_MAX_FRAME_CAMS); }
+  for (int k = 0; k < count; ++k) g->mirror.set(hid[k], flags[k], rec[k].active);
   return 0;
 }
 
@@ -2844,14 +2914,11 @@ mcp_map_graph* mcp_map_graph_create(mcp_map_points* m, int ncam, const double* c
   mcp_map_graph* g = new mcp_map_graph(); g->m = m;
   std::memset(&g->rig, 0, sizeof g->rig); g->rig.ncam = ncam;
   for (int c = 0; c < ncam; ++c) mg_se3_of12(cfb + 12*(size_t)c, g->rig.cfb[c]);
-  g->h_flags.assign(MCP_MAP_MAX_MKFS, 0);
-  g->h_act.assign((size_t)MCP_MAP_MAX_MKFS*MCP_MAX_FRAME_CAMS, 0);
-  const bool ok = !g->slots.alloc(MCP_MAP_MAX_MKFS) && !g->ctl.alloc(1) && !g->h_ctl.alloc(1) && !g->h_res.alloc(1) && !g->adjust.alloc(MCP_MAP_MAX_MKFS) &&
-                  !g->mkf_bidx.alloc(MCP_MAP_MAX_MKFS) && !g->v_mkfs.alloc(MCP_MAP_MAX_MKFS) && hipEventCreateWithFlags(&g->staged, hipEventDisableTiming) == hipSuccess &&
-                  hipEventCreate(&g->t0) == hipSuccess && hipEventCreate(&g->t1) == hipSuccess &&
+  const bool ok = !g->slots.alloc(MCP_MAP_MAX_MKFS) && !g->ctl.alloc(1) && !g->h_ctl.alloc(1) && !g->sel.h_res.alloc(1) && !g->sel.adjust.alloc(MCP_MAP_MAX_MKFS) &&
+                  !g->sel.mkf_bidx.alloc(MCP_MAP_MAX_MKFS) && !g->sel.v_mkfs.alloc(MCP_MAP_MAX_MKFS) && hipEventCreateWithFlags(&g->up.done, hipEventDisableTiming) == hipSuccess &&
                   hipMemsetAsync(g->slots.p, 0, sizeof(MgMkf)*(size_t)MCP_MAP_MAX_MKFS, m->st) == hipSuccess && hipMemsetAsync(g->ctl.p, 0, sizeof(MgCtl), m->st) == hipSuccess;
   if (!ok) { mcp_set_error("mcp_map_graph_create: allocation failed"); delete g; return nullptr; }
-  std::memset(g->h_res.p, 0, sizeof(mcp_bundle_select_result));
+  std::memset(g->sel.h_res.p, 0, sizeof(mcp_bundle_select_result));
   return g;
 }
 void mcp_map_graph_destroy(mcp_map_graph* g) { if (g) { (void)hipSetDevice(g->m->device); delete g; } }
@@ -2879,13 +2946,13 @@ int mcp_map_graph_update_points(mcp_map_graph* g, int count, const int* rows, co
   if (count == 0) return 0;
   ICK(hipSetDevice(g->m->device));
   const size_t o_ids = tm_align(sizeof(MgPoint)*(size_t)count), need = o_ids + sizeof(int)*(size_t)count;
-  if (g->stage(need) || g->grow_points(R)) return -1;
-  MgPoint* rec = reinterpret_cast<MgPoint*>(g->up_in.p);
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, need) || g->grow_points(G, R)) return -1;
+  MgPoint* rec = reinterpret_cast<MgPoint*>(g->up.in.p);
   for (int k = 0; k < count; ++k) { rec[k].src_mkf = src_mkf[k] < 0 ? -1 : src_mkf[k]; rec[k].src_cam = src_mkf[k] < 0 ? 0 : src_cam[k]; rec[k].flags = flags[k]; rec[k].pending = 0; }      // (a row that is written starts without a pending mark: mcp_map_cull_*)
-  std::memcpy(g->up_in.p + o_ids, rows, sizeof(int)*(size_t)count);
-  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, need, hipMemcpyHostToDevice, g->m->st));
-  hipLaunchKernelGGL(k_mg_points_scatter, dim3((unsigned)((count + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, g->m->st, g->pts.p, count,
-                     (const int*)(g->up_dev.p + o_ids), (const MgPoint*)g->up_dev.p);
+  std::memcpy(g->up.in.p + o_ids, rows, sizeof(int)*(size_t)count);
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, need, hipMemcpyHostToDevice, g->m->st));
+  hipLaunchKernelGGL(k_mg_points_scatter, dim3(mg_grid(count)), dim3(MG_BLOCK), 0, g->m->st, g->pts.p, count, (const int*)(g->up.dev.p + o_ids), (const MgPoint*)g->up.dev.p);
   ICK(hipGetLastError());
   return g->staged_now();
 }
@@ -2898,22 +2965,21 @@ int mcp_map_graph_add_meas(mcp_map_graph* g, int count, const int* mkf, const in
   const int R = g->m->rows;
   for (int k = 0; k < count; ++k) {
     const std::string at = who + ": entry " + std::to_string(k);
-    if (mkf[k] < 0 || mkf[k] >= MCP_MAP_MAX_MKFS || !(g->h_flags[mkf[k]] & MCP_MKF_PRESENT)) return img_fail(at + " names MKF slot " + std::to_string(mkf[k]) + ", which is not present");
+    if (!g->mirror.present(mkf[k])) return img_fail(at + " names MKF slot " + std::to_string(mkf[k]) + ", which is not present");
     if (cam[k] < 0 || cam[k] >= g->rig.ncam) return img_fail(at + " names camera " + std::to_string(cam[k]));
-    if (row[k] < 0 || row[k] >= R) return img_fail(at + " names row " + std::to_string(row[k]) + ", the table has " + std::to_string(R));
-    if (level[k] < 0 || level[k] >= MCP_LEVELS) return img_fail(at + " has level " + std::to_string(level[k]));
-    if (!std::isfinite(uv[2*(size_t)k]) || !std::isfinite(uv[2*(size_t)k + 1])) return img_fail(at + " has a non-finite position");
+    if (mg_entry_check(at, row[k], R, level[k], uv + 2*(size_t)k)) return -1;
   }
   const int first = g->n_store;
   if (count == 0) return first;
   ICK(hipSetDevice(g->m->device));
-  if (g->stage(sizeof(MgMeas)*(size_t)count) || g->grow_store((size_t)first + count)) return -1;
-  MgMeas* rec = reinterpret_cast<MgMeas*>(g->up_in.p);
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, sizeof(MgMeas)*(size_t)count) || g->grow_store(G, (size_t)first + count)) return -1;
+  MgMeas* rec = reinterpret_cast<MgMeas*>(g->up.in.p);
   for (int k = 0; k < count; ++k) {
     rec[k].uv[0] = uv[2*(size_t)k]; rec[k].uv[1] = uv[2*(size_t)k + 1]; rec[k].mkf = mkf[k]; rec[k].cam = cam[k]; rec[k].row = row[k];
     rec[k].level = level[k]; rec[k].source = source[k]; rec[k].alive = 1;
   }
-  ICK(hipMemcpyAsync(g->store.p + first, g->up_in.p, sizeof(MgMeas)*(size_t)count, hipMemcpyHostToDevice, g->m->st));
+  ICK(hipMemcpyAsync(g->store.p + first, g->up.in.p, sizeof(MgMeas)*(size_t)count, hipMemcpyHostToDevice, g->m->st));
   if (g->staged_now()) return -1;
   g->n_store += count; g->n_live += count;
   return first;
@@ -2923,7 +2989,7 @@ int mcp_map_graph_add_meas(mcp_map_graph* g, int count, const int* mkf, const in
 static int mg_erase_run(mcp_map_graph* g, const unsigned long long* d_keys, int n_keys, int slot) {
   hipStream_t st = g->m->st;
   ICK(hipMemsetAsync(&g->ctl.p->erased, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_mg_erase, dim3((unsigned)std::max(1, (g->n_store + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, st, g->store.p, g->n_store, d_keys, n_keys, slot, g->slots.p, g->ctl.p, (const int*)nullptr);
+  hipLaunchKernelGGL(k_mg_erase, dim3(mg_grid1(g->n_store)), dim3(MG_BLOCK), 0, st, g->store.p, g->n_store, d_keys, n_keys, slot, g->slots.p, g->ctl.p, (const int*)nullptr);
   ICK(hipGetLastError());
   ICK(hipMemcpyAsync(g->h_ctl.p, g->ctl.p, sizeof(MgCtl), hipMemcpyDeviceToHost, st));
   if (g->sync()) return -1;
@@ -2946,10 +3012,11 @@ int mcp_map_graph_erase_meas(mcp_map_graph* g, int count, const int* mkf, const 
   for (int k = 1; k < count; ++k) if (keys[k] == keys[k - 1]) return img_fail(who + ": a key appears twice");
   if (count == 0 || g->n_store == 0) return 0;
   ICK(hipSetDevice(g->m->device));
-  if (g->stage(8*(size_t)count)) return -1;
-  std::memcpy(g->up_in.p, keys.data(), 8*(size_t)count);
-  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, 8*(size_t)count, hipMemcpyHostToDevice, g->m->st));
-  return mg_erase_run(g, (const unsigned long long*)g->up_dev.p, count, -1);
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, 8*(size_t)count)) return -1;
+  std::memcpy(g->up.in.p, keys.data(), 8*(size_t)count);
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, 8*(size_t)count, hipMemcpyHostToDevice, g->m->st));
+  return mg_erase_run(g, (const unsigned long long*)g->up.dev.p, count, -1);
 }
 
 int mcp_map_graph_erase_mkf(mcp_map_graph* g, int slot) {
@@ -2957,7 +3024,7 @@ int mcp_map_graph_erase_mkf(mcp_map_graph* g, int slot) {
   if (slot < 0 || slot >= MCP_MAP_MAX_MKFS) return img_fail("mcp_map_graph_erase_mkf: slot " + std::to_string(slot) + " is outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
   ICK(hipSetDevice(g->m->device));
   const int died = mg_erase_run(g, nullptr, 0, slot);
-  if (died >= 0) g->h_flags[slot] &= ~MCP_MKF_PRESENT;
+  if (died >= 0) g->mirror.set(slot, g->mirror.flags_of(slot) & ~MCP_MKF_PRESENT);
   return died;
 }
 
@@ -2965,9 +3032,9 @@ int mcp_map_graph_compact(mcp_map_graph* g) {
   if (!g) return img_fail("mcp_map_graph_compact: NULL graph");
   if (g->n_live == g->n_store) return 0;
   ICK(hipSetDevice(g->m->device));
-  const int n = g->n_store, nblk = (n + MG_BLOCK - 1)/MG_BLOCK;
-  if (g->store_alt.n < g->store.n || g->blk.n < (size_t)nblk) { if (g->sync()) return -1; }
-  if (g->store_alt.alloc(g->store.n) || g->blk.alloc(nblk)) return -1;
+  const int n = g->n_store, nblk = mg_grid(n);
+  mcp_map_graph::Guard G(g);
+  if (G.grow(g->store_alt, g->store.n) || G.grow(g->blk, nblk)) return -1;
   hipLaunchKernelGGL(k_mg_compact_mark, dim3(nblk), dim3(MG_BLOCK), 0, g->m->st, (const MgMeas*)g->store.p, n, g->blk.p);
   hipLaunchKernelGGL(k_mg_compact_scatter, dim3(nblk), dim3(MG_BLOCK), 0, g->m->st, (const MgMeas*)g->store.p, n, nblk, (const int*)g->blk.p, g->store_alt.p, g->n_live);
   ICK(hipGetLastError());
@@ -2990,9 +3057,8 @@ int mcp_map_graph_get_meas(mcp_map_graph* g, int first, int count, int* mkf, int
   if (first < 0 || count < 0 || (long long)first + count > g->n_store) return img_fail("mcp_map_graph_get_meas: bad range");
   if (count == 0) return 0;
   ICK(hipSetDevice(g->m->device));
-  std::vector<MgMeas> tmp(count);
-  ICK(hipMemcpyAsync(tmp.data(), g->store.p + first, sizeof(MgMeas)*(size_t)count, hipMemcpyDeviceToHost, g->m->st));
-  if (g->sync()) return -1;
+  std::vector<MgMeas> tmp;
+  if (g->read_back(tmp, g->store.p + first, (size_t)count)) return -1;
   for (int k = 0; k < count; ++k) {
     const MgMeas& E = tmp[k];
     if (mkf) mkf[k] = E.mkf; if (cam) cam[k] = E.cam; if (row) row[k] = E.row; if (uv) { uv[2*(size_t)k] = E.uv[0]; uv[2*(size_t)k + 1] = E.uv[1]; }
@@ -3007,15 +3073,11 @@ int mcp_map_graph_good_counts(mcp_map_graph* g, int first, int count, int* out) 
   if (first < 0 || count < 0 || (long long)first + count > R || (count > 0 && !out)) return img_fail("mcp_map_graph_good_counts: bad arguments");
   if (count == 0) return 0;
   ICK(hipSetDevice(g->m->device));
-  if (g->marks.n < (size_t)R) { if (g->sync()) return -1; }
-  if (g->marks.alloc(R)) return -1;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(g->marks, R)) return -1;
   hipStream_t st = g->m->st;
   ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*(size_t)R, st));
-  if (g->n_store) {
-    hipLaunchKernelGGL(k_mg_edges_count, dim3((unsigned)((g->n_store + MG_BLOCK - 1)/MG_BLOCK)), dim3(MG_BLOCK), 0, st, (const MgCtl*)nullptr, (const MgMeas*)g->store.p, g->n_store, R,
-                       (const MgMkf*)g->slots.p, (const uint8_t*)nullptr, g->marks.p, (int*)nullptr);
-    ICK(hipGetLastError());
-  }
+  if (g->n_store) { g->good_counts_enqueue(R); ICK(hipGetLastError()); }
   ICK(hipMemcpyAsync(out, g->marks.p + first, sizeof(int)*(size_t)count, hipMemcpyDeviceToHost, st));
   return g->sync();
 }
@@ -3026,9 +3088,8 @@ int mcp_map_graph_check(mcp_map_graph* g, int* n_dup, int* n_dead) {
   *n_dup = 0; *n_dead = 0;
   if (g->n_store == 0) return 0;
   ICK(hipSetDevice(g->m->device));
-  std::vector<MgMeas> tmp(g->n_store);
-  ICK(hipMemcpyAsync(tmp.data(), g->store.p, sizeof(MgMeas)*(size_t)g->n_store, hipMemcpyDeviceToHost, g->m->st));
-  if (g->sync()) return -1;
+  std::vector<MgMeas> tmp;
+  if (g->read_back(tmp, g->store.p, (size_t)g->n_store)) return -1;
   std::vector<unsigned long long> keys;
   for (const MgMeas& E : tmp) { if (E.alive) keys.push_back(mg_key(E.mkf, E.cam, E.row)); else ++*n_dead; }
   std::sort(keys.begin(), keys.end());
@@ -3042,75 +3103,68 @@ int mcp_map_bundle_select(mcp_map_graph* g, const mcp_bundle_select_params* p, m
   if (!res) return img_fail(who + ": NULL result");
   const std::string bad = mg_params_check(p);
   if (!bad.empty()) return img_fail(who + ": " + bad);
-  if (p->mode == MCP_BUNDLE_RECENT && (p->newest < 0 || p->newest >= MCP_MAP_MAX_MKFS || !(g->h_flags[p->newest] & MCP_MKF_PRESENT)))
-    return img_fail(who + ": the newest MKF (slot " + std::to_string(p->newest) + ") is not present");
+  if (p->mode == MCP_BUNDLE_RECENT && !g->mirror.present(p->newest)) return img_fail(who + ": the newest MKF (slot " + std::to_string(p->newest) + ") is not present");
   mcp_map_points* m = g->m;
+  mcp_map_graph::Sel& s = g->sel;
   ICK(hipSetDevice(m->device));
   const int R = m->rows, M = g->n_store;
-  const int nbr = std::max(1, (R + MG_BLOCK - 1)/MG_BLOCK), nbm = std::max(1, (M + MG_BLOCK - 1)/MG_BLOCK);
+  const int nbr = mg_grid1(R), nbm = mg_grid1(M);
   const size_t n_marks = (size_t)MCP_MAP_MAX_MKFS + 2*(size_t)std::max(R, 1);
-  // everything is allocated before the first enqueue (a block that grows is replaced with nothing in flight on the old one; the pinned views of
-  // the last call are replaced only here, past the refusals)
-  if (g->marks.n < n_marks || g->bidx.n < (size_t)R || g->sel.n < (size_t)R || g->mkeep.n < (size_t)M || g->blk.n < (size_t)(nbr + nbm) ||
-      g->v_points.n < (size_t)R || g->v_meas.n < (size_t)M) { if (g->sync()) return -1; }
-  if (g->marks.alloc(n_marks) || g->bidx.alloc(R) || g->sel.alloc(R) || g->mkeep.alloc(M) || g->blk.alloc((size_t)nbr + nbm) || g->v_points.alloc(R) || g->v_meas.alloc(M) ||
-      g->grow_points(R)) return -1;
-  g->n_mkfs = g->n_points = g->n_meas = 0; g->timed = false;
+  // everything is allocated before the first enqueue (the pinned views of the last call are replaced only here, past the refusals)
+  mcp_map_graph::Guard G(g);
+  if (G.grow(g->marks, n_marks) || G.grow(s.bidx, R) || G.grow(s.rows, R) || G.grow(s.mkeep, M) || G.grow(g->blk, (size_t)nbr + nbm) || G.grow(s.v_points, R) || G.grow(s.v_meas, M) ||
+      g->grow_points(G, R)) return -1;
+  s.n_mkfs = s.n_points = s.n_meas = 0; s.t.timed = false;
   MgSelect S; S.mode = p->mode; S.newest = p->newest; S.n_recent = p->n_recent; S.recent_min_size = p->recent_min_size; S.min_points = p->min_points; S.frac = p->mean_diff_fraction;
   int* mkf_in = g->marks.p; int* good = mkf_in + MCP_MAP_MAX_MKFS; int* seen = good + std::max(R, 1);
   int* blk_rows = g->blk.p; int* blk_meas = blk_rows + nbr;
   hipStream_t st = m->st;
   const dim3 B(MG_BLOCK);
   Drain drain{m, true};
-  ICK(hipEventRecord(g->t0, st));
+  if (s.t.begin(st)) return -1;
   ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*n_marks, st));
   ICK(hipMemsetAsync(g->blk.p, 0, sizeof(int)*((size_t)nbr + nbm), st));
-  hipLaunchKernelGGL(k_mg_closest, dim3(1), B, 0, st, S, g->rig, (const MgMkf*)g->slots.p, g->adjust.p, g->ctl.p);
-  hipLaunchKernelGGL(k_mg_edges_count, dim3(nbm), B, 0, st, (const MgCtl*)g->ctl.p, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)g->adjust.p, good, seen);
+  hipLaunchKernelGGL(k_mg_closest, dim3(1), B, 0, st, S, g->rig, (const MgMkf*)g->slots.p, s.adjust.p, g->ctl.p);
+  hipLaunchKernelGGL(k_mg_edges_count, dim3(nbm), B, 0, st, (const MgCtl*)g->ctl.p, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)s.adjust.p, good, seen);
   hipLaunchKernelGGL(k_mg_rows_mark, dim3(nbr), B, 0, st, S, g->rig.ncam, g->ctl.p, (const MgMkf*)g->slots.p, (const MgPoint*)g->pts.p, R, (const int*)good, (const int*)seen,
-                     g->sel.p, mkf_in, blk_rows);
-  hipLaunchKernelGGL(k_mg_rank_mark, dim3(nbr + nbm), B, 0, st, (const MgCtl*)g->ctl.p, R, nbr, (const uint8_t*)g->sel.p, (const int*)blk_rows, g->bidx.p, (const MgMeas*)g->store.p, M,
-                     (const MgMkf*)g->slots.p, mkf_in, g->mkeep.p, blk_meas);
-  hipLaunchKernelGGL(k_mg_mkfs, dim3(1), B, 0, st, S, g->ctl.p, (const MgMkf*)g->slots.p, (const uint8_t*)g->adjust.p, (const int*)mkf_in, (const int*)blk_rows, nbr,
-                     (const int*)blk_meas, nbm, g->mkf_bidx.p, g->v_mkfs.p, g->h_res.p);
-  hipLaunchKernelGGL(k_mg_emit, dim3(nbr + nbm), B, 0, st, (const MgCtl*)g->ctl.p, g->rig, (const MgMkf*)g->slots.p, (const int*)g->mkf_bidx.p, (const MgPoint*)g->pts.p,
-                     (const PvsPoint*)m->pts.row(), R, nbr, (const int*)g->bidx.p, (const MgMeas*)g->store.p, M, (const uint8_t*)g->mkeep.p, (const int*)blk_meas, nbm,
-                     g->v_points.p, R, g->v_meas.p, M);
+                     s.rows.p, mkf_in, blk_rows);
+  hipLaunchKernelGGL(k_mg_rank_mark, dim3(nbr + nbm), B, 0, st, (const MgCtl*)g->ctl.p, R, nbr, (const uint8_t*)s.rows.p, (const int*)blk_rows, s.bidx.p, (const MgMeas*)g->store.p, M,
+                     (const MgMkf*)g->slots.p, mkf_in, s.mkeep.p, blk_meas);
+  hipLaunchKernelGGL(k_mg_mkfs, dim3(1), B, 0, st, S, g->ctl.p, (const MgMkf*)g->slots.p, (const uint8_t*)s.adjust.p, (const int*)mkf_in, (const int*)blk_rows, nbr,
+                     (const int*)blk_meas, nbm, s.mkf_bidx.p, s.v_mkfs.p, s.h_res.p);
+  hipLaunchKernelGGL(k_mg_emit, dim3(nbr + nbm), B, 0, st, (const MgCtl*)g->ctl.p, g->rig, (const MgMkf*)g->slots.p, (const int*)s.mkf_bidx.p, (const MgPoint*)g->pts.p,
+                     (const PvsPoint*)m->pts.row(), R, nbr, (const int*)s.bidx.p, (const MgMeas*)g->store.p, M, (const uint8_t*)s.mkeep.p, (const int*)blk_meas, nbm,
+                     s.v_points.p, R, s.v_meas.p, M);
   ICK(hipGetLastError());
-  ICK(hipEventRecord(g->t1, st));
-  if (g->sync()) return -1;
-  drain.armed = false; g->timed = true;
-  *res = *g->h_res.p;
-  g->n_mkfs = res->n_adjust + res->n_fixed; g->n_points = res->n_points; g->n_meas = res->n_meas;
+  if (s.t.end(st) || g->one_wait(drain, &s.t)) return -1;
+  *res = *s.h_res.p;
+  s.n_mkfs = res->n_adjust + res->n_fixed; s.n_points = res->n_points; s.n_meas = res->n_meas;
   return 0;
 }
 
 int mcp_map_bundle_select_last_timing(const mcp_map_graph* g, double* device_ms) {
   if (!g || !device_ms) return img_fail("mcp_map_bundle_select_last_timing: bad arguments");
-  if (!g->timed) return img_fail("mcp_map_bundle_select_last_timing: the last mcp_map_bundle_select on this graph did not run");
-  float ms = 0.f;
-  ICK(hipEventElapsedTime(&ms, g->t0, g->t1));
-  *device_ms = ms;
-  return 0;
+  if (!g->sel.t.timed) return img_fail("mcp_map_bundle_select_last_timing: the last mcp_map_bundle_select on this graph did not run");
+  return g->sel.t.ms(device_ms);
 }
 
 const mcp_bundle_mkf* mcp_map_bundle_mkfs_view(const mcp_map_graph* g, int* count) {
   if (count) *count = 0;
   if (!g) { img_fail("mcp_map_bundle_mkfs_view: NULL graph"); return nullptr; }
-  if (count) *count = g->n_mkfs;
-  return g->n_mkfs > 0 ? g->v_mkfs.p : nullptr;
+  if (count) *count = g->sel.n_mkfs;
+  return g->sel.n_mkfs > 0 ? g->sel.v_mkfs.p : nullptr;
 }
 const mcp_bundle_point* mcp_map_bundle_points_view(const mcp_map_graph* g, int* count) {
   if (count) *count = 0;
   if (!g) { img_fail("mcp_map_bundle_points_view: NULL graph"); return nullptr; }
-  if (count) *count = g->n_points;
-  return g->n_points > 0 ? g->v_points.p : nullptr;
+  if (count) *count = g->sel.n_points;
+  return g->sel.n_points > 0 ? g->sel.v_points.p : nullptr;
 }
 const mcp_bundle_meas* mcp_map_bundle_meas_view(const mcp_map_graph* g, int* count) {
   if (count) *count = 0;
   if (!g) { img_fail("mcp_map_bundle_meas_view: NULL graph"); return nullptr; }
-  if (count) *count = g->n_meas;
-  return g->n_meas > 0 ? g->v_meas.p : nullptr;
+  if (count) *count = g->sel.n_meas;
+  return g->sel.n_meas > 0 ? g->sel.v_meas.p : nullptr;
 }
 
 int mcp_map_bundle_select_host(const mcp_bundle_select_params* p, int ncam, const double* cfb, int n_slots, const double* bfw, const int* mflags, const uint8_t* act,
@@ -3154,7 +3208,7 @@ int mgl_slots_check(const mcp_map_graph* g, const std::string& who, int n_mkfs, 
   for (int i = 0; i < n_mkfs; ++i) {
     const int s = slots[i];
     if (s < 0 || s >= MCP_MAP_MAX_MKFS) return img_fail(who + ": slot " + std::to_string(s) + " is outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
-    if (!(g->h_flags[s] & MCP_MKF_PRESENT)) return img_fail(who + ": MKF slot " + std::to_string(s) + " is not present");
+    if (!g->mirror.present(s)) return img_fail(who + ": MKF slot " + std::to_string(s) + " is not present");
     if (pos_of[s] >= 0) return img_fail(who + ": slot " + std::to_string(s) + " appears twice");
     pos_of[s] = i;
   }
@@ -3176,32 +3230,30 @@ struct MglIn {
     if (n_mkfs && pose) std::memcpy(h + pose_idx, pose, sizeof(int)*(size_t)n_mkfs);
   }
 };
-// every buffer of the list passes, sized from n_store, n_mkfs, ncam and nb before the first enqueue (a block that grows is replaced with
-// nothing in flight on the old one); the scene-depth scratch of the table with them
-int mgl_reserve(mcp_map_graph* g, int n_kf, int nb) {
+// every buffer of the list passes, sized from n_store, n_mkfs, ncam and nb before the first enqueue; the scene-depth scratch of the table with them
+int mgl_reserve(mcp_map_graph::Guard& G, mcp_map_graph* g, int n_kf, int nb) {
   const size_t M = (size_t)std::max(g->n_store, 1), K = (size_t)std::max(n_kf, 1);
-  if (g->l_key_row.n < M || g->l_rows.n < M || g->l_w.n < M || g->l_table.n < K*nb || g->l_start.n < K + 1 || g->l_cfw.n < 12*K || g->m->wb.depth.n < M) { if (g->sync()) return -1; }
-  return (g->l_key_row.alloc(M) || g->l_rows.alloc(M) || g->l_w.alloc(M) || g->l_table.alloc(K*nb) || g->l_start.alloc(K + 1) || g->l_cfw.alloc(12*K) || g->m->wb.depth.alloc(M) ||
-          g->grow_points(g->m->rows)) ? -1 : 0;
+  mcp_map_graph::Lists& l = g->lists;
+  return (G.grow(l.key_row, M) || G.grow(l.rows, M) || G.grow(l.w, M) || G.grow(l.table, K*nb) || G.grow(l.start, K + 1) || G.grow(l.cfw, 12*K) || G.grow(g->m->wb.depth, M) ||
+          g->grow_points(G, g->m->rows)) ? -1 : 0;
 }
 // the three list launches on the table's stream (behind one memset of the count table); d_pos_of: on the device
 void mgl_enqueue(mcp_map_graph* g, int n_kf, int nb, const int* d_pos_of) {
   mcp_map_points* m = g->m;
+  mcp_map_graph::Lists& l = g->lists;
   const int M = g->n_store, chunk = mgl_chunk_len(M, nb);
-  (void)hipMemsetAsync(g->l_table.p, 0, sizeof(int)*(size_t)std::max(n_kf, 1)*nb, m->st);
+  (void)hipMemsetAsync(l.table.p, 0, sizeof(int)*(size_t)std::max(n_kf, 1)*nb, m->st);
   hipLaunchKernelGGL(k_mgl_count, dim3(nb), dim3(MGL_BLOCK), 0, m->st, (const MgMeas*)g->store.p, M, chunk, g->rig.ncam, n_kf, m->rows, d_pos_of, (const MgMkf*)g->slots.p,
-                     (const MgPoint*)g->pts.p, g->l_key_row.p, g->l_table.p);
-  hipLaunchKernelGGL(k_mgl_scan, dim3(1), dim3(MGL_BLOCK), 0, m->st, nb, n_kf, g->l_table.p, g->l_start.p);
-  hipLaunchKernelGGL(k_mgl_scatter, dim3(nb), dim3(MGL_BLOCK), 0, m->st, (const int2*)g->l_key_row.p, M, chunk, n_kf, g->l_table.p, (const int*)g->l_start.p,
-                     (const int*)m->cnt.row(), g->l_rows.p, g->l_w.p);
+                     (const MgPoint*)g->pts.p, l.key_row.p, l.table.p);
+  hipLaunchKernelGGL(k_mgl_scan, dim3(1), dim3(MGL_BLOCK), 0, m->st, nb, n_kf, l.table.p, l.start.p);
+  hipLaunchKernelGGL(k_mgl_scatter, dim3(nb), dim3(MGL_BLOCK), 0, m->st, (const int2*)l.key_row.p, M, chunk, n_kf, l.table.p, (const int*)l.start.p, (const int*)m->cnt.row(), l.rows.p, l.w.p);
 }
 // k_wb_scene_depth over the device-built lists (T: 12 doubles per pose, slot: pose of keyframe j or null), then the depth store into the slots
 void mgl_depth_enqueue(mcp_map_graph* g, int n_kf, const double* T, const int* slot, const int* d_slots, mcp_scene_depth* sd_pinned) {
   mcp_map_points* m = g->m;
-  hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)n_kf), dim3(SD_BLOCK), 0, m->st, T, slot, (const int*)g->l_start.p, (const int*)g->l_rows.p, (const double*)g->l_w.p,
+  hipLaunchKernelGGL(k_wb_scene_depth, dim3((unsigned)n_kf), dim3(SD_BLOCK), 0, m->st, T, slot, (const int*)g->lists.start.p, (const int*)g->lists.rows.p, (const double*)g->lists.w.p,
                      m->pts.row(), m->wb.depth.p, sd_pinned, (double*)nullptr);
-  hipLaunchKernelGGL(k_mgl_depth_store, dim3((unsigned)((n_kf + MGL_BLOCK - 1)/MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, n_kf, g->rig.ncam, d_slots, (const mcp_scene_depth*)sd_pinned,
-                     g->slots.p);
+  hipLaunchKernelGGL(k_mgl_depth_store, dim3(mg_grid(n_kf, MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, n_kf, g->rig.ncam, d_slots, (const mcp_scene_depth*)sd_pinned, g->slots.p);
 }
 }  // namespace
 
@@ -3212,9 +3264,8 @@ int mcp_graph_get_mkfs(mcp_map_graph* g, int first, int count, double* bfw, int*
   if (first < 0 || count < 0 || (long long)first + count > MCP_MAP_MAX_MKFS) return img_fail("mcp_graph_get_mkfs: bad range");
   if (count == 0) return 0;
   ICK(hipSetDevice(g->m->device));
-  std::vector<MgMkf> tmp((size_t)count);
-  ICK(hipMemcpyAsync(tmp.data(), g->slots.p + first, sizeof(MgMkf)*(size_t)count, hipMemcpyDeviceToHost, g->m->st));
-  if (g->sync()) return -1;
+  std::vector<MgMkf> tmp;
+  if (g->read_back(tmp, g->slots.p + first, (size_t)count)) return -1;
   const int nc = g->rig.ncam;
   for (int k = 0; k < count; ++k) {
     if (bfw) std::memcpy(bfw + 12*(size_t)k, tmp[k].bfw, 96);
@@ -3236,23 +3287,25 @@ int mcp_graph_debug_kf_lists(mcp_map_graph* g, int n_mkfs, const int* slots, int
   const int n_kf = n_mkfs*g->rig.ncam, nb = blocks ? blocks : mgl_default_blocks(g->n_store);
   const MglIn L(n_mkfs);
   const size_t o_rows = wb_align(sizeof(int)*((size_t)n_kf + 1)), o_w = wb_align(o_rows + sizeof(int)*(size_t)std::max(g->n_store, 1));
-  if (g->l_in.alloc(L.bytes) || g->l_dev.alloc(L.bytes) || g->l_out.alloc(o_w + 8*(size_t)std::max(g->n_store, 1)) || mgl_reserve(g, n_kf, nb)) return -1;
-  L.fill(g->l_in.p, pos_of, n_mkfs, slots, nullptr);
+  mcp_map_graph::Lists& l = g->lists;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(l.in, L.bytes) || G.grow(l.dev, L.bytes) || G.grow(l.out, o_w + 8*(size_t)std::max(g->n_store, 1)) || mgl_reserve(G, g, n_kf, nb)) return -1;
+  L.fill(l.in.p, pos_of, n_mkfs, slots, nullptr);
   Drain drain{m, true};
-  ICK(hipMemcpyAsync(g->l_dev.p, g->l_in.p, L.bytes, hipMemcpyHostToDevice, m->st));
-  mgl_enqueue(g, n_kf, nb, (const int*)(g->l_dev.p + L.pos_of));
+  ICK(hipMemcpyAsync(l.dev.p, l.in.p, L.bytes, hipMemcpyHostToDevice, m->st));
+  mgl_enqueue(g, n_kf, nb, (const int*)(l.dev.p + L.pos_of));
   ICK(hipGetLastError());
-  ICK(hipMemcpyAsync(g->l_out.p, g->l_start.p, sizeof(int)*((size_t)n_kf + 1), hipMemcpyDeviceToHost, m->st));
+  ICK(hipMemcpyAsync(l.out.p, l.start.p, sizeof(int)*((size_t)n_kf + 1), hipMemcpyDeviceToHost, m->st));
   if (g->sync()) return -1;
-  std::memcpy(seg_start, g->l_out.p, sizeof(int)*((size_t)n_kf + 1));
+  std::memcpy(seg_start, l.out.p, sizeof(int)*((size_t)n_kf + 1));
   const int total = seg_start[n_kf];
   if (total > cap) { drain.armed = false; return img_fail(who + ": the lists hold " + std::to_string(total) + " entries, the caller's arrays " + std::to_string(cap)); }
   if (total) {
-    ICK(hipMemcpyAsync(g->l_out.p + o_rows, g->l_rows.p, sizeof(int)*(size_t)total, hipMemcpyDeviceToHost, m->st));
-    ICK(hipMemcpyAsync(g->l_out.p + o_w, g->l_w.p, 8*(size_t)total, hipMemcpyDeviceToHost, m->st));
+    ICK(hipMemcpyAsync(l.out.p + o_rows, l.rows.p, sizeof(int)*(size_t)total, hipMemcpyDeviceToHost, m->st));
+    ICK(hipMemcpyAsync(l.out.p + o_w, l.w.p, 8*(size_t)total, hipMemcpyDeviceToHost, m->st));
     if (g->sync()) return -1;
-    std::memcpy(seg_rows, g->l_out.p + o_rows, sizeof(int)*(size_t)total);
-    std::memcpy(seg_w, g->l_out.p + o_w, 8*(size_t)total);
+    std::memcpy(seg_rows, l.out.p + o_rows, sizeof(int)*(size_t)total);
+    std::memcpy(seg_w, l.out.p + o_w, 8*(size_t)total);
   }
   drain.armed = false;
   return total;
@@ -3268,22 +3321,23 @@ int mcp_graph_refresh_depth(mcp_map_graph* g, int n_mkfs, const int* slots, mcp_
   ICK(hipSetDevice(m->device));
   const int n_kf = n_mkfs*g->rig.ncam, nb = mgl_default_blocks(g->n_store);
   const MglIn L(n_mkfs);
-  if (g->l_in.alloc(L.bytes) || g->l_dev.alloc(L.bytes) || g->l_out.alloc(sizeof(mcp_scene_depth)*(size_t)n_kf) || mgl_reserve(g, n_kf, nb)) return -1;
-  L.fill(g->l_in.p, pos_of, n_mkfs, slots, nullptr);
-  mcp_scene_depth* sd = reinterpret_cast<mcp_scene_depth*>(g->l_out.p);
-  const int* d_slots = (const int*)(g->l_dev.p + L.slots);
+  mcp_map_graph::Lists& l = g->lists;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(l.in, L.bytes) || G.grow(l.dev, L.bytes) || G.grow(l.out, sizeof(mcp_scene_depth)*(size_t)n_kf) || mgl_reserve(G, g, n_kf, nb)) return -1;
+  L.fill(l.in.p, pos_of, n_mkfs, slots, nullptr);
+  mcp_scene_depth* sd = reinterpret_cast<mcp_scene_depth*>(l.out.p);
+  const int* d_slots = (const int*)(l.dev.p + L.slots);
   Drain drain{m, true};
   m->wb.invalidate();
   ICK(hipEventRecord(m->wb.t[0], m->st));
-  ICK(hipMemcpyAsync(g->l_dev.p, g->l_in.p, L.bytes, hipMemcpyHostToDevice, m->st));
+  ICK(hipMemcpyAsync(l.dev.p, l.in.p, L.bytes, hipMemcpyHostToDevice, m->st));
   ICK(hipEventRecord(m->wb.t[1], m->st)); ICK(hipEventRecord(m->wb.t[2], m->st));
-  mgl_enqueue(g, n_kf, nb, (const int*)(g->l_dev.p + L.pos_of));
-  hipLaunchKernelGGL(k_mgl_cfw, dim3((unsigned)((n_kf + MGL_BLOCK - 1)/MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, g->rig, n_kf, d_slots, (const MgMkf*)g->slots.p, g->l_cfw.p, (double*)nullptr);
-  mgl_depth_enqueue(g, n_kf, (const double*)g->l_cfw.p, nullptr, d_slots, sd);
+  mgl_enqueue(g, n_kf, nb, (const int*)(l.dev.p + L.pos_of));
+  hipLaunchKernelGGL(k_mgl_cfw, dim3(mg_grid(n_kf, MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, g->rig, n_kf, d_slots, (const MgMkf*)g->slots.p, l.cfw.p, (double*)nullptr);
+  mgl_depth_enqueue(g, n_kf, (const double*)l.cfw.p, nullptr, d_slots, sd);
   const hipError_t le = hipGetLastError();
   (void)hipEventRecord(m->wb.t[3], m->st);
-  if (g->sync()) return -1;
-  drain.armed = false;
+  if (g->one_wait(drain)) return -1;
   if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
   m->wb.timed = true;
   sd_copy_out(n_kf, sd, depth_out);
@@ -3331,7 +3385,8 @@ int mcp_graph_write_back(mcp_ba* h, mcp_map_graph* g, int n_points, const int* p
   const WbLayout W(nslot, n_points, n_kf, 0, want_vec, false);                 // (its list fields stay empty: the lists are built on the device)
   const MglIn L(n_mkfs, W.in_bytes);
   const size_t in_bytes = W.in_bytes + L.bytes, o_bfw = W.out_bytes, out_bytes = o_bfw + 96*(size_t)n_mkfs;
-  if (m->wb.in.alloc(in_bytes) || m->wb.dev.alloc(in_bytes) || m->wb.out.alloc(out_bytes) || m->wb.T.alloc(12*(size_t)nslot) || mgl_reserve(g, n_kf, nb)) return -1;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(m->wb.in, in_bytes) || G.grow(m->wb.dev, in_bytes) || G.grow(m->wb.out, out_bytes) || G.grow(m->wb.T, 12*(size_t)nslot) || mgl_reserve(G, g, n_kf, nb)) return -1;
   char* hin = m->wb.in.p;
   std::memcpy(hin + W.chains, plan.chains.data(), sizeof(WbChain)*(size_t)nslot);
   if (n_points) std::memcpy(hin + W.items, plan.items.data(), sizeof(WbItem)*(size_t)n_points);
@@ -3352,15 +3407,14 @@ int mcp_graph_write_back(mcp_ba* h, mcp_map_graph* g, int n_points, const int* p
   (void)hipEventRecord(m->wb.t[2], m->st);
   if (n_mkfs) {
     const int* d_slots = (const int*)(din + L.slots);
-    hipLaunchKernelGGL(k_mgl_pose_store, dim3((unsigned)((12*n_mkfs + MGL_BLOCK - 1)/MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, n_mkfs, d_slots, (const int*)(din + L.pose_idx), S.pose,
+    hipLaunchKernelGGL(k_mgl_pose_store, dim3(mg_grid(12*n_mkfs, MGL_BLOCK)), dim3(MGL_BLOCK), 0, m->st, n_mkfs, d_slots, (const int*)(din + L.pose_idx), S.pose,
                        g->slots.p, bfw_out ? (double*)(hout + o_bfw) : (double*)nullptr);
     mgl_enqueue(g, n_kf, nb, (const int*)(din + L.pos_of));
     mgl_depth_enqueue(g, n_kf, (const double*)m->wb.T.p, (const int*)(din + W.kf_slot), d_slots, (mcp_scene_depth*)(hout + W.sd));
   }
   if (le == hipSuccess) le = hipGetLastError();
   (void)hipEventRecord(m->wb.t[3], m->st);
-  if (g->sync()) return -1;                                           // the one wait: the solver's memory is not read after this
-  drain.armed = false;
+  if (g->one_wait(drain)) return -1;                                  // the solver's memory is not read after this
   if (le != hipSuccess) return img_fail(who + ": launch failed: " + hipGetErrorString(le));
   m->wb.timed = true;
   if (want_vec) wb_copy_vec((const double*)(hout + W.vec), n_points, world_out, right_out, down_out);
@@ -3383,12 +3437,10 @@ struct mcp_meas_parcel {
   bool filled = false, committed = false;
   PinBuf<mcp_parcel_entry> up_in; hipEvent_t staged = nullptr; bool stage_busy = false;      // from_host: packed here, copied on the table's stream
   ~mcp_meas_parcel() { if (m && m->st) (void)hipStreamSynchronize(m->st); if (staged) (void)hipEventDestroy(staged); }
-  // room for `need` entries, contents not kept (a fill replaces them); a block that grows is replaced with nothing in flight on the old one
-  int reserve(size_t need) {
-    if (need <= ent.n && ent.p) return 0;
-    if (ent.p) ICK(m->sync());
-    return ent.alloc(std::max<size_t>({need, 2*ent.n, (size_t)1024}));
-  }
+  using Guard = Grow<mcp_meas_parcel>;
+  int sync() { ICK(m->sync()); return 0; }
+  // room for `need` entries, contents not kept (a fill replaces them)
+  int reserve(Guard& G, size_t need) { return G.regrow(ent, need, 0); }
   int filled_now(int count, int top, bool known) {
     n = count; h_max_lane = top; lane_known = known; filled = true; committed = false;
     return count;
@@ -3415,12 +3467,13 @@ int mcp_meas_parcel_from_track(mcp_meas_parcel* p) {
   if (!m->tr.ok) return img_fail(who + ": the last track / PVS call on this table was no successful mcp_track_map_record, mcp_track_frame_motion or mcp_track_frame_recover");
   const int ncam = m->tr.ncam, n = m->tr.meas_first[ncam];
   ICK(hipSetDevice(m->device));
-  if (p->reserve((size_t)n)) return -1;
+  mcp_meas_parcel::Guard G(p);
+  if (p->reserve(G, (size_t)n)) return -1;
   ICK(hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st));
   if (n > 0) {
     MgpFirst F; std::memset(&F, 0, sizeof F);
     for (int c = 0; c <= ncam; ++c) F.v[c] = m->tr.meas_first[c];
-    hipLaunchKernelGGL(k_mgp_from_track, dim3((unsigned)((n + MGP_BLOCK - 1)/MGP_BLOCK)), dim3(MGP_BLOCK), 0, m->st, (const mcp_track_meas*)m->tr.h_meas.p, n, ncam, F,
+    hipLaunchKernelGGL(k_mgp_from_track, dim3(mg_grid(n)), dim3(MG_BLOCK), 0, m->st, (const mcp_track_meas*)m->tr.h_meas.p, n, ncam, F,
                        (const TmSrc*)m->src.row(), m->rows, p->ent.p, p->max_lane.p);
     ICK(hipGetLastError());
     m->parcel_reads = true;
@@ -3435,10 +3488,11 @@ int mcp_meas_parcel_from_refind(mcp_meas_parcel* p) {
   if (m->rf.view < 0) return img_fail(who + ": the last mcp_map_refind on this table left no measurements to take");
   const int n = m->rf.view;
   ICK(hipSetDevice(m->device));
-  if (p->reserve((size_t)n)) return -1;
+  mcp_meas_parcel::Guard G(p);
+  if (p->reserve(G, (size_t)n)) return -1;
   ICK(hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st));
   if (n > 0) {
-    hipLaunchKernelGGL(k_mgp_from_refind, dim3((unsigned)((n + MGP_BLOCK - 1)/MGP_BLOCK)), dim3(MGP_BLOCK), 0, m->st, reinterpret_cast<const mcp_refind_meas*>(m->rf.out.p + m->rf.meas_off), n,
+    hipLaunchKernelGGL(k_mgp_from_refind, dim3(mg_grid(n)), dim3(MG_BLOCK), 0, m->st, reinterpret_cast<const mcp_refind_meas*>(m->rf.out.p + m->rf.meas_off), n,
                        (const TmSrc*)m->src.row(), m->rows, p->ent.p, p->max_lane.p);
     ICK(hipGetLastError());
     m->parcel_reads = true;
@@ -3456,20 +3510,19 @@ int mcp_meas_parcel_from_host(mcp_meas_parcel* p, int n, const int* lane, const 
   for (int k = 0; k < n; ++k) {
     const std::string at = who + ": entry " + std::to_string(k);
     if (lane[k] < 0) return img_fail(at + " names lane " + std::to_string(lane[k]));
-    if (row[k] < 0 || row[k] >= R) return img_fail(at + " names row " + std::to_string(row[k]) + ", the table has " + std::to_string(R));
-    if (level[k] < 0 || level[k] >= MCP_LEVELS) return img_fail(at + " has level " + std::to_string(level[k]));
-    if (!std::isfinite(uv[2*(size_t)k]) || !std::isfinite(uv[2*(size_t)k + 1])) return img_fail(at + " has a non-finite position");
+    if (mg_entry_check(at, row[k], R, level[k], uv + 2*(size_t)k)) return -1;
     top = std::max(top, lane[k]);
   }
   ICK(hipSetDevice(m->device));
   if (p->stage_busy) { ICK(hipEventSynchronize(p->staged)); p->stage_busy = false; }
-  if (p->up_in.alloc((size_t)n) || p->reserve((size_t)n)) return -1;
+  mcp_meas_parcel::Guard G(p);
+  if (G.grow(p->up_in, (size_t)n) || p->reserve(G, (size_t)n)) return -1;
   ICK(hipMemsetAsync(p->max_lane.p, 0xff, sizeof(int), m->st));
   if (n > 0) {
     mcp_parcel_entry* rec = p->up_in.p;
     for (int k = 0; k < n; ++k) { rec[k].uv[0] = uv[2*(size_t)k]; rec[k].uv[1] = uv[2*(size_t)k + 1]; rec[k].lane = lane[k]; rec[k].row = row[k]; rec[k].key = 0; rec[k].level = level[k]; }
     ICK(hipMemcpyAsync(p->ent.p, rec, sizeof(mcp_parcel_entry)*(size_t)n, hipMemcpyHostToDevice, m->st));
-    hipLaunchKernelGGL(k_mgp_keys, dim3((unsigned)((n + MGP_BLOCK - 1)/MGP_BLOCK)), dim3(MGP_BLOCK), 0, m->st, p->ent.p, n, (const TmSrc*)m->src.row(), R);
+    hipLaunchKernelGGL(k_mgp_keys, dim3(mg_grid(n)), dim3(MG_BLOCK), 0, m->st, p->ent.p, n, (const TmSrc*)m->src.row(), R);
     ICK(hipGetLastError());
     ICK(hipEventRecord(p->staged, m->st)); p->stage_busy = true;
   }
@@ -3503,7 +3556,7 @@ int mcp_meas_parcel_commit(mcp_map_graph* g, mcp_meas_parcel* p, int n_lanes, co
   if (n_lanes < 0 || (n_lanes > 0 && (!lane_mkf || !lane_cam))) return img_fail(who + ": bad lane tables");
   for (int l = 0; l < n_lanes; ++l) {
     if (lane_mkf[l] < 0) continue;
-    if (lane_mkf[l] >= MCP_MAP_MAX_MKFS || !(g->h_flags[lane_mkf[l]] & MCP_MKF_PRESENT)) return img_fail(who + ": lane " + std::to_string(l) + " names MKF slot " + std::to_string(lane_mkf[l]) + ", which is not present");
+    if (!g->mirror.present(lane_mkf[l])) return img_fail(who + ": lane " + std::to_string(l) + " names MKF slot " + std::to_string(lane_mkf[l]) + ", which is not present");
     if (lane_cam[l] < 0 || lane_cam[l] >= g->rig.ncam) return img_fail(who + ": lane " + std::to_string(l) + " names camera " + std::to_string(lane_cam[l]));
   }
   const int n = p->n, first = g->n_store;
@@ -3517,35 +3570,35 @@ int mcp_meas_parcel_commit(mcp_map_graph* g, mcp_meas_parcel* p, int n_lanes, co
   }
   mcp_map_points* m = g->m;
   ICK(hipSetDevice(m->device));
-  const int R = m->rows, nblk = (n + MGP_BLOCK - 1)/MGP_BLOCK;
+  const int R = m->rows, nblk = mg_grid(n);
   // staging: lane_mkf | lane_cam up; MgpCtl | lane_appended down.  Everything is allocated before the first enqueue.
   const size_t o_cam = tm_align(sizeof(int)*(size_t)std::max(n_lanes, 1)), up = 2*o_cam, o_lanes = tm_align(sizeof(MgpCtl)), down = o_lanes + sizeof(int)*(size_t)std::max(n_lanes, 1);
-  if (g->pc_vd.n < (size_t)n || g->pc_blk.n < (size_t)nblk || g->pc_dev.n < down || g->pc_out.n < down) { if (g->sync()) return -1; }
-  if (g->pc_vd.alloc(n) || g->pc_blk.alloc(nblk) || g->pc_dev.alloc(down) || g->pc_out.alloc(down)) return -1;
-  if (g->stage(up) || g->grow_store((size_t)first + n) || g->grow_points(R)) return -1;
-  std::memset(g->up_in.p, 0, up);
-  if (n_lanes) { std::memcpy(g->up_in.p, lane_mkf, sizeof(int)*(size_t)n_lanes); std::memcpy(g->up_in.p + o_cam, lane_cam, sizeof(int)*(size_t)n_lanes); }
+  mcp_map_graph::Commit& c = g->commit;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(c.vd, n) || G.grow(c.blk, nblk) || G.grow(c.dev, down) || G.grow(c.out, down) || g->stage(G, up) || g->grow_store(G, (size_t)first + n) || g->grow_points(G, R)) return -1;
+  std::memset(g->up.in.p, 0, up);
+  if (n_lanes) { std::memcpy(g->up.in.p, lane_mkf, sizeof(int)*(size_t)n_lanes); std::memcpy(g->up.in.p + o_cam, lane_cam, sizeof(int)*(size_t)n_lanes); }
   hipStream_t st = m->st;
   MgpCommit Q; Q.n = n; Q.n_lanes = n_lanes; Q.cross_camera = prm->cross_camera ? 1 : 0; Q.source = prm->source; Q.first = first; Q.cap = (long long)g->store.n;
-  const int* d_mkf = (const int*)g->up_dev.p; const int* d_cam = (const int*)(g->up_dev.p + o_cam);
-  MgpCtl* d_ctl = reinterpret_cast<MgpCtl*>(g->pc_dev.p); int* d_lanes = reinterpret_cast<int*>(g->pc_dev.p + o_lanes);
+  const int* d_mkf = (const int*)g->up.dev.p; const int* d_cam = (const int*)(g->up.dev.p + o_cam);
+  MgpCtl* d_ctl = reinterpret_cast<MgpCtl*>(c.dev.p); int* d_lanes = reinterpret_cast<int*>(c.dev.p + o_lanes);
+  const dim3 B(MG_BLOCK);
   Drain drain{m, true};
-  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, up, hipMemcpyHostToDevice, st));
-  ICK(hipMemsetAsync(g->pc_dev.p, 0, down, st));
-  hipLaunchKernelGGL(k_mgp_judge, dim3(nblk), dim3(MGP_BLOCK), 0, st, Q, (const mcp_parcel_entry*)p->ent.p, d_mkf, d_cam, (const TmSrc*)m->src.row(), R, (const MgPoint*)g->pts.p, g->prow,
-                     (const int*)p->max_lane.p, g->pc_vd.p, g->pc_blk.p, d_ctl, d_lanes);
-  hipLaunchKernelGGL(k_mgp_append, dim3(nblk), dim3(MGP_BLOCK), 0, st, Q, (const mcp_parcel_entry*)p->ent.p, d_mkf, d_cam, (const uint8_t*)g->pc_vd.p, (const int*)g->pc_blk.p, nblk,
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, up, hipMemcpyHostToDevice, st));
+  ICK(hipMemsetAsync(c.dev.p, 0, down, st));
+  hipLaunchKernelGGL(k_mgp_judge, dim3(nblk), B, 0, st, Q, (const mcp_parcel_entry*)p->ent.p, d_mkf, d_cam, (const TmSrc*)m->src.row(), R, (const MgPoint*)g->pts.p, g->prow,
+                     (const int*)p->max_lane.p, c.vd.p, c.blk.p, d_ctl, d_lanes);
+  hipLaunchKernelGGL(k_mgp_append, dim3(nblk), B, 0, st, Q, (const mcp_parcel_entry*)p->ent.p, d_mkf, d_cam, (const uint8_t*)c.vd.p, (const int*)c.blk.p, nblk,
                      (const int*)p->max_lane.p, reinterpret_cast<mcp_store_entry*>(g->store.p));
   ICK(hipGetLastError());
-  ICK(hipMemcpyAsync(g->pc_out.p, g->pc_dev.p, down, hipMemcpyDeviceToHost, st));
-  if (g->sync()) return -1;                            // the one wait
-  drain.armed = false;
-  const MgpCtl& C = *reinterpret_cast<const MgpCtl*>(g->pc_out.p);
+  ICK(hipMemcpyAsync(c.out.p, c.dev.p, down, hipMemcpyDeviceToHost, st));
+  if (g->one_wait(drain)) return -1;
+  const MgpCtl& C = *reinterpret_cast<const MgpCtl*>(c.out.p);
   p->h_max_lane = C.max_lane; p->lane_known = true;
   if (C.refused) return img_fail(who + ": the parcel holds an entry of lane " + std::to_string(C.max_lane) + ", the call has " + std::to_string(n_lanes) + " lanes");
   res->first = first; res->n_appended = C.counts[MCP_PARCEL_APPENDED]; res->n_skipped_lane = C.counts[MCP_PARCEL_SKIPPED]; res->n_stale = C.counts[MCP_PARCEL_STALE];
   res->n_bad = C.counts[MCP_PARCEL_BAD]; res->n_cross = C.counts[MCP_PARCEL_CROSS];
-  if (lane_appended && n_lanes) std::memcpy(lane_appended, g->pc_out.p + o_lanes, sizeof(int)*(size_t)n_lanes);
+  if (lane_appended && n_lanes) std::memcpy(lane_appended, c.out.p + o_lanes, sizeof(int)*(size_t)n_lanes);
   g->n_store += res->n_appended; g->n_live += res->n_appended;
   p->committed = true;
   return 0;
@@ -3563,8 +3616,9 @@ int mcp_map_cull_outliers(mcp_map_graph* g, int n, const int* mkf, const int* ca
   if (!prm || !res) return img_fail(who + ": NULL params or result");
   if (n < 0 || (n > 0 && (!mkf || !cam || !row))) return img_fail(who + ": bad arguments");
   if (prm->bad_good_count < 0) return img_fail(who + ": a negative bad_good_count");
-  std::vector<std::pair<unsigned long long, int>>& keys = g->c_keys;
-  std::vector<MgcRun>& runs = g->c_runs;
+  mcp_map_graph::Cull& c = g->cull;
+  std::vector<std::pair<unsigned long long, int>>& keys = c.keys;
+  std::vector<MgcRun>& runs = c.runs;
   keys.resize(n); runs.resize(n);
   for (int k = 0; k < n; ++k) {
     if (mkf[k] < 0 || mkf[k] >= MCP_MAP_MAX_MKFS) return img_fail(who + ": key " + std::to_string(k) + " names slot " + std::to_string(mkf[k]) + ", outside 0.." + std::to_string(MCP_MAP_MAX_MKFS - 1));
@@ -3574,46 +3628,42 @@ int mcp_map_cull_outliers(mcp_map_graph* g, int n, const int* mkf, const int* ca
   }
   std::sort(keys.begin(), keys.end());
   for (int k = 1; k < n; ++k) if (keys[k].first == keys[k - 1].first) return img_fail(who + ": a key appears twice (list entries " + std::to_string(keys[k - 1].second) + " and " + std::to_string(keys[k].second) + ")");
-  if (n == 0) { std::memset(res, 0, sizeof *res); g->c_timed[0] = false; return 0; }
+  if (n == 0) { std::memset(res, 0, sizeof *res); c.t_outliers.timed = false; return 0; }
   std::sort(runs.begin(), runs.end(), [](const MgcRun& a, const MgcRun& b) { return a.row != b.row ? a.row < b.row : a.idx < b.idx; });
   mcp_map_points* m = g->m;
   ICK(hipSetDevice(m->device));
   const int R = m->rows, M = g->n_store;
   // staging: sorted keys | their list indices | the runs up; MgcCtl | verdict bytes down.  Everything is allocated before the first enqueue.
   const size_t o_idx = tm_align(8*(size_t)n), o_runs = o_idx + tm_align(sizeof(int)*(size_t)n), up = o_runs + sizeof(MgcRun)*(size_t)n, o_vd = tm_align(sizeof(MgcCtl)), down = o_vd + (size_t)n;
-  if (g->cull_ready()) return -1;
-  if (g->marks.n < (size_t)R || g->c_match.n < (size_t)n || g->c_vd.n < (size_t)n || g->c_out.n < down) { if (g->sync()) return -1; }
-  if (g->marks.alloc(R) || g->c_match.alloc(n) || g->c_vd.alloc(n) || g->c_out.alloc(down) || g->stage(up) || g->grow_points(R)) return -1;
-  unsigned long long* hk = reinterpret_cast<unsigned long long*>(g->up_in.p); int* hi = reinterpret_cast<int*>(g->up_in.p + o_idx);
+  mcp_map_graph::Guard G(g);
+  if (G.grow(c.ctl, 1) || G.grow(g->marks, R) || G.grow(c.match, n) || G.grow(c.vd, n) || G.grow(c.out, down) || g->stage(G, up) || g->grow_points(G, R)) return -1;
+  unsigned long long* hk = reinterpret_cast<unsigned long long*>(g->up.in.p); int* hi = reinterpret_cast<int*>(g->up.in.p + o_idx);
   for (int k = 0; k < n; ++k) { hk[k] = keys[k].first; hi[k] = keys[k].second; }
-  std::memcpy(g->up_in.p + o_runs, runs.data(), sizeof(MgcRun)*(size_t)n);
+  std::memcpy(g->up.in.p + o_runs, runs.data(), sizeof(MgcRun)*(size_t)n);
   hipStream_t st = m->st;
-  const dim3 B(MGC_BLOCK);
-  g->c_timed[0] = false;
+  const dim3 B(MG_BLOCK);
   Drain drain{m, true};
-  ICK(hipEventRecord(g->c_ev[0], st));
-  ICK(hipMemcpyAsync(g->up_dev.p, g->up_in.p, up, hipMemcpyHostToDevice, st));
+  if (c.t_outliers.begin(st)) return -1;
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, up, hipMemcpyHostToDevice, st));
   if (R) ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*(size_t)R, st));
-  ICK(hipMemsetAsync(g->c_match.p, 0xff, sizeof(int)*(size_t)n, st));
-  ICK(hipMemsetAsync(g->c_ctl.p, 0, sizeof(MgcCtl), st));
+  ICK(hipMemsetAsync(c.match.p, 0xff, sizeof(int)*(size_t)n, st));
+  ICK(hipMemsetAsync(c.ctl.p, 0, sizeof(MgcCtl), st));
   if (M) {
-    const dim3 G((unsigned)((M + MGC_BLOCK - 1)/MGC_BLOCK));
-    hipLaunchKernelGGL(k_mg_edges_count, G, B, 0, st, (const MgCtl*)nullptr, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)nullptr, g->marks.p, (int*)nullptr);
-    hipLaunchKernelGGL(k_mgc_match, G, B, 0, st, (const MgMeas*)g->store.p, M, (const unsigned long long*)g->up_dev.p, (const int*)(g->up_dev.p + o_idx), n, g->c_match.p);
+    g->good_counts_enqueue(R);
+    hipLaunchKernelGGL(k_mgc_match, dim3(mg_grid(M)), B, 0, st, (const MgMeas*)g->store.p, M, (const unsigned long long*)g->up.dev.p, (const int*)(g->up.dev.p + o_idx), n, c.match.p);
   }
-  hipLaunchKernelGGL(k_mgc_judge, dim3((unsigned)((n + MGC_BLOCK - 1)/MGC_BLOCK)), B, 0, st, n, (const MgcRun*)(g->up_dev.p + o_runs), (const int*)g->c_match.p, g->store.p,
-                     (const MgMkf*)g->slots.p, g->pts.p, g->prow, R, (const int*)g->marks.p, prm->bad_good_count, g->c_vd.p, g->c_ctl.p);
+  hipLaunchKernelGGL(k_mgc_judge, dim3(mg_grid(n)), B, 0, st, n, (const MgcRun*)(g->up.dev.p + o_runs), (const int*)c.match.p, g->store.p, (const MgMkf*)g->slots.p, g->pts.p, g->prow, R,
+                     (const int*)g->marks.p, prm->bad_good_count, c.vd.p, c.ctl.p);
   ICK(hipGetLastError());
-  ICK(hipEventRecord(g->c_ev[1], st));
-  ICK(hipMemcpyAsync(g->c_out.p, g->c_ctl.p, sizeof(MgcCtl), hipMemcpyDeviceToHost, st));
-  ICK(hipMemcpyAsync(g->c_out.p + o_vd, g->c_vd.p, (size_t)n, hipMemcpyDeviceToHost, st));
-  if (g->sync()) return -1;                            // the one wait
-  drain.armed = false; g->c_timed[0] = true;
-  const MgcCtl& C = *reinterpret_cast<const MgcCtl*>(g->c_out.p);
+  if (c.t_outliers.end(st)) return -1;
+  ICK(hipMemcpyAsync(c.out.p, c.ctl.p, sizeof(MgcCtl), hipMemcpyDeviceToHost, st));
+  ICK(hipMemcpyAsync(c.out.p + o_vd, c.vd.p, (size_t)n, hipMemcpyDeviceToHost, st));
+  if (g->one_wait(drain, &c.t_outliers)) return -1;
+  const MgcCtl& C = *reinterpret_cast<const MgcCtl*>(c.out.p);
   res->n_missing = C.verdicts[MCP_CULL_MISSING]; res->n_fixed = C.verdicts[MCP_CULL_FIXED]; res->n_point_bad = C.verdicts[MCP_CULL_POINT_BAD]; res->n_retry = C.verdicts[MCP_CULL_RETRY];
   res->n_never_retry = C.verdicts[MCP_CULL_NEVER_RETRY]; res->n_already_bad = C.verdicts[MCP_CULL_ALREADY_BAD]; res->n_fixed_rows = C.fixed_rows; res->n_rows_marked = C.rows_marked;
   g->n_live -= res->n_retry + res->n_never_retry;
-  if (verdict_out) std::memcpy(verdict_out, g->c_out.p + o_vd, (size_t)n);
+  if (verdict_out) std::memcpy(verdict_out, c.out.p + o_vd, (size_t)n);
   return 0;
 }
 
@@ -3626,54 +3676,41 @@ int mcp_map_cull_sweep(mcp_map_graph* g, const mcp_cull_sweep_params* prm, mcp_c
   mcp_map_points* m = g->m;
   ICK(hipSetDevice(m->device));
   const int R = m->rows, M = g->n_store;
-  const int nbr = std::max(1, (R + MGC_BLOCK - 1)/MGC_BLOCK), nbm = (M + MGC_BLOCK - 1)/MGC_BLOCK;
-  if (g->cull_ready()) return -1;
-  if (g->marks.n < (size_t)R || g->c_rep.n < (size_t)R || g->blk.n < (size_t)nbr || g->c_out.n < sizeof(MgcCtl) || g->c_rows.n < (size_t)R) { if (g->sync()) return -1; }
-  if (g->marks.alloc(R) || g->c_rep.alloc(R) || g->blk.alloc(nbr) || g->c_out.alloc(sizeof(MgcCtl)) || g->c_rows.alloc(R) || g->grow_points(R)) return -1;
-  int n_present = 0;
-  for (int f : g->h_flags) n_present += (f & MCP_MKF_PRESENT) ? 1 : 0;
-  MgcSweep Q; Q.min_outliers = prm->min_outliers; Q.danglers_on = (prm->danglers && n_present >= 2) ? 1 : 0; Q.multiplier = prm->outlier_multiplier;
+  const int nbr = mg_grid1(R), nbm = mg_grid(M);
+  mcp_map_graph::Cull& c = g->cull;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(c.ctl, 1) || G.grow(g->marks, R) || G.grow(c.rep, R) || G.grow(g->blk, nbr) || G.grow(c.out, sizeof(MgcCtl)) || G.grow(c.rows, R) || g->grow_points(G, R)) return -1;
+  MgcSweep Q; Q.min_outliers = prm->min_outliers; Q.danglers_on = (prm->danglers && g->mirror.n_present() >= 2) ? 1 : 0; Q.multiplier = prm->outlier_multiplier;
   hipStream_t st = m->st;
-  const dim3 B(MGC_BLOCK);
-  g->c_timed[1] = false; g->c_nrows = 0;
+  const dim3 B(MG_BLOCK);
+  c.nrows = 0;
   Drain drain{m, true};
-  ICK(hipEventRecord(g->c_ev[2], st));
+  if (c.t_sweep.begin(st)) return -1;
   if (R) ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*(size_t)R, st));
-  ICK(hipMemsetAsync(g->c_ctl.p, 0, sizeof(MgcCtl), st));
-  if (M) hipLaunchKernelGGL(k_mg_edges_count, dim3((unsigned)nbm), B, 0, st, (const MgCtl*)nullptr, (const MgMeas*)g->store.p, M, R, (const MgMkf*)g->slots.p, (const uint8_t*)nullptr, g->marks.p, (int*)nullptr);
-  hipLaunchKernelGGL(k_mgc_sweep_rows, dim3((unsigned)nbr), B, 0, st, Q, g->pts.p, g->prow, R, (const int*)g->marks.p, (const int*)m->cnt.row(), m->pts.row(), g->c_rep.p, g->blk.p, g->c_ctl.p);
-  hipLaunchKernelGGL(k_mgc_sweep_emit, dim3((unsigned)(nbr + nbm)), B, 0, st, R, g->prow, nbr, (const uint8_t*)g->c_rep.p, (const int*)g->blk.p, g->c_rows.p, R, g->store.p, M,
-                     (const MgPoint*)g->pts.p, g->c_ctl.p);
+  ICK(hipMemsetAsync(c.ctl.p, 0, sizeof(MgcCtl), st));
+  if (M) g->good_counts_enqueue(R);
+  hipLaunchKernelGGL(k_mgc_sweep_rows, dim3(nbr), B, 0, st, Q, g->pts.p, g->prow, R, (const int*)g->marks.p, (const int*)m->cnt.row(), m->pts.row(), c.rep.p, g->blk.p, c.ctl.p);
+  hipLaunchKernelGGL(k_mgc_sweep_emit, dim3(nbr + nbm), B, 0, st, R, g->prow, nbr, (const uint8_t*)c.rep.p, (const int*)g->blk.p, c.rows.p, R, g->store.p, M, (const MgPoint*)g->pts.p, c.ctl.p);
   ICK(hipGetLastError());
-  ICK(hipEventRecord(g->c_ev[3], st));
-  ICK(hipMemcpyAsync(g->c_out.p, g->c_ctl.p, sizeof(MgcCtl), hipMemcpyDeviceToHost, st));
-  if (g->sync()) return -1;                            // the one wait
-  drain.armed = false; g->c_timed[1] = true;
-  const MgcCtl& C = *reinterpret_cast<const MgcCtl*>(g->c_out.p);
+  if (c.t_sweep.end(st)) return -1;
+  ICK(hipMemcpyAsync(c.out.p, c.ctl.p, sizeof(MgcCtl), hipMemcpyDeviceToHost, st));
+  if (g->one_wait(drain, &c.t_sweep)) return -1;
+  const MgcCtl& C = *reinterpret_cast<const MgcCtl*>(c.out.p);
   res->n_danglers = C.danglers; res->n_tracker_outliers = C.tracker; res->n_reported = C.reported; res->n_bad_rows = C.bad_rows; res->n_meas_erased = C.erased;
-  g->n_live -= C.erased; g->c_nrows = C.reported;
+  g->n_live -= C.erased; c.nrows = C.reported;
   return 0;
 }
 
 const int* mcp_map_cull_rows_view(const mcp_map_graph* g, int* count) {
   if (count) *count = 0;
   if (!g) { img_fail("mcp_map_cull_rows_view: NULL graph"); return nullptr; }
-  if (count) *count = g->c_nrows;
-  return g->c_nrows > 0 ? g->c_rows.p : nullptr;
+  if (count) *count = g->cull.nrows;
+  return g->cull.nrows > 0 ? g->cull.rows.p : nullptr;
 }
 
 int mcp_map_cull_last_timing(const mcp_map_graph* g, double* outliers_ms, double* sweep_ms) {
   if (!g) return img_fail("mcp_map_cull_last_timing: NULL graph");
-  double* out[2] = {outliers_ms, sweep_ms};
-  for (int k = 0; k < 2; ++k) {
-    if (!out[k]) continue;
-    *out[k] = -1.0;
-    if (!g->c_timed[k]) continue;
-    float ms = 0.f;
-    ICK(hipEventElapsedTime(&ms, g->c_ev[2*k], g->c_ev[2*k + 1]));
-    *out[k] = ms;
-  }
-  return 0;
+  return ((outliers_ms && g->cull.t_outliers.ms(outliers_ms)) || (sweep_ms && g->cull.t_sweep.ms(sweep_ms))) ? -1 : 0;
 }
 
 }  // extern "C"
@@ -3683,23 +3720,13 @@ namespace {
 // the two launches of one query on the table's stream, into entry q of the graph's hand-offs and results (zeroed here).  src_from: see k_mgn_dist
 int mgn_enqueue(mcp_map_graph* g, const MgnQuery& Q, int q, const int* src_from) {
   hipStream_t st = g->m->st;
-  ICK(hipMemsetAsync(g->n_ctl.p + q, 0, sizeof(MgnCtl), st));
-  ICK(hipMemsetAsync(g->n_res.p + q, 0, sizeof(mcp_neigh_result), st));
-  int n_slots = MCP_MAP_MAX_MKFS;                      // the slots up to the last present one: nothing above them is a candidate
-  while (n_slots > 0 && !(g->h_flags[n_slots - 1] & MCP_MKF_PRESENT)) --n_slots;
-  const int n_idx = mgn_indices(Q.kind, n_slots);
-  hipLaunchKernelGGL(k_mgn_dist, dim3((unsigned)((n_idx + MGN_BLOCK - 1)/MGN_BLOCK)), dim3(MGN_BLOCK), 0, st, Q, n_idx, g->rig, (const MgMkf*)g->slots.p, (const MgMkf*)g->n_ext.p, src_from,
-                     g->n_dist.p, g->n_cand.p, g->n_ctl.p + q);
-  hipLaunchKernelGGL(k_mgn_select, dim3(1), dim3(MGN_BLOCK), 0, st, Q, n_idx, (const MgMkf*)g->slots.p, (const double*)g->n_dist.p, (const uint8_t*)g->n_cand.p, g->n_ctl.p + q, g->n_res.p + q);
+  mcp_map_graph::Neigh& nb = g->neigh;
+  ICK(hipMemsetAsync(nb.ctl.p + q, 0, sizeof(MgnCtl), st));
+  ICK(hipMemsetAsync(nb.res.p + q, 0, sizeof(mcp_neigh_result), st));
+  const int n_idx = mgn_indices(Q.kind, g->mirror.top_present() + 1);      // the slots up to the last present one: nothing above them is a candidate
+  hipLaunchKernelGGL(k_mgn_dist, dim3(mg_grid(n_idx)), dim3(MG_BLOCK), 0, st, Q, n_idx, g->rig, (const MgMkf*)g->slots.p, (const MgMkf*)nb.ext.p, src_from, nb.dist.p, nb.cand.p, nb.ctl.p + q);
+  hipLaunchKernelGGL(k_mgn_select, dim3(1), dim3(MG_BLOCK), 0, st, Q, n_idx, (const MgMkf*)g->slots.p, (const double*)nb.dist.p, (const uint8_t*)nb.cand.p, nb.ctl.p + q, nb.res.p + q);
   ICK(hipGetLastError());
-  return 0;
-}
-int mgn_timing(const mcp_map_graph* g, int k, double* device_ms) {
-  *device_ms = -1.0;
-  if (!g->n_timed[k]) return 0;
-  float ms = 0.f;
-  ICK(hipEventElapsedTime(&ms, g->n_ev[2*k], g->n_ev[2*k + 1]));
-  *device_ms = ms;
   return 0;
 }
 }  // namespace
@@ -3711,107 +3738,104 @@ int mcp_map_neighbours(mcp_map_graph* g, const mcp_neigh_params* p, mcp_neigh_re
   if (!g) return img_fail(who + ": NULL graph");
   if (!res) return img_fail(who + ": NULL result");
   std::string bad = mgn_params_check(p, g->rig.ncam);
-  if (bad.empty()) bad = mgn_source_check(p, p->src_slot >= 0 ? g->h_flags[p->src_slot] : 0, p->src_slot >= 0 ? &g->h_act[(size_t)p->src_slot*MCP_MAX_FRAME_CAMS] : nullptr);
+  if (bad.empty()) bad = mgn_source_check(p, p->src_slot >= 0 ? g->mirror.flags_of(p->src_slot) : 0, p->src_slot >= 0 ? g->mirror.active(p->src_slot) : nullptr);
   if (!bad.empty()) return img_fail(who + ": " + bad);
   mcp_map_points* m = g->m;
   ICK(hipSetDevice(m->device));
   const MgnQuery Q = mgn_query(*p);
   const bool ext = p->src_slot < 0;
-  if (g->n_dist.n == 0 && g->sync()) return -1;        // (the scratch is allocated once, with nothing in flight)
-  if (g->neigh_ready() || (ext && g->stage(sizeof(MgMkf)))) return -1;
+  mcp_map_graph::Neigh& nb = g->neigh;
+  mcp_map_graph::Guard G(g);
+  if (g->neigh_reserve(G) || (ext && g->stage(G, sizeof(MgMkf)))) return -1;
   if (ext) {
-    MgMkf* rec = reinterpret_cast<MgMkf*>(g->up_in.p);
+    MgMkf* rec = reinterpret_cast<MgMkf*>(g->up.in.p);
     std::memset(rec, 0, sizeof(MgMkf));
     std::memcpy(rec->bfw, p->ext_base_from_world, 96);
     for (int c = 0; c < g->rig.ncam; ++c) { const bool a = p->ext_active[c] != 0; rec->active[c] = a ? 1 : 0; rec->depth[c] = a ? p->ext_depth_mean[c] : 0.0; }
   }
   hipStream_t st = m->st;
-  g->n_timed[0] = false;
   Drain drain{m, true};
-  ICK(hipEventRecord(g->n_ev[0], st));
-  if (ext) { ICK(hipMemcpyAsync(g->n_ext.p, g->up_in.p, sizeof(MgMkf), hipMemcpyHostToDevice, st)); if (g->staged_now()) return -1; }
+  if (nb.t_query.begin(st)) return -1;
+  if (ext) { ICK(hipMemcpyAsync(nb.ext.p, g->up.in.p, sizeof(MgMkf), hipMemcpyHostToDevice, st)); if (g->staged_now()) return -1; }
   if (mgn_enqueue(g, Q, 0, nullptr)) return -1;
   if (Q.want_meas && g->n_store) {
-    hipLaunchKernelGGL(k_mgn_count, dim3((unsigned)((g->n_store + MGN_BLOCK - 1)/MGN_BLOCK)), dim3(MGN_BLOCK), 0, st, Q.kind, (const MgMeas*)g->store.p, g->n_store, g->n_res.p);
+    hipLaunchKernelGGL(k_mgn_count, dim3(mg_grid(g->n_store)), dim3(MG_BLOCK), 0, st, Q.kind, (const MgMeas*)g->store.p, g->n_store, nb.res.p);
     ICK(hipGetLastError());
   }
-  ICK(hipEventRecord(g->n_ev[1], st));
-  ICK(hipMemcpyAsync(g->n_out.p, g->n_res.p, sizeof(mcp_neigh_result), hipMemcpyDeviceToHost, st));
-  if (g->sync()) return -1;                            // the one wait
-  drain.armed = false; g->n_timed[0] = true;
-  std::memcpy(res, g->n_out.p, sizeof(mcp_neigh_result));
+  if (nb.t_query.end(st)) return -1;
+  ICK(hipMemcpyAsync(nb.out.p, nb.res.p, sizeof(mcp_neigh_result), hipMemcpyDeviceToHost, st));
+  if (g->one_wait(drain, &nb.t_query)) return -1;
+  std::memcpy(res, nb.out.p, sizeof(mcp_neigh_result));
   return 0;
 }
 
 int mcp_map_neighbours_last_timing(const mcp_map_graph* g, double* device_ms) {
   if (!g || !device_ms) return img_fail("mcp_map_neighbours_last_timing: bad arguments");
-  return mgn_timing(g, 0, device_ms);
+  return g->neigh.t_query.ms(device_ms);
 }
 
 int mcp_map_mkf_cull(mcp_map_graph* g, const mcp_mkf_cull_params* p, mcp_mkf_cull_result* res) {
   const std::string who = "mcp_map_mkf_cull";
   if (!g) return img_fail(who + ": NULL graph");
   if (!p || !res) return img_fail(who + ": NULL params or result");
-  auto present = [&](int k) { return k >= 0 && k < MCP_MAP_MAX_MKFS && (g->h_flags[k] & MCP_MKF_PRESENT); };
-  if (p->slot != -1 && !present(p->slot)) return img_fail(who + ": the victim (slot " + std::to_string(p->slot) + ") is not a present slot");
-  if (p->slot == -1 && !present(p->furthest_from)) return img_fail(who + ": furthest_from (slot " + std::to_string(p->furthest_from) + ") is not a present slot");
+  mcp_map_graph::Mirror& mir = g->mirror;
+  if (p->slot != -1 && !mir.present(p->slot)) return img_fail(who + ": the victim (slot " + std::to_string(p->slot) + ") is not a present slot");
+  if (p->slot == -1 && !mir.present(p->furthest_from)) return img_fail(who + ": furthest_from (slot " + std::to_string(p->furthest_from) + ") is not a present slot");
   if (p->max_kfs < 0) return img_fail(who + ": a negative max_kfs");
   if (!std::isfinite(p->mean_diff_fraction)) return img_fail(who + ": mean_diff_fraction is not finite");
   mcp_map_points* m = g->m;
   ICK(hipSetDevice(m->device));
   const int R = m->rows, M = g->n_store;
   const size_t n_marks = 2*(size_t)std::max(R, 1);
-  if ((g->n_dist.n == 0 || g->marks.n < n_marks) && g->sync()) return -1;      // (a block that grows is replaced with nothing in flight on the old one)
-  if (g->neigh_ready() || g->marks.alloc(n_marks) || g->grow_points(R)) return -1;
+  mcp_map_graph::Neigh& nb = g->neigh;
+  mcp_map_graph::Guard G(g);
+  if (g->neigh_reserve(G) || G.grow(g->marks, n_marks) || g->grow_points(G, R)) return -1;
   MgnQuery Q;
   Q.kind = MCP_NB_MKF; Q.region = MCP_NB_ALL; Q.src_cam = 0; Q.same_cam = 0; Q.n_max = 1; Q.want_meas = 0; Q.max_dist = HUGE_VAL; Q.frac = p->mean_diff_fraction;
   MgnCullIn P; P.slot = p->slot; P.mark_points = p->mark_points ? 1 : 0; P.max_kfs = p->max_kfs; P.erase = p->erase ? 1 : 0;
   int* live = g->marks.p; int* by_src = live + std::max(R, 1);
   hipStream_t st = m->st;
-  const dim3 B(MGN_BLOCK), GM((unsigned)std::max(1, (M + MGN_BLOCK - 1)/MGN_BLOCK));
-  g->n_timed[1] = false;
+  const dim3 B(MG_BLOCK), GM(mg_grid1(M));
   Drain drain{m, true};
-  ICK(hipEventRecord(g->n_ev[2], st));
-  ICK(hipMemsetAsync(g->n_cc.p, 0, sizeof(MgnCull), st));
+  if (nb.t_remove.begin(st)) return -1;
+  ICK(hipMemsetAsync(nb.cc.p, 0, sizeof(MgnCull), st));
   ICK(hipMemsetAsync(&g->ctl.p->erased, 0, sizeof(int), st));
   const mcp_neigh_result* far = nullptr;
   if (p->slot == -1) {                                 // FurthestMultiKeyFrame(furthest_from)
     Q.order = MCP_NB_FURTHEST; Q.src_slot = p->furthest_from;
     if (mgn_enqueue(g, Q, 0, nullptr)) return -1;
-    far = g->n_res.p;
+    far = nb.res.p;
   }
   Q.order = MCP_NB_NEAREST; Q.src_slot = p->slot;      // ClosestMultiKeyFrame(victim): used if the victim is fixed
-  if (mgn_enqueue(g, Q, 1, far ? &g->n_ctl.p->first_slot : nullptr)) return -1;
-  hipLaunchKernelGGL(k_mgn_decide, dim3(1), dim3(64), 0, st, P, far, (const mcp_neigh_result*)(g->n_res.p + 1), g->slots.p, g->n_cc.p);
+  if (mgn_enqueue(g, Q, 1, far ? &nb.ctl.p->first_slot : nullptr)) return -1;
+  hipLaunchKernelGGL(k_mgn_decide, dim3(1), dim3(64), 0, st, P, far, (const mcp_neigh_result*)(nb.res.p + 1), g->slots.p, nb.cc.p);
   if (P.mark_points && M) {
     ICK(hipMemsetAsync(g->marks.p, 0, sizeof(int)*n_marks, st));
-    hipLaunchKernelGGL(k_mgn_rows_count, GM, B, 0, st, (const MgnCull*)g->n_cc.p, (const MgMeas*)g->store.p, M, R, g->prow, (const MgPoint*)g->pts.p, live, by_src);
+    hipLaunchKernelGGL(k_mgn_rows_count, GM, B, 0, st, (const MgnCull*)nb.cc.p, (const MgMeas*)g->store.p, M, R, g->prow, (const MgPoint*)g->pts.p, live, by_src);
   }
-  if (M) hipLaunchKernelGGL(k_mgn_mark, GM, B, 0, st, P, g->n_cc.p, (const MgMeas*)g->store.p, M, R, g->prow, g->pts.p, (const int*)live, (const int*)by_src);
-  if (P.erase) hipLaunchKernelGGL(k_mg_erase, GM, dim3(MG_BLOCK), 0, st, g->store.p, M, (const unsigned long long*)nullptr, 0, -1, g->slots.p, g->ctl.p, (const int*)&g->n_cc.p->victim);
+  if (M) hipLaunchKernelGGL(k_mgn_mark, GM, B, 0, st, P, nb.cc.p, (const MgMeas*)g->store.p, M, R, g->prow, g->pts.p, (const int*)live, (const int*)by_src);
+  if (P.erase) hipLaunchKernelGGL(k_mg_erase, GM, B, 0, st, g->store.p, M, (const unsigned long long*)nullptr, 0, -1, g->slots.p, g->ctl.p, (const int*)&nb.cc.p->victim);
   ICK(hipGetLastError());
-  ICK(hipEventRecord(g->n_ev[3], st));
-  ICK(hipMemcpyAsync(g->n_out.p, g->n_cc.p, sizeof(MgnCull), hipMemcpyDeviceToHost, st));
+  if (nb.t_remove.end(st)) return -1;
+  ICK(hipMemcpyAsync(nb.out.p, nb.cc.p, sizeof(MgnCull), hipMemcpyDeviceToHost, st));
   ICK(hipMemcpyAsync(g->h_ctl.p, g->ctl.p, sizeof(MgCtl), hipMemcpyDeviceToHost, st));
-  if (g->sync()) return -1;                            // the one wait
-  drain.armed = false; g->n_timed[1] = true;
-  const MgnCull& C = *reinterpret_cast<const MgnCull*>(g->n_out.p);
+  if (g->one_wait(drain, &nb.t_remove)) return -1;
+  const MgnCull& C = *reinterpret_cast<const MgnCull*>(nb.out.p);
   std::memset(res, 0, sizeof *res);
   res->status = C.status; res->victim = C.victim; res->victim_dist_valid = C.dist_valid; res->victim_dist = C.dist; res->new_fixed = C.new_fixed;
   if (C.status == 0) {
     res->n_victim_meas = C.n_victim_meas; res->n_rows_marked = C.n_rows_marked; res->n_by_count = C.n_by_count; res->n_by_source = C.n_by_source;
     res->n_meas_erased = P.erase ? g->h_ctl.p->erased : 0;
     g->n_live -= res->n_meas_erased;
-    g->h_flags[C.victim] |= MCP_MKF_BAD;
-    if (C.new_fixed >= 0) g->h_flags[C.new_fixed] |= MCP_MKF_FIXED;
-    if (P.erase) g->h_flags[C.victim] &= ~MCP_MKF_PRESENT;
+    if (C.new_fixed >= 0) mir.set(C.new_fixed, mir.flags_of(C.new_fixed) | MCP_MKF_FIXED);
+    mir.set(C.victim, (mir.flags_of(C.victim) | MCP_MKF_BAD) & (P.erase ? ~MCP_MKF_PRESENT : ~0));
   }
   return 0;
 }
 
 int mcp_map_mkf_cull_last_timing(const mcp_map_graph* g, double* device_ms) {
   if (!g || !device_ms) return img_fail("mcp_map_mkf_cull_last_timing: bad arguments");
-  return mgn_timing(g, 1, device_ms);
+  return g->neigh.t_remove.ms(device_ms);
 }
 
 }  // extern "C"

@@ -308,3 +308,107 @@ def test_refusals(gpu_required):
     again = g.select_raw(S)
     assert (bytes(again[0]), again[1].tobytes(), again[2].tobytes(), again[3].tobytes()) == keep
     g.close(); t.close()
+
+
+def _every_call(t, g, a, rng, lane_mkf, lane_cam, n_parcel):
+    """Every device call that sizes scratch from the map, once, on a live graph: each answer against its host twin on the flat arrays `a`
+    (byte for byte, or equal integers).  Returns `a` as the calls leave the map."""
+    import graph_list_cases as lc
+    R, P, C = t.rows, len(a["mkf_flags"]), int(a["ncam"])
+    assert len(a["pt_flags"]) == R
+    for S in (mg.select_params(mg.BUNDLE_ALL, min_points=1), mc.recent(a, recent_min_size=2, min_points=1)):
+        mc.assert_same_selection(g.select_raw(S), mg.bundle_select_host(a, S), exact=True)
+    ok = ((a["mkf_flags"] & mg.MKF_PRESENT) != 0) & ((a["mkf_flags"] & mg.MKF_BAD) == 0)
+    assert np.array_equal(g.good_counts(), np.bincount(a["ms_row"][(a["ms_alive"] != 0) & ok[a["ms_mkf"]]], minlength=R))
+    # outliers: a handful of live entries and one key that matches nothing
+    pick = np.flatnonzero(a["ms_alive"])[5::97][:6]
+    km, kc, kr = np.r_[a["ms_mkf"][pick], 0], np.r_[a["ms_cam"][pick], 0], np.r_[a["ms_row"][pick], R + 7]
+    r1, vd = g.cull_outliers(km, kc, kr)
+    h1, hvd, a = mg.cull_outliers_host(a, km, kc, kr, n_rows=R)
+    assert r1 == h1 and np.array_equal(vd, hvd)
+    r2, rows = g.cull_sweep()
+    h2, hrows, a = mg.cull_sweep_host(a, n_rows=R)
+    assert r2 == h2 and np.array_equal(rows, hrows)
+    for q in (dict(kind=mg.NB_MKF, src_slot=0, n_max=3, want_meas=True), dict(kind=mg.NB_KF, src_slot=1, src_cam=0, n_max=4)):
+        assert bytes(g.neighbours(raw=True, **q)) == bytes(mg.neighbours_host(a, q, raw=True)), q
+    slots = np.arange(P - 1, -1, -2)
+    lists = mg.kf_lists_host(a, slots, R)
+    lc.assert_same_lists(g.debug_kf_lists(slots), lists)
+    # the scene depth at the graph's own poses against mcp_scene_depth_robust over the host twin's lists; the refreshed means go into the graph
+    rec = g.refresh_depth(slots)
+    cfb, bfw = a["cam_from_base"], a["base_from_world"]
+    Rk, tk = mg._compose(cfb[None, :, :9].reshape(1, C, 3, 3), cfb[None, :, 9:], bfw[slots, None, :9].reshape(len(slots), 1, 3, 3), bfw[slots, None, 9:])
+    want, _ = t.scene_depth(np.concatenate([Rk.reshape(-1, 9), tk.reshape(-1, 3)], axis=1), *lists)
+    assert rec.tobytes() == want.tobytes()
+    rec = rec.reshape(len(slots), C)
+    fresh = rec["refreshed"] == 1
+    dep = a["kf_depth_mean"][slots]; dep[fresh] = rec["mean"][fresh]; a["kf_depth_mean"][slots] = dep
+    # a parcel of entries the store does not hold yet
+    have = set(zip(a["ms_mkf"].tolist(), a["ms_cam"].tolist(), a["ms_row"].tolist()))
+    free = [(l, r) for l in range(len(lane_mkf)) for r in range(R) if (lane_mkf[l], lane_cam[l], r) not in have]
+    assert len(free) >= n_parcel
+    lane, row = np.array([free[i] for i in rng.choice(len(free), n_parcel, replace=False)], dtype=np.int32).T
+    uv, level = rng.uniform(0, 480, (n_parcel, 2)), rng.integers(0, 4, n_parcel)
+    p = mg.MeasParcel.from_host(t, lane, row, uv, level)
+    e = mg.parcel_entries(lane, row, uv, level, key=100 + row)
+    assert p.entries().tobytes() == e.tobytes()
+    res, lanes = g.commit_parcel(p, lane_mkf, lane_cam)
+    _, hres, recs, hlanes = mg.parcel_commit_host(e, 100 + np.arange(R), a["pt_flags"], a["src_mkf"], a["src_cam"], lane_mkf, lane_cam, first=len(a["ms_mkf"]))
+    assert res == hres and np.array_equal(lanes, hlanes)
+    p.close()
+    for k in ("mkf", "cam", "row", "level", "source"):
+        a["ms_" + k] = np.concatenate([a["ms_" + k], recs[k]]).astype(np.int32)
+    a["ms_uv"] = np.concatenate([a["ms_uv"], recs["uv"]]); a["ms_alive"] = np.concatenate([a["ms_alive"], recs["alive"] != 0]).astype(np.uint8)
+    got = g.get_meas()
+    for k in ("mkf", "cam", "row", "level", "source", "alive"):
+        assert np.array_equal(got[k], a["ms_" + k]), k
+    assert got["uv"].tobytes() == a["ms_uv"].tobytes() and g.num_meas() == (int(a["ms_alive"].sum()), len(a["ms_mkf"]))
+    return a
+
+
+def test_one_graph_lives_through_growth(gpu_required):
+    """One graph stays alive while its table, point columns, store, slots and every call's scratch grow with work still queued: every call on
+    it at 8 MKFs / 255 rows / 1000 entries, then growth to 9 MKFs / 513 rows / 2100 entries without a wait, then every call again.  The sizes
+    cross one and two workgroups of rows, the store's first capacity and its doubling, and both formulas of the shared scratch."""
+    rng = np.random.default_rng(20261020)
+    R0, R1, M1 = 255, 513, 2100
+    a = _random_map(77, 8, R0, 1000)
+    t, g = _device(a)
+    z = np.zeros((R1, 3))
+    t.set_source(100 + np.arange(R0), [None] * R0, np.zeros(R0), np.zeros((R0, 2)))
+    a = _every_call(t, g, a, rng, [2, 5], [0, 1], 40)
+    # growth, nothing waited for in between: rows, point columns, store entries, an erase and a compaction, a ninth slot
+    new = np.arange(R0, R1)
+    world = a["base_from_world"][rng.integers(0, 8, len(new)), 9:] * -1.0 + rng.normal(size=(len(new), 3)) * 3
+    t.resize(R1)
+    t.set(world, z[:len(new)], z[:len(new)], np.ones(len(new), dtype=np.uint8), first=R0)
+    t.update_source(new, 100 + new, [None] * len(new), np.zeros(len(new)), np.zeros((len(new), 2)))
+    n_add = M1 - len(a["ms_mkf"])
+    keys = rng.choice(8 * 2 * len(new), n_add, replace=False)                # distinct (mkf, cam, row) over the new rows: none is in the store
+    am, ac, ar = (keys // (2 * len(new))).astype(np.int32), ((keys // len(new)) % 2).astype(np.int32), (R0 + keys % len(new)).astype(np.int32)
+    sm, sc = rng.integers(0, 8, len(new)).astype(np.int32), rng.integers(0, 2, len(new)).astype(np.int32)
+    g.update_points(new, sm, sc, np.zeros(len(new), dtype=np.int32))
+    auv, alv, asrc = rng.uniform(0, 480, (n_add, 2)), rng.integers(0, 4, n_add).astype(np.int32), rng.integers(0, 5, n_add).astype(np.int32)
+    assert g.add_meas(am, ac, ar, auv, alv, asrc) == len(a["ms_mkf"])
+    a["world_pos"] = np.concatenate([a["world_pos"], world])
+    a["src_mkf"], a["src_cam"] = np.concatenate([a["src_mkf"], sm]), np.concatenate([a["src_cam"], sc])
+    a["pt_flags"] = np.concatenate([a["pt_flags"], np.zeros(len(new), dtype=np.int32)])
+    a["pending"] = np.concatenate([a["pending"], np.zeros(len(new), dtype=np.uint8)]); a["usable"] = np.concatenate([a["usable"], np.ones(len(new), dtype=np.uint8)])
+    for k, v in (("mkf", am), ("cam", ac), ("row", ar), ("level", alv), ("source", asrc)):
+        a["ms_" + k] = np.concatenate([a["ms_" + k], v])
+    a["ms_uv"] = np.concatenate([a["ms_uv"], auv]); a["ms_alive"] = np.concatenate([a["ms_alive"], np.ones(n_add, dtype=np.uint8)])
+    assert len(a["ms_mkf"]) == M1
+    dead = np.flatnonzero(a["ms_alive"])[3::211]
+    assert g.erase_meas(a["ms_mkf"][dead], a["ms_cam"][dead], a["ms_row"][dead]) == len(dead)
+    a["ms_alive"][dead] = 0
+    g.compact()
+    live = np.flatnonzero(a["ms_alive"])
+    for k in ("mkf", "cam", "row", "uv", "level", "source", "alive"):
+        a["ms_" + k] = a["ms_" + k][live]
+    assert len(live) > 1024
+    ninth = mg.poses12(np.eye(3)[None], np.array([[-4.0, 0.3, 0.0]])), np.array([mg.MKF_PRESENT], dtype=np.int32), np.ones((1, 2), dtype=np.uint8), np.array([[3.0, 4.0]])
+    g.update_mkfs([8], *ninth)
+    for k, v in zip(("base_from_world", "mkf_flags", "kf_active", "kf_depth_mean"), ninth):
+        a[k] = np.concatenate([a[k], v])
+    a = _every_call(t, g, a, rng, [3, 8, 8], [0, 0, 1], 1100)               # (a parcel past the 1024 entries its block starts with)
+    g.close(); t.close()
