@@ -240,6 +240,14 @@ int mcp_chol_debug_factor(const double* A, int n, const double* b, double* L_out
 /* device time (HIP events, ms per solve, first repetition left out) of the factorisation and the back-substitution launches
  * for (A + q I) x_q = b, q < nsys; band > 0: banded + bordered tile plan (i - j <= band, last `band` block rows dense) */
 int mcp_chol_time(const double* A, int n, const double* b, int nsys, int reps, int band, double* ms_factor, double* ms_back, double* x);
+/* factorisation + back-substitution of `runs` batches of `nsys` (<= 4) systems, every system with a matrix of its own, on ONE plan
+ * (test hook): A[runs][nsys][n*n] (row-major, lower triangles read), b[runs][nsys][n].  band as in mcp_chol_time (0 dense, > 0 band +
+ * border, < 0 dissected band with the chains {0, h, ntc + band}); min_ntc: smallest system in tiles the one-launch plan is built for
+ * (the solver's own is 3).  Per run, in order: upload, zero the flags, factor, back-substitute.  x[runs][nsys][n]; fail[runs][4]: the
+ * kernels' flags (2 = not positive definite, 4 = a hand-off timed out); err[runs][4]: the one-launch error words (0 without a
+ * one-launch plan); info[4] = {one-launch plan built and still in use after the last run, its chains, its helpers, tiles per side}.
+ * A raised flag or error word is RETURNED to the caller, it is no error of this call. */
+int mcp_chol_debug_runs(const double* A, int n, const double* b, int nsys, int runs, int band, int min_ntc, double* x, int* fail, int* err, int* info);
 /* the cut of the pose coupling graph Prepare() gives the factorisation its chains with (mcptam_amd/csrc/ba_cut.h; host code, no device
  * needed): adjacency[u*nf + v] != 0 = poses u and v (free poses in add order) couple.  order_out[nf]: position -> pose; segs_out[8]:
  * first tile (32 unknowns = 16/3 poses) of every chain, the separator's last, -1 behind them (segs_out[1] < 0: one chain);

@@ -81,7 +81,7 @@ BA_SYMBOLS = [
     "mcp_ba_num_outliers", "mcp_ba_get_outliers", "mcp_ba_sigma_squared", "mcp_ba_mean_chi_squared", "mcp_ba_max_cov",
     "mcp_ba_lambda", "mcp_ba_num_iter_logs", "mcp_ba_get_iter_logs", "mcp_ba_get_timing", "mcp_ba_set_allreduce",
     "mcp_ba_prepare", "mcp_ba_eval", "mcp_ba_robust_chi2", "mcp_ba_debug_solve", "mcp_dense_spd_solve",
-    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_ba_debug_head", "mcp_ba_debug_trial", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_debug_pose_cut",
+    "mcp_dense_spd_stress", "mcp_ba_debug_system", "mcp_ba_debug_systems", "mcp_ba_debug_structure", "mcp_ba_debug_head", "mcp_ba_debug_trial", "mcp_chol_debug_factor", "mcp_chol_time", "mcp_chol_debug_runs", "mcp_debug_pose_cut",
     "mcp_ba_struct_cache_stats", "mcp_ba_struct_cache_near_hits", "mcp_ba_struct_cache_clear",
     "mcp_comm_unique_id", "mcp_comm_init", "mcp_comm_destroy", "mcp_ba_set_comm", "mcp_comm_allreduce", "mcp_comm_allreduce_lane",
 ]
@@ -127,6 +127,7 @@ def lib():
     L.mcp_debug_pose_cut.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.mcp_chol_time.argtypes = [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, c_double_p]
     L.mcp_dense_spd_stress.argtypes = [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.POINTER(ctypes.c_int)]
+    L.mcp_chol_debug_runs.argtypes = [c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, c_int_p, c_int_p, c_int_p]
     L.mcp_ba_debug_system.argtypes = [ctypes.c_void_p, ctypes.c_double, c_double_p]
     L.mcp_ba_debug_systems.argtypes = [ctypes.c_void_p, ctypes.c_int, c_double_p, c_double_p]
     L.mcp_ba_debug_structure.argtypes = [ctypes.c_void_p, ctypes.POINTER(McpBaStructure)]
@@ -260,6 +261,22 @@ def chol_time(A, b, nsys=1, reps=20, band=0):
     if lib().mcp_chol_time(_dp(A), A.shape[0], _dp(b), int(nsys), int(reps), int(band), ctypes.byref(tf), ctypes.byref(tb), _dp(x)) != 0:
         raise RuntimeError("mcp_chol_time failed: " + last_error())
     return tf.value, tb.value, x
+
+
+def chol_debug_runs(A, b, band=0, min_ntc=3):
+    """`runs` batches of `nsys` systems, each with a matrix of its own, factored and solved one batch after the other on ONE plan (test
+    hook, include/mcp_ba.h): A (runs, nsys, n, n), lower triangles read, b (runs, nsys, n).  Returns (x (runs, nsys, n), fail (runs, 4),
+    err (runs, 4), info = [one-launch plan still in use, chains, helpers, tiles per side]); raised flags are returned, not raised."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if A.ndim != 4 or A.shape[2] != A.shape[3] or b.shape != A.shape[:3]:
+        raise ValueError("chol_debug_runs: A is (runs, nsys, n, n) and b (runs, nsys, n)")
+    runs, nsys, n = b.shape
+    x = np.zeros((runs, nsys, n))
+    fail = np.zeros((runs, 4), dtype=np.int32); err = np.zeros((runs, 4), dtype=np.int32); info = np.zeros(4, dtype=np.int32)
+    if lib().mcp_chol_debug_runs(_dp(A), n, _dp(b), nsys, runs, int(band), int(min_ntc), _dp(x), _ip(fail), _ip(err), _ip(info)) != 0:
+        raise RuntimeError("mcp_chol_debug_runs failed: " + last_error())
+    return x, fail, err, info
 
 
 def dense_spd_stress(A, b, nsys=1, reps=10):

@@ -4448,6 +4448,51 @@ int mcp_chol_time(const double* A, int n, const double* b, int nsys, int reps, i
   return 0;
 }
 
+// `runs` batches of nsys systems, each with a matrix of its own, through ONE plan (test hook): see mcp_ba.h.  What the kernels flag --
+// fail[q], the one-launch error word of system q -- is handed back, never turned into an error return.
+int mcp_chol_debug_runs(const double* A, int n, const double* b, int nsys, int runs, int band, int min_ntc, double* x, int* fail, int* err, int* info) {
+  if (!A || !b || !x || !fail || !err || !info || n <= 0 || n > CH_SOLVE_MAX || nsys < 1 || nsys > MAX_SYS || runs < 1 || min_ntc < 1) { set_err("mcp_chol_debug_runs: bad arguments"); return -1; }
+  const size_t stride = (size_t)n*n + n;
+  DevBuf<double> work; DevBuf<int> f;
+  if (work.alloc(stride*nsys) || f.alloc(4)) return -1;
+  CholPlan plan; plan.persist_min_ntc = min_ntc;
+  std::vector<unsigned char> pattern;
+  const int ntc = (n + CH_NB - 1)/CH_NB;
+  if (band > 0) {
+    pattern.assign((size_t)ntc*ntc, 0);
+    for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (i - j <= band || i >= ntc - band) pattern[(size_t)i*ntc + j] = 1;
+  } else if (band < 0) {      // a dissected band, ordered [left half | right half reversed | the -band blocks between them]: as mcp_chol_time
+    const int bw = -band, h = (ntc - bw)/2;
+    if (n % CH_NB || h < 3 || ntc - bw - h < 3) { set_err("mcp_chol_debug_runs: a dissected band needs whole tiles and halves of at least three"); return -1; }
+    auto orig = [&](int i) { return i < h ? i : (i < ntc - bw ? (ntc - 1) - (i - h) : h + (i - (ntc - bw))); };
+    pattern.assign((size_t)ntc*ntc, 0);
+    for (int i = 0; i < ntc; ++i) for (int j = 0; j <= i; ++j) if (std::abs(orig(i) - orig(j)) <= bw) pattern[(size_t)i*ntc + j] = 1;
+    plan.persist_segs = {0, h, ntc - bw};
+  }
+  if (plan.build(n, pattern)) { set_err("mcp_chol_debug_runs: plan allocation failed"); return -1; }
+  std::vector<double> host(stride*nsys);
+  for (int run = 0; run < runs; ++run) {
+    for (int q = 0; q < nsys; ++q) {
+      const size_t at = (size_t)run*nsys + q;
+      std::memcpy(host.data() + q*stride, A + at*n*n, (size_t)n*n*8);
+      std::memcpy(host.data() + q*stride + (size_t)n*n, b + at*n, (size_t)n*8);
+    }
+    HIPCK(hipMemcpyAsync(work.p, host.data(), stride*nsys*8, hipMemcpyHostToDevice, nullptr));
+    HIPCK(hipMemsetAsync(f.p, 0, 16, nullptr));
+    chol_factor(nullptr, plan, work.p, f.p, nsys, stride);
+    chol_back(nullptr, plan, work.p, nsys, stride);
+    for (int q = 0; q < nsys; ++q) HIPCK(hipMemcpyAsync(x + ((size_t)run*nsys + q)*n, work.p + q*stride + (size_t)n*n, (size_t)n*8, hipMemcpyDeviceToHost, nullptr));
+    HIPCK(hipMemcpyAsync(fail + 4*run, f.p, 16, hipMemcpyDeviceToHost, nullptr));
+    HIPCK(hipStreamSynchronize(nullptr));
+    for (int q = 0; q < 4; ++q) err[4*run + q] = 0;
+    if (plan.use_persist && plan.persist.ok) HIPCK(hipMemcpy(err + 4*run, plan.persist.d_err, 16, hipMemcpyDeviceToHost));
+    if (plan.launch_failed) { set_err(std::string("mcp_chol_debug_runs: launch refused: ") + plan.launch_failed); return -1; }
+  }
+  const bool one = plan.use_persist && plan.persist.ok;
+  info[0] = one ? 1 : 0; info[1] = one ? plan.persist.nseg : 0; info[2] = one ? plan.persist.nhelpers : 0; info[3] = plan.ntc;
+  return 0;
+}
+
 // Dense SPD solve A x = b on the device with the reduced-system kernels (test hook for ba_chol.h)
 int mcp_dense_spd_solve(const double* A, int n, const double* b, double* x) {
   if (n <= 0 || n > CH_SOLVE_MAX) { set_err("mcp_dense_spd_solve: bad n"); return -1; }
