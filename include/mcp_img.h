@@ -452,6 +452,8 @@ typedef struct mcp_stereo_point {      /* one created MapPoint with its two meas
 int mcp_stereo_points(mcp_kf* src, const mcp_camera* src_cam, const double src_cam_from_world[12], int level, int n_cand, const mcp_int2* cand,
                       int n_meas, const mcp_stereo_meas* meas, int n_targets, const mcp_stereo_target* targets, int limit,
                       int cap, mcp_stereo_point* out, uint8_t* keep, uint8_t* outcome);
+/* (mcp_stereo_map_points, at the end of this header with the map graph it writes into, is the form that also leaves the created points in the
+ * map-point table, the graph's point columns and the store, without the host sending them up again) */
 /* The hypotheses of mcp_stereo_points for candidates cand[0..n_cand) against one target, computed by the same device code: hypothesis h of candidate
  * i is out[offsets[i] + h] (offsets: n_cand + 1), as the mcp_td_in the finder sees (world position, pixel vectors of the probe MapPoint, source =
  * src at `level`, center = the candidate).  Returns the total; out == NULL counts only, otherwise total > cap is refused. */
@@ -1235,6 +1237,71 @@ int mcp_map_mkf_cull_host(const mcp_mkf_cull_params*, int ncam, const double* ca
                           const uint8_t* kf_active, const double* kf_depth_mean, int n_rows, int n_point_rows, const int* src_mkf, const int* src_cam,
                           int* point_flags, uint8_t* pending, int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row, uint8_t* ms_alive,
                           mcp_mkf_cull_result*);
+
+/* ---- AddStereoMapPoints into the map: new points and their measurements stay on the device ------- src/MapMakerServerBase.cc:452-496, 855-914
+ * mcp_stereo_points (above) hands every created point back to the host, which then sends the same numbers up again through
+ * mcp_map_points_update, _update_rays, _update_source, mcp_map_graph_update_points and mcp_map_graph_add_meas.  mcp_stereo_map_points is the
+ * one-call form for one source keyframe and level: it creates the points exactly as mcp_stereo_points does -- candidates, targets, limit, keep,
+ * outcome, the created set and its order are that call's, byte for byte -- and leaves each of them in the table's columns, the graph's point
+ * columns and the store, with one host wait.  Rows are the host's to assign, so it hands in a list of free rows and their keys up front:
+ * created point k (creation order) takes rows[k] and keys[k]; the host learns `made` from the one wait.
+ *
+ * BUSY POSITIONS.  busy_from_store = 1: ThinCandidates' measurement list is every live store entry with (mkf, cam) == (src_mkf, src_cam), as
+ * {uv, level}, gathered on the device in store order (per-workgroup counts, then ranks by index: deterministic); n_busy is its length; the level
+ * filter (level, level + 1) stays in the thinning; meas / n_meas must be NULL / 0.  busy_from_store = 0: the caller's meas[], n_busy = n_meas.
+ *
+ * APPEND.  Row rows[k] holds afterwards what the five calls above would have written for point k: world_pos / pixel_right_w / pixel_down_w
+ * from the record, usable 0 (mbOptimized is false until an adjustment); the patch rays; the source src at `level`, centre = the candidate's
+ * level position, fixed 0, key keys[k] -- and, as a key change does in mcp_map_points_update_source, every camera's finder state of the row
+ * zeroed when the key differs from the row's; the graph columns (src_mkf, src_cam, flags 0), pending mark cleared.  It also holds the counts
+ * (1, 0) of a MapPoint that has just been constructed, which a fresh row has anyway and the owner of the table sets for a recycled one.  Two
+ * store entries follow, in the order of the reference's AddMeasurement calls (:901-902), t = the record's target:
+ *   first_store + 2k      {root_pos,   src_mkf,       src_cam,       rows[k], level, MCP_SRC_ROOT,     alive}
+ *   first_store + 2k + 1  {target_pos, target_mkf[t], target_cam[t], rows[k], level, MCP_SRC_EPIPOLAR, alive}
+ * Rows rows[made .. n_rows) are untouched and stay the caller's.  out, when not NULL, receives the records as mcp_stereo_points returns them.
+ * As with mcp_map_graph_add_meas, the caller guarantees that no live store entry names a row it hands in.
+ *
+ * SHAPE.  Before anything is enqueued the table is grown to cover the largest row, the rays column is switched on, the graph's point columns
+ * are grown and the store is grown by 2 * n_rows (through the graph's grow-when-idle rule).  The whole submission goes on the TABLE's stream,
+ * behind an event recorded on the source keyframe's stream (as mcp_track_map reads keyframes); the scratch is the source's, the busy list the
+ * graph's.  [busy_from_store: k_sa_busy_mark, k_sa_busy_gather, k_sa_thin_busy | k_stereo_thin_meas], per target [k_stereo_thin_new,]
+ * k_stereo_walk, k_stereo_commit -- mcp_stereo_points' kernels, unchanged -- then k_sa_append (one thread per created point, the record read
+ * once from the pinned block) and ONE wait; a later call on the table's stream sees whole rows.  After the wait the host's mirrors follow for
+ * rows[0 .. made): has_rays, the source-slot reference counts, the store's length (+ 2 * made).  Returns made.  With n_cand == 0 there is
+ * nothing to thin or create: the arguments are checked, nothing is enqueued, made = 0 (and n_busy = 0 with busy_from_store: no gather ran).
+ * REFUSALS (-1, mcp_last_error() starting "mcp_stereo_map_points:", nothing enqueued, table / graph / store unchanged): everything
+ * mcp_stereo_points refuses; NULL graph / params / result; src on another device than the table; src_mkf or a target_mkf[t] that is not a present
+ * slot; src_cam or a target_cam[t] outside the rig; n_rows < n_cand; a negative or duplicate row; NULL rows / keys with n_cand > 0; NULL
+ * target_mkf / target_cam with n_targets > 0; meas given together with busy_from_store; a store that would pass INT_MAX. */
+typedef struct mcp_stereo_map_params {
+  int src_mkf, src_cam;        /* the source keyframe as the graph names it: MKF slot, camera index */
+  int limit;                   /* nLimit, as mcp_stereo_points */
+  int busy_from_store;         /* 1: ThinCandidates' measurement list is gathered from the store; 0: the caller's meas[] */
+} mcp_stereo_map_params;
+typedef struct mcp_stereo_map_result { int made, first_store, n_busy; } mcp_stereo_map_result;
+int mcp_stereo_map_points(mcp_map_graph*, mcp_kf* src, const mcp_camera* src_cam, const double src_cam_from_world[12], int level,
+                          int n_cand, const mcp_int2* cand, int n_meas, const mcp_stereo_meas* meas,
+                          int n_targets, const mcp_stereo_target* targets, const int* target_mkf, const int* target_cam,
+                          int n_rows, const int* rows, const int* keys,
+                          const mcp_stereo_map_params*, mcp_stereo_map_result*,
+                          mcp_stereo_point* out /* NULL or n_cand */, uint8_t* keep, uint8_t* outcome /* NULL or n_targets x n_cand */);
+/* the two halves from host arrays, by the same bodies under the host compiler: they need no device and give the device's bytes.
+ * mcp_stereo_busy_host: the busy list of a store, in store order.  cap = 0: counts only; otherwise out has room for cap records and a longer list
+ * is refused.  Returns the length.
+ * mcp_stereo_append_host: created points pts[0 .. made) into per-point arrays (world_pos, pixel_right_w, pixel_down_w: made x 3; rays: made x 9;
+ * center_xy: made x 2; the graph columns: made) and their 2 x made store entries.  Returns first_store + 2 * made, the store's length afterwards. */
+int mcp_stereo_busy_host(int n_store, const mcp_store_entry* store, int src_mkf, int src_cam, int cap, mcp_stereo_meas* out);
+int mcp_stereo_append_host(int made, const mcp_stereo_point* pts, const int* rows, int level, int src_mkf, int src_cam,
+                           const int* target_mkf, const int* target_cam, int first_store,
+                           double* world_pos, double* pixel_right_w, double* pixel_down_w, double* rays /* made x 9 */,
+                           int* center_xy, int* gp_src_mkf, int* gp_src_cam, int* gp_flags, mcp_store_entry* appended /* 2 x made */);
+/* read-backs of rows first .. first+count-1 (every output pointer may be NULL: it is skipped); each waits for the table's stream, as
+ * mcp_map_points_get does.  rays: count x 9 (zeros for a row without), has: the host's record of which rows have rays.  source: the row's key,
+ * level, centre (count x 2), fixed byte and whether it names a source keyframe.  gp: the graph's point columns; a row they do not cover yet
+ * reads as never written (-1, 0, MCP_GP_BAD). */
+int mcp_map_points_get_rays(const mcp_map_points*, int first, int count, double* rays /* count x 9 */, uint8_t* has);
+int mcp_map_points_get_source(const mcp_map_points*, int first, int count, int* keys, int* source_level, int* center_xy, uint8_t* fixed, uint8_t* has_source);
+int mcp_map_gp_get(mcp_map_graph*, int first, int count, int* src_mkf, int* src_cam, int* flags);
 
 #ifdef __cplusplus
 }

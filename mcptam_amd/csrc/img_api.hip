@@ -34,6 +34,7 @@
 #include "map_graph_parcel.h"
 #include "map_graph_cull.h"
 #include "map_graph_neigh.h"
+#include "stereo_append.h"
 
 using namespace mcp;
 
@@ -2714,6 +2715,9 @@ struct mcp_map_graph {
     Buf<double> dist; Buf<uint8_t> cand; Buf<MgnCtl> ctl; Buf<mcp_neigh_result> res; Buf<MgMkf> ext; Buf<MgnCull> cc; PinBuf<char> out;
     MgTimer t_query, t_remove;
   } neigh;
+  // mcp_stereo_map_points (stereo_append.h): the source keyframe's busy list gathered from the store, its length (device, pinned).  The rows, keys
+  // and target slots go up through `up`, the per-workgroup counts through `blk`.
+  struct Stereo { Buf<mcp_stereo_meas> busy; Buf<int> n_busy; PinBuf<int> h_n_busy; } stereo;
   using Guard = Grow<mcp_map_graph>;
   ~mcp_map_graph() {                                  // (the timers destroy their events after this wait)
     if (m && m->st) (void)hipStreamSynchronize(m->st);
@@ -3836,6 +3840,176 @@ int mcp_map_mkf_cull(mcp_map_graph* g, const mcp_mkf_cull_params* p, mcp_mkf_cul
 int mcp_map_mkf_cull_last_timing(const mcp_map_graph* g, double* device_ms) {
   if (!g || !device_ms) return img_fail("mcp_map_mkf_cull_last_timing: bad arguments");
   return g->neigh.t_remove.ms(device_ms);
+}
+
+}  // extern "C"
+
+// ---- AddStereoMapPoints into the map (include/mcp_img.h mcp_stereo_map_points; stereo_kernels.h, stereo_append.h) ----------------------------
+namespace {
+// one reference on the source keyframe's slot for the length of the call: the rows' own references are taken after the wait, once `made` is known
+struct SlotHold { mcp_map_points* m; int slot1; ~SlotHold() { m->slot_release(slot1); } };
+}  // namespace
+
+extern "C" {
+
+int mcp_stereo_map_points(mcp_map_graph* g, mcp_kf* src, const mcp_camera* src_cam, const double src_cfw[12], int level, int n_cand, const mcp_int2* cand,
+                          int n_meas, const mcp_stereo_meas* meas, int n_targets, const mcp_stereo_target* targets, const int* target_mkf, const int* target_cam,
+                          int n_rows, const int* rows, const int* keys, const mcp_stereo_map_params* prm, mcp_stereo_map_result* res,
+                          mcp_stereo_point* out, uint8_t* keep, uint8_t* outcome) {
+  static const char* W = "mcp_stereo_map_points";
+  const std::string who = W;
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!prm || !res) return img_fail(who + ": NULL params or result");
+  if (stereo_check_source(W, src, src_cam, src_cfw, level, n_cand, cand)) return -1;
+  if (n_meas < 0 || (n_meas > 0 && !meas) || n_targets < 0 || (n_targets > 0 && (!targets || !target_mkf || !target_cam))) return img_fail(who + ": negative count or missing array");
+  const bool from_store = prm->busy_from_store != 0;
+  if (from_store && (meas || n_meas)) return img_fail(who + ": meas given together with busy_from_store");
+  if (n_cand > 0 && !keep) return img_fail(who + ": keep is needed");
+  for (int k = 0; k < n_meas; ++k)
+    if (!std::isfinite(meas[k].root_pos[0]) || !std::isfinite(meas[k].root_pos[1]) || std::fabs(meas[k].root_pos[0]) > 1e9 || std::fabs(meas[k].root_pos[1]) > 1e9)
+      return img_fail(who + ": a measurement with a non-finite or huge root position");
+  mcp_map_points* m = g->m;
+  if (src->device != m->device) return img_fail(who + ": the source is on device " + std::to_string(src->device) + ", the table on device " + std::to_string(m->device));
+  if (!g->mirror.present(prm->src_mkf)) return img_fail(who + ": the source names MKF slot " + std::to_string(prm->src_mkf) + ", which is not present");
+  if (prm->src_cam < 0 || prm->src_cam >= g->rig.ncam) return img_fail(who + ": the source names camera " + std::to_string(prm->src_cam));
+  std::vector<StereoTargetDev> tab(std::max(n_targets, 1));
+  for (int t = 0; t < n_targets; ++t) {
+    if (stereo_target_dev(W, src, targets[t], tab[t])) return -1;
+    if (!g->mirror.present(target_mkf[t])) return img_fail(who + ": target " + std::to_string(t) + " names MKF slot " + std::to_string(target_mkf[t]) + ", which is not present");
+    if (target_cam[t] < 0 || target_cam[t] >= g->rig.ncam) return img_fail(who + ": target " + std::to_string(t) + " names camera " + std::to_string(target_cam[t]));
+  }
+  if (n_rows < n_cand) return img_fail(who + ": n_rows < n_cand");
+  if (n_rows > 0 && (!rows || !keys)) return img_fail(who + ": rows and keys are needed");
+  int top = m->rows;
+  for (int k = 0; k < n_rows; ++k) { if (rows[k] < 0 || rows[k] == 0x7fffffff) return img_fail(who + ": bad row id"); top = std::max(top, rows[k] + 1); }
+  if (n_rows && mg_distinct(g->sorted_ids, rows, n_rows, who, "row")) return -1;
+  const int first = g->n_store;
+  if ((long long)first + 2LL*n_rows > 0x7fffffffLL) return img_fail(who + ": the store is full");
+  res->made = 0; res->first_store = first; res->n_busy = from_store ? 0 : n_meas;
+  if (n_cand == 0) return 0;                           // (nothing to thin, nothing to create: nothing is enqueued)
+
+  ICK(hipSetDevice(m->device));
+  const size_t nto = (size_t)std::max(n_targets, 1)*n_cand;
+  if (src->st_tab.alloc(std::max(n_targets, 1)) || src->st_cand.alloc(n_cand) || src->st_meas.alloc(std::max(n_meas, 1)) || src->st_alive.alloc(n_cand) ||
+      src->st_outcome.alloc(nto) || src->st_res.alloc(n_cand) || src->st_counts.alloc(n_targets + 1) || src->h_st_out.alloc(n_cand) ||
+      src->h_st_counts.alloc(n_targets + 1) || src->h_st_keep.alloc(n_cand) || src->h_st_outcome.alloc(nto)) return -1;
+  // the table's columns, then the graph's blocks; each grows with nothing in flight on the block it replaces
+  if (m->grow(top) || m->ensure(m->rays)) return -1;
+  const int n_store = first, nblk = mg_grid(n_store);
+  const size_t o_keys = tm_align(sizeof(int)*(size_t)n_rows), o_tmkf = 2*o_keys, o_tcam = o_tmkf + tm_align(sizeof(int)*(size_t)std::max(n_targets, 1)),
+               up = o_tcam + tm_align(sizeof(int)*(size_t)std::max(n_targets, 1));
+  mcp_map_graph::Stereo& sg = g->stereo;
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, up) || G.grow(sg.n_busy, 1) || G.grow(sg.h_n_busy, 1) || (from_store && (G.grow(sg.busy, n_store) || G.grow(g->blk, nblk))) ||
+      g->grow_points(G, m->rows) || g->grow_store(G, (size_t)first + 2*(size_t)n_rows)) return -1;
+  std::memset(g->up.in.p, 0, up);
+  std::memcpy(g->up.in.p, rows, sizeof(int)*(size_t)n_rows); std::memcpy(g->up.in.p + o_keys, keys, sizeof(int)*(size_t)n_rows);
+  if (n_targets) { std::memcpy(g->up.in.p + o_tmkf, target_mkf, sizeof(int)*(size_t)n_targets); std::memcpy(g->up.in.p + o_tcam, target_cam, sizeof(int)*(size_t)n_targets); }
+  SlotHold hold{m, m->slot_acquire(std::make_pair((const mcp_kf*)src, kf_live_serial(src)))};
+
+  StereoSrcDev S; S.cam = *src_cam; S.cfw = se3_of12(src_cfw);
+  S.img = src->lev[level].img.p; S.w = src->lev[level].w; S.h = src->lev[level].h; S.level = level;
+  hipStream_t st = m->st;
+  Drain drain{m, true};
+  // the table's stream waits for whatever the source's stream still has to write of its frame
+  ICK(hipEventRecord(src->ev, src->st));
+  ICK(hipStreamWaitEvent(st, src->ev, 0));
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, up, hipMemcpyHostToDevice, st));
+  if (n_targets) ICK(hipMemcpyAsync(src->st_tab.p, tab.data(), sizeof(StereoTargetDev)*(size_t)n_targets, hipMemcpyHostToDevice, st));
+  ICK(hipMemcpyAsync(src->st_cand.p, cand, sizeof(mcp_int2)*(size_t)n_cand, hipMemcpyHostToDevice, st));
+  if (n_meas) ICK(hipMemcpyAsync(src->st_meas.p, meas, sizeof(mcp_stereo_meas)*(size_t)n_meas, hipMemcpyHostToDevice, st));
+  ICK(hipMemsetAsync(src->st_counts.p, 0, sizeof(int)*(size_t)(n_targets + 1), st));
+  const int nb = (n_cand + 255)/256;
+  if (from_store) {
+    const mcp_store_entry* store = reinterpret_cast<const mcp_store_entry*>(g->store.p);
+    if (n_store) hipLaunchKernelGGL(k_sa_busy_mark, dim3(nblk), dim3(SA_BLOCK), 0, st, store, n_store, prm->src_mkf, prm->src_cam, g->blk.p);
+    hipLaunchKernelGGL(k_sa_busy_gather, dim3(mg_grid1(n_store)), dim3(SA_BLOCK), 0, st, store, n_store, nblk, (const int*)g->blk.p, prm->src_mkf, prm->src_cam, sg.busy.p,
+                       n_store, sg.n_busy.p);
+    hipLaunchKernelGGL(k_sa_thin_busy, dim3(nb), dim3(256), 0, st, n_cand, (const mcp_int2*)src->st_cand.p, (const int*)sg.n_busy.p, n_store, (const mcp_stereo_meas*)sg.busy.p,
+                       level, src->st_alive.p);
+    ICK(hipMemcpyAsync(sg.h_n_busy.p, sg.n_busy.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  } else
+    hipLaunchKernelGGL(k_stereo_thin_meas, dim3(nb), dim3(256), 0, st, n_cand, (const mcp_int2*)src->st_cand.p, n_meas, (const mcp_stereo_meas*)src->st_meas.p,
+                       level, src->st_alive.p);
+  for (int j = 0; j < n_targets; ++j) {
+    if (j > 0)
+      hipLaunchKernelGGL(k_stereo_thin_new, dim3(nb), dim3(256), 0, st, j, n_cand, (const mcp_int2*)src->st_cand.p, level, (const int*)src->st_counts.p,
+                         (const mcp_stereo_point*)src->h_st_out.p, src->st_alive.p);
+    hipLaunchKernelGGL(k_stereo_walk, dim3(n_cand), dim3(64), 0, st, S, (const StereoTargetDev*)src->st_tab.p, j, n_cand, (const mcp_int2*)src->st_cand.p,
+                       (const uint8_t*)src->st_alive.p, src->st_res.p, src->st_outcome.p);
+    hipLaunchKernelGGL(k_stereo_commit, dim3(1), dim3(STEREO_COMMIT_NT), 0, st, j, n_cand, prm->limit, (const uint8_t*)src->st_alive.p, src->st_outcome.p,
+                       (const mcp_stereo_point*)src->st_res.p, src->st_counts.p, src->h_st_out.p);
+  }
+  if (n_targets) {
+    SaAppend Q; Q.n_targets = n_targets; Q.n_rows = n_rows; Q.level = level; Q.src_mkf = prm->src_mkf; Q.src_cam = prm->src_cam; Q.slot1 = hold.slot1; Q.first_store = first;
+    Q.table_rows = m->rows; Q.graph_rows = g->prow; Q.ncam_states = m->st_ncam; Q.store_cap = (long long)g->store.n;
+    const char* d = g->up.dev.p;
+    hipLaunchKernelGGL(k_sa_append, dim3(mg_grid(n_cand)), dim3(SA_BLOCK), 0, st, Q, (const int*)src->st_counts.p, (const mcp_stereo_point*)src->h_st_out.p, (const int*)d,
+                       (const int*)(d + o_keys), (const int*)(d + o_tmkf), (const int*)(d + o_tcam), m->pts.row(), m->src.row(), m->state_ptrs(), m->cnt.row(), m->rays.row(),
+                       g->pts.p, reinterpret_cast<mcp_store_entry*>(g->store.p));
+  }
+  ICK(hipGetLastError());
+  if (g->staged_now()) return -1;
+  ICK(hipMemcpyAsync(src->h_st_counts.p, src->st_counts.p, sizeof(int)*(size_t)(n_targets + 1), hipMemcpyDeviceToHost, st));
+  ICK(hipMemcpyAsync(src->h_st_keep.p, src->st_alive.p, (size_t)n_cand, hipMemcpyDeviceToHost, st));
+  if (outcome && n_targets) ICK(hipMemcpyAsync(src->h_st_outcome.p, src->st_outcome.p, (size_t)n_targets*n_cand, hipMemcpyDeviceToHost, st));
+  if (g->one_wait(drain)) return -1;
+  const int made = src->h_st_counts.p[n_targets];
+  if (made < 0 || made > n_cand) return img_fail(who + ": inconsistent device count");
+  if (out) std::memcpy(out, src->h_st_out.p, sizeof(mcp_stereo_point)*(size_t)made);
+  std::memcpy(keep, src->h_st_keep.p, (size_t)n_cand);
+  if (outcome && n_targets) std::memcpy(outcome, src->h_st_outcome.p, (size_t)n_targets*n_cand);
+  // the host's mirrors of the rows that were taken
+  const std::pair<const mcp_kf*, unsigned long long> id = m->slots[hold.slot1 - 1];
+  for (int k = 0; k < made; ++k) {
+    const int row = rows[k];
+    m->has_rays[row] = 1;
+    const int s1 = m->slot_acquire(id);                  // (before the release: a row that keeps its source keeps the slot)
+    m->slot_release(m->row_slot[row]);
+    m->row_slot[row] = s1;
+  }
+  g->n_store += 2*made; g->n_live += 2*made;
+  res->made = made; res->n_busy = from_store ? *sg.h_n_busy.p : n_meas;
+  return made;
+}
+
+int mcp_map_points_get_rays(const mcp_map_points* m, int first, int count, double* rays, uint8_t* has) {
+  std::vector<char> bounce;                              // (rays == NULL: the read still waits for the stream)
+  if (column_get(m, "mcp_map_points_get_rays", m ? &m->rays : nullptr, first, count, rays, &bounce)) return -1;
+  for (int k = 0; k < count; ++k) {                      // (the column is created without a fill: a row that was never given rays reads as zeros)
+    const uint8_t h = m->has_rays[(size_t)first + k];
+    if (has) has[k] = h;
+    if (rays && !h) std::memset(rays + 9*(size_t)k, 0, 72);
+  }
+  return 0;
+}
+
+int mcp_map_points_get_source(const mcp_map_points* m, int first, int count, int* keys, int* source_level, int* center_xy, uint8_t* fixed, uint8_t* has_source) {
+  std::vector<char> bounce;
+  if (column_get(m, "mcp_map_points_get_source", m ? &m->src : nullptr, first, count, nullptr, &bounce)) return -1;
+  const TmSrc* h = reinterpret_cast<const TmSrc*>(bounce.data());
+  for (int k = 0; k < count; ++k) {
+    if (keys) keys[k] = h[k].key; if (source_level) source_level[k] = h[k].level;
+    if (center_xy) { center_xy[2*(size_t)k] = h[k].cx; center_xy[2*(size_t)k + 1] = h[k].cy; }
+    if (fixed) fixed[k] = h[k].fixed ? 1 : 0; if (has_source) has_source[k] = h[k].slot1 ? 1 : 0;
+  }
+  return 0;
+}
+
+int mcp_map_gp_get(mcp_map_graph* g, int first, int count, int* src_mkf, int* src_cam, int* flags) {
+  if (!g) return img_fail("mcp_map_gp_get: NULL graph");
+  if (first < 0 || count < 0 || (long long)first + count > g->m->rows) return img_fail("mcp_map_gp_get: bad range");
+  if (count == 0) return 0;
+  ICK(hipSetDevice(g->m->device));
+  const int covered = std::max(0, std::min(count, g->prow - first));
+  std::vector<MgPoint> tmp;
+  if (covered > 0 ? g->read_back(tmp, (const MgPoint*)(g->pts.p + first), (size_t)covered) : g->sync()) return -1;
+  for (int k = 0; k < count; ++k) {
+    MgPoint P; P.src_mkf = -1; P.src_cam = 0; P.flags = MCP_GP_BAD; P.pending = 0;      // (k_mg_points_fill's row)
+    if (k < covered) P = tmp[k];
+    if (src_mkf) src_mkf[k] = P.src_mkf; if (src_cam) src_cam[k] = P.src_cam; if (flags) flags[k] = P.flags;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -1016,6 +1016,22 @@ class MapGraph:
         s = np.zeros(n, dtype=np.int32) if source is None else _i32(source, (n,))
         return _chk(self._L.mcp_map_graph_add_meas(self._h, n, m.ctypes.data, c.ctypes.data, r.ctypes.data, u.ctypes.data, l.ctypes.data, s.ctypes.data), "map_graph_add_meas")
 
+    def get_points(self, first=0, count=None):
+        """mcp_map_gp_get: the point columns of rows first .. first+count-1 read back, dict(src_mkf, src_cam, flags); a row they do not cover yet
+        reads as never written (-1, 0, GP_BAD)."""
+        from .stereo import lib as _stereo_lib
+        count = self.table.rows - first if count is None else int(count)
+        n = max(count, 1)
+        o = dict(src_mkf=np.zeros(n, np.int32), src_cam=np.zeros(n, np.int32), flags=np.zeros(n, np.int32))
+        _chk(_stereo_lib().mcp_map_gp_get(self._h, int(first), count, *[o[k].ctypes.data for k in ("src_mkf", "src_cam", "flags")]), "map_gp_get")
+        return {k: v[:count] for k, v in o.items()}
+
+    def add_stereo_points(self, src, src_cam, src_pose, level, cand, targets, target_mkf, target_cam, rows, keys, src_mkf, src_cam_index, **kw):
+        """mcp_stereo_map_points: AddStereoMapPoints of one source keyframe and level whose created points take rows[k] / keys[k] of the table and
+        two entries of the store on the device -- see mcptam_amd.stereo.stereo_map_points, whose result it returns."""
+        from .stereo import stereo_map_points
+        return stereo_map_points(self, src, src_cam, src_pose, level, cand, targets, target_mkf, target_cam, rows, keys, src_mkf, src_cam_index, **kw)
+
     def erase_meas(self, mkf, cam, row):
         """KeyFrame::EraseMeasurementOfPoint for distinct keys; returns how many live entries died."""
         m = _i32(mkf)

@@ -199,6 +199,24 @@ class MapPointTable:
         _chk(L.mcp_map_points_get(self._h, int(first), count, wp.ctypes.data, pr.ctypes.data, pd.ctypes.data, us.ctypes.data), "map_points_get")
         return wp, pr, pd, us
 
+    def get_rays(self, first=0, count=None):
+        """Patch rays of rows first .. first+count-1 read back: (rays (count, 9): center, one right, one down; has: which rows have them)."""
+        from .stereo import lib as _stereo_lib
+        count = self.rows - first if count is None else int(count)
+        rays, has = np.zeros((max(count, 1), 9)), np.zeros(max(count, 1), dtype=np.uint8)
+        _chk(_stereo_lib().mcp_map_points_get_rays(self._h, int(first), count, rays.ctypes.data, has.ctypes.data), "map_points_get_rays")
+        return rays[:count], has[:count]
+
+    def get_source(self, first=0, count=None):
+        """The source column of rows first .. first+count-1 read back: dict(key, level, center (count, 2), fixed, has_source)."""
+        from .stereo import lib as _stereo_lib
+        count = self.rows - first if count is None else int(count)
+        n = max(count, 1)
+        o = dict(key=np.zeros(n, np.int32), level=np.zeros(n, np.int32), center=np.zeros((n, 2), np.int32), fixed=np.zeros(n, np.uint8), has_source=np.zeros(n, np.uint8))
+        _chk(_stereo_lib().mcp_map_points_get_source(self._h, int(first), count, *[o[k].ctypes.data for k in ("key", "level", "center", "fixed", "has_source")]),
+             "map_points_get_source")
+        return {k: v[:count] for k, v in o.items()}
+
     def last_timing(self):
         """Device milliseconds of the last write_back / scene_depth on this table: dict(copy, points, depth)."""
         L = _bind_write_back(self._L)

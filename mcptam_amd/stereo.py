@@ -1,6 +1,10 @@
 """MapMakerServerBase::AddStereoMapPoints of one source keyframe and level on the GPU (include/mcp_img.h mcp_stereo_points), its hypothesis
 export (mcp_stereo_hypotheses), and numpy restatements of the pieces the device runs -- ThinCandidates, the epipolar arc, the ambiguity rules,
-ReprojectPoint -- with which the tests compose the same result from existing calls.  src/MapMakerServerBase.cc:123-143, 411-496, 604-918."""
+ReprojectPoint -- with which the tests compose the same result from existing calls.  src/MapMakerServerBase.cc:123-143, 411-496, 604-918.
+
+stereo_map_points (mcp_stereo_map_points) is the form whose created points stay on the device, in the rows of a MapPointTable and the store of its
+MapGraph; stereo_busy_host / stereo_append_host are its two host twins (no device) and stereo_busy_ref / stereo_append_ref the numpy restatements
+of the busy list it gathers from the store and of what a created point becomes in the map (:855-914)."""
 import ctypes
 import math
 
@@ -12,7 +16,21 @@ from . import keyframe as K
 THINNED, NO_ARC, NO_MATCH, TOO_MANY, INDEX_FAR, NO_SUBPIX, CREATED, PAST_LIMIT = range(1, 9)
 OUTCOME_NAMES = {THINNED: "THINNED", NO_ARC: "NO_ARC", NO_MATCH: "NO_MATCH", TOO_MANY: "TOO_MANY", INDEX_FAR: "INDEX_FAR", NO_SUBPIX: "NO_SUBPIX",
                  CREATED: "CREATED", PAST_LIMIT: "PAST_LIMIT"}
-STEREO_SYMBOLS = ["mcp_stereo_points", "mcp_stereo_hypotheses"]
+STEREO_SYMBOLS = ["mcp_stereo_points", "mcp_stereo_hypotheses", "mcp_stereo_map_points", "mcp_stereo_busy_host", "mcp_stereo_append_host",
+                  "mcp_map_points_get_rays", "mcp_map_points_get_source", "mcp_map_gp_get"]
+SRC_ROOT, SRC_EPIPOLAR = 2, 4                 # Measurement::eSource of a created point's two measurements (include/mcp_img.h MCP_SRC_*)
+BUSY_BLOCK = 256                              # stereo_append.h: store entries of a workgroup of the busy gather
+
+
+class StereoMapParams(ctypes.Structure):
+    _fields_ = [("src_mkf", ctypes.c_int), ("src_cam", ctypes.c_int), ("limit", ctypes.c_int), ("busy_from_store", ctypes.c_int)]
+
+
+class StereoMapResult(ctypes.Structure):
+    _fields_ = [("made", ctypes.c_int), ("first_store", ctypes.c_int), ("n_busy", ctypes.c_int)]
+
+    def as_dict(self):
+        return dict(made=self.made, first_store=self.first_store, n_busy=self.n_busy)
 
 
 class StereoTarget(ctypes.Structure):
@@ -51,6 +69,14 @@ def lib():
         L.mcp_stereo_points.restype = ip
         L.mcp_stereo_hypotheses.argtypes = [vp, vp, vp, ip, ip, vp, vp, ip, vp, vp]
         L.mcp_stereo_hypotheses.restype = ip
+        L.mcp_stereo_map_points.argtypes = [vp, vp, vp, vp, ip, ip, vp, ip, vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
+        L.mcp_stereo_busy_host.argtypes = [ip, vp, ip, ip, ip, vp]
+        L.mcp_stereo_append_host.argtypes = [ip, vp, vp, ip, ip, ip, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.mcp_map_points_get_rays.argtypes = [vp, ip, ip, vp, vp]
+        L.mcp_map_points_get_source.argtypes = [vp, ip, ip, vp, vp, vp, vp, vp]
+        L.mcp_map_gp_get.argtypes = [vp, ip, ip, vp, vp, vp]
+        for n in STEREO_SYMBOLS[2:]:
+            getattr(L, n).restype = ip
         _BOUND = True
     return L
 
@@ -129,6 +155,119 @@ def stereo_hypotheses(src, src_cam, src_pose, level, cand, target):
             raise RuntimeError("mcp_stereo_hypotheses failed: " + _cb.last_error())
     del keep_cams
     return out[:tot], off
+
+
+# ---- AddStereoMapPoints into the map (include/mcp_img.h mcp_stereo_map_points): the call, its host twins, its numpy restatements ----------------
+def _store_dtype():
+    from .map_graph import STORE_ENTRY_DTYPE
+    return STORE_ENTRY_DTYPE
+
+
+def stereo_map_points(graph, src, src_cam, src_pose, level, cand, targets, target_mkf, target_cam, rows, keys, src_mkf, src_cam_index, limit=1 << 30,
+                      meas=None, busy_from_store=None, outcomes=True, want_points=True):
+    """mcp_stereo_map_points: mcp_stereo_points of one source keyframe and level whose created points stay on the device -- point k (creation order)
+    takes rows[k] / keys[k] of graph.table and two entries of the graph's store.  targets as for stereo_points, target_mkf / target_cam their MKF
+    slots and camera indices; busy_from_store defaults to `no meas given`.  Returns (points or None, keep mask, outcome or None, dict(made,
+    first_store, n_busy))."""
+    L = lib()
+    c = _cand(cand)
+    n = len(c)
+    busy_from_store = meas is None if busy_from_store is None else bool(busy_from_store)
+    tab, keep_cams = _targets(targets)
+    tm, tc = np.ascontiguousarray(target_mkf, dtype=np.int32), np.ascontiguousarray(target_cam, dtype=np.int32)
+    r, k = np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(keys, dtype=np.int32)
+    if len(tm) != len(targets) or len(tc) != len(targets) or len(r) != len(k):
+        raise ValueError("stereo_map_points: lengths differ")
+    cs = src_cam.to_struct()
+    sp = _pose12(src_pose)
+    out = np.zeros(max(n, 1), dtype=STEREO_POINT_DTYPE) if want_points else None
+    keep = np.zeros(max(n, 1), dtype=np.uint8)
+    oc = np.zeros((max(len(targets), 1), max(n, 1)), dtype=np.uint8) if outcomes else None
+    prm, res = StereoMapParams(int(src_mkf), int(src_cam_index), int(limit), 1 if busy_from_store else 0), StereoMapResult()
+    rc = L.mcp_stereo_map_points(graph._h, src._h if src is not None else None, ctypes.addressof(cs), sp.ctypes.data, int(level), n, c.ctypes.data if n else None,
+                                 0 if meas is None else len(meas), None if meas is None or len(meas) == 0 else meas.ctypes.data,
+                                 len(targets), ctypes.addressof(tab) if len(targets) else None, tm.ctypes.data if len(tm) else None, tc.ctypes.data if len(tc) else None,
+                                 len(r), r.ctypes.data if len(r) else None, k.ctypes.data if len(k) else None, ctypes.addressof(prm), ctypes.addressof(res),
+                                 out.ctypes.data if out is not None else None, keep.ctypes.data, oc.ctypes.data if oc is not None else None)
+    if rc < 0:
+        raise RuntimeError("mcp_stereo_map_points failed: " + _cb.last_error())
+    del keep_cams
+    if oc is not None:
+        oc = oc[:len(targets), :n]
+    return (out[:rc].copy() if out is not None else None), keep[:n].astype(bool), oc, res.as_dict()
+
+
+def stereo_busy_ref(store, src_mkf, src_cam):
+    """ThinCandidates' measurement list of the keyframe (src_mkf, src_cam) as the store holds it: every live entry of it, in store order, every
+    level (the thinning filters).  store: STORE_ENTRY_DTYPE.  Returns STEREO_MEAS_DTYPE."""
+    s = np.asarray(store, dtype=_store_dtype())
+    hit = np.flatnonzero((s["alive"] != 0) & (s["mkf"] == src_mkf) & (s["cam"] == src_cam))
+    out = np.zeros(len(hit), dtype=STEREO_MEAS_DTYPE)
+    out["root_pos"], out["level"] = s["uv"][hit], s["level"][hit]
+    return out
+
+
+def stereo_busy_host(store, src_mkf, src_cam):
+    """mcp_stereo_busy_host: the same list by the body the gather kernel calls, under the host compiler.  Needs no device."""
+    s = np.ascontiguousarray(store, dtype=_store_dtype())
+    L = lib()
+    n = L.mcp_stereo_busy_host(len(s), s.ctypes.data if len(s) else None, int(src_mkf), int(src_cam), 0, None)
+    if n < 0:
+        raise RuntimeError("mcp_stereo_busy_host failed: " + _cb.last_error())
+    out = np.zeros(max(n, 1), dtype=STEREO_MEAS_DTYPE)
+    if n and L.mcp_stereo_busy_host(len(s), s.ctypes.data, int(src_mkf), int(src_cam), n, out.ctypes.data) != n:
+        raise RuntimeError("mcp_stereo_busy_host failed: " + _cb.last_error())
+    return out[:n]
+
+
+def _append_args(pts, rows, target_mkf, target_cam):
+    p = np.ascontiguousarray(pts, dtype=STEREO_POINT_DTYPE)
+    r = np.ascontiguousarray(rows, dtype=np.int32)[:len(p)]
+    if len(r) != len(p):
+        raise ValueError("stereo_append: fewer rows than points")
+    return p, r, np.ascontiguousarray(target_mkf, dtype=np.int32), np.ascontiguousarray(target_cam, dtype=np.int32)
+
+
+def stereo_append_ref(pts, rows, level, src_mkf, src_cam, target_mkf, target_cam, first_store=0):
+    """What created points pts (STEREO_POINT_DTYPE, creation order) become in the map (src/MapMakerServerBase.cc:855-914): per point the table's
+    columns (world_pos, pixel_right_w, pixel_down_w, usable 0, counts (1, 0), rays, the source's level / centre / fixed 0), the graph's columns
+    (src_mkf, src_cam, flags 0) and two store entries -- the source's SRC_ROOT, then the target's SRC_EPIPOLAR -- at first_store + 2k.  Returns a
+    dict of arrays; `store_end` is the store's length afterwards."""
+    p, r, tm, tc = _append_args(pts, rows, target_mkf, target_cam)
+    n = len(p)
+    if n and (p["target"].min() < 0 or p["target"].max() >= len(tm)):
+        raise ValueError("stereo_append_ref: a record names a target outside the target tables")
+    s = float(1 << level)
+    ap = np.zeros(2 * n, dtype=_store_dtype())
+    ap["uv"][0::2], ap["uv"][1::2] = p["root_pos"], p["target_pos"]
+    ap["mkf"][0::2], ap["cam"][0::2] = src_mkf, src_cam
+    ap["mkf"][1::2], ap["cam"][1::2] = tm[p["target"]], tc[p["target"]]
+    ap["row"][0::2] = ap["row"][1::2] = r
+    ap["level"], ap["alive"] = level, 1
+    ap["source"][0::2], ap["source"][1::2] = SRC_ROOT, SRC_EPIPOLAR
+    return dict(world_pos=p["world_pos"].copy(), pixel_right_w=p["pixel_right_w"].copy(), pixel_down_w=p["pixel_down_w"].copy(),
+                usable=np.zeros(n, dtype=np.uint8), inlier=np.ones(n, dtype=np.int32), outlier=np.zeros(n, dtype=np.int32),
+                rays=np.concatenate([p["center_nc"], p["one_right_nc"], p["one_down_nc"]], axis=1).reshape(n, 9),
+                source_level=np.full(n, level, dtype=np.int32), center_xy=np.trunc((p["root_pos"] + 0.5) / s - 0.5).astype(np.int32).reshape(n, 2),
+                fixed=np.zeros(n, dtype=np.uint8), gp_src_mkf=np.full(n, src_mkf, dtype=np.int32), gp_src_cam=np.full(n, src_cam, dtype=np.int32),
+                gp_flags=np.zeros(n, dtype=np.int32), appended=ap, store_end=int(first_store) + 2 * n)
+
+
+def stereo_append_host(pts, rows, level, src_mkf, src_cam, target_mkf, target_cam, first_store=0):
+    """mcp_stereo_append_host: the body the append kernel calls, under the host compiler.  Needs no device.  Returns the arrays of
+    stereo_append_ref that the call writes (the constant columns -- usable, counts, level, fixed -- are the kernel's own)."""
+    p, r, tm, tc = _append_args(pts, rows, target_mkf, target_cam)
+    n, m = len(p), max(len(p), 1)
+    o = dict(world_pos=np.zeros((m, 3)), pixel_right_w=np.zeros((m, 3)), pixel_down_w=np.zeros((m, 3)), rays=np.zeros((m, 9)), center_xy=np.zeros((m, 2), np.int32),
+             gp_src_mkf=np.zeros(m, np.int32), gp_src_cam=np.zeros(m, np.int32), gp_flags=np.zeros(m, np.int32), appended=np.zeros(2 * m, dtype=_store_dtype()))
+    rc = lib().mcp_stereo_append_host(n, p.ctypes.data, r.ctypes.data, int(level), int(src_mkf), int(src_cam), tm.ctypes.data, tc.ctypes.data, int(first_store),
+                                      *[o[k].ctypes.data for k in ("world_pos", "pixel_right_w", "pixel_down_w", "rays", "center_xy", "gp_src_mkf", "gp_src_cam", "gp_flags",
+                                                                   "appended")])
+    if rc < 0:
+        raise RuntimeError("mcp_stereo_append_host failed: " + _cb.last_error())
+    o = {k: (v[:2 * n] if k == "appended" else v[:n]) for k, v in o.items()}
+    o["store_end"] = rc
+    return o
 
 
 # ---- numpy restatements (test infrastructure) ------------------------------------------------------------------------------------------------

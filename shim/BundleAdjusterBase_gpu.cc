@@ -116,8 +116,9 @@ void GraphEraseMKF(Map& map, MultiKeyFrame& mkf)
   mkf.mnGraphSlot = -1;
 }
 
-// MapPoint created, its source set, mbFixed / mbBad changed by the host (AddStereoMapPoints, AddInitDepthMapPoints, HandleBadPoints): the graph columns of its row.
-// Not for the rows HandleOutliers / HandleBadEntities turn bad: the device marks those itself (mcp_map_cull_*) and reports them.  Its MapPoint columns go to the table as before.
+// MapPoint created, its source set, mbFixed / mbBad changed by the host (AddInitDepthMapPoints and the initialisers, HandleBadPoints): the graph columns of its row.
+// Not for the rows HandleOutliers / HandleBadEntities turn bad: the device marks those itself (mcp_map_cull_*) and reports them; and not for the points of
+// AddStereoMapPoints, whose rows mcp_stereo_map_points writes on the device (shim/MapMakerServerBase_gpu.cc).  Its MapPoint columns go to the table as before.
 void GraphUploadPoints(Map& map, const std::vector<MapPoint*>& vpPoints)
 {
   const int n = (int)vpPoints.size();
@@ -134,9 +135,10 @@ void GraphUploadPoints(Map& map, const std::vector<MapPoint*>& vpPoints)
     ROS_ERROR_STREAM("mcp_map_graph_update_points: " << mcp_last_error());
 }
 
-// KeyFrame::AddMeasurement, batched by the caller that makes many from host data (AddStereoMapPoints, the initialisers): one append.
-// MeasPtrMap guarantees one entry per (keyframe, point), which is what the store relies on.  The tracker's measurements of a new MKF and
-// ReFindBatch's do not come through here any more: their lists are on the device already (GraphCommitTrackerParcel / GraphCommitReFindParcel).
+// KeyFrame::AddMeasurement, batched by the caller that makes many from host data (the initialisers): one append.
+// MeasPtrMap guarantees one entry per (keyframe, point), which is what the store relies on.  The tracker's measurements of a new MKF,
+// ReFindBatch's and the two measurements of every point AddStereoMapPoints creates do not come through here any more: they are on the device
+// already (GraphCommitTrackerParcel / GraphCommitReFindParcel / mcp_stereo_map_points).
 void GraphAddMeasurements(Map& map, const std::vector<std::pair<KeyFrame*, MapPoint*> >& vPairs)
 {
   const int n = (int)vPairs.size();

@@ -13,6 +13,8 @@
 // Needs KeyFrame::mpDev (shim/KeyFrame_gpu.cc), shim/CameraExport.h, and the table with MapPoint::mnTableRow (shim/Tracker_gpu.cc: the map
 // maker holds the same mcp_map_points* as mpMapTable), and in class MapMakerServerBase: mcp_meas_parcel* mpReFindParcel
 // (mcp_meas_parcel_create(mpMapTable) where the table is handed over; mcp_meas_parcel_destroy before the table goes).
+// AddStereoMapPoints also needs the map's row allocator -- in class Map: std::vector<int> mvFreeRows; int mnNextRow, mnNextKey -- and
+// MapPoint::mnTableKey next to mnTableRow (the key the row carries for this point: parcels and the finders tell points apart by it).
 // At the end of this file: HandleOutliers (:1198-1238) and MapMaker::HandleBadEntities (src/MapMaker.cc:477-492) over mcp_map_cull_outliers /
 // mcp_map_cull_sweep, and MarkFurthestMultiKeyFrameAsBad (:264-318) over mcp_map_mkf_cull -- delete those three bodies too.
 #include <mcptam/MapMakerServerBase.h>
@@ -325,13 +327,48 @@ void MapMakerServerBase::ReFindFromFailureQueue()
   }
 }
 
-// ---- AddStereoMapPoints (:452-496) with one mcp_stereo_points call per source keyframe and level: ThinCandidates before every target, the arc,
-// both PatchFinder loops, the selection, ReprojectPoint and the nLimit counter run on the device in one submission (include/mcp_img.h).  The
+// ---- AddStereoMapPoints (:452-496) with one mcp_stereo_map_points call per source keyframe and level: ThinCandidates before every target, the
+// arc, both PatchFinder loops, the selection, ReprojectPoint and the nLimit counter run on the device in one submission, and the created points
+// go straight into the map-point table, the graph's point columns and the store (include/mcp_img.h): nothing is sent up again.  The
 // targets come from the map graph: mcp_map_neighbours (keyframe kind, n_max = snMaxTriangulationKFs, max_dist as :463-470) is
 // ClosestKeyFramesWithinDist over the graph's poses, active bytes and depth means -- at most n_max items come back, each with its MKF's flags.
 // The host keeps the mbBad / CrossCamera / sbOnlyFirstCameraGeneratesPoints skips (a skipped target neither thins nor creates; a bad MKF is a
 // candidate of the query, as in the reference's walk, and is skipped here after the list is cut), and building the MapPoints and Measurements
 // from the records, in the reference's creation order.
+// THE ROW HAND-OFF.  Rows are the host's to assign, and the call must know them before it knows how many points it makes: the map's row
+// allocator (in class Map: std::vector<int> mvFreeRows, the rows of points whose trash was emptied; int mnNextRow, the table's end; int
+// mnNextKey, the counter that gives every MapPoint its key) hands out one row and key per candidate, point k takes vRows[k], and the rows that
+// were not taken go back.  A row comes out of mvFreeRows only after Map::EmptyTrash, when no live store entry names it.
+// BUSY POSITIONS.  The source keyframe's measurements are in the store already (the tracker's parcel was committed when the MKF entered the
+// map, the points of the levels before this one were appended by this call), so mmpMeasurements is not walked: busy_from_store = 1 gathers
+// them on the device.  The gather is one pass over the store; profiles/map_graph/README.md has its cost against the walk it replaces.
+namespace
+{
+void TakeFreeRows(Map& map, int n, std::vector<int>& vRows, std::vector<int>& vKeys)
+{
+  vRows.resize(n);
+  vKeys.resize(n);
+  for(int i = 0; i < n; ++i)
+  {
+    if(!map.mvFreeRows.empty())
+    {
+      vRows[i] = map.mvFreeRows.back();
+      map.mvFreeRows.pop_back();
+    }
+    else
+      vRows[i] = map.mnNextRow++;
+    vKeys[i] = map.mnNextKey++;
+  }
+}
+
+// the rows vRows[nTaken ..) were not used: back they go, the first of them to be handed out first again (their keys are just skipped)
+void ReturnFreeRows(Map& map, const std::vector<int>& vRows, int nTaken)
+{
+  for(int i = (int)vRows.size() - 1; i >= nTaken; --i)
+    map.mvFreeRows.push_back(vRows[i]);
+}
+}  // namespace
+
 void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, int nLimit, double dDistThresh, KeyFrameRegion region)
 {
   static gvar3<int> gvnCrossCamera("CrossCamera", 1, HIDDEN|SILENT);
@@ -364,6 +401,7 @@ void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, i
       ROS_BREAK();
     }
     std::vector<KeyFrame*> vpTargets;
+    std::vector<int> vTargetMKF, vTargetCam;     // the targets as the graph names them: where the SRC_EPIPOLAR entries go
     for(int j = 0; j < nbRes.count; ++j)
     {
       const mcp_neigh_item& item = nbRes.item[j];
@@ -373,6 +411,8 @@ void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, i
         continue;
       MultiKeyFrame* pMKF = mBundleAdjuster.mvpSlotMKF[item.slot];
       vpTargets.push_back(pMKF->mmpKeyFrames[mBundleAdjuster.mvCamNames[item.cam]]);
+      vTargetMKF.push_back(item.slot);
+      vTargetCam.push_back(item.cam);
     }
     TaylorCamera& cameraSrc = mmCameraModels[kfSrc.mCamName];
     const mcp_camera camSrc = mcptam_hip::CameraExport::Make(cameraSrc);
@@ -394,35 +434,43 @@ void MapMakerServerBase::AddStereoMapPoints(MultiKeyFrame& mkfSrc, int nLevel, i
       vCand[i].x = level.vCandidates[i].irLevelPos.x;
       vCand[i].y = level.vCandidates[i].irLevelPos.y;
     }
-    std::vector<mcp_stereo_meas> vMeas;
-    for(MeasPtrMap::iterator itm = kfSrc.mmpMeasurements.begin(); itm != kfSrc.mmpMeasurements.end(); ++itm)
-    {
-      mcp_stereo_meas m;
-      m.root_pos[0] = itm->second->v2RootPos[0];
-      m.root_pos[1] = itm->second->v2RootPos[1];
-      m.level = itm->second->nLevel;
-      m.pad_ = 0;
-      vMeas.push_back(m);
-    }
     double adSrc[12];
     ToArray12(kfSrc.mse3CamFromWorld, adSrc);
     const int n = (int)vCand.size();
     std::vector<mcp_stereo_point> vOut(n + 1);
     std::vector<uint8_t> vKeep(n + 1);
+    std::vector<int> vRows, vKeys;
+    TakeFreeRows(mMap, n, vRows, vKeys);
     ROS_ASSERT(kfSrc.mpDev);
-    const int nMade = mcp_stereo_points(kfSrc.mpDev, &camSrc, adSrc, nLevel, n, n ? &vCand[0] : NULL, (int)vMeas.size(), vMeas.empty() ? NULL : &vMeas[0],
-                                        (int)vTargets.size(), vTargets.empty() ? NULL : &vTargets[0], nLimit, n, &vOut[0], &vKeep[0], NULL);
+    mcp_stereo_map_params params;
+    params.src_mkf = mkfSrc.mnGraphSlot;
+    params.src_cam = kfSrc.mnCamIndex;
+    params.limit = nLimit;
+    params.busy_from_store = 1;
+    mcp_stereo_map_result result;
+    const int nMade = mcp_stereo_map_points(mMap.mpMapGraph, kfSrc.mpDev, &camSrc, adSrc, nLevel, n, n ? &vCand[0] : NULL, 0, NULL,
+                                            (int)vTargets.size(), vTargets.empty() ? NULL : &vTargets[0], vTargets.empty() ? NULL : &vTargetMKF[0],
+                                            vTargets.empty() ? NULL : &vTargetCam[0], n, n ? &vRows[0] : NULL, n ? &vKeys[0] : NULL, &params, &result,
+                                            &vOut[0], &vKeep[0], NULL);
     if(nMade < 0)
     {
       ROS_FATAL_STREAM("MapMakerServerBase::AddStereoMapPoints: "<<mcp_last_error());
       ros::shutdown();
       return;
     }
+    ReturnFreeRows(mMap, vRows, nMade);
+    if((int)mBundleAdjuster.mvpRowPoint.size() < mMap.mnNextRow)
+      mBundleAdjuster.mvpRowPoint.resize(mMap.mnNextRow, NULL);
+    // The host objects follow the records; their rows, graph columns and store entries are on the device already, so none of them goes through
+    // the table updates, GraphUploadPoints or GraphAddMeasurements.
     for(int k = 0; k < nMade; ++k)       // :862-914, in creation order
     {
       const mcp_stereo_point& r = vOut[k];
       KeyFrame& kfTarget = *vpTargets[r.target];
       MapPoint* pPointNew = new MapPoint;
+      pPointNew->mnTableRow = vRows[k];
+      pPointNew->mnTableKey = vKeys[k];
+      mBundleAdjuster.mvpRowPoint[vRows[k]] = pPointNew;
       pPointNew->mv3WorldPos = makeVector(r.world_pos[0], r.world_pos[1], r.world_pos[2]);
       pPointNew->mpPatchSourceKF = &kfSrc;
       pPointNew->mnSourceLevel = nLevel;
