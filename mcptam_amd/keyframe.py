@@ -126,6 +126,15 @@ def _dp(a):
     return a.ctypes.data_as(c_double_p)
 
 
+def _u8_rows(img):
+    """A uint8 image as the C ABI takes it: dense rows at any row stride.  A row-strided view (unit column stride, stride >= width)
+    passes through with its true stride; anything else is copied to a dense array."""
+    a = np.asarray(img)
+    if a.dtype == np.uint8 and a.ndim == 2 and a.shape[1] > 0 and a.strides[1] == 1 and a.shape[1] <= a.strides[0] < 2**31:
+        return a
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
 class KeyFrame:
     """One camera's KeyFrame with a device-resident 4-level pyramid (include/mcptam/KeyFrame.h:93-150)."""
 
@@ -146,7 +155,7 @@ class KeyFrame:
         self.close()
 
     def MakeKeyFrame_Lite(self, img, masks=None):
-        img = np.ascontiguousarray(img, dtype=np.uint8)
+        img = _u8_rows(img)
         assert img.shape == (self.h, self.w)
         mp = None
         if masks is not None:
@@ -231,7 +240,7 @@ def make_lite_batch(kfs, imgs, masks=None, on_device=False, strides=None):
         st = (ctypes.c_int * n)(*[int(s_) for s_ in (strides or [k.w for k in kfs])])
         keep = None
     else:
-        keep = [np.ascontiguousarray(a, dtype=np.uint8) for a in imgs]
+        keep = [_u8_rows(a) for a in imgs]
         for k, a in zip(kfs, keep):
             assert a.shape == (k.h, k.w)
         ip = (ctypes.c_void_p * n)(*[a.ctypes.data for a in keep])
