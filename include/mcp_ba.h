@@ -105,6 +105,9 @@ typedef struct mcp_ba_timing {
   /* chains of block columns the one-launch factorisation walks beside each other (1: the poses in add order; 3: a trajectory's band cut into
    * two halves + the separator between them; 0 if no plan was built) */
   int    chol_chains;
+  /* iterations whose iteration-start robust chi2 was summed inside the first trial's launches (k_eval_start + that trial's
+   * k_final_sums) instead of two launches in front of the linearisation (takes the structure's tail padding) */
+  int    n_start_rides;
 } mcp_ba_timing;
 
 const char* mcp_last_error(void);

@@ -45,7 +45,7 @@ class McpBaTiming(ctypes.Structure):
                 ("collective_bytes_main", ctypes.c_double), ("collective_bytes_spec", ctypes.c_double),
                 ("n_median_fast", ctypes.c_int), ("n_persist_fallbacks", ctypes.c_int),
                 ("schur_mfma_per_system", ctypes.c_double), ("schur_flops_structural", ctypes.c_double),
-                ("chol_flops_plan", ctypes.c_double), ("chol_chains", ctypes.c_int)]
+                ("chol_flops_plan", ctypes.c_double), ("chol_chains", ctypes.c_int), ("n_start_rides", ctypes.c_int)]
 
 
 class McpBaStructure(ctypes.Structure):

@@ -193,11 +193,9 @@ k_eval(DevProblem P, const double* __restrict__ pt_x, const double* __restrict__
   eval_body<SUM>(P, pt_x, last, chi2, err_out, sigma, partial);
 }
 
-// robust sum over an existing chi2 array (first evaluation of an iteration, after the median)
-__global__ void __launch_bounds__(EVAL_BLOCK)
-k_robust_sum(int n, int robust, const double* __restrict__ chi2, const double* __restrict__ sigma,
-             double* __restrict__ partial) {
-  __shared__ double lds[EVAL_BLOCK/64];
+// robust sum over an existing chi2 array, one partial per EVAL_BLOCK values: this block's (shared by k_robust_sum and k_eval_start,
+// so that the two take the same sum with the same instructions)
+__device__ __forceinline__ double robust_sum_term(int n, int robust, const double* __restrict__ chi2, const double* __restrict__ sigma) {
   const int m = blockIdx.x*EVAL_BLOCK + threadIdx.x;
   double contrib = 0.0;
   if (m < n) {
@@ -205,45 +203,119 @@ k_robust_sum(int n, int robust, const double* __restrict__ chi2, const double* _
     if (robust) { double r0, r1; robustify(c, sigma[1], sigma[2], r0, r1); contrib = r0; }
     else contrib = c;
   }
+  return contrib;
+}
+__device__ __forceinline__ void robust_sum_block(double contrib, double* __restrict__ partial, double* lds) {
   const double t = block_sum<EVAL_BLOCK>(contrib, lds);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
+// (first evaluation of an iteration, after the median)
+__global__ void __launch_bounds__(EVAL_BLOCK)
+k_robust_sum(int n, int robust, const double* __restrict__ chi2, const double* __restrict__ sigma,
+             double* __restrict__ partial) {
+  __shared__ double lds[EVAL_BLOCK/64];
+  robust_sum_block(robust_sum_term(n, robust, chi2, sigma), partial, lds);
+}
+// the evaluation of an iteration's first trial with the iteration-start robust chi2 riding along: k_eval<true> of the trial state,
+// and k_robust_sum's partials of the CURRENT state's chi2 (the same blocks of EVAL_BLOCK values) into their own array.  Only the host
+// reads that sum, and only with this trial's result (ba_solver.hip iteration_head): it needs no launches of its own in front of the
+// linearisation.
+__global__ void __launch_bounds__(EVAL_BLOCK)
+k_eval_start(DevProblem P, const double* __restrict__ pt_x, const double* __restrict__ last,
+             double* __restrict__ chi2, const double* __restrict__ sigma, double* __restrict__ partial,
+             int robust, const double* __restrict__ chi2_cur, double* __restrict__ partial_cur) {
+  __shared__ double lds[EVAL_BLOCK/64];
+  const double start_term = robust_sum_term(P.nmeas, robust, chi2_cur, sigma);      // (requested in front of the evaluation's chain of loads)
+  eval_body<true>(P, pt_x, last, chi2, nullptr, sigma, partial);
+  robust_sum_block(start_term, partial_cur, lds);
+}
 
-// fixed-order final reduction of up to 3 partial arrays into out[off..off+2] (single block); out[off+3] = failure flag
-// mail (may be null): device-visible pinned host memory.  The first mail_count entries of `out` are forwarded there, then the
+// fixed-order final reduction of up to 4 partial arrays (single block): three into out[off..off+2], the fourth into out[dst3];
+// out[off+3] = failure flag
+// mail (may be null): device-visible pinned host memory.  The first mail_count entries of `out` (at most 64: lane i of wavefront 0
+// forwards entry i; the callers pass 6, 29 or MAIL_TICKET) are forwarded there, then the
 // ticket mail[MAIL_TICKET] is released at system scope -- the host polls the ticket instead of enqueueing a copy and waiting on
 // the stream (the LM accept/reject decision is one PCIe write away instead of a blit kernel + a stream wait).
 constexpr int MAIL_TICKET = 31;
+constexpr int FS_ARRAYS = 4;       // partial arrays one launch sums
+constexpr int FS_AHEAD = 8;        // strided steps of every array requested together: 2048 partials per array in one round trip
+static_assert(MAIL_TICKET <= 64, "the forwarded block is one wavefront's: lane i holds entry i");
+// One round trip: every load -- the strided partials of all arrays, the failure word, the riding value and the entries of `out` (or
+// start_src) that earlier kernels of the stream wrote and the mailbox forwards -- is requested before the first barrier.  The sums
+// themselves are what block_sum<256> makes of each array (per-thread i = t, t + 256, ...; the shuffle tree; the waves in order),
+// with one pair of barriers for all of them; wavefront 0 then writes `out` and the mailbox from its registers.
+// The fourth array's sum goes to out[dst3] (the iteration-start robust chi2 that rides on a trial, ba_solver.hip).
 __device__ __forceinline__ void final_sums_body(int n0, const double* p0, int n1, const double* p1, int n2, const double* p2,
              double* __restrict__ out, int off, const int* __restrict__ fail, double* mail, int mail_count, unsigned long long ticket,
-             const double* ride_src, int ride_dst, const double* start_src = nullptr /* entries [24, 29) of the mailbox from here instead of out */) {
-  __shared__ double lds[4];
-  const double* ps[3] = { p0, p1, p2 }; const int ns[3] = { n0, n1, n2 };
-  for (int a = 0; a < 3; ++a) {
-    if (!ps[a]) continue;
-    double v = 0.0;
-    for (int i = threadIdx.x; i < ns[a]; i += 256) v += ps[a][i];
-    const double t = block_sum<256>(v, lds);
-    if (threadIdx.x == 0) out[off + a] = t;
+             const double* ride_src, int ride_dst, const double* start_src = nullptr /* entries [24, 29) of the mailbox from here instead of out */,
+             int n3 = 0, const double* p3 = nullptr, int dst3 = 0) {
+  __shared__ double lds[FS_ARRAYS][4];
+  const int t = threadIdx.x;
+  const double* ps[FS_ARRAYS] = { p0, p1, p2, p3 };
+  const int ns[FS_ARRAYS] = { p0 ? n0 : 0, p1 ? n1 : 0, p2 ? n2 : 0, p3 ? n3 : 0 };
+  const bool from_start = start_src && t >= 24 && t < 29;
+  double fw = 0.0;
+  if (mail && t < mail_count) fw = from_start ? start_src[t - 24] : out[t];
+  // (a zero the compiler cannot see through, so that the two words are vector loads in flight with the partials.  Read in the
+  //  kernel's assembly, not measured on its own: as uniform loads they become scalar loads, each followed by a wait that also covers
+  //  a batch of the kernel's arguments, in front of the first partial's request -- two more dependent round trips.  An assumption
+  //  about this compiler; without the line the kernel is as correct, and at worst two hops longer.)
+  int zero = 0; asm volatile("" : "+v"(zero));  const int fl = fail ? fail[zero] : 0;
+  const double rd = ride_src ? ride_src[zero] : 0.0;
+  double v[FS_ARRAYS] = { 0.0, 0.0, 0.0, 0.0 };
+  const int nmax = max(max(ns[0], ns[1]), max(ns[2], ns[3]));
+  for (int base = 0; base < nmax; base += 256*FS_AHEAD) {
+    double x[FS_ARRAYS][FS_AHEAD];
+#pragma unroll
+    for (int a = 0; a < FS_ARRAYS; ++a)
+#pragma unroll
+      for (int k = 0; k < FS_AHEAD; ++k) { const int i = base + 256*k + t; x[a][k] = (i < ns[a]) ? ps[a][i] : 0.0; }
+#pragma unroll
+    for (int a = 0; a < FS_ARRAYS; ++a)
+#pragma unroll
+      for (int k = 0; k < FS_AHEAD; ++k) if (base + 256*k + t < ns[a]) v[a] += x[a][k];
   }
-  // (bit 2: a hand-off of the one-launch factorisation timed out, ba_chol2.h -- the host redoes the solve with the per-step kernels;
-  //  1e9 survives the sum over ranks as "some rank had it")
-  if (fail && threadIdx.x == 0) out[off + 3] = (fail[0] & 4) ? 1e9 : ((fail[0] != 0) ? 1.0 : 0.0);
-  if (ride_src && threadIdx.x == 0) out[ride_dst] = ride_src[0];
+#pragma unroll
+  for (int a = 0; a < FS_ARRAYS; ++a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[a] += __shfl_down(v[a], o, 64);
+    if ((t & 63) == 0) lds[a][t >> 6] = v[a];
+  }
+  __syncthreads();
+  if (t < 64) {       // (every lane of wavefront 0 adds the four waves' sums in thread 0's order: the totals need no broadcast)
+    double tot[FS_ARRAYS];
+#pragma unroll
+    for (int a = 0; a < FS_ARRAYS; ++a) { double s = 0.0; for (int i = 0; i < 4; ++i) s += lds[a][i]; tot[a] = s; }
+    // (bit 2: a hand-off of the one-launch factorisation timed out, ba_chol2.h -- the host redoes the solve with the per-step kernels;
+    //  1e9 survives the sum over ranks as "some rank had it")
+    const double fv = (fl & 4) ? 1e9 : ((fl != 0) ? 1.0 : 0.0);
+    // what this launch writes to `out`, in the order it always has: lane 0 stores it, lane i keeps entry i for the mailbox
+#pragma unroll
+    for (int a = 0; a < FS_ARRAYS; ++a) {
+      if (!ps[a]) continue;
+      const int d = (a < 3) ? off + a : dst3;
+      if (t == 0) out[d] = tot[a];
+      if (t == d && !from_start) fw = tot[a];
+    }
+    if (fail) { if (t == 0) out[off + 3] = fv; if (t == off + 3 && !from_start) fw = fv; }
+    if (ride_src) { if (t == 0) out[ride_dst] = rd; if (t == ride_dst && !from_start) fw = rd; }
+    if (mail) {
+      if (t < mail_count) mail[t] = fw;
+      __threadfence_system();
+    }
+  }
   if (mail) {
-    __syncthreads();                                 // thread 0's stores to `out` above; the other entries come from earlier kernels of the stream
-    for (int i = threadIdx.x; i < mail_count; i += 256) mail[i] = (start_src && i >= 24 && i < 29) ? start_src[i - 24] : out[i];
-    __threadfence_system();
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store((unsigned long long*)(mail + MAIL_TICKET), ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (t == 0) __hip_atomic_store((unsigned long long*)(mail + MAIL_TICKET), ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 __global__ void __launch_bounds__(256)
 k_final_sums(int n0, const double* p0, int n1, const double* p1, int n2, const double* p2,
              double* __restrict__ out, int off, const int* __restrict__ fail, double* mail = nullptr, int mail_count = 0, unsigned long long ticket = 0,
              const double* ride_src = nullptr, int ride_dst = 0 /* out[ride_dst] = ride_src[0]: a value of an earlier kernel joins this block's all-reduce */,
-             const double* start_src = nullptr /* the iteration-start block forwarded to the host lives here (a per-trial head's, ba_solver.hip enqueue_head) */) {
-  final_sums_body(n0, p0, n1, p1, n2, p2, out, off, fail, mail, mail_count, ticket, ride_src, ride_dst, start_src);
+             const double* start_src = nullptr /* the iteration-start block forwarded to the host lives here (a per-trial head's, ba_solver.hip enqueue_head) */,
+             int n3 = 0, const double* p3 = nullptr, int dst3 = 0 /* a fourth partial array, summed into out[dst3] */) {
+  final_sums_body(n0, p0, n1, p1, n2, p2, out, off, fail, mail, mail_count, ticket, ride_src, ride_dst, start_src, n3, p3, dst3);
 }
 
 // ------------------------------------------------------------------------------------------

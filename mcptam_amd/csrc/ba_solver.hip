@@ -521,6 +521,10 @@ struct mcp_ba {
   unsigned long long head_ticket_ctr = 0;
   int head_par = 0, acc_head_q = -1, dbg_head_miss = 0;
   const double* start_blk = nullptr;      // the iteration-start block the first trial forwards to the host (nullptr: d_res[24..28])
+  // the plain head left the iteration-start robust chi2 to the first main-stream trial (k_eval_start -> d_parth -> d_res[24]).  Set in one
+  // place (iteration_head: one rank, measurements, mailbox in use, no profile, after the first iteration), consumed in one place (the next
+  // main block of launch_trial_step); begin_solve and mcp_ba_debug_trial clear what a Compute() that returned early may have left
+  bool start_ride = false;
   unsigned int* head_hist(int q) { return hsc[head_par*MAX_SYS + q].hist; }
   int enqueue_head(hipStream_t s, int q, int w, bool side);
   int wait_head(int q);
@@ -2779,7 +2783,15 @@ int mcp_ba::launch_trial_step(const TrialIo& io) {
   if (io.main_block) { toc(); tic(ST_EVAL); }
   if (io.record_wf) HIPCK(hipEventRecord(lane[io.q].ev_wf, s));      // the linearisation's outputs are not read below this line (join_spec_lin)
   if (P.nchain && !ncb) hipLaunchKernelGGL(k_chains, dim3((P.nchain + 63)/64), dim3(64), 0, s, P, (const double*)d_pose[slot].p, d_first[slot].p, d_second[slot].p, d_last[slot].p);
-  if (nbe) hipLaunchKernelGGL((k_eval<true>), dim3(nbe), dim3(EVAL_BLOCK), 0, s, P, (const double*)d_pt[slot].p, (const double*)d_last[slot].p, d_chi2[slot].p, (double*)nullptr,
+  // the iteration's first main-stream trial takes the iteration-start robust chi2 along (iteration_head): k_robust_sum's partials of
+  // the current state's chi2 from the evaluation's blocks, summed by this trial's k_final_sums into d_res[RS] in front of the block's
+  // way to the host.  Once per iteration: a later batch, or a re-entered solve, forwards what is in d_res[RS] by then.
+  // (start_ride is only ever set for one rank with measurements, iteration_head; the stale step is no main block)
+  const bool ride = io.main_block && start_ride;
+  if (ride) { start_ride = false; ++timing.n_start_rides; }
+  if (ride) hipLaunchKernelGGL(k_eval_start, dim3(nbe), dim3(EVAL_BLOCK), 0, s, P, (const double*)d_pt[slot].p, (const double*)d_last[slot].p, d_chi2[slot].p,
+                               (const double*)sig(), io.p0, robust ? 1 : 0, (const double*)d_chi2[cur].p, d_parth.p);
+  else if (nbe) hipLaunchKernelGGL((k_eval<true>), dim3(nbe), dim3(EVAL_BLOCK), 0, s, P, (const double*)d_pt[slot].p, (const double*)d_last[slot].p, d_chi2[slot].p, (double*)nullptr,
                               (const double*)sig(), io.p0);
   const double* p1 = (nfl && !io.stale) ? io.p1 : nullptr; const double* p2 = (nfl && !io.stale) ? io.p2 : nullptr;
   const int nbs = p1 ? nbb : 0;
@@ -2788,8 +2800,10 @@ int mcp_ba::launch_trial_step(const TrialIo& io) {
     if (multi_trial_tail(s, io.lane, io.q, slot, nbe, io.p0, nbs, p1, p2, io.pose_parts, io.pose_off, io.main_block, io.mail, io.mail_count, io.ticket)) return -1;
   } else {
     if (io.main_block && join_sum()) return -1;      // (this launch forwards d_res[24..28], the head of the iteration, to the host)
+    if (io.mail_count > MAIL_TICKET) { set_err("a trial's mailbox block is longer than the mailbox"); return -1; }      // (k_final_sums forwards at most a wavefront's worth)
     hipLaunchKernelGGL(k_final_sums, dim3(1), dim3(256), 0, s, nbe, (const double*)io.p0, nbs, p1, nbs, p2, io.res, 0, io.fail,
-                       io.mail, io.mail_count, io.ticket, (const double*)nullptr, 0, io.main_block ? start_blk : (const double*)nullptr);
+                       io.mail, io.mail_count, io.ticket, (const double*)nullptr, 0, io.main_block ? start_blk : (const double*)nullptr,
+                       ride ? nbe : 0, ride ? (const double*)d_parth.p : (const double*)nullptr, RS);
     if (io.main_block && !nfl) HIPCK(hipMemsetAsync(d_res.p + 1, 0, 2*sizeof(double), s));
   }
   if (io.main_block) toc();
@@ -3270,7 +3284,7 @@ int mcp_ba::begin_solve(LmRun& R) {
   timing.schur_mfma_per_system = schur_mfma; timing.schur_flops_structural = schur_flops;
   timing.chol_flops_plan = (np > 0 && plan.persist.ok) ? plan.persist.flops : 0.0;
   timing.chol_chains = (np > 0 && plan.persist.ok) ? plan.persist.nseg : 0;
-  converged = 0; total_iterations = 0; spec_hot = 0;
+  converged = 0; total_iterations = 0; spec_hot = 0; start_ride = false;
   return 0;
 }
 // preIteration + first robustify: sigma^2 from |chi2| at the iteration-start state, its robust chi2, and the linearisation there.
@@ -3282,7 +3296,7 @@ int mcp_ba::iteration_head(LmRun& R, LmIter& I) {
   I.head_done = (it > 0 && head_ahead_for == cur);
   head_ahead_for = -1;
   if (I.head_done) { if (robust) flip_sig(); ++dbg_head_ahead; }
-  start_blk = nullptr;
+  start_blk = nullptr; start_ride = false;
   if (it > 0 && large_heads() && acc_head_q >= 0 && lane[acc_head_q].head_enq && lane[acc_head_q].head_state == cur) { if (head_brought_along(I)) return MCP_ERR_RUNTIME; }
   acc_head_q = -1;
   for (int q = 0; q < MAX_SYS; ++q) lane[q].head_enq = false;      // (what this iteration's trials enqueue goes to the other parity's slots)
@@ -3293,12 +3307,17 @@ int mcp_ba::iteration_head(LmRun& R, LmIter& I) {
   else if (use_head_large()) { if (head_large(cur, RS, nullptr)) return MCP_ERR_RUNTIME; }
   else {
     if (robust) { if (median_sigma(cur)) return MCP_ERR_RUNTIME; }
-    tic(ST_EVAL);
     // iteration-start robust chi2 and the sigma block go to d_res[24..28]; they are read back together with the first
     // trial's results (one host synchronisation less per iteration) -- except in the first iteration, whose lambda comes
-    // from the diagonal of the freshly built system
-    if (robust_total(st, cur, sig(), d_part0.p, d_res.p, RS)) return MCP_ERR_RUNTIME;
-    toc();
+    // from the diagonal of the freshly built system.  Nothing on the device reads that sum, and the linearisation needs only the
+    // sigma block: where the first trial's mailbox carries the block (one rank, after the first iteration), the sum is taken
+    // inside that trial's own launches (launch_trial_step) instead of two launches in front of the linearisation.
+    start_ride = it > 0 && !multi() && hk.use_mailbox && !prm.profile && P.nmeas > 0 && d_parth.p;
+    if (!start_ride) {
+      tic(ST_EVAL);
+      if (robust_total(st, cur, sig(), d_part0.p, d_res.p, RS)) return MCP_ERR_RUNTIME;
+      toc();
+    }
   }
   // several ranks: the sum over the ranks rides on the first trial's all-reduce (d_res[0..3] + d_res[4], see multi_trial_tail);
   // the first iteration needs it before its first trial
@@ -4180,6 +4199,7 @@ int mcp_ba_debug_trial(mcp_ba* h, double lambda, const double* x, int n_poses, i
   const int np = h->np, nfl = h->nfl;
   if (h->cancel_spec_trials() || h->join_spec() || h->join_sum()) return -1;
   h->head_ahead_want = false; h->head_ahead_for = -1;      // (no head of a next iteration rides behind this trial)
+  h->start_ride = false;                                   // (... and no start sum on it)
   if (h->state_ready(true)) return -1;
   mcp_ba_trial_report r; std::memset(&r, 0, sizeof r);
   r.ncb = x ? 0 : h->trial_chain_blocks(); r.nbb = nfl ? h->backsub_blocks() : 0;
