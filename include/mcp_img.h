@@ -748,6 +748,11 @@ int mcp_track_pose_cov_host(int n, const mcp_pose_point* pts, const double* weig
 /* for tests: the fine records, last weights and mu_last of the last successful track call on the table, as they stand on the device; *n
  * receives the count (more than cap: -1, nothing copied).  Waits for the table's stream. */
 int mcp_debug_track_fine_records(const mcp_map_points*, int cap, mcp_pose_point* pts, double* weights, double mu_last[6], int* n);
+/* for tests: which kernels computed the last pose iterations that mcp_track_pose_refine(_m) or mcp_track_frame ran on the calling thread's
+ * current device.  *route: 0 k_pose_refine_regs, 1 k_pose_refine, 2 k_pose_refine_multi, 3 k_pose_refine_multi given up and redone by
+ * k_pose_refine; *nwg: the workgroups of the multi launch (0 on routes 0 and 1); *gathered: 1 when its median went through LDS
+ * (MCP_TRACK_REFINE_GATHER), else 0.  Host bookkeeping only.  -1 + mcp_last_error() before the first such call or after a failed one. */
+int mcp_debug_last_pose_route(int* route, int* nwg, int* gathered);
 
 /* ---- MapMakerServerBase::ReFind_Common over the table in ONE submission ---------------------------- src/MapMakerServerBase.cc:921-1080
  * ReFindInSingleKeyFrame (every point of the map against a new keyframe), ReFindNewlyMade (every new point against every keyframe) and

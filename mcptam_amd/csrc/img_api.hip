@@ -420,6 +420,9 @@ int mcp_track_pose_refine(int n, mcp_pose_point* pts, int ncam, const mcp_camera
 // pad 6 d | override sigma n_iter d | CamFromBase 12 ncam d | camera models | nonlinear flags], the results [BaseFromWorld | mu] come back
 // in one copy: 2 uploads + 2-3 downloads per call instead of 6 + 4.
 struct RefineScratch { Buf<mcp_pose_point> dp, dp_keep; Buf<uint8_t> dblk; Buf<double> dJ, dex, de2, dw; Buf<PrmScratch> dprm; Buf<double> de2all; std::vector<uint8_t> hblk; bool last_multi = false;
+                       // what the last call on this scratch ran (mcp_debug_last_pose_route): -1 none yet, 0 k_pose_refine_regs, 1 k_pose_refine,
+                       // 2 k_pose_refine_multi, 3 k_pose_refine_multi given up and redone by k_pose_refine; the multi launch's workgroups and median
+                       int route = -1, route_nwg = 0; bool route_gather = false;
                        // k_pose_refine_regs reads the block and leaves BaseFromWorld | mu and the weights in PINNED HOST memory: no upload of the
                        // block, no fill of the weights, no copy back (three copy-engine operations and their queue switches per frame)
                        PinBuf<uint8_t> pblk; PinBuf<double> pw; bool res_pinned = false; };
@@ -470,6 +473,7 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
   const bool multi = n_iter <= PRM_MAX_ITER && ((use_multi == 2 && n >= 64) || (use_multi == 1 && !regs && n > PRR_THREADS*PRR_PPT));
   if (multi) regs = false;
   rs.last_multi = multi;
+  rs.route = -1; rs.route_nwg = 0; rs.route_gather = false;
   if (rs.dp.alloc(n) || rs.dblk.alloc(blk) || rs.dw.alloc(n)) return -1;
   auto alloc_plain = [&]() { return rs.dJ.alloc(12*(size_t)n) || rs.dex.alloc(2*(size_t)n) || rs.de2.alloc(n); };
   if (!regs && alloc_plain()) return -1;
@@ -529,6 +533,7 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
                        gather ? rs.de2all.p : (double*)nullptr, reinterpret_cast<double*>(rs.pblk.p));
     ICK(hipGetLastError());
     rs.res_pinned = true;
+    rs.route_nwg = nwg; rs.route_gather = gather;
     ICK(hipMemcpyAsync(prm_err, &rs.dprm.p->err, sizeof *prm_err, hipMemcpyDeviceToHost, st));
   } else if (!regs)
     hipLaunchKernelGGL(k_pose_refine, dim3(1), dim3(PR_THREADS), 0, st, n, rs.dp.p, d_cam, d_cfb, d_bfw, n_iter, d_nl, d_ov, rs.dJ.p, rs.dex.p, rs.de2.p, d_mu, rs.dw.p, est);
@@ -546,6 +551,7 @@ static int refine_enqueue(int n, const mcp_pose_point* host_pts, int ncam, const
   }
 #endif
   ICK(hipGetLastError());
+  rs.route = multi ? 2 : regs ? 0 : 1;
   return 0;
 }
 // BaseFromWorld | mu (18 doubles) and the last weights to the caller: copies enqueued where the results are on the device; where the kernel
@@ -592,7 +598,9 @@ static int refine_collect(int n, int n_iter, int ncam, int est, hipStream_t st, 
   if (fetch()) return -1;
   if (*prm_err || (rs.last_multi && mcp::knobs::track_test_prm_giveup())) {
     // a workgroup gave up waiting for the others: the frame is not lost, one workgroup redoes the iterations
+    rs.route = -1;
     if (refine_redo_single(n, n_iter, ncam, est, st) || fetch()) return -1;
+    rs.route = 3;
   }
   return 0;
 }
@@ -1693,6 +1701,13 @@ int mcp_debug_track_fine_records(const mcp_map_points* mc, int cap, mcp_pose_poi
     ICK(hipMemcpy(weights, m->tm.w.p, 8*(size_t)m->cv.n_fine, hipMemcpyDeviceToHost));
   }
   std::memcpy(mu_last, m->cv.mu, 48);
+  return 0;
+}
+int mcp_debug_last_pose_route(int* route, int* nwg, int* gathered) {
+  if (!route || !nwg || !gathered) return img_fail("mcp_debug_last_pose_route: bad arguments");
+  const RefineScratch& rs = refine_scratch();
+  if (rs.route < 0) return img_fail("mcp_debug_last_pose_route: no pose iterations have succeeded on this thread and device");
+  *route = rs.route; *nwg = rs.route_nwg; *gathered = rs.route_gather ? 1 : 0;
   return 0;
 }
 

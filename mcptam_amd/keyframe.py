@@ -53,7 +53,7 @@ IMG_SYMBOLS = [
     "mcp_track_map_meas_view",
     "mcp_track_frame_motion", "mcp_track_motion_reset", "mcp_track_motion_get_sbi", "mcp_track_motion_prior_host", "mcp_track_motion_update_host",
     "mcp_track_frame_recover", "mcp_track_recover_pose_host",
-    "mcp_track_pose_cov_enable", "mcp_track_pose_cov_last", "mcp_track_pose_cov", "mcp_track_pose_cov_host", "mcp_debug_track_fine_records",
+    "mcp_track_pose_cov_enable", "mcp_track_pose_cov_last", "mcp_track_pose_cov", "mcp_track_pose_cov_host", "mcp_debug_track_fine_records", "mcp_debug_last_pose_route",
     "mcp_map_graph_create", "mcp_map_graph_destroy", "mcp_map_graph_set_mkfs", "mcp_map_graph_update_mkfs", "mcp_map_graph_update_points",
     "mcp_map_graph_add_meas", "mcp_map_graph_erase_meas", "mcp_map_graph_erase_mkf", "mcp_map_graph_compact", "mcp_map_graph_num_meas",
     "mcp_map_graph_get_meas", "mcp_map_graph_good_counts", "mcp_map_graph_check", "mcp_map_bundle_select", "mcp_map_bundle_mkfs_view",
@@ -478,7 +478,7 @@ def _refine(fn, pts, cams, cam_from_base, base_from_world, nonlinear, override_s
 
 
 def track_pose_refine_sharded(pts, cams, cam_from_base, base_from_world, allreduce=None, rank=0, world=1, cap=None,
-                              nonlinear=FINE_NONLINEAR, override_sigma=FINE_OVERRIDE):
+                              nonlinear=FINE_NONLINEAR, override_sigma=FINE_OVERRIDE, estimator="Tukey"):
     """The pose iterations with the cameras spread over ranks (one camera per GPU, BASELINE config c5): `pts` are THIS rank's points,
     `allreduce(device_ptr, count, stream)` an in-place SUM all-reduce of doubles (e.g. mcptam_amd.dist.RcclAllReduce / GlooAllReduce);
     `cap` >= the largest point count of any rank.  Returns what track_pose_refine returns; the pose is the same on every rank."""
@@ -492,8 +492,11 @@ def track_pose_refine_sharded(pts, cams, cam_from_base, base_from_world, allredu
     hook = _cb.ALLREDUCE_FN(tramp) if allreduce is not None else ctypes.cast(None, _cb.ALLREDUCE_FN)
     cap = max(len(pts), 1) if cap is None else int(cap)
 
+    L = lib()
+    L.mcp_track_pose_refine_sharded_m.argtypes = list(L.mcp_track_pose_refine_sharded.argtypes) + [ctypes.c_int]
+
     def fn(n, p, ncam, carr, cfb, bfw, nit, nl, ov, mu, w):
-        return lib().mcp_track_pose_refine_sharded(n, p, ncam, carr, cfb, bfw, nit, nl, ov, mu, w, hook, None, int(rank), int(world), cap)
+        return L.mcp_track_pose_refine_sharded_m(n, p, ncam, carr, cfb, bfw, nit, nl, ov, mu, w, hook, None, int(rank), int(world), cap, MEST[estimator])
     rc, pose, mu, w, out = _refine(fn, pts, cams, cam_from_base, base_from_world, nonlinear, override_sigma, McpCamera)
     _chk(rc, "track_pose_refine_sharded")
     return pose, mu, w, out
@@ -583,3 +586,14 @@ def track_pose_refine(pts, cams, cam_from_base, base_from_world, nonlinear=FINE_
     rc, pose, mu, w, out = _refine(L.mcp_track_pose_refine_m, pts, cams, cam_from_base, base_from_world, nonlinear, override_sigma, McpCamera, extra=(MEST[estimator],))
     _chk(rc, "track_pose_refine")
     return pose, mu, w, out
+
+
+POSE_ROUTES = ("regs", "plain", "multi", "multi_redone")
+
+
+def last_pose_route():
+    """mcp_debug_last_pose_route: (route name, workgroups of the multi launch, median gathered) of the last pose iterations that
+    track_pose_refine or TrackFrame.run ran on this thread's current device."""
+    r, nwg, g = ctypes.c_int(-1), ctypes.c_int(0), ctypes.c_int(0)
+    _chk(lib().mcp_debug_last_pose_route(ctypes.byref(r), ctypes.byref(nwg), ctypes.byref(g)), "debug_last_pose_route")
+    return POSE_ROUTES[r.value], nwg.value, bool(g.value)
