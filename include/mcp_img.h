@@ -1308,6 +1308,74 @@ int mcp_map_points_get_rays(const mcp_map_points*, int first, int count, double*
 int mcp_map_points_get_source(const mcp_map_points*, int first, int count, int* keys, int* source_level, int* center_xy, uint8_t* fixed, uint8_t* has_source);
 int mcp_map_gp_get(mcp_map_graph*, int first, int count, int* src_mkf, int* src_cam, int* flags);
 
+/* ---- The map's beginning, its rescale and its re-alignment on the device --------------------------- src/MapMakerServerBase.cc:146-261, 499-596
+ * mcp_init_depth_map_points is AddInitDepthMapPoints (:499-546) of ONE MKF at ONE level, all cameras of the rig in one call (cams[c] is the rig's
+ * camera c; ncam must be the rig's): one submission on the table's stream, one host wait.  Per camera c: the busy list of (src_mkf, c) is gathered
+ * from the store in store order and ThinCandidates runs against it (levels level and level + 1, squared integer distance < 100), exactly as
+ * mcp_stereo_map_points does with busy_from_store = 1; keep (all cameras' candidates one after the other) is the thinning's verdict -- the
+ * reference leaves vCandidates = vCGood, created ones included.  The first `limit` survivors in candidate order become points.  Per point:
+ * root = LevelZeroPos(cand, level); the three patch rays UnProject(root), UnProject(root + (2^level, 0)), UnProject(root + (0, 2^level)), each
+ * normalised again; world = CamFromWorld^-1 * (UnProject(root) * init_depth) with CamFromWorld = cam_from_base[c] * base_from_world(src_mkf) TAKEN
+ * FROM THE GRAPH (no pose argument); RefreshPixelVectors.  Creation order is camera-major, then candidate order; point k in that order takes
+ * rows[k] / keys[k] (camera c's points start at the sum of made[c'] over c' < c, which only the device knows before the wait).  Row rows[k]
+ * receives what mcp_stereo_map_points writes for a stereo point: world position and pixel vectors, usable 0, counts (1, 0), rays, source =
+ * cams[c].src at `level` with the candidate as centre, fixed 0, the key (every camera's finder state of the row zeroed when the key changes),
+ * graph columns (src_mkf, c, flags 0, pending 0) -- and ONE store entry at first_store + k: {root, src_mkf, c, rows[k], level, MCP_SRC_ROOT,
+ * alive}.  Rows rows[made_total ..) stay untouched.  out, when not NULL, receives the records (target = -1, target_pos zero).  After the wait
+ * the host's mirrors follow: has_rays, the source-slot reference counts, the store's length (+ made_total).  n_busy[c] / n_alive[c]: the length
+ * of camera c's busy list and its surviving candidates (0 / 0 for a camera without candidates: no gather ran).  Growth before anything is
+ * enqueued, the grow-when-idle rule and the event on each source keyframe's stream are mcp_stereo_map_points'.  Returns made_total.
+ * REFUSALS (-1, mcp_last_error() starting "mcp_init_depth_map_points:", nothing enqueued, nothing changed): NULL graph / cams / params / result;
+ * ncam not the rig's; level outside 0..3; a negative limit or n_cand; a camera with candidates whose src is not a live keyframe handle with a
+ * frame on the table's device, whose camera is bad or that has a candidate outside the level image; n_rows < sum over c of min(n_cand, limit);
+ * a negative or duplicate row; NULL rows / keys with n_rows > 0; NULL keep with candidates; init_depth not finite or <= 0; src_mkf not present; a
+ * store that would pass INT_MAX.  sum n_cand == 0: the arguments are checked, nothing is enqueued, 0 is returned. */
+typedef struct mcp_init_depth_cam { mcp_kf* src; const mcp_camera* cam; int n_cand; const mcp_int2* cand; int limit; } mcp_init_depth_cam;
+typedef struct mcp_init_depth_params { int src_mkf, level; double init_depth; } mcp_init_depth_params;
+typedef struct mcp_init_depth_result { int made_total, first_store; int made[MCP_MAX_FRAME_CAMS], n_busy[MCP_MAX_FRAME_CAMS], n_alive[MCP_MAX_FRAME_CAMS]; } mcp_init_depth_result;
+int mcp_init_depth_map_points(mcp_map_graph*, int ncam, const mcp_init_depth_cam* cams, int n_rows, const int* rows, const int* keys,
+                              const mcp_init_depth_params*, mcp_init_depth_result*, mcp_stereo_point* out /* NULL or n_rows */, uint8_t* keep /* sum of n_cand */);
+/* NAMES.  mcp_map_mark_optimized, mcp_map_rescale and mcp_map_transform take the graph, like mcp_map_bundle_select, mcp_map_cull_*, mcp_map_neighbours
+ * and mcp_map_mkf_cull, and pair with their host twins mcp_map_mark_optimized_host / mcp_map_transform_host.  They do not carry the prefix
+ * mcp_map_graph_: that prefix names the graph's own upkeep (create .. check), a closed set that tests/test_capi_map_graph_cpu.py counts.
+ * The end of InitFromMultiKeyFrame (:212-215, mbOptimized = true on every point): usable = 1 on every table row whose graph column has been
+ * written and is not MCP_GP_BAD; every other byte of every row keeps its value.  One kernel, one wait; *n_marked (may be NULL): the rows named. */
+int mcp_map_mark_optimized(mcp_map_graph*, int* n_marked);
+/* ApplyGlobalScaleToMap (:549-574) / ApplyGlobalTransformationToMap (:577-596) over the resident map, one submission and one wait each:
+ *  1. every MCP_MKF_PRESENT slot (bad ones included): rescale multiplies the translation of base_from_world by scale (the rig's cam_from_base is
+ *     not scaled, as in the reference); transform sets base_from_world = base_from_world * new_from_old^-1.
+ *  2. every table row whose graph column names a present src_mkf and a camera of the rig: world *= scale, or world = new_from_old * world; then,
+ *     when the row has rays (the table's host record, sent up as one bit per row), RefreshPixelVectors at the NEW pose of its source keyframe.
+ *     Counted in n_refreshed, or in n_no_rays (new world position only).  A row without such a source keeps every byte: n_no_source.
+ *  3. rescale only: RefreshSceneDepthRobust of every present MKF, exactly as mcp_graph_refresh_depth over all present slots in ascending order
+ *     (same lists, kernel and summation contract; mean stored into the slot's depth column); depth_out as there, n present slots x ncam.
+ * usable, counts, rays, sources, keys, finder states, graph columns and the store keep every byte.  n_rows: the table's; n_mkfs: present slots.
+ * REFUSALS (-1, message starting with the call's name, nothing enqueued): NULL graph or result; scale not finite or <= 0; a non-finite entry of
+ * new_from_old (R row-major 9, t 3); a rotation part with max |R R^T - I| > 1e-9 (a caller's mistake is rejected, nothing is re-orthogonalised).
+ * An empty table and a graph without a present slot are allowed. */
+typedef struct mcp_map_transform_result { int n_rows, n_refreshed, n_no_rays, n_no_source, n_mkfs; } mcp_map_transform_result;
+int mcp_map_rescale(mcp_map_graph*, double scale, mcp_map_transform_result*, mcp_scene_depth* depth_out /* NULL or n present slots x ncam, ascending slot */);
+int mcp_map_transform(mcp_map_graph*, const double new_from_old[12], mcp_map_transform_result*);
+/* device time in ms of the last mcp_init_depth_map_points / the last mcp_map_rescale or mcp_map_transform that ran to its wait (between two events
+ * around the submission on the table's stream); -1.0 before the first such call */
+int mcp_map_life_last_timing(const mcp_map_graph*, double* init_depth_ms, double* move_ms);
+/* The three from host arrays, by the bodies the kernels call (map_life.h) under the host compiler: no device, the device's bytes.
+ * mcp_init_depth_points_host: cams / n_cand / limit / n_busy: ncam entries; cand and busy: the cameras' lists one after the other; the busy lists
+ * are the caller's (mcp_stereo_busy_host).  keep: sum n_cand; out, the per-point arrays (x 3, rays x 9, center_xy x 2) and appended: n_rows
+ * entries, the first made_total written.  res->n_busy is the caller's n_busy.  Returns made_total.
+ * mcp_map_mark_optimized_host: usable[r] = 1 where the rule holds (point_flags: n_point_rows graph columns); returns the count.
+ * mcp_map_transform_host: kind 0 (scale) or 1 (new_from_old); base_from_world (n_slots x 12), world_pos, pixel_right_w, pixel_down_w (n_rows x 3)
+ * are rewritten in place; has_rays: one byte per row; rays: n_rows x 9; gp_src_mkf / gp_src_cam: n_point_rows (rows past them have no source). */
+int mcp_init_depth_points_host(int ncam, const double* cam_from_base, const double src_base_from_world[12], const mcp_camera* cams, const int* n_cand,
+                               const mcp_int2* cand, const int* limit, const int* n_busy, const mcp_stereo_meas* busy, int n_rows, const int* rows,
+                               const mcp_init_depth_params*, int first_store, mcp_init_depth_result*, uint8_t* keep, mcp_stereo_point* out,
+                               double* world_pos, double* pixel_right_w, double* pixel_down_w, double* rays, int* center_xy, int* gp_src_mkf, int* gp_src_cam,
+                               int* gp_flags, mcp_store_entry* appended);
+int mcp_map_mark_optimized_host(int n_rows, int n_point_rows, const int* point_flags, uint8_t* usable);
+int mcp_map_transform_host(int kind, double scale, const double new_from_old[12], int ncam, const double* cam_from_base, int n_slots, double* base_from_world,
+                           const int* mkf_flags, int n_rows, int n_point_rows, const int* gp_src_mkf, const int* gp_src_cam, const uint8_t* has_rays,
+                           const double* rays, double* world_pos, double* pixel_right_w, double* pixel_down_w, mcp_map_transform_result*);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@
 #include "map_graph_cull.h"
 #include "map_graph_neigh.h"
 #include "stereo_append.h"
+#include "map_life.h"
 
 using namespace mcp;
 
@@ -2733,6 +2734,10 @@ struct mcp_map_graph {
   // mcp_stereo_map_points (stereo_append.h): the source keyframe's busy list gathered from the store, its length (device, pinned).  The rows, keys
   // and target slots go up through `up`, the per-workgroup counts through `blk`.
   struct Stereo { Buf<mcp_stereo_meas> busy; Buf<int> n_busy; PinBuf<int> h_n_busy; } stereo;
+  // mcp_init_depth_map_points / mcp_map_mark_optimized / _rescale / _transform (map_life.h): the candidates' survivor bytes and their per-workgroup
+  // counts, the hand-off block of the cameras' launches (device, pinned), the pinned keep bytes and records; the counters (device, pinned).
+  // The rows, keys and candidates -- or the rows' ray bits -- go up through `up`, the busy list through `stereo` and `blk`.
+  struct Life { Buf<uint8_t> alive; Buf<int> blk; Buf<MlInitCtl> ctl; PinBuf<MlInitCtl> h_ctl; PinBuf<uint8_t> h_keep; PinBuf<mcp_stereo_point> h_out; Buf<int> cnt; PinBuf<int> h_cnt; MgTimer t_init, t_move; } life;
   using Guard = Grow<mcp_map_graph>;
   ~mcp_map_graph() {                                  // (the timers destroy their events after this wait)
     if (m && m->st) (void)hipStreamSynchronize(m->st);
@@ -4025,6 +4030,239 @@ int mcp_map_gp_get(mcp_map_graph* g, int first, int count, int* src_mkf, int* sr
     if (src_mkf) src_mkf[k] = P.src_mkf; if (src_cam) src_cam[k] = P.src_cam; if (flags) flags[k] = P.flags;
   }
   return 0;
+}
+
+}  // extern "C"
+
+// ---- the map's beginning, its rescale and its re-alignment (include/mcp_img.h mcp_init_depth_map_points, mcp_map_mark_optimized, ----
+// ---- mcp_map_rescale, mcp_map_transform; map_life.h) ------------------------------------------------------------------------------
+namespace {
+// one reference on every source keyframe's slot for the length of the call, as SlotHold (slot_release ignores 0)
+struct SlotHolds { mcp_map_points* m; int slot1[MCP_MAX_FRAME_CAMS]; ~SlotHolds() { for (int s : slot1) m->slot_release(s); } };
+
+// a rescale or a rigid motion of the whole map: the MKFs, the rows, and (a rescale with a present slot) the scene depths
+int life_move(mcp_map_graph* g, const std::string& who, const MlXform& X, mcp_map_transform_result* res, mcp_scene_depth* depth_out) {
+  mcp_map_points* m = g->m;
+  std::memset(res, 0, sizeof *res);
+  res->n_rows = m->rows;
+  std::vector<int> slots;
+  for (int k = 0; k < MCP_MAP_MAX_MKFS; ++k) if (g->mirror.present(k)) slots.push_back(k);
+  const int n_mkfs = (int)slots.size(), R = m->rows;
+  res->n_mkfs = n_mkfs;
+  if (R == 0 && n_mkfs == 0) return 0;
+  const bool depth = X.kind == ML_SCALE && n_mkfs > 0;
+  std::vector<int> pos_of;
+  if (depth && mgl_slots_check(g, who, n_mkfs, slots.data(), pos_of)) return -1;
+  ICK(hipSetDevice(m->device));
+  const int n_kf = n_mkfs*g->rig.ncam, nb = mgl_default_blocks(g->n_store);
+  const size_t bits = ((size_t)R + 7)/8;
+  const MglIn L(n_mkfs);
+  mcp_map_graph::Lists& l = g->lists;
+  mcp_map_graph::Life& lf = g->life;
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, std::max<size_t>(bits, 1)) || G.grow(lf.cnt, 4) || G.grow(lf.h_cnt, 4)) return -1;
+  if (depth ? (G.grow(l.in, L.bytes) || G.grow(l.dev, L.bytes) || G.grow(l.out, sizeof(mcp_scene_depth)*(size_t)n_kf) || mgl_reserve(G, g, n_kf, nb)) : g->grow_points(G, R)) return -1;
+  std::memset(g->up.in.p, 0, std::max<size_t>(bits, 1));
+  const bool any_rays = m->rays.on;
+  for (int r = 0; r < R; ++r) if (any_rays && m->has_rays[r]) g->up.in.p[r >> 3] |= (char)(1 << (r & 7));
+  hipStream_t st = m->st;
+  Drain drain{m, true};
+  if (lf.t_move.begin(st)) return -1;
+  if (bits) ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, bits, hipMemcpyHostToDevice, st));
+  ICK(hipMemsetAsync(lf.cnt.p, 0, sizeof(int)*4, st));
+  hipLaunchKernelGGL(k_ml_mkfs, dim3(mg_grid(MG_MAX_MKFS)), dim3(ML_BLOCK), 0, st, X, g->slots.p);
+  if (R) hipLaunchKernelGGL(k_ml_points, dim3(mg_grid(R)), dim3(ML_BLOCK), 0, st, X, g->rig, R, (const MgMkf*)g->slots.p, (const MgPoint*)g->pts.p, (const uint8_t*)g->up.dev.p,
+                            any_rays ? (const double*)m->rays.row() : (const double*)nullptr, m->pts.row(), lf.cnt.p);
+  ICK(hipGetLastError());
+  if (g->staged_now()) return -1;
+  mcp_scene_depth* sd = nullptr;
+  if (depth) {                                         // mcp_graph_refresh_depth's submission over every present slot, at the moved state
+    L.fill(l.in.p, pos_of, n_mkfs, slots.data(), nullptr);
+    sd = reinterpret_cast<mcp_scene_depth*>(l.out.p);
+    const int* d_slots = (const int*)(l.dev.p + L.slots);
+    m->wb.invalidate();
+    ICK(hipMemcpyAsync(l.dev.p, l.in.p, L.bytes, hipMemcpyHostToDevice, st));
+    mgl_enqueue(g, n_kf, nb, (const int*)(l.dev.p + L.pos_of));
+    hipLaunchKernelGGL(k_mgl_cfw, dim3(mg_grid(n_kf, MGL_BLOCK)), dim3(MGL_BLOCK), 0, st, g->rig, n_kf, d_slots, (const MgMkf*)g->slots.p, l.cfw.p, (double*)nullptr);
+    mgl_depth_enqueue(g, n_kf, (const double*)l.cfw.p, nullptr, d_slots, sd);
+    ICK(hipGetLastError());
+  }
+  ICK(hipMemcpyAsync(lf.h_cnt.p, lf.cnt.p, sizeof(int)*4, hipMemcpyDeviceToHost, st));
+  if (lf.t_move.end(st) || g->one_wait(drain, &lf.t_move)) return -1;
+  res->n_refreshed = lf.h_cnt.p[0]; res->n_no_rays = lf.h_cnt.p[1]; res->n_no_source = lf.h_cnt.p[2];
+  if (depth) sd_copy_out(n_kf, sd, depth_out);
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mcp_init_depth_map_points(mcp_map_graph* g, int ncam, const mcp_init_depth_cam* cams, int n_rows, const int* rows, const int* keys, const mcp_init_depth_params* prm,
+                              mcp_init_depth_result* res, mcp_stereo_point* out, uint8_t* keep) {
+  static const char* W = "mcp_init_depth_map_points";
+  const std::string who = W;
+  static const double eye12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!prm || !res) return img_fail(who + ": NULL params or result");
+  mcp_map_points* m = g->m;
+  if (ncam != g->rig.ncam) return img_fail(who + ": ncam is " + std::to_string(ncam) + ", the rig has " + std::to_string(g->rig.ncam) + " cameras");
+  if (!cams) return img_fail(who + ": NULL cams");
+  if (prm->level < 0 || prm->level >= MCP_LEVELS) return img_fail(who + ": level outside 0..3");
+  if (!std::isfinite(prm->init_depth) || !(prm->init_depth > 0.0)) return img_fail(who + ": init_depth must be finite and positive");
+  if (!g->mirror.present(prm->src_mkf)) return img_fail(who + ": the source names MKF slot " + std::to_string(prm->src_mkf) + ", which is not present");
+  long long total = 0, need = 0;
+  for (int c = 0; c < ncam; ++c) {
+    const mcp_init_depth_cam& C = cams[c];
+    if (C.n_cand < 0 || C.limit < 0) return img_fail(who + ": camera " + std::to_string(c) + " has a negative limit or n_cand");
+    total += C.n_cand; need += std::min(C.n_cand, C.limit);
+    if (C.n_cand == 0) continue;
+    if (stereo_check_source(W, C.src, C.cam, eye12, prm->level, C.n_cand, C.cand)) return -1;
+    if (C.src->device != m->device) return img_fail(who + ": camera " + std::to_string(c) + "'s source is on device " + std::to_string(C.src->device) + ", the table on device " + std::to_string(m->device));
+  }
+  if (total > 0x7fffffffLL) return img_fail(who + ": too many candidates");
+  if (n_rows < 0 || n_rows < need) return img_fail(who + ": n_rows < the sum of min(n_cand, limit)");
+  if (n_rows > 0 && (!rows || !keys)) return img_fail(who + ": rows and keys are needed");
+  if (total > 0 && !keep) return img_fail(who + ": keep is needed");
+  int top = m->rows;
+  for (int k = 0; k < n_rows; ++k) { if (rows[k] < 0 || rows[k] == 0x7fffffff) return img_fail(who + ": bad row id"); top = std::max(top, rows[k] + 1); }
+  if (n_rows && mg_distinct(g->sorted_ids, rows, n_rows, who, "row")) return -1;
+  const int first = g->n_store;
+  if ((long long)first + n_rows > 0x7fffffffLL) return img_fail(who + ": the store is full");
+  std::memset(res, 0, sizeof *res);
+  res->first_store = first;
+  if (total == 0) return 0;                            // (nothing to thin, nothing to create: nothing is enqueued)
+
+  ICK(hipSetDevice(m->device));
+  // the table's columns, then the graph's blocks; each grows with nothing in flight on the block it replaces
+  if (m->grow(top) || m->ensure(m->rays)) return -1;
+  const int n_store = first, nblk = mg_grid(n_store), n_total = (int)total;
+  int nb_max = 1;
+  for (int c = 0; c < ncam; ++c) nb_max = std::max(nb_max, mg_grid(cams[c].n_cand));
+  const size_t o_keys = tm_align(sizeof(int)*(size_t)n_rows), o_cand = 2*o_keys, up = o_cand + tm_align(sizeof(mcp_int2)*(size_t)n_total);
+  mcp_map_graph::Stereo& sg = g->stereo;
+  mcp_map_graph::Life& lf = g->life;
+  mcp_map_graph::Guard G(g);
+  if (g->stage(G, up) || G.grow(sg.n_busy, 1) || G.grow(sg.busy, n_store) || G.grow(g->blk, nblk) || G.grow(lf.alive, n_total) || G.grow(lf.blk, nb_max) || G.grow(lf.ctl, 1) ||
+      G.grow(lf.h_ctl, 1) || G.grow(lf.h_keep, n_total) || G.grow(lf.h_out, n_rows) || g->grow_points(G, m->rows) || g->grow_store(G, (size_t)first + (size_t)n_rows)) return -1;
+  std::memset(g->up.in.p, 0, up);
+  if (n_rows) { std::memcpy(g->up.in.p, rows, sizeof(int)*(size_t)n_rows); std::memcpy(g->up.in.p + o_keys, keys, sizeof(int)*(size_t)n_rows); }
+  {
+    size_t at = 0;
+    for (int c = 0; c < ncam; ++c) { if (cams[c].n_cand) std::memcpy(g->up.in.p + o_cand + sizeof(mcp_int2)*at, cams[c].cand, sizeof(mcp_int2)*(size_t)cams[c].n_cand); at += (size_t)cams[c].n_cand; }
+  }
+  SlotHolds hold; hold.m = m;
+  for (int c = 0; c < MCP_MAX_FRAME_CAMS; ++c)
+    hold.slot1[c] = (c < ncam && cams[c].n_cand) ? m->slot_acquire(std::make_pair((const mcp_kf*)cams[c].src, kf_live_serial(cams[c].src))) : 0;
+
+  hipStream_t st = m->st;
+  Drain drain{m, true};
+  // the table's stream waits for whatever each source's stream still has to write of its frame
+  for (int c = 0; c < ncam; ++c) {
+    if (!cams[c].n_cand) continue;
+    ICK(hipEventRecord(cams[c].src->ev, cams[c].src->st));
+    ICK(hipStreamWaitEvent(st, cams[c].src->ev, 0));
+  }
+  if (lf.t_init.begin(st)) return -1;
+  ICK(hipMemcpyAsync(g->up.dev.p, g->up.in.p, up, hipMemcpyHostToDevice, st));
+  ICK(hipMemsetAsync(lf.ctl.p, 0, sizeof(MlInitCtl), st));
+  const char* d = g->up.dev.p;
+  const mcp_store_entry* store = reinterpret_cast<const mcp_store_entry*>(g->store.p);
+  size_t at = 0;
+  for (int c = 0; c < ncam; ++c) {
+    const int n_cand = cams[c].n_cand, nb = mg_grid(n_cand);
+    const mcp_int2* d_cand = reinterpret_cast<const mcp_int2*>(d + o_cand) + at;
+    uint8_t* d_alive = lf.alive.p + at;
+    if (n_cand) {
+      if (n_store) hipLaunchKernelGGL(k_sa_busy_mark, dim3(nblk), dim3(SA_BLOCK), 0, st, store, n_store, prm->src_mkf, c, g->blk.p);
+      hipLaunchKernelGGL(k_sa_busy_gather, dim3(mg_grid1(n_store)), dim3(SA_BLOCK), 0, st, store, n_store, nblk, (const int*)g->blk.p, prm->src_mkf, c, sg.busy.p, n_store, sg.n_busy.p);
+      hipLaunchKernelGGL(k_sa_thin_busy, dim3(nb), dim3(256), 0, st, n_cand, d_cand, (const int*)sg.n_busy.p, n_store, (const mcp_stereo_meas*)sg.busy.p, prm->level, d_alive);
+      hipLaunchKernelGGL(k_ml_alive_mark, dim3(nb), dim3(ML_BLOCK), 0, st, n_cand, (const uint8_t*)d_alive, lf.blk.p);
+    } else
+      ICK(hipMemsetAsync(sg.n_busy.p, 0, sizeof(int), st));      // (no gather ran: the camera reports an empty busy list)
+    MlCreate Q; std::memset(&Q, 0, sizeof Q);
+    if (n_cand) Q.camera = *cams[c].cam;
+    Q.cam = c; Q.n_cand = n_cand; Q.limit = cams[c].limit; Q.level = prm->level; Q.src_mkf = prm->src_mkf; Q.slot1 = hold.slot1[c]; Q.n_rows = n_rows; Q.first_store = first;
+    Q.table_rows = m->rows; Q.graph_rows = g->prow; Q.ncam_states = m->st_ncam; Q.init_depth = prm->init_depth; Q.store_cap = (long long)g->store.n;
+    hipLaunchKernelGGL(k_ml_create, dim3(mg_grid1(n_cand)), dim3(ML_BLOCK), 0, st, Q, g->rig, (const MgMkf*)g->slots.p, d_cand, (const uint8_t*)d_alive, (const int*)lf.blk.p, nb,
+                       (const int*)sg.n_busy.p, lf.ctl.p, (const int*)d, (const int*)(d + o_keys), lf.h_out.p, m->pts.row(), m->src.row(), m->state_ptrs(), m->cnt.row(),
+                       m->rays.row(), g->pts.p, reinterpret_cast<mcp_store_entry*>(g->store.p));
+    at += (size_t)n_cand;
+  }
+  ICK(hipGetLastError());
+  if (g->staged_now()) return -1;
+  ICK(hipMemcpyAsync(lf.h_ctl.p, lf.ctl.p, sizeof(MlInitCtl), hipMemcpyDeviceToHost, st));
+  ICK(hipMemcpyAsync(lf.h_keep.p, lf.alive.p, (size_t)n_total, hipMemcpyDeviceToHost, st));
+  if (lf.t_init.end(st) || g->one_wait(drain, &lf.t_init)) return -1;
+  const MlInitCtl& C = *lf.h_ctl.p;
+  int made_total = 0;
+  for (int c = 0; c < ncam; ++c) {
+    if (C.made[c] < 0 || C.made[c] > std::min(cams[c].n_cand, cams[c].limit) || C.base[c] != made_total) return img_fail(who + ": inconsistent device count");
+    made_total += C.made[c];
+    res->made[c] = C.made[c]; res->n_busy[c] = C.n_busy[c]; res->n_alive[c] = C.n_alive[c];
+  }
+  if (made_total > n_rows) return img_fail(who + ": inconsistent device count");
+  if (out && made_total) std::memcpy(out, lf.h_out.p, sizeof(mcp_stereo_point)*(size_t)made_total);
+  std::memcpy(keep, lf.h_keep.p, (size_t)n_total);
+  // the host's mirrors of the rows that were taken
+  int k = 0;
+  for (int c = 0; c < ncam; ++c) {
+    if (!C.made[c]) continue;
+    const std::pair<const mcp_kf*, unsigned long long> id = m->slots[hold.slot1[c] - 1];
+    for (int j = 0; j < C.made[c]; ++j, ++k) {
+      const int row = rows[k];
+      m->has_rays[row] = 1;
+      const int s1 = m->slot_acquire(id);                // (before the release: a row that keeps its source keeps the slot)
+      m->slot_release(m->row_slot[row]);
+      m->row_slot[row] = s1;
+    }
+  }
+  g->n_store += made_total; g->n_live += made_total;
+  res->made_total = made_total;
+  return made_total;
+}
+
+int mcp_map_life_last_timing(const mcp_map_graph* g, double* init_depth_ms, double* move_ms) {
+  if (!g || !init_depth_ms || !move_ms) return img_fail("mcp_map_life_last_timing: bad arguments");
+  ICK(hipSetDevice(g->m->device));
+  return (g->life.t_init.ms(init_depth_ms) || g->life.t_move.ms(move_ms)) ? -1 : 0;
+}
+
+int mcp_map_mark_optimized(mcp_map_graph* g, int* n_marked) {
+  const std::string who = "mcp_map_mark_optimized";
+  if (!g) return img_fail(who + ": NULL graph");
+  mcp_map_points* m = g->m;
+  if (n_marked) *n_marked = 0;
+  if (m->rows == 0) return 0;
+  ICK(hipSetDevice(m->device));
+  mcp_map_graph::Life& lf = g->life;
+  mcp_map_graph::Guard G(g);
+  if (G.grow(lf.cnt, 4) || G.grow(lf.h_cnt, 4)) return -1;
+  Drain drain{m, true};
+  ICK(hipMemsetAsync(lf.cnt.p, 0, sizeof(int)*4, m->st));
+  hipLaunchKernelGGL(k_ml_mark_optimized, dim3(mg_grid(m->rows)), dim3(ML_BLOCK), 0, m->st, m->rows, std::min(g->prow, m->rows), (const MgPoint*)g->pts.p, m->pts.row(), lf.cnt.p);
+  ICK(hipGetLastError());
+  ICK(hipMemcpyAsync(lf.h_cnt.p, lf.cnt.p, sizeof(int), hipMemcpyDeviceToHost, m->st));
+  if (g->one_wait(drain)) return -1;
+  if (n_marked) *n_marked = lf.h_cnt.p[0];
+  return 0;
+}
+
+int mcp_map_rescale(mcp_map_graph* g, double scale, mcp_map_transform_result* res, mcp_scene_depth* depth_out) {
+  const std::string who = "mcp_map_rescale";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!res) return img_fail(who + ": NULL result");
+  MlXform X;
+  if (const char* why = ml_xform_make(ML_SCALE, scale, nullptr, X)) return img_fail(who + ": " + why);
+  return life_move(g, who, X, res, depth_out);
+}
+
+int mcp_map_transform(mcp_map_graph* g, const double new_from_old[12], mcp_map_transform_result* res) {
+  const std::string who = "mcp_map_transform";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!res) return img_fail(who + ": NULL result");
+  MlXform X;
+  if (const char* why = ml_xform_make(ML_RIGID, 1.0, new_from_old, X)) return img_fail(who + ": " + why);
+  return life_move(g, who, X, res, nullptr);
 }
 
 }  // extern "C"

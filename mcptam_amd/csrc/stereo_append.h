@@ -113,6 +113,28 @@ k_sa_thin_busy(int n_cand, const mcp_int2* __restrict__ cand, const int* __restr
   alive[i] = good ? 1 : 0;
 }
 
+// one created point's row into the table's columns and the graph's: what k_sa_append and k_ml_create (map_life.h) both leave in a row
+__device__ __forceinline__ void sa_write_row(const SaRow& R, int row, int key, int slot1, int ncam_states, PvsPoint* __restrict__ pts, TmSrc* __restrict__ src, TmStates states,
+                                             int* __restrict__ cnt, double* __restrict__ rays, MgPoint* __restrict__ gp) {
+  PvsPoint O;
+  for (int a = 0; a < 3; ++a) { O.world_pos[a] = R.world_pos[a]; O.pixel_right_w[a] = R.pixel_right_w[a]; O.pixel_down_w[a] = R.pixel_down_w[a]; }
+  O.usable = R.usable; O.pad_ = 0;
+  pts[row] = O;
+  cnt[2*(size_t)row] = R.inlier; cnt[2*(size_t)row + 1] = R.outlier;
+#pragma unroll
+  for (int a = 0; a < 9; ++a) rays[9*(size_t)row + a] = R.rays[a];
+  // the source, as k_tm_source_scatter writes it: a row whose key changes forgets what its finders saw
+  if (src[row].key != key)
+    for (int c = 0; c < ncam_states; ++c) {
+      unsigned long long* s = reinterpret_cast<unsigned long long*>(states.s[c] + row);
+      for (int q = 0; q < (int)(sizeof(mcp_pf_state)/8); ++q) s[q] = 0ull;
+    }
+  TmSrc S; S.key = key; S.slot1 = slot1; S.level = R.level; S.cx = R.cx; S.cy = R.cy; S.fixed = R.fixed;
+  src[row] = S;
+  MgPoint G; G.src_mkf = R.gp_src_mkf; G.src_cam = R.gp_src_cam; G.flags = R.gp_flags; G.pending = R.gp_pending;
+  gp[row] = G;
+}
+
 // where an append writes, and how far it may: the blocks were grown on the host to cover every row handed in and 2*n_rows store entries
 struct SaAppend {
   int n_targets, n_rows, level, src_mkf, src_cam, slot1, first_store, table_rows, graph_rows, ncam_states;
@@ -132,24 +154,7 @@ k_sa_append(SaAppend Q, const int* __restrict__ counts /* k_stereo_commit's: cou
   if (row < 0 || row >= Q.table_rows || row >= Q.graph_rows || P.target < 0 || P.target >= Q.n_targets || at + 1 >= Q.store_cap) return;      // (never: checked and grown on the host)
   SaRow R; mcp_store_entry root, epi;
   sa_point(P, row, Q.level, Q.src_mkf, Q.src_cam, target_mkf[P.target], target_cam[P.target], R, root, epi);
-  PvsPoint O;
-  for (int a = 0; a < 3; ++a) { O.world_pos[a] = R.world_pos[a]; O.pixel_right_w[a] = R.pixel_right_w[a]; O.pixel_down_w[a] = R.pixel_down_w[a]; }
-  O.usable = R.usable; O.pad_ = 0;
-  pts[row] = O;
-  cnt[2*(size_t)row] = R.inlier; cnt[2*(size_t)row + 1] = R.outlier;
-#pragma unroll
-  for (int a = 0; a < 9; ++a) rays[9*(size_t)row + a] = R.rays[a];
-  // the source, as k_tm_source_scatter writes it: a row whose key changes forgets what its finders saw
-  const int key = keys[k];
-  if (src[row].key != key)
-    for (int c = 0; c < Q.ncam_states; ++c) {
-      unsigned long long* s = reinterpret_cast<unsigned long long*>(states.s[c] + row);
-      for (int q = 0; q < (int)(sizeof(mcp_pf_state)/8); ++q) s[q] = 0ull;
-    }
-  TmSrc S; S.key = key; S.slot1 = Q.slot1; S.level = R.level; S.cx = R.cx; S.cy = R.cy; S.fixed = R.fixed;
-  src[row] = S;
-  MgPoint G; G.src_mkf = R.gp_src_mkf; G.src_cam = R.gp_src_cam; G.flags = R.gp_flags; G.pending = R.gp_pending;
-  gp[row] = G;
+  sa_write_row(R, row, keys[k], Q.slot1, Q.ncam_states, pts, src, states, cnt, rays, gp);
   store[at] = root; store[at + 1] = epi;
 }
 #endif  // __HIPCC__

@@ -12,14 +12,21 @@
 //     k_stereo_commit    one workgroup: the nLimit rule (:486-493) over the candidates in order and the created points, compacted in creation
 //                        order, into pinned host memory; the running count stays in device memory for the next target.
 // Hand-offs are kernel boundaries on one stream; no workgroup waits for another.
+// Where STEREO_HOST_ONLY is defined only the __host__ __device__ bodies appear (the camera, the arc, the pixel vectors, ReprojectPoint): a host
+// twin that shares them (map_life_host.cpp) must not define the kernels of img_kernels.h a second time.
 #pragma once
+#include <cmath>
+#ifndef STEREO_HOST_ONLY
 #include "img_kernels.h"
+#endif
 #include "map_graph_dist.h"      // se3_inverse
 
 namespace mcp {
 
+#ifndef STEREO_HOST_ONLY
 struct StereoSrcDev { mcp_camera cam; Se3 cfw; const uint8_t* img; int w, h, level; };
 struct StereoTargetDev { DevKfView T; const uint8_t* mask0; mcp_camera cam; Se3 cfw; double opa; };
+#endif
 
 // TaylorCamera::UnProject (src/TaylorCamera.cc:319-347), the arithmetic of mcp_sbi_se3_from_se2 and the oracle
 __host__ __device__ inline void stereo_unproject(const mcp_camera& c, double u, double v, double out[3]) {
@@ -145,13 +152,15 @@ __host__ __device__ inline void stereo_reproject(const Se3& AfromB, const double
   out[0] = v4[0]/v4[3]; out[1] = v4[1]/v4[3]; out[2] = v4[2]/v4[3];
 }
 
-__device__ inline bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 // libCVD ir_rounded: half away from zero (restated from memory of libCVD, not checked against its source here)
-__device__ inline int ir_round(double v) { return (int)(v > 0.0 ? v + 0.5 : v - 0.5); }
-__device__ inline bool stereo_busy(int bx, int by, int cx, int cy) {
+__host__ __device__ inline int ir_round(double v) { return (int)(v > 0.0 ? v + 0.5 : v - 0.5); }
+__host__ __device__ inline bool stereo_busy(int bx, int by, int cx, int cy) {
   const long long dx = (long long)bx - cx, dy = (long long)by - cy;
   return dx*dx + dy*dy < 100;
 }
+
+#ifndef STEREO_HOST_ONLY
+__device__ inline bool finite3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 
 // ThinCandidates against the source's measurements (filtered to level L / L+1, as :422-429)
 __global__ void __launch_bounds__(256)
@@ -312,5 +321,7 @@ k_stereo_hyp_fill(mcp_camera cs, Se3 Ts, Se3 Tt, double opa, int level, int n_ca
     o.source_kf = src_handle; o.source_level = level; o.center_x = cand[i].x; o.center_y = cand[i].y; o.fixed = 0;
   }
 }
+
+#endif  // STEREO_HOST_ONLY
 
 }  // namespace mcp

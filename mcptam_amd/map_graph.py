@@ -25,7 +25,13 @@ closest_multi_keyframe, n_closest_multi_keyframes, furthest_multi_keyframe, clos
 n_closest_keyframes (src/MapMakerBase.cc:90-339) and the tracker's need_new_multi_keyframe / is_distance_to_nearest_mkf_excessive
 (src/MapMakerClientBase.cc:111-226); MapGraph.cull_mkf is MarkFurthestMultiKeyFrameAsBad with the MKF half of HandleBadEntities
 (src/MapMakerServerBase.cc:264-318, src/Map.cc:119-187); neighbours_host / cull_mkf_host are the host twins (no device), neighbours_ref /
-cull_mkf_ref the numpy restatements."""
+cull_mkf_ref the numpy restatements.
+
+How the map begins and how it is rescaled or moved (mcp_init_depth_map_points, mcp_map_mark_optimized, mcp_map_rescale, mcp_map_transform):
+MapGraph.add_init_depth_points is MapMakerServerBase::AddInitDepthMapPoints of one MKF and level for every camera of the rig, mark_optimized the
+mbOptimized loop at the end of InitFromMultiKeyFrame, rescale / transform ApplyGlobalScaleToMap / ApplyGlobalTransformationToMap over the resident
+map (src/MapMakerServerBase.cc:212-215, 499-596); init_depth_host / mark_optimized_host / map_transform_host are the host twins (no device),
+init_depth_ref / mark_optimized_ref / map_transform_ref the numpy restatements."""
 import ctypes
 
 import numpy as np
@@ -932,6 +938,236 @@ def selection_problem(mkfs, points, meas, base_from_world, cam_from_base, cams):
     return q
 
 
+# ---- the map's beginning, its rescale and its re-alignment (include/mcp_img.h mcp_init_depth_map_points, mcp_map_mark_optimized, mcp_map_rescale, ----
+# ---- mcp_map_transform; map_life.h): structs, host twins (no device) and numpy restatements (src/MapMakerServerBase.cc:212-215, 499-596) -----------
+LIFE_SYMBOLS = ["mcp_init_depth_map_points", "mcp_map_mark_optimized", "mcp_map_rescale", "mcp_map_transform", "mcp_init_depth_points_host",
+                "mcp_map_mark_optimized_host", "mcp_map_transform_host", "mcp_map_life_last_timing"]
+XFORM_SCALE, XFORM_RIGID = 0, 1
+LIFE_BLOCK = 256                              # map_life.h: candidates / rows of a workgroup
+
+
+class InitDepthCam(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("cam", ctypes.c_void_p), ("n_cand", ctypes.c_int), ("cand", ctypes.c_void_p), ("limit", ctypes.c_int)]
+
+
+class InitDepthParams(ctypes.Structure):
+    _fields_ = [("src_mkf", ctypes.c_int), ("level", ctypes.c_int), ("init_depth", ctypes.c_double)]
+
+
+class InitDepthResult(ctypes.Structure):
+    _fields_ = [("made_total", ctypes.c_int), ("first_store", ctypes.c_int), ("made", ctypes.c_int * MAX_CAMS), ("n_busy", ctypes.c_int * MAX_CAMS),
+                ("n_alive", ctypes.c_int * MAX_CAMS)]
+
+    def as_dict(self, ncam=MAX_CAMS):
+        return dict(made_total=self.made_total, first_store=self.first_store, made=list(self.made)[:ncam], n_busy=list(self.n_busy)[:ncam],
+                    n_alive=list(self.n_alive)[:ncam])
+
+
+class MapTransformResult(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int), ("n_refreshed", ctypes.c_int), ("n_no_rays", ctypes.c_int), ("n_no_source", ctypes.c_int), ("n_mkfs", ctypes.c_int)]
+
+    def as_dict(self):
+        return {f[0]: getattr(self, f[0]) for f in self._fields_}
+
+
+def _life_lib():
+    L = lib()
+    if getattr(L, "_mcp_life_bound", False):
+        return L
+    vp, ip, dp = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    L.mcp_init_depth_map_points.argtypes = [vp, ip, vp, ip, vp, vp, vp, vp, vp, vp]
+    L.mcp_map_mark_optimized.argtypes = [vp, vp]
+    L.mcp_map_rescale.argtypes = [vp, dp, vp, vp]
+    L.mcp_map_transform.argtypes = [vp, vp, vp]
+    L.mcp_init_depth_points_host.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mcp_map_mark_optimized_host.argtypes = [ip, ip, vp, vp]
+    L.mcp_map_transform_host.argtypes = [ip, dp, vp, ip, vp, ip, vp, vp, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mcp_map_life_last_timing.argtypes = [vp, vp, vp]
+    for n in LIFE_SYMBOLS:
+        getattr(L, n).restype = ip
+    L._mcp_life_bound = True
+    return L
+
+
+def _cand_lists(cands):
+    from .stereo import _cand
+    cs = [_cand(c) for c in cands]
+    return cs, np.array([len(c) for c in cs], dtype=np.int32)
+
+
+def _point_dtype():
+    from .stereo import STEREO_POINT_DTYPE
+    return STEREO_POINT_DTYPE
+
+
+def init_depth_ref(cam_from_base, src_base_from_world, cams, cands, limits, busy, rows, src_mkf, level, init_depth, first_store=0):
+    """AddInitDepthMapPoints (src/MapMakerServerBase.cc:499-546) of one MKF at one level over flat arrays: per camera c ThinCandidates against busy[c]
+    (STEREO_MEAS_DTYPE, the keyframe's measurements), then the first limits[c] survivors in candidate order become points at init_depth along
+    their unprojected ray, with the three patch rays and RefreshPixelVectors.  cams: TaylorCamera objects; cands: per camera (n, 2) level
+    positions.  Point k (camera-major, then candidate order) takes rows[k].  Returns a dict: keep (per camera bool arrays), made, n_alive, n_busy,
+    points (STEREO_POINT_DTYPE) and what the points become in the map, as stereo_append_ref names it, with ONE store entry each."""
+    from . import stereo as S
+    cfb = _f64(cam_from_base).reshape(-1, 12)
+    bfw = _f64(src_base_from_world).reshape(12)
+    cs, _ = _cand_lists(cands)
+    r = _i32(rows)
+    keep, made, alive, nbusy, recs, cam_of = [], [], [], [], [], []
+    for c, cam in enumerate(cams):
+        Rw, tw = _compose(cfb[c, :9].reshape(3, 3), cfb[c, 9:], bfw[:9].reshape(3, 3), bfw[9:])      # CamFromWorld = CamFromBase * BaseFromWorld
+        b = np.asarray(busy[c], dtype=S.STEREO_MEAS_DTYPE)
+        k = S.thin_candidates(cs[c], level, b["root_pos"], b["level"]) if len(cs[c]) else np.zeros(0, dtype=bool)
+        keep.append(k)
+        take = np.flatnonzero(k)[:int(limits[c])]
+        alive.append(int(k.sum())); made.append(len(take)); nbusy.append(len(b))
+        p = np.zeros(len(take), dtype=S.STEREO_POINT_DTYPE)
+        for j, i in enumerate(take):
+            root, ce, ri, dn = S.probe(cam, level, cs[c][i])
+            ray = cam.unproject(root)[0]                                   # v3UnProj = UnProject(v2RootPos) * dInitDepth
+            world = Rw.T @ (ray * float(init_depth) - tw)                  # mse3CamFromWorld.inverse() * v3UnProj
+            pr, pd = S.pixel_vectors((Rw, tw), ce, ri, dn, world)
+            p[j] = (i, -1, 0, 0, world, root, (0.0, 0.0), ce, ri, dn, pr[0], pd[0])
+        recs.append(p); cam_of += [c] * len(take)
+    pts = np.concatenate(recs) if recs else np.zeros(0, dtype=S.STEREO_POINT_DTYPE)
+    n = len(pts)
+    if n > len(r):
+        raise ValueError("init_depth_ref: fewer rows than points")
+    cam_of = np.array(cam_of, dtype=np.int32)
+    ap = np.zeros(n, dtype=STORE_ENTRY_DTYPE)
+    ap["uv"], ap["mkf"], ap["cam"], ap["row"], ap["level"], ap["source"], ap["alive"] = pts["root_pos"], src_mkf, cam_of, r[:n], level, SRC_ROOT, 1
+    centre = np.concatenate([cs[c][np.flatnonzero(keep[c])[:made[c]]] for c in range(len(cams))]).astype(np.int32).reshape(n, 2) if n else np.zeros((0, 2), np.int32)
+    return dict(keep=keep, made=made, n_alive=alive, n_busy=nbusy, made_total=n, points=pts, world_pos=pts["world_pos"].copy(),
+                pixel_right_w=pts["pixel_right_w"].copy(), pixel_down_w=pts["pixel_down_w"].copy(), usable=np.zeros(n, dtype=np.uint8),
+                inlier=np.ones(n, dtype=np.int32), outlier=np.zeros(n, dtype=np.int32),
+                rays=np.concatenate([pts["center_nc"], pts["one_right_nc"], pts["one_down_nc"]], axis=1).reshape(n, 9),
+                source_level=np.full(n, level, dtype=np.int32), center_xy=centre, fixed=np.zeros(n, dtype=np.uint8),
+                gp_src_mkf=np.full(n, src_mkf, dtype=np.int32), gp_src_cam=cam_of, gp_flags=np.zeros(n, dtype=np.int32), appended=ap,
+                store_end=int(first_store) + n)
+
+
+def init_depth_host(cam_from_base, src_base_from_world, cams, cands, limits, busy, rows, src_mkf, level, init_depth, first_store=0):
+    """mcp_init_depth_points_host: the bodies the kernels call, under the host compiler.  Needs no device.  Arguments and result as init_depth_ref
+    (the constant columns -- usable, counts, level, fixed -- are the kernel's own and are not returned).  A refusal raises RuntimeError."""
+    from .stereo import STEREO_MEAS_DTYPE
+    from .taylor_camera import camera_array
+    cfb = _f64(cam_from_base).reshape(-1, 12)
+    nc = len(cfb)
+    bfw = _f64(src_base_from_world).reshape(12)
+    cs, ncand = _cand_lists(cands)
+    cand = np.ascontiguousarray(np.concatenate(cs)) if nc else np.zeros((0, 2), np.int32)
+    bs = [np.ascontiguousarray(b, dtype=STEREO_MEAS_DTYPE) for b in busy]
+    nb = np.array([len(b) for b in bs], dtype=np.int32)
+    bcat = np.ascontiguousarray(np.concatenate(bs)) if nc else np.zeros(0, dtype=STEREO_MEAS_DTYPE)
+    lim = _i32(limits, (nc,))
+    r = _i32(rows)
+    m = max(len(r), 1)
+    arr = camera_array(cams)
+    prm, res = InitDepthParams(int(src_mkf), int(level), float(init_depth)), InitDepthResult()
+    keep = np.zeros(max(len(cand), 1), dtype=np.uint8)
+    o = dict(points=np.zeros(m, dtype=_point_dtype()), world_pos=np.zeros((m, 3)), pixel_right_w=np.zeros((m, 3)), pixel_down_w=np.zeros((m, 3)), rays=np.zeros((m, 9)),
+             center_xy=np.zeros((m, 2), np.int32), gp_src_mkf=np.zeros(m, np.int32), gp_src_cam=np.zeros(m, np.int32), gp_flags=np.zeros(m, np.int32),
+             appended=np.zeros(m, dtype=STORE_ENTRY_DTYPE))
+    n = _chk(_life_lib().mcp_init_depth_points_host(nc, cfb.ctypes.data, bfw.ctypes.data, ctypes.addressof(arr), ncand.ctypes.data, cand.ctypes.data if len(cand) else None,
+                                                    lim.ctypes.data, nb.ctypes.data, bcat.ctypes.data if len(bcat) else None, len(r), r.ctypes.data if len(r) else None,
+                                                    ctypes.addressof(prm), int(first_store), ctypes.addressof(res), keep.ctypes.data,
+                                                    *[o[k].ctypes.data for k in ("points", "world_pos", "pixel_right_w", "pixel_down_w", "rays", "center_xy", "gp_src_mkf",
+                                                                                 "gp_src_cam", "gp_flags", "appended")]), "init_depth_points_host")
+    out = {k: v[:n] for k, v in o.items()}
+    off = np.concatenate([[0], np.cumsum(ncand)])
+    out.update(res.as_dict(nc), keep=[keep[off[c]:off[c + 1]].astype(bool) for c in range(nc)], store_end=int(first_store) + n)
+    return out
+
+
+def mark_optimized_ref(usable, point_flags):
+    """The loop at src/MapMakerServerBase.cc:212-215 over the table: usable = 1 on every row the graph's point columns cover and do not call bad.
+    point_flags: the columns of the rows written or filled so far (the rest of the table was never written).  Returns (usable, count)."""
+    u = np.array(usable, dtype=np.uint8)
+    pf = _i32(point_flags)
+    hit = np.zeros(len(u), dtype=bool)
+    n = min(len(u), len(pf))
+    hit[:n] = (pf[:n] & GP_BAD) == 0
+    u[hit] = 1
+    return u, int(hit.sum())
+
+
+def mark_optimized_host(usable, point_flags):
+    """mcp_map_mark_optimized_host (no device): (usable, count)."""
+    u = np.ascontiguousarray(usable, dtype=np.uint8).copy()
+    pf = _i32(point_flags)
+    n = _chk(_life_lib().mcp_map_mark_optimized_host(len(u), len(pf), pf.ctypes.data if len(pf) else None, u.ctypes.data if len(u) else None), "map_mark_optimized_host")
+    return u, n
+
+
+def _xform_args(scale, new_from_old):
+    if (scale is None) == (new_from_old is None):
+        raise ValueError("give either scale or new_from_old (R, t)")
+    if scale is not None:
+        return XFORM_SCALE, float(scale), None
+    R, t = new_from_old
+    return XFORM_RIGID, 1.0, np.ascontiguousarray(np.concatenate([np.asarray(R, dtype=np.float64).reshape(9), np.asarray(t, dtype=np.float64).reshape(3)]))
+
+
+def _row_sources(a, n_rows):
+    """(src_mkf, src_cam, has a present source keyframe of the rig) per table row; rows past the graph's point columns have no source"""
+    sm, sc = np.full(n_rows, -1, dtype=np.int64), np.zeros(n_rows, dtype=np.int64)
+    k = min(n_rows, len(a["src_mkf"]))
+    sm[:k], sc[:k] = np.asarray(a["src_mkf"])[:k], np.asarray(a["src_cam"])[:k]
+    mf = np.asarray(a["mkf_flags"])
+    ok = (sm >= 0) & (sm < len(mf)) & (sc >= 0) & (sc < a["ncam"])
+    ok[ok] = (mf[sm[ok]] & MKF_PRESENT) != 0
+    return sm, sc, ok
+
+
+def map_transform_ref(a, scale=None, new_from_old=None):
+    """ApplyGlobalScaleToMap (src/MapMakerServerBase.cc:549-574) or ApplyGlobalTransformationToMap (:577-596) over flat arrays, without the scene
+    depths.  a: ncam, cam_from_base, base_from_world (P, 12), mkf_flags, src_mkf / src_cam (the graph's point columns), has_rays, rays (N, 9),
+    world_pos, pixel_right_w, pixel_down_w (N, 3).  Every present MKF moves; a row whose column names a present MKF and a camera of the rig gets
+    its new world position and, with rays, RefreshPixelVectors at its source keyframe's NEW CamFromWorld; other rows keep their values.  Returns
+    (dict(base_from_world, world_pos, pixel_right_w, pixel_down_w), counters)."""
+    from .stereo import pixel_vectors
+    kind, s, T = _xform_args(scale, new_from_old)
+    bfw = _f64(a["base_from_world"]).reshape(-1, 12).copy()
+    mf = _i32(a["mkf_flags"])
+    pres = (mf & MKF_PRESENT) != 0
+    if kind == XFORM_SCALE:
+        bfw[pres, 9:] *= s                                                         # mse3BaseFromWorld.get_translation() *= dScale
+    else:
+        Rn, tn = T[:9].reshape(3, 3), T[9:]
+        Ri, ti = Rn.T, -(Rn.T @ tn)                                                # se3NewFromOld.inverse()
+        for k in np.flatnonzero(pres):
+            Rb, tb = bfw[k, :9].reshape(3, 3), bfw[k, 9:]
+            bfw[k, :9], bfw[k, 9:] = (Rb @ Ri).reshape(9), Rb @ ti + tb            # mse3BaseFromWorld * se3NewFromOld.inverse()
+    wp, pr, pd = (_f64(a[k]).reshape(-1, 3).copy() for k in ("world_pos", "pixel_right_w", "pixel_down_w"))
+    N = len(wp)
+    rays, has = _f64(a["rays"]).reshape(-1, 9), np.asarray(a["has_rays"]).astype(bool)
+    cfb = _f64(a["cam_from_base"]).reshape(-1, 12)
+    sm, sc, ok = _row_sources(a, N)
+    for r in np.flatnonzero(ok):
+        wp[r] = wp[r] * s if kind == XFORM_SCALE else Rn @ wp[r] + tn
+        if has[r]:
+            Rw, tw = _compose(cfb[sc[r], :9].reshape(3, 3), cfb[sc[r], 9:], bfw[sm[r], :9].reshape(3, 3), bfw[sm[r], 9:])
+            a_, b_ = pixel_vectors((Rw, tw), rays[r, :3], rays[r, 3:6], rays[r, 6:], wp[r])
+            pr[r], pd[r] = a_[0], b_[0]
+    cnt = dict(n_rows=N, n_refreshed=int((ok & has).sum()), n_no_rays=int((ok & ~has).sum()), n_no_source=int((~ok).sum()), n_mkfs=int(pres.sum()))
+    return dict(base_from_world=bfw, world_pos=wp, pixel_right_w=pr, pixel_down_w=pd), cnt
+
+
+def map_transform_host(a, scale=None, new_from_old=None):
+    """mcp_map_transform_host: the bodies the kernels call, under the host compiler.  Needs no device.  Arguments and result as map_transform_ref."""
+    kind, s, T = _xform_args(scale, new_from_old)
+    cfb = _f64(a["cam_from_base"]).reshape(-1, 12)
+    bfw = _f64(a["base_from_world"]).reshape(-1, 12).copy()
+    mf = _i32(a["mkf_flags"], (len(bfw),))
+    wp, pr, pd = (_f64(a[k]).reshape(-1, 3).copy() for k in ("world_pos", "pixel_right_w", "pixel_down_w"))
+    N = len(wp)
+    rays, has = _f64(a["rays"]).reshape(-1, 9), _u8(a["has_rays"], (N,))
+    sm, sc = _i32(a["src_mkf"]), _i32(a["src_cam"], (len(a["src_mkf"]),))
+    res = MapTransformResult()
+    p = lambda x: x.ctypes.data if x.size else None      # noqa: E731
+    _chk(_life_lib().mcp_map_transform_host(kind, s, None if T is None else T.ctypes.data, int(a["ncam"]), cfb.ctypes.data, len(bfw), p(bfw), p(mf), N, len(sm), p(sm), p(sc),
+                                            p(has), p(rays), p(wp), p(pr), p(pd), ctypes.addressof(res)), "map_transform_host")
+    return dict(base_from_world=bfw, world_pos=wp, pixel_right_w=pr, pixel_down_w=pd), res.as_dict()
+
+
 # ---- the device graph ----------------------------------------------------------------------------------------------------------------------
 class MapGraph:
     """The device-resident map graph of one MapPointTable (which must outlive it).  Slots are MKF indices, rows are the table's rows."""
@@ -1031,6 +1267,73 @@ class MapGraph:
         two entries of the store on the device -- see mcptam_amd.stereo.stereo_map_points, whose result it returns."""
         from .stereo import stereo_map_points
         return stereo_map_points(self, src, src_cam, src_pose, level, cand, targets, target_mkf, target_cam, rows, keys, src_mkf, src_cam_index, **kw)
+
+    # ---- the map's beginning, its rescale and its re-alignment (mcp_init_depth_map_points, mcp_map_mark_optimized, mcp_map_rescale, mcp_map_transform) ----
+    def add_init_depth_points(self, srcs, cams, cands, limits, rows, keys, src_mkf, level, init_depth, want_points=True):
+        """mcp_init_depth_map_points: AddInitDepthMapPoints of MKF slot src_mkf at `level`, every camera of the rig in one call.  srcs: the
+        keyframes (KeyFrame or None for a camera without candidates), cams: their TaylorCameras, cands: per camera (n, 2) level positions,
+        limits: nLimit per camera.  Created point k (camera-major, then candidate order) takes rows[k] / keys[k] and one store entry.  Returns
+        (points (STEREO_POINT_DTYPE) or None, keep masks per camera, dict of mcp_init_depth_result)."""
+        L = _life_lib()
+        cs, ncand = _cand_lists(cands)
+        nc = len(cs)
+        if not (len(srcs) == len(cams) == len(limits) == nc):
+            raise ValueError("add_init_depth_points: lengths differ")
+        structs = [c.to_struct() for c in cams]
+        tab = (InitDepthCam * max(nc, 1))()
+        for c in range(nc):
+            tab[c].src = srcs[c]._h if srcs[c] is not None else None
+            tab[c].cam = ctypes.addressof(structs[c])
+            tab[c].n_cand, tab[c].cand, tab[c].limit = int(ncand[c]), (cs[c].ctypes.data if len(cs[c]) else None), int(limits[c])
+        r, k = _i32(rows), _i32(keys)
+        if len(r) != len(k):
+            raise ValueError("add_init_depth_points: rows and keys differ in length")
+        total = int(ncand.sum())
+        out = np.zeros(max(len(r), 1), dtype=_point_dtype()) if want_points else None
+        keep = np.zeros(max(total, 1), dtype=np.uint8)
+        prm, res = InitDepthParams(int(src_mkf), int(level), float(init_depth)), InitDepthResult()
+        n = _chk(L.mcp_init_depth_map_points(self._h, nc, ctypes.addressof(tab), len(r), r.ctypes.data if len(r) else None, k.ctypes.data if len(k) else None,
+                                             ctypes.addressof(prm), ctypes.addressof(res), out.ctypes.data if out is not None else None, keep.ctypes.data),
+                 "init_depth_map_points")
+        del structs
+        off = np.concatenate([[0], np.cumsum(ncand)])
+        return (out[:n].copy() if out is not None else None), [keep[off[c]:off[c + 1]].astype(bool) for c in range(nc)], res.as_dict(nc)
+
+    def mark_optimized(self):
+        """mcp_map_mark_optimized: usable = 1 on every row whose graph column has been written and is not GP_BAD (the end of
+        InitFromMultiKeyFrame).  Returns the number of rows named."""
+        n = ctypes.c_int(0)
+        _chk(_life_lib().mcp_map_mark_optimized(self._h, ctypes.addressof(n)), "map_mark_optimized")
+        return n.value
+
+    def _refresh_pose_mirror(self):
+        m = self.get_mkfs()
+        pres = (m["flags"] & MKF_PRESENT) != 0
+        self.base_from_world[pres] = m["base_from_world"][pres]
+
+    def rescale(self, scale, want_depth=True):
+        """mcp_map_rescale: ApplyGlobalScaleToMap over the resident map.  Returns (dict of mcp_map_transform_result, SCENE_DEPTH_DTYPE records of
+        the present slots x ncam in ascending slot order, or None)."""
+        from .pvs import SCENE_DEPTH_DTYPE
+        res = MapTransformResult()
+        depth = np.zeros(MAX_MKFS * self.ncam, dtype=SCENE_DEPTH_DTYPE) if want_depth else None
+        _chk(_life_lib().mcp_map_rescale(self._h, float(scale), ctypes.addressof(res), depth.ctypes.data if depth is not None else None), "map_rescale")
+        self._refresh_pose_mirror()
+        return res.as_dict(), (depth[:res.n_mkfs * self.ncam].copy() if depth is not None else None)
+
+    def transform(self, R, t):
+        """mcp_map_transform: ApplyGlobalTransformationToMap with se3NewFromOld = (R, t).  Returns the dict of mcp_map_transform_result."""
+        T = _xform_args(None, (R, t))[2]
+        res = MapTransformResult()
+        _chk(_life_lib().mcp_map_transform(self._h, T.ctypes.data, ctypes.addressof(res)), "map_transform")
+        self._refresh_pose_mirror()
+        return res.as_dict()
+
+    def life_last_timing(self):
+        """Device times in ms of the last add_init_depth_points() and of the last rescale() / transform(); -1 before the first."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _chk(_life_lib().mcp_map_life_last_timing(self._h, ctypes.addressof(a), ctypes.addressof(b)), "map_life_last_timing")
+        return a.value, b.value
 
     def erase_meas(self, mkf, cam, row):
         """KeyFrame::EraseMeasurementOfPoint for distinct keys; returns how many live entries died."""

@@ -116,9 +116,9 @@ void GraphEraseMKF(Map& map, MultiKeyFrame& mkf)
   mkf.mnGraphSlot = -1;
 }
 
-// MapPoint created, its source set, mbFixed / mbBad changed by the host (AddInitDepthMapPoints and the initialisers, HandleBadPoints): the graph columns of its row.
+// MapPoint created, its source set, mbFixed / mbBad changed by the host (initialisers other than InitFromMultiKeyFrame, HandleBadPoints): the graph columns of its row.
 // Not for the rows HandleOutliers / HandleBadEntities turn bad: the device marks those itself (mcp_map_cull_*) and reports them; and not for the points of
-// AddStereoMapPoints, whose rows mcp_stereo_map_points writes on the device (shim/MapMakerServerBase_gpu.cc).  Its MapPoint columns go to the table as before.
+// AddStereoMapPoints / AddInitDepthMapPoints, whose rows mcp_stereo_map_points / mcp_init_depth_map_points write on the device (shim/MapMakerServerBase_gpu.cc).  Its MapPoint columns go to the table as before.
 void GraphUploadPoints(Map& map, const std::vector<MapPoint*>& vpPoints)
 {
   const int n = (int)vpPoints.size();

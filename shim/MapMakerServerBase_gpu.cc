@@ -16,7 +16,9 @@
 // AddStereoMapPoints also needs the map's row allocator -- in class Map: std::vector<int> mvFreeRows; int mnNextRow, mnNextKey -- and
 // MapPoint::mnTableKey next to mnTableRow (the key the row carries for this point: parcels and the finders tell points apart by it).
 // At the end of this file: HandleOutliers (:1198-1238) and MapMaker::HandleBadEntities (src/MapMaker.cc:477-492) over mcp_map_cull_outliers /
-// mcp_map_cull_sweep, and MarkFurthestMultiKeyFrameAsBad (:264-318) over mcp_map_mkf_cull -- delete those three bodies too.
+// mcp_map_cull_sweep, and MarkFurthestMultiKeyFrameAsBad (:264-318) over mcp_map_mkf_cull -- delete those three bodies too; then InitFromMultiKeyFrame
+// (:146-261), AddInitDepthMapPoints (:499-546), ApplyGlobalScaleToMap (:549-574) and ApplyGlobalTransformationToMap (:577-596) over
+// mcp_init_depth_map_points, mcp_map_mark_optimized, mcp_map_rescale and mcp_map_transform -- delete those four bodies as well.
 #include <mcptam/MapMakerServerBase.h>
 #include <mcptam/MapMaker.h>
 #include <mcptam/BundleAdjusterBase.h>
@@ -673,4 +675,274 @@ void MapMakerServerBase::MarkFurthestMultiKeyFrameAsBad(MultiKeyFrame& mkf)
     mBundleAdjuster.mvpSlotMKF[res.new_fixed]->mbFixed = true;
   ROS_INFO_STREAM("MarkFurthestMultiKeyFrameAsBad: slot " << res.victim << " at distance " << res.victim_dist << ", " << res.n_victim_meas << " measurements, "
                   << res.n_rows_marked << " points go bad (" << res.n_by_count << " by count, " << res.n_by_source << " by source)");
+}
+
+// ---- The map's beginning, its rescale and its re-alignment on the device ------------------------------------------------------------------------------
+// Replace, in /root/reference/src/MapMakerServerBase.cc: InitFromMultiKeyFrame (:146-261), AddInitDepthMapPoints (:499-546), ApplyGlobalScaleToMap
+// (:549-574) and ApplyGlobalTransformationToMap (:577-596) by the four bodies below.  The points of ssInitPointMode "idp" / "both" no longer go up by
+// hand (mcp_map_points_update, _update_rays, _update_source, mcp_map_graph_update_points, mcp_map_graph_add_meas): mcp_init_depth_map_points makes
+// them where the map lives, all cameras of the MKF in one call, with the row hand-off of AddStereoMapPoints above.  A rescale or a re-alignment
+// no longer tears the table and the graph down: mcp_map_rescale / mcp_map_transform rewrite every pose, every point and its pixel vectors (and,
+// for a rescale, every keyframe's scene depth) in one submission, and every row keeps its finder state.  The host's own objects follow from the
+// read-backs (mcp_map_points_get, mcp_graph_get_mkfs, depth_out); they are what the reference's host code (the tracker's hand-over, the
+// queues) goes on reading.
+void GraphUploadMKFs(Map& map, const std::vector<MultiKeyFrame*>& vpMKFs, const std::vector<std::string>& vCamNames);      // shim/BundleAdjusterBase_gpu.cc
+void GraphRefreshSceneDepth(Map& map, MultiKeyFrame& mkf, const std::vector<std::string>& vCamNames);
+
+bool MapMakerServerBase::InitFromMultiKeyFrame(MultiKeyFrame* pMKF, bool bPutPlaneAtOrigin)
+{
+  ROS_INFO("MapMakerServerBase::InitFromMultiKeyFrame");
+  pMKF->mbFixed = true;
+  pMKF->mse3BaseFromWorld = SE3<>();
+  for(KeyFramePtrMap::iterator it = pMKF->mmpKeyFrames.begin(); it != pMKF->mmpKeyFrames.end(); it++)
+  {
+    KeyFrame& kf = *(it->second);
+    kf.mse3CamFromWorld = kf.mse3CamFromBase * pMKF->mse3BaseFromWorld;
+    kf.mdSceneDepthMean = 100;
+    kf.mdSceneDepthSigma = 100000;
+    kf.MakeKeyFrame_Rest();
+  }
+  mMap.mlpMultiKeyFrames.push_back(pMKF);
+  // its slot: pose, flags and the depth mean of 100 (:158) go up once; everything below reads them from the graph
+  int nSlot = 0;                                  // the first free slot of mvpSlotMKF, as where an MKF enters the map from the queue
+  while(nSlot < (int)mBundleAdjuster.mvpSlotMKF.size() && mBundleAdjuster.mvpSlotMKF[nSlot])
+    ++nSlot;
+  if(nSlot == (int)mBundleAdjuster.mvpSlotMKF.size())
+    mBundleAdjuster.mvpSlotMKF.push_back(NULL);
+  mBundleAdjuster.mvpSlotMKF[nSlot] = pMKF;
+  pMKF->mnGraphSlot = nSlot;
+  GraphUploadMKFs(mMap, std::vector<MultiKeyFrame*>(1, pMKF), mBundleAdjuster.mvCamNames);
+
+  const int nNumCams = pMKF->mmpKeyFrames.size();
+  static gvar3<int> gvnLevelZeroPoints("LevelZeroPoints", 0, HIDDEN|SILENT);
+  ROS_INFO_STREAM("==== STARTING INIT POINT CREATION, MODE: "<<MapMakerServerBase::ssInitPointMode<<"  =========");
+  for(int l = 3; l >= 0; --l)
+  {
+    if(l == 0 && *gvnLevelZeroPoints == false)
+      continue;
+    const int nLevelLimit = MapMakerServerBase::snMaxInitPointsLevelZero/LevelScale(l);
+    int nNumPointsBefore = mMap.mlpPoints.size();
+    if(MapMakerServerBase::ssInitPointMode == "stereo" || MapMakerServerBase::ssInitPointMode == "both")
+      AddStereoMapPoints(*pMKF, l, nLevelLimit, std::numeric_limits<double>::max(), KF_ONLY_SELF);     // the body above: mcp_stereo_map_points
+    const int nLevelPoints = mMap.mlpPoints.size() - nNumPointsBefore;
+    const int nLevelPointsLeft = (nLevelLimit*nNumCams - nLevelPoints)/nNumCams;
+    ROS_INFO_STREAM("Level "<<l<<" made "<<nLevelPoints<<" with stereo, "<<nLevelPointsLeft<<" points left to make with each cam");
+    if(nLevelPointsLeft < 1)
+      continue;
+    nNumPointsBefore = mMap.mlpPoints.size();
+    if(MapMakerServerBase::ssInitPointMode == "idp" || MapMakerServerBase::ssInitPointMode == "both")
+      AddInitDepthMapPoints(*pMKF, l, nLevelPointsLeft, MapMakerServerBase::sdInitDepth);
+    ROS_INFO_STREAM("Made "<<mMap.mlpPoints.size() - nNumPointsBefore<<" points with Init Depth");
+  }
+  if((int)mMap.mlpPoints.size() < MapMakerServerBase::snMinMapPoints)
+  {
+    ROS_ERROR_STREAM("MapMakerServerBase: Epipolar matching and init depth method didn't make enough map points: "<<mMap.mlpPoints.size()<<"  Minimum is: "<<MapMakerServerBase::snMinMapPoints);
+    return false;
+  }
+  // :212-215 -- the tracker may track these points: usable = 1 on every row of the table that the graph knows and does not call bad
+  int nMarked = 0;
+  if(mcp_map_mark_optimized(mMap.mpMapGraph, &nMarked) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_mark_optimized: "<<mcp_last_error());
+    ROS_BREAK();
+  }
+  for(MapPointPtrList::iterator point_it = mMap.mlpPoints.begin(); point_it != mMap.mlpPoints.end(); ++point_it)
+    (*point_it)->mbOptimized = true;
+  if(nMarked != (int)mMap.mlpPoints.size())
+    ROS_WARN_STREAM("InitFromMultiKeyFrame: the device marked "<<nMarked<<" rows, the map holds "<<mMap.mlpPoints.size()<<" points");
+  mBundleAdjuster.SetNotConverged();
+  GraphRefreshSceneDepth(mMap, *pMKF, mBundleAdjuster.mvCamNames);     // pMKF->RefreshSceneDepthRobust() (:219): mcp_graph_refresh_depth
+  ROS_INFO_STREAM("MapMakerServerBase: Made initial map with " << mMap.mlpPoints.size());
+  mMap.mbGood = true;
+  return true;
+}
+
+void MapMakerServerBase::AddInitDepthMapPoints(MultiKeyFrame& mkfSrc, int nLevel, int nLimit, double dInitDepth)
+{
+  const std::vector<std::string>& vCamNames = mBundleAdjuster.mvCamNames;
+  const int nc = (int)vCamNames.size();
+  std::vector<mcp_init_depth_cam> vCams(nc);
+  std::vector<mcp_camera> vCamModels(nc);
+  std::vector<std::vector<mcp_int2> > vvCand(nc);
+  std::vector<KeyFrame*> vpKFs(nc, (KeyFrame*)NULL);
+  int nTotal = 0, nNeed = 0;
+  for(int c = 0; c < nc; ++c)
+  {
+    std::memset(&vCams[c], 0, sizeof vCams[c]);
+    KeyFramePtrMap::iterator kf_it = mkfSrc.mmpKeyFrames.find(vCamNames[c]);
+    if(kf_it == mkfSrc.mmpKeyFrames.end())
+      continue;                                   // a camera the MKF does not have: no candidates
+    KeyFrame& kfSrc = *(kf_it->second);
+    vpKFs[c] = &kfSrc;
+    Level& level = kfSrc.maLevels[nLevel];
+    vvCand[c].resize(level.vCandidates.size());
+    for(unsigned i = 0; i < vvCand[c].size(); ++i)
+    {
+      vvCand[c][i].x = level.vCandidates[i].irLevelPos.x;
+      vvCand[c][i].y = level.vCandidates[i].irLevelPos.y;
+    }
+    vCamModels[c] = mcptam_hip::CameraExport::Make(mmCameraModels[kfSrc.mCamName]);
+    ROS_ASSERT(kfSrc.mpDev);
+    vCams[c].src = kfSrc.mpDev;
+    vCams[c].cam = &vCamModels[c];
+    vCams[c].n_cand = (int)vvCand[c].size();
+    vCams[c].cand = vvCand[c].empty() ? NULL : &vvCand[c][0];
+    vCams[c].limit = nLimit;
+    nTotal += vCams[c].n_cand;
+    nNeed += std::min(vCams[c].n_cand, nLimit);
+  }
+  std::vector<int> vRows, vKeys;
+  TakeFreeRows(mMap, nNeed, vRows, vKeys);
+  std::vector<mcp_stereo_point> vOut(nNeed + 1);
+  std::vector<uint8_t> vKeep(nTotal + 1);
+  mcp_init_depth_params params;
+  params.src_mkf = mkfSrc.mnGraphSlot;
+  params.level = nLevel;
+  params.init_depth = dInitDepth;
+  mcp_init_depth_result result;
+  const int nMade = mcp_init_depth_map_points(mMap.mpMapGraph, nc, &vCams[0], nNeed, nNeed ? &vRows[0] : NULL, nNeed ? &vKeys[0] : NULL, &params, &result, &vOut[0], &vKeep[0]);
+  if(nMade < 0)
+  {
+    ROS_FATAL_STREAM("MapMakerServerBase::AddInitDepthMapPoints: "<<mcp_last_error());
+    ros::shutdown();
+    return;
+  }
+  ReturnFreeRows(mMap, vRows, nMade);
+  if((int)mBundleAdjuster.mvpRowPoint.size() < mMap.mnNextRow)
+    mBundleAdjuster.mvpRowPoint.resize(mMap.mnNextRow, NULL);
+  // The host objects follow the records (:517-541), camera by camera in creation order; their rows, graph columns and store entries are on the
+  // device already
+  int k = 0, nCandAt = 0;
+  for(int c = 0; c < nc; ++c)
+  {
+    if(!vpKFs[c])
+      continue;
+    KeyFrame& kfSrc = *vpKFs[c];
+    Level& level = kfSrc.maLevels[nLevel];
+    std::cout<<"AddInitDepthMapPoints, processing "<<level.vCandidates.size()<<" candidates"<<std::endl;
+    for(int j = 0; j < result.made[c]; ++j, ++k)
+    {
+      const mcp_stereo_point& r = vOut[k];
+      MapPoint* pPointNew = new MapPoint;
+      pPointNew->mnTableRow = vRows[k];
+      pPointNew->mnTableKey = vKeys[k];
+      mBundleAdjuster.mvpRowPoint[vRows[k]] = pPointNew;
+      pPointNew->mv3WorldPos = makeVector(r.world_pos[0], r.world_pos[1], r.world_pos[2]);
+      pPointNew->mpPatchSourceKF = &kfSrc;
+      pPointNew->mbFixed = false;
+      pPointNew->mnSourceLevel = nLevel;
+      pPointNew->mv3Normal_NC = makeVector(0, 0, -1);
+      pPointNew->mirCenter = level.vCandidates[r.candidate].irLevelPos;
+      pPointNew->mv3Center_NC = makeVector(r.center_nc[0], r.center_nc[1], r.center_nc[2]);
+      pPointNew->mv3OneRightFromCenter_NC = makeVector(r.one_right_nc[0], r.one_right_nc[1], r.one_right_nc[2]);
+      pPointNew->mv3OneDownFromCenter_NC = makeVector(r.one_down_nc[0], r.one_down_nc[1], r.one_down_nc[2]);
+      pPointNew->mv3PixelRight_W = makeVector(r.pixel_right_w[0], r.pixel_right_w[1], r.pixel_right_w[2]);     // RefreshPixelVectors, on the device
+      pPointNew->mv3PixelDown_W = makeVector(r.pixel_down_w[0], r.pixel_down_w[1], r.pixel_down_w[2]);
+      mMap.mlpPoints.push_back(pPointNew);
+      Measurement* pMeas = new Measurement;
+      pMeas->v2RootPos = makeVector(r.root_pos[0], r.root_pos[1]);
+      pMeas->nLevel = nLevel;
+      pMeas->eSource = Measurement::SRC_ROOT;
+      kfSrc.AddMeasurement(pPointNew, pMeas);
+    }
+    std::vector<Candidate> vKept;                // ThinCandidates (:506) leaves vCandidates = vCGood; the created ones stay in the list
+    for(unsigned i = 0; i < level.vCandidates.size(); ++i)
+      if(vKeep[nCandAt + i])
+        vKept.push_back(level.vCandidates[i]);
+    nCandAt += (int)level.vCandidates.size();
+    level.vCandidates = vKept;
+  }
+}
+
+namespace
+{
+// the host's objects after a rescale or a re-alignment: every pose from the graph (ONE ranged read over the slots in use), every point's position
+// and pixel vectors from the table (one read)
+void ReadMapBack(Map& map)
+{
+  const int nRows = map.mnNextRow;
+  std::vector<double> vWorld(3*(size_t)nRows + 3), vRight(3*(size_t)nRows + 3), vDown(3*(size_t)nRows + 3);
+  if(nRows > 0 && mcp_map_points_get(map.mpMapTable, 0, nRows, &vWorld[0], &vRight[0], &vDown[0], NULL) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_points_get: "<<mcp_last_error());
+    ROS_BREAK();
+  }
+  for(MapPointPtrList::iterator it = map.mlpPoints.begin(); it != map.mlpPoints.end(); ++it)
+  {
+    MapPoint& point = *(*it);
+    const size_t r = 3*(size_t)point.mnTableRow;
+    point.mv3WorldPos = makeVector(vWorld[r], vWorld[r + 1], vWorld[r + 2]);
+    point.mv3PixelRight_W = makeVector(vRight[r], vRight[r + 1], vRight[r + 2]);
+    point.mv3PixelDown_W = makeVector(vDown[r], vDown[r + 1], vDown[r + 2]);
+  }
+  int nTop = -1;
+  for(MultiKeyFramePtrList::iterator it = map.mlpMultiKeyFrames.begin(); it != map.mlpMultiKeyFrames.end(); ++it)
+    nTop = std::max(nTop, (*it)->mnGraphSlot);
+  std::vector<double> vPoses(12*(size_t)(nTop + 1) + 12);
+  if(nTop >= 0 && mcp_graph_get_mkfs(map.mpMapGraph, 0, nTop + 1, &vPoses[0], NULL, NULL, NULL) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_graph_get_mkfs: "<<mcp_last_error());
+    ROS_BREAK();
+  }
+  for(MultiKeyFramePtrList::iterator it = map.mlpMultiKeyFrames.begin(); it != map.mlpMultiKeyFrames.end(); ++it)
+  {
+    MultiKeyFrame& mkf = *(*it);
+    if(mkf.mnGraphSlot < 0)
+      continue;
+    const double* adPose = &vPoses[12*(size_t)mkf.mnGraphSlot];
+    Matrix<3> m3;
+    for(int i = 0; i < 3; ++i)
+      for(int j = 0; j < 3; ++j)
+        m3(i, j) = adPose[3*i + j];
+    mkf.mse3BaseFromWorld = SE3<>(SO3<>(m3), makeVector(adPose[9], adPose[10], adPose[11]));
+    for(KeyFramePtrMap::iterator kf_it = mkf.mmpKeyFrames.begin(); kf_it != mkf.mmpKeyFrames.end(); ++kf_it)
+      kf_it->second->mse3CamFromWorld = kf_it->second->mse3CamFromBase * mkf.mse3BaseFromWorld;
+  }
+}
+}  // namespace
+
+void MapMakerServerBase::ApplyGlobalScaleToMap(double dScale)
+{
+  const int nc = (int)mBundleAdjuster.mvCamNames.size();
+  std::vector<mcp_scene_depth> vDepth((size_t)MCP_MAP_MAX_MKFS*nc);
+  mcp_map_transform_result res;
+  if(mcp_map_rescale(mMap.mpMapGraph, dScale, &res, &vDepth[0]) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_rescale: "<<mcp_last_error());
+    ROS_BREAK();
+  }
+  ReadMapBack(mMap);
+  // depth_out: the present slots in ascending order, cameras in graph order
+  int i = 0;
+  for(int nSlot = 0; nSlot < (int)mBundleAdjuster.mvpSlotMKF.size() && i < res.n_mkfs; ++nSlot)
+  {
+    MultiKeyFrame* pMKF = mBundleAdjuster.mvpSlotMKF[nSlot];
+    if(!pMKF || pMKF->mnGraphSlot != nSlot)
+      continue;
+    for(int c = 0; c < nc; ++c)
+    {
+      KeyFramePtrMap::iterator kf_it = pMKF->mmpKeyFrames.find(mBundleAdjuster.mvCamNames[c]);
+      const mcp_scene_depth& d = vDepth[(size_t)i*nc + c];
+      if(kf_it == pMKF->mmpKeyFrames.end() || d.refreshed != 1)
+        continue;
+      kf_it->second->mdSceneDepthMean = d.mean;
+      kf_it->second->mdSceneDepthSigma = d.sigma;
+    }
+    ++i;
+  }
+  if(res.n_no_source > 0 || res.n_no_rays > 0)
+    ROS_WARN_STREAM("ApplyGlobalScaleToMap: "<<res.n_no_source<<" rows without a source keyframe were left alone, "<<res.n_no_rays<<" rows without patch rays kept their pixel vectors");
+}
+
+void MapMakerServerBase::ApplyGlobalTransformationToMap(SE3<> se3NewFromOld)
+{
+  double adNewFromOld[12];
+  ToArray12(se3NewFromOld, adNewFromOld);
+  mcp_map_transform_result res;
+  if(mcp_map_transform(mMap.mpMapGraph, adNewFromOld, &res) != 0)
+  {
+    ROS_FATAL_STREAM("mcp_map_transform: "<<mcp_last_error());
+    ROS_BREAK();
+  }
+  ReadMapBack(mMap);
 }
