@@ -298,7 +298,14 @@ def thin_candidates(cand, level, meas_root=(), meas_level=(), created_root=()):
 
 
 def _unit(v):
-    return v / math.sqrt(float(v @ v))
+    """TooN normalize: a zero or non-finite vector becomes NaN / inf as in C++, without a warning"""
+    with np.errstate(all="ignore"):
+        return v / math.sqrt(float(v @ v))
+
+
+def _acos(x):
+    """acos as the C library has it: NaN outside [-1, 1] and for NaN, where math.acos raises"""
+    return math.acos(x) if -1.0 <= x <= 1.0 else float("nan")
 
 
 def pixel_vectors(pose_src, center, right, down, world):
@@ -322,10 +329,17 @@ def probe(cam_src, level, c):
 
 def arc(cam_src, pose_src, pose_tgt, one_pixel_angle, level, c):
     """The hypotheses of AddPointEpipolar (:611-723) for candidate c: dict(n, world (n x 3), tc (n x 3), pixel_right_w, pixel_down_w, root,
-    center, right, down); n = 0 when the v3BetweenEndpoints guard or a non-finite step count stops it."""
+    center, right, down); n = 0 when the v3BetweenEndpoints guard or a non-finite step count stops it.  Total: where the C++ carries NaN or inf
+    (no baseline, a cosine past 1 by rounding, an end point on the target's centre) this carries it too and returns n = 0; nothing raises or warns."""
+    with np.errstate(all="ignore"):
+        return _arc(cam_src, pose_src, pose_tgt, one_pixel_angle, level, c)
+
+
+def _arc(cam_src, pose_src, pose_tgt, one_pixel_angle, level, c):
     Rs, ts = pose_src
     Rt, tt = pose_tgt
     s = 1 << level
+    nan = float("nan")
     root, cen, rig, dow = probe(cam_src, level, c)
     ray = cam_src.unproject(root)[0]
     dirn = Rt @ (Rs.T @ ray)
@@ -336,33 +350,38 @@ def arc(cam_src, pose_src, pose_tgt, one_pixel_angle, level, c):
                center=cen, right=rig, down=dow, step=0.0)
     if sep == 0.0:                    # the device divides by zero here and gets NaN all the way to the step count: no hypotheses
         return res
-    src_angle = math.acos(float(cc_sc @ ray) / sep)
+    src_angle = _acos(float(cc_sc @ ray) / sep)
+    if math.isnan(src_angle):         # NaN all the way to the step count
+        return res
     start = sep * math.sin(math.pi - src_angle - math.pi / 3) / math.sin(math.pi / 3)
     end = sep * math.sin(math.pi - src_angle - 0.05) / math.sin(0.05)
-    start = max(start, 0.2)
+    res.update(start_raw=start)
+    if start < 0.2:
+        start = 0.2
     RS, RE = cc_tc + start * dirn, cc_tc + end * dirn
     a, b = _unit(RS), _unit(RE)
     res.update(start=start, end=end)
-    if (a - b) @ (a - b) < 1e-8:
+    d = a - b
+    if d @ d < 1e-8:
         return res
     nrm = _unit(np.cross(a, b))
     J = np.cross(nrm, a)
-    max_angle = math.acos(float(a @ b))
-    q = math.ceil(max_angle / (one_pixel_angle * s * 3)) if math.isfinite(max_angle) else float("nan")
+    max_angle = _acos(float(a @ b) * 1 + float(J @ b) * 0)      # v2PlaneB * (1, 0) (:697): a NaN in the plane's y axis reaches the angle
+    q = math.ceil(max_angle / (one_pixel_angle * s * 3)) if math.isfinite(max_angle) else nan
     if not (-2147483648.0 <= q <= 2147483646.0):
         return res
     n_steps = int(q)
-    step = max_angle / n_steps
+    step = max_angle / n_steps if n_steps else nan            # 0 / 0 in C++ (not reachable: the guard above keeps max_angle above 1e-4)
     rs = np.array([a @ RS, J @ RS])
     rd = np.array([a @ RE, J @ RE]) - rs
     rd = rd / math.sqrt(float(rd @ rd))
-    ang = np.arange(n_steps + 1) * step
+    ang = np.arange(max(n_steps + 1, 0)) * step
     cs, sn = np.cos(ang), np.sin(ang)
     alpha = (rs[0] * sn - rs[1] * cs) / (rd[1] * cs - rd[0] * sn)
     tc = RS[None, :] + alpha[:, None] * dirn[None, :]
     world = (tc - tt) @ Rt
     pr, pd = pixel_vectors(pose_src, cen, rig, dow, world)
-    res.update(n=n_steps + 1, world=world, tc=tc, pixel_right_w=pr, pixel_down_w=pd, step=step)
+    res.update(n=len(ang), world=world, tc=tc, pixel_right_w=pr, pixel_down_w=pd, step=step, max_angle=max_angle)
     return res
 
 
