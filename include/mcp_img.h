@@ -1243,6 +1243,63 @@ int mcp_map_mkf_cull_host(const mcp_mkf_cull_params*, int ncam, const double* ca
                           int* point_flags, uint8_t* pending, int n_store, const int* ms_mkf, const int* ms_cam, const int* ms_row, uint8_t* ms_alive,
                           mcp_mkf_cull_result*);
 
+/* ---- The co-visible points of the nearest keyframe ---------------------------- src/Tracker.cc:1785-1854, src/MapMakerBase.cc:115-140
+ * Tracker::CollectNearestPoints with tracker_collect_all_points false: the map keyframe closest to the current keyframe, every keyframe that
+ * measures one of its points, every point one of those measures.  One collection serves all cameras of a frame: a mark is a byte whose bit c
+ * belongs to frame camera c; bits past the camera count are never set.
+ *   nearest     per used camera c: CamFromWorld = cam_from_base[c] * base_from_world; the candidates are every (slot, cam) of a present slot
+ *               with kf_active[cam] set, bad MKFs included (the reference walks mlpMultiKeyFrames; the tracker's own MKF is not in the map);
+ *               KeyFrame::Distance with the map keyframe's CamFromWorld from the graph's rig, its stored depth mean, depth_mean[c] and
+ *               mean_diff_fraction; the winner is the smallest by ascending (dist, slot, cam).  status[c]: 0 a winner; 1 no candidate (the
+ *               reference asserts; here the set is empty); 3 some candidate's distance is not finite or exceeds 1e10 (the reference stops
+ *               the process; here the set is empty).  nearest_slot / nearest_cam are -1 and nearest_dist 0 unless status is 0.
+ *   the walk    over the store entries that count (alive, row inside the table, MKF a slot, camera below MCP_MAX_FRAME_CAMS):
+ *               seed[row] |= bit c where the entry is camera c's winner's; kf_mark[mkf, cam] |= seed[row]; near[row] |= kf_mark[mkf, cam].
+ *               Two hops, not three.  n_seed_rows, n_kfs, n_rows: per camera the marks of seed, kf_mark and near with bit c.
+ * SHAPE: one memset of the marks, then k_mgcl_nearest (one workgroup per camera), k_mgcl_seed, k_mgcl_kfs, k_mgcl_rows (one thread per store
+ * entry each), k_mgcl_counts (one workgroup) on the table's stream; every atomic ors an integer, so two runs give the same bytes.
+ * DEVIATIONS from the reference: ties go to the smaller (slot, cam), not to list order; status 1 and 3 instead of an assert and a stop; the
+ * set is computed once per frame for all cameras.
+ *
+ * mcp_map_collect_nearest is the stand-alone call (one submission, one wait): cam_from_base NULL means the graph's rig, otherwise ncam x 12
+ * (ncam the graph's); near, if given, receives one byte per table row.  mcp_map_collect_rows_view returns the same mask zero-copy from the
+ * pinned block; it stays valid until the next collection on the graph (a frame's included: NULL after one of those).
+ * REFUSALS (-1, mcp_last_error() starting with the entry's name, nothing enqueued, outputs and mode untouched): NULL handles or structs; a graph
+ * whose table is not this table; a frame whose camera count differs from the graph's; mean_diff_fraction not finite; a used camera's depth
+ * mean that is not finite or not positive; a non-finite pose or CamFromBase in the stand-alone call. */
+typedef struct mcp_collect_params {
+  double mean_diff_fraction;                      /* KeyFrame::sdDistanceMeanDiffFraction */
+  double depth_mean[MCP_MAX_FRAME_CAMS];          /* mdSceneDepthMean of the current keyframes: finite, > 0 for every camera used */
+  uint8_t active[MCP_MAX_FRAME_CAMS];             /* stand-alone call: cameras to collect for; the frame mode uses all ncam */
+} mcp_collect_params;
+typedef struct mcp_collect_report {
+  int valid;                                      /* 1 filled; 0 the stages did not run (a recovery frame where nobody recovered) */
+  int status[MCP_MAX_FRAME_CAMS];                 /* 0, 1, 3 as above; cameras not used: 0 with nearest -1 */
+  int nearest_slot[MCP_MAX_FRAME_CAMS], nearest_cam[MCP_MAX_FRAME_CAMS]; int pad_; double nearest_dist[MCP_MAX_FRAME_CAMS];
+  int n_candidates[MCP_MAX_FRAME_CAMS], n_seed_rows[MCP_MAX_FRAME_CAMS], n_kfs[MCP_MAX_FRAME_CAMS], n_rows[MCP_MAX_FRAME_CAMS];
+} mcp_collect_report;
+int mcp_map_collect_nearest(mcp_map_graph*, const double base_from_world[12], const double* cam_from_base, const mcp_collect_params*,
+                            mcp_collect_report*, uint8_t* near);
+const uint8_t* mcp_map_collect_rows_view(const mcp_map_graph*, int* count);
+/* device time in ms of the collection launches of the last collection on the graph, stand-alone or a frame's; -1 before the first that ran */
+int mcp_map_collect_last_timing(const mcp_map_graph*, double* device_ms);
+/* the same from host arrays by the same bodies under the host compiler (no device; the device's bytes): the pose, the current keyframes'
+ * CamFromBase (NULL: the rig's), the rig, n_slots MKF columns as mcp_map_bundle_select_host takes them, n_rows, the store's columns. */
+int mcp_map_collect_nearest_host(const double base_from_world[12], const double* cur_cam_from_base, const mcp_collect_params*, int ncam,
+                                 const double* cam_from_base, int n_slots, const double* mkf_base_from_world, const int* mkf_flags,
+                                 const uint8_t* kf_active, const double* kf_depth_mean, int n_rows, int n_store, const int* ms_mkf,
+                                 const int* ms_cam, const int* ms_row, const uint8_t* ms_alive, mcp_collect_report*, uint8_t* near);
+/* THE FRAME MODE.  mcp_track_collect_nearest(table, graph, params) switches it on for the table (graph NULL: off; params then ignored):
+ * host-only, nothing enqueued, cheap enough to call before every frame with fresh depth means.  While it is on, mcp_track_find_pvs,
+ * mcp_track_map, mcp_track_map_record, mcp_track_frame_motion and mcp_track_frame_recover run the collection stages in front of their PVS
+ * launch, on the same stream and behind the same wait, at the pose that launch reads (the given pose, k_motion_prior's, or k_reloc_pick's
+ * behind the gate), with the frame's own cam_from_base for the current keyframes and the graph's rig for the map's; a row is judged for
+ * camera c only if bit c of near[row] is set, in addition to its usable byte.  Every other stage of the frame is unchanged.  Default off:
+ * no launch more, and the bits of before.  mcp_map_graph_destroy switches the mode off on its table if it names the graph destroyed.
+ * mcp_track_collect_last gives the report of the last such call; -1 unless that call succeeded with the mode on. */
+int mcp_track_collect_nearest(mcp_map_points*, mcp_map_graph*, const mcp_collect_params*);
+int mcp_track_collect_last(const mcp_map_points*, mcp_collect_report*);
+
 /* ---- AddStereoMapPoints into the map: new points and their measurements stay on the device ------- src/MapMakerServerBase.cc:452-496, 855-914
  * mcp_stereo_points (above) hands every created point back to the host, which then sends the same numbers up again through
  * mcp_map_points_update, _update_rays, _update_source, mcp_map_graph_update_points and mcp_map_graph_add_meas.  mcp_stereo_map_points is the

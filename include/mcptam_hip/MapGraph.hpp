@@ -79,6 +79,32 @@ class MapGraph {
     return res;
   }
 
+  /// Tracker::CollectNearestPoints with tracker_collect_all_points false, at the tracker's pose se3BaseFromWorld, for the cameras of params.active:
+  /// the report, and (vNear non-null) one byte per table row whose bit c says that the row is a co-visible point of the map keyframe nearest to
+  /// current keyframe c.  pCamFromBase: the current keyframes' (nCams x 12), or null for the rig's.
+  mcp_collect_report CollectNearestPoints(const std::array<double, 12>& se3BaseFromWorld, const mcp_collect_params& params, std::vector<uint8_t>* vNear = nullptr,
+                                          const double* pCamFromBase = nullptr) {
+    mcp_collect_report rep;
+    check(mcp_map_collect_nearest(mpGraph, se3BaseFromWorld.data(), pCamFromBase, &params, &rep, nullptr));
+    if (vNear) {
+      int n = 0;
+      const uint8_t* p = mcp_map_collect_rows_view(mpGraph, &n);
+      vNear->assign(p, p + n);
+    }
+    return rep;
+  }
+
+  /// The frame mode: while it is on, FindPVS and the one-call frames of pTable (the graph's table) judge only those rows.  Host-only; call it
+  /// before every frame with the current keyframes' mdSceneDepthMean.  TrackCollectAllPoints switches it off again (the default).
+  void TrackCollectNearestPoints(mcp_map_points* pTable, const mcp_collect_params& params) { check(mcp_track_collect_nearest(pTable, mpGraph, &params)); }
+  static void TrackCollectAllPoints(mcp_map_points* pTable) { check(mcp_track_collect_nearest(pTable, nullptr, nullptr)); }
+  /// The report of the last FindPVS / frame call on pTable with the mode on
+  static mcp_collect_report TrackCollectLast(const mcp_map_points* pTable) {
+    mcp_collect_report rep;
+    check(mcp_track_collect_last(pTable, &rep));
+    return rep;
+  }
+
  private:
   static void check(int rc) { if (rc < 0) throw std::runtime_error(mcp_last_error()); }
   mcp_map_graph* mpGraph;

@@ -34,6 +34,7 @@
 #include "map_graph_parcel.h"
 #include "map_graph_cull.h"
 #include "map_graph_neigh.h"
+#include "map_graph_collect.h"
 #include "stereo_append.h"
 #include "map_life.h"
 
@@ -1199,6 +1200,12 @@ struct mcp_map_points {
     int reserve(size_t nb) { const size_t tiles = (nb + COV_TILE - 1)/COV_TILE; return (part.alloc(COV_NPROD*tiles) || used.alloc(tiles) || h_out.alloc(1)) ? -1 : 0; }
     void invalidate() { ok = false; fine_ok = false; }
   } cv;
+  // mcp_track_collect_nearest: the graph whose store the frames walk in front of their PVS launch (NULL: the mode is off), the current
+  // keyframes' depth means; the report of the last frame call (ok: that call succeeded with the mode on)
+  struct Co {
+    mcp_map_graph* g = nullptr; mcp_collect_params p = {}; mcp_collect_report last = {}; bool ok = false;
+    void invalidate() { ok = false; }
+  } co;
   // mcp_map_refind: the packed inputs (pinned | device), the passes' scratch, the pinned results (RfOut | verdict bytes | measurements)
   struct Rf {
     PinBuf<char> in; Buf<char> dev; Buf<uint8_t> flags, vd; Buf<int> blk, first; Buf<RfItem> items; Buf<mcp_refind_meas> cand; PinBuf<char> out;
@@ -1265,6 +1272,15 @@ struct mcp_map_points {
     return 0;
   }
 };
+
+// the frame mode of the collection (mcp_track_collect_nearest; defined with the map graph below).  collect_frame_check: the refusal of a frame
+// whose camera count is not the graph's; collect_frame_reserve: the graph's scratch, before the first enqueue; collect_frame_enqueue: the
+// stages on the table's stream at the pose in d_bfw (device memory; NULL: host_bfw is sent there first), *near: the marks the PVS launch
+// reads; collect_frame_done: the pinned report into the table once the stream has been waited for
+static int collect_frame_check(const std::string& who, const mcp_map_points* m, int ncam);
+static int collect_frame_reserve(mcp_map_points* m);
+static int collect_frame_enqueue(mcp_map_points* m, int ncam, const double* cfb, const double* host_bfw, const double* d_bfw, const int* d_gate, const uint8_t** near);
+static void collect_frame_done(mcp_map_points* m);
 
 // ---- the uploads and read-backs of the columns -----------------------------------------------------------------------------------------
 // The rows an upload names: first .. first+count-1, or (by_ids) ids[0 .. count): distinct, none negative, none without a successor.  *top is
@@ -1443,8 +1459,9 @@ static size_t pvs_layout(int ncam, const int* caps, int n, PvsLayout* Y) {
 // with tab_last.clear()).
 // d_bfw != NULL: the pose is read from there (12 doubles in device memory, left by an earlier kernel of the stream) instead of bfw;
 // d_gate != NULL (with d_bfw): the marking pass runs behind that device-side word (k_pvs_mark_gated).
+// near != NULL: the marks of a collection enqueued before this (one byte per row, bit c: camera c judges the row).
 static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double* cfb, const double* bfw, const PvsLayout& Y,
-                       mcp_pvs_entry* lists, int* counts, const double* d_bfw = nullptr, const int* d_gate = nullptr) {
+                       mcp_pvs_entry* lists, int* counts, const double* d_bfw = nullptr, const int* d_gate = nullptr, const uint8_t* near = nullptr) {
   const int n = m->rows, nblk = (n + PVS_BLOCK - 1)/PVS_BLOCK;
   std::vector<PvsCam> tab(ncam);
   for (int c = 0; c < ncam; ++c) {
@@ -1457,9 +1474,9 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
   // the cameras, their CamFromBase, masks and caps rarely change from frame to frame
   mcp_map_points::Pvs& V = m->pvs;
   if (upload_when_changed(V.tab_last, V.h_tab, V.d_tab, tab, m->st)) return -1;
-  if (d_bfw && d_gate) hipLaunchKernelGGL(k_pvs_mark_gated, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, d_gate, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
-  else if (d_bfw) hipLaunchKernelGGL(k_pvs_mark_at, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
-  else hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p);
+  if (d_bfw && d_gate) hipLaunchKernelGGL(k_pvs_mark_gated, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, d_gate, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p, near);
+  else if (d_bfw) hipLaunchKernelGGL(k_pvs_mark_at, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, d_bfw, m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p, near);
+  else hipLaunchKernelGGL(k_pvs_mark, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, se3_of12(bfw), m->pts.row(), n, nblk, V.lvl.p, V.ent.p, V.blk_cnt.p, near);
   hipLaunchKernelGGL(k_pvs_scatter, dim3(nblk, ncam), dim3(PVS_BLOCK), 0, m->st, (const PvsCam*)V.d_tab.p, n, nblk, (const signed char*)V.lvl.p,
                      (const mcp_pvs_entry*)V.ent.p, (const int*)V.blk_cnt.p, lists, counts);
   return 0;
@@ -1468,28 +1485,37 @@ static int pvs_enqueue(mcp_map_points* m, int ncam, mcp_kf* const* targets, cons
 int mcp_track_find_pvs(mcp_map_points* m, int ncam, mcp_kf* const* targets, const mcp_camera* cams, const double bfw[12], const double* cfb,
                        const int* caps, mcp_pvs_entry* const* out, int* counts) {
   if (!m) return img_fail("mcp_track_find_pvs: NULL table");
-  m->pvs.invalidate(); m->tr.invalidate(); m->cv.invalidate();
+  m->pvs.invalidate(); m->tr.invalidate(); m->cv.invalidate(); m->co.invalidate();
   if (ncam < 1 || ncam > MCP_MAX_FRAME_CAMS || !targets || !cams || !bfw || !cfb || !caps || !counts) return img_fail("mcp_track_find_pvs: bad arguments");
   for (int c = 0; c < ncam; ++c) {
     if (!targets[c] || !cam_ok(&cams[c]) || caps[c] < 0 || (out && !out[c])) return img_fail("mcp_track_find_pvs: bad arguments for camera " + std::to_string(c));
     if (target_on_table_device("mcp_track_find_pvs", m, c, targets[c])) return -1;
   }
+  const bool collect = m->co.g != nullptr;             // mcp_track_collect_nearest: the collection stages in front of the marking pass
+  if (collect && collect_frame_check("mcp_track_find_pvs", m, ncam)) return -1;
   for (int k = 0; k < ncam*MCP_LEVELS; ++k) counts[k] = 0;
   ICK(hipSetDevice(m->device));
   mcp_map_points::Pvs& V = m->pvs;
   const int n = m->rows;
-  if (n == 0) {
+  if (n == 0 && !collect) {
     for (int c = 0; c < ncam; ++c) { V.ok[c] = true; for (int l = 0; l < MCP_LEVELS; ++l) { V.first[c][l] = 0; V.count[c][l] = 0; } }
     V.ncam = ncam;
     return 0;
   }
   PvsLayout Y;
-  if (V.h_out.alloc(pvs_layout(ncam, caps, n, &Y)) || V.h_counts.alloc((size_t)ncam*MCP_LEVELS) || V.reserve(ncam, n)) return -1;
-  if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, V.h_out.p, V.h_counts.p)) return -1;
+  if (V.h_out.alloc(std::max<size_t>(pvs_layout(ncam, caps, n, &Y), 1)) || V.h_counts.alloc((size_t)ncam*MCP_LEVELS) || V.reserve(ncam, n)) return -1;
+  if (collect && collect_frame_reserve(m)) return -1;
+  const uint8_t* near = nullptr;
+  Drain drain{m, collect};
+  if (collect && collect_frame_enqueue(m, ncam, cfb, bfw, nullptr, nullptr, &near)) { V.tab_last.clear(); return -1; }
+  if (n == 0) std::memset(V.h_counts.p, 0, sizeof(int)*(size_t)ncam*MCP_LEVELS);
+  else if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, V.h_out.p, V.h_counts.p, nullptr, nullptr, near)) { V.tab_last.clear(); return -1; }
   const hipError_t le = hipGetLastError();
   const hipError_t se = m->sync();
+  drain.armed = false;
   if (le != hipSuccess) { V.tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: launch: ") + hipGetErrorString(le)); }
   if (se != hipSuccess) { V.tab_last.clear(); return img_fail(std::string("mcp_track_find_pvs: ") + hipGetErrorString(se)); }
+  if (collect) collect_frame_done(m);
   std::memcpy(counts, V.h_counts.p, sizeof(int)*(size_t)ncam*MCP_LEVELS);
   std::string over;
   for (int c = 0; c < ncam; ++c) {
@@ -1760,6 +1786,7 @@ struct TrackFrame {
       if (mo && !imgs && !targets[c]->has_image) return img_fail(who + ": camera " + std::to_string(c) + "'s target holds no frame and no images were given");
     }
     if (mo && motion_check(who, ncam, mo->cams_sbi, mo->p, mo->out)) return -1;
+    if (m->co.g && collect_frame_check(who, m, ncam)) return -1;      // mcp_track_collect_nearest: the frame's cameras are the graph's
     return rc ? recover_check(who, m, ncam, targets, mo->p, *rc, cand_live) : 0;
   }
   void derive() {
@@ -1792,6 +1819,7 @@ struct TrackFrame {
     }
     if (cov && m->cv.reserve(NB)) return -1;
     if (cov) std::memset(m->cv.h_out.p, 0, sizeof(mcp_track_pose_cov_record));        // (valid = 0 unless k_pose_cov_finish runs)
+    if (m->co.g && collect_frame_reserve(m)) return -1;
     if (rp) {
       if (m->parcel_reads && m->tr.h_meas.n < NB) ICK(m->sync());       // (a parcel's fill may still read the block replaced below)
       if (m->tr.h_notes.alloc(NB) || m->tr.h_meas.alloc(NB) || m->tr.h_rec.alloc(1) || m->tr.flags.alloc(NB) || m->tr.tile.alloc(n_tile) || m->tr.acc.alloc(1) ||
@@ -1882,8 +1910,11 @@ struct TrackFrame {
   }
   // FindPVS, lists and counts in device memory (on a recovery frame behind the relocaliser's gate), and the sets
   int pvs_sets_enqueue() {
+    // mcp_track_collect_nearest: the collection stages at the pose in the block -- the given one, k_motion_prior's or k_reloc_pick's
+    const uint8_t* near = nullptr;
+    if (m->co.g && collect_frame_enqueue(m, ncam, cfb, nullptr, D.pm, rc ? m->rc.gate.p : nullptr, &near)) return -1;
     if (n > 0) {
-      if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? D.pm : nullptr, rc ? m->rc.gate.p : nullptr)) return -1;
+      if (pvs_enqueue(m, ncam, targets, cams, cfb, bfw, Y, m->tm.pvs.p, m->tm.counts.p, mo ? D.pm : nullptr, rc ? m->rc.gate.p : nullptr, near)) return -1;
     } else ICK(hipMemsetAsync(m->tm.counts.p, 0, sizeof(int)*(size_t)MCP_MAX_FRAME_CAMS*MCP_LEVELS, st));
     hipLaunchKernelGGL(k_tm_select, dim3(ncam), dim3(TM_SEL_NT), 0, st, P, (const mcp_pvs_entry*)m->tm.pvs.p, (const int*)m->tm.counts.p, m->src.row(),
                        (const TmSlot*)m->tm.slots.p, m->tm.k0.p, m->tm.k1.p, m->tm.live.p, m->tm.sel.p, ctl);
@@ -1968,6 +1999,7 @@ struct TrackFrame {
     m->pvs.ncam = ncam; m->pvs.on_device = true; m->pvs.rows = n;
     std::memcpy(res->mu_last, R.mu, 48);
     m->cv.ok = cov; m->cv.fine_ok = true; m->cv.n_fine = R.ctl.n_fine; std::memcpy(m->cv.mu, R.mu, 48);
+    if (m->co.g) collect_frame_done(m);
     if (mo) *mo->out = *m->mo.h_out.p;
     if (rc) {
       *rc->out = *m->rc.h_out.p;
@@ -1982,7 +2014,7 @@ struct TrackFrame {
     if (check()) return -1;
     ICK(hipSetDevice(m->device));
     // the results of the last call are gone from here on (their blocks may be reallocated and rewritten below)
-    m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate(); m->cv.invalidate();
+    m->pvs.invalidate(); m->tm.invalidate(); m->tr.invalidate(); m->cv.invalidate(); m->co.invalidate();
     derive();
     if (reserve()) return -1;
     Drain drain{m, true, true, ncam, imgs ? targets : nullptr};
@@ -2675,7 +2707,7 @@ struct MgTimer {
 };
 
 // every launch of the map graph but the list passes' (MGL_BLOCK: a tile of the list algorithm) runs workgroups of MG_BLOCK threads
-static_assert(MGP_BLOCK == MG_BLOCK && MGC_BLOCK == MG_BLOCK && MGN_BLOCK == MG_BLOCK, "the map-graph kernels share one workgroup size");
+static_assert(MGP_BLOCK == MG_BLOCK && MGC_BLOCK == MG_BLOCK && MGN_BLOCK == MG_BLOCK && MGCL_BLOCK == MG_BLOCK, "the map-graph kernels share one workgroup size");
 static int mg_grid(long long n, int block = MG_BLOCK) { return (int)((n + block - 1)/block); }      // (empty for n == 0: the launch is skipped or n is positive)
 static int mg_grid1(long long n) { return std::max(1, mg_grid(n)); }
 
@@ -2731,6 +2763,17 @@ struct mcp_map_graph {
     Buf<double> dist; Buf<uint8_t> cand; Buf<MgnCtl> ctl; Buf<mcp_neigh_result> res; Buf<MgMkf> ext; Buf<MgnCull> cc; PinBuf<char> out;
     MgTimer t_query, t_remove;
   } neigh;
+  // the co-visible points of the nearest keyframe (map_graph_collect.h): the marks (kf_mark | seed | near), the report (device, pinned), the
+  // pose where a call brings its own (pinned, device), the pinned copy of near for the stand-alone call's view (view: its rows; -1: none);
+  // the timer of mcp_map_collect_last_timing
+  struct Collect {
+    Buf<uint8_t> marks; Buf<mcp_collect_report> rep; PinBuf<mcp_collect_report> h_rep; PinBuf<double> h_pose; Buf<double> pose; PinBuf<uint8_t> h_near;
+    int view = -1; MgTimer t;
+    uint8_t* kf_mark() const { return marks.p; }
+    uint8_t* seed() const { return marks.p + MGCL_KF_MARKS; }
+    uint8_t* near(int rows) const { return marks.p + MGCL_KF_MARKS + mgcl_row_bytes(rows); }
+    static size_t bytes(int rows) { return (size_t)MGCL_KF_MARKS + 2*mgcl_row_bytes(rows); }
+  } collect;
   // mcp_stereo_map_points (stereo_append.h): the source keyframe's busy list gathered from the store, its length (device, pinned).  The rows, keys
   // and target slots go up through `up`, the per-workgroup counts through `blk`.
   struct Stereo { Buf<mcp_stereo_meas> busy; Buf<int> n_busy; PinBuf<int> h_n_busy; } stereo;
@@ -2766,6 +2809,9 @@ struct mcp_map_graph {
     const size_t n_idx = (size_t)(MCP_MAP_MAX_MKFS + 1)*MCP_MAX_FRAME_CAMS;
     return (G.grow(neigh.dist, n_idx) || G.grow(neigh.cand, n_idx) || G.grow(neigh.ctl, 2) || G.grow(neigh.res, 2) || G.grow(neigh.ext, 1) || G.grow(neigh.cc, 1) ||
             G.grow(neigh.out, 2*sizeof(mcp_neigh_result) + sizeof(MgnCull))) ? -1 : 0;
+  }
+  int collect_reserve(Guard& G) {
+    return (G.grow(collect.marks, Collect::bytes(m->rows)) || G.grow(collect.rep, 1) || G.grow(collect.h_rep, 1) || G.grow(collect.h_pose, 12) || G.grow(collect.pose, 12)) ? -1 : 0;
   }
   // the good count of every row into marks[0 .. R) (zeroed by the caller): k_mg_edges_count without a select's hand-off
   void good_counts_enqueue(int R) {
@@ -2945,7 +2991,11 @@ mcp_map_graph* mcp_map_graph_create(mcp_map_points* m, int ncam, const double* c
   std::memset(g->sel.h_res.p, 0, sizeof(mcp_bundle_select_result));
   return g;
 }
-void mcp_map_graph_destroy(mcp_map_graph* g) { if (g) { (void)hipSetDevice(g->m->device); delete g; } }
+void mcp_map_graph_destroy(mcp_map_graph* g) {
+  if (!g) return;
+  if (g->m->co.g == g) g->m->co.g = nullptr;           // mcp_track_collect_nearest: no later frame follows a dead pointer
+  (void)hipSetDevice(g->m->device); delete g;
+}
 
 int mcp_map_graph_set_mkfs(mcp_map_graph* g, int first, int count, const double* bfw, const int* flags, const uint8_t* act, const double* dep) {
   return mg_mkfs_upload(g, "mcp_map_graph_set_mkfs", false, first, count, nullptr, bfw, flags, act, dep);
@@ -3796,6 +3846,133 @@ int mcp_map_neighbours(mcp_map_graph* g, const mcp_neigh_params* p, mcp_neigh_re
 int mcp_map_neighbours_last_timing(const mcp_map_graph* g, double* device_ms) {
   if (!g || !device_ms) return img_fail("mcp_map_neighbours_last_timing: bad arguments");
   return g->neigh.t_query.ms(device_ms);
+}
+
+}  // extern "C"
+
+// ---- the co-visible points of the nearest keyframe (include/mcp_img.h mcp_map_collect_nearest, mcp_track_collect_nearest; map_graph_collect.h) ----
+// what both routes refuse in the parameters; ncam: the cameras looked at, use: which of them (NULL: all)
+static std::string mgcl_params_check(const mcp_collect_params* p, int ncam, const uint8_t* use) {
+  if (!p) return "NULL params";
+  if (!std::isfinite(p->mean_diff_fraction)) return "mean_diff_fraction is not finite";
+  for (int c = 0; c < ncam; ++c)
+    if ((!use || use[c]) && !(std::isfinite(p->depth_mean[c]) && p->depth_mean[c] > 0.0)) return "camera " + std::to_string(c) + ": the depth mean of a used camera must be finite and positive";
+  return "";
+}
+// the memset and the five launches on the table's stream between the timer's events (the graph's scratch reserved, h_rep cleared by the
+// caller).  d_bfw: the pose in device memory; gate: NULL, or the device-side word behind which the stages run
+static int mgcl_enqueue(mcp_map_graph* g, const MgclIn& In, const double* d_bfw, const int* gate) {
+  hipStream_t st = g->m->st;
+  mcp_map_graph::Collect& C = g->collect;
+  const int R = g->m->rows, M = g->n_store;
+  const dim3 GM(mg_grid(M)), B(MG_BLOCK);
+  if (C.t.begin(st)) return -1;
+  ICK(hipMemsetAsync(C.marks.p, 0, mcp_map_graph::Collect::bytes(R), st));
+  ICK(hipMemsetAsync(C.rep.p, 0, sizeof(mcp_collect_report), st));
+  hipLaunchKernelGGL(k_mgcl_nearest, dim3(MCP_MAX_FRAME_CAMS), B, 0, st, gate, In, d_bfw, g->rig, (const MgMkf*)g->slots.p, g->mirror.top_present() + 1, C.rep.p);
+  if (M) {
+    hipLaunchKernelGGL(k_mgcl_seed, GM, B, 0, st, gate, (const mcp_collect_report*)C.rep.p, (const MgMeas*)g->store.p, M, R, C.seed());
+    hipLaunchKernelGGL(k_mgcl_kfs, GM, B, 0, st, gate, (const MgMeas*)g->store.p, M, R, (const uint8_t*)C.seed(), C.kf_mark());
+    hipLaunchKernelGGL(k_mgcl_rows, GM, B, 0, st, gate, (const MgMeas*)g->store.p, M, R, (const uint8_t*)C.kf_mark(), C.near(R));
+  }
+  hipLaunchKernelGGL(k_mgcl_counts, dim3(1), dim3(MGCL_COUNT_BLOCK), 0, st, gate, (const uint8_t*)C.kf_mark(), (const uint8_t*)C.seed(), (const uint8_t*)C.near(R), R, C.rep.p, C.h_rep.p);
+  ICK(hipGetLastError());
+  return C.t.end(st);
+}
+
+static int collect_frame_check(const std::string& who, const mcp_map_points* m, int ncam) {
+  if (ncam == m->co.g->rig.ncam) return 0;
+  return img_fail(who + ": mcp_track_collect_nearest is on and the frame has " + std::to_string(ncam) + " cameras, the graph " + std::to_string(m->co.g->rig.ncam));
+}
+static int collect_frame_reserve(mcp_map_points* m) {
+  mcp_map_graph::Guard G(m->co.g);
+  return m->co.g->collect_reserve(G);
+}
+static int collect_frame_enqueue(mcp_map_points* m, int ncam, const double* cfb, const double* host_bfw, const double* d_bfw, const int* d_gate, const uint8_t** near) {
+  mcp_map_graph* g = m->co.g;
+  mcp_map_graph::Collect& C = g->collect;
+  MgclIn In; std::memset(&In, 0, sizeof In);
+  In.frac = m->co.p.mean_diff_fraction;
+  for (int c = 0; c < ncam; ++c) { In.cfb[c] = se3_of12(cfb + 12*c); In.depth[c] = m->co.p.depth_mean[c]; In.use[c] = 1; }
+  C.view = -1;
+  mgcl_report_clear(C.h_rep.p);                        // (valid = 0 unless k_mgcl_counts runs)
+  if (!d_bfw) {
+    std::memcpy(C.h_pose.p, host_bfw, 96);
+    ICK(hipMemcpyAsync(C.pose.p, C.h_pose.p, 96, hipMemcpyHostToDevice, m->st));
+    d_bfw = C.pose.p;
+  }
+  if (mgcl_enqueue(g, In, d_bfw, d_gate)) return -1;
+  *near = C.near(m->rows);
+  return 0;
+}
+static void collect_frame_done(mcp_map_points* m) {
+  m->co.g->collect.t.timed = true;
+  m->co.last = *m->co.g->collect.h_rep.p; m->co.ok = true;
+}
+
+extern "C" {
+
+int mcp_map_collect_nearest(mcp_map_graph* g, const double bfw[12], const double* cfb, const mcp_collect_params* p, mcp_collect_report* rep, uint8_t* near) {
+  const std::string who = "mcp_map_collect_nearest";
+  if (!g) return img_fail(who + ": NULL graph");
+  if (!bfw || !rep) return img_fail(who + ": NULL pose or report");
+  const int nc = g->rig.ncam;
+  std::string bad = mgcl_params_check(p, nc, p ? p->active : nullptr);
+  if (bad.empty() && !finite12(bfw)) bad = "the pose is not finite";
+  for (int c = 0; bad.empty() && cfb && c < nc; ++c) if (!finite12(cfb + 12*(size_t)c)) bad = "a CamFromBase is not finite";
+  if (!bad.empty()) return img_fail(who + ": " + bad);
+  mcp_map_points* m = g->m;
+  ICK(hipSetDevice(m->device));
+  mcp_map_graph::Collect& C = g->collect;
+  const int R = m->rows;
+  mcp_map_graph::Guard G(g);
+  if (g->collect_reserve(G) || G.grow(C.h_near, (size_t)R)) return -1;
+  MgclIn In; std::memset(&In, 0, sizeof In);
+  In.frac = p->mean_diff_fraction;
+  for (int c = 0; c < nc; ++c) { In.cfb[c] = cfb ? se3_of12(cfb + 12*c) : g->rig.cfb[c]; In.depth[c] = p->depth_mean[c]; In.use[c] = p->active[c] ? 1 : 0; }
+  C.view = -1;
+  mgcl_report_clear(C.h_rep.p);
+  std::memcpy(C.h_pose.p, bfw, 96);
+  hipStream_t st = m->st;
+  Drain drain{m, true};
+  ICK(hipMemcpyAsync(C.pose.p, C.h_pose.p, 96, hipMemcpyHostToDevice, st));
+  if (mgcl_enqueue(g, In, C.pose.p, nullptr)) return -1;
+  if (R) ICK(hipMemcpyAsync(C.h_near.p, C.near(R), (size_t)R, hipMemcpyDeviceToHost, st));
+  if (g->one_wait(drain, &C.t)) return -1;
+  *rep = *C.h_rep.p;
+  if (near && R) std::memcpy(near, C.h_near.p, (size_t)R);
+  C.view = R;
+  return 0;
+}
+
+const uint8_t* mcp_map_collect_rows_view(const mcp_map_graph* g, int* count) {
+  if (count) *count = 0;
+  if (!g || g->collect.view < 0) { img_fail("mcp_map_collect_rows_view: the last collection on this graph was no mcp_map_collect_nearest that succeeded"); return nullptr; }
+  if (count) *count = g->collect.view;
+  return g->collect.view > 0 ? g->collect.h_near.p : nullptr;
+}
+
+int mcp_map_collect_last_timing(const mcp_map_graph* g, double* device_ms) {
+  if (!g || !device_ms) return img_fail("mcp_map_collect_last_timing: bad arguments");
+  return g->collect.t.ms(device_ms);
+}
+
+int mcp_track_collect_nearest(mcp_map_points* m, mcp_map_graph* g, const mcp_collect_params* p) {
+  const std::string who = "mcp_track_collect_nearest";
+  if (!m) return img_fail(who + ": NULL table");
+  if (!g) { m->co.g = nullptr; return 0; }
+  if (g->m != m) return img_fail(who + ": the graph's table is not this table");
+  const std::string bad = mgcl_params_check(p, g->rig.ncam, nullptr);
+  if (!bad.empty()) return img_fail(who + ": " + bad);
+  m->co.g = g; m->co.p = *p;
+  return 0;
+}
+
+int mcp_track_collect_last(const mcp_map_points* m, mcp_collect_report* out) {
+  if (!m || !out) return img_fail("mcp_track_collect_last: NULL table or report");
+  if (!m->co.ok) return img_fail("mcp_track_collect_last: the last track / PVS call on this table did not succeed with mcp_track_collect_nearest on");
+  *out = m->co.last;
+  return 0;
 }
 
 int mcp_map_mkf_cull(mcp_map_graph* g, const mcp_mkf_cull_params* p, mcp_mkf_cull_result* res) {

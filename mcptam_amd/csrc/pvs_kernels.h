@@ -20,9 +20,10 @@ struct PvsCam {
 };
 constexpr int PVS_BLOCK = 256;
 
-// (the body of k_pvs_mark and k_pvs_mark_at; cnt: MCP_LEVELS ints of the caller's LDS)
+// (the body of k_pvs_mark and k_pvs_mark_at; cnt: MCP_LEVELS ints of the caller's LDS; near: NULL, or one byte per row whose bit c says
+// whether camera c judges the row at all -- mcp_track_collect_nearest)
 __device__ __forceinline__ void pvs_mark_body(const PvsCam* __restrict__ tab, const Se3& bfw, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl,
-                                              mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt, int* cnt) {
+                                              mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt, int* cnt, const uint8_t* __restrict__ near) {
   const int c = blockIdx.y, i = blockIdx.x*PVS_BLOCK + threadIdx.x;
   if (threadIdx.x < MCP_LEVELS) cnt[threadIdx.x] = 0;
   __syncthreads();
@@ -30,7 +31,7 @@ __device__ __forceinline__ void pvs_mark_body(const PvsCam* __restrict__ tab, co
     const PvsPoint& P = pts[i];
     const PvsCam& C = tab[c];
     int level = -1;
-    if (P.usable) {                                                                      // !mbBad && mbOptimized, Tracker.cc:680
+    if (P.usable && (!near || ((near[i] >> c) & 1))) {                                   // !mbBad && mbOptimized, Tracker.cc:680; near: the collected set (map_graph_collect.h)
       Se3 cfw; double xc[3]; Projection pr;
       bool keep = track_project(C.cam, bfw, C.cfb, P.world_pos, cfw, xc, pr);             // mbInImage, :693-695
       // :698: mask[ir(v2Image)] == 0 drops the point.  The reference reads past the mask for u == w or v == h; here such a point is
@@ -56,29 +57,30 @@ __device__ __forceinline__ void pvs_mark_body(const PvsCam* __restrict__ tab, co
 }
 __global__ void __launch_bounds__(PVS_BLOCK)
 k_pvs_mark(const PvsCam* __restrict__ tab, Se3 bfw, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl /* ncam x n */,
-           mcp_pvs_entry* __restrict__ ent /* ncam x n, written where lvl >= 0 */, int* __restrict__ blk_cnt /* ncam x nblk x MCP_LEVELS */) {
+           mcp_pvs_entry* __restrict__ ent /* ncam x n, written where lvl >= 0 */, int* __restrict__ blk_cnt /* ncam x nblk x MCP_LEVELS */,
+           const uint8_t* __restrict__ near /* n, or null */) {
   __shared__ int cnt[MCP_LEVELS];
-  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt);
+  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt, near);
 }
 // the same pass with BaseFromWorld read from device memory (12 doubles, R row-major then t): the pose an earlier kernel of the same stream left
 // there (mcp_track_frame_motion: k_motion_prior)
 __global__ void __launch_bounds__(PVS_BLOCK)
 k_pvs_mark_at(const PvsCam* __restrict__ tab, const double* __restrict__ bfw12, const PvsPoint* __restrict__ pts, int n, int nblk, signed char* __restrict__ lvl,
-              mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt) {
+              mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt, const uint8_t* __restrict__ near) {
   __shared__ int cnt[MCP_LEVELS];
   Se3 bfw;
 #pragma unroll
   for (int k = 0; k < 9; ++k) bfw.R[k] = bfw12[k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) bfw.t[k] = bfw12[9 + k];
-  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt);
+  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt, near);
 }
 // k_pvs_mark_at behind a device-side word an earlier kernel of the stream left (mcp_track_frame_recover: k_reloc_pick).  *gate == 0: nobody
 // recovered, the reference runs no TrackMap -- every (row, camera) is marked outside and every count is zero, the empty-PVS case for all
 // later launches.  *gate != 0: k_pvs_mark_at's pass, the same body
 __global__ void __launch_bounds__(PVS_BLOCK)
 k_pvs_mark_gated(const int* __restrict__ gate, const PvsCam* __restrict__ tab, const double* __restrict__ bfw12, const PvsPoint* __restrict__ pts, int n, int nblk,
-                 signed char* __restrict__ lvl, mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt) {
+                 signed char* __restrict__ lvl, mcp_pvs_entry* __restrict__ ent, int* __restrict__ blk_cnt, const uint8_t* __restrict__ near) {
   __shared__ int cnt[MCP_LEVELS];
   if (*gate == 0) {      // (uniform over the grid)
     const int c = blockIdx.y, i = blockIdx.x*PVS_BLOCK + threadIdx.x;
@@ -91,7 +93,7 @@ k_pvs_mark_gated(const int* __restrict__ gate, const PvsCam* __restrict__ tab, c
   for (int k = 0; k < 9; ++k) bfw.R[k] = bfw12[k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) bfw.t[k] = bfw12[9 + k];
-  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt);
+  pvs_mark_body(tab, bfw, pts, n, nblk, lvl, ent, blk_cnt, cnt, near);
 }
 
 __global__ void __launch_bounds__(PVS_BLOCK)

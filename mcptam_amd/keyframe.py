@@ -63,6 +63,7 @@ IMG_SYMBOLS = [
     "mcp_meas_parcel_size", "mcp_meas_parcel_get", "mcp_meas_parcel_commit", "mcp_parcel_commit_host",
     "mcp_map_cull_outliers", "mcp_map_cull_sweep", "mcp_map_cull_rows_view", "mcp_map_cull_last_timing", "mcp_map_cull_outliers_host", "mcp_map_cull_sweep_host",
     "mcp_map_neighbours", "mcp_map_neighbours_last_timing", "mcp_map_neighbours_host", "mcp_map_mkf_cull", "mcp_map_mkf_cull_last_timing", "mcp_map_mkf_cull_host",
+    "mcp_map_collect_nearest", "mcp_map_collect_rows_view", "mcp_map_collect_last_timing", "mcp_map_collect_nearest_host", "mcp_track_collect_nearest", "mcp_track_collect_last",
     "mcp_stereo_map_points", "mcp_stereo_busy_host", "mcp_stereo_append_host", "mcp_map_points_get_rays", "mcp_map_points_get_source", "mcp_map_gp_get",
     "mcp_init_depth_map_points", "mcp_map_mark_optimized", "mcp_map_rescale", "mcp_map_transform", "mcp_init_depth_points_host", "mcp_map_mark_optimized_host",
     "mcp_map_transform_host", "mcp_map_life_last_timing",

@@ -27,6 +27,11 @@ n_closest_keyframes (src/MapMakerBase.cc:90-339) and the tracker's need_new_mult
 (src/MapMakerServerBase.cc:264-318, src/Map.cc:119-187); neighbours_host / cull_mkf_host are the host twins (no device), neighbours_ref /
 cull_mkf_ref the numpy restatements.
 
+The co-visible points of the nearest keyframe (mcp_map_collect_nearest): MapGraph.collect_nearest is Tracker::CollectNearestPoints with
+tracker_collect_all_points false (src/Tracker.cc:1797-1854) for every camera of a frame at once -- a byte per row whose bit c is camera c's;
+pvs.MapPointTable.collect_nearest switches the same walk on in front of the PVS launch of find_pvs and the one-call frames;
+collect_nearest_host is the host twin (no device), collect_nearest_ref the restatement over sets of keyframes and points.
+
 How the map begins and how it is rescaled or moved (mcp_init_depth_map_points, mcp_map_mark_optimized, mcp_map_rescale, mcp_map_transform):
 MapGraph.add_init_depth_points is MapMakerServerBase::AddInitDepthMapPoints of one MKF and level for every camera of the rig, mark_optimized the
 mbOptimized loop at the end of InitFromMultiKeyFrame, rescale / transform ApplyGlobalScaleToMap / ApplyGlobalTransformationToMap over the resident
@@ -40,6 +45,7 @@ from . import chain_bundle as _cb
 from . import synth
 from .keyframe import _chk
 from .pvs import lib as _pvs_lib
+from .pvs import COLLECT_STRUCT_SIZES, COLLECT_SYMBOLS, CollectParams, CollectReport, _bind_collect, collect_params
 
 MAX_MKFS = 4096
 MAX_CAMS = 8
@@ -819,6 +825,75 @@ def cull_mkf_ref(a, slot=-1, furthest_from=-1, mark_points=True, max_kfs=2, eras
 
 
 # ---- the numpy restatement, from the reference -----------------------------------------------------------------------------------------------
+# ---- the co-visible points of the nearest keyframe (mcp_map_collect_nearest; the structs and the binding live in pvs.py) ------------------
+def _collect_args(a, base_from_world, depth_mean, mean_diff_fraction, active, cam_from_base, n_rows):
+    C = int(a["ncam"])
+    prm = collect_params(depth_mean, mean_diff_fraction, active)
+    if len(np.asarray(depth_mean).reshape(-1)) != C:
+        raise ValueError("collect_nearest: one depth mean per camera of the rig")
+    cur = None if cam_from_base is None else _f64(cam_from_base).reshape(C, 12)
+    n_rows = int(a.get("n_rows", len(a["pt_flags"]))) if n_rows is None else int(n_rows)
+    return prm, _f64(base_from_world).reshape(12), cur, n_rows
+
+
+def collect_nearest_host(a, base_from_world, depth_mean, mean_diff_fraction=0.5, active=None, cam_from_base=None, n_rows=None, raw=False):
+    """mcp_map_collect_nearest_host over the flat arrays `a` (problem_arrays' keys): (the report as a dict, the near mask, one byte per row), or
+    with raw the CollectReport itself in place of the dict.  base_from_world (12,): the tracker's pose; depth_mean, active: per camera of the
+    rig; cam_from_base: the current keyframes', None for the rig's.  Needs no device.  A refusal raises RuntimeError."""
+    prm, b, cur, n_rows = _collect_args(a, base_from_world, depth_mean, mean_diff_fraction, active, cam_from_base, n_rows)
+    C, P, cfb, bfw, mf, act, dep = _mkf_columns(a)
+    M = len(a["ms_mkf"])
+    mm, mc, mr, al = _i32(a["ms_mkf"], (M,)), _i32(a["ms_cam"], (M,)), _i32(a["ms_row"], (M,)), _u8(a["ms_alive"], (M,))
+    rep, near = CollectReport(), np.zeros(n_rows, dtype=np.uint8)
+    _chk(_bind_collect(lib()).mcp_map_collect_nearest_host(b.ctypes.data, None if cur is None else cur.ctypes.data, ctypes.addressof(prm), C, cfb.ctypes.data, P, bfw.ctypes.data,
+                                                           mf.ctypes.data, act.ctypes.data, dep.ctypes.data, n_rows, M, mm.ctypes.data, mc.ctypes.data, mr.ctypes.data,
+                                                           al.ctypes.data, ctypes.addressof(rep), near.ctypes.data), "map_collect_nearest_host")
+    return (rep if raw else rep.as_dict()), near
+
+
+def collect_nearest_ref(a, base_from_world, depth_mean, mean_diff_fraction=0.5, active=None, cam_from_base=None, n_rows=None):
+    """Tracker::CollectNearestPoints with tracker_collect_all_points false (src/Tracker.cc:1785-1854) over the flat arrays, as the reference's
+    loops read: ClosestKeyFrame (src/MapMakerBase.cc:115-140) walks the keyframes of the map in list order -- here (slot, cam) -- and keeps the
+    first strict minimum; then the set of keyframes that measure one of its points, then the set of points those measure.  The documented
+    deviations: an empty set with status 1 where the reference asserts and with status 3 where KeyFrame::Distance stops the process.  Returns
+    what collect_nearest_host returns."""
+    prm, b, cur, n_rows = _collect_args(a, base_from_world, depth_mean, mean_diff_fraction, active, cam_from_base, n_rows)
+    C, P, cfb, bfw, mf, act, dep = _mkf_columns(a)
+    cur = cfb if cur is None else cur
+    # the map as the reference holds it: KeyFrame::mmpMeasurements and MapPoint::mMMData.spMeasurementKFs
+    kf_points, point_kfs = {}, {}
+    for al, m, c, r in zip(np.asarray(a["ms_alive"]), np.asarray(a["ms_mkf"]), np.asarray(a["ms_cam"]), np.asarray(a["ms_row"])):
+        if al and 0 <= r < n_rows and 0 <= m < MAX_MKFS and 0 <= c < MAX_CAMS:
+            kf_points.setdefault((int(m), int(c)), set()).add(int(r))
+            point_kfs.setdefault(int(r), set()).add((int(m), int(c)))
+    keyframes = [(s, c) for s in range(P) if mf[s] & MKF_PRESENT for c in range(C) if act[s, c]]
+    centre, mean = _kf_frames(cfb, bfw, np.where(act != 0, dep, 0.0))
+    own_centre, own_mean = _kf_frames(cur, b.reshape(1, 12), np.array(prm.depth_mean[:C]).reshape(1, C))
+    rep = {k: np.zeros(MAX_CAMS, dtype=np.int32) for k in ("status", "n_candidates", "n_seed_rows", "n_kfs", "n_rows")}
+    rep.update(valid=1, nearest_slot=np.full(MAX_CAMS, -1, dtype=np.int32), nearest_cam=np.full(MAX_CAMS, -1, dtype=np.int32), nearest_dist=np.zeros(MAX_CAMS))
+    near = np.zeros(n_rows, dtype=np.uint8)
+    for c in range(C):
+        if not prm.active[c]:
+            continue
+        closest, closest_dist, broken = None, 0.0, False
+        for kf in keyframes:
+            d = float(_kf_dist(own_centre[0, c], own_mean[0, c], centre[kf], mean[kf], prm.mean_diff_fraction))
+            broken = broken or not np.isfinite(d) or d > 1e10
+            if closest is None or d < closest_dist:
+                closest, closest_dist = kf, d
+        rep["n_candidates"][c] = len(keyframes)
+        rep["status"][c] = 3 if broken else (1 if closest is None else 0)
+        if rep["status"][c] != 0:
+            continue
+        rep["nearest_slot"][c], rep["nearest_cam"][c], rep["nearest_dist"][c] = closest[0], closest[1], closest_dist
+        seed = kf_points.get(closest, set())
+        kfs = set().union(*[point_kfs[r] for r in seed])
+        rows = set().union(*[kf_points[k] for k in kfs])
+        rep["n_seed_rows"][c], rep["n_kfs"][c], rep["n_rows"][c] = len(seed), len(kfs), len(rows)
+        near[sorted(rows)] |= np.uint8(1 << c)
+    return rep, near
+
+
 def mkf_distances(a, newest, mean_diff_fraction):
     """MultiKeyFrame::Distance(newest, k) for every slot k (KeyFrame.cc:903-927 over KeyFrame::Distance, :715-747): (P,) distances (DBL_MAX
     without a pair of active keyframes) and whether any pair's distance is one the reference stops the process on (:734-744)."""
@@ -1506,6 +1581,35 @@ class MapGraph:
         """Device time of the last neighbours() submission in ms; -1 before the first."""
         ms = ctypes.c_double(0.0)
         _chk(self._L.mcp_map_neighbours_last_timing(self._h, ctypes.addressof(ms)), "map_neighbours_last_timing")
+        return ms.value
+
+    # ---- the co-visible points of the nearest keyframe (mcp_map_collect_nearest) ----
+    def collect_nearest(self, base_from_world, depth_mean, mean_diff_fraction=0.5, active=None, cam_from_base=None, raw=False):
+        """mcp_map_collect_nearest at the tracker's pose base_from_world (12,): (the report as a dict, the near mask, one byte per table row
+        whose bit c says that the row is a co-visible point of the map keyframe nearest to current keyframe c), or with raw the CollectReport
+        itself in place of the dict.  depth_mean, active: per camera of the rig; cam_from_base: the current keyframes', None for the rig's."""
+        prm = collect_params(depth_mean, mean_diff_fraction, active)
+        if len(np.asarray(depth_mean).reshape(-1)) != self.ncam:
+            raise ValueError("collect_nearest: one depth mean per camera of the rig")
+        b = _f64(base_from_world).reshape(12)
+        cur = None if cam_from_base is None else _f64(cam_from_base).reshape(self.ncam, 12)
+        rep, near = CollectReport(), np.zeros(self.table.rows, dtype=np.uint8)
+        _chk(_bind_collect(self._L).mcp_map_collect_nearest(self._h, b.ctypes.data, None if cur is None else cur.ctypes.data, ctypes.addressof(prm), ctypes.addressof(rep),
+                                                            near.ctypes.data), "map_collect_nearest")
+        return (rep if raw else rep.as_dict()), near
+
+    def collect_rows(self):
+        """The near mask of the last collect_nearest (mcp_map_collect_rows_view), copied; empty after a frame's collection."""
+        cnt = ctypes.c_int(0)
+        ptr = _bind_collect(self._L).mcp_map_collect_rows_view(self._h, ctypes.byref(cnt))
+        if not cnt.value:
+            return np.zeros(0, dtype=np.uint8)
+        return np.frombuffer((ctypes.c_char * cnt.value).from_address(ptr), dtype=np.uint8).copy()
+
+    def collect_last_timing(self):
+        """Device time of the collection launches of the last collection on the graph in ms (a frame's included); -1 before the first."""
+        ms = ctypes.c_double(0.0)
+        _chk(_bind_collect(self._L).mcp_map_collect_last_timing(self._h, ctypes.addressof(ms)), "map_collect_last_timing")
         return ms.value
 
     def n_closest_multi_keyframes(self, n, src_slot=-1, ext=None, want_meas=False, mean_diff_fraction=0.5):

@@ -441,6 +441,25 @@ class MapPointTable:
         _chk(_bind_track_cov(self._L).mcp_track_pose_cov_last(self._h, ctypes.byref(out)), "track_pose_cov_last")
         return out
 
+    # ---- FindPVS over the co-visible points of the nearest keyframe (include/mcp_img.h mcp_track_collect_nearest) ----
+    def collect_nearest(self, graph, depth_mean, mean_diff_fraction=0.5):
+        """tracker_collect_all_points = false: while it is on, find_pvs and the four one-call frames judge a row for camera c only if it is a
+        co-visible point of the map keyframe nearest to the current keyframe c (map_graph.MapGraph.collect_nearest, at the pose the PVS launch
+        reads).  graph: the MapGraph of this table; depth_mean: mdSceneDepthMean per frame camera.  Host-only: call it before every frame with
+        fresh depth means.  A refusal raises RuntimeError and leaves the mode as it was."""
+        prm = collect_params(depth_mean, mean_diff_fraction)
+        _chk(_bind_collect(self._L).mcp_track_collect_nearest(self._h, graph._h, ctypes.byref(prm)), "track_collect_nearest")
+
+    def collect_nearest_off(self):
+        """tracker_collect_all_points = true (the default): every usable row."""
+        _chk(_bind_collect(self._L).mcp_track_collect_nearest(self._h, None, None), "track_collect_nearest")
+
+    def collect_last(self):
+        """The CollectReport of the last find_pvs / track call on this table as a dict; raises unless that call succeeded with the mode on."""
+        out = CollectReport()
+        _chk(_bind_collect(self._L).mcp_track_collect_last(self._h, ctypes.byref(out)), "track_collect_last")
+        return out.as_dict()
+
     def debug_fine_records(self):
         """(records (POSE_POINT_DTYPE), weights, mu_last) of the last track call's fine iterations, copied from the device; for tests."""
         from .keyframe import POSE_POINT_DTYPE
@@ -1162,3 +1181,54 @@ def pose_covariance_restate(pts, weights, cams_from_base, refined, mu_last, pose
         return dict(info=info, cov=np.zeros((6, 6)), eig=np.zeros(6), rank=0, n_used=n_used, pose_before=pose_before, valid=-1)
     cov, eig, rank = pinv_truncated(info)
     return dict(info=info, cov=cov, eig=eig, rank=rank, n_used=n_used, pose_before=pose_before, valid=1)
+
+
+# ---- the co-visible points of the nearest keyframe (include/mcp_img.h mcp_map_collect_nearest, mcp_track_collect_nearest) ------------------
+COLLECT_SYMBOLS = ["mcp_map_collect_nearest", "mcp_map_collect_rows_view", "mcp_map_collect_last_timing", "mcp_map_collect_nearest_host", "mcp_track_collect_nearest",
+                   "mcp_track_collect_last"]
+
+
+class CollectParams(ctypes.Structure):
+    _fields_ = [("mean_diff_fraction", ctypes.c_double), ("depth_mean", ctypes.c_double * MAX_FRAME_CAMS), ("active", ctypes.c_uint8 * MAX_FRAME_CAMS)]
+
+
+class CollectReport(ctypes.Structure):
+    _fields_ = [("valid", ctypes.c_int), ("status", ctypes.c_int * MAX_FRAME_CAMS), ("nearest_slot", ctypes.c_int * MAX_FRAME_CAMS), ("nearest_cam", ctypes.c_int * MAX_FRAME_CAMS),
+                ("pad_", ctypes.c_int), ("nearest_dist", ctypes.c_double * MAX_FRAME_CAMS)] + \
+               [(k, ctypes.c_int * MAX_FRAME_CAMS) for k in ("n_candidates", "n_seed_rows", "n_kfs", "n_rows")]
+
+    def as_dict(self):
+        """valid as an int, every other field as an array of MAX_FRAME_CAMS."""
+        out = {k: np.array(getattr(self, k)) for k, _ in self._fields_ if k not in ("valid", "pad_")}
+        out["valid"] = int(self.valid)
+        return out
+
+
+COLLECT_STRUCT_SIZES = {"mcp_collect_params": ctypes.sizeof(CollectParams), "mcp_collect_report": ctypes.sizeof(CollectReport)}
+
+
+def collect_params(depth_mean, mean_diff_fraction=0.5, active=None):
+    """mcp_collect_params: one depth mean per camera looked at; active (the stand-alone call): which of them, None for all."""
+    d = np.asarray(depth_mean, dtype=np.float64).reshape(-1)
+    use = np.ones(len(d), dtype=bool) if active is None else np.asarray(active).reshape(-1) != 0
+    if len(d) > MAX_FRAME_CAMS or len(use) != len(d):
+        raise ValueError("collect_params: one depth mean and one active byte per camera, at most %d" % MAX_FRAME_CAMS)
+    p = CollectParams(float(mean_diff_fraction))
+    for c in range(len(d)):
+        p.depth_mean[c], p.active[c] = d[c], int(use[c])
+    return p
+
+
+def _bind_collect(L):
+    if getattr(L, "_collect_bound", False):
+        return L
+    vp, ip = ctypes.c_void_p, ctypes.c_int
+    L.mcp_map_collect_nearest.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mcp_map_collect_rows_view.restype = vp
+    L.mcp_map_collect_rows_view.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.mcp_map_collect_last_timing.argtypes = [vp, vp]
+    L.mcp_map_collect_nearest_host.argtypes = [vp, vp, vp, ip, vp, ip, vp, vp, vp, vp, ip, ip, vp, vp, vp, vp, vp, vp]
+    L.mcp_track_collect_nearest.argtypes = [vp, vp, vp]
+    L.mcp_track_collect_last.argtypes = [vp, vp]
+    L._collect_bound = True
+    return L

@@ -348,6 +348,8 @@ Vector<6> Tracker::TrackStageOnDevice(std::vector<TrackerDataPtrVector>& vIterat
 //     std::vector<MapPoint*> mvMapTableRows;   // table row -> MapPoint
 //     std::vector<mcp_pvs_entry> mvPvsOut;     // scratch of the call
 //     void UploadMapTable();                   // option (a) below
+//     std::vector<uint8_t> mvNearRows;         // !sbCollectAllPoints: the collected set of this frame, one byte per table row (bit c: camera c)
+//     mcp_collect_params CollectParams();      // the current keyframes' depth means for the collection
 // and in class PatchFinder (include/mcptam/PatchFinder.h) a setter for the two members CalcSearchLevelAndWarpMatrix leaves behind:
 //     void SetSearchLevelAndWarp(int nLevel, const TooN::Matrix<2>& m2WarpInverse) { mnSearchLevel = nLevel; mm2WarpInverse = m2WarpInverse; }
 //
@@ -395,7 +397,24 @@ void Tracker::UploadMapTable()
   }
 }
 
-// The reference body collects the nearest points (sbCollectAllPoints = true: all of them, :1785-1795), projects each, tests the mask,
+// tracker_collect_all_points = false (Tracker::sbCollectAllPoints, CollectNearestPoints :1797-1854): the co-visible points of the map keyframe
+// nearest to each current keyframe, collected on the device from the map graph's store (include/mcp_img.h, mcp_map_collect_nearest /
+// mcp_track_collect_nearest).  The depth means are the current keyframes' mdSceneDepthMean: CopySceneDepths gave them to a fresh MKF, and the
+// previous frame's record refreshed them (TrackMapOnDevice, below).  The camera order is mvCurrCamNames', which is the graph's rig order.
+mcp_collect_params Tracker::CollectParams()
+{
+  mcp_collect_params params;
+  memset(&params, 0, sizeof params);
+  params.mean_diff_fraction = KeyFrame::sdDistanceMeanDiffFraction;
+  for(unsigned c = 0; c < mvCurrCamNames.size(); ++c)
+  {
+    params.depth_mean[c] = mpCurrentMKF->mmpKeyFrames[mvCurrCamNames[c]]->mdSceneDepthMean;
+    params.active[c] = 1;
+  }
+  return params;
+}
+
+// The reference body collects the nearest points (sbCollectAllPoints: all of them, :1785-1795, or the walk above), projects each, tests the mask,
 // takes the derivatives and asks the PatchFinder for the search level.  Here one device call does that for every row of the table; the
 // host only walks the PVS.  A TrackerData is created for PVS points only: one the reference would create for a point outside the PVS holds
 // a PatchFinder that has seen nothing and is only ever touched again by the next FindPVS, so creating it then changes nothing.
@@ -408,7 +427,28 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
 
   boost::mutex::scoped_lock lock(mMap.mMutex);
   if(cameraName == mvCurrCamNames[0])
+  {
     UploadMapTable();                 // option (a): once per frame, before the first camera
+    // This drop-in asks for one camera per call, so it cannot use the frame mode (whose frames have the rig's cameras): the set of every
+    // camera is collected once per frame by the stand-alone call, and the walk over the PVS below skips the rows outside it
+    // (std::vector<uint8_t> mvNearRows in class Tracker).
+    mvNearRows.clear();
+    if(!Tracker::sbCollectAllPoints)
+    {
+      double adPose[12];
+      ToArray12(mpCurrentMKF->mse3BaseFromWorld, adPose);
+      mcp_collect_params params = CollectParams();
+      mcp_collect_report report;
+      mvNearRows.resize(std::max<size_t>(mvMapTableRows.size(), 1));
+      if(mcp_map_collect_nearest(mMap.mpMapGraph, adPose, NULL, &params, &report, &mvNearRows[0]) != 0)
+      {
+        ROS_FATAL_STREAM("Tracker::FindPVS: "<<mcp_last_error());
+        ros::shutdown();
+        return;
+      }
+    }
+  }
+  const int nCamIndex = (int)(std::find(mvCurrCamNames.begin(), mvCurrCamNames.end(), cameraName) - mvCurrCamNames.begin());
 
   mcp_camera cam = mcptam_hip::CameraExport::Make(camera);
   double adBaseFromWorld[12], adCamFromBase[12];
@@ -434,6 +474,8 @@ void Tracker::FindPVS(std::string cameraName, TDVLevels& vPVSLevels)
     {
       const mcp_pvs_entry& e = mvPvsOut[k];
       ROS_ASSERT(e.point >= 0 && e.point < (int)mvMapTableRows.size());     // the table has exactly the rows UploadMapTable wrote
+      if(!mvNearRows.empty() && !((mvNearRows[e.point] >> nCamIndex) & 1))
+        continue;                       // !sbCollectAllPoints: not a co-visible point of this camera's nearest keyframe
       MapPoint& point = *mvMapTableRows[e.point];
       if(!point.mmpTData.count(cameraName))
         point.mmpTData[cameraName] = new TrackerData(&point, mmSizes[cameraName]);
@@ -575,6 +617,15 @@ bool Tracker::TrackMapOnDevice(const mcp_track_motion_params* pMotion, const uin
     qprm.reloc_blur = 2.5;                                // SmallBlurryImage's default blur, KeyFrame::MakeSBI
     qprm.reloc_iterations = 6;                            // src/Relocaliser.cc:76
     qprm.max_score = Relocaliser::sdRecoveryMaxScore;
+    // tracker_collect_all_points: false walks the store in front of the PVS launch, at the pose that launch reads (host-only, every frame:
+    // the depth means are this frame's)
+    mcp_collect_params cprm = CollectParams();
+    if(mcp_track_collect_nearest(mpMapTable, Tracker::sbCollectAllPoints ? NULL : mMap.mpMapGraph, &cprm) != 0)
+    {
+      ROS_FATAL_STREAM("Tracker::TrackMapOnDevice: "<<mcp_last_error());
+      ros::shutdown();
+      return false;
+    }
     mcp_track_pose_cov_enable(mpMapTable, 1);             // mm6PoseCovariance rides in the same submission (two launches behind the fine iterations)
     const int rc = pRecover ? mcp_track_frame_recover(mpMapTable, nCams, &vKF[0], apImages, anStrides, 0, NULL, &vCams[0], &vCamsSBI[0], adBfW, &vCfB[0], &prm, &res, &rprm,
                                                       &mTrackRecord, pMotion, pMotionOut, (int)pRecover->vKF.size(), pRecover->vKF.empty() ? NULL : &pRecover->vKF[0],
